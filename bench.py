@@ -18,7 +18,12 @@ every rank solves its shard in ONE batched launch, and ONE RCCL all-gather of fi
 n_unscheduled, first node's InstanceTypeOptions]` closes the step.  Fixed total work: "strong" scaling; `value` = decisions of
 all 512 what-ifs / max-over-ranks time; its N=1 reference is the `whatif_batch` object of the N=1 line.
 
-Extra objects on the JSON line:
+A plain N=1 run (`bench.py --gpus 1 --steps K --warmup W`) does only what the headline needs: set up, warm up, time the K steps, print the
+line.  Everything else on the N=1 line (the objects below, `alt_kernel`, `egress`, `grid`, `ingress`, the what-if leg, the config #5 sample, the
+CPU baseline) is measured only with `--full`.  `--dump-outputs DIR` writes what the last timed step computed -- the result arrays a caller of
+that path reads back (N>1: the gathered records) -- as DIR/<name>.npy, in float64 without loss.
+
+Extra objects on the JSON line (--full):
   roofline     dominant kernel ks_pack: algorithmic bytes of the REFERENCE algorithm for this workload (SURVEY 8d formula with
                the documented R=4, K=8 record sizes; attempts / scanned-type counts from an untimed KS_FLAG_STATS launch) divided
                by the mean launch duration measured with HIP events on the solve stream; `traffic` only from a PMC file recorded
@@ -78,6 +83,56 @@ def kernel_source_sha16():
     return h.hexdigest()[:16]
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def exact_float64(a):
+    """An integer array as float64 without losing a bit: 64-bit words (type masks, records) split into their two 32-bit halves along a new last axis."""
+    import numpy as np
+    a = np.ascontiguousarray(a)
+    if a.dtype.itemsize == 8:
+        return a.view(np.uint32).reshape(a.shape + (2,)).astype(np.float64)
+    return a.astype(np.float64)
+
+
+def result_outputs(arrays):
+    """What a caller of `solve_from_pods` receives through ksh_result_arrays_get, as float64 arrays (node_requests stay quantities where float64 holds them exactly).
+    The list of unscheduled pods is given per pod -- its place in that list, -1 for a pod that was scheduled --, so its shape does not depend on the result."""
+    import numpy as np
+    unscheduled = arrays["unscheduled"]
+    out = {"counts": np.array([arrays["n_existing"], arrays["n_new"], len(unscheduled)], dtype=np.float64)}
+    order = np.full(len(arrays["pod_node"]), -1.0)
+    order[unscheduled] = np.arange(len(unscheduled), dtype=np.float64)
+    out["pod_unscheduled_order"] = order
+    for name in ("pod_node", "pod_stage", "pod_reason", "node_pods_off", "node_pods", "node_tmpl", "node_types", "node_requests",
+                 "node_requests_present", "node_present", "node_complement", "node_mask"):
+        a = arrays[name]
+        if name == "node_requests" and (a.size == 0 or int(np.abs(a).max()) < 2 ** 53):
+            out[name] = a.astype(np.float64)
+        else:
+            out[name] = exact_float64(a)
+    return out
+
+
+def dump_outputs(d, outputs):
+    """--dump-outputs DIR: every non-empty array as DIR/<name>.npy (an empty one -- the node arrays of a Solve that opened no node -- says nothing `counts`
+    does not).  Over DUMP_LIMIT_BYTES in all, each array keeps the same fixed, seeded sample of its rows (the row numbers beside it as <name>.rows.npy),
+    so two builds given the same arguments write comparable files."""
+    import zlib
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    outputs = {name: a for name, a in outputs.items() if a.size}
+    frac = 1.0
+    if sum(a.nbytes for a in outputs.values()) > DUMP_LIMIT_BYTES:
+        frac = DUMP_LIMIT_BYTES * 0.95 / sum(a.nbytes + 8 * len(a) for a in outputs.values())     # (the row numbers count too)
+    for name, a in outputs.items():
+        if frac < 1.0 and len(a) > 1:
+            rows = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(len(a), max(1, int(len(a) * frac)), replace=False))
+            a = a[rows]
+            np.save(os.path.join(d, f"{name}.rows.npy"), rows.astype(np.float64))
+        np.save(os.path.join(d, f"{name}.npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -94,10 +149,17 @@ def main():
     ap.add_argument("--config5-sample", type=int, default=250_000, metavar="PODS", help="also solve BASELINE configs[4]'s generator at PODS pods (250000: the size with an oracle "
                     "fingerprint) and put the object `config5` on the line; 0 skips it (about a minute of generation and a 3 s Solve)")
     ap.add_argument("--whatifs-only", action="store_true", help="diagnostic: only the N=1 what-if leg (prints its object alone, not the contract line)")
+    ap.add_argument("--full", action="store_true", help="N=1: also measure everything beside the headline figure (resident, roofline, alt_kernel, egress, grid, ingress, "
+                    "the what-if leg, the config #5 sample, the CPU baseline); a plain run only times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the result arrays of the last timed step as DIR/<name>.npy (float64, at most 64 MB in all)")
     args = ap.parse_args()
 
     if args.gpus < 1:
         sys.exit("bench.py: --gpus must be >= 1")
+    if args.steps < 1:
+        sys.exit("bench.py: --steps must be >= 1")
+    if args.dump_outputs and (args.config5 or args.whatifs_only):
+        sys.exit("bench.py: --dump-outputs writes the contract line's outputs; --config5 / --whatifs-only have none")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return spawn_ranks(args)      # `python bench.py --gpus N` launches its own N ranks (one per GPU); under torchrun the ranks arrive here with WORLD_SIZE set
     rank = int(os.environ.get("RANK", "0"))
@@ -143,9 +205,14 @@ def main():
     parsed = S.ParsedProblem(problem)
     prep_s = time.time() - t0
 
-    def step():
+    held = []
+
+    def step(hold=False):
         fp, ms = S.solve_from_pods(parsed, local_rank)
-        fp.close()
+        if hold:
+            held.append(fp)         # the last timed step's result: read after the timer, its handle released there with the teardown still counted
+        else:
+            fp.close()
         return ms
 
     for _ in range(args.warmup):
@@ -153,18 +220,50 @@ def main():
     torch.cuda.synchronize()
     rows, lat_ms = [], []
     t_start = time.perf_counter()
-    for _ in range(args.steps):
+    for i in range(args.steps):
         t1 = time.perf_counter()
-        rows.append(step())
+        rows.append(step(hold=i == args.steps - 1))
         lat_ms.append((time.perf_counter() - t1) * 1e3)
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t_start
+    last = held.pop()
+    dims = last.dims
+    arrays = last.result_arrays()       # what a caller of solve_from_pods reads back (ksh_result_arrays_get)
+    t1 = time.perf_counter()
+    last.close()
+    close_s = time.perf_counter() - t1
+    elapsed += close_s
+    lat_ms[-1] += close_s * 1e3
     value = args.pods * args.steps / elapsed
     phase = {k: statistics.mean(r[k] for r in rows) for k in S.TIMING_KEYS}
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, result_outputs(arrays))
 
+    out = {
+        "metric": "pod-placement decisions/sec (Solve())", "value": value, "unit": "decisions/s", "n_gpus": 1,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
+        "scaling": "n/a", "scaling_note": "N=1: one Solve on one GPU (a single Solve is replicas-only, SURVEY 8e): nothing scales; the N>1 line (the what-if fan-out) says strong / weak", "vs_baseline": None, "dtype": "int64", "data": "synthetic",
+        "config": {"workload": f"BASELINE configs[2]: {dims['P']} pods, {dims['T']} instance types, zonal+hostname topology spread and "
+                               f"hostname pod anti-affinity (workloads.config3 seed 44)", "pods": dims["P"], "instance_types": dims["T"],
+                   "pod_classes": dims["C"], "topology_groups": dims["G"], "new_nodes": int(arrays["n_new"]),
+                   "unschedulable": len(arrays["unscheduled"]), "parallelism": "1 Solve on 1 GPU",
+                   "timed_window": "Solve() from the pod list in host memory: per-pod requests/requirements/classes, relaxation chains, topology groups, NewQueue sort, "
+                                   "flattening of the batch, upload, static tables + grid, pack kernel, read-back (scheduler.solve_from_pods).  The environment's own "
+                                   "flattening (instance types, templates, state nodes) is cached with the caller's objects per universe signature and adopted by the timed "
+                                   "steps (the warm-up step builds it; KSH_NO_ENV_CACHE=1 re-does it per Solve: +11 ms); the reference's benchmark leaves NewScheduler's "
+                                   "whole assembly out of its timer (scheduling_benchmark_test.go:130)"},
+        "p50_solve_latency_ms": statistics.median(lat_ms),
+        "phases_ms_mean": phase, "host_threads": os.cpu_count(), "prep_seconds_untimed": prep_s,
+    }
+    if args.full:
+        out.update(full_legs(args, problem, parsed, dims, phase, local_rank, torch, S, W))
+    print(json.dumps(out))
+
+
+def full_legs(args, problem, parsed, dims, phase, local_rank, torch, S, W):
+    """--full, N=1: the objects of the line beside the headline figure, measured after the timed steps (none of them is `value`)."""
     # ---- inputs resident in HBM: the pack loop alone (round 1's measurement), and the statistics launch for the roofline ----
     fp, _ = S.solve_from_pods(parsed, local_rank)
-    dims = fp.dims
     res = fp.result()
     resident = []
     for _ in range(3):
@@ -223,20 +322,6 @@ def main():
     except Exception:
         pass
     out = {
-        "metric": "pod-placement decisions/sec (Solve())", "value": value, "unit": "decisions/s", "n_gpus": 1,
-        "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
-        "scaling": "n/a", "scaling_note": "N=1: one Solve on one GPU (a single Solve is replicas-only, SURVEY 8e): nothing scales; the N>1 line (the what-if fan-out) says strong / weak", "vs_baseline": None, "dtype": "int64", "data": "synthetic",
-        "config": {"workload": f"BASELINE configs[2]: {dims['P']} pods, {dims['T']} instance types, zonal+hostname topology spread and "
-                               f"hostname pod anti-affinity (workloads.config3 seed 44)", "pods": dims["P"], "instance_types": dims["T"],
-                   "pod_classes": dims["C"], "topology_groups": dims["G"], "new_nodes": len(res.new_nodes),
-                   "unschedulable": len(res.unscheduled), "parallelism": "1 Solve on 1 GPU",
-                   "timed_window": "Solve() from the pod list in host memory: per-pod requests/requirements/classes, relaxation chains, topology groups, NewQueue sort, "
-                                   "flattening of the batch, upload, static tables + grid, pack kernel, read-back (scheduler.solve_from_pods).  The environment's own "
-                                   "flattening (instance types, templates, state nodes) is cached with the caller's objects per universe signature and adopted by the timed "
-                                   "steps (the warm-up step builds it; KSH_NO_ENV_CACHE=1 re-does it per Solve: +11 ms); the reference's benchmark leaves NewScheduler's "
-                                   "whole assembly out of its timer (scheduling_benchmark_test.go:130)"},
-        "p50_solve_latency_ms": statistics.median(lat_ms),
-        "phases_ms_mean": phase, "host_threads": os.cpu_count(), "prep_seconds_untimed": prep_s,
         "resident": {"what": "pack loop only, flattened problem already resident in HBM (ks_solve_dev incl. read-back) -- round 1's window",
                      "decisions_per_s": dims["P"] / (statistics.median(r[0] for r in resident) / 1e3),
                      "wall_ms": statistics.median(r[0] for r in resident), "kernel_ms": statistics.median(r[1] for r in resident)},
@@ -303,7 +388,7 @@ def main():
                                              "thread like the Go path); the oracle's cost grows super-linearly with pods",
                                    "full_size_recorded": {"pods": 100000, "oracle_seconds": full, "decisions_per_s": (100000 / full) if full else None,
                                                           "source": "tests/golden/config_hashes.json (tests/golden/make_config_hashes.py, build container)"}}
-    print(json.dumps(out))
+    return out
 
 
 def config5_leg(args, device, torch, S, W):
@@ -603,6 +688,8 @@ def whatif_fanout(args, rank, world, local_rank, torch, dist, S, W):
     total_pods = int(tp.item())
     table = table[table[:, 0] >= 0]
     table = table[torch.argsort(table[:, 0])]
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"records": exact_float64(table.cpu().numpy())})      # the gathered records of the last timed step, in what-if order
     # kernel time of the batched launch (HIP events on the solve stream inside ks_solve_batch_dev), mean over a few launches
     kms = []
     for _ in range(3):

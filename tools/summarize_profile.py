@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Condense a tools/profile_bench.sh output directory (gpurun_out/prof_<tag>) into the files kept under profiles/:
-  <tag>_bench.json                 the bench.py JSON line (plain run, default arguments)
+  <tag>_bench.json                 the bench.py JSON line (--full, default arguments)
   <tag>_bench_kernel_stats.csv     rocprofv3 --kernel-trace --stats of the same command: per-kernel calls / total / average ns
   <tag>_bench_pmc.json             per-kernel counter sums of the separate --pmc passes, and per ks_pack launch: HBM bytes (FETCH_SIZE x2 +
                                    WRITE_SIZE, MI355X_MICROARCH.md gfx950 note), instructions issued, wave-cycle split; keyed by the sha of the
@@ -32,7 +32,7 @@ def sums(kind):
 
 
 out = {"kernel_source_sha16": bench.kernel_source_sha16(), "pods": line["config"]["pods"], "instance_types": line["config"]["instance_types"],
-       "command": "rocprofv3 --kernel-trace --pmc <counters> -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline --whatifs 0   (one pass per counter group)",
+       "command": "rocprofv3 --kernel-trace --pmc <counters> -- python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --whatifs 0   (one pass per counter group)",
        "per_kernel": {}}
 allk = {}
 for kind in ("fetch", "write", "insts", "cycles"):
