@@ -28,7 +28,8 @@
  *             because its universe is the whole catalogue.
  *   hostname key       implicit: new node n owns a placeholder hostname no pod can name (node.go:46);
  *             existing node e owns hostname e.  Pod classes carry {mode, list of existing-node ids}.
- *   resources R <= 8 int64 milli-units; index 0 = cpu, 1 = memory, 2 = pods.
+ *   resources R <= 16 int64 milli-units; index 0 = cpu, 1 = memory, 2 = pods.  A problem with more than 8 runs on
+ *             the wide kernel variants; up to 8 take the same kernels as always.
  *   taints    <= 64 distinct (key,value,effect) triples -> u64 masks; tolerations pre-evaluated.
  *   offerings zone x capacity-type pairs (<= 64) -> u64 per instance type.
  *   pods      deduplicated into classes (one per distinct pod spec x relaxation stage); a pod is a
@@ -46,7 +47,7 @@ extern "C" {
 #endif
 
 #define KS_MAX_KEYS 32
-#define KS_MAX_RES 8
+#define KS_MAX_RES 16
 #define KS_MAX_VALUES 64
 #define KS_MAX_ITSTATES 65535
 #define KS_NO_BOUND_GT INT32_MIN /* "no greaterThan" */
@@ -248,6 +249,9 @@ int ks_problem_device(const ks_dev_problem* d);                /* device an uplo
  * *decline_code: 0 it took the Solve, else why it declined (the codes are listed in karpenter_core_amd/csrc/ks_pack_rr.inc; e.g. 1 static limits, 4 more nodes than it
  * holds, 8 its watchdog).  Diagnostics only: the result is the same either way (scheduler.go:96-219). */
 int ks_problem_rr_status(const ks_dev_problem* d, int* started, int* decline_code);
+/* Which ks_pack variant took the last solve of `d`, by its compile-time resource bound: 4 (LEAN), 8 (general), 16 (wide: a problem with R > 8, or a
+ * what-if batch holding one); 0 if ks_pack_rr took it.  Diagnostics only, like ks_problem_rr_status. */
+int ks_problem_pack_width(const ks_dev_problem* d, int* rm);
 int ks_problem_upload(const ks_problem* p, int device, ks_dev_problem** out);
 void ks_problem_free(ks_dev_problem* d);
 /* Consolidation what-ifs over ONE cluster snapshot (deprovisioning/helpers.go:42-99) differ in their pods and in which state nodes stay, not in

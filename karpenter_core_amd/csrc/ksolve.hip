@@ -42,6 +42,9 @@
 #define KS_FLAG_NOFOLD 0x10000u   /* internal (KS_NO_FOLD=1 at upload): the rounds do not fold node-opening pods in (A/B and parity of both ways) */
 #define KS_MAX_TOPO 24       // topology groups evaluated per pod class
 #define KS_MAX_TOUCH 12      // distinct narrow keys a class may touch (own requirements + topology + recorded keys)
+// Resources per plan / brief record and per lane array of the narrow kernels.  A problem with R in (8, KS_MAX_RES] runs on the wide
+// variants (RM = 16), which read resources 8.. of a class from DevProb::cls_requests: the records keep their size and layout.
+#define KS_RES_NARROW 8
 
 #ifdef KS_SIM      /* tests/sim/hip_sim.h: the kernels of this file run on the host, a fibre per lane (test infrastructure; hipcc never defines it) */
 struct u32x4 { unsigned int x, y, z, w; };
@@ -286,7 +289,9 @@ __host__ __device__ inline u32 ks_grid_chunks(size_t MC, u32 TW, u32 wave_target
 //   hasOffering = some available offering whose zone / capacity-type the node allows (node.go:151)
 // Wave (w, chunk): lane owns type t = 64*w + lane for the whole kernel; (m,c) records are wave-uniform.
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void ks_grid_types(const DevProb* probs, u32 wave_target, u32 row_lo, u32 row_hi) {      // rows [row_lo, row_hi) of the grid (SURVEY 8e row 2: the rows split over GPUs; everything: 0, ~0)
+// RM: resources held per lane (KS_RES_NARROW; 16 in ks_grid_types_wide, which launch_static picks when a problem of the batch has R > 8).
+template <int RM>
+__device__ __forceinline__ void grid_types(const DevProb* probs, u32 wave_target, u32 row_lo, u32 row_hi) {
   const DevProb& P = probs[blockIdx.y];
   const size_t MC0 = (size_t)P.M * P.C; if (MC0 == 0) return;
   const u32 chunks = ks_grid_chunks(MC0, P.TW, wave_target);
@@ -296,12 +301,12 @@ __global__ __launch_bounds__(256) void ks_grid_types(const DevProb* probs, u32 w
   if (chunk >= chunks) return;
   const u32 t = w * 64 + lane; const bool valid = t < P.T;
   // lane-private type record (registers)
-  u32 tpres = 0, tcomp = 0; u64 tmask[KS_MAX_KEYS]; i64 talloc[KS_MAX_RES]; u64 toffer = 0;
+  u32 tpres = 0, tcomp = 0; u64 tmask[KS_MAX_KEYS]; i64 talloc[RM]; u64 toffer = 0;
   if (valid) { tpres = P.it_present[t]; tcomp = P.it_complement[t]; toffer = P.it_offer[t]; }
 #pragma unroll
   for (int k = 0; k < KS_MAX_KEYS; ++k) tmask[k] = (valid && (u32)k < P.K) ? P.it_mask[(size_t)k * P.T + t] : 0;
 #pragma unroll
-  for (int r = 0; r < KS_MAX_RES; ++r) talloc[r] = (valid && (u32)r < P.R) ? P.it_alloc[(size_t)r * P.T + t] : 0;
+  for (int r = 0; r < RM; ++r) talloc[r] = (valid && (u32)r < P.R) ? P.it_alloc[(size_t)r * P.T + t] : 0;
   const size_t MCall = (size_t)P.M * P.C, MC = MCall < (size_t)row_hi ? MCall : (size_t)row_hi;
   for (size_t mc = (size_t)row_lo + chunk; mc < MC; mc += chunks) {
     const u32 m = mc / P.C, c = mc % P.C;
@@ -324,7 +329,7 @@ __global__ __launch_bounds__(256) void ks_grid_types(const DevProb* probs, u32 w
     // fits
     const u32 rp = P.tmpl_daemon_present[m] | P.cls_requests_present[c];
 #pragma unroll
-    for (int r = 0; r < KS_MAX_RES; ++r) {
+    for (int r = 0; r < RM; ++r) {
       if (!((rp >> r) & 1u)) continue;
       const i64 need = P.tmpl_daemon[(size_t)m * P.R + r] + P.cls_requests[(size_t)c * P.R + r];
       if (need > talloc[r]) ok = false;
@@ -341,6 +346,10 @@ __global__ __launch_bounds__(256) void ks_grid_types(const DevProb* probs, u32 w
     if (lane == 0) P.grid[mc * P.TW + w] = word;
   }
 }
+__global__ __launch_bounds__(256) void ks_grid_types(const DevProb* probs, u32 wave_target, u32 row_lo, u32 row_hi) {      // rows [row_lo, row_hi) of the grid (SURVEY 8e row 2: the rows split over GPUs; everything: 0, ~0)
+  grid_types<KS_RES_NARROW>(probs, wave_target, row_lo, row_hi);
+}
+__global__ __launch_bounds__(256) void ks_grid_types_wide(const DevProb* probs, u32 wave_target, u32 row_lo, u32 row_hi) { grid_types<16>(probs, wave_target, row_lo, row_hi); }
 
 // ------------------------------------------------------------------------------------------------
 // pack kernel: ONE workgroup per Solve().
@@ -386,7 +395,7 @@ struct alignas(16) ClsPlan {
   u64 tol; u32 port_off, port_cnt;
   u32 vol_off, vol_cnt, mono, dyn;     // mono: an existing node that refused this class once refuses it for the rest of the Solve (see the watermark in ks_pack); dyn: see ClsBrief::dyn
   u32 ntouch, ntopo, nhost, nrec;
-  i64 req[KS_MAX_RES];
+  i64 req[KS_RES_NARROW];
   PlanTouch touch[KS_MAX_TOUCH];
   PlanTopo topo[KS_MAX_TOPO];        // narrow-key items, grouped by touch entry
   PlanTopo host[KS_MAX_HOST];        // hostname-key items
@@ -410,7 +419,7 @@ struct alignas(16) ClsBrief {
                 // bit 0: the evaluation's only topology item is a spread over a group of DevProb::dyn_groups and the pod has no requirement of its own on that
                 // key: 1 | g << 8 | selfSelecting << 16.  On a node whose requirement on the key is a single value the item then depends on that value
                 // and the group's counts alone, so the resolver can apply it against counts it keeps for the round.
-  i64 req[KS_MAX_RES];
+  i64 req[KS_RES_NARROW];
   u64 zmask;    // hostname-keyed groups whose item accepts a node only while the node's own counter is 0 (anti-affinity; spread with maxSkew - self == 0)
   u64 rsure;    // hostname-keyed groups this class records into for certain (group present from the start, no node filter): subset of rmask
   i32 dyn_maxskew; u32 dyn_pd;      // dyn: maxSkew and the pod's domains (PlanTopo::PD) over the key's <= 8 values
@@ -430,7 +439,7 @@ __global__ __launch_bounds__(64) void ks_build_plans(const DevProb* probs) {
   pl.hn_mode = P.cls_hn_mode[c]; pl.hn_cnt = P.cls_hn_off[c + 1] - P.cls_hn_off[c]; pl.hn_off = pl.hn_cnt ? P.cls_hn_off[c] : 0;      // (an empty list has no position: classes that differ only there evaluate alike)
   pl.reqmask = P.cls_requests_present[c]; pl.tol = P.cls_tolerated[c]; pl.port_cnt = P.cls_port_off[c + 1] - P.cls_port_off[c]; pl.port_off = pl.port_cnt ? P.cls_port_off[c] : 0;
   pl.vol_cnt = P.cls_vol_off[c + 1] - P.cls_vol_off[c]; pl.vol_off = pl.vol_cnt ? P.cls_vol_off[c] : 0;
-  for (u32 r = 0; r < P.R; ++r) pl.req[r] = P.cls_requests[(size_t)c * P.R + r];
+  for (u32 r = 0; r < P.R && r < KS_RES_NARROW; ++r) pl.req[r] = P.cls_requests[(size_t)c * P.R + r];      // (resources 8.. of a wide problem: cls_requests, read by the wide variants)
   // own requirement keys, ascending
   for (u32 k = 0; k < P.K; ++k) if ((pl.present >> k) & 1u) {
     if (pl.ntouch >= KS_MAX_TOUCH) { pl.overflow = 1; break; }
@@ -522,7 +531,7 @@ __global__ __launch_bounds__(64) void ks_build_plans(const DevProb* probs) {
   ClsBrief b; b.zmask = zmask; b.rsure = rsure; b.tmask = pl.tmask; b.tfull = tfull; b.rmask = pl.rmask; bool late_host = false;       // a record into a hostname-keyed group a relaxation creates later: such hostnames may be unregistered
   for (u32 j = 0; j < pl.nrec; ++j) if (pl.rec[j].key == KS_KEY_HOSTNAME && !pl.rec[j].owned_inverse && P.grp_active[pl.rec[j].g] == 0) late_host = true;
   b.ev = 0; b.flags = (!pl.overflow && pl.port_cnt == 0 && pl.vol_cnt == 0 && !late_host) ? 1u : 0u; b.reqmask = pl.reqmask; b.dyn = pl.dyn; b.dyn_maxskew = (pl.dyn & 1u) ? pl.topo[0].maxskew : 0; b.dyn_pd = (pl.dyn & 1u) ? (u32)pl.topo[0].PD : 0u;
-  for (u32 r = 0; r < KS_MAX_RES; ++r) b.req[r] = pl.req[r];
+  for (u32 r = 0; r < KS_RES_NARROW; ++r) b.req[r] = pl.req[r];
   briefs[c] = b;
 }
 
@@ -554,6 +563,22 @@ __global__ __launch_bounds__(64) void ks_link_ev(const DevProb* probs) {
     const u32 prev = atomicCAS(&tab[slot], 0u, c + 1);
     if (prev == 0) { ev = c + 1; break; }                        // first of its kind: it represents the evaluation class
     if (ks_plan_eval_equal(plans[prev - 1], me)) { ev = prev; break; }
+  }
+  briefs[c].ev = ev ? ev : c + 1;
+}
+// ks_link_ev for a batch with R > 8 (launch_static): the plan records stop at resource 8, so equal classes must also request the same of the rest.
+__global__ __launch_bounds__(64) void ks_link_ev_wide(const DevProb* probs) {
+  const DevProb& P = probs[blockIdx.y]; const ClsPlan* const plans = (const ClsPlan*)P.plans; ClsBrief* const briefs = (ClsBrief*)P.briefs; u32* const tab = P.ev_tab; const u32 tab_size = P.ev_tab_size, C = P.C;
+  const u32 c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= C) return;
+  const ClsPlan& me = plans[c];
+  u32 slot = (u32)ks_plan_eval_hash(me) & (tab_size - 1), ev = 0;
+  for (u32 probes = 0; probes < tab_size; ++probes, slot = (slot + 1) & (tab_size - 1)) {
+    const u32 prev = atomicCAS(&tab[slot], 0u, c + 1);
+    if (prev == 0) { ev = c + 1; break; }
+    bool same = ks_plan_eval_equal(plans[prev - 1], me);
+    for (u32 r = KS_RES_NARROW; r < P.R && same; ++r) same = P.cls_requests[(size_t)(prev - 1) * P.R + r] == P.cls_requests[(size_t)c * P.R + r];
+    if (same) { ev = prev; break; }
   }
   briefs[c].ev = ev ? ev : c + 1;
 }
@@ -613,7 +638,7 @@ struct ReqOut {    // per-key requirement of the winning node after the pod is a
 };
 // The winner's evaluation, broadcast to the whole wave with v_readlane: wave-uniform registers, so the
 // filter and the commit branch on scalars instead of waiting on LDS round trips.
-// RM: compile-time bound on the resource count (4 in the LEAN kernel variant, KS_MAX_RES otherwise) -- every loop over
+// RM: compile-time bound on the resource count (4 in the LEAN kernel variant, KS_RES_NARROW otherwise) -- every loop over
 // resources is fully unrolled, so the bound is paid in instructions and registers whether or not R reaches it.
 template <int RM> struct PubT {
   u32 slot, present, complement, changed, narrowed, valid, rm, count; i32 it_state, it_before; bool need;
@@ -623,10 +648,11 @@ struct TopoDyn { u64 reg, pos; i32 minc; i32 pad; };
 struct alignas(16) WaveShared {      // one per wave of the workgroup
   ClsPlan cls; ReqOut rq;
   TopoDyn dyn[KS_MAX_TOPO]; i32 host_anypos[KS_MAX_HOST]; i32 host_zero[KS_MAX_HOST]; i32 pad_hz[2];
-  i64 low_new[KS_MAX_RES]; u32 low_idx[KS_MAX_RES];
+  i64 low_new[KS_RES_NARROW]; u32 low_idx[KS_RES_NARROW];
   u64 la_mask[KS_MAX_TOUCH][64];                                                            // per-lane requirement slots of eval_node
 };
 struct WaveBounds { i32 la_gt[KS_MAX_TOUCH][64]; i32 la_lt[KS_MAX_TOUCH][64]; };            // ... their Gt/Lt halves (BOUNDS variants only)
+struct alignas(16) WideLow { i64 low_new[16 - KS_RES_NARROW]; u32 low_idx[16 - KS_RES_NARROW]; };   // wide variants (RM = 16): WaveShared::low_new / low_idx of resources 8..15
 struct LeaderShared {                // owned by wave 0, which carries the Solve's sequential state
   u32 hard[8];          // 256-bit hashed set of classes whose last pod found nothing in the first candidate window (heuristic only)
   u8 hslot_of[64];      // group g (< 64) -> row of the hostname tables (grp_hslot), 0xFF if its key is not the hostname
@@ -1119,7 +1145,7 @@ __device__ __forceinline__ void ge_row_indices(const Tabs& tb, const PubT<RM>& p
 // Lane w owns word w; there is no per-type loop: resources.Fits is one precomputed row per requested resource.
 template <int RM>
 __device__ __forceinline__ bool filter_types(const DevProb& P, const Tabs& tb, const PubT<RM>& pb, WaveShared& sh, const Rec& r, const GA u64* alive_in, GA u64* alive_out, u32 reqmask_new,
-                             u32 changed_keys, bool check_offer, bool check_it, int lane, u64& tprobe, u64 (&word)[2]) {   // alive_out == nullptr (TW <= 128 only): the result stays in `word` (lane l: words l and 64+l)
+                             u32 changed_keys, bool check_offer, bool check_it, int lane, u64& tprobe, u64 (&word)[2], WideLow* wl = nullptr) {   // alive_out == nullptr (TW <= 128 only): the result stays in `word` (lane l: words l and 64+l)
   const GA u64* rows[RM]; u32 ridx[RM];
   ge_row_indices(tb, pb, reqmask_new, lane, ridx);
   bool none = false;
@@ -1131,7 +1157,11 @@ __device__ __forceinline__ bool filter_types(const DevProb& P, const Tabs& tb, c
   word[0] = 0; word[1] = 0;
   if (none) { if (alive_out) for (u32 w = lane; w < tb.TW; w += 64) alive_out[w] = 0; LSYNC(); return false; }   // nothing has that much of some resource
 #pragma unroll
-  for (int i = 0; i < RM; ++i) if (lane == 0) { if ((reqmask_new >> i) & 1u) { sh.low_new[i] = tb.ge_vals[(size_t)i * tb.ge_stride + ridx[i]]; sh.low_idx[i] = ridx[i]; } else sh.low_idx[i] = 0xFFFFu; }
+  for (int i = 0; i < (RM > KS_RES_NARROW ? KS_RES_NARROW : RM); ++i) if (lane == 0) { if ((reqmask_new >> i) & 1u) { sh.low_new[i] = tb.ge_vals[(size_t)i * tb.ge_stride + ridx[i]]; sh.low_idx[i] = ridx[i]; } else sh.low_idx[i] = 0xFFFFu; }
+  if constexpr (RM > KS_RES_NARROW) {
+#pragma unroll
+    for (int i = KS_RES_NARROW; i < RM; ++i) if (lane == 0) { if ((reqmask_new >> i) & 1u) { wl->low_new[i - KS_RES_NARROW] = tb.ge_vals[(size_t)i * tb.ge_stride + ridx[i]]; wl->low_idx[i - KS_RES_NARROW] = ridx[i]; } else wl->low_idx[i - KS_RES_NARROW] = 0xFFFFu; }
+  }
   bool any = false;
   for (u32 wbase = 0; wbase < tb.TW; wbase += 64) {
     const u32 w = wbase + lane; u64 a = 0;
@@ -1188,16 +1218,26 @@ __device__ __forceinline__ void write_record(const Tabs& tb, const Rec& r, const
 }
 
 // FAST variant: the small hot tables of one Solve as true LDS arrays
-struct alignas(16) FastTabs {
-  u64 g_reg[KS_FAST_G]; u64 g_pos[KS_FAST_G]; i32 g_hpos[KS_FAST_G]; i32 g_hzero[KS_FAST_G]; u32 key_nvalues[KS_MAX_KEYS]; u32 ge_cnt[KS_MAX_RES];
+template <int RW> struct alignas(16) FastTabsT {      // RW: resources (KS_RES_NARROW, 16 in the wide variants)
+  u64 g_reg[KS_FAST_G]; u64 g_pos[KS_FAST_G]; i32 g_hpos[KS_FAST_G]; i32 g_hzero[KS_FAST_G]; u32 key_nvalues[KS_MAX_KEYS]; u32 ge_cnt[RW];
   u16 its_inter[KS_FAST_S * KS_FAST_S]; u8 its_fail[KS_FAST_S * KS_FAST_S]; u8 g_active[KS_FAST_G];
   i32 gcnt[KS_FAST_G * 64]; i32 value_int[KS_MAX_KEYS * 64];
 };
+using FastTabs = FastTabsT<KS_RES_NARROW>;
 struct alignas(16) NoTabs { u32 pad[4]; };
 template <bool FAST, bool BOUNDS, int NW, int RM> struct alignas(16) PackLds {
-  alignas(16) unsigned char rc_raw[NW > 1 ? sizeof(RoundCtlT<RM>) : 16]; LeaderShared ls; typename std::conditional<FAST, FastTabs, NoTabs>::type ft; DevProb P; DevState S;
+  alignas(16) unsigned char rc_raw[NW > 1 ? sizeof(RoundCtlT<RM>) : 16]; LeaderShared ls; typename std::conditional<FAST, FastTabsT<(RM > KS_RES_NARROW ? 16 : KS_RES_NARROW)>, NoTabs>::type ft; DevProb P; DevState S;
   alignas(16) unsigned char wbs_raw[BOUNDS ? sizeof(WaveBounds) * NW : 16]; WaveShared shw[NW];      // (no Gt/Lt anywhere in the problem: the bounds slots are never touched)
 };
+// The wide variants' LDS: the narrow layout, then what holds resources 8..15 (the narrow kernels' LDS object is unchanged).
+template <bool FAST, bool BOUNDS, int NW, int RM> struct alignas(16) PackLdsWide : PackLds<FAST, BOUNDS, NW, RM> { WideLow wl[NW]; };
+template <bool FAST, bool BOUNDS, int NW, int RM> using PackLdsOf = typename std::conditional<(RM > KS_RES_NARROW), PackLdsWide<FAST, BOUNDS, NW, RM>, PackLds<FAST, BOUNDS, NW, RM>>::type;
+// Request r of class cls: plan and brief records hold resources [0, 8); the wide variants read the rest from DevProb::cls_requests.
+__device__ __forceinline__ i64 cls_req_wide(const DevProb& P, const Tabs& tb, u32 cls, int r) { return (u32)r < tb.R ? ((const GA i64*)P.cls_requests)[(size_t)cls * tb.R + r] : 0; }
+// A wave-uniform class's requests 8.. (nothing in the narrow variants, whose loops over the plan record cover every resource they hold).
+template <int RM> __device__ __forceinline__ void wide_req(const DevProb& P, const Tabs& tb, u32 cls, i64 (&req)[RM]) {
+  if constexpr (RM > KS_RES_NARROW) { cls = UF(cls); for (int i = KS_RES_NARROW; i < RM; ++i) req[i] = (i64)UF64(cls_req_wide(P, tb, cls, i)); }
+}
 #ifdef KS_SIM
 static unsigned char ks_dyn_lds[160 * 1024] __attribute__((aligned(16)));
 #else
@@ -1208,21 +1248,22 @@ extern __shared__ __attribute__((aligned(16))) unsigned char ks_dyn_lds[];
 // LEAN: no class has host ports, a hostname selector or an instance-type requirement, no provisioner has limits,
 // R <= 4 and no statistics are requested -- the code for all of that (and half of every unrolled resource loop) is
 // compiled out.  One wave issues ~1 instruction per 5 cycles, so instructions, not bytes, are what a Solve costs.
-template <bool FAST, bool BOUNDS, bool LEAN, int NW>
+// RM: compile-time bound on the resource count -- 4 (LEAN), KS_RES_NARROW, or 16 (the wide variants, single-wave and not LEAN: problems with R > 8).
+template <bool FAST, bool BOUNDS, bool LEAN, int NW, int RM = (LEAN ? 4 : KS_RES_NARROW)>
 __global__ __launch_bounds__(64 * NW) void ks_pack(const DevProb* probs, const DevState* states, u32 lds_bytes) {
-  constexpr int RM = LEAN ? 4 : KS_MAX_RES;
   using ClsR = ClsRT<RM>; using Ev = EvT<RM>; using Pub = PubT<RM>;
   static_assert(NW >= 1 && NW <= KS_MAX_WAVES, "wave count");
   // descriptors are copied to LDS: loads from them can then be CSE'd across global stores (no aliasing)
   // ONE static LDS object, hot lane-indexed arrays first: a ds instruction carries a 16-bit immediate offset, so everything in the first
   // 64 KiB is addressed as lane*stride + immediate; an array beyond that needs its base in a register of its own, which the compiler hoists
   // out of the Solve loop and -- the 8-wave kernel sits at its 256-VGPR budget -- spills to scratch (a memory round trip per reload).
-  __shared__ PackLds<FAST, BOUNDS, NW, RM> L;
+  __shared__ PackLdsOf<FAST, BOUNDS, NW, RM> L;
   DevProb& P_lds = L.P; DevState& S_lds = L.S;
   WaveShared (&shw)[NW] = L.shw; WaveBounds* const wbs = (WaveBounds*)L.wbs_raw; LeaderShared& ls = L.ls;
   RoundCtlT<RM>& rc = *(RoundCtlT<RM>*)L.rc_raw;      // (single-wave kernels have no rounds: nothing of rc is touched)
   const int lane = threadIdx.x & 63; const u32 wv = NW > 1 ? UF(threadIdx.x >> 6) : 0u;
   WaveShared& sh = shw[wv]; WaveBounds& wb = wbs[BOUNDS ? wv : 0];
+  WideLow* wl = nullptr; if constexpr (RM > KS_RES_NARROW) wl = &L.wl[wv];
 #ifdef KS_CHECK   /* debug builds: LDS starts out as garbage from whatever ran before -- make that garbage deterministic and hostile */
   { u32* z = (u32*)&L; for (u32 i = threadIdx.x; i < sizeof(L) / 4; i += 64 * NW) z[i] = 0xA5A5A5A5u; u32* y = (u32*)ks_dyn_lds; for (u32 i = threadIdx.x; i < lds_bytes / 4; i += 64 * NW) y[i] = 0xA5A5A5A5u; }
   __syncthreads();
@@ -1267,11 +1308,11 @@ __global__ __launch_bounds__(64 * NW) void ks_pack(const DevProb* probs, const D
   // ---------------- small hot tables: true LDS arrays in the FAST variant, global memory otherwise ----------------
   u32 lds_used = 0;
   if constexpr (FAST) {
-    FastTabs& ft = L.ft;
+    auto& ft = L.ft;
     u32 (&sm_key_nvalues)[KS_MAX_KEYS] = ft.key_nvalues; i32 (&sm_value_int)[KS_MAX_KEYS * 64] = ft.value_int;
     u8 (&sm_its_fail)[KS_FAST_S * KS_FAST_S] = ft.its_fail; u16 (&sm_its_inter)[KS_FAST_S * KS_FAST_S] = ft.its_inter;
     i32 (&sm_gcnt)[KS_FAST_G * 64] = ft.gcnt; u64 (&sm_g_reg)[KS_FAST_G] = ft.g_reg; u64 (&sm_g_pos)[KS_FAST_G] = ft.g_pos; u8 (&sm_g_active)[KS_FAST_G] = ft.g_active;
-    i32 (&sm_g_hpos)[KS_FAST_G] = ft.g_hpos; i32 (&sm_g_hzero)[KS_FAST_G] = ft.g_hzero; u32 (&sm_ge_cnt)[KS_MAX_RES] = ft.ge_cnt;
+    i32 (&sm_g_hpos)[KS_FAST_G] = ft.g_hpos; i32 (&sm_g_hzero)[KS_FAST_G] = ft.g_hzero; u32 (&sm_ge_cnt)[RM > KS_RES_NARROW ? 16 : KS_RES_NARROW] = ft.ge_cnt;
     i64* ge = (i64*)ks_dyn_lds;
     const u32 gs = UF(P.ge_max);            // the Allocatable ladders are stored with the longest one's stride
     if (wv == 0) {
@@ -1360,7 +1401,8 @@ __global__ __launch_bounds__(64 * NW) void ks_pack(const DevProb* probs, const D
           const u32x4 v0 = bp[0], v1 = bp[1]; const u32 rqm = *(const GA u32*)((const GA u8*)bp + 32);
           const GA i64* rqp = (const GA i64*)((const GA u8*)bp + 40);
 #pragma unroll
-          for (int i = 0; i < RM; ++i) b_req[i] = rqp[i];
+          for (int i = 0; i < (RM > KS_RES_NARROW ? KS_RES_NARROW : RM); ++i) b_req[i] = rqp[i];
+          if constexpr (RM > KS_RES_NARROW) for (int i = KS_RES_NARROW; i < RM; ++i) b_req[i] = cls_req_wide(P, tb, cls, i);      // (lane-varying class)
           u32 dynw_l = 0;
           { const u32 dynw = *(const GA u32*)((const GA u8*)bp + 36); const u32 dms = *(const GA u32*)((const GA u8*)bp + 120), dpd = *(const GA u32*)((const GA u8*)bp + 124);
             rc.dynq[wpar][lane] = (dms & 0xFFFFFFu) | (dpd << 24); dynw_l = dynw; }
@@ -1439,7 +1481,8 @@ __global__ __launch_bounds__(64 * NW) void ks_pack(const DevProb* probs, const D
     if (UF(c.overflow)) { err = (u32)(-KS_ERR_UNSUPPORTED); break; }
     ClsR cr; cr.tol = UF64(c.tol); cr.reqmask = UF(c.reqmask); cr.ntouch = UF(c.ntouch); cr.nhost = UF(c.nhost); cr.hn_mode = UF(c.hn_mode); cr.port_cnt = UF(c.port_cnt); cr.vol_cnt = UF(c.vol_cnt); cr.it_state = (i32)UF(c.it_state); cr.tkeys = UF64(c.tkeys); cr.eq = UF(c.eq);
 #pragma unroll
-    for (int i = 0; i < RM; ++i) cr.req[i] = (i64)UF64(c.req[i]);
+    for (int i = 0; i < (RM > KS_RES_NARROW ? KS_RES_NARROW : RM); ++i) cr.req[i] = (i64)UF64(c.req[i]);
+    wide_req(P, tb, c.c, cr.req);
     if constexpr (LEAN) { cr.port_cnt = 0; cr.vol_cnt = 0; cr.hn_mode = 0; cr.it_state = 0; }
     bool placed = false;
     PROBE(13);
@@ -1584,12 +1627,12 @@ __global__ __launch_bounds__(64 * NW) void ks_pack(const DevProb* probs, const D
           if (pb.need) {     // otherwise the filter would pick the same rows as last time: InstanceTypeOptions unchanged
             const bool inreg = !fresh && tb.TW <= 128;  // the surviving-type words stay in registers: no scratch round trip
             u64 aw[2];
-            const bool ok = filter_types(P, tb, pb, sh, r, fresh ? scratch : alive, fresh ? alive : (inreg ? (GA u64*)nullptr : scratch), rm, keys, zc, itc, lane, tprobe, aw);
+            const bool ok = filter_types(P, tb, pb, sh, r, fresh ? scratch : alive, fresh ? alive : (inreg ? (GA u64*)nullptr : scratch), rm, keys, zc, itc, lane, tprobe, aw, wl);
             PROBE(16);
             if (!ok) { CTR(KS_STAT_FULLFAILS, 1); if (!fresh) recompute_cap<RM>(P, tb, alive, r, lane); else if (m_t < 8) why |= (u32)KS_WHY_NO_INSTANCE_TYPE << (4 * m_t); m &= m - 1; continue; }
             if (inreg) { if ((u32)lane < tb.TW) alive[lane] = aw[0]; if ((u32)lane + 64 < tb.TW) alive[lane + 64] = aw[1]; }
             else if (!fresh) for (u32 w = lane; w < tb.TW; w += 64) alive[w] = scratch[w];
-            if ((u32)lane < tb.R && ((rm >> lane) & 1u)) r.low()[lane] = sh.low_new[lane];
+            if ((u32)lane < tb.R && ((rm >> lane) & 1u)) { if constexpr (RM > KS_RES_NARROW) r.low()[lane] = lane < KS_RES_NARROW ? sh.low_new[lane] : wl->low_new[lane - KS_RES_NARROW]; else r.low()[lane] = sh.low_new[lane]; }
             if constexpr (NW > 1) if (lane < 2 && 4 * lane < RM) { u64 li = 0; for (int i = 0; i < 4; ++i) li |= (u64)((u32)(4 * lane + i) < tb.R ? (sh.low_idx[4 * lane + i] & 0xFFFFu) : 0xFFFFu) << (16 * i); ((GA u64*)S.lowi)[2 * (size_t)sw + lane] = li; }
           }
         }
@@ -1770,7 +1813,8 @@ __global__ __launch_bounds__(64 * NW) void ks_pack(const DevProb* probs, const D
               const ClsPlan& c = sh.cls;
               cr.tol = UF64(c.tol); cr.reqmask = UF(c.reqmask); cr.ntouch = UF(c.ntouch); cr.nhost = UF(c.nhost); cr.hn_mode = UF(c.hn_mode); cr.port_cnt = UF(c.port_cnt); cr.vol_cnt = UF(c.vol_cnt); cr.it_state = (i32)UF(c.it_state); cr.tkeys = UF64(c.tkeys); cr.eq = UF(c.eq);
 #pragma unroll
-              for (int i = 0; i < RM; ++i) cr.req[i] = (i64)UF64(c.req[i]);
+              for (int i = 0; i < (RM > KS_RES_NARROW ? KS_RES_NARROW : RM); ++i) cr.req[i] = (i64)UF64(c.req[i]);
+    wide_req(P, tb, c.c, cr.req);
               if constexpr (LEAN) { cr.port_cnt = 0; cr.vol_cnt = 0; cr.hn_mode = 0; cr.it_state = 0; }
               staged = true;
             }
@@ -1826,7 +1870,8 @@ __global__ __launch_bounds__(64 * NW) void ks_pack(const DevProb* probs, const D
         const ClsPlan& c = sh.cls;
         cr.tol = UF64(c.tol); cr.reqmask = UF(c.reqmask); cr.ntouch = UF(c.ntouch); cr.nhost = UF(c.nhost); cr.hn_mode = UF(c.hn_mode); cr.port_cnt = UF(c.port_cnt); cr.vol_cnt = UF(c.vol_cnt); cr.it_state = (i32)UF(c.it_state); cr.tkeys = UF64(c.tkeys); cr.eq = UF(c.eq);
 #pragma unroll
-        for (int i = 0; i < RM; ++i) cr.req[i] = (i64)UF64(c.req[i]);
+        for (int i = 0; i < (RM > KS_RES_NARROW ? KS_RES_NARROW : RM); ++i) cr.req[i] = (i64)UF64(c.req[i]);
+    wide_req(P, tb, c.c, cr.req);
         if constexpr (LEAN) { cr.port_cnt = 0; cr.vol_cnt = 0; cr.hn_mode = 0; cr.it_state = 0; }
         slot = 0xFFFFFFFFu;
         if ((u32)lane < nwin) slot = (u32)lane < tb.E ? (u32)lane : tb.E + (ord_lds_r ? ord_l[lane - tb.E] : ord_g[lane - tb.E]);
@@ -2345,7 +2390,8 @@ __global__ __launch_bounds__(64 * NW) void ks_pack(const DevProb* probs, const D
           const ClsPlan& c = sh.cls;
           ClsR fcr; fcr.tol = UF64(c.tol); fcr.reqmask = UF(c.reqmask); fcr.ntouch = UF(c.ntouch); fcr.nhost = UF(c.nhost); fcr.hn_mode = 0; fcr.port_cnt = 0; fcr.vol_cnt = 0; fcr.it_state = 0; fcr.tkeys = UF64(c.tkeys); fcr.eq = UF(c.eq);
 #pragma unroll
-          for (int i = 0; i < RM; ++i) fcr.req[i] = (i64)UF64(c.req[i]);
+          for (int i = 0; i < (RM > KS_RES_NARROW ? KS_RES_NARROW : RM); ++i) fcr.req[i] = (i64)UF64(c.req[i]);
+          wide_req(P, tb, c.c, fcr.req);
           const u32 fnn = UF(nnew);
           if (!UF(c.overflow) && fnn < nMAX) {
             // the first template that survives the pre-checks (scheduler.go:193-213; LEAN: no provisioner has limits)
@@ -2380,7 +2426,7 @@ __global__ __launch_bounds__(64 * NW) void ks_pack(const DevProb* probs, const D
                 const u32 keys = f_pb.narrowed;
                 const bool zc = (tb.key_zone >= 0 && ((keys >> tb.key_zone) & 1u)) || (tb.key_ct >= 0 && ((keys >> tb.key_ct) & 1u));
                 u64 aw[2];
-                if (filter_types(P, tb, f_pb, sh, fr, scratch, alive, f_pb.rm, keys, zc, false, lane, tprobe, aw)) {
+                if (filter_types(P, tb, f_pb, sh, fr, scratch, alive, f_pb.rm, keys, zc, false, lane, tprobe, aw, wl)) {
                   if ((u32)lane < tb.R && ((f_pb.rm >> lane) & 1u)) fr.low()[lane] = sh.low_new[lane];
                   if (lane < 2 && 4 * lane < RM) { u64 li2 = 0; for (int i = 0; i < 4; ++i) li2 |= (u64)((u32)(4 * lane + i) < tb.R ? (sh.low_idx[4 * lane + i] & 0xFFFFu) : 0xFFFFu) << (16 * i); ((GA u64*)S.lowi)[2 * (size_t)fs + lane] = li2; }
                   fold_ok = true; f_mt = m_t;
@@ -2746,6 +2792,7 @@ struct ks_dev_problem {
   bool lean_ok = false;          // none of the rarely used features is present -> the LEAN kernel variant (see ks_pack)
   u32 pp_cap = 0;
   bool view = false;             // a what-if derived from a resident snapshot (ks_whatifs_open): memory and stream belong to its ks_whatif_batch
+  int pack_rm = 0;                 // the last solve: resource bound of the ks_pack variant that ran (4, 8, 16), 0 if ks_pack_rr took it
   int rr_started = 0, rr_code = 0; // the last solve: ks_pack_rr was launched | why it declined (0: it took the Solve; the codes are in ks_pack_rr.inc)
   bool no_multi = false;         // ... over a snapshot with topology groups: the class briefs (round eligibility, certain records) were built for the snapshot's group activity, not this what-if's -- single-wave kernel only
 };
@@ -2787,12 +2834,13 @@ extern "C" int ks_device_count(void) {
 
 extern "C" int ks_current_device(void) { int d = 0; if (hipGetDevice(&d) != hipSuccess) return 0; return d; }
 extern "C" int ks_problem_device(const ks_dev_problem* d) { return d ? d->device : -1; }
+extern "C" int ks_problem_pack_width(const ks_dev_problem* d, int* rm) { if (!d || !rm) return fail(KS_ERR_INVALID, "null argument"); *rm = d->pack_rm; return KS_OK; }
 extern "C" int ks_problem_rr_status(const ks_dev_problem* d, int* started, int* decline_code) { if (!d) return fail(KS_ERR_INVALID, "null problem"); if (started) *started = d->rr_started; if (decline_code) *decline_code = d->rr_code; return KS_OK; }
 
 static int validate(const ks_problem* p) {
   if (!p) return fail(KS_ERR_INVALID, "null problem");
   if (p->K > KS_MAX_KEYS) return fail(KS_ERR_UNSUPPORTED, "more than 32 narrow label keys");
-  if (p->R > KS_MAX_RES || p->R < 3) return fail(KS_ERR_INVALID, "R must be in [3,8]");
+  if (p->R > KS_MAX_RES || p->R < 3) return fail(KS_ERR_INVALID, "R must be in [3,16]");
   if (p->S == 0 || p->S > KS_MAX_ITSTATES || p->SC == 0 || p->SC > KS_MAX_ITSTATES) return fail(KS_ERR_INVALID, "S and SC must be in [1,65535]");
   if (p->M == 0) return fail(KS_ERR_INVALID, "no provisioners found");   // provisioner.go:278-280
   if (p->T == 0) return fail(KS_ERR_INVALID, "no instance types");
@@ -3180,16 +3228,17 @@ extern "C" int ks_whatifs_pod_ids(ks_whatif_batch* b, uint32_t i, uint32_t* out)
 
 // Build the derived tables + the feasibility grid (idempotent).  Returns the grid kernels' time.
 // Launch the static-table kernels for the problems behind `probs` (device descriptor array, n of them) on one stream.
-struct StaticDims { u32 rows = 0, C = 0, RT = 0, TW = 1; size_t MC = 0; };
+struct StaticDims { u32 rows = 0, C = 0, RT = 0, TW = 1, R = 0; size_t MC = 0; };
 static void static_dims_of(const DevProb& h, StaticDims& a) {
   if (!h.derived_shared) { a.rows = std::max(a.rows, h.K * 64 + 2 * h.K + 64); a.RT = std::max(a.RT, h.R * h.T); }
-  a.C = std::max(a.C, h.C); a.MC = std::max(a.MC, (size_t)h.M * h.C); a.TW = std::max(a.TW, h.TW);
+  a.C = std::max(a.C, h.C); a.MC = std::max(a.MC, (size_t)h.M * h.C); a.TW = std::max(a.TW, h.TW); a.R = std::max(a.R, h.R);
 }
 static void launch_static(const DevProb* probs, u32 n, const StaticDims& a, u32 wave_target, hipStream_t st, hipEvent_t before_grid, u32 row_lo = 0, u32 row_hi = 0xFFFFFFFFu) {
   if (a.rows) hipLaunchKernelGGL(ks_build_type_tables, dim3((a.rows * 64 + 255) / 256, n), dim3(256), 0, st, probs);
   if (a.C) {
     hipLaunchKernelGGL(ks_build_plans, dim3((a.C + 63) / 64, n), dim3(64), 0, st, probs);
-    hipLaunchKernelGGL(ks_link_ev, dim3((a.C + 63) / 64, n), dim3(64), 0, st, probs);      // (ev_tab comes zero-filled from the upload; a repeated build finds its own entries again)
+    if (a.R > KS_RES_NARROW) { hipLaunchKernelGGL(ks_link_ev_wide, dim3((a.C + 63) / 64, n), dim3(64), 0, st, probs); }
+    else { hipLaunchKernelGGL(ks_link_ev, dim3((a.C + 63) / 64, n), dim3(64), 0, st, probs); }      // (ev_tab comes zero-filled from the upload; a repeated build finds its own entries again)
     hipLaunchKernelGGL(ks_link_plans, dim3((a.C + 63) / 64, n), dim3(64), 0, st, probs);
     hipLaunchKernelGGL(ks_build_rr, dim3((a.C + 63) / 64, n), dim3(64), 0, st, probs);
     hipLaunchKernelGGL(ks_link_rr, dim3((a.C + 63) / 64, n), dim3(64), 0, st, probs);      // (rr_tab comes zero-filled from the upload, like ev_tab)
@@ -3200,7 +3249,8 @@ static void launch_static(const DevProb* probs, u32 n, const StaticDims& a, u32 
   if (a.MC) {
     hipLaunchKernelGGL(ks_grid_mc, dim3((u32)((a.MC + 255) / 256), n), dim3(256), 0, st, probs);
     const size_t waves = (size_t)a.TW * ks_grid_chunks(a.MC, a.TW, wave_target);      // (an upper bound over the batch: a problem's surplus waves return at once)
-    hipLaunchKernelGGL(ks_grid_types, dim3((u32)((waves * 64 + 255) / 256), n), dim3(256), 0, st, probs, wave_target, row_lo, row_hi);
+    if (a.R > KS_RES_NARROW) { hipLaunchKernelGGL(ks_grid_types_wide, dim3((u32)((waves * 64 + 255) / 256), n), dim3(256), 0, st, probs, wave_target, row_lo, row_hi); }
+    else { hipLaunchKernelGGL(ks_grid_types, dim3((u32)((waves * 64 + 255) / 256), n), dim3(256), 0, st, probs, wave_target, row_lo, row_hi); }
   }
 }
 // Build the derived tables + the feasibility grid (idempotent).  Returns the grid kernels' time.
@@ -3385,7 +3435,8 @@ extern "C" int ks_solve_batch_dev(ks_dev_problem* const* ds, uint32_t n, ks_resu
   // The register-resident kernel (ks_pack_rr.inc) takes a single LEAN Solve without Gt/Lt bounds; it declines what it does not cover -- before
   // or during the run, without having touched the inputs -- and ks_pack below takes over.
   bool rr_done = false;
-  for (u32 i = 0; i < n; ++i) { ds[i]->rr_started = 0; ds[i]->rr_code = 0; }
+  for (u32 i = 0; i < n; ++i) { ds[i]->rr_started = 0; ds[i]->rr_code = 0; ds[i]->pack_rm = 0; }
+  bool wide = false; for (u32 i = 0; i < n; ++i) wide = wide || ds[i]->h.R > KS_RES_NARROW;      // (R > 4: never LEAN, so never ks_pack_rr)
   const bool asked_one_wave = getenv("KS_ONE_WAVE") != nullptr || (any_flags & KS_FLAG_ONE_WAVE);      // KS_ONE_WAVE asks for ks_pack's single-wave variant
   const bool asked_no_rr = getenv("KS_NO_RR") != nullptr || (any_flags & KS_FLAG_NO_RR);                 // KS_NO_RR=1: ks_pack only (A/B, and the parity of both kernels)
 #ifdef KS_SIM
@@ -3437,12 +3488,14 @@ extern "C" int ks_solve_batch_dev(ks_dev_problem* const* ds, uint32_t n, ks_resu
   typedef void (*pack_fn)(const DevProb*, const DevState*, u32);
   static const pack_fn variants[8] = {ks_pack<false, false, false, 1>, ks_pack<false, true, false, 1>, ks_pack<true, false, false, 1>, ks_pack<true, true, false, 1>,
                                       ks_pack<false, false, true, 1>, ks_pack<false, true, true, 1>, ks_pack<true, false, true, 1>, ks_pack<true, true, true, 1>};
+  static const pack_fn variants_wide[4] = {ks_pack<false, false, false, 1, 16>, ks_pack<false, true, false, 1, 16>, ks_pack<true, false, false, 1, 16>, ks_pack<true, true, false, 1, 16>};
   {   // the large dynamic-LDS opt-in is a per-device function attribute: set it once per device, race-free (two Solves may run concurrently)
     static std::mutex attr_mu; static std::vector<char> attr_done;
     std::lock_guard<std::mutex> g(attr_mu);
     if ((size_t)device >= attr_done.size()) attr_done.resize(device + 1, 0);
     if (!attr_done[device]) {
       for (int i = 0; i < 8; ++i) HIPCHK(hipFuncSetAttribute((const void*)variants[i], hipFuncAttributeMaxDynamicSharedMemorySize, 104 * 1024));
+      for (int i = 0; i < 4; ++i) HIPCHK(hipFuncSetAttribute((const void*)variants_wide[i], hipFuncAttributeMaxDynamicSharedMemorySize, 104 * 1024));
       HIPCHK(hipFuncSetAttribute((const void*)ks_pack<true, false, true, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 44 * 1024));
       HIPCHK(hipFuncSetAttribute((const void*)ks_pack<true, false, false, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 44 * 1024));
       HIPCHK(hipFuncSetAttribute((const void*)ks_pack<true, true, false, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 44 * 1024));
@@ -3451,7 +3504,7 @@ extern "C" int ks_solve_batch_dev(ks_dev_problem* const* ds, uint32_t n, ks_resu
   }
   // A single Solve whose problem takes the LEAN, FAST, no-bounds kernel gets 8 waves: waves 1..7 join wave 0 for the
   // speculation rounds (see ks_pack).  T <= 8192 keeps a node's surviving-type mask in two registers per lane.
-  bool multi = n == 1 && fast && ds[0]->h.TW <= 128 && !(ds[0]->h.flags & KS_FLAG_STATS) && !one_wave && !ds[0]->no_multi;
+  bool multi = n == 1 && fast && ds[0]->h.TW <= 128 && !(ds[0]->h.flags & KS_FLAG_STATS) && !one_wave && !ds[0]->no_multi && !wide;
   if (multi) {
     const u32 lds_mw = 44u * 1024u;
     if ((size_t)ds[0]->h.R * ds[0]->h.ge_max * 8 + 8192 > lds_mw) multi = false;
@@ -3462,7 +3515,9 @@ extern "C" int ks_solve_batch_dev(ks_dev_problem* const* ds, uint32_t n, ks_resu
                                                                                                                      // needs > 256 VGPRs, so 4 waves (one per SIMD): leader + 3 workers
     }
   }
-  if (!multi) hipLaunchKernelGGL(variants[(lean ? 4 : 0) + (fast ? 2 : 0) + (bounds ? 1 : 0)], dim3(n), dim3(64), lds_bytes, st, dp, dsv, lds_bytes);
+  if (!multi && wide) { hipLaunchKernelGGL(variants_wide[(fast ? 2 : 0) + (bounds ? 1 : 0)], dim3(n), dim3(64), lds_bytes, st, dp, dsv, lds_bytes); }
+  else if (!multi) hipLaunchKernelGGL(variants[(lean ? 4 : 0) + (fast ? 2 : 0) + (bounds ? 1 : 0)], dim3(n), dim3(64), lds_bytes, st, dp, dsv, lds_bytes);
+  for (u32 i = 0; i < n; ++i) ds[i]->pack_rm = wide ? 16 : (multi ? (lean && !bounds ? 4 : KS_RES_NARROW) : (lean ? 4 : KS_RES_NARROW));
   }
 #endif
   HIPCHK(hipEventRecord(e1, st));

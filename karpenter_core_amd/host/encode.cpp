@@ -409,7 +409,7 @@ struct Builder {
     }
     K = (uint32_t)key_vals.size(); R = (uint32_t)res_id.size(); T = (uint32_t)pr.instance_types.size(); TW = (T + 63) / 64;
     if (K > KS_MAX_KEYS) throw Unsupported("more than 32 distinct label keys on the path");
-    if (R > KS_MAX_RES) throw Unsupported("more than 8 distinct resource names");
+    if (R > KS_MAX_RES) throw Unsupported(std::to_string(R) + " distinct resource names (the limit is " + std::to_string(KS_MAX_RES) + ")");
     E.key_names.assign(K, ""); for (auto& kv : key_id) E.key_names[kv.second] = kv.first;
     E.key_values.resize(K); E.key_nvalues.assign(K, 0); E.value_int.assign((size_t)K * 64, INT32_MIN); E.key_members.assign(K, {}); E.key_class.assign(K, {}); E.key_ints.assign(K, {});
     for (uint32_t k = 0; k < K; ++k) {

@@ -67,6 +67,7 @@ def libs():
                                         ctypes.POINTER(ctypes.c_uint64), ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]
         kh.ksh_dims.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32)]
         kh.ksh_rr_status.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]
+        kh.ksh_pack_width.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]
         kh.ksh_solve_whatifs_sharded.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint64), ctypes.c_uint32, ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]
         ks.ks_deal_lpt.argtypes = [ctypes.POINTER(ctypes.c_uint64), ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]
         ks.ks_deal_lpt.restype = None
@@ -170,6 +171,15 @@ class FlatProblem:
         if rc != KS_OK:
             raise KSolveError(rc, "ksh_rr_status")
         return bool(out[0]), int(out[1])
+
+    def pack_width(self) -> int:
+        """Resource bound of the ks_pack variant that took the last solve: 4 (LEAN), 8, 16 (a problem with more than 8 resource names); 0 if ks_pack_rr took it.
+        include/ksolve.h ks_problem_pack_width."""
+        out = ctypes.c_int()
+        rc = libs()[1].ksh_pack_width(self._h, ctypes.byref(out))
+        if rc != KS_OK:
+            raise KSolveError(rc, "ksh_pack_width")
+        return int(out.value)
 
     def result_arrays(self) -> dict:
         """The result through the binary door (include/kshost.h ksh_result_arrays_get): numpy copies of the arrays plus the key / resource names."""

@@ -13,9 +13,9 @@ import dataclasses
 import numpy as np
 
 from . import fake
-from .model import (ClusterPod, Container, Expr, HostPort, LabelSelector, Pod, PodAffinityTerm, Problem, StateNode,
+from .model import (ClusterPod, Container, Expr, HostPort, LabelSelector, Pod, PodAffinityTerm, PreferredTerm, Problem, StateNode,
                     Taint, Toleration, TopologySpreadConstraint, DO_NOT_SCHEDULE, LABEL_ARCH, LABEL_CAPACITY_TYPE,
-                    LABEL_HOSTNAME, LABEL_INSTANCE_TYPE, LABEL_OS, LABEL_PROVISIONER, LABEL_ZONE, NO_SCHEDULE)
+                    LABEL_HOSTNAME, LABEL_INSTANCE_TYPE, LABEL_OS, LABEL_PROVISIONER, LABEL_ZONE, NO_SCHEDULE, parse_quantity_milli)
 
 CPU_CHOICES = [100, 250, 500, 1000, 1500]                 # scheduling_benchmark_test.go:285
 MEM_CHOICES = [100, 256, 512, 1024, 2048, 4096]           # :280
@@ -364,3 +364,151 @@ def cluster_after(nodes, bound, events):
             else:
                 raise KeyError(ev[1])
     return [e[0] for e in live], [e[1] for e in live], [e[2] for e in live]
+
+
+# ---- a cloud-like catalogue with 9 to 16 resource names ----
+# The names an AWS-style provider lists on every instance type, whether or not the type has the device, then what device plugins add.
+WIDE_NAMES = ["cpu", "memory", "ephemeral-storage", "pods", "vpc.amazonaws.com/pod-eni", "nvidia.com/gpu", "amd.com/gpu", "aws.amazon.com/neuron",
+              "habana.ai/gaudi", "hugepages-2Mi", "vpc.amazonaws.com/efa", "hugepages-1Gi", "xilinx.com/fpga", "example.com/nic", "smarter-devices/fuse",
+              "intel.com/qat"]
+GPU_TAINT = Taint("nvidia.com/gpu", "true", NO_SCHEDULE)
+
+
+def wide_requested(names: int) -> List[str]:
+    """The names something in `wide_catalogue(names=...)` requests, limits or consumes (at most 8); the others only ever appear in a catalogue or a node's capacity."""
+    return WIDE_NAMES[:6] + [n for n in ("hugepages-2Mi", "vpc.amazonaws.com/efa") if n in WIDE_NAMES[:names]]
+
+
+def wide_catalogue(names: int = 9, pods: int = 400, types: int = 24, existing: int = 6, seed: int = 0, strip: bool = False, dense: bool = False) -> Problem:
+    """A provisioning Solve over a catalogue whose instance types list `names` (9..16) resource names, most of them 0 on most types: general-purpose
+    sizes, GPU types behind a tainted provisioner with a limit on nvidia.com/gpu (subtractMax / filterByRemainingResources over the wide vector), existing
+    nodes whose `available` carries the extended names, a daemonset requesting ephemeral-storage, and pods that request subsets of the names -- some
+    through limits only, some through init containers -- with zonal spread and preferences that relax.
+    strip=True: the same problem with every name that nothing requests removed from the catalogue and the nodes (R <= 8: today's kernels).
+    dense=True (names >= 12): the same problem with requests on every name of the catalogue, so that resources 8.. are requested too (`_densify`)."""
+    assert 9 <= names <= len(WIDE_NAMES) and not (strip and dense) and (names >= 12 or not dense)
+    rs = np.random.RandomState(9000 + seed)
+    catalogue = WIDE_NAMES[:names]
+    keep = set(wide_requested(names)) if strip else set(catalogue)
+    hp, efa = "hugepages-2Mi" in catalogue, "vpc.amazonaws.com/efa" in catalogue
+    its, gpu_idx = [], []
+    for i in range(types):
+        gpu = i % 4 == 3
+        cpu = [2, 4, 8, 16, 32, 48, 64, 96][int(rs.randint(8))]
+        cap = {n: "0" for n in catalogue}
+        cap.update({"cpu": str(cpu), "memory": f"{cpu * int(rs.choice([2, 4, 8]))}Gi", "ephemeral-storage": f"{int(rs.choice([20, 100, 500]))}Gi",
+                    "pods": str(int(rs.choice([29, 58, 110, 234]))), "vpc.amazonaws.com/pod-eni": str(int(rs.choice([0, 9, 38, 107])))})
+        if gpu:
+            cap["nvidia.com/gpu"] = str(int(rs.choice([1, 2, 4, 8])))
+            if efa:
+                cap["vpc.amazonaws.com/efa"] = str(int(rs.choice([0, 1, 4])))
+        elif rs.rand() < 0.2:
+            cap[["amd.com/gpu", "aws.amazon.com/neuron", "habana.ai/gaudi"][int(rs.randint(3))]] = str(int(rs.choice([1, 4, 16])))
+        if hp and cpu >= 8:
+            cap["hugepages-2Mi"] = f"{int(rs.choice([0, 512, 2048]))}Mi"
+        for n in catalogue[11:]:
+            if rs.rand() < 0.3:
+                cap[n] = str(int(rs.randint(1, 8)))
+        it = fake.new_instance_type(f"{'g' if gpu else 'm'}{i:03d}-{cpu}x", resources={k: v for k, v in cap.items() if k in keep},
+                                    architecture="amd64", operating_systems=["linux"])
+        it.overhead = {"cpu": "100m", "memory": "10Mi", "ephemeral-storage": "1Gi"}
+        its.append(it)
+        if gpu:
+            gpu_idx.append(i)
+    gen = [i for i in range(types) if i not in gpu_idx]
+    provs = [fake.provisioner("gpu", weight=10, taints=[GPU_TAINT], instance_types=gpu_idx,
+                              limits={"nvidia.com/gpu": str(int(rs.randint(8, 48))), "cpu": str(int(rs.randint(200, 800)))}),
+             fake.provisioner("default", instance_types=gen, limits={"cpu": str(int(rs.randint(pods // 2 + 2, 2 * pods + 3)))} if rs.rand() < 0.5 else None)]
+    nodes = []
+    for e in range(existing):
+        ti = int(rs.randint(types))
+        it = its[ti]
+        frac = rs.uniform(0.2, 0.9)
+        avail = {}
+        for n, v in it.capacity.items():
+            m = parse_quantity_milli(v)
+            avail[n] = str(int(m * frac) // 1000) if n in ("cpu", "pods") or n not in ("memory", "ephemeral-storage", "hugepages-2Mi") else f"{int(m * frac) // 1000 // 2**20}Mi"
+        zone = it.offerings[int(rs.randint(len(it.offerings)))]
+        name = f"wide-node-{e:04d}"
+        labels = {LABEL_PROVISIONER: "gpu" if ti in gpu_idx else "default", LABEL_INSTANCE_TYPE: it.name, LABEL_ZONE: zone.zone,
+                  LABEL_CAPACITY_TYPE: zone.capacity_type, LABEL_ARCH: "amd64", LABEL_OS: "linux", LABEL_HOSTNAME: name, "karpenter.sh/initialized": "true"}
+        nodes.append(StateNode(name=name, labels=labels, taints=[GPU_TAINT] if ti in gpu_idx else [], available=avail, capacity=dict(it.capacity)))
+    out = []
+    for k in range(pods):
+        c = Container(requests={"cpu": f"{CPU_CHOICES[rs.randint(len(CPU_CHOICES))]}m", "memory": f"{MEM_CHOICES[rs.randint(len(MEM_CHOICES))]}Mi"})
+        p = Pod(uid=f"wide-{k:06d}", labels={"my-label": _lab(rs)}, containers=[c])
+        kind = int(rs.randint(10))
+        if kind == 0:
+            c.requests["ephemeral-storage"] = f"{int(rs.choice([1, 4, 30]))}Gi"
+        elif kind == 1:
+            c.limits["vpc.amazonaws.com/pod-eni"] = "1"                      # limits only: the request defaults to the limit
+        elif kind in (2, 3):
+            c.limits["nvidia.com/gpu"] = str(int(rs.choice([1, 1, 2, 4])))
+            if kind == 3 and efa:
+                c.limits["vpc.amazonaws.com/efa"] = "1"
+            p.tolerations = [Toleration(key=GPU_TAINT.key, operator="Exists")]
+        elif kind == 4:
+            init = Container(requests={"cpu": f"{int(rs.choice([500, 2000, 6000]))}m"})
+            if hp:
+                init.requests["hugepages-2Mi"] = f"{int(rs.choice([64, 256]))}Mi"
+            p.init_containers = [init]
+        elif kind == 5:
+            p.preferred_affinity = [PreferredTerm(10, [Expr(LABEL_ZONE, "In", ["no-such-zone"])]), PreferredTerm(5, [Expr(LABEL_CAPACITY_TYPE, "In", ["spot"])])]
+        elif kind == 6:
+            p.spread = [TopologySpreadConstraint(1, LABEL_ZONE, DO_NOT_SCHEDULE, LabelSelector({"my-label": p.labels["my-label"]}))]
+        elif kind == 7 and rs.rand() < 0.3:
+            c.requests["cpu"] = "200"                                         # fits nothing: stays unschedulable
+        out.append(p)
+    ds = [Pod(uid="wide-ds", containers=[Container(requests={"cpu": "50m", "memory": "32Mi", "ephemeral-storage": "512Mi"})])]
+    pr = Problem(instance_types=its, provisioners=provs, pods=out, daemonset_pods=ds, nodes=nodes, extra_well_known=fake.EXTRA_WELL_KNOWN)
+    return _densify(pr, catalogue, seed) if dense else pr
+
+
+# device names the general-purpose (untainted) types may carry, and the unit a request of each is written in
+_DENSE_DEVICES = {"amd.com/gpu": "", "aws.amazon.com/neuron": "", "habana.ai/gaudi": "", "hugepages-2Mi": "Mi", "hugepages-1Gi": "", "xilinx.com/fpga": "",
+                  "example.com/nic": "", "smarter-devices/fuse": "", "intel.com/qat": ""}
+
+
+def _densify(pr: Problem, catalogue: List[str], seed: int) -> Problem:
+    """wide_catalogue(dense=True): requests on resources 8.. of the encoding (cpu, memory, pods, then first use -- the first provisioner's limits
+    name every catalogue name, so the order is the sorted catalogue).  The GPU provisioner's limit on nvidia.com/gpu and the default provisioner's
+    limits on two late names bind; pods request devices through requests, limits only and init containers; pairs of pods differ only in a request
+    on a late name (distinct evaluation classes); existing nodes hold one or two of a late device; a second daemonset, on the GPU provisioner's
+    nodes only, requests vpc.amazonaws.com/efa.  Its own random stream: the problem it starts from is wide_catalogue(dense=False)'s."""
+    rd = np.random.RandomState(19000 + seed)
+    order = ["cpu", "memory", "pods"] + sorted(n for n in catalogue if n not in ("cpu", "memory", "pods"))
+    late = [n for n in order[8:] if n in _DENSE_DEVICES]
+    gpu, default = pr.provisioners
+    gpu.limits = dict({n: "1000000Gi" for n in catalogue}, **gpu.limits)
+    def limit(n):      # what the existing nodes of the provisioner hold (remainingResources starts below it), plus room for a few new nodes
+        held = sum(parse_quantity_milli(nd.capacity.get(n, "0")) for nd in pr.nodes if nd.labels.get(LABEL_PROVISIONER) == "default") // 1000
+        return f"{held // 2**20 + int(rd.randint(30, 120)) * 1024}Mi" if _DENSE_DEVICES[n] else str(held + int(rd.randint(30, 120)))
+    default.limits = dict(default.limits or {}, **{n: limit(n) for n in late[:2]})
+    for it in pr.instance_types:
+        if it.name.startswith("m") and rd.rand() < 0.6:
+            for n in rd.choice(sorted(_DENSE_DEVICES.keys() & set(catalogue)), size=2, replace=False):
+                it.capacity[n] = f"{int(rd.choice([512, 2048]))}Mi" if _DENSE_DEVICES[n] else str(int(rd.randint(1, 6)))
+    for nd in pr.nodes:
+        for n in late:
+            if n in nd.available and nd.available[n] != "0":
+                nd.available[n] = str(int(rd.randint(1, 3)))
+    devices = sorted(_DENSE_DEVICES.keys() & set(catalogue))
+    for p in pr.pods:
+        if p.tolerations or p.containers[0].requests.get("cpu") == "200" or rd.rand() < 0.5:
+            continue
+        n = devices[int(rd.randint(len(devices)))]
+        q = f"{int(rd.choice([64, 256]))}Mi" if _DENSE_DEVICES[n] else str(int(rd.choice([1, 1, 2])))
+        how = int(rd.randint(3))
+        if how == 0:
+            p.containers[0].requests[n] = q
+        elif how == 1:
+            p.containers[0].limits[n] = q                                 # limits only
+        else:
+            p.init_containers = [Container(requests={"cpu": "100m", n: q})]
+    for k, n in enumerate(late[:3]):                                          # same spec but for a request on a late name
+        for amount in ("1", "2"):
+            pr.pods.append(Pod(uid=f"wide-pair-{k}-{amount}", labels={"my-label": "pair"},
+                               containers=[Container(requests={"cpu": "250m", "memory": "256Mi", n: amount})]))
+    pr.daemonset_pods = pr.daemonset_pods + [Pod(uid="wide-ds-gpu", node_selector={LABEL_PROVISIONER: "gpu"}, tolerations=[Toleration(key=GPU_TAINT.key, operator="Exists")],
+                                                 containers=[Container(requests={"cpu": "10m", "vpc.amazonaws.com/efa": "1"})])]
+    return pr

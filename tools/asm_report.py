@@ -11,7 +11,7 @@ between LDS and global memory (FLAT accesses), and a loop counter the analysis t
 import collections, os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "karpenter_core_amd", "csrc", "ksolve.hip")
-K8 = "_Z7ks_packILb1ELb0ELb1ELi8EEvPK7DevProbPK8DevStatej"
+K8 = "_Z7ks_packILb1ELb0ELb1ELi8ELi4EEvPK7DevProbPK8DevStatej"
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 tmp = tempfile.mkdtemp(prefix="ksasm")
 

@@ -40,9 +40,22 @@ for kind in ("fetch", "write", "insts", "cycles"):
         for c, (v, n) in ctrs.items():
             allk.setdefault(k, {})[c] = {"sum": v, "dispatches": n, "per_dispatch": v / n}
 out["per_kernel"] = {k: allk[k] for k in sorted(allk)}
+def pack_args(k):
+    """ks_pack<FAST, BOUNDS, LEAN, waves[, RM]> -> the template arguments as strings (None for any other kernel)."""
+    k = k.replace(" ", "")
+    if not k.split("(")[0].endswith(">") or "ks_pack<" not in k:
+        return None
+    return k[k.index("ks_pack<") + len("ks_pack<"):k.index(">")].split(",")
+
+
+def pack_waves(k, waves):
+    a = pack_args(k)
+    return a is not None and len(a) >= 4 and a[3] == str(waves)
+
+
 # the kernel that takes the headline Solve: ks_pack_rr since round 4 (when it ran), else the 8-wave ks_pack variant
 pk = ([k for k in allk if k.startswith("ks_pack_rr")] if line.get("roofline", {}).get("kernel") == "ks_pack_rr" else []) or \
-     [k for k in allk if "ks_pack" in k and "8>" in k.replace(" ", "")] or [k for k in allk if "ks_pack" in k]
+     [k for k in allk if pack_waves(k, 8)] or [k for k in allk if "ks_pack" in k]
 if pk:
     k = pk[0]; c = allk[k]
     per = lambda name: c[name]["per_dispatch"] if name in c else None
@@ -81,9 +94,9 @@ def leg(tag, pick, workgroups, waves):
             "wave_cycles": {n: per(n) for n in ("SQ_WAVE_CYCLES", "SQ_BUSY_CYCLES", "SQ_WAIT_ANY", "SQ_WAIT_INST_ANY", "SQ_ACTIVE_INST_ANY", "SQ_WAVES", "GRBM_GUI_ACTIVE") if per(n) is not None},
             "wait_fraction": (wa / wc) if wc and wa is not None else None, "workgroups": workgroups, "waves_per_workgroup": waves}
 out["legs"] = {}
-wi = leg("wi", lambda k: "ks_pack<" in k and k.rstrip(">").endswith(",1") and "true,false,true" in k, 512, 1)
+wi = leg("wi", lambda k: pack_waves(k, 1) and pack_args(k)[:3] == ["true", "false", "true"], 512, 1)
 if wi: out["legs"]["whatifs"] = dict(wi, command="bench.py --whatifs-only")
-c5 = leg("c5", lambda k: "ks_pack<" in k and k.rstrip(">").endswith(",4"), 1, 4)
+c5 = leg("c5", lambda k: pack_waves(k, 4), 1, 4)
 if c5: out["legs"]["config5"] = dict(c5, command="bench.py --config5 250000 --steps 1 --warmup 0")
 if prof_line:
     out["bench_under_rocprof"] = {"value": prof_line["value"], "pack_kernel_ms_mean": prof_line["phases_ms_mean"]["pack_kernel_ms"]}
