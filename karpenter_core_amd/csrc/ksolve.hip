@@ -2769,6 +2769,8 @@ DevPool& pool() { static DevPool* p = new DevPool(); return *p; }      // never 
 struct TmpDev {
   int device; size_t bytes = 0; void* p = nullptr;
   explicit TmpDev(int dev) : device(dev) {}
+  TmpDev(const TmpDev&) = delete;                   // one owner per block: a copy would hand the block back to the pool twice (a launch names .as<T>(), taken beforehand)
+  TmpDev& operator=(const TmpDev&) = delete;
   int alloc(size_t n) { bytes = n ? n : 1; return pool().get(device, bytes, false, &p); }
   ~TmpDev() { pool().put(device, bytes, false, p); }
   template <class T> T* as() const { return (T*)p; }
@@ -3559,7 +3561,8 @@ extern "C" int ks_batch_records_dev(ks_dev_problem* const* ds, uint32_t n, const
   }
   TmpDev t_desc(device); TRY(t_desc.alloc(n * sizeof(RecordDesc)));
   HIPCHK(hipMemcpyAsync(t_desc.p, hd.data(), n * sizeof(RecordDesc), hipMemcpyHostToDevice, ds[0]->stream));
-  hipLaunchKernelGGL(ks_records, dim3(n), dim3(64), 0, ds[0]->stream, t_desc.as<RecordDesc>(), (u64*)d_out, words);
+  const RecordDesc* d_desc = t_desc.as<RecordDesc>();
+  hipLaunchKernelGGL(ks_records, dim3(n), dim3(64), 0, ds[0]->stream, d_desc, (u64*)d_out, words);
   HIPCHK(hipStreamSynchronize(ds[0]->stream)); HIPCHK(hipGetLastError());      // the buffer is complete when this returns: the caller's own stream may read it
   return KS_OK;
 }
@@ -3754,7 +3757,9 @@ extern "C" int ks_launch_pick_dev(ks_dev_problem* const* ds, uint32_t n, const u
   TmpDev t_dp(device), t_dsv(device), t_node(device), t_type(device), t_pair(device), t_price(device);
   TRY(batch_descriptors(ds, n, node, true, t_dp, t_dsv, t_node));
   TRY(t_type.alloc(n * sizeof(i32))); TRY(t_pair.alloc(n * sizeof(i32))); TRY(t_price.alloc(n * sizeof(double)));
-  hipLaunchKernelGGL(ks_launch_pick, dim3(n), dim3(64), 0, ds[0]->stream, t_dp.as<DevProb>(), t_dsv.as<DevState>(), t_node.as<u32>(), t_type.as<i32>(), t_pair.as<i32>(), t_price.as<double>());
+  const DevProb* dp = t_dp.as<DevProb>(); const DevState* dsv = t_dsv.as<DevState>(); const u32* dnode = t_node.as<u32>();
+  i32* dtype = t_type.as<i32>(); i32* dpair = t_pair.as<i32>(); double* dprice = t_price.as<double>();
+  hipLaunchKernelGGL(ks_launch_pick, dim3(n), dim3(64), 0, ds[0]->stream, dp, dsv, dnode, dtype, dpair, dprice);
   HIPCHK(hipMemcpyAsync(out_type, t_type.p, n * sizeof(i32), hipMemcpyDeviceToHost, ds[0]->stream)); HIPCHK(hipMemcpyAsync(out_pair, t_pair.p, n * sizeof(i32), hipMemcpyDeviceToHost, ds[0]->stream));
   HIPCHK(hipMemcpyAsync(out_price, t_price.p, n * sizeof(double), hipMemcpyDeviceToHost, ds[0]->stream));
   HIPCHK(hipStreamSynchronize(ds[0]->stream)); HIPCHK(hipGetLastError());
@@ -3769,7 +3774,8 @@ extern "C" int ks_types_subset_dev(ks_dev_problem* const* ds, uint32_t n, const 
   TRY(batch_descriptors(ds, n, node, false, t_dp, t_dsv, t_node));
   TRY(t_lhs.alloc((size_t)n * stride_words * sizeof(u64))); TRY(t_out.alloc(n * sizeof(u32)));
   HIPCHK(hipMemcpy(t_lhs.p, lhs, (size_t)n * stride_words * sizeof(u64), hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(ks_types_subset, dim3(n), dim3(64), 0, ds[0]->stream, t_dp.as<DevProb>(), t_dsv.as<DevState>(), t_node.as<u32>(), t_lhs.as<u64>(), stride_words, t_out.as<u32>());
+  const DevProb* dp = t_dp.as<DevProb>(); const DevState* dsv = t_dsv.as<DevState>(); const u32* dnode = t_node.as<u32>(); const u64* dlhs = t_lhs.as<u64>(); u32* dout = t_out.as<u32>();
+  hipLaunchKernelGGL(ks_types_subset, dim3(n), dim3(64), 0, ds[0]->stream, dp, dsv, dnode, dlhs, stride_words, dout);
   HIPCHK(hipMemcpyAsync(out, t_out.p, n * sizeof(u32), hipMemcpyDeviceToHost, ds[0]->stream));
   HIPCHK(hipStreamSynchronize(ds[0]->stream)); HIPCHK(hipGetLastError());
   return KS_OK;
@@ -3829,7 +3835,8 @@ extern "C" int ks_probe_has(const ks_req1* a, const int32_t* value_int, uint32_t
   TRY(tv.alloc(64 * sizeof(i32))); TRY(to.alloc(sizeof(ks_req_facts)));
   i32 tmp[64]; for (int i = 0; i < 64; ++i) tmp[i] = (u32)i < nvalues ? value_int[i] : INT32_MIN;
   HIPCHK(hipMemcpy(tv.p, tmp, sizeof tmp, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(ks_probe_has_kernel, dim3(1), dim3(1), 0, 0, *a, tv.as<i32>(), nvalues, to.as<ks_req_facts>());
+  const i32* dv = tv.as<i32>(); ks_req_facts* dout = to.as<ks_req_facts>();
+  hipLaunchKernelGGL(ks_probe_has_kernel, dim3(1), dim3(1), 0, 0, *a, dv, nvalues, dout);
   HIPCHK(hipDeviceSynchronize());
   HIPCHK(hipMemcpy(out, to.p, sizeof(ks_req_facts), hipMemcpyDeviceToHost));
   return KS_OK;

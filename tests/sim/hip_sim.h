@@ -19,6 +19,7 @@
 #include <stdio.h>
 #include <sys/mman.h>
 #include <functional>
+#include <tuple>
 #include <mutex>
 #include <vector>
 #include <map>
@@ -114,4 +115,8 @@ static inline uint64_t max(uint64_t a, uint64_t b) { return a > b ? a : b; }
 static inline int64_t min(int64_t a, int64_t b) { return a < b ? a : b; }
 static inline int64_t max(int64_t a, int64_t b) { return a > b ? a : b; }
 
-#define hipLaunchKernelGGL(kern, grid, block, lds, stream, ...) ks_sim::launch(dim3(grid), dim3(block), [=]() { kern(__VA_ARGS__); })
+// The kernel and its arguments are evaluated once, here, as on the device; the body captures only those values.  (Capturing the argument EXPRESSIONS would copy
+// whatever they name -- a host-side owner of a device block, say -- into the lambda and again into the std::function, and run their destructors as often.)
+#define hipLaunchKernelGGL(kern, grid, block, lds, stream, ...) do { \
+    auto ks_sim_kern_ = (kern); auto ks_sim_args_ = std::make_tuple(__VA_ARGS__); \
+    ks_sim::launch(dim3(grid), dim3(block), [=]() { std::apply(ks_sim_kern_, ks_sim_args_); }); } while (0)

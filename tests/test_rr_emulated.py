@@ -105,18 +105,18 @@ sys.path.insert(0, %(root)r); sys.path.insert(0, %(tests)r)
 import simlib
 S = simlib.use_sim()
 from karpenter_core_amd import workloads as W
-import test_fuzz_mid as T, test_fuzz as F
+import test_wide_resources as WR, test_rr_emulated as E
 out = {}
 def fp(res):
     return hashlib.sha256(json.dumps(res.canonical(), sort_keys=True).encode()).hexdigest()
 def reasons(res):
     return hashlib.sha256(json.dumps(sorted((int(k), int(v)) for k, v in res.reasons.items())).encode()).hexdigest()
 for name, kind, args, no_rr in json.loads(sys.argv[1]):
-    p = {"config3": lambda: W.config3(**args), "mid": lambda: T.mid_problem(args["seed"]), "fuzz": lambda: F.fuzz_problem(args["seed"])}[kind]()
+    p = E._problem(kind, args)
     try:
         f = S.FlatProblem(p, flags=S.KS_FLAG_NO_RR if no_rr else 0)
-        r = f.solve(); st = f.rr_status(); f.close()
-        out[name] = {"fp": fp(r), "reasons": reasons(r), "rr": list(st)}
+        r = f.solve(); st = f.rr_status(); pw = f.pack_width(); f.close()
+        out[name] = {"fp": fp(r), "reasons": reasons(r), "rr": list(st), "width": pw}
     except Exception as e:
         out[name] = {"error": str(e)[:200]}
 # a what-if batch: the batched single-wave launch (one block per what-if) over one snapshot, flattened one by one
@@ -127,6 +127,17 @@ flats = S.open_whatifs(snap, pn, sets, derive=False)
 for f in flats: f.upload(0)
 res, _, _ = S.solve_batch(flats)
 out["whatifs"] = {"fps": [fp(r) for r in res]}
+# the same over a snapshot whose catalogue names 14 resources, with requests past the eighth: the batched launch of the wide single-wave variant
+snap, pod_node, bound, _ = WR.wide_snapshot(**E.WIDE_SNAPSHOT)
+parsed = S.ParsedProblem(snap)
+for derive in (False, True):
+    try:
+        flats = S.open_whatifs(parsed, pod_node, E.WIDE_SETS, derive=derive)
+        res, _, _ = S.solve_batch(flats)
+        out["wide_whatifs_derived" if derive else "wide_whatifs"] = {"fps": [fp(r) for r in res], "reasons": [reasons(r) for r in res], "widths": [f.pack_width() for f in flats]}
+        for f in flats: f.close()
+    except Exception as e:
+        out["wide_whatifs_derived" if derive else "wide_whatifs"] = {"error": str(e)[:200]}
 print("RESULT " + json.dumps(out))
 """
 
@@ -136,7 +147,11 @@ PACK_CASES = [
 ] + [(f"fuzz_{seed}", "fuzz", {"seed": seed}, False) for seed in range(32)] + [      # the small family, every committed seed: host ports, volumes, existing nodes, limits, hostname selectors -- the general (not LEAN) variants
     ("mid_0_no_rr", "mid", {"seed": 0}, True),
     ("mid_12_declined", "mid", {"seed": 12}, False),   # ks_pack_rr starts, declines with code 7 mid-run, ks_pack takes over
-]
+] + [      # 9-16 resource names (tests/test_wide_resources.py's families, first seeds): the wide variant (R bound 16), ks_grid_types_wide, ks_link_ev_wide
+    (f"wide_sparse_{seed}", "wide_sparse", {"seed": seed}, False) for seed in range(8)] + [
+    (f"wide_dense_{seed}", "wide_dense", {"seed": seed}, False) for seed in range(8)]      # requests, limits and daemonset overhead on resources 8..15
+WIDE_SNAPSHOT = {"names": 14, "seed": 7, "existing": 16, "dense": True}
+WIDE_SETS = [[0, 3], [5], [1, 2, 9], [7, 11], [4, 6, 8, 10, 12], [15]]
 
 
 @pytest.fixture(scope="module")
@@ -155,7 +170,9 @@ def _problem(kind, args):
     from karpenter_core_amd import workloads as W
     import test_fuzz as F
     import test_fuzz_mid as T
-    return {"config3": lambda: W.config3(**args), "mid": lambda: T.mid_problem(args["seed"]), "fuzz": lambda: F.fuzz_problem(args["seed"])}[kind]()
+    import test_wide_resources as WR
+    return {"config3": lambda: W.config3(**args), "mid": lambda: T.mid_problem(args["seed"]), "fuzz": lambda: F.fuzz_problem(args["seed"]),
+            "wide_sparse": lambda: W.wide_catalogue(**WR._family(args["seed"])), "wide_dense": lambda: W.wide_catalogue(**WR._dense_family(args["seed"]))}[kind]()
 
 
 @pytest.mark.parametrize("name,kind,args,no_rr", PACK_CASES, ids=[c[0] for c in PACK_CASES])
@@ -170,6 +187,8 @@ def test_ks_pack_source_matches_oracle_on_the_emulator(emulated_pack, name, kind
         assert got["rr"] == [1, 7]                       # launched, gave the Solve back: the result above is ks_pack's
     elif no_rr:
         assert got["rr"][0] == 0
+    if kind.startswith("wide"):
+        assert got["width"] == 16                        # the wide variant took the Solve
 
 
 def test_whatif_batch_kernel_on_the_emulator(emulated_pack):
@@ -180,3 +199,19 @@ def test_whatif_batch_kernel_on_the_emulator(emulated_pack):
     sets = [[0, 3], [5], [1, 2, 9], [7, 11]]
     want = [hashlib.sha256(json.dumps(O.solve(W.whatif(its, prov, nodes, bound, c, False)).canonical(), sort_keys=True).encode()).hexdigest() for c in sets]
     assert emulated_pack["whatifs"]["fps"] == want
+
+
+@pytest.mark.parametrize("derived", [False, True], ids=["flattened", "derived"])
+def test_wide_whatif_batch_kernel_on_the_emulator(emulated_pack, derived):
+    """The batched launch over what-ifs of a 14-name snapshot with requests past the eighth resource (flattened on the host, and derived on the device by
+    ks_derive_whatifs): every what-if taken by the wide variant, its result and reasons the oracle's."""
+    import hashlib
+    import test_wide_resources as WR
+    got = emulated_pack["wide_whatifs_derived" if derived else "wide_whatifs"]
+    assert "error" not in got, got
+    snap, _, bound, _ = WR.wide_snapshot(**WIDE_SNAPSHOT)
+    want = [O.solve(WR.whatif_problem(snap, bound, cs)) for cs in WIDE_SETS]
+    assert got["widths"] == [16] * len(WIDE_SETS)
+    assert got["fps"] == [hashlib.sha256(json.dumps(w.canonical(), sort_keys=True).encode()).hexdigest() for w in want]
+    assert got["reasons"] == [hashlib.sha256(json.dumps(sorted((int(k), int(v)) for k, v in w.reasons.items())).encode()).hexdigest() for w in want]
+    assert sum(1 for w in want if w.new_nodes) >= 2
