@@ -164,12 +164,23 @@ int ksh_types_subset(void** handles, uint32_t n, const uint32_t* node, const uin
  * what-if starts with and what countDomains finds for it follow from per-node tables of the snapshot (ks_whatif_topo).  Required anti-affinity is covered as well: an inverse group
  * exists only while an owner is in the batch or stays bound (decided per what-if on the device; the evaluation skips a group that does not exist), and the
  * staying owners are counted per node.  KS_ERR_UNSUPPORTED -- nothing opened -- where a what-if depends on its candidate set in other ways: more than 1024
- * groups, one spread group shared by pods whose node filters differ, volume limits / claims.  Use ksh_open_whatifs_parsed then. */
+ * groups, one spread group shared by pods whose node filters differ, volume limits / claims (without KSH_DERIVE_VOLUMES).  Use ksh_open_whatifs_parsed then.
+ *
+ * KSH_DERIVE_VOLUMES (opt-in; a bit no KS_FLAG_* uses, never passed on to the flat problem): snapshots with CSI volume limits and / or claims are derived too.
+ * The snapshot is then flattened with a partition of its claims that does not depend on the candidate set: a SOLO claim -- mounted by
+ * exactly one bound pod and listed on no state node but that pod's -- is a per-driver count in the pod's volume entries; every other claim a bound pod mounts
+ * is a MULTI claim, one bit over a snapshot-wide universe in the per-node sets.  Each derived what-if carries its own per-node volume counts and sets
+ * (ks_whatifs_open_ex with KS_WHATIFS_VOLUMES).  This flattening is kept apart from the flag-0 one (which ksh_snapshot_fingerprint(flags 0) hashes and
+ * ksh_open_whatifs_parsed uses); KS_ERR_UNSUPPORTED still for more than 64 limited drivers, 2^24 multi claims, or per-what-if volume state above 64 MiB. */
+#define KSH_DERIVE_VOLUMES (1u << 16)
 int ksh_open_whatifs_derived(void* parsed_snapshot, uint32_t flags, uint32_t n, const uint32_t* cand_off, const uint32_t* cand, const int32_t* pod_node, int device, void** out_handles);
+uint64_t ksh_whatifs_arena_bytes(void* handle);      /* a derived what-if: device bytes of the arena its batch shares (ks_whatifs_arena_bytes); 0 for any other handle */
 int ksh_open_whatifs_parsed(void* parsed_snapshot, uint32_t flags, uint32_t n, const uint32_t* cand_off, const uint32_t* cand, const int32_t* pod_node, uint32_t nthreads, void** out_handles);
 /* Diagnostic (no GPU needed, not on any solving path): what the device would derive for ONE candidate set -- group activity, domain counts, hostname rows --
  * restated in plain loops over the per-node tables and compared with that what-if flattened by itself.  KS_OK, or KS_ERR_INVALID with the first difference
- * in ksh_last_error(); KS_ERR_UNSUPPORTED for a snapshot ksh_open_whatifs_derived refuses. */
+ * in ksh_last_error(); KS_ERR_UNSUPPORTED for a snapshot ksh_open_whatifs_derived refuses.  With KSH_DERIVE_VOLUMES it also restates, for every node that
+ * stays, the volume counts and limits per driver and the multi claims it lists, and for every pod of the batch on every such node whether the volume test
+ * admits it and what it adds per driver -- against the what-if's own (candidate-dependent) partition. */
 int ksh_check_whatif_derivation(void* parsed_snapshot, uint32_t flags, const uint32_t* cand, uint32_t ncand, const int32_t* pod_node);
 
 /* ---- the snapshot kept current by EVENTS ("cached incremental SoA builder fed from state.Cluster") ----
@@ -194,7 +205,7 @@ int ksh_check_whatif_derivation(void* parsed_snapshot, uint32_t flags, const uin
 int ksh_env_apply(void* parsed_snapshot, const int32_t* pod_node /* first call: the bindings; later NULL */, const char* ksd_text, size_t len, uint32_t info[4] /* or NULL */);
 int ksh_snapshot_bindings(void* parsed_snapshot, int32_t* out /* [cap] or NULL */, uint32_t cap, uint32_t* n_pods /* or NULL */, uint32_t* n_nodes /* or NULL */);
 /* Diagnostic (tests): FNV-1a over the snapshot's flattening -- the flat problem and the per-node tables behind the device derivation; `cold` != 0: of a
- * flattening made from scratch for the comparison (nothing cached is touched). */
+ * flattening made from scratch for the comparison (nothing cached is touched); flags with KSH_DERIVE_VOLUMES: of the flattening derived volume what-ifs use. */
 int ksh_snapshot_fingerprint(void* parsed_snapshot, const int32_t* pod_node /* or NULL */, uint32_t flags, int cold, uint64_t* out);
 
 #ifdef __cplusplus

@@ -266,8 +266,8 @@ int ks_problem_upload_shared(const ks_problem* p, const ks_dev_problem* base, ks
  * descriptors) and builds every batch on the device (the snapshot's queue order restricted to the candidates' pods).  ks_whatifs_problems are
  * ordinary device problems (views owned by the batch) for ks_solve_batch_dev / ks_batch_records_dev / ks_price_filter_dev / ...; in their
  * results pod i is the i-th pod of the what-if in the SNAPSHOT's queue order (ks_whatifs_pod_ids names the snapshot pod behind each) and
- * existing node e is the snapshot's row e (removed nodes receive nothing).  Not for snapshots with volume limits or more than 1024 topology groups
- * (KS_ERR_UNSUPPORTED: the caller flattens those what-ifs one by one). */
+ * existing node e is the snapshot's row e (removed nodes receive nothing).  Not for snapshots with volume limits (base ND > 0: see ks_whatifs_open_ex)
+ * or more than 1024 topology groups (KS_ERR_UNSUPPORTED: the caller flattens those what-ifs one by one). */
 typedef struct ks_whatif_batch ks_whatif_batch;
 /* Snapshots whose bound pods carry spread / affinity / anti-affinity terms (base G > 0, G <= 1024): what a what-if's topology takes from its
  * candidate set is derived on the device too -- which groups exist from the start (owned by a pod of the batch: topology.go:72-78) and countDomains over
@@ -290,7 +290,21 @@ int ks_whatifs_open(const ks_dev_problem* base, uint32_t n_nodes, const int32_t*
                     const uint32_t* cand /* node indices */, const uint32_t* n_pods /* [n] pods bound to each candidate set */,
                     const int64_t* remaining /* [n][M][R] remainingResources without the candidates */,
                     const ks_whatif_topo* topo /* NULL for a snapshot without topology groups */, ks_whatif_batch** out);
+/* The same with options.  KS_WHATIFS_VOLUMES accepts a snapshot with volume drivers (base ND > 0): every what-if gets per-node volume counts [E][ND] and
+ * claim sets [E][SW] of its own, initialised from the snapshot's en_vol_count / en_vol_set when it is solved.  That is exact only for a snapshot whose
+ * claim partition does not depend on the candidate set -- a claim that is a count (0x80000000 entry) in some pod's vol_list must be mounted by no other
+ * snapshot pod and listed on no existing row but that pod's node; libkshost flattens snapshots so under KSH_DERIVE_VOLUMES (kshost.h).  ks_whatifs_open
+ * keeps refusing such a snapshot. */
+#define KS_WHATIFS_VOLUMES 1u
+typedef struct ks_whatifs_options {
+  const ks_whatif_topo* topo;   /* as ks_whatifs_open's `topo` */
+  uint32_t flags;               /* KS_WHATIFS_* */
+  uint32_t reserved;            /* 0 */
+} ks_whatifs_options;
+int ks_whatifs_open_ex(const ks_dev_problem* base, uint32_t n_nodes, const int32_t* pod_node, const int32_t* node_row, uint32_t n, const uint32_t* cand_off,
+                       const uint32_t* cand, const uint32_t* n_pods, const int64_t* remaining, const ks_whatifs_options* opt, ks_whatif_batch** out);
 ks_dev_problem* const* ks_whatifs_problems(ks_whatif_batch* b);
+uint64_t ks_whatifs_arena_bytes(const ks_whatif_batch* b);          /* device bytes of the batch's arena (diagnostics: tools/time_whatif_volumes.py) */
 uint32_t ks_whatifs_count(const ks_whatif_batch* b);
 int ks_whatifs_pod_ids(ks_whatif_batch* b, uint32_t i, uint32_t* out /* [n_pods of what-if i] snapshot pod ids, what-if pod order */);
 void ks_whatifs_free(ks_whatif_batch* b);

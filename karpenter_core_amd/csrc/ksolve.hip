@@ -3029,7 +3029,8 @@ extern "C" int ks_problem_upload_shared(const ks_problem* p, const ks_dev_proble
 // snapshot's queue order restricted to the pods of its candidate nodes -- on the device.  Each what-if is then an ordinary ks_dev_problem
 // (a view: it owns nothing) and goes through ks_solve_batch_dev / ks_batch_records_dev / the price stage like any other.
 // What the derivation cannot express falls to the caller: it requires a snapshot whose what-ifs differ in nothing but the pod subset,
-// the removed nodes and remainingResources (no topology groups, no volume limits: libkshost checks, and flattens per what-if otherwise).
+// the removed nodes and remainingResources (topology groups through per-node tables; volume limits only through ks_whatifs_open_ex: libkshost checks, and
+// flattens per what-if otherwise).
 // ------------------------------------------------------------------------------------------------
 struct DeriveDesc { const u64* cand_nodes; u32* pod_gid; u32 P_expected, pad; };
 // one block per what-if: the snapshot's queue in order, 256 pods per step; a pod joins iff its node is a candidate; ballots give its place
@@ -3100,20 +3101,24 @@ extern "C" void ks_whatifs_free(ks_whatif_batch* b) {
 }
 extern "C" ks_dev_problem* const* ks_whatifs_problems(ks_whatif_batch* b) { return b ? b->views.data() : nullptr; }
 extern "C" uint32_t ks_whatifs_count(const ks_whatif_batch* b) { return b ? b->n : 0; }
+extern "C" uint64_t ks_whatifs_arena_bytes(const ks_whatif_batch* b) { return b ? (uint64_t)b->arena_bytes : 0; }
 
 // base: the resident snapshot (tables built).  pod_node[base P]: snapshot node index of every snapshot pod (-1: none); node_row[n_nodes]: the node's
 // existing-node row in `base`, or -1 (a node no provisioner owns).  What-if w removes nodes cand[cand_off[w] .. cand_off[w+1]); n_pods[w] = pods
 // bound to them (the caller knows; checked on the device); remaining[w][M][R] = remainingResources with those nodes gone (scheduler.go:71-75).
-extern "C" int ks_whatifs_open(const ks_dev_problem* base, uint32_t n_nodes, const int32_t* pod_node, const int32_t* node_row, uint32_t n, const uint32_t* cand_off,
-                               const uint32_t* cand, const uint32_t* n_pods, const int64_t* remaining, const ks_whatif_topo* topo, ks_whatif_batch** out) {
+// volumes (ks_whatifs_open_ex, KS_WHATIFS_VOLUMES): a snapshot with volume drivers (ND > 0) is accepted; every what-if gets counts [E][ND] and multi-claim
+// sets [E][SW] of its own in the uninitialised region, which the pack kernel's prologue fills from the snapshot's en_vol_count / en_vol_set like any problem's.
+static int whatifs_open(const ks_dev_problem* base, uint32_t n_nodes, const int32_t* pod_node, const int32_t* node_row, uint32_t n, const uint32_t* cand_off,
+                        const uint32_t* cand, const uint32_t* n_pods, const int64_t* remaining, const ks_whatif_topo* topo, bool volumes, ks_whatif_batch** out) {
   if (out) *out = nullptr;
   if (!base || !out || (n && (!cand_off || !n_pods || !remaining)) || (n_nodes && (!node_row)) || (base->h.P && !pod_node)) return fail(KS_ERR_INVALID, "null argument");
   if (!base->tables_built) return fail(KS_ERR_INVALID, "the snapshot must be resident with its tables built (ks_problem_prepare)");
-  if (base->h.ND || base->h.pod_gid) return fail(KS_ERR_UNSUPPORTED, "what-ifs cannot be derived from a snapshot with volume limits");
+  if ((base->h.ND && !volumes) || base->h.pod_gid) return fail(KS_ERR_UNSUPPORTED, "what-ifs cannot be derived from a snapshot with volume limits");
   const bool with_topo = base->h.G != 0;
   if (with_topo && (!topo || !topo->node_cnt || !topo->node_dom || !topo->node_own || !topo->tot || (base->h.GH && (!topo->extra_tot || (base->h.E && !topo->grph_base))))) return fail(KS_ERR_UNSUPPORTED, "the snapshot has topology groups: their per-node tables (ks_whatif_topo) are needed to derive what-ifs from it");
   if (with_topo && base->h.G > 1024) return fail(KS_ERR_UNSUPPORTED, "derived what-ifs: at most 1024 topology groups");
   const DevProb& bh = base->h; const u32 E = bh.E, M = bh.M, R = bh.R, K = bh.K, TW = bh.TW, C = bh.C, Pb = bh.P;
+  const bool vols = volumes && bh.ND != 0;
   HIPCHK(hipSetDevice(base->device));
   auto b = new ks_whatif_batch(); b->device = base->device; b->n = n;
   struct Guard { ks_whatif_batch* b; bool ok = false; ~Guard() { if (!ok) ks_whatifs_free(b); } } guard{b};
@@ -3124,7 +3129,7 @@ extern "C" int ks_whatifs_open(const ks_dev_problem* base, uint32_t n_nodes, con
   auto take = [&](int region, size_t bytes) { const size_t at = sz[region]; sz[region] += ks_align256(bytes ? bytes : 1); return at; };
   struct Lay { size_t cand_bits, removed, remaining, q, lastlen, lastgen, pod_stage, pod_node, pod_seq, pod_reason, rec, n_tmpl, n_alive, lowi, bstart, order_g, rem_state,
                o_present, o_complement, o_mask, o_gt, o_lt, o_it, o_req, o_reqmask, pp_entry, pp_next, wm, stats, out_counts, unscheduled, pod_gid, round_scratch,
-               t_active, t_count, t_extra, gcnt, g_reg, g_pos, g_active, hcnt, g_hpos, g_hzero; u32 P, NMAX, pp_cap; };
+               t_active, t_count, t_extra, gcnt, g_reg, g_pos, g_active, hcnt, g_hpos, g_hzero, vol_cnt, vol_set; u32 P, NMAX, pp_cap; };
   std::vector<Lay> L(n);
   const size_t pod_node_at = take(0, (size_t)Pb * sizeof(i32));
   const u32 G = bh.G, GH = bh.GH; const size_t GN = (size_t)G * n_nodes;
@@ -3153,6 +3158,7 @@ extern "C" int ks_whatifs_open(const ks_dev_problem* base, uint32_t n_nodes, con
       l.gcnt = take(2, (size_t)G * 64 * 4); l.g_reg = take(2, (size_t)G * 8); l.g_pos = take(2, (size_t)G * 8); l.g_active = take(2, G);
       l.hcnt = take(2, (size_t)GH * NS * 4); l.g_hpos = take(2, (size_t)GH * 4); l.g_hzero = take(2, (size_t)GH * 4);
     }
+    if (vols) { l.vol_cnt = take(2, (size_t)E * bh.ND * 4); l.vol_set = take(2, (size_t)E * bh.SW * 8); }
   }
   const size_t desc_at = take(0, (size_t)n * sizeof(DeriveDesc)), dprob_at = take(0, (size_t)n * sizeof(DevProb)), dstate_at = take(0, (size_t)n * sizeof(DevState));
   const size_t mismatch_at = take(1, 4);
@@ -3201,7 +3207,7 @@ extern "C" int ks_whatifs_open(const ks_dev_problem* base, uint32_t n_nodes, con
                      st.g_hpos = (i32*)(r2 + l.g_hpos); st.g_hzero = (i32*)(r2 + l.g_hzero); }
     st.remaining = (i64*)(r2 + l.rem_state);
     st.pp_entry = (u64*)(r2 + l.pp_entry); st.pp_next = (i32*)(r2 + l.pp_next); st.pp_cap = l.pp_cap;
-    st.vol_pad = 0; st.vol_cnt = nullptr; st.vol_set = nullptr; st.wm = (u32*)(r2 + l.wm);
+    st.vol_pad = 0; st.vol_cnt = vols ? (i32*)(r2 + l.vol_cnt) : nullptr; st.vol_set = vols ? (u64*)(r2 + l.vol_set) : nullptr; st.wm = (u32*)(r2 + l.wm);
     st.stats = (u64*)(r1 + l.stats); st.out_counts = (u32*)(r1 + l.out_counts); st.batch_meta = nullptr; st.unscheduled = (i32*)(r2 + l.unscheduled);
     st.o_present = (u32*)(r2 + l.o_present); st.o_complement = (u32*)(r2 + l.o_complement); st.o_mask = (u64*)(r2 + l.o_mask); st.o_gt = (i32*)(r2 + l.o_gt); st.o_lt = (i32*)(r2 + l.o_lt);
     st.o_it = (i32*)(r2 + l.o_it); st.o_req = (i64*)(r2 + l.o_req); st.o_reqmask = (u32*)(r2 + l.o_reqmask);
@@ -3219,6 +3225,17 @@ extern "C" int ks_whatifs_open(const ks_dev_problem* base, uint32_t n_nodes, con
   HIPCHK(hipStreamSynchronize(b->stream)); HIPCHK(hipGetLastError());
   if (mismatch) return fail(KS_ERR_INVALID, "n_pods does not match the pods bound to the candidate nodes");
   guard.ok = true; *out = b; return KS_OK;
+}
+extern "C" int ks_whatifs_open(const ks_dev_problem* base, uint32_t n_nodes, const int32_t* pod_node, const int32_t* node_row, uint32_t n, const uint32_t* cand_off,
+                               const uint32_t* cand, const uint32_t* n_pods, const int64_t* remaining, const ks_whatif_topo* topo, ks_whatif_batch** out) {
+  return whatifs_open(base, n_nodes, pod_node, node_row, n, cand_off, cand, n_pods, remaining, topo, false, out);
+}
+extern "C" int ks_whatifs_open_ex(const ks_dev_problem* base, uint32_t n_nodes, const int32_t* pod_node, const int32_t* node_row, uint32_t n, const uint32_t* cand_off,
+                                  const uint32_t* cand, const uint32_t* n_pods, const int64_t* remaining, const ks_whatifs_options* opt, ks_whatif_batch** out) {
+  if (out) *out = nullptr;
+  if (!opt) return fail(KS_ERR_INVALID, "null argument");
+  if (opt->flags & ~KS_WHATIFS_VOLUMES) return fail(KS_ERR_INVALID, "unknown KS_WHATIFS_* flag");
+  return whatifs_open(base, n_nodes, pod_node, node_row, n, cand_off, cand, n_pods, remaining, opt->topo, (opt->flags & KS_WHATIFS_VOLUMES) != 0, out);
 }
 // the snapshot pods behind what-if i's batch, in ITS pod order (= the snapshot's queue order): out[n_pods]
 extern "C" int ks_whatifs_pod_ids(ks_whatif_batch* b, uint32_t i, uint32_t* out) {

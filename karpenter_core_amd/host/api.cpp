@@ -439,7 +439,10 @@ int ksh_open_whatifs_derived(void* parsed, uint32_t flags, uint32_t n, const uin
       }
     }
     lap("masks / remaining (host)");
-    rc = ks_whatifs_open((const ks_dev_problem*)D->base_dev.get(), in.n_nodes, P->sb_pod_node.data(), in.node_row, n, cand_off, cand, npods.data(), rem.data(), in.topo, &D->b);
+    if (in.volumes) {      // (KSH_DERIVE_VOLUMES: the snapshot was flattened with the candidate-independent claim partition; every what-if carries its own volume state)
+      ks_whatifs_options opt{}; opt.topo = in.topo; opt.flags = KS_WHATIFS_VOLUMES;
+      rc = ks_whatifs_open_ex((const ks_dev_problem*)D->base_dev.get(), in.n_nodes, P->sb_pod_node.data(), in.node_row, n, cand_off, cand, npods.data(), rem.data(), &opt, &D->b);
+    } else rc = ks_whatifs_open((const ks_dev_problem*)D->base_dev.get(), in.n_nodes, P->sb_pod_node.data(), in.node_row, n, cand_off, cand, npods.data(), rem.data(), in.topo, &D->b);
     if (rc != KS_OK) return set_err(rc, ks_last_error());
     lap("ks_whatifs_open (device)");
     ks_dev_problem* const* views = ks_whatifs_problems(D->b);
@@ -455,6 +458,8 @@ int ksh_open_whatifs_derived(void* parsed, uint32_t flags, uint32_t n, const uin
   } catch (const ksh::Unsupported& e) { return set_err(KS_ERR_UNSUPPORTED, e.what());
   } catch (const std::exception& e) { return set_err(KS_ERR_INVALID, e.what()); }
 }
+
+uint64_t ksh_whatifs_arena_bytes(void* hv) { const Handle* h = (const Handle*)hv; return h && h->delta ? ks_whatifs_arena_bytes(h->delta->b) : 0; }
 
 // CPU self-check of what ksh_open_whatifs_derived would derive on the device for ONE candidate set (kshost.h).
 int ksh_check_whatif_derivation(void* parsed, uint32_t flags, const uint32_t* cand, uint32_t ncand, const int32_t* pod_node) {

@@ -598,6 +598,9 @@ struct Builder {
   std::map<std::string, int> vol_driver_id;
   std::unordered_map<std::string, uint32_t> vol_ref, vol_shared;
   bool pods_have_volumes = false; int blocked_taint = -1;
+  // A snapshot flattened for what-ifs derived with their volumes (KSH_DERIVE_VOLUMES): the node every pod is bound to (-1: none).  The claims are then
+  // partitioned once for every candidate set (collect_solo_volumes) instead of by this batch; null for every other flattening.
+  const int32_t* solo_pod_node = nullptr;
   static std::string vol_pair(const ksp::Volume& v) { return v.driver + '\1' + v.pvc; }
   void collect_volumes() {
     if (base && !base->any_volume_limits) { for (auto* p : podp) if (p->volume_error) { pods_have_volumes = true; break; } return; }      // no node limits a volume: only a failed lookup matters
@@ -607,6 +610,7 @@ struct Builder {
       parallel_chunks(podp.size(), [&](size_t b, size_t e, uint32_t) { for (size_t i = b; i < e && !any.load(std::memory_order_relaxed); ++i) if (podp[i]->volume_error || !podp[i]->volumes.empty()) any = true; }, 16384);
       pods_have_volumes = any; }
     if (!pods_have_volumes || vol_driver_id.empty()) return;
+    if (solo_pod_node) { collect_solo_volumes(); return; }
     std::unordered_set<std::string> on_node;
     for (size_t i = 0; i < pr.nodes.size(); ++i) if (node_in_state(i) && pr.nodes[i].owned()) for (auto& v : pr.nodes[i].volumes) if (vol_driver_id.count(v.driver)) on_node.insert(vol_pair(v));
     std::vector<std::string> mine;
@@ -620,6 +624,35 @@ struct Builder {
       if ((vol_ref[s2] >= 2 || on_node.count(s2)) && !vol_shared.count(s2)) { const uint32_t id = (uint32_t)vol_shared.size(); vol_shared.emplace(std::move(s2), id); }
     }
     if (vol_shared.size() >= (1u << 24)) throw Unsupported("more than 16M shared volume claims");
+  }
+  // The partition of a snapshot's claims that holds for EVERY candidate set.  A claim (of a limited driver) is SOLO when exactly one bound
+  // pod mounts it and no state node lists it but the node that pod is bound to: in a what-if it is either on a removed node -- its pod is in the batch and
+  // no other pod or remaining node has it, a unique claim -- or on a staying node, where no pod of the batch names it.  Either way a count is exact.  Every
+  // other claim a bound pod mounts is MULTI: an id over the snapshot (vol_shared) and a bit in the per-node sets.  vol_entries / encode_volumes then read
+  // vol_shared as always.  Claims no bound pod mounts only count on their nodes.
+  void collect_solo_volumes() {
+    if (lite || podp.size() != pr.pods.size()) throw ksp::Error("a snapshot flattened for derived volumes must hold its own pods");
+    struct Ref { uint32_t pods = 0; int32_t node = -1; };
+    std::unordered_map<std::string, Ref> ref; std::vector<std::string> mine;
+    auto claims_of = [&](const Pod& p) { mine.clear(); for (auto& v : p.volumes) if (vol_driver_id.count(v.driver)) mine.push_back(vol_pair(v)); std::sort(mine.begin(), mine.end()); mine.erase(std::unique(mine.begin(), mine.end()), mine.end()); };
+    for (size_t i = 0; i < podp.size(); ++i) {
+      if (solo_pod_node[i] < 0) continue;      // (a pod bound nowhere is in no batch)
+      claims_of(*podp[i]); for (auto& s2 : mine) { Ref& r = ref[s2]; ++r.pods; r.node = solo_pod_node[i]; }
+    }
+    std::unordered_map<std::string, int32_t> listed;      // claim -> the one state node that lists it, -2 for several
+    for (size_t i = 0; i < pr.nodes.size(); ++i) if (node_in_state(i) && pr.nodes[i].owned()) for (auto& v : pr.nodes[i].volumes) if (vol_driver_id.count(v.driver)) {
+      auto it = listed.emplace(vol_pair(v), (int32_t)i); if (!it.second && it.first->second != (int32_t)i) it.first->second = -2;
+    }
+    for (size_t i = 0; i < podp.size(); ++i) {
+      if (solo_pod_node[i] < 0) continue;
+      claims_of(*podp[i]);
+      for (auto& s2 : mine) {
+        const Ref& r = ref.at(s2); auto l = listed.find(s2);
+        const bool solo = r.pods == 1 && (l == listed.end() || l->second == r.node);
+        if (!solo && !vol_shared.count(s2)) { const uint32_t id = (uint32_t)vol_shared.size(); vol_shared.emplace(s2, id); }
+      }
+    }
+    if (vol_shared.size() >= (1u << 24)) throw Unsupported("more than 16M multi volume claims");
   }
   // What ExistingNode.Add needs of a pod's volumes: tagged words ordered by driver (ks_problem.vol_list).
   std::vector<uint32_t> vol_entries(const Pod& p) const {
@@ -1494,6 +1527,7 @@ std::shared_ptr<const ksp::PodBatch> ingest_pod_blocks(const ksh_pod_block* bloc
 
 struct SnapshotBase {
   bool continued = false;      // the flattening continued the one before (ksh_env_apply) instead of starting over
+  bool volumes = false;        // KSH_DERIVE_VOLUMES: the claims are partitioned for every candidate set at once (Builder::collect_solo_volumes)
   std::shared_ptr<const ksp::Problem> snapshot; std::shared_ptr<Encoded> enc; std::unique_ptr<Builder> builder;
   std::vector<std::vector<uint32_t>> by_node;      // pods bound to each node, in pod order
   std::vector<int32_t> node_row, node_tmpl; std::vector<int64_t> node_cap; bool delta_ok = false; std::string delta_why;      // (delta_inputs)
@@ -1584,14 +1618,16 @@ static std::string build_topo_tables(SnapshotBase& sb, const int32_t* pod_node) 
 }
 std::shared_ptr<const SnapshotBase> make_snapshot_base(std::shared_ptr<const ksp::Problem> snapshot, const int32_t* pod_node, uint32_t flags, const SnapshotBase* before) {
   auto sb = std::make_shared<SnapshotBase>(); sb->snapshot = snapshot;
+  sb->volumes = (flags & KSH_DERIVE_VOLUMES) != 0; flags &= ~KSH_DERIVE_VOLUMES;      // (a library flag: the flat problem never carries it)
   sb->by_node.resize(snapshot->nodes.size());
   // pod_node[i] = -1: a pod that is bound nowhere any more (ksh_env_apply keeps it in place: nothing that points into the problem moves); it is in no what-if's batch
   for (size_t i = 0; i < snapshot->pods.size(); ++i) { if (pod_node[i] < 0) continue; if ((size_t)pod_node[i] >= snapshot->nodes.size()) throw ksp::Error("pod_node out of range"); sb->by_node[pod_node[i]].push_back((uint32_t)i); }
   sb->enc = std::make_shared<Encoded>(); sb->enc->src = snapshot;
   sb->builder = std::make_unique<Builder>(*sb->enc, flags); sb->builder->keep_warm_state = true;
-  if (before && before->snapshot.get() == snapshot.get() && !getenv("KSH_NO_WARM_SNAPSHOT")) sb->builder->prev = before->builder.get();
+  if (before && before->snapshot.get() == snapshot.get() && before->volumes == sb->volumes && !getenv("KSH_NO_WARM_SNAPSHOT")) sb->builder->prev = before->builder.get();
+  if (sb->volumes) sb->builder->solo_pod_node = pod_node;
   sb->builder->run(); sb->continued = sb->builder->warm;
-  sb->builder->prev = nullptr;      // (this flattening now stands alone: `before` may go)
+  sb->builder->prev = nullptr; sb->builder->solo_pod_node = nullptr;      // (this flattening now stands alone: `before` and the caller's bindings may go)
   {   // what deriving what-ifs on the device needs (delta_inputs)
     const Builder& b = *sb->builder; const Encoded& E = *sb->enc; const uint32_t R = b.R, M = (uint32_t)E.templates.size(); const size_t NN = snapshot->nodes.size();
     sb->node_row.assign(b.base_existing_of.begin(), b.base_existing_of.end()); sb->node_row.resize(NN, -1);
@@ -1604,7 +1640,8 @@ std::shared_ptr<const SnapshotBase> make_snapshot_base(std::shared_ptr<const ksp
       }
     }
     sb->delta_ok = true;
-    if (b.any_volume_limits || b.pods_have_volumes) { sb->delta_ok = false; sb->delta_why = "volume limits / claims: the shared-claim partition depends on the candidate set"; }
+    if ((b.any_volume_limits || b.pods_have_volumes) && !sb->volumes) { sb->delta_ok = false; sb->delta_why = "volume limits / claims: the shared-claim partition depends on the candidate set"; }
+    if (sb->volumes && (size_t)E.prob.E * (4ull * E.prob.ND + 8ull * E.prob.SW) > (64ull << 20)) { sb->delta_ok = false; sb->delta_why = "the per-what-if volume state (counts and multi-claim sets of every node) would exceed 64 MiB"; }
     if (sb->delta_ok && !b.groups.empty()) { const std::string why = build_topo_tables(*sb, pod_node); if (!why.empty()) { sb->delta_ok = false; sb->delta_why = why; } }
   }
   return sb;
@@ -1621,9 +1658,11 @@ uint64_t snapshot_fingerprint(const SnapshotBase& sb) {
 }
 DeltaInputs delta_inputs(const SnapshotBase& sb) {
   DeltaInputs d; d.base = sb.enc; d.n_nodes = (uint32_t)sb.snapshot->nodes.size(); d.node_row = sb.node_row.data(); d.by_node = &sb.by_node; d.pod_rank = sb.builder->pod_rank.data();
-  d.node_cap = sb.node_cap.data(); d.node_tmpl = sb.node_tmpl.data(); d.eligible = sb.delta_ok; d.why = sb.delta_why; d.topo = sb.has_topo ? &sb.topo : nullptr; return d;
+  d.node_cap = sb.node_cap.data(); d.node_tmpl = sb.node_tmpl.data(); d.eligible = sb.delta_ok; d.why = sb.delta_why; d.topo = sb.has_topo ? &sb.topo : nullptr;
+  d.volumes = sb.volumes && sb.enc->prob.ND != 0; return d;
 }
 std::unique_ptr<Encoded> encode_whatif(const SnapshotBase& sb, const uint32_t* cand, uint32_t ncand, uint32_t flags) {
+  flags &= ~KSH_DERIVE_VOLUMES;
   auto e = std::make_unique<Encoded>(); e->src = sb.snapshot; e->shared = sb.enc;
   std::vector<uint8_t> removed(sb.snapshot->nodes.size(), 0);
   Builder b(*e, flags); b.base = sb.builder.get(); b.removed = &removed;
@@ -1632,11 +1671,73 @@ std::unique_ptr<Encoded> encode_whatif(const SnapshotBase& sb, const uint32_t* c
   return e;
 }
 
+// (KSH_DERIVE_VOLUMES) The volume state a derived what-if starts from -- the snapshot's rows: counts and limits per driver, multi-claim sets -- restated from
+// the node objects and held against the what-if flattened by itself (its own, candidate-dependent partition), and what the volume test (ksolve.hip
+// volumes_walk) makes of every pod of the batch on every node that stays: admitted or not, and how many claims it adds per driver.  "" or the first difference.
+static std::string check_derived_volumes(const SnapshotBase& sb, const Builder& wb, const Encoded& EW) {
+  const Builder& bb = *sb.builder; const Encoded& EB = *sb.enc; const ksp::Problem& pr = *sb.snapshot;
+  const uint32_t NDb = EB.prob.ND, SWb = EB.prob.SW, NDw = EW.prob.ND, SWw = EW.prob.SW;
+  std::vector<int> w_of_b(NDb, -1); std::vector<const std::string*> driver_name(NDb, nullptr);
+  for (auto& kv : bb.vol_driver_id) if ((uint32_t)kv.second < NDb) driver_name[kv.second] = &kv.first;
+  for (auto& kv : wb.vol_driver_id) {
+    auto it = bb.vol_driver_id.find(kv.first);
+    if (it == bb.vol_driver_id.end() || (uint32_t)it->second >= NDb) { if (NDw) return "the what-if limits a driver the snapshot's flattening does not track: " + kv.first; continue; }
+    if ((uint32_t)kv.second < NDw) w_of_b[it->second] = kv.second;
+  }
+  auto where = [&](uint32_t ew) { return " (node " + pr.nodes[EW.existing[ew]].name + ")"; };
+  for (uint32_t ew = 0; ew < EW.prob.E; ++ew) {
+    const size_t i = (size_t)EW.existing[ew]; const int32_t eb = sb.node_row[i]; const ksp::StateNode& n = pr.nodes[i];
+    if (eb < 0) return "a node that stays has no row in the snapshot" + where(ew);
+    std::vector<std::set<std::string>> claims(NDb); std::vector<uint64_t> set(SWb, 0);
+    for (auto& v : n.volumes) { auto d = bb.vol_driver_id.find(v.driver); if (d == bb.vol_driver_id.end() || (uint32_t)d->second >= NDb) continue; claims[d->second].insert(v.pvc);
+      auto m = bb.vol_shared.find(Builder::vol_pair(v)); if (m != bb.vol_shared.end()) set[m->second >> 6] |= 1ull << (m->second & 63u); }
+    for (uint32_t d = 0; d < NDb; ++d) {
+      int32_t lim = INT32_MAX; for (auto& kv : n.volume_limits) if (kv.first == *driver_name[d]) lim = (int32_t)kv.second;      // (the last entry, as encode_volumes reads them)
+      const int32_t cb = EB.en_vol_count[(size_t)eb * NDb + d], lb = EB.en_vol_limit[(size_t)eb * NDb + d];
+      if (cb != (int32_t)claims[d].size()) return "volume count of driver " + *driver_name[d] + " differs: " + std::to_string(cb) + " in the snapshot, " + std::to_string(claims[d].size()) + " listed" + where(ew);
+      if (lb != lim) return "volume limit of driver " + *driver_name[d] + " differs" + where(ew);
+      const int w = w_of_b[d];
+      if (w < 0) { if (lb != INT32_MAX && NDw) return "the snapshot limits driver " + *driver_name[d] + " on a node the what-if does not" + where(ew); continue; }
+      if (EW.en_vol_count[(size_t)ew * NDw + w] != cb || EW.en_vol_limit[(size_t)ew * NDw + w] != lb) return "volume count / limit of driver " + *driver_name[d] + " differs from the what-if's" + where(ew);
+    }
+    for (uint32_t x = 0; x < SWb; ++x) if (EB.en_vol_set[(size_t)eb * SWb + x] != set[x]) return "multi-claim set word " + std::to_string(x) + " differs from the claims the node lists" + where(ew);
+  }
+  // the volume test, pod by pod, node by node: kernel arithmetic on both flattenings
+  auto walk = [](const std::vector<uint32_t>& vl, uint32_t off, uint32_t end, const int32_t* cnt, const int32_t* lim, const uint64_t* set, uint32_t ND, std::vector<int64_t>& add) {
+    add.assign(ND, 0); std::vector<uint8_t> named(ND, 0);
+    for (uint32_t k = off; k < end; ++k) {
+      const uint32_t e = vl[k]; if (e == 0xFFFFFFFFu) return true;
+      const uint32_t d = (e >> 24) & 63u; if (d >= ND) return true;
+      named[d] = 1;
+      if (e >> 31) add[d] += e & 0xFFFFFFu; else { const uint32_t id = e & 0xFFFFFFu; if (!((set[id >> 6] >> (id & 63u)) & 1ull)) add[d] += 1; }
+    }
+    for (uint32_t d = 0; d < ND; ++d) if (named[d] && (int64_t)cnt[d] + add[d] > (int64_t)lim[d]) return true;
+    return false;
+  };
+  const Pod* p0 = pr.pods.data(); std::vector<int64_t> ab, aw;
+  for (size_t k = 0; k < wb.podp.size(); ++k) {
+    const size_t gp = (size_t)(wb.podp[k] - p0);
+    const uint32_t cbl = EB.stage_cls[EB.pod_stage_off[gp]], cwl = EW.stage_cls[EW.pod_stage_off[k]];
+    const uint32_t b0 = EB.cls_vol_off[cbl], b1 = EB.cls_vol_off[cbl + 1], w0 = EW.cls_vol_off[cwl], w1 = EW.cls_vol_off[cwl + 1];
+    if (b0 == b1 && w0 == w1) continue;
+    for (uint32_t ew = 0; ew < EW.prob.E; ++ew) {
+      const int32_t eb = sb.node_row[EW.existing[ew]];
+      const bool rb = walk(EB.vol_list, b0, b1, &EB.en_vol_count[(size_t)eb * NDb], &EB.en_vol_limit[(size_t)eb * NDb], SWb ? &EB.en_vol_set[(size_t)eb * SWb] : nullptr, NDb, ab);
+      const bool rw = NDw ? walk(EW.vol_list, w0, w1, &EW.en_vol_count[(size_t)ew * NDw], &EW.en_vol_limit[(size_t)ew * NDw], SWw ? &EW.en_vol_set[(size_t)ew * SWw] : nullptr, NDw, aw)
+                          : (w0 != w1 && EW.vol_list[w0] == 0xFFFFFFFFu);
+      if (rb != rw) return "pod " + p0[gp].uid + ": the volume test " + (rb ? "refuses" : "admits") + " it in the derivation, " + (rw ? "refuses" : "admits") + " it in the what-if" + where(ew);
+      if (!rb && NDw) for (uint32_t d = 0; d < NDb; ++d) if (w_of_b[d] >= 0 && ab[d] != aw[w_of_b[d]]) return "pod " + p0[gp].uid + " adds " + std::to_string(ab[d]) + " claims of driver " + *driver_name[d] + " in the derivation, " + std::to_string(aw[w_of_b[d]]) + " in the what-if" + where(ew);
+    }
+  }
+  return "";
+}
+
 // CPU self-check of the device derivation (tests): what ks_derive_topology computes from the per-node tables for ONE candidate set -- restated here in
 // plain loops -- against the what-if flattened by itself (encode_whatif), group by group (matched by identity), domain by domain, row by row.  "" or the
 // first difference.  Not on any solving path.
 std::string check_derived_topology(const SnapshotBase& sb, const uint32_t* cand, uint32_t ncand, uint32_t flags) {
   if (!sb.delta_ok) return "not derivable: " + sb.delta_why;
+  flags &= ~KSH_DERIVE_VOLUMES;
   const Builder& bb = *sb.builder; const Encoded& EB = *sb.enc; const uint32_t G = EB.prob.G, GH = EB.prob.GH, NE = EB.prob.E, NT = EB.prob.n_topologies, GW = (G + 63) / 64;
   const size_t NN = sb.snapshot->nodes.size();
   auto e = std::make_unique<Encoded>(); e->src = sb.snapshot; e->shared = sb.enc;
@@ -1645,6 +1746,7 @@ std::string check_derived_topology(const SnapshotBase& sb, const uint32_t* cand,
   for (uint32_t i = 0; i < ncand; ++i) { if (cand[i] >= NN) throw ksp::Error("candidate node out of range"); removed[cand[i]] = 1; for (uint32_t p : sb.by_node[cand[i]]) wb.podp.push_back(&sb.snapshot->pods[p]); }
   wb.run();
   const Encoded& EW = *e;
+  if (sb.volumes && EB.prob.ND) { const std::string why = check_derived_volumes(sb, wb, EW); if (!why.empty()) return why; }
   if (!G) return EW.prob.G ? "the what-if has groups the snapshot lacks" : "";
   // ---- the derivation (ksolve.hip ks_derive_topology + ks_host_count0) ----
   std::vector<uint8_t> active(G, 0); std::vector<int32_t> count((size_t)G * 64, -1), extra(GH, 0); std::vector<uint8_t> exists(G, 1);

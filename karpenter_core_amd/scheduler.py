@@ -29,6 +29,7 @@ _LIBS = None
 
 KS_OK, KS_ERR_INVALID, KS_ERR_UNSUPPORTED, KS_ERR_DEVICE, KS_ERR_CAPACITY = 0, -1, -2, -3, -4
 KS_FLAG_SIMULATION, KS_FLAG_STATS, KS_FLAG_NO_RR, KS_FLAG_ONE_WAVE, KS_FLAG_NO_LEAN = 1, 2, 4, 8, 16
+KSH_DERIVE_VOLUMES = 1 << 16      # kshost.h: derive what-ifs over snapshots with CSI volume limits / claims too (opt-in)
 
 
 class KSolveError(RuntimeError):
@@ -337,15 +338,15 @@ class ParsedProblem:
             raise KSolveError(rc, kh.ksh_last_error().decode())
         return out[:n_pods.value], int(n_nodes.value)
 
-    def snapshot_fingerprint(self, pod_node: Optional[Sequence[int]] = None, cold: bool = False) -> int:
+    def snapshot_fingerprint(self, pod_node: Optional[Sequence[int]] = None, cold: bool = False, volumes: bool = False) -> int:
         """Hash of the snapshot's flattening (flat problem + the tables the device derivation reads); `cold`: of one made from scratch (tests: a flattening
-        continued after `apply` must equal it)."""
+        continued after `apply` must equal it); `volumes`: of the flattening derived what-ifs with volumes use (KSH_DERIVE_VOLUMES)."""
         import numpy as np
         kh = libs()[1]
         kh.ksh_snapshot_fingerprint.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64)]
         pn = None if pod_node is None else np.ascontiguousarray(np.asarray(pod_node, dtype=np.int32))
         out = ctypes.c_uint64()
-        rc = kh.ksh_snapshot_fingerprint(self._p, None if pn is None or pn.size == 0 else pn.ctypes.data, 0, 1 if cold else 0, ctypes.byref(out))
+        rc = kh.ksh_snapshot_fingerprint(self._p, None if pn is None or pn.size == 0 else pn.ctypes.data, KSH_DERIVE_VOLUMES if volumes else 0, 1 if cold else 0, ctypes.byref(out))
         if rc != KS_OK:
             raise KSolveError(rc, kh.ksh_last_error().decode())
         return int(out.value)
@@ -448,7 +449,8 @@ def solve_from_batch(env: ParsedProblem, batch: PodBatch, device: int = 0, stats
     return fp, dict(zip(TIMING_KEYS, [float(x) for x in ms]))
 
 
-def open_whatifs(snapshot, pod_node: Sequence[int], candidate_sets: Sequence[Sequence[int]], threads: int = 0, stats: bool = False, derive=None, device: int = 0) -> List[FlatProblem]:
+def open_whatifs(snapshot, pod_node: Sequence[int], candidate_sets: Sequence[Sequence[int]], threads: int = 0, stats: bool = False, derive=None, device: int = 0,
+                 volumes: bool = False) -> List[FlatProblem]:
     """Flatten N consolidation what-ifs over one cluster snapshot natively (simulateScheduling, deprovisioning/helpers.go:42-115):
     `snapshot` (a `Problem`, or a `ParsedProblem` already held as objects) lists every state node and, as its pod batch, every bound pod
     (full spec); pod_node[i] = node index of pod i.  What-if w removes candidate_sets[w] from the state nodes and makes their pods
@@ -471,10 +473,11 @@ def open_whatifs(snapshot, pod_node: Sequence[int], candidate_sets: Sequence[Seq
     hs = (ctypes.c_void_p * max(1, n))()
     # derive: None = derive the what-ifs on the device when the snapshot allows it (a ParsedProblem without topology terms / volume limits), else flatten
     # them one by one on the host; True = derive or raise; False = always flatten on the host.  Derived what-ifs are resident on `device` at once.
+    # volumes: opt in to deriving snapshots with CSI volume limits / claims too (kshost.h KSH_DERIVE_VOLUMES); the host route is the same either way.
     if derive is not False and not stats and n:
         if not isinstance(snapshot, ParsedProblem):
             snapshot = ParsedProblem(snapshot)       # (the handles keep what they need of it alive)
-        rc = kh.ksh_open_whatifs_derived(snapshot._p, 0, n, c_off, c_cand, c_pn, device, hs)
+        rc = kh.ksh_open_whatifs_derived(snapshot._p, KSH_DERIVE_VOLUMES if volumes else 0, n, c_off, c_cand, c_pn, device, hs)
         if rc == KS_OK:
             return [FlatProblem(None, _handle=ctypes.c_void_p(hs[i])) for i in range(n)]
         if derive is True or rc not in (KS_ERR_UNSUPPORTED, KS_ERR_DEVICE):
@@ -491,15 +494,16 @@ def open_whatifs(snapshot, pod_node: Sequence[int], candidate_sets: Sequence[Seq
     return [FlatProblem(None, _handle=ctypes.c_void_p(hs[i])) for i in range(n)]
 
 
-def check_whatif_derivation(snapshot: "ParsedProblem", pod_node: Sequence[int], candidates: Sequence[int]) -> None:
+def check_whatif_derivation(snapshot: "ParsedProblem", pod_node: Sequence[int], candidates: Sequence[int], volumes: bool = False) -> None:
     """Diagnostic, no GPU needed (kshost.h `ksh_check_whatif_derivation`): what the device would derive for this candidate set -- group activity, domain
-    counts, hostname rows -- restated on the host and compared with the what-if flattened by itself.  Raises KSolveError with the first difference."""
+    counts, hostname rows; with `volumes`, the volume state of every node that stays and the volume test of every pod of the batch on it -- restated on
+    the host and compared with the what-if flattened by itself.  Raises KSolveError with the first difference."""
     import numpy as np
     kh = libs()[1]
     cand = np.ascontiguousarray(np.asarray(list(candidates) or [0], dtype=np.uint32))
     pn = None if pod_node is None else (np.ascontiguousarray(np.asarray(pod_node, dtype=np.int32)) if len(pod_node) else np.zeros(1, dtype=np.int32))
     kh.ksh_check_whatif_derivation.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint32, ctypes.POINTER(ctypes.c_int32)]
-    rc = kh.ksh_check_whatif_derivation(snapshot._p, 0, cand.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), len(candidates), None if pn is None else pn.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)))
+    rc = kh.ksh_check_whatif_derivation(snapshot._p, KSH_DERIVE_VOLUMES if volumes else 0, cand.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), len(candidates), None if pn is None else pn.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)))
     if rc != KS_OK:
         raise KSolveError(rc, kh.ksh_last_error().decode())
 

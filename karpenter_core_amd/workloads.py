@@ -262,6 +262,66 @@ def cluster_snapshot(existing: int = 2048, sizes: int = 50, seed: int = 45, spar
     return its, prov, nodes, bound
 
 
+EBS_DRIVER, EFS_DRIVER, FSX_DRIVER = "ebs.csi.aws.com", "efs.csi.aws.com", "fsx.csi.aws.com"
+
+
+def volume_snapshot(existing: int = 2048, sizes: int = 50, seed: int = 45, spare_pod_slots: int = -1, unowned: bool = True):
+    """`cluster_snapshot` decorated like an EKS cluster with CSI drivers (state/cluster.go:292-304 VolumeLimits, volumeusage.go:102-143):
+      - every owned node has a CSINode limit for the EBS driver (25 / 27 / 39; about one in six 2-4, so that limits bind), about a third one for EFS too;
+        the FSx driver is mounted but no node limits it;
+      - StatefulSet-like pods with 1-2 private EBS claims, RWX claims (EFS or EBS) mounted by pods on several nodes, a claim shared by two pods of one node,
+        a few pods whose volume lookup failed (`volume_error`), and a few nodes already over one of their limits;
+      - `unowned`: one more node, no provisioner owns it (index `existing`: no config #4 candidate set names it), whose pods mount claims only they mount and
+        one of the RWX claims.
+    A node's volume usage (`StateNode.volumes`) lists the claims of its bound pods, one entry per pod that mounts it (state/node.go:161-182 adds and removes
+    per pod).  Returns (instance_types, provisioner, nodes, per-node bound pods) like `cluster_snapshot`."""
+    from .model import Volume
+    its, prov, nodes, bound = cluster_snapshot(existing, sizes, seed, spare_pod_slots)
+    decorate_volumes(nodes, bound, np.random.RandomState(seed + 7000))
+    if unowned and nodes:
+        name = "unowned-0"
+        pods = []
+        for i, p in enumerate(bound[0][:4]):
+            q = dataclasses.replace(p, uid=f"unowned-pod-{i}", volume_error=False,
+                                    volumes=[Volume(EBS_DRIVER, f"default/orphan-{i}")] + ([Volume(EFS_DRIVER, "default/rwx-0000")] if i == 0 else []))
+            pods.append(q)
+        nodes.append(StateNode(name=name, labels={LABEL_ZONE: nodes[0].labels[LABEL_ZONE], LABEL_HOSTNAME: name}, volume_limits={EBS_DRIVER: 25},
+                               volumes=[v for p in pods for v in p.volumes]))
+        bound.append(pods)
+    return its, prov, nodes, bound
+
+
+def decorate_volumes(nodes, bound, rs):
+    """`volume_snapshot`'s limits and claims on the owned nodes `nodes` and their pods `bound` (in place, drawn from the RandomState `rs`)."""
+    from .model import Volume
+    n_rwx = max(2, len(nodes) // 16)
+    sts = 0
+    for e, (n, pods) in enumerate(zip(nodes, bound)):
+        n.volume_limits = {EBS_DRIVER: int(rs.choice([25, 27, 39])) if rs.rand() >= 0.16 else int(rs.randint(2, 5))}
+        if rs.rand() < 0.33:
+            n.volume_limits[EFS_DRIVER] = int(rs.randint(3, 9))
+        for p in pods:
+            r = rs.rand()
+            if r < 0.25:
+                p.volumes = [Volume(EBS_DRIVER, f"default/data-sts-{sts:06d}-{k}") for k in range(1 + int(rs.rand() < 0.4))]
+                sts += 1
+            elif r < 0.32:
+                p.volumes = [Volume(EFS_DRIVER if rs.rand() < 0.6 else EBS_DRIVER, f"default/rwx-{int(rs.randint(n_rwx)):04d}")]
+            elif r < 0.35:
+                p.volumes = [Volume(FSX_DRIVER, f"default/scratch-{int(rs.randint(n_rwx)):04d}")]
+            elif r < 0.36:
+                p.volume_error = True
+        if len(pods) >= 2 and rs.rand() < 0.2:
+            pair = Volume(EBS_DRIVER, f"default/pair-{e:05d}")
+            pods[0].volumes = pods[0].volumes + [pair]
+            pods[1].volumes = pods[1].volumes + [pair]
+        n.volumes = [v for p in pods for v in p.volumes]
+        if rs.rand() < 0.03:
+            ebs = len({v.pvc_id for v in n.volumes if v.driver == EBS_DRIVER})
+            if ebs:
+                n.volume_limits[EBS_DRIVER] = ebs - 1
+
+
 def whatif(its, prov, nodes, bound, candidates: List[int], with_cluster_pods: bool = True) -> Problem:
     """simulateScheduling (deprovisioning/helpers.go:42-115): candidate nodes leave the state-node list,
     their pods become the pending batch; the cluster still holds the bound pods (excluded by UID,
