@@ -203,6 +203,31 @@ int ksh_check_whatif_derivation(void* parsed_snapshot, uint32_t flags, const uin
  * snapshot; handles opened before the call keep what they were opened with.  KS_ERR_INVALID "spare room ... used up": the snapshot was parsed with room for a
  * quarter more nodes / pods (at least 256 / 4096); ingest it again. */
 int ksh_env_apply(void* parsed_snapshot, const int32_t* pod_node /* first call: the bindings; later NULL */, const char* ksd_text, size_t len, uint32_t info[4] /* or NULL */);
+/* ---- the same door without the text: the events as ONE stream of u32 words over ONE string table (conventions of ksh_env_block; grammar in
+ * karpenter_core_amd/host/kspb.hpp, DeltaReader).  Per event a kind word, then its body: KSH_EVENT_NODE_ADD the state-node record of ksh_env_block, KSH_EVENT_NODE_REMOVE
+ * the node's name, KSH_EVENT_BIND the node's name + the pod (word count, spec record of ksh_pod_block, uid, creationTimestamp as two words), KSH_EVENT_UNBIND the pod's uid.
+ * A cgo caller fills it with the writer it has for the other two doors; quantities are int64 milli-units, nothing is quoted or printed.  Everything after the decoding is
+ * ksh_env_apply's: same patching, same info[0..3], same bindings held by the library, same error texts for an event that cannot be applied (the events before it stay,
+ * info[0] counts them).  Text and binary calls may be mixed on one snapshot in any order.
+ * Stricter than the text door: the block is decoded completely before the first event is applied, so a MALFORMED block -- string id >= n_strings, offsets not ascending or
+ * beyond str_bytes_len, a record running past n_words, words left over, an unknown kind, n_events not matching the stream -- is KS_ERR_INVALID with the event's index in
+ * ksh_last_error() and NOTHING applied.
+ * flags: 0, or KSH_APPLY_TRACK_CLUSTER_PODS -- BIND / UNBIND are mirrored into the snapshot's cluster pods (what countDomains lists, topology.go:231-276) whatever the
+ * snapshot held at the first call.  Without it the door does what ksh_env_apply does: it mirrors iff the snapshot had cluster pods when the first event call was made, so a
+ * topology-tracking snapshot that starts with no bound pod must pass the flag.  Any other bit: KS_ERR_INVALID. */
+#define KSH_EVENT_NODE_ADD 1u
+#define KSH_EVENT_NODE_REMOVE 2u
+#define KSH_EVENT_BIND 3u
+#define KSH_EVENT_UNBIND 4u
+#define KSH_APPLY_TRACK_CLUSTER_PODS 1u
+typedef struct ksh_delta_block {
+  uint32_t n_events, n_strings, n_words;
+  const uint32_t* str_off;      /* [n_strings + 1] byte offsets into str_bytes */
+  const char* str_bytes;
+  const uint32_t* words;        /* [n_words] */
+  uint64_t str_bytes_len;       /* bytes behind str_bytes: str_off[n_strings] must not reach beyond */
+} ksh_delta_block;
+int ksh_env_apply_block(void* parsed_snapshot, const int32_t* pod_node /* first call: the bindings; later NULL */, const ksh_delta_block* delta, uint32_t flags, uint32_t info[4] /* or NULL */);
 int ksh_snapshot_bindings(void* parsed_snapshot, int32_t* out /* [cap] or NULL */, uint32_t cap, uint32_t* n_pods /* or NULL */, uint32_t* n_nodes /* or NULL */);
 /* Diagnostic (tests): FNV-1a over the snapshot's flattening -- the flat problem and the per-node tables behind the device derivation; `cold` != 0: of a
  * flattening made from scratch for the comparison (nothing cached is touched); flags with KSH_DERIVE_VOLUMES: of the flattening derived volume what-ifs use. */

@@ -305,12 +305,10 @@ extern "C" {
 // The problem object is patched in place -- new nodes and pods are appended (the vectors were parsed with room: nothing moves), what leaves stays as a tombstone
 // (a node out of state, a pod bound nowhere) -- and the snapshot's flattening, if there is one, is continued from the one before (ksh::make_snapshot_base `before`).
 // Not to be called while another thread uses handles opened over this snapshot; handles opened BEFORE the call keep solving what they were opened for.
-int ksh_env_apply(void* parsed, const int32_t* pod_node, const char* ksd_text, size_t len, uint32_t info[4]) {
-  if (info) info[0] = info[1] = info[2] = info[3] = 0;
-  if (!parsed || !ksd_text) return set_err(KS_ERR_INVALID, "null argument");
-  Parsed* P = (Parsed*)parsed;
-  try {
-    std::vector<ksp::DeltaEvent> ev = ksp::Parser(ksd_text, len).parse_delta();
+// What both doors do once the events are objects (`ev` is consumed): the text door (ksh_env_apply) and the binary one (ksh_env_apply_block) differ in the decoding alone.
+// `track_cluster_pods`: mirror BIND / UNBIND into the snapshot's cluster pods whatever the first call found there (KSH_APPLY_TRACK_CLUSTER_PODS); otherwise iff it found some.
+static int apply_events(Parsed* P, const int32_t* pod_node, std::vector<ksp::DeltaEvent>& ev, bool track_cluster_pods, uint32_t info[4]) {
+  {
     std::lock_guard<std::mutex> g(P->mu);
     ksp::Problem& pr = const_cast<ksp::Problem&>(*P->pr);      // (the only writer; see above)
     if (!P->bind_set) {
@@ -321,13 +319,14 @@ int ksh_env_apply(void* parsed, const int32_t* pod_node, const char* ksd_text, s
       for (size_t i = 0; i < pr.pods.size(); ++i) if (P->bind[i] >= 0 && !P->live_pod.emplace(pr.pods[i].uid, (uint32_t)i).second) { P->live_node.clear(); P->live_pod.clear(); return set_err(KS_ERR_INVALID, "two bound pods share a uid"); }
       P->had_cluster_pods = !pr.cluster_pods.empty(); P->bind_set = true;
     } else if (pod_node && !std::equal(pod_node, pod_node + pr.pods.size(), P->bind.begin())) return set_err(KS_ERR_INVALID, "the bindings passed differ from the ones the library holds since the last ksh_env_apply (pass NULL)");
+    const bool mirror = track_cluster_pods || P->had_cluster_pods;
     auto unbind = [&](uint32_t i) {
       ksp::Pod& p = pr.pods[i]; ksp::StateNode& n = pr.nodes[P->bind[i]];
       const ksp::ResList req = ksh::RequestsForPod(p);      // state.Node.cleanupForPod (node.go:175-182): Available() = Allocatable - the requests of the pods still there
       for (auto& kv : n.available) { auto r = req.find(kv.first); if (r != req.end()) kv.second += r->second; }
       for (auto& c : p.containers) for (auto& hp : c.ports) if (hp.port != 0) for (size_t k = 0; k < n.host_ports.size(); ++k) if (n.host_ports[k].ip == hp.ip && n.host_ports[k].port == hp.port && n.host_ports[k].proto == hp.proto) { n.host_ports.erase(n.host_ports.begin() + k); break; }
       for (auto& v : p.volumes) for (size_t k = 0; k < n.volumes.size(); ++k) if (n.volumes[k].driver == v.driver && n.volumes[k].pvc == v.pvc) { n.volumes.erase(n.volumes.begin() + k); break; }
-      if (P->had_cluster_pods) for (size_t k = 0; k < pr.cluster_pods.size(); ++k) if (pr.cluster_pods[k].uid == p.uid) { pr.cluster_pods.erase(pr.cluster_pods.begin() + k); break; }
+      if (mirror) for (size_t k = 0; k < pr.cluster_pods.size(); ++k) if (pr.cluster_pods[k].uid == p.uid) { pr.cluster_pods.erase(pr.cluster_pods.begin() + k); break; }
       P->live_pod.erase(p.uid); P->bind[i] = -1;
       p.uid = std::string("\1unbound-") + std::to_string(++P->tombstones);      // (uids stay unique: the same pod may be bound again)
     };
@@ -352,7 +351,7 @@ int ksh_env_apply(void* parsed, const int32_t* pod_node, const char* ksd_text, s
         for (auto& kv : n.available) { auto r = req.find(kv.first); if (r != req.end()) kv.second -= r->second; }
         for (auto& c : e.pod.containers) for (auto& hp : c.ports) if (hp.port != 0) n.host_ports.push_back(hp);
         for (auto& v : e.pod.volumes) n.volumes.push_back(v);
-        if (P->had_cluster_pods) { ksp::ClusterPod cp; cp.uid = e.pod.uid; cp.ns = e.pod.ns; cp.node_name = n.name; cp.labels = e.pod.labels; cp.anti_required = e.pod.anti_required; pr.cluster_pods.push_back(std::move(cp)); }
+        if (mirror) { ksp::ClusterPod cp; cp.uid = e.pod.uid; cp.ns = e.pod.ns; cp.node_name = n.name; cp.labels = e.pod.labels; cp.anti_required = e.pod.anti_required; pr.cluster_pods.push_back(std::move(cp)); }
         P->live_pod.emplace(e.pod.uid, (uint32_t)pr.pods.size()); pr.pods.push_back(std::move(e.pod)); P->bind.push_back((int32_t)it->second);
       } else {
         auto it = P->live_pod.find(e.name); if (it == P->live_pod.end()) { why = "UNBIND: no bound pod with uid " + e.name; break; }
@@ -372,6 +371,29 @@ int ksh_env_apply(void* parsed, const int32_t* pod_node, const char* ksd_text, s
     if (info) { info[0] = done; info[1] = (uint32_t)pr.nodes.size(); info[2] = (uint32_t)pr.pods.size(); info[3] = continued ? 1u : 0u; }
     if (done != ev.size()) return set_err(KS_ERR_INVALID, "event " + std::to_string(done) + ": " + why + " (the events before it were applied)");
     return KS_OK;
+  }
+}
+int ksh_env_apply(void* parsed, const int32_t* pod_node, const char* ksd_text, size_t len, uint32_t info[4]) {
+  if (info) info[0] = info[1] = info[2] = info[3] = 0;
+  if (!parsed || !ksd_text) return set_err(KS_ERR_INVALID, "null argument");
+  try {
+    std::vector<ksp::DeltaEvent> ev = ksp::Parser(ksd_text, len).parse_delta();
+    return apply_events((Parsed*)parsed, pod_node, ev, false, info);
+  } catch (const ksh::Unsupported& e) { return set_err(KS_ERR_UNSUPPORTED, e.what());
+  } catch (const std::exception& e) { return set_err(KS_ERR_INVALID, e.what()); }
+}
+// The same events without the text (kshost.h ksh_delta_block; grammar in kspb.hpp DeltaReader).  The block is decoded COMPLETELY before the first event is applied:
+// a malformed block changes nothing, not even the hand-over of the bindings on a first call.
+int ksh_env_apply_block(void* parsed, const int32_t* pod_node, const ksh_delta_block* d, uint32_t flags, uint32_t info[4]) {
+  if (info) info[0] = info[1] = info[2] = info[3] = 0;
+  if (!parsed || !d || !d->str_off || (!d->words && d->n_words) || (!d->str_bytes && d->n_strings)) return set_err(KS_ERR_INVALID, "null argument");
+  if (flags & ~(uint32_t)KSH_APPLY_TRACK_CLUSTER_PODS) return set_err(KS_ERR_INVALID, "ksh_env_apply_block: unknown flag bit");
+  try {
+    for (uint32_t i = 0; i < d->n_strings; ++i) if (d->str_off[i + 1] < d->str_off[i]) return set_err(KS_ERR_INVALID, "delta block: string offsets not ascending");
+    if (d->n_strings && d->str_off[d->n_strings] > d->str_bytes_len) return set_err(KS_ERR_INVALID, "delta block: string offsets reach beyond str_bytes_len");
+    ksh_pod_block strings{}; strings.n_strings = d->n_strings; strings.str_off = d->str_off; strings.str_bytes = d->str_bytes; strings.str_bytes_len = d->str_bytes_len;
+    std::vector<ksp::DeltaEvent> ev = ksp::DeltaReader(strings, d->words, d->words + d->n_words).read_delta(d->n_events);
+    return apply_events((Parsed*)parsed, pod_node, ev, (flags & KSH_APPLY_TRACK_CLUSTER_PODS) != 0, info);
   } catch (const ksh::Unsupported& e) { return set_err(KS_ERR_UNSUPPORTED, e.what());
   } catch (const std::exception& e) { return set_err(KS_ERR_INVALID, e.what()); }
 }

@@ -119,15 +119,7 @@ class EnvReader : public SpecReader {
       for (uint32_t m = cnt(); m; --m) { const uint32_t ix = u(); if (ix >= pr.instance_types.size()) throw Error("env block: instance type index out of range"); pv.instance_types.push_back((int32_t)ix); }
       pr.provisioners.push_back(std::move(pv));
     }
-    for (uint32_t n = cnt(); n; --n) {
-      StateNode sn; sn.name = s(); sn.in_state = u() != 0; sn.labels = map();
-      for (uint32_t m = cnt(); m; --m) sn.taints.push_back(taint());
-      sn.available = res(); sn.capacity = res(); sn.daemonset_requests = res();
-      for (uint32_t m = cnt(); m; --m) { HostPort h; h.ip = s(); h.port = i(); h.proto = s(); sn.host_ports.push_back(std::move(h)); }
-      for (uint32_t m = cnt(); m; --m) { std::string d = s(); sn.volume_limits.emplace_back(std::move(d), i()); }
-      for (uint32_t m = cnt(); m; --m) { Volume v; v.driver = s(); v.pvc = s(); sn.volumes.push_back(std::move(v)); }
-      pr.nodes.push_back(std::move(sn));
-    }
+    for (uint32_t n = cnt(); n; --n) pr.nodes.push_back(state_node());
     for (uint32_t n = cnt(); n; --n) {
       ClusterPod cp; cp.uid = s(); cp.ns = s(); cp.node_name = s(); cp.labels = map();
       for (uint32_t m = cnt(); m; --m) cp.anti_required.push_back(term());
@@ -143,8 +135,57 @@ class EnvReader : public SpecReader {
     if (w_ != e_) throw Error("env block: trailing words");
     return pr;
   }
- private:
+ protected:
   Taint taint() { Taint t; t.key = s(); t.value = s(); t.effect = s(); return t; }
+  // the state_node record of the grammar above: also the body of a NODE+ event (DeltaReader below)
+  StateNode state_node() {
+    StateNode sn; sn.name = s(); sn.in_state = u() != 0; sn.labels = map();
+    for (uint32_t m = cnt(); m; --m) sn.taints.push_back(taint());
+    sn.available = res(); sn.capacity = res(); sn.daemonset_requests = res();
+    for (uint32_t m = cnt(); m; --m) { HostPort h; h.ip = s(); h.port = i(); h.proto = s(); sn.host_ports.push_back(std::move(h)); }
+    for (uint32_t m = cnt(); m; --m) { std::string d = s(); sn.volume_limits.emplace_back(std::move(d), i()); }
+    for (uint32_t m = cnt(); m; --m) { Volume v; v.driver = s(); v.pvc = s(); sn.volumes.push_back(std::move(v)); }
+    return sn;
+  }
+};
+
+// The snapshot's EVENTS through the same kind of door (include/kshost.h `ksh_delta_block`, ksh_env_apply_block): what state.Cluster hears between two passes
+// (cluster.go UpdateNode / DeleteNode / UpdatePod / DeletePod) as ONE stream of u32 words over ONE string table -- the binary form of the KSD1 text
+// (ksp.hpp Parser::parse_delta), built from the records above and nothing else:
+//
+//   delta      := n_events { event }
+//   event      := KSH_EVENT_NODE_ADD    state_node                                   (NODE+: the environment's state_node record)
+//               | KSH_EVENT_NODE_REMOVE name:S                                       (NODE-)
+//               | KSH_EVENT_BIND        node_name:S nwords:U spec uid:S ts_lo:U ts_hi:U   (BIND: the pod blocks' spec record, nwords words; then uid and creationTimestamp)
+//               | KSH_EVENT_UNBIND      uid:S                                        (UNBIND)
+//
+// n_events is the block's own field (no count word leads the stream); the stream must hold exactly that many events and end with the last one.
+enum : uint32_t { kEventNodeAdd = KSH_EVENT_NODE_ADD, kEventNodeRemove = KSH_EVENT_NODE_REMOVE, kEventBind = KSH_EVENT_BIND, kEventUnbind = KSH_EVENT_UNBIND };
+class DeltaReader : public EnvReader {
+ public:
+  DeltaReader(const ksh_pod_block& strings, const uint32_t* w, const uint32_t* e) : EnvReader(strings, w, e) {}
+  // The events Parser::parse_delta() gives for the KSD1 text of the same objects.  Throws ksp::Error naming the event a malformed record belongs to.
+  std::vector<DeltaEvent> read_delta(uint32_t n_events) {
+    std::vector<DeltaEvent> ev;
+    if (n_events > (uint32_t)(e_ - w_)) throw Error("delta block: n_events is larger than the stream (every event takes at least one word)");
+    ev.reserve(n_events);
+    for (uint32_t k = 0; k < n_events; ++k) {
+      try {
+        DeltaEvent e; const uint32_t kind = u();
+        if (kind == kEventNodeAdd) { e.kind = DeltaEvent::NodeAdd; e.node = state_node(); }
+        else if (kind == kEventNodeRemove) { e.kind = DeltaEvent::NodeRemove; e.name = s(); }
+        else if (kind == kEventBind) {
+          e.kind = DeltaEvent::PodBind; e.name = s(); const uint32_t nw = cnt();
+          e.pod = SpecReader(b_, w_, w_ + nw).read(); w_ += nw;
+          e.pod.uid = s(); const uint64_t lo = u(), hi = u(); e.pod.creation_ts = (int64_t)(lo | (hi << 32));
+        } else if (kind == kEventUnbind) { e.kind = DeltaEvent::PodUnbind; e.name = s(); }
+        else throw Error("unknown event kind " + std::to_string(kind));
+        ev.push_back(std::move(e));
+      } catch (const Error& x) { throw Error("delta block: event " + std::to_string(k) + ": " + x.what()); }
+    }
+    if (w_ != e_) throw Error("delta block: event " + std::to_string(n_events) + ": trailing words (the stream goes on after its n_events events)");
+    return ev;
+  }
 };
 
 }  // namespace ksp

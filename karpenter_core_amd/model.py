@@ -400,9 +400,42 @@ class EnvBlockWriter(PodBlockWriter):
         for t in ts:
             w.extend((self._s(t.key), self._s(t.value), self._s(t.effect)))
 
+    def _node(self, w, n: "StateNode"):
+        """The state_node record (also the body of a NODE+ event, `DeltaBlockWriter`)."""
+        w.extend((self._s(n.name), 1 if n.in_state else 0))
+        self._map(w, n.labels)
+        self._taints(w, n.taints)
+        self._res(w, n.available)
+        self._res(w, n.capacity)
+        self._res(w, n.daemonset_requests)
+        w.append(len(n.host_ports))
+        for hp in n.host_ports:
+            w.extend((self._s(hp.host_ip), int(hp.port) & 0xFFFFFFFF, self._s(hp.protocol)))
+        w.append(len(n.volume_limits))
+        for d in sorted(n.volume_limits):
+            w.extend((self._s(d), int(n.volume_limits[d]) & 0xFFFFFFFF))
+        w.append(len(n.volumes))
+        for v in n.volumes:
+            w.extend((self._s(v.driver), self._s(v.pvc_id)))
+
+    def _pod(self, w, p: "Pod"):
+        """A whole pod inside a stream: word count, spec record, uid, creationTimestamp -- the tail of a BIND event (`DeltaBlockWriter`)."""
+        w.append(0)
+        at = len(w)
+        self.add(p)                           # (the spec record; add() also notes uid / timestamp / offset for a pod block: not used here)
+        w[at - 1] = len(w) - at
+        ts = int(p.creation_ts) & 0xFFFFFFFFFFFFFFFF
+        w.extend((self._s(p.uid), ts & 0xFFFFFFFF, ts >> 32))
+
+    def _block(self) -> dict:
+        import numpy as np
+        so = np.zeros(len(self._strs) + 1, dtype=np.uint32)
+        np.cumsum([len(b) for b in self._strs], out=so[1:])
+        return {"n_strings": len(self._strs), "n_words": len(self._words), "str_off": so, "str_bytes": np.frombuffer(b"".join(self._strs) + b"\0", dtype=np.uint8).copy(),
+                "words": np.asarray(self._words if self._words else [0], dtype=np.uint32)}
+
     def write(self, pr: "Problem") -> dict:
         import struct
-        import numpy as np
         w = self._words
         w.append(len(pr.extra_well_known))
         w.extend(self._s(k) for k in pr.extra_well_known)
@@ -431,21 +464,7 @@ class EnvBlockWriter(PodBlockWriter):
             w.extend(int(i) for i in p.instance_types)
         w.append(len(pr.nodes))
         for n in pr.nodes:
-            w.extend((self._s(n.name), 1 if n.in_state else 0))
-            self._map(w, n.labels)
-            self._taints(w, n.taints)
-            self._res(w, n.available)
-            self._res(w, n.capacity)
-            self._res(w, n.daemonset_requests)
-            w.append(len(n.host_ports))
-            for hp in n.host_ports:
-                w.extend((self._s(hp.host_ip), int(hp.port) & 0xFFFFFFFF, self._s(hp.protocol)))
-            w.append(len(n.volume_limits))
-            for d in sorted(n.volume_limits):
-                w.extend((self._s(d), int(n.volume_limits[d]) & 0xFFFFFFFF))
-            w.append(len(n.volumes))
-            for v in n.volumes:
-                w.extend((self._s(v.driver), self._s(v.pvc_id)))
+            self._node(w, n)
         w.append(len(pr.cluster_pods))
         for cp in pr.cluster_pods:
             w.extend((self._s(cp.uid), self._s(cp.namespace), self._s(cp.node_name)))
@@ -461,15 +480,38 @@ class EnvBlockWriter(PodBlockWriter):
             self.add(d)                       # (the spec record; add() also notes uid / timestamp / offset for a pod block: not used here)
             w[at - 1] = len(w) - at
         w.append(1 if pr.simulation_mode else 0)
-        so = np.zeros(len(self._strs) + 1, dtype=np.uint32)
-        np.cumsum([len(b) for b in self._strs], out=so[1:])
-        return {"n_strings": len(self._strs), "n_words": len(w), "str_off": so, "str_bytes": np.frombuffer(b"".join(self._strs) + b"\0", dtype=np.uint8).copy(),
-                "words": np.asarray(w, dtype=np.uint32)}
+        return self._block()
 
 
 def env_to_block(pr: "Problem") -> dict:
     """Everything of `pr` but its pending pods as one binary block (`ksh_env_ingest`)."""
     return EnvBlockWriter().write(pr)
+
+
+EVENT_NODE_ADD, EVENT_NODE_REMOVE, EVENT_BIND, EVENT_UNBIND = 1, 2, 3, 4      # include/kshost.h KSH_EVENT_*
+
+
+class DeltaBlockWriter(EnvBlockWriter):
+    """Binary EVENTS ingress (include/kshost.h `ksh_delta_block`, grammar in karpenter_core_amd/host/kspb.hpp DeltaReader): what a cgo shim would fill from the
+    *v1.Node / *v1.Pod its informers hand it instead of printing KSD1 text -- per event a kind word, then the environment's state-node record (NODE+), a node name
+    (NODE-), a node name and the pod (BIND) or a pod uid (UNBIND), over one string table."""
+
+    def write_events(self, events: Sequence[tuple]) -> dict:
+        w = self._words
+        for e in events:
+            if e[0] == "node+":
+                w.append(EVENT_NODE_ADD)
+                self._node(w, e[1])
+            elif e[0] == "node-":
+                w.extend((EVENT_NODE_REMOVE, self._s(e[1])))
+            elif e[0] == "bind":
+                w.extend((EVENT_BIND, self._s(e[1])))
+                self._pod(w, e[2])
+            elif e[0] == "unbind":
+                w.extend((EVENT_UNBIND, self._s(e[1])))
+            else:
+                raise ValueError(f"unknown snapshot event {e[0]!r}")
+        return dict(self._block(), n_events=len(events))
 
 
 def _ksp_reslist(rl: Dict[str, str], w):
@@ -647,6 +689,11 @@ def _ksp_node(n: "StateNode", w):
     w.write(f" VU {len(n.volumes)}")
     for v in n.volumes:
         w.write(f" {_tok(v.driver)} {_tok(v.pvc_id)}")
+
+
+def delta_to_block(events: Sequence[tuple]) -> dict:
+    """The events `delta_to_ksd` takes as one binary block for `scheduler.ParsedProblem.apply_block` (kshost.h `ksh_env_apply_block`): no text on the way."""
+    return DeltaBlockWriter().write_events(events)
 
 
 def delta_to_ksd(events: Sequence[tuple]) -> str:

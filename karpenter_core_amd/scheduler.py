@@ -30,6 +30,7 @@ _LIBS = None
 KS_OK, KS_ERR_INVALID, KS_ERR_UNSUPPORTED, KS_ERR_DEVICE, KS_ERR_CAPACITY = 0, -1, -2, -3, -4
 KS_FLAG_SIMULATION, KS_FLAG_STATS, KS_FLAG_NO_RR, KS_FLAG_ONE_WAVE, KS_FLAG_NO_LEAN = 1, 2, 4, 8, 16
 KSH_DERIVE_VOLUMES = 1 << 16      # kshost.h: derive what-ifs over snapshots with CSI volume limits / claims too (opt-in)
+KSH_APPLY_TRACK_CLUSTER_PODS = 1  # kshost.h: ksh_env_apply_block mirrors BIND / UNBIND into the cluster pods whatever the snapshot started with
 
 
 class KSolveError(RuntimeError):
@@ -324,6 +325,30 @@ class ParsedProblem:
             raise KSolveError(rc, kh.ksh_last_error().decode())
         return {"applied": int(info[0]), "nodes": int(info[1]), "pods": int(info[2]), "continued": bool(info[3]), "ms": ms}
 
+    def apply_block(self, events, pod_node: Optional[Sequence[int]] = None, track_cluster_pods: bool = False) -> dict:
+        """`apply` through the binary door (kshost.h `ksh_env_apply_block`): the same events (or the block `model.delta_to_block` made of them, for a caller that
+        builds it ahead of the call), no KSD1 text on the way, the same returned dict.  A malformed block applies nothing.  `track_cluster_pods`
+        (KSH_APPLY_TRACK_CLUSTER_PODS): mirror BIND / UNBIND into the snapshot's cluster pods even if it had none at the first call -- what a topology-tracking
+        snapshot that starts with no bound pod needs.  A refused call raises KSolveError carrying `.info`: the same dict, saying what was applied before the refusal."""
+        import numpy as np, time
+        from .model import delta_to_block
+        kh = libs()[1]
+        b = events if isinstance(events, dict) else delta_to_block(events)
+        db = _DeltaBlock(b["n_events"], b["n_strings"], b["n_words"], b["str_off"].ctypes.data, b["str_bytes"].ctypes.data, b["words"].ctypes.data,
+                         int(b.get("str_bytes_len", b["str_bytes"].size)))
+        pn = None if pod_node is None else np.ascontiguousarray(np.asarray(pod_node, dtype=np.int32))
+        info = (ctypes.c_uint32 * 4)()
+        kh.ksh_env_apply_block.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]
+        t0 = time.perf_counter()
+        rc = kh.ksh_env_apply_block(self._p, None if pn is None or pn.size == 0 else pn.ctypes.data, ctypes.byref(db), KSH_APPLY_TRACK_CLUSTER_PODS if track_cluster_pods else 0, info)
+        ms = (time.perf_counter() - t0) * 1e3
+        out = {"applied": int(info[0]), "nodes": int(info[1]), "pods": int(info[2]), "continued": bool(info[3]), "ms": ms}
+        if rc != KS_OK:
+            err = KSolveError(rc, kh.ksh_last_error().decode())
+            err.info = out
+            raise err
+        return out
+
     def bindings(self):
         """(pod -> node index, -1 for a pod that was unbound; number of node slots) as the library holds them after `apply`."""
         import numpy as np
@@ -390,6 +415,11 @@ class _PodBlock(ctypes.Structure):      # include/kshost.h ksh_pod_block
 
 class _EnvBlock(ctypes.Structure):
     _fields_ = [("n_strings", ctypes.c_uint32), ("n_words", ctypes.c_uint32), ("str_off", ctypes.c_void_p), ("str_bytes", ctypes.c_void_p), ("words", ctypes.c_void_p), ("str_bytes_len", ctypes.c_uint64)]
+
+
+class _DeltaBlock(ctypes.Structure):      # include/kshost.h ksh_delta_block
+    _fields_ = [("n_events", ctypes.c_uint32), ("n_strings", ctypes.c_uint32), ("n_words", ctypes.c_uint32), ("str_off", ctypes.c_void_p), ("str_bytes", ctypes.c_void_p),
+                ("words", ctypes.c_void_p), ("str_bytes_len", ctypes.c_uint64)]
 
 
 class PodBatch:
