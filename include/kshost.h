@@ -119,6 +119,7 @@ typedef struct ksh_result_arrays {
 int ksh_result_arrays_get(void* handle, ksh_result_arrays* out);
 const char* ksh_name(void* handle, int what /* 0 key, 1 value b of key a, 2 resource */, uint32_t a, uint32_t b);
 int ksh_pack_width(void* handle, int* out);                                              /* ks_problem_pack_width of the handle's device problem: 4, 8 or 16 (the wide variants), 0 if ks_pack_rr took the last solve */
+int ksh_pack_lean(void* handle, int* out);                                               /* ks_problem_pack_lean of the handle's device problem: 1 if the ks_pack variant of the last solve was a LEAN one (width 4, or 8 under KSH_ACTIVE_RESOURCES) */
 int ksh_rr_status(void* handle, int out[2]);                                           /* ks_problem_rr_status of the handle's device problem: out[0] ks_pack_rr was launched, out[1] why it declined (0: it took the Solve) */
 void ksh_dims(void* handle, uint32_t dims[10]);                                        /* P,C,T,M,E,K,R,G,GH,S */
 uint64_t ksh_fingerprint(void* handle);                                                /* hash of every array of the flat problem */
@@ -173,6 +174,22 @@ int ksh_types_subset(void** handles, uint32_t n, const uint32_t* node, const uin
  * (ks_whatifs_open_ex with KS_WHATIFS_VOLUMES).  This flattening is kept apart from the flag-0 one (which ksh_snapshot_fingerprint(flags 0) hashes and
  * ksh_open_whatifs_parsed uses); KS_ERR_UNSUPPORTED still for more than 64 limited drivers, 2^24 multi claims, or per-what-if volume state above 64 MiB. */
 #define KSH_DERIVE_VOLUMES (1u << 16)
+/* KSH_ACTIVE_RESOURCES (opt-in; a library flag like KSH_DERIVE_VOLUMES: a bit no KS_FLAG_* uses, stripped before the flat problem is built, so it is never hashed by
+ * ksh_fingerprint nor passed to ks_problem_upload): flatten over the resource names the problem REQUESTS, not over all a catalogue lists.  Interned are cpu, memory, pods
+ * (ids 0, 1, 2 as always) and, in the same first-use order as without the flag, every name that is NAMED -- present, a quantity of 0 included -- in
+ *   a container's or init container's requests or limits of a pending pod, a daemonset pod or a bound pod of a snapshot; a provisioner's limits; a state node's
+ *   daemonset_requests.
+ * A name that only an instance type's capacity / overhead or a state node's available / capacity carries is INERT: it decides nothing (resources.Fits walks the requested
+ * names, scheduler.go:273-309 the limited ones, a result's Requests hold requested names), so it gets no id and its quantities are not stored.  ksh_dims' R,
+ * ksh_name(h, 2, r, 0), ksh_result_arrays' n_resources and KSR1 text then speak of the active names only, and the 16-name limit counts active names (a 20-name catalogue
+ * whose pods request six opens; 17 active names are refused with both counts in the message).  The flat problem is byte for byte the one the same objects give without
+ * the flag once the inert names are deleted from them, so every result is the same; with at most 8 (4) active names the narrow (LEAN, ks_pack_rr) kernels take a problem
+ * the wide single-wave variants would otherwise run, and the LEAN variants take it at up to 8 names (ks_problem.lean_r8).
+ * Accepted by every call that takes `flags` and flattens: ksh_open*, ksh_solve_from_pods / _batch, ksh_open_batch, ksh_open_whatifs*, ksh_open_whatifs_derived (with or
+ * without KSH_DERIVE_VOLUMES; a snapshot's active set is the union over ALL its bound pods, so it does not depend on a candidate set), ksh_snapshot_fingerprint,
+ * ksh_check_whatif_derivation.  A parsed object keeps the flag-on flattenings (environment cache, snapshot) apart from the flag-off ones; after ksh_env_apply / _block an
+ * event that makes a new name active falls back to the full flattening, as a new label value does.  Without the flag nothing changes. */
+#define KSH_ACTIVE_RESOURCES (1u << 17)
 int ksh_open_whatifs_derived(void* parsed_snapshot, uint32_t flags, uint32_t n, const uint32_t* cand_off, const uint32_t* cand, const int32_t* pod_node, int device, void** out_handles);
 uint64_t ksh_whatifs_arena_bytes(void* handle);      /* a derived what-if: device bytes of the arena its batch shares (ks_whatifs_arena_bytes); 0 for any other handle */
 int ksh_open_whatifs_parsed(void* parsed_snapshot, uint32_t flags, uint32_t n, const uint32_t* cand_off, const uint32_t* cand, const int32_t* pod_node, uint32_t nthreads, void** out_handles);

@@ -178,6 +178,9 @@ typedef struct ks_problem {
   const int32_t* grph_count;    /* [GH*E] initial counts on the existing nodes' hostnames; -1 unregistered */
   const int32_t* grph_extra_pos;/* [GH] hostnames outside the state nodes with count > 0 (pod affinity options) */
   uint32_t n_topologies;        /* groups [0, n_topologies) are Topology.topologies, the rest inverseTopologies */
+  uint32_t lean_r8;             /* != 0: the LEAN kernel variants may take this problem at up to 8 resources (their RM = 8 instantiations); 0 (every problem before this
+                                   field existed): LEAN at R <= 4 only, so such a problem runs the kernel it always ran.  libkshost sets it for a problem flattened under
+                                   KSH_ACTIVE_RESOURCES.  A kernel choice, not part of the problem: no fingerprint covers it, no result depends on it. */
 } ks_problem;
 
 #define KS_FLAG_SIMULATION 1u /* SchedulerOptions.SimulationMode (scheduler.go:37-40); informational */
@@ -252,6 +255,7 @@ int ks_problem_rr_status(const ks_dev_problem* d, int* started, int* decline_cod
 /* Which ks_pack variant took the last solve of `d`, by its compile-time resource bound: 4 (LEAN), 8 (general), 16 (wide: a problem with R > 8, or a
  * what-if batch holding one); 0 if ks_pack_rr took it.  Diagnostics only, like ks_problem_rr_status. */
 int ks_problem_pack_width(const ks_dev_problem* d, int* rm);
+int ks_problem_pack_lean(const ks_dev_problem* d, int* lean);      /* its neighbour: 1 if the ks_pack variant the last solve ran was a LEAN one (at width 4, or 8 under ks_problem.lean_r8), else 0 */
 int ks_problem_upload(const ks_problem* p, int device, ks_dev_problem** out);
 void ks_problem_free(ks_dev_problem* d);
 /* Consolidation what-ifs over ONE cluster snapshot (deprovisioning/helpers.go:42-99) differ in their pods and in which state nodes stay, not in

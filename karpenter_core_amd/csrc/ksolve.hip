@@ -45,6 +45,7 @@
 // Resources per plan / brief record and per lane array of the narrow kernels.  A problem with R in (8, KS_MAX_RES] runs on the wide
 // variants (RM = 16), which read resources 8.. of a class from DevProb::cls_requests: the records keep their size and layout.
 #define KS_RES_NARROW 8
+#define KS_LEAN8_NW 4      // waves of the multi-wave LEAN variant at RM = 8 (a LEAN problem with 5..8 resources, ks_problem.lean_r8): at 8 waves its static LDS plus the 44 KiB of ladders is 7 248 B over the CU's 160 KiB and 112 VGPRs spill
 
 #ifdef KS_SIM      /* tests/sim/hip_sim.h: the kernels of this file run on the host, a fibre per lane (test infrastructure; hipcc never defines it) */
 struct u32x4 { unsigned int x, y, z, w; };
@@ -2795,6 +2796,7 @@ struct ks_dev_problem {
   u32 pp_cap = 0;
   bool view = false;             // a what-if derived from a resident snapshot (ks_whatifs_open): memory and stream belong to its ks_whatif_batch
   int pack_rm = 0;                 // the last solve: resource bound of the ks_pack variant that ran (4, 8, 16), 0 if ks_pack_rr took it
+  int pack_lean = 0;               // the last solve: 1 if that variant was a LEAN one
   int rr_started = 0, rr_code = 0; // the last solve: ks_pack_rr was launched | why it declined (0: it took the Solve; the codes are in ks_pack_rr.inc)
   bool no_multi = false;         // ... over a snapshot with topology groups: the class briefs (round eligibility, certain records) were built for the snapshot's group activity, not this what-if's -- single-wave kernel only
 };
@@ -2837,6 +2839,7 @@ extern "C" int ks_device_count(void) {
 extern "C" int ks_current_device(void) { int d = 0; if (hipGetDevice(&d) != hipSuccess) return 0; return d; }
 extern "C" int ks_problem_device(const ks_dev_problem* d) { return d ? d->device : -1; }
 extern "C" int ks_problem_pack_width(const ks_dev_problem* d, int* rm) { if (!d || !rm) return fail(KS_ERR_INVALID, "null argument"); *rm = d->pack_rm; return KS_OK; }
+extern "C" int ks_problem_pack_lean(const ks_dev_problem* d, int* lean) { if (!d || !lean) return fail(KS_ERR_INVALID, "null argument"); *lean = d->pack_lean; return KS_OK; }
 extern "C" int ks_problem_rr_status(const ks_dev_problem* d, int* started, int* decline_code) { if (!d) return fail(KS_ERR_INVALID, "null problem"); if (started) *started = d->rr_started; if (decline_code) *decline_code = d->rr_code; return KS_OK; }
 
 static int validate(const ks_problem* p) {
@@ -2906,7 +2909,7 @@ static int upload_impl(const ks_problem* p, int device, const ks_dev_problem* ba
   }
   const u32 K = h.K, R = h.R, T = h.T, TW = h.TW, C = h.C, M = h.M, E = h.E, G = h.G, P = h.P;
   {   // LEAN kernel variant eligibility (see ks_pack)
-    bool lean = R <= 4 && h.SC == 1 && !(p->flags & KS_FLAG_STATS);
+    bool lean = R <= (p->lean_r8 ? 8u : 4u) && h.SC == 1 && !(p->flags & KS_FLAG_STATS);      // (lean_r8: the caller lets the LEAN variants' RM = 8 instantiations take 5..8 resources, ksolve.h)
     for (u32 m = 0; m < M && lean; ++m) lean = p->tmpl_limit_present[m] == 0xFFFFFFFFu || p->tmpl_limit_present[m] == 0;
     for (u32 c = 0; c < C && lean; ++c) lean = p->cls_hn_mode[c] == 0 && p->cls_port_off[c + 1] == p->cls_port_off[c] && p->cls_vol_off[c + 1] == p->cls_vol_off[c];
     d->lean_ok = lean;
@@ -3454,8 +3457,9 @@ extern "C" int ks_solve_batch_dev(ks_dev_problem* const* ds, uint32_t n, ks_resu
   // The register-resident kernel (ks_pack_rr.inc) takes a single LEAN Solve without Gt/Lt bounds; it declines what it does not cover -- before
   // or during the run, without having touched the inputs -- and ks_pack below takes over.
   bool rr_done = false;
-  for (u32 i = 0; i < n; ++i) { ds[i]->rr_started = 0; ds[i]->rr_code = 0; ds[i]->pack_rm = 0; }
-  bool wide = false; for (u32 i = 0; i < n; ++i) wide = wide || ds[i]->h.R > KS_RES_NARROW;      // (R > 4: never LEAN, so never ks_pack_rr)
+  for (u32 i = 0; i < n; ++i) { ds[i]->rr_started = 0; ds[i]->rr_code = 0; ds[i]->pack_rm = 0; ds[i]->pack_lean = 0; }
+  bool wide = false; for (u32 i = 0; i < n; ++i) wide = wide || ds[i]->h.R > KS_RES_NARROW;      // (R > 8: never LEAN, so never ks_pack_rr)
+  bool lean8 = false; for (u32 i = 0; i < n; ++i) lean8 = lean8 || ds[i]->h.R > 4;               // a LEAN problem with 5..8 resources (ks_problem.lean_r8): the LEAN variants' RM = 8 instantiations; ks_pack_rr stays at 4
   const bool asked_one_wave = getenv("KS_ONE_WAVE") != nullptr || (any_flags & KS_FLAG_ONE_WAVE);      // KS_ONE_WAVE asks for ks_pack's single-wave variant
   const bool asked_no_rr = getenv("KS_NO_RR") != nullptr || (any_flags & KS_FLAG_NO_RR);                 // KS_NO_RR=1: ks_pack only (A/B, and the parity of both kernels)
 #ifdef KS_SIM
@@ -3471,7 +3475,7 @@ extern "C" int ks_solve_batch_dev(ks_dev_problem* const* ds, uint32_t n, ks_resu
   const bool one_wave = asked_one_wave;
   const bool rr_on = !asked_no_rr && !asked_one_wave;
 #endif
-  if (rr_on && n == 1 && lean && !bounds && fast && !ds[0]->view && !(ds[0]->h.flags & KS_FLAG_STATS) && ds[0]->h.rr_briefs) {
+  if (rr_on && n == 1 && lean && !lean8 && !bounds && fast && !ds[0]->view && !(ds[0]->h.flags & KS_FLAG_STATS) && ds[0]->h.rr_briefs) {
     // dynamic LDS: the Allocatable ladders (R x ge_max x 8 bytes), at most what the kernel's static LDS object leaves of the CU's 160 KiB (a problem whose ladders
     // do not fit is declined by the kernel itself: its eligibility test reads the size it was given)
     u32 lds_rr = 0;
@@ -3507,6 +3511,7 @@ extern "C" int ks_solve_batch_dev(ks_dev_problem* const* ds, uint32_t n, ks_resu
   typedef void (*pack_fn)(const DevProb*, const DevState*, u32);
   static const pack_fn variants[8] = {ks_pack<false, false, false, 1>, ks_pack<false, true, false, 1>, ks_pack<true, false, false, 1>, ks_pack<true, true, false, 1>,
                                       ks_pack<false, false, true, 1>, ks_pack<false, true, true, 1>, ks_pack<true, false, true, 1>, ks_pack<true, true, true, 1>};
+  static const pack_fn variants_lean8[4] = {ks_pack<false, false, true, 1, 8>, ks_pack<false, true, true, 1, 8>, ks_pack<true, false, true, 1, 8>, ks_pack<true, true, true, 1, 8>};
   static const pack_fn variants_wide[4] = {ks_pack<false, false, false, 1, 16>, ks_pack<false, true, false, 1, 16>, ks_pack<true, false, false, 1, 16>, ks_pack<true, true, false, 1, 16>};
   {   // the large dynamic-LDS opt-in is a per-device function attribute: set it once per device, race-free (two Solves may run concurrently)
     static std::mutex attr_mu; static std::vector<char> attr_done;
@@ -3515,7 +3520,9 @@ extern "C" int ks_solve_batch_dev(ks_dev_problem* const* ds, uint32_t n, ks_resu
     if (!attr_done[device]) {
       for (int i = 0; i < 8; ++i) HIPCHK(hipFuncSetAttribute((const void*)variants[i], hipFuncAttributeMaxDynamicSharedMemorySize, 104 * 1024));
       for (int i = 0; i < 4; ++i) HIPCHK(hipFuncSetAttribute((const void*)variants_wide[i], hipFuncAttributeMaxDynamicSharedMemorySize, 104 * 1024));
+      for (int i = 0; i < 4; ++i) HIPCHK(hipFuncSetAttribute((const void*)variants_lean8[i], hipFuncAttributeMaxDynamicSharedMemorySize, 104 * 1024));
       HIPCHK(hipFuncSetAttribute((const void*)ks_pack<true, false, true, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 44 * 1024));
+      HIPCHK(hipFuncSetAttribute((const void*)ks_pack<true, false, true, KS_LEAN8_NW, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 44 * 1024));
       HIPCHK(hipFuncSetAttribute((const void*)ks_pack<true, false, false, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 44 * 1024));
       HIPCHK(hipFuncSetAttribute((const void*)ks_pack<true, true, false, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 44 * 1024));
       attr_done[device] = 1;
@@ -3528,15 +3535,17 @@ extern "C" int ks_solve_batch_dev(ks_dev_problem* const* ds, uint32_t n, ks_resu
     const u32 lds_mw = 44u * 1024u;
     if ((size_t)ds[0]->h.R * ds[0]->h.ge_max * 8 + 8192 > lds_mw) multi = false;
     else {
-      if (lean && !bounds) hipLaunchKernelGGL((ks_pack<true, false, true, 8>), dim3(1), dim3(512), lds_mw, st, dp, dsv, lds_mw);
+      if (lean && !bounds && lean8) hipLaunchKernelGGL((ks_pack<true, false, true, KS_LEAN8_NW, 8>), dim3(1), dim3(64 * KS_LEAN8_NW), lds_mw, st, dp, dsv, lds_mw);
+      else if (lean && !bounds) hipLaunchKernelGGL((ks_pack<true, false, true, 8>), dim3(1), dim3(512), lds_mw, st, dp, dsv, lds_mw);
       else if (bounds) hipLaunchKernelGGL((ks_pack<true, true, false, 4>), dim3(1), dim3(256), lds_mw, st, dp, dsv, lds_mw);
       else hipLaunchKernelGGL((ks_pack<true, false, false, 4>), dim3(1), dim3(256), lds_mw, st, dp, dsv, lds_mw);     // host ports / limits / selectors on hostname or instance type: the general code
                                                                                                                      // needs > 256 VGPRs, so 4 waves (one per SIMD): leader + 3 workers
     }
   }
   if (!multi && wide) { hipLaunchKernelGGL(variants_wide[(fast ? 2 : 0) + (bounds ? 1 : 0)], dim3(n), dim3(64), lds_bytes, st, dp, dsv, lds_bytes); }
+  else if (!multi && lean && lean8) hipLaunchKernelGGL(variants_lean8[(fast ? 2 : 0) + (bounds ? 1 : 0)], dim3(n), dim3(64), lds_bytes, st, dp, dsv, lds_bytes);
   else if (!multi) hipLaunchKernelGGL(variants[(lean ? 4 : 0) + (fast ? 2 : 0) + (bounds ? 1 : 0)], dim3(n), dim3(64), lds_bytes, st, dp, dsv, lds_bytes);
-  for (u32 i = 0; i < n; ++i) ds[i]->pack_rm = wide ? 16 : (multi ? (lean && !bounds ? 4 : KS_RES_NARROW) : (lean ? 4 : KS_RES_NARROW));
+  for (u32 i = 0; i < n; ++i) { ds[i]->pack_rm = wide ? 16 : (multi ? (lean && !bounds && !lean8 ? 4 : KS_RES_NARROW) : (lean && !lean8 ? 4 : KS_RES_NARROW)); ds[i]->pack_lean = !wide && lean && !(multi && bounds); }
   }
 #endif
   HIPCHK(hipEventRecord(e1, st));

@@ -304,7 +304,11 @@ struct Builder {
   std::map<std::string, int> pre_it_state_id, pre_it_col_id;      // kept by encode_it_states: the lattice's states / columns before its closure
   std::string act_sig; std::map<std::string, int> act_key_id, act_res_id; size_t n_nodes_built = 0, n_pods_built = 0;      // kept by run(): what collect_active left, how large the problem was
 
-  Builder(Encoded& e, uint32_t f) : E(e), pr(*e.src), flags(f), lite(e.batch.get()) {}
+  // KSH_ACTIVE_RESOURCES (a library flag: the flat problem never carries it): only the resource names something requests or limits are interned -- what a pod, a
+  // daemonset, a provisioner's limits or a node's daemonset_requests names.  A name that only an instance type's capacity / overhead or a node's available / capacity
+  // carries is inert (resources.Fits walks the requested names, scheduler.go:273-309 the limited ones): it gets no id and its quantities are not stored.
+  bool active_res = false;
+  Builder(Encoded& e, uint32_t f) : E(e), pr(*e.src), flags(f & ~(uint32_t)KSH_ACTIVE_RESOURCES), lite(e.batch.get()), active_res((f & KSH_ACTIVE_RESOURCES) != 0) {}
   std::chrono::steady_clock::time_point tl_ = std::chrono::steady_clock::now();
   void sublap(const char* what) { if (!getenv("KSH_TIMING")) return; auto t1 = std::chrono::steady_clock::now(); fprintf(stderr, "      . %-26s %8.2f ms\n", what, std::chrono::duration<double, std::milli>(t1 - tl_).count()); tl_ = t1; }
 
@@ -368,7 +372,7 @@ struct Builder {
   // May this run continue `prev`?  After collect_active: the same problem object, what the batch / provisioners / daemonsets name unchanged (keys with their ids,
   // named values, bounds, topology keys, resources), and nothing a new node carries is new to a universe.
   bool can_continue() const {
-    if (!prev || &prev->pr != &pr || prev->flags != flags || prev->act_sig.empty() || prev->base || prev->lite) return false;
+    if (!prev || &prev->pr != &pr || prev->flags != flags || prev->active_res != active_res || prev->act_sig.empty() || prev->base || prev->lite) return false;
     if (key_id != prev->act_key_id || res_id != prev->act_res_id || active_signature() != prev->act_sig) return false;
     if (prev->n_nodes_built > pr.nodes.size() || prev->T != pr.instance_types.size()) return false;
     for (size_t i = prev->n_nodes_built; i < pr.nodes.size(); ++i) {
@@ -376,7 +380,7 @@ struct Builder {
       for (auto& kv : n.labels) { const std::string k = ksp::normalize_key(kv.first);
         auto it = prev->key_id.find(k); if (it != prev->key_id.end() && !prev->key_vals[it->second].count(kv.second)) return false;
         auto raw = prev->key_id.find(kv.first); if (raw != prev->key_id.end() && raw->first != k && !prev->key_vals[raw->second].count(kv.second)) return false; }
-      for (const ksp::ResList* l : {&n.available, &n.capacity, &n.daemonset_requests}) for (auto& kv : *l) if (!prev->res_id.count(kv.first)) return false;
+      for (const ksp::ResList* l : {&n.available, &n.capacity, &n.daemonset_requests}) { if (active_res && l != &n.daemonset_requests) continue; for (auto& kv : *l) if (!prev->res_id.count(kv.first)) return false; }
     }
     return true;
   }
@@ -398,18 +402,25 @@ struct Builder {
         if (special_key(k) || key_id.count(k)) note_expr(e);
       }
       for (auto& o : it.offerings) { note_value(key_of(ksp::kZone, true), o.zone); note_value(key_of(ksp::kCapacityType, true), o.capacity_type); }
-      note_res(it.capacity); note_res(it.overhead);
+      if (!active_res) { note_res(it.capacity); note_res(it.overhead); }
     }
     // node labels: only keys something else references matter (existing-node requirements are never
     // returned); values of referenced keys join the universe (they become topology domains / In sets)
     for (auto& n : pr.nodes) {
       for (auto& kv : n.labels) { std::string k = ksp::normalize_key(kv.first); auto it = key_id.find(k); if (it != key_id.end()) note_value(it->second, kv.second);
         auto raw = key_id.find(kv.first); if (raw != key_id.end() && raw->first != k) note_value(raw->second, kv.second); }
-      note_res(n.available); note_res(n.capacity); note_res(n.daemonset_requests);
+      if (!active_res) { note_res(n.available); note_res(n.capacity); }
+      note_res(n.daemonset_requests);
     }
     K = (uint32_t)key_vals.size(); R = (uint32_t)res_id.size(); T = (uint32_t)pr.instance_types.size(); TW = (T + 63) / 64;
     if (K > KS_MAX_KEYS) throw Unsupported("more than 32 distinct label keys on the path");
-    if (R > KS_MAX_RES) throw Unsupported(std::to_string(R) + " distinct resource names (the limit is " + std::to_string(KS_MAX_RES) + ")");
+    if (R > KS_MAX_RES) {
+      if (!active_res) throw Unsupported(std::to_string(R) + " distinct resource names (the limit is " + std::to_string(KS_MAX_RES) + ")");
+      std::set<std::string> all; for (auto& kv : res_id) all.insert(kv.first);
+      for (auto& it : pr.instance_types) for (const ksp::ResList* l : {&it.capacity, &it.overhead}) for (auto& kv : *l) all.insert(kv.first);
+      for (auto& n : pr.nodes) for (const ksp::ResList* l : {&n.available, &n.capacity}) for (auto& kv : *l) all.insert(kv.first);
+      throw Unsupported(std::to_string(R) + " active resource names of " + std::to_string(all.size()) + " (the limit is " + std::to_string(KS_MAX_RES) + " active names)");
+    }
     E.key_names.assign(K, ""); for (auto& kv : key_id) E.key_names[kv.second] = kv.first;
     E.key_values.resize(K); E.key_nvalues.assign(K, 0); E.value_int.assign((size_t)K * 64, INT32_MIN); E.key_members.assign(K, {}); E.key_class.assign(K, {}); E.key_ints.assign(K, {});
     for (uint32_t k = 0; k < K; ++k) {
@@ -499,7 +510,8 @@ struct Builder {
   }
   void res_vec(const ksp::ResList& l, std::vector<int64_t>& out, uint32_t* present) {
     size_t base = out.size(); out.resize(base + R, 0); uint32_t p = 0;
-    for (auto& kv : l) { int r = res_id.at(kv.first); out[base + r] = kv.second; p |= 1u << r; }
+    for (auto& kv : l) { auto f = res_id.find(kv.first); if (f == res_id.end()) { if (active_res) continue; throw std::out_of_range("resource missing from universe: " + kv.first); }      // (an inert name: KSH_ACTIVE_RESOURCES)
+      const int r = f->second; out[base + r] = kv.second; p |= 1u << r; }
     if (present) *present = p;
   }
   uint64_t taint_mask(const std::vector<ksp::Taint>& ts) {
@@ -553,8 +565,8 @@ struct Builder {
         double& pl = E.it_price_lo[(size_t)t * NP + pair]; if (o.price < pl) pl = o.price;  // Offerings.Cheapest the minimum (types.go:141)
       }
       ksp::ResList alloc = Subtract(it.capacity, it.overhead);   // Allocatable(), types.go:87-89
-      for (auto& kv : alloc) E.it_alloc[(size_t)res_id.at(kv.first) * T + t] = kv.second;
-      for (auto& kv : it.capacity) E.it_cap[(size_t)res_id.at(kv.first) * T + t] = kv.second;
+      for (auto& kv : alloc) { auto f = res_id.find(kv.first); if (f != res_id.end()) E.it_alloc[(size_t)f->second * T + t] = kv.second; }      // (every name is in the universe unless it is inert: KSH_ACTIVE_RESOURCES)
+      for (auto& kv : it.capacity) { auto f = res_id.find(kv.first); if (f != res_id.end()) E.it_cap[(size_t)f->second * T + t] = kv.second; }
     } }, 128);
   }
 
@@ -748,7 +760,7 @@ struct Builder {
   void adopt_base() {
     const Builder& b = *base; const Encoded& B = b.E;
     wellKnown = b.wellKnown; key_id = b.key_id; res_id = b.res_id; taint_id = b.taint_id; taints = b.taints; ip_id = b.ip_id; proto_id = b.proto_id;      // (domains: read in place)
-    blocked_taint = b.blocked_taint; toleratePreferNoSchedule = b.toleratePreferNoSchedule; K = b.K; R = b.R; T = b.T; TW = b.TW;
+    active_res = b.active_res; blocked_taint = b.blocked_taint; toleratePreferNoSchedule = b.toleratePreferNoSchedule; K = b.K; R = b.R; T = b.T; TW = b.TW;
     E.key_names = B.key_names; E.key_values = B.key_values; E.key_members = B.key_members; E.key_class = B.key_class; E.key_ints = B.key_ints; E.res_names = B.res_names; E.key_nvalues = B.key_nvalues; E.value_int = B.value_int;
     // the catalogue arrays (it_*) stay the snapshot's: Encoded::shared keeps them alive, finish() points ks_problem at them
     E.templates = B.templates; E.tmpl = B.tmpl; E.tmpl_taints = B.tmpl_taints; E.tmpl_types = B.tmpl_types; E.tmpl_daemon = B.tmpl_daemon; E.tmpl_daemon_present = B.tmpl_daemon_present;
@@ -1310,6 +1322,7 @@ struct Builder {
     ks_problem& p = E.prob;
     p.P = (uint32_t)podp.size(); p.C = E.cls.n; p.T = T; p.M = (uint32_t)E.templates.size(); p.E = (uint32_t)E.existing.size(); p.K = K; p.R = R;
     p.max_new_nodes = p.P ? p.P : 1; p.flags = flags | ((pr.simulation_mode || (base && !env_mode)) ? KS_FLAG_SIMULATION : 0);
+    p.lean_r8 = active_res ? 1u : 0u;      // (the kernel choice that comes with KSH_ACTIVE_RESOURCES: LEAN at up to 8 resources; ksolve.h)
     p.wellknown_mask = 0; for (uint32_t k = 0; k < K; ++k) if (wellKnown.count(E.key_names[k])) p.wellknown_mask |= 1u << k;
     p.key_nvalues = E.key_nvalues.data(); p.value_int = E.value_int.data(); p.key_zone = key_id.at(ksp::kZone); p.key_ct = key_id.at(ksp::kCapacityType); p.n_ct = E.key_nvalues[p.key_ct];
     const Encoded& CAT = E.catalogue(); const Encoded& LAT = E.lattice();

@@ -30,6 +30,7 @@ _LIBS = None
 KS_OK, KS_ERR_INVALID, KS_ERR_UNSUPPORTED, KS_ERR_DEVICE, KS_ERR_CAPACITY = 0, -1, -2, -3, -4
 KS_FLAG_SIMULATION, KS_FLAG_STATS, KS_FLAG_NO_RR, KS_FLAG_ONE_WAVE, KS_FLAG_NO_LEAN = 1, 2, 4, 8, 16
 KSH_DERIVE_VOLUMES = 1 << 16      # kshost.h: derive what-ifs over snapshots with CSI volume limits / claims too (opt-in)
+KSH_ACTIVE_RESOURCES = 1 << 17    # kshost.h: flatten over the resource names the problem requests or limits, not over all a catalogue lists (opt-in)
 KSH_APPLY_TRACK_CLUSTER_PODS = 1  # kshost.h: ksh_env_apply_block mirrors BIND / UNBIND into the cluster pods whatever the snapshot started with
 
 
@@ -70,6 +71,7 @@ def libs():
         kh.ksh_dims.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32)]
         kh.ksh_rr_status.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]
         kh.ksh_pack_width.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]
+        kh.ksh_pack_lean.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]
         kh.ksh_solve_whatifs_sharded.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint64), ctypes.c_uint32, ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]
         ks.ks_deal_lpt.argtypes = [ctypes.POINTER(ctypes.c_uint64), ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]
         ks.ks_deal_lpt.restype = None
@@ -115,14 +117,14 @@ def device_count() -> int:
 class FlatProblem:
     """A Solve() problem flattened to the C-ABI `ks_problem` (host side only until `upload`)."""
 
-    def __init__(self, problem: Optional[Problem], stats: bool = False, _handle=None, flags: int = 0):
+    def __init__(self, problem: Optional[Problem], stats: bool = False, _handle=None, flags: int = 0, active_resources: bool = False):
         ks, kh = libs()
         if _handle is not None:
             self._h = _handle
         else:
             text = problem.to_ksp().encode()
             self._h = ctypes.c_void_p()
-            flags = (KS_FLAG_STATS if stats else 0) | flags      # (KS_FLAG_NO_RR / _ONE_WAVE / _NO_LEAN: the kernel choice travels with the problem)
+            flags = (KS_FLAG_STATS if stats else 0) | (KSH_ACTIVE_RESOURCES if active_resources else 0) | flags      # (KS_FLAG_NO_RR / _ONE_WAVE / _NO_LEAN: the kernel choice travels with the problem)
             rc = kh.ksh_open(text, len(text), flags, ctypes.byref(self._h))
             if rc != KS_OK:
                 raise KSolveError(rc, kh.ksh_last_error().decode())
@@ -182,6 +184,20 @@ class FlatProblem:
         if rc != KS_OK:
             raise KSolveError(rc, "ksh_pack_width")
         return int(out.value)
+
+    def pack_lean(self) -> bool:
+        """Whether the ks_pack variant that took the last solve was a LEAN one (width 4, or 8 for a problem flattened with `active_resources`); False if ks_pack_rr
+        took it.  include/ksolve.h ks_problem_pack_lean."""
+        out = ctypes.c_int()
+        rc = libs()[1].ksh_pack_lean(self._h, ctypes.byref(out))
+        if rc != KS_OK:
+            raise KSolveError(rc, "ksh_pack_lean")
+        return bool(out.value)
+
+    def resource_names(self) -> List[str]:
+        """The resource universe of the flat problem, by id (kshost.h ksh_name(h, 2, r, 0)): with `active_resources` the active names only."""
+        kh = libs()[1]
+        return [kh.ksh_name(self._h, 2, r, 0).decode() for r in range(self.dims["R"])]
 
     def result_arrays(self) -> dict:
         """The result through the binary door (include/kshost.h ksh_result_arrays_get): numpy copies of the arrays plus the key / resource names."""
@@ -363,15 +379,16 @@ class ParsedProblem:
             raise KSolveError(rc, kh.ksh_last_error().decode())
         return out[:n_pods.value], int(n_nodes.value)
 
-    def snapshot_fingerprint(self, pod_node: Optional[Sequence[int]] = None, cold: bool = False, volumes: bool = False) -> int:
+    def snapshot_fingerprint(self, pod_node: Optional[Sequence[int]] = None, cold: bool = False, volumes: bool = False, active_resources: bool = False) -> int:
         """Hash of the snapshot's flattening (flat problem + the tables the device derivation reads); `cold`: of one made from scratch (tests: a flattening
-        continued after `apply` must equal it); `volumes`: of the flattening derived what-ifs with volumes use (KSH_DERIVE_VOLUMES)."""
+        continued after `apply` must equal it); `volumes`: of the flattening derived what-ifs with volumes use (KSH_DERIVE_VOLUMES);
+        `active_resources`: of the flattening over the active resource names (KSH_ACTIVE_RESOURCES)."""
         import numpy as np
         kh = libs()[1]
         kh.ksh_snapshot_fingerprint.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64)]
         pn = None if pod_node is None else np.ascontiguousarray(np.asarray(pod_node, dtype=np.int32))
         out = ctypes.c_uint64()
-        rc = kh.ksh_snapshot_fingerprint(self._p, None if pn is None or pn.size == 0 else pn.ctypes.data, KSH_DERIVE_VOLUMES if volumes else 0, 1 if cold else 0, ctypes.byref(out))
+        rc = kh.ksh_snapshot_fingerprint(self._p, None if pn is None or pn.size == 0 else pn.ctypes.data, (KSH_DERIVE_VOLUMES if volumes else 0) | (KSH_ACTIVE_RESOURCES if active_resources else 0), 1 if cold else 0, ctypes.byref(out))
         if rc != KS_OK:
             raise KSolveError(rc, kh.ksh_last_error().decode())
         return int(out.value)
@@ -391,14 +408,14 @@ class ParsedProblem:
 TIMING_KEYS = ("flatten_ms", "upload_ms", "tables_grid_ms", "pack_kernel_ms", "solve_readback_ms", "total_ms")
 
 
-def solve_from_pods(parsed: ParsedProblem, device: int = 0, stats: bool = False, keep: bool = True):
+def solve_from_pods(parsed: ParsedProblem, device: int = 0, stats: bool = False, keep: bool = True, active_resources: bool = False):
     """Everything the reference does inside NewScheduler + Solve for a pod list it already holds: flatten (incl. NewQueue's
     sort, per-pod requests / requirements / classes / relaxation chains), upload, static tables + feasibility grid, the pack
     kernel, read-back.  Returns (FlatProblem holding the result or None, timings dict in milliseconds)."""
     kh = libs()[1]
     h = ctypes.c_void_p()
     ms = (ctypes.c_double * 6)()
-    rc = kh.ksh_solve_from_pods(parsed._p, device, KS_FLAG_STATS if stats else 0, ctypes.byref(h) if keep else None, ms)
+    rc = kh.ksh_solve_from_pods(parsed._p, device, (KS_FLAG_STATS if stats else 0) | (KSH_ACTIVE_RESOURCES if active_resources else 0), ctypes.byref(h) if keep else None, ms)
     if rc != KS_OK:
         raise KSolveError(rc, kh.ksh_last_error().decode())
     fp = FlatProblem(None, _handle=h) if keep else None
@@ -455,22 +472,22 @@ class PodBatch:
             pass
 
 
-def open_batch(env: ParsedProblem, batch: PodBatch, stats: bool = False) -> FlatProblem:
+def open_batch(env: ParsedProblem, batch: PodBatch, stats: bool = False, active_resources: bool = False) -> FlatProblem:
     """Flatten `batch` against the environment `env` (a ParsedProblem of a Problem WITHOUT pods): host side only, like FlatProblem(problem)."""
     kh = libs()[1]
     h = ctypes.c_void_p()
-    rc = kh.ksh_open_batch(env._p, batch._b, KS_FLAG_STATS if stats else 0, ctypes.byref(h))
+    rc = kh.ksh_open_batch(env._p, batch._b, (KS_FLAG_STATS if stats else 0) | (KSH_ACTIVE_RESOURCES if active_resources else 0), ctypes.byref(h))
     if rc != KS_OK:
         raise KSolveError(rc, kh.ksh_last_error().decode())
     return FlatProblem(None, _handle=h)
 
 
-def solve_from_batch(env: ParsedProblem, batch: PodBatch, device: int = 0, stats: bool = False, keep: bool = True):
+def solve_from_batch(env: ParsedProblem, batch: PodBatch, device: int = 0, stats: bool = False, keep: bool = True, active_resources: bool = False):
     """`solve_from_pods` for a batch that came in through the binary door."""
     kh = libs()[1]
     h = ctypes.c_void_p()
     ms = (ctypes.c_double * 6)()
-    rc = kh.ksh_solve_from_batch(env._p, batch._b, device, KS_FLAG_STATS if stats else 0, ctypes.byref(h) if keep else None, ms)
+    rc = kh.ksh_solve_from_batch(env._p, batch._b, device, (KS_FLAG_STATS if stats else 0) | (KSH_ACTIVE_RESOURCES if active_resources else 0), ctypes.byref(h) if keep else None, ms)
     if rc != KS_OK:
         raise KSolveError(rc, kh.ksh_last_error().decode())
     fp = FlatProblem(None, _handle=h) if keep else None
@@ -480,7 +497,7 @@ def solve_from_batch(env: ParsedProblem, batch: PodBatch, device: int = 0, stats
 
 
 def open_whatifs(snapshot, pod_node: Sequence[int], candidate_sets: Sequence[Sequence[int]], threads: int = 0, stats: bool = False, derive=None, device: int = 0,
-                 volumes: bool = False) -> List[FlatProblem]:
+                 volumes: bool = False, active_resources: bool = False) -> List[FlatProblem]:
     """Flatten N consolidation what-ifs over one cluster snapshot natively (simulateScheduling, deprovisioning/helpers.go:42-115):
     `snapshot` (a `Problem`, or a `ParsedProblem` already held as objects) lists every state node and, as its pod batch, every bound pod
     (full spec); pod_node[i] = node index of pod i.  What-if w removes candidate_sets[w] from the state nodes and makes their pods
@@ -501,13 +518,14 @@ def open_whatifs(snapshot, pod_node: Sequence[int], candidate_sets: Sequence[Seq
     c_cand = flat.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))
     c_pn = None if pn is None else pn.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
     hs = (ctypes.c_void_p * max(1, n))()
+    act = KSH_ACTIVE_RESOURCES if active_resources else 0      # (kshost.h: the snapshot flattened over the names its bound pods, daemonsets and limits name)
     # derive: None = derive the what-ifs on the device when the snapshot allows it (a ParsedProblem without topology terms / volume limits), else flatten
     # them one by one on the host; True = derive or raise; False = always flatten on the host.  Derived what-ifs are resident on `device` at once.
     # volumes: opt in to deriving snapshots with CSI volume limits / claims too (kshost.h KSH_DERIVE_VOLUMES); the host route is the same either way.
     if derive is not False and not stats and n:
         if not isinstance(snapshot, ParsedProblem):
             snapshot = ParsedProblem(snapshot)       # (the handles keep what they need of it alive)
-        rc = kh.ksh_open_whatifs_derived(snapshot._p, KSH_DERIVE_VOLUMES if volumes else 0, n, c_off, c_cand, c_pn, device, hs)
+        rc = kh.ksh_open_whatifs_derived(snapshot._p, (KSH_DERIVE_VOLUMES if volumes else 0) | act, n, c_off, c_cand, c_pn, device, hs)
         if rc == KS_OK:
             return [FlatProblem(None, _handle=ctypes.c_void_p(hs[i])) for i in range(n)]
         if derive is True or rc not in (KS_ERR_UNSUPPORTED, KS_ERR_DEVICE):
@@ -515,16 +533,16 @@ def open_whatifs(snapshot, pod_node: Sequence[int], candidate_sets: Sequence[Seq
     elif derive is True:
         raise KSolveError(KS_ERR_UNSUPPORTED, "derived what-ifs carry no reference-algorithm statistics")
     if isinstance(snapshot, ParsedProblem):
-        rc = kh.ksh_open_whatifs_parsed(snapshot._p, KS_FLAG_STATS if stats else 0, n, c_off, c_cand, c_pn, threads, hs)
+        rc = kh.ksh_open_whatifs_parsed(snapshot._p, (KS_FLAG_STATS if stats else 0) | act, n, c_off, c_cand, c_pn, threads, hs)
     else:
         text = snapshot.to_ksp().encode()
-        rc = kh.ksh_open_whatifs(text, len(text), KS_FLAG_STATS if stats else 0, n, c_off, c_cand, c_pn, threads, hs)
+        rc = kh.ksh_open_whatifs(text, len(text), (KS_FLAG_STATS if stats else 0) | act, n, c_off, c_cand, c_pn, threads, hs)
     if rc != KS_OK:
         raise KSolveError(rc, kh.ksh_last_error().decode())
     return [FlatProblem(None, _handle=ctypes.c_void_p(hs[i])) for i in range(n)]
 
 
-def check_whatif_derivation(snapshot: "ParsedProblem", pod_node: Sequence[int], candidates: Sequence[int], volumes: bool = False) -> None:
+def check_whatif_derivation(snapshot: "ParsedProblem", pod_node: Sequence[int], candidates: Sequence[int], volumes: bool = False, active_resources: bool = False) -> None:
     """Diagnostic, no GPU needed (kshost.h `ksh_check_whatif_derivation`): what the device would derive for this candidate set -- group activity, domain
     counts, hostname rows; with `volumes`, the volume state of every node that stays and the volume test of every pod of the batch on it -- restated on
     the host and compared with the what-if flattened by itself.  Raises KSolveError with the first difference."""
@@ -533,7 +551,7 @@ def check_whatif_derivation(snapshot: "ParsedProblem", pod_node: Sequence[int], 
     cand = np.ascontiguousarray(np.asarray(list(candidates) or [0], dtype=np.uint32))
     pn = None if pod_node is None else (np.ascontiguousarray(np.asarray(pod_node, dtype=np.int32)) if len(pod_node) else np.zeros(1, dtype=np.int32))
     kh.ksh_check_whatif_derivation.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint32, ctypes.POINTER(ctypes.c_int32)]
-    rc = kh.ksh_check_whatif_derivation(snapshot._p, KSH_DERIVE_VOLUMES if volumes else 0, cand.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), len(candidates), None if pn is None else pn.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)))
+    rc = kh.ksh_check_whatif_derivation(snapshot._p, (KSH_DERIVE_VOLUMES if volumes else 0) | (KSH_ACTIVE_RESOURCES if active_resources else 0), cand.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), len(candidates), None if pn is None else pn.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)))
     if rc != KS_OK:
         raise KSolveError(rc, kh.ksh_last_error().decode())
 
@@ -712,8 +730,8 @@ def types_subset(flats: Sequence[FlatProblem], nodes: Sequence[int], type_sets: 
     return [bool(x) for x in out]
 
 
-def solve_problem(problem: Problem, stats: bool = False) -> SolveResult:
-    fp = FlatProblem(problem, stats=stats)
+def solve_problem(problem: Problem, stats: bool = False, active_resources: bool = False) -> SolveResult:
+    fp = FlatProblem(problem, stats=stats, active_resources=active_resources)
     try:
         return fp.solve()
     finally:
@@ -727,6 +745,7 @@ def solve_problem(problem: Problem, stats: bool = False) -> SolveResult:
 class SchedulerOptions:
     """scheduling.SchedulerOptions, scheduler.go:36-40."""
     SimulationMode: bool = False
+    ActiveResources: bool = False      # not the reference's: flatten over the resource names the batch requests or limits (kshost.h KSH_ACTIVE_RESOURCES); same decisions
 
 
 @dataclass
@@ -816,7 +835,7 @@ class Scheduler:
         problem = Problem(instance_types=self.instance_types, provisioners=self.provisioners, pods=list(pods),
                           daemonset_pods=self.daemonset_pods, nodes=self.state_nodes, cluster_pods=self.cluster_pods,
                           extra_well_known=self.extra_well_known, simulation_mode=self.opts.SimulationMode)
-        res = solve_problem(problem)
+        res = solve_problem(problem, active_resources=self.opts.ActiveResources)
         self.last_result = res
         by_name = {it.name: it for it in self.instance_types}
         nodes = [Node(n.provisioner, [pods[i] for i in n.pods], [by_name[x] for x in n.instance_types], n.requirements, n.requests)

@@ -572,3 +572,32 @@ def _densify(pr: Problem, catalogue: List[str], seed: int) -> Problem:
     pr.daemonset_pods = pr.daemonset_pods + [Pod(uid="wide-ds-gpu", node_selector={LABEL_PROVISIONER: "gpu"}, tolerations=[Toleration(key=GPU_TAINT.key, operator="Exists")],
                                                  containers=[Container(requests={"cpu": "10m", "vpc.amazonaws.com/efa": "1"})])]
     return pr
+
+
+# ---- any problem dressed in a cloud provider's catalogue ----
+# names 17.. of a dressing: what further device plugins add (WIDE_NAMES stops at the 16 the wide kernels hold)
+CLOUD_EXTRA_NAMES = ["gpu.intel.com/i915", "squat.ai/video", "devices.kubevirt.io/kvm", "example.com/dongle", "example.com/tpm", "example.com/sgx-epc"]
+
+
+def cloud_catalogue(problem: Problem, names: int = 12, seed: int = 0) -> Problem:
+    """A deep copy of `problem` whose instance types and state nodes all list the first `names` (up to 22) of WIDE_NAMES + CLOUD_EXTRA_NAMES, the way a cloud
+    provider's catalogue does: a name a type or node already carries keeps its quantity, every other one is added -- 0 on most types (`wide_catalogue` does the
+    same), a few devices on some; a node gets the added names in `capacity` and `available` alike.  Pods, daemonsets and provisioners are untouched, so the
+    added names are requested and limited by nothing unless the problem already did: every decision is the undressed problem's."""
+    import copy
+    pool = WIDE_NAMES + CLOUD_EXTRA_NAMES
+    assert 1 <= names <= len(pool)
+    rs = np.random.RandomState(29000 + seed)
+    pr = copy.deepcopy(problem)
+    for it in pr.instance_types:
+        for n in pool[:names]:
+            if n not in it.capacity:
+                it.capacity[n] = str(int(rs.choice([1, 2, 4, 8]))) if rs.rand() < 0.15 else "0"
+    for nd in pr.nodes:
+        for n in pool[:names]:
+            q = str(int(rs.choice([1, 2]))) if rs.rand() < 0.15 else "0"
+            if n not in nd.capacity:
+                nd.capacity[n] = q
+            if n not in nd.available:
+                nd.available[n] = q if nd.capacity[n] == q else "0"
+    return pr
