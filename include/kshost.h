@@ -15,6 +15,9 @@
  *   ksh_open_whatifs          deprovisioning.simulateScheduling's problem construction for N candidate sets over ONE cluster snapshot
  *                             (helpers.go:42-99): candidates leave the state nodes, their pods become the batch.
  *   ksh_price_filter          filterByPrice / worstLaunchPrice on results still on the device (helpers.go:148-157,292-315).
+ *   ksh_consolidation_commands / ksh_first_n_node_option / ksh_single_node_option
+ *                             computeConsolidation (consolidation.go:190-274) and the two searches built on it (multinodeconsolidation.go:74-165,
+ *                             singlenodeconsolidation.go:54-78): snapshot and candidate sets in, fixed-size command rows out, decided on the device.
  *   ksh_result_text / ksh_result_summary
  *                             what callers read from Solve's return values: KSR1 text (Node.Pods, InstanceTypeOptions,
  *                             Requirements, Requests, ExistingNode.Pods, unscheduled queue, relaxation stages), or the fixed-size record
@@ -199,6 +202,56 @@ int ksh_open_whatifs_parsed(void* parsed_snapshot, uint32_t flags, uint32_t n, c
  * stays, the volume counts and limits per driver and the multi claims it lists, and for every pod of the batch on every such node whether the volume test
  * admits it and what it adds per driver -- against the what-if's own (candidate-dependent) partition. */
 int ksh_check_whatif_derivation(void* parsed_snapshot, uint32_t flags, const uint32_t* cand, uint32_t ncand, const int32_t* pod_node);
+
+/* ---- consolidation COMMANDS, decided on the device (deprovisioning/consolidation.go:190-274 computeConsolidation, multinodeconsolidation.go:74-165
+ * firstNNodeConsolidationOption + filterOutSameType, singlenodeconsolidation.go:54-78 the scan of SingleNodeConsolidation.ComputeCommand): snapshot and candidate
+ * sets in, one fixed-size row per candidate set out (layout: ksolve.h KS_CMD_*, KS_CMD_ROW_WORDS(words) uint64 each, words >= ceil(T/64)).
+ * ksh_consolidation_commands opens the what-ifs derived on the device (flags: KS_FLAG_SIMULATION / _NO_RR / _ONE_WAVE / _NO_LEAN, KSH_DERIVE_VOLUMES,
+ * KSH_ACTIVE_RESOURCES; any other bit is KS_ERR_INVALID) -- flattened one by one and uploaded where ksh_open_whatifs_derived answers KS_ERR_UNSUPPORTED --, solves
+ * them resident in one launch, decides all of them in one more (ks_consolidation_commands_dev), reads the rows back and closes the handles.  Nothing but the rows
+ * crosses back: no result is decoded on the host.  What the decision reads beside the simulation comes from the parsed nodes' labels:
+ *   node.kubernetes.io/instance-type, topology.kubernetes.io/zone, karpenter.sh/capacity-type of every candidate: getNodePrices (the sum, in candidate order, of
+ *     Offerings.Get -- the parsed offerings, available or not: types.go:117-124 does not consult availability), "all candidates are spot", and per distinct
+ *     candidate type the lowest such price (0.0 if none of its candidates has an offering: Go's map miss) for filterOutSameType;
+ *   karpenter.sh/initialized, karpenter.sh/provisioner-name and in_state of every node that STAYS: one owned, in-state node that is not initialised makes the
+ *     simulation count as "not all pods scheduled" (helpers.go:102-113).
+ * deleting[n_deleting]: nodes that leave EVERY what-if with their pods joining its batch.  Owned ones are the nodes marked for deletion (helpers.go:48-61,81-84):
+ *   they leave last, and a candidate set that names one gets an error row (KS_CMD_ERROR, KS_CMD_WHY_DELETING: helpers.go:62-67) and is not simulated.  Pending pods
+ *   stay the caller's business, as with ksh_open_whatifs*: bind them to ONE extra node of the snapshot that no provisioner owns (no labels, no cluster-pod records)
+ *   and list that node here; an unowned node of `deleting` leaves first (the pending pods head the batch, helpers.go:76-79).
+ * same_type != 0: also filterOutSameType on every replace (KS_CMD_F_SAME_TYPE; the row then carries both stages).  ms[5] (may be NULL): [0] open, [1] solve,
+ * [2] command kernel (inputs up, launch, completion), [3] read-back of the rows, [4] the host work around them (the per-what-if inputs, closing the handles),
+ * milliseconds: the five sum to the call.  Row i answers candidate set i; row[KS_CMD_ID] = i.
+ * What the decision reads of the nodes' labels is tabulated by the first command call over a snapshot and kept with it until ksh_env_apply* changes the nodes.
+ * Whole-call refusals, nothing opened: KS_ERR_INVALID for an unknown flag bit, words < ceil(T/64), offsets that do not ascend, a node index out of range, and for a
+ * candidate (other than the unowned carrier of pending pods, which belongs in `deleting`) whose instance-type label names no type of the catalogue -- candidateNodes
+ * never yields such a node (helpers.go:165-230), so it is a caller's mistake, not a per-set error row like a deleting candidate.  KS_ERR_UNSUPPORTED, after the
+ * what-ifs were flattened but before anything is uploaded or launched: on the fallback route a what-if that needs instance-type requirement states of its own (a
+ * row's KS_CMD_IT_STATE is read through the snapshot's lattice); such a batch goes through ksh_open_whatifs_parsed / ksh_result_text. */
+int ksh_consolidation_commands(void* parsed_snapshot, uint32_t flags, uint32_t n, const uint32_t* cand_off /* [n+1] */, const uint32_t* cand, const int32_t* pod_node /* or NULL after ksh_env_apply */,
+                               const uint32_t* deleting, uint32_t n_deleting, int device, int same_type, uint64_t* out_rows /* [n][KS_CMD_ROW_WORDS(words)] */, uint32_t words, double* ms /* [5] or NULL */);
+/* firstNNodeConsolidationOption: every prefix candidates[0 .. mid] the binary search could probe (mid = 1 .. min(max_nodes, n - 1)) in ONE batch with same_type = 1,
+ * then the search of multinodeconsolidation.go:86-114 replayed over the rows: out_row is the row of the longest prefix the search settled on (action delete or
+ * replace; the launch options are the row's SECOND stage), all zero (do-nothing) if there is none, or the error row of a prefix the search probed (:92-95).
+ * out_row[KS_CMD_ID] = the number of leading candidates the command removes. */
+int ksh_first_n_node_option(void* parsed_snapshot, uint32_t flags, const uint32_t* candidates, uint32_t n, uint32_t max_nodes /* the reference passes 100 */, const int32_t* pod_node,
+                            const uint32_t* deleting, uint32_t n_deleting, int device, uint64_t* out_row /* [KS_CMD_ROW_WORDS(words)] */, uint32_t words, double* ms /* [5] or NULL */);
+/* The scan of SingleNodeConsolidation.ComputeCommand: every singleton in ONE batch; out_row is the first delete or replace in candidate order -- error rows are
+ * passed over, as the reference logs and continues --, all zero (do-nothing) if there is none.  out_row[KS_CMD_ID] = the position of that candidate. */
+int ksh_single_node_option(void* parsed_snapshot, uint32_t flags, const uint32_t* candidates, uint32_t n, const int32_t* pod_node, const uint32_t* deleting, uint32_t n_deleting,
+                           int device, uint64_t* out_row, uint32_t words, double* ms);
+/* The rows of handles whose results are on the device (ksh_solve_batch_resident / ksh_solve / ...; derived or not), for a caller that keeps its what-ifs open or
+ * shards them itself: ks_consolidation_commands_host (ksolve.h) over handles, the per-what-if inputs built by the caller. */
+int ksh_command_rows(void** handles, uint32_t n, const uint64_t* ids, const ks_command_inputs* in, uint32_t words, uint64_t* out_rows, double* ms /* [2] or NULL */);
+/* Turning a row into strings without a handle: what 0 = requirement key a (KS_CMD_MASK + a), 1 = value b of key a (bit b of that mask; a key encoded over value
+ * classes names one member per class, as ksh_name does), 3 = state node a (a candidate index), 4 = instance type a (bit a of the option masks).  Keys and values
+ * are the snapshot's flattening's: available once a what-if call flattened it.  NULL when out of range; the strings live as long as the snapshot is neither
+ * changed (ksh_env_apply*) nor freed.  A requirement reads: present bit k of row[KS_CMD_PRESENT], complement bit k of its high half, values = the mask's bits,
+ * greaterThan / lessThan = the low / high half of row[KS_CMD_BOUNDS + k] unless KS_NO_BOUND_GT / KS_NO_BOUND_LT.  row[KS_CMD_IT_STATE] != 0: the node also carries
+ * a requirement on node.kubernetes.io/instance-type, spelled out by ksh_snapshot_it_state (complement, number of values) / ksh_snapshot_it_state_value. */
+const char* ksh_snapshot_name(void* parsed_snapshot, int what, uint32_t a, uint32_t b);
+int ksh_snapshot_it_state(void* parsed_snapshot, uint32_t state, int* complement, uint32_t* n_values);
+const char* ksh_snapshot_it_state_value(void* parsed_snapshot, uint32_t state, uint32_t i);
 
 /* ---- the snapshot kept current by EVENTS ("cached incremental SoA builder fed from state.Cluster") ----
  * Replaces, for the snapshot consolidation simulates over, what the reference does between two passes of the deprovisioner (deprovisioning/controller.go:64,

@@ -8,6 +8,8 @@
  *                                     (multinodeconsolidation.go:74-114, singlenodeconsolidation.go:43-78)
  *   ks_price_filter_dev          <->  filterByPrice / worstLaunchPrice on a what-if's replacement node,
  *                                     deprovisioning/helpers.go:148-157,292-315 (consolidation.go:238, multinodeconsolidation.go:164)
+ *   ks_consolidation_commands_dev <-> computeConsolidation's decision over a what-if's result, deprovisioning/consolidation.go:190-274,
+ *                                     and filterOutSameType, multinodeconsolidation.go:132-165
  *   ks_feasibility_grid          <->  filterInstanceTypesByRequirements for a fresh node, node.go:137-159
  *                                     (compatible && fits && hasOffering over every instance type)
  *   ks_probe_*                   <->  Requirement.Intersection/Has/Operator/Len, Requirements.Compatible
@@ -355,6 +357,69 @@ int ks_feasibility_grid_install(ks_dev_problem* d, uint32_t row_lo, uint32_t row
  * spot_only may be NULL.  One launch for the whole batch. */
 int ks_price_filter_dev(ks_dev_problem* const* ds, uint32_t n, const uint32_t* node, const double* max_price,
                         const uint32_t* spot_only, uint64_t* const* out_types, uint32_t* out_counts);
+
+/* ---- consolidation commands, decided on the device (deprovisioning/consolidation.go:190-274 computeConsolidation; multinodeconsolidation.go:132-165
+ * filterOutSameType): for problem i, over the result the last ks_solve*_dev of ds[i] left on the device, ONE fixed-size row of uint64 in a caller-owned DEVICE
+ * buffer d_out[n][KS_CMD_ROW_WORDS(words)] -- like ks_batch_records_dev's it can be handed to an all-gather without a host hop.  One launch for the batch (one wave
+ * per what-if), on ds[0]'s stream; the buffer is complete when the call returns.  Every word of every row is written (words beyond a problem's ceil(T/64) are zero).
+ *
+ * The steps, in the reference's order: (1) blocked or n_unscheduled > 0 -> do-nothing; (2) n_new == 0 -> delete; (3) n_new != 1 -> do-nothing; (4) price error ->
+ * error; (5) filterByPrice of new node 0's InstanceTypeOptions under its zone / capacity-type requirements against cand_price -- the arithmetic of
+ * ks_price_filter_dev --; (6) nothing kept -> do-nothing; (7) all candidates spot and the capacity-type requirement Has(spot) -> do-nothing; (8) capacity type
+ * Has(spot) and Has(on-demand) -> the command is narrowed to spot (:262-265); (9) with KS_CMD_F_SAME_TYPE, filterOutSameType: max_price = the lowest listed price
+ * among the listed types that step 5 kept (MaxFloat64 if none is), the kept options priced again -- as spot only if step 8 narrowed -- against it; nothing left ->
+ * do-nothing.  Prices are only compared on the device: getNodePrices' sum is made by the caller, in candidate order (float64 addition does not commute with a
+ * reduction tree), and arrives as cand_price. */
+#define KS_CMD_F_BLOCKED 1u      /* an owned, in-state node that is not initialised stays in the cluster: simulateScheduling reports "not all pods scheduled" (helpers.go:102-113) */
+#define KS_CMD_F_ALL_SPOT 2u     /* every candidate's capacity type is spot (consolidation.go:250) */
+#define KS_CMD_F_PRICE_ERROR 4u  /* getNodePrices failed for a candidate (consolidation.go:224-228, 277-287) */
+#define KS_CMD_F_SAME_TYPE 8u    /* also run filterOutSameType (what firstNNodeConsolidationOption does with a replace, multinodeconsolidation.go:97-106) */
+#define KS_CMD_F_ALL 15u
+typedef struct ks_command_inputs {
+  const uint32_t* flags;      /* [n]   KS_CMD_F_*; any other bit: KS_ERR_INVALID */
+  const double* cand_price;   /* [n]   getNodePrices of the candidate set (ignored under KS_CMD_F_PRICE_ERROR) */
+  const uint32_t* type_off;   /* [n+1] CSR into type_idx / type_price: one entry per DISTINCT instance type among what-if i's candidates (read under KS_CMD_F_SAME_TYPE) */
+  const uint32_t* type_idx;   /*       instance-type index (< T) */
+  const double* type_price;   /*       the lowest Offerings.Get price among the candidates of that type; 0.0 if none of them has an offering: the Go map miss of
+                                       multinodeconsolidation.go:150-158 */
+} ks_command_inputs;
+/* the row: words of uint64 */
+#define KS_CMD_ID 0                  /* ids[i] */
+#define KS_CMD_DECISION 1            /* action | reason << 8 | narrowed << 16.  narrowed: step 8 replaced the capacity-type requirement by In [spot]; the requirement
+                                        words below carry that.  (In a catalogue with no capacity type called spot the value has no bit: the mask is then empty
+                                        and this flag alone says In [spot].)  Under KS_CMD_F_SAME_TYPE a row whose step 9 kept nothing reads do-nothing / KS_CMD_WHY_SAME_TYPE and
+                                        KEEPS this bit and the narrowed requirement words: they describe the replace step 9 turned down. */
+#define KS_CMD_N_NEW 2
+#define KS_CMD_N_UNSCHEDULED 3
+#define KS_CMD_N_OPTIONS 4           /* types step 5 kept */
+#define KS_CMD_N_OPTIONS_SAME_TYPE 5 /* types step 9 kept (0 without KS_CMD_F_SAME_TYPE) */
+#define KS_CMD_PRESENT 6             /* new node 0's Requirements (zero if there is none), after step 8's narrowing: present | complement << 32 */
+#define KS_CMD_IT_STATE 7            /* ... its instance-type key state (ks_result.node_it_state) */
+#define KS_CMD_MASK 8                /* ... [KS_MAX_KEYS] value masks, key k at KS_CMD_MASK + k (zero for k >= K) */
+#define KS_CMD_BOUNDS 40             /* ... [KS_MAX_KEYS] (uint32_t)gt | (uint64_t)(uint32_t)lt << 32 */
+#define KS_CMD_OPTIONS 72            /* [words] what step 5 kept: a plain computeConsolidation caller's replacement InstanceTypeOptions; then [words] what step 9 kept:
+                                        what firstNNodeConsolidationOption launches.  Both zero where the step did not run. */
+#define KS_CMD_ROW_WORDS(words) (KS_CMD_OPTIONS + 2 * (size_t)(words))
+/* action (KS_CMD_DECISION & 0xff).  Under KS_CMD_F_SAME_TYPE the action is firstNNodeConsolidationOption's: a replace whose step 9 kept nothing reads do-nothing
+ * with KS_CMD_WHY_SAME_TYPE, and step 5's options stay in the row. */
+#define KS_CMD_DO_NOTHING 0
+#define KS_CMD_DELETE 1
+#define KS_CMD_REPLACE 2
+#define KS_CMD_ERROR 3
+/* reason ((KS_CMD_DECISION >> 8) & 0xff): the step that said do-nothing / error; 0 for delete and replace */
+#define KS_CMD_WHY_NOT_ALL_SCHEDULED 1 /* step 1 */
+#define KS_CMD_WHY_MANY_NODES 3        /* step 3 */
+#define KS_CMD_WHY_PRICE_ERROR 4       /* step 4 (action error) */
+#define KS_CMD_WHY_NOT_CHEAPER 6       /* step 6 */
+#define KS_CMD_WHY_SPOT_TO_SPOT 7      /* step 7 */
+#define KS_CMD_WHY_SAME_TYPE 9         /* step 9 left nothing */
+#define KS_CMD_WHY_DELETING 10         /* written by libkshost, never by the kernel: a candidate is itself being deleted (action error, helpers.go:62-67) */
+/* Refusals (KS_ERR_INVALID, nothing launched): a batch over two devices, a problem without prices or without zone / capacity-type keys, words < ceil(T/64),
+ * type_off not ascending, a type index >= T, an unknown flag bit. */
+int ks_consolidation_commands_dev(ks_dev_problem* const* ds, uint32_t n, const uint64_t* ids, const ks_command_inputs* in, uint32_t words, void* d_out);
+/* The same with the rows brought to HOST memory out_rows[n][KS_CMD_ROW_WORDS(words)] (one launch, one device-to-host copy); ms (may be NULL): [0] inputs up + launch +
+ * completion, [1] the read-back, milliseconds.  The inputs are validated once, before any device work. */
+int ks_consolidation_commands_host(ks_dev_problem* const* ds, uint32_t n, const uint64_t* ids, const ks_command_inputs* in, uint32_t words, uint64_t* out_rows, double* ms);
 
 /* Launch-time instance-type pick of the reference's in-memory provider (cloudprovider/fake/cloudprovider.go:79-84: order the machine's
  * InstanceTypeOptions by `Offerings.Available().Requirements(reqs).Cheapest().Price`, types.go:126-145, and take the first): for problem i,

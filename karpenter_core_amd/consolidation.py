@@ -442,3 +442,90 @@ def single_node_consolidation_option(snapshot: Snapshot, candidates: Sequence[in
         if cmd.action in (ACTION_REPLACE, ACTION_DELETE):
             return cmd
     return Command()
+
+
+# =====================================================================================================
+# The same three decisions through the C ABI's command rows (include/kshost.h ksh_consolidation_commands, ksh_first_n_node_option, ksh_single_node_option): the
+# what-ifs are derived, solved and DECIDED on the device (ks_consolidation_commands, csrc/ksolve.hip); no result is decoded on the host, the price stage makes no
+# second trip.  Same Command objects as the functions above, which stay as they are.
+# =====================================================================================================
+_CMD_ERRORS = {4: "unable to determine offering for a candidate node", 10: "candidate node is deleting"}
+
+
+def _command_snapshot(snapshot: Snapshot):
+    """The snapshot as the C ABI takes it: (ParsedProblem, pod_node, nodes that leave every what-if -- the carrier of the pending pods, then the deleting nodes)."""
+    from . import scheduler, workloads
+    PENDING = "~pending~"
+    nodes, bound = list(snapshot.nodes), list(snapshot.bound)
+    leaving = []
+    if snapshot.pending:
+        leaving.append(len(nodes))
+        nodes.append(StateNode(name=PENDING)); bound.append(list(snapshot.pending))
+    leaving += [int(j) for j in snapshot.deleting]
+    snap, pod_node = workloads.snapshot_problem(snapshot.instance_types, snapshot.provisioner, nodes, bound)
+    snap.cluster_pods = [cp for cp in snap.cluster_pods if cp.node_name != PENDING]      # pending pods are bound nowhere: countDomains does not see them
+    return scheduler.ParsedProblem(snap), pod_node, leaving
+
+
+def _command_of_row(snapshot: Snapshot, parsed, row, words: int, cands: Sequence[int], second_stage: bool = False) -> Command:
+    from . import scheduler as S
+    d = S.decode_command_row(parsed, row, words)
+    if d["action"] == S.KS_CMD_ERROR:
+        return Command(error=_CMD_ERRORS.get(d["reason"], "error"))
+    names = [snapshot.nodes[j].name for j in cands]
+    if d["action"] == S.KS_CMD_DELETE:
+        return Command(ACTION_DELETE, names)
+    if d["action"] != S.KS_CMD_REPLACE:
+        return Command()
+    keep = set(d["options_same_type"] if second_stage else d["options"])
+    options = [snapshot.instance_types[t].name for t in snapshot.provisioner.instance_types if t in keep]      # filterByPrice preserves the option order (lo.Filter)
+    return Command(ACTION_REPLACE, names, options, d["requirements"])
+
+
+def _words(snapshot: Snapshot) -> int:
+    return (len(snapshot.instance_types) + 63) // 64
+
+
+def compute_consolidations_dev(snapshot: Snapshot, candidate_sets: Sequence[Sequence[int]], timings: Optional[dict] = None) -> List[Command]:
+    """`compute_consolidations` through `ksh_consolidation_commands`: one call, one command per candidate set.  `timings` (a dict) receives the call's open / solve /
+    command kernel / read-back milliseconds."""
+    from . import scheduler as S
+    parsed, pod_node, leaving = _command_snapshot(snapshot)
+    try:
+        rows, ms = S.consolidation_commands(parsed, pod_node, candidate_sets, _words(snapshot), deleting=leaving)
+        if timings is not None:
+            timings.update(ms)
+        return [_command_of_row(snapshot, parsed, rows[i], _words(snapshot), cs) for i, cs in enumerate(candidate_sets)]
+    finally:
+        parsed.close()
+
+
+def first_n_node_consolidation_option_dev(snapshot: Snapshot, candidates: Sequence[int], max_nodes: int = 100, timings: Optional[dict] = None) -> Command:
+    """`first_n_node_consolidation_option` through `ksh_first_n_node_option`: every prefix AND its filterOutSameType in one batch, the search replayed in the library."""
+    from . import scheduler as S
+    parsed, pod_node, leaving = _command_snapshot(snapshot)
+    try:
+        row, ms = S.first_n_node_option(parsed, pod_node, candidates, _words(snapshot), max_nodes=max_nodes, deleting=leaving)
+        if timings is not None:
+            timings.update(ms)
+        cmd = _command_of_row(snapshot, parsed, row, _words(snapshot), list(candidates[: int(row[S.KS_CMD_ID])]), second_stage=True)
+        if cmd.error is not None:
+            raise ValueError(cmd.error)
+        return cmd
+    finally:
+        parsed.close()
+
+
+def single_node_consolidation_option_dev(snapshot: Snapshot, candidates: Sequence[int], timings: Optional[dict] = None) -> Command:
+    """`single_node_consolidation_option` through `ksh_single_node_option`."""
+    from . import scheduler as S
+    parsed, pod_node, leaving = _command_snapshot(snapshot)
+    try:
+        row, ms = S.single_node_option(parsed, pod_node, candidates, _words(snapshot), deleting=leaving)
+        if timings is not None:
+            timings.update(ms)
+        if (int(row[S.KS_CMD_DECISION]) & 0xFF) == S.KS_CMD_DO_NOTHING:
+            return Command()
+        return _command_of_row(snapshot, parsed, row, _words(snapshot), [candidates[int(row[S.KS_CMD_ID])]])
+    finally:
+        parsed.close()

@@ -20,6 +20,8 @@
 //                         others evaluate the next queued pods against the same snapshot (speculation rounds,
 //                         resolved exactly) and scan ahead for pods whose first fit lies deep in the order.
 //   ks_price_filter       consolidation price stage (filterByPrice / worstLaunchPrice) on device-resident results.
+//   ks_consolidation_commands  computeConsolidation's decision (and filterOutSameType) per what-if over the same results:
+//                         one fixed-size row of u64 each, into a caller-owned device buffer.
 //   ks_gather             batched read-back of a what-if batch's results.
 //
 // The reference functions each device function restates are cited inline (paths relative to
@@ -2738,6 +2740,7 @@ __global__ void ks_probe_has_kernel(ks_req1 a, const i32* vint, u32 nv, ks_req_f
 // Device / pinned-host buffer cache.  A controller solves every few seconds with problems of similar size: hipMalloc / hipFree /
 // hipHostMalloc per Solve would cost more than the upload itself, so freed blocks are kept (per device, by power-of-two size
 // class, a few of each) and handed out again.  Thread-safe; blocks never migrate between devices.
+#include <chrono>
 #include <mutex>
 #include <thread>
 #include <map>
@@ -3653,37 +3656,50 @@ extern "C" int ks_solve_batch_sharded(ks_dev_problem* const* const* shards, cons
 // :292-315) on a what-if's replacement node while its result is still on the device.  One block per problem,
 // lane w owns word w of the node's InstanceTypeOptions; float64 compares only (prices are never added here).
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(64) void ks_price_filter(const DevProb* probs, const DevState* states, const u32* node, const double* max_price, const u32* spot_only, u64* const* outs, u32* counts) {
-  const DevProb& P = probs[blockIdx.x]; const DevState& S = states[blockIdx.x];
-  const u32 j = node[blockIdx.x]; const double maxp = max_price[blockIdx.x]; const int lane = threadIdx.x;
+// What worstLaunchPrice reads of a node's requirements (helpers.go:292-315): the zones it admits, whether its capacity-type requirement Has(spot) /
+// Has(on-demand) -- spot_only: after Requirements.Add(capacity-type In [spot]) --, the stride of the price table.
+struct PriceCtx { u64 allowZ; u32 NP; bool spot, od; };
+__device__ __forceinline__ PriceCtx price_ctx(const DevProb& P, const DevState& S, u32 j, bool spot_only) {
   const u32 pres = S.o_present[j], comp = S.o_complement[j];
   // reqs.Get(key): a missing key reads as Exists (requirements.go:114-120), which Has() every value
   const KReq zq = ((pres >> P.key_zone) & 1u) ? load_req(pres, comp, S.o_mask + (size_t)j * P.K, S.o_gt + (size_t)j * P.K, S.o_lt + (size_t)j * P.K, P.key_zone) : kreq_exists();
   const KReq cq = ((pres >> P.key_ct) & 1u) ? load_req(pres, comp, S.o_mask + (size_t)j * P.K, S.o_gt + (size_t)j * P.K, S.o_lt + (size_t)j * P.K, P.key_ct) : kreq_exists();
-  const u64 allowZ = kreq_has_mask(zq, P.value_int + P.key_zone * 64, P.key_nvalues[P.key_zone]);
+  PriceCtx c; c.allowZ = kreq_has_mask(zq, P.value_int + P.key_zone * 64, P.key_nvalues[P.key_zone]);
   u64 allowC = kreq_has_mask(cq, P.value_int + P.key_ct * 64, P.key_nvalues[P.key_ct]);
-  if (spot_only && spot_only[blockIdx.x]) allowC &= P.ct_spot >= 0 ? (1ull << P.ct_spot) : 0ull;     // Requirements.Add(capacity-type In [spot])
-  const u32 NP = P.key_nvalues[P.key_zone] * P.n_ct;
-  const bool spot = P.ct_spot >= 0 && ((allowC >> P.ct_spot) & 1ull), od = P.ct_ondemand >= 0 && ((allowC >> P.ct_ondemand) & 1ull);
+  if (spot_only) allowC &= P.ct_spot >= 0 ? (1ull << P.ct_spot) : 0ull;     // Requirements.Add(capacity-type In [spot])
+  c.NP = P.key_nvalues[P.key_zone] * P.n_ct;
+  c.spot = P.ct_spot >= 0 && ((allowC >> P.ct_spot) & 1ull); c.od = P.ct_ondemand >= 0 && ((allowC >> P.ct_ondemand) & 1ull);
+  return c;
+}
+// filterByPrice over one word of a type mask (helpers.go:148-157): of the types `bits` names in word w, those whose worst launch price is < maxp
+__device__ __forceinline__ u64 price_filter_word(const DevProb& P, const PriceCtx& c, u64 bits, u32 w, double maxp) {
+  u64 out = 0;
+  for (; bits; bits &= bits - 1) {
+    const u32 b = (u32)__builtin_ctzll(bits), t = w * 64 + b; const u64 offer = P.it_offer[t];
+    double launch = 1.7976931348623157e308; bool got = false;      // math.MaxFloat64
+    if (c.spot) {          // "we prefer to launch spot offerings": the worst (highest) spot price in the allowed zones
+      double mx = 0.0;
+      for (u64 zz = c.allowZ; zz; zz &= zz - 1) { const u32 pair = (u32)__builtin_ctzll(zz) * P.n_ct + (u32)P.ct_spot; if (pair < 64 && ((offer >> pair) & 1ull)) { const double pr = P.it_price[(size_t)t * c.NP + pair]; if (!got || pr > mx) mx = pr; got = true; } }
+      if (got) launch = mx;
+    }
+    if (!got && c.od) {
+      double mx = 0.0;
+      for (u64 zz = c.allowZ; zz; zz &= zz - 1) { const u32 pair = (u32)__builtin_ctzll(zz) * P.n_ct + (u32)P.ct_ondemand; if (pair < 64 && ((offer >> pair) & 1ull)) { const double pr = P.it_price[(size_t)t * c.NP + pair]; if (!got || pr > mx) mx = pr; got = true; } }
+      if (got) launch = mx;
+    }
+    if (launch < maxp) out |= 1ull << b;
+  }
+  return out;
+}
+__global__ __launch_bounds__(64) void ks_price_filter(const DevProb* probs, const DevState* states, const u32* node, const double* max_price, const u32* spot_only, u64* const* outs, u32* counts) {
+  const DevProb& P = probs[blockIdx.x]; const DevState& S = states[blockIdx.x];
+  const u32 j = node[blockIdx.x]; const double maxp = max_price[blockIdx.x]; const int lane = threadIdx.x;
+  const PriceCtx c = price_ctx(P, S, j, spot_only && spot_only[blockIdx.x]);
   u32 kept = 0;
   for (u32 wbase = 0; wbase < P.TW; wbase += 64) {
     const u32 w = wbase + lane; u64 out = 0;
     if (w < P.TW) {
-      for (u64 bits = S.n_alive[(size_t)j * P.TW + w]; bits; bits &= bits - 1) {
-        const u32 b = (u32)__builtin_ctzll(bits), t = w * 64 + b; const u64 offer = P.it_offer[t];
-        double launch = 1.7976931348623157e308; bool got = false;      // math.MaxFloat64
-        if (spot) {          // "we prefer to launch spot offerings": the worst (highest) spot price in the allowed zones
-          double mx = 0.0;
-          for (u64 zz = allowZ; zz; zz &= zz - 1) { const u32 pair = (u32)__builtin_ctzll(zz) * P.n_ct + (u32)P.ct_spot; if (pair < 64 && ((offer >> pair) & 1ull)) { const double pr = P.it_price[(size_t)t * NP + pair]; if (!got || pr > mx) mx = pr; got = true; } }
-          if (got) launch = mx;
-        }
-        if (!got && od) {
-          double mx = 0.0;
-          for (u64 zz = allowZ; zz; zz &= zz - 1) { const u32 pair = (u32)__builtin_ctzll(zz) * P.n_ct + (u32)P.ct_ondemand; if (pair < 64 && ((offer >> pair) & 1ull)) { const double pr = P.it_price[(size_t)t * NP + pair]; if (!got || pr > mx) mx = pr; got = true; } }
-          if (got) launch = mx;
-        }
-        if (launch < maxp) out |= 1ull << b;
-      }
+      out = price_filter_word(P, c, S.n_alive[(size_t)j * P.TW + w], w, maxp);
       outs[blockIdx.x][w] = out;
     }
     u32 pc = (u32)__builtin_popcountll(out); for (int off = 32; off > 0; off >>= 1) pc += __shfl_xor(pc, off);
@@ -3719,6 +3735,152 @@ extern "C" int ks_price_filter_dev(ks_dev_problem* const* ds, uint32_t n, const 
   HIPCHK(hipMemcpyAsync(out_counts, dcnt, n * sizeof(u32), hipMemcpyDeviceToHost, ds[0]->stream));
   HIPCHK(hipStreamSynchronize(ds[0]->stream)); HIPCHK(hipGetLastError());
   for (u32 i = 0; i < n; ++i) memcpy(out_types[i], host.data() + off[i], ds[i]->h.TW * sizeof(u64));
+  return KS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// computeConsolidation (deprovisioning/consolidation.go:190-274) and filterOutSameType (multinodeconsolidation.go:132-165) over results that are
+// still on the device: one wave per what-if, one fixed-size row of u64 out (layout: ksolve.h KS_CMD_*).  Lane w owns words w, w + 64, ... of the
+// type mask.  Everything is a float64 compare: the candidates' price sum (getNodePrices) is made on the host, in candidate order, and arrives as a number.
+// Every branch below is taken by the whole wave (what decides it is loaded from the same address by every lane), so the reductions are reached together.
+// ------------------------------------------------------------------------------------------------
+struct CmdDesc { u64 id; double cand_price; u32 flags, type_lo, type_hi, pad; };
+__global__ __launch_bounds__(64) void ks_consolidation_commands(const DevProb* probs, const DevState* states, const CmdDesc* descs, const u32* type_idx, const double* type_price, u64* out, u32 words) {
+  const DevProb& P = probs[blockIdx.x]; const DevState& S = states[blockIdx.x]; const CmdDesc d = descs[blockIdx.x]; const u32 lane = threadIdx.x;
+  u64* row = out + (size_t)blockIdx.x * (KS_CMD_OPTIONS + 2 * (size_t)words);
+  const u32 n_new = S.out_counts[0], n_unsched = S.out_counts[1];
+  u32 action = KS_CMD_DO_NOTHING, reason = 0;
+  if ((d.flags & KS_CMD_F_BLOCKED) || n_unsched > 0) reason = KS_CMD_WHY_NOT_ALL_SCHEDULED;      // helpers.go:102-113 / consolidation.go:199-204
+  else if (n_new == 0) action = KS_CMD_DELETE;                                                   // :207-214
+  else if (n_new != 1) reason = KS_CMD_WHY_MANY_NODES;                                           // :217-222
+  else if (d.flags & KS_CMD_F_PRICE_ERROR) { action = KS_CMD_ERROR; reason = KS_CMD_WHY_PRICE_ERROR; }      // :224-228
+  const bool priced = action == KS_CMD_DO_NOTHING && reason == 0;      // the simulation asks for exactly one node and the candidates have a price
+  // new node 0's requirements travel with every row that has one (a Command holds the replacement's Requirements)
+  u32 pres = 0, comp = 0; bool has_spot = false, has_od = false;
+  if (n_new >= 1) {
+    pres = S.o_present[0]; comp = S.o_complement[0];
+    const KReq cq = ((pres >> P.key_ct) & 1u) ? load_req(pres, comp, S.o_mask, S.o_gt, S.o_lt, P.key_ct) : kreq_exists();
+    const u64 allowC = kreq_has_mask(cq, P.value_int + P.key_ct * 64, P.key_nvalues[P.key_ct]);
+    // Has("spot") / Has("on-demand") where the catalogue knows no such capacity type: a value outside the universe is in every complement set without bounds
+    // (requirement.go:171-176) -- the reference then still refuses spot-to-spot and narrows, and so does this
+    const bool outside = cq.complement && cq.gt == KS_NOGT && cq.lt == KS_NOLT;
+    has_spot = P.ct_spot >= 0 ? (bool)((allowC >> P.ct_spot) & 1ull) : outside; has_od = P.ct_ondemand >= 0 ? (bool)((allowC >> P.ct_ondemand) & 1ull) : outside;
+  }
+  const bool narrow = has_spot && has_od;      // consolidation.go:262-265: priced on the spot assumption, so the launch is pinned to spot
+  PriceCtx c1 = PriceCtx{0, 0, false, false}, c2 = c1;
+  if (priced) { c1 = price_ctx(P, S, 0, false); c2 = narrow ? price_ctx(P, S, 0, true) : c1; }
+  // stage 1: filterByPrice against the candidates' price (:238)
+  u32 kept1 = 0;
+  for (u32 wbase = 0; wbase < words; wbase += 64) {
+    const u32 w = wbase + lane; u64 o = 0;
+    if (priced && w < P.TW) o = price_filter_word(P, c1, S.n_alive[w], w, d.cand_price);
+    if (w < words) row[KS_CMD_OPTIONS + w] = o;
+    kept1 += (u32)__builtin_popcountll(o);
+  }
+  for (int off = 32; off > 0; off >>= 1) kept1 += __shfl_xor(kept1, off);
+  if (priced) {
+    if (kept1 == 0) reason = KS_CMD_WHY_NOT_CHEAPER;                                             // :239-244
+    else if ((d.flags & KS_CMD_F_ALL_SPOT) && has_spot) reason = KS_CMD_WHY_SPOT_TO_SPOT;        // :250-257
+    else action = KS_CMD_REPLACE;
+  }
+  const bool narrowed = action == KS_CMD_REPLACE && narrow;
+  // stage 2: filterOutSameType -- the cheapest listed price among the candidates' own types that stage 1 kept is the new ceiling (a type listed at 0.0:
+  // the Go map miss), MaxFloat64 if stage 1 kept none of them; the options are priced again, under the narrowed capacity type if :262-265 narrowed
+  const bool second = action == KS_CMD_REPLACE && (d.flags & KS_CMD_F_SAME_TYPE);
+  double ceiling = 1.7976931348623157e308;
+  if (second) for (u32 i = d.type_lo + lane; i < d.type_hi; i += 64) {
+    const u32 t = type_idx[i], w = t >> 6;
+    if (price_filter_word(P, c1, S.n_alive[w] & (1ull << (t & 63u)), w, d.cand_price) && type_price[i] < ceiling) ceiling = type_price[i];
+  }
+  for (int off = 32; off > 0; off >>= 1) { const double o = __shfl_xor(ceiling, off); if (o < ceiling) ceiling = o; }
+  u32 kept2 = 0;
+  for (u32 wbase = 0; wbase < words; wbase += 64) {
+    const u32 w = wbase + lane; u64 o = 0;
+    if (second && w < P.TW) o = price_filter_word(P, c2, price_filter_word(P, c1, S.n_alive[w], w, d.cand_price), w, ceiling);
+    if (w < words) row[KS_CMD_OPTIONS + words + w] = o;
+    kept2 += (u32)__builtin_popcountll(o);
+  }
+  for (int off = 32; off > 0; off >>= 1) kept2 += __shfl_xor(kept2, off);
+  if (second && kept2 == 0) { action = KS_CMD_DO_NOTHING; reason = KS_CMD_WHY_SAME_TYPE; }       // multinodeconsolidation.go:102-106
+  // the requirement rows: lane k writes key k (zero beyond K, and for a what-if without a new node)
+  if (lane < KS_MAX_KEYS) {
+    u64 m = 0, b = 0;
+    if (n_new >= 1 && lane < P.K) {
+      m = S.o_mask[lane]; b = (u64)(u32)S.o_gt[lane] | ((u64)(u32)S.o_lt[lane] << 32);
+      if (narrowed && (i32)lane == P.key_ct) { m = P.ct_spot >= 0 ? 1ull << P.ct_spot : 0ull; b = (u64)(u32)KS_NO_BOUND_GT | ((u64)(u32)KS_NO_BOUND_LT << 32); }      // Requirements.Add(capacity-type In [spot])
+    }
+    row[KS_CMD_MASK + lane] = m; row[KS_CMD_BOUNDS + lane] = b;
+  }
+  if (lane == 0) {
+    if (narrowed) { pres |= 1u << P.key_ct; comp &= ~(1u << P.key_ct); }
+    row[KS_CMD_ID] = d.id; row[KS_CMD_DECISION] = (u64)action | ((u64)reason << 8) | ((u64)(narrowed ? 1u : 0u) << 16);
+    row[KS_CMD_N_NEW] = n_new; row[KS_CMD_N_UNSCHEDULED] = n_unsched; row[KS_CMD_N_OPTIONS] = kept1; row[KS_CMD_N_OPTIONS_SAME_TYPE] = kept2;
+    row[KS_CMD_PRESENT] = (u64)pres | ((u64)comp << 32); row[KS_CMD_IT_STATE] = n_new >= 1 ? (u64)(u32)S.o_it[0] : 0ull;
+  }
+}
+
+// every refusal of ks_consolidation_commands*: before any device work
+static int commands_check(ks_dev_problem* const* ds, u32 n, const uint64_t* ids, const ks_command_inputs* in, u32 words) {
+  if (!ds || !ids || !in || !in->flags || !in->cand_price || !in->type_off) return fail(KS_ERR_INVALID, "null argument");
+  for (u32 i = 0; i < n; ++i) if (!ds[i]) return fail(KS_ERR_INVALID, "null device problem");
+  for (u32 i = 0; i < n; ++i) if (in->type_off[i + 1] < in->type_off[i]) return fail(KS_ERR_INVALID, "type list offsets not ascending");
+  const int device = ds[0]->device; const u32 n_types = in->type_off[n];
+  if (n_types && (!in->type_idx || !in->type_price)) return fail(KS_ERR_INVALID, "null argument");
+  for (u32 i = 0; i < n; ++i) {
+    if (ds[i]->device != device) return fail(KS_ERR_INVALID, "batch spans devices");
+    if (!ds[i]->h.it_price || ds[i]->h.key_zone < 0 || ds[i]->h.key_ct < 0) return fail(KS_ERR_INVALID, "problem carries no offering prices");
+    if (ds[i]->h.TW > words) return fail(KS_ERR_INVALID, "command row too short");
+    if (ds[i]->h.K > KS_MAX_KEYS || ds[i]->h.NMAX < 1) return fail(KS_ERR_INVALID, "problem outside the command row's layout");
+    if (in->flags[i] & ~(uint32_t)KS_CMD_F_ALL) return fail(KS_ERR_INVALID, "unknown command flag bit");
+    if (in->type_off[i + 1] < in->type_off[i] || in->type_off[i + 1] > n_types) return fail(KS_ERR_INVALID, "type list offsets not ascending");
+    for (u32 k = in->type_off[i]; k < in->type_off[i + 1]; ++k) if (in->type_idx[k] >= ds[i]->h.T) return fail(KS_ERR_INVALID, "type index out of range");
+  }
+  return KS_OK;
+}
+// inputs up in one block, one launch, completion: what both entry points do once commands_check has passed
+static int commands_launch(ks_dev_problem* const* ds, u32 n, const uint64_t* ids, const ks_command_inputs* in, u32 words, void* d_out) {
+  const int device = ds[0]->device;
+  const u32 n_types = in->type_off[n];
+  std::vector<DevProb> hp(n); std::vector<DevState> hs(n); std::vector<CmdDesc> hd(n);
+  for (u32 i = 0; i < n; ++i) {
+    hp[i] = ds[i]->h; hs[i] = ds[i]->hs; hd[i] = CmdDesc{ids[i], in->cand_price[i], in->flags[i], in->type_off[i], in->type_off[i + 1], 0};
+  }
+  HIPCHK(hipSetDevice(device));
+  // one block of inputs, one transfer: [DevProb n | DevState n | CmdDesc n | type prices | type indices]
+  const size_t o_state = n * sizeof(DevProb), o_desc = o_state + n * sizeof(DevState), o_price = o_desc + n * sizeof(CmdDesc), o_idx = o_price + (size_t)n_types * sizeof(double),
+               total = o_idx + (size_t)n_types * sizeof(u32);
+  std::vector<u64> host((total + 7) / 8);
+  memcpy((u8*)host.data(), hp.data(), n * sizeof(DevProb)); memcpy((u8*)host.data() + o_state, hs.data(), n * sizeof(DevState)); memcpy((u8*)host.data() + o_desc, hd.data(), n * sizeof(CmdDesc));
+  if (n_types) { memcpy((u8*)host.data() + o_price, in->type_price, (size_t)n_types * sizeof(double)); memcpy((u8*)host.data() + o_idx, in->type_idx, (size_t)n_types * sizeof(u32)); }
+  TmpDev t_in(device); TRY(t_in.alloc(host.size() * 8));
+  HIPCHK(hipMemcpy(t_in.p, host.data(), total, hipMemcpyHostToDevice));      // (synchronous, like ks_price_filter_dev's: `host` is pageable and dies with this call)
+  const u8* base = t_in.as<u8>();
+  const DevProb* dp = (const DevProb*)base; const DevState* dsv = (const DevState*)(base + o_state); const CmdDesc* dd = (const CmdDesc*)(base + o_desc);
+  const double* dprice = (const double*)(base + o_price); const u32* didx = (const u32*)(base + o_idx);
+  hipLaunchKernelGGL(ks_consolidation_commands, dim3(n), dim3(64), 0, ds[0]->stream, dp, dsv, dd, didx, dprice, (u64*)d_out, words);
+  HIPCHK(hipStreamSynchronize(ds[0]->stream)); HIPCHK(hipGetLastError());      // the buffer is complete when this returns: the caller's own stream may read it
+  return KS_OK;
+}
+
+extern "C" int ks_consolidation_commands_dev(ks_dev_problem* const* ds, uint32_t n, const uint64_t* ids, const ks_command_inputs* in, uint32_t words, void* d_out) {
+  if (!n) return KS_OK;
+  if (!d_out) return fail(KS_ERR_INVALID, "null argument");
+  TRY(commands_check(ds, n, ids, in, words));
+  return commands_launch(ds, n, ids, in, words, d_out);
+}
+// The same with the rows brought to the host (what a caller without a device buffer of its own wants): ms[0] = inputs up + launch + completion, ms[1] = read-back.
+extern "C" int ks_consolidation_commands_host(ks_dev_problem* const* ds, uint32_t n, const uint64_t* ids, const ks_command_inputs* in, uint32_t words, uint64_t* out_rows, double* ms) {
+  if (ms) ms[0] = ms[1] = 0.0;
+  if (!n) return KS_OK;
+  if (!out_rows) return fail(KS_ERR_INVALID, "null argument");
+  TRY(commands_check(ds, n, ids, in, words));
+  const size_t bytes = (size_t)n * KS_CMD_ROW_WORDS(words) * sizeof(u64);
+  TmpDev buf(ds[0]->device); TRY(buf.alloc(bytes));
+  const auto t0 = std::chrono::steady_clock::now();
+  TRY(commands_launch(ds, n, ids, in, words, buf.p));
+  const auto t1 = std::chrono::steady_clock::now();
+  HIPCHK(hipMemcpy(out_rows, buf.p, bytes, hipMemcpyDeviceToHost));
+  if (ms) { ms[0] = std::chrono::duration<double, std::milli>(t1 - t0).count(); ms[1] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count(); }
   return KS_OK;
 }
 

@@ -84,6 +84,7 @@ struct Parsed {
   std::shared_ptr<const ksp::Problem> pr;
   std::mutex mu; std::shared_ptr<const ksh::SnapshotBase> sb; std::vector<int32_t> sb_pod_node; uint32_t sb_flags = 0;
   ksh::EnvCache env;      // the flattening of everything but the pods, reused by the next batch with the same universe signature
+  std::shared_ptr<const void> cmd_nodes;      // what the consolidation commands read of the nodes' labels (CmdSnapshot below), made once; ksh_env_apply* drops it
   // ksh_env_apply (round 6): once events were applied the library holds the bindings itself -- bind[i] = the node pod i is bound to, -1 for a pod that was unbound
   // (it stays in place: nothing that points into the problem may move) -- and the names of what is alive
   bool bind_set = false, had_cluster_pods = false; std::vector<int32_t> bind; std::unordered_map<std::string, uint32_t> live_node, live_pod; uint64_t tombstones = 0; uint32_t applied = 0;
@@ -359,7 +360,7 @@ static int apply_events(Parsed* P, const int32_t* pod_node, std::vector<ksp::Del
       }
       ++done;
     }
-    P->applied += done; { std::lock_guard<std::mutex> ge(P->env.mu); P->env.base.reset(); }      // (a Solve over these objects flattens its environment again)
+    P->applied += done; P->cmd_nodes.reset(); { std::lock_guard<std::mutex> ge(P->env.mu); P->env.base.reset(); }      // (a Solve over these objects flattens its environment again)
     // the snapshot's flattening follows, continued from the one before when there is one
     bool continued = false;
     if (P->sb) {
@@ -730,6 +731,203 @@ int ksh_solve_whatifs_sharded(void** hv, const uint32_t* shard_off, uint32_t nsh
   if (rc != KS_OK) return set_err(rc, ks_last_error());
   for (uint32_t i = 0; i < n; ++i) ((Handle*)hv[i])->dev_result = true;
   return KS_OK;
+}
+
+// ---- consolidation commands (kshost.h): computeConsolidation / firstNNodeConsolidationOption / SingleNodeConsolidation.ComputeCommand over a snapshot ----
+// The rows of handles that hold a result on the device (any route: derived, flattened one by one, a plain Solve): ks_consolidation_commands_host for handles.
+int ksh_command_rows(void** hv, uint32_t n, const uint64_t* ids, const ks_command_inputs* in, uint32_t words, uint64_t* out_rows, double* ms) {
+  if (n && !hv) return set_err(KS_ERR_INVALID, "null argument");
+  std::vector<ks_dev_problem*> ds(n);
+  for (uint32_t i = 0; i < n; ++i) { Handle* h = (Handle*)hv[i]; if (!h || !h->dev || !h->dev_result) return set_err(KS_ERR_INVALID, "command rows before solve"); ds[i] = h->dev; }
+  int rc = ks_consolidation_commands_host(ds.data(), n, ids, in, words, out_rows, ms);
+  if (rc != KS_OK) return set_err(rc, ks_last_error());
+  return KS_OK;
+}
+}  // extern "C"
+// What getNodePrices / filterOutSameType / simulateScheduling's readiness rule read of the snapshot's nodes, once per call
+namespace {
+struct CmdNode { int32_t type = -1; bool spot = false, has_price = false, unready = false, owned = false; double price = 0.0; };
+struct CmdSnapshot {
+  std::vector<CmdNode> nodes; uint32_t unready = 0;
+  explicit CmdSnapshot(const ksp::Problem& pr) : nodes(pr.nodes.size()) {
+    std::unordered_map<std::string, int32_t> tindex; for (size_t t = 0; t < pr.instance_types.size(); ++t) tindex.emplace(pr.instance_types[t].name, (int32_t)t);
+    for (size_t i = 0; i < pr.nodes.size(); ++i) {
+      const ksp::StateNode& nd = pr.nodes[i]; CmdNode& c = nodes[i];
+      auto lab = [&](const char* k) -> const std::string& { static const std::string none; auto it = nd.labels.find(k); return it == nd.labels.end() ? none : it->second; };
+      c.owned = nd.owned();
+      auto init = nd.labels.find("karpenter.sh/initialized");
+      c.unready = nd.in_state && c.owned && !(init != nd.labels.end() && init->second == "true");      // helpers.go:102-111
+      unready += c.unready ? 1u : 0u;
+      auto t = tindex.find(lab(ksp::kInstanceType)); if (t == tindex.end()) continue;
+      c.type = t->second; const std::string& ct = lab(ksp::kCapacityType); const std::string& zone = lab(ksp::kZone); c.spot = ct == "spot";
+      for (auto& o : pr.instance_types[c.type].offerings) if (o.capacity_type == ct && o.zone == zone) { c.has_price = true; c.price = o.price; break; }      // Offerings.Get (types.go:117-124): availability is not consulted
+    }
+  }
+};
+// all the what-ifs of one call: open (derived on the device, else flattened one by one), solve resident, decide on the device, rows back.  ms[5]: open | solve | command kernel | read-back | the host work around them
+int commands_over(Parsed* P, uint32_t flags, uint32_t n, const uint32_t* cand_off, const uint32_t* cand, const int32_t* pod_node, const uint32_t* deleting, uint32_t n_deleting,
+                  int device, bool same_type, const uint64_t* ids, uint64_t* out_rows, uint32_t words, double* ms) {
+  using clk = std::chrono::steady_clock; auto since = [](clk::time_point a) { return std::chrono::duration<double, std::milli>(clk::now() - a).count(); };
+  if (ms) ms[0] = ms[1] = ms[2] = ms[3] = ms[4] = 0.0;
+  if (!P || (n && (!cand_off || !out_rows)) || (n_deleting && !deleting)) return set_err(KS_ERR_INVALID, "null argument");
+  const uint32_t known = KS_FLAG_SIMULATION | KS_FLAG_NO_RR | KS_FLAG_ONE_WAVE | KS_FLAG_NO_LEAN | KSH_DERIVE_VOLUMES | KSH_ACTIVE_RESOURCES;
+  if (flags & ~known) return set_err(KS_ERR_INVALID, "consolidation commands: unknown flag bit");
+  if (!n) return KS_OK;
+  const ksp::Problem& pr = *P->pr; const size_t NN = pr.nodes.size(); const uint32_t TW = ((uint32_t)pr.instance_types.size() + 63) / 64;
+  if (words < TW) return set_err(KS_ERR_INVALID, "command row too short: " + std::to_string(words) + " words for " + std::to_string(pr.instance_types.size()) + " instance types");
+  for (uint32_t i = 0; i < n; ++i) if (cand_off[i + 1] < cand_off[i]) return set_err(KS_ERR_INVALID, "candidate offsets not ascending");
+  if (cand_off[n] && !cand) return set_err(KS_ERR_INVALID, "null argument");
+  for (uint32_t i = 0; i < cand_off[n]; ++i) if (cand[i] >= NN) return set_err(KS_ERR_INVALID, "candidate node out of range");
+  for (uint32_t i = 0; i < n_deleting; ++i) if (deleting[i] >= NN) return set_err(KS_ERR_INVALID, "deleting node out of range");
+  const auto t_call = clk::now();
+  std::shared_ptr<const void> held;      // the label table: made by the first command call over this snapshot, kept until events change the nodes
+  { std::lock_guard<std::mutex> g(P->mu); if (!P->cmd_nodes) P->cmd_nodes = std::make_shared<const CmdSnapshot>(pr); held = P->cmd_nodes; }
+  const CmdSnapshot& cs = *static_cast<const CmdSnapshot*>(held.get());
+  // nodes that leave EVERY what-if: the carrier of the pending pods (a node no provisioner owns) first -- the pending pods head simulateScheduling's batch,
+  // helpers.go:76-79 --, the nodes marked for deletion last (:81-84); a candidate that is itself being deleted is an error, not a simulation (:62-67)
+  std::vector<uint8_t> is_del(NN, 0); std::vector<uint32_t> first, last; uint32_t del_unready = 0;
+  for (uint32_t i = 0; i < n_deleting; ++i) { if (is_del[deleting[i]]) continue; is_del[deleting[i]] = 1; (cs.nodes[deleting[i]].owned ? last : first).push_back(deleting[i]); del_unready += cs.nodes[deleting[i]].unready ? 1u : 0u; }
+  const size_t W = KS_CMD_ROW_WORDS(words);
+  std::vector<uint32_t> live, off2{0}, cand2; std::vector<uint32_t> cflags; std::vector<double> cprice, tprice; std::vector<uint32_t> toff{0}, tidx; std::vector<uint64_t> lids;
+  std::vector<uint8_t> seen(NN, 0);
+  for (uint32_t i = 0; i < n; ++i) {
+    bool refused = false;
+    for (uint32_t k = cand_off[i]; k < cand_off[i + 1]; ++k) if (is_del[cand[k]]) refused = true;
+    uint64_t* row = out_rows + (size_t)i * W;
+    if (refused) { std::fill(row, row + W, 0ull); row[KS_CMD_ID] = ids ? ids[i] : i; row[KS_CMD_DECISION] = (uint64_t)KS_CMD_ERROR | ((uint64_t)KS_CMD_WHY_DELETING << 8); continue; }
+    live.push_back(i); lids.push_back(ids ? ids[i] : i);
+    cand2.insert(cand2.end(), first.begin(), first.end());
+    uint32_t f = same_type ? KS_CMD_F_SAME_TYPE : 0u, gone_unready = del_unready; bool all_spot = true; double price = 0.0; const size_t t0 = tidx.size();
+    for (uint32_t k = cand_off[i]; k < cand_off[i + 1]; ++k) {
+      const uint32_t nd = cand[k]; cand2.push_back(nd);
+      if (seen[nd]) continue;      // (a node listed twice leaves once)
+      seen[nd] = 1; const CmdNode& c = cs.nodes[nd];
+      gone_unready += c.unready ? 1u : 0u;
+      if (c.type < 0) return set_err(KS_ERR_INVALID, "candidate node " + pr.nodes[nd].name + " carries no instance type of the snapshot's catalogue");
+      all_spot = all_spot && c.spot;
+      if (c.has_price) price += c.price; else f |= KS_CMD_F_PRICE_ERROR;      // getNodePrices, consolidation.go:277-287: summed in candidate order
+      size_t at = t0; while (at < tidx.size() && tidx[at] != (uint32_t)c.type) ++at;
+      if (at == tidx.size()) { tidx.push_back((uint32_t)c.type); tprice.push_back(c.has_price ? c.price : -1.0); }      // (-1: no candidate of the type has an offering yet)
+      else if (c.has_price && (tprice[at] < 0.0 || c.price < tprice[at])) tprice[at] = c.price;
+    }
+    for (uint32_t k = cand_off[i]; k < cand_off[i + 1]; ++k) seen[cand[k]] = 0;
+    for (size_t at = t0; at < tprice.size(); ++at) if (tprice[at] < 0.0) tprice[at] = 0.0;      // the Go map miss of multinodeconsolidation.go:150-158
+    if (all_spot) f |= KS_CMD_F_ALL_SPOT;
+    if (cs.unready > gone_unready) f |= KS_CMD_F_BLOCKED;
+    cand2.insert(cand2.end(), last.begin(), last.end());
+    off2.push_back((uint32_t)cand2.size()); cflags.push_back(f); cprice.push_back(price); toff.push_back((uint32_t)tidx.size());
+  }
+  const uint32_t m = (uint32_t)live.size(); if (!m) return KS_OK;
+  if (cand2.empty()) cand2.push_back(0);
+  std::vector<void*> hs(m, nullptr);
+  auto close_all = [&] { for (void* h : hs) if (h) ksh_close(h); };
+  auto t0 = clk::now();
+  int rc = ksh_open_whatifs_derived(P, flags, m, off2.data(), cand2.data(), pod_node, device, hs.data());
+  if (rc == KS_ERR_UNSUPPORTED) {      // what scheduler.open_whatifs(derive=None) does: flatten the what-ifs one by one, then make them resident
+    rc = ksh_open_whatifs_parsed(P, flags & ~(uint32_t)KSH_DERIVE_VOLUMES, m, off2.data(), cand2.data(), pod_node, 0, hs.data());
+    // KS_CMD_IT_STATE is spelled out through the snapshot's lattice (ksh_snapshot_it_state): a what-if flattened by itself that needed instance-type states of
+    // its own cannot be read that way -- refused here, before anything is uploaded or launched
+    for (uint32_t k = 0; k < m && rc == KS_OK; ++k) { const ksh::Encoded& e = *((Handle*)hs[k])->enc; if (!(e.shared && e.shared_lattice)) rc = set_err(KS_ERR_UNSUPPORTED, "a what-if carries instance-type requirement states of its own: simulate it through ksh_open_whatifs_parsed and read it through ksh_result_text"); }
+    if (rc == KS_OK) rc = ksh_upload_batch(hs.data(), m, device, 0);
+  }
+  if (rc != KS_OK) { close_all(); return rc; }
+  if (ms) ms[0] = since(t0);
+  t0 = clk::now();
+  rc = ksh_solve_batch_resident(hs.data(), m, nullptr, nullptr);
+  if (rc != KS_OK) { close_all(); return rc; }
+  if (ms) ms[1] = since(t0);
+  ks_command_inputs in{}; in.flags = cflags.data(); in.cand_price = cprice.data(); in.type_off = toff.data(); in.type_idx = tidx.data(); in.type_price = tprice.data();
+  std::vector<uint64_t> rows; uint64_t* dst = out_rows;
+  if (m != n) { rows.resize((size_t)m * W); dst = rows.data(); }      // (refused candidate sets keep their rows: the live ones are scattered around them)
+  rc = ksh_command_rows(hs.data(), m, lids.data(), &in, words, dst, ms ? ms + 2 : nullptr);
+  close_all();
+  if (rc != KS_OK) return rc;
+  if (m != n) for (uint32_t k = 0; k < m; ++k) std::copy(rows.begin() + (size_t)k * W, rows.begin() + (size_t)(k + 1) * W, out_rows + (size_t)live[k] * W);
+  if (ms) ms[4] = since(t_call) - ms[0] - ms[1] - ms[2] - ms[3];      // the host work around the four: the per-what-if inputs, closing the handles
+  return KS_OK;
+}
+}  // namespace
+extern "C" {
+int ksh_consolidation_commands(void* parsed, uint32_t flags, uint32_t n, const uint32_t* cand_off, const uint32_t* cand, const int32_t* pod_node, const uint32_t* deleting, uint32_t n_deleting,
+                               int device, int same_type, uint64_t* out_rows, uint32_t words, double* ms) {
+  try { return commands_over((Parsed*)parsed, flags, n, cand_off, cand, pod_node, deleting, n_deleting, device, same_type != 0, nullptr, out_rows, words, ms); }
+  catch (const ksh::Unsupported& e) { return set_err(KS_ERR_UNSUPPORTED, e.what()); } catch (const std::exception& e) { return set_err(KS_ERR_INVALID, e.what()); }
+}
+// firstNNodeConsolidationOption (multinodeconsolidation.go:74-114): every prefix the binary search could probe in one batch, filterOutSameType included, then the search
+// replayed over the rows.  out_row[KS_CMD_ID] = how many leading candidates the command removes.
+int ksh_first_n_node_option(void* parsed, uint32_t flags, const uint32_t* candidates, uint32_t n, uint32_t max_nodes, const int32_t* pod_node, const uint32_t* deleting, uint32_t n_deleting,
+                            int device, uint64_t* out_row, uint32_t words, double* ms) {
+  if (!out_row || (n && !candidates)) return set_err(KS_ERR_INVALID, "null argument");
+  try {
+    const size_t W = KS_CMD_ROW_WORDS(words); std::fill(out_row, out_row + W, 0ull);
+    if (ms) ms[0] = ms[1] = ms[2] = ms[3] = ms[4] = 0.0;
+    if (n < 2) return KS_OK;                                   // :75-77
+    uint32_t lo = 1, hi = max_nodes; if (n <= hi) hi = n - 1;      // :78-84
+    if (hi < lo) return KS_OK;
+    const uint32_t np = hi - lo + 1;
+    std::vector<uint32_t> off(np + 1, 0), cand; std::vector<uint64_t> ids(np);
+    for (uint32_t mid = lo; mid <= hi; ++mid) { cand.insert(cand.end(), candidates, candidates + mid + 1); off[mid - lo + 1] = (uint32_t)cand.size(); ids[mid - lo] = mid + 1; }
+    std::vector<uint64_t> rows((size_t)np * W);
+    int rc = commands_over((Parsed*)parsed, flags, np, off.data(), cand.data(), pod_node, deleting, n_deleting, device, true, ids.data(), rows.data(), words, ms);
+    if (rc != KS_OK) return rc;
+    int64_t l = lo, h = hi;
+    while (l <= h) {
+      const int64_t mid = (l + h) / 2; const uint64_t* row = rows.data() + (size_t)(mid - lo) * W; const uint32_t action = (uint32_t)(row[KS_CMD_DECISION] & 0xffu);
+      if (action == KS_CMD_ERROR) { std::copy(row, row + W, out_row); return KS_OK; }      // the probed prefix's error is the search's (:92-95)
+      if (action == KS_CMD_REPLACE || action == KS_CMD_DELETE) { std::copy(row, row + W, out_row); l = mid + 1; } else h = mid - 1;
+    }
+    return KS_OK;
+  } catch (const ksh::Unsupported& e) { return set_err(KS_ERR_UNSUPPORTED, e.what()); } catch (const std::exception& e) { return set_err(KS_ERR_INVALID, e.what()); }
+}
+// SingleNodeConsolidation.ComputeCommand's scan (singlenodeconsolidation.go:54-78): every singleton in one batch; the first delete or replace in candidate order, errors
+// passed over.  out_row[KS_CMD_ID] = the position of that candidate.
+int ksh_single_node_option(void* parsed, uint32_t flags, const uint32_t* candidates, uint32_t n, const int32_t* pod_node, const uint32_t* deleting, uint32_t n_deleting,
+                           int device, uint64_t* out_row, uint32_t words, double* ms) {
+  if (!out_row || (n && !candidates)) return set_err(KS_ERR_INVALID, "null argument");
+  try {
+    const size_t W = KS_CMD_ROW_WORDS(words); std::fill(out_row, out_row + W, 0ull);
+    if (ms) ms[0] = ms[1] = ms[2] = ms[3] = ms[4] = 0.0;
+    if (!n) return KS_OK;
+    std::vector<uint32_t> off(n + 1); for (uint32_t i = 0; i <= n; ++i) off[i] = i;
+    std::vector<uint64_t> rows((size_t)n * W);
+    int rc = commands_over((Parsed*)parsed, flags, n, off.data(), candidates, pod_node, deleting, n_deleting, device, false, nullptr, rows.data(), words, ms);
+    if (rc != KS_OK) return rc;
+    for (uint32_t i = 0; i < n; ++i) {
+      const uint64_t* row = rows.data() + (size_t)i * W; const uint32_t action = (uint32_t)(row[KS_CMD_DECISION] & 0xffu);
+      if (action == KS_CMD_REPLACE || action == KS_CMD_DELETE) { std::copy(row, row + W, out_row); return KS_OK; }
+    }
+    return KS_OK;
+  } catch (const ksh::Unsupported& e) { return set_err(KS_ERR_UNSUPPORTED, e.what()); } catch (const std::exception& e) { return set_err(KS_ERR_INVALID, e.what()); }
+}
+// The names behind a row, without a handle: what 0 = requirement key a, 1 = value b of key a (the flattening's universes: available once a what-if call flattened the
+// snapshot), 3 = state node a, 4 = instance type a.  NULL when out of range.
+const char* ksh_snapshot_name(void* parsed, int what, uint32_t a, uint32_t b) {
+  Parsed* P = (Parsed*)parsed; if (!P) return nullptr;
+  std::lock_guard<std::mutex> g(P->mu);
+  if (what == 3) return a < P->pr->nodes.size() ? P->pr->nodes[a].name.c_str() : nullptr;
+  if (what == 4) return a < P->pr->instance_types.size() ? P->pr->instance_types[a].name.c_str() : nullptr;
+  if (!P->sb) return nullptr;
+  const ksh::Encoded& E = *ksh::delta_inputs(*P->sb).base;
+  if (what == 0) return a < E.key_names.size() ? E.key_names[a].c_str() : nullptr;
+  if (what == 1) return (a < E.key_values.size() && b < E.key_values[a].size()) ? E.key_values[a][b].c_str() : nullptr;
+  return nullptr;
+}
+// the instance-type key's requirement of a row (KS_CMD_IT_STATE), spelled out: *complement, the number of values; value i through ksh_snapshot_it_state_value
+int ksh_snapshot_it_state(void* parsed, uint32_t state, int* complement, uint32_t* n_values) {
+  Parsed* P = (Parsed*)parsed; if (!P || !complement || !n_values) return set_err(KS_ERR_INVALID, "null argument");
+  std::lock_guard<std::mutex> g(P->mu);
+  if (!P->sb) return set_err(KS_ERR_INVALID, "the snapshot was not flattened yet");
+  const ksh::Encoded& L = ksh::delta_inputs(*P->sb).base->lattice();
+  if (state == 0 || state >= L.it_states.size()) return set_err(KS_ERR_INVALID, "instance-type state out of range");
+  *complement = L.it_states[state].complement ? 1 : 0; *n_values = (uint32_t)L.it_states[state].values.size(); return KS_OK;
+}
+const char* ksh_snapshot_it_state_value(void* parsed, uint32_t state, uint32_t i) {
+  Parsed* P = (Parsed*)parsed; if (!P) return nullptr;
+  std::lock_guard<std::mutex> g(P->mu);
+  if (!P->sb) return nullptr;
+  const ksh::Encoded& L = ksh::delta_inputs(*P->sb).base->lattice();
+  if (state == 0 || state >= L.it_states.size() || i >= L.it_states[state].values.size()) return nullptr;
+  auto it = L.it_states[state].values.begin(); std::advance(it, i); return it->c_str();
 }
 int ksh_pack_width(void* hv, int* out) { Handle* h = (Handle*)hv; if (!h || !h->dev) return KS_ERR_INVALID; return ks_problem_pack_width(h->dev, out); }
 int ksh_pack_lean(void* hv, int* out) { Handle* h = (Handle*)hv; if (!h || !h->dev) return KS_ERR_INVALID; return ks_problem_pack_lean(h->dev, out); }

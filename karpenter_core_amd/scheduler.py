@@ -682,6 +682,163 @@ def price_filter(flats: Sequence[FlatProblem], nodes: Sequence[int], max_prices:
     return out
 
 
+# ---- consolidation commands decided on the device (include/ksolve.h KS_CMD_*, include/kshost.h ksh_consolidation_commands) ----
+KS_CMD_F_BLOCKED, KS_CMD_F_ALL_SPOT, KS_CMD_F_PRICE_ERROR, KS_CMD_F_SAME_TYPE = 1, 2, 4, 8
+KS_CMD_ID, KS_CMD_DECISION, KS_CMD_N_NEW, KS_CMD_N_UNSCHEDULED, KS_CMD_N_OPTIONS, KS_CMD_N_OPTIONS_SAME_TYPE, KS_CMD_PRESENT, KS_CMD_IT_STATE = range(8)
+KS_CMD_MASK, KS_CMD_BOUNDS, KS_CMD_OPTIONS = 8, 40, 72
+KS_CMD_DO_NOTHING, KS_CMD_DELETE, KS_CMD_REPLACE, KS_CMD_ERROR = 0, 1, 2, 3
+KS_CMD_WHY_NOT_ALL_SCHEDULED, KS_CMD_WHY_MANY_NODES, KS_CMD_WHY_PRICE_ERROR, KS_CMD_WHY_NOT_CHEAPER, KS_CMD_WHY_SPOT_TO_SPOT, KS_CMD_WHY_SAME_TYPE, KS_CMD_WHY_DELETING = 1, 3, 4, 6, 7, 9, 10
+COMMAND_TIMING_KEYS = ("open_ms", "solve_ms", "command_kernel_ms", "readback_ms", "host_ms")
+
+
+def command_row_words(words: int) -> int:
+    """KS_CMD_ROW_WORDS: uint64 words of one command row whose option masks are `words` wide."""
+    return KS_CMD_OPTIONS + 2 * words
+
+
+class _CommandInputs(ctypes.Structure):      # include/ksolve.h ks_command_inputs
+    _fields_ = [("flags", ctypes.c_void_p), ("cand_price", ctypes.c_void_p), ("type_off", ctypes.c_void_p), ("type_idx", ctypes.c_void_p), ("type_price", ctypes.c_void_p)]
+
+
+def _u32s(xs):
+    import numpy as np
+    a = np.ascontiguousarray(np.asarray(list(xs), dtype=np.uint32))
+    return a if a.size else np.zeros(1, dtype=np.uint32)
+
+
+def _cand_csr(candidate_sets):
+    import numpy as np
+    off = np.zeros(len(candidate_sets) + 1, dtype=np.uint32)
+    np.cumsum([len(cs) for cs in candidate_sets], out=off[1:])
+    return off, _u32s(c for cs in candidate_sets for c in cs)
+
+
+def _pod_node_arg(pod_node):
+    import numpy as np
+    if pod_node is None:
+        return None, None
+    pn = np.ascontiguousarray(np.asarray(pod_node, dtype=np.int32)) if len(pod_node) else np.zeros(1, dtype=np.int32)
+    return pn, pn.ctypes.data
+
+
+def consolidation_commands(snapshot: "ParsedProblem", pod_node: Optional[Sequence[int]], candidate_sets: Sequence[Sequence[int]], words: int, deleting: Sequence[int] = (),
+                           same_type: bool = False, device: int = 0, volumes: bool = False, active_resources: bool = False, flags: int = 0):
+    """computeConsolidation for every candidate set in ONE call (kshost.h `ksh_consolidation_commands`): what-ifs derived, solved resident and decided on the
+    device; only the fixed-size rows come back.  Returns (numpy uint64 [n, command_row_words(words)], {open_ms, solve_ms, command_kernel_ms, readback_ms, host_ms}: the library's own split of the call)."""
+    import numpy as np
+    kh = libs()[1]
+    n = len(candidate_sets)
+    off, cand = _cand_csr(candidate_sets)
+    pn, pn_ptr = _pod_node_arg(pod_node)
+    dl = _u32s(deleting)
+    rows = np.zeros((max(1, n), command_row_words(words)), dtype=np.uint64)
+    ms = (ctypes.c_double * 5)()
+    kh.ksh_consolidation_commands.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
+                                              ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint32, ctypes.POINTER(ctypes.c_double)]
+    rc = kh.ksh_consolidation_commands(snapshot._p, (KSH_DERIVE_VOLUMES if volumes else 0) | (KSH_ACTIVE_RESOURCES if active_resources else 0) | flags, n, off.ctypes.data, cand.ctypes.data,
+                                       pn_ptr, dl.ctypes.data, len(deleting), device, 1 if same_type else 0, rows.ctypes.data, words, ms)
+    if rc != KS_OK:
+        raise KSolveError(rc, kh.ksh_last_error().decode())
+    return rows[:n], dict(zip(COMMAND_TIMING_KEYS, [float(x) for x in ms]))
+
+
+def _search_option(name: str, snapshot, pod_node, candidates, words, deleting, device, volumes, active_resources, flags, max_nodes=None):
+    import numpy as np
+    kh = libs()[1]
+    cand, dl = _u32s(candidates), _u32s(deleting)
+    pn, pn_ptr = _pod_node_arg(pod_node)
+    row = np.zeros(command_row_words(words), dtype=np.uint64)
+    ms = (ctypes.c_double * 5)()
+    fl = (KSH_DERIVE_VOLUMES if volumes else 0) | (KSH_ACTIVE_RESOURCES if active_resources else 0) | flags
+    fn = getattr(kh, name)
+    head = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32]
+    tail = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint32, ctypes.POINTER(ctypes.c_double)]
+    if max_nodes is None:
+        fn.argtypes = head + tail
+        rc = fn(snapshot._p, fl, cand.ctypes.data, len(candidates), pn_ptr, dl.ctypes.data, len(deleting), device, row.ctypes.data, words, ms)
+    else:
+        fn.argtypes = head + [ctypes.c_uint32] + tail
+        rc = fn(snapshot._p, fl, cand.ctypes.data, len(candidates), max_nodes, pn_ptr, dl.ctypes.data, len(deleting), device, row.ctypes.data, words, ms)
+    if rc != KS_OK:
+        raise KSolveError(rc, kh.ksh_last_error().decode())
+    return row, dict(zip(COMMAND_TIMING_KEYS, [float(x) for x in ms]))
+
+
+def first_n_node_option(snapshot: "ParsedProblem", pod_node, candidates: Sequence[int], words: int, max_nodes: int = 100, deleting: Sequence[int] = (), device: int = 0,
+                        volumes: bool = False, active_resources: bool = False, flags: int = 0):
+    """firstNNodeConsolidationOption (kshost.h `ksh_first_n_node_option`): every prefix in one batch, the binary search replayed over the rows.  Returns (row, timings);
+    row[KS_CMD_ID] = how many leading candidates the command removes."""
+    return _search_option("ksh_first_n_node_option", snapshot, pod_node, candidates, words, deleting, device, volumes, active_resources, flags, max_nodes=max_nodes)
+
+
+def single_node_option(snapshot: "ParsedProblem", pod_node, candidates: Sequence[int], words: int, deleting: Sequence[int] = (), device: int = 0,
+                       volumes: bool = False, active_resources: bool = False, flags: int = 0):
+    """The scan of SingleNodeConsolidation.ComputeCommand (kshost.h `ksh_single_node_option`).  Returns (row, timings); row[KS_CMD_ID] = the candidate's position."""
+    return _search_option("ksh_single_node_option", snapshot, pod_node, candidates, words, deleting, device, volumes, active_resources, flags)
+
+
+def command_rows(flats: Sequence[FlatProblem], ids: Sequence[int], flags: Sequence[int], cand_prices: Sequence[float], type_lists: Sequence[Sequence[Tuple[int, float]]], words: int,
+                 out=None, type_off=None):
+    """`ksh_command_rows`: the command rows of handles whose results are on the device, the per-what-if inputs given by the caller (flags: KS_CMD_F_*; type_lists[i]:
+    (instance-type index, lowest candidate price) per distinct candidate type).  `out`: a preallocated [n, command_row_words(words)] uint64 array to fill (tests poison
+    it first); `type_off`: CSR offsets to pass instead of the ones the lists give (tests: malformed offsets).  Returns the rows."""
+    import numpy as np
+    kh = libs()[1]
+    n = len(flats)
+    hs = (ctypes.c_void_p * max(1, n))(*[f._h for f in flats])
+    c_ids = np.ascontiguousarray(np.asarray(list(ids) or [0], dtype=np.uint64))
+    fl, cp = _u32s(flags), np.ascontiguousarray(np.asarray(list(cand_prices) or [0.0], dtype=np.float64))
+    off = np.zeros(n + 1, dtype=np.uint32)
+    np.cumsum([len(t) for t in type_lists], out=off[1:])
+    if type_off is not None:
+        off = _u32s(type_off)
+    tidx = _u32s(t for ts in type_lists for t, _ in ts)
+    tpr = np.ascontiguousarray(np.asarray([p for ts in type_lists for _, p in ts] or [0.0], dtype=np.float64))
+    inp = _CommandInputs(fl.ctypes.data, cp.ctypes.data, off.ctypes.data, tidx.ctypes.data, tpr.ctypes.data)
+    rows = out if out is not None else np.zeros((max(1, n), command_row_words(words)), dtype=np.uint64)
+    kh.ksh_command_rows.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]
+    rc = kh.ksh_command_rows(hs, n, c_ids.ctypes.data, ctypes.byref(inp), words, rows.ctypes.data, None)
+    if rc != KS_OK:
+        raise KSolveError(rc, kh.ksh_last_error().decode())
+    return rows[:n]
+
+
+def decode_command_row(snapshot: "ParsedProblem", row, words: int) -> dict:
+    """A command row as Python values, through the handle-free name accessors a C caller has (`ksh_snapshot_name`, `ksh_snapshot_it_state*`): action / reason / narrowed,
+    counts, both option stages as instance-type indices, and the replacement's requirements {key: (complement, sorted values, greaterThan, lessThan)}."""
+    from .model import LABEL_INSTANCE_TYPE
+    kh = libs()[1]
+    kh.ksh_snapshot_name.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32]
+    kh.ksh_snapshot_name.restype = ctypes.c_char_p
+    kh.ksh_snapshot_it_state.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_uint32)]
+    kh.ksh_snapshot_it_state_value.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32]
+    kh.ksh_snapshot_it_state_value.restype = ctypes.c_char_p
+    r = [int(x) for x in row]
+    dec = r[KS_CMD_DECISION]
+    bits = lambda base: [w * 64 + b for w in range(words) for b in range(64) if (r[base + w] >> b) & 1]
+    present, complement = r[KS_CMD_PRESENT] & 0xFFFFFFFF, r[KS_CMD_PRESENT] >> 32
+    reqs = {}
+    for k in range(32):
+        if not (present >> k) & 1:
+            continue
+        key = kh.ksh_snapshot_name(snapshot._p, 0, k, 0).decode()
+        vals = tuple(sorted(kh.ksh_snapshot_name(snapshot._p, 1, k, v).decode() for v in range(64) if (r[KS_CMD_MASK + k] >> v) & 1))
+        gt, lt = r[KS_CMD_BOUNDS + k] & 0xFFFFFFFF, r[KS_CMD_BOUNDS + k] >> 32
+        gt, lt = (gt - (1 << 32) if gt >= (1 << 31) else gt), (lt - (1 << 32) if lt >= (1 << 31) else lt)
+        reqs[key] = (bool((complement >> k) & 1), vals, None if gt == -(1 << 31) else gt, None if lt == (1 << 31) - 1 else lt)
+    if r[KS_CMD_IT_STATE]:
+        c, nv = ctypes.c_int(), ctypes.c_uint32()
+        if kh.ksh_snapshot_it_state(snapshot._p, r[KS_CMD_IT_STATE], ctypes.byref(c), ctypes.byref(nv)) != KS_OK:
+            raise KSolveError(KS_ERR_INVALID, kh.ksh_last_error().decode())
+        reqs[LABEL_INSTANCE_TYPE] = (bool(c.value), tuple(sorted(kh.ksh_snapshot_it_state_value(snapshot._p, r[KS_CMD_IT_STATE], i).decode() for i in range(nv.value))), None, None)
+    if (dec >> 16) & 1:      # narrowed to spot (consolidation.go:262-265); "spot" need not be a value of the catalogue's universe
+        from .model import LABEL_CAPACITY_TYPE
+        reqs[LABEL_CAPACITY_TYPE] = (False, ("spot",), None, None)
+    return {"id": r[KS_CMD_ID], "action": dec & 0xFF, "reason": (dec >> 8) & 0xFF, "narrowed": bool((dec >> 16) & 1), "n_new": r[KS_CMD_N_NEW], "n_unscheduled": r[KS_CMD_N_UNSCHEDULED],
+            "n_options": r[KS_CMD_N_OPTIONS], "n_options_same_type": r[KS_CMD_N_OPTIONS_SAME_TYPE], "options": bits(KS_CMD_OPTIONS), "options_same_type": bits(KS_CMD_OPTIONS + words),
+            "requirements": reqs}
+
+
 def launch_pick(flats: Sequence[FlatProblem], nodes: Sequence[int]):
     """The launch-time instance-type pick of the reference's in-memory provider (cloudprovider/fake/cloudprovider.go:79-84) on the device, over
     the results the last solve of `flats` left there: for flats[i]'s new node nodes[i], (instance-type index, zone, capacity type, price) of the
