@@ -2824,6 +2824,50 @@ template <typename T> static int dev_alloc(ks_dev_problem* d, size_t n, T** dst,
 }
 #define TRY(x) do { int rc_ = (x); if (rc_ != KS_OK) return rc_; } while (0)
 
+// What a call over a batch of resident problems sends to its kernel, and reads back: [DevProb n | DevState n | the caller's segments ...] in ONE host block and
+// ONE device block, every segment 16-byte aligned.  open() makes the refusals every such call shares and selects the device; add() reserves a segment; place()
+// allocates both blocks and fills in the problems' views; upload() is one synchronous transfer (the host block is pageable and dies with the call) of everything
+// below `upto`; fetch() brings everything from `from` on -- the segments the kernel wrote -- back in one.
+struct BatchStage {
+  TmpDev dev{0}; std::vector<u64> host; size_t bytes = 0, o_prob = 0, o_state = 0; ks_dev_problem* const* ds = nullptr; u32 n = 0; bool views = true;
+  static int not_null(ks_dev_problem* const* ds, u32 n) {
+    if (!ds) return fail(KS_ERR_INVALID, "null argument");
+    for (u32 i = 0; i < n; ++i) if (!ds[i]) return fail(KS_ERR_INVALID, "null device problem");
+    return KS_OK;
+  }
+  // node (optional): a new-node index per problem; per_problem(i): the caller's own refusals about problem i, after the shared ones about it
+  template <class F> int open(ks_dev_problem* const* ds_, u32 n_, const u32* node, bool need_prices, F&& per_problem) {
+    TRY(not_null(ds_, n_));
+    ds = ds_; n = n_; dev.device = ds[0]->device;
+    for (u32 i = 0; i < n; ++i) {
+      if (ds[i]->device != dev.device) return fail(KS_ERR_INVALID, "batch spans devices");
+      if (need_prices && (!ds[i]->h.it_price || ds[i]->h.key_zone < 0 || ds[i]->h.key_ct < 0)) return fail(KS_ERR_INVALID, "problem carries no offering prices");
+      if (node && node[i] >= ds[i]->h.NMAX) return fail(KS_ERR_INVALID, "node index out of range");
+      TRY(per_problem(i));
+    }
+    HIPCHK(hipSetDevice(dev.device));
+    if (views) { o_prob = add<DevProb>(n); o_state = add<DevState>(n); }
+    return KS_OK;
+  }
+  int open(ks_dev_problem* const* ds_, u32 n_, const u32* node, bool need_prices) { return open(ds_, n_, node, need_prices, [](u32) { return KS_OK; }); }
+  template <class T> size_t add(size_t count) { const size_t at = bytes; bytes = (bytes + count * sizeof(T) + 15) & ~(size_t)15; return at; }
+  int place() {
+    host.assign(bytes / 8 + 1, 0); TRY(dev.alloc(bytes));
+    if (views) for (u32 i = 0; i < n; ++i) { h<DevProb>(o_prob)[i] = ds[i]->h; h<DevState>(o_state)[i] = ds[i]->hs; }
+    return KS_OK;
+  }
+  template <class T> T* h(size_t off) { return (T*)((u8*)host.data() + off); }      // a segment in the host block | in the device block
+  template <class T> T* d(size_t off) const { return (T*)(dev.as<u8>() + off); }
+  const DevProb* probs() const { return d<DevProb>(o_prob); } const DevState* states() const { return d<DevState>(o_state); } hipStream_t stream() const { return ds[0]->stream; }
+  int upload(size_t upto) { if (upto) HIPCHK(hipMemcpy(dev.p, host.data(), upto, hipMemcpyHostToDevice)); return KS_OK; }
+  // the caller's launch is complete, and its outputs are in the host block, when this returns
+  int fetch(size_t from) {
+    if (from < bytes) HIPCHK(hipMemcpyAsync(h<u8>(from), d<u8>(from), bytes - from, hipMemcpyDeviceToHost, stream()));
+    HIPCHK(hipStreamSynchronize(stream())); HIPCHK(hipGetLastError());
+    return KS_OK;
+  }
+};
+
 static int copy_reqsets(ks_dev_problem* d, const ks_reqsets& s, u32 n, u32 K, ReqSetsD* out) {
   out->n = n;
   for (size_t i = 0; i < (size_t)n * K; ++i) if (s.gt[i] != KS_NO_BOUND_GT || s.lt[i] != KS_NO_BOUND_LT) d->any_bounds = true;
@@ -3395,10 +3439,7 @@ static int download(ks_dev_problem* d, ks_result* out) {
   u32 counts[4]; HIPCHK(hipMemcpy(counts, s.out_counts, sizeof counts, hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(out->stats, s.stats, 32 * sizeof(u64), hipMemcpyDeviceToHost));
   out->n_new = counts[0]; out->n_unscheduled = counts[1];
-  if (out->stats[KS_STAT_ERR]) return fail(-(int)out->stats[KS_STAT_ERR], out->stats[KS_STAT_ERR] == (u64)(-KS_ERR_CAPACITY) ? "more new nodes than max_new_nodes" :
-                                           out->stats[KS_STAT_ERR] == (u64)(-KS_ERR_INTERNAL) ? "pack kernel watchdog: step bound exceeded" :
-                                           out->stats[KS_STAT_ERR] >= 100 ? "pack kernel self-check failed (KS_CHECK build): visiting order inconsistent" :
-                                           "a pod class exceeds the kernel's per-class limits (12 touched keys / 24 topology groups / 3 hostname groups / 24 recorded groups)");
+  TRY(ks_stats_error(out->stats));
   const u32 P = h.P, K = h.K, R = h.R, TW = h.TW, N = out->n_new;
   if (P) {
     HIPCHK(hipMemcpy(out->pod_node, s.pod_node, P * sizeof(i32), hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(out->pod_stage, s.pod_stage, P * sizeof(i32), hipMemcpyDeviceToHost));
@@ -3418,24 +3459,78 @@ static int download(ks_dev_problem* d, ks_result* out) {
   return KS_OK;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Every ks_pack instantiation the library launches, once: the attribute loop, the launch, pack_rm and pack_lean of ks_solve_batch_dev all read the row
+// pack_choose() names.  Single-wave rows may take most of a CU's LDS for the ladders (one Solve) or share the CU (a batch); the multi-wave rows' static LDS leaves 44 KiB.
+// ------------------------------------------------------------------------------------------------
+#define KS_PACK_LDS_MULTI (44u * 1024u)
+typedef void (*pack_fn)(const DevProb*, const DevState*, u32);
+struct PackRow { pack_fn fn; bool fast, bounds, lean; int nw, rm; u32 lds_max; };
+#if !defined(KS_SIM) || defined(KS_SIM_PACK)
+#define KS_PACK_ROW(F, B, L, NW, RM) {ks_pack<F, B, L, NW, RM>, F, B, L, NW, RM, (NW) == 1 ? 104u * 1024u : KS_PACK_LDS_MULTI}
+#else
+#define KS_PACK_ROW(F, B, L, NW, RM) {nullptr, F, B, L, NW, RM, (NW) == 1 ? 104u * 1024u : KS_PACK_LDS_MULTI}      /* (no ks_pack in this build: the rows still say what a GPU build would run) */
+#endif
+#define KS_PACK_ROWS4(L, RM) KS_PACK_ROW(false, false, L, 1, RM), KS_PACK_ROW(false, true, L, 1, RM), KS_PACK_ROW(true, false, L, 1, RM), KS_PACK_ROW(true, true, L, 1, RM)
+static const PackRow pack_rows[] = {
+  KS_PACK_ROWS4(false, KS_RES_NARROW), KS_PACK_ROWS4(true, 4), KS_PACK_ROWS4(true, 8), KS_PACK_ROWS4(false, 16),      // one wave: general | LEAN | LEAN with 5..8 resources | wide
+  KS_PACK_ROW(true, false, true, 8, 4),                  // a single LEAN Solve without bounds: waves 1..7 join wave 0 for the speculation rounds (see ks_pack)
+  KS_PACK_ROW(true, false, true, KS_LEAN8_NW, 8),        // ... with 5..8 resources
+  KS_PACK_ROW(true, false, false, 4, KS_RES_NARROW),     // host ports / limits / selectors on hostname or instance type: the general code needs > 256 VGPRs, so 4 waves (one per SIMD): leader + 3 workers
+  KS_PACK_ROW(true, true, false, 4, KS_RES_NARROW),      // ... or Gt/Lt bounds, LEAN or not
+};
+static const int pack_nrows = (int)(sizeof pack_rows / sizeof pack_rows[0]);
+// What decides the row, as bits of `traits` (ks_solve_batch_dev gathers them from the batch, the problems' flags and the environment): SINGLE one problem, not a batch | FAST every
+// problem fits the FAST tables and its ladders the single-wave LDS | BOUNDS some requirement carries Gt/Lt | LEAN every problem is LEAN and nothing asked for the general code | LEAN8
+// some problem has more than 4 resources | WIDE more than 8 | ONE_WAVE the single-wave variant was asked for (always, on the emulator) | TW128 T <= 8192: a node's surviving-type mask
+// in two registers per lane | STATS KS_FLAG_STATS | NO_MULTI ks_dev_problem::no_multi | LADDERS44 the ladders fit the multi-wave rows' 44 KiB
+enum : u32 { KS_PT_SINGLE = 1u << 0, KS_PT_FAST = 1u << 1, KS_PT_BOUNDS = 1u << 2, KS_PT_LEAN = 1u << 3, KS_PT_LEAN8 = 1u << 4, KS_PT_WIDE = 1u << 5, KS_PT_ONE_WAVE = 1u << 6,
+             KS_PT_TW128 = 1u << 7, KS_PT_STATS = 1u << 8, KS_PT_NO_MULTI = 1u << 9, KS_PT_LADDERS44 = 1u << 10, KS_PT_ALL = (1u << 11) - 1 };
+static u32 pack_lds_one_wave(bool single) { return single ? 100u * 1024u : 64u * 1024u; }      // one Solve gets most of the CU's 160 KiB; batched what-ifs take 64 KiB each so two workgroups share a CU
+// Pure: the row of pack_rows a batch with these traits runs and the dynamic LDS it is launched with; -1 if the table lacks the row.
+static int pack_choose(u32 t, u32* lds_bytes) {
+  const bool fast = t & KS_PT_FAST, bounds = t & KS_PT_BOUNDS, lean = t & KS_PT_LEAN, lean8 = t & KS_PT_LEAN8, wide = t & KS_PT_WIDE;
+  const u32 multi_want = KS_PT_SINGLE | KS_PT_FAST | KS_PT_TW128 | KS_PT_LADDERS44, multi_bar = KS_PT_STATS | KS_PT_ONE_WAVE | KS_PT_NO_MULTI | KS_PT_WIDE;
+  PackRow w{nullptr, fast, bounds, false, 1, KS_RES_NARROW, 0};
+  if ((t & multi_want) == multi_want && !(t & multi_bar)) {
+    *lds_bytes = KS_PACK_LDS_MULTI; w.nw = 4;
+    if (lean && !bounds) { w.lean = true; w.nw = lean8 ? KS_LEAN8_NW : 8; w.rm = lean8 ? 8 : 4; }      // (LEAN with bounds: the general four waves)
+  } else {
+    *lds_bytes = pack_lds_one_wave(t & KS_PT_SINGLE);
+    if (wide) w.rm = 16;                                               // (never LEAN)
+    else if (lean) { w.lean = true; w.rm = lean8 ? 8 : 4; }
+  }
+  for (int i = 0; i < pack_nrows; ++i) { const PackRow& r = pack_rows[i]; if (r.fast == w.fast && r.bounds == w.bounds && r.lean == w.lean && r.nw == w.nw && r.rm == w.rm) return i; }
+  return -1;
+}
+// Diagnostics: the chooser and its table as tests see them, no device needed.  fields = {FAST, BOUNDS, LEAN, NW, RM, largest dynamic LDS the row may be launched with}.
+// ks_debug_pack_choice: traits (KS_PT_* bits) in; the chosen row's fields (RM and LEAN are what ks_problem_pack_width / ks_problem_pack_lean then report) and the dynamic
+// LDS of the launch out; returns the row's index.  ks_debug_pack_row: row `row` of the table; returns the number of rows.
+extern "C" int ks_debug_pack_row(uint32_t row, int32_t* fields) {
+  if (fields && row < (u32)pack_nrows) { const PackRow& r = pack_rows[row]; const i32 f[6] = {r.fast, r.bounds, r.lean, r.nw, r.rm, (i32)r.lds_max}; memcpy(fields, f, sizeof f); }
+  return pack_nrows;
+}
+extern "C" int ks_debug_pack_choice(uint32_t traits, int32_t* fields, uint32_t* lds_bytes) {
+  u32 lds = 0; const int row = pack_choose(traits & KS_PT_ALL, &lds);
+  if (row < 0) return fail(KS_ERR_INTERNAL, "ks_pack: no instantiation for these traits");
+  ks_debug_pack_row((u32)row, fields); if (lds_bytes) *lds_bytes = lds;
+  return row;
+}
+
 extern "C" int ks_solve_batch_dev(ks_dev_problem* const* ds, uint32_t n, ks_result* const* outs, float* kernel_ms) {
   if (!n) return KS_OK;
   if (!ds) return fail(KS_ERR_INVALID, "null batch");
+  BatchStage stage; TRY(stage.open(ds, n, nullptr, false));
   const int device = ds[0]->device;
-  HIPCHK(hipSetDevice(device));
   u32 unbuilt = 0;
-  for (u32 i = 0; i < n; ++i) { if (ds[i]->device != device) return fail(KS_ERR_INVALID, "batch spans devices"); if (!ds[i]->tables_built) ++unbuilt; }
+  for (u32 i = 0; i < n; ++i) if (!ds[i]->tables_built) ++unbuilt;
   if (n == 1 && unbuilt) TRY(build_static(ds[0], nullptr));
-  std::vector<DevProb> hp(n); std::vector<DevState> hs(n);
-  for (u32 i = 0; i < n; ++i) { hp[i] = ds[i]->h; hs[i] = ds[i]->hs; }
-  DevProb* dp = nullptr; DevState* dsv = nullptr; u64* d_meta = nullptr;
-  TmpDev t_meta(device), t_dp(device), t_dsv(device);
-  if (n == 1) { dp = ds[0]->d_prob; dsv = ds[0]->d_state; }
-  else {
-    TRY(t_meta.alloc((size_t)n * 34 * sizeof(u64))); d_meta = t_meta.as<u64>();
-    for (u32 i = 0; i < n; ++i) hs[i].batch_meta = d_meta + (size_t)i * 34;
-    TRY(t_dp.alloc(n * sizeof(DevProb))); TRY(t_dsv.alloc(n * sizeof(DevState))); dp = t_dp.as<DevProb>(); dsv = t_dsv.as<DevState>();
-    HIPCHK(hipMemcpy(dp, hp.data(), n * sizeof(DevProb), hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(dsv, hs.data(), n * sizeof(DevState), hipMemcpyHostToDevice));
+  const DevProb* dp = ds[0]->d_prob; const DevState* dsv = ds[0]->d_state; u64* d_meta = nullptr;      // one Solve: the problem's own resident views
+  if (n > 1) {      // a batch: the views side by side, each state pointing at its 34 words of the batch's read-back block
+    const size_t o_meta = stage.add<u64>((size_t)n * 34);
+    TRY(stage.place()); d_meta = stage.d<u64>(o_meta);
+    for (u32 i = 0; i < n; ++i) stage.h<DevState>(stage.o_state)[i].batch_meta = d_meta + (size_t)i * 34;
+    TRY(stage.upload(o_meta)); dp = stage.probs(); dsv = stage.states();
   }
   hipStream_t st = ds[0]->stream;
   if (n > 1 && unbuilt) {
@@ -3448,23 +3543,24 @@ extern "C" int ks_solve_batch_dev(ks_dev_problem* const* ds, uint32_t n, ks_resu
   }
   hipEvent_t e0, e1; HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
   HIPCHK(hipEventRecord(e0, st));
-  // dynamic LDS: Allocatable table + visiting-order array.  One Solve gets most of the CU's 160 KiB;
-  // batched what-ifs take 64 KiB each so two workgroups share a CU.
-  const u32 lds_bytes = n == 1 ? 100u * 1024u : 64u * 1024u;
-  bool fast = true;
-  for (u32 i = 0; i < n; ++i) { const DevProb& q = ds[i]->h; if (q.G > KS_FAST_G || q.GH > KS_FAST_G || (q.SC > 1 && (size_t)q.S * q.SC > KS_FAST_S * KS_FAST_S) || (size_t)q.R * q.ge_max > KS_FAST_RT || (size_t)q.R * q.ge_max * 8 + 8192 > lds_bytes) fast = false; }
-  bool bounds = false; for (u32 i = 0; i < n; ++i) bounds = bounds || ds[i]->any_bounds;
-  bool lean = true; for (u32 i = 0; i < n; ++i) lean = lean && ds[i]->lean_ok;
-  u32 any_flags = 0; for (u32 i = 0; i < n; ++i) any_flags |= ds[i]->h.flags;
-  if (getenv("KS_NO_LEAN") || (any_flags & KS_FLAG_NO_LEAN)) lean = false;      // run the general variant on a problem the LEAN one would take (ksolve.h; the variable: test hook for the whole process)
+  // What the batch is, for the choice of kernel.  FAST reads the dynamic LDS of the single-wave launch: Allocatable table + visiting-order array.
+  const u32 lds_one = pack_lds_one_wave(n == 1);
+  bool fast = true, bounds = false, lean = true, wide = false, lean8 = false; u32 any_flags = 0;
+  for (u32 i = 0; i < n; ++i) {
+    const DevProb& q = ds[i]->h;
+    if (q.G > KS_FAST_G || q.GH > KS_FAST_G || (q.SC > 1 && (size_t)q.S * q.SC > KS_FAST_S * KS_FAST_S) || (size_t)q.R * q.ge_max > KS_FAST_RT || (size_t)q.R * q.ge_max * 8 + 8192 > lds_one) fast = false;
+    bounds = bounds || ds[i]->any_bounds; lean = lean && ds[i]->lean_ok; any_flags |= q.flags;
+    wide = wide || q.R > KS_RES_NARROW;      // (R > 8: never LEAN, so never ks_pack_rr)
+    lean8 = lean8 || q.R > 4;                // a LEAN problem with 5..8 resources (ks_problem.lean_r8): the LEAN variants' RM = 8 instantiations; ks_pack_rr stays at 4
+    ds[i]->rr_started = 0; ds[i]->rr_code = 0; ds[i]->pack_rm = 0; ds[i]->pack_lean = 0;
+  }
+  // the flag bits of ksolve.h, and the variables that ask the same of the whole process (test hooks)
+  if (getenv("KS_NO_LEAN") || (any_flags & KS_FLAG_NO_LEAN)) lean = false;                                // the general variant on a problem the LEAN one would take
+  const bool asked_one_wave = getenv("KS_ONE_WAVE") != nullptr || (any_flags & KS_FLAG_ONE_WAVE);      // ks_pack's single-wave variant
+  const bool asked_no_rr = getenv("KS_NO_RR") != nullptr || (any_flags & KS_FLAG_NO_RR);                 // ks_pack only (A/B, and the parity of both kernels)
   // The register-resident kernel (ks_pack_rr.inc) takes a single LEAN Solve without Gt/Lt bounds; it declines what it does not cover -- before
   // or during the run, without having touched the inputs -- and ks_pack below takes over.
   bool rr_done = false;
-  for (u32 i = 0; i < n; ++i) { ds[i]->rr_started = 0; ds[i]->rr_code = 0; ds[i]->pack_rm = 0; ds[i]->pack_lean = 0; }
-  bool wide = false; for (u32 i = 0; i < n; ++i) wide = wide || ds[i]->h.R > KS_RES_NARROW;      // (R > 8: never LEAN, so never ks_pack_rr)
-  bool lean8 = false; for (u32 i = 0; i < n; ++i) lean8 = lean8 || ds[i]->h.R > 4;               // a LEAN problem with 5..8 resources (ks_problem.lean_r8): the LEAN variants' RM = 8 instantiations; ks_pack_rr stays at 4
-  const bool asked_one_wave = getenv("KS_ONE_WAVE") != nullptr || (any_flags & KS_FLAG_ONE_WAVE);      // KS_ONE_WAVE asks for ks_pack's single-wave variant
-  const bool asked_no_rr = getenv("KS_NO_RR") != nullptr || (any_flags & KS_FLAG_NO_RR);                 // KS_NO_RR=1: ks_pack only (A/B, and the parity of both kernels)
 #ifdef KS_SIM
   // The emulator runs ks_pack_rr and (-DKS_SIM_PACK, round 5) ks_pack's single-wave variants -- what a what-if batch runs, LEAN and general.  The multi-wave variants'
   // speculation rounds lean on hand-offs between lanes in lockstep that the fibre emulator does not model yet: their results differ THERE, not on the GPU.
@@ -3511,44 +3607,24 @@ extern "C" int ks_solve_batch_dev(ks_dev_problem* const* ds, uint32_t n, ks_resu
   if (!rr_done) return fail(KS_ERR_UNSUPPORTED, "emulator build: the problem is outside what ks_pack_rr covers (ks_pack is not emulated in this build)");
 #else
   if (!rr_done) {
-  typedef void (*pack_fn)(const DevProb*, const DevState*, u32);
-  static const pack_fn variants[8] = {ks_pack<false, false, false, 1>, ks_pack<false, true, false, 1>, ks_pack<true, false, false, 1>, ks_pack<true, true, false, 1>,
-                                      ks_pack<false, false, true, 1>, ks_pack<false, true, true, 1>, ks_pack<true, false, true, 1>, ks_pack<true, true, true, 1>};
-  static const pack_fn variants_lean8[4] = {ks_pack<false, false, true, 1, 8>, ks_pack<false, true, true, 1, 8>, ks_pack<true, false, true, 1, 8>, ks_pack<true, true, true, 1, 8>};
-  static const pack_fn variants_wide[4] = {ks_pack<false, false, false, 1, 16>, ks_pack<false, true, false, 1, 16>, ks_pack<true, false, false, 1, 16>, ks_pack<true, true, false, 1, 16>};
-  {   // the large dynamic-LDS opt-in is a per-device function attribute: set it once per device, race-free (two Solves may run concurrently)
-    static std::mutex attr_mu; static std::vector<char> attr_done;
-    std::lock_guard<std::mutex> g(attr_mu);
-    if ((size_t)device >= attr_done.size()) attr_done.resize(device + 1, 0);
-    if (!attr_done[device]) {
-      for (int i = 0; i < 8; ++i) HIPCHK(hipFuncSetAttribute((const void*)variants[i], hipFuncAttributeMaxDynamicSharedMemorySize, 104 * 1024));
-      for (int i = 0; i < 4; ++i) HIPCHK(hipFuncSetAttribute((const void*)variants_wide[i], hipFuncAttributeMaxDynamicSharedMemorySize, 104 * 1024));
-      for (int i = 0; i < 4; ++i) HIPCHK(hipFuncSetAttribute((const void*)variants_lean8[i], hipFuncAttributeMaxDynamicSharedMemorySize, 104 * 1024));
-      HIPCHK(hipFuncSetAttribute((const void*)ks_pack<true, false, true, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 44 * 1024));
-      HIPCHK(hipFuncSetAttribute((const void*)ks_pack<true, false, true, KS_LEAN8_NW, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 44 * 1024));
-      HIPCHK(hipFuncSetAttribute((const void*)ks_pack<true, false, false, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 44 * 1024));
-      HIPCHK(hipFuncSetAttribute((const void*)ks_pack<true, true, false, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 44 * 1024));
-      attr_done[device] = 1;
+    const DevProb& q = ds[0]->h;
+    const u32 traits = (n == 1 ? KS_PT_SINGLE : 0) | (fast ? KS_PT_FAST : 0) | (bounds ? KS_PT_BOUNDS : 0) | (lean ? KS_PT_LEAN : 0) | (lean8 ? KS_PT_LEAN8 : 0) | (wide ? KS_PT_WIDE : 0) |
+                       (one_wave ? KS_PT_ONE_WAVE : 0) | (q.TW <= 128 ? KS_PT_TW128 : 0) | ((q.flags & KS_FLAG_STATS) ? KS_PT_STATS : 0) | (ds[0]->no_multi ? KS_PT_NO_MULTI : 0) |
+                       ((size_t)q.R * q.ge_max * 8 + 8192 <= KS_PACK_LDS_MULTI ? KS_PT_LADDERS44 : 0);
+    u32 lds = 0; const int row = pack_choose(traits, &lds);
+    if (row < 0) return fail(KS_ERR_INTERNAL, "ks_pack: no instantiation for these traits");
+    const PackRow& r = pack_rows[row];
+    {   // the large dynamic-LDS opt-in is a per-device function attribute: set it once per device, race-free (two Solves may run concurrently)
+      static std::mutex attr_mu; static std::vector<char> attr_done;
+      std::lock_guard<std::mutex> g(attr_mu);
+      if ((size_t)device >= attr_done.size()) attr_done.resize(device + 1, 0);
+      if (!attr_done[device]) {
+        for (const PackRow& a : pack_rows) HIPCHK(hipFuncSetAttribute((const void*)a.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)a.lds_max));
+        attr_done[device] = 1;
+      }
     }
-  }
-  // A single Solve whose problem takes the LEAN, FAST, no-bounds kernel gets 8 waves: waves 1..7 join wave 0 for the
-  // speculation rounds (see ks_pack).  T <= 8192 keeps a node's surviving-type mask in two registers per lane.
-  bool multi = n == 1 && fast && ds[0]->h.TW <= 128 && !(ds[0]->h.flags & KS_FLAG_STATS) && !one_wave && !ds[0]->no_multi && !wide;
-  if (multi) {
-    const u32 lds_mw = 44u * 1024u;
-    if ((size_t)ds[0]->h.R * ds[0]->h.ge_max * 8 + 8192 > lds_mw) multi = false;
-    else {
-      if (lean && !bounds && lean8) hipLaunchKernelGGL((ks_pack<true, false, true, KS_LEAN8_NW, 8>), dim3(1), dim3(64 * KS_LEAN8_NW), lds_mw, st, dp, dsv, lds_mw);
-      else if (lean && !bounds) hipLaunchKernelGGL((ks_pack<true, false, true, 8>), dim3(1), dim3(512), lds_mw, st, dp, dsv, lds_mw);
-      else if (bounds) hipLaunchKernelGGL((ks_pack<true, true, false, 4>), dim3(1), dim3(256), lds_mw, st, dp, dsv, lds_mw);
-      else hipLaunchKernelGGL((ks_pack<true, false, false, 4>), dim3(1), dim3(256), lds_mw, st, dp, dsv, lds_mw);     // host ports / limits / selectors on hostname or instance type: the general code
-                                                                                                                     // needs > 256 VGPRs, so 4 waves (one per SIMD): leader + 3 workers
-    }
-  }
-  if (!multi && wide) { hipLaunchKernelGGL(variants_wide[(fast ? 2 : 0) + (bounds ? 1 : 0)], dim3(n), dim3(64), lds_bytes, st, dp, dsv, lds_bytes); }
-  else if (!multi && lean && lean8) hipLaunchKernelGGL(variants_lean8[(fast ? 2 : 0) + (bounds ? 1 : 0)], dim3(n), dim3(64), lds_bytes, st, dp, dsv, lds_bytes);
-  else if (!multi) hipLaunchKernelGGL(variants[(lean ? 4 : 0) + (fast ? 2 : 0) + (bounds ? 1 : 0)], dim3(n), dim3(64), lds_bytes, st, dp, dsv, lds_bytes);
-  for (u32 i = 0; i < n; ++i) { ds[i]->pack_rm = wide ? 16 : (multi ? (lean && !bounds && !lean8 ? 4 : KS_RES_NARROW) : (lean && !lean8 ? 4 : KS_RES_NARROW)); ds[i]->pack_lean = !wide && lean && !(multi && bounds); }
+    hipLaunchKernelGGL(r.fn, dim3(n), dim3(64 * r.nw), lds, st, dp, dsv, lds);
+    for (u32 i = 0; i < n; ++i) { ds[i]->pack_rm = r.rm; ds[i]->pack_lean = r.lean; }
   }
 #endif
   HIPCHK(hipEventRecord(e1, st));
@@ -3581,19 +3657,14 @@ __global__ __launch_bounds__(64) void ks_records(const RecordDesc* descs, u64* o
 extern "C" int ks_batch_records_dev(ks_dev_problem* const* ds, uint32_t n, const uint64_t* ids, uint32_t words, void* d_out) {
   if (!n) return KS_OK;
   if (!ds || !ids || !d_out) return fail(KS_ERR_INVALID, "null argument");
-  const int device = ds[0]->device; HIPCHK(hipSetDevice(device));
-  std::vector<RecordDesc> hd(n);
-  for (u32 i = 0; i < n; ++i) {
-    if (ds[i]->device != device) return fail(KS_ERR_INVALID, "batch spans devices");
-    if (ds[i]->h.TW > words) return fail(KS_ERR_INVALID, "record row too short");
-    hd[i] = RecordDesc{ds[i]->hs.out_counts, ds[i]->hs.n_alive, ids[i], ds[i]->h.TW, 0};
-  }
-  TmpDev t_desc(device); TRY(t_desc.alloc(n * sizeof(RecordDesc)));
-  HIPCHK(hipMemcpyAsync(t_desc.p, hd.data(), n * sizeof(RecordDesc), hipMemcpyHostToDevice, ds[0]->stream));
-  const RecordDesc* d_desc = t_desc.as<RecordDesc>();
-  hipLaunchKernelGGL(ks_records, dim3(n), dim3(64), 0, ds[0]->stream, d_desc, (u64*)d_out, words);
-  HIPCHK(hipStreamSynchronize(ds[0]->stream)); HIPCHK(hipGetLastError());      // the buffer is complete when this returns: the caller's own stream may read it
-  return KS_OK;
+  BatchStage st; st.views = false;      // (the kernel reads the two arrays its descriptors name, nothing else of a problem)
+  TRY(st.open(ds, n, nullptr, false, [&](u32 i) { return ds[i]->h.TW > words ? fail(KS_ERR_INVALID, "record row too short") : KS_OK; }));
+  const size_t o_desc = st.add<RecordDesc>(n);
+  TRY(st.place());
+  for (u32 i = 0; i < n; ++i) st.h<RecordDesc>(o_desc)[i] = RecordDesc{ds[i]->hs.out_counts, ds[i]->hs.n_alive, ids[i], ds[i]->h.TW, 0};
+  TRY(st.upload(st.bytes));
+  hipLaunchKernelGGL(ks_records, dim3(n), dim3(64), 0, st.stream(), st.d<const RecordDesc>(o_desc), (u64*)d_out, words);
+  return st.fetch(st.bytes);      // the buffer is complete when this returns: the caller's own stream may read it
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -3659,11 +3730,15 @@ extern "C" int ks_solve_batch_sharded(ks_dev_problem* const* const* shards, cons
 // What worstLaunchPrice reads of a node's requirements (helpers.go:292-315): the zones it admits, whether its capacity-type requirement Has(spot) /
 // Has(on-demand) -- spot_only: after Requirements.Add(capacity-type In [spot]) --, the stride of the price table.
 struct PriceCtx { u64 allowZ; u32 NP; bool spot, od; };
-__device__ __forceinline__ PriceCtx price_ctx(const DevProb& P, const DevState& S, u32 j, bool spot_only) {
+// new node j's requirements on the zone and the capacity type
+__device__ __forceinline__ void node_zone_ct_reqs(const DevProb& P, const DevState& S, u32 j, KReq& zq, KReq& cq) {
   const u32 pres = S.o_present[j], comp = S.o_complement[j];
   // reqs.Get(key): a missing key reads as Exists (requirements.go:114-120), which Has() every value
-  const KReq zq = ((pres >> P.key_zone) & 1u) ? load_req(pres, comp, S.o_mask + (size_t)j * P.K, S.o_gt + (size_t)j * P.K, S.o_lt + (size_t)j * P.K, P.key_zone) : kreq_exists();
-  const KReq cq = ((pres >> P.key_ct) & 1u) ? load_req(pres, comp, S.o_mask + (size_t)j * P.K, S.o_gt + (size_t)j * P.K, S.o_lt + (size_t)j * P.K, P.key_ct) : kreq_exists();
+  zq = ((pres >> P.key_zone) & 1u) ? load_req(pres, comp, S.o_mask + (size_t)j * P.K, S.o_gt + (size_t)j * P.K, S.o_lt + (size_t)j * P.K, P.key_zone) : kreq_exists();
+  cq = ((pres >> P.key_ct) & 1u) ? load_req(pres, comp, S.o_mask + (size_t)j * P.K, S.o_gt + (size_t)j * P.K, S.o_lt + (size_t)j * P.K, P.key_ct) : kreq_exists();
+}
+__device__ __forceinline__ PriceCtx price_ctx(const DevProb& P, const DevState& S, u32 j, bool spot_only) {
+  KReq zq, cq; node_zone_ct_reqs(P, S, j, zq, cq);
   PriceCtx c; c.allowZ = kreq_has_mask(zq, P.value_int + P.key_zone * 64, P.key_nvalues[P.key_zone]);
   u64 allowC = kreq_has_mask(cq, P.value_int + P.key_ct * 64, P.key_nvalues[P.key_ct]);
   if (spot_only) allowC &= P.ct_spot >= 0 ? (1ull << P.ct_spot) : 0ull;     // Requirements.Add(capacity-type In [spot])
@@ -3671,22 +3746,21 @@ __device__ __forceinline__ PriceCtx price_ctx(const DevProb& P, const DevState& 
   c.spot = P.ct_spot >= 0 && ((allowC >> P.ct_spot) & 1ull); c.od = P.ct_ondemand >= 0 && ((allowC >> P.ct_ondemand) & 1ull);
   return c;
 }
+// The worst (highest) price among type t's offerings of capacity type `ct` in the allowed zones; false if it has none there
+__device__ __forceinline__ bool worst_price(const DevProb& P, const PriceCtx& c, u32 t, u64 offer, i32 ct, double* out) {
+  double mx = 0.0; bool got = false;
+  for (u64 zz = c.allowZ; zz; zz &= zz - 1) { const u32 pair = (u32)__builtin_ctzll(zz) * P.n_ct + (u32)ct; if (pair < 64 && ((offer >> pair) & 1ull)) { const double pr = P.it_price[(size_t)t * c.NP + pair]; if (!got || pr > mx) mx = pr; got = true; } }
+  if (got) *out = mx;
+  return got;
+}
 // filterByPrice over one word of a type mask (helpers.go:148-157): of the types `bits` names in word w, those whose worst launch price is < maxp
 __device__ __forceinline__ u64 price_filter_word(const DevProb& P, const PriceCtx& c, u64 bits, u32 w, double maxp) {
   u64 out = 0;
   for (; bits; bits &= bits - 1) {
     const u32 b = (u32)__builtin_ctzll(bits), t = w * 64 + b; const u64 offer = P.it_offer[t];
-    double launch = 1.7976931348623157e308; bool got = false;      // math.MaxFloat64
-    if (c.spot) {          // "we prefer to launch spot offerings": the worst (highest) spot price in the allowed zones
-      double mx = 0.0;
-      for (u64 zz = c.allowZ; zz; zz &= zz - 1) { const u32 pair = (u32)__builtin_ctzll(zz) * P.n_ct + (u32)P.ct_spot; if (pair < 64 && ((offer >> pair) & 1ull)) { const double pr = P.it_price[(size_t)t * c.NP + pair]; if (!got || pr > mx) mx = pr; got = true; } }
-      if (got) launch = mx;
-    }
-    if (!got && c.od) {
-      double mx = 0.0;
-      for (u64 zz = c.allowZ; zz; zz &= zz - 1) { const u32 pair = (u32)__builtin_ctzll(zz) * P.n_ct + (u32)P.ct_ondemand; if (pair < 64 && ((offer >> pair) & 1ull)) { const double pr = P.it_price[(size_t)t * c.NP + pair]; if (!got || pr > mx) mx = pr; got = true; } }
-      if (got) launch = mx;
-    }
+    double launch = 1.7976931348623157e308;      // math.MaxFloat64
+    const bool got = c.spot && worst_price(P, c, t, offer, P.ct_spot, &launch);      // "we prefer to launch spot offerings": the worst spot price in the allowed zones
+    if (!got && c.od) worst_price(P, c, t, offer, P.ct_ondemand, &launch);
     if (launch < maxp) out |= 1ull << b;
   }
   return out;
@@ -3711,30 +3785,21 @@ __global__ __launch_bounds__(64) void ks_price_filter(const DevProb* probs, cons
 extern "C" int ks_price_filter_dev(ks_dev_problem* const* ds, uint32_t n, const uint32_t* node, const double* max_price, const uint32_t* spot_only, uint64_t* const* out_types, uint32_t* out_counts) {
   if (!n) return KS_OK;
   if (!ds || !node || !max_price || !out_types || !out_counts) return fail(KS_ERR_INVALID, "null argument");
-  const int device = ds[0]->device; HIPCHK(hipSetDevice(device));
-  std::vector<DevProb> hp(n); std::vector<DevState> hs(n); size_t words = 0; std::vector<size_t> off(n);
-  for (u32 i = 0; i < n; ++i) {
-    if (ds[i]->device != device) return fail(KS_ERR_INVALID, "batch spans devices");
-    if (!ds[i]->h.it_price || ds[i]->h.key_zone < 0 || ds[i]->h.key_ct < 0) return fail(KS_ERR_INVALID, "problem carries no offering prices");
-    if (node[i] >= ds[i]->h.NMAX) return fail(KS_ERR_INVALID, "node index out of range");
-    hp[i] = ds[i]->h; hs[i] = ds[i]->hs; off[i] = words; words += ds[i]->h.TW;
-  }
-  TmpDev t_dp(device), t_dsv(device), t_node(device), t_max(device), t_out(device), t_ptr(device), t_cnt(device), t_spot(device);
-  u32* dspot = nullptr;
-  if (spot_only) { TRY(t_spot.alloc(n * sizeof(u32))); dspot = t_spot.as<u32>(); HIPCHK(hipMemcpy(dspot, spot_only, n * sizeof(u32), hipMemcpyHostToDevice)); }
-  TRY(t_dp.alloc(n * sizeof(DevProb))); TRY(t_dsv.alloc(n * sizeof(DevState))); TRY(t_node.alloc(n * sizeof(u32))); TRY(t_max.alloc(n * sizeof(double)));
-  TRY(t_out.alloc((words ? words : 1) * sizeof(u64))); TRY(t_ptr.alloc(n * sizeof(u64*))); TRY(t_cnt.alloc(n * sizeof(u32)));
-  DevProb* dp = t_dp.as<DevProb>(); DevState* dsv = t_dsv.as<DevState>(); u32* dnode = t_node.as<u32>(); double* dmax = t_max.as<double>(); u64* dout = t_out.as<u64>(); u64** dptr = t_ptr.as<u64*>(); u32* dcnt = t_cnt.as<u32>();
-  std::vector<u64*> ptrs(n); for (u32 i = 0; i < n; ++i) ptrs[i] = dout + off[i];
-  HIPCHK(hipMemcpy(dp, hp.data(), n * sizeof(DevProb), hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(dsv, hs.data(), n * sizeof(DevState), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(dnode, node, n * sizeof(u32), hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(dmax, max_price, n * sizeof(double), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(dptr, ptrs.data(), n * sizeof(u64*), hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(ks_price_filter, dim3(n), dim3(64), 0, ds[0]->stream, dp, dsv, dnode, dmax, (const u32*)dspot, dptr, dcnt);
-  std::vector<u64> host(words ? words : 1);
-  HIPCHK(hipMemcpyAsync(host.data(), dout, (words ? words : 1) * sizeof(u64), hipMemcpyDeviceToHost, ds[0]->stream));
-  HIPCHK(hipMemcpyAsync(out_counts, dcnt, n * sizeof(u32), hipMemcpyDeviceToHost, ds[0]->stream));
-  HIPCHK(hipStreamSynchronize(ds[0]->stream)); HIPCHK(hipGetLastError());
-  for (u32 i = 0; i < n; ++i) memcpy(out_types[i], host.data() + off[i], ds[i]->h.TW * sizeof(u64));
+  BatchStage st; TRY(st.open(ds, n, node, true));
+  size_t words = 0; std::vector<size_t> off(n);
+  for (u32 i = 0; i < n; ++i) { off[i] = words; words += ds[i]->h.TW; }
+  // in: [max price n | mask pointers n | node n | spot-only n]; out: [masks | counts n]
+  const size_t o_max = st.add<double>(n), o_ptr = st.add<u64*>(n), o_node = st.add<u32>(n), o_spot = st.add<u32>(spot_only ? n : 0), o_out = st.add<u64>(words), o_cnt = st.add<u32>(n);
+  TRY(st.place());
+  memcpy(st.h<double>(o_max), max_price, n * sizeof(double)); memcpy(st.h<u32>(o_node), node, n * sizeof(u32));
+  if (spot_only) memcpy(st.h<u32>(o_spot), spot_only, n * sizeof(u32));
+  for (u32 i = 0; i < n; ++i) st.h<u64*>(o_ptr)[i] = st.d<u64>(o_out) + off[i];
+  TRY(st.upload(o_out));
+  hipLaunchKernelGGL(ks_price_filter, dim3(n), dim3(64), 0, st.stream(), st.probs(), st.states(), st.d<const u32>(o_node), st.d<const double>(o_max),
+                     spot_only ? st.d<const u32>(o_spot) : (const u32*)nullptr, st.d<u64*>(o_ptr), st.d<u32>(o_cnt));
+  TRY(st.fetch(o_out));
+  for (u32 i = 0; i < n; ++i) memcpy(out_types[i], st.h<u64>(o_out) + off[i], ds[i]->h.TW * sizeof(u64));
+  memcpy(out_counts, st.h<u32>(o_cnt), n * sizeof(u32));
   return KS_OK;
 }
 
@@ -3819,65 +3884,50 @@ __global__ __launch_bounds__(64) void ks_consolidation_commands(const DevProb* p
   }
 }
 
-// every refusal of ks_consolidation_commands*: before any device work
-static int commands_check(ks_dev_problem* const* ds, u32 n, const uint64_t* ids, const ks_command_inputs* in, u32 words) {
+// every refusal of ks_consolidation_commands*: before any device work (`st` is opened by it)
+static int commands_check(BatchStage& st, ks_dev_problem* const* ds, u32 n, const uint64_t* ids, const ks_command_inputs* in, u32 words) {
   if (!ds || !ids || !in || !in->flags || !in->cand_price || !in->type_off) return fail(KS_ERR_INVALID, "null argument");
-  for (u32 i = 0; i < n; ++i) if (!ds[i]) return fail(KS_ERR_INVALID, "null device problem");
+  TRY(BatchStage::not_null(ds, n));
   for (u32 i = 0; i < n; ++i) if (in->type_off[i + 1] < in->type_off[i]) return fail(KS_ERR_INVALID, "type list offsets not ascending");
-  const int device = ds[0]->device; const u32 n_types = in->type_off[n];
+  const u32 n_types = in->type_off[n];
   if (n_types && (!in->type_idx || !in->type_price)) return fail(KS_ERR_INVALID, "null argument");
-  for (u32 i = 0; i < n; ++i) {
-    if (ds[i]->device != device) return fail(KS_ERR_INVALID, "batch spans devices");
-    if (!ds[i]->h.it_price || ds[i]->h.key_zone < 0 || ds[i]->h.key_ct < 0) return fail(KS_ERR_INVALID, "problem carries no offering prices");
+  return st.open(ds, n, nullptr, true, [&](u32 i) {
     if (ds[i]->h.TW > words) return fail(KS_ERR_INVALID, "command row too short");
     if (ds[i]->h.K > KS_MAX_KEYS || ds[i]->h.NMAX < 1) return fail(KS_ERR_INVALID, "problem outside the command row's layout");
     if (in->flags[i] & ~(uint32_t)KS_CMD_F_ALL) return fail(KS_ERR_INVALID, "unknown command flag bit");
-    if (in->type_off[i + 1] < in->type_off[i] || in->type_off[i + 1] > n_types) return fail(KS_ERR_INVALID, "type list offsets not ascending");
+    if (in->type_off[i + 1] > n_types) return fail(KS_ERR_INVALID, "type list offsets not ascending");
     for (u32 k = in->type_off[i]; k < in->type_off[i + 1]; ++k) if (in->type_idx[k] >= ds[i]->h.T) return fail(KS_ERR_INVALID, "type index out of range");
-  }
-  return KS_OK;
+    return (int)KS_OK;
+  });
 }
 // inputs up in one block, one launch, completion: what both entry points do once commands_check has passed
-static int commands_launch(ks_dev_problem* const* ds, u32 n, const uint64_t* ids, const ks_command_inputs* in, u32 words, void* d_out) {
-  const int device = ds[0]->device;
-  const u32 n_types = in->type_off[n];
-  std::vector<DevProb> hp(n); std::vector<DevState> hs(n); std::vector<CmdDesc> hd(n);
-  for (u32 i = 0; i < n; ++i) {
-    hp[i] = ds[i]->h; hs[i] = ds[i]->hs; hd[i] = CmdDesc{ids[i], in->cand_price[i], in->flags[i], in->type_off[i], in->type_off[i + 1], 0};
-  }
-  HIPCHK(hipSetDevice(device));
-  // one block of inputs, one transfer: [DevProb n | DevState n | CmdDesc n | type prices | type indices]
-  const size_t o_state = n * sizeof(DevProb), o_desc = o_state + n * sizeof(DevState), o_price = o_desc + n * sizeof(CmdDesc), o_idx = o_price + (size_t)n_types * sizeof(double),
-               total = o_idx + (size_t)n_types * sizeof(u32);
-  std::vector<u64> host((total + 7) / 8);
-  memcpy((u8*)host.data(), hp.data(), n * sizeof(DevProb)); memcpy((u8*)host.data() + o_state, hs.data(), n * sizeof(DevState)); memcpy((u8*)host.data() + o_desc, hd.data(), n * sizeof(CmdDesc));
-  if (n_types) { memcpy((u8*)host.data() + o_price, in->type_price, (size_t)n_types * sizeof(double)); memcpy((u8*)host.data() + o_idx, in->type_idx, (size_t)n_types * sizeof(u32)); }
-  TmpDev t_in(device); TRY(t_in.alloc(host.size() * 8));
-  HIPCHK(hipMemcpy(t_in.p, host.data(), total, hipMemcpyHostToDevice));      // (synchronous, like ks_price_filter_dev's: `host` is pageable and dies with this call)
-  const u8* base = t_in.as<u8>();
-  const DevProb* dp = (const DevProb*)base; const DevState* dsv = (const DevState*)(base + o_state); const CmdDesc* dd = (const CmdDesc*)(base + o_desc);
-  const double* dprice = (const double*)(base + o_price); const u32* didx = (const u32*)(base + o_idx);
-  hipLaunchKernelGGL(ks_consolidation_commands, dim3(n), dim3(64), 0, ds[0]->stream, dp, dsv, dd, didx, dprice, (u64*)d_out, words);
-  HIPCHK(hipStreamSynchronize(ds[0]->stream)); HIPCHK(hipGetLastError());      // the buffer is complete when this returns: the caller's own stream may read it
-  return KS_OK;
+static int commands_launch(BatchStage& st, const uint64_t* ids, const ks_command_inputs* in, u32 words, void* d_out) {
+  const u32 n = st.n, n_types = in->type_off[n];
+  const size_t o_desc = st.add<CmdDesc>(n), o_price = st.add<double>(n_types), o_idx = st.add<u32>(n_types);
+  TRY(st.place());
+  for (u32 i = 0; i < n; ++i) st.h<CmdDesc>(o_desc)[i] = CmdDesc{ids[i], in->cand_price[i], in->flags[i], in->type_off[i], in->type_off[i + 1], 0};
+  if (n_types) { memcpy(st.h<double>(o_price), in->type_price, (size_t)n_types * sizeof(double)); memcpy(st.h<u32>(o_idx), in->type_idx, (size_t)n_types * sizeof(u32)); }
+  TRY(st.upload(st.bytes));
+  hipLaunchKernelGGL(ks_consolidation_commands, dim3(n), dim3(64), 0, st.stream(), st.probs(), st.states(), st.d<const CmdDesc>(o_desc), st.d<const u32>(o_idx), st.d<const double>(o_price), (u64*)d_out, words);
+  return st.fetch(st.bytes);      // the buffer is complete when this returns: the caller's own stream may read it
 }
 
 extern "C" int ks_consolidation_commands_dev(ks_dev_problem* const* ds, uint32_t n, const uint64_t* ids, const ks_command_inputs* in, uint32_t words, void* d_out) {
   if (!n) return KS_OK;
   if (!d_out) return fail(KS_ERR_INVALID, "null argument");
-  TRY(commands_check(ds, n, ids, in, words));
-  return commands_launch(ds, n, ids, in, words, d_out);
+  BatchStage st; TRY(commands_check(st, ds, n, ids, in, words));
+  return commands_launch(st, ids, in, words, d_out);
 }
 // The same with the rows brought to the host (what a caller without a device buffer of its own wants): ms[0] = inputs up + launch + completion, ms[1] = read-back.
 extern "C" int ks_consolidation_commands_host(ks_dev_problem* const* ds, uint32_t n, const uint64_t* ids, const ks_command_inputs* in, uint32_t words, uint64_t* out_rows, double* ms) {
   if (ms) ms[0] = ms[1] = 0.0;
   if (!n) return KS_OK;
   if (!out_rows) return fail(KS_ERR_INVALID, "null argument");
-  TRY(commands_check(ds, n, ids, in, words));
+  BatchStage st; TRY(commands_check(st, ds, n, ids, in, words));
   const size_t bytes = (size_t)n * KS_CMD_ROW_WORDS(words) * sizeof(u64);
   TmpDev buf(ds[0]->device); TRY(buf.alloc(bytes));
   const auto t0 = std::chrono::steady_clock::now();
-  TRY(commands_launch(ds, n, ids, in, words, buf.p));
+  TRY(commands_launch(st, ids, in, words, buf.p));
   const auto t1 = std::chrono::steady_clock::now();
   HIPCHK(hipMemcpy(out_rows, buf.p, bytes, hipMemcpyDeviceToHost));
   if (ms) { ms[0] = std::chrono::duration<double, std::milli>(t1 - t0).count(); ms[1] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count(); }
@@ -3892,9 +3942,7 @@ extern "C" int ks_consolidation_commands_host(ks_dev_problem* const* ds, uint32_
 __global__ __launch_bounds__(64) void ks_launch_pick(const DevProb* probs, const DevState* states, const u32* node, i32* out_type, i32* out_pair, double* out_price) {
   const DevProb& P = probs[blockIdx.x]; const DevState& S = states[blockIdx.x];
   const u32 j = node[blockIdx.x]; const int lane = threadIdx.x;
-  const u32 pres = S.o_present[j], comp = S.o_complement[j];
-  const KReq zq = ((pres >> P.key_zone) & 1u) ? load_req(pres, comp, S.o_mask + (size_t)j * P.K, S.o_gt + (size_t)j * P.K, S.o_lt + (size_t)j * P.K, P.key_zone) : kreq_exists();
-  const KReq cq = ((pres >> P.key_ct) & 1u) ? load_req(pres, comp, S.o_mask + (size_t)j * P.K, S.o_gt + (size_t)j * P.K, S.o_lt + (size_t)j * P.K, P.key_ct) : kreq_exists();
+  KReq zq, cq; node_zone_ct_reqs(P, S, j, zq, cq);
   const u64 allowZ = kreq_has_mask(zq, P.value_int + P.key_zone * 64, P.key_nvalues[P.key_zone]);
   const u64 allowC = kreq_has_mask(cq, P.value_int + P.key_ct * 64, P.key_nvalues[P.key_ct]) & (P.n_ct >= 64 ? ~0ull : ((1ull << P.n_ct) - 1ull));
   const u32 NP = P.key_nvalues[P.key_zone] * P.n_ct;
@@ -3923,49 +3971,32 @@ __global__ __launch_bounds__(64) void ks_types_subset(const DevProb* probs, cons
   const u64 b = ballot64(bad);
   if (lane == 0) out[blockIdx.x] = b ? 0u : 1u;
 }
-static int batch_descriptors(ks_dev_problem* const* ds, u32 n, const u32* node, bool need_prices, TmpDev& t_dp, TmpDev& t_dsv, TmpDev& t_node) {
-  if (!ds || !node) return fail(KS_ERR_INVALID, "null argument");
-  const int device = ds[0]->device;
-  std::vector<DevProb> hp(n); std::vector<DevState> hs(n);
-  for (u32 i = 0; i < n; ++i) {
-    if (ds[i]->device != device) return fail(KS_ERR_INVALID, "batch spans devices");
-    if (need_prices && (!ds[i]->h.it_price || ds[i]->h.key_zone < 0 || ds[i]->h.key_ct < 0)) return fail(KS_ERR_INVALID, "problem carries no offering prices");
-    if (node[i] >= ds[i]->h.NMAX) return fail(KS_ERR_INVALID, "node index out of range");
-    hp[i] = ds[i]->h; hs[i] = ds[i]->hs;
-  }
-  TRY(t_dp.alloc(n * sizeof(DevProb))); TRY(t_dsv.alloc(n * sizeof(DevState))); TRY(t_node.alloc(n * sizeof(u32)));
-  HIPCHK(hipMemcpy(t_dp.p, hp.data(), n * sizeof(DevProb), hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(t_dsv.p, hs.data(), n * sizeof(DevState), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(t_node.p, node, n * sizeof(u32), hipMemcpyHostToDevice));
-  return KS_OK;
-}
 extern "C" int ks_launch_pick_dev(ks_dev_problem* const* ds, uint32_t n, const uint32_t* node, int32_t* out_type, int32_t* out_pair, double* out_price) {
   if (!n) return KS_OK;
-  if (!ds || !out_type || !out_pair || !out_price) return fail(KS_ERR_INVALID, "null argument");
-  const int device = ds[0]->device; HIPCHK(hipSetDevice(device));
-  TmpDev t_dp(device), t_dsv(device), t_node(device), t_type(device), t_pair(device), t_price(device);
-  TRY(batch_descriptors(ds, n, node, true, t_dp, t_dsv, t_node));
-  TRY(t_type.alloc(n * sizeof(i32))); TRY(t_pair.alloc(n * sizeof(i32))); TRY(t_price.alloc(n * sizeof(double)));
-  const DevProb* dp = t_dp.as<DevProb>(); const DevState* dsv = t_dsv.as<DevState>(); const u32* dnode = t_node.as<u32>();
-  i32* dtype = t_type.as<i32>(); i32* dpair = t_pair.as<i32>(); double* dprice = t_price.as<double>();
-  hipLaunchKernelGGL(ks_launch_pick, dim3(n), dim3(64), 0, ds[0]->stream, dp, dsv, dnode, dtype, dpair, dprice);
-  HIPCHK(hipMemcpyAsync(out_type, t_type.p, n * sizeof(i32), hipMemcpyDeviceToHost, ds[0]->stream)); HIPCHK(hipMemcpyAsync(out_pair, t_pair.p, n * sizeof(i32), hipMemcpyDeviceToHost, ds[0]->stream));
-  HIPCHK(hipMemcpyAsync(out_price, t_price.p, n * sizeof(double), hipMemcpyDeviceToHost, ds[0]->stream));
-  HIPCHK(hipStreamSynchronize(ds[0]->stream)); HIPCHK(hipGetLastError());
+  if (!ds || !node || !out_type || !out_pair || !out_price) return fail(KS_ERR_INVALID, "null argument");
+  BatchStage st; TRY(st.open(ds, n, node, true));
+  const size_t o_node = st.add<u32>(n), o_price = st.add<double>(n), o_type = st.add<i32>(n), o_pair = st.add<i32>(n);      // in: the nodes; out: the three answers
+  TRY(st.place());
+  memcpy(st.h<u32>(o_node), node, n * sizeof(u32));
+  TRY(st.upload(o_price));
+  hipLaunchKernelGGL(ks_launch_pick, dim3(n), dim3(64), 0, st.stream(), st.probs(), st.states(), st.d<const u32>(o_node), st.d<i32>(o_type), st.d<i32>(o_pair), st.d<double>(o_price));
+  TRY(st.fetch(o_price));
+  memcpy(out_type, st.h<i32>(o_type), n * sizeof(i32)); memcpy(out_pair, st.h<i32>(o_pair), n * sizeof(i32)); memcpy(out_price, st.h<double>(o_price), n * sizeof(double));
   return KS_OK;
 }
 extern "C" int ks_types_subset_dev(ks_dev_problem* const* ds, uint32_t n, const uint32_t* node, const uint64_t* lhs, uint32_t stride_words, uint32_t* out) {
   if (!n) return KS_OK;
   if (!ds || !lhs || !out) return fail(KS_ERR_INVALID, "null argument");
-  const int device = ds[0]->device; HIPCHK(hipSetDevice(device));
   for (u32 i = 0; i < n; ++i) if (ds[i]->h.TW > stride_words) return fail(KS_ERR_INVALID, "mask row too short");
-  TmpDev t_dp(device), t_dsv(device), t_node(device), t_lhs(device), t_out(device);
-  TRY(batch_descriptors(ds, n, node, false, t_dp, t_dsv, t_node));
-  TRY(t_lhs.alloc((size_t)n * stride_words * sizeof(u64))); TRY(t_out.alloc(n * sizeof(u32)));
-  HIPCHK(hipMemcpy(t_lhs.p, lhs, (size_t)n * stride_words * sizeof(u64), hipMemcpyHostToDevice));
-  const DevProb* dp = t_dp.as<DevProb>(); const DevState* dsv = t_dsv.as<DevState>(); const u32* dnode = t_node.as<u32>(); const u64* dlhs = t_lhs.as<u64>(); u32* dout = t_out.as<u32>();
-  hipLaunchKernelGGL(ks_types_subset, dim3(n), dim3(64), 0, ds[0]->stream, dp, dsv, dnode, dlhs, stride_words, dout);
-  HIPCHK(hipMemcpyAsync(out, t_out.p, n * sizeof(u32), hipMemcpyDeviceToHost, ds[0]->stream));
-  HIPCHK(hipStreamSynchronize(ds[0]->stream)); HIPCHK(hipGetLastError());
+  if (!node) return fail(KS_ERR_INVALID, "null argument");
+  BatchStage st; TRY(st.open(ds, n, node, false));
+  const size_t o_lhs = st.add<u64>((size_t)n * stride_words), o_node = st.add<u32>(n), o_out = st.add<u32>(n);
+  TRY(st.place());
+  memcpy(st.h<u64>(o_lhs), lhs, (size_t)n * stride_words * sizeof(u64)); memcpy(st.h<u32>(o_node), node, n * sizeof(u32));
+  TRY(st.upload(o_out));
+  hipLaunchKernelGGL(ks_types_subset, dim3(n), dim3(64), 0, st.stream(), st.probs(), st.states(), st.d<const u32>(o_node), st.d<const u64>(o_lhs), stride_words, st.d<u32>(o_out));
+  TRY(st.fetch(o_out));
+  memcpy(out, st.h<u32>(o_out), n * sizeof(u32));
   return KS_OK;
 }
 
