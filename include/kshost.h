@@ -253,6 +253,73 @@ const char* ksh_snapshot_name(void* parsed_snapshot, int what, uint32_t a, uint3
 int ksh_snapshot_it_state(void* parsed_snapshot, uint32_t state, int* complement, uint32_t* n_values);
 const char* ksh_snapshot_it_state_value(void* parsed_snapshot, uint32_t state, uint32_t i);
 
+/* ---- consolidation CANDIDATES, selected and ordered on the device: the first step of a consolidation pass, so that snapshot -> candidates -> commands runs through
+ * this header alone.  candidateNodes (deprovisioning/helpers.go:171-249) with consolidation.ShouldDeprovision (consolidation.go:106-121) as its filter, then
+ * sortAndFilterCandidates (consolidation.go:83-104): canBeTerminated with PDBLimits.CanEvictPods and PodsPreventEviction (helpers.go:339-366, pdblimits.go:55-70),
+ * disruptionCost x calculateLifetimeRemaining (helpers.go:124-165,275-287), and the sort.  out->order is what ksh_first_n_node_option / ksh_single_node_option take as
+ * `candidates`; out->empty is EmptyNodeConsolidation's nodesToRemove (emptynodeconsolidation.go:54).
+ *
+ * The snapshot's nodes and bound pods are the slots ksh_snapshot_bindings reports; its bound pods are GetNodePods' output (utils/node/node.go:30-49: daemonset-owned,
+ * node-owned, terminal and terminating pods are not in it), so the skips of PodsPreventEviction are vacuous and "no pods" is "no bound pod".  `pod_node`: as for the
+ * command calls (NULL after ksh_env_apply*).  `deleting`: the nodes that are MarkedForDeletion.
+ * ksh_candidate_inputs: what the snapshot's objects do not carry.  n_nodes / n_pods / n_provisioners must equal the snapshot's slot counts and its provisioner count
+ * (the provisioners in the snapshot's order).  age_seconds is what clock.Since(CreationTimestamp).Seconds() gave; deletion_cost is the parsed
+ * controller.kubernetes.io/pod-deletion-cost annotation (parsing it, and dropping one that does not parse, stays with the caller); ttl_seconds_until_expired is -1 for nil.
+ * KS_ERR_INVALID: a deletion cost that is not finite, an age that is not finite, a ttl of 0 -- the reference divides by zero there -- or below -1, a wrong array
+ * length, an unknown flag bit (KSH_CAND_NODE_DO_NOT_CONSOLIDATE_TRUE without KSH_CAND_NODE_DO_NOT_CONSOLIDATE included), a deleting node out of range.
+ * ksh_pdb_block: the PodDisruptionBudgets as one stream of u32 words over one string table (conventions of ksh_delta_block; grammar in
+ * karpenter_core_amd/host/kspb.hpp, PdbReader): per PDB namespace:S disruptions_allowed:I selector.  The block is decoded completely before anything else happens: a
+ * malformed one -- or a selector metav1.LabelSelectorAsSelector refuses -- is KS_ERR_INVALID with the PDB's index in ksh_last_error().  NULL means no PDBs.
+ * Selectors are flattened for the device: the label keys some selector mentions, at most KS_CAND_MAX_KEYS, and per key the values some selector
+ * mentions, at most KS_CAND_MAX_VALUES; beyond either, KS_ERR_UNSUPPORTED with both counts in the message and nothing written.
+ *
+ * out->why[node] (0 = candidate; the first reason in the reference's own order wins), out->detail[node] (-1 unless stated):
+ *    1  listed in `deleting` (helpers.go:186)                2  no provisioner-name label, or it names no provisioner of the snapshot (:190)
+ *    3  the instance-type label names no type of that provisioner (:194-198)          4  no capacity-type label (:201)          5  no zone label (:205)
+ *    6  not initialised (:211)          7  nominated (:215)          8  the do-not-consolidate annotation is "true" (consolidation.go:108-111: literally
+ *       `return val != "true"` -- an annotation with any other value makes the node pass WITHOUT the provisioner checks)
+ *    9  the provisioner has consolidation disabled (:116-119)          10  deletion timestamp set (helpers.go:340)
+ *   11  a PDB prevents evictions; detail = the PDB's index (first pod in slot order, first PDB in order; a PDB with disruptions allowed never blocks)
+ *   12  a pod has do-not-evict; detail = the pod slot          13  the slot's node left (NODE-, or a node that is not in state)
+ * 1-9: not in candidateNodes' result; 10-12: in it, filtered by sortAndFilterCandidates.  out->cost[node] is the final disruption cost: the pods' eviction costs
+ * summed sequentially in ascending slot order -- float64 addition is order-dependent and Go walks GetNodePods' list; the slot order is the canonical execution --
+ * times the lifetime remaining.  It is written for 0 and 10-12 and is 0.0 for 1-9 and 13.  out->n_node_pods[node]: the bound pods of the slot.
+ * out->order[0 .. n_candidates): the candidates by `cost <`, the reference's comparator (-0.0 and +0.0 tie); ties by ascending node slot -- Go's sort.Slice is
+ * unstable and ForEachNode walks a map, the canonical execution is the stable sort over ascending slot.  out->empty[0 .. n_empty): the candidates without pods, in the
+ * same order.  The arrays are the caller's, [node slots] each.
+ * ms[4] (may be NULL): host tabulation | upload | kernels | read-back, milliseconds.  Reasons 2-6 are tabulated from the nodes' labels by the first call over a
+ * snapshot and kept with it, next to the command calls' label table, until ksh_env_apply* changes the nodes.  There is no host path: without a device, KS_ERR_DEVICE. */
+#define KSH_CAND_NODE_NOMINATED 1u
+#define KSH_CAND_NODE_DO_NOT_CONSOLIDATE 2u         /* the karpenter.sh/do-not-consolidate annotation is present */
+#define KSH_CAND_NODE_DO_NOT_CONSOLIDATE_TRUE 4u    /* ... and its value is "true" */
+#define KSH_CAND_NODE_DELETION_TIMESTAMP 8u
+#define KSH_CAND_POD_DO_NOT_EVICT KS_CAND_POD_DO_NOT_EVICT
+#define KSH_CAND_POD_HAS_DELETION_COST KS_CAND_POD_HAS_DELETION_COST
+#define KSH_CAND_POD_HAS_PRIORITY KS_CAND_POD_HAS_PRIORITY
+typedef struct ksh_candidate_inputs {
+  uint32_t n_nodes, n_pods, n_provisioners, pad;
+  const uint32_t* node_flags;                 /* [n_nodes] KSH_CAND_NODE_* */
+  const double* node_age_seconds;             /* [n_nodes] */
+  const uint32_t* pod_flags;                  /* [n_pods] KSH_CAND_POD_* */
+  const double* pod_deletion_cost;            /* [n_pods] read under KSH_CAND_POD_HAS_DELETION_COST */
+  const int32_t* pod_priority;                /* [n_pods] read under KSH_CAND_POD_HAS_PRIORITY */
+  const uint32_t* prov_consolidation_enabled; /* [n_provisioners] Spec.Consolidation != nil && *Enabled */
+  const int64_t* prov_ttl_seconds_until_expired; /* [n_provisioners] -1: nil */
+} ksh_candidate_inputs;
+typedef struct ksh_pdb_block {
+  uint32_t n_pdbs, n_strings, n_words;
+  const uint32_t* str_off;      /* [n_strings + 1] byte offsets into str_bytes */
+  const char* str_bytes;
+  const uint32_t* words;        /* [n_words] */
+  uint64_t str_bytes_len;       /* bytes behind str_bytes: str_off[n_strings] must not reach beyond */
+} ksh_pdb_block;
+typedef struct ksh_candidates_out {
+  uint32_t n_candidates, n_empty;
+  uint32_t* order; uint32_t* empty; uint32_t* why; int32_t* detail; uint32_t* n_node_pods; double* cost;      /* [node slots] each, the caller's */
+} ksh_candidates_out;
+int ksh_consolidation_candidates(void* parsed_snapshot, const int32_t* pod_node /* or NULL after ksh_env_apply* */, const uint32_t* deleting, uint32_t n_deleting,
+                                 const ksh_candidate_inputs* in, const ksh_pdb_block* pdbs /* or NULL */, int device, ksh_candidates_out* out, double* ms /* [4] or NULL */);
+
 /* ---- the snapshot kept current by EVENTS ("cached incremental SoA builder fed from state.Cluster") ----
  * Replaces, for the snapshot consolidation simulates over, what the reference does between two passes of the deprovisioner (deprovisioning/controller.go:64,
  * every 10 s): state.Cluster hears UpdateNode / DeleteNode / UpdatePod / DeletePod (pkg/controllers/state/cluster.go:151-200) and patches its nodes in place

@@ -421,6 +421,61 @@ int ks_consolidation_commands_dev(ks_dev_problem* const* ds, uint32_t n, const u
  * completion, [1] the read-back, milliseconds.  The inputs are validated once, before any device work. */
 int ks_consolidation_commands_host(ks_dev_problem* const* ds, uint32_t n, const uint64_t* ids, const ks_command_inputs* in, uint32_t words, uint64_t* out_rows, double* ms);
 
+/* ---- consolidation CANDIDATES, selected and ordered on the device (deprovisioning/helpers.go:124-165,275-287 GetPodEvictionCost / disruptionCost /
+ * calculateLifetimeRemaining, pdblimits.go:57-70 CanEvictPods, helpers.go:339-366 canBeTerminated / PodsPreventEviction, consolidation.go:83-104 the sort).
+ * Flat arrays in, flat arrays out; three kernels (per pod, per node, rank), no host fallback.
+ * Label selectors are flattened by the caller: it interns the label KEYS some PDB selector mentions (n_keys <= KS_CAND_MAX_KEYS) and, per key, the VALUES some
+ * selector mentions as bits 0 .. KS_CAND_MAX_VALUES - 1; bit KS_CAND_BIT_OTHER = the pod has the key with a value no selector mentions, KS_CAND_BIT_ABSENT = the
+ * pod lacks the key.  pod_val[k * n_pods + pod] is the pod's bit for key k (key-major: a wave reads it coalesced).  A PDB is a namespace id, disruptionsAllowed
+ * and a CSR of (key, u64 allowed-set mask); it matches a pod iff the namespace ids are equal and (mask >> pod_val[key][pod]) & 1 for every requirement.  Only a
+ * matching PDB with disruptionsAllowed == 0 blocks.
+ * Per node slot: node_why (a reason the caller already decided, 0 = still in the running; KS_CAND_WHY_PDB / _DO_NOT_EVICT are the kernel's own and refused as
+ * input), age in seconds, TTLSecondsUntilExpired (-1: none; 0 is refused -- the reference divides by zero there), and its pod slots in ASCENDING slot order
+ * (node_pods_off / node_pods).  The disruption cost is the sum of the pods' eviction costs taken sequentially in that order as float64 -- deletion costs are
+ * arbitrary doubles, so the sum depends on the order, and this is the canonical one -- times clamp(0, (ttl - age) / ttl, 1).  It is computed for nodes with
+ * node_why 0 or KS_CAND_WHY_DELETING_NODE (they are in candidateNodes' result) and is 0.0 for every other code.
+ * Out (caller-owned, [n_nodes] each): why (0 = candidate), detail (KS_CAND_WHY_PDB: the PDB's index -- first pod in slot order, lowest PDB index;
+ * KS_CAND_WHY_DO_NOT_EVICT: the pod slot; else -1), n_node_pods, cost; order[0 .. n_candidates) = the candidates by `cost <` (so -0.0 and +0.0 tie), ties by
+ * ascending node index (the stable sort over ascending index); empty[0 .. n_empty) = the candidates without pods, in the same order.
+ * KS_ERR_INVALID (nothing launched, nothing written): a null array, a pod_val above 63, a requirement key >= n_keys, offsets that do not ascend, a pod slot out of
+ * range / not ascending within its node / bound elsewhere according to pod_node, an unknown flag bit, a deletion cost or age that is not finite, a ttl of 0 or
+ * below -1, a node_why above KS_CAND_WHY_LEFT or one of the kernel's own.  KS_ERR_UNSUPPORTED: n_keys > KS_CAND_MAX_KEYS (both counts in the message).
+ * ms (may be NULL): [0] inputs up, [1] the three kernels, [2] read-back, milliseconds. */
+#define KS_CAND_MAX_KEYS 16
+#define KS_CAND_MAX_VALUES 62
+#define KS_CAND_BIT_OTHER 62
+#define KS_CAND_BIT_ABSENT 63
+#define KS_CAND_POD_DO_NOT_EVICT 1u
+#define KS_CAND_POD_HAS_DELETION_COST 2u
+#define KS_CAND_POD_HAS_PRIORITY 4u
+#define KS_CAND_WHY_DELETING_NODE 10   /* deletion timestamp set: in candidateNodes' result, filtered by canBeTerminated; its cost is still computed */
+#define KS_CAND_WHY_PDB 11
+#define KS_CAND_WHY_DO_NOT_EVICT 12
+#define KS_CAND_WHY_LEFT 13
+typedef struct ks_candidates_inputs {
+  uint32_t n_pods, n_nodes, n_pdbs, n_keys;
+  const int32_t* pod_node;            /* [n_pods] node slot, -1: unbound (ignored) */
+  const uint32_t* pod_ns;             /* [n_pods] namespace id */
+  const uint32_t* pod_flags;          /* [n_pods] KS_CAND_POD_* */
+  const double* pod_deletion_cost;    /* [n_pods] read under KS_CAND_POD_HAS_DELETION_COST */
+  const int32_t* pod_priority;        /* [n_pods] read under KS_CAND_POD_HAS_PRIORITY */
+  const uint8_t* pod_val;             /* [n_keys][n_pods] */
+  const uint32_t* pdb_ns;             /* [n_pdbs] */
+  const int32_t* pdb_allowed;         /* [n_pdbs] disruptionsAllowed */
+  const uint32_t* pdb_req_off;        /* [n_pdbs + 1] */
+  const uint32_t* pdb_req_key; const uint64_t* pdb_req_mask;
+  const uint32_t* node_why;           /* [n_nodes] */
+  const double* node_age_seconds;     /* [n_nodes] */
+  const int64_t* node_ttl_seconds;    /* [n_nodes] */
+  const uint32_t* node_pods_off;      /* [n_nodes + 1] */
+  const uint32_t* node_pods;
+} ks_candidates_inputs;
+typedef struct ks_candidates_outputs {
+  uint32_t n_candidates, n_empty;
+  uint32_t* order; uint32_t* empty; uint32_t* why; int32_t* detail; uint32_t* n_node_pods; double* cost;
+} ks_candidates_outputs;
+int ks_consolidation_candidates_host(const ks_candidates_inputs* in, ks_candidates_outputs* out, int device, double* ms /* [3] or NULL */);
+
 /* Launch-time instance-type pick of the reference's in-memory provider (cloudprovider/fake/cloudprovider.go:79-84: order the machine's
  * InstanceTypeOptions by `Offerings.Available().Requirements(reqs).Cheapest().Price`, types.go:126-145, and take the first): for problem i,
  * of new node node[i]'s InstanceTypeOptions (as left by the last ks_solve*_dev) the type whose cheapest available offering under the node's zone /

@@ -529,3 +529,50 @@ def single_node_consolidation_option_dev(snapshot: Snapshot, candidates: Sequenc
         return _command_of_row(snapshot, parsed, row, _words(snapshot), [candidates[int(row[S.KS_CMD_ID])]])
     finally:
         parsed.close()
+
+
+@dataclass
+class CandidateInfo:
+    """What candidate selection reads beside the snapshot's objects (kshost.h `ksh_candidate_inputs`), per node and per bound pod of a `Snapshot`."""
+    node_age_seconds: List[float]
+    nominated: Sequence[int] = ()                       # node indices
+    do_not_consolidate: Dict[int, str] = field(default_factory=dict)      # node index -> the annotation's value
+    deletion_timestamp: Sequence[int] = ()              # node indices
+    do_not_evict: Sequence[str] = ()                    # pod uids
+    deletion_cost: Dict[str, float] = field(default_factory=dict)         # pod uid -> the parsed annotation
+    priority: Dict[str, int] = field(default_factory=dict)                # pod uid -> Spec.Priority
+    consolidation_enabled: bool = True
+    ttl_seconds_until_expired: Optional[int] = None
+    pdbs: Sequence = ()                                 # model.PodDisruptionBudget
+
+
+def consolidation_candidates_dev(snapshot: Snapshot, info: CandidateInfo, device: int = 0, timings: Optional[dict] = None) -> dict:
+    """candidateNodes + ShouldDeprovision + sortAndFilterCandidates through `ksh_consolidation_candidates`: {"order": the candidates' node indices by disruption
+    cost -- what `first_n_node_consolidation_option_dev` / `single_node_consolidation_option_dev` take as they are --, "empty": the candidates without pods in the same
+    order, "why" / "detail" / "cost" / "n_node_pods" per node (kshost.h lists the reason codes)}.  Pending pods and their carrier node are not candidates' business:
+    only the snapshot's own nodes are reported."""
+    from . import scheduler as S
+    parsed, pod_node, leaving = _command_snapshot(snapshot)
+    try:
+        pods = [p for b in snapshot.bound for p in b] + list(snapshot.pending)
+        nn = len(snapshot.nodes) + (1 if snapshot.pending else 0)
+        nf = [0] * nn
+        for i in info.nominated:
+            nf[i] |= S.KSH_CAND_NODE_NOMINATED
+        for i, v in info.do_not_consolidate.items():
+            nf[i] |= S.KSH_CAND_NODE_DO_NOT_CONSOLIDATE | (S.KSH_CAND_NODE_DO_NOT_CONSOLIDATE_TRUE if v == "true" else 0)
+        for i in info.deletion_timestamp:
+            nf[i] |= S.KSH_CAND_NODE_DELETION_TIMESTAMP
+        dne = set(info.do_not_evict)
+        pf = [(S.KSH_CAND_POD_DO_NOT_EVICT if p.uid in dne else 0) | (S.KSH_CAND_POD_HAS_DELETION_COST if p.uid in info.deletion_cost else 0) |
+              (S.KSH_CAND_POD_HAS_PRIORITY if p.uid in info.priority else 0) for p in pods]
+        age = list(info.node_age_seconds) + [0.0] * (nn - len(info.node_age_seconds))
+        got = S.consolidation_candidates(parsed, pod_node, nf, age, pf, [float(info.deletion_cost.get(p.uid, 0.0)) for p in pods], [int(info.priority.get(p.uid, 0)) for p in pods],
+                                         [info.consolidation_enabled], [info.ttl_seconds_until_expired], pdbs=info.pdbs, deleting=[int(j) for j in snapshot.deleting], device=device)
+        if timings is not None:
+            timings.update(got["ms"])
+        n = len(snapshot.nodes)
+        return {"order": got["order"], "empty": got["empty"], "why": [int(x) for x in got["why"][:n]], "detail": [int(x) for x in got["detail"][:n]],
+                "cost": [float(x) for x in got["cost"][:n]], "n_node_pods": [int(x) for x in got["n_node_pods"][:n]]}
+    finally:
+        parsed.close()

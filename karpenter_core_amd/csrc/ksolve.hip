@@ -29,6 +29,7 @@
 // device is present every entry point returns KS_ERR_DEVICE.
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <algorithm>
@@ -3931,6 +3932,198 @@ extern "C" int ks_consolidation_commands_host(ks_dev_problem* const* ds, uint32_
   const auto t1 = std::chrono::steady_clock::now();
   HIPCHK(hipMemcpy(out_rows, buf.p, bytes, hipMemcpyDeviceToHost));
   if (ms) { ms[0] = std::chrono::duration<double, std::milli>(t1 - t0).count(); ms[1] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count(); }
+  return KS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Consolidation candidates (ksolve.h ks_consolidation_candidates_host): which nodes sortAndFilterCandidates keeps, and in what order.
+//   ks_cand_pods   one lane per pod slot: GetPodEvictionCost (helpers.go:124-146), and the lowest-index PDB with disruptionsAllowed == 0 that matches the pod
+//                  (pdblimits.go:57-70).  The PDB table goes through LDS in tiles -- every lane of a wave reads the same entry, a broadcast --; the pod's own
+//                  value bits sit in two registers (eight 8-bit fields each).
+//   ks_cand_nodes  one lane per node slot: the pods' costs summed SEQUENTIALLY in ascending slot order (disruptionCost, :159-165: float64 addition is not
+//                  associative, the slot order is the canonical one), times the lifetime remaining (:275-287); the first pod a PDB blocks and that PDB; the first
+//                  do-not-evict pod (:354-366); the final reason.
+//   ks_cand_order  a counting rank over LDS tiles: rank = candidates with a smaller cost + candidates with an equal cost and a smaller index, i.e. the stable
+//                  sort of consolidation.go:100-102's comparator over ascending index.  Deterministic: no atomics decide a position.
+// No product here may be fused into an addition: the pragma below keeps the one multiply and the sums apart whatever the compiler's default is.
+// ------------------------------------------------------------------------------------------------
+#define KS_CAND_BLOCK 256u
+#define KS_CAND_PDB_TILE 128u
+#define KS_CAND_REQ_TILE 1024u
+struct CandDev {
+  u32 n_pods, n_nodes, n_pdbs, n_keys;
+  const u32* pod_ns; const u32* pod_flags; const double* pod_dcost; const i32* pod_prio; const u8* pod_val;
+  const u32* pdb_ns; const i32* pdb_allowed; const u32* pdb_req_off; const u32* pdb_req_key; const u64* pdb_req_mask;
+  const u32* node_why; const double* node_age; const i64* node_ttl; const u32* node_pods_off; const u32* node_pods;
+  double* pod_cost; i32* pod_block; u32* node_fl;      // scratch: per pod its eviction cost and blocking PDB (-1: none); per node bit 0 candidate, bit 1 candidate without pods
+  u32* out_why; i32* out_detail; u32* out_npods; double* out_cost; u32* out_order; u32* out_empty; u32* counts;
+};
+__device__ __forceinline__ double cand_clamp(double lo, double v, double hi) { if (v < lo) return lo; if (v > hi) return hi; return v; }      // helpers.go:317-325: two comparisons
+__device__ __forceinline__ double cand_eviction_cost(u32 flags, double dcost, i32 prio) {
+#pragma clang fp contract(off)
+  double cost = 1.0;
+  if (flags & KS_CAND_POD_HAS_DELETION_COST) cost += dcost / 134217728.0;      // math.Pow(2, 27): exact
+  if (flags & KS_CAND_POD_HAS_PRIORITY) cost += (double)prio / 33554432.0;     // math.Pow(2, 25): exact
+  return cand_clamp(-10.0, cost, 10.0);
+}
+__global__ __launch_bounds__(256) void ks_cand_pods(const CandDev c) {
+  __shared__ u32 s_ns[KS_CAND_PDB_TILE]; __shared__ i32 s_allowed[KS_CAND_PDB_TILE]; __shared__ u32 s_off[KS_CAND_PDB_TILE + 1];
+  __shared__ u32 s_key[KS_CAND_REQ_TILE]; __shared__ u64 s_mask[KS_CAND_REQ_TILE];
+  const u32 tid = threadIdx.x, pod = blockIdx.x * KS_CAND_BLOCK + tid; const bool live = pod < c.n_pods;
+  u32 ns = 0; u64 vlo = 0, vhi = 0;
+  if (live) {
+    ns = c.pod_ns[pod];
+    for (u32 k = 0; k < c.n_keys; ++k) { const u64 v = (u64)c.pod_val[(size_t)k * c.n_pods + pod] << ((k & 7u) * 8u); if (k < 8u) vlo |= v; else vhi |= v; }
+  }
+  i32 blk = -1;
+  for (u32 base = 0; base < c.n_pdbs; base += KS_CAND_PDB_TILE) {
+    const u32 cnt = min(KS_CAND_PDB_TILE, c.n_pdbs - base);
+    const u32 r0 = c.pdb_req_off[base], nreq = min(c.pdb_req_off[base + cnt] - r0, KS_CAND_REQ_TILE);      // requirements beyond the LDS tile are read from memory below
+    __syncthreads();      // (the tile before has been read by every lane)
+    for (u32 i = tid; i < cnt; i += KS_CAND_BLOCK) { s_ns[i] = c.pdb_ns[base + i]; s_allowed[i] = c.pdb_allowed[base + i]; }
+    for (u32 i = tid; i <= cnt; i += KS_CAND_BLOCK) s_off[i] = c.pdb_req_off[base + i];
+    for (u32 i = tid; i < nreq; i += KS_CAND_BLOCK) { s_key[i] = c.pdb_req_key[r0 + i]; s_mask[i] = c.pdb_req_mask[r0 + i]; }
+    __syncthreads();
+    for (u32 j = 0; j < cnt; ++j) {
+      if (s_allowed[j] != 0) continue;      // a PDB with disruptions allowed never blocks (pdblimits.go:62)
+      bool m = s_ns[j] == ns;
+      for (u32 r = s_off[j]; r < s_off[j + 1]; ++r) {
+        const u32 q = r - r0; u32 key; u64 mask;
+        if (q < KS_CAND_REQ_TILE) { key = s_key[q]; mask = s_mask[q]; } else { key = c.pdb_req_key[r]; mask = c.pdb_req_mask[r]; }
+        const u32 v = (u32)((key < 8u ? vlo : vhi) >> ((key & 7u) * 8u)) & 63u;
+        m = m && ((mask >> v) & 1ull);
+      }
+      if (m && blk < 0) blk = (i32)(base + j);
+    }
+  }
+  if (live) { c.pod_cost[pod] = cand_eviction_cost(c.pod_flags[pod], c.pod_dcost[pod], c.pod_prio[pod]); c.pod_block[pod] = blk; }
+}
+__global__ __launch_bounds__(256) void ks_cand_nodes(const CandDev c) {
+#pragma clang fp contract(off)
+  const u32 nd = blockIdx.x * KS_CAND_BLOCK + threadIdx.x; if (nd >= c.n_nodes) return;
+  u32 why = c.node_why[nd]; const u32 lo = c.node_pods_off[nd], hi = c.node_pods_off[nd + 1];
+  double cost = 0.0; i32 blocked_by = -1, dne = -1;
+  if (why == 0 || why == KS_CAND_WHY_DELETING_NODE) {      // the node is in candidateNodes' result: it carries a disruption cost
+    for (u32 i = lo; i < hi; ++i) {
+      const u32 p = c.node_pods[i];
+      cost += c.pod_cost[p];
+      if (blocked_by < 0 && c.pod_block[p] >= 0) blocked_by = c.pod_block[p];
+      if (dne < 0 && (c.pod_flags[p] & KS_CAND_POD_DO_NOT_EVICT)) dne = (i32)p;
+    }
+    const i64 ttl = c.node_ttl[nd];
+    if (ttl >= 0) {      // calculateLifetimeRemaining
+      const double total = (double)ttl, left = total - c.node_age[nd];
+      const double remaining = cand_clamp(0.0, left / total, 1.0);
+      cost = cost * remaining;
+    }
+  }
+  i32 detail = -1;
+  if (why == 0) {      // canBeTerminated: the PDBs first, then do-not-evict
+    if (blocked_by >= 0) { why = KS_CAND_WHY_PDB; detail = blocked_by; }
+    else if (dne >= 0) { why = KS_CAND_WHY_DO_NOT_EVICT; detail = dne; }
+  }
+  const u32 fl = why == 0 ? (1u | (hi == lo ? 2u : 0u)) : 0u;
+  c.out_why[nd] = why; c.out_detail[nd] = detail; c.out_npods[nd] = hi - lo; c.out_cost[nd] = cost; c.node_fl[nd] = fl;
+  if (fl & 1u) atomicAdd(&c.counts[0], 1u);
+  if (fl & 2u) atomicAdd(&c.counts[1], 1u);
+}
+__global__ __launch_bounds__(256) void ks_cand_order(const CandDev c) {
+  __shared__ double s_cost[KS_CAND_BLOCK]; __shared__ u32 s_fl[KS_CAND_BLOCK];
+  const u32 tid = threadIdx.x, i = blockIdx.x * KS_CAND_BLOCK + tid; const bool live = i < c.n_nodes;
+  const double ci = live ? c.out_cost[i] : 0.0; const u32 fi = live ? c.node_fl[i] : 0u;
+  u32 rank = 0, erank = 0;
+  for (u32 base = 0; base < c.n_nodes; base += KS_CAND_BLOCK) {
+    const u32 cnt = min(KS_CAND_BLOCK, c.n_nodes - base);
+    __syncthreads();
+    if (tid < cnt) { s_cost[tid] = c.out_cost[base + tid]; s_fl[tid] = c.node_fl[base + tid]; }
+    __syncthreads();
+    for (u32 t = 0; t < cnt; ++t) {
+      const double cj = s_cost[t]; const u32 fj = s_fl[t];
+      const bool before = (cj < ci) || (!(ci < cj) && base + t < i);      // sort.Slice's less, made stable over ascending index
+      rank += (before && (fj & 1u)) ? 1u : 0u; erank += (before && (fj & 2u)) ? 1u : 0u;
+    }
+  }
+  if (fi & 1u) c.out_order[rank] = i;
+  if (fi & 2u) c.out_empty[erank] = i;
+}
+
+extern "C" int ks_consolidation_candidates_host(const ks_candidates_inputs* in, ks_candidates_outputs* out, int device, double* ms) {
+  if (ms) ms[0] = ms[1] = ms[2] = 0.0;
+  if (!in || !out) return fail(KS_ERR_INVALID, "null argument");
+  const u32 NP = in->n_pods, NN = in->n_nodes, NB = in->n_pdbs, NK = in->n_keys;
+  if (NK > KS_CAND_MAX_KEYS) return fail(KS_ERR_UNSUPPORTED, "consolidation candidates: " + std::to_string(NK) + " selector keys, " + std::to_string(KS_CAND_MAX_KEYS) + " supported");
+  if ((NP && (!in->pod_node || !in->pod_ns || !in->pod_flags || !in->pod_deletion_cost || !in->pod_priority || (NK && !in->pod_val))) || !in->pdb_req_off ||
+      (NB && (!in->pdb_ns || !in->pdb_allowed)) || !in->node_pods_off || (NN && (!in->node_why || !in->node_age_seconds || !in->node_ttl_seconds)) ||
+      (NN && (!out->order || !out->empty || !out->why || !out->detail || !out->n_node_pods || !out->cost))) return fail(KS_ERR_INVALID, "null argument");
+  // every refusal before any device work: the kernels index with these numbers
+  if (in->pdb_req_off[0] != 0 || in->node_pods_off[0] != 0) return fail(KS_ERR_INVALID, "consolidation candidates: offsets must start at 0");
+  for (u32 b = 0; b < NB; ++b) if (in->pdb_req_off[b + 1] < in->pdb_req_off[b]) return fail(KS_ERR_INVALID, "consolidation candidates: PDB requirement offsets not ascending");
+  const u32 NR = in->pdb_req_off[NB];
+  if (NR && (!in->pdb_req_key || !in->pdb_req_mask)) return fail(KS_ERR_INVALID, "null argument");
+  for (u32 r = 0; r < NR; ++r) if (in->pdb_req_key[r] >= NK) return fail(KS_ERR_INVALID, "consolidation candidates: requirement key out of range");
+  for (size_t i = 0; i < (size_t)NK * NP; ++i) if (in->pod_val[i] > 63) return fail(KS_ERR_INVALID, "consolidation candidates: pod value bit above 63");
+  for (u32 p = 0; p < NP; ++p) {
+    if (in->pod_flags[p] & ~7u) return fail(KS_ERR_INVALID, "consolidation candidates: unknown pod flag bit");
+    if ((in->pod_flags[p] & KS_CAND_POD_HAS_DELETION_COST) && !std::isfinite(in->pod_deletion_cost[p])) return fail(KS_ERR_INVALID, "consolidation candidates: pod " + std::to_string(p) + ": deletion cost is not finite");
+    if (in->pod_node[p] >= (i32)NN || in->pod_node[p] < -1) return fail(KS_ERR_INVALID, "consolidation candidates: pod_node out of range");
+  }
+  for (u32 n = 0; n < NN; ++n) {
+    if (in->node_pods_off[n + 1] < in->node_pods_off[n]) return fail(KS_ERR_INVALID, "consolidation candidates: node pod offsets not ascending");
+    if (in->node_why[n] > KS_CAND_WHY_LEFT || in->node_why[n] == KS_CAND_WHY_PDB || in->node_why[n] == KS_CAND_WHY_DO_NOT_EVICT) return fail(KS_ERR_INVALID, "consolidation candidates: node " + std::to_string(n) + ": reason code not the caller's to give");
+    if (!std::isfinite(in->node_age_seconds[n])) return fail(KS_ERR_INVALID, "consolidation candidates: node " + std::to_string(n) + ": age is not finite");
+    if (in->node_ttl_seconds[n] == 0 || in->node_ttl_seconds[n] < -1) return fail(KS_ERR_INVALID, "consolidation candidates: node " + std::to_string(n) + ": ttl must be positive or -1 (the reference divides by a ttl of 0)");
+  }
+  const u32 NL = in->node_pods_off[NN];
+  if (NL > NP || (NL && !in->node_pods)) return fail(KS_ERR_INVALID, "consolidation candidates: more listed pods than pod slots");
+  for (u32 n = 0; n < NN; ++n) for (u32 i = in->node_pods_off[n]; i < in->node_pods_off[n + 1]; ++i) {
+    const u32 p = in->node_pods[i];
+    if (p >= NP || (i > in->node_pods_off[n] && p <= in->node_pods[i - 1]) || in->pod_node[p] != (i32)n) return fail(KS_ERR_INVALID, "consolidation candidates: node " + std::to_string(n) + ": pod slots must ascend and be bound to the node");
+  }
+  out->n_candidates = out->n_empty = 0;
+  if (!NN) return KS_OK;
+  if (ks_device_count() <= 0) return fail(KS_ERR_DEVICE, "no gfx950 (MI355X) device visible; libksolve has no CPU path");
+  HIPCHK(hipSetDevice(device));
+  // one host block, one device block: [inputs | outputs | scratch], every segment 16-byte aligned
+  size_t bytes = 0; auto seg = [&](size_t n) { const size_t at = bytes; bytes = (bytes + (n ? n : 1) + 15) & ~(size_t)15; return at; };
+  const size_t o_ns = seg((size_t)NP * 4), o_fl = seg((size_t)NP * 4), o_dc = seg((size_t)NP * 8), o_pr = seg((size_t)NP * 4), o_val = seg((size_t)NK * NP);
+  const size_t o_bns = seg((size_t)NB * 4), o_ball = seg((size_t)NB * 4), o_boff = seg(((size_t)NB + 1) * 4), o_bkey = seg((size_t)NR * 4), o_bmask = seg((size_t)NR * 8);
+  const size_t o_why = seg((size_t)NN * 4), o_age = seg((size_t)NN * 8), o_ttl = seg((size_t)NN * 8), o_noff = seg(((size_t)NN + 1) * 4), o_npods = seg((size_t)NL * 4), o_cnt = seg(16);
+  const size_t up = bytes;
+  const size_t r_why = seg((size_t)NN * 4), r_det = seg((size_t)NN * 4), r_np = seg((size_t)NN * 4), r_cost = seg((size_t)NN * 8), r_ord = seg((size_t)NN * 4), r_emp = seg((size_t)NN * 4);
+  const size_t down = bytes;
+  const size_t s_cost = seg((size_t)NP * 8), s_blk = seg((size_t)NP * 4), s_nfl = seg((size_t)NN * 4);
+  std::vector<u64> host(down / 8 + 1, 0); u8* hb = (u8*)host.data();
+  auto put = [&](size_t at, const void* src, size_t n) { if (n) memcpy(hb + at, src, n); };
+  put(o_ns, in->pod_ns, (size_t)NP * 4); put(o_fl, in->pod_flags, (size_t)NP * 4); put(o_dc, in->pod_deletion_cost, (size_t)NP * 8); put(o_pr, in->pod_priority, (size_t)NP * 4); put(o_val, in->pod_val, (size_t)NK * NP);
+  put(o_bns, in->pdb_ns, (size_t)NB * 4); put(o_ball, in->pdb_allowed, (size_t)NB * 4); put(o_boff, in->pdb_req_off, ((size_t)NB + 1) * 4); put(o_bkey, in->pdb_req_key, (size_t)NR * 4); put(o_bmask, in->pdb_req_mask, (size_t)NR * 8);
+  put(o_why, in->node_why, (size_t)NN * 4); put(o_age, in->node_age_seconds, (size_t)NN * 8); put(o_ttl, in->node_ttl_seconds, (size_t)NN * 8); put(o_noff, in->node_pods_off, ((size_t)NN + 1) * 4); put(o_npods, in->node_pods, (size_t)NL * 4);
+  TmpDev buf(device); TRY(buf.alloc(bytes)); u8* db = buf.as<u8>();
+  hipStream_t stream = nullptr; TRY(pool().get_stream(device, &stream));
+  struct StreamBack { int device; hipStream_t s; ~StreamBack() { pool().put_stream(device, s); } } back{device, stream};
+  const auto t0 = std::chrono::steady_clock::now();
+  HIPCHK(hipMemcpy(db, hb, up, hipMemcpyHostToDevice));
+  const auto t1 = std::chrono::steady_clock::now();
+  CandDev c{};
+  c.n_pods = NP; c.n_nodes = NN; c.n_pdbs = NB; c.n_keys = NK;
+  c.pod_ns = (const u32*)(db + o_ns); c.pod_flags = (const u32*)(db + o_fl); c.pod_dcost = (const double*)(db + o_dc); c.pod_prio = (const i32*)(db + o_pr); c.pod_val = db + o_val;
+  c.pdb_ns = (const u32*)(db + o_bns); c.pdb_allowed = (const i32*)(db + o_ball); c.pdb_req_off = (const u32*)(db + o_boff); c.pdb_req_key = (const u32*)(db + o_bkey); c.pdb_req_mask = (const u64*)(db + o_bmask);
+  c.node_why = (const u32*)(db + o_why); c.node_age = (const double*)(db + o_age); c.node_ttl = (const i64*)(db + o_ttl); c.node_pods_off = (const u32*)(db + o_noff); c.node_pods = (const u32*)(db + o_npods);
+  c.pod_cost = (double*)(db + s_cost); c.pod_block = (i32*)(db + s_blk); c.node_fl = (u32*)(db + s_nfl);
+  c.out_why = (u32*)(db + r_why); c.out_detail = (i32*)(db + r_det); c.out_npods = (u32*)(db + r_np); c.out_cost = (double*)(db + r_cost); c.out_order = (u32*)(db + r_ord); c.out_empty = (u32*)(db + r_emp);
+  c.counts = (u32*)(db + o_cnt);      // (uploaded as zeros)
+  const u32 gn = (NN + KS_CAND_BLOCK - 1) / KS_CAND_BLOCK;
+  if (NP) hipLaunchKernelGGL(ks_cand_pods, dim3((NP + KS_CAND_BLOCK - 1) / KS_CAND_BLOCK), dim3(KS_CAND_BLOCK), 0, stream, c);
+  hipLaunchKernelGGL(ks_cand_nodes, dim3(gn), dim3(KS_CAND_BLOCK), 0, stream, c);
+  hipLaunchKernelGGL(ks_cand_order, dim3(gn), dim3(KS_CAND_BLOCK), 0, stream, c);
+  HIPCHK(hipStreamSynchronize(stream)); HIPCHK(hipGetLastError());
+  const auto t2 = std::chrono::steady_clock::now();
+  HIPCHK(hipMemcpy(hb + o_cnt, db + o_cnt, down - o_cnt, hipMemcpyDeviceToHost));
+  const u32* cnt = (const u32*)(hb + o_cnt);
+  if (cnt[0] > NN || cnt[1] > cnt[0]) return fail(KS_ERR_INTERNAL, "consolidation candidates: counts out of range");
+  memcpy(out->why, hb + r_why, (size_t)NN * 4); memcpy(out->detail, hb + r_det, (size_t)NN * 4); memcpy(out->n_node_pods, hb + r_np, (size_t)NN * 4); memcpy(out->cost, hb + r_cost, (size_t)NN * 8);
+  memcpy(out->order, hb + r_ord, (size_t)cnt[0] * 4); memcpy(out->empty, hb + r_emp, (size_t)cnt[1] * 4);
+  out->n_candidates = cnt[0]; out->n_empty = cnt[1];
+  if (ms) { ms[0] = std::chrono::duration<double, std::milli>(t1 - t0).count(); ms[1] = std::chrono::duration<double, std::milli>(t2 - t1).count(); ms[2] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t2).count(); }
   return KS_OK;
 }
 

@@ -6,6 +6,7 @@
 #include <atomic>
 #include <mutex>
 #include <chrono>
+#include <cmath>
 #include <cstring>
 #include <string>
 #include <thread>
@@ -85,6 +86,7 @@ struct Parsed {
   std::mutex mu; std::shared_ptr<const ksh::SnapshotBase> sb; std::vector<int32_t> sb_pod_node; uint32_t sb_flags = 0;
   ksh::EnvCache env;      // the flattening of everything but the pods, reused by the next batch with the same universe signature
   std::shared_ptr<const void> cmd_nodes;      // what the consolidation commands read of the nodes' labels (CmdSnapshot below), made once; ksh_env_apply* drops it
+  std::shared_ptr<const void> cand_nodes;     // what candidate selection reads of them (CandSnapshot below), likewise
   // ksh_env_apply (round 6): once events were applied the library holds the bindings itself -- bind[i] = the node pod i is bound to, -1 for a pod that was unbound
   // (it stays in place: nothing that points into the problem may move) -- and the names of what is alive
   bool bind_set = false, had_cluster_pods = false; std::vector<int32_t> bind; std::unordered_map<std::string, uint32_t> live_node, live_pod; uint64_t tombstones = 0; uint32_t applied = 0;
@@ -360,7 +362,7 @@ static int apply_events(Parsed* P, const int32_t* pod_node, std::vector<ksp::Del
       }
       ++done;
     }
-    P->applied += done; P->cmd_nodes.reset(); { std::lock_guard<std::mutex> ge(P->env.mu); P->env.base.reset(); }      // (a Solve over these objects flattens its environment again)
+    P->applied += done; P->cmd_nodes.reset(); P->cand_nodes.reset(); { std::lock_guard<std::mutex> ge(P->env.mu); P->env.base.reset(); }      // (a Solve over these objects flattens its environment again)
     // the snapshot's flattening follows, continued from the one before when there is one
     bool continued = false;
     if (P->sb) {
@@ -898,6 +900,154 @@ int ksh_single_node_option(void* parsed, uint32_t flags, const uint32_t* candida
     }
     return KS_OK;
   } catch (const ksh::Unsupported& e) { return set_err(KS_ERR_UNSUPPORTED, e.what()); } catch (const std::exception& e) { return set_err(KS_ERR_INVALID, e.what()); }
+}
+// ---- consolidation candidates (kshost.h): candidateNodes + ShouldDeprovision + sortAndFilterCandidates over a snapshot ----
+}  // extern "C"
+namespace {
+// What candidateNodes reads of the nodes' labels, once per snapshot: the reason a node is skipped for (2-6, 13; 0: none) and its provisioner
+struct CandSnapshot {
+  std::vector<uint8_t> why; std::vector<int32_t> prov;
+  explicit CandSnapshot(const ksp::Problem& pr) : why(pr.nodes.size(), 0), prov(pr.nodes.size(), -1) {
+    std::unordered_map<std::string, int32_t> pindex; for (size_t m = 0; m < pr.provisioners.size(); ++m) pindex.emplace(pr.provisioners[m].name, (int32_t)m);
+    std::vector<std::unordered_map<std::string, int32_t>> types(pr.provisioners.size());      // buildProvisionerMap: provName -> instanceName -> instance type
+    for (size_t m = 0; m < pr.provisioners.size(); ++m) for (int32_t t : pr.provisioners[m].instance_types) types[m].emplace(pr.instance_types[t].name, t);
+    for (size_t i = 0; i < pr.nodes.size(); ++i) {
+      const ksp::StateNode& nd = pr.nodes[i];
+      auto lab = [&](const char* k) -> const std::string* { auto it = nd.labels.find(k); return it == nd.labels.end() ? nullptr : &it->second; };
+      static const std::string none;
+      if (!nd.in_state) { why[i] = KS_CAND_WHY_LEFT; continue; }
+      const std::string* pn = lab(ksp::kProvisionerName); auto pm = pn ? pindex.find(*pn) : pindex.end();
+      if (pm == pindex.end()) { why[i] = 2; continue; }                                         // helpers.go:181-192
+      prov[i] = pm->second;
+      const std::string* it = lab(ksp::kInstanceType);
+      if (!types[pm->second].count(it ? *it : none)) { why[i] = 3; continue; }                  // :194-198
+      if (!lab(ksp::kCapacityType)) { why[i] = 4; continue; }                                   // :201
+      if (!lab(ksp::kZone)) { why[i] = 5; continue; }                                           // :205
+      const std::string* init = lab("karpenter.sh/initialized");
+      if (!(init && *init == "true")) { why[i] = 6; continue; }                                 // :211, state/node.go:80-82
+    }
+  }
+};
+int candidates_over(Parsed* P, const int32_t* pod_node, const uint32_t* deleting, uint32_t n_deleting, const ksh_candidate_inputs* in, const ksh_pdb_block* pb, int device, ksh_candidates_out* out, double* ms) {
+  using clk = std::chrono::steady_clock; const auto t_call = clk::now();
+  if (ms) ms[0] = ms[1] = ms[2] = ms[3] = 0.0;
+  if (!P || !in || !out || (n_deleting && !deleting)) return set_err(KS_ERR_INVALID, "null argument");
+  // the PDBs first, completely: a malformed block changes and launches nothing
+  std::vector<ksp::Pdb> pdbs;
+  if (pb) {
+    if (!pb->str_off || (!pb->words && pb->n_words) || (!pb->str_bytes && pb->n_strings)) return set_err(KS_ERR_INVALID, "null argument");
+    for (uint32_t i = 0; i < pb->n_strings; ++i) if (pb->str_off[i + 1] < pb->str_off[i]) return set_err(KS_ERR_INVALID, "pdb block: string offsets not ascending");
+    if (pb->n_strings && pb->str_off[pb->n_strings] > pb->str_bytes_len) return set_err(KS_ERR_INVALID, "pdb block: string offsets reach beyond str_bytes_len");
+    ksh_pod_block strings{}; strings.n_strings = pb->n_strings; strings.str_off = pb->str_off; strings.str_bytes = pb->str_bytes; strings.str_bytes_len = pb->str_bytes_len;
+    pdbs = ksp::PdbReader(strings, pb->words, pb->words + pb->n_words).read_pdbs(pb->n_pdbs);
+  }
+  std::shared_ptr<const void> held; std::vector<int32_t> bind;
+  const ksp::Problem& pr = *P->pr;
+  { std::lock_guard<std::mutex> g(P->mu);
+    const int32_t* pn = bindings_of(P, pod_node); if (!pn && !pr.pods.empty()) return set_err(KS_ERR_INVALID, "no bindings (pod_node)");
+    bind.assign(pn, pn + pr.pods.size());
+    if (!P->cand_nodes) P->cand_nodes = std::make_shared<const CandSnapshot>(pr);
+    held = P->cand_nodes; }
+  const CandSnapshot& cs = *static_cast<const CandSnapshot*>(held.get());
+  const uint32_t NN = (uint32_t)pr.nodes.size(), NP = (uint32_t)pr.pods.size(), NM = (uint32_t)pr.provisioners.size();
+  if (in->n_nodes != NN || in->n_pods != NP || in->n_provisioners != NM)
+    return set_err(KS_ERR_INVALID, "consolidation candidates: the input arrays are for " + std::to_string(in->n_nodes) + " nodes / " + std::to_string(in->n_pods) + " pods / " + std::to_string(in->n_provisioners) +
+                                   " provisioners, the snapshot has " + std::to_string(NN) + " / " + std::to_string(NP) + " / " + std::to_string(NM));
+  if ((NN && (!in->node_flags || !in->node_age_seconds || !out->order || !out->empty || !out->why || !out->detail || !out->n_node_pods || !out->cost)) ||
+      (NP && (!in->pod_flags || !in->pod_deletion_cost || !in->pod_priority)) || (NM && (!in->prov_consolidation_enabled || !in->prov_ttl_seconds_until_expired))) return set_err(KS_ERR_INVALID, "null argument");
+  for (uint32_t i = 0; i < n_deleting; ++i) if (deleting[i] >= NN) return set_err(KS_ERR_INVALID, "deleting node out of range");
+  for (uint32_t p = 0; p < NP; ++p) if (bind[p] >= (int32_t)NN || bind[p] < -1) return set_err(KS_ERR_INVALID, "pod_node out of range");
+  for (uint32_t n = 0; n < NN; ++n) {
+    const uint32_t f = in->node_flags[n];
+    if ((f & ~15u) || ((f & KSH_CAND_NODE_DO_NOT_CONSOLIDATE_TRUE) && !(f & KSH_CAND_NODE_DO_NOT_CONSOLIDATE))) return set_err(KS_ERR_INVALID, "consolidation candidates: node " + std::to_string(n) + ": unknown flag bit");
+    if (!std::isfinite(in->node_age_seconds[n])) return set_err(KS_ERR_INVALID, "consolidation candidates: node " + std::to_string(n) + ": age is not finite");
+  }
+  for (uint32_t p = 0; p < NP; ++p) {
+    if (in->pod_flags[p] & ~7u) return set_err(KS_ERR_INVALID, "consolidation candidates: pod " + std::to_string(p) + ": unknown flag bit");
+    if ((in->pod_flags[p] & KSH_CAND_POD_HAS_DELETION_COST) && !std::isfinite(in->pod_deletion_cost[p])) return set_err(KS_ERR_INVALID, "consolidation candidates: pod " + std::to_string(p) + ": deletion cost is not finite");
+  }
+  for (uint32_t m = 0; m < NM; ++m) {
+    const int64_t ttl = in->prov_ttl_seconds_until_expired[m];
+    if (ttl == 0 || ttl < -1) return set_err(KS_ERR_INVALID, "consolidation candidates: provisioner " + pr.provisioners[m].name + ": ttlSecondsUntilExpired " + std::to_string(ttl) + " (the reference divides by a ttl of 0; -1 means none)");
+  }
+  // selectors -> (key, allowed-set mask): the keys and values some selector mentions
+  std::vector<std::string> keys; std::unordered_map<std::string, uint32_t> kindex; std::vector<std::unordered_map<std::string, uint32_t>> vindex;
+  auto key_of = [&](const std::string& k) { auto it = kindex.find(k); if (it != kindex.end()) return it->second; const uint32_t id = (uint32_t)keys.size(); kindex.emplace(k, id); keys.push_back(k); vindex.emplace_back(); return id; };
+  auto bit_of = [&](uint32_t k, const std::string& v) { auto& m = vindex[k]; auto it = m.find(v); if (it != m.end()) return it->second; const uint32_t id = (uint32_t)m.size(); m.emplace(v, id); return id; };
+  for (const ksp::Pdb& b : pdbs) if (!b.selector.nil) {
+    for (auto& kv : b.selector.match_labels) bit_of(key_of(kv.first), kv.second);
+    for (auto& x : b.selector.match_exprs) { const uint32_t k = key_of(x.key); for (auto& v : x.values) bit_of(k, v); }
+  }
+  if (keys.size() > KS_CAND_MAX_KEYS) return set_err(KS_ERR_UNSUPPORTED, "consolidation candidates: the PDB selectors mention " + std::to_string(keys.size()) + " label keys, " + std::to_string(KS_CAND_MAX_KEYS) + " are supported");
+  for (size_t k = 0; k < keys.size(); ++k) if (vindex[k].size() > KS_CAND_MAX_VALUES)
+    return set_err(KS_ERR_UNSUPPORTED, "consolidation candidates: the PDB selectors mention " + std::to_string(vindex[k].size()) + " values of label key " + keys[k] + ", " + std::to_string(KS_CAND_MAX_VALUES) + " are supported");
+  const uint32_t NK = (uint32_t)keys.size(), NB = (uint32_t)pdbs.size();
+  // namespaces: the bound pods' get ids; a PDB in a namespace no pod has, and a nil selector (LabelSelectorAsSelector(nil) selects nothing), get an id no pod has
+  const uint32_t kNoNs = 0xFFFFFFFFu; std::unordered_map<std::string, uint32_t> nsindex;
+  std::vector<uint32_t> pod_ns(NP, 0); std::vector<uint8_t> pod_val((size_t)NK * NP, (uint8_t)KS_CAND_BIT_ABSENT);
+  for (uint32_t p = 0; p < NP; ++p) {
+    if (bind[p] < 0) continue;
+    const ksp::Pod& pod = pr.pods[p];
+    pod_ns[p] = nsindex.emplace(pod.ns, (uint32_t)nsindex.size()).first->second;
+    for (uint32_t k = 0; k < NK; ++k) {
+      auto it = pod.labels.find(keys[k]); if (it == pod.labels.end()) continue;
+      auto v = vindex[k].find(it->second);
+      pod_val[(size_t)k * NP + p] = v == vindex[k].end() ? (uint8_t)KS_CAND_BIT_OTHER : (uint8_t)v->second;
+    }
+  }
+  std::vector<uint32_t> pdb_ns(NB), req_off(NB + 1, 0), req_key; std::vector<int32_t> pdb_allowed(NB); std::vector<uint64_t> req_mask;
+  const uint64_t kAbsent = 1ull << KS_CAND_BIT_ABSENT;
+  for (uint32_t b = 0; b < NB; ++b) {
+    const ksp::Pdb& d = pdbs[b]; auto ns = nsindex.find(d.ns);
+    pdb_ns[b] = (d.selector.nil || ns == nsindex.end()) ? kNoNs : ns->second; pdb_allowed[b] = d.disruptions_allowed;
+    if (!d.selector.nil) {
+      for (auto& kv : d.selector.match_labels) { const uint32_t k = kindex[kv.first]; req_key.push_back(k); req_mask.push_back(1ull << vindex[k][kv.second]); }
+      for (auto& x : d.selector.match_exprs) {
+        const uint32_t k = kindex[x.key]; uint64_t bits = 0; for (auto& v : x.values) bits |= 1ull << vindex[k][v];
+        req_key.push_back(k);
+        req_mask.push_back(x.op == ksp::Op::In ? bits : x.op == ksp::Op::NotIn ? ~bits : x.op == ksp::Op::Exists ? ~kAbsent : kAbsent);
+      }
+    }
+    req_off[b + 1] = (uint32_t)req_key.size();
+  }
+  // nodes: the reason the host can give (the reference's order), the provisioner's ttl, the pods in ascending slot order
+  std::vector<uint8_t> is_del(NN, 0); for (uint32_t i = 0; i < n_deleting; ++i) is_del[deleting[i]] = 1;
+  std::vector<uint32_t> node_why(NN, 0), pods_off(NN + 1, 0), node_pods; std::vector<int64_t> node_ttl(NN, -1);
+  for (uint32_t n = 0; n < NN; ++n) {
+    const uint32_t f = in->node_flags[n]; uint32_t w = 0;
+    if (cs.why[n] == KS_CAND_WHY_LEFT) w = KS_CAND_WHY_LEFT;
+    else if (is_del[n]) w = 1;                                                                   // helpers.go:186
+    else if (cs.why[n]) w = cs.why[n];                                                           // :190-211
+    else if (f & KSH_CAND_NODE_NOMINATED) w = 7;                                                 // :215
+    else if (f & KSH_CAND_NODE_DO_NOT_CONSOLIDATE) w = (f & KSH_CAND_NODE_DO_NOT_CONSOLIDATE_TRUE) ? 8 : 0;      // consolidation.go:108-111: `return val != "true"`
+    else if (!in->prov_consolidation_enabled[cs.prov[n]]) w = 9;                                 // :116-119
+    if (w == 0 && (f & KSH_CAND_NODE_DELETION_TIMESTAMP)) w = KS_CAND_WHY_DELETING_NODE;         // helpers.go:340
+    node_why[n] = w;
+    if ((w == 0 || w == KS_CAND_WHY_DELETING_NODE) && cs.prov[n] >= 0) node_ttl[n] = in->prov_ttl_seconds_until_expired[cs.prov[n]];
+  }
+  for (uint32_t p = 0; p < NP; ++p) if (bind[p] >= 0) pods_off[(size_t)bind[p] + 1]++;
+  for (uint32_t n = 0; n < NN; ++n) pods_off[n + 1] += pods_off[n];
+  node_pods.resize(pods_off[NN]);
+  { std::vector<uint32_t> fill(pods_off.begin(), pods_off.end() - 1); for (uint32_t p = 0; p < NP; ++p) if (bind[p] >= 0) node_pods[fill[bind[p]]++] = p; }
+  ks_candidates_inputs ki{}; ki.n_pods = NP; ki.n_nodes = NN; ki.n_pdbs = NB; ki.n_keys = NK;
+  ki.pod_node = bind.data(); ki.pod_ns = pod_ns.data(); ki.pod_flags = in->pod_flags; ki.pod_deletion_cost = in->pod_deletion_cost; ki.pod_priority = in->pod_priority; ki.pod_val = pod_val.data();
+  ki.pdb_ns = pdb_ns.data(); ki.pdb_allowed = pdb_allowed.data(); ki.pdb_req_off = req_off.data(); ki.pdb_req_key = req_key.data(); ki.pdb_req_mask = req_mask.data();
+  ki.node_why = node_why.data(); ki.node_age_seconds = in->node_age_seconds; ki.node_ttl_seconds = node_ttl.data(); ki.node_pods_off = pods_off.data(); ki.node_pods = node_pods.data();
+  ks_candidates_outputs ko{}; ko.order = out->order; ko.empty = out->empty; ko.why = out->why; ko.detail = out->detail; ko.n_node_pods = out->n_node_pods; ko.cost = out->cost;
+  const double host_ms = std::chrono::duration<double, std::milli>(clk::now() - t_call).count();
+  double kms[3] = {0, 0, 0};
+  const int rc = ks_consolidation_candidates_host(&ki, &ko, device, kms);
+  if (rc != KS_OK) return set_err(rc, ks_last_error());
+  out->n_candidates = ko.n_candidates; out->n_empty = ko.n_empty;
+  if (ms) { ms[0] = host_ms; ms[1] = kms[0]; ms[2] = kms[1]; ms[3] = kms[2]; }
+  return KS_OK;
+}
+}  // namespace
+extern "C" {
+int ksh_consolidation_candidates(void* parsed, const int32_t* pod_node, const uint32_t* deleting, uint32_t n_deleting, const ksh_candidate_inputs* in, const ksh_pdb_block* pdbs, int device,
+                                 ksh_candidates_out* out, double* ms) {
+  try { return candidates_over((Parsed*)parsed, pod_node, deleting, n_deleting, in, pdbs, device, out, ms); }
+  catch (const ksh::Unsupported& e) { return set_err(KS_ERR_UNSUPPORTED, e.what()); } catch (const std::exception& e) { return set_err(KS_ERR_INVALID, e.what()); }
 }
 // The names behind a row, without a handle: what 0 = requirement key a, 1 = value b of key a (the flattening's universes: available once a what-if call flattened the
 // snapshot), 3 = state node a, 4 = instance type a.  NULL when out of range.

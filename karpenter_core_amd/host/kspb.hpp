@@ -188,4 +188,35 @@ class DeltaReader : public EnvReader {
   }
 };
 
+// The cluster's PodDisruptionBudgets through the same kind of door (include/kshost.h `ksh_pdb_block`, ksh_consolidation_candidates): what NewPDBLimits lists
+// (pdblimits.go:34-53) as ONE stream of u32 words over ONE string table:
+//
+//   pdbs       := n_pdbs { namespace:S disruptions_allowed:I selector }        (selector: the pod records' grammar; 1 = nil, selects nothing)
+//
+// n_pdbs is the block's own field; the stream must hold exactly that many records and end with the last one.
+struct Pdb { std::string ns; int32_t disruptions_allowed = 0; Selector selector; };
+class PdbReader : public SpecReader {
+ public:
+  PdbReader(const ksh_pod_block& strings, const uint32_t* w, const uint32_t* e) : SpecReader(strings, w, e) {}
+  std::vector<Pdb> read_pdbs(uint32_t n_pdbs) {
+    std::vector<Pdb> out;
+    if (n_pdbs > (uint32_t)(e_ - w_)) throw Error("pdb block: n_pdbs is larger than the stream (every PDB takes at least three words)");
+    out.reserve(n_pdbs);
+    for (uint32_t k = 0; k < n_pdbs; ++k) {
+      try {
+        Pdb p; p.ns = s(); p.disruptions_allowed = i(); p.selector = selector();
+        // metav1.LabelSelectorAsSelector's own refusals (NewPDBLimits returns its error)
+        for (const Expr& x : p.selector.match_exprs) {
+          if (x.op == Op::Gt || x.op == Op::Lt) throw Error("not a label-selector operator");
+          if ((x.op == Op::In || x.op == Op::NotIn) && x.values.empty()) throw Error("In / NotIn need at least one value");
+          if ((x.op == Op::Exists || x.op == Op::DoesNotExist) && !x.values.empty()) throw Error("Exists / DoesNotExist take no values");
+        }
+        out.push_back(std::move(p));
+      } catch (const Error& x) { throw Error("pdb block: PDB " + std::to_string(k) + ": " + x.what()); }
+    }
+    if (w_ != e_) throw Error("pdb block: PDB " + std::to_string(n_pdbs) + ": trailing words (the stream goes on after its n_pdbs records)");
+    return out;
+  }
+};
+
 }  // namespace ksp

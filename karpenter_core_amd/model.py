@@ -514,6 +514,33 @@ class DeltaBlockWriter(EnvBlockWriter):
         return dict(self._block(), n_events=len(events))
 
 
+@dataclass
+class PodDisruptionBudget:
+    """policyv1.PodDisruptionBudget as far as PDBLimits reads it (deprovisioning/pdblimits.go:72-88): namespace, Spec.Selector (None: nil, selects nothing),
+    Status.DisruptionsAllowed."""
+    namespace: str = "default"
+    selector: Optional["LabelSelector"] = None
+    disruptions_allowed: int = 0
+    name: str = ""
+
+
+class PdbBlockWriter(EnvBlockWriter):
+    """Binary PDB ingress (include/kshost.h `ksh_pdb_block`, grammar in karpenter_core_amd/host/kspb.hpp PdbReader): per PDB namespace, disruptionsAllowed and the
+    selector, as one stream of u32 words over one string table."""
+
+    def write_pdbs(self, pdbs: Sequence["PodDisruptionBudget"]) -> dict:
+        w = self._words
+        for b in pdbs:
+            w.extend((self._s(b.namespace), int(b.disruptions_allowed) & 0xFFFFFFFF))
+            self._sel(w, b.selector)
+        return dict(self._block(), n_pdbs=len(pdbs))
+
+
+def pdbs_to_block(pdbs: Sequence["PodDisruptionBudget"]) -> dict:
+    """The PodDisruptionBudgets as one binary block (`ksh_consolidation_candidates`)."""
+    return PdbBlockWriter().write_pdbs(pdbs)
+
+
 def _ksp_reslist(rl: Dict[str, str], w):
     w.write(f" {len(rl)}")
     for k in sorted(rl):

@@ -777,6 +777,70 @@ def single_node_option(snapshot: "ParsedProblem", pod_node, candidates: Sequence
     return _search_option("ksh_single_node_option", snapshot, pod_node, candidates, words, deleting, device, volumes, active_resources, flags)
 
 
+KSH_CAND_NODE_NOMINATED, KSH_CAND_NODE_DO_NOT_CONSOLIDATE, KSH_CAND_NODE_DO_NOT_CONSOLIDATE_TRUE, KSH_CAND_NODE_DELETION_TIMESTAMP = 1, 2, 4, 8      # kshost.h
+KSH_CAND_POD_DO_NOT_EVICT, KSH_CAND_POD_HAS_DELETION_COST, KSH_CAND_POD_HAS_PRIORITY = 1, 2, 4
+KS_CAND_MAX_KEYS, KS_CAND_MAX_VALUES = 16, 62
+CANDIDATE_TIMING_KEYS = ("host_ms", "upload_ms", "kernels_ms", "readback_ms")
+
+
+class _CandidateInputs(ctypes.Structure):      # include/kshost.h ksh_candidate_inputs
+    _fields_ = [("n_nodes", ctypes.c_uint32), ("n_pods", ctypes.c_uint32), ("n_provisioners", ctypes.c_uint32), ("pad", ctypes.c_uint32), ("node_flags", ctypes.c_void_p),
+                ("node_age_seconds", ctypes.c_void_p), ("pod_flags", ctypes.c_void_p), ("pod_deletion_cost", ctypes.c_void_p), ("pod_priority", ctypes.c_void_p),
+                ("prov_consolidation_enabled", ctypes.c_void_p), ("prov_ttl_seconds_until_expired", ctypes.c_void_p)]
+
+
+class _PdbBlock(ctypes.Structure):      # include/kshost.h ksh_pdb_block
+    _fields_ = [("n_pdbs", ctypes.c_uint32), ("n_strings", ctypes.c_uint32), ("n_words", ctypes.c_uint32), ("str_off", ctypes.c_void_p), ("str_bytes", ctypes.c_void_p),
+                ("words", ctypes.c_void_p), ("str_bytes_len", ctypes.c_uint64)]
+
+
+class _CandidatesOut(ctypes.Structure):      # include/kshost.h ksh_candidates_out
+    _fields_ = [("n_candidates", ctypes.c_uint32), ("n_empty", ctypes.c_uint32), ("order", ctypes.c_void_p), ("empty", ctypes.c_void_p), ("why", ctypes.c_void_p),
+                ("detail", ctypes.c_void_p), ("n_node_pods", ctypes.c_void_p), ("cost", ctypes.c_void_p)]
+
+
+def consolidation_candidates(snapshot: "ParsedProblem", pod_node: Optional[Sequence[int]], node_flags: Sequence[int], node_age_seconds: Sequence[float],
+                             pod_flags: Sequence[int], pod_deletion_cost: Sequence[float], pod_priority: Sequence[int], prov_consolidation_enabled: Sequence[bool],
+                             prov_ttl_seconds: Sequence[Optional[int]], pdbs=(), deleting: Sequence[int] = (), device: int = 0, out: Optional[dict] = None) -> dict:
+    """candidateNodes + consolidation.ShouldDeprovision + sortAndFilterCandidates in ONE call (kshost.h `ksh_consolidation_candidates`): the per-pod eviction costs and
+    PDB matches, the per-node sums and reasons and the order are computed on the device.  The arrays run over the snapshot's node / pod slots and its provisioners;
+    `pdbs`: `model.PodDisruptionBudget`s, or the block `model.pdbs_to_block` made of them; `prov_ttl_seconds`: None (or -1) for nil.  Returns {"order", "empty": lists of
+    node slots; "why", "detail", "n_node_pods": int arrays per node slot; "cost": float64 per node slot; "ms": the library's split of the call}.  `order` is what
+    `first_n_node_option` / `single_node_option` take as candidates.  `out`: preallocated arrays to fill instead
+    ({"order", "empty", "why", "n_node_pods": uint32, "detail": int32, "cost": float64}, one entry per node slot)."""
+    import numpy as np
+    from .model import pdbs_to_block
+    kh = libs()[1]
+    nf = np.ascontiguousarray(np.asarray(list(node_flags) or [0], dtype=np.uint32)); age = np.ascontiguousarray(np.asarray(list(node_age_seconds) or [0.0], dtype=np.float64))
+    pf = np.ascontiguousarray(np.asarray(list(pod_flags) or [0], dtype=np.uint32)); dc = np.ascontiguousarray(np.asarray(list(pod_deletion_cost) or [0.0], dtype=np.float64))
+    pp = np.ascontiguousarray(np.asarray(list(pod_priority) or [0], dtype=np.int32))
+    en = np.ascontiguousarray(np.asarray([1 if e else 0 for e in prov_consolidation_enabled] or [0], dtype=np.uint32))
+    ttl = np.ascontiguousarray(np.asarray([-1 if t is None else int(t) for t in prov_ttl_seconds] or [-1], dtype=np.int64))
+    n_nodes, n_pods = len(node_flags), len(pod_flags)
+    if len(node_age_seconds) != n_nodes or len(pod_deletion_cost) != n_pods or len(pod_priority) != n_pods or len(prov_ttl_seconds) != len(prov_consolidation_enabled):
+        raise KSolveError(KS_ERR_INVALID, "consolidation_candidates: array lengths differ")
+    inp = _CandidateInputs(n_nodes, n_pods, len(prov_consolidation_enabled), 0, nf.ctypes.data, age.ctypes.data, pf.ctypes.data, dc.ctypes.data, pp.ctypes.data, en.ctypes.data, ttl.ctypes.data)
+    b = pdbs if isinstance(pdbs, dict) else pdbs_to_block(list(pdbs))
+    pb = _PdbBlock(b["n_pdbs"], b["n_strings"], b["n_words"], b["str_off"].ctypes.data, b["str_bytes"].ctypes.data, b["words"].ctypes.data, int(b.get("str_bytes_len", b["str_bytes"].size)))
+    m = max(1, n_nodes)
+    if out is not None:          # (tests: preallocated arrays, poisoned first)
+        order, empty, why, npods, detail, cost = (out[k] for k in ("order", "empty", "why", "n_node_pods", "detail", "cost"))
+    else:
+        order, empty, why, npods = (np.zeros(m, dtype=np.uint32) for _ in range(4))
+        detail, cost = np.zeros(m, dtype=np.int32), np.zeros(m, dtype=np.float64)
+    out = _CandidatesOut(0, 0, order.ctypes.data, empty.ctypes.data, why.ctypes.data, detail.ctypes.data, npods.ctypes.data, cost.ctypes.data)
+    pn, pn_ptr = _pod_node_arg(pod_node)
+    dl = _u32s(deleting)
+    ms = (ctypes.c_double * 4)()
+    kh.ksh_consolidation_candidates.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+                                                ctypes.POINTER(ctypes.c_double)]
+    rc = kh.ksh_consolidation_candidates(snapshot._p, pn_ptr, dl.ctypes.data, len(deleting), ctypes.byref(inp), ctypes.byref(pb), device, ctypes.byref(out), ms)
+    if rc != KS_OK:
+        raise KSolveError(rc, kh.ksh_last_error().decode())
+    return {"order": [int(x) for x in order[:out.n_candidates]], "empty": [int(x) for x in empty[:out.n_empty]], "why": why[:n_nodes], "detail": detail[:n_nodes],
+            "n_node_pods": npods[:n_nodes], "cost": cost[:n_nodes], "ms": dict(zip(CANDIDATE_TIMING_KEYS, [float(x) for x in ms]))}
+
+
 def command_rows(flats: Sequence[FlatProblem], ids: Sequence[int], flags: Sequence[int], cand_prices: Sequence[float], type_lists: Sequence[Sequence[Tuple[int, float]]], words: int,
                  out=None, type_off=None):
     """`ksh_command_rows`: the command rows of handles whose results are on the device, the per-what-if inputs given by the caller (flags: KS_CMD_F_*; type_lists[i]:
