@@ -18,6 +18,9 @@
  *   ksh_consolidation_commands / ksh_first_n_node_option / ksh_single_node_option
  *                             computeConsolidation (consolidation.go:190-274) and the two searches built on it (multinodeconsolidation.go:74-165,
  *                             singlenodeconsolidation.go:54-78): snapshot and candidate sets in, fixed-size command rows out, decided on the device.
+ *   ksh_validate_commands / ksh_single_node_resume / ksh_validate_empty_nodes
+ *                             Validation.IsValid / ValidateCommand on the cluster as it is after consolidationTTL (validation.go:63-172), the rest of the single-node
+ *                             loop (singlenodeconsolidation.go:54-84) and EmptyNodeConsolidation's own check (emptynodeconsolidation.go:77-87).
  *   ksh_result_text / ksh_result_summary
  *                             what callers read from Solve's return values: KSR1 text (Node.Pods, InstanceTypeOptions,
  *                             Requirements, Requests, ExistingNode.Pods, unscheduled queue, relaxation stages), or the fixed-size record
@@ -252,6 +255,47 @@ int ksh_command_rows(void** handles, uint32_t n, const uint64_t* ids, const ks_c
 const char* ksh_snapshot_name(void* parsed_snapshot, int what, uint32_t a, uint32_t b);
 int ksh_snapshot_it_state(void* parsed_snapshot, uint32_t state, int* complement, uint32_t* n_values);
 const char* ksh_snapshot_it_state_value(void* parsed_snapshot, uint32_t state, uint32_t i);
+
+/* ---- consolidation commands VALIDATED, on the device: the last step of a pass -- snapshot -> candidates -> commands -> (events, consolidationTTL) -> validated
+ * commands.  Validation.IsValid after its wait (deprovisioning/validation.go:63-100) and ValidateCommand (:109-172) with mapNodes (helpers.go:328-337), a second
+ * simulateScheduling and instanceTypesAreSubset (helpers.go:118-122), for n commands against the snapshot as it is NOW (kept current by ksh_env_apply*; the wait
+ * itself stays with the caller).  One fixed-size row per command (layout: ksolve.h KS_VAL_*, KS_VAL_ROW_WORDS(words) uint64 each); row i answers command i,
+ * row[KS_VAL_ID] = i.
+ *   node_off / nodes   each command's nodesToRemove as node slots of THIS snapshot (slots are stable across events; an empty list is allowed)
+ *   expect_replacement len(cmd.replacementNodes) != 0;  options[i]: that node's InstanceTypeOptions -- of a command row, its launch options -- as a bit mask whose
+ *                      bits are indices into the catalogue of the snapshot PASSED (the same catalogue unless the snapshot was ingested again); read only where a
+ *                      replacement is expected; may be NULL if none is
+ *   why / node_flags   [node slots] ksh_consolidation_candidates' out->why over THIS snapshot, and the node flags it was given (KSH_CAND_NODE_NOMINATED is read)
+ *   pod_node, deleting, flags: as for ksh_consolidation_commands.
+ * Host steps, the reference's order, first wins: (1) a node of the command is nominated -- over ALL its nodes, before the mapping (validation.go:87-91) -> invalid;
+ * (2) mapping: a node maps iff why[node] is 0, 10, 11 or 12, i.e. it is in candidateNodes' result under Validation.ShouldDeprovision == consolidation.ShouldDeprovision
+ * (sortAndFilterCandidates is NOT applied in validation); a tombstoned slot (13) and an empty list do not map; nothing maps -> invalid (:114); (3) a mapped node is
+ * listed in `deleting` -> verdict KS_VAL_ERROR, the error of helpers.go:62-67 (reachable when `deleting` is newer than `why`: the reference's own race).  Rows 1-3 are
+ * written by the library and not simulated.  Every other command's MAPPED nodes -- in ascending slot order, each once: mapNodes walks the candidates, and slot order is
+ * the canonical order of DESIGN 7.16; NewQueue's order is total, so the order decides nothing -- leave the cluster in ONE batch of what-ifs on the route of
+ * ksh_consolidation_commands (derived on the device, else flattened one by one; the carrier of pending pods first, owned deleting nodes last; KS_VAL_F_BLOCKED from the
+ * same label table as KS_CMD_F_BLOCKED), and kernel ks_validate_commands writes steps 4-8 or valid.  Validation reads no requirement state, so the fallback route's
+ * instance-type-state refusal does not apply here.
+ * Whole-call refusals (nothing simulated, out_rows untouched): KS_ERR_INVALID for an unknown flag bit, words < ceil(T/64), offsets not ascending, a slot out of
+ * range, a listed type index >= T, NULL arrays.  ms[5] as ksh_consolidation_commands ([2] = the validation kernel).  No CPU path: without a device KS_ERR_DEVICE. */
+int ksh_validate_commands(void* parsed_snapshot_now, uint32_t flags, uint32_t n, const uint32_t* node_off /* [n+1] */, const uint32_t* nodes, const uint32_t* expect_replacement /* [n] */,
+                          const uint64_t* options /* [n][words] */, const uint32_t* why /* [node slots] */, const uint32_t* node_flags /* [node slots] */,
+                          const int32_t* pod_node /* or NULL after ksh_env_apply */, const uint32_t* deleting, uint32_t n_deleting, int device,
+                          uint64_t* out_rows /* [n][KS_VAL_ROW_WORDS(words)] */, uint32_t words, double* ms /* [5] or NULL */);
+/* SingleNodeConsolidation.ComputeCommand's loop (singlenodeconsolidation.go:54-84) AFTER a first validation has failed: candidates[0 .. n) are the candidates that
+ * follow the one whose command failed, as slots of the CURRENT snapshot.  Their singleton commands are computed in one command batch, the deletes and replaces among
+ * them validated in one validation batch, and the first VALID one in candidate order is returned: out_state = 1, out_row its command row (row[KS_CMD_ID] = its
+ * position in `candidates`), out_vrow its validation row.  Error rows and validation errors are passed over, as the reference logs and continues.  If none is valid
+ * both rows are zero and out_state = 2 (actionRetry) when failed_before != 0 or any validation here said invalid, else 0 (do-nothing).  A candidate whose slot has left
+ * is an empty node to the command step and fails validation (nothing maps).  ms[5]: the sums over both batches. */
+int ksh_single_node_resume(void* parsed_snapshot_now, uint32_t flags, const uint32_t* candidates, uint32_t n, int failed_before, const uint32_t* why, const uint32_t* node_flags,
+                           const int32_t* pod_node, const uint32_t* deleting, uint32_t n_deleting, int device, uint64_t* out_row /* [KS_CMD_ROW_WORDS(words)] */,
+                           uint64_t* out_vrow /* [KS_VAL_ROW_WORDS(words)] */, uint32_t* out_state, uint32_t words, double* ms /* [5] or NULL */);
+/* EmptyNodeConsolidation's own, cheaper check (emptynodeconsolidation.go:77-87), literally; host only, no simulation.  nodes[0 .. n): the command's nodes as slots;
+ * why / n_node_pods: ksh_consolidation_candidates' outputs over the snapshot NOW; node_flags as above ([node slots] each; every slot listed must be in range).  The
+ * nodes are mapped as above; *out_retry = 1 iff a mapped node has pods and is not nominated.  A command none of whose nodes maps comes back with *out_retry = 0 -- the
+ * reference returns such a command as it is, and so does this. */
+int ksh_validate_empty_nodes(const uint32_t* nodes, uint32_t n, const uint32_t* why, const uint32_t* n_node_pods, const uint32_t* node_flags, uint32_t* out_retry);
 
 /* ---- consolidation CANDIDATES, selected and ordered on the device: the first step of a consolidation pass, so that snapshot -> candidates -> commands runs through
  * this header alone.  candidateNodes (deprovisioning/helpers.go:171-249) with consolidation.ShouldDeprovision (consolidation.go:106-121) as its filter, then

@@ -10,6 +10,7 @@
  *                                     deprovisioning/helpers.go:148-157,292-315 (consolidation.go:238, multinodeconsolidation.go:164)
  *   ks_consolidation_commands_dev <-> computeConsolidation's decision over a what-if's result, deprovisioning/consolidation.go:190-274,
  *                                     and filterOutSameType, multinodeconsolidation.go:132-165
+ *   ks_validate_commands_dev     <->  Validation.ValidateCommand's verdict over a re-simulation's result, deprovisioning/validation.go:118-171
  *   ks_feasibility_grid          <->  filterInstanceTypesByRequirements for a fresh node, node.go:137-159
  *                                     (compatible && fits && hasOffering over every instance type)
  *   ks_probe_*                   <->  Requirement.Intersection/Has/Operator/Len, Requirements.Compatible
@@ -420,6 +421,53 @@ int ks_consolidation_commands_dev(ks_dev_problem* const* ds, uint32_t n, const u
 /* The same with the rows brought to HOST memory out_rows[n][KS_CMD_ROW_WORDS(words)] (one launch, one device-to-host copy); ms (may be NULL): [0] inputs up + launch +
  * completion, [1] the read-back, milliseconds.  The inputs are validated once, before any device work. */
 int ks_consolidation_commands_host(ks_dev_problem* const* ds, uint32_t n, const uint64_t* ids, const ks_command_inputs* in, uint32_t words, uint64_t* out_rows, double* ms);
+
+/* ---- consolidation commands VALIDATED on the device (deprovisioning/validation.go:118-171 Validation.ValidateCommand after mapNodes and simulateScheduling): for
+ * command i, over the result the last ks_solve*_dev of ds[i] -- the re-simulation of the command's nodes that are still candidates -- left on the device, ONE
+ * fixed-size row of uint64 in a caller-owned DEVICE buffer d_out[n][KS_VAL_ROW_WORDS(words)].  ks_consolidation_commands_dev's sibling: one launch for the batch (one
+ * wave per command), on ds[0]'s stream; the buffer is complete when the call returns; every word of every row is written (words beyond a problem's ceil(T/64) are zero).
+ * The steps, in the reference's order, the first that applies decides: blocked or n_unscheduled > 0 -> invalid (4); n_new == 0 -> valid unless a replacement was
+ * expected (5); n_new > 1 -> invalid (6); one new node but none expected -> invalid (7); instanceTypesAreSubset(the command's options, new node 0's options now) fails
+ * -> invalid (8); else valid.  options[i] is read only under KS_VAL_F_EXPECT_REPLACEMENT (len(cmd.replacementNodes) != 0); its bits are instance-type indices of
+ * ds[i]'s catalogue. */
+#define KS_VAL_F_BLOCKED 1u              /* an owned, in-state node that is not initialised stays in the cluster (helpers.go:102-113), as KS_CMD_F_BLOCKED */
+#define KS_VAL_F_EXPECT_REPLACEMENT 2u   /* the command carries a replacement node */
+#define KS_VAL_F_ALL 3u
+typedef struct ks_validate_inputs {
+  const uint32_t* flags;      /* [n] KS_VAL_F_*; any other bit: KS_ERR_INVALID */
+  const uint32_t* n_mapped;   /* [n] how many of the command's nodes were simulated (echoed into the row) */
+  const uint64_t* options;    /* [n][words] the command's replacement InstanceTypeOptions; may be NULL when no command expects a replacement */
+} ks_validate_inputs;
+/* the row: words of uint64 */
+#define KS_VAL_ID 0                  /* ids[i] */
+#define KS_VAL_VERDICT 1             /* verdict | why << 8 */
+#define KS_VAL_N_NEW 2
+#define KS_VAL_N_UNSCHEDULED 3
+#define KS_VAL_N_MAPPED 4            /* nodes of the command that were simulated (host-supplied, echoed) */
+#define KS_VAL_N_OPTIONS 5           /* popcount of new node 0's options now (0 if there is no new node) */
+#define KS_VAL_N_MISSING 6           /* popcount(command options & ~options now); 0 unless the subset test ran */
+                                     /* word 7: reserved, zero */
+#define KS_VAL_OPTIONS 8             /* [words] new node 0's InstanceTypeOptions now; then [words] the command's types the re-simulation no longer offers */
+#define KS_VAL_ROW_WORDS(words) (KS_VAL_OPTIONS + 2 * (size_t)(words))
+/* verdict (KS_VAL_VERDICT & 0xff) */
+#define KS_VAL_INVALID 0
+#define KS_VAL_VALID 1
+#define KS_VAL_ERROR 2               /* ValidateCommand returned an error, not a verdict (written by libkshost only) */
+/* why ((KS_VAL_VERDICT >> 8) & 0xff): the reference's step that decided.  1-3 are written by libkshost and never simulated; 0 and 4-8 by the kernel. */
+#define KS_VAL_WHY_VALID 0
+#define KS_VAL_WHY_NOMINATED 1          /* a node of the command is nominated (validation.go:87-91) */
+#define KS_VAL_WHY_NO_CANDIDATES 2      /* no node of the command is still a candidate (:114) */
+#define KS_VAL_WHY_DELETING 3           /* a mapped node is itself being deleted: verdict KS_VAL_ERROR (helpers.go:62-67) */
+#define KS_VAL_WHY_NOT_ALL_SCHEDULED 4  /* :122, KS_VAL_F_BLOCKED included */
+#define KS_VAL_WHY_NO_NEW_NODE 5        /* no new node but a replacement was expected (:139) */
+#define KS_VAL_WHY_MANY_NODES 6         /* more than one new node (:143) */
+#define KS_VAL_WHY_UNEXPECTED_NODE 7    /* one new node but the command is a delete (:148) */
+#define KS_VAL_WHY_NOT_A_SUBSET 8       /* the command's options are not a subset of the re-simulation's (:164) */
+/* Refusals (KS_ERR_INVALID, nothing launched): a null array, a batch over two devices, words < ceil(T/64), an unknown flag bit, a listed type index >= T. */
+int ks_validate_commands_dev(ks_dev_problem* const* ds, uint32_t n, const uint64_t* ids, const ks_validate_inputs* in, uint32_t words, void* d_out);
+/* The same with the rows brought to HOST memory out_rows[n][KS_VAL_ROW_WORDS(words)] (one launch, one device-to-host copy); ms (may be NULL): [0] inputs up + launch +
+ * completion, [1] the read-back, milliseconds. */
+int ks_validate_commands_host(ks_dev_problem* const* ds, uint32_t n, const uint64_t* ids, const ks_validate_inputs* in, uint32_t words, uint64_t* out_rows, double* ms);
 
 /* ---- consolidation CANDIDATES, selected and ordered on the device (deprovisioning/helpers.go:124-165,275-287 GetPodEvictionCost / disruptionCost /
  * calculateLifetimeRemaining, pdblimits.go:57-70 CanEvictPods, helpers.go:339-366 canBeTerminated / PodsPreventEviction, consolidation.go:83-104 the sort).

@@ -546,6 +546,26 @@ class CandidateInfo:
     pdbs: Sequence = ()                                 # model.PodDisruptionBudget
 
 
+def _candidates_call(S, parsed, pod_node, snapshot: Snapshot, info: CandidateInfo, device: int = 0):
+    """`ksh_consolidation_candidates` over a `Snapshot` opened by `_command_snapshot`: (the call's result over every node slot, the node flags it was given)."""
+    pods = [p for b in snapshot.bound for p in b] + list(snapshot.pending)
+    nn = len(snapshot.nodes) + (1 if snapshot.pending else 0)
+    nf = [0] * nn
+    for i in info.nominated:
+        nf[i] |= S.KSH_CAND_NODE_NOMINATED
+    for i, v in info.do_not_consolidate.items():
+        nf[i] |= S.KSH_CAND_NODE_DO_NOT_CONSOLIDATE | (S.KSH_CAND_NODE_DO_NOT_CONSOLIDATE_TRUE if v == "true" else 0)
+    for i in info.deletion_timestamp:
+        nf[i] |= S.KSH_CAND_NODE_DELETION_TIMESTAMP
+    dne = set(info.do_not_evict)
+    pf = [(S.KSH_CAND_POD_DO_NOT_EVICT if p.uid in dne else 0) | (S.KSH_CAND_POD_HAS_DELETION_COST if p.uid in info.deletion_cost else 0) |
+          (S.KSH_CAND_POD_HAS_PRIORITY if p.uid in info.priority else 0) for p in pods]
+    age = list(info.node_age_seconds) + [0.0] * (nn - len(info.node_age_seconds))
+    got = S.consolidation_candidates(parsed, pod_node, nf, age, pf, [float(info.deletion_cost.get(p.uid, 0.0)) for p in pods], [int(info.priority.get(p.uid, 0)) for p in pods],
+                                     [info.consolidation_enabled], [info.ttl_seconds_until_expired], pdbs=info.pdbs, deleting=[int(j) for j in snapshot.deleting], device=device)
+    return got, nf
+
+
 def consolidation_candidates_dev(snapshot: Snapshot, info: CandidateInfo, device: int = 0, timings: Optional[dict] = None) -> dict:
     """candidateNodes + ShouldDeprovision + sortAndFilterCandidates through `ksh_consolidation_candidates`: {"order": the candidates' node indices by disruption
     cost -- what `first_n_node_consolidation_option_dev` / `single_node_consolidation_option_dev` take as they are --, "empty": the candidates without pods in the same
@@ -554,25 +574,77 @@ def consolidation_candidates_dev(snapshot: Snapshot, info: CandidateInfo, device
     from . import scheduler as S
     parsed, pod_node, leaving = _command_snapshot(snapshot)
     try:
-        pods = [p for b in snapshot.bound for p in b] + list(snapshot.pending)
-        nn = len(snapshot.nodes) + (1 if snapshot.pending else 0)
-        nf = [0] * nn
-        for i in info.nominated:
-            nf[i] |= S.KSH_CAND_NODE_NOMINATED
-        for i, v in info.do_not_consolidate.items():
-            nf[i] |= S.KSH_CAND_NODE_DO_NOT_CONSOLIDATE | (S.KSH_CAND_NODE_DO_NOT_CONSOLIDATE_TRUE if v == "true" else 0)
-        for i in info.deletion_timestamp:
-            nf[i] |= S.KSH_CAND_NODE_DELETION_TIMESTAMP
-        dne = set(info.do_not_evict)
-        pf = [(S.KSH_CAND_POD_DO_NOT_EVICT if p.uid in dne else 0) | (S.KSH_CAND_POD_HAS_DELETION_COST if p.uid in info.deletion_cost else 0) |
-              (S.KSH_CAND_POD_HAS_PRIORITY if p.uid in info.priority else 0) for p in pods]
-        age = list(info.node_age_seconds) + [0.0] * (nn - len(info.node_age_seconds))
-        got = S.consolidation_candidates(parsed, pod_node, nf, age, pf, [float(info.deletion_cost.get(p.uid, 0.0)) for p in pods], [int(info.priority.get(p.uid, 0)) for p in pods],
-                                         [info.consolidation_enabled], [info.ttl_seconds_until_expired], pdbs=info.pdbs, deleting=[int(j) for j in snapshot.deleting], device=device)
+        got, _ = _candidates_call(S, parsed, pod_node, snapshot, info, device)
         if timings is not None:
             timings.update(got["ms"])
         n = len(snapshot.nodes)
         return {"order": got["order"], "empty": got["empty"], "why": [int(x) for x in got["why"][:n]], "detail": [int(x) for x in got["detail"][:n]],
                 "cost": [float(x) for x in got["cost"][:n]], "n_node_pods": [int(x) for x in got["n_node_pods"][:n]]}
+    finally:
+        parsed.close()
+
+
+# =====================================================================================================
+# Validation through the C ABI (include/kshost.h ksh_validate_commands, ksh_single_node_resume, ksh_validate_empty_nodes): `snapshot_now` is the cluster after
+# consolidationTTL; node and instance-type NAMES are translated to slots and bits of that snapshot.  `validate_command` above stays as it is.
+# =====================================================================================================
+def _command_inputs_now(snapshot_now: Snapshot, commands: Sequence[Command]):
+    slot = {n.name: i for i, n in enumerate(snapshot_now.nodes)}
+    tindex = {it.name: i for i, it in enumerate(snapshot_now.instance_types)}
+    for cmd in commands:
+        for t in cmd.replacement_types:
+            if t not in tindex:
+                raise ValueError(f"replacement type {t} is not in the catalogue of the snapshot passed")
+    node_sets = [[slot[n] for n in cmd.nodes_to_remove if n in slot] for cmd in commands]      # (a node that is not in the cluster any more cannot map)
+    return node_sets, [bool(cmd.replacement_types) for cmd in commands], [[tindex[t] for t in cmd.replacement_types] for cmd in commands]
+
+
+def validate_commands_dev(snapshot_now: Snapshot, commands: Sequence[Command], info: CandidateInfo, device: int = 0, timings: Optional[dict] = None) -> List[Tuple[Optional[bool], int]]:
+    """Validation.IsValid (after its wait) for every command in ONE call: candidates over `snapshot_now` (`ksh_consolidation_candidates`), then `ksh_validate_commands`.
+    -> [(valid, why)] per command; valid is None where the reference returns an error (a node of the command that is still a candidate is being deleted); why: ksolve.h
+    KS_VAL_WHY_*."""
+    from . import scheduler as S
+    parsed, pod_node, leaving = _command_snapshot(snapshot_now)
+    try:
+        got, nf = _candidates_call(S, parsed, pod_node, snapshot_now, info, device)
+        node_sets, expect, type_sets = _command_inputs_now(snapshot_now, commands)
+        rows, ms = S.validate_commands(parsed, pod_node, node_sets, expect, type_sets, got["why"], nf, _words(snapshot_now), deleting=leaving, device=device)
+        if timings is not None:
+            timings.update(ms)
+        out = []
+        for row in rows:
+            d = S.decode_validation_row(row, _words(snapshot_now))
+            out.append((d["valid"], d["why"]))
+        return out
+    finally:
+        parsed.close()
+
+
+def single_node_resume_dev(snapshot_now: Snapshot, candidates: Sequence[int], failed_before: bool, info: CandidateInfo, device: int = 0, timings: Optional[dict] = None) -> Tuple[str, Command]:
+    """The rest of SingleNodeConsolidation.ComputeCommand's loop after a validation has failed, through `ksh_single_node_resume`: `candidates` are the node indices (of
+    `snapshot_now`) that follow the failed one.  -> ("found", the valid command) | ("retry", Command()) | ("do-nothing", Command())."""
+    from . import scheduler as S
+    parsed, pod_node, leaving = _command_snapshot(snapshot_now)
+    try:
+        got, nf = _candidates_call(S, parsed, pod_node, snapshot_now, info, device)
+        state, row, _, ms = S.single_node_resume(parsed, pod_node, candidates, failed_before, got["why"], nf, _words(snapshot_now), deleting=leaving, device=device)
+        if timings is not None:
+            timings.update(ms)
+        if state != 1:
+            return ("retry" if state == 2 else "do-nothing"), Command()
+        return "found", _command_of_row(snapshot_now, parsed, row, _words(snapshot_now), [candidates[int(row[S.KS_CMD_ID])]])
+    finally:
+        parsed.close()
+
+
+def validate_empty_nodes(snapshot_now: Snapshot, node_names: Sequence[str], info: CandidateInfo, device: int = 0) -> bool:
+    """EmptyNodeConsolidation's check after its wait (emptynodeconsolidation.go:77-87) through `ksh_validate_empty_nodes`: True = retry.  A command none of whose nodes
+    is still a candidate is NOT a retry: the reference returns it as it is."""
+    from . import scheduler as S
+    parsed, pod_node, leaving = _command_snapshot(snapshot_now)
+    try:
+        got, nf = _candidates_call(S, parsed, pod_node, snapshot_now, info, device)
+        slot = {n.name: i for i, n in enumerate(snapshot_now.nodes)}
+        return S.validate_empty_nodes([slot[n] for n in node_names if n in slot], got["why"], got["n_node_pods"], nf)
     finally:
         parsed.close()

@@ -22,6 +22,7 @@
 //   ks_price_filter       consolidation price stage (filterByPrice / worstLaunchPrice) on device-resident results.
 //   ks_consolidation_commands  computeConsolidation's decision (and filterOutSameType) per what-if over the same results:
 //                         one fixed-size row of u64 each, into a caller-owned device buffer.
+//   ks_validate_commands  Validation.ValidateCommand's verdict per command over a re-simulation's result, likewise.
 //   ks_gather             batched read-back of a what-if batch's results.
 //
 // The reference functions each device function restates are cited inline (paths relative to
@@ -3929,6 +3930,91 @@ extern "C" int ks_consolidation_commands_host(ks_dev_problem* const* ds, uint32_
   TmpDev buf(ds[0]->device); TRY(buf.alloc(bytes));
   const auto t0 = std::chrono::steady_clock::now();
   TRY(commands_launch(st, ids, in, words, buf.p));
+  const auto t1 = std::chrono::steady_clock::now();
+  HIPCHK(hipMemcpy(out_rows, buf.p, bytes, hipMemcpyDeviceToHost));
+  if (ms) { ms[0] = std::chrono::duration<double, std::milli>(t1 - t0).count(); ms[1] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count(); }
+  return KS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Validation.ValidateCommand (deprovisioning/validation.go:118-171) over the re-simulation's result while it is still on the device: ks_consolidation_commands'
+// sibling.  One wave per command, one fixed-size row of u64 out (layout: ksolve.h KS_VAL_*).  Lane w owns words w, w + 64, ... of the two type masks.  What decides a
+// branch -- the counts, the descriptor -- is loaded from the same address by every lane, so the whole wave takes it and reaches the two reductions together.
+// ------------------------------------------------------------------------------------------------
+struct ValDesc { u64 id, opt_off; u32 flags, n_mapped; };      // opt_off: where the command's own option words start in the staged [n][words] block
+__global__ __launch_bounds__(64) void ks_validate_commands(const DevProb* probs, const DevState* states, const ValDesc* descs, const u64* options, u64* out, u32 words) {
+  const DevProb& P = probs[blockIdx.x]; const DevState& S = states[blockIdx.x]; const ValDesc d = descs[blockIdx.x]; const u32 lane = threadIdx.x;
+  u64* row = out + (size_t)blockIdx.x * (KS_VAL_OPTIONS + 2 * (size_t)words);
+  const u32 n_new = S.out_counts[0], n_unsched = S.out_counts[1];
+  const bool expect = (d.flags & KS_VAL_F_EXPECT_REPLACEMENT) != 0;
+  u32 why = KS_VAL_WHY_VALID;
+  if ((d.flags & KS_VAL_F_BLOCKED) || n_unsched > 0) why = KS_VAL_WHY_NOT_ALL_SCHEDULED;      // helpers.go:102-113 / validation.go:122
+  else if (n_new == 0) why = expect ? KS_VAL_WHY_NO_NEW_NODE : KS_VAL_WHY_VALID;              // :132-141
+  else if (n_new > 1) why = KS_VAL_WHY_MANY_NODES;                                            // :143
+  else if (!expect) why = KS_VAL_WHY_UNEXPECTED_NODE;                                         // :148
+  const bool subset = why == KS_VAL_WHY_VALID && n_new == 1;      // instanceTypesAreSubset runs (:164): the command lists types, the re-simulation opened exactly one node
+  const u64* mine = options + d.opt_off;
+  u32 n_now = 0, n_missing = 0;
+  for (u32 wbase = 0; wbase < words; wbase += 64) {
+    const u32 w = wbase + lane; u64 now = 0, miss = 0;
+    if (n_new >= 1 && w < P.TW) now = S.n_alive[w];
+    if (subset && w < P.TW) miss = mine[w] & ~now;
+    if (w < words) { row[KS_VAL_OPTIONS + w] = now; row[KS_VAL_OPTIONS + words + w] = miss; }
+    n_now += (u32)__builtin_popcountll(now); n_missing += (u32)__builtin_popcountll(miss);
+  }
+  for (int off = 32; off > 0; off >>= 1) { n_now += __shfl_xor(n_now, off); n_missing += __shfl_xor(n_missing, off); }
+  if (subset && n_missing > 0) why = KS_VAL_WHY_NOT_A_SUBSET;                                 // :164
+  if (lane == 0) {
+    row[KS_VAL_ID] = d.id; row[KS_VAL_VERDICT] = (u64)(why == KS_VAL_WHY_VALID ? KS_VAL_VALID : KS_VAL_INVALID) | ((u64)why << 8);
+    row[KS_VAL_N_NEW] = n_new; row[KS_VAL_N_UNSCHEDULED] = n_unsched; row[KS_VAL_N_MAPPED] = d.n_mapped; row[KS_VAL_N_OPTIONS] = n_now; row[KS_VAL_N_MISSING] = n_missing; row[7] = 0;
+  }
+}
+
+// every refusal of ks_validate_commands*: before any device work (`st` is opened by it)
+static int validate_check(BatchStage& st, ks_dev_problem* const* ds, u32 n, const uint64_t* ids, const ks_validate_inputs* in, u32 words) {
+  if (!ds || !ids || !in || !in->flags || !in->n_mapped) return fail(KS_ERR_INVALID, "null argument");
+  TRY(BatchStage::not_null(ds, n));
+  return st.open(ds, n, nullptr, false, [&](u32 i) {
+    const u32 TW = ds[i]->h.TW, T = ds[i]->h.T;
+    if (TW > words) return fail(KS_ERR_INVALID, "validation row too short");
+    if (ds[i]->h.NMAX < 1) return fail(KS_ERR_INVALID, "problem outside the validation row's layout");
+    if (in->flags[i] & ~(uint32_t)KS_VAL_F_ALL) return fail(KS_ERR_INVALID, "unknown validation flag bit");
+    if (!(in->flags[i] & KS_VAL_F_EXPECT_REPLACEMENT)) return (int)KS_OK;
+    if (!in->options) return fail(KS_ERR_INVALID, "null argument");
+    const u64* o = in->options + (size_t)i * words;      // a command may only list types of the catalogue: bit t < T
+    for (u32 w = T / 64; w < words; ++w) if (w * 64 >= T ? o[w] != 0 : (o[w] >> (T % 64)) != 0) return fail(KS_ERR_INVALID, "type index out of range");
+    return (int)KS_OK;
+  });
+}
+// inputs up in one block, one launch, completion: what both entry points do once validate_check has passed
+static int validate_launch(BatchStage& st, const uint64_t* ids, const ks_validate_inputs* in, u32 words, void* d_out) {
+  const u32 n = st.n;
+  const size_t o_desc = st.add<ValDesc>(n), o_opt = st.add<u64>((size_t)n * words);
+  TRY(st.place());
+  for (u32 i = 0; i < n; ++i) {
+    st.h<ValDesc>(o_desc)[i] = ValDesc{ids[i], (u64)i * words, in->flags[i], in->n_mapped[i]};
+    if (in->flags[i] & KS_VAL_F_EXPECT_REPLACEMENT) memcpy(st.h<u64>(o_opt) + (size_t)i * words, in->options + (size_t)i * words, (size_t)words * sizeof(u64));      // (else zero: place() cleared the block)
+  }
+  TRY(st.upload(st.bytes));
+  hipLaunchKernelGGL(ks_validate_commands, dim3(n), dim3(64), 0, st.stream(), st.probs(), st.states(), st.d<const ValDesc>(o_desc), st.d<const u64>(o_opt), (u64*)d_out, words);
+  return st.fetch(st.bytes);      // the buffer is complete when this returns: the caller's own stream may read it
+}
+extern "C" int ks_validate_commands_dev(ks_dev_problem* const* ds, uint32_t n, const uint64_t* ids, const ks_validate_inputs* in, uint32_t words, void* d_out) {
+  if (!n) return KS_OK;
+  if (!d_out) return fail(KS_ERR_INVALID, "null argument");
+  BatchStage st; TRY(validate_check(st, ds, n, ids, in, words));
+  return validate_launch(st, ids, in, words, d_out);
+}
+// The same with the rows brought to the host: ms[0] = inputs up + launch + completion, ms[1] = read-back.
+extern "C" int ks_validate_commands_host(ks_dev_problem* const* ds, uint32_t n, const uint64_t* ids, const ks_validate_inputs* in, uint32_t words, uint64_t* out_rows, double* ms) {
+  if (ms) ms[0] = ms[1] = 0.0;
+  if (!n) return KS_OK;
+  if (!out_rows) return fail(KS_ERR_INVALID, "null argument");
+  BatchStage st; TRY(validate_check(st, ds, n, ids, in, words));
+  const size_t bytes = (size_t)n * KS_VAL_ROW_WORDS(words) * sizeof(u64);
+  TmpDev buf(ds[0]->device); TRY(buf.alloc(bytes));
+  const auto t0 = std::chrono::steady_clock::now();
+  TRY(validate_launch(st, ids, in, words, buf.p));
   const auto t1 = std::chrono::steady_clock::now();
   HIPCHK(hipMemcpy(out_rows, buf.p, bytes, hipMemcpyDeviceToHost));
   if (ms) { ms[0] = std::chrono::duration<double, std::milli>(t1 - t0).count(); ms[1] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count(); }

@@ -766,86 +766,173 @@ struct CmdSnapshot {
     }
   }
 };
-// all the what-ifs of one call: open (derived on the device, else flattened one by one), solve resident, decide on the device, rows back.  ms[5]: open | solve | command kernel | read-back | the host work around them
+// What the command call and the validation call share: the whole-call refusals, the label table, the nodes that leave EVERY what-if, per what-if its own node list and
+// readiness, and the route -- open (derived on the device, else flattened one by one), solve resident.  The handles are closed with the object.
+struct SimBatch {
+  Parsed* P = nullptr; std::shared_ptr<const void> held; const CmdSnapshot* cs = nullptr;
+  std::vector<uint8_t> is_del, seen; std::vector<uint32_t> first, last, off2{0}, cand2; uint32_t del_unready = 0; std::vector<void*> hs;
+  ~SimBatch() { close(); }
+  void close() { for (void*& h : hs) if (h) { ksh_close(h); h = nullptr; } }
+  // KS_ERR_INVALID for an unknown flag bit, a row too short, offsets that do not ascend, a node out of range; then the label table and the deleting nodes.  `call` / `row` word the messages
+  int begin(Parsed* P_, const char* call, const char* row, uint32_t flags, uint32_t n, const uint32_t* off, const uint32_t* nodes, const uint32_t* deleting, uint32_t n_deleting, uint32_t words) {
+    P = P_;
+    const uint32_t known = KS_FLAG_SIMULATION | KS_FLAG_NO_RR | KS_FLAG_ONE_WAVE | KS_FLAG_NO_LEAN | KSH_DERIVE_VOLUMES | KSH_ACTIVE_RESOURCES;
+    if (flags & ~known) return set_err(KS_ERR_INVALID, std::string(call) + ": unknown flag bit");
+    if (!n) return KS_OK;
+    const ksp::Problem& pr = *P->pr; const size_t NN = pr.nodes.size(); const uint32_t TW = ((uint32_t)pr.instance_types.size() + 63) / 64;
+    if (words < TW) return set_err(KS_ERR_INVALID, std::string(row) + " row too short: " + std::to_string(words) + " words for " + std::to_string(pr.instance_types.size()) + " instance types");
+    for (uint32_t i = 0; i < n; ++i) if (off[i + 1] < off[i]) return set_err(KS_ERR_INVALID, "candidate offsets not ascending");
+    if (off[n] && !nodes) return set_err(KS_ERR_INVALID, "null argument");
+    for (uint32_t i = 0; i < off[n]; ++i) if (nodes[i] >= NN) return set_err(KS_ERR_INVALID, "candidate node out of range");
+    for (uint32_t i = 0; i < n_deleting; ++i) if (deleting[i] >= NN) return set_err(KS_ERR_INVALID, "deleting node out of range");
+    // the label table: made by the first command call over this snapshot, kept until events change the nodes
+    { std::lock_guard<std::mutex> g(P->mu); if (!P->cmd_nodes) P->cmd_nodes = std::make_shared<const CmdSnapshot>(pr); held = P->cmd_nodes; }
+    cs = static_cast<const CmdSnapshot*>(held.get());
+    // nodes that leave EVERY what-if: the carrier of the pending pods (a node no provisioner owns) first -- the pending pods head simulateScheduling's batch,
+    // helpers.go:76-79 --, the nodes marked for deletion last (:81-84); a candidate that is itself being deleted is an error, not a simulation (:62-67)
+    is_del.assign(NN, 0); seen.assign(NN, 0);
+    for (uint32_t i = 0; i < n_deleting; ++i) { if (is_del[deleting[i]]) continue; is_del[deleting[i]] = 1; (cs->nodes[deleting[i]].owned ? last : first).push_back(deleting[i]); del_unready += cs->nodes[deleting[i]].unready ? 1u : 0u; }
+    return KS_OK;
+  }
+  bool names_deleting(const uint32_t* nodes, uint32_t count) const { for (uint32_t k = 0; k < count; ++k) if (is_del[nodes[k]]) return true; return false; }
+  // one more what-if: these nodes leave (a node listed twice leaves once; `distinct` sees each once, in order).  True when an owned, in-state node that is not
+  // initialised STAYS: simulateScheduling then reports "not all pods scheduled" (helpers.go:102-113)
+  template <class F> bool add(const uint32_t* nodes, uint32_t count, F&& distinct) {
+    cand2.insert(cand2.end(), first.begin(), first.end());
+    uint32_t gone_unready = del_unready;
+    for (uint32_t k = 0; k < count; ++k) {
+      const uint32_t nd = nodes[k]; cand2.push_back(nd);
+      if (seen[nd]) continue;
+      seen[nd] = 1; gone_unready += cs->nodes[nd].unready ? 1u : 0u; distinct(cs->nodes[nd]);
+    }
+    for (uint32_t k = 0; k < count; ++k) seen[nodes[k]] = 0;
+    cand2.insert(cand2.end(), last.begin(), last.end());
+    off2.push_back((uint32_t)cand2.size());
+    return cs->unready > gone_unready;
+  }
+  uint32_t size() const { return (uint32_t)off2.size() - 1; }
+  // ms[0] open, ms[1] solve.  `rows_name_it_states`: the rows to come carry instance-type requirement states, read through the snapshot's lattice
+  int open_and_solve(uint32_t flags, const int32_t* pod_node, int device, bool rows_name_it_states, double* ms) {
+    using clk = std::chrono::steady_clock; auto since = [](clk::time_point a) { return std::chrono::duration<double, std::milli>(clk::now() - a).count(); };
+    const uint32_t m = size(); hs.assign(m, nullptr);
+    if (cand2.empty()) cand2.push_back(0);
+    auto t0 = clk::now();
+    int rc = ksh_open_whatifs_derived(P, flags, m, off2.data(), cand2.data(), pod_node, device, hs.data());
+    if (rc == KS_ERR_UNSUPPORTED) {      // what scheduler.open_whatifs(derive=None) does: flatten the what-ifs one by one, then make them resident
+      rc = ksh_open_whatifs_parsed(P, flags & ~(uint32_t)KSH_DERIVE_VOLUMES, m, off2.data(), cand2.data(), pod_node, 0, hs.data());
+      // KS_CMD_IT_STATE is spelled out through the snapshot's lattice (ksh_snapshot_it_state): a what-if flattened by itself that needed instance-type states of
+      // its own cannot be read that way -- refused here, before anything is uploaded or launched
+      for (uint32_t k = 0; rows_name_it_states && k < m && rc == KS_OK; ++k) { const ksh::Encoded& e = *((Handle*)hs[k])->enc; if (!(e.shared && e.shared_lattice)) rc = set_err(KS_ERR_UNSUPPORTED, "a what-if carries instance-type requirement states of its own: simulate it through ksh_open_whatifs_parsed and read it through ksh_result_text"); }
+      if (rc == KS_OK) rc = ksh_upload_batch(hs.data(), m, device, 0);
+    }
+    if (rc != KS_OK) { close(); return rc; }
+    if (ms) ms[0] = since(t0);
+    t0 = clk::now();
+    rc = ksh_solve_batch_resident(hs.data(), m, nullptr, nullptr);
+    if (rc != KS_OK) { close(); return rc; }
+    if (ms) ms[1] = since(t0);
+    return KS_OK;
+  }
+};
+// all the what-ifs of one call: open, solve resident, decide on the device, rows back.  ms[5]: open | solve | command kernel | read-back | the host work around them
 int commands_over(Parsed* P, uint32_t flags, uint32_t n, const uint32_t* cand_off, const uint32_t* cand, const int32_t* pod_node, const uint32_t* deleting, uint32_t n_deleting,
                   int device, bool same_type, const uint64_t* ids, uint64_t* out_rows, uint32_t words, double* ms) {
   using clk = std::chrono::steady_clock; auto since = [](clk::time_point a) { return std::chrono::duration<double, std::milli>(clk::now() - a).count(); };
   if (ms) ms[0] = ms[1] = ms[2] = ms[3] = ms[4] = 0.0;
   if (!P || (n && (!cand_off || !out_rows)) || (n_deleting && !deleting)) return set_err(KS_ERR_INVALID, "null argument");
-  const uint32_t known = KS_FLAG_SIMULATION | KS_FLAG_NO_RR | KS_FLAG_ONE_WAVE | KS_FLAG_NO_LEAN | KSH_DERIVE_VOLUMES | KSH_ACTIVE_RESOURCES;
-  if (flags & ~known) return set_err(KS_ERR_INVALID, "consolidation commands: unknown flag bit");
-  if (!n) return KS_OK;
-  const ksp::Problem& pr = *P->pr; const size_t NN = pr.nodes.size(); const uint32_t TW = ((uint32_t)pr.instance_types.size() + 63) / 64;
-  if (words < TW) return set_err(KS_ERR_INVALID, "command row too short: " + std::to_string(words) + " words for " + std::to_string(pr.instance_types.size()) + " instance types");
-  for (uint32_t i = 0; i < n; ++i) if (cand_off[i + 1] < cand_off[i]) return set_err(KS_ERR_INVALID, "candidate offsets not ascending");
-  if (cand_off[n] && !cand) return set_err(KS_ERR_INVALID, "null argument");
-  for (uint32_t i = 0; i < cand_off[n]; ++i) if (cand[i] >= NN) return set_err(KS_ERR_INVALID, "candidate node out of range");
-  for (uint32_t i = 0; i < n_deleting; ++i) if (deleting[i] >= NN) return set_err(KS_ERR_INVALID, "deleting node out of range");
+  SimBatch B; int rc = B.begin(P, "consolidation commands", "command", flags, n, cand_off, cand, deleting, n_deleting, words);
+  if (rc != KS_OK || !n) return rc;
+  const ksp::Problem& pr = *P->pr;
   const auto t_call = clk::now();
-  std::shared_ptr<const void> held;      // the label table: made by the first command call over this snapshot, kept until events change the nodes
-  { std::lock_guard<std::mutex> g(P->mu); if (!P->cmd_nodes) P->cmd_nodes = std::make_shared<const CmdSnapshot>(pr); held = P->cmd_nodes; }
-  const CmdSnapshot& cs = *static_cast<const CmdSnapshot*>(held.get());
-  // nodes that leave EVERY what-if: the carrier of the pending pods (a node no provisioner owns) first -- the pending pods head simulateScheduling's batch,
-  // helpers.go:76-79 --, the nodes marked for deletion last (:81-84); a candidate that is itself being deleted is an error, not a simulation (:62-67)
-  std::vector<uint8_t> is_del(NN, 0); std::vector<uint32_t> first, last; uint32_t del_unready = 0;
-  for (uint32_t i = 0; i < n_deleting; ++i) { if (is_del[deleting[i]]) continue; is_del[deleting[i]] = 1; (cs.nodes[deleting[i]].owned ? last : first).push_back(deleting[i]); del_unready += cs.nodes[deleting[i]].unready ? 1u : 0u; }
   const size_t W = KS_CMD_ROW_WORDS(words);
-  std::vector<uint32_t> live, off2{0}, cand2; std::vector<uint32_t> cflags; std::vector<double> cprice, tprice; std::vector<uint32_t> toff{0}, tidx; std::vector<uint64_t> lids;
-  std::vector<uint8_t> seen(NN, 0);
+  std::vector<uint32_t> live; std::vector<uint32_t> cflags; std::vector<double> cprice, tprice; std::vector<uint32_t> toff{0}, tidx; std::vector<uint64_t> lids;
   for (uint32_t i = 0; i < n; ++i) {
-    bool refused = false;
-    for (uint32_t k = cand_off[i]; k < cand_off[i + 1]; ++k) if (is_del[cand[k]]) refused = true;
+    const uint32_t* mine = cand + cand_off[i]; const uint32_t count = cand_off[i + 1] - cand_off[i];
     uint64_t* row = out_rows + (size_t)i * W;
-    if (refused) { std::fill(row, row + W, 0ull); row[KS_CMD_ID] = ids ? ids[i] : i; row[KS_CMD_DECISION] = (uint64_t)KS_CMD_ERROR | ((uint64_t)KS_CMD_WHY_DELETING << 8); continue; }
+    if (B.names_deleting(mine, count)) { std::fill(row, row + W, 0ull); row[KS_CMD_ID] = ids ? ids[i] : i; row[KS_CMD_DECISION] = (uint64_t)KS_CMD_ERROR | ((uint64_t)KS_CMD_WHY_DELETING << 8); continue; }
+    for (uint32_t k = 0; k < count; ++k) if (B.cs->nodes[mine[k]].type < 0) return set_err(KS_ERR_INVALID, "candidate node " + pr.nodes[mine[k]].name + " carries no instance type of the snapshot's catalogue");
     live.push_back(i); lids.push_back(ids ? ids[i] : i);
-    cand2.insert(cand2.end(), first.begin(), first.end());
-    uint32_t f = same_type ? KS_CMD_F_SAME_TYPE : 0u, gone_unready = del_unready; bool all_spot = true; double price = 0.0; const size_t t0 = tidx.size();
-    for (uint32_t k = cand_off[i]; k < cand_off[i + 1]; ++k) {
-      const uint32_t nd = cand[k]; cand2.push_back(nd);
-      if (seen[nd]) continue;      // (a node listed twice leaves once)
-      seen[nd] = 1; const CmdNode& c = cs.nodes[nd];
-      gone_unready += c.unready ? 1u : 0u;
-      if (c.type < 0) return set_err(KS_ERR_INVALID, "candidate node " + pr.nodes[nd].name + " carries no instance type of the snapshot's catalogue");
+    uint32_t f = same_type ? KS_CMD_F_SAME_TYPE : 0u; bool all_spot = true; double price = 0.0; const size_t t0 = tidx.size();
+    const bool blocked = B.add(mine, count, [&](const CmdNode& c) {
       all_spot = all_spot && c.spot;
       if (c.has_price) price += c.price; else f |= KS_CMD_F_PRICE_ERROR;      // getNodePrices, consolidation.go:277-287: summed in candidate order
       size_t at = t0; while (at < tidx.size() && tidx[at] != (uint32_t)c.type) ++at;
       if (at == tidx.size()) { tidx.push_back((uint32_t)c.type); tprice.push_back(c.has_price ? c.price : -1.0); }      // (-1: no candidate of the type has an offering yet)
       else if (c.has_price && (tprice[at] < 0.0 || c.price < tprice[at])) tprice[at] = c.price;
-    }
-    for (uint32_t k = cand_off[i]; k < cand_off[i + 1]; ++k) seen[cand[k]] = 0;
+    });
     for (size_t at = t0; at < tprice.size(); ++at) if (tprice[at] < 0.0) tprice[at] = 0.0;      // the Go map miss of multinodeconsolidation.go:150-158
     if (all_spot) f |= KS_CMD_F_ALL_SPOT;
-    if (cs.unready > gone_unready) f |= KS_CMD_F_BLOCKED;
-    cand2.insert(cand2.end(), last.begin(), last.end());
-    off2.push_back((uint32_t)cand2.size()); cflags.push_back(f); cprice.push_back(price); toff.push_back((uint32_t)tidx.size());
+    if (blocked) f |= KS_CMD_F_BLOCKED;
+    cflags.push_back(f); cprice.push_back(price); toff.push_back((uint32_t)tidx.size());
   }
   const uint32_t m = (uint32_t)live.size(); if (!m) return KS_OK;
-  if (cand2.empty()) cand2.push_back(0);
-  std::vector<void*> hs(m, nullptr);
-  auto close_all = [&] { for (void* h : hs) if (h) ksh_close(h); };
-  auto t0 = clk::now();
-  int rc = ksh_open_whatifs_derived(P, flags, m, off2.data(), cand2.data(), pod_node, device, hs.data());
-  if (rc == KS_ERR_UNSUPPORTED) {      // what scheduler.open_whatifs(derive=None) does: flatten the what-ifs one by one, then make them resident
-    rc = ksh_open_whatifs_parsed(P, flags & ~(uint32_t)KSH_DERIVE_VOLUMES, m, off2.data(), cand2.data(), pod_node, 0, hs.data());
-    // KS_CMD_IT_STATE is spelled out through the snapshot's lattice (ksh_snapshot_it_state): a what-if flattened by itself that needed instance-type states of
-    // its own cannot be read that way -- refused here, before anything is uploaded or launched
-    for (uint32_t k = 0; k < m && rc == KS_OK; ++k) { const ksh::Encoded& e = *((Handle*)hs[k])->enc; if (!(e.shared && e.shared_lattice)) rc = set_err(KS_ERR_UNSUPPORTED, "a what-if carries instance-type requirement states of its own: simulate it through ksh_open_whatifs_parsed and read it through ksh_result_text"); }
-    if (rc == KS_OK) rc = ksh_upload_batch(hs.data(), m, device, 0);
-  }
-  if (rc != KS_OK) { close_all(); return rc; }
-  if (ms) ms[0] = since(t0);
-  t0 = clk::now();
-  rc = ksh_solve_batch_resident(hs.data(), m, nullptr, nullptr);
-  if (rc != KS_OK) { close_all(); return rc; }
-  if (ms) ms[1] = since(t0);
+  rc = B.open_and_solve(flags, pod_node, device, true, ms);
+  if (rc != KS_OK) return rc;
   ks_command_inputs in{}; in.flags = cflags.data(); in.cand_price = cprice.data(); in.type_off = toff.data(); in.type_idx = tidx.data(); in.type_price = tprice.data();
   std::vector<uint64_t> rows; uint64_t* dst = out_rows;
   if (m != n) { rows.resize((size_t)m * W); dst = rows.data(); }      // (refused candidate sets keep their rows: the live ones are scattered around them)
-  rc = ksh_command_rows(hs.data(), m, lids.data(), &in, words, dst, ms ? ms + 2 : nullptr);
-  close_all();
+  rc = ksh_command_rows(B.hs.data(), m, lids.data(), &in, words, dst, ms ? ms + 2 : nullptr);
+  B.close();
   if (rc != KS_OK) return rc;
   if (m != n) for (uint32_t k = 0; k < m; ++k) std::copy(rows.begin() + (size_t)k * W, rows.begin() + (size_t)(k + 1) * W, out_rows + (size_t)live[k] * W);
   if (ms) ms[4] = since(t_call) - ms[0] - ms[1] - ms[2] - ms[3];      // the host work around the four: the per-what-if inputs, closing the handles
+  return KS_OK;
+}
+// mapNodes (helpers.go:328-337) by reason code: a node of a command is still a candidate iff candidateNodes yields it under consolidation.ShouldDeprovision -- reasons
+// 0 and 10-12 (sortAndFilterCandidates is not applied in validation)
+inline bool still_candidate(uint32_t why) { return why == 0 || (why >= KS_CAND_WHY_DELETING_NODE && why <= KS_CAND_WHY_DO_NOT_EVICT); }
+// Validation.IsValid after the wait (validation.go:84-96) and ValidateCommand (:109-172) for n commands: nomination, mapping and the deleting error on the host; the
+// mapped subsets re-simulated in ONE batch and judged on the device.  ms[5] as commands_over.
+int validate_over(Parsed* P, uint32_t flags, uint32_t n, const uint32_t* node_off, const uint32_t* nodes, const uint32_t* expect, const uint64_t* options, const uint32_t* why,
+                  const uint32_t* node_flags, const int32_t* pod_node, const uint32_t* deleting, uint32_t n_deleting, int device, const uint64_t* ids, uint64_t* out_rows, uint32_t words, double* ms) {
+  using clk = std::chrono::steady_clock; auto since = [](clk::time_point a) { return std::chrono::duration<double, std::milli>(clk::now() - a).count(); };
+  if (ms) ms[0] = ms[1] = ms[2] = ms[3] = ms[4] = 0.0;
+  if (!P || (n && (!node_off || !out_rows || !expect)) || (n_deleting && !deleting)) return set_err(KS_ERR_INVALID, "null argument");
+  SimBatch B; int rc = B.begin(P, "validate commands", "validation", flags, n, node_off, nodes, deleting, n_deleting, words);
+  if (rc != KS_OK || !n) return rc;
+  if (node_off[n] && (!why || !node_flags)) return set_err(KS_ERR_INVALID, "null argument");
+  const uint32_t T = (uint32_t)P->pr->instance_types.size();
+  for (uint32_t i = 0; i < n; ++i) if (expect[i]) {
+    if (!options) return set_err(KS_ERR_INVALID, "null argument");
+    const uint64_t* o = options + (size_t)i * words;      // option bits are indices into THIS snapshot's catalogue
+    for (uint32_t w = T / 64; w < words; ++w) if (w * 64 >= T ? o[w] != 0 : (o[w] >> (T % 64)) != 0) return set_err(KS_ERR_INVALID, "command " + std::to_string(i) + ": type index out of range");
+  }
+  const auto t_call = clk::now();
+  const size_t W = KS_VAL_ROW_WORDS(words);
+  struct HostRow { uint32_t i, verdict, why, n_mapped; };
+  std::vector<HostRow> decided; std::vector<uint32_t> live, vflags, nmapped, mapped; std::vector<uint64_t> lids, lopts;
+  for (uint32_t i = 0; i < n; ++i) {
+    const uint32_t* mine = nodes + node_off[i]; const uint32_t count = node_off[i + 1] - node_off[i];
+    bool nominated = false; mapped.clear();
+    for (uint32_t k = 0; k < count; ++k) { nominated = nominated || (node_flags[mine[k]] & KSH_CAND_NODE_NOMINATED); if (still_candidate(why[mine[k]])) mapped.push_back(mine[k]); }
+    std::sort(mapped.begin(), mapped.end()); mapped.erase(std::unique(mapped.begin(), mapped.end()), mapped.end());      // mapNodes walks the candidates: slot order, each once
+    if (nominated) { decided.push_back({i, KS_VAL_INVALID, KS_VAL_WHY_NOMINATED, 0}); continue; }                          // validation.go:87-91, before the mapping
+    if (mapped.empty()) { decided.push_back({i, KS_VAL_INVALID, KS_VAL_WHY_NO_CANDIDATES, 0}); continue; }                 // :114
+    if (B.names_deleting(mapped.data(), (uint32_t)mapped.size())) { decided.push_back({i, KS_VAL_ERROR, KS_VAL_WHY_DELETING, (uint32_t)mapped.size()}); continue; }      // helpers.go:62-67
+    live.push_back(i); lids.push_back(ids ? ids[i] : i); nmapped.push_back((uint32_t)mapped.size());
+    const bool blocked = B.add(mapped.data(), (uint32_t)mapped.size(), [](const CmdNode&) {});
+    vflags.push_back((blocked ? KS_VAL_F_BLOCKED : 0u) | (expect[i] ? KS_VAL_F_EXPECT_REPLACEMENT : 0u));
+    lopts.resize(lopts.size() + words, 0ull);
+    if (expect[i]) std::copy(options + (size_t)i * words, options + (size_t)(i + 1) * words, lopts.end() - words);
+  }
+  const uint32_t m = (uint32_t)live.size();
+  std::vector<uint64_t> rows((size_t)m * W);
+  if (m) {
+    rc = B.open_and_solve(flags, pod_node, device, false, ms);      // (validation reads no requirement state: the fallback route's instance-type-state refusal does not apply)
+    if (rc != KS_OK) return rc;
+    std::vector<ks_dev_problem*> ds(m); for (uint32_t k = 0; k < m; ++k) ds[k] = ((Handle*)B.hs[k])->dev;
+    ks_validate_inputs in{}; in.flags = vflags.data(); in.n_mapped = nmapped.data(); in.options = lopts.data();
+    rc = ks_validate_commands_host(ds.data(), m, lids.data(), &in, words, rows.data(), ms ? ms + 2 : nullptr);
+    B.close();
+    if (rc != KS_OK) return set_err(rc, ks_last_error());
+  }
+  // nothing was written so far: a refusal leaves the caller's rows as they were
+  for (uint32_t k = 0; k < m; ++k) std::copy(rows.begin() + (size_t)k * W, rows.begin() + (size_t)(k + 1) * W, out_rows + (size_t)live[k] * W);
+  for (const HostRow& h : decided) {
+    uint64_t* row = out_rows + (size_t)h.i * W; std::fill(row, row + W, 0ull);
+    row[KS_VAL_ID] = ids ? ids[h.i] : h.i; row[KS_VAL_VERDICT] = (uint64_t)h.verdict | ((uint64_t)h.why << 8); row[KS_VAL_N_MAPPED] = h.n_mapped;
+  }
+  if (ms) ms[4] = since(t_call) - ms[0] - ms[1] - ms[2] - ms[3];
   return KS_OK;
 }
 }  // namespace
@@ -900,6 +987,59 @@ int ksh_single_node_option(void* parsed, uint32_t flags, const uint32_t* candida
     }
     return KS_OK;
   } catch (const ksh::Unsupported& e) { return set_err(KS_ERR_UNSUPPORTED, e.what()); } catch (const std::exception& e) { return set_err(KS_ERR_INVALID, e.what()); }
+}
+// ---- validation (kshost.h): Validation.IsValid / ValidateCommand over the snapshot as it is NOW, and the two loops built on it ----
+int ksh_validate_commands(void* parsed, uint32_t flags, uint32_t n, const uint32_t* node_off, const uint32_t* nodes, const uint32_t* expect_replacement, const uint64_t* options,
+                          const uint32_t* why, const uint32_t* node_flags, const int32_t* pod_node, const uint32_t* deleting, uint32_t n_deleting, int device,
+                          uint64_t* out_rows, uint32_t words, double* ms) {
+  try { return validate_over((Parsed*)parsed, flags, n, node_off, nodes, expect_replacement, options, why, node_flags, pod_node, deleting, n_deleting, device, nullptr, out_rows, words, ms); }
+  catch (const ksh::Unsupported& e) { return set_err(KS_ERR_UNSUPPORTED, e.what()); } catch (const std::exception& e) { return set_err(KS_ERR_INVALID, e.what()); }
+}
+// SingleNodeConsolidation.ComputeCommand's loop (singlenodeconsolidation.go:54-84) from the candidate AFTER the one whose validation failed: the remaining singletons in
+// one command batch, the deletes and replaces among them in one validation batch, the first valid one in candidate order.
+int ksh_single_node_resume(void* parsed, uint32_t flags, const uint32_t* candidates, uint32_t n, int failed_before, const uint32_t* why, const uint32_t* node_flags, const int32_t* pod_node,
+                           const uint32_t* deleting, uint32_t n_deleting, int device, uint64_t* out_row, uint64_t* out_vrow, uint32_t* out_state, uint32_t words, double* ms) {
+  if (!out_row || !out_vrow || !out_state || (n && !candidates)) return set_err(KS_ERR_INVALID, "null argument");
+  try {
+    const size_t W = KS_CMD_ROW_WORDS(words), VW = KS_VAL_ROW_WORDS(words);
+    if (ms) ms[0] = ms[1] = ms[2] = ms[3] = ms[4] = 0.0;
+    std::vector<uint64_t> rows((size_t)n * W), vrows; std::vector<uint32_t> off(n + 1); for (uint32_t i = 0; i <= n; ++i) off[i] = i;
+    double ms1[5] = {0, 0, 0, 0, 0}, ms2[5] = {0, 0, 0, 0, 0};
+    int rc = commands_over((Parsed*)parsed, flags, n, off.data(), candidates, pod_node, deleting, n_deleting, device, false, nullptr, rows.data(), words, ms1);
+    if (rc != KS_OK) return rc;
+    // the commands the loop would validate (:62-64 passes do-nothing over, :57-60 an error), each a command over its one node
+    std::vector<uint32_t> pos, voff{0}, vnodes, expect; std::vector<uint64_t> vopts, vids;
+    for (uint32_t i = 0; i < n; ++i) {
+      const uint64_t* row = rows.data() + (size_t)i * W; const uint32_t action = (uint32_t)(row[KS_CMD_DECISION] & 0xffu);
+      if (action != KS_CMD_REPLACE && action != KS_CMD_DELETE) continue;
+      pos.push_back(i); vids.push_back(i); vnodes.push_back(candidates[i]); voff.push_back((uint32_t)vnodes.size()); expect.push_back(action == KS_CMD_REPLACE ? 1u : 0u);
+      vopts.insert(vopts.end(), row + KS_CMD_OPTIONS, row + KS_CMD_OPTIONS + words);
+    }
+    const uint32_t m = (uint32_t)pos.size(); vrows.resize((size_t)m * VW);
+    if (m) {
+      rc = validate_over((Parsed*)parsed, flags, m, voff.data(), vnodes.data(), expect.data(), vopts.data(), why, node_flags, pod_node, deleting, n_deleting, device, vids.data(), vrows.data(), words, ms2);
+      if (rc != KS_OK) return rc;
+    }
+    if (ms) for (int k = 0; k < 5; ++k) ms[k] = ms1[k] + ms2[k];
+    std::fill(out_row, out_row + W, 0ull); std::fill(out_vrow, out_vrow + VW, 0ull);
+    bool failed = failed_before != 0;
+    for (uint32_t k = 0; k < m; ++k) {
+      const uint64_t* vrow = vrows.data() + (size_t)k * VW; const uint32_t verdict = (uint32_t)(vrow[KS_VAL_VERDICT] & 0xffu);
+      if (verdict == KS_VAL_ERROR) continue;                       // "validating consolidation": logged, next candidate (:67-70)
+      if (verdict == KS_VAL_INVALID) { failed = true; continue; }  // :71-74
+      std::copy(rows.begin() + (size_t)pos[k] * W, rows.begin() + (size_t)(pos[k] + 1) * W, out_row); std::copy(vrow, vrow + VW, out_vrow);
+      *out_state = 1; return KS_OK;                                // :76-78
+    }
+    *out_state = failed ? 2u : 0u;                                 // :82-85
+    return KS_OK;
+  } catch (const ksh::Unsupported& e) { return set_err(KS_ERR_UNSUPPORTED, e.what()); } catch (const std::exception& e) { return set_err(KS_ERR_INVALID, e.what()); }
+}
+// EmptyNodeConsolidation's own check (emptynodeconsolidation.go:77-87), literally: map the nodes; retry iff a mapped node has pods and is not nominated.
+int ksh_validate_empty_nodes(const uint32_t* nodes, uint32_t n, const uint32_t* why, const uint32_t* n_node_pods, const uint32_t* node_flags, uint32_t* out_retry) {
+  if (!out_retry || (n && (!nodes || !why || !n_node_pods || !node_flags))) return set_err(KS_ERR_INVALID, "null argument");
+  *out_retry = 0;
+  for (uint32_t i = 0; i < n; ++i) if (still_candidate(why[nodes[i]]) && n_node_pods[nodes[i]] != 0 && !(node_flags[nodes[i]] & KSH_CAND_NODE_NOMINATED)) *out_retry = 1;
+  return KS_OK;
 }
 // ---- consolidation candidates (kshost.h): candidateNodes + ShouldDeprovision + sortAndFilterCandidates over a snapshot ----
 }  // extern "C"

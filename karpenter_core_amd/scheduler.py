@@ -777,6 +777,100 @@ def single_node_option(snapshot: "ParsedProblem", pod_node, candidates: Sequence
     return _search_option("ksh_single_node_option", snapshot, pod_node, candidates, words, deleting, device, volumes, active_resources, flags)
 
 
+# ---- consolidation commands validated on the device (include/ksolve.h KS_VAL_*, include/kshost.h ksh_validate_commands) ----
+KS_VAL_F_BLOCKED, KS_VAL_F_EXPECT_REPLACEMENT = 1, 2
+KS_VAL_ID, KS_VAL_VERDICT, KS_VAL_N_NEW, KS_VAL_N_UNSCHEDULED, KS_VAL_N_MAPPED, KS_VAL_N_OPTIONS, KS_VAL_N_MISSING = range(7)
+KS_VAL_OPTIONS = 8
+KS_VAL_INVALID, KS_VAL_VALID, KS_VAL_ERROR = 0, 1, 2
+(KS_VAL_WHY_VALID, KS_VAL_WHY_NOMINATED, KS_VAL_WHY_NO_CANDIDATES, KS_VAL_WHY_DELETING, KS_VAL_WHY_NOT_ALL_SCHEDULED, KS_VAL_WHY_NO_NEW_NODE, KS_VAL_WHY_MANY_NODES,
+ KS_VAL_WHY_UNEXPECTED_NODE, KS_VAL_WHY_NOT_A_SUBSET) = range(9)
+
+
+def validation_row_words(words: int) -> int:
+    """KS_VAL_ROW_WORDS: uint64 words of one validation row whose option masks are `words` wide."""
+    return KS_VAL_OPTIONS + 2 * words
+
+
+def _type_masks(type_sets, words):
+    import numpy as np
+    m = np.zeros((max(1, len(type_sets)), words), dtype=np.uint64)
+    for i, ts in enumerate(type_sets):
+        for t in ts:
+            m[i, t // 64] |= np.uint64(1 << (t % 64))
+    return m
+
+
+def validate_commands(snapshot: "ParsedProblem", pod_node: Optional[Sequence[int]], node_sets: Sequence[Sequence[int]], expect_replacement: Sequence[bool],
+                      type_sets: Sequence[Sequence[int]], why: Sequence[int], node_flags: Sequence[int], words: int, deleting: Sequence[int] = (), device: int = 0,
+                      volumes: bool = False, active_resources: bool = False, flags: int = 0, out=None, node_off=None, options=None):
+    """Validation.IsValid / ValidateCommand for every command in ONE call (kshost.h `ksh_validate_commands`) over the snapshot as it is now: node_sets[i] = the command's
+    nodesToRemove as node slots, type_sets[i] = its replacement's instance-type indices (read where expect_replacement[i]), why / node_flags per node slot
+    (`consolidation_candidates`' why over this snapshot; KSH_CAND_NODE_NOMINATED is read).  Returns (numpy uint64 [n, validation_row_words(words)], the library's split
+    of the call).  `out`: a preallocated array to fill; `node_off` / `options`: raw arrays to pass instead (tests: malformed input)."""
+    import numpy as np
+    kh = libs()[1]
+    n = len(node_sets)
+    off, nodes = _cand_csr(node_sets)
+    if node_off is not None:
+        off = _u32s(node_off)
+    ex = _u32s(1 if e else 0 for e in expect_replacement)
+    opts = np.ascontiguousarray(options) if options is not None else _type_masks(type_sets, words)
+    wy, nf = _u32s(why), _u32s(node_flags)
+    pn, pn_ptr = _pod_node_arg(pod_node)
+    dl = _u32s(deleting)
+    rows = out if out is not None else np.zeros((max(1, n), validation_row_words(words)), dtype=np.uint64)
+    ms = (ctypes.c_double * 5)()
+    kh.ksh_validate_commands.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32] + [ctypes.c_void_p] * 7 + [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int, ctypes.c_void_p,
+                                                                                                                       ctypes.c_uint32, ctypes.POINTER(ctypes.c_double)]
+    rc = kh.ksh_validate_commands(snapshot._p, (KSH_DERIVE_VOLUMES if volumes else 0) | (KSH_ACTIVE_RESOURCES if active_resources else 0) | flags, n, off.ctypes.data, nodes.ctypes.data,
+                                  ex.ctypes.data, opts.ctypes.data, wy.ctypes.data, nf.ctypes.data, pn_ptr, dl.ctypes.data, len(deleting), device, rows.ctypes.data, words, ms)
+    if rc != KS_OK:
+        raise KSolveError(rc, kh.ksh_last_error().decode())
+    return rows[:n], dict(zip(COMMAND_TIMING_KEYS, [float(x) for x in ms]))
+
+
+def decode_validation_row(row, words: int) -> dict:
+    """A validation row as Python values: verdict (True / False / None for the error), why, counts, the re-simulation's options and the command's missing types as indices."""
+    r = [int(x) for x in row]
+    bits = lambda base: [w * 64 + b for w in range(words) for b in range(64) if (r[base + w] >> b) & 1]
+    verdict = r[KS_VAL_VERDICT] & 0xFF
+    return {"id": r[KS_VAL_ID], "valid": None if verdict == KS_VAL_ERROR else verdict == KS_VAL_VALID, "why": (r[KS_VAL_VERDICT] >> 8) & 0xFF, "n_new": r[KS_VAL_N_NEW],
+            "n_unscheduled": r[KS_VAL_N_UNSCHEDULED], "n_mapped": r[KS_VAL_N_MAPPED], "n_options": r[KS_VAL_N_OPTIONS], "n_missing": r[KS_VAL_N_MISSING], "reserved": r[7],
+            "options": bits(KS_VAL_OPTIONS), "missing": bits(KS_VAL_OPTIONS + words)}
+
+
+def single_node_resume(snapshot: "ParsedProblem", pod_node, candidates: Sequence[int], failed_before: bool, why: Sequence[int], node_flags: Sequence[int], words: int,
+                       deleting: Sequence[int] = (), device: int = 0, volumes: bool = False, active_resources: bool = False, flags: int = 0):
+    """The rest of SingleNodeConsolidation.ComputeCommand's loop after a failed validation (kshost.h `ksh_single_node_resume`).  Returns (state: 1 found / 2 retry /
+    0 do-nothing, command row, validation row, timings); row[KS_CMD_ID] = the found candidate's position."""
+    import numpy as np
+    kh = libs()[1]
+    cand, dl, wy, nf = _u32s(candidates), _u32s(deleting), _u32s(why), _u32s(node_flags)
+    pn, pn_ptr = _pod_node_arg(pod_node)
+    row, vrow = np.zeros(command_row_words(words), dtype=np.uint64), np.zeros(validation_row_words(words), dtype=np.uint64)
+    state, ms = ctypes.c_uint32(99), (ctypes.c_double * 5)()
+    kh.ksh_single_node_resume.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                          ctypes.c_uint32, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint32, ctypes.POINTER(ctypes.c_double)]
+    rc = kh.ksh_single_node_resume(snapshot._p, (KSH_DERIVE_VOLUMES if volumes else 0) | (KSH_ACTIVE_RESOURCES if active_resources else 0) | flags, cand.ctypes.data, len(candidates),
+                                   1 if failed_before else 0, wy.ctypes.data, nf.ctypes.data, pn_ptr, dl.ctypes.data, len(deleting), device, row.ctypes.data, vrow.ctypes.data,
+                                   ctypes.byref(state), words, ms)
+    if rc != KS_OK:
+        raise KSolveError(rc, kh.ksh_last_error().decode())
+    return int(state.value), row, vrow, dict(zip(COMMAND_TIMING_KEYS, [float(x) for x in ms]))
+
+
+def validate_empty_nodes(nodes: Sequence[int], why: Sequence[int], n_node_pods: Sequence[int], node_flags: Sequence[int]) -> bool:
+    """EmptyNodeConsolidation's own check (kshost.h `ksh_validate_empty_nodes`, host only): True = retry."""
+    kh = libs()[1]
+    nd, wy, npods, nf = _u32s(nodes), _u32s(why), _u32s(n_node_pods), _u32s(node_flags)
+    retry = ctypes.c_uint32(99)
+    kh.ksh_validate_empty_nodes.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32)]
+    rc = kh.ksh_validate_empty_nodes(nd.ctypes.data, len(nodes), wy.ctypes.data, npods.ctypes.data, nf.ctypes.data, ctypes.byref(retry))
+    if rc != KS_OK:
+        raise KSolveError(rc, kh.ksh_last_error().decode())
+    return bool(retry.value)
+
+
 KSH_CAND_NODE_NOMINATED, KSH_CAND_NODE_DO_NOT_CONSOLIDATE, KSH_CAND_NODE_DO_NOT_CONSOLIDATE_TRUE, KSH_CAND_NODE_DELETION_TIMESTAMP = 1, 2, 4, 8      # kshost.h
 KSH_CAND_POD_DO_NOT_EVICT, KSH_CAND_POD_HAS_DELETION_COST, KSH_CAND_POD_HAS_PRIORITY = 1, 2, 4
 KS_CAND_MAX_KEYS, KS_CAND_MAX_VALUES = 16, 62
