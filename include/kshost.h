@@ -246,7 +246,7 @@ int ksh_single_node_option(void* parsed_snapshot, uint32_t flags, const uint32_t
 /* The rows of handles whose results are on the device (ksh_solve_batch_resident / ksh_solve / ...; derived or not), for a caller that keeps its what-ifs open or
  * shards them itself: ks_consolidation_commands_host (ksolve.h) over handles, the per-what-if inputs built by the caller. */
 int ksh_command_rows(void** handles, uint32_t n, const uint64_t* ids, const ks_command_inputs* in, uint32_t words, uint64_t* out_rows, double* ms /* [2] or NULL */);
-/* Turning a row into strings without a handle: what 0 = requirement key a (KS_CMD_MASK + a), 1 = value b of key a (bit b of that mask; a key encoded over value
+/* Turning a row into strings without a handle: what 0 = requirement key a (KS_CMD_MASK + a), 2 = resource a (KS_REP_NODE_REQ + a), 1 = value b of key a (bit b of that mask; a key encoded over value
  * classes names one member per class, as ksh_name does), 3 = state node a (a candidate index), 4 = instance type a (bit a of the option masks).  Keys and values
  * are the snapshot's flattening's: available once a what-if call flattened it.  NULL when out of range; the strings live as long as the snapshot is neither
  * changed (ksh_env_apply*) nor freed.  A requirement reads: present bit k of row[KS_CMD_PRESENT], complement bit k of its high half, values = the mask's bits,
@@ -363,6 +363,81 @@ typedef struct ksh_candidates_out {
 } ksh_candidates_out;
 int ksh_consolidation_candidates(void* parsed_snapshot, const int32_t* pod_node /* or NULL after ksh_env_apply* */, const uint32_t* deleting, uint32_t n_deleting,
                                  const ksh_candidate_inputs* in, const ksh_pdb_block* pdbs /* or NULL */, int device, ksh_candidates_out* out, double* ms /* [4] or NULL */);
+
+/* ---- candidates of the methods the deprovisioning controller tries BEFORE consolidation (deprovisioning/controller.go:142-162): expiration, drift, emptiness.
+ * ksh_consolidation_candidates' sibling: the snapshot, `pod_node`, `deleting`, the PDB block, the output arrays, ms[4] and reasons 1-7 and 10-13 mean what they mean
+ * there; `method`'s ShouldDeprovision takes the place of 8 and 9, which never occur here (base.prov_consolidation_enabled is not read and may be NULL; the
+ * do-not-consolidate flags are accepted and ignored).  1-7 come before the method's code, in the reference's order (helpers.go:171-249); 10-12 after it.
+ *   14  expiration: the provisioner has no TTLSecondsUntilExpired (detail 0), or `now` is not after creation + ttl (detail 1)          expiration.go:56-58,120-127
+ *   15  drift: drift_enabled == 0 (detail 0), or the node lacks KSH_CAND_NODE_DRIFTED -- the karpenter.sh/voluntary-disruption annotation is absent or not
+ *       "drifted" (detail 1)                                                                                                             drift.go:50-56
+ *   16  emptiness: no TTLSecondsAfterEmpty (detail 0), the node has bound pods (1), no emptiness timestamp annotation (2), the ttl is not reached (3).  An annotation
+ *       that does not parse (KSH_CAND_NODE_EMPTINESS_UNPARSABLE) makes the node a candidate, as in the reference.  Daemonset pods are not bound pods of the snapshot
+ *       (see ksh_consolidation_candidates), so a node that runs only those is empty.                                                    emptiness.go:52-70
+ * Time is exact integer arithmetic, never age_seconds: a node is expired iff now_unix_nanos > node_creation_unix_nanos + ttl * 10^9 in int64 (time.Time.After is
+ * strict: at the expiration time itself the node is not expired), empty long enough iff now > node_emptiness_unix_nanos + ttl * 10^9.  KS_ERR_INVALID for a ttl above
+ * 9 223 372 036 s -- where Go's Duration(ttl) * time.Second wraps -- and for a sum the method needs that would overflow; plus every refusal of
+ * ksh_consolidation_candidates, an unknown method, a ttlSecondsAfterEmpty below -1, UNPARSABLE without HAS_EMPTINESS_TIMESTAMP.  base.node_age_seconds is still read,
+ * for disruptionCost's lifetime factor only; out->base.cost is written as there for 0 and 10-12.
+ * The order.  Expiration: the nodes with code 0 by expiration time ascending, ties by ascending slot (SortCandidates, expiration.go:61-66, executed stably over slot
+ * order: DESIGN.md 7.16).  Drift: the nodes with code 0 by ascending slot (candidateNodes walks a map; slot order is the canonical one).  Nodes with 10-12 are in
+ * candidateNodes' result but ComputeCommand's canBeTerminated test passes them over, so they are not in `order`; out->n_in_result counts codes 0 and 10-12 -- the
+ * controller moves to the next method when it is 0 (controller.go:167-170).  Emptiness: Emptiness.ComputeCommand never calls canBeTerminated, so 10 is not assigned
+ * and 11 / 12 cannot occur (no pods); `order` and `empty` both list the code-0 nodes by ascending slot, which is the whole DELETE command (ksh_emptiness_command).
+ * Under expiration and drift `empty` lists the nodes of `order` without pods.  No host path: without a device, KS_ERR_DEVICE. */
+#define KSH_METHOD_EXPIRATION KS_METHOD_EXPIRATION
+#define KSH_METHOD_DRIFT KS_METHOD_DRIFT
+#define KSH_METHOD_EMPTINESS KS_METHOD_EMPTINESS
+#define KSH_CAND_NODE_HAS_EMPTINESS_TIMESTAMP 16u   /* the karpenter.sh/emptiness-timestamp annotation is present */
+#define KSH_CAND_NODE_EMPTINESS_UNPARSABLE 32u      /* ... and time.Parse(time.RFC3339, ...) refuses it */
+#define KSH_CAND_NODE_DRIFTED 64u                   /* karpenter.sh/voluntary-disruption == "drifted" */
+typedef struct ksh_deprovisioning_inputs {
+  ksh_candidate_inputs base;                      /* node_flags may carry the three bits above */
+  int64_t now_unix_nanos;                         /* clock.Now() */
+  const int64_t* node_creation_unix_nanos;        /* [n_nodes] CreationTimestamp */
+  const int64_t* node_emptiness_unix_nanos;       /* [n_nodes] the parsed annotation; read under HAS_EMPTINESS_TIMESTAMP without UNPARSABLE */
+  const int64_t* prov_ttl_seconds_after_empty;    /* [n_provisioners] -1: nil */
+  uint32_t drift_enabled, pad;                    /* settings.DriftEnabled */
+} ksh_deprovisioning_inputs;
+typedef struct ksh_deprovisioning_out { ksh_candidates_out base; uint32_t n_in_result, pad; } ksh_deprovisioning_out;
+int ksh_deprovisioning_candidates(void* parsed_snapshot, uint32_t method, const int32_t* pod_node /* or NULL after ksh_env_apply* */, const uint32_t* deleting, uint32_t n_deleting,
+                                  const ksh_deprovisioning_inputs* in, const ksh_pdb_block* pdbs /* or NULL */, int device, ksh_deprovisioning_out* out, double* ms /* [4] or NULL */);
+/* Emptiness.ComputeCommand (emptiness.go:73-82), literally; host only, no simulation.  candidates[0 .. n): ksh_deprovisioning_candidates' out->base.order under
+ * KSH_METHOD_EMPTINESS; n_node_pods: its out->base.n_node_pods ([node slots]).  out_nodes[0 .. *out_n_nodes) (room for n): the candidates without pods, in order --
+ * the command's nodesToRemove; *out_action = KS_CMD_DELETE, or KS_CMD_DO_NOTHING when there is none. */
+int ksh_emptiness_command(const uint32_t* candidates, uint32_t n, const uint32_t* n_node_pods, uint32_t* out_action, uint32_t* out_nodes, uint32_t* out_n_nodes);
+
+/* ---- replacement commands with m -> n rows (deprovisioning/expiration.go:75-111, drift.go:64-96): Expiration / Drift.ComputeCommand's simulation and command for n
+ * candidate sets over ONE snapshot.  `flags`, `pod_node`, `deleting`, the route (what-ifs derived on the device, else flattened one by one, solved resident in one
+ * launch) and ms[5] are as for ksh_consolidation_commands ([2] = the two replacement kernels).  Two caller-owned tables come back (layout: ksolve.h KS_REP_*):
+ * out_heads[n][KS_REP_HEAD_WORDS] -- head i answers candidate set i, head[KS_REP_ID] = i -- and out_nodes[cap_nodes][KS_REP_NODE_WORDS(words)], one fixed-size row per
+ * replacement node in what-if order and then new-node order, found through the head's KS_REP_NODE_OFF.  A node row's requirement words decode as a command row's
+ * (ksh_snapshot_name what 0 / 1, ksh_snapshot_it_state*); its KS_REP_NODE_REQ words are the node's resource requests, resource r named by ksh_snapshot_name(what = 2)
+ * -- under KSH_ACTIVE_RESOURCES the active names.  The decision, in the reference's order: (1) a candidate listed in `deleting` -> an error head (KS_CMD_ERROR,
+ * KS_CMD_WHY_DELETING), written here, not simulated; (2) blocked (KS_CMD_F_BLOCKED's rule: helpers.go:106-113 returns `nil, false, nil`) -> delete, n_nodes 0,
+ * KS_REP_BLOCKED; (3) n_new == 0 -> delete; (4) replace with all n_new nodes.  n_unscheduled > 0 is reported and changes nothing (the reference logs it).  No price
+ * stage and no narrowing: the reference applies neither here.
+ * Capacity: *out_total_nodes = the sum of n_nodes; beyond cap_nodes the call still returns KS_OK with every head complete, rows written for the sets that fit entirely,
+ * KS_REP_TRUNCATED on the others and nothing at or beyond cap_nodes touched -- call again with a larger table.  cap_nodes = 0 with out_nodes = NULL is the sizing call.
+ * Whole-call refusals as ksh_consolidation_commands (without the instance-type one: nothing here is priced). */
+int ksh_replacement_commands(void* parsed_snapshot, uint32_t flags, uint32_t n, const uint32_t* cand_off /* [n+1] */, const uint32_t* cand, const int32_t* pod_node /* or NULL after ksh_env_apply */,
+                             const uint32_t* deleting, uint32_t n_deleting, int device, uint64_t* out_heads, uint64_t* out_nodes /* or NULL */, uint64_t cap_nodes, uint64_t* out_total_nodes,
+                             uint32_t words, double* ms /* [5] or NULL */);
+/* ComputeCommand's loop for expiration and drift.  candidates[0 .. n): ksh_deprovisioning_candidates' out->base.order (or any list of node slots); why: its out->base.why
+ * ([node slots]).  The first candidate with why == 0 that is not in `deleting` decides (`continue` for both, drift.go:67-77); that ONE set is simulated and its head, its
+ * node rows (from row 0) and *out_position (its index in `candidates`; out_head[KS_REP_ID] too) come back.  None: the head is all zero (do-nothing), *out_position = -1,
+ * nothing is simulated.  Capacity as above. */
+int ksh_replacement_option(void* parsed_snapshot, uint32_t flags, const uint32_t* candidates, uint32_t n, const uint32_t* why, const int32_t* pod_node, const uint32_t* deleting, uint32_t n_deleting,
+                           int device, uint64_t* out_head /* [KS_REP_HEAD_WORDS] */, uint64_t* out_nodes, uint64_t cap_nodes, uint64_t* out_total_nodes, int32_t* out_position, uint32_t words,
+                           double* ms /* [5] or NULL */);
+/* Diagnostic: how many what-ifs the calls that simulate for the caller -- ksh_consolidation_commands and the searches on it, ksh_validate_commands / ksh_single_node_resume,
+ * ksh_replacement_commands / ksh_replacement_option -- have opened AND solved in this process so far (all threads).  The difference across one call is the number of
+ * simulations it made: ksh_replacement_option adds 1, or 0 when no candidate is eligible; a batch of n live sets adds n. */
+uint64_t ksh_whatifs_simulated(void);
+/* The two tables of handles whose results are on the device, for a caller that keeps its what-ifs open or shards them itself: ks_replacement_commands_host (ksolve.h)
+ * over handles, flags[i] = KS_REP_F_* built by the caller. */
+int ksh_replacement_rows(void** handles, uint32_t n, const uint64_t* ids, const uint32_t* flags, uint32_t words, uint64_t* out_heads, uint64_t* out_nodes, uint64_t cap_nodes,
+                         uint64_t* out_total_nodes, double* ms /* [2] or NULL */);
 
 /* ---- the snapshot kept current by EVENTS ("cached incremental SoA builder fed from state.Cluster") ----
  * Replaces, for the snapshot consolidation simulates over, what the reference does between two passes of the deprovisioner (deprovisioning/controller.go:64,

@@ -469,6 +469,48 @@ int ks_validate_commands_dev(ks_dev_problem* const* ds, uint32_t n, const uint64
  * completion, [1] the read-back, milliseconds. */
 int ks_validate_commands_host(ks_dev_problem* const* ds, uint32_t n, const uint64_t* ids, const ks_validate_inputs* in, uint32_t words, uint64_t* out_rows, double* ms);
 
+/* ---- replacement commands with m -> n rows, decided on the device (deprovisioning/expiration.go:75-111, drift.go:64-96: Expiration / Drift.ComputeCommand after the
+ * candidate has passed canBeTerminated): for problem i, over the result the last ks_solve*_dev of ds[i] left on the device, ONE head of KS_REP_HEAD_WORDS uint64 in
+ * d_heads[n][KS_REP_HEAD_WORDS] and n_nodes rows of KS_REP_NODE_WORDS(words) uint64 in d_nodes[cap_nodes][...], both caller-owned DEVICE buffers of one width each (either
+ * can go through one all-gather).  Two launches on ds[0]'s stream (ks_replacement_heads: one workgroup, the decisions and an exclusive scan for node_off, no atomics;
+ * ks_replacement_nodes: one wave per what-if); both buffers are complete when the call returns.
+ * The decision: KS_REP_F_BLOCKED -> delete with KS_REP_BLOCKED set and n_nodes 0 (simulateScheduling returns `nil, false, nil` when an owned, in-state node that stays is
+ * not initialised, helpers.go:106-113, and ComputeCommand reads len(newNodes) only); n_new == 0 -> delete; else replace with all n_new nodes.  n_unscheduled never
+ * changes the action (the reference only logs it).  No price stage, no narrowing.
+ * Capacity: *out_total_nodes = the sum of n_nodes.  Beyond cap_nodes every head is still complete; node rows are written for the what-ifs whose rows fit entirely below
+ * cap_nodes, the others carry KS_REP_TRUNCATED; no row at or beyond cap_nodes is touched; the call returns KS_OK and the caller calls again with a larger table.
+ * cap_nodes = 0 with a NULL node table is the sizing call.
+ * Refusals (KS_ERR_INVALID, nothing launched): a null array, a batch over two devices, words < ceil(T/64), K > KS_MAX_KEYS, R > KS_MAX_RES, an unknown flag bit. */
+#define KS_REP_F_BLOCKED 1u          /* input flag: as KS_CMD_F_BLOCKED */
+#define KS_REP_HEAD_WORDS 8
+#define KS_REP_ID 0                  /* ids[i] */
+#define KS_REP_DECISION 1            /* action (KS_CMD_DO_NOTHING / _DELETE / _REPLACE / _ERROR) | why << 8 (KS_CMD_WHY_DELETING, written by libkshost only) | flags << 16 */
+#define KS_REP_N_NEW 2               /* as the simulation counted it */
+#define KS_REP_N_UNSCHEDULED 3
+#define KS_REP_N_NODES 4             /* the command's replacement count: 0 for a delete, a blocked set and an error */
+#define KS_REP_NODE_OFF 5            /* index of its first row in the node table */
+#define KS_REP_N_OPTIONS 6           /* the sum over its nodes of popcount(options) */
+                                     /* word 7: reserved, zero */
+#define KS_REP_BLOCKED 1u            /* flags (KS_REP_DECISION >> 16) */
+#define KS_REP_TRUNCATED 2u
+/* the node row: words of uint64 */
+#define KS_REP_NODE_ID 0             /* (uint32) what-if id | node index << 32: what-if order, then new-node order */
+#define KS_REP_NODE_PRESENT 1        /* the node's Requirements: present | complement << 32 */
+#define KS_REP_NODE_IT_STATE 2
+#define KS_REP_NODE_N_OPTIONS 3      /* popcount of its InstanceTypeOptions */
+#define KS_REP_NODE_REQMASK 4        /* bit r: resource r is in the node's Requests */
+#define KS_REP_NODE_MASK 5           /* [KS_MAX_KEYS] value masks, layout and meaning of KS_CMD_MASK */
+#define KS_REP_NODE_BOUNDS 37        /* [KS_MAX_KEYS] as KS_CMD_BOUNDS */
+#define KS_REP_NODE_REQ 69           /* [KS_MAX_RES] the node's resource requests (int64 milli-units, zero beyond R): what ToMachine needs */
+#define KS_REP_NODE_OPTIONS 85       /* [words] InstanceTypeOptions */
+#define KS_REP_NODE_WORDS(words) (KS_REP_NODE_OPTIONS + (size_t)(words))
+int ks_replacement_commands_dev(ks_dev_problem* const* ds, uint32_t n, const uint64_t* ids, const uint32_t* flags /* [n] KS_REP_F_* */, uint32_t words, void* d_heads, void* d_nodes,
+                                uint64_t cap_nodes, uint64_t* out_total_nodes);
+/* The same with both tables brought to HOST memory; of out_nodes only the rows that were written are touched.  ms (may be NULL): [0] inputs up + launches + completion,
+ * [1] the read-back, milliseconds. */
+int ks_replacement_commands_host(ks_dev_problem* const* ds, uint32_t n, const uint64_t* ids, const uint32_t* flags, uint32_t words, uint64_t* out_heads, uint64_t* out_nodes,
+                                 uint64_t cap_nodes, uint64_t* out_total_nodes, double* ms);
+
 /* ---- consolidation CANDIDATES, selected and ordered on the device (deprovisioning/helpers.go:124-165,275-287 GetPodEvictionCost / disruptionCost /
  * calculateLifetimeRemaining, pdblimits.go:57-70 CanEvictPods, helpers.go:339-366 canBeTerminated / PodsPreventEviction, consolidation.go:83-104 the sort).
  * Flat arrays in, flat arrays out; three kernels (per pod, per node, rank), no host fallback.
@@ -523,6 +565,49 @@ typedef struct ks_candidates_outputs {
   uint32_t* order; uint32_t* empty; uint32_t* why; int32_t* detail; uint32_t* n_node_pods; double* cost;
 } ks_candidates_outputs;
 int ks_consolidation_candidates_host(const ks_candidates_inputs* in, ks_candidates_outputs* out, int device, double* ms /* [3] or NULL */);
+
+/* ---- candidates of the other deprovisioning methods (deprovisioning/controller.go:142-162 tries them before consolidation): candidateNodes under
+ * Expiration.ShouldDeprovision (expiration.go:56-58,120-127), Drift.ShouldDeprovision (drift.go:50-56) or Emptiness.ShouldDeprovision (emptiness.go:52-70), then the
+ * order their ComputeCommand walks them in.  ks_consolidation_candidates_host's sibling: the same flat arrays (c), refusals and outputs; kernel ks_cand_pods is reused,
+ * ks_deprov_nodes and ks_cand_order_key are the method's own.  No host fallback.
+ * c.node_why carries the steps BEFORE the method's filter only: 0-7 or KS_CAND_WHY_LEFT (anything else is refused); the deletion timestamp arrives as
+ * KS_DEPROV_NODE_DELETION_TIMESTAMP, because canBeTerminated runs after the filter.  c.node_ttl_seconds is the provisioner's TTLSecondsUntilExpired, read by
+ * calculateLifetimeRemaining under every method and by the expiration filter.  Time is exact int64 arithmetic in unix nanoseconds: a node is expired iff
+ * now > creation + ttl * 10^9, empty long enough iff now > emptiness + ttl * 10^9 (time.Time.After is strict).
+ * why: c's codes 1-7, 10-13 and the method's own, with detail = the clause that decided:
+ *   KS_DEPROV_WHY_NOT_EXPIRED  0 no TTLSecondsUntilExpired, 1 not after the expiration time
+ *   KS_DEPROV_WHY_NOT_DRIFTED  0 drift_enabled == 0, 1 no KS_DEPROV_NODE_DRIFTED
+ *   KS_DEPROV_WHY_NOT_EMPTY    0 no TTLSecondsAfterEmpty, 1 the node has pods, 2 no KS_DEPROV_NODE_HAS_EMPTINESS, 3 the ttl is not reached
+ *                              (KS_DEPROV_NODE_EMPTINESS_UNPARSABLE makes the node a candidate, as the reference's parse error does)
+ * Under expiration and drift a node the filter passes gets canBeTerminated's verdict (10-12) as under consolidation; under emptiness it does not
+ * (Emptiness.ComputeCommand never asks).  cost: written for 0 and 10-12, 0.0 otherwise.  n_in_result: the nodes with 0 or 10-12, i.e. len(candidateNodes(...)).
+ * order[0 .. n_candidates): the nodes with code 0 -- expiration: by expiration time ascending, ties by ascending slot (the stable execution of SortCandidates);
+ * drift and emptiness: by ascending slot.  empty: those of them without pods, same order (under emptiness: all of them).
+ * KS_ERR_INVALID beyond c's own: an unknown method or flag bit, UNPARSABLE without HAS_EMPTINESS, a ttl-after-empty below -1, either ttl above
+ * KS_DEPROV_MAX_TTL_SECONDS (Go's Duration(ttl) * time.Second wraps there), a sum the method needs that overflows int64. */
+#define KS_METHOD_EXPIRATION 1u
+#define KS_METHOD_DRIFT 2u
+#define KS_METHOD_EMPTINESS 3u
+#define KS_DEPROV_WHY_NOT_EXPIRED 14
+#define KS_DEPROV_WHY_NOT_DRIFTED 15
+#define KS_DEPROV_WHY_NOT_EMPTY 16
+#define KS_DEPROV_NODE_DELETION_TIMESTAMP 1u
+#define KS_DEPROV_NODE_HAS_EMPTINESS 2u
+#define KS_DEPROV_NODE_EMPTINESS_UNPARSABLE 4u
+#define KS_DEPROV_NODE_DRIFTED 8u
+#define KS_DEPROV_NODE_ALL 15u
+#define KS_DEPROV_MAX_TTL_SECONDS 9223372036ll
+typedef struct ks_deprov_inputs {
+  ks_candidates_inputs c;
+  uint32_t method, drift_enabled;
+  int64_t now_unix_nanos;
+  const uint32_t* node_dflags;                       /* [n_nodes] KS_DEPROV_NODE_* */
+  const int64_t* node_creation_unix_nanos;           /* [n_nodes] */
+  const int64_t* node_emptiness_unix_nanos;          /* [n_nodes] read under HAS_EMPTINESS without UNPARSABLE */
+  const int64_t* node_ttl_seconds_after_empty;       /* [n_nodes] the provisioner's TTLSecondsAfterEmpty, -1: nil */
+} ks_deprov_inputs;
+typedef struct ks_deprov_outputs { ks_candidates_outputs c; uint32_t n_in_result, pad; } ks_deprov_outputs;
+int ks_deprovisioning_candidates_host(const ks_deprov_inputs* in, ks_deprov_outputs* out, int device, double* ms /* [3] or NULL */);
 
 /* Launch-time instance-type pick of the reference's in-memory provider (cloudprovider/fake/cloudprovider.go:79-84: order the machine's
  * InstanceTypeOptions by `Offerings.Available().Requirements(reqs).Cheapest().Price`, types.go:126-145, and take the first): for problem i,

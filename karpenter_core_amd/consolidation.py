@@ -180,6 +180,7 @@ class Command:
     replacement_types: List[str] = field(default_factory=list)                 # replacementNodes[0].InstanceTypeOptions
     replacement_requirements: Dict[str, tuple] = field(default_factory=dict)  # ... .Requirements (canonical tuples)
     error: Optional[str] = None     # computeConsolidation returned an error for this candidate set (consolidation.go:224-228)
+    replacements: List[tuple] = field(default_factory=list)    # Expiration / Drift: EVERY replacement node as (InstanceTypeOptions, canonical Requirements), in new-node order
 
     def canonical(self):
         return (self.action, tuple(self.nodes_to_remove), tuple(self.replacement_types), tuple(sorted(self.replacement_requirements.items())))
@@ -544,6 +545,13 @@ class CandidateInfo:
     consolidation_enabled: bool = True
     ttl_seconds_until_expired: Optional[int] = None
     pdbs: Sequence = ()                                 # model.PodDisruptionBudget
+    # expiration / drift / emptiness (kshost.h `ksh_deprovisioning_inputs`); the defaults leave every consolidation use as it is
+    now_unix_nanos: int = 0                             # clock.Now()
+    node_creation_unix_nanos: Sequence[int] = ()        # per node; missing entries read 0
+    emptiness_unix_nanos: Dict[int, Optional[int]] = field(default_factory=dict)      # node index -> the parsed emptiness timestamp; None: it does not parse
+    drifted: Sequence[int] = ()                         # node indices whose voluntary-disruption annotation says "drifted"
+    drift_enabled: bool = False
+    ttl_seconds_after_empty: Optional[int] = None
 
 
 def _candidates_call(S, parsed, pod_node, snapshot: Snapshot, info: CandidateInfo, device: int = 0):
@@ -582,6 +590,98 @@ def consolidation_candidates_dev(snapshot: Snapshot, info: CandidateInfo, device
                 "cost": [float(x) for x in got["cost"][:n]], "n_node_pods": [int(x) for x in got["n_node_pods"][:n]]}
     finally:
         parsed.close()
+
+
+from .scheduler import KSH_METHOD_EXPIRATION as METHOD_EXPIRATION, KSH_METHOD_DRIFT as METHOD_DRIFT, KSH_METHOD_EMPTINESS as METHOD_EMPTINESS      # noqa: E402  (one definition)
+
+
+def _deprovisioning_call(S, parsed, pod_node, snapshot: Snapshot, info: CandidateInfo, method: int, device: int = 0):
+    """`ksh_deprovisioning_candidates` over a `Snapshot` opened by `_command_snapshot`."""
+    pods = [p for b in snapshot.bound for p in b] + list(snapshot.pending)
+    nn = len(snapshot.nodes) + (1 if snapshot.pending else 0)
+    nf = [0] * nn
+    for i in info.nominated:
+        nf[i] |= S.KSH_CAND_NODE_NOMINATED
+    for i in info.deletion_timestamp:
+        nf[i] |= S.KSH_CAND_NODE_DELETION_TIMESTAMP
+    for i in info.drifted:
+        nf[i] |= S.KSH_CAND_NODE_DRIFTED
+    for i, t in info.emptiness_unix_nanos.items():
+        nf[i] |= S.KSH_CAND_NODE_HAS_EMPTINESS_TIMESTAMP | (S.KSH_CAND_NODE_EMPTINESS_UNPARSABLE if t is None else 0)
+    dne = set(info.do_not_evict)
+    pf = [(S.KSH_CAND_POD_DO_NOT_EVICT if p.uid in dne else 0) | (S.KSH_CAND_POD_HAS_DELETION_COST if p.uid in info.deletion_cost else 0) |
+          (S.KSH_CAND_POD_HAS_PRIORITY if p.uid in info.priority else 0) for p in pods]
+    pad = lambda xs, fill: list(xs) + [fill] * (nn - len(xs))
+    return S.deprovisioning_candidates(parsed, method, pod_node, info.now_unix_nanos, nf, pad(info.node_creation_unix_nanos, 0), pad(info.node_age_seconds, 0.0), pf,
+                                       [float(info.deletion_cost.get(p.uid, 0.0)) for p in pods], [int(info.priority.get(p.uid, 0)) for p in pods], [info.ttl_seconds_until_expired],
+                                       [info.ttl_seconds_after_empty], [info.emptiness_unix_nanos.get(i) or 0 for i in range(nn)], drift_enabled=info.drift_enabled, pdbs=info.pdbs,
+                                       deleting=[int(j) for j in snapshot.deleting], device=device)
+
+
+def deprovisioning_candidates_dev(snapshot: Snapshot, info: CandidateInfo, method: int, device: int = 0, timings: Optional[dict] = None) -> dict:
+    """candidateNodes under Expiration / Drift / Emptiness.ShouldDeprovision (`method`: METHOD_*) through `ksh_deprovisioning_candidates`: `consolidation_candidates_dev`'s
+    dict plus "n_in_result".  "order" is what Expiration / Drift.ComputeCommand walk (`replacement_command` takes it as it is); under emptiness it is the whole command."""
+    from . import scheduler as S
+    parsed, pod_node, leaving = _command_snapshot(snapshot)
+    try:
+        got = _deprovisioning_call(S, parsed, pod_node, snapshot, info, method, device)
+        if timings is not None:
+            timings.update(got["ms"])
+        n = len(snapshot.nodes)
+        return {"order": got["order"], "empty": got["empty"], "why": [int(x) for x in got["why"][:n]], "detail": [int(x) for x in got["detail"][:n]],
+                "cost": [float(x) for x in got["cost"][:n]], "n_node_pods": [int(x) for x in got["n_node_pods"][:n]], "n_in_result": got["n_in_result"]}
+    finally:
+        parsed.close()
+
+
+def emptiness_command_dev(snapshot: Snapshot, info: CandidateInfo, device: int = 0) -> Command:
+    """Emptiness: candidates on the device, then Emptiness.ComputeCommand (`ksh_emptiness_command`): every empty node past its ttl deleted in one command."""
+    from . import scheduler as S
+    parsed, pod_node, leaving = _command_snapshot(snapshot)
+    try:
+        got = _deprovisioning_call(S, parsed, pod_node, snapshot, info, METHOD_EMPTINESS, device)
+        action, nodes = S.emptiness_command(got["order"], got["n_node_pods"])
+        return Command(ACTION_DELETE, [snapshot.nodes[i].name for i in nodes]) if action == S.KS_CMD_DELETE else Command()
+    finally:
+        parsed.close()
+
+
+def _replacement_command_dev(snapshot: Snapshot, info: CandidateInfo, method: int, device: int, timings: Optional[dict]) -> Command:
+    from . import scheduler as S
+    parsed, pod_node, leaving = _command_snapshot(snapshot)
+    try:
+        got = _deprovisioning_call(S, parsed, pod_node, snapshot, info, method, device)
+        if got["n_in_result"] == 0:
+            return Command()
+        words = _words(snapshot)
+        head, nodes, _, pos, ms = S.replacement_option(parsed, pod_node, got["order"], got["why"], words, deleting=leaving, device=device)
+        if timings is not None:
+            timings.update(ms)
+        h = S.decode_replacement_head(head)
+        if pos < 0 or h["action"] not in (S.KS_CMD_DELETE, S.KS_CMD_REPLACE):
+            return Command()
+        name = [snapshot.nodes[got["order"][pos]].name]
+        if h["action"] == S.KS_CMD_DELETE:
+            return Command(ACTION_DELETE, name)
+        reps = []
+        for row in nodes[h["node_off"]:h["node_off"] + h["n_nodes"]]:
+            d = S.decode_replacement_node(parsed, row, words)
+            keep = set(d["options"])
+            reps.append(([snapshot.instance_types[t].name for t in snapshot.provisioner.instance_types if t in keep], tuple(sorted(d["requirements"].items()))))
+        return Command(ACTION_REPLACE, name, list(reps[0][0]), dict(reps[0][1]), replacements=reps)
+    finally:
+        parsed.close()
+
+
+def expiration_command_dev(snapshot: Snapshot, info: CandidateInfo, device: int = 0, timings: Optional[dict] = None) -> Command:
+    """Expiration through the C ABI: `ksh_deprovisioning_candidates` (most expired first), then `ksh_replacement_option` -- ONE what-if simulated.  Command.replacements
+    lists every replacement node.  Follows the reference where `replacement_command` does not: an uninitialised node that stays makes the command a plain delete."""
+    return _replacement_command_dev(snapshot, info, METHOD_EXPIRATION, device, timings)
+
+
+def drift_command_dev(snapshot: Snapshot, info: CandidateInfo, device: int = 0, timings: Optional[dict] = None) -> Command:
+    """Drift through the C ABI: one drifted node at a time, in slot order."""
+    return _replacement_command_dev(snapshot, info, METHOD_DRIFT, device, timings)
 
 
 # =====================================================================================================

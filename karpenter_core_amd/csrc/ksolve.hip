@@ -4022,6 +4022,138 @@ extern "C" int ks_validate_commands_host(ks_dev_problem* const* ds, uint32_t n, 
 }
 
 // ------------------------------------------------------------------------------------------------
+// Expiration / Drift.ComputeCommand (deprovisioning/expiration.go:75-111, drift.go:64-96) over results that are still on the device: delete, or replace with EVERY
+// node the simulation opened -- an m -> n command, so the output is two tables (layout: ksolve.h KS_REP_*): one fixed-size head per what-if and one fixed-size row
+// per replacement node, found through the head's node_off.
+//   ks_replacement_heads   ONE workgroup.  Lane t of a tile takes what-if base + t: the decision from out_counts and the descriptor, then node_off by an exclusive
+//                          scan of n_nodes in what-if order -- Hillis-Steele over an LDS tile, the tile's sum carried to the next.  No atomic: the offsets are the same
+//                          every run.  Every lane walks every tile and every scan step, so the barriers are reached together.
+//   ks_replacement_nodes   one wave per what-if, looping over its nodes (the count is loaded from the same address by every lane).  Lane k writes key k, lane r
+//                          resource r, lanes stride over the option words; one popcount reduction per node, reached by all lanes whether or not the rows fit.
+// ------------------------------------------------------------------------------------------------
+#define KS_REP_TILE 256u
+struct RepDesc { u64 id; u32 flags, pad; };
+__global__ __launch_bounds__(256) void ks_replacement_heads(const DevState* states, const RepDesc* descs, u32 n, u64 cap_nodes, u64* heads, u64* total) {
+  __shared__ u64 s_sum[KS_REP_TILE];
+  const u32 tid = threadIdx.x; u64 carry = 0;
+  for (u32 base = 0; base < n; base += KS_REP_TILE) {
+    const u32 i = base + tid; const bool live = i < n;
+    u32 action = KS_CMD_DO_NOTHING, n_new = 0, n_unsched = 0, fl = 0; u64 mine = 0, id = 0;
+    if (live) {
+      const RepDesc d = descs[i]; id = d.id; n_new = states[i].out_counts[0]; n_unsched = states[i].out_counts[1];
+      if (d.flags & KS_REP_F_BLOCKED) { action = KS_CMD_DELETE; fl = KS_REP_BLOCKED; }      // helpers.go:106-113: `nil, false, nil`, and ComputeCommand reads len(newNodes) only
+      else if (n_new == 0) action = KS_CMD_DELETE;
+      else { action = KS_CMD_REPLACE; mine = n_new; }
+    }
+    s_sum[tid] = mine;
+    for (u32 off = 1; off < KS_REP_TILE; off <<= 1) {      // inclusive scan of the tile
+      __syncthreads();
+      const u64 x = tid >= off ? s_sum[tid - off] : 0ull;
+      __syncthreads();
+      s_sum[tid] += x;
+    }
+    __syncthreads();
+    const u64 node_off = carry + s_sum[tid] - mine;
+    carry += s_sum[KS_REP_TILE - 1];
+    __syncthreads();      // (the tile's sum has been read by every lane before the next tile overwrites it)
+    if (live) {
+      if (mine && node_off + mine > cap_nodes) fl |= KS_REP_TRUNCATED;
+      u64* h = heads + (size_t)i * KS_REP_HEAD_WORDS;
+      h[KS_REP_ID] = id; h[KS_REP_DECISION] = (u64)action | ((u64)fl << 16); h[KS_REP_N_NEW] = n_new; h[KS_REP_N_UNSCHEDULED] = n_unsched;
+      h[KS_REP_N_NODES] = mine; h[KS_REP_NODE_OFF] = node_off; h[KS_REP_N_OPTIONS] = 0; h[7] = 0;
+    }
+  }
+  if (tid == 0) *total = carry;
+}
+__global__ __launch_bounds__(64) void ks_replacement_nodes(const DevProb* probs, const DevState* states, u64* heads, u64* nodes, u32 words) {
+  const DevProb& P = probs[blockIdx.x]; const DevState& S = states[blockIdx.x]; const u32 lane = threadIdx.x;
+  u64* head = heads + (size_t)blockIdx.x * KS_REP_HEAD_WORDS;
+  const u32 n_nodes = (u32)head[KS_REP_N_NODES]; const u64 off = head[KS_REP_NODE_OFF], id = head[KS_REP_ID];
+  const bool fits = !((head[KS_REP_DECISION] >> 16) & KS_REP_TRUNCATED);
+  const size_t NW = KS_REP_NODE_OPTIONS + (size_t)words;
+  u32 total = 0;
+  for (u32 j = 0; j < n_nodes; ++j) {
+    u64* row = nodes + (size_t)(off + j) * NW;      // (only dereferenced where the what-if's rows fit below the table's capacity)
+    u32 pc = 0;
+    for (u32 wbase = 0; wbase < words; wbase += 64) {
+      const u32 w = wbase + lane; u64 o = 0;
+      if (w < P.TW) o = S.n_alive[(size_t)j * P.TW + w];
+      if (fits && w < words) row[KS_REP_NODE_OPTIONS + w] = o;
+      pc += (u32)__builtin_popcountll(o);
+    }
+    for (int x = 32; x > 0; x >>= 1) pc += __shfl_xor(pc, x);
+    total += pc;
+    if (fits && lane < KS_MAX_KEYS) {
+      u64 m = 0, b = 0;
+      if (lane < P.K) { m = S.o_mask[(size_t)j * P.K + lane]; b = (u64)(u32)S.o_gt[(size_t)j * P.K + lane] | ((u64)(u32)S.o_lt[(size_t)j * P.K + lane] << 32); }
+      row[KS_REP_NODE_MASK + lane] = m; row[KS_REP_NODE_BOUNDS + lane] = b;
+    }
+    if (fits && lane < KS_MAX_RES) row[KS_REP_NODE_REQ + lane] = lane < P.R ? (u64)S.o_req[(size_t)j * P.R + lane] : 0ull;
+    if (fits && lane == 0) {
+      row[KS_REP_NODE_ID] = (id & 0xFFFFFFFFull) | ((u64)j << 32); row[KS_REP_NODE_PRESENT] = (u64)S.o_present[j] | ((u64)S.o_complement[j] << 32);
+      row[KS_REP_NODE_IT_STATE] = (u64)(u32)S.o_it[j]; row[KS_REP_NODE_N_OPTIONS] = pc; row[KS_REP_NODE_REQMASK] = S.o_reqmask[j];
+    }
+  }
+  if (lane == 0) head[KS_REP_N_OPTIONS] = total;
+}
+// every refusal of ks_replacement_commands*: before any device work (`st` is opened by it)
+static int replacement_check(BatchStage& st, ks_dev_problem* const* ds, u32 n, const uint64_t* ids, const uint32_t* flags, u32 words) {
+  if (!ds || !ids || !flags) return fail(KS_ERR_INVALID, "null argument");
+  TRY(BatchStage::not_null(ds, n));
+  return st.open(ds, n, nullptr, false, [&](u32 i) {
+    if (ds[i]->h.TW > words) return fail(KS_ERR_INVALID, "replacement row too short");
+    if (ds[i]->h.K > KS_MAX_KEYS || ds[i]->h.R > KS_MAX_RES || ds[i]->h.NMAX < 1) return fail(KS_ERR_INVALID, "problem outside the replacement row's layout");
+    if (flags[i] & ~(uint32_t)KS_REP_F_BLOCKED) return fail(KS_ERR_INVALID, "unknown replacement flag bit");
+    return (int)KS_OK;
+  });
+}
+// inputs up, two launches on one stream, completion; *out_total = the sum of n_nodes
+static int replacement_launch(BatchStage& st, const uint64_t* ids, const uint32_t* flags, u32 words, void* d_heads, void* d_nodes, uint64_t cap_nodes, uint64_t* out_total) {
+  const u32 n = st.n;
+  const size_t o_desc = st.add<RepDesc>(n), o_total = st.add<u64>(1);
+  TRY(st.place());
+  for (u32 i = 0; i < n; ++i) st.h<RepDesc>(o_desc)[i] = RepDesc{ids[i], flags[i], 0};
+  TRY(st.upload(o_total));
+  hipLaunchKernelGGL(ks_replacement_heads, dim3(1), dim3(KS_REP_TILE), 0, st.stream(), st.states(), st.d<const RepDesc>(o_desc), n, (u64)cap_nodes, (u64*)d_heads, st.d<u64>(o_total));
+  hipLaunchKernelGGL(ks_replacement_nodes, dim3(n), dim3(64), 0, st.stream(), st.probs(), st.states(), (u64*)d_heads, (u64*)d_nodes, words);
+  TRY(st.fetch(o_total));
+  *out_total = st.h<u64>(o_total)[0];
+  return KS_OK;
+}
+extern "C" int ks_replacement_commands_dev(ks_dev_problem* const* ds, uint32_t n, const uint64_t* ids, const uint32_t* flags, uint32_t words, void* d_heads, void* d_nodes, uint64_t cap_nodes, uint64_t* out_total_nodes) {
+  if (!out_total_nodes) return fail(KS_ERR_INVALID, "null argument");
+  *out_total_nodes = 0;
+  if (!n) return KS_OK;
+  if (!d_heads || (cap_nodes && !d_nodes)) return fail(KS_ERR_INVALID, "null argument");
+  BatchStage st; TRY(replacement_check(st, ds, n, ids, flags, words));
+  return replacement_launch(st, ids, flags, words, d_heads, d_nodes, cap_nodes, out_total_nodes);
+}
+// The same with both tables brought to the host: the heads in full, and the node rows that were written -- a prefix of the table, because node_off ascends: up to
+// the first truncated what-if's node_off.  Nothing beyond that prefix is touched in out_nodes.  ms[0] = inputs up + launches + completion, ms[1] = the read-back.
+extern "C" int ks_replacement_commands_host(ks_dev_problem* const* ds, uint32_t n, const uint64_t* ids, const uint32_t* flags, uint32_t words, uint64_t* out_heads, uint64_t* out_nodes, uint64_t cap_nodes, uint64_t* out_total_nodes, double* ms) {
+  if (ms) ms[0] = ms[1] = 0.0;
+  if (!out_total_nodes) return fail(KS_ERR_INVALID, "null argument");
+  *out_total_nodes = 0;
+  if (!n) return KS_OK;
+  if (!out_heads || (cap_nodes && !out_nodes)) return fail(KS_ERR_INVALID, "null argument");
+  BatchStage st; TRY(replacement_check(st, ds, n, ids, flags, words));
+  const size_t hbytes = (size_t)n * KS_REP_HEAD_WORDS * sizeof(u64), NW = KS_REP_NODE_WORDS(words);
+  TmpDev hbuf(ds[0]->device), nbuf(ds[0]->device); TRY(hbuf.alloc(hbytes)); TRY(nbuf.alloc((size_t)cap_nodes * NW * sizeof(u64)));
+  std::vector<u64> heads((size_t)n * KS_REP_HEAD_WORDS);
+  const auto t0 = std::chrono::steady_clock::now();
+  uint64_t total = 0; TRY(replacement_launch(st, ids, flags, words, hbuf.p, nbuf.p, cap_nodes, &total));
+  const auto t1 = std::chrono::steady_clock::now();
+  HIPCHK(hipMemcpy(heads.data(), hbuf.p, hbytes, hipMemcpyDeviceToHost));
+  uint64_t written = total;
+  for (u32 i = 0; i < n; ++i) if ((heads[(size_t)i * KS_REP_HEAD_WORDS + KS_REP_DECISION] >> 16) & KS_REP_TRUNCATED) { written = heads[(size_t)i * KS_REP_HEAD_WORDS + KS_REP_NODE_OFF]; break; }
+  if (written > cap_nodes) return fail(KS_ERR_INTERNAL, "replacement commands: node rows beyond the table");
+  if (written) HIPCHK(hipMemcpy(out_nodes, nbuf.p, (size_t)written * NW * sizeof(u64), hipMemcpyDeviceToHost));
+  memcpy(out_heads, heads.data(), hbytes); *out_total_nodes = total;
+  if (ms) { ms[0] = std::chrono::duration<double, std::milli>(t1 - t0).count(); ms[1] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count(); }
+  return KS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
 // Consolidation candidates (ksolve.h ks_consolidation_candidates_host): which nodes sortAndFilterCandidates keeps, and in what order.
 //   ks_cand_pods   one lane per pod slot: GetPodEvictionCost (helpers.go:124-146), and the lowest-index PDB with disruptionsAllowed == 0 that matches the pod
 //                  (pdblimits.go:57-70).  The PDB table goes through LDS in tiles -- every lane of a wave reads the same entry, a broadcast --; the pod's own
@@ -4031,6 +4163,10 @@ extern "C" int ks_validate_commands_host(ks_dev_problem* const* ds, uint32_t n, 
 //                  do-not-evict pod (:354-366); the final reason.
 //   ks_cand_order  a counting rank over LDS tiles: rank = candidates with a smaller cost + candidates with an equal cost and a smaller index, i.e. the stable
 //                  sort of consolidation.go:100-102's comparator over ascending index.  Deterministic: no atomics decide a position.
+// The other deprovisioning methods (ksolve.h ks_deprovisioning_candidates_host: expiration.go:56-66,120-127, drift.go:50-56, emptiness.go:52-70) reuse ks_cand_pods and add
+//   ks_deprov_nodes     one lane per node slot: the method's ShouldDeprovision in int64 nanoseconds, then the cost (the same helper as ks_cand_nodes), canBeTerminated
+//                       -- not under emptiness, whose ComputeCommand never calls it --, the final reason and detail, and the sort key (the expiration time; 0 elsewhere).
+//   ks_cand_order_key   ks_cand_order's counting rank on (int64 key, slot) instead of (cost, slot).
 // No product here may be fused into an addition: the pragma below keeps the one multiply and the sums apart whatever the compiler's default is.
 // ------------------------------------------------------------------------------------------------
 #define KS_CAND_BLOCK 256u
@@ -4043,6 +4179,9 @@ struct CandDev {
   const u32* node_why; const double* node_age; const i64* node_ttl; const u32* node_pods_off; const u32* node_pods;
   double* pod_cost; i32* pod_block; u32* node_fl;      // scratch: per pod its eviction cost and blocking PDB (-1: none); per node bit 0 candidate, bit 1 candidate without pods
   u32* out_why; i32* out_detail; u32* out_npods; double* out_cost; u32* out_order; u32* out_empty; u32* counts;
+  // ks_deprov_nodes / ks_cand_order_key only (unset for a consolidation call)
+  u32 method, drift_enabled; i64 now; const u32* node_dflags; const i64* node_creation; const i64* node_emptiness; const i64* node_ttl_empty;
+  i64* node_key;      // scratch: per node its sort key
 };
 __device__ __forceinline__ double cand_clamp(double lo, double v, double hi) { if (v < lo) return lo; if (v > hi) return hi; return v; }      // helpers.go:317-325: two comparisons
 __device__ __forceinline__ double cand_eviction_cost(u32 flags, double dcost, i32 prio) {
@@ -4084,25 +4223,29 @@ __global__ __launch_bounds__(256) void ks_cand_pods(const CandDev c) {
   }
   if (live) { c.pod_cost[pod] = cand_eviction_cost(c.pod_flags[pod], c.pod_dcost[pod], c.pod_prio[pod]); c.pod_block[pod] = blk; }
 }
-__global__ __launch_bounds__(256) void ks_cand_nodes(const CandDev c) {
+// disruptionCost x calculateLifetimeRemaining of node nd's pods [lo, hi), and on the way the first pod a PDB blocks (that PDB) and the first do-not-evict pod
+__device__ __forceinline__ double cand_node_cost(const CandDev& c, u32 nd, u32 lo, u32 hi, i32& blocked_by, i32& dne) {
 #pragma clang fp contract(off)
+  double cost = 0.0;
+  for (u32 i = lo; i < hi; ++i) {
+    const u32 p = c.node_pods[i];
+    cost += c.pod_cost[p];
+    if (blocked_by < 0 && c.pod_block[p] >= 0) blocked_by = c.pod_block[p];
+    if (dne < 0 && (c.pod_flags[p] & KS_CAND_POD_DO_NOT_EVICT)) dne = (i32)p;
+  }
+  const i64 ttl = c.node_ttl[nd];
+  if (ttl >= 0) {      // calculateLifetimeRemaining
+    const double total = (double)ttl, left = total - c.node_age[nd];
+    const double remaining = cand_clamp(0.0, left / total, 1.0);
+    cost = cost * remaining;
+  }
+  return cost;
+}
+__global__ __launch_bounds__(256) void ks_cand_nodes(const CandDev c) {
   const u32 nd = blockIdx.x * KS_CAND_BLOCK + threadIdx.x; if (nd >= c.n_nodes) return;
   u32 why = c.node_why[nd]; const u32 lo = c.node_pods_off[nd], hi = c.node_pods_off[nd + 1];
   double cost = 0.0; i32 blocked_by = -1, dne = -1;
-  if (why == 0 || why == KS_CAND_WHY_DELETING_NODE) {      // the node is in candidateNodes' result: it carries a disruption cost
-    for (u32 i = lo; i < hi; ++i) {
-      const u32 p = c.node_pods[i];
-      cost += c.pod_cost[p];
-      if (blocked_by < 0 && c.pod_block[p] >= 0) blocked_by = c.pod_block[p];
-      if (dne < 0 && (c.pod_flags[p] & KS_CAND_POD_DO_NOT_EVICT)) dne = (i32)p;
-    }
-    const i64 ttl = c.node_ttl[nd];
-    if (ttl >= 0) {      // calculateLifetimeRemaining
-      const double total = (double)ttl, left = total - c.node_age[nd];
-      const double remaining = cand_clamp(0.0, left / total, 1.0);
-      cost = cost * remaining;
-    }
-  }
+  if (why == 0 || why == KS_CAND_WHY_DELETING_NODE) cost = cand_node_cost(c, nd, lo, hi, blocked_by, dne);      // the node is in candidateNodes' result: it carries a disruption cost
   i32 detail = -1;
   if (why == 0) {      // canBeTerminated: the PDBs first, then do-not-evict
     if (blocked_by >= 0) { why = KS_CAND_WHY_PDB; detail = blocked_by; }
@@ -4113,59 +4256,115 @@ __global__ __launch_bounds__(256) void ks_cand_nodes(const CandDev c) {
   if (fl & 1u) atomicAdd(&c.counts[0], 1u);
   if (fl & 2u) atomicAdd(&c.counts[1], 1u);
 }
-__global__ __launch_bounds__(256) void ks_cand_order(const CandDev c) {
-  __shared__ double s_cost[KS_CAND_BLOCK]; __shared__ u32 s_fl[KS_CAND_BLOCK];
+// rank = listed nodes with a smaller key + listed nodes with an equal key and a smaller index: the stable sort of a `key <` comparator over ascending index
+// (for float64 keys -0.0 and +0.0 tie).  Every lane of the block walks every tile, so the two barriers are reached together.
+template <class K> __device__ __forceinline__ void cand_rank(const CandDev& c, const K* key) {
+  __shared__ K s_key[KS_CAND_BLOCK]; __shared__ u32 s_fl[KS_CAND_BLOCK];
   const u32 tid = threadIdx.x, i = blockIdx.x * KS_CAND_BLOCK + tid; const bool live = i < c.n_nodes;
-  const double ci = live ? c.out_cost[i] : 0.0; const u32 fi = live ? c.node_fl[i] : 0u;
+  const K ki = live ? key[i] : (K)0; const u32 fi = live ? c.node_fl[i] : 0u;
   u32 rank = 0, erank = 0;
   for (u32 base = 0; base < c.n_nodes; base += KS_CAND_BLOCK) {
     const u32 cnt = min(KS_CAND_BLOCK, c.n_nodes - base);
     __syncthreads();
-    if (tid < cnt) { s_cost[tid] = c.out_cost[base + tid]; s_fl[tid] = c.node_fl[base + tid]; }
+    if (tid < cnt) { s_key[tid] = key[base + tid]; s_fl[tid] = c.node_fl[base + tid]; }
     __syncthreads();
     for (u32 t = 0; t < cnt; ++t) {
-      const double cj = s_cost[t]; const u32 fj = s_fl[t];
-      const bool before = (cj < ci) || (!(ci < cj) && base + t < i);      // sort.Slice's less, made stable over ascending index
+      const K kj = s_key[t]; const u32 fj = s_fl[t];
+      const bool before = (kj < ki) || (!(ki < kj) && base + t < i);      // sort.Slice's less, made stable over ascending index
       rank += (before && (fj & 1u)) ? 1u : 0u; erank += (before && (fj & 2u)) ? 1u : 0u;
     }
   }
   if (fi & 1u) c.out_order[rank] = i;
   if (fi & 2u) c.out_empty[erank] = i;
 }
+__global__ __launch_bounds__(256) void ks_cand_order(const CandDev c) { cand_rank<double>(c, c.out_cost); }
+__global__ __launch_bounds__(256) void ks_cand_order_key(const CandDev c) { cand_rank<i64>(c, c.node_key); }
+// candidateNodes under Expiration / Drift / Emptiness.ShouldDeprovision.  node_why arrives as 0-7 or 13 (the steps before the method's filter); the deletion
+// timestamp arrives as a flag, because canBeTerminated comes AFTER the filter.  All time arithmetic is int64 nanoseconds; the host has refused what would overflow.
+__global__ __launch_bounds__(256) void ks_deprov_nodes(const CandDev c) {
+  const u32 nd = blockIdx.x * KS_CAND_BLOCK + threadIdx.x; if (nd >= c.n_nodes) return;
+  u32 why = c.node_why[nd]; const u32 lo = c.node_pods_off[nd], hi = c.node_pods_off[nd + 1], df = c.node_dflags[nd];
+  i32 detail = -1; i64 key = 0;
+  if (why == 0) {
+    if (c.method == KS_METHOD_EXPIRATION) {                                         // expiration.go:56-58,120-127
+      const i64 ttl = c.node_ttl[nd];
+      if (ttl < 0) { why = KS_DEPROV_WHY_NOT_EXPIRED; detail = 0; }
+      else { key = c.node_creation[nd] + ttl * 1000000000ll; if (!(c.now > key)) { why = KS_DEPROV_WHY_NOT_EXPIRED; detail = 1; } }      // After() is strict
+    } else if (c.method == KS_METHOD_DRIFT) {                                       // drift.go:50-56
+      if (!c.drift_enabled) { why = KS_DEPROV_WHY_NOT_DRIFTED; detail = 0; }
+      else if (!(df & KS_DEPROV_NODE_DRIFTED)) { why = KS_DEPROV_WHY_NOT_DRIFTED; detail = 1; }
+    } else {                                                                        // emptiness.go:52-70
+      const i64 ttl = c.node_ttl_empty[nd];
+      if (ttl < 0) { why = KS_DEPROV_WHY_NOT_EMPTY; detail = 0; }
+      else if (hi != lo) { why = KS_DEPROV_WHY_NOT_EMPTY; detail = 1; }
+      else if (!(df & KS_DEPROV_NODE_HAS_EMPTINESS)) { why = KS_DEPROV_WHY_NOT_EMPTY; detail = 2; }
+      else if (!(df & KS_DEPROV_NODE_EMPTINESS_UNPARSABLE) && !(c.now > c.node_emptiness[nd] + ttl * 1000000000ll)) { why = KS_DEPROV_WHY_NOT_EMPTY; detail = 3; }
+    }
+  }
+  const bool listed = why == 0;      // in candidateNodes' result: it carries a disruption cost
+  double cost = 0.0; i32 blocked_by = -1, dne = -1;
+  if (listed) cost = cand_node_cost(c, nd, lo, hi, blocked_by, dne);
+  if (listed && c.method != KS_METHOD_EMPTINESS) {      // canBeTerminated (helpers.go:339-352): Emptiness.ComputeCommand does not call it
+    if (df & KS_DEPROV_NODE_DELETION_TIMESTAMP) why = KS_CAND_WHY_DELETING_NODE;
+    else if (blocked_by >= 0) { why = KS_CAND_WHY_PDB; detail = blocked_by; }
+    else if (dne >= 0) { why = KS_CAND_WHY_DO_NOT_EVICT; detail = dne; }
+  }
+  const u32 fl = why == 0 ? (1u | (hi == lo ? 2u : 0u)) : 0u;
+  c.out_why[nd] = why; c.out_detail[nd] = detail; c.out_npods[nd] = hi - lo; c.out_cost[nd] = cost; c.node_fl[nd] = fl; c.node_key[nd] = why == 0 ? key : 0;
+  if (fl & 1u) atomicAdd(&c.counts[0], 1u);
+  if (fl & 2u) atomicAdd(&c.counts[1], 1u);
+  if (listed) atomicAdd(&c.counts[2], 1u);
+}
 
-extern "C" int ks_consolidation_candidates_host(const ks_candidates_inputs* in, ks_candidates_outputs* out, int device, double* ms) {
-  if (ms) ms[0] = ms[1] = ms[2] = 0.0;
-  if (!in || !out) return fail(KS_ERR_INVALID, "null argument");
+// Both candidate calls: every refusal, one block up, the kernels, one block back.  `x` = NULL: consolidation (ks_cand_nodes / ks_cand_order); else `in` == &x->c and the
+// method's own kernels run, and *n_in_result receives the count of nodes candidateNodes returned.
+static int candidates_run(const std::string& what, const ks_candidates_inputs* in, const ks_deprov_inputs* x, ks_candidates_outputs* out, u32* n_in_result, int device, double* ms) {
   const u32 NP = in->n_pods, NN = in->n_nodes, NB = in->n_pdbs, NK = in->n_keys;
-  if (NK > KS_CAND_MAX_KEYS) return fail(KS_ERR_UNSUPPORTED, "consolidation candidates: " + std::to_string(NK) + " selector keys, " + std::to_string(KS_CAND_MAX_KEYS) + " supported");
+  if (NK > KS_CAND_MAX_KEYS) return fail(KS_ERR_UNSUPPORTED, what + std::to_string(NK) + " selector keys, " + std::to_string(KS_CAND_MAX_KEYS) + " supported");
   if ((NP && (!in->pod_node || !in->pod_ns || !in->pod_flags || !in->pod_deletion_cost || !in->pod_priority || (NK && !in->pod_val))) || !in->pdb_req_off ||
       (NB && (!in->pdb_ns || !in->pdb_allowed)) || !in->node_pods_off || (NN && (!in->node_why || !in->node_age_seconds || !in->node_ttl_seconds)) ||
       (NN && (!out->order || !out->empty || !out->why || !out->detail || !out->n_node_pods || !out->cost))) return fail(KS_ERR_INVALID, "null argument");
   // every refusal before any device work: the kernels index with these numbers
-  if (in->pdb_req_off[0] != 0 || in->node_pods_off[0] != 0) return fail(KS_ERR_INVALID, "consolidation candidates: offsets must start at 0");
-  for (u32 b = 0; b < NB; ++b) if (in->pdb_req_off[b + 1] < in->pdb_req_off[b]) return fail(KS_ERR_INVALID, "consolidation candidates: PDB requirement offsets not ascending");
+  if (in->pdb_req_off[0] != 0 || in->node_pods_off[0] != 0) return fail(KS_ERR_INVALID, what + "offsets must start at 0");
+  for (u32 b = 0; b < NB; ++b) if (in->pdb_req_off[b + 1] < in->pdb_req_off[b]) return fail(KS_ERR_INVALID, what + "PDB requirement offsets not ascending");
   const u32 NR = in->pdb_req_off[NB];
   if (NR && (!in->pdb_req_key || !in->pdb_req_mask)) return fail(KS_ERR_INVALID, "null argument");
-  for (u32 r = 0; r < NR; ++r) if (in->pdb_req_key[r] >= NK) return fail(KS_ERR_INVALID, "consolidation candidates: requirement key out of range");
-  for (size_t i = 0; i < (size_t)NK * NP; ++i) if (in->pod_val[i] > 63) return fail(KS_ERR_INVALID, "consolidation candidates: pod value bit above 63");
+  for (u32 r = 0; r < NR; ++r) if (in->pdb_req_key[r] >= NK) return fail(KS_ERR_INVALID, what + "requirement key out of range");
+  for (size_t i = 0; i < (size_t)NK * NP; ++i) if (in->pod_val[i] > 63) return fail(KS_ERR_INVALID, what + "pod value bit above 63");
   for (u32 p = 0; p < NP; ++p) {
-    if (in->pod_flags[p] & ~7u) return fail(KS_ERR_INVALID, "consolidation candidates: unknown pod flag bit");
-    if ((in->pod_flags[p] & KS_CAND_POD_HAS_DELETION_COST) && !std::isfinite(in->pod_deletion_cost[p])) return fail(KS_ERR_INVALID, "consolidation candidates: pod " + std::to_string(p) + ": deletion cost is not finite");
-    if (in->pod_node[p] >= (i32)NN || in->pod_node[p] < -1) return fail(KS_ERR_INVALID, "consolidation candidates: pod_node out of range");
+    if (in->pod_flags[p] & ~7u) return fail(KS_ERR_INVALID, what + "unknown pod flag bit");
+    if ((in->pod_flags[p] & KS_CAND_POD_HAS_DELETION_COST) && !std::isfinite(in->pod_deletion_cost[p])) return fail(KS_ERR_INVALID, what + "pod " + std::to_string(p) + ": deletion cost is not finite");
+    if (in->pod_node[p] >= (i32)NN || in->pod_node[p] < -1) return fail(KS_ERR_INVALID, what + "pod_node out of range");
   }
   for (u32 n = 0; n < NN; ++n) {
-    if (in->node_pods_off[n + 1] < in->node_pods_off[n]) return fail(KS_ERR_INVALID, "consolidation candidates: node pod offsets not ascending");
-    if (in->node_why[n] > KS_CAND_WHY_LEFT || in->node_why[n] == KS_CAND_WHY_PDB || in->node_why[n] == KS_CAND_WHY_DO_NOT_EVICT) return fail(KS_ERR_INVALID, "consolidation candidates: node " + std::to_string(n) + ": reason code not the caller's to give");
-    if (!std::isfinite(in->node_age_seconds[n])) return fail(KS_ERR_INVALID, "consolidation candidates: node " + std::to_string(n) + ": age is not finite");
-    if (in->node_ttl_seconds[n] == 0 || in->node_ttl_seconds[n] < -1) return fail(KS_ERR_INVALID, "consolidation candidates: node " + std::to_string(n) + ": ttl must be positive or -1 (the reference divides by a ttl of 0)");
+    if (in->node_pods_off[n + 1] < in->node_pods_off[n]) return fail(KS_ERR_INVALID, what + "node pod offsets not ascending");
+    if (in->node_why[n] > KS_CAND_WHY_LEFT || in->node_why[n] == KS_CAND_WHY_PDB || in->node_why[n] == KS_CAND_WHY_DO_NOT_EVICT || (x && in->node_why[n] > 7 && in->node_why[n] != KS_CAND_WHY_LEFT)) return fail(KS_ERR_INVALID, what + "node " + std::to_string(n) + ": reason code not the caller's to give");
+    if (!std::isfinite(in->node_age_seconds[n])) return fail(KS_ERR_INVALID, what + "node " + std::to_string(n) + ": age is not finite");
+    if (in->node_ttl_seconds[n] == 0 || in->node_ttl_seconds[n] < -1) return fail(KS_ERR_INVALID, what + "node " + std::to_string(n) + ": ttl must be positive or -1 (the reference divides by a ttl of 0)");
   }
   const u32 NL = in->node_pods_off[NN];
-  if (NL > NP || (NL && !in->node_pods)) return fail(KS_ERR_INVALID, "consolidation candidates: more listed pods than pod slots");
+  if (NL > NP || (NL && !in->node_pods)) return fail(KS_ERR_INVALID, what + "more listed pods than pod slots");
   for (u32 n = 0; n < NN; ++n) for (u32 i = in->node_pods_off[n]; i < in->node_pods_off[n + 1]; ++i) {
     const u32 p = in->node_pods[i];
-    if (p >= NP || (i > in->node_pods_off[n] && p <= in->node_pods[i - 1]) || in->pod_node[p] != (i32)n) return fail(KS_ERR_INVALID, "consolidation candidates: node " + std::to_string(n) + ": pod slots must ascend and be bound to the node");
+    if (p >= NP || (i > in->node_pods_off[n] && p <= in->node_pods[i - 1]) || in->pod_node[p] != (i32)n) return fail(KS_ERR_INVALID, what + "node " + std::to_string(n) + ": pod slots must ascend and be bound to the node");
   }
-  out->n_candidates = out->n_empty = 0;
+  if (x) {      // the method's own inputs: what the int64 arithmetic of ks_deprov_nodes relies on
+    if (x->method < KS_METHOD_EXPIRATION || x->method > KS_METHOD_EMPTINESS) return fail(KS_ERR_INVALID, what + "unknown method " + std::to_string(x->method));
+    if (NN && (!x->node_dflags || !x->node_creation_unix_nanos || !x->node_emptiness_unix_nanos || !x->node_ttl_seconds_after_empty)) return fail(KS_ERR_INVALID, "null argument");
+    for (u32 n = 0; n < NN; ++n) {
+      const u32 df = x->node_dflags[n]; const i64 ttl = in->node_ttl_seconds[n], ttl_e = x->node_ttl_seconds_after_empty[n];
+      if (df & ~(u32)KS_DEPROV_NODE_ALL) return fail(KS_ERR_INVALID, what + "node " + std::to_string(n) + ": unknown flag bit");
+      if ((df & KS_DEPROV_NODE_EMPTINESS_UNPARSABLE) && !(df & KS_DEPROV_NODE_HAS_EMPTINESS)) return fail(KS_ERR_INVALID, what + "node " + std::to_string(n) + ": the emptiness timestamp is flagged unparsable but not present");
+      if (ttl_e < -1) return fail(KS_ERR_INVALID, what + "node " + std::to_string(n) + ": ttlSecondsAfterEmpty must be -1 or not negative");
+      if (ttl > KS_DEPROV_MAX_TTL_SECONDS || ttl_e > KS_DEPROV_MAX_TTL_SECONDS) return fail(KS_ERR_INVALID, what + "node " + std::to_string(n) + ": a ttl above " + std::to_string(KS_DEPROV_MAX_TTL_SECONDS) + " s wraps as a Duration");
+      if (in->node_why[n] != 0) continue;      // the kernel adds only for nodes still in the running
+      i64 sum;
+      if (x->method == KS_METHOD_EXPIRATION && ttl >= 0 && __builtin_add_overflow(x->node_creation_unix_nanos[n], ttl * 1000000000ll, &sum)) return fail(KS_ERR_INVALID, what + "node " + std::to_string(n) + ": creation time + ttl overflows int64 nanoseconds");
+      if (x->method == KS_METHOD_EMPTINESS && ttl_e >= 0 && in->node_pods_off[n + 1] == in->node_pods_off[n] && (df & KS_DEPROV_NODE_HAS_EMPTINESS) && !(df & KS_DEPROV_NODE_EMPTINESS_UNPARSABLE) && __builtin_add_overflow(x->node_emptiness_unix_nanos[n], ttl_e * 1000000000ll, &sum))
+        return fail(KS_ERR_INVALID, what + "node " + std::to_string(n) + ": emptiness time + ttl overflows int64 nanoseconds");
+    }
+  }
+  out->n_candidates = out->n_empty = 0; if (n_in_result) *n_in_result = 0;
   if (!NN) return KS_OK;
   if (ks_device_count() <= 0) return fail(KS_ERR_DEVICE, "no gfx950 (MI355X) device visible; libksolve has no CPU path");
   HIPCHK(hipSetDevice(device));
@@ -4173,16 +4372,18 @@ extern "C" int ks_consolidation_candidates_host(const ks_candidates_inputs* in, 
   size_t bytes = 0; auto seg = [&](size_t n) { const size_t at = bytes; bytes = (bytes + (n ? n : 1) + 15) & ~(size_t)15; return at; };
   const size_t o_ns = seg((size_t)NP * 4), o_fl = seg((size_t)NP * 4), o_dc = seg((size_t)NP * 8), o_pr = seg((size_t)NP * 4), o_val = seg((size_t)NK * NP);
   const size_t o_bns = seg((size_t)NB * 4), o_ball = seg((size_t)NB * 4), o_boff = seg(((size_t)NB + 1) * 4), o_bkey = seg((size_t)NR * 4), o_bmask = seg((size_t)NR * 8);
-  const size_t o_why = seg((size_t)NN * 4), o_age = seg((size_t)NN * 8), o_ttl = seg((size_t)NN * 8), o_noff = seg(((size_t)NN + 1) * 4), o_npods = seg((size_t)NL * 4), o_cnt = seg(16);
+  const size_t o_why = seg((size_t)NN * 4), o_age = seg((size_t)NN * 8), o_ttl = seg((size_t)NN * 8), o_noff = seg(((size_t)NN + 1) * 4), o_npods = seg((size_t)NL * 4);
+  const size_t o_df = seg(x ? (size_t)NN * 4 : 0), o_cre = seg(x ? (size_t)NN * 8 : 0), o_emp = seg(x ? (size_t)NN * 8 : 0), o_ttle = seg(x ? (size_t)NN * 8 : 0), o_cnt = seg(16);
   const size_t up = bytes;
   const size_t r_why = seg((size_t)NN * 4), r_det = seg((size_t)NN * 4), r_np = seg((size_t)NN * 4), r_cost = seg((size_t)NN * 8), r_ord = seg((size_t)NN * 4), r_emp = seg((size_t)NN * 4);
   const size_t down = bytes;
-  const size_t s_cost = seg((size_t)NP * 8), s_blk = seg((size_t)NP * 4), s_nfl = seg((size_t)NN * 4);
+  const size_t s_cost = seg((size_t)NP * 8), s_blk = seg((size_t)NP * 4), s_nfl = seg((size_t)NN * 4), s_key = seg(x ? (size_t)NN * 8 : 0);
   std::vector<u64> host(down / 8 + 1, 0); u8* hb = (u8*)host.data();
   auto put = [&](size_t at, const void* src, size_t n) { if (n) memcpy(hb + at, src, n); };
   put(o_ns, in->pod_ns, (size_t)NP * 4); put(o_fl, in->pod_flags, (size_t)NP * 4); put(o_dc, in->pod_deletion_cost, (size_t)NP * 8); put(o_pr, in->pod_priority, (size_t)NP * 4); put(o_val, in->pod_val, (size_t)NK * NP);
   put(o_bns, in->pdb_ns, (size_t)NB * 4); put(o_ball, in->pdb_allowed, (size_t)NB * 4); put(o_boff, in->pdb_req_off, ((size_t)NB + 1) * 4); put(o_bkey, in->pdb_req_key, (size_t)NR * 4); put(o_bmask, in->pdb_req_mask, (size_t)NR * 8);
   put(o_why, in->node_why, (size_t)NN * 4); put(o_age, in->node_age_seconds, (size_t)NN * 8); put(o_ttl, in->node_ttl_seconds, (size_t)NN * 8); put(o_noff, in->node_pods_off, ((size_t)NN + 1) * 4); put(o_npods, in->node_pods, (size_t)NL * 4);
+  if (x) { put(o_df, x->node_dflags, (size_t)NN * 4); put(o_cre, x->node_creation_unix_nanos, (size_t)NN * 8); put(o_emp, x->node_emptiness_unix_nanos, (size_t)NN * 8); put(o_ttle, x->node_ttl_seconds_after_empty, (size_t)NN * 8); }
   TmpDev buf(device); TRY(buf.alloc(bytes)); u8* db = buf.as<u8>();
   hipStream_t stream = nullptr; TRY(pool().get_stream(device, &stream));
   struct StreamBack { int device; hipStream_t s; ~StreamBack() { pool().put_stream(device, s); } } back{device, stream};
@@ -4197,20 +4398,34 @@ extern "C" int ks_consolidation_candidates_host(const ks_candidates_inputs* in, 
   c.pod_cost = (double*)(db + s_cost); c.pod_block = (i32*)(db + s_blk); c.node_fl = (u32*)(db + s_nfl);
   c.out_why = (u32*)(db + r_why); c.out_detail = (i32*)(db + r_det); c.out_npods = (u32*)(db + r_np); c.out_cost = (double*)(db + r_cost); c.out_order = (u32*)(db + r_ord); c.out_empty = (u32*)(db + r_emp);
   c.counts = (u32*)(db + o_cnt);      // (uploaded as zeros)
+  if (x) {
+    c.method = x->method; c.drift_enabled = x->drift_enabled; c.now = x->now_unix_nanos;
+    c.node_dflags = (const u32*)(db + o_df); c.node_creation = (const i64*)(db + o_cre); c.node_emptiness = (const i64*)(db + o_emp); c.node_ttl_empty = (const i64*)(db + o_ttle); c.node_key = (i64*)(db + s_key);
+  }
   const u32 gn = (NN + KS_CAND_BLOCK - 1) / KS_CAND_BLOCK;
   if (NP) hipLaunchKernelGGL(ks_cand_pods, dim3((NP + KS_CAND_BLOCK - 1) / KS_CAND_BLOCK), dim3(KS_CAND_BLOCK), 0, stream, c);
-  hipLaunchKernelGGL(ks_cand_nodes, dim3(gn), dim3(KS_CAND_BLOCK), 0, stream, c);
-  hipLaunchKernelGGL(ks_cand_order, dim3(gn), dim3(KS_CAND_BLOCK), 0, stream, c);
+  if (x) { hipLaunchKernelGGL(ks_deprov_nodes, dim3(gn), dim3(KS_CAND_BLOCK), 0, stream, c); hipLaunchKernelGGL(ks_cand_order_key, dim3(gn), dim3(KS_CAND_BLOCK), 0, stream, c); }
+  else { hipLaunchKernelGGL(ks_cand_nodes, dim3(gn), dim3(KS_CAND_BLOCK), 0, stream, c); hipLaunchKernelGGL(ks_cand_order, dim3(gn), dim3(KS_CAND_BLOCK), 0, stream, c); }
   HIPCHK(hipStreamSynchronize(stream)); HIPCHK(hipGetLastError());
   const auto t2 = std::chrono::steady_clock::now();
   HIPCHK(hipMemcpy(hb + o_cnt, db + o_cnt, down - o_cnt, hipMemcpyDeviceToHost));
   const u32* cnt = (const u32*)(hb + o_cnt);
-  if (cnt[0] > NN || cnt[1] > cnt[0]) return fail(KS_ERR_INTERNAL, "consolidation candidates: counts out of range");
+  if (cnt[0] > NN || cnt[1] > cnt[0] || cnt[2] > NN || (x && cnt[2] < cnt[0])) return fail(KS_ERR_INTERNAL, what + "counts out of range");
   memcpy(out->why, hb + r_why, (size_t)NN * 4); memcpy(out->detail, hb + r_det, (size_t)NN * 4); memcpy(out->n_node_pods, hb + r_np, (size_t)NN * 4); memcpy(out->cost, hb + r_cost, (size_t)NN * 8);
   memcpy(out->order, hb + r_ord, (size_t)cnt[0] * 4); memcpy(out->empty, hb + r_emp, (size_t)cnt[1] * 4);
-  out->n_candidates = cnt[0]; out->n_empty = cnt[1];
+  out->n_candidates = cnt[0]; out->n_empty = cnt[1]; if (n_in_result) *n_in_result = cnt[2];
   if (ms) { ms[0] = std::chrono::duration<double, std::milli>(t1 - t0).count(); ms[1] = std::chrono::duration<double, std::milli>(t2 - t1).count(); ms[2] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t2).count(); }
   return KS_OK;
+}
+extern "C" int ks_consolidation_candidates_host(const ks_candidates_inputs* in, ks_candidates_outputs* out, int device, double* ms) {
+  if (ms) ms[0] = ms[1] = ms[2] = 0.0;
+  if (!in || !out) return fail(KS_ERR_INVALID, "null argument");
+  return candidates_run("consolidation candidates: ", in, nullptr, out, nullptr, device, ms);
+}
+extern "C" int ks_deprovisioning_candidates_host(const ks_deprov_inputs* in, ks_deprov_outputs* out, int device, double* ms) {
+  if (ms) ms[0] = ms[1] = ms[2] = 0.0;
+  if (!in || !out) return fail(KS_ERR_INVALID, "null argument");
+  return candidates_run("deprovisioning candidates: ", &in->c, in, &out->c, &out->n_in_result, device, ms);
 }
 
 // ------------------------------------------------------------------------------------------------

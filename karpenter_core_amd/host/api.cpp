@@ -745,6 +745,15 @@ int ksh_command_rows(void** hv, uint32_t n, const uint64_t* ids, const ks_comman
   if (rc != KS_OK) return set_err(rc, ks_last_error());
   return KS_OK;
 }
+// The two tables of handles that hold a result on the device: ks_replacement_commands_host for handles.
+int ksh_replacement_rows(void** hv, uint32_t n, const uint64_t* ids, const uint32_t* flags, uint32_t words, uint64_t* out_heads, uint64_t* out_nodes, uint64_t cap_nodes, uint64_t* out_total_nodes, double* ms) {
+  if (n && !hv) return set_err(KS_ERR_INVALID, "null argument");
+  std::vector<ks_dev_problem*> ds(n);
+  for (uint32_t i = 0; i < n; ++i) { Handle* h = (Handle*)hv[i]; if (!h || !h->dev || !h->dev_result) return set_err(KS_ERR_INVALID, "replacement rows before solve"); ds[i] = h->dev; }
+  int rc = ks_replacement_commands_host(ds.data(), n, ids, flags, words, out_heads, out_nodes, cap_nodes, out_total_nodes, ms);
+  if (rc != KS_OK) return set_err(rc, ks_last_error());
+  return KS_OK;
+}
 }  // extern "C"
 // What getNodePrices / filterOutSameType / simulateScheduling's readiness rule read of the snapshot's nodes, once per call
 namespace {
@@ -768,6 +777,7 @@ struct CmdSnapshot {
 };
 // What the command call and the validation call share: the whole-call refusals, the label table, the nodes that leave EVERY what-if, per what-if its own node list and
 // readiness, and the route -- open (derived on the device, else flattened one by one), solve resident.  The handles are closed with the object.
+std::atomic<uint64_t> g_whatifs_simulated{0};      // ksh_whatifs_simulated: what-ifs SimBatch has opened and solved in this process
 struct SimBatch {
   Parsed* P = nullptr; std::shared_ptr<const void> held; const CmdSnapshot* cs = nullptr;
   std::vector<uint8_t> is_del, seen; std::vector<uint32_t> first, last, off2{0}, cand2; uint32_t del_unready = 0; std::vector<void*> hs;
@@ -831,6 +841,7 @@ struct SimBatch {
     rc = ksh_solve_batch_resident(hs.data(), m, nullptr, nullptr);
     if (rc != KS_OK) { close(); return rc; }
     if (ms) ms[1] = since(t0);
+    g_whatifs_simulated += m;
     return KS_OK;
   }
 };
@@ -876,6 +887,44 @@ int commands_over(Parsed* P, uint32_t flags, uint32_t n, const uint32_t* cand_of
   if (rc != KS_OK) return rc;
   if (m != n) for (uint32_t k = 0; k < m; ++k) std::copy(rows.begin() + (size_t)k * W, rows.begin() + (size_t)(k + 1) * W, out_rows + (size_t)live[k] * W);
   if (ms) ms[4] = since(t_call) - ms[0] - ms[1] - ms[2] - ms[3];      // the host work around the four: the per-what-if inputs, closing the handles
+  return KS_OK;
+}
+// Expiration / Drift.ComputeCommand for n candidate sets: open, solve resident, both tables written on the device, read back.  A set that names a deleting node gets an
+// error head here and is not simulated; its node_off is the next simulated set's, so the offsets stay ascending.  ms[5] as commands_over.
+int replacement_over(Parsed* P, uint32_t flags, uint32_t n, const uint32_t* cand_off, const uint32_t* cand, const int32_t* pod_node, const uint32_t* deleting, uint32_t n_deleting,
+                     int device, uint64_t* out_heads, uint64_t* out_nodes, uint64_t cap_nodes, uint64_t* out_total, uint32_t words, double* ms) {
+  using clk = std::chrono::steady_clock; auto since = [](clk::time_point a) { return std::chrono::duration<double, std::milli>(clk::now() - a).count(); };
+  if (ms) ms[0] = ms[1] = ms[2] = ms[3] = ms[4] = 0.0;
+  if (!P || !out_total || (n && (!cand_off || !out_heads)) || (n_deleting && !deleting) || (cap_nodes && !out_nodes)) return set_err(KS_ERR_INVALID, "null argument");
+  SimBatch B; int rc = B.begin(P, "replacement commands", "replacement", flags, n, cand_off, cand, deleting, n_deleting, words);
+  if (rc != KS_OK) return rc;
+  *out_total = 0;
+  if (!n) return KS_OK;
+  const auto t_call = clk::now();
+  std::vector<uint32_t> live, rflags; std::vector<uint64_t> lids;
+  for (uint32_t i = 0; i < n; ++i) {
+    const uint32_t* mine = cand + cand_off[i]; const uint32_t count = cand_off[i + 1] - cand_off[i];
+    if (B.names_deleting(mine, count)) continue;
+    live.push_back(i); lids.push_back(i);
+    rflags.push_back(B.add(mine, count, [](const CmdNode&) {}) ? KS_REP_F_BLOCKED : 0u);
+  }
+  const uint32_t m = (uint32_t)live.size();
+  std::vector<uint64_t> heads((size_t)m * KS_REP_HEAD_WORDS);
+  if (m) {
+    rc = B.open_and_solve(flags, pod_node, device, true, ms);
+    if (rc != KS_OK) return rc;
+    rc = ksh_replacement_rows(B.hs.data(), m, lids.data(), rflags.data(), words, heads.data(), out_nodes, cap_nodes, out_total, ms ? ms + 2 : nullptr);
+    B.close();
+    if (rc != KS_OK) return rc;
+  }
+  uint64_t next_off = *out_total;      // (walking backwards: an error head points at the next simulated set's first row)
+  for (uint32_t i = n, k = m; i-- > 0;) {
+    uint64_t* h = out_heads + (size_t)i * KS_REP_HEAD_WORDS;
+    if (k && live[k - 1] == i) { --k; std::copy(heads.begin() + (size_t)k * KS_REP_HEAD_WORDS, heads.begin() + (size_t)(k + 1) * KS_REP_HEAD_WORDS, h); next_off = h[KS_REP_NODE_OFF]; continue; }
+    std::fill(h, h + KS_REP_HEAD_WORDS, 0ull);
+    h[KS_REP_ID] = i; h[KS_REP_DECISION] = (uint64_t)KS_CMD_ERROR | ((uint64_t)KS_CMD_WHY_DELETING << 8); h[KS_REP_NODE_OFF] = next_off;
+  }
+  if (ms) ms[4] = since(t_call) - ms[0] - ms[1] - ms[2] - ms[3];
   return KS_OK;
 }
 // mapNodes (helpers.go:328-337) by reason code: a node of a command is still a candidate iff candidateNodes yields it under consolidation.ShouldDeprovision -- reasons
@@ -988,6 +1037,34 @@ int ksh_single_node_option(void* parsed, uint32_t flags, const uint32_t* candida
     return KS_OK;
   } catch (const ksh::Unsupported& e) { return set_err(KS_ERR_UNSUPPORTED, e.what()); } catch (const std::exception& e) { return set_err(KS_ERR_INVALID, e.what()); }
 }
+uint64_t ksh_whatifs_simulated(void) { return g_whatifs_simulated.load(); }
+// ---- replacement commands (kshost.h): Expiration / Drift.ComputeCommand's simulation and m -> n command ----
+int ksh_replacement_commands(void* parsed, uint32_t flags, uint32_t n, const uint32_t* cand_off, const uint32_t* cand, const int32_t* pod_node, const uint32_t* deleting, uint32_t n_deleting,
+                             int device, uint64_t* out_heads, uint64_t* out_nodes, uint64_t cap_nodes, uint64_t* out_total_nodes, uint32_t words, double* ms) {
+  try { return replacement_over((Parsed*)parsed, flags, n, cand_off, cand, pod_node, deleting, n_deleting, device, out_heads, out_nodes, cap_nodes, out_total_nodes, words, ms); }
+  catch (const ksh::Unsupported& e) { return set_err(KS_ERR_UNSUPPORTED, e.what()); } catch (const std::exception& e) { return set_err(KS_ERR_INVALID, e.what()); }
+}
+// ComputeCommand's loop (expiration.go:75-111, drift.go:64-96): the first candidate canBeTerminated lets through (why == 0) that is not deleting decides, and only it is
+// simulated -- which one that is is known before any simulation.
+int ksh_replacement_option(void* parsed, uint32_t flags, const uint32_t* candidates, uint32_t n, const uint32_t* why, const int32_t* pod_node, const uint32_t* deleting, uint32_t n_deleting,
+                           int device, uint64_t* out_head, uint64_t* out_nodes, uint64_t cap_nodes, uint64_t* out_total_nodes, int32_t* out_position, uint32_t words, double* ms) {
+  if (!parsed || !out_head || !out_total_nodes || !out_position || (n && (!candidates || !why)) || (n_deleting && !deleting)) return set_err(KS_ERR_INVALID, "null argument");
+  if (ms) ms[0] = ms[1] = ms[2] = ms[3] = ms[4] = 0.0;
+  const size_t NN = ((Parsed*)parsed)->pr->nodes.size();
+  for (uint32_t i = 0; i < n; ++i) if (candidates[i] >= NN) return set_err(KS_ERR_INVALID, "candidate node out of range");
+  for (uint32_t i = 0; i < n_deleting; ++i) if (deleting[i] >= NN) return set_err(KS_ERR_INVALID, "deleting node out of range");
+  std::fill(out_head, out_head + KS_REP_HEAD_WORDS, 0ull); *out_total_nodes = 0; *out_position = -1;
+  for (uint32_t i = 0; i < n; ++i) {
+    if (why[candidates[i]] != 0) continue;                                                             // canBeTerminated said no: `continue`
+    if (std::find(deleting, deleting + n_deleting, candidates[i]) != deleting + n_deleting) continue;  // errCandidateNodeDeleting: "just retry" with the next one
+    const uint32_t off[2] = {0, 1};
+    int rc = ksh_replacement_commands(parsed, flags, 1, off, candidates + i, pod_node, deleting, n_deleting, device, out_head, out_nodes, cap_nodes, out_total_nodes, words, ms);
+    if (rc != KS_OK) return rc;
+    out_head[KS_REP_ID] = i; *out_position = (int32_t)i;
+    return KS_OK;
+  }
+  return KS_OK;
+}
 // ---- validation (kshost.h): Validation.IsValid / ValidateCommand over the snapshot as it is NOW, and the two loops built on it ----
 int ksh_validate_commands(void* parsed, uint32_t flags, uint32_t n, const uint32_t* node_off, const uint32_t* nodes, const uint32_t* expect_replacement, const uint64_t* options,
                           const uint32_t* why, const uint32_t* node_flags, const int32_t* pod_node, const uint32_t* deleting, uint32_t n_deleting, int device,
@@ -1068,10 +1145,15 @@ struct CandSnapshot {
     }
   }
 };
-int candidates_over(Parsed* P, const int32_t* pod_node, const uint32_t* deleting, uint32_t n_deleting, const ksh_candidate_inputs* in, const ksh_pdb_block* pb, int device, ksh_candidates_out* out, double* ms) {
+// `dx` = NULL: consolidation (`in`, codes 8 / 9).  Else `in` == &dx->base and `method`'s ShouldDeprovision takes the place of 8 / 9: the host gives reasons 1-7 and 13 and
+// the flags, the device decides the rest (ks_deprovisioning_candidates_host); *n_in_result = len(candidateNodes(...)).
+int candidates_over(Parsed* P, uint32_t method, const int32_t* pod_node, const uint32_t* deleting, uint32_t n_deleting, const ksh_candidate_inputs* in, const ksh_deprovisioning_inputs* dx,
+                    const ksh_pdb_block* pb, int device, ksh_candidates_out* out, uint32_t* n_in_result, double* ms) {
   using clk = std::chrono::steady_clock; const auto t_call = clk::now();
   if (ms) ms[0] = ms[1] = ms[2] = ms[3] = 0.0;
   if (!P || !in || !out || (n_deleting && !deleting)) return set_err(KS_ERR_INVALID, "null argument");
+  const std::string what = dx ? "deprovisioning candidates" : "consolidation candidates";
+  if (dx && (method < KSH_METHOD_EXPIRATION || method > KSH_METHOD_EMPTINESS)) return set_err(KS_ERR_INVALID, what + ": unknown method " + std::to_string(method));
   // the PDBs first, completely: a malformed block changes and launches nothing
   std::vector<ksp::Pdb> pdbs;
   if (pb) {
@@ -1091,24 +1173,31 @@ int candidates_over(Parsed* P, const int32_t* pod_node, const uint32_t* deleting
   const CandSnapshot& cs = *static_cast<const CandSnapshot*>(held.get());
   const uint32_t NN = (uint32_t)pr.nodes.size(), NP = (uint32_t)pr.pods.size(), NM = (uint32_t)pr.provisioners.size();
   if (in->n_nodes != NN || in->n_pods != NP || in->n_provisioners != NM)
-    return set_err(KS_ERR_INVALID, "consolidation candidates: the input arrays are for " + std::to_string(in->n_nodes) + " nodes / " + std::to_string(in->n_pods) + " pods / " + std::to_string(in->n_provisioners) +
+    return set_err(KS_ERR_INVALID, what + ": the input arrays are for " + std::to_string(in->n_nodes) + " nodes / " + std::to_string(in->n_pods) + " pods / " + std::to_string(in->n_provisioners) +
                                    " provisioners, the snapshot has " + std::to_string(NN) + " / " + std::to_string(NP) + " / " + std::to_string(NM));
   if ((NN && (!in->node_flags || !in->node_age_seconds || !out->order || !out->empty || !out->why || !out->detail || !out->n_node_pods || !out->cost)) ||
-      (NP && (!in->pod_flags || !in->pod_deletion_cost || !in->pod_priority)) || (NM && (!in->prov_consolidation_enabled || !in->prov_ttl_seconds_until_expired))) return set_err(KS_ERR_INVALID, "null argument");
+      (NP && (!in->pod_flags || !in->pod_deletion_cost || !in->pod_priority)) || (NM && ((!dx && !in->prov_consolidation_enabled) || !in->prov_ttl_seconds_until_expired)) ||
+      (dx && ((NN && (!dx->node_creation_unix_nanos || !dx->node_emptiness_unix_nanos)) || (NM && !dx->prov_ttl_seconds_after_empty)))) return set_err(KS_ERR_INVALID, "null argument");
   for (uint32_t i = 0; i < n_deleting; ++i) if (deleting[i] >= NN) return set_err(KS_ERR_INVALID, "deleting node out of range");
   for (uint32_t p = 0; p < NP; ++p) if (bind[p] >= (int32_t)NN || bind[p] < -1) return set_err(KS_ERR_INVALID, "pod_node out of range");
   for (uint32_t n = 0; n < NN; ++n) {
     const uint32_t f = in->node_flags[n];
-    if ((f & ~15u) || ((f & KSH_CAND_NODE_DO_NOT_CONSOLIDATE_TRUE) && !(f & KSH_CAND_NODE_DO_NOT_CONSOLIDATE))) return set_err(KS_ERR_INVALID, "consolidation candidates: node " + std::to_string(n) + ": unknown flag bit");
-    if (!std::isfinite(in->node_age_seconds[n])) return set_err(KS_ERR_INVALID, "consolidation candidates: node " + std::to_string(n) + ": age is not finite");
+    if ((f & KSH_CAND_NODE_EMPTINESS_UNPARSABLE) && !(f & KSH_CAND_NODE_HAS_EMPTINESS_TIMESTAMP) && dx)
+      return set_err(KS_ERR_INVALID, what + ": node " + std::to_string(n) + ": KSH_CAND_NODE_EMPTINESS_UNPARSABLE without KSH_CAND_NODE_HAS_EMPTINESS_TIMESTAMP");
+    if ((f & ~(dx ? 127u : 15u)) || ((f & KSH_CAND_NODE_DO_NOT_CONSOLIDATE_TRUE) && !(f & KSH_CAND_NODE_DO_NOT_CONSOLIDATE))) return set_err(KS_ERR_INVALID, what + ": node " + std::to_string(n) + ": unknown flag bit");
+    if (!std::isfinite(in->node_age_seconds[n])) return set_err(KS_ERR_INVALID, what + ": node " + std::to_string(n) + ": age is not finite");
   }
   for (uint32_t p = 0; p < NP; ++p) {
-    if (in->pod_flags[p] & ~7u) return set_err(KS_ERR_INVALID, "consolidation candidates: pod " + std::to_string(p) + ": unknown flag bit");
-    if ((in->pod_flags[p] & KSH_CAND_POD_HAS_DELETION_COST) && !std::isfinite(in->pod_deletion_cost[p])) return set_err(KS_ERR_INVALID, "consolidation candidates: pod " + std::to_string(p) + ": deletion cost is not finite");
+    if (in->pod_flags[p] & ~7u) return set_err(KS_ERR_INVALID, what + ": pod " + std::to_string(p) + ": unknown flag bit");
+    if ((in->pod_flags[p] & KSH_CAND_POD_HAS_DELETION_COST) && !std::isfinite(in->pod_deletion_cost[p])) return set_err(KS_ERR_INVALID, what + ": pod " + std::to_string(p) + ": deletion cost is not finite");
   }
   for (uint32_t m = 0; m < NM; ++m) {
     const int64_t ttl = in->prov_ttl_seconds_until_expired[m];
-    if (ttl == 0 || ttl < -1) return set_err(KS_ERR_INVALID, "consolidation candidates: provisioner " + pr.provisioners[m].name + ": ttlSecondsUntilExpired " + std::to_string(ttl) + " (the reference divides by a ttl of 0; -1 means none)");
+    if (ttl == 0 || ttl < -1) return set_err(KS_ERR_INVALID, what + ": provisioner " + pr.provisioners[m].name + ": ttlSecondsUntilExpired " + std::to_string(ttl) + " (the reference divides by a ttl of 0; -1 means none)");
+    const int64_t ttl_e = dx ? dx->prov_ttl_seconds_after_empty[m] : -1;
+    if (ttl_e < -1) return set_err(KS_ERR_INVALID, what + ": provisioner " + pr.provisioners[m].name + ": ttlSecondsAfterEmpty " + std::to_string(ttl_e) + " (-1 means none)");
+    if (dx && (ttl > KS_DEPROV_MAX_TTL_SECONDS || ttl_e > KS_DEPROV_MAX_TTL_SECONDS))
+      return set_err(KS_ERR_INVALID, what + ": provisioner " + pr.provisioners[m].name + ": a ttl above " + std::to_string(KS_DEPROV_MAX_TTL_SECONDS) + " s wraps as a Duration (Duration(ttl) * time.Second)");
   }
   // selectors -> (key, allowed-set mask): the keys and values some selector mentions
   std::vector<std::string> keys; std::unordered_map<std::string, uint32_t> kindex; std::vector<std::unordered_map<std::string, uint32_t>> vindex;
@@ -1118,9 +1207,9 @@ int candidates_over(Parsed* P, const int32_t* pod_node, const uint32_t* deleting
     for (auto& kv : b.selector.match_labels) bit_of(key_of(kv.first), kv.second);
     for (auto& x : b.selector.match_exprs) { const uint32_t k = key_of(x.key); for (auto& v : x.values) bit_of(k, v); }
   }
-  if (keys.size() > KS_CAND_MAX_KEYS) return set_err(KS_ERR_UNSUPPORTED, "consolidation candidates: the PDB selectors mention " + std::to_string(keys.size()) + " label keys, " + std::to_string(KS_CAND_MAX_KEYS) + " are supported");
+  if (keys.size() > KS_CAND_MAX_KEYS) return set_err(KS_ERR_UNSUPPORTED, what + ": the PDB selectors mention " + std::to_string(keys.size()) + " label keys, " + std::to_string(KS_CAND_MAX_KEYS) + " are supported");
   for (size_t k = 0; k < keys.size(); ++k) if (vindex[k].size() > KS_CAND_MAX_VALUES)
-    return set_err(KS_ERR_UNSUPPORTED, "consolidation candidates: the PDB selectors mention " + std::to_string(vindex[k].size()) + " values of label key " + keys[k] + ", " + std::to_string(KS_CAND_MAX_VALUES) + " are supported");
+    return set_err(KS_ERR_UNSUPPORTED, what + ": the PDB selectors mention " + std::to_string(vindex[k].size()) + " values of label key " + keys[k] + ", " + std::to_string(KS_CAND_MAX_VALUES) + " are supported");
   const uint32_t NK = (uint32_t)keys.size(), NB = (uint32_t)pdbs.size();
   // namespaces: the bound pods' get ids; a PDB in a namespace no pod has, and a nil selector (LabelSelectorAsSelector(nil) selects nothing), get an id no pod has
   const uint32_t kNoNs = 0xFFFFFFFFu; std::unordered_map<std::string, uint32_t> nsindex;
@@ -1152,18 +1241,26 @@ int candidates_over(Parsed* P, const int32_t* pod_node, const uint32_t* deleting
   }
   // nodes: the reason the host can give (the reference's order), the provisioner's ttl, the pods in ascending slot order
   std::vector<uint8_t> is_del(NN, 0); for (uint32_t i = 0; i < n_deleting; ++i) is_del[deleting[i]] = 1;
-  std::vector<uint32_t> node_why(NN, 0), pods_off(NN + 1, 0), node_pods; std::vector<int64_t> node_ttl(NN, -1);
+  std::vector<uint32_t> node_why(NN, 0), pods_off(NN + 1, 0), node_pods, node_dflags(dx ? NN : 0, 0); std::vector<int64_t> node_ttl(NN, -1), node_ttl_e(dx ? NN : 0, -1);
   for (uint32_t n = 0; n < NN; ++n) {
     const uint32_t f = in->node_flags[n]; uint32_t w = 0;
     if (cs.why[n] == KS_CAND_WHY_LEFT) w = KS_CAND_WHY_LEFT;
     else if (is_del[n]) w = 1;                                                                   // helpers.go:186
     else if (cs.why[n]) w = cs.why[n];                                                           // :190-211
     else if (f & KSH_CAND_NODE_NOMINATED) w = 7;                                                 // :215
-    else if (f & KSH_CAND_NODE_DO_NOT_CONSOLIDATE) w = (f & KSH_CAND_NODE_DO_NOT_CONSOLIDATE_TRUE) ? 8 : 0;      // consolidation.go:108-111: `return val != "true"`
-    else if (!in->prov_consolidation_enabled[cs.prov[n]]) w = 9;                                 // :116-119
-    if (w == 0 && (f & KSH_CAND_NODE_DELETION_TIMESTAMP)) w = KS_CAND_WHY_DELETING_NODE;         // helpers.go:340
-    node_why[n] = w;
-    if ((w == 0 || w == KS_CAND_WHY_DELETING_NODE) && cs.prov[n] >= 0) node_ttl[n] = in->prov_ttl_seconds_until_expired[cs.prov[n]];
+    node_why[n] = w;      // codes 1-7 and 13 are the same under every method
+    if (w != 0) continue;
+    if (dx) {      // the method's ShouldDeprovision and canBeTerminated are the device's: it needs the provisioner's ttls and the node's flags
+      node_dflags[n] = ((f & KSH_CAND_NODE_DELETION_TIMESTAMP) ? KS_DEPROV_NODE_DELETION_TIMESTAMP : 0u) | ((f & KSH_CAND_NODE_HAS_EMPTINESS_TIMESTAMP) ? KS_DEPROV_NODE_HAS_EMPTINESS : 0u) |
+                       ((f & KSH_CAND_NODE_EMPTINESS_UNPARSABLE) ? KS_DEPROV_NODE_EMPTINESS_UNPARSABLE : 0u) | ((f & KSH_CAND_NODE_DRIFTED) ? KS_DEPROV_NODE_DRIFTED : 0u);
+      node_ttl[n] = in->prov_ttl_seconds_until_expired[cs.prov[n]]; node_ttl_e[n] = dx->prov_ttl_seconds_after_empty[cs.prov[n]];
+    } else {       // consolidation.ShouldDeprovision, then the deletion timestamp of canBeTerminated
+      if (f & KSH_CAND_NODE_DO_NOT_CONSOLIDATE) w = (f & KSH_CAND_NODE_DO_NOT_CONSOLIDATE_TRUE) ? 8 : 0;      // consolidation.go:108-111: `return val != "true"`
+      else if (!in->prov_consolidation_enabled[cs.prov[n]]) w = 9;                                           // :116-119
+      if (w == 0 && (f & KSH_CAND_NODE_DELETION_TIMESTAMP)) w = KS_CAND_WHY_DELETING_NODE;                   // helpers.go:340
+      node_why[n] = w;
+      if (w == 0 || w == KS_CAND_WHY_DELETING_NODE) node_ttl[n] = in->prov_ttl_seconds_until_expired[cs.prov[n]];
+    }
   }
   for (uint32_t p = 0; p < NP; ++p) if (bind[p] >= 0) pods_off[(size_t)bind[p] + 1]++;
   for (uint32_t n = 0; n < NN; ++n) pods_off[n + 1] += pods_off[n];
@@ -1176,7 +1273,14 @@ int candidates_over(Parsed* P, const int32_t* pod_node, const uint32_t* deleting
   ks_candidates_outputs ko{}; ko.order = out->order; ko.empty = out->empty; ko.why = out->why; ko.detail = out->detail; ko.n_node_pods = out->n_node_pods; ko.cost = out->cost;
   const double host_ms = std::chrono::duration<double, std::milli>(clk::now() - t_call).count();
   double kms[3] = {0, 0, 0};
-  const int rc = ks_consolidation_candidates_host(&ki, &ko, device, kms);
+  int rc;
+  if (dx) {
+    ks_deprov_inputs di{}; di.c = ki; di.method = method; di.drift_enabled = dx->drift_enabled; di.now_unix_nanos = dx->now_unix_nanos; di.node_dflags = node_dflags.data();
+    di.node_creation_unix_nanos = dx->node_creation_unix_nanos; di.node_emptiness_unix_nanos = dx->node_emptiness_unix_nanos; di.node_ttl_seconds_after_empty = node_ttl_e.data();
+    ks_deprov_outputs dout{}; dout.c = ko;
+    rc = ks_deprovisioning_candidates_host(&di, &dout, device, kms);
+    ko = dout.c; if (n_in_result) *n_in_result = dout.n_in_result;
+  } else rc = ks_consolidation_candidates_host(&ki, &ko, device, kms);
   if (rc != KS_OK) return set_err(rc, ks_last_error());
   out->n_candidates = ko.n_candidates; out->n_empty = ko.n_empty;
   if (ms) { ms[0] = host_ms; ms[1] = kms[0]; ms[2] = kms[1]; ms[3] = kms[2]; }
@@ -1186,8 +1290,27 @@ int candidates_over(Parsed* P, const int32_t* pod_node, const uint32_t* deleting
 extern "C" {
 int ksh_consolidation_candidates(void* parsed, const int32_t* pod_node, const uint32_t* deleting, uint32_t n_deleting, const ksh_candidate_inputs* in, const ksh_pdb_block* pdbs, int device,
                                  ksh_candidates_out* out, double* ms) {
-  try { return candidates_over((Parsed*)parsed, pod_node, deleting, n_deleting, in, pdbs, device, out, ms); }
+  try { return candidates_over((Parsed*)parsed, 0, pod_node, deleting, n_deleting, in, nullptr, pdbs, device, out, nullptr, ms); }
   catch (const ksh::Unsupported& e) { return set_err(KS_ERR_UNSUPPORTED, e.what()); } catch (const std::exception& e) { return set_err(KS_ERR_INVALID, e.what()); }
+}
+// candidateNodes under Expiration / Drift / Emptiness.ShouldDeprovision and the order their ComputeCommand walks (kshost.h)
+int ksh_deprovisioning_candidates(void* parsed, uint32_t method, const int32_t* pod_node, const uint32_t* deleting, uint32_t n_deleting, const ksh_deprovisioning_inputs* in,
+                                  const ksh_pdb_block* pdbs, int device, ksh_deprovisioning_out* out, double* ms) {
+  if (!in || !out) return set_err(KS_ERR_INVALID, "null argument");
+  try {
+    uint32_t n_in_result = 0;
+    const int rc = candidates_over((Parsed*)parsed, method, pod_node, deleting, n_deleting, &in->base, in, pdbs, device, &out->base, &n_in_result, ms);
+    if (rc == KS_OK) out->n_in_result = n_in_result;
+    return rc;
+  } catch (const ksh::Unsupported& e) { return set_err(KS_ERR_UNSUPPORTED, e.what()); } catch (const std::exception& e) { return set_err(KS_ERR_INVALID, e.what()); }
+}
+// Emptiness.ComputeCommand (emptiness.go:73-82), literally: of the candidates those without pods, all deleted in one command; none -> do-nothing.  Host only.
+int ksh_emptiness_command(const uint32_t* candidates, uint32_t n, const uint32_t* n_node_pods, uint32_t* out_action, uint32_t* out_nodes, uint32_t* out_n_nodes) {
+  if (!out_action || !out_n_nodes || (n && (!candidates || !n_node_pods || !out_nodes))) return set_err(KS_ERR_INVALID, "null argument");
+  uint32_t k = 0;
+  for (uint32_t i = 0; i < n; ++i) if (n_node_pods[candidates[i]] == 0) out_nodes[k++] = candidates[i];
+  *out_n_nodes = k; *out_action = k ? KS_CMD_DELETE : KS_CMD_DO_NOTHING;
+  return KS_OK;
 }
 // The names behind a row, without a handle: what 0 = requirement key a, 1 = value b of key a (the flattening's universes: available once a what-if call flattened the
 // snapshot), 3 = state node a, 4 = instance type a.  NULL when out of range.
@@ -1200,6 +1323,7 @@ const char* ksh_snapshot_name(void* parsed, int what, uint32_t a, uint32_t b) {
   const ksh::Encoded& E = *ksh::delta_inputs(*P->sb).base;
   if (what == 0) return a < E.key_names.size() ? E.key_names[a].c_str() : nullptr;
   if (what == 1) return (a < E.key_values.size() && b < E.key_values[a].size()) ? E.key_values[a][b].c_str() : nullptr;
+  if (what == 2) return a < E.res_names.size() ? E.res_names[a].c_str() : nullptr;
   return nullptr;
 }
 // the instance-type key's requirement of a row (KS_CMD_IT_STATE), spelled out: *complement, the number of values; value i through ksh_snapshot_it_state_value

@@ -935,6 +935,217 @@ def consolidation_candidates(snapshot: "ParsedProblem", pod_node: Optional[Seque
             "n_node_pods": npods[:n_nodes], "cost": cost[:n_nodes], "ms": dict(zip(CANDIDATE_TIMING_KEYS, [float(x) for x in ms]))}
 
 
+# ---- candidates of expiration / drift / emptiness (include/kshost.h ksh_deprovisioning_candidates, ksh_emptiness_command) ----
+KSH_METHOD_EXPIRATION, KSH_METHOD_DRIFT, KSH_METHOD_EMPTINESS = 1, 2, 3
+KSH_CAND_NODE_HAS_EMPTINESS_TIMESTAMP, KSH_CAND_NODE_EMPTINESS_UNPARSABLE, KSH_CAND_NODE_DRIFTED = 16, 32, 64
+KS_DEPROV_WHY_NOT_EXPIRED, KS_DEPROV_WHY_NOT_DRIFTED, KS_DEPROV_WHY_NOT_EMPTY = 14, 15, 16
+KS_DEPROV_MAX_TTL_SECONDS = 9223372036
+
+
+class _DeprovisioningInputs(ctypes.Structure):      # include/kshost.h ksh_deprovisioning_inputs
+    _fields_ = [("base", _CandidateInputs), ("now_unix_nanos", ctypes.c_int64), ("node_creation_unix_nanos", ctypes.c_void_p), ("node_emptiness_unix_nanos", ctypes.c_void_p),
+                ("prov_ttl_seconds_after_empty", ctypes.c_void_p), ("drift_enabled", ctypes.c_uint32), ("pad", ctypes.c_uint32)]
+
+
+class _DeprovisioningOut(ctypes.Structure):      # include/kshost.h ksh_deprovisioning_out
+    _fields_ = [("base", _CandidatesOut), ("n_in_result", ctypes.c_uint32), ("pad", ctypes.c_uint32)]
+
+
+def deprovisioning_candidates(snapshot: "ParsedProblem", method: int, pod_node: Optional[Sequence[int]], now_unix_nanos: int, node_flags: Sequence[int],
+                              node_creation_unix_nanos: Sequence[int], node_age_seconds: Sequence[float], pod_flags: Sequence[int], pod_deletion_cost: Sequence[float],
+                              pod_priority: Sequence[int], prov_ttl_seconds: Sequence[Optional[int]], prov_ttl_seconds_after_empty: Sequence[Optional[int]] = None,
+                              node_emptiness_unix_nanos: Sequence[int] = None, drift_enabled: bool = False, pdbs=(), deleting: Sequence[int] = (), device: int = 0,
+                              out: Optional[dict] = None) -> dict:
+    """candidateNodes under Expiration / Drift / Emptiness.ShouldDeprovision and the order their ComputeCommand walks, in ONE call (kshost.h
+    `ksh_deprovisioning_candidates`; `method`: KSH_METHOD_*).  Arrays as for `consolidation_candidates`; times are unix nanoseconds as Python ints (exact int64 arithmetic
+    on the device); `node_flags` may carry KSH_CAND_NODE_HAS_EMPTINESS_TIMESTAMP / _EMPTINESS_UNPARSABLE / _DRIFTED; ttls: None (or -1) for nil.  Returns
+    `consolidation_candidates`' dict plus "n_in_result": len(candidateNodes(...)) -- the controller moves to the next method when it is 0."""
+    import numpy as np
+    from .model import pdbs_to_block
+    kh = libs()[1]
+    n_nodes, n_pods, n_prov = len(node_flags), len(pod_flags), len(prov_ttl_seconds)
+    if prov_ttl_seconds_after_empty is None:
+        prov_ttl_seconds_after_empty = [None] * n_prov
+    if node_emptiness_unix_nanos is None:
+        node_emptiness_unix_nanos = [0] * n_nodes
+    if (len(node_age_seconds) != n_nodes or len(node_creation_unix_nanos) != n_nodes or len(node_emptiness_unix_nanos) != n_nodes or len(pod_deletion_cost) != n_pods or
+            len(pod_priority) != n_pods or len(prov_ttl_seconds_after_empty) != n_prov):
+        raise KSolveError(KS_ERR_INVALID, "deprovisioning_candidates: array lengths differ")
+    i64 = lambda xs, fill: np.ascontiguousarray(np.asarray([fill if x is None else int(x) for x in xs] or [fill], dtype=np.int64))
+    nf = np.ascontiguousarray(np.asarray(list(node_flags) or [0], dtype=np.uint32)); age = np.ascontiguousarray(np.asarray(list(node_age_seconds) or [0.0], dtype=np.float64))
+    pf = np.ascontiguousarray(np.asarray(list(pod_flags) or [0], dtype=np.uint32)); dc = np.ascontiguousarray(np.asarray(list(pod_deletion_cost) or [0.0], dtype=np.float64))
+    pp = np.ascontiguousarray(np.asarray(list(pod_priority) or [0], dtype=np.int32))
+    ttl, ttl_e, cre, emp = i64(prov_ttl_seconds, -1), i64(prov_ttl_seconds_after_empty, -1), i64(node_creation_unix_nanos, 0), i64(node_emptiness_unix_nanos, 0)
+    base = _CandidateInputs(n_nodes, n_pods, n_prov, 0, nf.ctypes.data, age.ctypes.data, pf.ctypes.data, dc.ctypes.data, pp.ctypes.data, None, ttl.ctypes.data)
+    inp = _DeprovisioningInputs(base, int(now_unix_nanos), cre.ctypes.data, emp.ctypes.data, ttl_e.ctypes.data, 1 if drift_enabled else 0, 0)
+    b = pdbs if isinstance(pdbs, dict) else pdbs_to_block(list(pdbs))
+    pb = _PdbBlock(b["n_pdbs"], b["n_strings"], b["n_words"], b["str_off"].ctypes.data, b["str_bytes"].ctypes.data, b["words"].ctypes.data, int(b.get("str_bytes_len", b["str_bytes"].size)))
+    m = max(1, n_nodes)
+    if out is not None:          # (tests: preallocated arrays, poisoned first)
+        order, empty, why, npods, detail, cost = (out[k] for k in ("order", "empty", "why", "n_node_pods", "detail", "cost"))
+    else:
+        order, empty, why, npods = (np.zeros(m, dtype=np.uint32) for _ in range(4))
+        detail, cost = np.zeros(m, dtype=np.int32), np.zeros(m, dtype=np.float64)
+    res = _DeprovisioningOut(_CandidatesOut(0, 0, order.ctypes.data, empty.ctypes.data, why.ctypes.data, detail.ctypes.data, npods.ctypes.data, cost.ctypes.data), 0, 0)
+    pn, pn_ptr = _pod_node_arg(pod_node)
+    dl = _u32s(deleting)
+    ms = (ctypes.c_double * 4)()
+    kh.ksh_deprovisioning_candidates.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                                 ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]
+    rc = kh.ksh_deprovisioning_candidates(snapshot._p, method, pn_ptr, dl.ctypes.data, len(deleting), ctypes.byref(inp), ctypes.byref(pb), device, ctypes.byref(res), ms)
+    if rc != KS_OK:
+        raise KSolveError(rc, kh.ksh_last_error().decode())
+    return {"order": [int(x) for x in order[:res.base.n_candidates]], "empty": [int(x) for x in empty[:res.base.n_empty]], "why": why[:n_nodes], "detail": detail[:n_nodes],
+            "n_node_pods": npods[:n_nodes], "cost": cost[:n_nodes], "n_in_result": int(res.n_in_result), "ms": dict(zip(CANDIDATE_TIMING_KEYS, [float(x) for x in ms]))}
+
+
+def emptiness_command(candidates: Sequence[int], n_node_pods: Sequence[int]):
+    """Emptiness.ComputeCommand (kshost.h `ksh_emptiness_command`, host only) over `deprovisioning_candidates`' order and n_node_pods under KSH_METHOD_EMPTINESS:
+    (KS_CMD_DELETE or KS_CMD_DO_NOTHING, the node slots to remove)."""
+    import numpy as np
+    kh = libs()[1]
+    cand, npods = _u32s(candidates), _u32s(n_node_pods)
+    nodes = np.zeros(max(1, len(candidates)), dtype=np.uint32)
+    action, n = ctypes.c_uint32(99), ctypes.c_uint32(0)
+    kh.ksh_emptiness_command.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32), ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32)]
+    rc = kh.ksh_emptiness_command(cand.ctypes.data, len(candidates), npods.ctypes.data, ctypes.byref(action), nodes.ctypes.data, ctypes.byref(n))
+    if rc != KS_OK:
+        raise KSolveError(rc, kh.ksh_last_error().decode())
+    return int(action.value), [int(x) for x in nodes[:n.value]]
+
+
+# ---- replacement commands with m -> n rows (include/ksolve.h KS_REP_*, include/kshost.h ksh_replacement_commands / ksh_replacement_option / ksh_replacement_rows) ----
+KS_REP_F_BLOCKED = 1
+KS_REP_HEAD_WORDS = 8
+KS_REP_ID, KS_REP_DECISION, KS_REP_N_NEW, KS_REP_N_UNSCHEDULED, KS_REP_N_NODES, KS_REP_NODE_OFF, KS_REP_N_OPTIONS = range(7)
+KS_REP_BLOCKED, KS_REP_TRUNCATED = 1, 2
+KS_REP_NODE_ID, KS_REP_NODE_PRESENT, KS_REP_NODE_IT_STATE, KS_REP_NODE_N_OPTIONS, KS_REP_NODE_REQMASK, KS_REP_NODE_MASK, KS_REP_NODE_BOUNDS, KS_REP_NODE_REQ, KS_REP_NODE_OPTIONS = 0, 1, 2, 3, 4, 5, 37, 69, 85
+KS_MAX_RES = 16
+
+
+def replacement_node_words(words: int) -> int:
+    """KS_REP_NODE_WORDS: uint64 words of one node row whose option mask is `words` wide."""
+    return KS_REP_NODE_OPTIONS + words
+
+
+def _rep_tables(n, cap_nodes, words, heads, nodes):
+    import numpy as np
+    if heads is None:
+        heads = np.zeros((max(1, n), KS_REP_HEAD_WORDS), dtype=np.uint64)
+    if nodes is None and cap_nodes:
+        nodes = np.zeros((cap_nodes, replacement_node_words(words)), dtype=np.uint64)
+    return heads, nodes
+
+
+def replacement_commands(snapshot: "ParsedProblem", pod_node: Optional[Sequence[int]], candidate_sets: Sequence[Sequence[int]], words: int, cap_nodes: Optional[int] = None,
+                         deleting: Sequence[int] = (), device: int = 0, volumes: bool = False, active_resources: bool = False, flags: int = 0, heads=None, nodes=None):
+    """Expiration / Drift.ComputeCommand's simulation and m -> n command for every candidate set in ONE call (kshost.h `ksh_replacement_commands`).  cap_nodes None:
+    the sizing call first, then a table that is exactly large enough.  `heads` / `nodes`: preallocated tables to fill (tests poison them; their row widths must be
+    KS_REP_HEAD_WORDS / replacement_node_words(words)).  Returns (heads [n, 8], nodes [cap_nodes, replacement_node_words(words)] or None, total nodes, timings)."""
+    kh = libs()[1]
+    n = len(candidate_sets)
+    off, cand = _cand_csr(candidate_sets)
+    pn, pn_ptr = _pod_node_arg(pod_node)
+    dl = _u32s(deleting)
+    fl = (KSH_DERIVE_VOLUMES if volumes else 0) | (KSH_ACTIVE_RESOURCES if active_resources else 0) | flags
+    kh.ksh_replacement_commands.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int,
+                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), ctypes.c_uint32, ctypes.POINTER(ctypes.c_double)]
+
+    def call(cap, hd, nd):
+        total, ms = ctypes.c_uint64(0), (ctypes.c_double * 5)()
+        rc = kh.ksh_replacement_commands(snapshot._p, fl, n, off.ctypes.data, cand.ctypes.data, pn_ptr, dl.ctypes.data, len(deleting), device, hd.ctypes.data,
+                                         nd.ctypes.data if nd is not None else None, cap, ctypes.byref(total), words, ms)
+        if rc != KS_OK:
+            raise KSolveError(rc, kh.ksh_last_error().decode())
+        return int(total.value), dict(zip(COMMAND_TIMING_KEYS, [float(x) for x in ms]))
+    if cap_nodes is None:
+        hd, _ = _rep_tables(n, 0, words, None, None)
+        cap_nodes, _ = call(0, hd, None)
+    heads, nodes = _rep_tables(n, cap_nodes, words, heads, nodes)
+    total, ms = call(cap_nodes, heads, nodes)
+    return heads[:n], nodes, total, ms
+
+
+def replacement_option(snapshot: "ParsedProblem", pod_node, candidates: Sequence[int], why: Sequence[int], words: int, cap_nodes: int = 64, deleting: Sequence[int] = (), device: int = 0,
+                       volumes: bool = False, active_resources: bool = False, flags: int = 0):
+    """ComputeCommand's loop for expiration and drift (kshost.h `ksh_replacement_option`): the first candidate with why == 0 that is not deleting is simulated, alone.
+    Returns (head, nodes, total nodes, position in `candidates` or -1, timings); called again with a larger table if `cap_nodes` was too small."""
+    import numpy as np
+    kh = libs()[1]
+    cand, wy, dl = _u32s(candidates), _u32s(why), _u32s(deleting)
+    pn, pn_ptr = _pod_node_arg(pod_node)
+    fl = (KSH_DERIVE_VOLUMES if volumes else 0) | (KSH_ACTIVE_RESOURCES if active_resources else 0) | flags
+    kh.ksh_replacement_option.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int,
+                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_int32), ctypes.c_uint32,
+                                          ctypes.POINTER(ctypes.c_double)]
+    while True:
+        head = np.zeros(KS_REP_HEAD_WORDS, dtype=np.uint64)
+        nodes = np.zeros((max(1, cap_nodes), replacement_node_words(words)), dtype=np.uint64)
+        total, pos, ms = ctypes.c_uint64(0), ctypes.c_int32(-2), (ctypes.c_double * 5)()
+        rc = kh.ksh_replacement_option(snapshot._p, fl, cand.ctypes.data, len(candidates), wy.ctypes.data, pn_ptr, dl.ctypes.data, len(deleting), device, head.ctypes.data, nodes.ctypes.data,
+                                       cap_nodes, ctypes.byref(total), ctypes.byref(pos), words, ms)
+        if rc != KS_OK:
+            raise KSolveError(rc, kh.ksh_last_error().decode())
+        if int(total.value) <= cap_nodes:
+            return head, nodes[:int(total.value)], int(total.value), int(pos.value), dict(zip(COMMAND_TIMING_KEYS, [float(x) for x in ms]))
+        cap_nodes = int(total.value)
+
+
+def whatifs_simulated() -> int:
+    """`ksh_whatifs_simulated`: what-ifs the simulating calls have opened and solved in this process so far; the difference across a call counts its simulations."""
+    kh = libs()[1]
+    kh.ksh_whatifs_simulated.restype = ctypes.c_uint64
+    kh.ksh_whatifs_simulated.argtypes = []
+    return int(kh.ksh_whatifs_simulated())
+
+
+def replacement_rows(flats: Sequence[FlatProblem], ids: Sequence[int], flags: Sequence[int], words: int, cap_nodes: int, heads=None, nodes=None):
+    """`ksh_replacement_rows`: both tables of handles whose results are on the device.  Returns (heads, nodes or None, total nodes)."""
+    import numpy as np
+    kh = libs()[1]
+    n = len(flats)
+    hs = (ctypes.c_void_p * max(1, n))(*[f._h for f in flats])
+    c_ids = np.ascontiguousarray(np.asarray(list(ids) or [0], dtype=np.uint64))
+    fl = _u32s(flags)
+    heads, nodes = _rep_tables(n, cap_nodes, words, heads, nodes)
+    total = ctypes.c_uint64(0)
+    kh.ksh_replacement_rows.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
+                                        ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p]
+    rc = kh.ksh_replacement_rows(hs, n, c_ids.ctypes.data, fl.ctypes.data, words, heads.ctypes.data, nodes.ctypes.data if nodes is not None else None, cap_nodes, ctypes.byref(total), None)
+    if rc != KS_OK:
+        raise KSolveError(rc, kh.ksh_last_error().decode())
+    return heads[:n], nodes, int(total.value)
+
+
+def decode_replacement_head(head) -> dict:
+    r = [int(x) for x in head]
+    return {"id": r[KS_REP_ID], "action": r[KS_REP_DECISION] & 0xFF, "why": (r[KS_REP_DECISION] >> 8) & 0xFF, "blocked": bool((r[KS_REP_DECISION] >> 16) & KS_REP_BLOCKED),
+            "truncated": bool((r[KS_REP_DECISION] >> 16) & KS_REP_TRUNCATED), "n_new": r[KS_REP_N_NEW], "n_unscheduled": r[KS_REP_N_UNSCHEDULED], "n_nodes": r[KS_REP_N_NODES],
+            "node_off": r[KS_REP_NODE_OFF], "n_options": r[KS_REP_N_OPTIONS], "reserved": r[7]}
+
+
+def decode_replacement_node(snapshot: "ParsedProblem", row, words: int) -> dict:
+    """A node row as Python values, through the handle-free name accessors: what-if id, node index, options as instance-type indices, requirements as
+    `decode_command_row` gives them, requests {resource name: milli-units} for the resources the request mask lists."""
+    kh = libs()[1]
+    r = [int(x) for x in row]
+    as_cmd = [0] * command_row_words(words)      # the requirement words have KS_CMD_*'s layout and meaning: decoded by the same code
+    as_cmd[KS_CMD_PRESENT], as_cmd[KS_CMD_IT_STATE] = r[KS_REP_NODE_PRESENT], r[KS_REP_NODE_IT_STATE]
+    as_cmd[KS_CMD_MASK:KS_CMD_MASK + 32] = r[KS_REP_NODE_MASK:KS_REP_NODE_MASK + 32]
+    as_cmd[KS_CMD_BOUNDS:KS_CMD_BOUNDS + 32] = r[KS_REP_NODE_BOUNDS:KS_REP_NODE_BOUNDS + 32]
+    reqs = decode_command_row(snapshot, as_cmd, words)["requirements"]
+    kh.ksh_snapshot_name.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32]
+    kh.ksh_snapshot_name.restype = ctypes.c_char_p
+    requests = {}
+    for a in range(KS_MAX_RES):
+        if (r[KS_REP_NODE_REQMASK] >> a) & 1:
+            v = r[KS_REP_NODE_REQ + a]
+            requests[kh.ksh_snapshot_name(snapshot._p, 2, a, 0).decode()] = v - (1 << 64) if v >= (1 << 63) else v
+    return {"id": r[KS_REP_NODE_ID] & 0xFFFFFFFF, "node": r[KS_REP_NODE_ID] >> 32, "n_options": r[KS_REP_NODE_N_OPTIONS], "reqmask": r[KS_REP_NODE_REQMASK],
+            "options": [w * 64 + b for w in range(words) for b in range(64) if (r[KS_REP_NODE_OPTIONS + w] >> b) & 1], "requirements": reqs, "requests": requests,
+            "req_words": r[KS_REP_NODE_REQ:KS_REP_NODE_REQ + KS_MAX_RES]}
+
+
 def command_rows(flats: Sequence[FlatProblem], ids: Sequence[int], flags: Sequence[int], cand_prices: Sequence[float], type_lists: Sequence[Sequence[Tuple[int, float]]], words: int,
                  out=None, type_off=None):
     """`ksh_command_rows`: the command rows of handles whose results are on the device, the per-what-if inputs given by the caller (flags: KS_CMD_F_*; type_lists[i]:
