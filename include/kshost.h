@@ -444,24 +444,38 @@ int ksh_replacement_rows(void** handles, uint32_t n, const uint64_t* ids, const 
  * every 10 s): state.Cluster hears UpdateNode / DeleteNode / UpdatePod / DeletePod (pkg/controllers/state/cluster.go:151-200) and patches its nodes in place
  * (state/node.go:161-182 updateForPod / cleanupForPod; Available() = Allocatable - the requests of the pods bound, node.go:113); the next pass then flattens
  * everything again (helpers.go:42-99 -> provisioner.go:237-296).  Here the events patch the objects ksh_parse holds AND the snapshot's flattening follows them.
- * `ksd_text`:  KSD1 <n>  { NODE+ <KSP1 NODE record without its keyword>  |  NODE- <node name>  |  BIND <node name> POD <KSP1 pod record>  |  UNBIND <pod uid> }*  END
+ * `ksd_text`:  KSD1 <n>  { NODE+ <KSP1 NODE record without its keyword>  |  NODE= <the same record>  |  NODE- <node name>  |  BIND <node name> POD <KSP1 pod record>  |  UNBIND <pod uid> }*  END
  *   NODE+   a state node joins (slot = the next node index; slots are never reused, candidate sets keep naming nodes by slot)
  *   NODE-   a state node leaves; the pods bound to it are unbound with it
  *   BIND    a pod is bound to a node: it joins the snapshot's pods (index = the next one), the node's available resources shrink by RequestsForPods(pod),
  *           its host ports and volumes join the node's usage
  *   UNBIND  the reverse
+ *   NODE=   a state node that is in state already is replaced in place (state.Cluster.UpdateNode on every node reconciliation after the first sight of the node,
+ *           cluster.go:151-166, newStateFromNode :227-255; NODE+ is the first sight).  The record's name must be a live state node -- a node that left is not --
+ *           or the event is refused with "NODE=: no state node named X".  The node keeps its slot, the pods bound to it stay bound to that slot
+ *           (ksh_snapshot_bindings does not change, the mirrored cluster pods name the same node).  Everything else the record carries REPLACES what the slot
+ *           held: labels, taints, available, capacity, daemonset requests, host ports, volume limits, volumes -- taken as given: they are state.Node's own
+ *           outputs at the moment of the event, already net of the pods bound; later BIND / UNBIND patch from there.  The provisioner-name label may change
+ *           (owned <-> unowned, another provisioner).  The record's in_state word is not read: the node is in state.
  * The first call hands the snapshot's bindings over (`pod_node`, as the what-if calls take it); from then on the library holds them -- every call that takes a
  * `pod_node` accepts NULL for "the library's", ksh_snapshot_bindings reads them.  info[0] = events applied (an event that cannot be applied ends the call with
  * KS_ERR_INVALID; the ones before it stay), info[1] / info[2] = node / pod slots, info[3] = 1 when the snapshot's flattening was CONTINUED from the one before:
  * pods already seen keep their specs, the catalogue's arrays, the universes and the old nodes' requirement rows are taken over (possible while the events bring no
  * label key / value / resource name the universes lack; otherwise, and when no flattening existed yet, the next what-if call flattens from scratch -- same result
- * either way, tests/test_env_apply.py compares the two byte for byte).  The objects are patched in place: do not call while another thread solves over this
+ * either way, tests/test_env_apply.py compares the two byte for byte).  A NODE= bumps the change stamp of its slot: the continuation rebuilds the requirement row
+ * of such a slot and takes over the rows of the others (taints, remaining resources, volume counts and the per-node topology tables behind the device derivation
+ * are worked out for every node on either road).  It is continued (info[3] = 1) while the universes stay put -- an initialised flip whose two values other nodes
+ * carry, a taint of the known set added or removed, available / capacity changed, an ownership change among known provisioners.  It falls back to the full run
+ * (info[3] = 0, same bytes) when the update brings a label value of a referenced key, a taint or a resource name (under KSH_ACTIVE_RESOURCES: a name in its
+ * daemonset requests) that the flattening before did not have, when it removes the last use of a label value, and when it changes which resource names that only nodes
+ * carry the node lists.  The objects are patched in place: do not call while another thread solves over this
  * snapshot; handles opened before the call keep what they were opened with.  KS_ERR_INVALID "spare room ... used up": the snapshot was parsed with room for a
  * quarter more nodes / pods (at least 256 / 4096); ingest it again. */
 int ksh_env_apply(void* parsed_snapshot, const int32_t* pod_node /* first call: the bindings; later NULL */, const char* ksd_text, size_t len, uint32_t info[4] /* or NULL */);
 /* ---- the same door without the text: the events as ONE stream of u32 words over ONE string table (conventions of ksh_env_block; grammar in
  * karpenter_core_amd/host/kspb.hpp, DeltaReader).  Per event a kind word, then its body: KSH_EVENT_NODE_ADD the state-node record of ksh_env_block, KSH_EVENT_NODE_REMOVE
- * the node's name, KSH_EVENT_BIND the node's name + the pod (word count, spec record of ksh_pod_block, uid, creationTimestamp as two words), KSH_EVENT_UNBIND the pod's uid.
+ * the node's name, KSH_EVENT_BIND the node's name + the pod (word count, spec record of ksh_pod_block, uid, creationTimestamp as two words), KSH_EVENT_UNBIND the pod's uid,
+ * KSH_EVENT_NODE_UPDATE (NODE=) the state-node record again, word for word what KSH_EVENT_NODE_ADD carries.
  * A cgo caller fills it with the writer it has for the other two doors; quantities are int64 milli-units, nothing is quoted or printed.  Everything after the decoding is
  * ksh_env_apply's: same patching, same info[0..3], same bindings held by the library, same error texts for an event that cannot be applied (the events before it stay,
  * info[0] counts them).  Text and binary calls may be mixed on one snapshot in any order.
@@ -475,6 +489,7 @@ int ksh_env_apply(void* parsed_snapshot, const int32_t* pod_node /* first call: 
 #define KSH_EVENT_NODE_REMOVE 2u
 #define KSH_EVENT_BIND 3u
 #define KSH_EVENT_UNBIND 4u
+#define KSH_EVENT_NODE_UPDATE 5u
 #define KSH_APPLY_TRACK_CLUSTER_PODS 1u
 typedef struct ksh_delta_block {
   uint32_t n_events, n_strings, n_words;

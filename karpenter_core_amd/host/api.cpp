@@ -305,7 +305,8 @@ static int resident_base(const ksh::Encoded* base, int device, std::shared_ptr<v
 }
 extern "C" {
 // ---- the snapshot kept current by events instead of re-ingested (state.Cluster's UpdateNode / DeleteNode / UpdatePod / DeletePod, cluster.go) ----
-// The problem object is patched in place -- new nodes and pods are appended (the vectors were parsed with room: nothing moves), what leaves stays as a tombstone
+// The problem object is patched in place -- new nodes and pods are appended (the vectors were parsed with room: nothing moves), a node that is updated is replaced
+// in its slot (NODE=), what leaves stays as a tombstone
 // (a node out of state, a pod bound nowhere) -- and the snapshot's flattening, if there is one, is continued from the one before (ksh::make_snapshot_base `before`).
 // Not to be called while another thread uses handles opened over this snapshot; handles opened BEFORE the call keep solving what they were opened for.
 // What both doors do once the events are objects (`ev` is consumed): the text door (ksh_env_apply) and the binary one (ksh_env_apply_block) differ in the decoding alone.
@@ -334,6 +335,7 @@ static int apply_events(Parsed* P, const int32_t* pod_node, std::vector<ksp::Del
       p.uid = std::string("\1unbound-") + std::to_string(++P->tombstones);      // (uids stay unique: the same pod may be bound again)
     };
     uint32_t done = 0; std::string why;
+    std::vector<ksh::ReplacedNode> replaced;      // NODE=: the nodes as the flattening before saw them (the first replacement of a slot in this call)
     for (auto& e : ev) {
       if (e.kind == ksp::DeltaEvent::NodeAdd) {
         if (P->live_node.count(e.node.name)) { why = "NODE+: a state node named " + e.node.name + " exists"; break; }
@@ -356,6 +358,15 @@ static int apply_events(Parsed* P, const int32_t* pod_node, std::vector<ksp::Del
         for (auto& v : e.pod.volumes) n.volumes.push_back(v);
         if (mirror) { ksp::ClusterPod cp; cp.uid = e.pod.uid; cp.ns = e.pod.ns; cp.node_name = n.name; cp.labels = e.pod.labels; cp.anti_required = e.pod.anti_required; pr.cluster_pods.push_back(std::move(cp)); }
         P->live_pod.emplace(e.pod.uid, (uint32_t)pr.pods.size()); pr.pods.push_back(std::move(e.pod)); P->bind.push_back((int32_t)it->second);
+      } else if (e.kind == ksp::DeltaEvent::NodeUpdate) {
+        // state.Cluster.UpdateNode for a node already in state (cluster.go:151-166): the node object is replaced, slot and bindings stay; what the record carries is
+        // state.Node's own output, already net of the pods bound -- taken as given
+        auto it = P->live_node.find(e.node.name); if (it == P->live_node.end()) { why = "NODE=: no state node named " + e.node.name; break; }
+        const uint32_t nd = it->second; ksp::StateNode& n = pr.nodes[nd];
+        e.node.in_state = true; e.node.stamp = n.stamp + 1;
+        bool first = true; for (auto& r : replaced) if (r.slot == nd) first = false;
+        if (first) replaced.push_back(ksh::ReplacedNode{nd, std::move(n)});
+        n = std::move(e.node);
       } else {
         auto it = P->live_pod.find(e.name); if (it == P->live_pod.end()) { why = "UNBIND: no bound pod with uid " + e.name; break; }
         unbind(it->second);
@@ -367,7 +378,7 @@ static int apply_events(Parsed* P, const int32_t* pod_node, std::vector<ksp::Del
     bool continued = false;
     if (P->sb) {
       std::shared_ptr<const ksh::SnapshotBase> before = P->sb;
-      try { P->sb = ksh::make_snapshot_base(P->pr, P->bind.data(), P->sb_flags, before.get()); P->sb_pod_node = P->bind; continued = ksh::snapshot_continued(*P->sb); }
+      try { P->sb = ksh::make_snapshot_base(P->pr, P->bind.data(), P->sb_flags, before.get(), &replaced); P->sb_pod_node = P->bind; continued = ksh::snapshot_continued(*P->sb); }
       catch (...) { P->sb.reset(); P->sb_pod_node.clear(); throw; }
       ksh::dispose_later(std::move(before));      // (the flattening before: torn down off this thread, once the handles that still use it are closed)
     }

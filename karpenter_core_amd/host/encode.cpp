@@ -303,6 +303,12 @@ struct Builder {
   std::vector<Hash128> spec_hs; std::vector<int32_t> spec_tab; std::vector<uint32_t> spec_first;      // kept by dedupe_specs: the hash of every spec's first pod, the table over them, the first pods
   std::map<std::string, int> pre_it_state_id, pre_it_col_id;      // kept by encode_it_states: the lattice's states / columns before its closure
   std::string act_sig; std::map<std::string, int> act_key_id, act_res_id; size_t n_nodes_built = 0, n_pods_built = 0;      // kept by run(): what collect_active left, how large the problem was
+  // A NODE= event replaces a node in place and bumps the change stamp of its slot (ksp::StateNode::stamp).  node_stamp_built: the stamps this flattening saw.  A run
+  // that continues `prev` treats a slot whose stamp moved like a new node -- its requirement row is rebuilt -- and, since what the node carried BEFORE is in the
+  // universes it adopts, asks whether that was the last use (`replaced`: the nodes the events replaced, as `prev` saw them; fixed_key_vals / fixed_res_n: the values
+  // and resource names the universes hold whatever the nodes carry -- from the batch, the provisioners, the daemonsets and the catalogue).
+  std::vector<uint32_t> node_stamp_built; const std::vector<ReplacedNode>* replaced = nullptr;
+  std::shared_ptr<const std::vector<std::set<std::string>>> fixed_key_vals; size_t fixed_res_n = 0;
 
   // KSH_ACTIVE_RESOURCES (a library flag: the flat problem never carries it): only the resource names something requests or limits are interned -- what a pod, a
   // daemonset, a provisioner's limits or a node's daemonset_requests names.  A name that only an instance type's capacity / overhead or a node's available / capacity
@@ -375,19 +381,52 @@ struct Builder {
     if (!prev || &prev->pr != &pr || prev->flags != flags || prev->active_res != active_res || prev->act_sig.empty() || prev->base || prev->lite) return false;
     if (key_id != prev->act_key_id || res_id != prev->act_res_id || active_signature() != prev->act_sig) return false;
     if (prev->n_nodes_built > pr.nodes.size() || prev->T != pr.instance_types.size()) return false;
-    for (size_t i = prev->n_nodes_built; i < pr.nodes.size(); ++i) {
-      const auto& n = pr.nodes[i];
+    auto brings_nothing_new = [&](const ksp::StateNode& n) {
       for (auto& kv : n.labels) { const std::string k = ksp::normalize_key(kv.first);
         auto it = prev->key_id.find(k); if (it != prev->key_id.end() && !prev->key_vals[it->second].count(kv.second)) return false;
         auto raw = prev->key_id.find(kv.first); if (raw != prev->key_id.end() && raw->first != k && !prev->key_vals[raw->second].count(kv.second)) return false; }
       for (const ksp::ResList* l : {&n.available, &n.capacity, &n.daemonset_requests}) { if (active_res && l != &n.daemonset_requests) continue; for (auto& kv : *l) if (!prev->res_id.count(kv.first)) return false; }
+      return true;
+    };
+    for (size_t i = prev->n_nodes_built; i < pr.nodes.size(); ++i) if (!brings_nothing_new(pr.nodes[i])) return false;
+    // the slots a NODE= replaced since `prev`
+    for (size_t i = 0; i < prev->n_nodes_built; ++i) {
+      const auto& n = pr.nodes[i]; if (n.stamp == prev->node_stamp_built[i]) continue;
+      const ksp::StateNode* old = nullptr;
+      if (replaced) for (auto& r : *replaced) if (r.slot == i && r.before.stamp == prev->node_stamp_built[i]) { old = &r.before; break; }
+      if (!old || !prev->fixed_key_vals || !brings_nothing_new(n)) return false;
+      if (n.owned()) for (auto& t : n.taints) if (!prev->taint_id.count(t.key + "\1" + t.value + "\1" + t.effect)) return false;      // (a taint the set lacks: the full run)
+      // a value the node no longer carries stays in the universe only if something else holds it there
+      for (auto& kv : old->labels) {
+        auto now = n.labels.find(kv.first); if (now != n.labels.end() && now->second == kv.second) continue;
+        const std::string k = ksp::normalize_key(kv.first);
+        for (const std::string* kn : {&k, &kv.first}) {
+          if (kn == &kv.first && kv.first == k) continue;
+          auto it = prev->key_id.find(*kn); if (it == prev->key_id.end() || (*prev->fixed_key_vals)[it->second].count(kv.second)) continue;
+          bool used = false;
+          for (auto& o : pr.nodes) { for (auto& ol : o.labels) if (ol.second == kv.second && (ol.first == *kn || ksp::normalize_key(ol.first) == *kn)) { used = true; break; } if (used) break; }
+          if (!used) return false;
+        }
+      }
+      // a resource name only nodes carry is numbered by the first node that names it, in the order the node's lists name it: the node must name the same ones in
+      // the same order as before, or the full run numbers them
+      auto node_only = [&](const ksp::StateNode& x) {
+        std::vector<const std::string*> seq;
+        for (const ksp::ResList* l : {&x.available, &x.capacity, &x.daemonset_requests}) {
+          if (active_res && l != &x.daemonset_requests) continue;
+          for (auto& kv : *l) { auto id = prev->res_id.find(kv.first); if (id == prev->res_id.end() || (size_t)id->second < prev->fixed_res_n) continue;
+            bool seen = false; for (auto* s : seq) if (*s == kv.first) seen = true; if (!seen) seq.push_back(&kv.first); }
+        }
+        return seq;
+      };
+      { const auto a = node_only(*old), b = node_only(n); if (a.size() != b.size()) return false; for (size_t x = 0; x < a.size(); ++x) if (*a[x] != *b[x]) return false; }
     }
     return true;
   }
   void collect_passive() {
     if (warm) {      // the catalogue's and the old nodes' contributions are in the previous universes, the new nodes add nothing (can_continue): adopt them and the tables made from them
       const Encoded& B = prev->E;
-      key_vals = prev->key_vals; res_id = prev->res_id; K = prev->K; R = prev->R; T = prev->T; TW = prev->TW;
+      key_vals = prev->key_vals; res_id = prev->res_id; K = prev->K; R = prev->R; T = prev->T; TW = prev->TW; fixed_key_vals = prev->fixed_key_vals; fixed_res_n = prev->fixed_res_n;
       E.key_names = B.key_names; E.key_values = B.key_values; E.key_nvalues = B.key_nvalues; E.value_int = B.value_int; E.key_members = B.key_members; E.key_class = B.key_class; E.key_ints = B.key_ints; E.res_names = B.res_names;
       return;
     }
@@ -404,6 +443,7 @@ struct Builder {
       for (auto& o : it.offerings) { note_value(key_of(ksp::kZone, true), o.zone); note_value(key_of(ksp::kCapacityType, true), o.capacity_type); }
       if (!active_res) { note_res(it.capacity); note_res(it.overhead); }
     }
+    if (keep_warm_state) { fixed_key_vals = std::make_shared<const std::vector<std::set<std::string>>>(key_vals); fixed_res_n = res_id.size(); }
     // node labels: only keys something else references matter (existing-node requirements are never
     // returned); values of referenced keys join the universe (they become topology domains / In sets)
     for (auto& n : pr.nodes) {
@@ -777,7 +817,7 @@ struct Builder {
     for (uint32_t m = 0; m < M; ++m) if (E.templates[m]->has_limits) remaining[m] = E.templates[m]->limits;
     for (uint32_t e = 0; e < NE; ++e) {
       const auto& n = pr.nodes[E.existing[e]];
-      const int pb = (warm && pr.daemons.empty() && (size_t)E.existing[e] < prev->base_existing_of.size()) ? prev->base_existing_of[E.existing[e]] : -1;
+      const int pb = (warm && pr.daemons.empty() && (size_t)E.existing[e] < prev->base_existing_of.size() && n.stamp == prev->node_stamp_built[E.existing[e]]) ? prev->base_existing_of[E.existing[e]] : -1;      // (a slot NODE= replaced: its row is made anew)
       if (pb >= 0) {
         // The node was a row of the previous flattening and its labels are what they were: the row's requirement words are copied; what numbers things in order of
         // first use (the instance-type state, taints) or changes with the pods bound to the node (available) is worked out as always.
@@ -1358,7 +1398,8 @@ struct Builder {
     }
     if (!specs_done) { dedupe_specs(); lap("dedupe_specs"); }
     if (!active_done) collect_active();
-    if (keep_warm_state) { act_sig = active_signature(); act_key_id = key_id; act_res_id = res_id; n_nodes_built = pr.nodes.size(); n_pods_built = podp.size(); }
+    if (keep_warm_state) { act_sig = active_signature(); act_key_id = key_id; act_res_id = res_id; n_nodes_built = pr.nodes.size(); n_pods_built = podp.size();
+      node_stamp_built.resize(pr.nodes.size()); for (size_t i = 0; i < pr.nodes.size(); ++i) node_stamp_built[i] = pr.nodes[i].stamp; }
     warm = can_continue();
     collect_passive(); lap(warm ? "universes (continued)" : "collect_universes");
     encode_instance_types(); lap("encode_instance_types");
@@ -1629,7 +1670,7 @@ static std::string build_topo_tables(SnapshotBase& sb, const int32_t* pod_node) 
   sb.topo.extra_tot = sb.t_extra_tot.data(); sb.topo.grph_base = sb.t_grph_base.data(); sb.has_topo = true;
   return "";
 }
-std::shared_ptr<const SnapshotBase> make_snapshot_base(std::shared_ptr<const ksp::Problem> snapshot, const int32_t* pod_node, uint32_t flags, const SnapshotBase* before) {
+std::shared_ptr<const SnapshotBase> make_snapshot_base(std::shared_ptr<const ksp::Problem> snapshot, const int32_t* pod_node, uint32_t flags, const SnapshotBase* before, const std::vector<ReplacedNode>* replaced) {
   auto sb = std::make_shared<SnapshotBase>(); sb->snapshot = snapshot;
   sb->volumes = (flags & KSH_DERIVE_VOLUMES) != 0; flags &= ~KSH_DERIVE_VOLUMES;      // (a library flag: the flat problem never carries it)
   sb->by_node.resize(snapshot->nodes.size());
@@ -1637,10 +1678,10 @@ std::shared_ptr<const SnapshotBase> make_snapshot_base(std::shared_ptr<const ksp
   for (size_t i = 0; i < snapshot->pods.size(); ++i) { if (pod_node[i] < 0) continue; if ((size_t)pod_node[i] >= snapshot->nodes.size()) throw ksp::Error("pod_node out of range"); sb->by_node[pod_node[i]].push_back((uint32_t)i); }
   sb->enc = std::make_shared<Encoded>(); sb->enc->src = snapshot;
   sb->builder = std::make_unique<Builder>(*sb->enc, flags); sb->builder->keep_warm_state = true;
-  if (before && before->snapshot.get() == snapshot.get() && before->volumes == sb->volumes && !getenv("KSH_NO_WARM_SNAPSHOT")) sb->builder->prev = before->builder.get();
+  if (before && before->snapshot.get() == snapshot.get() && before->volumes == sb->volumes && !getenv("KSH_NO_WARM_SNAPSHOT")) { sb->builder->prev = before->builder.get(); sb->builder->replaced = replaced; }
   if (sb->volumes) sb->builder->solo_pod_node = pod_node;
   sb->builder->run(); sb->continued = sb->builder->warm;
-  sb->builder->prev = nullptr; sb->builder->solo_pod_node = nullptr;      // (this flattening now stands alone: `before` and the caller's bindings may go)
+  sb->builder->prev = nullptr; sb->builder->replaced = nullptr; sb->builder->solo_pod_node = nullptr;      // (this flattening now stands alone: `before` and the caller's bindings may go)
   {   // what deriving what-ifs on the device needs (delta_inputs)
     const Builder& b = *sb->builder; const Encoded& E = *sb->enc; const uint32_t R = b.R, M = (uint32_t)E.templates.size(); const size_t NN = snapshot->nodes.size();
     sb->node_row.assign(b.base_existing_of.begin(), b.base_existing_of.end()); sb->node_row.resize(NN, -1);

@@ -102,7 +102,11 @@ uint32_t host_threads();
 struct SnapshotBase;
 // `before`: the flattening of the SAME problem object before ksh_env_apply appended nodes / pods to it (nothing else may have changed but the pods' nodes and the
 // nodes' available resources / in_state): what does not depend on the events is taken from it when the universes come out the same.  pod_node[i] = -1: bound nowhere.
-std::shared_ptr<const SnapshotBase> make_snapshot_base(std::shared_ptr<const ksp::Problem> snapshot, const int32_t* pod_node, uint32_t flags, const SnapshotBase* before = nullptr);
+// A node a NODE= event replaced in place carries a higher change stamp (ksp::StateNode::stamp) than `before` saw: `replaced` lists such slots with the node as it was
+// (its stamp the one `before` saw); the row of the slot is rebuilt.  A slot whose stamp moved and that `replaced` does not list makes the flattening start over.
+struct ReplacedNode { uint32_t slot; ksp::StateNode before; };
+std::shared_ptr<const SnapshotBase> make_snapshot_base(std::shared_ptr<const ksp::Problem> snapshot, const int32_t* pod_node, uint32_t flags, const SnapshotBase* before = nullptr,
+                                                       const std::vector<ReplacedNode>* replaced = nullptr);
 void dispose_later(std::shared_ptr<const void> p);      // destroyed on the library's teardown thread, not on the caller's (a snapshot's flattening: a millisecond of free())
 bool snapshot_continued(const SnapshotBase& sb);      // did the flattening take the short road
 uint64_t snapshot_fingerprint(const SnapshotBase& sb);      // FNV-1a over the flat problem and the per-node tables behind the device derivation (tests: short road == full run)

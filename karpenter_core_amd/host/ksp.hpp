@@ -114,12 +114,13 @@ struct StateNode {
   std::vector<HostPort> host_ports;
   std::vector<std::pair<std::string, int32_t>> volume_limits;   // state.Node.VolumeLimits(): CSINode allocatable count per driver (cluster.go:292-304)
   std::vector<Volume> volumes;                                   // state.Node.VolumeUsage(): volumes of the pods bound to the node
+  uint32_t stamp = 0;                                            // change stamp of the node's slot: a NODE= event (ksh_env_apply) bumps it; no record carries it
   bool owned() const { auto it = labels.find(kProvisionerName); return it != labels.end() && !it->second.empty(); }
 };
 struct ClusterPod { std::string uid, ns, node_name; StrMap labels; std::vector<AffinityTerm> anti_required; };
 
 // One event of a cluster's life between two snapshots (ksh_env_apply; state.Cluster's UpdateNode / DeleteNode / UpdatePod / DeletePod, cluster.go)
-struct DeltaEvent { enum Kind { NodeAdd, NodeRemove, PodBind, PodUnbind } kind = NodeAdd; StateNode node; Pod pod; std::string name; };
+struct DeltaEvent { enum Kind { NodeAdd, NodeRemove, PodBind, PodUnbind, NodeUpdate } kind = NodeAdd; StateNode node; Pod pod; std::string name; };
 
 struct Problem {
   std::vector<std::string> extra_well_known;
@@ -184,7 +185,7 @@ class Parser {
   Parser(const char* text, size_t len) : p_(text), e_(text + len) {}
 
   // What state.Cluster hears between two passes over the cluster (cluster.go UpdateNode / DeleteNode / UpdatePod / DeletePod), as KSD1 text:
-  //   KSD1 <n events>  { NODE+ <NODE record> | NODE- <node name> | BIND <node name> POD <pod record> | UNBIND <pod uid> }*  END
+  //   KSD1 <n events>  { NODE+ <NODE record> | NODE= <NODE record> | NODE- <node name> | BIND <node name> POD <pod record> | UNBIND <pod uid> }*  END
   // The records are KSP1's own (the NODE record without its leading keyword, the POD record with it).
   std::vector<DeltaEvent> parse_delta() {
     std::vector<DeltaEvent> ev;
@@ -195,7 +196,8 @@ class Parser {
       else if (k == "NODE-") { e.kind = DeltaEvent::NodeRemove; e.name = str(); }
       else if (k == "BIND") { e.kind = DeltaEvent::PodBind; e.name = str(); expect("POD"); e.pod = pod(); }
       else if (k == "UNBIND") { e.kind = DeltaEvent::PodUnbind; e.name = str(); }
-      else throw Error("KSD1: expected NODE+|NODE-|BIND|UNBIND got " + k);
+      else if (k == "NODE=") { e.kind = DeltaEvent::NodeUpdate; e.node = node(); }
+      else throw Error("KSD1: expected NODE+|NODE=|NODE-|BIND|UNBIND got " + k);
       ev.push_back(std::move(e));
     }
     expect("END");

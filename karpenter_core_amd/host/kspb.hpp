@@ -137,7 +137,7 @@ class EnvReader : public SpecReader {
   }
  protected:
   Taint taint() { Taint t; t.key = s(); t.value = s(); t.effect = s(); return t; }
-  // the state_node record of the grammar above: also the body of a NODE+ event (DeltaReader below)
+  // the state_node record of the grammar above: also the body of a NODE+ and of a NODE= event (DeltaReader below)
   StateNode state_node() {
     StateNode sn; sn.name = s(); sn.in_state = u() != 0; sn.labels = map();
     for (uint32_t m = cnt(); m; --m) sn.taints.push_back(taint());
@@ -158,9 +158,10 @@ class EnvReader : public SpecReader {
 //               | KSH_EVENT_NODE_REMOVE name:S                                       (NODE-)
 //               | KSH_EVENT_BIND        node_name:S nwords:U spec uid:S ts_lo:U ts_hi:U   (BIND: the pod blocks' spec record, nwords words; then uid and creationTimestamp)
 //               | KSH_EVENT_UNBIND      uid:S                                        (UNBIND)
+//               | KSH_EVENT_NODE_UPDATE state_node                                   (NODE=: the record NODE+ carries, for a node that is in state already)
 //
 // n_events is the block's own field (no count word leads the stream); the stream must hold exactly that many events and end with the last one.
-enum : uint32_t { kEventNodeAdd = KSH_EVENT_NODE_ADD, kEventNodeRemove = KSH_EVENT_NODE_REMOVE, kEventBind = KSH_EVENT_BIND, kEventUnbind = KSH_EVENT_UNBIND };
+enum : uint32_t { kEventNodeAdd = KSH_EVENT_NODE_ADD, kEventNodeRemove = KSH_EVENT_NODE_REMOVE, kEventBind = KSH_EVENT_BIND, kEventUnbind = KSH_EVENT_UNBIND, kEventNodeUpdate = KSH_EVENT_NODE_UPDATE };
 class DeltaReader : public EnvReader {
  public:
   DeltaReader(const ksh_pod_block& strings, const uint32_t* w, const uint32_t* e) : EnvReader(strings, w, e) {}
@@ -179,6 +180,7 @@ class DeltaReader : public EnvReader {
           e.pod = SpecReader(b_, w_, w_ + nw).read(); w_ += nw;
           e.pod.uid = s(); const uint64_t lo = u(), hi = u(); e.pod.creation_ts = (int64_t)(lo | (hi << 32));
         } else if (kind == kEventUnbind) { e.kind = DeltaEvent::PodUnbind; e.name = s(); }
+        else if (kind == kEventNodeUpdate) { e.kind = DeltaEvent::NodeUpdate; e.node = state_node(); }
         else throw Error("unknown event kind " + std::to_string(kind));
         ev.push_back(std::move(e));
       } catch (const Error& x) { throw Error("delta block: event " + std::to_string(k) + ": " + x.what()); }

@@ -488,13 +488,13 @@ def env_to_block(pr: "Problem") -> dict:
     return EnvBlockWriter().write(pr)
 
 
-EVENT_NODE_ADD, EVENT_NODE_REMOVE, EVENT_BIND, EVENT_UNBIND = 1, 2, 3, 4      # include/kshost.h KSH_EVENT_*
+EVENT_NODE_ADD, EVENT_NODE_REMOVE, EVENT_BIND, EVENT_UNBIND, EVENT_NODE_UPDATE = 1, 2, 3, 4, 5      # include/kshost.h KSH_EVENT_*
 
 
 class DeltaBlockWriter(EnvBlockWriter):
     """Binary EVENTS ingress (include/kshost.h `ksh_delta_block`, grammar in karpenter_core_amd/host/kspb.hpp DeltaReader): what a cgo shim would fill from the
     *v1.Node / *v1.Pod its informers hand it instead of printing KSD1 text -- per event a kind word, then the environment's state-node record (NODE+), a node name
-    (NODE-), a node name and the pod (BIND) or a pod uid (UNBIND), over one string table."""
+    (NODE-), a node name and the pod (BIND), a pod uid (UNBIND) or the state-node record again for a node that is in state already (NODE=), over one string table."""
 
     def write_events(self, events: Sequence[tuple]) -> dict:
         w = self._words
@@ -509,6 +509,9 @@ class DeltaBlockWriter(EnvBlockWriter):
                 self._pod(w, e[2])
             elif e[0] == "unbind":
                 w.extend((EVENT_UNBIND, self._s(e[1])))
+            elif e[0] == "node=":
+                w.append(EVENT_NODE_UPDATE)
+                self._node(w, e[1])
             else:
                 raise ValueError(f"unknown snapshot event {e[0]!r}")
         return dict(self._block(), n_events=len(events))
@@ -726,7 +729,9 @@ def delta_to_block(events: Sequence[tuple]) -> dict:
 def delta_to_ksd(events: Sequence[tuple]) -> str:
     """KSD1 text for `scheduler.ParsedProblem.apply` (kshost.h `ksh_env_apply`): what state.Cluster hears between two passes over the cluster
     (cluster.go UpdateNode / DeleteNode / UpdatePod / DeletePod).  Events, in order:
-        ("node+", StateNode) | ("node-", node_name) | ("bind", node_name, Pod) | ("unbind", pod_uid)"""
+        ("node+", StateNode) | ("node-", node_name) | ("bind", node_name, Pod) | ("unbind", pod_uid) | ("node=", StateNode)
+    `node=` replaces a node that is in state already (state.Cluster.UpdateNode after the first sight): slot and bound pods stay, everything the record carries is
+    taken as given."""
     w = io.StringIO()
     w.write(f"KSD1 {len(events)}\n")
     for e in events:
@@ -740,6 +745,9 @@ def delta_to_ksd(events: Sequence[tuple]) -> str:
             e[2].ksp(w)
         elif e[0] == "unbind":
             w.write(f"UNBIND {_tok(e[1])}")
+        elif e[0] == "node=":
+            w.write("NODE= ")
+            _ksp_node(e[1], w)
         else:
             raise ValueError(f"unknown snapshot event {e[0]!r}")
         w.write("\n")

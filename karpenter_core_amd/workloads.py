@@ -423,7 +423,68 @@ def cluster_after(nodes, bound, events):
                     break
             else:
                 raise KeyError(ev[1])
+        elif ev[0] == "node=":      # (the object is replaced -- its values as given, already net of the pods bound; the bound list and the slot stay)
+            find(ev[1].name)[0] = dataclasses.replace(ev[1], available=dict(ev[1].available))
     return [e[0] for e in live], [e[1] for e in live], [e[2] for e in live]
+
+
+# ---- node reconciliations: state.Cluster.UpdateNode for a node that is in state already (the `node=` event) ----
+UPDATE_KINDS = ("initialized", "taint", "zone", "available", "volume_limits", "owner")
+UPDATE_TAINTS = [Taint("node.example.com/maintenance", "true", NO_SCHEDULE), Taint("node.example.com/dedicated", "batch", NO_SCHEDULE)]
+
+
+def updated_node(rs, node, kind):
+    """`node` -- the object the cluster holds NOW (`cluster_after`'s: available net of the pods bound, usage following them) -- after one reconciliation of `kind`:
+    the initialised label flips (true <-> false), a taint of UPDATE_TAINTS is set or cleared, the zone label moves to another of ZONES, available cpu shrinks or
+    grows by a few hundred millicores, the CSINode limit of the EBS driver changes, or the provisioner-name label goes / comes back (owned <-> unowned).
+    A fresh object: every other field is the node's own."""
+    from .model import format_milli
+    n = dataclasses.replace(node, labels=dict(node.labels), taints=list(node.taints), available=dict(node.available), volume_limits=dict(node.volume_limits))
+    if kind == "initialized":
+        n.labels["karpenter.sh/initialized"] = "false" if n.labels.get("karpenter.sh/initialized") == "true" else "true"
+    elif kind == "taint":
+        t = UPDATE_TAINTS[int(rs.randint(len(UPDATE_TAINTS)))]
+        n.taints = [x for x in n.taints if x != t] if t in n.taints else n.taints + [t]
+    elif kind == "zone":
+        n.labels[LABEL_ZONE] = [z for z in ZONES if z != n.labels.get(LABEL_ZONE)][int(rs.randint(len(ZONES) - 1))]
+    elif kind == "available":
+        have = parse_quantity_milli(n.available["cpu"])
+        n.available["cpu"] = format_milli(max(0, have + int(rs.choice([-700, -300, 200, 500]))))
+    elif kind == "volume_limits":
+        n.volume_limits[EBS_DRIVER] = int(rs.choice([2, 3, 5, 25, 39]))
+    elif kind == "owner":
+        if n.labels.get(LABEL_PROVISIONER):
+            del n.labels[LABEL_PROVISIONER]
+        else:
+            n.labels[LABEL_PROVISIONER] = "default"
+    else:
+        raise ValueError(f"unknown node update {kind!r}")
+    return n
+
+
+def random_events_with_updates(rs, its, nodes, bound, n, tag, removes=True, make_pod=generic_pod, after=cluster_after, new_node=fresh_node, kinds=UPDATE_KINDS, share=0.25):
+    """`n` events against the cluster (nodes, bound) as it is, about `share` of them `node=` (a reconciliation of a random live node, of a random kind of
+    `kinds`), the others node+ / bind / unbind / node-; returns them with the cluster they lead to (`after`: the model, `cluster_after` or a wrapper of it)."""
+    events = []
+    for k in range(n):
+        if events:
+            nodes, bound, _ = after(nodes, bound, events[-1:])
+        if rs.rand() < share:
+            events.append(("node=", updated_node(rs, nodes[int(rs.randint(len(nodes)))], kinds[int(rs.randint(len(kinds)))])))
+            continue
+        kind = rs.choice(["node+", "bind", "bind", "bind"] + (["unbind", "unbind", "node-"] if removes else []))
+        if kind == "node+":
+            events.append(("node+", new_node(its, f"{tag}-node-{k}", rs)))
+        elif kind == "node-" and len(nodes) > 4:
+            events.append(("node-", nodes[int(rs.randint(len(nodes)))].name))
+        elif kind == "unbind" and any(bound):
+            i = int(rs.choice([j for j, b in enumerate(bound) if b]))
+            events.append(("unbind", bound[i][int(rs.randint(len(bound[i])))].uid))
+        else:
+            events.append(("bind", nodes[int(rs.randint(len(nodes)))].name, make_pod(rs, f"{tag}-pod-{k}")))
+    if events:
+        nodes, bound, _ = after(nodes, bound, events[-1:])
+    return events, nodes, bound
 
 
 # ---- a cloud-like catalogue with 9 to 16 resource names ----
