@@ -139,6 +139,11 @@ int ksh_grid(void* handle, uint64_t* out /* [M][C][ceil(T/64)] or NULL */, float
  * handle's device and copied out (host and / or device destination, either may be NULL); rows computed elsewhere installed (complete != 0 with the last of them). */
 int ksh_grid_rows(void* handle, uint32_t row_lo, uint32_t row_hi, uint64_t* out_rows, void* out_rows_dev, float* kernel_ms);
 int ksh_grid_install(void* handle, uint32_t row_lo, uint32_t row_hi, const uint64_t* rows, const void* rows_dev, int complete);
+/* Diagnostics.  ksh_debug_grid: ks_debug_grid of ksolve.h for a handle -- the grid as the last build left it (a batch's included), read-only, nothing launched;
+ * KS_ERR_INVALID before an upload or while the grid is not built.  ksh_debug_pod_classes: out[i] = the pod class (grid row c, before relaxation) of pod i of the
+ * handle's problem, in the caller's pod order; KS_ERR_UNSUPPORTED for a what-if derived on the device (it has no flattening of its own). */
+int ksh_debug_grid(void* handle, uint64_t* out /* [M][C][ceil(T/64)] */);
+int ksh_debug_pod_classes(void* handle, uint32_t* out /* [P] */);
 int ksh_solve_ksp(const char* ksp_text, size_t len, uint32_t flags, char** out_text);  /* one shot: KSP1 in, KSR1 out */
 
 /* ---- results ---- */

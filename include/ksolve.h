@@ -342,6 +342,9 @@ int ks_solve_batch(const ks_problem* const* p, uint32_t n, ks_result* const* out
 /* The static pod-class x instance-type feasibility grid for fresh nodes of every template:
  * out_grid[(m*C + c)*TW + w].  Exposed for parity tests and roofline measurement. */
 int ks_feasibility_grid(ks_dev_problem* d, uint64_t* out_grid, float* kernel_ms);
+/* Diagnostics: the M * C * TW words of the grid as the last build left it -- ks_feasibility_grid rebuilds before it copies, so the grid a batch built
+ * (ks_solve_batch_dev) shows only here.  Read-only, launches nothing; KS_ERR_INVALID while the grid has not been built (or installed completely). */
+int ks_debug_grid(ks_dev_problem* d, uint64_t* out_grid);
 /* SURVEY 8e row 2 -- the static grid's rows split over GPUs (node.go:137-159 for a fresh node of template m and a pod of class c is row m * C + c, ceil(T/64) words):
  * ks_feasibility_grid_rows computes rows [row_lo, row_hi) on this device (every other static table in full) and copies them to host memory (out_rows) and / or into
  * device memory of the caller's (out_rows_dev: e.g. its slice of the buffer ONE all-gather fills); ks_feasibility_grid_install puts rows computed elsewhere in place

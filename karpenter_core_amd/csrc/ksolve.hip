@@ -3299,10 +3299,13 @@ extern "C" int ks_whatifs_pod_ids(ks_whatif_batch* b, uint32_t i, uint32_t* out)
 
 // Build the derived tables + the feasibility grid (idempotent).  Returns the grid kernels' time.
 // Launch the static-table kernels for the problems behind `probs` (device descriptor array, n of them) on one stream.
-struct StaticDims { u32 rows = 0, C = 0, RT = 0, TW = 1, R = 0; size_t MC = 0; };
-static void static_dims_of(const DevProb& h, StaticDims& a) {
+// (grid_waves: the widest ks_grid_types launch a member needs.  It is a maximum of per-member products, TW_i * ks_grid_chunks(MC_i, TW_i, wave_target): the product of
+// the batch's maxima is NOT an upper bound of it -- TW * ceil(wave_target / TW) is not monotone in TW, e.g. 4 * 32 = 128 < 3 * 43 = 129 at wave_target 128.)
+struct StaticDims { u32 rows = 0, C = 0, RT = 0, R = 0; size_t MC = 0, grid_waves = 0; };
+static void static_dims_of(const DevProb& h, u32 wave_target, StaticDims& a) {
   if (!h.derived_shared) { a.rows = std::max(a.rows, h.K * 64 + 2 * h.K + 64); a.RT = std::max(a.RT, h.R * h.T); }
-  a.C = std::max(a.C, h.C); a.MC = std::max(a.MC, (size_t)h.M * h.C); a.TW = std::max(a.TW, h.TW); a.R = std::max(a.R, h.R);
+  a.C = std::max(a.C, h.C); a.MC = std::max(a.MC, (size_t)h.M * h.C); a.R = std::max(a.R, h.R);
+  if ((size_t)h.M * h.C) a.grid_waves = std::max(a.grid_waves, (size_t)h.TW * ks_grid_chunks((size_t)h.M * h.C, h.TW, wave_target));
 }
 static void launch_static(const DevProb* probs, u32 n, const StaticDims& a, u32 wave_target, hipStream_t st, hipEvent_t before_grid, u32 row_lo = 0, u32 row_hi = 0xFFFFFFFFu) {
   if (a.rows) hipLaunchKernelGGL(ks_build_type_tables, dim3((a.rows * 64 + 255) / 256, n), dim3(256), 0, st, probs);
@@ -3319,7 +3322,7 @@ static void launch_static(const DevProb* probs, u32 n, const StaticDims& a, u32 
   if (before_grid) hipEventRecord(before_grid, st);
   if (a.MC) {
     hipLaunchKernelGGL(ks_grid_mc, dim3((u32)((a.MC + 255) / 256), n), dim3(256), 0, st, probs);
-    const size_t waves = (size_t)a.TW * ks_grid_chunks(a.MC, a.TW, wave_target);      // (an upper bound over the batch: a problem's surplus waves return at once)
+    const size_t waves = a.grid_waves;      // (the widest member's TW * chunks, for the same wave_target the kernel decodes with: a narrower problem's surplus waves return at once)
     if (a.R > KS_RES_NARROW) { hipLaunchKernelGGL(ks_grid_types_wide, dim3((u32)((waves * 64 + 255) / 256), n), dim3(256), 0, st, probs, wave_target, row_lo, row_hi); }
     else { hipLaunchKernelGGL(ks_grid_types, dim3((u32)((waves * 64 + 255) / 256), n), dim3(256), 0, st, probs, wave_target, row_lo, row_hi); }
   }
@@ -3328,7 +3331,7 @@ static void launch_static(const DevProb* probs, u32 n, const StaticDims& a, u32 
 static int build_static(ks_dev_problem* d, float* grid_ms, u32 row_lo = 0, u32 row_hi = 0xFFFFFFFFu) {
   HIPCHK(hipSetDevice(d->device));
   hipEvent_t e0 = nullptr, e1 = nullptr; HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
-  StaticDims a; static_dims_of(d->h, a);
+  StaticDims a; static_dims_of(d->h, 8192, a);
   launch_static(d->d_prob, 1, a, 8192, d->stream, e0, row_lo, row_hi);
   d->tables_built = row_lo == 0 && (size_t)row_hi >= (size_t)d->h.M * d->h.C;      // (a row range: the grid is whole once the other rows are installed)
   HIPCHK(hipEventRecord(e1, d->stream));
@@ -3349,6 +3352,17 @@ extern "C" int ks_feasibility_grid(ks_dev_problem* d, uint64_t* out_grid, float*
   if (!d) return fail(KS_ERR_INVALID, "null device problem");
   TRY(build_static(d, kernel_ms));
   if (out_grid) HIPCHK(hipMemcpy(out_grid, d->h.grid, (size_t)d->h.M * d->h.C * d->h.TW * sizeof(u64), hipMemcpyDeviceToHost));
+  return KS_OK;
+}
+
+// Diagnostics: the grid as it stands -- what the last build (one problem's, or a batch's in ks_solve_batch_dev) or ks_feasibility_grid_install left.  Copies only: nothing is
+// launched, nothing rebuilt.  Refused while the grid is not whole.
+extern "C" int ks_debug_grid(ks_dev_problem* d, uint64_t* out_grid) {
+  if (!d || !out_grid) return fail(KS_ERR_INVALID, "null argument");
+  if (!d->tables_built) return fail(KS_ERR_INVALID, "the feasibility grid has not been built");
+  HIPCHK(hipSetDevice(d->device));
+  const size_t bytes = (size_t)d->h.M * d->h.C * d->h.TW * sizeof(u64);
+  if (bytes) HIPCHK(hipMemcpy(out_grid, d->h.grid, bytes, hipMemcpyDeviceToHost));
   return KS_OK;
 }
 
@@ -3539,8 +3553,9 @@ extern "C" int ks_solve_batch_dev(ks_dev_problem* const* ds, uint32_t n, ks_resu
     // The static tables of the whole batch in seven launches (grid.y = what-if) instead of seven per what-if.  The uploads were queued on
     // the what-ifs' own streams: one wait for all of them first.  (Problems built earlier are rebuilt in place: the build is idempotent.)
     HIPCHK(hipDeviceSynchronize());
-    StaticDims a; for (u32 i = 0; i < n; ++i) static_dims_of(ds[i]->h, a);
-    launch_static(dp, n, a, std::max(64u, 16384u / n), st, nullptr);
+    const u32 wave_target = std::max(64u, 16384u / n);
+    StaticDims a; for (u32 i = 0; i < n; ++i) static_dims_of(ds[i]->h, wave_target, a);
+    launch_static(dp, n, a, wave_target, st, nullptr);
     for (u32 i = 0; i < n; ++i) ds[i]->tables_built = true;
   }
   hipEvent_t e0, e1; HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));

@@ -686,6 +686,21 @@ int ksh_grid_install(void* hv, uint32_t row_lo, uint32_t row_hi, const uint64_t*
   return KS_OK;
 }
 
+// Diagnostics: the grid as the last build left it (nothing launched), and the class row of every pod as submitted (stage 0 of its relaxation chain).
+int ksh_debug_grid(void* hv, uint64_t* out) {
+  Handle* h = (Handle*)hv; if (!h || !h->dev) return set_err(KS_ERR_INVALID, "grid of a handle that was not uploaded");
+  const int rc = ks_debug_grid(h->dev, out);
+  if (rc != KS_OK) return set_err(rc, ks_last_error());
+  return KS_OK;
+}
+int ksh_debug_pod_classes(void* hv, uint32_t* out) {
+  Handle* h = (Handle*)hv; if (!h || !out) return set_err(KS_ERR_INVALID, "null argument");
+  if (h->enc->view) return set_err(KS_ERR_UNSUPPORTED, "a what-if derived on the device has no flattening of its own");
+  const ks_problem& p = h->enc->prob;
+  for (uint32_t i = 0; i < p.P; ++i) out[i] = p.stage_cls[p.pod_stage_off[i]];
+  return KS_OK;
+}
+
 // One-shot convenience: KSP1 text in, KSR1 text out.
 int ksh_solve_ksp(const char* ksp_text, size_t len, uint32_t flags, char** out_text) {
   void* h = nullptr; int rc = ksh_open(ksp_text, len, flags, &h); if (rc != KS_OK) return rc;

@@ -66,6 +66,8 @@ def libs():
         kh.ksh_grid.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]
         kh.ksh_grid_rows.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]
         kh.ksh_grid_install.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
+        kh.ksh_debug_grid.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        kh.ksh_debug_pod_classes.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
         kh.ksh_price_filter.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint32),
                                         ctypes.POINTER(ctypes.c_uint64), ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]
         kh.ksh_dims.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32)]
@@ -250,6 +252,26 @@ class FlatProblem:
             raise KSolveError(rc, kh.ksh_last_error().decode())
         return arr, float(ms.value)
 
+    def built_grid(self):
+        """ksh_debug_grid: the grid as the last build left it -- this handle's own, or the batch's it was solved in (`grid()` rebuilds before it copies) -- as numpy
+        uint64 [M, C, TW].  Read-only, nothing is launched; raises KS_ERR_INVALID before an upload or while the grid is not built."""
+        import numpy as np
+        kh = libs()[1]
+        arr = np.zeros((self.dims["M"], self.dims["C"], (self.dims["T"] + 63) // 64), dtype=np.uint64)
+        rc = kh.ksh_debug_grid(self._h, arr.ctypes.data)
+        if rc != KS_OK:
+            raise KSolveError(rc, kh.ksh_last_error().decode())
+        return arr
+
+    def pod_classes(self):
+        """ksh_debug_pod_classes: numpy uint32 [P], the pod class (grid row c) of every pod as submitted, in the caller's pod order."""
+        import numpy as np
+        kh = libs()[1]
+        arr = np.zeros(max(1, self.dims["P"]), dtype=np.uint32)
+        rc = kh.ksh_debug_pod_classes(self._h, arr.ctypes.data)
+        if rc != KS_OK:
+            raise KSolveError(rc, kh.ksh_last_error().decode())
+        return arr[:self.dims["P"]]
 
     def grid_rows(self, lo: int, hi: int, dev_ptr: int = 0):
         """ksh_grid_rows: rows [lo, hi) of the M * C grid rows computed on this handle's device; returns (numpy uint64 [hi - lo, TW], kernel ms).  dev_ptr: also
