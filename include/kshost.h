@@ -126,6 +126,7 @@ int ksh_result_arrays_get(void* handle, ksh_result_arrays* out);
 const char* ksh_name(void* handle, int what /* 0 key, 1 value b of key a, 2 resource */, uint32_t a, uint32_t b);
 int ksh_pack_width(void* handle, int* out);                                              /* ks_problem_pack_width of the handle's device problem: 4, 8 or 16 (the wide variants), 0 if ks_pack_rr took the last solve */
 int ksh_pack_lean(void* handle, int* out);                                               /* ks_problem_pack_lean of the handle's device problem: 1 if the ks_pack variant of the last solve was a LEAN one (width 4, or 8 under KSH_ACTIVE_RESOURCES) */
+int ksh_pack_row(void* handle, int* out);                                                /* ks_problem_pack_row of the handle's device problem: the row of the ks_pack instantiation table the last solve launched, -1 if ks_pack_rr took it or nothing ran */
 int ksh_rr_status(void* handle, int out[2]);                                           /* ks_problem_rr_status of the handle's device problem: out[0] ks_pack_rr was launched, out[1] why it declined (0: it took the Solve) */
 void ksh_dims(void* handle, uint32_t dims[10]);                                        /* P,C,T,M,E,K,R,G,GH,S */
 uint64_t ksh_fingerprint(void* handle);                                                /* hash of every array of the flat problem */

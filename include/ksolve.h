@@ -259,6 +259,7 @@ int ks_problem_rr_status(const ks_dev_problem* d, int* started, int* decline_cod
  * what-if batch holding one); 0 if ks_pack_rr took it.  Diagnostics only, like ks_problem_rr_status. */
 int ks_problem_pack_width(const ks_dev_problem* d, int* rm);
 int ks_problem_pack_lean(const ks_dev_problem* d, int* lean);      /* its neighbour: 1 if the ks_pack variant the last solve ran was a LEAN one (at width 4, or 8 under ks_problem.lean_r8), else 0 */
+int ks_problem_pack_row(const ks_dev_problem* d, int* row);        /* and which instantiation exactly: the index into the library's table of ks_pack instantiations (ks_debug_pack_row names its FAST, BOUNDS, LEAN, waves, RM) that the last solve of `d` -- alone or as a member of a batch -- launched; -1 if ks_pack_rr took it or nothing ran */
 int ks_problem_upload(const ks_problem* p, int device, ks_dev_problem** out);
 void ks_problem_free(ks_dev_problem* d);
 /* Consolidation what-ifs over ONE cluster snapshot (deprovisioning/helpers.go:42-99) differ in their pods and in which state nodes stay, not in

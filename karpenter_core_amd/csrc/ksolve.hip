@@ -2802,6 +2802,7 @@ struct ks_dev_problem {
   bool view = false;             // a what-if derived from a resident snapshot (ks_whatifs_open): memory and stream belong to its ks_whatif_batch
   int pack_rm = 0;                 // the last solve: resource bound of the ks_pack variant that ran (4, 8, 16), 0 if ks_pack_rr took it
   int pack_lean = 0;               // the last solve: 1 if that variant was a LEAN one
+  int pack_row = -1;               // the last solve: index into pack_rows of the instantiation that ran, -1 if ks_pack_rr took it (or nothing ran)
   int rr_started = 0, rr_code = 0; // the last solve: ks_pack_rr was launched | why it declined (0: it took the Solve; the codes are in ks_pack_rr.inc)
   bool no_multi = false;         // ... over a snapshot with topology groups: the class briefs (round eligibility, certain records) were built for the snapshot's group activity, not this what-if's -- single-wave kernel only
 };
@@ -2889,6 +2890,7 @@ extern "C" int ks_current_device(void) { int d = 0; if (hipGetDevice(&d) != hipS
 extern "C" int ks_problem_device(const ks_dev_problem* d) { return d ? d->device : -1; }
 extern "C" int ks_problem_pack_width(const ks_dev_problem* d, int* rm) { if (!d || !rm) return fail(KS_ERR_INVALID, "null argument"); *rm = d->pack_rm; return KS_OK; }
 extern "C" int ks_problem_pack_lean(const ks_dev_problem* d, int* lean) { if (!d || !lean) return fail(KS_ERR_INVALID, "null argument"); *lean = d->pack_lean; return KS_OK; }
+extern "C" int ks_problem_pack_row(const ks_dev_problem* d, int* row) { if (!d || !row) return fail(KS_ERR_INVALID, "null argument"); *row = d->pack_row; return KS_OK; }
 extern "C" int ks_problem_rr_status(const ks_dev_problem* d, int* started, int* decline_code) { if (!d) return fail(KS_ERR_INVALID, "null problem"); if (started) *started = d->rr_started; if (decline_code) *decline_code = d->rr_code; return KS_OK; }
 
 static int validate(const ks_problem* p) {
@@ -3569,7 +3571,7 @@ extern "C" int ks_solve_batch_dev(ks_dev_problem* const* ds, uint32_t n, ks_resu
     bounds = bounds || ds[i]->any_bounds; lean = lean && ds[i]->lean_ok; any_flags |= q.flags;
     wide = wide || q.R > KS_RES_NARROW;      // (R > 8: never LEAN, so never ks_pack_rr)
     lean8 = lean8 || q.R > 4;                // a LEAN problem with 5..8 resources (ks_problem.lean_r8): the LEAN variants' RM = 8 instantiations; ks_pack_rr stays at 4
-    ds[i]->rr_started = 0; ds[i]->rr_code = 0; ds[i]->pack_rm = 0; ds[i]->pack_lean = 0;
+    ds[i]->rr_started = 0; ds[i]->rr_code = 0; ds[i]->pack_rm = 0; ds[i]->pack_lean = 0; ds[i]->pack_row = -1;
   }
   // the flag bits of ksolve.h, and the variables that ask the same of the whole process (test hooks)
   if (getenv("KS_NO_LEAN") || (any_flags & KS_FLAG_NO_LEAN)) lean = false;                                // the general variant on a problem the LEAN one would take
@@ -3641,7 +3643,7 @@ extern "C" int ks_solve_batch_dev(ks_dev_problem* const* ds, uint32_t n, ks_resu
       }
     }
     hipLaunchKernelGGL(r.fn, dim3(n), dim3(64 * r.nw), lds, st, dp, dsv, lds);
-    for (u32 i = 0; i < n; ++i) { ds[i]->pack_rm = r.rm; ds[i]->pack_lean = r.lean; }
+    for (u32 i = 0; i < n; ++i) { ds[i]->pack_rm = r.rm; ds[i]->pack_lean = r.lean; ds[i]->pack_row = row; }
   }
 #endif
   HIPCHK(hipEventRecord(e1, st));

@@ -1371,6 +1371,7 @@ const char* ksh_snapshot_it_state_value(void* parsed, uint32_t state, uint32_t i
 }
 int ksh_pack_width(void* hv, int* out) { Handle* h = (Handle*)hv; if (!h || !h->dev) return KS_ERR_INVALID; return ks_problem_pack_width(h->dev, out); }
 int ksh_pack_lean(void* hv, int* out) { Handle* h = (Handle*)hv; if (!h || !h->dev) return KS_ERR_INVALID; return ks_problem_pack_lean(h->dev, out); }
+int ksh_pack_row(void* hv, int* out) { Handle* h = (Handle*)hv; if (!h || !h->dev) return KS_ERR_INVALID; return ks_problem_pack_row(h->dev, out); }
 int ksh_rr_status(void* hv, int* out2) { Handle* h = (Handle*)hv; if (!h || !h->dev) return KS_ERR_INVALID; return ks_problem_rr_status(h->dev, out2, out2 + 1); }
 void ksh_dims(void* hv, uint32_t* d) { const ks_problem& p = ((Handle*)hv)->enc->prob; uint32_t v[10] = {p.P, p.C, p.T, p.M, p.E, p.K, p.R, p.G, p.GH, p.S}; memcpy(d, v, sizeof v); }
 

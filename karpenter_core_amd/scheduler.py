@@ -74,6 +74,8 @@ def libs():
         kh.ksh_rr_status.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]
         kh.ksh_pack_width.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]
         kh.ksh_pack_lean.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]
+        kh.ksh_pack_row.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]
+        ks.ks_debug_pack_row.argtypes = [ctypes.c_uint32, ctypes.POINTER(ctypes.c_int32)]
         kh.ksh_solve_whatifs_sharded.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint64), ctypes.c_uint32, ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]
         ks.ks_deal_lpt.argtypes = [ctypes.POINTER(ctypes.c_uint64), ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]
         ks.ks_deal_lpt.restype = None
@@ -195,6 +197,22 @@ class FlatProblem:
         if rc != KS_OK:
             raise KSolveError(rc, "ksh_pack_lean")
         return bool(out.value)
+
+    def pack_row(self):
+        """Which ks_pack instantiation took the last solve (alone or as a member of a batch): (row, FAST, BOUNDS, LEAN, NW, RM) -- the row's index in the library's
+        table and its fields as `ks_debug_pack_row` names them -- or None if ks_pack_rr took it or nothing ran.  include/ksolve.h ks_problem_pack_row."""
+        ks, kh = libs()
+        out = ctypes.c_int()
+        rc = kh.ksh_pack_row(self._h, ctypes.byref(out))
+        if rc != KS_OK:
+            raise KSolveError(rc, "ksh_pack_row")
+        row = int(out.value)
+        if row < 0:
+            return None
+        f = (ctypes.c_int32 * 6)()
+        if row >= ks.ks_debug_pack_row(row, f):
+            raise KSolveError(KS_ERR_INVALID, f"ksh_pack_row: row {row} is not in the table")
+        return (row, bool(f[0]), bool(f[1]), bool(f[2]), int(f[3]), int(f[4]))
 
     def resource_names(self) -> List[str]:
         """The resource universe of the flat problem, by id (kshost.h ksh_name(h, 2, r, 0)): with `active_resources` the active names only."""
