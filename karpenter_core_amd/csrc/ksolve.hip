@@ -2783,22 +2783,71 @@ struct TmpDev {
 };
 }  // namespace
 
+#define TRY(x) do { int rc_ = (x); if (rc_ != KS_OK) return rc_; } while (0)
+
+// One device arena in four regions -- [copied from the host | zero-filled | 0xFF-filled | uninitialised], pieces 256-byte aligned -- laid out by running ONE layout
+// function twice: a measuring pass sizes the regions, a placing pass hands out pointers and packs the host data into ONE pinned staging buffer, which goes over in
+// ONE transfer.  The two passes are checked against each other: a piece the placing pass takes beyond, or leaves short of, what was measured is an error.
+static inline size_t ks_align256(size_t b) { return (b + 255) & ~(size_t)255; }
+struct Arena {
+  enum { COPIED = 0, ZEROED = 1, ONES = 2, RAW = 3 };
+  bool measure = true; size_t sz[4] = {0, 0, 0, 0}, off[4] = {0, 0, 0, 0}; u8* base[4] = {nullptr, nullptr, nullptr, nullptr}; u8* stage = nullptr;      // (pinned; sz[COPIED] bytes)
+  size_t bytes() const { return sz[0] + sz[1] + sz[2] + sz[3]; }
+  template <class F> int lay(int device, F&& layout) {
+    measure = true; TRY(layout());
+    { void* a = nullptr; TRY(pool().get(device, bytes(), false, &a)); base[0] = (u8*)a; void* st = nullptr; TRY(pool().get(device, sz[0], true, &st)); stage = (u8*)st; }
+    for (int r = 1; r < 4; ++r) base[r] = base[r - 1] + sz[r - 1];
+    measure = false; TRY(layout());
+    for (int r = 0; r < 4; ++r) if (off[r] != sz[r]) return fail(KS_ERR_INTERNAL, "arena: the two layout passes disagree");
+    return KS_OK;
+  }
+  // the staged host data over, the fills queued.  Diagnostic: KS_POISON=<byte> fills the region the kernels must initialise themselves before reading (queue, node
+  // records' tails, alive rows, ladder indices, order array, ...).  Results must not depend on it (tests/test_parity.py::test_poisoned_arena, tools/stress_cold.py).
+  int send(hipStream_t st) {
+    HIPCHK(hipMemcpyAsync(base[COPIED], stage, sz[COPIED], hipMemcpyHostToDevice, st));
+    if (sz[ZEROED]) HIPCHK(hipMemsetAsync(base[ZEROED], 0, sz[ZEROED], st));
+    if (sz[ONES]) HIPCHK(hipMemsetAsync(base[ONES], 0xFF, sz[ONES], st));
+    if (const char* pz = getenv("KS_POISON")) { if (sz[RAW]) HIPCHK(hipMemsetAsync(base[RAW], (int)strtol(pz, nullptr, 0) & 0xFF, sz[RAW], st)); }
+    return KS_OK;
+  }
+  void release(int device) { pool().put(device, bytes(), false, base[0]); pool().put(device, sz[0], true, stage); base[0] = nullptr; stage = nullptr; }
+};
+static int arena_take(Arena& a, int region, size_t bytes, void** out) {
+  bytes = ks_align256(bytes ? bytes : 1);
+  if (a.measure) { a.sz[region] += bytes; *out = nullptr; return KS_OK; }
+  if (a.off[region] + bytes > a.sz[region]) return fail(KS_ERR_INTERNAL, "arena: the two layout passes disagree");
+  *out = a.base[region] + a.off[region]; a.off[region] += bytes; return KS_OK;
+}
+// n elements in the copied region for the caller to fill in place: *host is their place in the staging buffer, zeroed (nullptr on the measuring pass)
+template <typename T> static int dev_stage(Arena& a, size_t n, const T** dst, T** host) {
+  void* p = nullptr; const size_t at = a.off[Arena::COPIED];
+  TRY(arena_take(a, Arena::COPIED, n * sizeof(T), &p));
+  *host = a.measure ? nullptr : (T*)(a.stage + at); if (*host && n) memset(*host, 0, n * sizeof(T));
+  *dst = (const T*)p; return KS_OK;
+}
+template <typename T> static int dev_copy(Arena& a, const T* src, size_t n, const T** dst) {
+  if (n && !src) return fail(KS_ERR_INVALID, "null array in ks_problem");
+  void* p = nullptr; const size_t at = a.off[Arena::COPIED];
+  TRY(arena_take(a, Arena::COPIED, n * sizeof(T), &p));
+  if (!a.measure && n) memcpy(a.stage + at, src, n * sizeof(T));
+  *dst = (const T*)p; return KS_OK;
+}
+template <typename T> static int dev_alloc(Arena& a, size_t n, T** dst, int fill = -2) {
+  void* p = nullptr; TRY(arena_take(a, fill == 0 ? Arena::ZEROED : (fill == -2 ? Arena::RAW : Arena::ONES), n * sizeof(T), &p));
+  *dst = (T*)p; return KS_OK;
+}
+
 struct ks_dev_problem {
   int device = 0;
   DevProb h{};                     // host copy of the device view (pointers are device pointers)
   DevProb* d_prob = nullptr;       // the same struct in device memory (for ks_pack)
   DevState hs{}; DevState* d_state = nullptr;
-  // one device arena: [copied from the host | zero-filled | 0xFF-filled | uninitialised]; sub-allocations are 256-byte aligned.
-  // ks_problem_upload lays the problem out twice: a measuring pass sizes the regions, a placing pass hands out pointers and
-  // packs the host data into ONE pinned staging buffer, which goes over in ONE transfer.
-  bool measure = true; size_t sz[4] = {0, 0, 0, 0}, off[4] = {0, 0, 0, 0}; u8* base[4] = {nullptr, nullptr, nullptr, nullptr};
-  u8* arena = nullptr; size_t arena_bytes = 0; u8* stage = nullptr; size_t stage_bytes = 0;
+  Arena a;                         // everything of the problem on the device (empty in a view)
   hipStream_t stream = nullptr;
   bool tables_built = false;
   ks_problem src{};              // the host arrays this problem was uploaded from (pointer identity decides what a what-if can share with it)
   bool any_bounds = false;       // some requirement carries Gt/Lt -> the BOUNDS kernel variant
   bool lean_ok = false;          // none of the rarely used features is present -> the LEAN kernel variant (see ks_pack)
-  u32 pp_cap = 0;
   bool view = false;             // a what-if derived from a resident snapshot (ks_whatifs_open): memory and stream belong to its ks_whatif_batch
   int pack_rm = 0;                 // the last solve: resource bound of the ks_pack variant that ran (4, 8, 16), 0 if ks_pack_rr took it
   int pack_lean = 0;               // the last solve: 1 if that variant was a LEAN one
@@ -2806,26 +2855,6 @@ struct ks_dev_problem {
   int rr_started = 0, rr_code = 0; // the last solve: ks_pack_rr was launched | why it declined (0: it took the Solve; the codes are in ks_pack_rr.inc)
   bool no_multi = false;         // ... over a snapshot with topology groups: the class briefs (round eligibility, certain records) were built for the snapshot's group activity, not this what-if's -- single-wave kernel only
 };
-
-static inline size_t ks_align256(size_t b) { return (b + 255) & ~(size_t)255; }
-static int arena_take(ks_dev_problem* d, int region, size_t bytes, void** out) {
-  bytes = ks_align256(bytes ? bytes : 1);
-  if (d->measure) { d->sz[region] += bytes; *out = nullptr; return KS_OK; }
-  if (d->off[region] + bytes > d->sz[region]) return fail(KS_ERR_INTERNAL, "upload: the two layout passes disagree");
-  *out = d->base[region] + d->off[region]; d->off[region] += bytes; return KS_OK;
-}
-template <typename T> static int dev_copy(ks_dev_problem* d, const T* src, size_t n, const T** dst) {
-  if (n && !src) return fail(KS_ERR_INVALID, "null array in ks_problem");
-  void* p = nullptr; const size_t at = d->off[0];
-  int rc = arena_take(d, 0, n * sizeof(T), &p); if (rc != KS_OK) return rc;
-  if (!d->measure && n) memcpy(d->stage + at, src, n * sizeof(T));
-  *dst = (const T*)p; return KS_OK;
-}
-template <typename T> static int dev_alloc(ks_dev_problem* d, size_t n, T** dst, int fill = -2) {
-  void* p = nullptr; int rc = arena_take(d, fill == 0 ? 1 : (fill == -2 ? 3 : 2), n * sizeof(T), &p); if (rc != KS_OK) return rc;
-  *dst = (T*)p; return KS_OK;
-}
-#define TRY(x) do { int rc_ = (x); if (rc_ != KS_OK) return rc_; } while (0)
 
 // What a call over a batch of resident problems sends to its kernel, and reads back: [DevProb n | DevState n | the caller's segments ...] in ONE host block and
 // ONE device block, every segment 16-byte aligned.  open() makes the refusals every such call shares and selects the device; add() reserves a segment; place()
@@ -2871,12 +2900,47 @@ struct BatchStage {
   }
 };
 
+// The arrays of one Solve's mutable state (DevState), each named ONCE: element type from the pointer, count, region.  A problem uploaded from the host
+// (ks_problem_upload) and a what-if derived on the device (ks_whatifs_open) both lay their state out through here; where they differ on purpose, a switch says so.
+struct StateDims {
+  size_t P, NMAX, E, M, R, K, TW, C, G, GH, ND, SW;
+  size_t pp_cap;            // entries of the host-port pool: the caller's own bound on the existing reservations plus the ports its pods can bring
+  bool hcnt_filled;         // uploaded: hcnt comes 0xFF-filled, every (node, hostname group) reads -1, "not a registered domain".  derived: uninitialised -- the pack prologue writes every existing node's row (ks_host_count0) and the opening of a node writes its row's entry for every hostname-keyed group (0 if the group is active, else -1), both before the row is read
+  bool topology;            // uploaded: always, pieces of one element where G or GH is 0.  derived from a snapshot without groups: gcnt .. g_hzero stay null -- the prologue's loops over G and GH make no trip, and ks_derive_topology, which gives a what-if its own group activity and counts, is not launched
+  bool round_scratch;       // uploaded: always.  derived: only a batch of one -- the rows a round keeps to restore are the multi-wave rows' alone, which a batch of several is never launched on
+  bool volumes;             // uploaded: always, pieces of one element where ND is 0.  derived: only when opened with KS_WHATIFS_VOLUMES over a snapshot with drivers; the prologue then copies en_vol_count / en_vol_set into them like any problem's, and without drivers its loops over E * ND and E * SW make no trip
+};
+static int state_layout(Arena& a, const StateDims& d, DevState& s) {
+  const size_t P = d.P, NM = d.NMAX, NS = d.E + d.NMAX, K = d.K, R = d.R, TW = d.TW;
+  s = DevState{}; s.rec_stride = ks_rec_stride((u32)R, (u32)K); s.pp_cap = (u32)d.pp_cap;
+  TRY(dev_alloc(a, P, &s.q)); TRY(dev_alloc(a, P, &s.lastlen)); TRY(dev_alloc(a, P, &s.lastgen));
+  TRY(dev_alloc(a, NS * s.rec_stride, &s.rec, 0));
+  TRY(dev_alloc(a, (NM + 1) * TW, &s.n_alive)); TRY(dev_alloc(a, 2 * NS, &s.lowi));
+  if (d.round_scratch) TRY(dev_alloc(a, (size_t)8 * 64 * TW, &s.round_scratch));
+  TRY(dev_alloc(a, P + 4, &s.bstart, 0)); TRY(dev_alloc(a, NM, &s.order_g));
+  if (d.topology) {
+    TRY(dev_alloc(a, d.G * 64, &s.gcnt)); TRY(dev_alloc(a, d.G, &s.g_reg)); TRY(dev_alloc(a, d.G, &s.g_pos)); TRY(dev_alloc(a, d.G, &s.g_active));
+    TRY(dev_alloc(a, d.GH * NS, &s.hcnt, d.hcnt_filled ? 0xFF : -2)); TRY(dev_alloc(a, d.GH, &s.g_hpos)); TRY(dev_alloc(a, d.GH, &s.g_hzero));
+  }
+  TRY(dev_alloc(a, d.M * R, &s.remaining));
+  TRY(dev_alloc(a, d.pp_cap, &s.pp_entry)); TRY(dev_alloc(a, d.pp_cap, &s.pp_next));
+  if (d.volumes) { TRY(dev_alloc(a, d.E * d.ND, &s.vol_cnt)); TRY(dev_alloc(a, d.E * d.SW, &s.vol_set)); }
+  TRY(dev_alloc(a, d.C, &s.wm));
+  TRY(dev_alloc(a, 32, &s.stats, 0)); TRY(dev_alloc(a, 4, &s.out_counts, 0));
+  // the result arrays (KS_RESULT_SEGS names what is read back of them)
+  TRY(dev_alloc(a, P, &s.pod_stage)); TRY(dev_alloc(a, P, &s.pod_node)); TRY(dev_alloc(a, P, &s.pod_seq)); TRY(dev_alloc(a, P, &s.pod_reason)); TRY(dev_alloc(a, P, &s.unscheduled));
+  TRY(dev_alloc(a, NM, &s.n_tmpl));
+  TRY(dev_alloc(a, NM, &s.o_present)); TRY(dev_alloc(a, NM, &s.o_complement)); TRY(dev_alloc(a, NM * K, &s.o_mask)); TRY(dev_alloc(a, NM * K, &s.o_gt)); TRY(dev_alloc(a, NM * K, &s.o_lt));
+  TRY(dev_alloc(a, NM, &s.o_it)); TRY(dev_alloc(a, NM * R, &s.o_req)); TRY(dev_alloc(a, NM, &s.o_reqmask));
+  return KS_OK;
+}
+
 static int copy_reqsets(ks_dev_problem* d, const ks_reqsets& s, u32 n, u32 K, ReqSetsD* out) {
-  out->n = n;
+  out->n = n; Arena& a = d->a;
   for (size_t i = 0; i < (size_t)n * K; ++i) if (s.gt[i] != KS_NO_BOUND_GT || s.lt[i] != KS_NO_BOUND_LT) d->any_bounds = true;
-  TRY(dev_copy(d, s.present, n, &out->present)); TRY(dev_copy(d, s.complement, n, &out->complement));
-  TRY(dev_copy(d, s.mask, (size_t)n * K, &out->mask)); TRY(dev_copy(d, s.gt, (size_t)n * K, &out->gt)); TRY(dev_copy(d, s.lt, (size_t)n * K, &out->lt));
-  TRY(dev_copy(d, s.it_state, n, &out->it_state)); return KS_OK;
+  TRY(dev_copy(a, s.present, n, &out->present)); TRY(dev_copy(a, s.complement, n, &out->complement));
+  TRY(dev_copy(a, s.mask, (size_t)n * K, &out->mask)); TRY(dev_copy(a, s.gt, (size_t)n * K, &out->gt)); TRY(dev_copy(a, s.lt, (size_t)n * K, &out->lt));
+  TRY(dev_copy(a, s.it_state, n, &out->it_state)); return KS_OK;
 }
 
 extern "C" int ks_device_count(void) {
@@ -2914,8 +2978,7 @@ extern "C" void ks_problem_free(ks_dev_problem* d) {
   if (d->view) { delete d; return; }
   hipSetDevice(d->device);
   if (d->stream) { hipStreamSynchronize(d->stream); pool().put_stream(d->device, d->stream); }
-  pool().put(d->device, d->arena_bytes, false, d->arena);
-  pool().put(d->device, d->stage_bytes, true, d->stage);
+  d->a.release(d->device);
   delete d;
 }
 
@@ -2930,13 +2993,13 @@ static int upload_impl(const ks_problem* p, int device, const ks_dev_problem* ba
   ks_dev_problem* d = new ks_dev_problem(); d->device = device; d->src = *p;
   // share X: same host array as the base's -> the base's device copy
 #define SHARED(field) (base && p->field && p->field == base->src.field)
-#define COPY_OR_SHARE(field, count, dst) do { if (SHARED(field)) (dst) = base->h.field; else TRY(dev_copy(d, p->field, (count), &(dst))); } while (0)
+#define COPY_OR_SHARE(field, count, dst) do { if (SHARED(field)) (dst) = base->h.field; else TRY(dev_copy(a, p->field, (count), &(dst))); } while (0)
   const bool share_cat = base && p->K == base->h.K && p->T == base->h.T && p->R == base->h.R && SHARED(it_present) && SHARED(it_complement) && SHARED(it_mask) && SHARED(it_alloc) && SHARED(it_offer) &&
                          memcmp(p->key_nvalues, base->src.key_nvalues, p->K * sizeof(u32)) == 0;
   struct Guard { ks_dev_problem* d; bool ok = false; ~Guard() { if (!ok) ks_problem_free(d); } } guard{d};
   TRY(pool().get_stream(device, &d->stream));
   auto layout = [&]() -> int {
-  DevProb& h = d->h;
+  DevProb& h = d->h; Arena& a = d->a;
   h.P = p->P; h.C = p->C; h.T = p->T; h.TW = (p->T + 63) / 64; h.M = p->M; h.E = p->E; h.K = p->K; h.R = p->R; h.G = p->G; h.GH = p->GH; h.S = p->S; h.SC = p->SC;
   h.NMAX = p->max_new_nodes ? p->max_new_nodes : 1; h.flags = p->flags | (getenv("KS_NO_FOLD") ? KS_FLAG_NOFOLD : 0u); h.n_topologies = p->n_topologies;
   h.wellknown_mask = p->wellknown_mask; h.key_zone = p->key_zone; h.key_ct = p->key_ct; h.n_ct = p->n_ct;
@@ -2965,105 +3028,82 @@ static int upload_impl(const ks_problem* p, int device, const ks_dev_problem* ba
     for (u32 c = 0; c < C && lean; ++c) lean = p->cls_hn_mode[c] == 0 && p->cls_port_off[c + 1] == p->cls_port_off[c] && p->cls_vol_off[c + 1] == p->cls_vol_off[c];
     d->lean_ok = lean;
   }
-  TRY(dev_copy(d, p->key_nvalues, K, &h.key_nvalues)); TRY(dev_copy(d, p->value_int, (size_t)K * 64, &h.value_int));
+  TRY(dev_copy(a, p->key_nvalues, K, &h.key_nvalues)); TRY(dev_copy(a, p->value_int, (size_t)K * 64, &h.value_int));
   COPY_OR_SHARE(it_present, T, h.it_present); COPY_OR_SHARE(it_complement, T, h.it_complement);
   COPY_OR_SHARE(it_mask, (size_t)K * T, h.it_mask); COPY_OR_SHARE(it_alloc, (size_t)R * T, h.it_alloc);
   COPY_OR_SHARE(it_cap, (size_t)R * T, h.it_cap); COPY_OR_SHARE(it_offer, T, h.it_offer);
   h.it_price = nullptr; h.ct_spot = p->ct_spot; h.ct_ondemand = p->ct_ondemand;
   const bool same_pairs = base && p->key_zone == base->src.key_zone && p->key_ct == base->src.key_ct && p->n_ct == base->src.n_ct;
-  if (p->it_price && p->key_zone >= 0 && p->key_ct >= 0) { if (same_pairs && SHARED(it_price) && base->h.it_price) h.it_price = base->h.it_price; else TRY(dev_copy(d, p->it_price, (size_t)T * p->key_nvalues[p->key_zone] * p->n_ct, &h.it_price)); }
+  if (p->it_price && p->key_zone >= 0 && p->key_ct >= 0) { if (same_pairs && SHARED(it_price) && base->h.it_price) h.it_price = base->h.it_price; else TRY(dev_copy(a, p->it_price, (size_t)T * p->key_nvalues[p->key_zone] * p->n_ct, &h.it_price)); }
   h.it_price_lo = h.it_price;
-  if (p->it_price_lo && p->key_zone >= 0 && p->key_ct >= 0) { if (same_pairs && SHARED(it_price_lo) && base->h.it_price_lo) h.it_price_lo = base->h.it_price_lo; else TRY(dev_copy(d, p->it_price_lo, (size_t)T * p->key_nvalues[p->key_zone] * p->n_ct, &h.it_price_lo)); }
+  if (p->it_price_lo && p->key_zone >= 0 && p->key_ct >= 0) { if (same_pairs && SHARED(it_price_lo) && base->h.it_price_lo) h.it_price_lo = base->h.it_price_lo; else TRY(dev_copy(a, p->it_price_lo, (size_t)T * p->key_nvalues[p->key_zone] * p->n_ct, &h.it_price_lo)); }
   const bool same_lattice = base && h.S == base->h.S && h.SC == base->h.SC;
-  if (same_lattice && SHARED(its_inter)) h.its_inter = base->h.its_inter; else TRY(dev_copy(d, p->its_inter, (size_t)h.S * h.SC, &h.its_inter));
-  if (same_lattice && SHARED(its_fail)) h.its_fail = base->h.its_fail; else TRY(dev_copy(d, p->its_fail, (size_t)h.S * h.SC, &h.its_fail));
-  if (same_lattice && SHARED(its_nidne)) h.its_nidne = base->h.its_nidne; else TRY(dev_copy(d, p->its_nidne, h.S, &h.its_nidne));
-  if (same_lattice && SHARED(its_types)) h.its_types = base->h.its_types; else TRY(dev_copy(d, p->its_types, (size_t)h.S * TW, &h.its_types));
-  TRY(copy_reqsets(d, p->tmpl, M, K, &h.tmpl)); TRY(dev_copy(d, p->tmpl_taints, M, &h.tmpl_taints));
-  TRY(dev_copy(d, p->tmpl_daemon, (size_t)M * R, &h.tmpl_daemon)); TRY(dev_copy(d, p->tmpl_daemon_present, M, &h.tmpl_daemon_present));
-  TRY(dev_copy(d, p->tmpl_types, (size_t)M * TW, &h.tmpl_types)); TRY(dev_copy(d, p->tmpl_limit_present, M, &h.tmpl_limit_present));
-  TRY(dev_copy(d, p->tmpl_remaining, (size_t)M * R, &h.tmpl_remaining));
-  TRY(copy_reqsets(d, p->en, E, K, &h.en)); TRY(dev_copy(d, p->en_taints, E, &h.en_taints)); TRY(dev_copy(d, p->en_avail, (size_t)E * R, &h.en_avail));
-  TRY(dev_copy(d, p->en_requests, (size_t)E * R, &h.en_requests)); TRY(dev_copy(d, p->en_requests_present, E, &h.en_requests_present));
-  TRY(dev_copy(d, p->en_port_off, (size_t)E + 1, &h.en_port_off));
-  TRY(copy_reqsets(d, p->cls, C, K, &h.cls)); TRY(dev_copy(d, p->cls_hn_mode, C, &h.cls_hn_mode)); TRY(dev_copy(d, p->cls_hn_off, (size_t)C + 1, &h.cls_hn_off));
-  TRY(dev_copy(d, p->hn_list, C ? p->cls_hn_off[C] : 0, &h.hn_list));
-  TRY(dev_copy(d, p->cls_requests, (size_t)C * R, &h.cls_requests)); TRY(dev_copy(d, p->cls_requests_present, C, &h.cls_requests_present));
-  TRY(dev_copy(d, p->cls_tolerated, C, &h.cls_tolerated)); TRY(dev_copy(d, p->cls_port_off, (size_t)C + 1, &h.cls_port_off));
+  if (same_lattice && SHARED(its_inter)) h.its_inter = base->h.its_inter; else TRY(dev_copy(a, p->its_inter, (size_t)h.S * h.SC, &h.its_inter));
+  if (same_lattice && SHARED(its_fail)) h.its_fail = base->h.its_fail; else TRY(dev_copy(a, p->its_fail, (size_t)h.S * h.SC, &h.its_fail));
+  if (same_lattice && SHARED(its_nidne)) h.its_nidne = base->h.its_nidne; else TRY(dev_copy(a, p->its_nidne, h.S, &h.its_nidne));
+  if (same_lattice && SHARED(its_types)) h.its_types = base->h.its_types; else TRY(dev_copy(a, p->its_types, (size_t)h.S * TW, &h.its_types));
+  TRY(copy_reqsets(d, p->tmpl, M, K, &h.tmpl)); TRY(dev_copy(a, p->tmpl_taints, M, &h.tmpl_taints));
+  TRY(dev_copy(a, p->tmpl_daemon, (size_t)M * R, &h.tmpl_daemon)); TRY(dev_copy(a, p->tmpl_daemon_present, M, &h.tmpl_daemon_present));
+  TRY(dev_copy(a, p->tmpl_types, (size_t)M * TW, &h.tmpl_types)); TRY(dev_copy(a, p->tmpl_limit_present, M, &h.tmpl_limit_present));
+  TRY(dev_copy(a, p->tmpl_remaining, (size_t)M * R, &h.tmpl_remaining));
+  TRY(copy_reqsets(d, p->en, E, K, &h.en)); TRY(dev_copy(a, p->en_taints, E, &h.en_taints)); TRY(dev_copy(a, p->en_avail, (size_t)E * R, &h.en_avail));
+  TRY(dev_copy(a, p->en_requests, (size_t)E * R, &h.en_requests)); TRY(dev_copy(a, p->en_requests_present, E, &h.en_requests_present));
+  TRY(dev_copy(a, p->en_port_off, (size_t)E + 1, &h.en_port_off));
+  TRY(copy_reqsets(d, p->cls, C, K, &h.cls)); TRY(dev_copy(a, p->cls_hn_mode, C, &h.cls_hn_mode)); TRY(dev_copy(a, p->cls_hn_off, (size_t)C + 1, &h.cls_hn_off));
+  TRY(dev_copy(a, p->hn_list, C ? p->cls_hn_off[C] : 0, &h.hn_list));
+  TRY(dev_copy(a, p->cls_requests, (size_t)C * R, &h.cls_requests)); TRY(dev_copy(a, p->cls_requests_present, C, &h.cls_requests_present));
+  TRY(dev_copy(a, p->cls_tolerated, C, &h.cls_tolerated)); TRY(dev_copy(a, p->cls_port_off, (size_t)C + 1, &h.cls_port_off));
   const u32 nports_static = C ? p->cls_port_off[C] : (E ? p->en_port_off[E] : 0);
-  TRY(dev_copy(d, p->ports, nports_static, &h.ports));
+  TRY(dev_copy(a, p->ports, nports_static, &h.ports));
   h.ND = p->ND; h.SW = p->SW;
-  TRY(dev_copy(d, p->en_vol_limit, (size_t)E * p->ND, &h.en_vol_limit)); TRY(dev_copy(d, p->en_vol_count, (size_t)E * p->ND, &h.en_vol_count)); TRY(dev_copy(d, p->en_vol_set, (size_t)E * p->SW, &h.en_vol_set));
-  TRY(dev_copy(d, p->cls_vol_off, (size_t)C + 1, &h.cls_vol_off)); TRY(dev_copy(d, p->vol_list, C ? p->cls_vol_off[C] : 0, &h.vol_list));
-  TRY(dev_copy(d, p->cls_own_off, (size_t)C + 1, &h.cls_own_off)); TRY(dev_copy(d, p->own_list, C ? p->cls_own_off[C] : 0, &h.own_list));
-  TRY(dev_copy(d, p->cls_sel_off, (size_t)C + 1, &h.cls_sel_off)); TRY(dev_copy(d, p->sel_list, C ? p->cls_sel_off[C] : 0, &h.sel_list));
-  TRY(dev_copy(d, p->cls_isel_off, (size_t)C + 1, &h.cls_isel_off)); TRY(dev_copy(d, p->isel_list, C ? p->cls_isel_off[C] : 0, &h.isel_list));
-  TRY(dev_copy(d, p->cls_iown_off, (size_t)C + 1, &h.cls_iown_off)); TRY(dev_copy(d, p->iown_list, C ? p->cls_iown_off[C] : 0, &h.iown_list));
-  TRY(dev_copy(d, p->pod_stage_off, (size_t)P + 1, &h.pod_stage_off)); TRY(dev_copy(d, p->stage_cls, P ? p->pod_stage_off[P] : 0, &h.stage_cls));
-  TRY(dev_copy(d, p->queue, P, &h.queue));
-  TRY(dev_copy(d, p->grp_type, G, &h.grp_type)); TRY(dev_copy(d, p->grp_key, G, &h.grp_key)); TRY(dev_copy(d, p->grp_max_skew, G, &h.grp_max_skew));
-  TRY(dev_copy(d, p->grp_active, G, &h.grp_active)); TRY(dev_copy(d, p->grp_filter_off, (size_t)G + 1, &h.grp_filter_off));
+  TRY(dev_copy(a, p->en_vol_limit, (size_t)E * p->ND, &h.en_vol_limit)); TRY(dev_copy(a, p->en_vol_count, (size_t)E * p->ND, &h.en_vol_count)); TRY(dev_copy(a, p->en_vol_set, (size_t)E * p->SW, &h.en_vol_set));
+  TRY(dev_copy(a, p->cls_vol_off, (size_t)C + 1, &h.cls_vol_off)); TRY(dev_copy(a, p->vol_list, C ? p->cls_vol_off[C] : 0, &h.vol_list));
+  TRY(dev_copy(a, p->cls_own_off, (size_t)C + 1, &h.cls_own_off)); TRY(dev_copy(a, p->own_list, C ? p->cls_own_off[C] : 0, &h.own_list));
+  TRY(dev_copy(a, p->cls_sel_off, (size_t)C + 1, &h.cls_sel_off)); TRY(dev_copy(a, p->sel_list, C ? p->cls_sel_off[C] : 0, &h.sel_list));
+  TRY(dev_copy(a, p->cls_isel_off, (size_t)C + 1, &h.cls_isel_off)); TRY(dev_copy(a, p->isel_list, C ? p->cls_isel_off[C] : 0, &h.isel_list));
+  TRY(dev_copy(a, p->cls_iown_off, (size_t)C + 1, &h.cls_iown_off)); TRY(dev_copy(a, p->iown_list, C ? p->cls_iown_off[C] : 0, &h.iown_list));
+  TRY(dev_copy(a, p->pod_stage_off, (size_t)P + 1, &h.pod_stage_off)); TRY(dev_copy(a, p->stage_cls, P ? p->pod_stage_off[P] : 0, &h.stage_cls));
+  TRY(dev_copy(a, p->queue, P, &h.queue));
+  TRY(dev_copy(a, p->grp_type, G, &h.grp_type)); TRY(dev_copy(a, p->grp_key, G, &h.grp_key)); TRY(dev_copy(a, p->grp_max_skew, G, &h.grp_max_skew));
+  TRY(dev_copy(a, p->grp_active, G, &h.grp_active)); TRY(dev_copy(a, p->grp_filter_off, (size_t)G + 1, &h.grp_filter_off));
   TRY(copy_reqsets(d, p->flt, p->flt.n, K, &h.flt));
-  TRY(dev_copy(d, p->grp_count, (size_t)G * 64, &h.grp_count)); TRY(dev_copy(d, p->grp_hslot, G, &h.grp_hslot));
-  TRY(dev_copy(d, p->grph_count, (size_t)p->GH * E, &h.grph_count)); TRY(dev_copy(d, p->grph_extra_pos, p->GH, &h.grph_extra_pos));
+  TRY(dev_copy(a, p->grp_count, (size_t)G * 64, &h.grp_count)); TRY(dev_copy(a, p->grp_hslot, G, &h.grp_hslot));
+  TRY(dev_copy(a, p->grph_count, (size_t)p->GH * E, &h.grph_count)); TRY(dev_copy(a, p->grph_extra_pos, p->GH, &h.grph_extra_pos));
   // derived tables
   h.derived_shared = share_cat ? 1u : 0u;
   if (share_cat) {
     h.kv_types = base->h.kv_types; h.cmplx_types = base->h.cmplx_types; h.nidnex_types = base->h.nidnex_types; h.pair_types = base->h.pair_types;
     h.ge_vals = base->h.ge_vals; h.ge_cnt = base->h.ge_cnt; h.ge_rows = base->h.ge_rows; h.ge_max = base->h.ge_max;
   } else {
-  TRY(dev_alloc(d, (size_t)K * 64 * TW, &h.kv_types, 0)); TRY(dev_alloc(d, (size_t)K * TW, &h.cmplx_types, 0)); TRY(dev_alloc(d, (size_t)K * TW, &h.nidnex_types, 0));
-  TRY(dev_alloc(d, (size_t)64 * TW, &h.pair_types, 0));
+  TRY(dev_alloc(a, (size_t)K * 64 * TW, &h.kv_types, 0)); TRY(dev_alloc(a, (size_t)K * TW, &h.cmplx_types, 0)); TRY(dev_alloc(a, (size_t)K * TW, &h.nidnex_types, 0));
+  TRY(dev_alloc(a, (size_t)64 * TW, &h.pair_types, 0));
   {   // ascending distinct Allocatable values per resource (host sort; the rows are built on the device)
     std::vector<i64> vals((size_t)R * T, 0); std::vector<u32> cnt(R, 0);
     for (u32 r = 0; r < R; ++r) { std::vector<i64> v(p->it_alloc + (size_t)r * T, p->it_alloc + (size_t)(r + 1) * T); std::sort(v.begin(), v.end()); v.erase(std::unique(v.begin(), v.end()), v.end()); cnt[r] = (u32)v.size(); std::copy(v.begin(), v.end(), vals.begin() + (size_t)r * T); }
-    const i64* dv; const u32* dc; TRY(dev_copy(d, vals.data(), vals.size(), &dv)); TRY(dev_copy(d, cnt.data(), cnt.size(), &dc)); h.ge_vals = (i64*)dv; h.ge_cnt = (u32*)dc;
+    const i64* dv; const u32* dc; TRY(dev_copy(a, vals.data(), vals.size(), &dv)); TRY(dev_copy(a, cnt.data(), cnt.size(), &dc)); h.ge_vals = (i64*)dv; h.ge_cnt = (u32*)dc;
     h.ge_max = 1; for (u32 r = 0; r < R; ++r) h.ge_max = std::max(h.ge_max, cnt[r]);
-    TRY(dev_alloc(d, (size_t)R * T * TW, &h.ge_rows, 0));
+    TRY(dev_alloc(a, (size_t)R * T * TW, &h.ge_rows, 0));
   }
   }
-  { u8* pl = nullptr; TRY(dev_alloc(d, (size_t)C * sizeof(ClsPlan), &pl, 0)); h.plans = pl; }
-  { u8* br = nullptr; TRY(dev_alloc(d, (size_t)C * sizeof(ClsBrief), &br, 0)); h.briefs = br;
-    h.ev_tab_size = 64; while (h.ev_tab_size < 2 * C) h.ev_tab_size <<= 1; TRY(dev_alloc(d, (size_t)h.ev_tab_size, &h.ev_tab, 0)); }
+  { u8* pl = nullptr; TRY(dev_alloc(a, (size_t)C * sizeof(ClsPlan), &pl, 0)); h.plans = pl; }
+  { u8* br = nullptr; TRY(dev_alloc(a, (size_t)C * sizeof(ClsBrief), &br, 0)); h.briefs = br;
+    h.ev_tab_size = 64; while (h.ev_tab_size < 2 * C) h.ev_tab_size <<= 1; TRY(dev_alloc(a, (size_t)h.ev_tab_size, &h.ev_tab, 0)); }
   const size_t MC = (size_t)M * C;
-  TRY(dev_alloc(d, MC, &h.mc_ok, 0)); TRY(dev_alloc(d, MC, &h.mc_why, 0)); TRY(dev_alloc(d, MC, &h.mc_present)); TRY(dev_alloc(d, MC, &h.mc_complement));
-  TRY(dev_alloc(d, MC * K, &h.mc_mask)); TRY(dev_alloc(d, MC * K, &h.mc_gt)); TRY(dev_alloc(d, MC * K, &h.mc_lt)); TRY(dev_alloc(d, MC, &h.mc_it));
-  TRY(dev_alloc(d, MC * TW, &h.grid, 0));
-  { u8* rb = nullptr; TRY(dev_alloc(d, (size_t)C * sizeof(RRBrief), &rb)); h.rr_briefs = rb; TRY(dev_alloc(d, (size_t)C * (sizeof(RRMemo) / 4), &h.rr_memo)); TRY(dev_alloc(d, MC, &h.rr_mcnrc)); TRY(dev_alloc(d, MC, &h.rr_mcch)); TRY(dev_alloc(d, (size_t)h.ev_tab_size, &h.rr_tab, 0)); TRY(dev_alloc(d, (size_t)h.ev_tab_size, &h.rr_tab2, 0)); TRY(dev_alloc(d, (size_t)C, &h.rr_mi)); TRY(dev_alloc(d, (size_t)C * 8, &h.rr_hot));
-    TRY(dev_alloc(d, (size_t)RR_NRC * TW, &h.rr_types)); TRY(dev_alloc(d, (size_t)RR_NODES * 5, &h.rr_nodes)); }
-  // state
-  DevState& s = d->hs; const size_t NS = (size_t)E + h.NMAX;
-  TRY(dev_alloc(d, P, &s.q)); TRY(dev_alloc(d, P, &s.lastlen)); TRY(dev_alloc(d, P, &s.lastgen)); TRY(dev_alloc(d, P, &s.pod_stage)); TRY(dev_alloc(d, P, &s.pod_node)); TRY(dev_alloc(d, P, &s.pod_seq)); TRY(dev_alloc(d, P, &s.pod_reason));
-  s.rec_stride = ks_rec_stride(R, K);
-  TRY(dev_alloc(d, NS * s.rec_stride, &s.rec, 0));
-  TRY(dev_alloc(d, (size_t)h.NMAX, &s.n_tmpl)); TRY(dev_alloc(d, ((size_t)h.NMAX + 1) * TW, &s.n_alive)); TRY(dev_alloc(d, (size_t)8 * 64 * TW, &s.round_scratch)); TRY(dev_alloc(d, 2 * NS, &s.lowi));
-  TRY(dev_alloc(d, (size_t)P + 4, &s.bstart, 0)); TRY(dev_alloc(d, (size_t)h.NMAX, &s.order_g));
-  TRY(dev_alloc(d, (size_t)G * 64, &s.gcnt)); TRY(dev_alloc(d, G, &s.g_reg)); TRY(dev_alloc(d, G, &s.g_pos)); TRY(dev_alloc(d, G, &s.g_active));
-  TRY(dev_alloc(d, (size_t)p->GH * NS, &s.hcnt, 0xFF)); TRY(dev_alloc(d, p->GH, &s.g_hpos)); TRY(dev_alloc(d, p->GH, &s.g_hzero)); TRY(dev_alloc(d, (size_t)M * R, &s.remaining));
-  const size_t NM = h.NMAX;
-  TRY(dev_alloc(d, NM, &s.o_present)); TRY(dev_alloc(d, NM, &s.o_complement)); TRY(dev_alloc(d, NM * K, &s.o_mask)); TRY(dev_alloc(d, NM * K, &s.o_gt)); TRY(dev_alloc(d, NM * K, &s.o_lt));
-  TRY(dev_alloc(d, NM, &s.o_it)); TRY(dev_alloc(d, NM * R, &s.o_req)); TRY(dev_alloc(d, NM, &s.o_reqmask));
-  // host-port pool: existing entries + one batch-worth of pod ports (max over stages)
+  TRY(dev_alloc(a, MC, &h.mc_ok, 0)); TRY(dev_alloc(a, MC, &h.mc_why, 0)); TRY(dev_alloc(a, MC, &h.mc_present)); TRY(dev_alloc(a, MC, &h.mc_complement));
+  TRY(dev_alloc(a, MC * K, &h.mc_mask)); TRY(dev_alloc(a, MC * K, &h.mc_gt)); TRY(dev_alloc(a, MC * K, &h.mc_lt)); TRY(dev_alloc(a, MC, &h.mc_it));
+  TRY(dev_alloc(a, MC * TW, &h.grid, 0));
+  { u8* rb = nullptr; TRY(dev_alloc(a, (size_t)C * sizeof(RRBrief), &rb)); h.rr_briefs = rb; TRY(dev_alloc(a, (size_t)C * (sizeof(RRMemo) / 4), &h.rr_memo)); TRY(dev_alloc(a, MC, &h.rr_mcnrc)); TRY(dev_alloc(a, MC, &h.rr_mcch)); TRY(dev_alloc(a, (size_t)h.ev_tab_size, &h.rr_tab, 0)); TRY(dev_alloc(a, (size_t)h.ev_tab_size, &h.rr_tab2, 0)); TRY(dev_alloc(a, (size_t)C, &h.rr_mi)); TRY(dev_alloc(a, (size_t)C * 8, &h.rr_hot));
+    TRY(dev_alloc(a, (size_t)RR_NRC * TW, &h.rr_types)); TRY(dev_alloc(a, (size_t)RR_NODES * 5, &h.rr_nodes)); }
+  // state.  host-port pool: existing entries + one batch-worth of pod ports (max over stages)
   size_t pp_pool = E ? p->en_port_off[E] : 0;
   for (u32 i = 0; i < P; ++i) { u32 mx = 0; for (u32 st = p->pod_stage_off[i]; st < p->pod_stage_off[i + 1]; ++st) { const u32 c = p->stage_cls[st]; const u32 n = p->cls_port_off[c + 1] - p->cls_port_off[c]; if (n > mx) mx = n; } pp_pool += mx; }
-  s.pp_cap = (u32)pp_pool; TRY(dev_alloc(d, pp_pool, &s.pp_entry)); TRY(dev_alloc(d, pp_pool, &s.pp_next));
-  s.vol_pad = 0; TRY(dev_alloc(d, (size_t)E * p->ND, &s.vol_cnt)); TRY(dev_alloc(d, (size_t)E * p->SW, &s.vol_set)); TRY(dev_alloc(d, C, &s.wm));
-  TRY(dev_alloc(d, 32, &s.stats, 0)); TRY(dev_alloc(d, 4, &s.out_counts, 0)); TRY(dev_alloc(d, P, &s.unscheduled));
+  StateDims sd{}; sd.P = P; sd.NMAX = h.NMAX; sd.E = E; sd.M = M; sd.R = R; sd.K = K; sd.TW = TW; sd.C = C; sd.G = G; sd.GH = p->GH; sd.ND = p->ND; sd.SW = p->SW; sd.pp_cap = pp_pool; sd.hcnt_filled = true; sd.topology = true; sd.round_scratch = true; sd.volumes = true;
+  TRY(state_layout(a, sd, d->hs));
   // the two descriptors go last: by now (placing pass) every pointer in them is final
-  { const DevProb* dp; const DevState* ds; TRY(dev_copy(d, &d->h, 1, &dp)); TRY(dev_copy(d, &d->hs, 1, &ds)); d->d_prob = (DevProb*)dp; d->d_state = (DevState*)ds; }
+  { const DevProb* dp; const DevState* ds; TRY(dev_copy(a, &d->h, 1, &dp)); TRY(dev_copy(a, &d->hs, 1, &ds)); d->d_prob = (DevProb*)dp; d->d_state = (DevState*)ds; }
   return KS_OK;
   };
-  d->measure = true; TRY(layout());
-  d->arena_bytes = d->sz[0] + d->sz[1] + d->sz[2] + d->sz[3]; d->stage_bytes = d->sz[0];
-  { void* a = nullptr; TRY(pool().get(device, d->arena_bytes, false, &a)); d->arena = (u8*)a; void* st = nullptr; TRY(pool().get(device, d->stage_bytes, true, &st)); d->stage = (u8*)st; }
-  d->base[0] = d->arena; d->base[1] = d->base[0] + d->sz[0]; d->base[2] = d->base[1] + d->sz[1]; d->base[3] = d->base[2] + d->sz[2];
-  d->measure = false; TRY(layout());
-  HIPCHK(hipMemcpyAsync(d->base[0], d->stage, d->sz[0], hipMemcpyHostToDevice, d->stream));
-  if (d->sz[1]) HIPCHK(hipMemsetAsync(d->base[1], 0, d->sz[1], d->stream));
-  if (d->sz[2]) HIPCHK(hipMemsetAsync(d->base[2], 0xFF, d->sz[2], d->stream));
-  // Diagnostic: KS_POISON=<byte> fills the region the kernels must initialise themselves before reading (queue, node records' tails, alive rows,
-  // ladder indices, order array, ...).  Results must not depend on it (tests/test_parity.py::test_poisoned_arena, tools/stress_cold.py).
-  if (const char* pz = getenv("KS_POISON")) { if (d->sz[3]) HIPCHK(hipMemsetAsync(d->base[3], (int)strtol(pz, nullptr, 0) & 0xFF, d->sz[3], d->stream)); }
+  TRY(d->a.lay(device, layout)); TRY(d->a.send(d->stream));
   guard.ok = true; *out = d; return KS_OK;
 #undef SHARED
 #undef COPY_OR_SHARE
@@ -3141,21 +3181,20 @@ __global__ __launch_bounds__(1024) void ks_derive_topology(const TopoDesc* descs
 
 struct ks_whatif_batch {
   int device = 0; u32 n = 0; hipStream_t stream = nullptr; bool own_stream = false;
-  u8* arena = nullptr; size_t arena_bytes = 0; u8* stage = nullptr; size_t stage_bytes = 0;
+  Arena a;      // the state of every what-if, and what their derivation reads
   std::vector<ks_dev_problem*> views;
 };
 extern "C" void ks_whatifs_free(ks_whatif_batch* b) {
   if (!b) return;
   hipSetDevice(b->device);
   if (b->stream) { hipStreamSynchronize(b->stream); pool().put_stream(b->device, b->stream); }
-  pool().put(b->device, b->arena_bytes, false, b->arena);
-  pool().put(b->device, b->stage_bytes, true, b->stage);
+  b->a.release(b->device);
   for (auto* v : b->views) delete v;
   delete b;
 }
 extern "C" ks_dev_problem* const* ks_whatifs_problems(ks_whatif_batch* b) { return b ? b->views.data() : nullptr; }
 extern "C" uint32_t ks_whatifs_count(const ks_whatif_batch* b) { return b ? b->n : 0; }
-extern "C" uint64_t ks_whatifs_arena_bytes(const ks_whatif_batch* b) { return b ? (uint64_t)b->arena_bytes : 0; }
+extern "C" uint64_t ks_whatifs_arena_bytes(const ks_whatif_batch* b) { return b ? (uint64_t)b->a.bytes() : 0; }
 
 // base: the resident snapshot (tables built).  pod_node[base P]: snapshot node index of every snapshot pod (-1: none); node_row[n_nodes]: the node's
 // existing-node row in `base`, or -1 (a node no provisioner owns).  What-if w removes nodes cand[cand_off[w] .. cand_off[w+1]); n_pods[w] = pods
@@ -3178,104 +3217,63 @@ static int whatifs_open(const ks_dev_problem* base, uint32_t n_nodes, const int3
   struct Guard { ks_whatif_batch* b; bool ok = false; ~Guard() { if (!ok) ks_whatifs_free(b); } } guard{b};
   TRY(pool().get_stream(b->device, &b->stream));
   const size_t NW = ((size_t)n_nodes + 63) / 64, EW = ((size_t)E + 63) / 64;
-  // ---- layout: [copied | zeroed | uninitialised], 256-byte aligned pieces ----
-  size_t sz[3] = {0, 0, 0};
-  auto take = [&](int region, size_t bytes) { const size_t at = sz[region]; sz[region] += ks_align256(bytes ? bytes : 1); return at; };
-  struct Lay { size_t cand_bits, removed, remaining, q, lastlen, lastgen, pod_stage, pod_node, pod_seq, pod_reason, rec, n_tmpl, n_alive, lowi, bstart, order_g, rem_state,
-               o_present, o_complement, o_mask, o_gt, o_lt, o_it, o_req, o_reqmask, pp_entry, pp_next, wm, stats, out_counts, unscheduled, pod_gid, round_scratch,
-               t_active, t_count, t_extra, gcnt, g_reg, g_pos, g_active, hcnt, g_hpos, g_hzero, vol_cnt, vol_set; u32 P, NMAX, pp_cap; };
-  std::vector<Lay> L(n);
-  const size_t pod_node_at = take(0, (size_t)Pb * sizeof(i32));
-  const u32 G = bh.G, GH = bh.GH; const size_t GN = (size_t)G * n_nodes;
-  size_t t_cnt_at = 0, t_dom_at = 0, t_own_at = 0, t_tot_at = 0, t_ext_at = 0, t_hbase_at = 0, t_row_at = 0, t_hg_at = 0, t_cand_at = 0, t_desc_at = 0;
-  if (with_topo) {
-    t_cnt_at = take(0, GN * 4); t_dom_at = take(0, GN * 4); t_own_at = take(0, (size_t)n_nodes * ((G + 63) / 64) * 8); t_tot_at = take(0, (size_t)G * 64 * 4); t_ext_at = take(0, (size_t)GH * 4);
-    t_hbase_at = take(0, (size_t)GH * E * 4); t_row_at = take(0, (size_t)n_nodes * 4); t_hg_at = take(0, (size_t)GH * 4); t_cand_at = take(0, (size_t)cand_off[n] * 4); t_desc_at = take(0, (size_t)n * sizeof(TopoDesc));
-  }
-  const u32 rec_stride = ks_rec_stride(R, K);
-  const size_t pp_static = E ? base->src.en_port_off[E] : 0;
-  for (u32 w = 0; w < n; ++w) {
-    Lay& l = L[w]; const u32 P = n_pods[w]; l.P = P; l.NMAX = P ? P : 1; const size_t NS = (size_t)E + l.NMAX, NM = l.NMAX;
-    l.cand_bits = take(0, NW * 8); l.removed = take(0, EW * 8); l.remaining = take(0, (size_t)M * R * 8);
-    l.rec = take(1, NS * rec_stride); l.bstart = take(1, ((size_t)P + 4) * 4); l.stats = take(1, 32 * 8); l.out_counts = take(1, 4 * 4);
-    l.q = take(2, (size_t)P * 8); l.lastlen = take(2, (size_t)P * 4); l.lastgen = take(2, (size_t)P * 4); l.pod_stage = take(2, (size_t)P * 4); l.pod_node = take(2, (size_t)P * 4);
-    l.pod_seq = take(2, (size_t)P * 4); l.pod_reason = take(2, (size_t)P * 4); l.n_tmpl = take(2, NM * 4); l.n_alive = take(2, (NM + 1) * TW * 8); l.lowi = take(2, 2 * NS * 8);
-    l.order_g = take(2, NM * 4); l.rem_state = take(2, (size_t)M * R * 8);
-    l.o_present = take(2, NM * 4); l.o_complement = take(2, NM * 4); l.o_mask = take(2, NM * K * 8); l.o_gt = take(2, NM * K * 4); l.o_lt = take(2, NM * K * 4); l.o_it = take(2, NM * 4);
-    l.o_req = take(2, NM * R * 8); l.o_reqmask = take(2, NM * 4);
-    // host-port pool: the existing reservations + at most the ports of every batch pod (an upper bound: 8 per pod would be unheard of; classes with ports carry their count)
-    size_t pp = pp_static; if (C && base->src.cls_port_off[C] != pp_static) { u32 mx = 0; for (u32 c = 0; c < C; ++c) mx = std::max(mx, base->src.cls_port_off[c + 1] - base->src.cls_port_off[c]); pp += (size_t)mx * P; }
-    l.pp_entry = take(2, pp * 8); l.pp_next = take(2, pp * 4); l.wm = take(2, (size_t)C * 4); l.unscheduled = take(2, (size_t)P * 4); l.pod_gid = take(2, (size_t)P * 4);
-    l.pp_cap = (u32)pp; l.round_scratch = n == 1 ? take(2, (size_t)8 * 64 * TW * 8) : 0;      // (a batch of one runs the multi-wave kernel, whose rounds keep rows to restore)
-    if (with_topo) {
-      l.t_active = take(2, G); l.t_count = take(2, (size_t)G * 64 * 4); l.t_extra = take(2, (size_t)GH * 4);
-      l.gcnt = take(2, (size_t)G * 64 * 4); l.g_reg = take(2, (size_t)G * 8); l.g_pos = take(2, (size_t)G * 8); l.g_active = take(2, G);
-      l.hcnt = take(2, (size_t)GH * NS * 4); l.g_hpos = take(2, (size_t)GH * 4); l.g_hzero = take(2, (size_t)GH * 4);
-    }
-    if (vols) { l.vol_cnt = take(2, (size_t)E * bh.ND * 4); l.vol_set = take(2, (size_t)E * bh.SW * 8); }
-  }
-  const size_t desc_at = take(0, (size_t)n * sizeof(DeriveDesc)), dprob_at = take(0, (size_t)n * sizeof(DevProb)), dstate_at = take(0, (size_t)n * sizeof(DevState));
-  const size_t mismatch_at = take(1, 4);
-  b->arena_bytes = sz[0] + sz[1] + sz[2]; b->stage_bytes = sz[0];
-  { void* a = nullptr; TRY(pool().get(b->device, b->arena_bytes, false, &a)); b->arena = (u8*)a; void* st = nullptr; TRY(pool().get(b->device, b->stage_bytes, true, &st)); b->stage = (u8*)st; }
-  u8* const r0 = b->arena; u8* const r1 = r0 + sz[0]; u8* const r2 = r1 + sz[1];
-  // ---- the copied region: pod -> node, per what-if candidate / removed masks and remaining resources, then the descriptors ----
-  memset(b->stage, 0, sz[0]);
-  if (Pb) memcpy(b->stage + pod_node_at, pod_node, (size_t)Pb * sizeof(i32));
+  const u32 G = bh.G, GH = bh.GH, GW = (G + 63) / 64; const size_t GN = (size_t)G * n_nodes;
+  // host-port pool: the existing reservations + at most the ports of every batch pod (an upper bound: 8 per pod would be unheard of; classes with ports carry their count)
+  const size_t pp_static = E ? base->src.en_port_off[E] : 0; size_t pp_per_pod = 0;
+  if (C && base->src.cls_port_off[C] != pp_static) for (u32 c = 0; c < C; ++c) pp_per_pod = std::max<size_t>(pp_per_pod, base->src.cls_port_off[c + 1] - base->src.cls_port_off[c]);
   b->views.resize(n, nullptr);
-  DeriveDesc* hd = (DeriveDesc*)(b->stage + desc_at); DevProb* hp = (DevProb*)(b->stage + dprob_at); DevState* hsv = (DevState*)(b->stage + dstate_at);
-  TopoDesc* htd = with_topo ? (TopoDesc*)(b->stage + t_desc_at) : nullptr;
-  if (with_topo) {
-    memcpy(b->stage + t_cnt_at, topo->node_cnt, GN * 4); memcpy(b->stage + t_dom_at, topo->node_dom, GN * 4); memcpy(b->stage + t_own_at, topo->node_own, (size_t)n_nodes * ((G + 63) / 64) * 8);
-    memcpy(b->stage + t_tot_at, topo->tot, (size_t)G * 64 * 4); if (GH) { memcpy(b->stage + t_ext_at, topo->extra_tot, (size_t)GH * 4); if (E) memcpy(b->stage + t_hbase_at, topo->grph_base, (size_t)GH * E * 4); }
-    memcpy(b->stage + t_row_at, node_row, (size_t)n_nodes * 4); if (cand_off[n]) memcpy(b->stage + t_cand_at, cand, (size_t)cand_off[n] * 4);
-    i32* hg = (i32*)(b->stage + t_hg_at); for (u32 g = 0; g < G; ++g) { const i32 hs = base->src.grp_hslot[g]; if (hs >= 0 && (u32)hs < GH) hg[hs] = (i32)g; }
-  }
   for (u32 w = 0; w < n; ++w) {
-    const Lay& l = L[w];
-    u64* cb = (u64*)(b->stage + l.cand_bits); u64* rb = (u64*)(b->stage + l.removed);
-    for (u32 i = cand_off[w]; i < cand_off[w + 1]; ++i) {
-      const u32 nd = cand[i]; if (nd >= n_nodes) return fail(KS_ERR_INVALID, "candidate node out of range");
-      cb[nd >> 6] |= 1ull << (nd & 63u);
-      const i32 row = node_row[nd]; if (row >= (i32)E) return fail(KS_ERR_INVALID, "node row out of range"); if (row >= 0) rb[row >> 6] |= 1ull << (row & 63);
-    }
-    memcpy(b->stage + l.remaining, remaining + (size_t)w * M * R, (size_t)M * R * 8);
-    hd[w] = DeriveDesc{(const u64*)(r0 + l.cand_bits), (u32*)(r2 + l.pod_gid), l.P, 0};
     auto* v = new ks_dev_problem(); b->views[w] = v;
-    v->device = b->device; v->view = true; v->stream = b->stream; v->tables_built = true; v->any_bounds = base->any_bounds; v->lean_ok = base->lean_ok; v->src = base->src;
-    DevProb& h = v->h; h = bh;
-    h.P = l.P; h.NMAX = l.NMAX; h.queue = nullptr; h.pod_gid = (const u32*)(r2 + l.pod_gid); h.en_removed = (const u64*)(r0 + l.removed); h.tmpl_remaining = (const i64*)(r0 + l.remaining);
-    h.derived_shared = 1;
-    if (with_topo) {
-      h.grp_active = (const u8*)(r2 + l.t_active); h.grp_count = (const i32*)(r2 + l.t_count); h.grph_count = (const i32*)(r0 + t_hbase_at); h.grph_extra_pos = (const i32*)(r2 + l.t_extra);
-      h.hgrp_of = (const i32*)(r0 + t_hg_at); v->no_multi = true;
-      htd[w] = TopoDesc{(const u32*)(r0 + t_cand_at) + cand_off[w], cand_off[w + 1] - cand_off[w], 0, (u8*)(r2 + l.t_active), (i32*)(r2 + l.t_count), (i32*)(r2 + l.t_extra)};
-    }
-    DevState& st = v->hs; st = DevState{};
-    st.q = (u64*)(r2 + l.q); st.lastlen = (u32*)(r2 + l.lastlen); st.lastgen = (u32*)(r2 + l.lastgen); st.pod_stage = (i32*)(r2 + l.pod_stage); st.pod_node = (i32*)(r2 + l.pod_node);
-    st.pod_seq = (i32*)(r2 + l.pod_seq); st.pod_reason = (u32*)(r2 + l.pod_reason);
-    st.rec = r1 + l.rec; st.rec_stride = rec_stride; st.n_tmpl = (i32*)(r2 + l.n_tmpl); st.n_alive = (u64*)(r2 + l.n_alive); st.lowi = (u64*)(r2 + l.lowi); st.round_scratch = n == 1 ? (u64*)(r2 + l.round_scratch) : nullptr;
-    st.bstart = (u32*)(r1 + l.bstart); st.order_g = (u32*)(r2 + l.order_g);
-    st.gcnt = nullptr; st.g_reg = nullptr; st.g_pos = nullptr; st.g_active = nullptr; st.hcnt = nullptr; st.g_hpos = nullptr; st.g_hzero = nullptr;
-    if (with_topo) { st.gcnt = (i32*)(r2 + l.gcnt); st.g_reg = (u64*)(r2 + l.g_reg); st.g_pos = (u64*)(r2 + l.g_pos); st.g_active = (u8*)(r2 + l.g_active); st.hcnt = (i32*)(r2 + l.hcnt);
-                     st.g_hpos = (i32*)(r2 + l.g_hpos); st.g_hzero = (i32*)(r2 + l.g_hzero); }
-    st.remaining = (i64*)(r2 + l.rem_state);
-    st.pp_entry = (u64*)(r2 + l.pp_entry); st.pp_next = (i32*)(r2 + l.pp_next); st.pp_cap = l.pp_cap;
-    st.vol_pad = 0; st.vol_cnt = vols ? (i32*)(r2 + l.vol_cnt) : nullptr; st.vol_set = vols ? (u64*)(r2 + l.vol_set) : nullptr; st.wm = (u32*)(r2 + l.wm);
-    st.stats = (u64*)(r1 + l.stats); st.out_counts = (u32*)(r1 + l.out_counts); st.batch_meta = nullptr; st.unscheduled = (i32*)(r2 + l.unscheduled);
-    st.o_present = (u32*)(r2 + l.o_present); st.o_complement = (u32*)(r2 + l.o_complement); st.o_mask = (u64*)(r2 + l.o_mask); st.o_gt = (i32*)(r2 + l.o_gt); st.o_lt = (i32*)(r2 + l.o_lt);
-    st.o_it = (i32*)(r2 + l.o_it); st.o_req = (i64*)(r2 + l.o_req); st.o_reqmask = (u32*)(r2 + l.o_reqmask);
-    hp[w] = h; hsv[w] = st;
-    v->d_prob = (DevProb*)(r0 + dprob_at) + w; v->d_state = (DevState*)(r0 + dstate_at) + w;
+    v->device = b->device; v->view = true; v->stream = b->stream; v->tables_built = true; v->any_bounds = base->any_bounds; v->lean_ok = base->lean_ok; v->src = base->src; v->no_multi = with_topo;
   }
-  HIPCHK(hipMemcpyAsync(r0, b->stage, sz[0], hipMemcpyHostToDevice, b->stream));
-  if (sz[1]) HIPCHK(hipMemsetAsync(r1, 0, sz[1], b->stream));
-  if (const char* pz = getenv("KS_POISON")) { if (sz[2]) HIPCHK(hipMemsetAsync(r2, (int)strtol(pz, nullptr, 0) & 0xFF, sz[2], b->stream)); }
-  if (n) hipLaunchKernelGGL(ks_derive_whatifs, dim3(n), dim3(256), 0, b->stream, bh.queue, (const i32*)(r0 + pod_node_at), Pb, (const DeriveDesc*)(r0 + desc_at), (u32*)(r1 + mismatch_at));
-  if (n && with_topo) hipLaunchKernelGGL(ks_derive_topology, dim3(n), dim3(64 * ((G + 63) / 64)), 0, b->stream, (const TopoDesc*)(r0 + t_desc_at), G, GH, n_nodes, (const i32*)(r0 + t_cnt_at), (const i32*)(r0 + t_dom_at),
-                                         (const u64*)(r0 + t_own_at), (const i32*)(r0 + t_tot_at), bh.grp_count, (const i32*)(r0 + t_ext_at), bh.grp_hslot, (const i32*)(r0 + t_row_at), bh.n_topologies);
+  // what the two derivation kernels read, in the copied region: pod -> node and the descriptors; with groups, the snapshot's per-node tables
+  const i32* d_pod_node = nullptr; const DeriveDesc* d_desc = nullptr; const TopoDesc* d_tdesc = nullptr; u32* d_mismatch = nullptr; const i32* t_cnt = nullptr; const i32* t_dom = nullptr; const u64* t_own = nullptr; const i32* t_tot = nullptr; const i32* t_ext = nullptr; const i32* t_row = nullptr;
+  // ---- one layout, run twice (Arena::lay): the shared tables, then per what-if its copied pieces and its state, then the descriptors ----
+  auto layout = [&]() -> int {
+    Arena& a = b->a;
+    DeriveDesc* hd = nullptr; TopoDesc* htd = nullptr; const i32* t_hbase = nullptr; const i32* t_hg = nullptr; const u32* t_cand = nullptr;
+    TRY(dev_copy(a, pod_node, Pb, &d_pod_node));
+    if (with_topo) {
+      TRY(dev_copy(a, topo->node_cnt, GN, &t_cnt)); TRY(dev_copy(a, topo->node_dom, GN, &t_dom)); TRY(dev_copy(a, topo->node_own, (size_t)n_nodes * GW, &t_own));
+      TRY(dev_copy(a, topo->tot, (size_t)G * 64, &t_tot)); TRY(dev_copy(a, topo->extra_tot, GH, &t_ext)); TRY(dev_copy(a, topo->grph_base, (size_t)GH * E, &t_hbase));
+      TRY(dev_copy(a, node_row, n_nodes, &t_row)); TRY(dev_copy(a, cand, cand_off[n], &t_cand));
+      i32* hg = nullptr; TRY(dev_stage(a, GH, &t_hg, &hg));
+      if (hg) for (u32 g = 0; g < G; ++g) { const i32 hs = base->src.grp_hslot[g]; if (hs >= 0 && (u32)hs < GH) hg[hs] = (i32)g; }
+      TRY(dev_stage(a, n, &d_tdesc, &htd));
+    }
+    TRY(dev_stage(a, n, &d_desc, &hd));
+    for (u32 w = 0; w < n; ++w) {
+      ks_dev_problem* v = b->views[w]; const u32 P = n_pods[w];
+      const u64* d_cb = nullptr; const u64* d_rb = nullptr; u64* cb = nullptr; u64* rb = nullptr; const i64* d_rem = nullptr; u32* gid = nullptr;
+      TRY(dev_stage(a, NW, &d_cb, &cb)); TRY(dev_stage(a, EW, &d_rb, &rb)); TRY(dev_copy(a, remaining + (size_t)w * M * R, (size_t)M * R, &d_rem)); TRY(dev_alloc(a, P, &gid));
+      if (cb) for (u32 i = cand_off[w]; i < cand_off[w + 1]; ++i) {
+        const u32 nd = cand[i]; if (nd >= n_nodes) return fail(KS_ERR_INVALID, "candidate node out of range");
+        cb[nd >> 6] |= 1ull << (nd & 63u);
+        const i32 row = node_row[nd]; if (row >= (i32)E) return fail(KS_ERR_INVALID, "node row out of range"); if (row >= 0) rb[row >> 6] |= 1ull << (row & 63);
+      }
+      if (hd) hd[w] = DeriveDesc{d_cb, gid, P, 0};
+      DevProb& h = v->h; h = bh;
+      h.P = P; h.NMAX = P ? P : 1; h.queue = nullptr; h.pod_gid = gid; h.en_removed = d_rb; h.tmpl_remaining = d_rem; h.derived_shared = 1;
+      if (with_topo) {      // this what-if's own group activity and counts (ks_derive_topology writes them); the hostname rows are the snapshot's
+        u8* act = nullptr; i32* cnt = nullptr; i32* ext = nullptr;
+        TRY(dev_alloc(a, G, &act)); TRY(dev_alloc(a, (size_t)G * 64, &cnt)); TRY(dev_alloc(a, GH, &ext));
+        h.grp_active = act; h.grp_count = cnt; h.grph_count = t_hbase; h.grph_extra_pos = ext; h.hgrp_of = t_hg;
+        if (htd) htd[w] = TopoDesc{t_cand + cand_off[w], cand_off[w + 1] - cand_off[w], 0, act, cnt, ext};
+      }
+      StateDims sd{}; sd.P = P; sd.NMAX = h.NMAX; sd.E = E; sd.M = M; sd.R = R; sd.K = K; sd.TW = TW; sd.C = C; sd.G = G; sd.GH = GH; sd.ND = bh.ND; sd.SW = bh.SW; sd.pp_cap = pp_static + pp_per_pod * P; sd.hcnt_filled = false; sd.topology = with_topo; sd.round_scratch = n == 1; sd.volumes = vols;
+      TRY(state_layout(a, sd, v->hs));
+    }
+    // the views' descriptors go last: by now (placing pass) every pointer in them is final
+    const DevProb* dp = nullptr; DevProb* hp = nullptr; const DevState* ds = nullptr; DevState* hsv = nullptr;
+    TRY(dev_stage(a, n, &dp, &hp)); TRY(dev_stage(a, n, &ds, &hsv));
+    if (hp) for (u32 w = 0; w < n; ++w) { ks_dev_problem* v = b->views[w]; hp[w] = v->h; hsv[w] = v->hs; v->d_prob = (DevProb*)dp + w; v->d_state = (DevState*)ds + w; }
+    return dev_alloc(a, 1, &d_mismatch, 0);
+  };
+  TRY(b->a.lay(b->device, layout)); TRY(b->a.send(b->stream));
+  if (n) hipLaunchKernelGGL(ks_derive_whatifs, dim3(n), dim3(256), 0, b->stream, bh.queue, d_pod_node, Pb, d_desc, d_mismatch);
+  if (n && with_topo) hipLaunchKernelGGL(ks_derive_topology, dim3(n), dim3(64 * GW), 0, b->stream, d_tdesc, G, GH, n_nodes, t_cnt, t_dom, t_own, t_tot, bh.grp_count, t_ext, bh.grp_hslot, t_row, bh.n_topologies);
   u32 mismatch = 0;
-  HIPCHK(hipMemcpyAsync(&mismatch, r1 + mismatch_at, 4, hipMemcpyDeviceToHost, b->stream));
+  HIPCHK(hipMemcpyAsync(&mismatch, d_mismatch, 4, hipMemcpyDeviceToHost, b->stream));
   HIPCHK(hipStreamSynchronize(b->stream)); HIPCHK(hipGetLastError());
   if (mismatch) return fail(KS_ERR_INVALID, "n_pods does not match the pods bound to the candidate nodes");
   guard.ok = true; *out = b; return KS_OK;
@@ -3329,18 +3327,23 @@ static void launch_static(const DevProb* probs, u32 n, const StaticDims& a, u32 
     else { hipLaunchKernelGGL(ks_grid_types, dim3((u32)((waves * 64 + 255) / 256), n), dim3(256), 0, st, probs, wave_target, row_lo, row_hi); }
   }
 }
+struct EventPair {      // the two events a timed launch sits between: destroyed on every exit path
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  EventPair() = default; EventPair(const EventPair&) = delete; EventPair& operator=(const EventPair&) = delete;
+  int create() { HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1)); return KS_OK; }
+  ~EventPair() { if (e0) hipEventDestroy(e0); if (e1) hipEventDestroy(e1); }
+};
 // Build the derived tables + the feasibility grid (idempotent).  Returns the grid kernels' time.
 static int build_static(ks_dev_problem* d, float* grid_ms, u32 row_lo = 0, u32 row_hi = 0xFFFFFFFFu) {
   HIPCHK(hipSetDevice(d->device));
-  hipEvent_t e0 = nullptr, e1 = nullptr; HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
+  EventPair ev; TRY(ev.create());
   StaticDims a; static_dims_of(d->h, 8192, a);
-  launch_static(d->d_prob, 1, a, 8192, d->stream, e0, row_lo, row_hi);
+  launch_static(d->d_prob, 1, a, 8192, d->stream, ev.e0, row_lo, row_hi);
   d->tables_built = row_lo == 0 && (size_t)row_hi >= (size_t)d->h.M * d->h.C;      // (a row range: the grid is whole once the other rows are installed)
-  HIPCHK(hipEventRecord(e1, d->stream));
+  HIPCHK(hipEventRecord(ev.e1, d->stream));
   HIPCHK(hipStreamSynchronize(d->stream));
   HIPCHK(hipGetLastError());
-  if (grid_ms) HIPCHK(hipEventElapsedTime(grid_ms, e0, e1));
-  hipEventDestroy(e0); hipEventDestroy(e1);
+  if (grid_ms) HIPCHK(hipEventElapsedTime(grid_ms, ev.e0, ev.e1));
   return KS_OK;
 }
 
@@ -3392,26 +3395,38 @@ extern "C" int ks_feasibility_grid_install(ks_dev_problem* d, uint32_t row_lo, u
   return KS_OK;
 }
 
+// The result arrays of one Solve, named ONCE: X(DevState field, ks_result field, element type, count), the count in terms of P pods, N new nodes, TW, R, K.
+// Every read-back goes by this list, in this order: ks_gather's segments and their size (a batch), download_batch's unpacking, download's transfers (one Solve).
+#define KS_RESULT_SEGS(X) \
+  X(pod_node, pod_node, i32, P) X(pod_stage, pod_stage, i32, P) X(pod_seq, pod_seq, i32, P) X(pod_reason, pod_reason, u32, P) X(unscheduled, unscheduled, i32, P) \
+  X(n_tmpl, node_tmpl, i32, N) X(n_alive, node_types, u64, N * TW) X(o_req, node_requests, i64, N * R) X(o_reqmask, node_requests_present, u32, N) \
+  X(o_present, node_present, u32, N) X(o_complement, node_complement, u32, N) X(o_mask, node_mask, u64, N * K) X(o_gt, node_gt, i32, N * K) X(o_lt, node_lt, i32, N * K) \
+  X(o_it, node_it_state, i32, N)
+#define X(sf, rf, T, cnt) static_assert(std::is_same<decltype(DevState::sf), T*>::value && std::is_same<decltype(ks_result::rf), T*>::value, "KS_RESULT_SEGS: element type of " #sf);
+KS_RESULT_SEGS(X)
+#undef X
 // Batched read-back: one descriptor per problem, one block copies that problem's result arrays into a contiguous blob
-// (segments in the order of ks_gather_layout), so the host needs three transfers per batch instead of ~16 per problem.
+// (the segments of KS_RESULT_SEGS, each padded to 8 bytes), so the host needs three transfers per batch instead of ~16 per problem.
 struct GatherDesc { u64 off; u32 P, K, R, TW, N, pad; };
 struct GatherSeg { const void* src; u64 bytes; };
 __device__ __host__ inline u64 ks_pad8(u64 b) { return (b + 7) & ~7ull; }
 __global__ __launch_bounds__(256) void ks_gather(const DevState* states, const GatherDesc* descs, u8* blob) {
   const DevState& s = states[blockIdx.x]; const GatherDesc g = descs[blockIdx.x];
   const u64 P = g.P, N = g.N, K = g.K, R = g.R, TW = g.TW;
-  const GatherSeg segs[15] = {{s.pod_node, P * 4}, {s.pod_stage, P * 4}, {s.pod_seq, P * 4}, {s.pod_reason, P * 4}, {s.unscheduled, P * 4}, {s.n_tmpl, N * 4}, {s.n_alive, N * TW * 8},
-                              {s.o_req, N * R * 8}, {s.o_reqmask, N * 4}, {s.o_present, N * 4}, {s.o_complement, N * 4}, {s.o_mask, N * K * 8}, {s.o_gt, N * K * 4},
-                              {s.o_lt, N * K * 4}, {s.o_it, N * 4}};
+#define X(sf, rf, T, cnt) {s.sf, (cnt) * sizeof(T)},
+  const GatherSeg segs[] = {KS_RESULT_SEGS(X)};
+#undef X
   u64 off = g.off;
-  for (int i = 0; i < 15; ++i) {
+  for (u32 i = 0; i < sizeof segs / sizeof segs[0]; ++i) {
     const u32* src = (const u32*)segs[i].src; u32* dst = (u32*)(blob + off);
     for (u64 j = threadIdx.x; j < segs[i].bytes / 4; j += blockDim.x) dst[j] = src[j];
     off += ks_pad8(segs[i].bytes);
   }
 }
 static u64 ks_gather_bytes(u64 P, u64 K, u64 R, u64 TW, u64 N) {
-  return 5 * ks_pad8(P * 4) + ks_pad8(N * 4) + ks_pad8(N * TW * 8) + ks_pad8(N * R * 8) + 3 * ks_pad8(N * 4) + ks_pad8(N * K * 8) + 2 * ks_pad8(N * K * 4) + ks_pad8(N * 4);
+#define X(sf, rf, T, cnt) + ks_pad8((cnt) * sizeof(T))
+  return 0 KS_RESULT_SEGS(X);
+#undef X
 }
 static int ks_stats_error(const u64* stats) {
   if (!stats[KS_STAT_ERR]) return KS_OK;
@@ -3443,11 +3458,9 @@ static int download_batch(ks_dev_problem* const* ds, u32 n, const DevState* dsv,
   for (u32 i = 0; i < n; ++i) {
     const DevProb& h = ds[i]->h; ks_result* out = outs[i]; const u64 P = h.P, K = h.K, R = h.R, TW = h.TW, N = out->n_new;
     const u8* p = blob.data() + descs[i].off;
-    auto take = [&](void* dst, u64 bytes) { if (bytes) memcpy(dst, p, bytes); p += ks_pad8(bytes); };
-    take(out->pod_node, P * 4); take(out->pod_stage, P * 4); take(out->pod_seq, P * 4); take(out->pod_reason, P * 4); take(out->unscheduled, P * 4);
-    take(out->node_tmpl, N * 4); take(out->node_types, N * TW * 8); take(out->node_requests, N * R * 8); take(out->node_requests_present, N * 4);
-    take(out->node_present, N * 4); take(out->node_complement, N * 4); take(out->node_mask, N * K * 8); take(out->node_gt, N * K * 4); take(out->node_lt, N * K * 4);
-    take(out->node_it_state, N * 4);
+#define X(sf, rf, T, cnt) { const u64 bytes = (cnt) * sizeof(T); if (bytes) memcpy(out->rf, p, bytes); p += ks_pad8(bytes); }
+    KS_RESULT_SEGS(X)
+#undef X
   }
   return KS_OK;
 }
@@ -3458,22 +3471,11 @@ static int download(ks_dev_problem* d, ks_result* out) {
   HIPCHK(hipMemcpy(out->stats, s.stats, 32 * sizeof(u64), hipMemcpyDeviceToHost));
   out->n_new = counts[0]; out->n_unscheduled = counts[1];
   TRY(ks_stats_error(out->stats));
-  const u32 P = h.P, K = h.K, R = h.R, TW = h.TW, N = out->n_new;
-  if (P) {
-    HIPCHK(hipMemcpy(out->pod_node, s.pod_node, P * sizeof(i32), hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(out->pod_stage, s.pod_stage, P * sizeof(i32), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(out->pod_seq, s.pod_seq, P * sizeof(i32), hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(out->unscheduled, s.unscheduled, P * sizeof(i32), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(out->pod_reason, s.pod_reason, P * sizeof(u32), hipMemcpyDeviceToHost));
-  }
-  if (N) {
-    HIPCHK(hipMemcpy(out->node_tmpl, s.n_tmpl, N * sizeof(i32), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(out->node_types, s.n_alive, (size_t)N * TW * sizeof(u64), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(out->node_requests, s.o_req, (size_t)N * R * sizeof(i64), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(out->node_requests_present, s.o_reqmask, N * sizeof(u32), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(out->node_present, s.o_present, N * sizeof(u32), hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(out->node_complement, s.o_complement, N * sizeof(u32), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(out->node_mask, s.o_mask, (size_t)N * K * sizeof(u64), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(out->node_gt, s.o_gt, (size_t)N * K * sizeof(i32), hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(out->node_lt, s.o_lt, (size_t)N * K * sizeof(i32), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(out->node_it_state, s.o_it, N * sizeof(i32), hipMemcpyDeviceToHost));
-  }
+  const u64 P = h.P, K = h.K, R = h.R, TW = h.TW, N = out->n_new;
+  // one transfer per segment, straight into the caller's arrays
+#define X(sf, rf, T, cnt) if (cnt) HIPCHK(hipMemcpy(out->rf, s.sf, (cnt) * sizeof(T), hipMemcpyDeviceToHost));
+  KS_RESULT_SEGS(X)
+#undef X
   return KS_OK;
 }
 
@@ -3535,6 +3537,18 @@ extern "C" int ks_debug_pack_choice(uint32_t traits, int32_t* fields, uint32_t* 
   return row;
 }
 
+// Once per device, under a lock (two Solves may run concurrently): `init` runs the first time a device comes by -- a function attribute is per device -- and the
+// nonzero word it leaves is kept for that device and handed to every later caller.
+struct OncePerDevice {
+  std::mutex mu; std::vector<u32> kept;
+  template <class F> int get(int device, u32* out, F&& init) {
+    std::lock_guard<std::mutex> g(mu);
+    if ((size_t)device >= kept.size()) kept.resize(device + 1, 0);
+    if (!kept[device]) TRY(init(&kept[device]));
+    *out = kept[device]; return KS_OK;
+  }
+};
+
 extern "C" int ks_solve_batch_dev(ks_dev_problem* const* ds, uint32_t n, ks_result* const* outs, float* kernel_ms) {
   if (!n) return KS_OK;
   if (!ds) return fail(KS_ERR_INVALID, "null batch");
@@ -3560,8 +3574,8 @@ extern "C" int ks_solve_batch_dev(ks_dev_problem* const* ds, uint32_t n, ks_resu
     launch_static(dp, n, a, wave_target, st, nullptr);
     for (u32 i = 0; i < n; ++i) ds[i]->tables_built = true;
   }
-  hipEvent_t e0, e1; HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
-  HIPCHK(hipEventRecord(e0, st));
+  EventPair ev; TRY(ev.create());
+  HIPCHK(hipEventRecord(ev.e0, st));
   // What the batch is, for the choice of kernel.  FAST reads the dynamic LDS of the single-wave launch: Allocatable table + visiting-order array.
   const u32 lds_one = pack_lds_one_wave(n == 1);
   bool fast = true, bounds = false, lean = true, wide = false, lean8 = false; u32 any_flags = 0;
@@ -3596,24 +3610,18 @@ extern "C" int ks_solve_batch_dev(ks_dev_problem* const* ds, uint32_t n, ks_resu
   if (rr_on && n == 1 && lean && !lean8 && !bounds && fast && !ds[0]->view && !(ds[0]->h.flags & KS_FLAG_STATS) && ds[0]->h.rr_briefs) {
     // dynamic LDS: the Allocatable ladders (R x ge_max x 8 bytes), at most what the kernel's static LDS object leaves of the CU's 160 KiB (a problem whose ladders
     // do not fit is declined by the kernel itself: its eligibility test reads the size it was given)
-    u32 lds_rr = 0;
-    {
-      static std::mutex rr_mu; static std::vector<u32> rr_attr;
-      std::lock_guard<std::mutex> g(rr_mu);
-      if ((size_t)device >= rr_attr.size()) rr_attr.resize(device + 1, 0);
-      if (!rr_attr[device]) {
+    static OncePerDevice rr_room; u32 room = 0;
+    TRY(rr_room.get(device, &room, [](u32* keep) -> int {
 #ifdef KS_SIM
-        const u32 room = 44u * 1024u;
+      const u32 room = 44u * 1024u;
 #else
-        hipFuncAttributes fa; HIPCHK(hipFuncGetAttributes(&fa, (const void*)ks_pack_rr));
-        if (fa.sharedSizeBytes + 1024u > 160u * 1024u) return fail(KS_ERR_DEVICE, "ks_pack_rr: the static LDS object leaves no room for the ladders");
-        const u32 room = std::min<u32>(44u * 1024u, (u32)(160u * 1024u - fa.sharedSizeBytes) & ~255u);
+      hipFuncAttributes fa; HIPCHK(hipFuncGetAttributes(&fa, (const void*)ks_pack_rr));
+      if (fa.sharedSizeBytes + 1024u > 160u * 1024u) return fail(KS_ERR_DEVICE, "ks_pack_rr: the static LDS object leaves no room for the ladders");
+      const u32 room = std::min<u32>(44u * 1024u, (u32)(160u * 1024u - fa.sharedSizeBytes) & ~255u);
 #endif
-        HIPCHK(hipFuncSetAttribute((const void*)ks_pack_rr, hipFuncAttributeMaxDynamicSharedMemorySize, (int)room)); rr_attr[device] = room;
-      }
-      const u32 need = (u32)(((size_t)ds[0]->h.R * ds[0]->h.ge_max * 8 + 64 + 255) & ~(size_t)255);
-      lds_rr = std::min(rr_attr[device], need);
-    }
+      HIPCHK(hipFuncSetAttribute((const void*)ks_pack_rr, hipFuncAttributeMaxDynamicSharedMemorySize, (int)room)); *keep = room; return KS_OK;
+    }));
+    const u32 lds_rr = std::min(room, (u32)(((size_t)ds[0]->h.R * ds[0]->h.ge_max * 8 + 64 + 255) & ~(size_t)255));
     hipLaunchKernelGGL(ks_pack_rr, dim3(1), dim3(64 * RR_NW), lds_rr, st, dp, dsv, lds_rr);
     u64 rr_err[8] = {0, 0, 0, 0, 0, 0, 0, 0};      // stats[7..14]: the error word ... the decline code
     HIPCHK(hipMemcpyAsync(rr_err, ds[0]->hs.stats + KS_STAT_ERR, sizeof rr_err, hipMemcpyDeviceToHost, st));
@@ -3633,24 +3641,19 @@ extern "C" int ks_solve_batch_dev(ks_dev_problem* const* ds, uint32_t n, ks_resu
     u32 lds = 0; const int row = pack_choose(traits, &lds);
     if (row < 0) return fail(KS_ERR_INTERNAL, "ks_pack: no instantiation for these traits");
     const PackRow& r = pack_rows[row];
-    {   // the large dynamic-LDS opt-in is a per-device function attribute: set it once per device, race-free (two Solves may run concurrently)
-      static std::mutex attr_mu; static std::vector<char> attr_done;
-      std::lock_guard<std::mutex> g(attr_mu);
-      if ((size_t)device >= attr_done.size()) attr_done.resize(device + 1, 0);
-      if (!attr_done[device]) {
-        for (const PackRow& a : pack_rows) HIPCHK(hipFuncSetAttribute((const void*)a.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)a.lds_max));
-        attr_done[device] = 1;
-      }
-    }
+    static OncePerDevice pack_attr; u32 attr_set = 0;      // the large dynamic-LDS opt-in of every row
+    TRY(pack_attr.get(device, &attr_set, [](u32* keep) -> int {
+      for (const PackRow& a : pack_rows) HIPCHK(hipFuncSetAttribute((const void*)a.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)a.lds_max));
+      *keep = 1; return KS_OK;
+    }));
     hipLaunchKernelGGL(r.fn, dim3(n), dim3(64 * r.nw), lds, st, dp, dsv, lds);
     for (u32 i = 0; i < n; ++i) { ds[i]->pack_rm = r.rm; ds[i]->pack_lean = r.lean; ds[i]->pack_row = row; }
   }
 #endif
-  HIPCHK(hipEventRecord(e1, st));
+  HIPCHK(hipEventRecord(ev.e1, st));
   HIPCHK(hipStreamSynchronize(st));
   HIPCHK(hipGetLastError());
-  if (kernel_ms) HIPCHK(hipEventElapsedTime(kernel_ms, e0, e1));
-  hipEventDestroy(e0); hipEventDestroy(e1);
+  if (kernel_ms) HIPCHK(hipEventElapsedTime(kernel_ms, ev.e0, ev.e1));
   int rc = KS_OK;
   if (!outs) {       // results stay on the device (ks_batch_records_dev / ks_price_filter_dev / ... read them there): only the error words come back
     if (n > 1) { std::vector<u64> meta((size_t)n * 34); HIPCHK(hipMemcpy(meta.data(), d_meta, meta.size() * sizeof(u64), hipMemcpyDeviceToHost)); for (u32 i = 0; i < n && rc == KS_OK; ++i) rc = ks_stats_error(&meta[(size_t)i * 34 + 2]); }
@@ -3937,20 +3940,25 @@ extern "C" int ks_consolidation_commands_dev(ks_dev_problem* const* ds, uint32_t
   BatchStage st; TRY(commands_check(st, ds, n, ids, in, words));
   return commands_launch(st, ids, in, words, d_out);
 }
-// The same with the rows brought to the host (what a caller without a device buffer of its own wants): ms[0] = inputs up + launch + completion, ms[1] = read-back.
-extern "C" int ks_consolidation_commands_host(ks_dev_problem* const* ds, uint32_t n, const uint64_t* ids, const ks_command_inputs* in, uint32_t words, uint64_t* out_rows, double* ms) {
+// What the *_commands_host entry points do around their own check and launch: the rows land in a device block of the call's, then on the host.
+// ms[0] = inputs up + launch + completion, ms[1] = read-back (both 0 where nothing ran).
+template <class Check, class Launch> static int rows_to_host(u32 n, size_t row_words, uint64_t* out_rows, double* ms, Check&& check, Launch&& launch) {
   if (ms) ms[0] = ms[1] = 0.0;
   if (!n) return KS_OK;
   if (!out_rows) return fail(KS_ERR_INVALID, "null argument");
-  BatchStage st; TRY(commands_check(st, ds, n, ids, in, words));
-  const size_t bytes = (size_t)n * KS_CMD_ROW_WORDS(words) * sizeof(u64);
-  TmpDev buf(ds[0]->device); TRY(buf.alloc(bytes));
+  BatchStage st; TRY(check(st));
+  const size_t bytes = (size_t)n * row_words * sizeof(u64); TmpDev buf(st.dev.device); TRY(buf.alloc(bytes));
   const auto t0 = std::chrono::steady_clock::now();
-  TRY(commands_launch(st, ids, in, words, buf.p));
+  TRY(launch(st, buf.p));
   const auto t1 = std::chrono::steady_clock::now();
   HIPCHK(hipMemcpy(out_rows, buf.p, bytes, hipMemcpyDeviceToHost));
   if (ms) { ms[0] = std::chrono::duration<double, std::milli>(t1 - t0).count(); ms[1] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count(); }
   return KS_OK;
+}
+// The same with the rows brought to the host (what a caller without a device buffer of its own wants).
+extern "C" int ks_consolidation_commands_host(ks_dev_problem* const* ds, uint32_t n, const uint64_t* ids, const ks_command_inputs* in, uint32_t words, uint64_t* out_rows, double* ms) {
+  return rows_to_host(n, KS_CMD_ROW_WORDS(words), out_rows, ms, [&](BatchStage& st) { return commands_check(st, ds, n, ids, in, words); },
+                      [&](BatchStage& st, void* d_out) { return commands_launch(st, ids, in, words, d_out); });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -4022,20 +4030,10 @@ extern "C" int ks_validate_commands_dev(ks_dev_problem* const* ds, uint32_t n, c
   BatchStage st; TRY(validate_check(st, ds, n, ids, in, words));
   return validate_launch(st, ids, in, words, d_out);
 }
-// The same with the rows brought to the host: ms[0] = inputs up + launch + completion, ms[1] = read-back.
+// The same with the rows brought to the host (rows_to_host).
 extern "C" int ks_validate_commands_host(ks_dev_problem* const* ds, uint32_t n, const uint64_t* ids, const ks_validate_inputs* in, uint32_t words, uint64_t* out_rows, double* ms) {
-  if (ms) ms[0] = ms[1] = 0.0;
-  if (!n) return KS_OK;
-  if (!out_rows) return fail(KS_ERR_INVALID, "null argument");
-  BatchStage st; TRY(validate_check(st, ds, n, ids, in, words));
-  const size_t bytes = (size_t)n * KS_VAL_ROW_WORDS(words) * sizeof(u64);
-  TmpDev buf(ds[0]->device); TRY(buf.alloc(bytes));
-  const auto t0 = std::chrono::steady_clock::now();
-  TRY(validate_launch(st, ids, in, words, buf.p));
-  const auto t1 = std::chrono::steady_clock::now();
-  HIPCHK(hipMemcpy(out_rows, buf.p, bytes, hipMemcpyDeviceToHost));
-  if (ms) { ms[0] = std::chrono::duration<double, std::milli>(t1 - t0).count(); ms[1] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count(); }
-  return KS_OK;
+  return rows_to_host(n, KS_VAL_ROW_WORDS(words), out_rows, ms, [&](BatchStage& st) { return validate_check(st, ds, n, ids, in, words); },
+                      [&](BatchStage& st, void* d_out) { return validate_launch(st, ids, in, words, d_out); });
 }
 
 // ------------------------------------------------------------------------------------------------
