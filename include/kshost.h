@@ -145,6 +145,10 @@ int ksh_grid_install(void* handle, uint32_t row_lo, uint32_t row_hi, const uint6
  * handle's problem, in the caller's pod order; KS_ERR_UNSUPPORTED for a what-if derived on the device (it has no flattening of its own). */
 int ksh_debug_grid(void* handle, uint64_t* out /* [M][C][ceil(T/64)] */);
 int ksh_debug_pod_classes(void* handle, uint32_t* out /* [P] */);
+/* ksh_debug_classes: the per-class records the pack kernels take their shortcuts from (csrc/ksolve.hip ClsBrief, 128 bytes each, and ClsPlan), as the last build left
+ * them -- the handle's own, or the batch's it was solved in; built first only if nothing has built them yet.  Either destination may be NULL.  Returns sizeof(ClsPlan)
+ * (> 0: a caller that mirrors the layout checks it against its own), or KS_ERR_INVALID before an upload. */
+int ksh_debug_classes(void* handle, void* briefs /* [C] ClsBrief or NULL */, void* plans /* [C] ClsPlan or NULL */);
 int ksh_solve_ksp(const char* ksp_text, size_t len, uint32_t flags, char** out_text);  /* one shot: KSP1 in, KSR1 out */
 
 /* ---- results ---- */

@@ -4570,10 +4570,12 @@ extern "C" int ks_probe_has(const ks_req1* a, const int32_t* value_int, uint32_t
   return KS_OK;
 }
 
-// Diagnostics: the class briefs (evaluation-class ids, conflict masks) and plan records as the kernels see them.
+// Diagnostics: the class briefs (evaluation-class ids, conflict masks) and plan records as the kernels see them -- as the last build left them (this problem's own, or
+// the batch's it was solved in); built here, like ks_problem_prepare, only when nothing has built them yet.  Returns sizeof(ClsPlan).
 extern "C" int ks_debug_classes(ks_dev_problem* d, void* briefs_out, void* plans_out) {
   if (!d) return fail(KS_ERR_INVALID, "null device problem");
-  TRY(build_static(d, nullptr));
+  if (!d->tables_built) TRY(build_static(d, nullptr));
+  HIPCHK(hipSetDevice(d->device));
   if (briefs_out) HIPCHK(hipMemcpy(briefs_out, d->h.briefs, (size_t)d->h.C * sizeof(ClsBrief), hipMemcpyDeviceToHost));
   if (plans_out) HIPCHK(hipMemcpy(plans_out, d->h.plans, (size_t)d->h.C * sizeof(ClsPlan), hipMemcpyDeviceToHost));
   return (int)sizeof(ClsPlan);

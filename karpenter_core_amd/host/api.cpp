@@ -708,7 +708,12 @@ int ksh_solve_ksp(const char* ksp_text, size_t len, uint32_t flags, char** out_t
 }
 
 extern "C" int ks_debug_classes(ks_dev_problem*, void*, void*);
-int ksh_debug_classes(void* hv, void* briefs, void* plans) { Handle* h = (Handle*)hv; if (!h->dev) return KS_ERR_INVALID; return ks_debug_classes(h->dev, briefs, plans); }
+int ksh_debug_classes(void* hv, void* briefs, void* plans) {
+  Handle* h = (Handle*)hv; if (!h || !h->dev) return set_err(KS_ERR_INVALID, "class tables of a handle that was not uploaded");
+  const int rc = ks_debug_classes(h->dev, briefs, plans);
+  if (rc < 0) return set_err(rc, ks_last_error());
+  return rc;
+}
 
 // dims for tests / bench: [P,C,T,M,E,K,R,G,GH,S]
 // The result as ARRAYS (round 5): what scheduler.Solve returns -- Node.Pods in commit order, InstanceTypeOptions, Requests, Requirements, the relaxation stage every pod

@@ -68,6 +68,7 @@ def libs():
         kh.ksh_grid_install.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
         kh.ksh_debug_grid.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
         kh.ksh_debug_pod_classes.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        kh.ksh_debug_classes.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
         kh.ksh_price_filter.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint32),
                                         ctypes.POINTER(ctypes.c_uint64), ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]
         kh.ksh_dims.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32)]
@@ -116,6 +117,42 @@ def libs():
 
 def device_count() -> int:
     return int(libs()[0].ks_device_count())
+
+
+# ---- mirrors of the per-class device records (csrc/ksolve.hip), read back by FlatProblem.class_tables() ----
+KS_RES_NARROW, KS_MAX_TOUCH, KS_MAX_TOPO, KS_MAX_HOST, KS_MAX_REC = 8, 12, 24, 3, 24
+
+
+class PlanTouch(ctypes.Structure):
+    _fields_ = [("mask", ctypes.c_uint64), ("gt", ctypes.c_int32), ("lt", ctypes.c_int32), ("key", ctypes.c_int32), ("own", ctypes.c_uint8), ("complement", ctypes.c_uint8),
+                ("topo_begin", ctypes.c_uint8), ("topo_end", ctypes.c_uint8)]
+
+
+class PlanTopo(ctypes.Structure):
+    _fields_ = [("PD", ctypes.c_uint64), ("g", ctypes.c_int32), ("maxskew", ctypes.c_int32), ("type", ctypes.c_uint8), ("self", ctypes.c_uint8), ("pod_has", ctypes.c_uint8),
+                ("hslot", ctypes.c_uint8), ("pad", ctypes.c_uint32)]
+
+
+class PlanRec(ctypes.Structure):
+    _fields_ = [("g", ctypes.c_int32), ("key", ctypes.c_int32), ("type", ctypes.c_uint8), ("owned_inverse", ctypes.c_uint8), ("hslot", ctypes.c_uint16), ("tidx", ctypes.c_uint8),
+                ("filtered", ctypes.c_uint8), ("pad", ctypes.c_uint16)]
+
+
+class ClsPlan(ctypes.Structure):      # alignas(16): the tail pads the record to the next multiple of 16 bytes
+    _fields_ = [("c", ctypes.c_uint32), ("present", ctypes.c_uint32), ("complement", ctypes.c_uint32), ("it_state", ctypes.c_int32),
+                ("hn_mode", ctypes.c_uint32), ("hn_off", ctypes.c_uint32), ("hn_cnt", ctypes.c_uint32), ("reqmask", ctypes.c_uint32),
+                ("tol", ctypes.c_uint64), ("port_off", ctypes.c_uint32), ("port_cnt", ctypes.c_uint32),
+                ("vol_off", ctypes.c_uint32), ("vol_cnt", ctypes.c_uint32), ("mono", ctypes.c_uint32), ("dyn", ctypes.c_uint32),
+                ("ntouch", ctypes.c_uint32), ("ntopo", ctypes.c_uint32), ("nhost", ctypes.c_uint32), ("nrec", ctypes.c_uint32),
+                ("req", ctypes.c_int64 * KS_RES_NARROW), ("touch", PlanTouch * KS_MAX_TOUCH), ("topo", PlanTopo * KS_MAX_TOPO), ("host", PlanTopo * KS_MAX_HOST),
+                ("rec", PlanRec * KS_MAX_REC), ("tmask", ctypes.c_uint64), ("rmask", ctypes.c_uint64), ("overflow", ctypes.c_uint32), ("eq", ctypes.c_uint32),
+                ("tkeys", ctypes.c_uint64), ("_tail", ctypes.c_uint8 * 8)]
+
+
+class ClsBrief(ctypes.Structure):
+    _fields_ = [("tmask", ctypes.c_uint64), ("tfull", ctypes.c_uint64), ("rmask", ctypes.c_uint64), ("ev", ctypes.c_uint32), ("flags", ctypes.c_uint32),
+                ("reqmask", ctypes.c_uint32), ("dyn", ctypes.c_uint32), ("req", ctypes.c_int64 * KS_RES_NARROW), ("zmask", ctypes.c_uint64), ("rsure", ctypes.c_uint64),
+                ("dyn_maxskew", ctypes.c_int32), ("dyn_pd", ctypes.c_uint32)]
 
 
 class FlatProblem:
@@ -290,6 +327,27 @@ class FlatProblem:
         if rc != KS_OK:
             raise KSolveError(rc, kh.ksh_last_error().decode())
         return arr[:self.dims["P"]]
+
+    def class_tables(self):
+        """ksh_debug_classes: (briefs, plans), ctypes arrays of `ClsBrief` / `ClsPlan` [C], row c = pod class c (`pod_classes()` maps pods to rows) -- the records the pack
+        kernels take their shortcuts from, as the last build left them: this handle's own (`grid()` rebuilds), or the batch's it was solved in.  Uploads the problem
+        if it is not resident and builds the tables only if nothing has built them yet.  The mirrors' sizes are checked against the library's: a layout that
+        drifted is an error, never a misread."""
+        kh = libs()[1]
+        assert ctypes.sizeof(ClsBrief) == 128, ctypes.sizeof(ClsBrief)
+        C = self.dims["C"]
+        briefs, plans = (ClsBrief * max(1, C))(), (ClsPlan * max(1, C))()
+        rc = kh.ksh_debug_classes(self._h, None, None)
+        if rc == KS_ERR_INVALID:      # not resident yet
+            self.upload()
+            rc = kh.ksh_debug_classes(self._h, None, None)
+        if rc < 0:
+            raise KSolveError(rc, kh.ksh_last_error().decode())
+        assert rc == ctypes.sizeof(ClsPlan), f"ClsPlan is {rc} bytes in the library, {ctypes.sizeof(ClsPlan)} in the Python mirror"
+        rc = kh.ksh_debug_classes(self._h, ctypes.byref(briefs), ctypes.byref(plans))
+        if rc < 0:
+            raise KSolveError(rc, kh.ksh_last_error().decode())
+        return briefs, plans
 
     def grid_rows(self, lo: int, hi: int, dev_ptr: int = 0):
         """ksh_grid_rows: rows [lo, hi) of the M * C grid rows computed on this handle's device; returns (numpy uint64 [hi - lo, TW], kernel ms).  dev_ptr: also

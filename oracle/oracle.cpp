@@ -902,12 +902,19 @@ struct Scheduler {
   //              candidate's evaluation reads; a taken node is covered by the order rule)
   // maxcls > 0:  a round holds at most `maxcls` distinct evaluation classes (one wave evaluates one class for all its pods)
   // out[6] pods in rounds of >= 8, out[7] largest round
-  std::string eval_signature(PodState& ps) {
+  // taints != nullptr (the exported class model, class_model below): the toleration text is replaced by WHICH of these taints the pod tolerates, and the pod's volumes
+  // are added -- two spellings of a toleration that tolerate the same taints evaluate alike, two pods with different volumes do not.
+  std::string eval_signature(PodState& ps, const std::vector<ksp::Taint>* taints = nullptr) {
     ksp::Pod& pod = ps.spec; std::string s;
     Reqs pr = new_pod_requirements(pod);
     for (auto& kv : pr.m) { s += STR(kv.first); s += kv.second.complement ? '!' : '='; for (Sym v : kv.second.values.v) { s += STR(v); s += ','; } s += kv.second.has_gt ? std::to_string(kv.second.gt) : "-"; s += kv.second.has_lt ? std::to_string(kv.second.lt) : "-"; s += ';'; }
     ResList rq = requests_for_pods({&pod}); for (auto& kv : rq) { s += kv.first; s += std::to_string(kv.second); s += ','; }
-    for (auto& t : pod.tolerations) { s += t.key + "/" + t.op + "/" + t.value + "/" + t.effect + ";"; }
+    if (!taints) for (auto& t : pod.tolerations) { s += t.key + "/" + t.op + "/" + t.value + "/" + t.effect + ";"; }
+    else {
+      for (auto& taint : *taints) { bool tol = false; for (auto& t : pod.tolerations) tol = tol || tolerates_taint(t, taint); s += tol ? '1' : '0'; }
+      s += pod.volume_error ? "|V!" : "|V"; for (auto& v : pod.volumes) s += v.driver + "/" + v.pvc + ";";
+      s += "|";
+    }
     for (auto& c : pod.containers) for (auto& hp : c.ports) { s += hp.ip + ":" + std::to_string(hp.port) + hp.proto + ";"; }
     for (auto& tc : topo.topologies) if (tc->owners.count(pod.uid)) { s += "T" + std::to_string((uintptr_t)tc.get()) + (tg_selects(*tc, pod) ? "s" : "n"); }
     for (auto& tc : topo.inverse) if (tg_selects(*tc, pod)) { s += "I" + std::to_string((uintptr_t)tc.get()); }
@@ -1025,6 +1032,19 @@ struct Scheduler {
   // mode 2 (a lead for the next round): EVERY class whose own requirements are on well-known keys -- spread and affinity classes too -- keeps
   // refusals monotone as long as the refusal happens BEFORE the topology steps.  out[4] counts the pre-topology refusals put on record, out[5] the later dry
   // runs of a recorded (class, node) pair; a recorded node that accepts is a violation (out[0]).
+  // The class-eligibility test of the watermark (ksolve.hip ClsPlan::mono): own requirements on well-known keys only, topology items all anti-affinity (own or inverse).
+  // any_item (the check's mutation / pre-topology modes): spread and affinity items do not disqualify.  *anti: the class has an anti-affinity item.
+  bool watermark_class(PodState& ps, bool any_item, bool* anti = nullptr) {
+    bool eligible = true, a = false;
+    Reqs pr = new_pod_requirements(ps.spec);
+    // (the hostname is no well-known label, but every existing node defines it -- NewExistingNode adds hostname In [its name], existingnode.go:73 -- so a requirement on
+    //  it never meets the "label does not have known values" case that makes a custom label non-monotone: the kernel keeps the key out of ClsPlan::present)
+    for (auto& kv : pr.m) if (!cx.well_known.count(kv.first) && kv.first != hostnameKey) eligible = false;
+    for (auto& tc : topo.topologies) if (tc->owners.count(ps.spec.uid)) { if (tc->type == kAntiAffinity) a = true; else if (!any_item) eligible = false; }
+    for (auto& tc : topo.inverse) if (tg_selects(*tc, ps.spec)) a = true;
+    if (anti) *anti = a;
+    return eligible;
+  }
   void solve_watermark_check(long long* out, bool mutate, bool pre_only = false) {
     for (int i = 0; i < 8; ++i) out[i] = 0;
     std::vector<int> q(pods.size()); for (size_t i = 0; i < pods.size(); ++i) q[i] = (int)i;
@@ -1047,11 +1067,7 @@ struct Scheduler {
       queue.pop_front(); st.queue_pops++;
       PodState& ps = pods[pi];
       {
-        bool eligible = true, anti = false;
-        Reqs pr = new_pod_requirements(ps.spec);
-        for (auto& kv : pr.m) if (!cx.well_known.count(kv.first)) eligible = false;
-        for (auto& tc : topo.topologies) if (tc->owners.count(ps.spec.uid)) { if (tc->type == kAntiAffinity) anti = true; else if (!mutate && !pre_only) eligible = false; }
-        for (auto& tc : topo.inverse) if (tg_selects(*tc, ps.spec)) anti = true;
+        bool anti = false; const bool eligible = watermark_class(ps, mutate || pre_only, &anti);
         if (eligible && !existing.empty()) {
           out[2]++; if (anti) out[3]++;
           auto& rf = refused[eval_signature(ps)]; rf.resize(existing.size(), 0);
@@ -1106,17 +1122,82 @@ struct Scheduler {
     if (m && filter_types(m->options, nodeReqs, requests).empty()) return done(false, false);
     return done(true, !reqs_equal(nodeReqs, base));
   }
-  void solve_spec_v2(int W, long long* out, int flags = 0, int maxcls = 0) {
-    typedef const TopologyGroup* G; typedef std::set<G> GS;
-    auto meets = [](const GS& a, const GS& b) { for (G g : a) if (b.count(g)) return true; return false; };
-    auto trivial_filter = [](const TopologyGroup& t) { if (t.filter.always || t.filter.terms.empty()) return true; for (auto& term : t.filter.terms) if (term.m.empty()) return true; return false; };
-    const bool no_rdyn = (flags & 4) != 0;
-    GS initial; for (auto& tc : topo.topologies) initial.insert(tc.get());
-    // groups the resolver follows exactly: unfiltered spread groups present from the start on ONE narrow key (the one with the most of them)
+  // ---- the model of a pod class (what ksolve.hip keeps per class in ClsPlan / ClsBrief): used by solve_spec_v2 below AND exported by class_model ----
+  typedef const TopologyGroup* G; typedef std::set<G> GS;
+  static bool trivial_filter(const TopologyGroup& t) { if (t.filter.always || t.filter.terms.empty()) return true; for (auto& term : t.filter.terms) if (term.m.empty()) return true; return false; }
+  GS initial_groups() { GS initial; for (auto& tc : topo.topologies) initial.insert(tc.get()); return initial; }
+  // groups the resolver follows exactly: unfiltered spread groups present from the start on ONE narrow key (the one with the most of them)
+  GS model_dyn_groups() {
     GS dyn_groups;
-    { std::map<Sym, std::vector<G>> per; for (auto& tc : topo.topologies) if (tc->type == kSpread && !tc->is_hostname && trivial_filter(*tc) && tc->domains.size() <= 8) per[tc->key].push_back(tc.get());
-      const std::vector<G>* best = nullptr; for (auto& kv : per) if (!best || kv.second.size() > best->size()) best = &kv.second;
-      if (best) for (size_t i = 0; i < best->size() && i < 16; ++i) dyn_groups.insert((*best)[i]); }
+    std::map<Sym, std::vector<G>> per; for (auto& tc : topo.topologies) if (tc->type == kSpread && !tc->is_hostname && trivial_filter(*tc) && tc->domains.size() <= 8) per[tc->key].push_back(tc.get());
+    const std::vector<G>* best = nullptr; for (auto& kv : per) if (!best || kv.second.size() > best->size()) best = &kv.second;
+    if (best) for (size_t i = 0; i < best->size() && i < 16; ++i) dyn_groups.insert((*best)[i]);
+    return dyn_groups;
+  }
+  struct Info { std::vector<TopologyGroup*> narrow, host; GS tmask, tfull, rmask, rsure, zmask; bool eligible = true; int dyn = 0; TopologyGroup* dg = nullptr; bool self = false; std::string ev; ResList req; };
+  Info class_info(PodState& ps, const GS& initial, const GS& dyn_groups) {
+    ksp::Pod& pod = ps.spec; Info in; in.ev = eval_signature(ps); in.req = requests_for_pods({&pod});
+    for (auto& c : pod.containers) if (!c.ports.empty()) in.eligible = false;
+    if (pod.volume_error || !pod.volumes.empty()) in.eligible = false;
+    if (!topo.inert) {
+      Reqs podReqs = new_pod_requirements(pod);
+      for (auto& tc : topo.topologies) if (tc->owners.count(pod.uid)) { (tc->is_hostname ? in.host : in.narrow).push_back(tc.get()); }
+      for (auto& tc : topo.inverse) if (tg_selects(*tc, pod)) { (tc->is_hostname ? in.host : in.narrow).push_back(tc.get()); }
+      for (auto* g : in.narrow) { in.tmask.insert(g); in.tfull.insert(g); }
+      for (auto* g : in.host) {
+        in.tfull.insert(g); const bool self = tg_selects(*g, pod);
+        const bool own_counter_only = g->type == kAntiAffinity || (g->type == kSpread && initial.count(g));
+        if (!own_counter_only) in.tmask.insert(g);
+        if (g->type == kAntiAffinity || (g->type == kSpread && (int64_t)g->max_skew - (self ? 1 : 0) <= 0)) in.zmask.insert(g);
+      }
+      for (auto& tc : topo.topologies) if (tg_selects(*tc, pod)) {
+        in.rmask.insert(tc.get());
+        if (tc->is_hostname) { if (initial.count(tc.get()) && trivial_filter(*tc)) in.rsure.insert(tc.get()); if (!initial.count(tc.get())) in.eligible = false; }
+      }
+      for (auto& tc : topo.inverse) if (tc->owners.count(pod.uid)) { in.rmask.insert(tc.get()); if (tc->is_hostname) in.rsure.insert(tc.get()); }
+      if (in.narrow.size() == 1 && in.host.empty() && in.narrow[0]->type == kSpread && dyn_groups.count(in.narrow[0]) && !podReqs.has(in.narrow[0]->key) && in.narrow[0]->max_skew >= 0 && in.narrow[0]->max_skew < (1 << 24)) { in.dyn = 1; in.dg = in.narrow[0]; in.self = tg_selects(*in.dg, pod); }
+      else if (in.narrow.empty() && in.host.size() == 1 && in.host[0]->type != kAffinity) { in.dyn = 2; in.dg = in.host[0]; in.self = tg_selects(*in.dg, pod); }
+    }
+    return in;
+  }
+  // The model, exported (ko_class_model; tests/test_class_tables.py compares the device's ClsPlan / ClsBrief records with it): for every pod as submitted, after
+  // NewTopology and before the first placement.  JSON.  Groups are numbered topologies first, then inverse groups.  The evaluation class is interned from
+  // eval_signature over the distinct taints of the templates and the existing nodes (see there).
+  std::string class_model() {
+    const GS initial = initial_groups(), dyn_groups = model_dyn_groups();
+    std::map<G, int> gid; std::vector<G> gl;
+    for (auto& tc : topo.topologies) { gid[tc.get()] = (int)gl.size(); gl.push_back(tc.get()); }
+    for (auto& tc : topo.inverse) { gid[tc.get()] = (int)gl.size(); gl.push_back(tc.get()); }
+    std::vector<ksp::Taint> taints;
+    auto add_taints = [&](const std::vector<ksp::Taint>& ts) { for (auto& t : ts) { bool seen = false; for (auto& u : taints) if (u.key == t.key && u.value == t.value && u.effect == t.effect) seen = true; if (!seen) taints.push_back(t); } };
+    for (auto& t : templates) add_taints(t.taints);
+    for (auto& e : existing) add_taints(e->taints);
+    auto js = [](const std::string& x) { std::string r = "\""; for (char c : x) { if (c == '"' || c == '\\') r += '\\'; r += c; } return r + "\""; };
+    std::ostringstream o;
+    o << "{\"inverse_from\":" << topo.topologies.size() << ",\"taints\":" << taints.size() << ",\"groups\":[";
+    for (size_t i = 0; i < gl.size(); ++i) o << (i ? "," : "") << "{\"type\":" << (int)gl[i]->type << ",\"hostname\":" << (gl[i]->is_hostname ? 1 : 0) << ",\"initial\":" << (initial.count(gl[i]) ? 1 : 0)
+                                             << ",\"dyn\":" << (dyn_groups.count(gl[i]) ? 1 : 0) << ",\"max_skew\":" << gl[i]->max_skew << ",\"key\":" << js(STR(gl[i]->key)) << "}";
+    o << "],\"pods\":[";
+    std::map<std::string, int> evs;
+    auto ids = [&](const GS& s) { std::vector<int> v; for (G g : s) v.push_back(gid.at(g)); std::sort(v.begin(), v.end()); std::string r = "["; for (size_t i = 0; i < v.size(); ++i) r += (i ? "," : "") + std::to_string(v[i]); return r + "]"; };
+    auto idl = [&](const std::vector<TopologyGroup*>& l) { std::string r = "["; for (size_t i = 0; i < l.size(); ++i) r += (i ? "," : "") + std::to_string(gid.at(l[i])); return r + "]"; };
+    for (size_t i = 0; i < pods.size(); ++i) {
+      PodState& ps = pods[i]; const Info in = class_info(ps, initial, dyn_groups);
+      const int ev = evs.emplace(eval_signature(ps, &taints), (int)evs.size()).first->second;
+      o << (i ? "," : "") << "{\"ev\":" << ev << ",\"eligible\":" << (in.eligible ? 1 : 0) << ",\"dyn\":" << in.dyn << ",\"self\":" << (in.self ? 1 : 0) << ",\"max_skew\":" << (in.dg ? in.dg->max_skew : 0)
+        << ",\"dyn_group\":" << (in.dg ? gid.at(in.dg) : -1) << ",\"watermark\":" << (watermark_class(ps, false) ? 1 : 0) << ",\"requests\":{";
+      bool first = true; for (auto& kv : in.req) { o << (first ? "" : ",") << js(kv.first) << ":" << kv.second; first = false; }
+      o << "},\"narrow\":" << idl(in.narrow) << ",\"host\":" << idl(in.host) << ",\"tmask\":" << ids(in.tmask) << ",\"tfull\":" << ids(in.tfull) << ",\"rmask\":" << ids(in.rmask)
+        << ",\"rsure\":" << ids(in.rsure) << ",\"zmask\":" << ids(in.zmask) << "}";
+    }
+    o << "]}";
+    return o.str();
+  }
+  void solve_spec_v2(int W, long long* out, int flags = 0, int maxcls = 0) {
+    auto meets = [](const GS& a, const GS& b) { for (G g : a) if (b.count(g)) return true; return false; };
+    const bool no_rdyn = (flags & 4) != 0;
+    const GS initial = initial_groups();
+    const GS dyn_groups = model_dyn_groups();
     const Sym dyn_key = dyn_groups.empty() ? (Sym)-1 : (*dyn_groups.begin())->key;
     std::vector<int> q(pods.size()); for (size_t i = 0; i < pods.size(); ++i) q[i] = (int)i;
     std::vector<ResList> rq(pods.size()); for (size_t i = 0; i < pods.size(); ++i) rq[i] = requests_for_pods({&pods[i].spec});
@@ -1142,7 +1223,6 @@ struct Scheduler {
       if (relaxed) { lastLen.clear(); ps.stage++; st.relaxations++; topo.update(ps.spec); } else lastLen[pi] = queue.size();
       return true;
     };
-    struct Info { std::vector<TopologyGroup*> narrow, host; GS tmask, tfull, rmask, rsure, zmask; bool eligible = true; int dyn = 0; TopologyGroup* dg = nullptr; bool self = false; std::string ev; ResList req; };
     struct Cand { Node* n = nullptr; ExistingNode* e = nullptr; size_t cnt0 = 0, cnt = 0; bool moved = false, closed = false; int np = 0, last = -1; ResList extra; GS racc, rsure, unsure; std::map<G, int> hrec; bool pinned = false; DomKey zone; uint64_t key = 0; };
     while (!queue.empty()) {
       std::stable_sort(new_nodes.begin(), new_nodes.end(), [](const std::unique_ptr<Node>& a, const std::unique_ptr<Node>& b) { return a->pods.size() < b->pods.size(); });
@@ -1159,28 +1239,7 @@ struct Scheduler {
       size_t n = 0; std::vector<Info> I;
       { std::set<std::string> seen;
         while (n < (size_t)W && n < queue.size() && lastLen.find(queue[n]) == lastLen.end()) {
-          PodState& ps = pods[queue[n]]; ksp::Pod& pod = ps.spec; Info in; in.ev = eval_signature(ps); in.req = requests_for_pods({&pod});
-          for (auto& c : pod.containers) if (!c.ports.empty()) in.eligible = false;
-          if (pod.volume_error || !pod.volumes.empty()) in.eligible = false;
-          if (!topo.inert) {
-            Reqs podReqs = new_pod_requirements(pod);
-            for (auto& tc : topo.topologies) if (tc->owners.count(pod.uid)) { (tc->is_hostname ? in.host : in.narrow).push_back(tc.get()); }
-            for (auto& tc : topo.inverse) if (tg_selects(*tc, pod)) { (tc->is_hostname ? in.host : in.narrow).push_back(tc.get()); }
-            for (auto* g : in.narrow) { in.tmask.insert(g); in.tfull.insert(g); }
-            for (auto* g : in.host) {
-              in.tfull.insert(g); const bool self = tg_selects(*g, pod);
-              const bool own_counter_only = g->type == kAntiAffinity || (g->type == kSpread && initial.count(g));
-              if (!own_counter_only) in.tmask.insert(g);
-              if (g->type == kAntiAffinity || (g->type == kSpread && (int64_t)g->max_skew - (self ? 1 : 0) <= 0)) in.zmask.insert(g);
-            }
-            for (auto& tc : topo.topologies) if (tg_selects(*tc, pod)) {
-              in.rmask.insert(tc.get());
-              if (tc->is_hostname) { if (initial.count(tc.get()) && trivial_filter(*tc)) in.rsure.insert(tc.get()); if (!initial.count(tc.get())) in.eligible = false; }
-            }
-            for (auto& tc : topo.inverse) if (tc->owners.count(pod.uid)) { in.rmask.insert(tc.get()); if (tc->is_hostname) in.rsure.insert(tc.get()); }
-            if (in.narrow.size() == 1 && in.host.empty() && in.narrow[0]->type == kSpread && dyn_groups.count(in.narrow[0]) && !podReqs.has(in.narrow[0]->key) && in.narrow[0]->max_skew >= 0 && in.narrow[0]->max_skew < (1 << 24)) { in.dyn = 1; in.dg = in.narrow[0]; in.self = tg_selects(*in.dg, pod); }
-            else if (in.narrow.empty() && in.host.size() == 1 && in.host[0]->type != kAffinity) { in.dyn = 2; in.dg = in.host[0]; in.self = tg_selects(*in.dg, pod); }
-          }
+          Info in = class_info(pods[queue[n]], initial, dyn_groups);
           if (!in.eligible) break;
           if (maxcls > 0 && !seen.count(in.ev)) { if ((int)seen.size() == maxcls) break; seen.insert(in.ev); }
           I.push_back(std::move(in)); ++n;
@@ -1447,6 +1506,16 @@ int ko_solve(const char* ksp_text, size_t len, int flags, char** out_text) {
   } catch (const std::exception& e) { *out_text = strdup(e.what()); oracle::g_in = nullptr; return -1; }
 }
 void ko_free(char* p) { free(p); }
+// The class model (Scheduler::class_model): 0 and a malloc'd JSON text, or <0 and a malloc'd error message.
+int ko_class_model(const char* ksp_text, size_t len, char** out_text) {
+  oracle::Interner in; oracle::g_in = &in;
+  try {
+    ksp::Problem pr = ksp::Parser(ksp_text, len).parse();
+    auto s = oracle::build(pr, false);
+    std::string r = s->class_model();
+    *out_text = strdup(r.c_str()); oracle::g_in = nullptr; return 0;
+  } catch (const std::exception& e) { *out_text = strdup(e.what()); oracle::g_in = nullptr; return -1; }
+}
 // The restated sort.Slice on plain keys: perm_out[i] = index (into keys) of the element at sorted position i.
 void ko_gosort_order(const int* keys, int n, int* perm_out) {
   std::vector<int> perm(n); for (int i = 0; i < n; ++i) perm[i] = i;

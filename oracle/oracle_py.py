@@ -25,6 +25,7 @@ def lib():
         l.ko_free.argtypes = [ctypes.c_void_p]
         l.ko_solve_spec.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_void_p)]
         l.ko_solve_spec2.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_void_p)]
+        l.ko_class_model.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p)]
         l.ko_req_intersection.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_size_t]
         l.ko_req_has.argtypes = [ctypes.c_char_p, ctypes.c_char_p]
         l.ko_req_operator.argtypes = [ctypes.c_char_p]
@@ -80,6 +81,23 @@ def watermark_check(problem, mutate: bool = False, pre_topology_only: bool = Fal
         raise RuntimeError("oracle: " + text)
     return parse_result(text), {"violations": int(ctr[0]), "dry_runs": int(ctr[1]), "watermark_pods": int(ctr[2]), "with_anti_affinity": int(ctr[3]),
                                 "refusals_recorded": int(ctr[4]), "recorded_pairs_rechecked": int(ctr[5])}
+
+
+def class_model(problem):
+    """The oracle's model of the per-class records of ksolve.hip (ClsPlan / ClsBrief), for every pod as submitted -- after NewTopology, before the first placement
+    (oracle.cpp Scheduler::class_model: the functions solve_spec_v2 and solve_watermark_check run on).  A dict:
+      groups[g]: type (0 spread, 1 affinity, 2 anti-affinity), hostname, initial, dyn (in dyn_groups), max_skew, key; topologies first, inverse groups from `inverse_from`;
+      pods[i]:   ev (evaluation-class id: eval_signature over the tolerated taints, plus the volumes), eligible, dyn (0, 1, 2), self, max_skew and dyn_group of the dyn
+                 item, watermark, requests {name: milli-units}, narrow / host (items, in evaluation order), tmask / tfull / rmask / rsure / zmask (sorted group indices)."""
+    import json
+    data = problem.to_ksp().encode()
+    out = ctypes.c_void_p()
+    rc = lib().ko_class_model(data, len(data), ctypes.byref(out))
+    text = ctypes.string_at(out).decode()
+    lib().ko_free(out)
+    if rc != 0:
+        raise RuntimeError("oracle: " + text)
+    return json.loads(text)
 
 
 def solve(problem, inert_topology: bool = False, gosort: bool = False):

@@ -34,7 +34,7 @@ def test_host_library_exports_every_declared_symbol():
     hdr = open(os.path.join(ROOT, "include", "kshost.h")).read()
     names = set(re.findall(r"\b(ksh_[a-z_0-9]+)\s*\(", hdr))
     assert {"ksh_parse", "ksh_solve_from_pods", "ksh_open", "ksh_upload", "ksh_solve", "ksh_solve_batch", "ksh_open_whatifs", "ksh_price_filter",
-            "ksh_result_text", "ksh_result_summary", "ksh_grid", "ksh_debug_grid", "ksh_debug_pod_classes"} <= names
+            "ksh_result_text", "ksh_result_summary", "ksh_grid", "ksh_debug_grid", "ksh_debug_pod_classes", "ksh_debug_classes"} <= names
     _, kh = S.libs()
     for n in names:
         assert hasattr(kh, n), f"libkshost.so does not export {n}"
