@@ -454,7 +454,8 @@ int ksh_replacement_rows(void** handles, uint32_t n, const uint64_t* ids, const 
  * every 10 s): state.Cluster hears UpdateNode / DeleteNode / UpdatePod / DeletePod (pkg/controllers/state/cluster.go:151-200) and patches its nodes in place
  * (state/node.go:161-182 updateForPod / cleanupForPod; Available() = Allocatable - the requests of the pods bound, node.go:113); the next pass then flattens
  * everything again (helpers.go:42-99 -> provisioner.go:237-296).  Here the events patch the objects ksh_parse holds AND the snapshot's flattening follows them.
- * `ksd_text`:  KSD1 <n>  { NODE+ <KSP1 NODE record without its keyword>  |  NODE= <the same record>  |  NODE- <node name>  |  BIND <node name> POD <KSP1 pod record>  |  UNBIND <pod uid> }*  END
+ * `ksd_text`:  KSD1 <n>  { NODE+ <KSP1 NODE record without its keyword>  |  NODE= <the same record>  |  NODE- <node name>  |  BIND <node name> POD <KSP1 pod record>  |  UNBIND <pod uid>
+ *                         |  IT= <KSP1 IT record without its keyword> }*  END
  *   NODE+   a state node joins (slot = the next node index; slots are never reused, candidate sets keep naming nodes by slot)
  *   NODE-   a state node leaves; the pods bound to it are unbound with it
  *   BIND    a pod is bound to a node: it joins the snapshot's pods (index = the next one), the node's available resources shrink by RequestsForPods(pod),
@@ -467,6 +468,21 @@ int ksh_replacement_rows(void** handles, uint32_t n, const uint64_t* ids, const 
  *           held: labels, taints, available, capacity, daemonset requests, host ports, volume limits, volumes -- taken as given: they are state.Node's own
  *           outputs at the moment of the event, already net of the pods bound; later BIND / UNBIND patch from there.  The provisioner-name label may change
  *           (owned <-> unowned, another provisioner).  The record's in_state word is not read: the node is in state.
+ *   IT=     an instance type of the catalogue is replaced in place: what cloudProvider.GetInstanceTypes lists NOW (Provisioner.NewScheduler asks on every pass,
+ *           provisioner.go:237-296) -- an offering unavailable or back, a price moved, the zone / capacity-type requirement values that follow availability.  The
+ *           record's name must be the name of an instance type of the parsed object, or the event is refused with "IT=: no instance type named X".  The type
+ *           keeps its index: provisioners' instance-type lists, nodes' instance-type labels and every InstanceTypeOptions bit keep their meaning.  Requirements,
+ *           offerings, capacity and overhead of the record REPLACE what the slot held.  Types are neither added nor removed: one the provider no longer lists is
+ *           a record with no available offering.  A record the ingest doors would refuse -- a requirement with Gt / Lt ("IT=: instance type requirement with
+ *           Gt/Lt bounds"), one on kubernetes.io/hostname ("IT=: instance type requirement on hostname") -- ends the call with KS_ERR_UNSUPPORTED, nothing of
+ *           that event applied (the events before it stay, info[0] counts them).  Continued (info[3] = 1) when the record differs from the one before in its
+ *           offerings (availability, price, which pairs are listed) or in the values of its requirements, and the universes a run from scratch would build are
+ *           the same: every zone, capacity type and requirement value it names is in them, no value it no longer names was the last use (other types, the
+ *           provisioners, the batch and the nodes are asked), and the topology-domain universe NewScheduler builds from the types' requirement values is the
+ *           same set.  The columns / rows of the touched types in the it_* arrays are then encoded anew, the others taken over.  The full run (info[3] = 0,
+ *           same bytes) for anything else: a zone or value no universe has, the last use of one, a requirement key that comes or goes, a changed
+ *           node.kubernetes.io/instance-type requirement, and ANY change of capacity or overhead (resource names, and everything made from the allocatable).
+ *           A Solve over these objects (ksh_solve_from_batch) flattens its environment again after the event, as after every other.
  * The first call hands the snapshot's bindings over (`pod_node`, as the what-if calls take it); from then on the library holds them -- every call that takes a
  * `pod_node` accepts NULL for "the library's", ksh_snapshot_bindings reads them.  info[0] = events applied (an event that cannot be applied ends the call with
  * KS_ERR_INVALID; the ones before it stay), info[1] / info[2] = node / pod slots, info[3] = 1 when the snapshot's flattening was CONTINUED from the one before:
@@ -485,7 +501,8 @@ int ksh_env_apply(void* parsed_snapshot, const int32_t* pod_node /* first call: 
 /* ---- the same door without the text: the events as ONE stream of u32 words over ONE string table (conventions of ksh_env_block; grammar in
  * karpenter_core_amd/host/kspb.hpp, DeltaReader).  Per event a kind word, then its body: KSH_EVENT_NODE_ADD the state-node record of ksh_env_block, KSH_EVENT_NODE_REMOVE
  * the node's name, KSH_EVENT_BIND the node's name + the pod (word count, spec record of ksh_pod_block, uid, creationTimestamp as two words), KSH_EVENT_UNBIND the pod's uid,
- * KSH_EVENT_NODE_UPDATE (NODE=) the state-node record again, word for word what KSH_EVENT_NODE_ADD carries.
+ * KSH_EVENT_NODE_UPDATE (NODE=) the state-node record again, word for word what KSH_EVENT_NODE_ADD carries, KSH_EVENT_INSTANCE_TYPE_UPDATE (IT=) the
+ * instance_type record of ksh_env_block.
  * A cgo caller fills it with the writer it has for the other two doors; quantities are int64 milli-units, nothing is quoted or printed.  Everything after the decoding is
  * ksh_env_apply's: same patching, same info[0..3], same bindings held by the library, same error texts for an event that cannot be applied (the events before it stay,
  * info[0] counts them).  Text and binary calls may be mixed on one snapshot in any order.
@@ -500,6 +517,7 @@ int ksh_env_apply(void* parsed_snapshot, const int32_t* pod_node /* first call: 
 #define KSH_EVENT_BIND 3u
 #define KSH_EVENT_UNBIND 4u
 #define KSH_EVENT_NODE_UPDATE 5u
+#define KSH_EVENT_INSTANCE_TYPE_UPDATE 6u
 #define KSH_APPLY_TRACK_CLUSTER_PODS 1u
 typedef struct ksh_delta_block {
   uint32_t n_events, n_strings, n_words;

@@ -89,6 +89,7 @@ struct Parsed {
   std::shared_ptr<const void> cand_nodes;     // what candidate selection reads of them (CandSnapshot below), likewise
   // ksh_env_apply (round 6): once events were applied the library holds the bindings itself -- bind[i] = the node pod i is bound to, -1 for a pod that was unbound
   // (it stays in place: nothing that points into the problem may move) -- and the names of what is alive
+  std::unordered_map<std::string, uint32_t> type_index;      // instance-type name -> index, made by the first IT= event (types are never added, removed or renamed)
   bool bind_set = false, had_cluster_pods = false; std::vector<int32_t> bind; std::unordered_map<std::string, uint32_t> live_node, live_pod; uint64_t tombstones = 0; uint32_t applied = 0;
 };
 // the bindings a what-if call means: the caller's array, or -- after ksh_env_apply -- the library's own
@@ -306,7 +307,7 @@ static int resident_base(const ksh::Encoded* base, int device, std::shared_ptr<v
 extern "C" {
 // ---- the snapshot kept current by events instead of re-ingested (state.Cluster's UpdateNode / DeleteNode / UpdatePod / DeletePod, cluster.go) ----
 // The problem object is patched in place -- new nodes and pods are appended (the vectors were parsed with room: nothing moves), a node that is updated is replaced
-// in its slot (NODE=), what leaves stays as a tombstone
+// in its slot (NODE=), an instance type likewise (IT=), what leaves stays as a tombstone
 // (a node out of state, a pod bound nowhere) -- and the snapshot's flattening, if there is one, is continued from the one before (ksh::make_snapshot_base `before`).
 // Not to be called while another thread uses handles opened over this snapshot; handles opened BEFORE the call keep solving what they were opened for.
 // What both doors do once the events are objects (`ev` is consumed): the text door (ksh_env_apply) and the binary one (ksh_env_apply_block) differ in the decoding alone.
@@ -334,8 +335,9 @@ static int apply_events(Parsed* P, const int32_t* pod_node, std::vector<ksp::Del
       P->live_pod.erase(p.uid); P->bind[i] = -1;
       p.uid = std::string("\1unbound-") + std::to_string(++P->tombstones);      // (uids stay unique: the same pod may be bound again)
     };
-    uint32_t done = 0; std::string why;
+    uint32_t done = 0; std::string why; int why_rc = KS_ERR_INVALID;
     std::vector<ksh::ReplacedNode> replaced;      // NODE=: the nodes as the flattening before saw them (the first replacement of a slot in this call)
+    std::vector<ksh::ReplacedType> replaced_types;      // IT=: the instance types likewise
     for (auto& e : ev) {
       if (e.kind == ksp::DeltaEvent::NodeAdd) {
         if (P->live_node.count(e.node.name)) { why = "NODE+: a state node named " + e.node.name + " exists"; break; }
@@ -367,6 +369,22 @@ static int apply_events(Parsed* P, const int32_t* pod_node, std::vector<ksp::Del
         bool first = true; for (auto& r : replaced) if (r.slot == nd) first = false;
         if (first) replaced.push_back(ksh::ReplacedNode{nd, std::move(n)});
         n = std::move(e.node);
+      } else if (e.kind == ksp::DeltaEvent::TypeUpdate) {
+        // the catalogue as cloudProvider.GetInstanceTypes lists it NOW (provisioner.go:237-296 asks on every pass): the record replaces the type in its slot -- the
+        // index stays, and with it the provisioners' lists, the nodes' instance-type labels and every bit of an InstanceTypeOptions row
+        if (P->type_index.empty()) for (size_t t = 0; t < pr.instance_types.size(); ++t) P->type_index.emplace(pr.instance_types[t].name, (uint32_t)t);
+        auto it = P->type_index.find(e.type.name); if (it == P->type_index.end()) { why = "IT=: no instance type named " + e.type.name; break; }
+        // what the ingest doors refuse of an instance type (encode.cpp collect_passive / encode_instance_types) is refused here, before anything is touched
+        for (auto& x : e.type.requirements) {
+          if (x.op == ksp::Op::Gt || x.op == ksp::Op::Lt) { why = "IT=: instance type requirement with Gt/Lt bounds"; why_rc = KS_ERR_UNSUPPORTED; break; }
+          if (ksp::normalize_key(x.key) == ksp::kHostname) { why = "IT=: instance type requirement on hostname"; why_rc = KS_ERR_UNSUPPORTED; break; }
+        }
+        if (!why.empty()) break;
+        const uint32_t t = it->second; ksp::InstanceType& ty = pr.instance_types[t];
+        e.type.stamp = ty.stamp + 1;
+        bool first = true; for (auto& r : replaced_types) if (r.slot == t) first = false;
+        if (first) replaced_types.push_back(ksh::ReplacedType{t, std::move(ty)});
+        ty = std::move(e.type);
       } else {
         auto it = P->live_pod.find(e.name); if (it == P->live_pod.end()) { why = "UNBIND: no bound pod with uid " + e.name; break; }
         unbind(it->second);
@@ -378,12 +396,12 @@ static int apply_events(Parsed* P, const int32_t* pod_node, std::vector<ksp::Del
     bool continued = false;
     if (P->sb) {
       std::shared_ptr<const ksh::SnapshotBase> before = P->sb;
-      try { P->sb = ksh::make_snapshot_base(P->pr, P->bind.data(), P->sb_flags, before.get(), &replaced); P->sb_pod_node = P->bind; continued = ksh::snapshot_continued(*P->sb); }
+      try { P->sb = ksh::make_snapshot_base(P->pr, P->bind.data(), P->sb_flags, before.get(), &replaced, &replaced_types); P->sb_pod_node = P->bind; continued = ksh::snapshot_continued(*P->sb); }
       catch (...) { P->sb.reset(); P->sb_pod_node.clear(); throw; }
       ksh::dispose_later(std::move(before));      // (the flattening before: torn down off this thread, once the handles that still use it are closed)
     }
     if (info) { info[0] = done; info[1] = (uint32_t)pr.nodes.size(); info[2] = (uint32_t)pr.pods.size(); info[3] = continued ? 1u : 0u; }
-    if (done != ev.size()) return set_err(KS_ERR_INVALID, "event " + std::to_string(done) + ": " + why + " (the events before it were applied)");
+    if (done != ev.size()) return set_err(why_rc, "event " + std::to_string(done) + ": " + why + " (the events before it were applied)");
     return KS_OK;
   }
 }

@@ -309,6 +309,12 @@ struct Builder {
   // and resource names the universes hold whatever the nodes carry -- from the batch, the provisioners, the daemonsets and the catalogue).
   std::vector<uint32_t> node_stamp_built; const std::vector<ReplacedNode>* replaced = nullptr;
   std::shared_ptr<const std::vector<std::set<std::string>>> fixed_key_vals; size_t fixed_res_n = 0;
+  // An IT= event replaces an instance type in place and bumps the stamp of its slot (ksp::InstanceType::stamp); it_stamp_built: the stamps this flattening saw.
+  // can_continue() decides from the replaced records (`replaced_types`, as `prev` saw them) whether the universes, the topology-domain universe and the types'
+  // resources stay what they are; if so it leaves the types to encode anew (touched_types), their requirements beside the others' (next_it_requirements, a COPY of the vector:
+  // `prev` and the handles opened over it keep reading theirs) and, where a value changed hands between the catalogue and the nodes, the new fixed_key_vals.
+  std::vector<uint32_t> it_stamp_built, touched_types; const std::vector<ReplacedType>* replaced_types = nullptr;
+  std::shared_ptr<std::vector<std::shared_ptr<const Requirements>>> next_it_requirements; std::shared_ptr<const std::vector<std::set<std::string>>> next_fixed_key_vals;
 
   // KSH_ACTIVE_RESOURCES (a library flag: the flat problem never carries it): only the resource names something requests or limits are interned -- what a pod, a
   // daemonset, a provisioner's limits or a node's daemonset_requests names.  A name that only an instance type's capacity / overhead or a node's available / capacity
@@ -377,7 +383,7 @@ struct Builder {
   void collect_universes() { collect_active(); collect_passive(); }
   // May this run continue `prev`?  After collect_active: the same problem object, what the batch / provisioners / daemonsets name unchanged (keys with their ids,
   // named values, bounds, topology keys, resources), and nothing a new node carries is new to a universe.
-  bool can_continue() const {
+  bool can_continue() {
     if (!prev || &prev->pr != &pr || prev->flags != flags || prev->active_res != active_res || prev->act_sig.empty() || prev->base || prev->lite) return false;
     if (key_id != prev->act_key_id || res_id != prev->act_res_id || active_signature() != prev->act_sig) return false;
     if (prev->n_nodes_built > pr.nodes.size() || prev->T != pr.instance_types.size()) return false;
@@ -421,12 +427,90 @@ struct Builder {
       };
       { const auto a = node_only(*old), b = node_only(n); if (a.size() != b.size()) return false; for (size_t x = 0; x < a.size(); ++x) if (*a[x] != *b[x]) return false; }
     }
+    return types_continue();
+  }
+  // What an instance type contributes to the universes (collect_passive): the values its In / NotIn requirements on referenced keys name, and the zone and the
+  // capacity type of every offering it lists, available or not.
+  template <class F> void type_universe_values(const ksp::InstanceType& it, F&& f) const {
+    for (auto& e : it.requirements) {
+      if (e.op != Op::In && e.op != Op::NotIn) continue;
+      const std::string k = ksp::normalize_key(e.key); if (special_key(k)) continue;
+      auto id = key_id.find(k); if (id == key_id.end()) continue;
+      for (auto& v : e.values) f(id->second, v);
+    }
+    const int kz = key_id.at(ksp::kZone), kc = key_id.at(ksp::kCapacityType);
+    for (auto& o : it.offerings) { f(kz, o.zone); f(kc, o.capacity_type); }
+  }
+  // The types an IT= replaced since `prev` (the second half of can_continue).  Continued: offerings (availability, price, which pairs are listed) and the values of
+  // requirements, while every value the record names is in the universes being adopted, no value it no longer names was the last use (the record as it WAS is in
+  // those universes: decided against the batch / provisioners -- key_named --, the other types and the nodes), and the topology-domain universe encode_templates
+  // builds from the listed types' requirement values is the same set.  The full run for: a changed capacity or overhead (resource names, and everything made from
+  // it_alloc), a requirement key that comes or goes, a changed node.kubernetes.io/instance-type requirement (the lattice's its_types).
+  bool types_continue() {
+    touched_types.clear(); next_it_requirements.reset(); next_fixed_key_vals.reset();
+    const size_t TT = pr.instance_types.size(); if (prev->it_stamp_built.size() != TT) return false;
+    for (size_t t = 0; t < TT; ++t) if (pr.instance_types[t].stamp != prev->it_stamp_built[t]) touched_types.push_back((uint32_t)t);
+    if (touched_types.empty()) return true;
+    if (!replaced_types || !prev->fixed_key_vals) return false;
+    std::vector<const ksp::InstanceType*> was_of;
+    auto reqs = std::make_shared<std::vector<std::shared_ptr<const Requirements>>>(*prev->it_requirements_p);      // (2 000 pointers: the sets themselves are shared)
+    for (uint32_t t : touched_types) {
+      const ksp::InstanceType& now = pr.instance_types[t]; const ksp::InstanceType* old = nullptr;
+      for (auto& r : *replaced_types) if (r.slot == t && r.before.stamp == prev->it_stamp_built[t]) { old = &r.before; break; }
+      if (!old || now.capacity != old->capacity || now.overhead != old->overhead) return false;
+      for (auto& e : now.requirements) if (e.op == Op::Gt || e.op == Op::Lt || ksp::normalize_key(e.key) == ksp::kHostname) return false;      // (the full run refuses it as the ingest does)
+      Requirements rs = Requirements::FromExprs(now.requirements); const Requirements& was = *(*prev->it_requirements_p)[t];
+      if (rs.m.size() != was.m.size()) return false;
+      for (auto a = rs.m.cbegin(), b = was.m.cbegin(); a != rs.m.cend(); ++a, ++b) {
+        if (a->first != b->first) return false;
+        if (a->first == ksp::kInstanceType && a->second.identity() != b->second.identity()) return false;
+      }
+      (*reqs)[t] = std::make_shared<const Requirements>(std::move(rs)); was_of.push_back(old);
+    }
+    std::vector<const std::string*> key_name(key_vals.size(), nullptr); for (auto& kv : key_id) key_name[kv.second] = &kv.first;
+    std::vector<uint8_t> listed(TT, 0); for (auto& p : pr.provisioners) for (int idx : p.instance_types) if (idx >= 0 && (size_t)idx < TT) listed[idx] = 1;
+    std::shared_ptr<std::vector<std::set<std::string>>> fixed;
+    auto fixed_w = [&]() -> std::vector<std::set<std::string>>& { if (!fixed) fixed = std::make_shared<std::vector<std::set<std::string>>>(*prev->fixed_key_vals); return *fixed; };
+    using KV = std::pair<int, std::string>;
+    for (size_t x = 0; x < touched_types.size(); ++x) {
+      const uint32_t t = touched_types[x]; const ksp::InstanceType& now = pr.instance_types[t];
+      std::set<KV> was_u, now_u;
+      type_universe_values(*was_of[x], [&](int k, const std::string& v) { was_u.emplace(k, v); });
+      type_universe_values(now, [&](int k, const std::string& v) { now_u.emplace(k, v); });
+      for (auto& kv : now_u) { if (was_u.count(kv)) continue;
+        if (!prev->key_vals[kv.first].count(kv.second)) return false;      // a value no universe has
+        if (!prev->fixed_key_vals->at(kv.first).count(kv.second)) fixed_w()[kv.first].insert(kv.second);      // (until now only nodes carried it)
+      }
+      for (auto& kv : was_u) { if (now_u.count(kv) || key_named[kv.first].count(kv.second)) continue;
+        bool held = false;
+        for (size_t o = 0; o < TT && !held; ++o) type_universe_values(pr.instance_types[o], [&](int k, const std::string& v) { if (k == kv.first && v == kv.second) held = true; });
+        if (held) continue;
+        fixed_w()[kv.first].erase(kv.second);      // the catalogue no longer holds it: in the universe only while a node carries it
+        const std::string& kn = *key_name[kv.first]; bool used = false;
+        for (auto& o : pr.nodes) { for (auto& ol : o.labels) if (ol.second == kv.second && (ol.first == kn || ksp::normalize_key(ol.first) == kn)) { used = true; break; } if (used) break; }
+        if (!used) return false;      // the last use
+      }
+      if (!listed[t]) continue;
+      // the topology-domain universe (encode_templates; provisioner.go:266-271): the values of every requirement of every listed type, whatever its operator
+      const Requirements& rs = *(*reqs)[t]; const Requirements& was = *(*prev->it_requirements_p)[t];
+      for (auto a = rs.m.cbegin(), b = was.m.cbegin(); a != rs.m.cend(); ++a, ++b) {
+        auto dom = prev->domains.find(a->first);
+        for (auto& v : a->second.values) if (!b->second.values.count(v) && (dom == prev->domains.end() || !dom->second.count(v))) return false;
+        for (auto& v : b->second.values) { if (a->second.values.count(v)) continue;
+          bool held = false;
+          for (size_t o = 0; o < TT && !held; ++o) if (listed[o]) { auto f = (*reqs)[o]->m.find(a->first); held = f != (*reqs)[o]->m.end() && f->second.values.count(v); }
+          for (auto& p : pr.provisioners) { if (held) break; const Requirements preq = Requirements::FromExprs(p.requirements); auto f = preq.m.find(a->first); held = f != preq.m.end() && f->second.Operator() == Op::In && f->second.values.count(v); }
+          if (!held) return false;
+        }
+      }
+    }
+    next_it_requirements = std::move(reqs); next_fixed_key_vals = std::move(fixed);
     return true;
   }
   void collect_passive() {
     if (warm) {      // the catalogue's and the old nodes' contributions are in the previous universes, the new nodes add nothing (can_continue): adopt them and the tables made from them
       const Encoded& B = prev->E;
-      key_vals = prev->key_vals; res_id = prev->res_id; K = prev->K; R = prev->R; T = prev->T; TW = prev->TW; fixed_key_vals = prev->fixed_key_vals; fixed_res_n = prev->fixed_res_n;
+      key_vals = prev->key_vals; res_id = prev->res_id; K = prev->K; R = prev->R; T = prev->T; TW = prev->TW; fixed_key_vals = next_fixed_key_vals ? next_fixed_key_vals : prev->fixed_key_vals; fixed_res_n = prev->fixed_res_n;
       E.key_names = B.key_names; E.key_values = B.key_values; E.key_nvalues = B.key_nvalues; E.value_int = B.value_int; E.key_members = B.key_members; E.key_class = B.key_class; E.key_ints = B.key_ints; E.res_names = B.res_names;
       return;
     }
@@ -570,15 +654,49 @@ struct Builder {
   }
 
   // ---------- instance types ----------
-  std::shared_ptr<std::vector<Requirements>> it_requirements_p = std::make_shared<std::vector<Requirements>>();      // (shared with the flattening that continues this one, `prev`)
+  using TypeReqs = std::vector<std::shared_ptr<const Requirements>>;      // a type's requirement set is made once and shared by every flattening that sees the same record
+  std::shared_ptr<TypeReqs> it_requirements_p = std::make_shared<TypeReqs>();      // (shared with the flattening that continues this one, `prev`)
+  // One type's column of it_present / it_complement / it_mask / it_alloc / it_cap and its row of it_offer / it_price / it_price_lo (a type only writes its own)
+  void encode_instance_type(uint32_t t, const Requirements& rs, int kz, int kc, uint32_t nct, uint32_t NP) {
+    const auto& it = pr.instance_types[t];
+    for (auto& kv : rs.m) {
+      if (kv.first == ksp::kInstanceType) continue;
+      if (kv.first == ksp::kHostname) throw Unsupported("instance type requirement on hostname");
+      auto kf = key_id.find(kv.first); if (kf == key_id.end()) continue;      // a key nothing else references (collect_universes)
+      int k = kf->second;
+      E.it_present[t] |= 1u << k; if (kv.second.complement) E.it_complement[t] |= 1u << k;
+      uint64_t m = 0; for (auto& v : kv.second.values) m |= 1ull << value_id(k, v);
+      E.it_mask[(size_t)k * T + t] = m;
+    }
+    for (auto& o : it.offerings) if (o.available) {
+      const uint32_t pair = value_id(kz, o.zone) * nct + value_id(kc, o.capacity_type);
+      E.it_offer[t] |= 1ull << pair;
+      double& pp = E.it_price[(size_t)t * NP + pair]; if (o.price > pp) pp = o.price;     // worstLaunchPrice takes the maximum (helpers.go:303,312)
+      double& pl = E.it_price_lo[(size_t)t * NP + pair]; if (o.price < pl) pl = o.price;  // Offerings.Cheapest the minimum (types.go:141)
+    }
+    ksp::ResList alloc = Subtract(it.capacity, it.overhead);   // Allocatable(), types.go:87-89
+    for (auto& kv : alloc) { auto f = res_id.find(kv.first); if (f != res_id.end()) E.it_alloc[(size_t)f->second * T + t] = kv.second; }      // (every name is in the universe unless it is inert: KSH_ACTIVE_RESOURCES)
+    for (auto& kv : it.capacity) { auto f = res_id.find(kv.first); if (f != res_id.end()) E.it_cap[(size_t)f->second * T + t] = kv.second; }
+  }
   void encode_instance_types() {
     if (warm) {      // same catalogue object, same universes: the arrays are the previous flattening's
       const Encoded& B = prev->E;
       E.it_present = B.it_present; E.it_complement = B.it_complement; E.it_mask = B.it_mask; E.it_offer = B.it_offer; E.it_alloc = B.it_alloc; E.it_cap = B.it_cap; E.it_price = B.it_price; E.it_price_lo = B.it_price_lo;
       it_requirements_p = prev->it_requirements_p;
+      if (touched_types.empty()) return;
+      // ... but for the types an IT= replaced (types_continue): their columns and rows are blanked and encoded anew, their requirements replaced in a copy
+      it_requirements_p = next_it_requirements;
+      const int kz = key_id.at(ksp::kZone), kc = key_id.at(ksp::kCapacityType); const uint32_t nct = E.key_nvalues[kc], NP = (uint32_t)E.key_nvalues[kz] * nct;
+      for (uint32_t t : touched_types) {
+        E.it_present[t] = 0; E.it_complement[t] = 0; E.it_offer[t] = 0;
+        for (uint32_t k = 0; k < K; ++k) E.it_mask[(size_t)k * T + t] = 0;
+        for (uint32_t r = 0; r < R; ++r) { E.it_alloc[(size_t)r * T + t] = 0; E.it_cap[(size_t)r * T + t] = 0; }
+        for (uint32_t q = 0; q < NP; ++q) { E.it_price[(size_t)t * NP + q] = -1.0; E.it_price_lo[(size_t)t * NP + q] = 1.7976931348623157e308; }
+        encode_instance_type(t, *(*it_requirements_p)[t], kz, kc, nct, NP);
+      }
       return;
     }
-    std::vector<Requirements>& it_requirements = *it_requirements_p;
+    TypeReqs& it_requirements = *it_requirements_p;
     E.it_present.assign(T, 0); E.it_complement.assign(T, 0); E.it_mask.assign((size_t)K * T, 0); E.it_offer.assign(T, 0);
     E.it_alloc.assign((size_t)R * T, 0); E.it_cap.assign((size_t)R * T, 0);
     const int kz = key_id.at(ksp::kZone), kc = key_id.at(ksp::kCapacityType);
@@ -587,26 +705,8 @@ struct Builder {
     const uint32_t NP = (uint32_t)E.key_nvalues[kz] * nct; E.it_price.assign((size_t)T * NP, -1.0); E.it_price_lo.assign((size_t)T * NP, 1.7976931348623157e308);
     it_requirements.resize(T);
     parallel_chunks(T, [&](size_t tb_, size_t te_, uint32_t) { for (uint32_t t = (uint32_t)tb_; t < (uint32_t)te_; ++t) {      // (a type only writes its own column / row)
-      const auto& it = pr.instance_types[t];
-      Requirements rs = Requirements::FromExprs(it.requirements); it_requirements[t] = rs;
-      for (auto& kv : rs.m) {
-        if (kv.first == ksp::kInstanceType) continue;
-        if (kv.first == ksp::kHostname) throw Unsupported("instance type requirement on hostname");
-        auto kf = key_id.find(kv.first); if (kf == key_id.end()) continue;      // a key nothing else references (collect_universes)
-        int k = kf->second;
-        E.it_present[t] |= 1u << k; if (kv.second.complement) E.it_complement[t] |= 1u << k;
-        uint64_t m = 0; for (auto& v : kv.second.values) m |= 1ull << value_id(k, v);
-        E.it_mask[(size_t)k * T + t] = m;
-      }
-      for (auto& o : it.offerings) if (o.available) {
-        const uint32_t pair = value_id(kz, o.zone) * nct + value_id(kc, o.capacity_type);
-        E.it_offer[t] |= 1ull << pair;
-        double& pp = E.it_price[(size_t)t * NP + pair]; if (o.price > pp) pp = o.price;     // worstLaunchPrice takes the maximum (helpers.go:303,312)
-        double& pl = E.it_price_lo[(size_t)t * NP + pair]; if (o.price < pl) pl = o.price;  // Offerings.Cheapest the minimum (types.go:141)
-      }
-      ksp::ResList alloc = Subtract(it.capacity, it.overhead);   // Allocatable(), types.go:87-89
-      for (auto& kv : alloc) { auto f = res_id.find(kv.first); if (f != res_id.end()) E.it_alloc[(size_t)f->second * T + t] = kv.second; }      // (every name is in the universe unless it is inert: KSH_ACTIVE_RESOURCES)
-      for (auto& kv : it.capacity) { auto f = res_id.find(kv.first); if (f != res_id.end()) E.it_cap[(size_t)f->second * T + t] = kv.second; }
+      it_requirements[t] = std::make_shared<const Requirements>(Requirements::FromExprs(pr.instance_types[t].requirements));
+      encode_instance_type(t, *it_requirements[t], kz, kc, nct, NP);
     } }, 128);
   }
 
@@ -616,7 +716,7 @@ struct Builder {
     for (auto& p : pr.provisioners) E.templates.push_back(&p);
     std::stable_sort(E.templates.begin(), E.templates.end(), [](const ksp::Provisioner* a, const ksp::Provisioner* b) { return a->weight > b->weight; });   // OrderByWeight
     if (E.templates.empty()) throw ksp::Error("no provisioners found");
-    const uint32_t M = (uint32_t)E.templates.size(); const std::vector<Requirements>& it_requirements = *it_requirements_p;
+    const uint32_t M = (uint32_t)E.templates.size(); const TypeReqs& it_requirements = *it_requirements_p;
     if (warm) domains = prev->domains;      // (only this function writes it, from the provisioners and the catalogue)
     E.tmpl_types.assign((size_t)M * TW, 0);
     for (uint32_t m = 0; m < M; ++m) {
@@ -632,7 +732,7 @@ struct Builder {
       // hashed view of the set's own strings before the ordered set is asked)
       if (!warm) { struct Seen { const std::string* key; std::set<std::string>* dom; std::unordered_set<std::string_view> vals; };
         std::vector<Seen> seen;
-        for (int idx : p.instance_types) for (auto& kv : it_requirements[idx].m) {
+        for (int idx : p.instance_types) for (auto& kv : it_requirements[idx]->m) {
           Seen* sn = nullptr; for (auto& c : seen) if (*c.key == kv.first) { sn = &c; break; }
           if (!sn) { seen.push_back(Seen{&kv.first, &domains[kv.first], {}}); sn = &seen.back(); for (auto& have : *sn->dom) sn->vals.insert(std::string_view(have)); }
           for (auto& v : kv.second.values) if (!sn->vals.count(std::string_view(v))) { auto ins = sn->dom->insert(v); sn->vals.insert(std::string_view(*ins.first)); }
@@ -1305,7 +1405,7 @@ struct Builder {
       E.shared_lattice = true; E.prob.S = base->E.prob.S; E.prob.SC = base->E.prob.SC;
       return;
     }
-    const std::vector<Requirements>& it_requirements = base ? *base->it_requirements_p : *this->it_requirements_p;
+    const TypeReqs& it_requirements = base ? *base->it_requirements_p : *this->it_requirements_p;
     // Node states are closed under intersection with every pod-side requirement (a node only ever narrows its
     // instance-type requirement by a class's, node.go:79 / existingnode.go:102); it_state_of appends while we iterate.
     if (it_reqs.empty()) it_reqs.push_back(Requirement());   // state 0 placeholder ("absent")
@@ -1335,8 +1435,8 @@ struct Builder {
     // `instance-type In [name]` are resolved through a name index (|values| work per state, not T).
     std::map<std::string, std::vector<uint32_t>> by_name; std::vector<uint32_t> general; std::vector<uint64_t> simple(TW, 0), unconstrained(TW, 0);
     for (uint32_t t = 0; t < T; ++t) {
-      auto it = it_requirements[t].m.find(ksp::kInstanceType);
-      if (it == it_requirements[t].m.end()) { unconstrained[t / 64] |= 1ull << (t % 64); continue; }
+      auto it = it_requirements[t]->m.find(ksp::kInstanceType);
+      if (it == it_requirements[t]->m.end()) { unconstrained[t / 64] |= 1ull << (t % 64); continue; }
       const Requirement& a = it->second;
       if (!a.complement && a.values.size() == 1 && !a.greaterThan && !a.lessThan) { by_name[*a.values.begin()].push_back(t); simple[t / 64] |= 1ull << (t % 64); }
       else general.push_back(t);
@@ -1351,7 +1451,7 @@ struct Builder {
         else for (auto& v : q.values) { auto f = by_name.find(v); if (f != by_name.end()) for (uint32_t t : f->second) row[t / 64] |= 1ull << (t % 64); }
       } else for (auto& kv : by_name) if (q.Has(kv.first)) for (uint32_t t : kv.second) row[t / 64] |= 1ull << (t % 64);
       for (uint32_t t : general) {
-        const Requirement& a = it_requirements[t].m.find(ksp::kInstanceType)->second; Requirement x = a.Intersection(q);
+        const Requirement& a = it_requirements[t]->m.find(ksp::kInstanceType)->second; Requirement x = a.Intersection(q);
         if (!(x.Len() == 0 && !(q.IsNotInOrDoesNotExist() && a.IsNotInOrDoesNotExist()))) row[t / 64] |= 1ull << (t % 64);
       }
     }
@@ -1399,7 +1499,8 @@ struct Builder {
     if (!specs_done) { dedupe_specs(); lap("dedupe_specs"); }
     if (!active_done) collect_active();
     if (keep_warm_state) { act_sig = active_signature(); act_key_id = key_id; act_res_id = res_id; n_nodes_built = pr.nodes.size(); n_pods_built = podp.size();
-      node_stamp_built.resize(pr.nodes.size()); for (size_t i = 0; i < pr.nodes.size(); ++i) node_stamp_built[i] = pr.nodes[i].stamp; }
+      node_stamp_built.resize(pr.nodes.size()); for (size_t i = 0; i < pr.nodes.size(); ++i) node_stamp_built[i] = pr.nodes[i].stamp;
+      it_stamp_built.resize(pr.instance_types.size()); for (size_t t = 0; t < pr.instance_types.size(); ++t) it_stamp_built[t] = pr.instance_types[t].stamp; }
     warm = can_continue();
     collect_passive(); lap(warm ? "universes (continued)" : "collect_universes");
     encode_instance_types(); lap("encode_instance_types");
@@ -1670,7 +1771,8 @@ static std::string build_topo_tables(SnapshotBase& sb, const int32_t* pod_node) 
   sb.topo.extra_tot = sb.t_extra_tot.data(); sb.topo.grph_base = sb.t_grph_base.data(); sb.has_topo = true;
   return "";
 }
-std::shared_ptr<const SnapshotBase> make_snapshot_base(std::shared_ptr<const ksp::Problem> snapshot, const int32_t* pod_node, uint32_t flags, const SnapshotBase* before, const std::vector<ReplacedNode>* replaced) {
+std::shared_ptr<const SnapshotBase> make_snapshot_base(std::shared_ptr<const ksp::Problem> snapshot, const int32_t* pod_node, uint32_t flags, const SnapshotBase* before, const std::vector<ReplacedNode>* replaced,
+                                                       const std::vector<ReplacedType>* replaced_types) {
   auto sb = std::make_shared<SnapshotBase>(); sb->snapshot = snapshot;
   sb->volumes = (flags & KSH_DERIVE_VOLUMES) != 0; flags &= ~KSH_DERIVE_VOLUMES;      // (a library flag: the flat problem never carries it)
   sb->by_node.resize(snapshot->nodes.size());
@@ -1678,10 +1780,10 @@ std::shared_ptr<const SnapshotBase> make_snapshot_base(std::shared_ptr<const ksp
   for (size_t i = 0; i < snapshot->pods.size(); ++i) { if (pod_node[i] < 0) continue; if ((size_t)pod_node[i] >= snapshot->nodes.size()) throw ksp::Error("pod_node out of range"); sb->by_node[pod_node[i]].push_back((uint32_t)i); }
   sb->enc = std::make_shared<Encoded>(); sb->enc->src = snapshot;
   sb->builder = std::make_unique<Builder>(*sb->enc, flags); sb->builder->keep_warm_state = true;
-  if (before && before->snapshot.get() == snapshot.get() && before->volumes == sb->volumes && !getenv("KSH_NO_WARM_SNAPSHOT")) { sb->builder->prev = before->builder.get(); sb->builder->replaced = replaced; }
+  if (before && before->snapshot.get() == snapshot.get() && before->volumes == sb->volumes && !getenv("KSH_NO_WARM_SNAPSHOT")) { sb->builder->prev = before->builder.get(); sb->builder->replaced = replaced; sb->builder->replaced_types = replaced_types; }
   if (sb->volumes) sb->builder->solo_pod_node = pod_node;
   sb->builder->run(); sb->continued = sb->builder->warm;
-  sb->builder->prev = nullptr; sb->builder->replaced = nullptr; sb->builder->solo_pod_node = nullptr;      // (this flattening now stands alone: `before` and the caller's bindings may go)
+  sb->builder->prev = nullptr; sb->builder->replaced = nullptr; sb->builder->replaced_types = nullptr; sb->builder->solo_pod_node = nullptr;      // (this flattening now stands alone: `before` and the caller's bindings may go)
   {   // what deriving what-ifs on the device needs (delta_inputs)
     const Builder& b = *sb->builder; const Encoded& E = *sb->enc; const uint32_t R = b.R, M = (uint32_t)E.templates.size(); const size_t NN = snapshot->nodes.size();
     sb->node_row.assign(b.base_existing_of.begin(), b.base_existing_of.end()); sb->node_row.resize(NN, -1);

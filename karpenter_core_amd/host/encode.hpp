@@ -105,8 +105,11 @@ struct SnapshotBase;
 // A node a NODE= event replaced in place carries a higher change stamp (ksp::StateNode::stamp) than `before` saw: `replaced` lists such slots with the node as it was
 // (its stamp the one `before` saw); the row of the slot is rebuilt.  A slot whose stamp moved and that `replaced` does not list makes the flattening start over.
 struct ReplacedNode { uint32_t slot; ksp::StateNode before; };
+// The same for an instance type an IT= event replaced (ksp::InstanceType::stamp; `replaced_types`): the type's column / row of the catalogue's arrays is encoded anew
+// and the others are taken over, while the record changes nothing of the universes, of the topology-domain universe or of what the type's resources are.
+struct ReplacedType { uint32_t slot; ksp::InstanceType before; };
 std::shared_ptr<const SnapshotBase> make_snapshot_base(std::shared_ptr<const ksp::Problem> snapshot, const int32_t* pod_node, uint32_t flags, const SnapshotBase* before = nullptr,
-                                                       const std::vector<ReplacedNode>* replaced = nullptr);
+                                                       const std::vector<ReplacedNode>* replaced = nullptr, const std::vector<ReplacedType>* replaced_types = nullptr);
 void dispose_later(std::shared_ptr<const void> p);      // destroyed on the library's teardown thread, not on the caller's (a snapshot's flattening: a millisecond of free())
 bool snapshot_continued(const SnapshotBase& sb);      // did the flattening take the short road
 uint64_t snapshot_fingerprint(const SnapshotBase& sb);      // FNV-1a over the flat problem and the per-node tables behind the device derivation (tests: short road == full run)

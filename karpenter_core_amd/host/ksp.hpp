@@ -98,6 +98,7 @@ struct InstanceType {
   std::vector<Expr> requirements;
   std::vector<Offering> offerings;
   ResList capacity, overhead;
+  uint32_t stamp = 0;                                            // change stamp of the type's slot: an IT= event (ksh_env_apply) bumps it; no record carries it
 };
 struct Provisioner {
   std::string name; int32_t weight = 0;
@@ -120,7 +121,7 @@ struct StateNode {
 struct ClusterPod { std::string uid, ns, node_name; StrMap labels; std::vector<AffinityTerm> anti_required; };
 
 // One event of a cluster's life between two snapshots (ksh_env_apply; state.Cluster's UpdateNode / DeleteNode / UpdatePod / DeletePod, cluster.go)
-struct DeltaEvent { enum Kind { NodeAdd, NodeRemove, PodBind, PodUnbind, NodeUpdate } kind = NodeAdd; StateNode node; Pod pod; std::string name; };
+struct DeltaEvent { enum Kind { NodeAdd, NodeRemove, PodBind, PodUnbind, NodeUpdate, TypeUpdate } kind = NodeAdd; StateNode node; Pod pod; std::string name; InstanceType type; };
 
 struct Problem {
   std::vector<std::string> extra_well_known;
@@ -185,8 +186,8 @@ class Parser {
   Parser(const char* text, size_t len) : p_(text), e_(text + len) {}
 
   // What state.Cluster hears between two passes over the cluster (cluster.go UpdateNode / DeleteNode / UpdatePod / DeletePod), as KSD1 text:
-  //   KSD1 <n events>  { NODE+ <NODE record> | NODE= <NODE record> | NODE- <node name> | BIND <node name> POD <pod record> | UNBIND <pod uid> }*  END
-  // The records are KSP1's own (the NODE record without its leading keyword, the POD record with it).
+  //   KSD1 <n events>  { NODE+ <NODE record> | NODE= <NODE record> | NODE- <node name> | BIND <node name> POD <pod record> | UNBIND <pod uid> | IT= <IT record> }*  END
+  // The records are KSP1's own (the NODE and the IT record without their leading keyword, the POD record with it).
   std::vector<DeltaEvent> parse_delta() {
     std::vector<DeltaEvent> ev;
     expect("KSD1");
@@ -197,7 +198,8 @@ class Parser {
       else if (k == "BIND") { e.kind = DeltaEvent::PodBind; e.name = str(); expect("POD"); e.pod = pod(); }
       else if (k == "UNBIND") { e.kind = DeltaEvent::PodUnbind; e.name = str(); }
       else if (k == "NODE=") { e.kind = DeltaEvent::NodeUpdate; e.node = node(); }
-      else throw Error("KSD1: expected NODE+|NODE=|NODE-|BIND|UNBIND got " + k);
+      else if (k == "IT=") { e.kind = DeltaEvent::TypeUpdate; e.type = instance_type(); }
+      else throw Error("KSD1: expected NODE+|NODE=|NODE-|BIND|UNBIND|IT= got " + k);
       ev.push_back(std::move(e));
     }
     expect("END");
@@ -215,14 +217,7 @@ class Parser {
     int nit = count(); pr.instance_types.reserve(nit);
     for (int i = 0; i < nit; ++i) {
       expect("IT");
-      InstanceType it; it.name = str();
-      for (int n = count(); n > 0; --n) it.requirements.push_back(expr());
-      for (int n = count(); n > 0; --n) {
-        Offering o; o.capacity_type = str(); o.zone = str(); o.price = std::strtod(tok().c_str(), nullptr); o.available = count() != 0;
-        it.offerings.push_back(o);
-      }
-      it.capacity = reslist(); it.overhead = reslist();
-      pr.instance_types.push_back(std::move(it));
+      pr.instance_types.push_back(instance_type());
     }
     expect("PROVS");
     for (int np = count(); np > 0; --np) {
@@ -298,6 +293,17 @@ class Parser {
     AffinityTerm t; t.topology_key = str();
     for (int n = count(); n > 0; --n) t.namespaces.push_back(str());
     t.selector = selector(); return t;
+  }
+  // the IT record after its keyword: also the body of an IT= event (parse_delta)
+  InstanceType instance_type() {
+    InstanceType it; it.name = str();
+    for (int n = count(); n > 0; --n) it.requirements.push_back(expr());
+    for (int n = count(); n > 0; --n) {
+      Offering o; o.capacity_type = str(); o.zone = str(); o.price = std::strtod(tok().c_str(), nullptr); o.available = count() != 0;
+      it.offerings.push_back(o);
+    }
+    it.capacity = reslist(); it.overhead = reslist();
+    return it;
   }
   StateNode node() {
     StateNode sn; sn.name = str(); sn.in_state = count() != 0;

@@ -104,13 +104,7 @@ class EnvReader : public SpecReader {
     Problem pr;
     for (uint32_t n = cnt(); n; --n) pr.extra_well_known.push_back(s());
     { const uint32_t n = cnt(); pr.instance_types.reserve(n);
-      for (uint32_t k = 0; k < n; ++k) {
-        InstanceType it; it.name = s();
-        for (uint32_t m = cnt(); m; --m) it.requirements.push_back(expr());
-        for (uint32_t m = cnt(); m; --m) { Offering o; o.capacity_type = s(); o.zone = s(); const uint64_t lo = u(), hi = u(), bits = lo | (hi << 32); std::memcpy(&o.price, &bits, 8); o.available = u() != 0; it.offerings.push_back(std::move(o)); }
-        it.capacity = res(); it.overhead = res();
-        pr.instance_types.push_back(std::move(it));
-      } }
+      for (uint32_t k = 0; k < n; ++k) pr.instance_types.push_back(instance_type()); }
     for (uint32_t n = cnt(); n; --n) {
       Provisioner pv; pv.name = s(); pv.weight = i(); pv.labels = map();
       for (uint32_t m = cnt(); m; --m) pv.requirements.push_back(expr());
@@ -137,6 +131,14 @@ class EnvReader : public SpecReader {
   }
  protected:
   Taint taint() { Taint t; t.key = s(); t.value = s(); t.effect = s(); return t; }
+  // the instance_type record of the grammar above: also the body of an IT= event (DeltaReader below)
+  InstanceType instance_type() {
+    InstanceType it; it.name = s();
+    for (uint32_t m = cnt(); m; --m) it.requirements.push_back(expr());
+    for (uint32_t m = cnt(); m; --m) { Offering o; o.capacity_type = s(); o.zone = s(); const uint64_t lo = u(), hi = u(), bits = lo | (hi << 32); std::memcpy(&o.price, &bits, 8); o.available = u() != 0; it.offerings.push_back(std::move(o)); }
+    it.capacity = res(); it.overhead = res();
+    return it;
+  }
   // the state_node record of the grammar above: also the body of a NODE+ and of a NODE= event (DeltaReader below)
   StateNode state_node() {
     StateNode sn; sn.name = s(); sn.in_state = u() != 0; sn.labels = map();
@@ -159,9 +161,10 @@ class EnvReader : public SpecReader {
 //               | KSH_EVENT_BIND        node_name:S nwords:U spec uid:S ts_lo:U ts_hi:U   (BIND: the pod blocks' spec record, nwords words; then uid and creationTimestamp)
 //               | KSH_EVENT_UNBIND      uid:S                                        (UNBIND)
 //               | KSH_EVENT_NODE_UPDATE state_node                                   (NODE=: the record NODE+ carries, for a node that is in state already)
+//               | KSH_EVENT_INSTANCE_TYPE_UPDATE instance_type                       (IT=: the environment's instance_type record, for a type the catalogue has)
 //
 // n_events is the block's own field (no count word leads the stream); the stream must hold exactly that many events and end with the last one.
-enum : uint32_t { kEventNodeAdd = KSH_EVENT_NODE_ADD, kEventNodeRemove = KSH_EVENT_NODE_REMOVE, kEventBind = KSH_EVENT_BIND, kEventUnbind = KSH_EVENT_UNBIND, kEventNodeUpdate = KSH_EVENT_NODE_UPDATE };
+enum : uint32_t { kEventNodeAdd = KSH_EVENT_NODE_ADD, kEventNodeRemove = KSH_EVENT_NODE_REMOVE, kEventBind = KSH_EVENT_BIND, kEventUnbind = KSH_EVENT_UNBIND, kEventNodeUpdate = KSH_EVENT_NODE_UPDATE, kEventTypeUpdate = KSH_EVENT_INSTANCE_TYPE_UPDATE };
 class DeltaReader : public EnvReader {
  public:
   DeltaReader(const ksh_pod_block& strings, const uint32_t* w, const uint32_t* e) : EnvReader(strings, w, e) {}
@@ -181,6 +184,7 @@ class DeltaReader : public EnvReader {
           e.pod.uid = s(); const uint64_t lo = u(), hi = u(); e.pod.creation_ts = (int64_t)(lo | (hi << 32));
         } else if (kind == kEventUnbind) { e.kind = DeltaEvent::PodUnbind; e.name = s(); }
         else if (kind == kEventNodeUpdate) { e.kind = DeltaEvent::NodeUpdate; e.node = state_node(); }
+        else if (kind == kEventTypeUpdate) { e.kind = DeltaEvent::TypeUpdate; e.type = instance_type(); }
         else throw Error("unknown event kind " + std::to_string(kind));
         ev.push_back(std::move(e));
       } catch (const Error& x) { throw Error("delta block: event " + std::to_string(k) + ": " + x.what()); }

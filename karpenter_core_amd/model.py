@@ -418,6 +418,19 @@ class EnvBlockWriter(PodBlockWriter):
         for v in n.volumes:
             w.extend((self._s(v.driver), self._s(v.pvc_id)))
 
+    def _instance_type(self, w, it: "InstanceType"):
+        """The instance_type record (also the body of an IT= event, `DeltaBlockWriter`)."""
+        import struct
+        w.extend((self._s(it.name), len(it.requirements)))
+        for e in it.requirements:
+            self._expr(w, e)
+        w.append(len(it.offerings))
+        for o in it.offerings:
+            bits = struct.unpack("<Q", struct.pack("<d", float(o.price)))[0]
+            w.extend((self._s(o.capacity_type), self._s(o.zone), bits & 0xFFFFFFFF, bits >> 32, 1 if o.available else 0))
+        self._res(w, it.capacity)
+        self._res(w, it.overhead)
+
     def _pod(self, w, p: "Pod"):
         """A whole pod inside a stream: word count, spec record, uid, creationTimestamp -- the tail of a BIND event (`DeltaBlockWriter`)."""
         w.append(0)
@@ -435,21 +448,12 @@ class EnvBlockWriter(PodBlockWriter):
                 "words": np.asarray(self._words if self._words else [0], dtype=np.uint32)}
 
     def write(self, pr: "Problem") -> dict:
-        import struct
         w = self._words
         w.append(len(pr.extra_well_known))
         w.extend(self._s(k) for k in pr.extra_well_known)
         w.append(len(pr.instance_types))
         for it in pr.instance_types:
-            w.extend((self._s(it.name), len(it.requirements)))
-            for e in it.requirements:
-                self._expr(w, e)
-            w.append(len(it.offerings))
-            for o in it.offerings:
-                bits = struct.unpack("<Q", struct.pack("<d", float(o.price)))[0]
-                w.extend((self._s(o.capacity_type), self._s(o.zone), bits & 0xFFFFFFFF, bits >> 32, 1 if o.available else 0))
-            self._res(w, it.capacity)
-            self._res(w, it.overhead)
+            self._instance_type(w, it)
         w.append(len(pr.provisioners))
         for p in pr.provisioners:
             w.extend((self._s(p.name), int(p.weight) & 0xFFFFFFFF))
@@ -488,13 +492,14 @@ def env_to_block(pr: "Problem") -> dict:
     return EnvBlockWriter().write(pr)
 
 
-EVENT_NODE_ADD, EVENT_NODE_REMOVE, EVENT_BIND, EVENT_UNBIND, EVENT_NODE_UPDATE = 1, 2, 3, 4, 5      # include/kshost.h KSH_EVENT_*
+EVENT_NODE_ADD, EVENT_NODE_REMOVE, EVENT_BIND, EVENT_UNBIND, EVENT_NODE_UPDATE, EVENT_INSTANCE_TYPE_UPDATE = 1, 2, 3, 4, 5, 6      # include/kshost.h KSH_EVENT_*
 
 
 class DeltaBlockWriter(EnvBlockWriter):
     """Binary EVENTS ingress (include/kshost.h `ksh_delta_block`, grammar in karpenter_core_amd/host/kspb.hpp DeltaReader): what a cgo shim would fill from the
     *v1.Node / *v1.Pod its informers hand it instead of printing KSD1 text -- per event a kind word, then the environment's state-node record (NODE+), a node name
-    (NODE-), a node name and the pod (BIND), a pod uid (UNBIND) or the state-node record again for a node that is in state already (NODE=), over one string table."""
+    (NODE-), a node name and the pod (BIND), a pod uid (UNBIND), the state-node record again for a node that is in state already (NODE=) or the environment's
+    instance-type record for a type the catalogue has (IT=), over one string table."""
 
     def write_events(self, events: Sequence[tuple]) -> dict:
         w = self._words
@@ -512,6 +517,9 @@ class DeltaBlockWriter(EnvBlockWriter):
             elif e[0] == "node=":
                 w.append(EVENT_NODE_UPDATE)
                 self._node(w, e[1])
+            elif e[0] == "IT=":
+                w.append(EVENT_INSTANCE_TYPE_UPDATE)
+                self._instance_type(w, e[1])
             else:
                 raise ValueError(f"unknown snapshot event {e[0]!r}")
         return dict(self._block(), n_events=len(events))
@@ -721,6 +729,18 @@ def _ksp_node(n: "StateNode", w):
         w.write(f" {_tok(v.driver)} {_tok(v.pvc_id)}")
 
 
+def _ksp_instance_type(it: "InstanceType", w):
+    """The IT record of KSP1 without its keyword (also the body of a KSD1 `IT=` event)."""
+    w.write(f"{_tok(it.name)} {len(it.requirements)}")
+    for e in it.requirements:
+        e.ksp(w)
+    w.write(f" {len(it.offerings)}")
+    for o in it.offerings:
+        w.write(f" {_tok(o.capacity_type)} {_tok(o.zone)} {float(o.price)!r} {1 if o.available else 0}")
+    _ksp_reslist(it.capacity, w)
+    _ksp_reslist(it.overhead, w)
+
+
 def delta_to_block(events: Sequence[tuple]) -> dict:
     """The events `delta_to_ksd` takes as one binary block for `scheduler.ParsedProblem.apply_block` (kshost.h `ksh_env_apply_block`): no text on the way."""
     return DeltaBlockWriter().write_events(events)
@@ -729,9 +749,10 @@ def delta_to_block(events: Sequence[tuple]) -> dict:
 def delta_to_ksd(events: Sequence[tuple]) -> str:
     """KSD1 text for `scheduler.ParsedProblem.apply` (kshost.h `ksh_env_apply`): what state.Cluster hears between two passes over the cluster
     (cluster.go UpdateNode / DeleteNode / UpdatePod / DeletePod).  Events, in order:
-        ("node+", StateNode) | ("node-", node_name) | ("bind", node_name, Pod) | ("unbind", pod_uid) | ("node=", StateNode)
+        ("node+", StateNode) | ("node-", node_name) | ("bind", node_name, Pod) | ("unbind", pod_uid) | ("node=", StateNode) | ("IT=", InstanceType)
     `node=` replaces a node that is in state already (state.Cluster.UpdateNode after the first sight): slot and bound pods stay, everything the record carries is
-    taken as given."""
+    taken as given.  `IT=` replaces the instance type of that name in the catalogue (what cloudProvider.GetInstanceTypes lists now: offerings, prices, requirements,
+    capacity, overhead); the type keeps its index."""
     w = io.StringIO()
     w.write(f"KSD1 {len(events)}\n")
     for e in events:
@@ -748,6 +769,9 @@ def delta_to_ksd(events: Sequence[tuple]) -> str:
         elif e[0] == "node=":
             w.write("NODE= ")
             _ksp_node(e[1], w)
+        elif e[0] == "IT=":
+            w.write("IT= ")
+            _ksp_instance_type(e[1], w)
         else:
             raise ValueError(f"unknown snapshot event {e[0]!r}")
         w.write("\n")
@@ -787,14 +811,8 @@ class Problem:
         w.write("\n")
         w.write(f"ITS {len(self.instance_types)}\n")
         for it in self.instance_types:
-            w.write(f"IT {_tok(it.name)} {len(it.requirements)}")
-            for e in it.requirements:
-                e.ksp(w)
-            w.write(f" {len(it.offerings)}")
-            for o in it.offerings:
-                w.write(f" {_tok(o.capacity_type)} {_tok(o.zone)} {float(o.price)!r} {1 if o.available else 0}")
-            _ksp_reslist(it.capacity, w)
-            _ksp_reslist(it.overhead, w)
+            w.write("IT ")
+            _ksp_instance_type(it, w)
             w.write("\n")
         w.write(f"PROVS {len(self.provisioners)}\n")
         for p in self.provisioners:

@@ -155,6 +155,14 @@ class ClsBrief(ctypes.Structure):
                 ("dyn_maxskew", ctypes.c_int32), ("dyn_pd", ctypes.c_uint32)]
 
 
+class _ProblemHead(ctypes.Structure):      # include/ksolve.h ks_problem, up to the offering arrays (FlatProblem.catalogue)
+    _fields_ = [(n, ctypes.c_uint32) for n in ("P", "C", "T", "M", "E", "K", "R", "G", "GH", "S", "SC", "max_new_nodes", "flags", "wellknown_mask")] + [
+        ("key_nvalues", ctypes.POINTER(ctypes.c_uint32)), ("value_int", ctypes.POINTER(ctypes.c_int32)), ("key_zone", ctypes.c_int32), ("key_ct", ctypes.c_int32),
+        ("n_ct", ctypes.c_uint32), ("it_present", ctypes.POINTER(ctypes.c_uint32)), ("it_complement", ctypes.POINTER(ctypes.c_uint32)),
+        ("it_mask", ctypes.POINTER(ctypes.c_uint64)), ("it_alloc", ctypes.POINTER(ctypes.c_int64)), ("it_cap", ctypes.POINTER(ctypes.c_int64)),
+        ("it_offer", ctypes.POINTER(ctypes.c_uint64)), ("it_price", ctypes.POINTER(ctypes.c_double)), ("it_price_lo", ctypes.POINTER(ctypes.c_double))]
+
+
 class FlatProblem:
     """A Solve() problem flattened to the C-ABI `ks_problem` (host side only until `upload`)."""
 
@@ -250,6 +258,21 @@ class FlatProblem:
         if row >= ks.ks_debug_pack_row(row, f):
             raise KSolveError(KS_ERR_INVALID, f"ksh_pack_row: row {row} is not in the table")
         return (row, bool(f[0]), bool(f[1]), bool(f[2]), int(f[3]), int(f[4]))
+
+    def catalogue(self) -> dict:
+        """The offering arrays of the flat problem as `ksh_problem` shows them (include/ksolve.h ks_problem): {"it_offer": [T] available (zone, capacity-type)
+        pairs, "it_price" / "it_price_lo": [T, NP] highest / lowest price of an available pair, -1 / DBL_MAX where there is none}.  Copies."""
+        import numpy as np
+        kh = libs()[1]
+        kh.ksh_problem.restype = ctypes.POINTER(_ProblemHead)
+        kh.ksh_problem.argtypes = [ctypes.c_void_p]
+        p = kh.ksh_problem(self._h).contents
+        t = int(p.T)
+        npairs = int(p.key_nvalues[p.key_zone]) * int(p.n_ct)
+        out = {"it_offer": np.ctypeslib.as_array(p.it_offer, shape=(t,)).copy() if t else np.zeros(0, dtype=np.uint64)}
+        for k, ptr in (("it_price", p.it_price), ("it_price_lo", p.it_price_lo)):
+            out[k] = np.ctypeslib.as_array(ptr, shape=(t, npairs)).copy() if t and npairs and ptr else np.zeros((t, npairs))
+        return out
 
     def resource_names(self) -> List[str]:
         """The resource universe of the flat problem, by id (kshost.h ksh_name(h, 2, r, 0)): with `active_resources` the active names only."""
@@ -424,7 +447,8 @@ class ParsedProblem:
         """Keep the snapshot current by events instead of ingesting it again (kshost.h `ksh_env_apply`; state.Cluster's UpdateNode / DeleteNode / UpdatePod /
         DeletePod, cluster.go): `events` as `model.delta_to_ksd` takes them.  The first call needs the snapshot's bindings (`pod_node`); from then on the library
         holds them (`bindings()`), and `open_whatifs(..., pod_node=None)` means those.  Returns {"applied", "nodes", "pods", "continued", "ms"}: `continued` says the
-        snapshot's flattening took the short road (same universes), `ms` is the library's time for events + flattening."""
+        snapshot's flattening took the short road (same universes), `ms` is the library's time for events + flattening.  ("IT=", InstanceType) replaces the
+        instance type of that name in place -- offerings, prices, requirements, capacity, overhead -- and keeps its index."""
         import numpy as np, time
         from .model import delta_to_ksd
         kh = libs()[1]

@@ -487,6 +487,88 @@ def random_events_with_updates(rs, its, nodes, bound, n, tag, removes=True, make
     return events, nodes, bound
 
 
+# ---- catalogue changes: what cloudProvider.GetInstanceTypes answers differently from one pass to the next (the `IT=` event) ----
+CATALOGUE_KINDS = ("availability", "price", "pair", "values", "rare")
+RARE_ZONE, RARE_OS = "test-zone-9", "plan9"
+
+
+def with_offerings(it, offerings):
+    """`it` with these offerings, its zone / capacity-type requirement values following the available ones (fake/instancetype.go:48-106 and the cloud providers
+    derive both from Offerings.Available())."""
+    from .model import Expr
+    avail = [o for o in offerings if o.available]
+    reqs = [Expr(LABEL_ZONE, "In", [o.zone for o in avail]) if r.key == LABEL_ZONE else
+            Expr(LABEL_CAPACITY_TYPE, "In", [o.capacity_type for o in avail]) if r.key == LABEL_CAPACITY_TYPE else r for r in it.requirements]
+    return dataclasses.replace(it, requirements=reqs, offerings=list(offerings))
+
+
+def updated_type(rs, it, kind):
+    """The instance type `it` as the provider lists it after one change of `kind`: an offering's availability flips, its price moves, a (zone, capacity-type) pair
+    is listed or no longer listed, a value joins or leaves the operating-system requirement, or -- `rare` -- something the catalogue has nowhere else comes or
+    goes (an offering in RARE_ZONE, the operating system RARE_OS).  A fresh object; name, capacity and overhead are the type's own."""
+    from .model import Expr, Offering
+    offs = [dataclasses.replace(o) for o in it.offerings]
+    if kind == "availability":
+        o = offs[int(rs.randint(len(offs)))]
+        o.available = not o.available
+        return with_offerings(it, offs)
+    if kind == "price":
+        o = offs[int(rs.randint(len(offs)))]
+        o.price = round(o.price * float(rs.choice([0.5, 0.8, 1.25, 2.0])), 6)
+        return with_offerings(it, offs)
+    if kind == "pair":
+        have = {(o.zone, o.capacity_type) for o in offs}
+        missing = [(z, c) for z in ZONES for c in ("spot", "on-demand") if (z, c) not in have]
+        if missing and (len(offs) < 2 or rs.rand() < 0.5):
+            z, c = missing[int(rs.randint(len(missing)))]
+            offs.append(Offering(c, z, offs[0].price if offs else 1.0))
+        elif len(offs) > 1:
+            offs.pop(int(rs.randint(len(offs))))
+        return with_offerings(it, offs)
+    if kind == "values" or kind == "rare":
+        if kind == "rare" and rs.rand() < 0.5:
+            if any(o.zone == RARE_ZONE for o in offs):
+                offs = [o for o in offs if o.zone != RARE_ZONE]
+            else:
+                offs.append(Offering("on-demand", RARE_ZONE, offs[0].price if offs else 1.0))
+            return with_offerings(it, offs)
+        pool = [RARE_OS] if kind == "rare" else ["linux", "windows", "darwin"]
+        reqs = []
+        for r in it.requirements:
+            if r.key == LABEL_OS:
+                v = pool[int(rs.randint(len(pool)))]
+                vals = [x for x in r.values if x != v] if v in r.values and len(r.values) > 1 else sorted(set(r.values) | {v})
+                r = Expr(LABEL_OS, "In", vals)
+            reqs.append(r)
+        return dataclasses.replace(it, requirements=reqs)
+    raise ValueError(f"unknown catalogue change {kind!r}")
+
+
+def catalogue_after(its, events):
+    """The catalogue after the `IT=` events among `events`: every type in its place, the named ones replaced (the model the tests hold `ParsedProblem.apply` against)."""
+    out = list(its)
+    for ev in events:
+        if ev[0] == "IT=":
+            out[[t.name for t in out].index(ev[1].name)] = ev[1]
+    return out
+
+
+def random_events_with_catalogue(rs, its, nodes, bound, n, tag, share=0.3, changes=CATALOGUE_KINDS, **kw):
+    """`n` events, `share` of them `IT=` (a change of a random kind of `changes` to a random type of the catalogue as it is now), the others
+    `random_events_with_updates`' (`kw` goes there); returns (events, catalogue, nodes, bound) as they are after the events.  Nodes that join are of the ORIGINAL types (a node may carry any label)."""
+    n_cat = int(round(n * share))
+    other, nodes2, bound2 = random_events_with_updates(rs, its, nodes, bound, n - n_cat, tag, **kw)
+    events, cat = [], list(its)
+    at = sorted(int(x) for x in rs.randint(0, len(other) + 1, size=n_cat))      # (the catalogue events go in between the others; both kinds keep their order)
+    for k in range(len(other) + 1):
+        for _ in range(at.count(k)):
+            t = int(rs.randint(len(cat)))
+            cat[t] = updated_type(rs, cat[t], changes[int(rs.randint(len(changes)))])
+            events.append(("IT=", cat[t]))
+        events += other[k:k + 1]
+    return events, cat, nodes2, bound2
+
+
 # ---- a cloud-like catalogue with 9 to 16 resource names ----
 # The names an AWS-style provider lists on every instance type, whether or not the type has the device, then what device plugins add.
 WIDE_NAMES = ["cpu", "memory", "ephemeral-storage", "pods", "vpc.amazonaws.com/pod-eni", "nvidia.com/gpu", "amd.com/gpu", "aws.amazon.com/neuron",
