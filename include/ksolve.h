@@ -639,6 +639,7 @@ int ks_probe_has(const ks_req1* a, const int32_t* value_int, uint32_t nvalues, i
 
 const char* ks_last_error(void); /* thread-local message of the last non-OK return */
 const char* ks_version(void);
+uint32_t ks_rr_run_max(void);       /* queue entries one RUN round of ks_pack_rr takes at most (the library's RR_RUN_MAX: a build-time choice, a multiple of 64) */
 
 #ifdef __cplusplus
 }

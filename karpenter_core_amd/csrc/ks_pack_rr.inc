@@ -228,8 +228,13 @@ struct RRCand { u64 kp; i64 room[4]; u64 meta; };     // a worker wave's best ca
 #define RR_B 8          /* pods per round */
 #define RR_RING 32      /* class records (brief + cached answers) of queue entries, by queue index */
 // One pod of a run: what differs between pods of one evaluation class -- the pod itself and the hostname-keyed groups Topology.Record counts it into
-struct alignas(16) RRRunPod { u32 pod, cls, nh; u8 hs[12]; u32 pad[2]; };
-static_assert(sizeof(RRRunPod) == 32, "RRRunPod layout");
+// (its hostname-keyed ITEMS are in RRLds::runitem: every wave reads those at every step)
+struct alignas(8) RRRunPod { u32 pod, cls, nh; u8 hs[12]; };
+static_assert(sizeof(RRRunPod) == 24, "RRRunPod layout");      // (the committing wave reads it as six words, lane i: word i)
+#ifndef RR_RUN_MAX
+#define RR_RUN_MAX 256u /* queue entries a RUN round takes at most: the leader looks at the queue 64 entries (one lane each) at a time, up to this many */
+#endif
+static_assert(RR_RUN_MAX >= 64u && RR_RUN_MAX % 64u == 0u, "a run's tables are filled 64 entries at a time");
 struct alignas(16) RRCtl { u32 hdr[32]; u32 create[24]; u32 pbrief[48]; u32 pad[8]; };      // create: key | rm | room[4] (8 words) | hc[8]
 // A queue entry prepared for its round: w[0..47] the class brief | w[48] stream position | w[49] class | w[50] pod | w[51] hostname records that count |
 // w[52] requeued unrelaxed; m[0..23] what every nrc answers (RRMemo image: acc[2] | chg[2] | vfy[2] | n | pad | child[64 bytes])
@@ -259,14 +264,12 @@ struct alignas(16) RRLds {
   DevProb P; DevState S; FastTabs ft; LeaderShared ls; WaveShared sh; RRNrc nt;
   RRCtl ctl[2];                             // the orders of a round (by round parity)
   u64 win[2][RR_B];                         // per pod of the round: min over the workers of key << 32 | ambiguous << 31 | nrc << 16 | node
-  u32 wk[RR_NWK][RR_B][64];                 // per lane: the slots that accepted the pod at EVALUATE
-  u64 wsub[RR_NWK][RR_B];                   // per worker wave and pod: its candidate as evaluated (what it submits to a pick while none of its nodes took a pod of the round)
   u64 stepk[2][RR_NWK][8];                  // a run's step: per worker wave its smallest accepting keys (key << 32 | nrc << 16 | node), by step parity
-  u64 runitem[2][64];                       // ... and their hostname-keyed items (RR_ITEM_LIM), apart: every wave reads them at every step, lane = pod
-  RRRunPod runtab[2][64];                   // a run's pods (by round parity: the workers still commit a round's last step while the leader forms the next round)
+  u64 runitem[2][RR_RUN_MAX];               // ... and their hostname-keyed items (RR_ITEM_LIM), apart: every wave reads them at every step, lane = pod
+  RRRunPod runtab[2][RR_RUN_MAX];           // a run's pods (by round parity: the workers still commit a round's last step while the leader forms the next round)
   u32 mrg_out[64], mrg_k[4];                // ... and what the leader's out-of-line copy hands back: the winners' payloads, kind | stop node | stop nrc
   u64 mrg[RR_NW][64];                       // rr_step_merge's scratch, one row per wave
-  u32 runres[64];                           // ... and where they went: child nrc << 16 | node
+  u32 runres[RR_RUN_MAX];                   // ... and where they went: child nrc << 16 | node
   RRCand ask;                               // the node the exact filter is asked about, as its owner holds it
   RREntry ring[RR_RING];
   u8 en_nrc[64]; u8 pkch[RR_B < 4 ? 4 : RR_B]; u32 scratch[64];
@@ -1934,19 +1937,21 @@ bool have = false;
     RRCtl& C = L.ctl[par];
     // ---------- 1. form the batch ----------
     u32 nb = 0, same = 0, prev_ev = 0, prev_flags = 1, run = 0; u64 rmask_acc = 0;
-    // A RUN?  The entries behind the head of its base class (ev0: same requests, same cached answers, at most one hostname-keyed item, no topology counters read): one lane each
+    // A RUN?  The entries behind the head of its base class (ev0: same requests, same cached answers, at most one hostname-keyed item, no topology counters read): one lane
+    // each, 64 entries of the queue at a time, up to RR_RUN_MAX.  The walk ends with the first 64 that hold an entry the run does not take: nothing behind it is read.
     auto try_run = [&](const u32 ev0) {
-        // ---- a RUN?  The entries behind the head that are evaluated like it (same evaluation class): one lane each ----
-      const u32 t = (u32)lane; const bool valid = t < q_len;
-      u32 ix = q_head + t; if (ix >= nP) ix -= nP;
-      const u64 e = valid ? tb.q[ix] : 0ull;
-      const u32 cls = (u32)(e >> 32) & 0x7FFFFFFFu;
-      const u32 evt = valid ? rrb[(size_t)cls * 48 + 27] : ~ev0, flt = valid ? rrb[(size_t)cls * 48 + 9] : 2u;      // (word 27: the base class, ks_link_rr2)
-      const bool okt = valid && (t == 0 || (e >> 63) == 0) && evt == ev0 && !(flt & 7u);
-      const u64 bad = ~ballot64(okt);
-      const u32 R = bad ? (u32)__builtin_ctzll(bad) : 64u;
-      if (R >= 2u) {
-        if (t < R) {
+      u32 R = 0;
+      for (u32 c0 = 0; c0 < RR_RUN_MAX; c0 += 64u) {
+        const u32 t = c0 + (u32)lane; const bool valid = t < q_len;      // (t: the entry's place in the RUN -- what the tables are indexed by, and what the rule for requeued entries asks about)
+        u32 ix = q_head + t; if (ix >= nP) ix -= nP;
+        const u64 e = valid ? tb.q[ix] : 0ull;
+        const u32 cls = (u32)(e >> 32) & 0x7FFFFFFFu;
+        const u32 evt = valid ? rrb[(size_t)cls * 48 + 27] : ~ev0, flt = valid ? rrb[(size_t)cls * 48 + 9] : 2u;      // (word 27: the base class, ks_link_rr2)
+        const bool okt = valid && (t == 0 || (e >> 63) == 0) && evt == ev0 && !(flt & 7u);      // (a requeued, unrelaxed entry only as the head of the run: queue.go:50-53 is tested there)
+        const u64 bad = ~ballot64(okt);
+        const u32 n = bad ? (u32)__builtin_ctzll(bad) : 64u;
+        if (c0 + n < 2u) return;               // (a run of one is a round's pod)
+        if ((u32)lane < n) {
           RRRunPod& rp = L.runtab[par][t];
           const u32 nh = rrb[(size_t)cls * 48 + 17]; u32 cnt = 0;
           for (u32 w = 0; w < nh && w < RR_MAXHREC; ++w) { const u32 word = rrb[(size_t)cls * 48 + 28 + w]; if (((word >> 16) & 1u) || ((g_active_mask >> ((word >> 8) & 63u)) & 1ull)) rp.hs[cnt++] = (u8)(word & 0xFFu); }
@@ -1957,11 +1962,13 @@ bool have = false;
             const u32 hw = rrb[(size_t)cls * 48 + 20 + q]; const i32 lim = (hw & 0xFFu) == 0 ? (i32)rrb[(size_t)cls * 48 + 23 + q] - (i32)((hw >> 8) & 0xFFu) : 0;
             it[q] = 0x80000000u | (((u32)lim & 0x1FFu) << 16) | ((8u * ((hw >> 16) & 3u)) << 8) | ((hw >> 18) & 7u);
           }
-          rp.pad[0] = it[0]; rp.pad[1] = it[1]; L.runitem[par][t] = (u64)it[0] | ((u64)it[1] << 32);
+          L.runitem[par][t] = (u64)it[0] | ((u64)it[1] << 32);
         }
-        LSYNC();
-        run = R; nb = R;
+        R = c0 + n;
+        if (n < 64u) break;
       }
+      LSYNC();
+      run = R; nb = R;
     };
     u32 last_flags = 0, last_base = 0;
     auto form_one = [&](const u32 adv, bool& was_dyn) -> bool {

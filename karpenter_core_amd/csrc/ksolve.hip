@@ -4583,3 +4583,4 @@ extern "C" int ks_debug_classes(ks_dev_problem* d, void* briefs_out, void* plans
 
 extern "C" const char* ks_last_error(void) { return g_err.c_str(); }
 extern "C" const char* ks_version(void) { return "ksolve 0.1.0 (gfx950)"; }
+extern "C" uint32_t ks_rr_run_max(void) { return RR_RUN_MAX; }
