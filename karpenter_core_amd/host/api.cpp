@@ -14,6 +14,20 @@
 
 #include "encode.hpp"
 
+// The caller's objects in memory.  A cluster snapshot additionally keeps its flattening (ksh::SnapshotBase) once a what-if batch asked for
+// it: a consolidation pass probes many candidate sets against the same snapshot (multinodeconsolidation.go:86-114 binary search,
+// singlenodeconsolidation.go:54 scan), and everything that does not depend on the candidate set is flattened once.
+struct Parsed {
+  std::shared_ptr<const ksp::Problem> pr;
+  std::mutex mu; std::shared_ptr<const ksh::SnapshotBase> sb; std::vector<int32_t> sb_pod_node; uint32_t sb_flags = 0;
+  ksh::EnvCache env;      // the flattening of everything but the pods, reused by the next batch with the same universe signature
+  std::shared_ptr<const void> cmd_nodes;      // what the consolidation commands read of the nodes' labels (CmdSnapshot below), made once; ksh_env_apply* drops it
+  std::shared_ptr<const void> cand_nodes;     // what candidate selection reads of them (CandSnapshot below), likewise
+  // ksh_env_apply (round 6): once events were applied the library holds the bindings itself -- bind[i] = the node pod i is bound to, -1 for a pod that was unbound
+  // (it stays in place: nothing that points into the problem may move) -- and the names of what is alive
+  std::unordered_map<std::string, uint32_t> type_index;      // instance-type name -> index, made by the first IT= event (types are never added, removed or renamed)
+  bool bind_set = false, had_cluster_pods = false; std::vector<int32_t> bind; std::unordered_map<std::string, uint32_t> live_node, live_pod; uint64_t tombstones = 0; uint32_t applied = 0;
+};
 namespace {
 // A batch of what-ifs derived on the device (ks_whatifs_open): the arena, the resident snapshot it points into and what the candidate sets were
 struct DeltaBatch {
@@ -45,8 +59,91 @@ static std::string decode_handle(Handle* h, double dt) {
   return h->enc->decode(t, dt);
 }
 thread_local std::string g_err;
-uint32_t default_threads() { return ksh::host_threads(); }
 int set_err(int code, const std::string& m) { g_err = m; return code; }
+// what a call into libksolve returned: KS_OK, or its code with its message
+int dev_rc(int rc) { return rc == KS_OK ? KS_OK : set_err(rc, ks_last_error()); }
+// The one error boundary: every extern "C" function that can throw runs its body through here, so that no exception -- a std::bad_alloc included -- leaves the library
+template <class F> int guarded(F&& body) {
+  try { return body(); }
+  catch (const ksh::Unsupported& e) { return set_err(KS_ERR_UNSUPPORTED, e.what()); }
+  catch (const std::exception& e) { return set_err(KS_ERR_INVALID, e.what()); }
+}
+using clk = std::chrono::steady_clock;
+double ms_since(clk::time_point t) { return std::chrono::duration<double, std::milli>(clk::now() - t).count(); }
+void zero(double* ms, int n) { if (ms) std::fill(ms, ms + n, 0.0); }
+bool timing() { return getenv("KSH_TIMING") != nullptr; }      // (asked at every call: a caller may set it after loading the library)
+// a flattening as a handle, its result buffers allocated
+Handle* new_handle(std::unique_ptr<ksh::Encoded> enc) {
+  auto h = std::make_unique<Handle>();
+  h->enc = std::move(enc); h->rb = h->enc->make_result();
+  return h.release();
+}
+// not uploaded yet: to the calling thread's current HIP device
+int ensure_resident(Handle* h) { return h->dev ? KS_OK : ksh_upload(h, ks_current_device()); }
+// ds = the device problems of hv[0 .. n).  A handle without one -- or, with `need_result`, without a solve's result on the device -- is refused in the caller's words
+int device_problems(void** hv, uint32_t n, bool need_result, const char* refusal, std::vector<ks_dev_problem*>& ds) {
+  ds = std::vector<ks_dev_problem*>(n);
+  for (uint32_t i = 0; i < n; ++i) {
+    Handle* h = (Handle*)hv[i];
+    if (!h || !h->dev || (need_result && !h->dev_result)) return set_err(KS_ERR_INVALID, refusal);
+    ds[i] = h->dev;
+  }
+  return KS_OK;
+}
+// The string table of a binary block (env / delta / pdb), checked: the offsets ascend and stay within str_bytes_len.  As the ksh_pod_block the readers take.
+ksh_pod_block string_table(const char* what, uint32_t n_strings, const uint32_t* str_off, const char* str_bytes, uint64_t str_bytes_len) {
+  for (uint32_t i = 0; i < n_strings; ++i) if (str_off[i + 1] < str_off[i]) throw ksp::Error(std::string(what) + " block: string offsets not ascending");
+  if (n_strings && str_off[n_strings] > str_bytes_len) throw ksp::Error(std::string(what) + " block: string offsets reach beyond str_bytes_len");
+  ksh_pod_block strings{}; strings.n_strings = n_strings; strings.str_off = str_off; strings.str_bytes = str_bytes; strings.str_bytes_len = str_bytes_len;
+  return strings;
+}
+// the bindings a what-if call means: the caller's array, or -- after ksh_env_apply -- the library's own
+const int32_t* bindings_of(Parsed* P, const int32_t* pod_node) { return pod_node ? pod_node : (P->bind_set ? P->bind.data() : nullptr); }
+// The snapshot's flattening for these bindings (the caller's, else the library's own) and flags: the one kept if it fits them, else a new one, which is kept.  P->mu is
+// held.  `may_continue`: a new one is continued from the one kept when the flags agree (ksh::make_snapshot_base `before`).  *made (may be NULL): a new one was made.
+std::shared_ptr<const ksh::SnapshotBase> flattening_of(Parsed* P, const int32_t* pod_node, uint32_t flags, bool may_continue, bool* made = nullptr) {
+  pod_node = bindings_of(P, pod_node);
+  const size_t np = P->pr->pods.size();
+  if (!pod_node && np) throw ksp::Error("no bindings (pod_node)");
+  const bool fits = P->sb && P->sb_flags == flags && P->sb_pod_node.size() == np && std::equal(pod_node, pod_node + np, P->sb_pod_node.begin());
+  if (made) *made = !fits;
+  if (fits) return P->sb;
+  P->sb = ksh::make_snapshot_base(P->pr, pod_node, flags, may_continue && P->sb_flags == flags ? P->sb.get() : nullptr);
+  P->sb_flags = flags; P->sb_pod_node.assign(pod_node, pod_node + np);
+  return P->sb;
+}
+// The snapshot's own flattening resident on `device` with its tables built (once per snapshot and device; shared by every what-if over it).
+int resident_base(const ksh::Encoded* base, int device, std::shared_ptr<void>* out) {
+  std::lock_guard<std::mutex> g(base->dev_mu);
+  auto it = base->dev_resident.find(device);
+  if (it != base->dev_resident.end()) { *out = it->second; return KS_OK; }
+  ks_dev_problem* raw = nullptr;
+  int rc = ks_problem_upload(&base->prob, device, &raw);
+  if (rc == KS_OK) rc = ks_problem_prepare(raw);
+  if (rc != KS_OK) { if (raw) ks_problem_free(raw); return set_err(rc, ks_last_error()); }
+  *out = std::shared_ptr<void>(raw, [](void* p) { ks_problem_free((ks_dev_problem*)p); });
+  base->dev_resident[device] = *out;
+  return KS_OK;
+}
+// FNV-1a over every array behind a flattening's ks_problem: two construction routes produced the same flat problem iff equal.
+uint64_t fingerprint_of(const ksh::Encoded& E) {
+  uint64_t h = 1469598103934665603ull;
+  auto mix = [&](const void* p, size_t bytes) { const unsigned char* c = (const unsigned char*)p; for (size_t i = 0; i < bytes; ++i) { h ^= c[i]; h *= 1099511628211ull; } };
+  auto vec = [&](const auto& v) { uint64_t n = v.size(); mix(&n, 8); if (n) mix(v.data(), n * sizeof(v[0])); };
+  auto rs = [&](const ksh::ReqSetsStore& r) { vec(r.present); vec(r.complement); vec(r.mask); vec(r.gt); vec(r.lt); vec(r.it_state); };
+  const ks_problem& p = E.prob; const uint32_t dims[16] = {p.P, p.C, p.T, p.M, p.E, p.K, p.R, p.G, p.GH, p.S, p.SC, p.max_new_nodes, p.flags, p.wellknown_mask, p.n_ct, p.n_topologies}; mix(dims, sizeof dims);
+  const ksh::Encoded& C = E.catalogue(); const ksh::Encoded& L = E.lattice();
+  vec(E.key_nvalues); vec(E.value_int); vec(C.it_present); vec(C.it_complement); vec(C.it_mask); vec(C.it_offer); vec(C.it_price); vec(C.it_alloc); vec(C.it_cap);
+  vec(L.its_inter); vec(L.its_fail); vec(L.its_nidne); vec(L.its_types); rs(E.tmpl); rs(E.en); rs(E.cls); rs(E.flt);
+  vec(E.tmpl_taints); vec(E.tmpl_types); vec(E.tmpl_daemon); vec(E.tmpl_remaining); vec(E.tmpl_daemon_present); vec(E.tmpl_limit_present);
+  vec(E.en_taints); vec(E.en_avail); vec(E.en_requests); vec(E.en_requests_present); vec(E.en_port_off);
+  vec(E.cls_hn_mode); vec(E.cls_hn_off); vec(E.hn_list); vec(E.cls_requests); vec(E.cls_requests_present); vec(E.cls_tolerated); vec(E.cls_port_off); vec(E.ports);
+  vec(E.en_vol_limit); vec(E.en_vol_count); vec(E.en_vol_set); vec(E.cls_vol_off); vec(E.vol_list);
+  vec(E.cls_own_off); vec(E.own_list); vec(E.cls_sel_off); vec(E.sel_list); vec(E.cls_isel_off); vec(E.isel_list); vec(E.cls_iown_off); vec(E.iown_list);
+  vec(E.pod_stage_off); vec(E.stage_cls); vec(E.queue); vec(E.grp_type); vec(E.grp_active); vec(E.grp_key); vec(E.grp_max_skew); vec(E.grp_count); vec(E.grp_hslot);
+  vec(E.grph_count); vec(E.grph_extra_pos); vec(E.grp_filter_off);
+  return h;
+}
 }  // namespace
 
 extern "C" {
@@ -57,19 +154,16 @@ void ksh_free(char* p) { free(p); }
 // Parse KSP1, run the host half of NewScheduler/NewTopology, flatten.  No GPU needed.
 int ksh_open(const char* ksp_text, size_t len, uint32_t flags, void** out) {
   *out = nullptr;
-  try {
-    auto h = std::make_unique<Handle>();
-    auto t0 = std::chrono::steady_clock::now();
+  return guarded([&] {
+    auto t0 = clk::now();
     ksp::Problem pr = ksp::Parser(ksp_text, len).parse();
-    auto t1 = std::chrono::steady_clock::now();
-    h->enc = ksh::encode(std::move(pr), flags);
-    auto t2 = std::chrono::steady_clock::now();
-    h->rb = h->enc->make_result();
-    if (getenv("KSH_TIMING")) fprintf(stderr, "ksh_open: parse %.2f ms, encode %.2f ms, result buffers %.2f ms\n", std::chrono::duration<double, std::milli>(t1 - t0).count(),
-                                      std::chrono::duration<double, std::milli>(t2 - t1).count(), std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t2).count());
-    *out = h.release(); return KS_OK;
-  } catch (const ksh::Unsupported& e) { return set_err(KS_ERR_UNSUPPORTED, e.what());
-  } catch (const std::exception& e) { return set_err(KS_ERR_INVALID, e.what()); }
+    const double parse_ms = ms_since(t0); t0 = clk::now();
+    auto enc = ksh::encode(std::move(pr), flags);
+    const double encode_ms = ms_since(t0); t0 = clk::now();
+    *out = new_handle(std::move(enc));
+    if (timing()) fprintf(stderr, "ksh_open: parse %.2f ms, encode %.2f ms, result buffers %.2f ms\n", parse_ms, encode_ms, ms_since(t0));
+    return KS_OK;
+  });
 }
 void ksh_close(void* h) { delete (Handle*)h; }
 const ks_problem* ksh_problem(void* h) { return &((Handle*)h)->enc->prob; }
@@ -78,67 +172,45 @@ const ks_problem* ksh_problem(void* h) { return &((Handle*)h)->enc->prob; }
 // ksh_parse turns KSP1 text into the C++ objects (the analogue of the []*v1.Pod, []*cloudprovider.InstanceType, []*state.Node a Go
 // caller holds); ksh_solve_from_pods then does what the reference does from that point: NewScheduler's flattening incl. NewQueue's
 // sort and every per-pod computation, upload, the HIP kernels, read-back -- the window bench.py times as "solve_from_pods".
-// The caller's objects in memory.  A cluster snapshot additionally keeps its flattening (ksh::SnapshotBase) once a what-if batch asked for
-// it: a consolidation pass probes many candidate sets against the same snapshot (multinodeconsolidation.go:86-114 binary search,
-// singlenodeconsolidation.go:54 scan), and everything that does not depend on the candidate set is flattened once.
-struct Parsed {
-  std::shared_ptr<const ksp::Problem> pr;
-  std::mutex mu; std::shared_ptr<const ksh::SnapshotBase> sb; std::vector<int32_t> sb_pod_node; uint32_t sb_flags = 0;
-  ksh::EnvCache env;      // the flattening of everything but the pods, reused by the next batch with the same universe signature
-  std::shared_ptr<const void> cmd_nodes;      // what the consolidation commands read of the nodes' labels (CmdSnapshot below), made once; ksh_env_apply* drops it
-  std::shared_ptr<const void> cand_nodes;     // what candidate selection reads of them (CandSnapshot below), likewise
-  // ksh_env_apply (round 6): once events were applied the library holds the bindings itself -- bind[i] = the node pod i is bound to, -1 for a pod that was unbound
-  // (it stays in place: nothing that points into the problem may move) -- and the names of what is alive
-  std::unordered_map<std::string, uint32_t> type_index;      // instance-type name -> index, made by the first IT= event (types are never added, removed or renamed)
-  bool bind_set = false, had_cluster_pods = false; std::vector<int32_t> bind; std::unordered_map<std::string, uint32_t> live_node, live_pod; uint64_t tombstones = 0; uint32_t applied = 0;
-};
-// the bindings a what-if call means: the caller's array, or -- after ksh_env_apply -- the library's own
-static const int32_t* bindings_of(Parsed* P, const int32_t* pod_node) { return pod_node ? pod_node : (P->bind_set ? P->bind.data() : nullptr); }
 int ksh_parse(const char* ksp_text, size_t len, void** out) {
   *out = nullptr;
-  try { auto p = std::make_unique<Parsed>(); p->pr = std::make_shared<const ksp::Problem>(ksp::Parser(ksp_text, len).parse()); *out = p.release(); return KS_OK; }
-  catch (const std::exception& e) { return set_err(KS_ERR_INVALID, e.what()); }
+  return guarded([&] { auto p = std::make_unique<Parsed>(); p->pr = std::make_shared<const ksp::Problem>(ksp::Parser(ksp_text, len).parse()); *out = p.release(); return KS_OK; });
 }
 int ksh_env_ingest(const ksh_env_block* env, void** out, double* ms) {
   if (out) *out = nullptr;
   if (!out || !env || !env->str_off || !env->words || (!env->str_bytes && env->n_strings)) return set_err(KS_ERR_INVALID, "null argument");
-  try {
-    auto t0 = std::chrono::steady_clock::now();
-    for (uint32_t i = 0; i < env->n_strings; ++i) if (env->str_off[i + 1] < env->str_off[i]) return set_err(KS_ERR_INVALID, "env block: string offsets not ascending");
-    if (env->n_strings && env->str_off[env->n_strings] > env->str_bytes_len) return set_err(KS_ERR_INVALID, "env block: string offsets reach beyond str_bytes_len");
-    ksh_pod_block strings{}; strings.n_strings = env->n_strings; strings.str_off = env->str_off; strings.str_bytes = env->str_bytes; strings.str_bytes_len = env->str_bytes_len;
+  return guarded([&] {
+    const auto t0 = clk::now();
+    const ksh_pod_block strings = string_table("env", env->n_strings, env->str_off, env->str_bytes, env->str_bytes_len);
     auto p = std::make_unique<Parsed>();
     p->pr = std::make_shared<const ksp::Problem>(ksp::EnvReader(strings, env->words, env->words + env->n_words).read_env());
-    if (ms) *ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (ms) *ms = ms_since(t0);
     *out = p.release(); return KS_OK;
-  } catch (const std::exception& e) { return set_err(KS_ERR_INVALID, e.what()); }
+  });
 }
 void ksh_parsed_free(void* p) { delete (Parsed*)p; }
 // ms[0..5]: flatten (host) | upload | static tables + feasibility grid | pack kernel (HIP events) | whole ks_solve_dev incl. read-back | total wall
 }  // extern "C"
 template <class ENC> static int solve_from(ENC&& make_encoded, int device, void** out_handle, double* ms) {
   if (out_handle) *out_handle = nullptr;
-  try {
-    using clk = std::chrono::steady_clock; auto now = [] { return clk::now(); }; auto since = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-    auto t0 = now();
-    auto h = std::make_unique<Handle>();
-    h->enc = make_encoded();
-    auto t0b = now();
-    h->rb = h->enc->make_result();
-    auto t1 = now();
-    if (getenv("KSH_TIMING")) fprintf(stderr, "  solve_from: encode %.2f ms, make_result %.2f ms\n", since(t0, t0b), since(t0b, t1));
-    int rc = ks_problem_upload(&h->enc->prob, device, &h->dev); if (rc != KS_OK) return set_err(rc, ks_last_error());
-    auto t2 = now();
-    float grid_ms = 0; rc = ks_feasibility_grid(h->dev, nullptr, &grid_ms); if (rc != KS_OK) return set_err(rc, ks_last_error());
-    auto t3 = now();
-    float kms = 0; rc = ks_solve_dev(h->dev, &h->rb->r, &kms); if (rc != KS_OK) return set_err(rc, ks_last_error());
+  return guarded([&] {
+    const auto t0 = clk::now();      // (every lap below is read off this one start: the parts add up to the total)
+    auto enc = make_encoded();
+    const double encoded = ms_since(t0);
+    std::unique_ptr<Handle> h(new_handle(std::move(enc)));
+    const double flat = ms_since(t0);
+    if (timing()) fprintf(stderr, "  solve_from: encode %.2f ms, make_result %.2f ms\n", encoded, flat - encoded);
+    int rc = dev_rc(ks_problem_upload(&h->enc->prob, device, &h->dev)); if (rc != KS_OK) return rc;
+    const double uploaded = ms_since(t0);
+    float grid_ms = 0; rc = dev_rc(ks_feasibility_grid(h->dev, nullptr, &grid_ms)); if (rc != KS_OK) return rc;
+    const double gridded = ms_since(t0);
+    float kms = 0; rc = dev_rc(ks_solve_dev(h->dev, &h->rb->r, &kms)); if (rc != KS_OK) return rc;
     h->solved = true; h->dev_result = true;
-    auto t4 = now();
-    if (ms) { ms[0] = since(t0, t1); ms[1] = since(t1, t2); ms[2] = since(t2, t3); ms[3] = kms; ms[4] = since(t3, t4); ms[5] = since(t0, t4); }
+    const double solved = ms_since(t0);
+    if (ms) { ms[0] = flat; ms[1] = uploaded - flat; ms[2] = gridded - uploaded; ms[3] = kms; ms[4] = solved - gridded; ms[5] = solved; }
     if (out_handle) *out_handle = h.release();
     return KS_OK;
-  } catch (const ksh::Unsupported& e) { return set_err(KS_ERR_UNSUPPORTED, e.what());
-  } catch (const std::exception& e) { return set_err(KS_ERR_INVALID, e.what()); }
+  });
 }
 extern "C" {
 int ksh_solve_from_pods(void* parsed, int device, uint32_t flags, void** out_handle, double* ms) {
@@ -150,12 +222,12 @@ struct Batch { std::shared_ptr<const ksp::PodBatch> b; };
 int ksh_pods_ingest(const ksh_pod_block* blocks, uint32_t n_blocks, void** out_batch, double* ms) {
   if (out_batch) *out_batch = nullptr;
   if (!out_batch || (n_blocks && !blocks)) return set_err(KS_ERR_INVALID, "null argument");
-  try {
-    auto t0 = std::chrono::steady_clock::now();
+  return guarded([&] {
+    const auto t0 = clk::now();
     auto b = std::make_unique<Batch>(); b->b = ksh::ingest_pod_blocks(blocks, n_blocks);
-    if (ms) *ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (ms) *ms = ms_since(t0);
     *out_batch = b.release(); return KS_OK;
-  } catch (const std::exception& e) { return set_err(KS_ERR_INVALID, e.what()); }
+  });
 }
 void ksh_pods_free(void* batch) { delete (Batch*)batch; }
 int ksh_pods_count(void* batch, uint32_t* n_pods, uint32_t* n_specs) {
@@ -172,32 +244,19 @@ int ksh_solve_from_batch(void* parsed_env, void* batch, int device, uint32_t fla
 int ksh_open_parsed(void* parsed, uint32_t flags, void** out) {
   if (out) *out = nullptr;
   if (!parsed || !out) return set_err(KS_ERR_INVALID, "null argument");
-  try {
-    auto h = std::make_unique<Handle>();
-    h->enc = ksh::encode(((Parsed*)parsed)->pr, flags, &((Parsed*)parsed)->env);
-    h->rb = h->enc->make_result();
-    *out = h.release(); return KS_OK;
-  } catch (const ksh::Unsupported& e) { return set_err(KS_ERR_UNSUPPORTED, e.what());
-  } catch (const std::exception& e) { return set_err(KS_ERR_INVALID, e.what()); }
+  return guarded([&] { *out = new_handle(ksh::encode(((Parsed*)parsed)->pr, flags, &((Parsed*)parsed)->env)); return KS_OK; });
 }
 int ksh_open_batch(void* parsed_env, void* batch, uint32_t flags, void** out) {
   if (out) *out = nullptr;
   if (!parsed_env || !batch || !out) return set_err(KS_ERR_INVALID, "null argument");
-  try {
-    auto h = std::make_unique<Handle>();
-    h->enc = ksh::encode(((Parsed*)parsed_env)->pr, ((Batch*)batch)->b, flags, &((Parsed*)parsed_env)->env);
-    h->rb = h->enc->make_result();
-    *out = h.release(); return KS_OK;
-  } catch (const ksh::Unsupported& e) { return set_err(KS_ERR_UNSUPPORTED, e.what());
-  } catch (const std::exception& e) { return set_err(KS_ERR_INVALID, e.what()); }
+  return guarded([&] { *out = new_handle(ksh::encode(((Parsed*)parsed_env)->pr, ((Batch*)batch)->b, flags, &((Parsed*)parsed_env)->env)); return KS_OK; });
 }
 // KSR1 text of the result a handle holds (after ksh_solve / ksh_solve_from_pods)
 int ksh_result_text(void* hv, char** out_text) {
   Handle* h = (Handle*)hv; if (out_text) *out_text = nullptr;
   if (!h || !out_text) return set_err(KS_ERR_INVALID, "null argument");
   if (!h->solved) return set_err(KS_ERR_INVALID, "the handle holds no result: solve it first (or the last solve failed)");
-  try { std::string s = decode_handle(h, 0.0); *out_text = strdup(s.c_str()); return KS_OK; }
-  catch (const std::exception& e) { return set_err(KS_ERR_INVALID, e.what()); }
+  return guarded([&] { std::string s = decode_handle(h, 0.0); *out_text = strdup(s.c_str()); return KS_OK; });
 }
 
 // Fixed-size record of the result a handle holds -- what consolidation reads of a simulation (consolidation.go:190-260):
@@ -221,90 +280,48 @@ int ksh_result_summary(void* hv, uint64_t* out, uint32_t words) {
 static int open_whatifs_over(std::shared_ptr<const ksp::Problem> snapshot, uint32_t flags, uint32_t n, const uint32_t* cand_off, const uint32_t* cand,
                              const int32_t* pod_node, uint32_t nthreads, void** out_handles, Parsed* cache = nullptr) {
   for (uint32_t w = 0; w < n; ++w) out_handles[w] = nullptr;
-  try {
+  return guarded([&] {
     for (uint32_t i = 0; i < cand_off[n]; ++i) if (cand[i] >= snapshot->nodes.size()) return set_err(KS_ERR_INVALID, "candidate node out of range");
     // the snapshot is flattened ONCE (catalogue, universes, templates, every state node's row); a what-if adds only what its candidate set decides
-    const bool timing = getenv("KSH_TIMING") != nullptr; auto t0 = std::chrono::steady_clock::now();
+    auto t0 = clk::now();
     std::shared_ptr<const ksh::SnapshotBase> sb;
-    if (cache) {
-      std::lock_guard<std::mutex> g(cache->mu);
-      pod_node = bindings_of(cache, pod_node); if (!pod_node && !snapshot->pods.empty()) return set_err(KS_ERR_INVALID, "no bindings (pod_node)");
-      const size_t np = snapshot->pods.size();
-      if (cache->sb && cache->sb_flags == flags && cache->sb_pod_node.size() == np && std::equal(pod_node, pod_node + np, cache->sb_pod_node.begin())) sb = cache->sb;
-      else { sb = ksh::make_snapshot_base(snapshot, pod_node, flags, cache->sb_flags == flags ? cache->sb.get() : nullptr); cache->sb = sb; cache->sb_flags = flags; cache->sb_pod_node.assign(pod_node, pod_node + np); }
-    } else { if (!pod_node && !snapshot->pods.empty()) return set_err(KS_ERR_INVALID, "no bindings (pod_node)"); sb = ksh::make_snapshot_base(snapshot, pod_node, flags); }
-    if (timing) { auto t1 = std::chrono::steady_clock::now(); fprintf(stderr, "  what-ifs: snapshot base %8.2f ms\n", std::chrono::duration<double, std::milli>(t1 - t0).count()); t0 = t1; }
+    if (cache) { std::lock_guard<std::mutex> g(cache->mu); sb = flattening_of(cache, pod_node, flags, true); }
+    else { if (!pod_node && !snapshot->pods.empty()) return set_err(KS_ERR_INVALID, "no bindings (pod_node)"); sb = ksh::make_snapshot_base(snapshot, pod_node, flags); }
+    if (timing()) { fprintf(stderr, "  what-ifs: snapshot base %8.2f ms\n", ms_since(t0)); t0 = clk::now(); }
     std::atomic<uint32_t> next{0}; std::atomic<int> rc{KS_OK}; std::vector<std::string> errs(n);
     auto work = [&]() {
       for (;;) {
         const uint32_t w = next.fetch_add(1); if (w >= n) return;
-        try {
-          auto h = std::make_unique<Handle>();
-          h->enc = ksh::encode_whatif(*sb, cand + cand_off[w], cand_off[w + 1] - cand_off[w], flags);
-          h->rb = h->enc->make_result();
-          out_handles[w] = h.release();
+        try { out_handles[w] = new_handle(ksh::encode_whatif(*sb, cand + cand_off[w], cand_off[w + 1] - cand_off[w], flags));
         } catch (const ksh::Unsupported& e) { errs[w] = e.what(); rc = KS_ERR_UNSUPPORTED;
         } catch (const std::exception& e) { errs[w] = e.what(); rc = KS_ERR_INVALID; }
       }
     };
-    const uint32_t nt = std::max(1u, std::min(nthreads ? nthreads : default_threads(), n));
+    const uint32_t nt = std::max(1u, std::min(nthreads ? nthreads : ksh::host_threads(), n));
     std::vector<std::thread> pool; for (uint32_t t = 1; t < nt; ++t) pool.emplace_back(work);
     work(); for (auto& t : pool) t.join();
-    if (timing) { auto t1 = std::chrono::steady_clock::now(); fprintf(stderr, "  what-ifs: %u flattened on %u threads %8.2f ms\n", n, nt, std::chrono::duration<double, std::milli>(t1 - t0).count()); }
+    if (timing()) fprintf(stderr, "  what-ifs: %u flattened on %u threads %8.2f ms\n", n, nt, ms_since(t0));
     if (rc != KS_OK) { std::string m; for (auto& e : errs) if (!e.empty()) { m = e; break; } for (uint32_t w = 0; w < n; ++w) { delete (Handle*)out_handles[w]; out_handles[w] = nullptr; } return set_err(rc, m); }
     return KS_OK;
-  } catch (const ksh::Unsupported& e) { return set_err(KS_ERR_UNSUPPORTED, e.what());
-  } catch (const std::exception& e) { return set_err(KS_ERR_INVALID, e.what()); }
+  });
 }
 int ksh_open_whatifs(const char* base_text, size_t len, uint32_t flags, uint32_t n, const uint32_t* cand_off, const uint32_t* cand,
                      const int32_t* pod_node, uint32_t nthreads, void** out_handles) {
-  try {
+  for (uint32_t w = 0; w < n; ++w) out_handles[w] = nullptr;
+  return guarded([&] {
     auto snapshot = std::make_shared<ksp::Problem>(ksp::Parser(base_text, len).parse());
     for (auto& nd : snapshot->nodes) nd.in_state = true;
     snapshot->simulation_mode = true;
     return open_whatifs_over(std::shared_ptr<const ksp::Problem>(snapshot), flags, n, cand_off, cand, pod_node, nthreads, out_handles);
-  } catch (const std::exception& e) { for (uint32_t w = 0; w < n; ++w) out_handles[w] = nullptr; return set_err(KS_ERR_INVALID, e.what()); }
+  });
 }
 // The same over a snapshot the caller already holds as objects (ksh_parse): every node of it is a state node, every pod a bound pod.
 int ksh_open_whatifs_parsed(void* parsed, uint32_t flags, uint32_t n, const uint32_t* cand_off, const uint32_t* cand, const int32_t* pod_node, uint32_t nthreads, void** out_handles) {
   return open_whatifs_over(((Parsed*)parsed)->pr, flags, n, cand_off, cand, pod_node, nthreads, out_handles, (Parsed*)parsed);
 }
 
-// FNV-1a over every array behind the handle's ks_problem: two construction routes produced the same flat problem iff equal.
-uint64_t ksh_fingerprint(void* hv) {
-  const ksh::Encoded& E = *((Handle*)hv)->enc; uint64_t h = 1469598103934665603ull;
-  auto mix = [&](const void* p, size_t bytes) { const unsigned char* c = (const unsigned char*)p; for (size_t i = 0; i < bytes; ++i) { h ^= c[i]; h *= 1099511628211ull; } };
-  auto vec = [&](const auto& v) { uint64_t n = v.size(); mix(&n, 8); if (n) mix(v.data(), n * sizeof(v[0])); };
-  auto rs = [&](const ksh::ReqSetsStore& r) { vec(r.present); vec(r.complement); vec(r.mask); vec(r.gt); vec(r.lt); vec(r.it_state); };
-  const ks_problem& p = E.prob; const uint32_t dims[16] = {p.P, p.C, p.T, p.M, p.E, p.K, p.R, p.G, p.GH, p.S, p.SC, p.max_new_nodes, p.flags, p.wellknown_mask, p.n_ct, p.n_topologies}; mix(dims, sizeof dims);
-  const ksh::Encoded& C = E.catalogue(); const ksh::Encoded& L = E.lattice();
-  vec(E.key_nvalues); vec(E.value_int); vec(C.it_present); vec(C.it_complement); vec(C.it_mask); vec(C.it_offer); vec(C.it_price); vec(C.it_alloc); vec(C.it_cap);
-  vec(L.its_inter); vec(L.its_fail); vec(L.its_nidne); vec(L.its_types); rs(E.tmpl); rs(E.en); rs(E.cls); rs(E.flt);
-  vec(E.tmpl_taints); vec(E.tmpl_types); vec(E.tmpl_daemon); vec(E.tmpl_remaining); vec(E.tmpl_daemon_present); vec(E.tmpl_limit_present);
-  vec(E.en_taints); vec(E.en_avail); vec(E.en_requests); vec(E.en_requests_present); vec(E.en_port_off);
-  vec(E.cls_hn_mode); vec(E.cls_hn_off); vec(E.hn_list); vec(E.cls_requests); vec(E.cls_requests_present); vec(E.cls_tolerated); vec(E.cls_port_off); vec(E.ports);
-  vec(E.en_vol_limit); vec(E.en_vol_count); vec(E.en_vol_set); vec(E.cls_vol_off); vec(E.vol_list);
-  vec(E.cls_own_off); vec(E.own_list); vec(E.cls_sel_off); vec(E.sel_list); vec(E.cls_isel_off); vec(E.isel_list); vec(E.cls_iown_off); vec(E.iown_list);
-  vec(E.pod_stage_off); vec(E.stage_cls); vec(E.queue); vec(E.grp_type); vec(E.grp_active); vec(E.grp_key); vec(E.grp_max_skew); vec(E.grp_count); vec(E.grp_hslot);
-  vec(E.grph_count); vec(E.grph_extra_pos); vec(E.grp_filter_off);
-  return h;
-}
+uint64_t ksh_fingerprint(void* hv) { return fingerprint_of(*((Handle*)hv)->enc); }
 
-}  // extern "C"
-// The snapshot's own flattening resident on `device` with its tables built (once per snapshot and device; shared by every what-if over it).
-static int resident_base(const ksh::Encoded* base, int device, std::shared_ptr<void>* out) {
-  std::lock_guard<std::mutex> g(base->dev_mu);
-  auto it = base->dev_resident.find(device);
-  if (it != base->dev_resident.end()) { *out = it->second; return KS_OK; }
-  ks_dev_problem* raw = nullptr;
-  int rc = ks_problem_upload(&base->prob, device, &raw);
-  if (rc == KS_OK) rc = ks_problem_prepare(raw);
-  if (rc != KS_OK) { if (raw) ks_problem_free(raw); return set_err(rc, ks_last_error()); }
-  *out = std::shared_ptr<void>(raw, [](void* p) { ks_problem_free((ks_dev_problem*)p); });
-  base->dev_resident[device] = *out;
-  return KS_OK;
-}
-extern "C" {
 // ---- the snapshot kept current by events instead of re-ingested (state.Cluster's UpdateNode / DeleteNode / UpdatePod / DeletePod, cluster.go) ----
 // The problem object is patched in place -- new nodes and pods are appended (the vectors were parsed with room: nothing moves), a node that is updated is replaced
 // in its slot (NODE=), an instance type likewise (IT=), what leaves stays as a tombstone
@@ -408,11 +425,10 @@ static int apply_events(Parsed* P, const int32_t* pod_node, std::vector<ksp::Del
 int ksh_env_apply(void* parsed, const int32_t* pod_node, const char* ksd_text, size_t len, uint32_t info[4]) {
   if (info) info[0] = info[1] = info[2] = info[3] = 0;
   if (!parsed || !ksd_text) return set_err(KS_ERR_INVALID, "null argument");
-  try {
+  return guarded([&] {
     std::vector<ksp::DeltaEvent> ev = ksp::Parser(ksd_text, len).parse_delta();
     return apply_events((Parsed*)parsed, pod_node, ev, false, info);
-  } catch (const ksh::Unsupported& e) { return set_err(KS_ERR_UNSUPPORTED, e.what());
-  } catch (const std::exception& e) { return set_err(KS_ERR_INVALID, e.what()); }
+  });
 }
 // The same events without the text (kshost.h ksh_delta_block; grammar in kspb.hpp DeltaReader).  The block is decoded COMPLETELY before the first event is applied:
 // a malformed block changes nothing, not even the hand-over of the bindings on a first call.
@@ -420,14 +436,11 @@ int ksh_env_apply_block(void* parsed, const int32_t* pod_node, const ksh_delta_b
   if (info) info[0] = info[1] = info[2] = info[3] = 0;
   if (!parsed || !d || !d->str_off || (!d->words && d->n_words) || (!d->str_bytes && d->n_strings)) return set_err(KS_ERR_INVALID, "null argument");
   if (flags & ~(uint32_t)KSH_APPLY_TRACK_CLUSTER_PODS) return set_err(KS_ERR_INVALID, "ksh_env_apply_block: unknown flag bit");
-  try {
-    for (uint32_t i = 0; i < d->n_strings; ++i) if (d->str_off[i + 1] < d->str_off[i]) return set_err(KS_ERR_INVALID, "delta block: string offsets not ascending");
-    if (d->n_strings && d->str_off[d->n_strings] > d->str_bytes_len) return set_err(KS_ERR_INVALID, "delta block: string offsets reach beyond str_bytes_len");
-    ksh_pod_block strings{}; strings.n_strings = d->n_strings; strings.str_off = d->str_off; strings.str_bytes = d->str_bytes; strings.str_bytes_len = d->str_bytes_len;
+  return guarded([&] {
+    const ksh_pod_block strings = string_table("delta", d->n_strings, d->str_off, d->str_bytes, d->str_bytes_len);
     std::vector<ksp::DeltaEvent> ev = ksp::DeltaReader(strings, d->words, d->words + d->n_words).read_delta(d->n_events);
     return apply_events((Parsed*)parsed, pod_node, ev, (flags & KSH_APPLY_TRACK_CLUSTER_PODS) != 0, info);
-  } catch (const ksh::Unsupported& e) { return set_err(KS_ERR_UNSUPPORTED, e.what());
-  } catch (const std::exception& e) { return set_err(KS_ERR_INVALID, e.what()); }
+  });
 }
 // the bindings the library holds after ksh_env_apply: out[0 .. n_pods) (cap entries at most); the sizes either way
 int ksh_snapshot_bindings(void* parsed, int32_t* out, uint32_t cap, uint32_t* n_pods, uint32_t* n_nodes) {
@@ -442,22 +455,14 @@ int ksh_snapshot_bindings(void* parsed, int32_t* out, uint32_t cap, uint32_t* n_
 // (tests: a continued flattening must equal it).  The snapshot must have been flattened (a what-if batch opened) or is flattened now.
 int ksh_snapshot_fingerprint(void* parsed, const int32_t* pod_node, uint32_t flags, int cold, uint64_t* out) {
   if (!parsed || !out) return set_err(KS_ERR_INVALID, "null argument");
-  try {
+  return guarded([&] {
     Parsed* P = (Parsed*)parsed; std::lock_guard<std::mutex> g(P->mu);
     const int32_t* pn = bindings_of(P, pod_node); if (!pn && !P->pr->pods.empty()) return set_err(KS_ERR_INVALID, "no bindings");
-    std::shared_ptr<const ksh::SnapshotBase> sb;
-    if (cold) sb = ksh::make_snapshot_base(P->pr, pn, flags);
-    else {
-      const size_t np = P->pr->pods.size();
-      if (!(P->sb && P->sb_flags == flags && P->sb_pod_node.size() == np && std::equal(pn, pn + np, P->sb_pod_node.begin()))) { P->sb = ksh::make_snapshot_base(P->pr, pn, flags); P->sb_flags = flags; P->sb_pod_node.assign(pn, pn + np); }
-      sb = P->sb;
-    }
-    const ksh::DeltaInputs in = ksh::delta_inputs(*sb);
-    uint64_t a; { Handle tmp; tmp.enc.reset(const_cast<ksh::Encoded*>(in.base.get())); a = ksh_fingerprint(&tmp); tmp.enc.release(); }
-    *out = a ^ (ksh::snapshot_fingerprint(*sb) * 0x9E3779B97F4A7C15ull);
+    // a flattening made here is never continued from the one kept: the tests compare what this call makes with a cold one
+    std::shared_ptr<const ksh::SnapshotBase> sb = cold ? ksh::make_snapshot_base(P->pr, pn, flags) : flattening_of(P, pn, flags, false);
+    *out = fingerprint_of(*ksh::delta_inputs(*sb).base) ^ (ksh::snapshot_fingerprint(*sb) * 0x9E3779B97F4A7C15ull);
     return KS_OK;
-  } catch (const ksh::Unsupported& e) { return set_err(KS_ERR_UNSUPPORTED, e.what());
-  } catch (const std::exception& e) { return set_err(KS_ERR_INVALID, e.what()); }
+  });
 }
 
 // What-ifs DERIVED on the device from the resident snapshot (include/ksolve.h ks_whatifs_open): no per-what-if flattening, an upload of KBs.
@@ -465,19 +470,16 @@ int ksh_snapshot_fingerprint(void* parsed, const int32_t* pod_node, uint32_t fla
 // snapshot's what-ifs do not differ by their candidate sets alone -- the caller then uses ksh_open_whatifs_parsed.
 int ksh_open_whatifs_derived(void* parsed, uint32_t flags, uint32_t n, const uint32_t* cand_off, const uint32_t* cand, const int32_t* pod_node, int device, void** out_handles) {
   for (uint32_t w = 0; w < n; ++w) out_handles[w] = nullptr;
-  try {
+  return guarded([&] {
     Parsed* P = (Parsed*)parsed; std::shared_ptr<const ksp::Problem> snapshot = P->pr;
     for (uint32_t i = 0; i < cand_off[n]; ++i) if (cand[i] >= snapshot->nodes.size()) return set_err(KS_ERR_INVALID, "candidate node out of range");
     if (flags & KS_FLAG_STATS) return set_err(KS_ERR_UNSUPPORTED, "derived what-ifs carry no reference-algorithm statistics");
-    std::shared_ptr<const ksh::SnapshotBase> sb;
-    { std::lock_guard<std::mutex> g(P->mu);
-      pod_node = bindings_of(P, pod_node); if (!pod_node && !snapshot->pods.empty()) return set_err(KS_ERR_INVALID, "no bindings (pod_node)");
-      const size_t np = snapshot->pods.size();
-      if (P->sb && P->sb_flags == flags && P->sb_pod_node.size() == np && std::equal(pod_node, pod_node + np, P->sb_pod_node.begin())) sb = P->sb;
-      else { auto ts = std::chrono::steady_clock::now(); sb = ksh::make_snapshot_base(snapshot, pod_node, flags, P->sb_flags == flags ? P->sb.get() : nullptr); P->sb = sb; P->sb_flags = flags; P->sb_pod_node.assign(pod_node, pod_node + np);
-             if (getenv("KSH_TIMING")) fprintf(stderr, "  derived what-ifs: %-28s %8.2f ms\n", "snapshot flattened (once)", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ts).count()); } }
-    const bool timing = getenv("KSH_TIMING") != nullptr; auto t0 = std::chrono::steady_clock::now();
-    auto lap = [&](const char* what) { if (!timing) return; auto t1 = std::chrono::steady_clock::now(); fprintf(stderr, "  derived what-ifs: %-28s %8.2f ms\n", what, std::chrono::duration<double, std::milli>(t1 - t0).count()); t0 = t1; };
+    const bool timed = timing(); auto t0 = clk::now();
+    auto lap = [&](const char* what) { if (!timed) return; fprintf(stderr, "  derived what-ifs: %-28s %8.2f ms\n", what, ms_since(t0)); t0 = clk::now(); };
+    std::shared_ptr<const ksh::SnapshotBase> sb; bool made = false;
+    { std::lock_guard<std::mutex> g(P->mu); sb = flattening_of(P, pod_node, flags, true, &made); }
+    if (made) lap("snapshot flattened (once)");
+    t0 = clk::now();
     const ksh::DeltaInputs in = ksh::delta_inputs(*sb);
     if (!in.eligible) return set_err(KS_ERR_UNSUPPORTED, "what-ifs of this snapshot cannot be derived on the device: " + in.why);
     auto D = std::make_shared<DeltaBatch>(); D->sb = sb; D->cand_off.assign(cand_off, cand_off + n + 1); D->cand.assign(cand, cand + cand_off[n]);
@@ -497,7 +499,7 @@ int ksh_open_whatifs_derived(void* parsed, uint32_t flags, uint32_t n, const uin
       ks_whatifs_options opt{}; opt.topo = in.topo; opt.flags = KS_WHATIFS_VOLUMES;
       rc = ks_whatifs_open_ex((const ks_dev_problem*)D->base_dev.get(), in.n_nodes, P->sb_pod_node.data(), in.node_row, n, cand_off, cand, npods.data(), rem.data(), &opt, &D->b);
     } else rc = ks_whatifs_open((const ks_dev_problem*)D->base_dev.get(), in.n_nodes, P->sb_pod_node.data(), in.node_row, n, cand_off, cand, npods.data(), rem.data(), in.topo, &D->b);
-    if (rc != KS_OK) return set_err(rc, ks_last_error());
+    if (rc != KS_OK) return dev_rc(rc);
     lap("ks_whatifs_open (device)");
     ks_dev_problem* const* views = ks_whatifs_problems(D->b);
     for (uint32_t w = 0; w < n; ++w) {
@@ -509,74 +511,59 @@ int ksh_open_whatifs_derived(void* parsed, uint32_t flags, uint32_t n, const uin
     }
     lap("handles");
     return KS_OK;
-  } catch (const ksh::Unsupported& e) { return set_err(KS_ERR_UNSUPPORTED, e.what());
-  } catch (const std::exception& e) { return set_err(KS_ERR_INVALID, e.what()); }
+  });
 }
 
 uint64_t ksh_whatifs_arena_bytes(void* hv) { const Handle* h = (const Handle*)hv; return h && h->delta ? ks_whatifs_arena_bytes(h->delta->b) : 0; }
 
 // CPU self-check of what ksh_open_whatifs_derived would derive on the device for ONE candidate set (kshost.h).
 int ksh_check_whatif_derivation(void* parsed, uint32_t flags, const uint32_t* cand, uint32_t ncand, const int32_t* pod_node) {
-  try {
-    Parsed* P = (Parsed*)parsed; std::shared_ptr<const ksp::Problem> snapshot = P->pr;
+  return guarded([&] {
+    Parsed* P = (Parsed*)parsed;
     std::shared_ptr<const ksh::SnapshotBase> sb;
-    { std::lock_guard<std::mutex> g(P->mu);
-      pod_node = bindings_of(P, pod_node); if (!pod_node && !snapshot->pods.empty()) return set_err(KS_ERR_INVALID, "no bindings (pod_node)");
-      const size_t np = snapshot->pods.size();
-      if (P->sb && P->sb_flags == flags && P->sb_pod_node.size() == np && std::equal(pod_node, pod_node + np, P->sb_pod_node.begin())) sb = P->sb;
-      else { sb = ksh::make_snapshot_base(snapshot, pod_node, flags, P->sb_flags == flags ? P->sb.get() : nullptr); P->sb = sb; P->sb_flags = flags; P->sb_pod_node.assign(pod_node, pod_node + np); } }
+    { std::lock_guard<std::mutex> g(P->mu); sb = flattening_of(P, pod_node, flags, true); }
     const std::string why = ksh::check_derived_topology(*sb, cand, ncand, flags);
     return why.empty() ? KS_OK : set_err(why.rfind("not derivable", 0) == 0 ? KS_ERR_UNSUPPORTED : KS_ERR_INVALID, why);
-  } catch (const ksh::Unsupported& e) { return set_err(KS_ERR_UNSUPPORTED, e.what());
-  } catch (const std::exception& e) { return set_err(KS_ERR_INVALID, e.what()); }
+  });
 }
 
 // Upload the flat problem to HBM (idempotent).
 int ksh_upload(void* hv, int device) {
-  Handle* h = (Handle*)hv;
-  if (h->dev) return ks_problem_device(h->dev) == device ? KS_OK : set_err(KS_ERR_INVALID, "problem already resident on another device");
-  int rc;
-  if (const ksh::Encoded* base = h->enc->shared.get()) {
+  return guarded([&] {
+    Handle* h = (Handle*)hv;
+    if (h->dev) return ks_problem_device(h->dev) == device ? KS_OK : set_err(KS_ERR_INVALID, "problem already resident on another device");
+    const ksh::Encoded* base = h->enc->shared.get();
+    if (!base) return dev_rc(ks_problem_upload(&h->enc->prob, device, &h->dev));
     // A what-if flattened over a shared snapshot: the snapshot's flattening goes to the device once (catalogue, prices, lattice, the tables
     // derived from them); the what-if then uploads only what its candidate set decides.
     std::shared_ptr<void> bd;
-    {
-      std::lock_guard<std::mutex> g(base->dev_mu);
-      auto it = base->dev_resident.find(device);
-      if (it != base->dev_resident.end()) bd = it->second;
-      else {
-        ks_dev_problem* raw = nullptr;
-        rc = ks_problem_upload(&base->prob, device, &raw);
-        if (rc == KS_OK) rc = ks_problem_prepare(raw);
-        if (rc != KS_OK) { if (raw) ks_problem_free(raw); return set_err(rc, ks_last_error()); }
-        bd = std::shared_ptr<void>(raw, [](void* p) { ks_problem_free((ks_dev_problem*)p); });
-        base->dev_resident[device] = bd;
-      }
-    }
+    int rc = resident_base(base, device, &bd); if (rc != KS_OK) return rc;
     rc = ks_problem_upload_shared(&h->enc->prob, (const ks_dev_problem*)bd.get(), &h->dev);
     if (rc == KS_OK) h->base_dev = bd;
-  } else rc = ks_problem_upload(&h->enc->prob, device, &h->dev);
-  if (rc != KS_OK) return set_err(rc, ks_last_error());
-  return KS_OK;
+    return dev_rc(rc);
+  });
 }
 
 // Upload a batch (what-ifs of one snapshot) on host threads: the per-problem cost is packing its arrays into the pinned staging buffer.
 int ksh_upload_batch(void** handles, uint32_t n, int device, uint32_t nthreads) {
   if (!n) return KS_OK;
   int rc0 = ksh_upload(handles[0], device); if (rc0 != KS_OK) return rc0;      // the first one also makes the snapshot resident (once)
-  std::atomic<uint32_t> next{1}; std::atomic<int> rc{KS_OK}; std::mutex emu; std::string emsg;
-  auto work = [&]() {
-    for (;;) {
-      const uint32_t i = next.fetch_add(1); if (i >= n) return;
-      const int r = ksh_upload(handles[i], device);
-      if (r != KS_OK) { rc = r; std::lock_guard<std::mutex> g(emu); if (emsg.empty()) emsg = g_err; }
-    }
-  };
-  const uint32_t nt = std::max(1u, std::min(nthreads ? nthreads : default_threads(), n - 1));
-  std::vector<std::thread> pool; for (uint32_t t = 1; t < nt; ++t) pool.emplace_back(work);
-  work(); for (auto& t : pool) t.join();
-  if (rc != KS_OK) return set_err(rc, emsg);
-  return KS_OK;
+  return guarded([&] {
+    std::atomic<uint32_t> next{1}; std::atomic<int> rc{KS_OK}; std::mutex emu; std::string emsg;
+    auto work = [&]() {
+      for (;;) {
+        const uint32_t i = next.fetch_add(1); if (i >= n) return;
+        try {      // (nothing may leave a worker thread; ksh_upload catches its own, keeping the message is what can still throw)
+          const int r = ksh_upload(handles[i], device);
+          if (r != KS_OK) { rc = r; std::lock_guard<std::mutex> g(emu); if (emsg.empty()) emsg = g_err; }
+        } catch (const std::exception&) { rc = KS_ERR_INVALID; }
+      }
+    };
+    const uint32_t nt = std::max(1u, std::min(nthreads ? nthreads : ksh::host_threads(), n - 1));
+    std::vector<std::thread> pool; for (uint32_t t = 1; t < nt; ++t) pool.emplace_back(work);
+    work(); for (auto& t : pool) t.join();
+    return rc != KS_OK ? set_err(rc, emsg) : KS_OK;
+  });
 }
 // The fixed-size records of a batch in one call: out[i*(2+words) ..] as ksh_result_summary.
 int ksh_result_summaries(void** handles, uint32_t n, uint64_t* out, uint32_t words) {
@@ -586,87 +573,90 @@ int ksh_result_summaries(void** handles, uint32_t n, uint64_t* out, uint32_t wor
 
 // Solve (device-resident inputs).  out_text may be NULL (skip decode).
 int ksh_solve(void* hv, char** out_text, float* kernel_ms, double* wall_ms) {
-  Handle* h = (Handle*)hv;
-  int rc = h->dev ? KS_OK : ksh_upload(hv, ks_current_device()); if (rc != KS_OK) return rc;      // not uploaded yet: the calling thread's current HIP device
-  auto t0 = std::chrono::steady_clock::now();
-  h->solved = false; h->dev_result = false;
-  if (!h->rb) h->rb = h->enc->make_result();
-  rc = ks_solve_dev(h->dev, &h->rb->r, kernel_ms);
-  double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  if (wall_ms) *wall_ms = dt * 1e3;
-  if (rc != KS_OK) return set_err(rc, ks_last_error());
-  h->solved = true; h->dev_result = true;
-  try { if (out_text) { std::string s = decode_handle(h, dt); *out_text = strdup(s.c_str()); } }
-  catch (const std::exception& e) { return set_err(KS_ERR_INVALID, e.what()); }
-  return KS_OK;
+  return guarded([&] {
+    Handle* h = (Handle*)hv;
+    int rc = ensure_resident(h); if (rc != KS_OK) return rc;
+    const auto t0 = clk::now();
+    h->solved = false; h->dev_result = false;
+    if (!h->rb) h->rb = h->enc->make_result();
+    rc = ks_solve_dev(h->dev, &h->rb->r, kernel_ms);
+    const double dt = std::chrono::duration<double>(clk::now() - t0).count();      // (seconds: what the KSR1 text carries)
+    if (wall_ms) *wall_ms = dt * 1e3;
+    if (rc != KS_OK) return dev_rc(rc);
+    h->solved = true; h->dev_result = true;
+    if (out_text) { std::string s = decode_handle(h, dt); *out_text = strdup(s.c_str()); }
+    return KS_OK;
+  });
 }
 
 // N independent problems in one launch (consolidation what-ifs, deprovisioning/helpers.go:42-115).
 int ksh_solve_batch(void** hv, uint32_t n, char** out_texts, float* kernel_ms, double* wall_ms) {
-  std::vector<ks_dev_problem*> ds(n); std::vector<ks_result*> rs(n);
-  const int dev = ks_current_device();
-  for (uint32_t i = 0; i < n; ++i) { Handle* h = (Handle*)hv[i]; if (!h->rb) h->rb = h->enc->make_result(); }      // (derived what-ifs allocate their result buffers on first use)
-  for (uint32_t i = 0; i < n; ++i) { int rc = ((Handle*)hv[i])->dev ? KS_OK : ksh_upload(hv[i], dev); if (rc != KS_OK) return rc; ds[i] = ((Handle*)hv[i])->dev; rs[i] = &((Handle*)hv[i])->rb->r; }
-  auto t0 = std::chrono::steady_clock::now();
-  for (uint32_t i = 0; i < n; ++i) { ((Handle*)hv[i])->solved = false; ((Handle*)hv[i])->dev_result = false; }
-  int rc = ks_solve_batch_dev(ds.data(), n, rs.data(), kernel_ms);
-  double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  if (wall_ms) *wall_ms = dt * 1e3;
-  if (rc != KS_OK) return set_err(rc, ks_last_error());
-  for (uint32_t i = 0; i < n; ++i) { ((Handle*)hv[i])->solved = true; ((Handle*)hv[i])->dev_result = true; }
-  try { if (out_texts) for (uint32_t i = 0; i < n; ++i) { std::string s = decode_handle((Handle*)hv[i], dt); out_texts[i] = strdup(s.c_str()); } }
-  catch (const std::exception& e) { return set_err(KS_ERR_INVALID, e.what()); }
-  return KS_OK;
+  return guarded([&] {
+    std::vector<ks_dev_problem*> ds(n); std::vector<ks_result*> rs(n);
+    for (uint32_t i = 0; i < n; ++i) { Handle* h = (Handle*)hv[i]; if (!h->rb) h->rb = h->enc->make_result(); }      // (derived what-ifs allocate their result buffers on first use)
+    for (uint32_t i = 0; i < n; ++i) { Handle* h = (Handle*)hv[i]; int rc = ensure_resident(h); if (rc != KS_OK) return rc; ds[i] = h->dev; rs[i] = &h->rb->r; }
+    const auto t0 = clk::now();
+    for (uint32_t i = 0; i < n; ++i) { ((Handle*)hv[i])->solved = false; ((Handle*)hv[i])->dev_result = false; }
+    int rc = ks_solve_batch_dev(ds.data(), n, rs.data(), kernel_ms);
+    const double dt = std::chrono::duration<double>(clk::now() - t0).count();
+    if (wall_ms) *wall_ms = dt * 1e3;
+    if (rc != KS_OK) return dev_rc(rc);
+    for (uint32_t i = 0; i < n; ++i) { ((Handle*)hv[i])->solved = true; ((Handle*)hv[i])->dev_result = true; }
+    if (out_texts) for (uint32_t i = 0; i < n; ++i) { std::string s = decode_handle((Handle*)hv[i], dt); out_texts[i] = strdup(s.c_str()); }
+    return KS_OK;
+  });
 }
 
 // The same launch with the results left on the device (no read-back but the error words), and the fixed-size records of the batch built there
 // into a caller-owned DEVICE buffer [n][3 + words] of uint64 -- [ids[i], n_new, n_unscheduled, new node 0's InstanceTypeOptions] -- which a
 // fan-out hands to its one all-gather as is (multinodeconsolidation.go:74-114: many candidate sets, one decision record each).
 int ksh_solve_batch_resident(void** hv, uint32_t n, float* kernel_ms, double* wall_ms) {
-  std::vector<ks_dev_problem*> ds(n);
-  const int dev = ks_current_device();
-  for (uint32_t i = 0; i < n; ++i) { int rc = ((Handle*)hv[i])->dev ? KS_OK : ksh_upload(hv[i], dev); if (rc != KS_OK) return rc; ds[i] = ((Handle*)hv[i])->dev; }
-  auto t0 = std::chrono::steady_clock::now();
-  for (uint32_t i = 0; i < n; ++i) { ((Handle*)hv[i])->solved = false; ((Handle*)hv[i])->dev_result = false; }
-  int rc = ks_solve_batch_dev(ds.data(), n, nullptr, kernel_ms);
-  if (wall_ms) *wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  if (rc != KS_OK) return set_err(rc, ks_last_error());
-  for (uint32_t i = 0; i < n; ++i) ((Handle*)hv[i])->dev_result = true;
-  return KS_OK;
+  return guarded([&] {
+    std::vector<ks_dev_problem*> ds(n);
+    for (uint32_t i = 0; i < n; ++i) { Handle* h = (Handle*)hv[i]; int rc = ensure_resident(h); if (rc != KS_OK) return rc; ds[i] = h->dev; }
+    const auto t0 = clk::now();
+    for (uint32_t i = 0; i < n; ++i) { ((Handle*)hv[i])->solved = false; ((Handle*)hv[i])->dev_result = false; }
+    int rc = ks_solve_batch_dev(ds.data(), n, nullptr, kernel_ms);
+    if (wall_ms) *wall_ms = ms_since(t0);
+    if (rc != KS_OK) return dev_rc(rc);
+    for (uint32_t i = 0; i < n; ++i) ((Handle*)hv[i])->dev_result = true;
+    return KS_OK;
+  });
 }
 int ksh_result_records_dev(void** hv, uint32_t n, const uint64_t* ids, uint32_t words, void* d_out) {
-  std::vector<ks_dev_problem*> ds(n);
-  for (uint32_t i = 0; i < n; ++i) { Handle* h = (Handle*)hv[i]; if (!h->dev || !h->dev_result) return set_err(KS_ERR_INVALID, "records before solve"); ds[i] = h->dev; }
-  int rc = ks_batch_records_dev(ds.data(), n, ids, words, d_out);
-  if (rc != KS_OK) return set_err(rc, ks_last_error());
-  return KS_OK;
+  return guarded([&] {
+    std::vector<ks_dev_problem*> ds;
+    int rc = device_problems(hv, n, true, "records before solve", ds); if (rc != KS_OK) return rc;
+    return dev_rc(ks_batch_records_dev(ds.data(), n, ids, words, d_out));
+  });
 }
 
 // Consolidation price stage on the results of the last ksh_solve / ksh_solve_batch, which are still on the device:
 // for handle i, of new node node[i]'s InstanceTypeOptions keep the types whose worst launch price is < max_price[i]
 // (filterByPrice, deprovisioning/helpers.go:148-157).  out_masks: n * ceil(T_max/64) words with row stride `stride_words`.
 int ksh_price_filter(void** hv, uint32_t n, const uint32_t* node, const double* max_price, const uint32_t* spot_only, uint64_t* out_masks, uint32_t stride_words, uint32_t* out_counts) {
-  std::vector<ks_dev_problem*> ds(n); std::vector<uint64_t*> outs(n);
-  for (uint32_t i = 0; i < n; ++i) {
-    Handle* h = (Handle*)hv[i]; if (!h->dev || !h->dev_result) return set_err(KS_ERR_INVALID, "price filter before solve");
-    if ((h->enc->prob.T + 63) / 64 > stride_words) return set_err(KS_ERR_INVALID, "mask row too short");
-    ds[i] = h->dev; outs[i] = out_masks + (size_t)i * stride_words;
-  }
-  int rc = ks_price_filter_dev(ds.data(), n, node, max_price, spot_only, outs.data(), out_counts);
-  if (rc != KS_OK) return set_err(rc, ks_last_error());
-  return KS_OK;
+  return guarded([&] {
+    std::vector<ks_dev_problem*> ds; std::vector<uint64_t*> outs(n);
+    int rc = device_problems(hv, n, true, "price filter before solve", ds); if (rc != KS_OK) return rc;
+    for (uint32_t i = 0; i < n; ++i) {
+      if ((((Handle*)hv[i])->enc->prob.T + 63) / 64 > stride_words) return set_err(KS_ERR_INVALID, "mask row too short");
+      outs[i] = out_masks + (size_t)i * stride_words;
+    }
+    return dev_rc(ks_price_filter_dev(ds.data(), n, node, max_price, spot_only, outs.data(), out_counts));
+  });
 }
 
 // Launch-time pick of the in-memory provider (fake/cloudprovider.go:79-84) and instanceTypesAreSubset (helpers.go:118-122) on results that are
 // still on the device.  launch pick: out_type = instance-type index (into the problem's catalogue) or -1, out_zone / out_ct = value ids in the zone /
 // capacity-type universes (ksh_key_value resolves them), out_price.
 int ksh_launch_pick(void** hv, uint32_t n, const uint32_t* node, int32_t* out_type, int32_t* out_zone, int32_t* out_ct, double* out_price) {
-  std::vector<ks_dev_problem*> ds(n); std::vector<int32_t> pair(n);
-  for (uint32_t i = 0; i < n; ++i) { Handle* h = (Handle*)hv[i]; if (!h->dev || !h->dev_result) return set_err(KS_ERR_INVALID, "launch pick before solve"); ds[i] = h->dev; }
-  int rc = ks_launch_pick_dev(ds.data(), n, node, out_type, pair.data(), out_price);
-  if (rc != KS_OK) return set_err(rc, ks_last_error());
-  for (uint32_t i = 0; i < n; ++i) { const uint32_t nct = ((Handle*)hv[i])->enc->prob.n_ct; out_zone[i] = pair[i] < 0 ? -1 : pair[i] / (int32_t)nct; out_ct[i] = pair[i] < 0 ? -1 : pair[i] % (int32_t)nct; }
-  return KS_OK;
+  return guarded([&] {
+    std::vector<ks_dev_problem*> ds; std::vector<int32_t> pair(n);
+    int rc = device_problems(hv, n, true, "launch pick before solve", ds); if (rc != KS_OK) return rc;
+    rc = dev_rc(ks_launch_pick_dev(ds.data(), n, node, out_type, pair.data(), out_price)); if (rc != KS_OK) return rc;
+    for (uint32_t i = 0; i < n; ++i) { const uint32_t nct = ((Handle*)hv[i])->enc->prob.n_ct; out_zone[i] = pair[i] < 0 ? -1 : pair[i] / (int32_t)nct; out_ct[i] = pair[i] < 0 ? -1 : pair[i] % (int32_t)nct; }
+    return KS_OK;
+  });
 }
 // value `v` of the zone (which = 0) or capacity-type (which = 1) universe of the handle's problem; NULL when out of range (owned by the handle)
 const char* ksh_key_value(void* hv, int which, int32_t v) {
@@ -675,41 +665,33 @@ const char* ksh_key_value(void* hv, int which, int32_t v) {
   return E.key_values[k][v].c_str();
 }
 int ksh_types_subset(void** hv, uint32_t n, const uint32_t* node, const uint64_t* lhs, uint32_t stride_words, uint32_t* out) {
-  std::vector<ks_dev_problem*> ds(n);
-  for (uint32_t i = 0; i < n; ++i) { Handle* h = (Handle*)hv[i]; if (!h->dev || !h->dev_result) return set_err(KS_ERR_INVALID, "subset test before solve"); ds[i] = h->dev; }
-  int rc = ks_types_subset_dev(ds.data(), n, node, lhs, stride_words, out);
-  if (rc != KS_OK) return set_err(rc, ks_last_error());
-  return KS_OK;
+  return guarded([&] {
+    std::vector<ks_dev_problem*> ds;
+    int rc = device_problems(hv, n, true, "subset test before solve", ds); if (rc != KS_OK) return rc;
+    return dev_rc(ks_types_subset_dev(ds.data(), n, node, lhs, stride_words, out));
+  });
 }
 
 // Static feasibility grid [M][C][TW]; `out` may be NULL (timing only).
 int ksh_grid(void* hv, uint64_t* out, float* kernel_ms) {
-  Handle* h = (Handle*)hv; int rc = h->dev ? KS_OK : ksh_upload(hv, ks_current_device()); if (rc != KS_OK) return rc;
-  rc = ks_feasibility_grid(h->dev, out, kernel_ms);
-  if (rc != KS_OK) return set_err(rc, ks_last_error());
-  return KS_OK;
+  Handle* h = (Handle*)hv; int rc = ensure_resident(h); if (rc != KS_OK) return rc;
+  return dev_rc(ks_feasibility_grid(h->dev, out, kernel_ms));
 }
 
 // The grid's rows split over GPUs: a range of rows computed on the handle's device / rows computed elsewhere installed.
 int ksh_grid_rows(void* hv, uint32_t row_lo, uint32_t row_hi, uint64_t* out_rows, void* out_rows_dev, float* kernel_ms) {
-  Handle* h = (Handle*)hv; int rc = h->dev ? KS_OK : ksh_upload(hv, ks_current_device()); if (rc != KS_OK) return rc;
-  rc = ks_feasibility_grid_rows(h->dev, row_lo, row_hi, out_rows, out_rows_dev, kernel_ms);
-  if (rc != KS_OK) return set_err(rc, ks_last_error());
-  return KS_OK;
+  Handle* h = (Handle*)hv; int rc = ensure_resident(h); if (rc != KS_OK) return rc;
+  return dev_rc(ks_feasibility_grid_rows(h->dev, row_lo, row_hi, out_rows, out_rows_dev, kernel_ms));
 }
 int ksh_grid_install(void* hv, uint32_t row_lo, uint32_t row_hi, const uint64_t* rows, const void* rows_dev, int complete) {
-  Handle* h = (Handle*)hv; int rc = h->dev ? KS_OK : ksh_upload(hv, ks_current_device()); if (rc != KS_OK) return rc;
-  rc = ks_feasibility_grid_install(h->dev, row_lo, row_hi, rows, rows_dev, complete);
-  if (rc != KS_OK) return set_err(rc, ks_last_error());
-  return KS_OK;
+  Handle* h = (Handle*)hv; int rc = ensure_resident(h); if (rc != KS_OK) return rc;
+  return dev_rc(ks_feasibility_grid_install(h->dev, row_lo, row_hi, rows, rows_dev, complete));
 }
 
 // Diagnostics: the grid as the last build left it (nothing launched), and the class row of every pod as submitted (stage 0 of its relaxation chain).
 int ksh_debug_grid(void* hv, uint64_t* out) {
   Handle* h = (Handle*)hv; if (!h || !h->dev) return set_err(KS_ERR_INVALID, "grid of a handle that was not uploaded");
-  const int rc = ks_debug_grid(h->dev, out);
-  if (rc != KS_OK) return set_err(rc, ks_last_error());
-  return KS_OK;
+  return dev_rc(ks_debug_grid(h->dev, out));
 }
 int ksh_debug_pod_classes(void* hv, uint32_t* out) {
   Handle* h = (Handle*)hv; if (!h || !out) return set_err(KS_ERR_INVALID, "null argument");
@@ -741,24 +723,26 @@ int ksh_result_arrays_get(void* hv, ksh_result_arrays* out) {
   if (!h || !out) return set_err(KS_ERR_INVALID, "null argument");
   if (!h->solved || !h->rb) return set_err(KS_ERR_INVALID, "result arrays before a solve");
   if (h->delta) return set_err(KS_ERR_UNSUPPORTED, "a what-if derived on the device numbers its pods in the snapshot's queue order: read it through ksh_result_text / ksh_result_summaries");
-  const ks_problem& p = h->enc->prob; const ks_result& r = h->rb->r;
-  const uint32_t nn = p.E + r.n_new;
-  h->csr_off.assign((size_t)nn + 1, 0);
-  uint32_t placed = 0;
-  for (uint32_t i = 0; i < p.P; ++i) if (r.pod_node[i] >= 0) { h->csr_off[(size_t)r.pod_node[i] + 1]++; ++placed; }
-  for (uint32_t n = 0; n < nn; ++n) h->csr_off[n + 1] += h->csr_off[n];
-  // commit order within a node = ascending commit number; the numbers are unique over the Solve, so one pass in that order fills every node's list in place
-  std::vector<int32_t> by_seq(placed, -1);
-  for (uint32_t i = 0; i < p.P; ++i) if (r.pod_node[i] >= 0) { const int32_t sq = r.pod_seq[i]; if (sq < 0 || (uint32_t)sq >= placed || by_seq[sq] >= 0) return set_err(KS_ERR_INTERNAL, "commit numbers are not a permutation"); by_seq[sq] = (int32_t)i; }
-  h->csr_pods.assign(placed, -1);
-  { std::vector<uint32_t> fill(h->csr_off.begin(), h->csr_off.end() - 1); for (uint32_t sq = 0; sq < placed; ++sq) { const int32_t i = by_seq[sq]; h->csr_pods[fill[r.pod_node[i]]++] = i; } }
-  memset(out, 0, sizeof *out);
-  out->n_pods = p.P; out->n_existing = p.E; out->n_new = r.n_new; out->n_unscheduled = r.n_unscheduled; out->types_words = (p.T + 63) / 64; out->n_resources = p.R; out->n_keys = p.K;
-  out->pod_node = r.pod_node; out->pod_stage = r.pod_stage; out->pod_reason = r.pod_reason; out->unscheduled = r.unscheduled;
-  out->node_pods_off = h->csr_off.data(); out->node_pods = h->csr_pods.data();
-  out->node_tmpl = r.node_tmpl; out->node_types = r.node_types; out->node_requests = r.node_requests; out->node_requests_present = r.node_requests_present;
-  out->node_present = r.node_present; out->node_complement = r.node_complement; out->node_mask = r.node_mask; out->node_gt = r.node_gt; out->node_lt = r.node_lt; out->node_it_state = r.node_it_state;
-  return KS_OK;
+  return guarded([&] {
+    const ks_problem& p = h->enc->prob; const ks_result& r = h->rb->r;
+    const uint32_t nn = p.E + r.n_new;
+    h->csr_off.assign((size_t)nn + 1, 0);
+    uint32_t placed = 0;
+    for (uint32_t i = 0; i < p.P; ++i) if (r.pod_node[i] >= 0) { h->csr_off[(size_t)r.pod_node[i] + 1]++; ++placed; }
+    for (uint32_t n = 0; n < nn; ++n) h->csr_off[n + 1] += h->csr_off[n];
+    // commit order within a node = ascending commit number; the numbers are unique over the Solve, so one pass in that order fills every node's list in place
+    std::vector<int32_t> by_seq(placed, -1);
+    for (uint32_t i = 0; i < p.P; ++i) if (r.pod_node[i] >= 0) { const int32_t sq = r.pod_seq[i]; if (sq < 0 || (uint32_t)sq >= placed || by_seq[sq] >= 0) return set_err(KS_ERR_INTERNAL, "commit numbers are not a permutation"); by_seq[sq] = (int32_t)i; }
+    h->csr_pods.assign(placed, -1);
+    { std::vector<uint32_t> fill(h->csr_off.begin(), h->csr_off.end() - 1); for (uint32_t sq = 0; sq < placed; ++sq) { const int32_t i = by_seq[sq]; h->csr_pods[fill[r.pod_node[i]]++] = i; } }
+    memset(out, 0, sizeof *out);
+    out->n_pods = p.P; out->n_existing = p.E; out->n_new = r.n_new; out->n_unscheduled = r.n_unscheduled; out->types_words = (p.T + 63) / 64; out->n_resources = p.R; out->n_keys = p.K;
+    out->pod_node = r.pod_node; out->pod_stage = r.pod_stage; out->pod_reason = r.pod_reason; out->unscheduled = r.unscheduled;
+    out->node_pods_off = h->csr_off.data(); out->node_pods = h->csr_pods.data();
+    out->node_tmpl = r.node_tmpl; out->node_types = r.node_types; out->node_requests = r.node_requests; out->node_requests_present = r.node_requests_present;
+    out->node_present = r.node_present; out->node_complement = r.node_complement; out->node_mask = r.node_mask; out->node_gt = r.node_gt; out->node_lt = r.node_lt; out->node_it_state = r.node_it_state;
+    return KS_OK;
+  });
 }
 // the names behind the arrays: requirement key k, its interned value v (a value class names its first member; ksh_result_text lists every member), resource r;
 // NULL when out of range (owned by the handle)
@@ -773,35 +757,37 @@ const char* ksh_name(void* hv, int what /* 0 key, 1 value of key a, 2 resource *
 // ids[] names each handle's what-if; out_rows[n][3 + words] comes back ordered by id.
 int ksh_solve_whatifs_sharded(void** hv, const uint32_t* shard_off, uint32_t nshards, const uint64_t* ids, uint32_t words, uint64_t* out_rows, float* kernel_ms_max) {
   if (!hv || !shard_off || !ids || !out_rows) return set_err(KS_ERR_INVALID, "null argument");
-  const uint32_t n = shard_off[nshards];
-  std::vector<ks_dev_problem*> ds(n);
-  for (uint32_t i = 0; i < n; ++i) { Handle* h = (Handle*)hv[i]; if (!h->dev) return set_err(KS_ERR_INVALID, "a what-if that is not resident (ksh_upload / ksh_upload_batch / ksh_open_whatifs_derived first)"); ds[i] = h->dev; h->solved = false; h->dev_result = false; }
-  std::vector<ks_dev_problem* const*> sp(nshards); std::vector<uint32_t> sn(nshards); std::vector<const uint64_t*> si(nshards);
-  for (uint32_t s = 0; s < nshards; ++s) { sp[s] = ds.data() + shard_off[s]; sn[s] = shard_off[s + 1] - shard_off[s]; si[s] = ids + shard_off[s]; }
-  int rc = ks_solve_batch_sharded(sp.data(), sn.data(), si.data(), nshards, words, out_rows, kernel_ms_max);
-  if (rc != KS_OK) return set_err(rc, ks_last_error());
-  for (uint32_t i = 0; i < n; ++i) ((Handle*)hv[i])->dev_result = true;
-  return KS_OK;
+  return guarded([&] {
+    const uint32_t n = shard_off[nshards];
+    std::vector<ks_dev_problem*> ds;
+    int rc = device_problems(hv, n, false, "a what-if that is not resident (ksh_upload / ksh_upload_batch / ksh_open_whatifs_derived first)", ds); if (rc != KS_OK) return rc;
+    for (uint32_t i = 0; i < n; ++i) { ((Handle*)hv[i])->solved = false; ((Handle*)hv[i])->dev_result = false; }
+    std::vector<ks_dev_problem* const*> sp(nshards); std::vector<uint32_t> sn(nshards); std::vector<const uint64_t*> si(nshards);
+    for (uint32_t s = 0; s < nshards; ++s) { sp[s] = ds.data() + shard_off[s]; sn[s] = shard_off[s + 1] - shard_off[s]; si[s] = ids + shard_off[s]; }
+    rc = dev_rc(ks_solve_batch_sharded(sp.data(), sn.data(), si.data(), nshards, words, out_rows, kernel_ms_max)); if (rc != KS_OK) return rc;
+    for (uint32_t i = 0; i < n; ++i) ((Handle*)hv[i])->dev_result = true;
+    return KS_OK;
+  });
 }
 
 // ---- consolidation commands (kshost.h): computeConsolidation / firstNNodeConsolidationOption / SingleNodeConsolidation.ComputeCommand over a snapshot ----
 // The rows of handles that hold a result on the device (any route: derived, flattened one by one, a plain Solve): ks_consolidation_commands_host for handles.
 int ksh_command_rows(void** hv, uint32_t n, const uint64_t* ids, const ks_command_inputs* in, uint32_t words, uint64_t* out_rows, double* ms) {
   if (n && !hv) return set_err(KS_ERR_INVALID, "null argument");
-  std::vector<ks_dev_problem*> ds(n);
-  for (uint32_t i = 0; i < n; ++i) { Handle* h = (Handle*)hv[i]; if (!h || !h->dev || !h->dev_result) return set_err(KS_ERR_INVALID, "command rows before solve"); ds[i] = h->dev; }
-  int rc = ks_consolidation_commands_host(ds.data(), n, ids, in, words, out_rows, ms);
-  if (rc != KS_OK) return set_err(rc, ks_last_error());
-  return KS_OK;
+  return guarded([&] {
+    std::vector<ks_dev_problem*> ds;
+    int rc = device_problems(hv, n, true, "command rows before solve", ds); if (rc != KS_OK) return rc;
+    return dev_rc(ks_consolidation_commands_host(ds.data(), n, ids, in, words, out_rows, ms));
+  });
 }
 // The two tables of handles that hold a result on the device: ks_replacement_commands_host for handles.
 int ksh_replacement_rows(void** hv, uint32_t n, const uint64_t* ids, const uint32_t* flags, uint32_t words, uint64_t* out_heads, uint64_t* out_nodes, uint64_t cap_nodes, uint64_t* out_total_nodes, double* ms) {
   if (n && !hv) return set_err(KS_ERR_INVALID, "null argument");
-  std::vector<ks_dev_problem*> ds(n);
-  for (uint32_t i = 0; i < n; ++i) { Handle* h = (Handle*)hv[i]; if (!h || !h->dev || !h->dev_result) return set_err(KS_ERR_INVALID, "replacement rows before solve"); ds[i] = h->dev; }
-  int rc = ks_replacement_commands_host(ds.data(), n, ids, flags, words, out_heads, out_nodes, cap_nodes, out_total_nodes, ms);
-  if (rc != KS_OK) return set_err(rc, ks_last_error());
-  return KS_OK;
+  return guarded([&] {
+    std::vector<ks_dev_problem*> ds;
+    int rc = device_problems(hv, n, true, "replacement rows before solve", ds); if (rc != KS_OK) return rc;
+    return dev_rc(ks_replacement_commands_host(ds.data(), n, ids, flags, words, out_heads, out_nodes, cap_nodes, out_total_nodes, ms));
+  });
 }
 }  // extern "C"
 // What getNodePrices / filterOutSameType / simulateScheduling's readiness rule read of the snapshot's nodes, once per call
@@ -872,7 +858,6 @@ struct SimBatch {
   uint32_t size() const { return (uint32_t)off2.size() - 1; }
   // ms[0] open, ms[1] solve.  `rows_name_it_states`: the rows to come carry instance-type requirement states, read through the snapshot's lattice
   int open_and_solve(uint32_t flags, const int32_t* pod_node, int device, bool rows_name_it_states, double* ms) {
-    using clk = std::chrono::steady_clock; auto since = [](clk::time_point a) { return std::chrono::duration<double, std::milli>(clk::now() - a).count(); };
     const uint32_t m = size(); hs.assign(m, nullptr);
     if (cand2.empty()) cand2.push_back(0);
     auto t0 = clk::now();
@@ -885,11 +870,11 @@ struct SimBatch {
       if (rc == KS_OK) rc = ksh_upload_batch(hs.data(), m, device, 0);
     }
     if (rc != KS_OK) { close(); return rc; }
-    if (ms) ms[0] = since(t0);
+    if (ms) ms[0] = ms_since(t0);
     t0 = clk::now();
     rc = ksh_solve_batch_resident(hs.data(), m, nullptr, nullptr);
     if (rc != KS_OK) { close(); return rc; }
-    if (ms) ms[1] = since(t0);
+    if (ms) ms[1] = ms_since(t0);
     g_whatifs_simulated += m;
     return KS_OK;
   }
@@ -897,8 +882,7 @@ struct SimBatch {
 // all the what-ifs of one call: open, solve resident, decide on the device, rows back.  ms[5]: open | solve | command kernel | read-back | the host work around them
 int commands_over(Parsed* P, uint32_t flags, uint32_t n, const uint32_t* cand_off, const uint32_t* cand, const int32_t* pod_node, const uint32_t* deleting, uint32_t n_deleting,
                   int device, bool same_type, const uint64_t* ids, uint64_t* out_rows, uint32_t words, double* ms) {
-  using clk = std::chrono::steady_clock; auto since = [](clk::time_point a) { return std::chrono::duration<double, std::milli>(clk::now() - a).count(); };
-  if (ms) ms[0] = ms[1] = ms[2] = ms[3] = ms[4] = 0.0;
+  zero(ms, 5);
   if (!P || (n && (!cand_off || !out_rows)) || (n_deleting && !deleting)) return set_err(KS_ERR_INVALID, "null argument");
   SimBatch B; int rc = B.begin(P, "consolidation commands", "command", flags, n, cand_off, cand, deleting, n_deleting, words);
   if (rc != KS_OK || !n) return rc;
@@ -935,15 +919,14 @@ int commands_over(Parsed* P, uint32_t flags, uint32_t n, const uint32_t* cand_of
   B.close();
   if (rc != KS_OK) return rc;
   if (m != n) for (uint32_t k = 0; k < m; ++k) std::copy(rows.begin() + (size_t)k * W, rows.begin() + (size_t)(k + 1) * W, out_rows + (size_t)live[k] * W);
-  if (ms) ms[4] = since(t_call) - ms[0] - ms[1] - ms[2] - ms[3];      // the host work around the four: the per-what-if inputs, closing the handles
+  if (ms) ms[4] = ms_since(t_call) - ms[0] - ms[1] - ms[2] - ms[3];      // the host work around the four: the per-what-if inputs, closing the handles
   return KS_OK;
 }
 // Expiration / Drift.ComputeCommand for n candidate sets: open, solve resident, both tables written on the device, read back.  A set that names a deleting node gets an
 // error head here and is not simulated; its node_off is the next simulated set's, so the offsets stay ascending.  ms[5] as commands_over.
 int replacement_over(Parsed* P, uint32_t flags, uint32_t n, const uint32_t* cand_off, const uint32_t* cand, const int32_t* pod_node, const uint32_t* deleting, uint32_t n_deleting,
                      int device, uint64_t* out_heads, uint64_t* out_nodes, uint64_t cap_nodes, uint64_t* out_total, uint32_t words, double* ms) {
-  using clk = std::chrono::steady_clock; auto since = [](clk::time_point a) { return std::chrono::duration<double, std::milli>(clk::now() - a).count(); };
-  if (ms) ms[0] = ms[1] = ms[2] = ms[3] = ms[4] = 0.0;
+  zero(ms, 5);
   if (!P || !out_total || (n && (!cand_off || !out_heads)) || (n_deleting && !deleting) || (cap_nodes && !out_nodes)) return set_err(KS_ERR_INVALID, "null argument");
   SimBatch B; int rc = B.begin(P, "replacement commands", "replacement", flags, n, cand_off, cand, deleting, n_deleting, words);
   if (rc != KS_OK) return rc;
@@ -973,7 +956,7 @@ int replacement_over(Parsed* P, uint32_t flags, uint32_t n, const uint32_t* cand
     std::fill(h, h + KS_REP_HEAD_WORDS, 0ull);
     h[KS_REP_ID] = i; h[KS_REP_DECISION] = (uint64_t)KS_CMD_ERROR | ((uint64_t)KS_CMD_WHY_DELETING << 8); h[KS_REP_NODE_OFF] = next_off;
   }
-  if (ms) ms[4] = since(t_call) - ms[0] - ms[1] - ms[2] - ms[3];
+  if (ms) ms[4] = ms_since(t_call) - ms[0] - ms[1] - ms[2] - ms[3];
   return KS_OK;
 }
 // mapNodes (helpers.go:328-337) by reason code: a node of a command is still a candidate iff candidateNodes yields it under consolidation.ShouldDeprovision -- reasons
@@ -983,8 +966,7 @@ inline bool still_candidate(uint32_t why) { return why == 0 || (why >= KS_CAND_W
 // mapped subsets re-simulated in ONE batch and judged on the device.  ms[5] as commands_over.
 int validate_over(Parsed* P, uint32_t flags, uint32_t n, const uint32_t* node_off, const uint32_t* nodes, const uint32_t* expect, const uint64_t* options, const uint32_t* why,
                   const uint32_t* node_flags, const int32_t* pod_node, const uint32_t* deleting, uint32_t n_deleting, int device, const uint64_t* ids, uint64_t* out_rows, uint32_t words, double* ms) {
-  using clk = std::chrono::steady_clock; auto since = [](clk::time_point a) { return std::chrono::duration<double, std::milli>(clk::now() - a).count(); };
-  if (ms) ms[0] = ms[1] = ms[2] = ms[3] = ms[4] = 0.0;
+  zero(ms, 5);
   if (!P || (n && (!node_off || !out_rows || !expect)) || (n_deleting && !deleting)) return set_err(KS_ERR_INVALID, "null argument");
   SimBatch B; int rc = B.begin(P, "validate commands", "validation", flags, n, node_off, nodes, deleting, n_deleting, words);
   if (rc != KS_OK || !n) return rc;
@@ -1020,9 +1002,9 @@ int validate_over(Parsed* P, uint32_t flags, uint32_t n, const uint32_t* node_of
     if (rc != KS_OK) return rc;
     std::vector<ks_dev_problem*> ds(m); for (uint32_t k = 0; k < m; ++k) ds[k] = ((Handle*)B.hs[k])->dev;
     ks_validate_inputs in{}; in.flags = vflags.data(); in.n_mapped = nmapped.data(); in.options = lopts.data();
-    rc = ks_validate_commands_host(ds.data(), m, lids.data(), &in, words, rows.data(), ms ? ms + 2 : nullptr);
+    rc = dev_rc(ks_validate_commands_host(ds.data(), m, lids.data(), &in, words, rows.data(), ms ? ms + 2 : nullptr));
     B.close();
-    if (rc != KS_OK) return set_err(rc, ks_last_error());
+    if (rc != KS_OK) return rc;
   }
   // nothing was written so far: a refusal leaves the caller's rows as they were
   for (uint32_t k = 0; k < m; ++k) std::copy(rows.begin() + (size_t)k * W, rows.begin() + (size_t)(k + 1) * W, out_rows + (size_t)live[k] * W);
@@ -1030,24 +1012,23 @@ int validate_over(Parsed* P, uint32_t flags, uint32_t n, const uint32_t* node_of
     uint64_t* row = out_rows + (size_t)h.i * W; std::fill(row, row + W, 0ull);
     row[KS_VAL_ID] = ids ? ids[h.i] : h.i; row[KS_VAL_VERDICT] = (uint64_t)h.verdict | ((uint64_t)h.why << 8); row[KS_VAL_N_MAPPED] = h.n_mapped;
   }
-  if (ms) ms[4] = since(t_call) - ms[0] - ms[1] - ms[2] - ms[3];
+  if (ms) ms[4] = ms_since(t_call) - ms[0] - ms[1] - ms[2] - ms[3];
   return KS_OK;
 }
 }  // namespace
 extern "C" {
 int ksh_consolidation_commands(void* parsed, uint32_t flags, uint32_t n, const uint32_t* cand_off, const uint32_t* cand, const int32_t* pod_node, const uint32_t* deleting, uint32_t n_deleting,
                                int device, int same_type, uint64_t* out_rows, uint32_t words, double* ms) {
-  try { return commands_over((Parsed*)parsed, flags, n, cand_off, cand, pod_node, deleting, n_deleting, device, same_type != 0, nullptr, out_rows, words, ms); }
-  catch (const ksh::Unsupported& e) { return set_err(KS_ERR_UNSUPPORTED, e.what()); } catch (const std::exception& e) { return set_err(KS_ERR_INVALID, e.what()); }
+  return guarded([&] { return commands_over((Parsed*)parsed, flags, n, cand_off, cand, pod_node, deleting, n_deleting, device, same_type != 0, nullptr, out_rows, words, ms); });
 }
 // firstNNodeConsolidationOption (multinodeconsolidation.go:74-114): every prefix the binary search could probe in one batch, filterOutSameType included, then the search
 // replayed over the rows.  out_row[KS_CMD_ID] = how many leading candidates the command removes.
 int ksh_first_n_node_option(void* parsed, uint32_t flags, const uint32_t* candidates, uint32_t n, uint32_t max_nodes, const int32_t* pod_node, const uint32_t* deleting, uint32_t n_deleting,
                             int device, uint64_t* out_row, uint32_t words, double* ms) {
   if (!out_row || (n && !candidates)) return set_err(KS_ERR_INVALID, "null argument");
-  try {
+  return guarded([&] {
     const size_t W = KS_CMD_ROW_WORDS(words); std::fill(out_row, out_row + W, 0ull);
-    if (ms) ms[0] = ms[1] = ms[2] = ms[3] = ms[4] = 0.0;
+    zero(ms, 5);
     if (n < 2) return KS_OK;                                   // :75-77
     uint32_t lo = 1, hi = max_nodes; if (n <= hi) hi = n - 1;      // :78-84
     if (hi < lo) return KS_OK;
@@ -1064,16 +1045,16 @@ int ksh_first_n_node_option(void* parsed, uint32_t flags, const uint32_t* candid
       if (action == KS_CMD_REPLACE || action == KS_CMD_DELETE) { std::copy(row, row + W, out_row); l = mid + 1; } else h = mid - 1;
     }
     return KS_OK;
-  } catch (const ksh::Unsupported& e) { return set_err(KS_ERR_UNSUPPORTED, e.what()); } catch (const std::exception& e) { return set_err(KS_ERR_INVALID, e.what()); }
+  });
 }
 // SingleNodeConsolidation.ComputeCommand's scan (singlenodeconsolidation.go:54-78): every singleton in one batch; the first delete or replace in candidate order, errors
 // passed over.  out_row[KS_CMD_ID] = the position of that candidate.
 int ksh_single_node_option(void* parsed, uint32_t flags, const uint32_t* candidates, uint32_t n, const int32_t* pod_node, const uint32_t* deleting, uint32_t n_deleting,
                            int device, uint64_t* out_row, uint32_t words, double* ms) {
   if (!out_row || (n && !candidates)) return set_err(KS_ERR_INVALID, "null argument");
-  try {
+  return guarded([&] {
     const size_t W = KS_CMD_ROW_WORDS(words); std::fill(out_row, out_row + W, 0ull);
-    if (ms) ms[0] = ms[1] = ms[2] = ms[3] = ms[4] = 0.0;
+    zero(ms, 5);
     if (!n) return KS_OK;
     std::vector<uint32_t> off(n + 1); for (uint32_t i = 0; i <= n; ++i) off[i] = i;
     std::vector<uint64_t> rows((size_t)n * W);
@@ -1084,21 +1065,20 @@ int ksh_single_node_option(void* parsed, uint32_t flags, const uint32_t* candida
       if (action == KS_CMD_REPLACE || action == KS_CMD_DELETE) { std::copy(row, row + W, out_row); return KS_OK; }
     }
     return KS_OK;
-  } catch (const ksh::Unsupported& e) { return set_err(KS_ERR_UNSUPPORTED, e.what()); } catch (const std::exception& e) { return set_err(KS_ERR_INVALID, e.what()); }
+  });
 }
 uint64_t ksh_whatifs_simulated(void) { return g_whatifs_simulated.load(); }
 // ---- replacement commands (kshost.h): Expiration / Drift.ComputeCommand's simulation and m -> n command ----
 int ksh_replacement_commands(void* parsed, uint32_t flags, uint32_t n, const uint32_t* cand_off, const uint32_t* cand, const int32_t* pod_node, const uint32_t* deleting, uint32_t n_deleting,
                              int device, uint64_t* out_heads, uint64_t* out_nodes, uint64_t cap_nodes, uint64_t* out_total_nodes, uint32_t words, double* ms) {
-  try { return replacement_over((Parsed*)parsed, flags, n, cand_off, cand, pod_node, deleting, n_deleting, device, out_heads, out_nodes, cap_nodes, out_total_nodes, words, ms); }
-  catch (const ksh::Unsupported& e) { return set_err(KS_ERR_UNSUPPORTED, e.what()); } catch (const std::exception& e) { return set_err(KS_ERR_INVALID, e.what()); }
+  return guarded([&] { return replacement_over((Parsed*)parsed, flags, n, cand_off, cand, pod_node, deleting, n_deleting, device, out_heads, out_nodes, cap_nodes, out_total_nodes, words, ms); });
 }
 // ComputeCommand's loop (expiration.go:75-111, drift.go:64-96): the first candidate canBeTerminated lets through (why == 0) that is not deleting decides, and only it is
 // simulated -- which one that is is known before any simulation.
 int ksh_replacement_option(void* parsed, uint32_t flags, const uint32_t* candidates, uint32_t n, const uint32_t* why, const int32_t* pod_node, const uint32_t* deleting, uint32_t n_deleting,
                            int device, uint64_t* out_head, uint64_t* out_nodes, uint64_t cap_nodes, uint64_t* out_total_nodes, int32_t* out_position, uint32_t words, double* ms) {
   if (!parsed || !out_head || !out_total_nodes || !out_position || (n && (!candidates || !why)) || (n_deleting && !deleting)) return set_err(KS_ERR_INVALID, "null argument");
-  if (ms) ms[0] = ms[1] = ms[2] = ms[3] = ms[4] = 0.0;
+  zero(ms, 5);
   const size_t NN = ((Parsed*)parsed)->pr->nodes.size();
   for (uint32_t i = 0; i < n; ++i) if (candidates[i] >= NN) return set_err(KS_ERR_INVALID, "candidate node out of range");
   for (uint32_t i = 0; i < n_deleting; ++i) if (deleting[i] >= NN) return set_err(KS_ERR_INVALID, "deleting node out of range");
@@ -1118,17 +1098,16 @@ int ksh_replacement_option(void* parsed, uint32_t flags, const uint32_t* candida
 int ksh_validate_commands(void* parsed, uint32_t flags, uint32_t n, const uint32_t* node_off, const uint32_t* nodes, const uint32_t* expect_replacement, const uint64_t* options,
                           const uint32_t* why, const uint32_t* node_flags, const int32_t* pod_node, const uint32_t* deleting, uint32_t n_deleting, int device,
                           uint64_t* out_rows, uint32_t words, double* ms) {
-  try { return validate_over((Parsed*)parsed, flags, n, node_off, nodes, expect_replacement, options, why, node_flags, pod_node, deleting, n_deleting, device, nullptr, out_rows, words, ms); }
-  catch (const ksh::Unsupported& e) { return set_err(KS_ERR_UNSUPPORTED, e.what()); } catch (const std::exception& e) { return set_err(KS_ERR_INVALID, e.what()); }
+  return guarded([&] { return validate_over((Parsed*)parsed, flags, n, node_off, nodes, expect_replacement, options, why, node_flags, pod_node, deleting, n_deleting, device, nullptr, out_rows, words, ms); });
 }
 // SingleNodeConsolidation.ComputeCommand's loop (singlenodeconsolidation.go:54-84) from the candidate AFTER the one whose validation failed: the remaining singletons in
 // one command batch, the deletes and replaces among them in one validation batch, the first valid one in candidate order.
 int ksh_single_node_resume(void* parsed, uint32_t flags, const uint32_t* candidates, uint32_t n, int failed_before, const uint32_t* why, const uint32_t* node_flags, const int32_t* pod_node,
                            const uint32_t* deleting, uint32_t n_deleting, int device, uint64_t* out_row, uint64_t* out_vrow, uint32_t* out_state, uint32_t words, double* ms) {
   if (!out_row || !out_vrow || !out_state || (n && !candidates)) return set_err(KS_ERR_INVALID, "null argument");
-  try {
+  return guarded([&] {
     const size_t W = KS_CMD_ROW_WORDS(words), VW = KS_VAL_ROW_WORDS(words);
-    if (ms) ms[0] = ms[1] = ms[2] = ms[3] = ms[4] = 0.0;
+    zero(ms, 5);
     std::vector<uint64_t> rows((size_t)n * W), vrows; std::vector<uint32_t> off(n + 1); for (uint32_t i = 0; i <= n; ++i) off[i] = i;
     double ms1[5] = {0, 0, 0, 0, 0}, ms2[5] = {0, 0, 0, 0, 0};
     int rc = commands_over((Parsed*)parsed, flags, n, off.data(), candidates, pod_node, deleting, n_deleting, device, false, nullptr, rows.data(), words, ms1);
@@ -1158,7 +1137,7 @@ int ksh_single_node_resume(void* parsed, uint32_t flags, const uint32_t* candida
     }
     *out_state = failed ? 2u : 0u;                                 // :82-85
     return KS_OK;
-  } catch (const ksh::Unsupported& e) { return set_err(KS_ERR_UNSUPPORTED, e.what()); } catch (const std::exception& e) { return set_err(KS_ERR_INVALID, e.what()); }
+  });
 }
 // EmptyNodeConsolidation's own check (emptynodeconsolidation.go:77-87), literally: map the nodes; retry iff a mapped node has pods and is not nominated.
 int ksh_validate_empty_nodes(const uint32_t* nodes, uint32_t n, const uint32_t* why, const uint32_t* n_node_pods, const uint32_t* node_flags, uint32_t* out_retry) {
@@ -1198,8 +1177,8 @@ struct CandSnapshot {
 // the flags, the device decides the rest (ks_deprovisioning_candidates_host); *n_in_result = len(candidateNodes(...)).
 int candidates_over(Parsed* P, uint32_t method, const int32_t* pod_node, const uint32_t* deleting, uint32_t n_deleting, const ksh_candidate_inputs* in, const ksh_deprovisioning_inputs* dx,
                     const ksh_pdb_block* pb, int device, ksh_candidates_out* out, uint32_t* n_in_result, double* ms) {
-  using clk = std::chrono::steady_clock; const auto t_call = clk::now();
-  if (ms) ms[0] = ms[1] = ms[2] = ms[3] = 0.0;
+  const auto t_call = clk::now();
+  zero(ms, 4);
   if (!P || !in || !out || (n_deleting && !deleting)) return set_err(KS_ERR_INVALID, "null argument");
   const std::string what = dx ? "deprovisioning candidates" : "consolidation candidates";
   if (dx && (method < KSH_METHOD_EXPIRATION || method > KSH_METHOD_EMPTINESS)) return set_err(KS_ERR_INVALID, what + ": unknown method " + std::to_string(method));
@@ -1207,10 +1186,7 @@ int candidates_over(Parsed* P, uint32_t method, const int32_t* pod_node, const u
   std::vector<ksp::Pdb> pdbs;
   if (pb) {
     if (!pb->str_off || (!pb->words && pb->n_words) || (!pb->str_bytes && pb->n_strings)) return set_err(KS_ERR_INVALID, "null argument");
-    for (uint32_t i = 0; i < pb->n_strings; ++i) if (pb->str_off[i + 1] < pb->str_off[i]) return set_err(KS_ERR_INVALID, "pdb block: string offsets not ascending");
-    if (pb->n_strings && pb->str_off[pb->n_strings] > pb->str_bytes_len) return set_err(KS_ERR_INVALID, "pdb block: string offsets reach beyond str_bytes_len");
-    ksh_pod_block strings{}; strings.n_strings = pb->n_strings; strings.str_off = pb->str_off; strings.str_bytes = pb->str_bytes; strings.str_bytes_len = pb->str_bytes_len;
-    pdbs = ksp::PdbReader(strings, pb->words, pb->words + pb->n_words).read_pdbs(pb->n_pdbs);
+    pdbs = ksp::PdbReader(string_table("pdb", pb->n_strings, pb->str_off, pb->str_bytes, pb->str_bytes_len), pb->words, pb->words + pb->n_words).read_pdbs(pb->n_pdbs);
   }
   std::shared_ptr<const void> held; std::vector<int32_t> bind;
   const ksp::Problem& pr = *P->pr;
@@ -1320,7 +1296,7 @@ int candidates_over(Parsed* P, uint32_t method, const int32_t* pod_node, const u
   ki.pdb_ns = pdb_ns.data(); ki.pdb_allowed = pdb_allowed.data(); ki.pdb_req_off = req_off.data(); ki.pdb_req_key = req_key.data(); ki.pdb_req_mask = req_mask.data();
   ki.node_why = node_why.data(); ki.node_age_seconds = in->node_age_seconds; ki.node_ttl_seconds = node_ttl.data(); ki.node_pods_off = pods_off.data(); ki.node_pods = node_pods.data();
   ks_candidates_outputs ko{}; ko.order = out->order; ko.empty = out->empty; ko.why = out->why; ko.detail = out->detail; ko.n_node_pods = out->n_node_pods; ko.cost = out->cost;
-  const double host_ms = std::chrono::duration<double, std::milli>(clk::now() - t_call).count();
+  const double host_ms = ms_since(t_call);
   double kms[3] = {0, 0, 0};
   int rc;
   if (dx) {
@@ -1330,7 +1306,7 @@ int candidates_over(Parsed* P, uint32_t method, const int32_t* pod_node, const u
     rc = ks_deprovisioning_candidates_host(&di, &dout, device, kms);
     ko = dout.c; if (n_in_result) *n_in_result = dout.n_in_result;
   } else rc = ks_consolidation_candidates_host(&ki, &ko, device, kms);
-  if (rc != KS_OK) return set_err(rc, ks_last_error());
+  if (rc != KS_OK) return dev_rc(rc);
   out->n_candidates = ko.n_candidates; out->n_empty = ko.n_empty;
   if (ms) { ms[0] = host_ms; ms[1] = kms[0]; ms[2] = kms[1]; ms[3] = kms[2]; }
   return KS_OK;
@@ -1339,19 +1315,18 @@ int candidates_over(Parsed* P, uint32_t method, const int32_t* pod_node, const u
 extern "C" {
 int ksh_consolidation_candidates(void* parsed, const int32_t* pod_node, const uint32_t* deleting, uint32_t n_deleting, const ksh_candidate_inputs* in, const ksh_pdb_block* pdbs, int device,
                                  ksh_candidates_out* out, double* ms) {
-  try { return candidates_over((Parsed*)parsed, 0, pod_node, deleting, n_deleting, in, nullptr, pdbs, device, out, nullptr, ms); }
-  catch (const ksh::Unsupported& e) { return set_err(KS_ERR_UNSUPPORTED, e.what()); } catch (const std::exception& e) { return set_err(KS_ERR_INVALID, e.what()); }
+  return guarded([&] { return candidates_over((Parsed*)parsed, 0, pod_node, deleting, n_deleting, in, nullptr, pdbs, device, out, nullptr, ms); });
 }
 // candidateNodes under Expiration / Drift / Emptiness.ShouldDeprovision and the order their ComputeCommand walks (kshost.h)
 int ksh_deprovisioning_candidates(void* parsed, uint32_t method, const int32_t* pod_node, const uint32_t* deleting, uint32_t n_deleting, const ksh_deprovisioning_inputs* in,
                                   const ksh_pdb_block* pdbs, int device, ksh_deprovisioning_out* out, double* ms) {
   if (!in || !out) return set_err(KS_ERR_INVALID, "null argument");
-  try {
+  return guarded([&] {
     uint32_t n_in_result = 0;
     const int rc = candidates_over((Parsed*)parsed, method, pod_node, deleting, n_deleting, &in->base, in, pdbs, device, &out->base, &n_in_result, ms);
     if (rc == KS_OK) out->n_in_result = n_in_result;
     return rc;
-  } catch (const ksh::Unsupported& e) { return set_err(KS_ERR_UNSUPPORTED, e.what()); } catch (const std::exception& e) { return set_err(KS_ERR_INVALID, e.what()); }
+  });
 }
 // Emptiness.ComputeCommand (emptiness.go:73-82), literally: of the candidates those without pods, all deleted in one command; none -> do-nothing.  Host only.
 int ksh_emptiness_command(const uint32_t* candidates, uint32_t n, const uint32_t* n_node_pods, uint32_t* out_action, uint32_t* out_nodes, uint32_t* out_n_nodes) {
@@ -1369,28 +1344,38 @@ const char* ksh_snapshot_name(void* parsed, int what, uint32_t a, uint32_t b) {
   if (what == 3) return a < P->pr->nodes.size() ? P->pr->nodes[a].name.c_str() : nullptr;
   if (what == 4) return a < P->pr->instance_types.size() ? P->pr->instance_types[a].name.c_str() : nullptr;
   if (!P->sb) return nullptr;
-  const ksh::Encoded& E = *ksh::delta_inputs(*P->sb).base;
-  if (what == 0) return a < E.key_names.size() ? E.key_names[a].c_str() : nullptr;
-  if (what == 1) return (a < E.key_values.size() && b < E.key_values[a].size()) ? E.key_values[a][b].c_str() : nullptr;
-  if (what == 2) return a < E.res_names.size() ? E.res_names[a].c_str() : nullptr;
-  return nullptr;
+  const char* name = nullptr;
+  guarded([&] {
+    const ksh::Encoded& E = *ksh::delta_inputs(*P->sb).base;
+    if (what == 0 && a < E.key_names.size()) name = E.key_names[a].c_str();
+    if (what == 1 && a < E.key_values.size() && b < E.key_values[a].size()) name = E.key_values[a][b].c_str();
+    if (what == 2 && a < E.res_names.size()) name = E.res_names[a].c_str();
+    return KS_OK;
+  });
+  return name;
 }
 // the instance-type key's requirement of a row (KS_CMD_IT_STATE), spelled out: *complement, the number of values; value i through ksh_snapshot_it_state_value
 int ksh_snapshot_it_state(void* parsed, uint32_t state, int* complement, uint32_t* n_values) {
   Parsed* P = (Parsed*)parsed; if (!P || !complement || !n_values) return set_err(KS_ERR_INVALID, "null argument");
   std::lock_guard<std::mutex> g(P->mu);
   if (!P->sb) return set_err(KS_ERR_INVALID, "the snapshot was not flattened yet");
-  const ksh::Encoded& L = ksh::delta_inputs(*P->sb).base->lattice();
-  if (state == 0 || state >= L.it_states.size()) return set_err(KS_ERR_INVALID, "instance-type state out of range");
-  *complement = L.it_states[state].complement ? 1 : 0; *n_values = (uint32_t)L.it_states[state].values.size(); return KS_OK;
+  return guarded([&] {
+    const ksh::Encoded& L = ksh::delta_inputs(*P->sb).base->lattice();
+    if (state == 0 || state >= L.it_states.size()) return set_err(KS_ERR_INVALID, "instance-type state out of range");
+    *complement = L.it_states[state].complement ? 1 : 0; *n_values = (uint32_t)L.it_states[state].values.size(); return KS_OK;
+  });
 }
 const char* ksh_snapshot_it_state_value(void* parsed, uint32_t state, uint32_t i) {
   Parsed* P = (Parsed*)parsed; if (!P) return nullptr;
   std::lock_guard<std::mutex> g(P->mu);
   if (!P->sb) return nullptr;
-  const ksh::Encoded& L = ksh::delta_inputs(*P->sb).base->lattice();
-  if (state == 0 || state >= L.it_states.size() || i >= L.it_states[state].values.size()) return nullptr;
-  auto it = L.it_states[state].values.begin(); std::advance(it, i); return it->c_str();
+  const char* value = nullptr;
+  guarded([&] {
+    const ksh::Encoded& L = ksh::delta_inputs(*P->sb).base->lattice();
+    if (state == 0 || state >= L.it_states.size() || i >= L.it_states[state].values.size()) return KS_OK;
+    auto it = L.it_states[state].values.begin(); std::advance(it, i); value = it->c_str(); return KS_OK;
+  });
+  return value;
 }
 int ksh_pack_width(void* hv, int* out) { Handle* h = (Handle*)hv; if (!h || !h->dev) return KS_ERR_INVALID; return ks_problem_pack_width(h->dev, out); }
 int ksh_pack_lean(void* hv, int* out) { Handle* h = (Handle*)hv; if (!h || !h->dev) return KS_ERR_INVALID; return ks_problem_pack_lean(h->dev, out); }
