@@ -77,6 +77,7 @@ typedef struct ks_reqsets {
   const int32_t* it_state;    /* [n]   state of the instance-type key (0 == key absent)       */
 } ks_reqsets;
 
+/* The [..] comments below state each array's length for the reader; KS_PROBLEM_ARRAYS under the struct is the executable form of the same lengths. */
 typedef struct ks_problem {
   /* ---- dimensions ---- */
   uint32_t P;  /* pods in the batch                                   */
@@ -144,29 +145,29 @@ typedef struct ks_problem {
   ks_reqsets cls;                 /* n = C : NewPodRequirements, requirements.go:61-78 */
   const uint8_t* cls_hn_mode;     /* [C] hostname requirement: 0 none, 1 In list, 2 NotIn list (Exists = 2 + empty) */
   const uint32_t* cls_hn_off;     /* [C+1] into hn_list[] (existing-node indices) */
-  const uint32_t* hn_list;
+  const uint32_t* hn_list;        /* [cls_hn_off[C]] */
   const int64_t* cls_requests;    /* [C*R] resources.RequestsForPods(pod), resources.go:25-33 */
   const uint32_t* cls_requests_present; /* [C] */
   const uint64_t* cls_tolerated;  /* [C] bit i: some toleration ToleratesTaint(taint i) (taints.go:28-40) */
   const uint32_t* cls_port_off;   /* [C+1] into ports[] */
-  const uint64_t* ports;          /* proto<<56 | port<<32 | ip_id (ip_id 0 == unspecified 0.0.0.0/::), hostportusage.go:39-57 */
+  const uint64_t* ports;          /* [cls_port_off[C]], or [en_port_off[E]] when C == 0: the existing nodes' reservations first, then the classes' ports.  proto<<56 | port<<32 | ip_id (ip_id 0 == unspecified 0.0.0.0/::), hostportusage.go:39-57 */
   const uint32_t* cls_vol_off;    /* [C+1] into vol_list[] */
-  const uint32_t* vol_list;       /* the class's volumes, ordered by driver: driver<<24 | shared-claim bit        (bit 31 clear)
+  const uint32_t* vol_list;       /* [cls_vol_off[C]] the class's volumes, ordered by driver: driver<<24 | shared-claim bit        (bit 31 clear)
                                      1<<31 | driver<<24 | n : n claims no other pod or node mounts
                                      0xFFFFFFFF            : VolumeUsage.validate failed -> no existing node accepts the pod */
   /* topology membership of a class (CSR lists of group ids) */
   const uint32_t* cls_own_off;  /* [C+1] groups in Topology.topologies owned by the pod; entry = g | selfSelecting<<31 */
-  const uint32_t* own_list;
+  const uint32_t* own_list;     /* [cls_own_off[C]] */
   const uint32_t* cls_sel_off;  /* [C+1] non-inverse groups whose selector selects the pod (Record, topology.go:120-133) */
-  const uint32_t* sel_list;
+  const uint32_t* sel_list;     /* [cls_sel_off[C]] */
   const uint32_t* cls_isel_off; /* [C+1] inverse groups selecting the pod (getMatchingTopologies, topology.go:358-362) */
-  const uint32_t* isel_list;
+  const uint32_t* isel_list;    /* [cls_isel_off[C]] */
   const uint32_t* cls_iown_off; /* [C+1] inverse groups owned by the pod (Record, topology.go:136-141) */
-  const uint32_t* iown_list;
+  const uint32_t* iown_list;    /* [cls_iown_off[C]] */
 
   /* ---- pods ---- */
   const uint32_t* pod_stage_off; /* [P+1] into stage_cls[]: one class per relaxation stage */
-  const uint32_t* stage_cls;
+  const uint32_t* stage_cls;     /* [pod_stage_off[P]] class ids */
   const uint32_t* queue;         /* [P] initial queue order: byCPUAndMemoryDescending, queue.go:74-110 */
 
   /* ---- topology groups (topologygroup.go:53-86) ---- */
@@ -175,7 +176,7 @@ typedef struct ks_problem {
   const int32_t* grp_max_skew;  /* [G] */
   const uint8_t* grp_active;    /* [G] 1: exists after NewTopology; 0: created by a later Topology.Update (topology.go:86-117) */
   const uint32_t* grp_filter_off; /* [G+1] TopologyNodeFilter terms (topologynodefilter.go:28-70) into `flt`; empty == always */
-  ks_reqsets flt;
+  ks_reqsets flt;               /* n = flt.n terms (grp_filter_off[G] of them are referenced) */
   const int32_t* grp_count;     /* [G*64] initial domain counts (countDomains, topology.go:231-276); -1 == not a registered domain */
   const int32_t* grp_hslot;     /* [G] row in the hostname tables or -1 */
   const int32_t* grph_count;    /* [GH*E] initial counts on the existing nodes' hostnames; -1 unregistered */
@@ -185,6 +186,92 @@ typedef struct ks_problem {
                                    field existed): LEAN at R <= 4 only, so such a problem runs the kernel it always ran.  libkshost sets it for a problem flattened under
                                    KSH_ACTIVE_RESOURCES.  A kernel choice, not part of the problem: no fingerprint covers it, no result depends on it. */
 } ks_problem;
+
+/* ---- the arrays of ks_problem, each named ONCE.  For the library's own use (libksolve's upload, libkshost's flattening and fingerprint, ks_debug_problem_array): not
+ * an interface.  Whoever adds an array to ks_problem adds its row here, and the wiring, the length check, the upload and the fingerprint follow.
+ *   X(field, owner, count, share)   one array.
+ *   XRS(field, n)                   one ks_reqsets member: its six arrays, present / complement / it_state of n elements, mask / gt / lt of n * K.
+ * count: elements, over a `const ks_problem* p`; an offset array is listed before the list it measures, so a count never reads an array that was not checked yet.
+ * owner: whose vector backs the pointer in libkshost's flattening -- SELF the flattening itself, CAT its catalogue() (a what-if over a shared snapshot points at the
+ *        snapshot's), LAT its lattice().
+ * share: the rule of ks_problem_upload_shared -- NEVER copied always; CAT not copied when the host pointer is the one `base` was uploaded from; LAT the same, and S / SC
+ *        agree with base's; PRICE the same, and key_zone / key_ct / n_ct agree with base's -- such an array may be NULL and is then not uploaded;
+ *        PRICE_LO as PRICE, NULL falls back to it_price, and the array is NOT FINGERPRINTED (the one row that is not): only ks_launch_pick_dev reads it, no Solve
+ *        depends on it, and it arrived after the committed fingerprints were pinned.
+ * The rows stand in the order libkshost's fingerprint hashes them, which is pinned (tests/golden); the upload packs its copied region in the same order. */
+#define KS_TW(p) (((size_t)(p)->T + 63) / 64)
+#define KS_NP(p) ((p)->key_zone >= 0 && (p)->key_ct >= 0 ? (size_t)(p)->key_nvalues[(p)->key_zone] * (p)->n_ct : (size_t)0) /* (zone, capacity-type) pairs */
+#define KS_PROBLEM_ARRAYS(X, XRS) \
+  X(key_nvalues, SELF, p->K, NEVER) \
+  X(value_int, SELF, (size_t)p->K * 64, NEVER) \
+  X(it_present, CAT, p->T, CAT) \
+  X(it_complement, CAT, p->T, CAT) \
+  X(it_mask, CAT, (size_t)p->K * p->T, CAT) \
+  X(it_offer, CAT, p->T, CAT) \
+  X(it_price, CAT, (size_t)p->T * KS_NP(p), PRICE) \
+  X(it_price_lo, CAT, (size_t)p->T * KS_NP(p), PRICE_LO) \
+  X(it_alloc, CAT, (size_t)p->R * p->T, CAT) \
+  X(it_cap, CAT, (size_t)p->R * p->T, CAT) \
+  X(its_inter, LAT, (size_t)p->S * p->SC, LAT) \
+  X(its_fail, LAT, (size_t)p->S * p->SC, LAT) \
+  X(its_nidne, LAT, p->S, LAT) \
+  X(its_types, LAT, (size_t)p->S * KS_TW(p), LAT) \
+  XRS(tmpl, p->M) \
+  XRS(en, p->E) \
+  XRS(cls, p->C) \
+  XRS(flt, p->flt.n) \
+  X(tmpl_taints, SELF, p->M, NEVER) \
+  X(tmpl_types, SELF, (size_t)p->M * KS_TW(p), NEVER) \
+  X(tmpl_daemon, SELF, (size_t)p->M * p->R, NEVER) \
+  X(tmpl_remaining, SELF, (size_t)p->M * p->R, NEVER) \
+  X(tmpl_daemon_present, SELF, p->M, NEVER) \
+  X(tmpl_limit_present, SELF, p->M, NEVER) \
+  X(en_taints, SELF, p->E, NEVER) \
+  X(en_avail, SELF, (size_t)p->E * p->R, NEVER) \
+  X(en_requests, SELF, (size_t)p->E * p->R, NEVER) \
+  X(en_requests_present, SELF, p->E, NEVER) \
+  X(en_port_off, SELF, (size_t)p->E + 1, NEVER) \
+  X(cls_hn_mode, SELF, p->C, NEVER) \
+  X(cls_hn_off, SELF, (size_t)p->C + 1, NEVER) \
+  X(hn_list, SELF, p->C ? p->cls_hn_off[p->C] : 0, NEVER) \
+  X(cls_requests, SELF, (size_t)p->C * p->R, NEVER) \
+  X(cls_requests_present, SELF, p->C, NEVER) \
+  X(cls_tolerated, SELF, p->C, NEVER) \
+  X(cls_port_off, SELF, (size_t)p->C + 1, NEVER) \
+  X(ports, SELF, p->C ? p->cls_port_off[p->C] : (p->E ? p->en_port_off[p->E] : 0), NEVER) \
+  X(en_vol_limit, SELF, (size_t)p->E * p->ND, NEVER) \
+  X(en_vol_count, SELF, (size_t)p->E * p->ND, NEVER) \
+  X(en_vol_set, SELF, (size_t)p->E * p->SW, NEVER) \
+  X(cls_vol_off, SELF, (size_t)p->C + 1, NEVER) \
+  X(vol_list, SELF, p->C ? p->cls_vol_off[p->C] : 0, NEVER) \
+  X(cls_own_off, SELF, (size_t)p->C + 1, NEVER) \
+  X(own_list, SELF, p->C ? p->cls_own_off[p->C] : 0, NEVER) \
+  X(cls_sel_off, SELF, (size_t)p->C + 1, NEVER) \
+  X(sel_list, SELF, p->C ? p->cls_sel_off[p->C] : 0, NEVER) \
+  X(cls_isel_off, SELF, (size_t)p->C + 1, NEVER) \
+  X(isel_list, SELF, p->C ? p->cls_isel_off[p->C] : 0, NEVER) \
+  X(cls_iown_off, SELF, (size_t)p->C + 1, NEVER) \
+  X(iown_list, SELF, p->C ? p->cls_iown_off[p->C] : 0, NEVER) \
+  X(pod_stage_off, SELF, (size_t)p->P + 1, NEVER) \
+  X(stage_cls, SELF, p->P ? p->pod_stage_off[p->P] : 0, NEVER) \
+  X(queue, SELF, p->P, NEVER) \
+  X(grp_type, SELF, p->G, NEVER) \
+  X(grp_active, SELF, p->G, NEVER) \
+  X(grp_key, SELF, p->G, NEVER) \
+  X(grp_max_skew, SELF, p->G, NEVER) \
+  X(grp_count, SELF, (size_t)p->G * 64, NEVER) \
+  X(grp_hslot, SELF, p->G, NEVER) \
+  X(grph_count, SELF, (size_t)p->GH * p->E, NEVER) \
+  X(grph_extra_pos, SELF, p->GH, NEVER) \
+  X(grp_filter_off, SELF, (size_t)p->G + 1, NEVER)
+/* The table covers the struct: the pointer members its rows name (a ks_reqsets member counts whole) plus the bytes of everything else -- the scalar members and the
+ * padding after them -- are sizeof(ks_problem).  An array added to the struct without a row fails this; after adding a SCALAR member, add what it makes sizeof grow by. */
+#define KS_PROBLEM_SCALAR_BYTES 96 /* 23 four-byte scalars and 4 bytes of padding after n_ct */
+#define KS_PA_PTR_(field, owner, count, share) + sizeof(void*)
+#define KS_PA_RS_(field, n) + sizeof(ks_reqsets)
+#ifdef __cplusplus
+static_assert(sizeof(void*) != 8 || (0 KS_PROBLEM_ARRAYS(KS_PA_PTR_, KS_PA_RS_)) + KS_PROBLEM_SCALAR_BYTES == sizeof(ks_problem), "KS_PROBLEM_ARRAYS does not cover ks_problem");
+#endif
 
 #define KS_FLAG_SIMULATION 1u /* SchedulerOptions.SimulationMode (scheduler.go:37-40); informational */
 #define KS_FLAG_STATS 2u      /* also count the reference algorithm's attempts / scanned types (DESIGN.md roofline) */
@@ -261,6 +348,13 @@ int ks_problem_pack_width(const ks_dev_problem* d, int* rm);
 int ks_problem_pack_lean(const ks_dev_problem* d, int* lean);      /* its neighbour: 1 if the ks_pack variant the last solve ran was a LEAN one (at width 4, or 8 under ks_problem.lean_r8), else 0 */
 int ks_problem_pack_row(const ks_dev_problem* d, int* row);        /* and which instantiation exactly: the index into the library's table of ks_pack instantiations (ks_debug_pack_row names its FAST, BOUNDS, LEAN, waves, RM) that the last solve of `d` -- alone or as a member of a batch -- launched; -1 if ks_pack_rr took it or nothing ran */
 int ks_problem_upload(const ks_problem* p, int device, ks_dev_problem** out);
+/* Diagnostics: row i of the library's table of ks_problem's arrays (KS_PROBLEM_ARRAYS; a ks_reqsets member appears as its six arrays, "cls.mask"): its name, the
+ * bytes of an element, the elements `p` states for it (*count: from p's dimensions and offset arrays, whether or not the pointer is set) and the byte offset of its
+ * pointer in ks_problem; *marks: KS_ARRAY_*.  Any out-pointer may be NULL; p may be NULL when count is.  Returns the number of rows (for every i; nothing is written
+ * for an i at or beyond it).  Needs no device.  What lets a caller -- or a test -- walk a problem it did not build without a list of its own. */
+#define KS_ARRAY_NOT_FINGERPRINTED 1u /* libkshost's fingerprint leaves the array out */
+#define KS_ARRAY_NULLABLE 2u          /* the pointer may be NULL whatever the count (offering prices) */
+uint32_t ks_debug_problem_array(const ks_problem* p, uint32_t i, const char** name, uint32_t* elem_bytes, uint64_t* count, uint32_t* offset, uint32_t* marks);
 void ks_problem_free(ks_dev_problem* d);
 /* Consolidation what-ifs over ONE cluster snapshot (deprovisioning/helpers.go:42-99) differ in their pods and in which state nodes stay, not in
  * the catalogue.  `base` is a resident problem flattened from the same snapshot (ks_problem_prepare'd): arrays of `p` whose HOST pointers are

@@ -2935,12 +2935,38 @@ static int state_layout(Arena& a, const StateDims& d, DevState& s) {
   return KS_OK;
 }
 
+// The caller's arrays, as include/ksolve.h KS_PROBLEM_ARRAYS names them: the device view carries every one of them under the same name with the same element type.
+#define X(f, owner, count, share) static_assert(std::is_same<decltype(ks_problem::f), decltype(DevProb::f)>::value, "KS_PROBLEM_ARRAYS: element type of " #f);
+#define XRS(f, n) static_assert(std::is_same<decltype(DevProb::f), ReqSetsD>::value, "KS_PROBLEM_ARRAYS: " #f);
+KS_PROBLEM_ARRAYS(X, XRS)
+#undef X
+#undef XRS
+#define X(f) static_assert(std::is_same<decltype(ks_reqsets::f), decltype(ReqSetsD::f)>::value, "ks_reqsets: element type of " #f);
+X(present) X(complement) X(mask) X(gt) X(lt) X(it_state)
+#undef X
+
 static int copy_reqsets(ks_dev_problem* d, const ks_reqsets& s, u32 n, u32 K, ReqSetsD* out) {
   out->n = n; Arena& a = d->a;
   for (size_t i = 0; i < (size_t)n * K; ++i) if (s.gt[i] != KS_NO_BOUND_GT || s.lt[i] != KS_NO_BOUND_LT) d->any_bounds = true;
   TRY(dev_copy(a, s.present, n, &out->present)); TRY(dev_copy(a, s.complement, n, &out->complement));
   TRY(dev_copy(a, s.mask, (size_t)n * K, &out->mask)); TRY(dev_copy(a, s.gt, (size_t)n * K, &out->gt)); TRY(dev_copy(a, s.lt, (size_t)n * K, &out->lt));
   TRY(dev_copy(a, s.it_state, n, &out->it_state)); return KS_OK;
+}
+
+// Row i of KS_PROBLEM_ARRAYS for a caller (ksolve.h): a ks_reqsets member is six rows.
+extern "C" uint32_t ks_debug_problem_array(const ks_problem* p, uint32_t i, const char** name, uint32_t* elem_bytes, uint64_t* count, uint32_t* offset, uint32_t* marks) {
+  struct Row { const char* name; u32 elem, off, marks; u64 count; };
+  enum { M_NEVER = 0, M_CAT = 0, M_LAT = 0, M_PRICE = KS_ARRAY_NULLABLE, M_PRICE_LO = KS_ARRAY_NULLABLE | KS_ARRAY_NOT_FINGERPRINTED };
+#define X(f, owner, cnt, share) {#f, (u32)sizeof(*ks_problem::f), (u32)offsetof(ks_problem, f), M_##share, p ? (u64)(cnt) : 0},
+#define RS1(f, m, cnt) {#f "." #m, (u32)sizeof(*ks_reqsets::m), (u32)(offsetof(ks_problem, f) + offsetof(ks_reqsets, m)), 0, p ? (u64)(cnt) : 0},
+#define XRS(f, n) RS1(f, present, n) RS1(f, complement, n) RS1(f, mask, (size_t)(n) * p->K) RS1(f, gt, (size_t)(n) * p->K) RS1(f, lt, (size_t)(n) * p->K) RS1(f, it_state, n)
+  const Row rows[] = {KS_PROBLEM_ARRAYS(X, XRS)};
+#undef X
+#undef RS1
+#undef XRS
+  const u32 n = (u32)(sizeof rows / sizeof rows[0]);
+  if (i < n) { if (name) *name = rows[i].name; if (elem_bytes) *elem_bytes = rows[i].elem; if (count) *count = rows[i].count; if (offset) *offset = rows[i].off; if (marks) *marks = rows[i].marks; }
+  return n;
 }
 
 extern "C" int ks_device_count(void) {
@@ -2993,7 +3019,6 @@ static int upload_impl(const ks_problem* p, int device, const ks_dev_problem* ba
   ks_dev_problem* d = new ks_dev_problem(); d->device = device; d->src = *p;
   // share X: same host array as the base's -> the base's device copy
 #define SHARED(field) (base && p->field && p->field == base->src.field)
-#define COPY_OR_SHARE(field, count, dst) do { if (SHARED(field)) (dst) = base->h.field; else TRY(dev_copy(a, p->field, (count), &(dst))); } while (0)
   const bool share_cat = base && p->K == base->h.K && p->T == base->h.T && p->R == base->h.R && SHARED(it_present) && SHARED(it_complement) && SHARED(it_mask) && SHARED(it_alloc) && SHARED(it_offer) &&
                          memcmp(p->key_nvalues, base->src.key_nvalues, p->K * sizeof(u32)) == 0;
   struct Guard { ks_dev_problem* d; bool ok = false; ~Guard() { if (!ok) ks_problem_free(d); } } guard{d};
@@ -3028,47 +3053,29 @@ static int upload_impl(const ks_problem* p, int device, const ks_dev_problem* ba
     for (u32 c = 0; c < C && lean; ++c) lean = p->cls_hn_mode[c] == 0 && p->cls_port_off[c + 1] == p->cls_port_off[c] && p->cls_vol_off[c + 1] == p->cls_vol_off[c];
     d->lean_ok = lean;
   }
-  TRY(dev_copy(a, p->key_nvalues, K, &h.key_nvalues)); TRY(dev_copy(a, p->value_int, (size_t)K * 64, &h.value_int));
-  COPY_OR_SHARE(it_present, T, h.it_present); COPY_OR_SHARE(it_complement, T, h.it_complement);
-  COPY_OR_SHARE(it_mask, (size_t)K * T, h.it_mask); COPY_OR_SHARE(it_alloc, (size_t)R * T, h.it_alloc);
-  COPY_OR_SHARE(it_cap, (size_t)R * T, h.it_cap); COPY_OR_SHARE(it_offer, T, h.it_offer);
-  h.it_price = nullptr; h.ct_spot = p->ct_spot; h.ct_ondemand = p->ct_ondemand;
+  h.ct_spot = p->ct_spot; h.ct_ondemand = p->ct_ondemand; h.ND = p->ND; h.SW = p->SW;
+  // the caller's arrays, row by row (KS_PROBLEM_ARRAYS): copied into the arena, or -- by the row's share rule -- the base's device copy
   const bool same_pairs = base && p->key_zone == base->src.key_zone && p->key_ct == base->src.key_ct && p->n_ct == base->src.n_ct;
-  if (p->it_price && p->key_zone >= 0 && p->key_ct >= 0) { if (same_pairs && SHARED(it_price) && base->h.it_price) h.it_price = base->h.it_price; else TRY(dev_copy(a, p->it_price, (size_t)T * p->key_nvalues[p->key_zone] * p->n_ct, &h.it_price)); }
-  h.it_price_lo = h.it_price;
-  if (p->it_price_lo && p->key_zone >= 0 && p->key_ct >= 0) { if (same_pairs && SHARED(it_price_lo) && base->h.it_price_lo) h.it_price_lo = base->h.it_price_lo; else TRY(dev_copy(a, p->it_price_lo, (size_t)T * p->key_nvalues[p->key_zone] * p->n_ct, &h.it_price_lo)); }
   const bool same_lattice = base && h.S == base->h.S && h.SC == base->h.SC;
-  if (same_lattice && SHARED(its_inter)) h.its_inter = base->h.its_inter; else TRY(dev_copy(a, p->its_inter, (size_t)h.S * h.SC, &h.its_inter));
-  if (same_lattice && SHARED(its_fail)) h.its_fail = base->h.its_fail; else TRY(dev_copy(a, p->its_fail, (size_t)h.S * h.SC, &h.its_fail));
-  if (same_lattice && SHARED(its_nidne)) h.its_nidne = base->h.its_nidne; else TRY(dev_copy(a, p->its_nidne, h.S, &h.its_nidne));
-  if (same_lattice && SHARED(its_types)) h.its_types = base->h.its_types; else TRY(dev_copy(a, p->its_types, (size_t)h.S * TW, &h.its_types));
-  TRY(copy_reqsets(d, p->tmpl, M, K, &h.tmpl)); TRY(dev_copy(a, p->tmpl_taints, M, &h.tmpl_taints));
-  TRY(dev_copy(a, p->tmpl_daemon, (size_t)M * R, &h.tmpl_daemon)); TRY(dev_copy(a, p->tmpl_daemon_present, M, &h.tmpl_daemon_present));
-  TRY(dev_copy(a, p->tmpl_types, (size_t)M * TW, &h.tmpl_types)); TRY(dev_copy(a, p->tmpl_limit_present, M, &h.tmpl_limit_present));
-  TRY(dev_copy(a, p->tmpl_remaining, (size_t)M * R, &h.tmpl_remaining));
-  TRY(copy_reqsets(d, p->en, E, K, &h.en)); TRY(dev_copy(a, p->en_taints, E, &h.en_taints)); TRY(dev_copy(a, p->en_avail, (size_t)E * R, &h.en_avail));
-  TRY(dev_copy(a, p->en_requests, (size_t)E * R, &h.en_requests)); TRY(dev_copy(a, p->en_requests_present, E, &h.en_requests_present));
-  TRY(dev_copy(a, p->en_port_off, (size_t)E + 1, &h.en_port_off));
-  TRY(copy_reqsets(d, p->cls, C, K, &h.cls)); TRY(dev_copy(a, p->cls_hn_mode, C, &h.cls_hn_mode)); TRY(dev_copy(a, p->cls_hn_off, (size_t)C + 1, &h.cls_hn_off));
-  TRY(dev_copy(a, p->hn_list, C ? p->cls_hn_off[C] : 0, &h.hn_list));
-  TRY(dev_copy(a, p->cls_requests, (size_t)C * R, &h.cls_requests)); TRY(dev_copy(a, p->cls_requests_present, C, &h.cls_requests_present));
-  TRY(dev_copy(a, p->cls_tolerated, C, &h.cls_tolerated)); TRY(dev_copy(a, p->cls_port_off, (size_t)C + 1, &h.cls_port_off));
-  const u32 nports_static = C ? p->cls_port_off[C] : (E ? p->en_port_off[E] : 0);
-  TRY(dev_copy(a, p->ports, nports_static, &h.ports));
-  h.ND = p->ND; h.SW = p->SW;
-  TRY(dev_copy(a, p->en_vol_limit, (size_t)E * p->ND, &h.en_vol_limit)); TRY(dev_copy(a, p->en_vol_count, (size_t)E * p->ND, &h.en_vol_count)); TRY(dev_copy(a, p->en_vol_set, (size_t)E * p->SW, &h.en_vol_set));
-  TRY(dev_copy(a, p->cls_vol_off, (size_t)C + 1, &h.cls_vol_off)); TRY(dev_copy(a, p->vol_list, C ? p->cls_vol_off[C] : 0, &h.vol_list));
-  TRY(dev_copy(a, p->cls_own_off, (size_t)C + 1, &h.cls_own_off)); TRY(dev_copy(a, p->own_list, C ? p->cls_own_off[C] : 0, &h.own_list));
-  TRY(dev_copy(a, p->cls_sel_off, (size_t)C + 1, &h.cls_sel_off)); TRY(dev_copy(a, p->sel_list, C ? p->cls_sel_off[C] : 0, &h.sel_list));
-  TRY(dev_copy(a, p->cls_isel_off, (size_t)C + 1, &h.cls_isel_off)); TRY(dev_copy(a, p->isel_list, C ? p->cls_isel_off[C] : 0, &h.isel_list));
-  TRY(dev_copy(a, p->cls_iown_off, (size_t)C + 1, &h.cls_iown_off)); TRY(dev_copy(a, p->iown_list, C ? p->cls_iown_off[C] : 0, &h.iown_list));
-  TRY(dev_copy(a, p->pod_stage_off, (size_t)P + 1, &h.pod_stage_off)); TRY(dev_copy(a, p->stage_cls, P ? p->pod_stage_off[P] : 0, &h.stage_cls));
-  TRY(dev_copy(a, p->queue, P, &h.queue));
-  TRY(dev_copy(a, p->grp_type, G, &h.grp_type)); TRY(dev_copy(a, p->grp_key, G, &h.grp_key)); TRY(dev_copy(a, p->grp_max_skew, G, &h.grp_max_skew));
-  TRY(dev_copy(a, p->grp_active, G, &h.grp_active)); TRY(dev_copy(a, p->grp_filter_off, (size_t)G + 1, &h.grp_filter_off));
-  TRY(copy_reqsets(d, p->flt, p->flt.n, K, &h.flt));
-  TRY(dev_copy(a, p->grp_count, (size_t)G * 64, &h.grp_count)); TRY(dev_copy(a, p->grp_hslot, G, &h.grp_hslot));
-  TRY(dev_copy(a, p->grph_count, (size_t)p->GH * E, &h.grph_count)); TRY(dev_copy(a, p->grph_extra_pos, p->GH, &h.grph_extra_pos));
+#define UP_NEVER(f, n) TRY(dev_copy(a, p->f, (n), &h.f));
+#define UP_IF(ok, f, n) if ((ok) && SHARED(f)) h.f = base->h.f; else TRY(dev_copy(a, p->f, (n), &h.f));
+#define UP_CAT(f, n) UP_IF(true, f, n)
+#define UP_LAT(f, n) UP_IF(same_lattice, f, n)
+#define UP_NULLABLE(f, n, absent) h.f = (absent); if (p->f && p->key_zone >= 0 && p->key_ct >= 0) { UP_IF(same_pairs && base->h.f, f, n) }
+#define UP_PRICE(f, n) UP_NULLABLE(f, n, nullptr)
+#define UP_PRICE_LO(f, n) UP_NULLABLE(f, n, h.it_price)
+#define X(f, owner, count, share) UP_##share(f, count)
+#define XRS(f, n) TRY(copy_reqsets(d, p->f, (n), K, &h.f));
+  KS_PROBLEM_ARRAYS(X, XRS)
+#undef X
+#undef XRS
+#undef UP_NEVER
+#undef UP_IF
+#undef UP_CAT
+#undef UP_LAT
+#undef UP_NULLABLE
+#undef UP_PRICE
+#undef UP_PRICE_LO
   // derived tables
   h.derived_shared = share_cat ? 1u : 0u;
   if (share_cat) {
@@ -3106,7 +3113,6 @@ static int upload_impl(const ks_problem* p, int device, const ks_dev_problem* ba
   TRY(d->a.lay(device, layout)); TRY(d->a.send(d->stream));
   guard.ok = true; *out = d; return KS_OK;
 #undef SHARED
-#undef COPY_OR_SHARE
 }
 extern "C" int ks_problem_upload(const ks_problem* p, int device, ks_dev_problem** out) { return upload_impl(p, device, nullptr, out); }
 extern "C" int ks_problem_upload_shared(const ks_problem* p, const ks_dev_problem* base, ks_dev_problem** out) {

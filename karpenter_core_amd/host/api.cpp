@@ -132,16 +132,14 @@ uint64_t fingerprint_of(const ksh::Encoded& E) {
   auto vec = [&](const auto& v) { uint64_t n = v.size(); mix(&n, 8); if (n) mix(v.data(), n * sizeof(v[0])); };
   auto rs = [&](const ksh::ReqSetsStore& r) { vec(r.present); vec(r.complement); vec(r.mask); vec(r.gt); vec(r.lt); vec(r.it_state); };
   const ks_problem& p = E.prob; const uint32_t dims[16] = {p.P, p.C, p.T, p.M, p.E, p.K, p.R, p.G, p.GH, p.S, p.SC, p.max_new_nodes, p.flags, p.wellknown_mask, p.n_ct, p.n_topologies}; mix(dims, sizeof dims);
-  const ksh::Encoded& C = E.catalogue(); const ksh::Encoded& L = E.lattice();
-  vec(E.key_nvalues); vec(E.value_int); vec(C.it_present); vec(C.it_complement); vec(C.it_mask); vec(C.it_offer); vec(C.it_price); vec(C.it_alloc); vec(C.it_cap);
-  vec(L.its_inter); vec(L.its_fail); vec(L.its_nidne); vec(L.its_types); rs(E.tmpl); rs(E.en); rs(E.cls); rs(E.flt);
-  vec(E.tmpl_taints); vec(E.tmpl_types); vec(E.tmpl_daemon); vec(E.tmpl_remaining); vec(E.tmpl_daemon_present); vec(E.tmpl_limit_present);
-  vec(E.en_taints); vec(E.en_avail); vec(E.en_requests); vec(E.en_requests_present); vec(E.en_port_off);
-  vec(E.cls_hn_mode); vec(E.cls_hn_off); vec(E.hn_list); vec(E.cls_requests); vec(E.cls_requests_present); vec(E.cls_tolerated); vec(E.cls_port_off); vec(E.ports);
-  vec(E.en_vol_limit); vec(E.en_vol_count); vec(E.en_vol_set); vec(E.cls_vol_off); vec(E.vol_list);
-  vec(E.cls_own_off); vec(E.own_list); vec(E.cls_sel_off); vec(E.sel_list); vec(E.cls_isel_off); vec(E.isel_list); vec(E.cls_iown_off); vec(E.iown_list);
-  vec(E.pod_stage_off); vec(E.stage_cls); vec(E.queue); vec(E.grp_type); vec(E.grp_active); vec(E.grp_key); vec(E.grp_max_skew); vec(E.grp_count); vec(E.grp_hslot);
-  vec(E.grph_count); vec(E.grph_extra_pos); vec(E.grp_filter_off);
+  // the arrays in the table's order (include/ksolve.h KS_PROBLEM_ARRAYS), which is the order the committed fingerprints were hashed in; a PRICE_LO row is left out
+  const ksh::Encoded& own_SELF = E; const ksh::Encoded& own_CAT = E.catalogue(); const ksh::Encoded& own_LAT = E.lattice();
+  enum { SKIP_NEVER = 0, SKIP_CAT = 0, SKIP_LAT = 0, SKIP_PRICE = 0, SKIP_PRICE_LO = 1 };
+#define X(f, owner, count, share) if (!SKIP_##share) vec(own_##owner.f);
+#define XRS(f, n) rs(E.f);
+  KS_PROBLEM_ARRAYS(X, XRS)
+#undef X
+#undef XRS
   return h;
 }
 }  // namespace

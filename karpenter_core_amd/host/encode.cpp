@@ -14,6 +14,7 @@
 #include <sstream>
 #include <string_view>
 #include <thread>
+#include <type_traits>
 #include <unordered_map>
 #include <unordered_set>
 
@@ -1464,21 +1465,22 @@ struct Builder {
     p.max_new_nodes = p.P ? p.P : 1; p.flags = flags | ((pr.simulation_mode || (base && !env_mode)) ? KS_FLAG_SIMULATION : 0);
     p.lean_r8 = active_res ? 1u : 0u;      // (the kernel choice that comes with KSH_ACTIVE_RESOURCES: LEAN at up to 8 resources; ksolve.h)
     p.wellknown_mask = 0; for (uint32_t k = 0; k < K; ++k) if (wellKnown.count(E.key_names[k])) p.wellknown_mask |= 1u << k;
-    p.key_nvalues = E.key_nvalues.data(); p.value_int = E.value_int.data(); p.key_zone = key_id.at(ksp::kZone); p.key_ct = key_id.at(ksp::kCapacityType); p.n_ct = E.key_nvalues[p.key_ct];
-    const Encoded& CAT = E.catalogue(); const Encoded& LAT = E.lattice();
-    p.it_present = CAT.it_present.data(); p.it_complement = CAT.it_complement.data(); p.it_mask = CAT.it_mask.data(); p.it_alloc = CAT.it_alloc.data(); p.it_cap = CAT.it_cap.data(); p.it_offer = CAT.it_offer.data(); p.it_price = CAT.it_price.data(); p.it_price_lo = CAT.it_price_lo.data(); p.ct_spot = value_id(p.key_ct, "spot"); p.ct_ondemand = value_id(p.key_ct, "on-demand");
-    p.its_inter = LAT.its_inter.data(); p.its_fail = LAT.its_fail.data(); p.its_nidne = LAT.its_nidne.data(); p.its_types = LAT.its_types.data();
-    p.tmpl = E.tmpl.view(); p.tmpl_taints = E.tmpl_taints.data(); p.tmpl_daemon = E.tmpl_daemon.data(); p.tmpl_daemon_present = E.tmpl_daemon_present.data(); p.tmpl_types = E.tmpl_types.data();
-    p.tmpl_limit_present = E.tmpl_limit_present.data(); p.tmpl_remaining = E.tmpl_remaining.data();
-    p.en = E.en.view(); p.en_taints = E.en_taints.data(); p.en_avail = E.en_avail.data(); p.en_requests = E.en_requests.data(); p.en_requests_present = E.en_requests_present.data(); p.en_port_off = E.en_port_off.data();
-    p.cls = E.cls.view(); p.cls_hn_mode = E.cls_hn_mode.data(); p.cls_hn_off = E.cls_hn_off.data(); p.hn_list = E.hn_list.data(); p.cls_requests = E.cls_requests.data(); p.cls_requests_present = E.cls_requests_present.data();
-    p.cls_tolerated = E.cls_tolerated.data(); p.cls_port_off = E.cls_port_off.data(); p.ports = E.ports.data();
-    p.en_vol_limit = E.en_vol_limit.data(); p.en_vol_count = E.en_vol_count.data(); p.en_vol_set = E.en_vol_set.data(); p.cls_vol_off = E.cls_vol_off.data(); p.vol_list = E.vol_list.data();
-    p.cls_own_off = E.cls_own_off.data(); p.own_list = E.own_list.data(); p.cls_sel_off = E.cls_sel_off.data(); p.sel_list = E.sel_list.data();
-    p.cls_isel_off = E.cls_isel_off.data(); p.isel_list = E.isel_list.data(); p.cls_iown_off = E.cls_iown_off.data(); p.iown_list = E.iown_list.data();
-    p.pod_stage_off = E.pod_stage_off.data(); p.stage_cls = E.stage_cls.data(); p.queue = E.queue.data();
-    p.grp_type = E.grp_type.data(); p.grp_key = E.grp_key.data(); p.grp_max_skew = E.grp_max_skew.data(); p.grp_active = E.grp_active.data(); p.grp_filter_off = E.grp_filter_off.data(); p.flt = E.flt.view();
-    p.grp_count = E.grp_count.data(); p.grp_hslot = E.grp_hslot.data(); p.grph_count = E.grph_count.data(); p.grph_extra_pos = E.grph_extra_pos.data();
+    p.key_zone = key_id.at(ksp::kZone); p.key_ct = key_id.at(ksp::kCapacityType); p.n_ct = E.key_nvalues[p.key_ct]; p.ct_spot = value_id(p.key_ct, "spot"); p.ct_ondemand = value_id(p.key_ct, "on-demand");
+    wire_arrays();
+  }
+  // ks_problem's pointers, one per row of the table (include/ksolve.h KS_PROBLEM_ARRAYS), each checked as it is set: the vector behind it holds exactly the elements the
+  // table -- and with it the upload -- counts for the array.  A disagreement is this library's bug and would have the upload read past a vector.
+  void wire_arrays() {
+    ks_problem* p = &E.prob; const Encoded& own_SELF = E; const Encoded& own_CAT = E.catalogue(); const Encoded& own_LAT = E.lattice();
+    auto holds = [](const char* name, size_t have, size_t want) { if (have != want) throw std::logic_error(std::string("flattening: ") + name + " holds " + std::to_string(have) + " elements, ks_problem states " + std::to_string(want)); };
+#define X(f, owner, count, share) static_assert(std::is_same<decltype(own_##owner.f)::value_type, std::remove_cv_t<std::remove_pointer_t<decltype(ks_problem::f)>>>::value, "KS_PROBLEM_ARRAYS: element type of " #f); \
+    p->f = own_##owner.f.data(); holds(#f, own_##owner.f.size(), (count));
+#define RS1(f, m, count) static_assert(std::is_same<decltype(E.f.m)::value_type, std::remove_cv_t<std::remove_pointer_t<decltype(ks_reqsets::m)>>>::value, "ks_reqsets: element type of " #m); holds(#f "." #m, E.f.m.size(), (count));
+#define XRS(f, cnt) p->f = E.f.view(); holds(#f ".n", E.f.n, (cnt)); RS1(f, present, (cnt)) RS1(f, complement, (cnt)) RS1(f, mask, (size_t)(cnt) * p->K) RS1(f, gt, (size_t)(cnt) * p->K) RS1(f, lt, (size_t)(cnt) * p->K) RS1(f, it_state, (cnt))
+    KS_PROBLEM_ARRAYS(X, XRS)
+#undef X
+#undef RS1
+#undef XRS
   }
 
   bool specs_done = false, active_done = false;      // encode() with an EnvCache runs these two first (it needs the signature)
