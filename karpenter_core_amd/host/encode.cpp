@@ -166,7 +166,6 @@ class WorkerPool {
 };
 // body(t) for t in [0, n) on n threads (bodies must not throw)
 thread_local int tl_pool = 0;      // which pool the parallel regions of this thread use
-thread_local bool tl_sync_confirm = false;      // this thread's flattening confirms its spec merges in line (the retry after ConfirmFailed)
 struct ConfirmFailed {};
 template <class B> void run_threads(uint32_t n, B&& body) {
   if (n <= 1) { body(0u); return; }
@@ -242,7 +241,28 @@ bool same_spec(const Pod& a, const Pod& b) {
 }
 uint64_t str_hash(std::string_view s) { Hash128 h; h.bytes(s.data(), s.size()); h.finish(); return h.a ^ h.b; }
 
+// Open-addressing tables (the batch's uids, the distinct specs): a power of two of at least four slots per entry -- a function of the entry count alone -- and
+// linear probing.  probe: the slot that ends the sequence of hash `h`, which is the first whose entry `hit` accepts or else the first that holds `empty`.
+uint64_t table_slots(uint64_t n) { uint64_t cap = 64; while (cap < 4 * n) cap <<= 1; return cap; }
+template <class T, class Hit> uint64_t probe(const std::vector<T>& tab, T empty, uint64_t h, Hit&& hit) {
+  const uint64_t mask = tab.size() - 1;
+  for (uint64_t j = h & mask;; j = (j + 1) & mask) if (tab[j] == empty || hit(tab[j])) return j;
+}
+
+// The four kinds of run.  A Builder is constructed for one (its constructors) and nothing outside it writes its members.
+//   Whole         one problem flattened alone.  With an EnvCache, encode_cached opens it (open(): the specs, the signature) and, when the cache holds the flattening
+//                 of the environment for that signature, finishes it as OverEnv: a batch against that flattening (`base`) -- nothing leaves, the pods are new.
+//   Continued     a snapshot's flattening, kept for the what-ifs over it and for the next flattening of the same problem object, which may continue it (`prev`).
+//   OverSnapshot  a what-if: the pods of its candidate nodes against the snapshot's finished flattening (`base`).
+enum class Kind { Whole, Continued, OverSnapshot, OverEnv };
+
 struct Builder {
+  // Ownership.  A Builder may live longer than the call that made it: on the teardown thread (encode_cached hands it over on every way out, exceptions
+  // included), in an EnvBase, in a SnapshotBase -- and the confirmer it started (dedupe_specs) may still be reading pods then.  So it co-owns what it reads, the
+  // problem and the batch, and `pr` / `lite` are views of these two: no caller has to keep anything alive or join anything.  Two rules go with it:
+  //   - the confirmer's future is the LAST member, so it is destroyed -- waited for -- first, while everything the confirmer reads is still there;
+  //   - ~Builder never touches `E`: on a failure path the Encoded dies before the Builder does.
+  const std::shared_ptr<const ksp::Problem> src; const std::shared_ptr<const ksp::PodBatch> batch;
   Encoded& E; const ksp::Problem& pr; uint32_t flags;
   std::set<std::string> wellKnown;
   std::map<std::string, int> key_id; std::vector<std::set<std::string>> key_vals;   // pre-pass universes
@@ -270,15 +290,11 @@ struct Builder {
   std::vector<Requirement> it_cols; std::map<std::string, int> it_col_id;     // pod-side instance-type requirements (classes, topology filters; 0 = none)
   // UIDs of the batch: open-addressing table of pod indices (topology.go:66-70 excludes the batch from countDomains)
   struct UidSet {
-    const std::vector<std::string_view>* uids = nullptr; std::vector<uint32_t> tab; uint64_t mask = 0;
-    bool count(const std::string& uid) const {
-      if (tab.empty()) return false;
-      for (uint64_t i = str_hash(uid) & mask;; i = (i + 1) & mask) { const uint32_t e = tab[i]; if (!e) return false; if ((*uids)[e - 1] == uid) return true; }
-    }
+    const std::vector<std::string_view>* uids = nullptr; std::vector<uint32_t> tab;      // (an entry is a pod index + 1)
     int64_t find(const std::string& uid) const {      // the batch pod with that uid, -1 if none
-      if (tab.empty()) return -1;
-      for (uint64_t i = str_hash(uid) & mask;; i = (i + 1) & mask) { const uint32_t e = tab[i]; if (!e) return -1; if ((*uids)[e - 1] == uid) return (int64_t)e - 1; }
+      return tab.empty() ? -1 : (int64_t)tab[probe(tab, 0u, str_hash(uid), [&](uint32_t e) { return (*uids)[e - 1] == uid; })] - 1;
     }
+    bool count(const std::string& uid) const { return find(uid) >= 0; }
   } batch_uids;
   std::map<std::string, const ksp::StateNode*> node_by_name;
   bool toleratePreferNoSchedule = false;
@@ -286,24 +302,26 @@ struct Builder {
 
   // The pending batch: every pod of the problem, or -- for a what-if flattened over a shared snapshot -- the pods of its candidate nodes.
   std::vector<const Pod*> podp;                       // (binary ingress: pod i points at its SPEC, ksp::PodBatch::specs)
-  const ksp::PodBatch* lite = nullptr;                // binary ingress: the batch in compact form (uids / timestamps live there)
+  const ksp::PodBatch* const lite;                    // binary ingress: the batch in compact form (uids / timestamps live there)
   std::vector<std::string_view> uidv;                 // uid of pod i (a view into the pod object or the batch's uid bytes)
   int64_t ts_of(size_t i) const { return lite ? lite->ts[i] : podp[i]->creation_ts; }
-  const Builder* base = nullptr;                      // what-if mode: the finished flattening of the whole snapshot
-  bool env_mode = false;                              // `base` is a cached flattening of the SAME environment for another batch (EnvCache): nothing leaves, the pods are new
-  std::vector<uint8_t> env_removed;                   // env mode: the nodes that are not in state, in the role of `removed'
-  const std::vector<uint8_t>* removed = nullptr;      // what-if mode: nodes that leave the state-node list (helpers.go:48-61)
-  bool node_in_state(size_t i) const { return removed ? !(*removed)[i] : pr.nodes[i].in_state; }
+  Kind kind = Kind::Whole;
+  const Builder* base = nullptr;                      // OverSnapshot: the finished flattening of the whole snapshot; OverEnv: the cached one of the same environment
+  std::vector<uint8_t> removed;                       // OverSnapshot: nodes that leave the state-node list (helpers.go:48-61); every other kind goes by the nodes' in_state
+  bool node_in_state(size_t i) const { return kind == Kind::OverSnapshot ? !removed[i] : pr.nodes[i].in_state; }
+  const bool sync_confirm;                            // the spec merges are confirmed in line (encode()'s second attempt, after ConfirmFailed)
   std::vector<uint32_t> pod_rank;                     // base only: a pod's position in the snapshot-wide queue order
   std::vector<int> base_existing_of;                  // base only: node index -> row of the base's existing-node tables (-1: not owned)
   std::vector<ksp::ResList> base_remaining;           // base only: remainingResources with every node in state
   // ---- a snapshot's flattening after ksh_env_apply (round 6): `prev` is the flattening of the SAME ksp::Problem object before the events -- pods and nodes were
   // appended to it or left in place as tombstones, nothing moved.  Whatever of this run is a function of things that did not change is taken from it, provided the
   // universes come out the same (`warm`); every shortcut reproduces what the full run would have written, byte for byte (tests/test_env_apply.py compares fingerprints).
-  const Builder* prev = nullptr; bool warm = false, keep_warm_state = false;
+  // A Continued run keeps, for the run that continues it, what the "kept by" members below hold.  `prev`, `replaced`, `replaced_types` and solo_pod_node are borrowed
+  // for the duration of run() only: the Builder lets go of them at its end, and then stands alone (`before` and the caller's bindings may go).
+  const Builder* prev = nullptr; bool warm = false;
   std::vector<Hash128> spec_hs; std::vector<int32_t> spec_tab; std::vector<uint32_t> spec_first;      // kept by dedupe_specs: the hash of every spec's first pod, the table over them, the first pods
   std::map<std::string, int> pre_it_state_id, pre_it_col_id;      // kept by encode_it_states: the lattice's states / columns before its closure
-  std::string act_sig; std::map<std::string, int> act_key_id, act_res_id; size_t n_nodes_built = 0, n_pods_built = 0;      // kept by run(): what collect_active left, how large the problem was
+  std::string act_sig; std::map<std::string, int> act_key_id, act_res_id; size_t n_nodes_built = 0, n_pods_built = 0;      // kept by note_built(): what collect_active left, how large the problem was
   // A NODE= event replaces a node in place and bumps the change stamp of its slot (ksp::StateNode::stamp).  node_stamp_built: the stamps this flattening saw.  A run
   // that continues `prev` treats a slot whose stamp moved like a new node -- its requirement row is rebuilt -- and, since what the node carried BEFORE is in the
   // universes it adopts, asks whether that was the last use (`replaced`: the nodes the events replaced, as `prev` saw them; fixed_key_vals / fixed_res_n: the values
@@ -321,9 +339,22 @@ struct Builder {
   // daemonset, a provisioner's limits or a node's daemonset_requests names.  A name that only an instance type's capacity / overhead or a node's available / capacity
   // carries is inert (resources.Fits walks the requested names, scheduler.go:273-309 the limited ones): it gets no id and its quantities are not stored.
   bool active_res = false;
-  Builder(Encoded& e, uint32_t f) : E(e), pr(*e.src), flags(f & ~(uint32_t)KSH_ACTIVE_RESOURCES), lite(e.batch.get()), active_res((f & KSH_ACTIVE_RESOURCES) != 0) {}
-  std::chrono::steady_clock::time_point tl_ = std::chrono::steady_clock::now();
-  void sublap(const char* what) { if (!getenv("KSH_TIMING")) return; auto t1 = std::chrono::steady_clock::now(); fprintf(stderr, "      . %-26s %8.2f ms\n", what, std::chrono::duration<double, std::milli>(t1 - tl_).count()); tl_ = t1; }
+  Builder(Encoded& e, uint32_t f, bool sync_confirm_ = false)      // Whole: the problem (and the batch, if any) of `e`
+      : src(e.src), batch(e.batch), E(e), pr(*src), flags(f & ~(uint32_t)KSH_ACTIVE_RESOURCES), lite(batch.get()), sync_confirm(sync_confirm_), active_res((f & KSH_ACTIVE_RESOURCES) != 0) {}
+  // Continued: `before` (may be null) is the flattening of the SAME problem object before the events, `replaced_` / `replaced_types_` what they replaced in place as
+  // `before` saw it (encode.hpp make_snapshot_base); solo_pod_node_ (KSH_DERIVE_VOLUMES, else null): the node every pod is bound to
+  Builder(Encoded& e, uint32_t f, const Builder* before, const std::vector<ReplacedNode>* replaced_, const std::vector<ReplacedType>* replaced_types_, const int32_t* solo_pod_node_)
+      : Builder(e, f) { kind = Kind::Continued; prev = before; replaced = replaced_; replaced_types = replaced_types_; solo_pod_node = solo_pod_node_; }
+  // OverSnapshot: the candidate nodes leave the state nodes, the pods bound to them (by_node) are the batch
+  Builder(Encoded& e, uint32_t f, const Builder& snapshot, const std::vector<std::vector<uint32_t>>& by_node, const uint32_t* cand, uint32_t ncand) : Builder(e, f) {
+    kind = Kind::OverSnapshot; base = &snapshot; removed.assign(pr.nodes.size(), 0);
+    for (uint32_t i = 0; i < ncand; ++i) { if (cand[i] >= removed.size()) throw ksp::Error("candidate node out of range"); removed[cand[i]] = 1; for (uint32_t p : by_node[cand[i]]) podp.push_back(&pr.pods[p]); }
+  }
+  // KSH_TIMING: lap, a phase of the run; sublap, a step inside one
+  std::chrono::steady_clock::time_point tl_ = std::chrono::steady_clock::now(), t0_ = tl_;
+  static void lap_line(const char* fmt, const char* what, std::chrono::steady_clock::time_point& since) { if (!getenv("KSH_TIMING")) return; auto t1 = std::chrono::steady_clock::now(); fprintf(stderr, fmt, what, std::chrono::duration<double, std::milli>(t1 - since).count()); since = t1; }
+  void lap(const char* what) { lap_line("  encode %-24s %8.2f ms\n", what, t0_); }
+  void sublap(const char* what) { lap_line("      . %-26s %8.2f ms\n", what, tl_); }
 
   // ---------- universes ----------
   int key_of(const std::string& k, bool create) {
@@ -528,7 +559,7 @@ struct Builder {
       for (auto& o : it.offerings) { note_value(key_of(ksp::kZone, true), o.zone); note_value(key_of(ksp::kCapacityType, true), o.capacity_type); }
       if (!active_res) { note_res(it.capacity); note_res(it.overhead); }
     }
-    if (keep_warm_state) { fixed_key_vals = std::make_shared<const std::vector<std::set<std::string>>>(key_vals); fixed_res_n = res_id.size(); }
+    if (kind == Kind::Continued) { fixed_key_vals = std::make_shared<const std::vector<std::set<std::string>>>(key_vals); fixed_res_n = res_id.size(); }
     // node labels: only keys something else references matter (existing-node requirements are never
     // returned); values of referenced keys join the universe (they become topology domains / In sets)
     for (auto& n : pr.nodes) {
@@ -859,7 +890,7 @@ struct Builder {
   void encode_existing() {
     if (base) {      // the name / hostname indices are the snapshot's; only the row numbering depends on which nodes left
       existing_row.assign(pr.nodes.size(), -1);
-      for (size_t i = 0; i < pr.nodes.size(); ++i) if (!(*removed)[i] && base->base_existing_of[i] >= 0) { existing_row[i] = (int)E.existing.size(); E.existing.push_back((int)i); }      // (a row of the base: owned AND in state -- a node ksh_env_apply took out of state stays in the list)
+      for (size_t i = 0; i < pr.nodes.size(); ++i) if (node_in_state(i) && base->base_existing_of[i] >= 0) { existing_row[i] = (int)E.existing.size(); E.existing.push_back((int)i); }      // (a row of the base: owned AND in state -- a node ksh_env_apply took out of state stays in the list)
       E.en_port_off.assign(1, 0);
       for (int i : E.existing) { for (auto& hp : pr.nodes[i].host_ports) E.ports.push_back(port_entry(hp.ip, hp.port, hp.proto)); E.en_port_off.push_back((uint32_t)E.ports.size()); }
       return;
@@ -892,7 +923,7 @@ struct Builder {
       std::copy_n(&B.en_avail[(size_t)b * R], R, &E.en_avail[(size_t)e * R]); std::copy_n(&B.en_requests[(size_t)b * R], R, &E.en_requests[(size_t)e * R]);
     }
     std::vector<ksp::ResList> remaining = base->base_remaining;
-    if (!env_mode) for (size_t i = 0; i < pr.nodes.size(); ++i) if ((*removed)[i] && base->base_existing_of[i] >= 0) {      // (env mode: the same nodes are in state as in the cached flattening)
+    if (kind == Kind::OverSnapshot) for (size_t i = 0; i < pr.nodes.size(); ++i) if (removed[i] && base->base_existing_of[i] >= 0) {      // (OverEnv: the same nodes are in state as in the cached flattening)
       auto pl = pr.nodes[i].labels.find(ksp::kProvisionerName);
       for (uint32_t m = 0; m < M; ++m) if (E.templates[m]->has_limits && E.templates[m]->name == pl->second) for (auto& kv : remaining[m]) { auto c = pr.nodes[i].capacity.find(kv.first); if (c != pr.nodes[i].capacity.end()) kv.second += c->second; }
     }
@@ -1040,116 +1071,114 @@ struct Builder {
   // Hashing and the field-by-field confirmation run on all host threads; the table is filled in pod order so that spec ids, and
   // with them the creation order of topology groups (NewTopology's Update per pod, topology.go:72-78), do not depend on threading.
   void build_uid_table(uint32_t P, bool check_unique) {
-    uint64_t cap = 64; while (cap < 4ull * P) cap <<= 1;
-    batch_uids.uids = &uidv; batch_uids.mask = cap - 1; batch_uids.tab.assign(cap, 0);
+    std::vector<uint32_t>& tab = batch_uids.tab; batch_uids.uids = &uidv; tab.assign(table_slots(P), 0);
     for (uint32_t i = 0; i < P; ++i) {
-      uint64_t j = str_hash(uidv[i]) & batch_uids.mask;
-      for (;; j = (j + 1) & batch_uids.mask) { const uint32_t e = batch_uids.tab[j]; if (!e) break; if (check_unique && uidv[e - 1] == uidv[i]) throw ksp::Error("pod UIDs must be unique (queue.go:102-108 needs a total order)"); }
-      batch_uids.tab[j] = i + 1;
+      const uint64_t j = probe(tab, 0u, str_hash(uidv[i]), [&](uint32_t e) { return check_unique && uidv[e - 1] == uidv[i]; });
+      if (tab[j]) throw ksp::Error("pod UIDs must be unique (queue.go:102-108 needs a total order)"); tab[j] = i + 1;
     }
+  }
+  // The batch's partition into specs: pod_spec[i] = the spec of pod i, ids in order of first occurrence; first[s] = the first pod with spec s.  Four sources, below.
+  // hs / tab (the hash of every spec's first pod, the table over the specs): what a Continued run keeps for the next one; left empty by a source that has none.
+  struct SpecPartition { std::vector<int> pod_spec; std::vector<uint32_t> first; std::vector<Hash128> hs; std::vector<int32_t> tab; bool confirmed = true; };
+  // 1. The binary batch: the ingest already partitioned it (records equal word for word, then field by field across blocks), in order of first
+  // occurrence; two of its specs may still be the same spec written differently -- that costs a spec, not correctness.
+  SpecPartition specs_from_batch(uint32_t P) {
+    SpecPartition sp; sp.pod_spec.assign(lite->pod_spec.begin(), lite->pod_spec.end());      // (first[s]: the first pod whose id is one more than any before)
+    for (uint32_t i = 0; i < P && sp.first.size() < lite->specs.size(); ++i) if ((size_t)sp.pod_spec[i] == sp.first.size()) sp.first.push_back(i);
+    if (sp.first.size() != lite->specs.size()) throw std::logic_error("pod batch: spec ids out of the order of first occurrence");
+    return sp;
+  }
+  // 2. The snapshot a what-if runs over: its pods ARE snapshot pods, and the snapshot's flattening already knows which of them share a spec (a partition
+  // at least as fine as this what-if needs).  Local spec ids in order of first occurrence, as always.
+  SpecPartition specs_from_snapshot(uint32_t P) {
+    SpecPartition sp; const Pod* p0 = pr.pods.data(); std::vector<int32_t> local(base->specs.size(), -1); sp.pod_spec.assign(P, -1);
+    for (uint32_t i = 0; i < P; ++i) { const int bs = base->pod_spec[podp[i] - p0]; if (local[bs] < 0) { local[bs] = (int32_t)sp.first.size(); sp.first.push_back(i); } sp.pod_spec[i] = local[bs]; }
+    return sp;
+  }
+  // 3. The flattening before: the pods it saw keep their specs (first occurrences in pod order: appending pods cannot renumber them); only the new ones are hashed,
+  // looked up among the specs' first pods and confirmed field by field.
+  bool specs_continue() const { return prev && !pods_have_volumes && !prev->pods_have_volumes && !prev->spec_tab.empty() && prev->n_pods_built <= podp.size() && pr.cluster_pods.empty() == prev->batch_uids.tab.empty(); }
+  SpecPartition specs_from_before(uint32_t P) {
+    SpecPartition sp; const uint32_t P0 = (uint32_t)prev->n_pods_built;
+    sp.pod_spec.assign(prev->pod_spec.begin(), prev->pod_spec.begin() + P0); sp.pod_spec.resize(P, -1);
+    sp.first = prev->spec_first; sp.hs = prev->spec_hs; sp.tab = prev->spec_tab;
+    if (sp.tab.size() < table_slots(P)) {      // (the table's size is a function of P: a fresh run would have sized it so; its content is rebuilt in spec order)
+      sp.tab.assign(table_slots(P), -1);
+      for (size_t s2 = 0; s2 < sp.first.size(); ++s2) sp.tab[probe(sp.tab, -1, sp.hs[s2].a, [](int32_t) { return false; })] = (int32_t)s2;
+    }
+    for (uint32_t i = P0; i < P; ++i) {
+      const Hash128 h = spec_hash(*podp[i]);
+      const uint64_t j = probe(sp.tab, -1, h.a, [&](int32_t s2) { return sp.hs[s2].a == h.a && sp.hs[s2].b == h.b; });
+      int found = sp.tab[j];
+      if (found >= 0 && !same_pod(*podp[sp.first[found]], *podp[i])) { found = -1; for (size_t s2 = 0; s2 < sp.first.size() && found < 0; ++s2) if (same_pod(*podp[sp.first[s2]], *podp[i])) found = (int)s2; if (found < 0) { found = (int)sp.first.size(); sp.first.push_back(i); sp.hs.push_back(h); } }      // (a collision: the full run's own way out)
+      else if (found < 0) { found = (int)sp.first.size(); sp.tab[j] = found; sp.first.push_back(i); sp.hs.push_back(h); }
+      sp.pod_spec[i] = found;
+    }
+    return sp;
+  }
+  // 4. Hash and table: two pods share a spec when their 128-bit spec hashes agree; the merges are yet to be confirmed (confirm_specs).
+  SpecPartition specs_by_hash(uint32_t P) {
+    SpecPartition sp; sp.confirmed = false; std::vector<Hash128> hs(P);
+    parallel_chunks(P, [&](size_t b, size_t e, uint32_t) { for (size_t i = b; i < e; ++i) {
+      if (pods_have_volumes) { const std::vector<uint32_t> ve = vol_entries(*podp[i]); hs[i] = spec_hash(*podp[i], &ve); } else hs[i] = spec_hash(*podp[i]); } });
+    sublap("hash"); sp.pod_spec.assign(P, -1); sp.tab.assign(table_slots(P), -1);
+    for (uint32_t i = 0; i < P; ++i) {
+      const uint64_t j = probe(sp.tab, -1, hs[i].a, [&](int32_t s2) { const Hash128& o = hs[sp.first[s2]]; return o.a == hs[i].a && o.b == hs[i].b; });
+      if (sp.tab[j] < 0) { sp.tab[j] = (int32_t)sp.first.size(); sp.first.push_back(i); }
+      sp.pod_spec[i] = sp.tab[j];
+    }
+    if (kind == Kind::Continued) { sp.hs.resize(sp.first.size()); for (size_t s2 = 0; s2 < sp.first.size(); ++s2) sp.hs[s2] = hs[sp.first[s2]]; }
+    return sp;
+  }
+  // Two independent 64-bit lanes over every field: a false merge needs a 2^-128 event for random inputs, but pod specs are tenant-supplied.  Every merge is
+  // therefore confirmed field by field (on the worker pool); a pod that merely collided gets a spec of its own.
+  // The Solve of a large batch does not wait for the confirmation: it runs on a thread of its own (second worker pool) beside what follows -- the specs' copies,
+  // the universes, the signature -- and is joined before the classing (encode_pods); should it ever find a merge that does not hold, the flattening starts over
+  // with the confirmation in line (ConfirmFailed, encode()).  KSH_SYNC_CONFIRM=1 confirms in line from the start.
+  // The confirmer may read only what the Builder owns or co-owns (see Ownership): the pods through podp, pod_spec, confirm_first, the volume tables behind same_pod.
+  // Never `E`, never `base` or `prev`.  For tests: KSH_TEST_CONFIRM_FAILS makes it report a merge that does not hold; KSH_TEST_CONFIRM_DELAY_MS holds it back that many
+  // milliseconds before its first read (tests/encode_lifetime.cpp: whoever lets go of the pods too early has done so by then).
+  void confirm_specs(SpecPartition& sp, uint32_t P) {
+    if (kind != Kind::Continued && !sync_confirm && P >= 8192 && host_threads() >= 4 && !getenv("KSH_SYNC_CONFIRM")) {
+      confirm_first = sp.first;
+      try { confirmer = std::async(std::launch::async, [this, P] {
+          tl_pool = 1; std::atomic<bool> any{false};
+          if (const char* ms = getenv("KSH_TEST_CONFIRM_DELAY_MS")) std::this_thread::sleep_for(std::chrono::milliseconds(atoi(ms)));
+          parallel_chunks(P, [&](size_t b, size_t e, uint32_t) { for (size_t i = b; i < e; ++i) { const uint32_t f = confirm_first[pod_spec[i]]; if (f != i && !same_pod(*podp[f], *podp[i])) any = true; } });
+          return any.load() || getenv("KSH_TEST_CONFIRM_FAILS") != nullptr; }); return;
+      } catch (const std::system_error&) {}      // (no thread to be had: in line)
+    }
+    std::vector<uint8_t> bad(P, 0); const std::vector<uint32_t>& first = sp.first;
+    parallel_chunks(P, [&](size_t b, size_t e, uint32_t) { for (size_t i = b; i < e; ++i) { const uint32_t f = first[pod_spec[i]]; if (f != i && !same_pod(*podp[f], *podp[i])) bad[i] = 1; } });
+    for (uint32_t i = 0; i < P; ++i) if (bad[i]) {
+      int found = -1; for (size_t s2 = 0; s2 < sp.first.size() && found < 0; ++s2) if (same_pod(*podp[sp.first[s2]], *podp[i])) found = (int)s2;
+      if (found < 0) { found = (int)sp.first.size(); sp.first.push_back(i); }
+      pod_spec[i] = found; sp.tab.clear();      // (a spec found by the collision path has no slot in the table: nothing is kept, such a run is not continued)
+    }
+  }
+  // specs[s] = a deep copy (strings, vectors) of the first pod with spec s
+  void copy_specs(const std::vector<uint32_t>& first) {
+    specs.resize(first.size());
+    parallel_chunks(first.size(), [&](size_t b, size_t e, uint32_t) { for (size_t s2 = b; s2 < e; ++s2) { StageInfo st; st.spec = *podp[first[s2]]; st.spec.uid.clear(); specs[s2].stages.push_back(std::move(st)); } }, 128);
   }
   void dedupe_specs() {
     if (lite) {
-      if (base && !env_mode) throw ksp::Error("a binary pod batch cannot be a what-if over a snapshot");
+      if (kind == Kind::OverSnapshot) throw ksp::Error("a binary pod batch cannot be a what-if over a snapshot");
       podp.resize(lite->size()); uidv.resize(lite->size());
       parallel_chunks(lite->size(), [&](size_t b, size_t e, uint32_t) { for (size_t i = b; i < e; ++i) { podp[i] = &lite->specs[lite->pod_spec[i]]; uidv[i] = lite->uid(i); } });
     } else {
-      if (podp.empty() && !base) { podp.resize(pr.pods.size()); const Pod* p0 = pr.pods.data(); parallel_chunks(podp.size(), [&](size_t b, size_t e, uint32_t) { for (size_t i = b; i < e; ++i) podp[i] = p0 + i; }, 16384); }
+      if (kind != Kind::OverSnapshot) { podp.resize(pr.pods.size()); const Pod* p0 = pr.pods.data(); parallel_chunks(podp.size(), [&](size_t b, size_t e, uint32_t) { for (size_t i = b; i < e; ++i) podp[i] = p0 + i; }, 16384); }
       uidv.resize(podp.size()); parallel_chunks(podp.size(), [&](size_t b, size_t e, uint32_t) { for (size_t i = b; i < e; ++i) uidv[i] = podp[i]->uid; }, 16384);
     }
     const uint32_t P = (uint32_t)podp.size(); collect_volumes(); sublap("(start)");
-    if (lite) {
-      // The ingest already partitioned the batch into distinct specs (records equal word for word, then field by field across blocks), in order
-      // of first occurrence; two of them may still be the same spec written differently -- that costs a spec, not correctness.
-      pod_spec.assign(lite->pod_spec.begin(), lite->pod_spec.end());
-      if (!pr.cluster_pods.empty()) build_uid_table(P, true);
-      specs.resize(lite->specs.size());
-      parallel_chunks(specs.size(), [&](size_t b, size_t e, uint32_t) { for (size_t s2 = b; s2 < e; ++s2) { StageInfo st; st.spec = lite->specs[s2]; specs[s2].stages.push_back(std::move(st)); } }, 128);
-      sublap("specs from the batch");
-      return;
-    }
-    if (base && !env_mode) {
-      // What-if over a snapshot: its pods ARE snapshot pods, and the snapshot's flattening already knows which of them share a spec (a partition
-      // at least as fine as this what-if needs).  Local spec ids in order of first occurrence, as always.
-      const Pod* p0 = pr.pods.data();
-      std::vector<int32_t> local(base->specs.size(), -1); std::vector<uint32_t> first; pod_spec.assign(P, -1);
-      for (uint32_t i = 0; i < P; ++i) { const int bs = base->pod_spec[podp[i] - p0]; if (local[bs] < 0) { local[bs] = (int32_t)first.size(); first.push_back(i); } pod_spec[i] = local[bs]; }
-      if (!pr.cluster_pods.empty()) build_uid_table(P, false);      // countDomains / inverse anti-affinity ask which cluster pods are in the batch
-      specs.resize(first.size());
-      for (size_t s2 = 0; s2 < first.size(); ++s2) { StageInfo st; st.spec = *podp[first[s2]]; st.spec.uid.clear(); specs[s2].stages.push_back(std::move(st)); }
-      sublap("specs from the snapshot");
-      return;
-    }
-    if (prev && !pods_have_volumes && !prev->pods_have_volumes && !prev->spec_tab.empty() && prev->n_pods_built <= P && pr.cluster_pods.empty() == prev->batch_uids.tab.empty()) {
-      // The pods the previous flattening saw keep their specs (first occurrences in pod order: appending pods cannot renumber them); only the new ones are hashed,
-      // looked up among the specs' first pods and confirmed field by field.
-      const uint32_t P0 = (uint32_t)prev->n_pods_built;
-      pod_spec.assign(prev->pod_spec.begin(), prev->pod_spec.begin() + P0); pod_spec.resize(P, -1);
-      spec_first = prev->spec_first; spec_hs = prev->spec_hs; spec_tab = prev->spec_tab;
-      uint64_t cap = spec_tab.size();
-      if (cap < 4ull * P) {      // (the table's size is a function of P: a fresh run would have sized it so; its content is rebuilt in spec order)
-        while (cap < 4ull * P) cap <<= 1;
-        spec_tab.assign(cap, -1);
-        for (size_t s2 = 0; s2 < spec_first.size(); ++s2) { uint64_t j = spec_hs[s2].a & (cap - 1); while (spec_tab[j] >= 0) j = (j + 1) & (cap - 1); spec_tab[j] = (int32_t)s2; }
-      }
-      for (uint32_t i = P0; i < P; ++i) {
-        const Hash128 h = spec_hash(*podp[i]);
-        uint64_t j = h.a & (cap - 1); int found = -1;
-        for (;; j = (j + 1) & (cap - 1)) { const int32_t sidx = spec_tab[j]; if (sidx < 0) break; const Hash128& o = spec_hs[sidx]; if (o.a == h.a && o.b == h.b) { found = sidx; break; } }
-        if (found >= 0 && !same_pod(*podp[spec_first[found]], *podp[i])) { found = -1; for (size_t s2 = 0; s2 < spec_first.size() && found < 0; ++s2) if (same_pod(*podp[spec_first[s2]], *podp[i])) found = (int)s2; if (found < 0) { found = (int)spec_first.size(); spec_first.push_back(i); spec_hs.push_back(h); } }      // (a collision: the full run's own way out)
-        else if (found < 0) { found = (int)spec_first.size(); spec_tab[j] = found; spec_first.push_back(i); spec_hs.push_back(h); }
-        pod_spec[i] = found;
-      }
-      if (!pr.cluster_pods.empty()) build_uid_table(P, true);
-      const std::vector<uint32_t>& first = spec_first;
-      sublap("specs from the flattening before"); specs.resize(first.size());
-      parallel_chunks(first.size(), [&](size_t b, size_t e, uint32_t) { for (size_t s2 = b; s2 < e; ++s2) { StageInfo st; st.spec = *podp[first[s2]]; st.spec.uid.clear(); specs[s2].stages.push_back(std::move(st)); } }, 128);
-      return;
-    }
-    std::vector<Hash128> hs(P);
-    parallel_chunks(P, [&](size_t b, size_t e, uint32_t) { for (size_t i = b; i < e; ++i) {
-      if (pods_have_volumes) { const std::vector<uint32_t> ve = vol_entries(*podp[i]); hs[i] = spec_hash(*podp[i], &ve); } else hs[i] = spec_hash(*podp[i]);
-      } });
-    sublap("hash"); uint64_t cap = 64; while (cap < 4ull * P) cap <<= 1;
-    if (!pr.cluster_pods.empty()) build_uid_table(P, true);      // countDomains / inverse anti-affinity ask which cluster pods are in the batch; without cluster pods nobody asks, and the
-                                                                 // uniqueness of the UIDs is checked on the sorted queue instead (encode_pods)
-    sublap("uid table"); pod_spec.assign(P, -1);
-    std::vector<int32_t> tab(cap, -1); std::vector<uint32_t> first;      // table of spec ids; first[s] = first pod with spec s
-    for (uint32_t i = 0; i < P; ++i) {
-      uint64_t j = hs[i].a & (cap - 1);
-      for (;; j = (j + 1) & (cap - 1)) { const int32_t sidx = tab[j]; if (sidx < 0) break; const Hash128& o = hs[first[sidx]]; if (o.a == hs[i].a && o.b == hs[i].b) { pod_spec[i] = sidx; break; } }
-      if (pod_spec[i] < 0) { tab[j] = (int32_t)first.size(); pod_spec[i] = (int32_t)first.size(); first.push_back(i); }
-    }
-    sublap("spec table");
-    // Two pods share a spec when their 128-bit spec hashes agree (two independent 64-bit lanes over every field: a false merge
-    // needs a 2^-128 event for random inputs, but pod specs are tenant-supplied).  Every merge is therefore confirmed field by field (on the
-    // worker pool; KSH_NO_CONFIRM_SPECS=1 skips it for A/B timing only); a pod
-    // that merely collided would get a spec of its own.
-    // The Solve of a large batch does not wait for the confirmation: it runs on a thread of its own (second worker pool) beside what follows -- the specs' copies,
-    // the universes, the signature -- and is joined before the classing (encode_pods); should it ever find a merge that does not hold, the flattening starts over
-    // with the confirmation in line (ConfirmFailed, encode()).
-    if (!keep_warm_state && !tl_sync_confirm && P >= 8192 && host_threads() >= 4 && !getenv("KSH_NO_CONFIRM_SPECS") && !getenv("KSH_SYNC_CONFIRM")) {
-      confirm_first = first;
-      try {
-        confirmer = std::async(std::launch::async, [this, P] {
-          tl_pool = 1; std::atomic<bool> any{false};
-          parallel_chunks(P, [&](size_t b, size_t e, uint32_t) { for (size_t i = b; i < e; ++i) { const uint32_t f = confirm_first[pod_spec[i]]; if (f != i && !same_pod(*podp[f], *podp[i])) any = true; } });
-          return any.load() || getenv("KSH_TEST_CONFIRM_FAILS") != nullptr; });
-      } catch (const std::system_error&) {}
-    }
-    std::vector<uint8_t> bad(P, 0);
-    if (!confirmer.valid() && !getenv("KSH_NO_CONFIRM_SPECS")) parallel_chunks(P, [&](size_t b, size_t e, uint32_t) { for (size_t i = b; i < e; ++i) { const uint32_t f = first[pod_spec[i]]; if (f != i && !same_pod(*podp[f], *podp[i])) bad[i] = 1; } });
-    for (uint32_t i = 0; i < P; ++i) if (bad[i]) {
-      int found = -1; for (size_t s2 = 0; s2 < first.size() && found < 0; ++s2) if (same_pod(*podp[first[s2]], *podp[i])) found = (int)s2;
-      if (found < 0) { found = (int)first.size(); first.push_back(i); }
-      pod_spec[i] = found;
-    }
-    sublap("confirm"); specs.resize(first.size());
-    if (keep_warm_state) {      // (what the next flattening of this snapshot starts from; a spec found by the collision path has no slot in the table -- such a run is not continued)
-      bool clean = true; for (uint32_t i = 0; i < P && clean; ++i) if (bad[i]) clean = false;
-      if (clean) { spec_first = first; spec_tab = tab; spec_hs.resize(first.size()); for (size_t s2 = 0; s2 < first.size(); ++s2) spec_hs[s2] = hs[first[s2]]; }
-    }
-    parallel_chunks(first.size(), [&](size_t b, size_t e, uint32_t) { for (size_t s2 = b; s2 < e; ++s2) { StageInfo st; st.spec = *podp[first[s2]]; st.spec.uid.clear(); specs[s2].stages.push_back(std::move(st)); } }, 128);      // (a spec is a deep copy of a pod: strings, vectors)
+    SpecPartition sp = lite ? specs_from_batch(P) : kind == Kind::OverSnapshot ? specs_from_snapshot(P) : specs_continue() ? specs_from_before(P) : specs_by_hash(P);
+    sublap(lite ? "specs from the batch" : kind == Kind::OverSnapshot ? "specs from the snapshot" : sp.confirmed ? "specs from the flattening before" : "spec table");
+    // countDomains / inverse anti-affinity ask which cluster pods are in the batch; without cluster pods nobody asks, and the uniqueness of the UIDs is checked on the sorted queue instead (encode_pods)
+    if (!pr.cluster_pods.empty()) { build_uid_table(P, kind != Kind::OverSnapshot); sublap("uid table"); }      // (a what-if's pods are the snapshot's: unique there)
+    pod_spec = std::move(sp.pod_spec);
+    if (!sp.confirmed) { confirm_specs(sp, P); sublap("confirm"); }
+    if (kind == Kind::Continued && !sp.tab.empty()) { spec_first = sp.first; spec_hs = std::move(sp.hs); spec_tab = std::move(sp.tab); }      // (what the next flattening of this snapshot starts from)
+    copy_specs(sp.first); sublap("spec copies");
   }
 
   void encode_pods() {
@@ -1158,7 +1187,7 @@ struct Builder {
     // before the chains below grow the specs' stage vectors
     if (confirmer.valid() && confirmer.get()) throw ConfirmFailed();      // (the batch's partition into specs, confirmed beside the work since dedupe_specs)
     std::future<void> sorter;
-    if (!(base && !env_mode)) {
+    if (kind != Kind::OverSnapshot) {
       spec_cm.resize(specs.size());
       parallel_chunks(specs.size(), [&](size_t b, size_t e, uint32_t) { for (size_t s2 = b; s2 < e; ++s2) { const ksp::ResList rq = RequestsForPod(specs[s2].stages[0].spec);
         auto c = rq.find("cpu"), m = rq.find("memory"); spec_cm[s2] = {c == rq.end() ? 0 : c->second, m == rq.end() ? 0 : m->second}; } }, 256);
@@ -1206,7 +1235,7 @@ struct Builder {
     E.stage_cls.resize(E.pod_stage_off[P]);
     parallel_chunks(P, [&](size_t b, size_t e, uint32_t) { for (size_t i = b; i < e; ++i) { const auto& cl = specs[pod_spec[i]].cls; std::copy(cl.begin(), cl.end(), E.stage_cls.begin() + E.pod_stage_off[i]); } });
     // NewQueue: byCPUAndMemoryDescending, queue.go:74-110
-    if (base && !env_mode) {      // the order is a total order on pods: a what-if's queue is its pods in the snapshot's order
+    if (kind == Kind::OverSnapshot) {      // the order is a total order on pods: a what-if's queue is its pods in the snapshot's order
       const Pod* p0 = pr.pods.data(); std::vector<std::pair<uint32_t, uint32_t>> k(P);
       for (uint32_t i = 0; i < P; ++i) k[i] = {base->pod_rank[podp[i] - p0], i};
       std::sort(k.begin(), k.end());
@@ -1231,15 +1260,14 @@ struct Builder {
     auto be64 = [](std::string_view s2, size_t off) { uint64_t v = 0; for (size_t j = 0; j < 8; ++j) v = (v << 8) | (off + j < s2.size() ? (unsigned char)s2[off + j] : 0u); return v; };
     parallel_chunks(P, [&](size_t b, size_t e, uint32_t) { for (size_t i = b; i < e; ++i) { const auto& cm0 = spec_cm[pod_spec[i]]; const std::string_view u = uidv[i];
       keys[i] = QKey{cm0.first, cm0.second, ts_of(i), be64(u, 0), be64(u, 8), (uint32_t)i, (uint32_t)u.size()}; } });
-    auto less = [&](const QKey& a, const QKey& b) {
-      if (a.cpu != b.cpu) return a.cpu > b.cpu;
-      if (a.mem != b.mem) return a.mem > b.mem;
+    auto lessb = [&](const QKey& a, const QKey& b) {      // inside a (cpu, memory) bucket
       if (a.ts != b.ts) return a.ts < b.ts;
       if (a.u0 != b.u0) return a.u0 < b.u0;
       if (a.u1 != b.u1) return a.u1 < b.u1;
       if (a.ulen <= 16 && b.ulen <= 16) return a.ulen < b.ulen;          // equal 16-byte prefixes incl. zero padding: the shorter one is a prefix (NUL bytes inside a uid fall through to the full compare)
       return uidv[a.pod] < uidv[b.pod];
     };
+    auto less = [&](const QKey& a, const QKey& b) { if (a.cpu != b.cpu) return a.cpu > b.cpu; if (a.mem != b.mem) return a.mem > b.mem; return lessb(a, b); };
     // cpu and memory are a function of the spec, so the queue falls into a few (cpu, memory) buckets -- 30 for BASELINE configs[2] -- whose order is
     // known at once; inside a bucket only (timestamp, uid) decide.  Buckets are counted, filled and sorted independently on the worker threads; a
     // batch that is mostly ONE bucket takes the chunked merge sort below instead.
@@ -1257,13 +1285,6 @@ struct Builder {
         if (biggest <= P / 3) {
           std::vector<QKey> sorted(P); { std::vector<size_t> at(off.begin(), off.end() - 1); for (uint32_t i = 0; i < P; ++i) sorted[at[bucket_of[pod_spec[i]]]++] = keys[i]; }
           std::atomic<size_t> next{0};
-          auto lessb = [&](const QKey& a, const QKey& b) {
-            if (a.ts != b.ts) return a.ts < b.ts;
-            if (a.u0 != b.u0) return a.u0 < b.u0;
-            if (a.u1 != b.u1) return a.u1 < b.u1;
-            if (a.ulen <= 16 && b.ulen <= 16) return a.ulen < b.ulen;
-            return uidv[a.pod] < uidv[b.pod];
-          };
           run_threads((uint32_t)std::min<size_t>(host_threads(), NB), [&](uint32_t) { for (;;) { const size_t b = next.fetch_add(1); if (b >= NB) return; std::sort(sorted.begin() + off[b], sorted.begin() + off[b + 1], lessb); } });
           keys.swap(sorted); bucketed = true;
         }
@@ -1286,7 +1307,7 @@ struct Builder {
                                                                                                                  keys[i].cpu == keys[i - 1].cpu && keys[i].mem == keys[i - 1].mem && uidv[keys[i].pod] == uidv[keys[i - 1].pod]) dup = true; });
       if (dup) throw ksp::Error("pod UIDs must be unique (queue.go:102-108 needs a total order)"); }
     E.queue.resize(P); for (uint32_t i = 0; i < P; ++i) E.queue[i] = keys[i].pod;
-    if (keep_warm_state || !env_mode) { pod_rank.resize(P); for (uint32_t i = 0; i < P; ++i) pod_rank[E.queue[i]] = i; }      // (read by the what-ifs over a snapshot: not by a Solve over a cached environment)
+    if (kind != Kind::OverEnv) { pod_rank.resize(P); for (uint32_t i = 0; i < P; ++i) pod_rank[E.queue[i]] = i; }      // (read by the what-ifs over a snapshot: not by a Solve over a cached environment)
   }
 
   // class_of in two halves: the PURE one -- the signature of everything Node.Add reads of the stage but the ids the serial half hands out (label set, topology groups) --
@@ -1411,7 +1432,7 @@ struct Builder {
     // instance-type requirement by a class's, node.go:79 / existingnode.go:102); it_state_of appends while we iterate.
     if (it_reqs.empty()) it_reqs.push_back(Requirement());   // state 0 placeholder ("absent")
     if (it_cols.empty()) it_cols.push_back(Requirement());
-    if (keep_warm_state) { pre_it_state_id = it_state_id; pre_it_col_id = it_col_id; }
+    if (kind == Kind::Continued) { pre_it_state_id = it_state_id; pre_it_col_id = it_col_id; }
     if (warm && !prev->pre_it_state_id.empty() && it_state_id == prev->pre_it_state_id && it_col_id == prev->pre_it_col_id && it_reqs.size() == prev->pre_it_state_id.size() + 1) {
       // the same node-side states and pod-side columns in the same order, over the same catalogue: the closure and its tables are the previous flattening's
       const Encoded& B = prev->E;
@@ -1462,7 +1483,7 @@ struct Builder {
   void finish() {
     ks_problem& p = E.prob;
     p.P = (uint32_t)podp.size(); p.C = E.cls.n; p.T = T; p.M = (uint32_t)E.templates.size(); p.E = (uint32_t)E.existing.size(); p.K = K; p.R = R;
-    p.max_new_nodes = p.P ? p.P : 1; p.flags = flags | ((pr.simulation_mode || (base && !env_mode)) ? KS_FLAG_SIMULATION : 0);
+    p.max_new_nodes = p.P ? p.P : 1; p.flags = flags | ((pr.simulation_mode || kind == Kind::OverSnapshot) ? KS_FLAG_SIMULATION : 0);
     p.lean_r8 = active_res ? 1u : 0u;      // (the kernel choice that comes with KSH_ACTIVE_RESOURCES: LEAN at up to 8 resources; ksolve.h)
     p.wellknown_mask = 0; for (uint32_t k = 0; k < K; ++k) if (wellKnown.count(E.key_names[k])) p.wellknown_mask |= 1u << k;
     p.key_zone = key_id.at(ksp::kZone); p.key_ct = key_id.at(ksp::kCapacityType); p.n_ct = E.key_nvalues[p.key_ct]; p.ct_spot = value_id(p.key_ct, "spot"); p.ct_ondemand = value_id(p.key_ct, "on-demand");
@@ -1483,39 +1504,35 @@ struct Builder {
 #undef XRS
   }
 
-  bool specs_done = false, active_done = false;      // encode() with an EnvCache runs these two first (it needs the signature)
-  // env mode: the batch against the cached flattening of its environment -- everything that does not depend on the pods is adopted
-  void run_env() {
-    const bool timing = getenv("KSH_TIMING") != nullptr; auto t0 = std::chrono::steady_clock::now();
-    adopt_base(); encode_existing(); encode_pods(); encode_existing_rest_from_base(); encode_groups(); encode_it_states(); encode_volumes(); finish();
-    if (timing) fprintf(stderr, "  encode %-24s %8.2f ms\n", "batch over cached env", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
-  }
-  void run() {
-    const bool timing = getenv("KSH_TIMING") != nullptr;
-    auto t0 = std::chrono::steady_clock::now();
-    auto lap = [&](const char* what) { if (!timing) return; auto t1 = std::chrono::steady_clock::now(); fprintf(stderr, "  encode %-24s %8.2f ms\n", what, std::chrono::duration<double, std::milli>(t1 - t0).count()); t0 = t1; };
-    if (base) {      // a what-if over a shared snapshot: catalogue, universes, templates and state-node rows come from the snapshot's flattening
-      adopt_base(); dedupe_specs(); encode_existing(); encode_pods(); encode_existing_rest_from_base(); encode_groups(); encode_it_states(); encode_volumes(); finish(); lap("what-if over shared snapshot");
-      return;
-    }
-    if (!specs_done) { dedupe_specs(); lap("dedupe_specs"); }
-    if (!active_done) collect_active();
-    if (keep_warm_state) { act_sig = active_signature(); act_key_id = key_id; act_res_id = res_id; n_nodes_built = pr.nodes.size(); n_pods_built = podp.size();
-      node_stamp_built.resize(pr.nodes.size()); for (size_t i = 0; i < pr.nodes.size(); ++i) node_stamp_built[i] = pr.nodes[i].stamp;
-      it_stamp_built.resize(pr.instance_types.size()); for (size_t t = 0; t < pr.instance_types.size(); ++t) it_stamp_built[t] = pr.instance_types[t].stamp; }
-    warm = can_continue();
+  // ---------- the kinds of run: each one's phases, in order ----------
+  // Whole and Continued.  The first half is all that encode_cached needs before it knows how the run ends: open() returns the signature it looks the environment up by.
+  void begin() { dedupe_specs(); lap("dedupe_specs"); collect_active(); }
+  std::string open() { begin(); return active_signature(); }
+  void finish_whole() {
+    if (kind == Kind::Continued) note_built();
+    warm = can_continue();      // (false at once unless there is a flattening before)
     collect_passive(); lap(warm ? "universes (continued)" : "collect_universes");
     encode_instance_types(); lap("encode_instance_types");
     it_reqs.push_back(Requirement()); it_cols.push_back(Requirement());   // state / column 0 == key absent
     encode_templates(); lap("encode_templates");
-    encode_existing();
-    collect_taints(); lap("encode_existing+taints");
+    encode_existing(); collect_taints(); lap("encode_existing+taints");
     encode_pods(); lap("encode_pods");
     encode_existing_rest(); lap("encode_existing_rest");
     encode_groups(); lap("encode_groups");
     encode_it_states(); lap("encode_it_states");
-    encode_volumes();
-    finish(); lap("finish");
+    encode_volumes(); finish(); lap("finish");
+    prev = nullptr; replaced = nullptr; replaced_types = nullptr; solo_pod_node = nullptr;      // (borrowed for the run: this flattening now stands alone)
+  }
+  // OverSnapshot and OverEnv: catalogue, universes, templates and state-node rows are the base's; a what-if's specs come from the snapshot's, a batch's were made by open()
+  void run_over_snapshot() { adopt_base(); dedupe_specs(); encode_existing(); encode_pods(); encode_existing_rest_from_base(); encode_groups(); encode_it_states(); encode_volumes(); finish(); lap("what-if over shared snapshot"); }
+  // (after open(): `env` is the flattening of the same environment for the same signature, `env_enc` its Encoded, whose catalogue E then shares)
+  void finish_over_env(const Builder& env, std::shared_ptr<const Encoded> env_enc) { kind = Kind::OverEnv; base = &env; E.shared = std::move(env_enc);
+                             adopt_base();                 encode_existing(); encode_pods(); encode_existing_rest_from_base(); encode_groups(); encode_it_states(); encode_volumes(); finish(); lap("batch over cached env"); }
+  void run() { if (kind == Kind::OverSnapshot) run_over_snapshot(); else { begin(); finish_whole(); } }
+  void note_built() {      // what a Continued run leaves for can_continue() of the next: what collect_active found, how large the problem was, the change stamps it saw
+    act_sig = active_signature(); act_key_id = key_id; act_res_id = res_id; n_nodes_built = pr.nodes.size(); n_pods_built = podp.size();
+    node_stamp_built.resize(pr.nodes.size()); for (size_t i = 0; i < pr.nodes.size(); ++i) node_stamp_built[i] = pr.nodes[i].stamp;
+    it_stamp_built.resize(pr.instance_types.size()); for (size_t t = 0; t < pr.instance_types.size(); ++t) it_stamp_built[t] = pr.instance_types[t].stamp;
   }
 };
 
@@ -1550,44 +1567,37 @@ void dispose_later(std::shared_ptr<const void> p) { Reaper::get().take(std::cons
 struct EnvBase { std::string sig; uint32_t flags = 0; std::shared_ptr<Encoded> enc; std::unique_ptr<Builder> builder; };
 EnvCache::EnvCache() {}
 EnvCache::~EnvCache() {}
-static std::unique_ptr<Encoded> encode_cached(std::unique_ptr<Encoded> e, uint32_t flags, EnvCache* cache) {
+static std::unique_ptr<Encoded> encode_cached(std::unique_ptr<Encoded> e, uint32_t flags, EnvCache* cache, bool sync_confirm /* Builder::sync_confirm */) {
   static const bool off = getenv("KSH_NO_ENV_CACHE") != nullptr;
   // (the builder's working set -- a deep copy of every distinct spec, the per-pod tables -- is torn down on a thread of its own, while the GPU solves: a millisecond
   // of free() that Solve's caller need not wait for)
-  auto bp = std::make_shared<Builder>(*e, flags); Builder& b = *bp;
+  auto bp = std::make_shared<Builder>(*e, flags, sync_confirm); Builder& b = *bp;
   struct Hand { std::shared_ptr<Builder>& p; ~Hand() { Reaper::get().take(std::move(p)); } } hand{bp};      // (on every way out)
   if (!cache || off) { b.run(); return e; }
-  const bool timing = getenv("KSH_TIMING") != nullptr; auto t0 = std::chrono::steady_clock::now();
-  b.dedupe_specs(); b.specs_done = true; b.collect_active(); b.active_done = true;
-  const std::string sig = b.active_signature();
-  if (timing) fprintf(stderr, "  encode %-24s %8.2f ms\n", "dedupe + signature", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+  const std::string sig = b.open();
   std::shared_ptr<const EnvBase> eb;
   { std::lock_guard<std::mutex> g(cache->mu); if (cache->base && cache->base->sig == sig && cache->base->flags == flags) eb = cache->base; }
   if (!eb) {
     // first batch with this signature: flatten completely (this batch is as good as any to close the universes over) and keep the result;
     // the batch itself then takes the same road every later one takes, so that a hit and a miss produce the same flat problem
     auto nb = std::make_shared<EnvBase>(); nb->sig = sig; nb->flags = flags; nb->enc = std::make_shared<Encoded>(); nb->enc->src = e->src; nb->enc->batch = e->batch;
-    nb->builder = std::make_unique<Builder>(*nb->enc, flags); nb->builder->run();
+    nb->builder = std::make_unique<Builder>(*nb->enc, flags, sync_confirm); nb->builder->run();
     eb = nb; std::lock_guard<std::mutex> g(cache->mu); cache->base = nb;
   }
-  b.base = eb->builder.get(); b.env_mode = true; e->shared = eb->enc;
-  b.env_removed.assign(e->src->nodes.size(), 0); for (size_t i = 0; i < e->src->nodes.size(); ++i) b.env_removed[i] = e->src->nodes[i].in_state ? 0 : 1;
-  b.removed = &b.env_removed;
-  b.run_env();
+  b.finish_over_env(*eb->builder, eb->enc);
   return e;
 }
 std::unique_ptr<Encoded> encode(std::shared_ptr<const ksp::Problem> pr, uint32_t flags, EnvCache* cache) {
   for (int attempt = 0;; ++attempt) {
     auto e = std::make_unique<Encoded>(); e->src = pr;
-    struct Flag { bool was = tl_sync_confirm; ~Flag() { tl_sync_confirm = was; } } flag; if (attempt) tl_sync_confirm = true;
-    try { return encode_cached(std::move(e), flags, cache); } catch (const ConfirmFailed&) { if (attempt) throw std::logic_error("spec confirmation failed twice"); }
+    try { return encode_cached(std::move(e), flags, cache, attempt != 0); } catch (const ConfirmFailed&) { if (attempt) throw std::logic_error("spec confirmation failed twice"); }
   }
 }
 
 std::unique_ptr<Encoded> encode(std::shared_ptr<const ksp::Problem> env, std::shared_ptr<const ksp::PodBatch> batch, uint32_t flags, EnvCache* cache) {
   if (!env->pods.empty()) throw ksp::Error("the environment of a binary pod batch must carry no pods of its own (PODS 0)");
   auto e = std::make_unique<Encoded>(); e->src = std::move(env); e->batch = std::move(batch);
-  return encode_cached(std::move(e), flags, cache);
+  return encode_cached(std::move(e), flags, cache, false);      // (a batch's specs are the ingest's: nothing to confirm)
 }
 
 // Binary pod ingress (include/kshost.h, kspb.hpp).  Per block: hash every record (all host threads), partition the block's pods by
@@ -1628,18 +1638,13 @@ std::shared_ptr<const ksp::PodBatch> ingest_pod_blocks(const ksh_pod_block* bloc
   std::vector<Local> loc(nb); std::vector<std::exception_ptr> errs(nb);
   run_threads(nb, [&](uint32_t b) { try {
     const ksh_pod_block& B = blocks[b]; Local& L = loc[b]; const uint32_t n = B.n_pods; L.of.resize(n);
-    uint64_t cap = 64; while (cap < 4ull * n) cap <<= 1;
-    std::vector<int32_t> tab(cap, -1);
+    std::vector<int32_t> tab(table_slots(n), -1);
     for (uint32_t i = 0; i < n; ++i) {
-      const Hash128& h = hs[pod0[b] + i]; const uint32_t len = B.spec_off[i + 1] - B.spec_off[i]; int32_t found = -1;
-      uint64_t j = h.a & (cap - 1);
-      for (;; j = (j + 1) & (cap - 1)) {
-        const int32_t sidx = tab[j]; if (sidx < 0) break;
-        const uint32_t f = L.first[sidx]; const Hash128& o = hs[pod0[b] + f];
-        if (o.a == h.a && o.b == h.b && B.spec_off[f + 1] - B.spec_off[f] == len && memcmp(B.spec_words + B.spec_off[f], B.spec_words + B.spec_off[i], 4 * (size_t)len) == 0) { found = sidx; break; }
-      }
-      if (found < 0) { found = (int32_t)L.first.size(); tab[j] = found; L.first.push_back(i); }
-      L.of[i] = (uint32_t)found;
+      const Hash128& h = hs[pod0[b] + i]; const uint32_t len = B.spec_off[i + 1] - B.spec_off[i];
+      const uint64_t j = probe(tab, -1, h.a, [&](int32_t sidx) { const uint32_t f = L.first[sidx]; const Hash128& o = hs[pod0[b] + f];
+        return o.a == h.a && o.b == h.b && B.spec_off[f + 1] - B.spec_off[f] == len && memcmp(B.spec_words + B.spec_off[f], B.spec_words + B.spec_off[i], 4 * (size_t)len) == 0; });
+      if (tab[j] < 0) { tab[j] = (int32_t)L.first.size(); L.first.push_back(i); }
+      L.of[i] = (uint32_t)tab[j];
     } } catch (...) { errs[b] = std::current_exception(); } });
   for (auto& e : errs) if (e) std::rethrow_exception(e);
   lap("partition blocks");
@@ -1656,13 +1661,13 @@ std::shared_ptr<const ksp::PodBatch> ingest_pod_blocks(const ksh_pod_block* bloc
     } }, 64);
   lap("decode distinct");
   auto same_volumes = [](const Pod& a, const Pod& b) { if (a.volume_error != b.volume_error || a.volumes.size() != b.volumes.size()) return false; for (size_t i = 0; i < a.volumes.size(); ++i) if (a.volumes[i].driver != b.volumes[i].driver || a.volumes[i].pvc != b.volumes[i].pvc) return false; return true; };
-  { uint64_t cap = 64; while (cap < 4ull * D) cap <<= 1; std::vector<int32_t> tab(cap, -1); std::vector<size_t> rep;      // rep[g] = index into dec of global spec g
+  { std::vector<int32_t> tab(table_slots(D), -1); std::vector<size_t> rep;      // rep[g] = index into dec of global spec g
     for (uint32_t b = 0; b < nb; ++b) { loc[b].global.resize(loc[b].first.size());
       for (size_t l = 0; l < loc[b].first.size(); ++l) {
-        const size_t x = d0[b] + l; int32_t found = -1; uint64_t j = dh[x].a & (cap - 1);
-        for (;; j = (j + 1) & (cap - 1)) { const int32_t g = tab[j]; if (g < 0) break; const size_t y = rep[g]; if (dh[y].a == dh[x].a && dh[y].b == dh[x].b && same_spec(dec[y], dec[x]) && same_volumes(dec[y], dec[x])) { found = g; break; } }
-        if (found < 0) { found = (int32_t)rep.size(); tab[j] = found; rep.push_back(x); }
-        loc[b].global[l] = (uint32_t)found;
+        const size_t x = d0[b] + l;
+        const uint64_t j = probe(tab, -1, dh[x].a, [&](int32_t g) { const size_t y = rep[g]; return dh[y].a == dh[x].a && dh[y].b == dh[x].b && same_spec(dec[y], dec[x]) && same_volumes(dec[y], dec[x]); });
+        if (tab[j] < 0) { tab[j] = (int32_t)rep.size(); rep.push_back(x); }
+        loc[b].global[l] = (uint32_t)tab[j];
       } }
     out->specs.reserve(rep.size()); for (size_t x : rep) out->specs.push_back(std::move(dec[x])); }
   lap("merge across blocks");
@@ -1781,11 +1786,9 @@ std::shared_ptr<const SnapshotBase> make_snapshot_base(std::shared_ptr<const ksp
   // pod_node[i] = -1: a pod that is bound nowhere any more (ksh_env_apply keeps it in place: nothing that points into the problem moves); it is in no what-if's batch
   for (size_t i = 0; i < snapshot->pods.size(); ++i) { if (pod_node[i] < 0) continue; if ((size_t)pod_node[i] >= snapshot->nodes.size()) throw ksp::Error("pod_node out of range"); sb->by_node[pod_node[i]].push_back((uint32_t)i); }
   sb->enc = std::make_shared<Encoded>(); sb->enc->src = snapshot;
-  sb->builder = std::make_unique<Builder>(*sb->enc, flags); sb->builder->keep_warm_state = true;
-  if (before && before->snapshot.get() == snapshot.get() && before->volumes == sb->volumes && !getenv("KSH_NO_WARM_SNAPSHOT")) { sb->builder->prev = before->builder.get(); sb->builder->replaced = replaced; sb->builder->replaced_types = replaced_types; }
-  if (sb->volumes) sb->builder->solo_pod_node = pod_node;
+  const bool same_object = before && before->snapshot.get() == snapshot.get() && before->volumes == sb->volumes;
+  sb->builder = std::make_unique<Builder>(*sb->enc, flags, same_object ? before->builder.get() : nullptr, replaced, replaced_types, sb->volumes ? pod_node : nullptr);
   sb->builder->run(); sb->continued = sb->builder->warm;
-  sb->builder->prev = nullptr; sb->builder->replaced = nullptr; sb->builder->replaced_types = nullptr; sb->builder->solo_pod_node = nullptr;      // (this flattening now stands alone: `before` and the caller's bindings may go)
   {   // what deriving what-ifs on the device needs (delta_inputs)
     const Builder& b = *sb->builder; const Encoded& E = *sb->enc; const uint32_t R = b.R, M = (uint32_t)E.templates.size(); const size_t NN = snapshot->nodes.size();
     sb->node_row.assign(b.base_existing_of.begin(), b.base_existing_of.end()); sb->node_row.resize(NN, -1);
@@ -1822,9 +1825,7 @@ DeltaInputs delta_inputs(const SnapshotBase& sb) {
 std::unique_ptr<Encoded> encode_whatif(const SnapshotBase& sb, const uint32_t* cand, uint32_t ncand, uint32_t flags) {
   flags &= ~KSH_DERIVE_VOLUMES;
   auto e = std::make_unique<Encoded>(); e->src = sb.snapshot; e->shared = sb.enc;
-  std::vector<uint8_t> removed(sb.snapshot->nodes.size(), 0);
-  Builder b(*e, flags); b.base = sb.builder.get(); b.removed = &removed;
-  for (uint32_t i = 0; i < ncand; ++i) { if (cand[i] >= removed.size()) throw ksp::Error("candidate node out of range"); removed[cand[i]] = 1; for (uint32_t p : sb.by_node[cand[i]]) b.podp.push_back(&sb.snapshot->pods[p]); }
+  Builder b(*e, flags, *sb.builder, sb.by_node, cand, ncand);
   b.run();
   return e;
 }
@@ -1899,9 +1900,7 @@ std::string check_derived_topology(const SnapshotBase& sb, const uint32_t* cand,
   const Builder& bb = *sb.builder; const Encoded& EB = *sb.enc; const uint32_t G = EB.prob.G, GH = EB.prob.GH, NE = EB.prob.E, NT = EB.prob.n_topologies, GW = (G + 63) / 64;
   const size_t NN = sb.snapshot->nodes.size();
   auto e = std::make_unique<Encoded>(); e->src = sb.snapshot; e->shared = sb.enc;
-  std::vector<uint8_t> removed(NN, 0);
-  Builder wb(*e, flags); wb.base = sb.builder.get(); wb.removed = &removed;
-  for (uint32_t i = 0; i < ncand; ++i) { if (cand[i] >= NN) throw ksp::Error("candidate node out of range"); removed[cand[i]] = 1; for (uint32_t p : sb.by_node[cand[i]]) wb.podp.push_back(&sb.snapshot->pods[p]); }
+  Builder wb(*e, flags, *sb.builder, sb.by_node, cand, ncand);
   wb.run();
   const Encoded& EW = *e;
   if (sb.volumes && EB.prob.ND) { const std::string why = check_derived_volumes(sb, wb, EW); if (!why.empty()) return why; }

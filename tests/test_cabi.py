@@ -216,6 +216,27 @@ def test_headers_are_plain_c(tmp_path):
         assert "solved in" in out.stdout
 
 
+def test_failed_flattening_does_not_outlive_its_problem(tmp_path):
+    """A flattening that fails after it has started the asynchronous spec confirmer (8192 pods or more) must keep the pods alive for it: on the one-shot door the only
+    owner of the problem unwinds with the exception.  tests/encode_lifetime.cpp and host/encode.cpp are compiled together under the address and undefined-behaviour
+    sanitizers and the program is run by itself: no library, nothing loaded into this process, no GPU.  The input is refused for an instance type's Gt requirement, which
+    the universes meet right after the specs; KSH_TEST_CONFIRM_DELAY_MS holds the confirmer back until the caller has long let go, so that the outcome is no race."""
+    import subprocess
+    from karpenter_core_amd.model import Expr
+    pr = W.config3(pods=30_000, sizes=10, seed=7)
+    pr.instance_types[0].requirements.append(Expr("example.com/gen", "Gt", ["3"]))
+    ksp = tmp_path / "refused.ksp"
+    ksp.write_text(pr.to_ksp())
+    exe = str(tmp_path / "encode_lifetime")
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-omit-frame-pointer", "-pthread",
+                           "-static-libasan", "-static-libubsan",      # (the program carries its runtimes: it runs the same whatever else the environment loads)
+                           "-o", exe, os.path.join(ROOT, "tests", "encode_lifetime.cpp"), os.path.join(ROOT, "karpenter_core_amd", "host", "encode.cpp")])
+    out = subprocess.run([exe, str(ksp), "3"], capture_output=True, text=True, env=dict(os.environ, KSH_THREADS="4", KSH_TEST_CONFIRM_DELAY_MS="100"))
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert out.stdout.strip() == "ok"
+    assert "Sanitizer" not in out.stderr and "runtime error" not in out.stderr, out.stderr
+
+
 def test_pod_and_node_named_like_section_keywords():
     """KSP1's optional sections (VOL after a pod, VL / VU after a state node) are told from the next record by peeking at a bare token: the writer always emits them, so
     a pod whose uid is "VOL" (or a node called "VL" / "VU") parses as what it is."""
