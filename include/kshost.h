@@ -325,7 +325,8 @@ int ksh_validate_empty_nodes(const uint32_t* nodes, uint32_t n, const uint32_t* 
  * karpenter_core_amd/host/kspb.hpp, PdbReader): per PDB namespace:S disruptions_allowed:I selector.  The block is decoded completely before anything else happens: a
  * malformed one -- or a selector metav1.LabelSelectorAsSelector refuses -- is KS_ERR_INVALID with the PDB's index in ksh_last_error().  NULL means no PDBs.
  * Selectors are flattened for the device: the label keys some selector mentions, at most KS_CAND_MAX_KEYS, and per key the values some selector
- * mentions, at most KS_CAND_MAX_VALUES; beyond either, KS_ERR_UNSUPPORTED with both counts in the message and nothing written.
+ * mentions, at most KS_CAND_MAX_VALUES; beyond either, KS_ERR_UNSUPPORTED with both counts in the message and nothing written -- ksh_consolidation_candidates_ex with
+ * KSH_CAND_WIDE_SELECTORS has neither limit.
  *
  * out->why[node] (0 = candidate; the first reason in the reference's own order wins), out->detail[node] (-1 unless stated):
  *    1  listed in `deleting` (helpers.go:186)                2  no provisioner-name label, or it names no provisioner of the snapshot (:190)
@@ -373,6 +374,19 @@ typedef struct ksh_candidates_out {
 } ksh_candidates_out;
 int ksh_consolidation_candidates(void* parsed_snapshot, const int32_t* pod_node /* or NULL after ksh_env_apply* */, const uint32_t* deleting, uint32_t n_deleting,
                                  const ksh_candidate_inputs* in, const ksh_pdb_block* pdbs /* or NULL */, int device, ksh_candidates_out* out, double* ms /* [4] or NULL */);
+/* The same call with `flags`; ksh_consolidation_candidates is this with flags 0, and with flags 0 the route, the results, the refusals and ms[4] are that call's.
+ * KSH_CAND_WIDE_SELECTORS (opt-in, the only bit; any other is KS_ERR_INVALID): the selectors are flattened as LISTS (ksolve.h ks_selector_lists) -- per
+ * bound pod the selector-mentioned keys it carries with a value id each, per requirement an operator and a sorted list of value ids -- and decided by kernel
+ * ks_cand_pods_lists, so that label keys, values per key and values per set are unbounded: neither KS_CAND_MAX_KEYS nor KS_CAND_MAX_VALUES applies and no selector
+ * size is KS_ERR_UNSUPPORTED (only a snapshot whose bound pods carry 2^32 selector-mentioned labels, or PDBs with 2^32 values in all, is -- both counts in the message).
+ * The usual cluster, one PDB per application with `matchLabels: {app: <name>}`, needs this from its 63rd application on.  With the flag the wide route is always taken,
+ * also for selectors the narrow form could hold; every output is bit for bit the narrow route's where both answer.  The tabulation walks each bound pod's labels once
+ * (key, then value: two hash look-ups per label), not keys x pods.  Everything that is not a selector -- reasons 1-10 and 13, the provisioners' ttls, the per-node pod
+ * lists, the cached label table, the behaviour after ksh_env_apply* -- is the same code as without the flag.  ms[4] as above; with the flag ms[1] also holds the
+ * library's regrouping of PDBs and pods by namespace. */
+#define KSH_CAND_WIDE_SELECTORS 1u
+int ksh_consolidation_candidates_ex(void* parsed_snapshot, const int32_t* pod_node /* or NULL after ksh_env_apply* */, const uint32_t* deleting, uint32_t n_deleting,
+                                    const ksh_candidate_inputs* in, const ksh_pdb_block* pdbs /* or NULL */, int device, uint32_t flags, ksh_candidates_out* out, double* ms /* [4] or NULL */);
 
 /* ---- candidates of the methods the deprovisioning controller tries BEFORE consolidation (deprovisioning/controller.go:142-162): expiration, drift, emptiness.
  * ksh_consolidation_candidates' sibling: the snapshot, `pod_node`, `deleting`, the PDB block, the output arrays, ms[4] and reasons 1-7 and 10-13 mean what they mean
@@ -412,6 +426,9 @@ typedef struct ksh_deprovisioning_inputs {
 typedef struct ksh_deprovisioning_out { ksh_candidates_out base; uint32_t n_in_result, pad; } ksh_deprovisioning_out;
 int ksh_deprovisioning_candidates(void* parsed_snapshot, uint32_t method, const int32_t* pod_node /* or NULL after ksh_env_apply* */, const uint32_t* deleting, uint32_t n_deleting,
                                   const ksh_deprovisioning_inputs* in, const ksh_pdb_block* pdbs /* or NULL */, int device, ksh_deprovisioning_out* out, double* ms /* [4] or NULL */);
+/* The same call with `flags` (KSH_CAND_WIDE_SELECTORS, as for ksh_consolidation_candidates_ex); ksh_deprovisioning_candidates is this with flags 0. */
+int ksh_deprovisioning_candidates_ex(void* parsed_snapshot, uint32_t method, const int32_t* pod_node /* or NULL after ksh_env_apply* */, const uint32_t* deleting, uint32_t n_deleting,
+                                     const ksh_deprovisioning_inputs* in, const ksh_pdb_block* pdbs /* or NULL */, int device, uint32_t flags, ksh_deprovisioning_out* out, double* ms /* [4] or NULL */);
 /* Emptiness.ComputeCommand (emptiness.go:73-82), literally; host only, no simulation.  candidates[0 .. n): ksh_deprovisioning_candidates' out->base.order under
  * KSH_METHOD_EMPTINESS; n_node_pods: its out->base.n_node_pods ([node slots]).  out_nodes[0 .. *out_n_nodes) (room for n): the candidates without pods, in order --
  * the command's nodesToRemove; *out_action = KS_CMD_DELETE, or KS_CMD_DO_NOTHING when there is none. */

@@ -707,6 +707,46 @@ typedef struct ks_deprov_inputs {
 typedef struct ks_deprov_outputs { ks_candidates_outputs c; uint32_t n_in_result, pad; } ks_deprov_outputs;
 int ks_deprovisioning_candidates_host(const ks_deprov_inputs* in, ks_deprov_outputs* out, int device, double* ms /* [3] or NULL */);
 
+/* ---- the same two calls over a second flat form of the selectors: LISTS instead of one byte per (key, pod) and one u64 mask per requirement, so that the number of
+ * label keys, of values per key and of values per set is unbounded (one PDB per application, `matchLabels: {app: <name>}`, passes KS_CAND_MAX_VALUES at its 63rd
+ * application).  Everything that is not a selector -- pods, nodes, costs, reasons, order, outputs, ms -- is ks_candidates_inputs / ks_deprov_inputs as above and
+ * means what it means there; of `in` the fields n_keys, pod_val, pdb_req_key and pdb_req_mask are NOT read, pdb_ns / pdb_allowed / pdb_req_off are (pdb_req_off is
+ * the CSR of requirements per PDB, into the req_* arrays below).  Kernel ks_cand_pods_lists takes ks_cand_pods' place; the node and rank kernels are the same.
+ *   keys and values   the caller interns the label keys some selector mentions (n_keys) and, per key, the values some selector mentions: value ids
+ *                     0 .. key_n_values[key] - 1; KS_CAND_VALUE_OTHER = the pod has the key with a value no selector mentions.
+ *   pod side          a CSR per pod slot (pod_label_off) of (pod_label_key, pod_label_val) pairs: only the mentioned keys the pod CARRIES, in strictly ascending
+ *                     key order.  A key the pod lacks is not listed.  Its size goes with the labels that matter, not with keys x pods.
+ *   PDB side          per requirement req_key, req_op (KS_CAND_OP_*; matchLabels is IN with one value) and req_val[req_val_off[r] .. req_val_off[r + 1]): value ids
+ *                     of that key, strictly ascending (sorted, each once).  The list is empty for EXISTS / DOES_NOT_EXIST and for them only.
+ *   semantics         labels.Selector.Matches: IN present and a member; NOT_IN absent, or not a member (KS_CAND_VALUE_OTHER is never a member); EXISTS / DOES_NOT_EXIST
+ *                     by presence; several requirements on one key must all hold.  A PDB matches a pod iff pdb_ns == pod_ns and every requirement holds: no
+ *                     requirement matches every pod of the namespace; a nil selector is a pdb_ns no pod has.  Only a match with disruptionsAllowed == 0 blocks; per pod
+ *                     the LOWEST PDB index that blocks is reported, exactly as by the narrow form.
+ *   namespaces        pod_ns < n_namespaces for every bound pod slot, n_namespaces <= n_pods; a pdb_ns >= n_namespaces is a namespace without pods.  The library groups the blocking PDBs by
+ *                     namespace (ascending index within one) and walks the pods through a permutation sorted by namespace: a pod meets only its own namespace's PDBs.
+ * KS_ERR_INVALID (nothing launched, nothing written) beyond the narrow form's: offsets that do not start at 0 or do not ascend, a key or value id out of range, a
+ * pod's keys not strictly ascending, a value list not strictly ascending, an unknown operator, an empty list under IN / NOT_IN or values under EXISTS /
+ * DOES_NOT_EXIST, a bound pod's pod_ns >= n_namespaces, n_namespaces > n_pods.  No selector size is KS_ERR_UNSUPPORTED here: every count is a uint32_t and every uint32_t is accepted.
+ * ms as above, with the regrouping by namespace and the packing of the lists counted in [0]. */
+#define KS_CAND_VALUE_OTHER 0xFFFFFFFFu
+#define KS_CAND_OP_IN 0u
+#define KS_CAND_OP_NOT_IN 1u
+#define KS_CAND_OP_EXISTS 2u
+#define KS_CAND_OP_DOES_NOT_EXIST 3u
+typedef struct ks_selector_lists {
+  uint32_t n_keys, n_namespaces;
+  const uint32_t* key_n_values;       /* [n_keys] */
+  const uint32_t* pod_label_off;      /* [n_pods + 1] */
+  const uint32_t* pod_label_key;      /* [pod_label_off[n_pods]] */
+  const uint32_t* pod_label_val;      /* value id or KS_CAND_VALUE_OTHER */
+  const uint32_t* req_key;            /* [pdb_req_off[n_pdbs]] */
+  const uint32_t* req_op;             /* KS_CAND_OP_* */
+  const uint32_t* req_val_off;        /* [pdb_req_off[n_pdbs] + 1] */
+  const uint32_t* req_val;            /* [req_val_off[last]] */
+} ks_selector_lists;
+int ks_consolidation_candidates_lists_host(const ks_candidates_inputs* in, const ks_selector_lists* sel, ks_candidates_outputs* out, int device, double* ms /* [3] or NULL */);
+int ks_deprovisioning_candidates_lists_host(const ks_deprov_inputs* in, const ks_selector_lists* sel, ks_deprov_outputs* out, int device, double* ms /* [3] or NULL */);
+
 /* Launch-time instance-type pick of the reference's in-memory provider (cloudprovider/fake/cloudprovider.go:79-84: order the machine's
  * InstanceTypeOptions by `Offerings.Available().Requirements(reqs).Cheapest().Price`, types.go:126-145, and take the first): for problem i,
  * of new node node[i]'s InstanceTypeOptions (as left by the last ks_solve*_dev) the type whose cheapest available offering under the node's zone /

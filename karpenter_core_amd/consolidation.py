@@ -554,7 +554,7 @@ class CandidateInfo:
     ttl_seconds_after_empty: Optional[int] = None
 
 
-def _candidates_call(S, parsed, pod_node, snapshot: Snapshot, info: CandidateInfo, device: int = 0):
+def _candidates_call(S, parsed, pod_node, snapshot: Snapshot, info: CandidateInfo, device: int = 0, wide_selectors: bool = False):
     """`ksh_consolidation_candidates` over a `Snapshot` opened by `_command_snapshot`: (the call's result over every node slot, the node flags it was given)."""
     pods = [p for b in snapshot.bound for p in b] + list(snapshot.pending)
     nn = len(snapshot.nodes) + (1 if snapshot.pending else 0)
@@ -570,19 +570,20 @@ def _candidates_call(S, parsed, pod_node, snapshot: Snapshot, info: CandidateInf
           (S.KSH_CAND_POD_HAS_PRIORITY if p.uid in info.priority else 0) for p in pods]
     age = list(info.node_age_seconds) + [0.0] * (nn - len(info.node_age_seconds))
     got = S.consolidation_candidates(parsed, pod_node, nf, age, pf, [float(info.deletion_cost.get(p.uid, 0.0)) for p in pods], [int(info.priority.get(p.uid, 0)) for p in pods],
-                                     [info.consolidation_enabled], [info.ttl_seconds_until_expired], pdbs=info.pdbs, deleting=[int(j) for j in snapshot.deleting], device=device)
+                                     [info.consolidation_enabled], [info.ttl_seconds_until_expired], pdbs=info.pdbs, deleting=[int(j) for j in snapshot.deleting], device=device,
+                                     wide_selectors=wide_selectors)
     return got, nf
 
 
-def consolidation_candidates_dev(snapshot: Snapshot, info: CandidateInfo, device: int = 0, timings: Optional[dict] = None) -> dict:
+def consolidation_candidates_dev(snapshot: Snapshot, info: CandidateInfo, device: int = 0, timings: Optional[dict] = None, wide_selectors: bool = False) -> dict:
     """candidateNodes + ShouldDeprovision + sortAndFilterCandidates through `ksh_consolidation_candidates`: {"order": the candidates' node indices by disruption
     cost -- what `first_n_node_consolidation_option_dev` / `single_node_consolidation_option_dev` take as they are --, "empty": the candidates without pods in the same
     order, "why" / "detail" / "cost" / "n_node_pods" per node (kshost.h lists the reason codes)}.  Pending pods and their carrier node are not candidates' business:
-    only the snapshot's own nodes are reported."""
+    only the snapshot's own nodes are reported.  `wide_selectors`: KSH_CAND_WIDE_SELECTORS -- PDB selectors of any number of keys, values and set sizes."""
     from . import scheduler as S
     parsed, pod_node, leaving = _command_snapshot(snapshot)
     try:
-        got, _ = _candidates_call(S, parsed, pod_node, snapshot, info, device)
+        got, _ = _candidates_call(S, parsed, pod_node, snapshot, info, device, wide_selectors)
         if timings is not None:
             timings.update(got["ms"])
         n = len(snapshot.nodes)
@@ -595,7 +596,7 @@ def consolidation_candidates_dev(snapshot: Snapshot, info: CandidateInfo, device
 from .scheduler import KSH_METHOD_EXPIRATION as METHOD_EXPIRATION, KSH_METHOD_DRIFT as METHOD_DRIFT, KSH_METHOD_EMPTINESS as METHOD_EMPTINESS      # noqa: E402  (one definition)
 
 
-def _deprovisioning_call(S, parsed, pod_node, snapshot: Snapshot, info: CandidateInfo, method: int, device: int = 0):
+def _deprovisioning_call(S, parsed, pod_node, snapshot: Snapshot, info: CandidateInfo, method: int, device: int = 0, wide_selectors: bool = False):
     """`ksh_deprovisioning_candidates` over a `Snapshot` opened by `_command_snapshot`."""
     pods = [p for b in snapshot.bound for p in b] + list(snapshot.pending)
     nn = len(snapshot.nodes) + (1 if snapshot.pending else 0)
@@ -615,16 +616,16 @@ def _deprovisioning_call(S, parsed, pod_node, snapshot: Snapshot, info: Candidat
     return S.deprovisioning_candidates(parsed, method, pod_node, info.now_unix_nanos, nf, pad(info.node_creation_unix_nanos, 0), pad(info.node_age_seconds, 0.0), pf,
                                        [float(info.deletion_cost.get(p.uid, 0.0)) for p in pods], [int(info.priority.get(p.uid, 0)) for p in pods], [info.ttl_seconds_until_expired],
                                        [info.ttl_seconds_after_empty], [info.emptiness_unix_nanos.get(i) or 0 for i in range(nn)], drift_enabled=info.drift_enabled, pdbs=info.pdbs,
-                                       deleting=[int(j) for j in snapshot.deleting], device=device)
+                                       deleting=[int(j) for j in snapshot.deleting], device=device, wide_selectors=wide_selectors)
 
 
-def deprovisioning_candidates_dev(snapshot: Snapshot, info: CandidateInfo, method: int, device: int = 0, timings: Optional[dict] = None) -> dict:
+def deprovisioning_candidates_dev(snapshot: Snapshot, info: CandidateInfo, method: int, device: int = 0, timings: Optional[dict] = None, wide_selectors: bool = False) -> dict:
     """candidateNodes under Expiration / Drift / Emptiness.ShouldDeprovision (`method`: METHOD_*) through `ksh_deprovisioning_candidates`: `consolidation_candidates_dev`'s
     dict plus "n_in_result".  "order" is what Expiration / Drift.ComputeCommand walk (`replacement_command` takes it as it is); under emptiness it is the whole command."""
     from . import scheduler as S
     parsed, pod_node, leaving = _command_snapshot(snapshot)
     try:
-        got = _deprovisioning_call(S, parsed, pod_node, snapshot, info, method, device)
+        got = _deprovisioning_call(S, parsed, pod_node, snapshot, info, method, device, wide_selectors)
         if timings is not None:
             timings.update(got["ms"])
         n = len(snapshot.nodes)

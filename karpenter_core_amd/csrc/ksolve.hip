@@ -4188,11 +4188,19 @@ extern "C" int ks_replacement_commands_host(ks_dev_problem* const* ds, uint32_t 
 //   ks_deprov_nodes     one lane per node slot: the method's ShouldDeprovision in int64 nanoseconds, then the cost (the same helper as ks_cand_nodes), canBeTerminated
 //                       -- not under emptiness, whose ComputeCommand never calls it --, the final reason and detail, and the sort key (the expiration time; 0 elsewhere).
 //   ks_cand_order_key   ks_cand_order's counting rank on (int64 key, slot) instead of (cost, slot).
+// The LISTS form of the selectors (ksolve.h ks_selector_lists: any number of keys, values and set sizes) replaces the first kernel only:
+//   ks_cand_pods_lists  one lane per LISTED pod, taken through a permutation sorted by namespace, so that the lanes of a wave mostly walk the same PDB list and its
+//                       entries are same-address reads.  A lane walks the blocking PDBs of its pod's own namespace in ascending index and stops at the first that
+//                       matches; per requirement it finds the pod's value of the key in the pod's own short ascending (key, value) list and, for In / NotIn, bisects
+//                       the requirement's ascending value list.  No LDS, no atomics, no wave operation: every lane's answer is its own.
 // No product here may be fused into an addition: the pragma below keeps the one multiply and the sums apart whatever the compiler's default is.
 // ------------------------------------------------------------------------------------------------
 #define KS_CAND_BLOCK 256u
 #define KS_CAND_PDB_TILE 128u
 #define KS_CAND_REQ_TILE 1024u
+struct alignas(8) CandLabL { u32 key, val; };                  // a mentioned label a pod carries: value id or KS_CAND_VALUE_OTHER
+struct alignas(16) CandPdbL { u32 idx, r_lo, r_hi, pad; };     // a blocking PDB in its namespace's list: its original index, its requirements l_req[r_lo .. r_hi)
+struct alignas(16) CandReqL { u32 key, op, v_lo, v_hi; };      // a requirement: its value ids l_val[v_lo .. v_hi), ascending
 struct CandDev {
   u32 n_pods, n_nodes, n_pdbs, n_keys;
   const u32* pod_ns; const u32* pod_flags; const double* pod_dcost; const i32* pod_prio; const u8* pod_val;
@@ -4203,6 +4211,8 @@ struct CandDev {
   // ks_deprov_nodes / ks_cand_order_key only (unset for a consolidation call)
   u32 method, drift_enabled; i64 now; const u32* node_dflags; const i64* node_creation; const i64* node_emptiness; const i64* node_ttl_empty;
   i64* node_key;      // scratch: per node its sort key
+  // ks_cand_pods_lists only (unset on the narrow route)
+  u32 l_n_perm, l_pad; const u32* l_perm; const u32* l_lab_off; const CandLabL* l_lab; const u32* l_ns_off; const CandPdbL* l_pdb; const CandReqL* l_req; const u32* l_val;
 };
 __device__ __forceinline__ double cand_clamp(double lo, double v, double hi) { if (v < lo) return lo; if (v > hi) return hi; return v; }      // helpers.go:317-325: two comparisons
 __device__ __forceinline__ double cand_eviction_cost(u32 flags, double dcost, i32 prio) {
@@ -4243,6 +4253,32 @@ __global__ __launch_bounds__(256) void ks_cand_pods(const CandDev c) {
     }
   }
   if (live) { c.pod_cost[pod] = cand_eviction_cost(c.pod_flags[pod], c.pod_dcost[pod], c.pod_prio[pod]); c.pod_block[pod] = blk; }
+}
+// The same verdict over the lists form.  Lane i takes pod l_perm[i] (the listed pods, sorted by namespace) and writes at the pod's own slot.
+__global__ __launch_bounds__(256) void ks_cand_pods_lists(const CandDev c) {
+  const u32 i = blockIdx.x * KS_CAND_BLOCK + threadIdx.x; if (i >= c.l_n_perm) return;
+  const u32 pod = c.l_perm[i], ns = c.pod_ns[pod], l0 = c.l_lab_off[pod], l1 = c.l_lab_off[pod + 1];
+  CandLabL first{0xFFFFFFFFu, 0u}; if (l0 < l1) first = c.l_lab[l0];      // most pods carry one mentioned key: it stays in registers
+  i32 blk = -1;
+  for (u32 j = c.l_ns_off[ns], je = c.l_ns_off[ns + 1]; j < je && blk < 0; ++j) {      // ascending original index: the first match is the lowest
+    const CandPdbL b = c.l_pdb[j];
+    bool m = true;
+    for (u32 r = b.r_lo; r < b.r_hi && m; ++r) {
+      const CandReqL q = c.l_req[r];
+      bool has = first.key == q.key; u32 val = first.val;
+      if (first.key < q.key) for (u32 l = l0 + 1; l < l1; ++l) { const CandLabL x = c.l_lab[l]; if (x.key >= q.key) { has = x.key == q.key; val = x.val; break; } }      // the pod's keys ascend
+      if (q.op >= KS_CAND_OP_EXISTS) { m = has == (q.op == KS_CAND_OP_EXISTS); continue; }
+      bool member = false;
+      if (has && val != KS_CAND_VALUE_OTHER) for (u32 lo = q.v_lo, hi = q.v_hi; lo < hi;) {
+        const u32 mid = lo + ((hi - lo) >> 1), v = c.l_val[mid];
+        if (v == val) { member = true; break; }
+        if (v < val) lo = mid + 1; else hi = mid;
+      }
+      m = member == (q.op == KS_CAND_OP_IN);
+    }
+    if (m) blk = (i32)b.idx;
+  }
+  c.pod_cost[pod] = cand_eviction_cost(c.pod_flags[pod], c.pod_dcost[pod], c.pod_prio[pod]); c.pod_block[pod] = blk;
 }
 // disruptionCost x calculateLifetimeRemaining of node nd's pods [lo, hi), and on the way the first pod a PDB blocks (that PDB) and the first do-not-evict pod
 __device__ __forceinline__ double cand_node_cost(const CandDev& c, u32 nd, u32 lo, u32 hi, i32& blocked_by, i32& dne) {
@@ -4339,8 +4375,37 @@ __global__ __launch_bounds__(256) void ks_deprov_nodes(const CandDev c) {
 
 // Both candidate calls: every refusal, one block up, the kernels, one block back.  `x` = NULL: consolidation (ks_cand_nodes / ks_cand_order); else `in` == &x->c and the
 // method's own kernels run, and *n_in_result receives the count of nodes candidateNodes returned.
-static int candidates_run(const std::string& what, const ks_candidates_inputs* in, const ks_deprov_inputs* x, ks_candidates_outputs* out, u32* n_in_result, int device, double* ms) {
-  const u32 NP = in->n_pods, NN = in->n_nodes, NB = in->n_pdbs, NK = in->n_keys;
+// Every refusal of the lists form of the selectors (ksolve.h ks_selector_lists): what ks_cand_pods_lists indexes with.  NR = the requirement count.
+static int candidates_lists_check(const std::string& what, const ks_candidates_inputs* in, const ks_selector_lists* L, u32 NR) {
+  const u32 NP = in->n_pods, NK = L->n_keys;
+  if ((NK && !L->key_n_values) || !L->pod_label_off || !L->req_val_off || (NR && (!L->req_key || !L->req_op))) return fail(KS_ERR_INVALID, "null argument");
+  if (L->n_namespaces > NP) return fail(KS_ERR_INVALID, what + std::to_string(L->n_namespaces) + " namespaces for " + std::to_string(NP) + " pod slots: a namespace id is some pod's");
+  for (u32 p = 0; p < NP; ++p) if (in->pod_node[p] >= 0 && in->pod_ns[p] >= L->n_namespaces) return fail(KS_ERR_INVALID, what + "pod " + std::to_string(p) + ": namespace id out of range");
+  if (L->pod_label_off[0] != 0 || L->req_val_off[0] != 0) return fail(KS_ERR_INVALID, what + "offsets must start at 0");
+  for (u32 p = 0; p < NP; ++p) if (L->pod_label_off[p + 1] < L->pod_label_off[p]) return fail(KS_ERR_INVALID, what + "pod label offsets not ascending");
+  for (u32 r = 0; r < NR; ++r) if (L->req_val_off[r + 1] < L->req_val_off[r]) return fail(KS_ERR_INVALID, what + "requirement value offsets not ascending");
+  if ((L->pod_label_off[NP] && (!L->pod_label_key || !L->pod_label_val)) || (L->req_val_off[NR] && !L->req_val)) return fail(KS_ERR_INVALID, "null argument");
+  for (u32 p = 0; p < NP; ++p) for (u32 l = L->pod_label_off[p]; l < L->pod_label_off[p + 1]; ++l) {
+    const u32 k = L->pod_label_key[l], v = L->pod_label_val[l];
+    if (k >= NK) return fail(KS_ERR_INVALID, what + "pod " + std::to_string(p) + ": label key out of range");
+    if (l > L->pod_label_off[p] && k <= L->pod_label_key[l - 1]) return fail(KS_ERR_INVALID, what + "pod " + std::to_string(p) + ": label keys must ascend, each once");
+    if (v != KS_CAND_VALUE_OTHER && v >= L->key_n_values[k]) return fail(KS_ERR_INVALID, what + "pod " + std::to_string(p) + ": label value out of range");
+  }
+  for (u32 r = 0; r < NR; ++r) {
+    const u32 k = L->req_key[r], op = L->req_op[r], lo = L->req_val_off[r], hi = L->req_val_off[r + 1];
+    if (k >= NK) return fail(KS_ERR_INVALID, what + "requirement key out of range");
+    if (op > KS_CAND_OP_DOES_NOT_EXIST) return fail(KS_ERR_INVALID, what + "requirement " + std::to_string(r) + ": unknown operator " + std::to_string(op));
+    if ((lo == hi) != (op >= KS_CAND_OP_EXISTS)) return fail(KS_ERR_INVALID, what + "requirement " + std::to_string(r) + ": In / NotIn need values, Exists / DoesNotExist take none");
+    for (u32 i = lo; i < hi; ++i) {
+      if (L->req_val[i] >= L->key_n_values[k]) return fail(KS_ERR_INVALID, what + "requirement " + std::to_string(r) + ": value out of range");
+      if (i > lo && L->req_val[i] <= L->req_val[i - 1]) return fail(KS_ERR_INVALID, what + "requirement " + std::to_string(r) + ": values must ascend, each once");
+    }
+  }
+  return KS_OK;
+}
+// `L` = NULL: the narrow form of the selectors (in->pod_val, in->pdb_req_key / _mask; ks_cand_pods).  Else the lists form (ks_cand_pods_lists); the rest is one path.
+static int candidates_run(const std::string& what, const ks_candidates_inputs* in, const ks_deprov_inputs* x, const ks_selector_lists* L, ks_candidates_outputs* out, u32* n_in_result, int device, double* ms) {
+  const u32 NP = in->n_pods, NN = in->n_nodes, NB = in->n_pdbs, NK = L ? 0u : in->n_keys;
   if (NK > KS_CAND_MAX_KEYS) return fail(KS_ERR_UNSUPPORTED, what + std::to_string(NK) + " selector keys, " + std::to_string(KS_CAND_MAX_KEYS) + " supported");
   if ((NP && (!in->pod_node || !in->pod_ns || !in->pod_flags || !in->pod_deletion_cost || !in->pod_priority || (NK && !in->pod_val))) || !in->pdb_req_off ||
       (NB && (!in->pdb_ns || !in->pdb_allowed)) || !in->node_pods_off || (NN && (!in->node_why || !in->node_age_seconds || !in->node_ttl_seconds)) ||
@@ -4349,9 +4414,12 @@ static int candidates_run(const std::string& what, const ks_candidates_inputs* i
   if (in->pdb_req_off[0] != 0 || in->node_pods_off[0] != 0) return fail(KS_ERR_INVALID, what + "offsets must start at 0");
   for (u32 b = 0; b < NB; ++b) if (in->pdb_req_off[b + 1] < in->pdb_req_off[b]) return fail(KS_ERR_INVALID, what + "PDB requirement offsets not ascending");
   const u32 NR = in->pdb_req_off[NB];
-  if (NR && (!in->pdb_req_key || !in->pdb_req_mask)) return fail(KS_ERR_INVALID, "null argument");
-  for (u32 r = 0; r < NR; ++r) if (in->pdb_req_key[r] >= NK) return fail(KS_ERR_INVALID, what + "requirement key out of range");
-  for (size_t i = 0; i < (size_t)NK * NP; ++i) if (in->pod_val[i] > 63) return fail(KS_ERR_INVALID, what + "pod value bit above 63");
+  if (L) TRY(candidates_lists_check(what, in, L, NR));
+  else {
+    if (NR && (!in->pdb_req_key || !in->pdb_req_mask)) return fail(KS_ERR_INVALID, "null argument");
+    for (u32 r = 0; r < NR; ++r) if (in->pdb_req_key[r] >= NK) return fail(KS_ERR_INVALID, what + "requirement key out of range");
+    for (size_t i = 0; i < (size_t)NK * NP; ++i) if (in->pod_val[i] > 63) return fail(KS_ERR_INVALID, what + "pod value bit above 63");
+  }
   for (u32 p = 0; p < NP; ++p) {
     if (in->pod_flags[p] & ~7u) return fail(KS_ERR_INVALID, what + "unknown pod flag bit");
     if ((in->pod_flags[p] & KS_CAND_POD_HAS_DELETION_COST) && !std::isfinite(in->pod_deletion_cost[p])) return fail(KS_ERR_INVALID, what + "pod " + std::to_string(p) + ": deletion cost is not finite");
@@ -4389,12 +4457,35 @@ static int candidates_run(const std::string& what, const ks_candidates_inputs* i
   if (!NN) return KS_OK;
   if (ks_device_count() <= 0) return fail(KS_ERR_DEVICE, "no gfx950 (MI355X) device visible; libksolve has no CPU path");
   HIPCHK(hipSetDevice(device));
+  // the lists form as the kernel reads it: the listed pods sorted by namespace (stably: ascending slot within one), the blocking PDBs grouped by namespace in ascending
+  // index -- a PDB in a namespace no pod has, or with disruptions allowed, can block nothing and is left out --, labels and requirements packed one load each
+  auto t0 = std::chrono::steady_clock::now();      // (the lists form: its regrouping and packing count as part of bringing the inputs up)
+  std::vector<u32> l_perm, l_ns_off; std::vector<CandLabL> l_lab; std::vector<CandPdbL> l_pdb; std::vector<CandReqL> l_req;
+  const u32 NS = L ? L->n_namespaces : 0u, NLab = L ? L->pod_label_off[NP] : 0u, NV = L ? L->req_val_off[NR] : 0u;
+  if (L) {
+    const u32 NLP = in->node_pods_off[NN];
+    std::vector<u32> at((size_t)NS + 1, 0);
+    for (u32 i = 0; i < NLP; ++i) at[in->pod_ns[in->node_pods[i]] + 1]++;
+    for (u32 s = 0; s < NS; ++s) at[s + 1] += at[s];
+    l_perm.resize(NLP);
+    { std::vector<u8> listed(NP, 0); for (u32 i = 0; i < NLP; ++i) listed[in->node_pods[i]] = 1; for (u32 p = 0; p < NP; ++p) if (listed[p]) l_perm[at[in->pod_ns[p]]++] = p; }
+    l_ns_off.assign((size_t)NS + 1, 0);
+    for (u32 b = 0; b < NB; ++b) if (in->pdb_allowed[b] == 0 && in->pdb_ns[b] < NS) l_ns_off[in->pdb_ns[b] + 1]++;
+    for (u32 s = 0; s < NS; ++s) l_ns_off[s + 1] += l_ns_off[s];
+    l_pdb.resize(l_ns_off[NS]);
+    { std::vector<u32> fill(l_ns_off.begin(), l_ns_off.end() - 1);
+      for (u32 b = 0; b < NB; ++b) if (in->pdb_allowed[b] == 0 && in->pdb_ns[b] < NS) l_pdb[fill[in->pdb_ns[b]]++] = CandPdbL{b, in->pdb_req_off[b], in->pdb_req_off[b + 1], 0}; }
+    l_lab.resize(NLab); for (u32 l = 0; l < NLab; ++l) l_lab[l] = CandLabL{L->pod_label_key[l], L->pod_label_val[l]};
+    l_req.resize(NR); for (u32 r = 0; r < NR; ++r) l_req[r] = CandReqL{L->req_key[r], L->req_op[r], L->req_val_off[r], L->req_val_off[r + 1]};
+  }
   // one host block, one device block: [inputs | outputs | scratch], every segment 16-byte aligned
   size_t bytes = 0; auto seg = [&](size_t n) { const size_t at = bytes; bytes = (bytes + (n ? n : 1) + 15) & ~(size_t)15; return at; };
   const size_t o_ns = seg((size_t)NP * 4), o_fl = seg((size_t)NP * 4), o_dc = seg((size_t)NP * 8), o_pr = seg((size_t)NP * 4), o_val = seg((size_t)NK * NP);
-  const size_t o_bns = seg((size_t)NB * 4), o_ball = seg((size_t)NB * 4), o_boff = seg(((size_t)NB + 1) * 4), o_bkey = seg((size_t)NR * 4), o_bmask = seg((size_t)NR * 8);
+  const size_t o_bns = seg((size_t)NB * 4), o_ball = seg((size_t)NB * 4), o_boff = seg(((size_t)NB + 1) * 4), o_bkey = seg(L ? 0 : (size_t)NR * 4), o_bmask = seg(L ? 0 : (size_t)NR * 8);
   const size_t o_why = seg((size_t)NN * 4), o_age = seg((size_t)NN * 8), o_ttl = seg((size_t)NN * 8), o_noff = seg(((size_t)NN + 1) * 4), o_npods = seg((size_t)NL * 4);
-  const size_t o_df = seg(x ? (size_t)NN * 4 : 0), o_cre = seg(x ? (size_t)NN * 8 : 0), o_emp = seg(x ? (size_t)NN * 8 : 0), o_ttle = seg(x ? (size_t)NN * 8 : 0), o_cnt = seg(16);
+  const size_t o_df = seg(x ? (size_t)NN * 4 : 0), o_cre = seg(x ? (size_t)NN * 8 : 0), o_emp = seg(x ? (size_t)NN * 8 : 0), o_ttle = seg(x ? (size_t)NN * 8 : 0);
+  const size_t o_lperm = seg(l_perm.size() * 4), o_lloff = seg(L ? ((size_t)NP + 1) * 4 : 0), o_llab = seg(l_lab.size() * sizeof(CandLabL)), o_lns = seg(l_ns_off.size() * 4),
+               o_lpdb = seg(l_pdb.size() * sizeof(CandPdbL)), o_lreq = seg(l_req.size() * sizeof(CandReqL)), o_lval = seg((size_t)NV * 4), o_cnt = seg(16);
   const size_t up = bytes;
   const size_t r_why = seg((size_t)NN * 4), r_det = seg((size_t)NN * 4), r_np = seg((size_t)NN * 4), r_cost = seg((size_t)NN * 8), r_ord = seg((size_t)NN * 4), r_emp = seg((size_t)NN * 4);
   const size_t down = bytes;
@@ -4402,13 +4493,15 @@ static int candidates_run(const std::string& what, const ks_candidates_inputs* i
   std::vector<u64> host(down / 8 + 1, 0); u8* hb = (u8*)host.data();
   auto put = [&](size_t at, const void* src, size_t n) { if (n) memcpy(hb + at, src, n); };
   put(o_ns, in->pod_ns, (size_t)NP * 4); put(o_fl, in->pod_flags, (size_t)NP * 4); put(o_dc, in->pod_deletion_cost, (size_t)NP * 8); put(o_pr, in->pod_priority, (size_t)NP * 4); put(o_val, in->pod_val, (size_t)NK * NP);
-  put(o_bns, in->pdb_ns, (size_t)NB * 4); put(o_ball, in->pdb_allowed, (size_t)NB * 4); put(o_boff, in->pdb_req_off, ((size_t)NB + 1) * 4); put(o_bkey, in->pdb_req_key, (size_t)NR * 4); put(o_bmask, in->pdb_req_mask, (size_t)NR * 8);
+  put(o_bns, in->pdb_ns, (size_t)NB * 4); put(o_ball, in->pdb_allowed, (size_t)NB * 4); put(o_boff, in->pdb_req_off, ((size_t)NB + 1) * 4); if (!L) { put(o_bkey, in->pdb_req_key, (size_t)NR * 4); put(o_bmask, in->pdb_req_mask, (size_t)NR * 8); }
+  if (L) { put(o_lperm, l_perm.data(), l_perm.size() * 4); put(o_lloff, L->pod_label_off, ((size_t)NP + 1) * 4); put(o_llab, l_lab.data(), l_lab.size() * sizeof(CandLabL)); put(o_lns, l_ns_off.data(), l_ns_off.size() * 4);
+           put(o_lpdb, l_pdb.data(), l_pdb.size() * sizeof(CandPdbL)); put(o_lreq, l_req.data(), l_req.size() * sizeof(CandReqL)); put(o_lval, L->req_val, (size_t)NV * 4); }
   put(o_why, in->node_why, (size_t)NN * 4); put(o_age, in->node_age_seconds, (size_t)NN * 8); put(o_ttl, in->node_ttl_seconds, (size_t)NN * 8); put(o_noff, in->node_pods_off, ((size_t)NN + 1) * 4); put(o_npods, in->node_pods, (size_t)NL * 4);
   if (x) { put(o_df, x->node_dflags, (size_t)NN * 4); put(o_cre, x->node_creation_unix_nanos, (size_t)NN * 8); put(o_emp, x->node_emptiness_unix_nanos, (size_t)NN * 8); put(o_ttle, x->node_ttl_seconds_after_empty, (size_t)NN * 8); }
   TmpDev buf(device); TRY(buf.alloc(bytes)); u8* db = buf.as<u8>();
   hipStream_t stream = nullptr; TRY(pool().get_stream(device, &stream));
   struct StreamBack { int device; hipStream_t s; ~StreamBack() { pool().put_stream(device, s); } } back{device, stream};
-  const auto t0 = std::chrono::steady_clock::now();
+  if (!L) t0 = std::chrono::steady_clock::now();
   HIPCHK(hipMemcpy(db, hb, up, hipMemcpyHostToDevice));
   const auto t1 = std::chrono::steady_clock::now();
   CandDev c{};
@@ -4423,8 +4516,13 @@ static int candidates_run(const std::string& what, const ks_candidates_inputs* i
     c.method = x->method; c.drift_enabled = x->drift_enabled; c.now = x->now_unix_nanos;
     c.node_dflags = (const u32*)(db + o_df); c.node_creation = (const i64*)(db + o_cre); c.node_emptiness = (const i64*)(db + o_emp); c.node_ttl_empty = (const i64*)(db + o_ttle); c.node_key = (i64*)(db + s_key);
   }
+  if (L) {
+    c.l_n_perm = (u32)l_perm.size(); c.l_perm = (const u32*)(db + o_lperm); c.l_lab_off = (const u32*)(db + o_lloff); c.l_lab = (const CandLabL*)(db + o_llab); c.l_ns_off = (const u32*)(db + o_lns);
+    c.l_pdb = (const CandPdbL*)(db + o_lpdb); c.l_req = (const CandReqL*)(db + o_lreq); c.l_val = (const u32*)(db + o_lval);
+  }
   const u32 gn = (NN + KS_CAND_BLOCK - 1) / KS_CAND_BLOCK;
-  if (NP) hipLaunchKernelGGL(ks_cand_pods, dim3((NP + KS_CAND_BLOCK - 1) / KS_CAND_BLOCK), dim3(KS_CAND_BLOCK), 0, stream, c);
+  if (L) { if (c.l_n_perm) hipLaunchKernelGGL(ks_cand_pods_lists, dim3((c.l_n_perm + KS_CAND_BLOCK - 1) / KS_CAND_BLOCK), dim3(KS_CAND_BLOCK), 0, stream, c); }
+  else if (NP) hipLaunchKernelGGL(ks_cand_pods, dim3((NP + KS_CAND_BLOCK - 1) / KS_CAND_BLOCK), dim3(KS_CAND_BLOCK), 0, stream, c);
   if (x) { hipLaunchKernelGGL(ks_deprov_nodes, dim3(gn), dim3(KS_CAND_BLOCK), 0, stream, c); hipLaunchKernelGGL(ks_cand_order_key, dim3(gn), dim3(KS_CAND_BLOCK), 0, stream, c); }
   else { hipLaunchKernelGGL(ks_cand_nodes, dim3(gn), dim3(KS_CAND_BLOCK), 0, stream, c); hipLaunchKernelGGL(ks_cand_order, dim3(gn), dim3(KS_CAND_BLOCK), 0, stream, c); }
   HIPCHK(hipStreamSynchronize(stream)); HIPCHK(hipGetLastError());
@@ -4441,12 +4539,22 @@ static int candidates_run(const std::string& what, const ks_candidates_inputs* i
 extern "C" int ks_consolidation_candidates_host(const ks_candidates_inputs* in, ks_candidates_outputs* out, int device, double* ms) {
   if (ms) ms[0] = ms[1] = ms[2] = 0.0;
   if (!in || !out) return fail(KS_ERR_INVALID, "null argument");
-  return candidates_run("consolidation candidates: ", in, nullptr, out, nullptr, device, ms);
+  return candidates_run("consolidation candidates: ", in, nullptr, nullptr, out, nullptr, device, ms);
 }
 extern "C" int ks_deprovisioning_candidates_host(const ks_deprov_inputs* in, ks_deprov_outputs* out, int device, double* ms) {
   if (ms) ms[0] = ms[1] = ms[2] = 0.0;
   if (!in || !out) return fail(KS_ERR_INVALID, "null argument");
-  return candidates_run("deprovisioning candidates: ", &in->c, in, &out->c, &out->n_in_result, device, ms);
+  return candidates_run("deprovisioning candidates: ", &in->c, in, nullptr, &out->c, &out->n_in_result, device, ms);
+}
+extern "C" int ks_consolidation_candidates_lists_host(const ks_candidates_inputs* in, const ks_selector_lists* sel, ks_candidates_outputs* out, int device, double* ms) {
+  if (ms) ms[0] = ms[1] = ms[2] = 0.0;
+  if (!in || !sel || !out) return fail(KS_ERR_INVALID, "null argument");
+  return candidates_run("consolidation candidates: ", in, nullptr, sel, out, nullptr, device, ms);
+}
+extern "C" int ks_deprovisioning_candidates_lists_host(const ks_deprov_inputs* in, const ks_selector_lists* sel, ks_deprov_outputs* out, int device, double* ms) {
+  if (ms) ms[0] = ms[1] = ms[2] = 0.0;
+  if (!in || !sel || !out) return fail(KS_ERR_INVALID, "null argument");
+  return candidates_run("deprovisioning candidates: ", &in->c, in, sel, &out->c, &out->n_in_result, device, ms);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -1173,12 +1173,15 @@ struct CandSnapshot {
 };
 // `dx` = NULL: consolidation (`in`, codes 8 / 9).  Else `in` == &dx->base and `method`'s ShouldDeprovision takes the place of 8 / 9: the host gives reasons 1-7 and 13 and
 // the flags, the device decides the rest (ks_deprovisioning_candidates_host); *n_in_result = len(candidateNodes(...)).
+// `flags`: KSH_CAND_WIDE_SELECTORS tabulates the selectors as lists (ksolve.h ks_selector_lists) instead of bytes and masks; everything that is not a selector is one path.
 int candidates_over(Parsed* P, uint32_t method, const int32_t* pod_node, const uint32_t* deleting, uint32_t n_deleting, const ksh_candidate_inputs* in, const ksh_deprovisioning_inputs* dx,
-                    const ksh_pdb_block* pb, int device, ksh_candidates_out* out, uint32_t* n_in_result, double* ms) {
+                    const ksh_pdb_block* pb, int device, uint32_t flags, ksh_candidates_out* out, uint32_t* n_in_result, double* ms) {
   const auto t_call = clk::now();
   zero(ms, 4);
   if (!P || !in || !out || (n_deleting && !deleting)) return set_err(KS_ERR_INVALID, "null argument");
   const std::string what = dx ? "deprovisioning candidates" : "consolidation candidates";
+  if (flags & ~(uint32_t)KSH_CAND_WIDE_SELECTORS) return set_err(KS_ERR_INVALID, what + ": unknown flag bit (KSH_CAND_WIDE_SELECTORS is the only one)");
+  const bool wide = (flags & KSH_CAND_WIDE_SELECTORS) != 0;
   if (dx && (method < KSH_METHOD_EXPIRATION || method > KSH_METHOD_EMPTINESS)) return set_err(KS_ERR_INVALID, what + ": unknown method " + std::to_string(method));
   // the PDBs first, completely: a malformed block changes and launches nothing
   std::vector<ksp::Pdb> pdbs;
@@ -1230,17 +1233,35 @@ int candidates_over(Parsed* P, uint32_t method, const int32_t* pod_node, const u
     for (auto& kv : b.selector.match_labels) bit_of(key_of(kv.first), kv.second);
     for (auto& x : b.selector.match_exprs) { const uint32_t k = key_of(x.key); for (auto& v : x.values) bit_of(k, v); }
   }
-  if (keys.size() > KS_CAND_MAX_KEYS) return set_err(KS_ERR_UNSUPPORTED, what + ": the PDB selectors mention " + std::to_string(keys.size()) + " label keys, " + std::to_string(KS_CAND_MAX_KEYS) + " are supported");
-  for (size_t k = 0; k < keys.size(); ++k) if (vindex[k].size() > KS_CAND_MAX_VALUES)
+  if (!wide && keys.size() > KS_CAND_MAX_KEYS) return set_err(KS_ERR_UNSUPPORTED, what + ": the PDB selectors mention " + std::to_string(keys.size()) + " label keys, " + std::to_string(KS_CAND_MAX_KEYS) + " are supported");
+  for (size_t k = 0; !wide && k < keys.size(); ++k) if (vindex[k].size() > KS_CAND_MAX_VALUES)
     return set_err(KS_ERR_UNSUPPORTED, what + ": the PDB selectors mention " + std::to_string(vindex[k].size()) + " values of label key " + keys[k] + ", " + std::to_string(KS_CAND_MAX_VALUES) + " are supported");
   const uint32_t NK = (uint32_t)keys.size(), NB = (uint32_t)pdbs.size();
   // namespaces: the bound pods' get ids; a PDB in a namespace no pod has, and a nil selector (LabelSelectorAsSelector(nil) selects nothing), get an id no pod has
   const uint32_t kNoNs = 0xFFFFFFFFu; std::unordered_map<std::string, uint32_t> nsindex;
-  std::vector<uint32_t> pod_ns(NP, 0); std::vector<uint8_t> pod_val((size_t)NK * NP, (uint8_t)KS_CAND_BIT_ABSENT);
+  std::vector<uint32_t> pod_ns(NP, 0); std::vector<uint8_t> pod_val(wide ? 0 : (size_t)NK * NP, (uint8_t)KS_CAND_BIT_ABSENT);
+  std::vector<uint32_t> lab_off(wide ? (size_t)NP + 1 : 0, 0), lab_key, lab_val;      // the wide route's pod side: per pod the mentioned keys it carries, ascending
+  std::vector<std::pair<uint32_t, uint32_t>> mine;
+  if (wide) { lab_key.reserve(NP); lab_val.reserve(NP); }
   for (uint32_t p = 0; p < NP; ++p) {
+    if (wide) lab_off[p + 1] = lab_off[p];
     if (bind[p] < 0) continue;
     const ksp::Pod& pod = pr.pods[p];
     pod_ns[p] = nsindex.emplace(pod.ns, (uint32_t)nsindex.size()).first->second;
+    if (wide) {      // the pod's labels once, key then value: the work goes with the labels, not with keys x pods
+      mine.clear();
+      for (auto& kv : pod.labels) {
+        auto k = kindex.find(kv.first); if (k == kindex.end()) continue;
+        auto v = vindex[k->second].find(kv.second);
+        mine.emplace_back(k->second, v == vindex[k->second].end() ? (uint32_t)KS_CAND_VALUE_OTHER : v->second);
+      }
+      if (mine.size() > 1) std::sort(mine.begin(), mine.end());
+      if (lab_key.size() + mine.size() > 0xFFFFFFFFull)
+        return set_err(KS_ERR_UNSUPPORTED, what + ": " + std::to_string(lab_key.size() + mine.size()) + " selector-mentioned pod labels, " + std::to_string(0xFFFFFFFFull) + " are supported");
+      for (auto& kv : mine) { lab_key.push_back(kv.first); lab_val.push_back(kv.second); }
+      lab_off[p + 1] = (uint32_t)lab_key.size();
+      continue;
+    }
     for (uint32_t k = 0; k < NK; ++k) {
       auto it = pod.labels.find(keys[k]); if (it == pod.labels.end()) continue;
       auto v = vindex[k].find(it->second);
@@ -1248,11 +1269,23 @@ int candidates_over(Parsed* P, uint32_t method, const int32_t* pod_node, const u
     }
   }
   std::vector<uint32_t> pdb_ns(NB), req_off(NB + 1, 0), req_key; std::vector<int32_t> pdb_allowed(NB); std::vector<uint64_t> req_mask;
+  std::vector<uint32_t> req_op, req_val; std::vector<size_t> req_val_off(1, 0);      // (the wide route's PDB side)
   const uint64_t kAbsent = 1ull << KS_CAND_BIT_ABSENT;
   for (uint32_t b = 0; b < NB; ++b) {
     const ksp::Pdb& d = pdbs[b]; auto ns = nsindex.find(d.ns);
     pdb_ns[b] = (d.selector.nil || ns == nsindex.end()) ? kNoNs : ns->second; pdb_allowed[b] = d.disruptions_allowed;
-    if (!d.selector.nil) {
+    if (!d.selector.nil && wide) {      // per requirement an operator and the value ids, sorted and each once, in one pool
+      auto list = [&](uint32_t k, uint32_t op, const std::vector<uint32_t>& ids) {
+        req_key.push_back(k); req_op.push_back(op); req_val.insert(req_val.end(), ids.begin(), ids.end()); req_val_off.push_back(req_val.size());
+      };
+      std::vector<uint32_t> ids;
+      for (auto& kv : d.selector.match_labels) { const uint32_t k = kindex[kv.first]; ids.assign(1, vindex[k][kv.second]); list(k, KS_CAND_OP_IN, ids); }
+      for (auto& x : d.selector.match_exprs) {
+        const uint32_t k = kindex[x.key]; ids.clear();
+        if (x.op == ksp::Op::In || x.op == ksp::Op::NotIn) { for (auto& v : x.values) ids.push_back(vindex[k][v]); std::sort(ids.begin(), ids.end()); ids.erase(std::unique(ids.begin(), ids.end()), ids.end()); }
+        list(k, x.op == ksp::Op::In ? KS_CAND_OP_IN : x.op == ksp::Op::NotIn ? KS_CAND_OP_NOT_IN : x.op == ksp::Op::Exists ? KS_CAND_OP_EXISTS : KS_CAND_OP_DOES_NOT_EXIST, ids);
+      }
+    } else if (!d.selector.nil) {
       for (auto& kv : d.selector.match_labels) { const uint32_t k = kindex[kv.first]; req_key.push_back(k); req_mask.push_back(1ull << vindex[k][kv.second]); }
       for (auto& x : d.selector.match_exprs) {
         const uint32_t k = kindex[x.key]; uint64_t bits = 0; for (auto& v : x.values) bits |= 1ull << vindex[k][v];
@@ -1293,6 +1326,15 @@ int candidates_over(Parsed* P, uint32_t method, const int32_t* pod_node, const u
   ki.pod_node = bind.data(); ki.pod_ns = pod_ns.data(); ki.pod_flags = in->pod_flags; ki.pod_deletion_cost = in->pod_deletion_cost; ki.pod_priority = in->pod_priority; ki.pod_val = pod_val.data();
   ki.pdb_ns = pdb_ns.data(); ki.pdb_allowed = pdb_allowed.data(); ki.pdb_req_off = req_off.data(); ki.pdb_req_key = req_key.data(); ki.pdb_req_mask = req_mask.data();
   ki.node_why = node_why.data(); ki.node_age_seconds = in->node_age_seconds; ki.node_ttl_seconds = node_ttl.data(); ki.node_pods_off = pods_off.data(); ki.node_pods = node_pods.data();
+  ks_selector_lists sl{}; std::vector<uint32_t> key_nv, val_off32;
+  if (wide) {
+    if (req_val.size() > 0xFFFFFFFFull) return set_err(KS_ERR_UNSUPPORTED, what + ": " + std::to_string(req_val.size()) + " selector values in all, " + std::to_string(0xFFFFFFFFull) + " are supported");
+    key_nv.resize(NK); for (uint32_t k = 0; k < NK; ++k) key_nv[k] = (uint32_t)vindex[k].size();
+    val_off32.assign(req_val_off.begin(), req_val_off.end());
+    ki.n_keys = 0; ki.pod_val = nullptr; ki.pdb_req_key = nullptr; ki.pdb_req_mask = nullptr;
+    sl.n_keys = NK; sl.n_namespaces = (uint32_t)nsindex.size(); sl.key_n_values = key_nv.data(); sl.pod_label_off = lab_off.data(); sl.pod_label_key = lab_key.data(); sl.pod_label_val = lab_val.data();
+    sl.req_key = req_key.data(); sl.req_op = req_op.data(); sl.req_val_off = val_off32.data(); sl.req_val = req_val.data();
+  }
   ks_candidates_outputs ko{}; ko.order = out->order; ko.empty = out->empty; ko.why = out->why; ko.detail = out->detail; ko.n_node_pods = out->n_node_pods; ko.cost = out->cost;
   const double host_ms = ms_since(t_call);
   double kms[3] = {0, 0, 0};
@@ -1301,9 +1343,9 @@ int candidates_over(Parsed* P, uint32_t method, const int32_t* pod_node, const u
     ks_deprov_inputs di{}; di.c = ki; di.method = method; di.drift_enabled = dx->drift_enabled; di.now_unix_nanos = dx->now_unix_nanos; di.node_dflags = node_dflags.data();
     di.node_creation_unix_nanos = dx->node_creation_unix_nanos; di.node_emptiness_unix_nanos = dx->node_emptiness_unix_nanos; di.node_ttl_seconds_after_empty = node_ttl_e.data();
     ks_deprov_outputs dout{}; dout.c = ko;
-    rc = ks_deprovisioning_candidates_host(&di, &dout, device, kms);
+    rc = wide ? ks_deprovisioning_candidates_lists_host(&di, &sl, &dout, device, kms) : ks_deprovisioning_candidates_host(&di, &dout, device, kms);
     ko = dout.c; if (n_in_result) *n_in_result = dout.n_in_result;
-  } else rc = ks_consolidation_candidates_host(&ki, &ko, device, kms);
+  } else rc = wide ? ks_consolidation_candidates_lists_host(&ki, &sl, &ko, device, kms) : ks_consolidation_candidates_host(&ki, &ko, device, kms);
   if (rc != KS_OK) return dev_rc(rc);
   out->n_candidates = ko.n_candidates; out->n_empty = ko.n_empty;
   if (ms) { ms[0] = host_ms; ms[1] = kms[0]; ms[2] = kms[1]; ms[3] = kms[2]; }
@@ -1313,15 +1355,23 @@ int candidates_over(Parsed* P, uint32_t method, const int32_t* pod_node, const u
 extern "C" {
 int ksh_consolidation_candidates(void* parsed, const int32_t* pod_node, const uint32_t* deleting, uint32_t n_deleting, const ksh_candidate_inputs* in, const ksh_pdb_block* pdbs, int device,
                                  ksh_candidates_out* out, double* ms) {
-  return guarded([&] { return candidates_over((Parsed*)parsed, 0, pod_node, deleting, n_deleting, in, nullptr, pdbs, device, out, nullptr, ms); });
+  return ksh_consolidation_candidates_ex(parsed, pod_node, deleting, n_deleting, in, pdbs, device, 0, out, ms);
+}
+int ksh_consolidation_candidates_ex(void* parsed, const int32_t* pod_node, const uint32_t* deleting, uint32_t n_deleting, const ksh_candidate_inputs* in, const ksh_pdb_block* pdbs, int device,
+                                    uint32_t flags, ksh_candidates_out* out, double* ms) {
+  return guarded([&] { return candidates_over((Parsed*)parsed, 0, pod_node, deleting, n_deleting, in, nullptr, pdbs, device, flags, out, nullptr, ms); });
 }
 // candidateNodes under Expiration / Drift / Emptiness.ShouldDeprovision and the order their ComputeCommand walks (kshost.h)
 int ksh_deprovisioning_candidates(void* parsed, uint32_t method, const int32_t* pod_node, const uint32_t* deleting, uint32_t n_deleting, const ksh_deprovisioning_inputs* in,
                                   const ksh_pdb_block* pdbs, int device, ksh_deprovisioning_out* out, double* ms) {
+  return ksh_deprovisioning_candidates_ex(parsed, method, pod_node, deleting, n_deleting, in, pdbs, device, 0, out, ms);
+}
+int ksh_deprovisioning_candidates_ex(void* parsed, uint32_t method, const int32_t* pod_node, const uint32_t* deleting, uint32_t n_deleting, const ksh_deprovisioning_inputs* in,
+                                     const ksh_pdb_block* pdbs, int device, uint32_t flags, ksh_deprovisioning_out* out, double* ms) {
   if (!in || !out) return set_err(KS_ERR_INVALID, "null argument");
   return guarded([&] {
     uint32_t n_in_result = 0;
-    const int rc = candidates_over((Parsed*)parsed, method, pod_node, deleting, n_deleting, &in->base, in, pdbs, device, &out->base, &n_in_result, ms);
+    const int rc = candidates_over((Parsed*)parsed, method, pod_node, deleting, n_deleting, &in->base, in, pdbs, device, flags, &out->base, &n_in_result, ms);
     if (rc == KS_OK) out->n_in_result = n_in_result;
     return rc;
   });

@@ -996,6 +996,7 @@ def validate_empty_nodes(nodes: Sequence[int], why: Sequence[int], n_node_pods: 
 KSH_CAND_NODE_NOMINATED, KSH_CAND_NODE_DO_NOT_CONSOLIDATE, KSH_CAND_NODE_DO_NOT_CONSOLIDATE_TRUE, KSH_CAND_NODE_DELETION_TIMESTAMP = 1, 2, 4, 8      # kshost.h
 KSH_CAND_POD_DO_NOT_EVICT, KSH_CAND_POD_HAS_DELETION_COST, KSH_CAND_POD_HAS_PRIORITY = 1, 2, 4
 KS_CAND_MAX_KEYS, KS_CAND_MAX_VALUES = 16, 62
+KSH_CAND_WIDE_SELECTORS = 1      # kshost.h: the `flags` bit of ksh_*_candidates_ex
 CANDIDATE_TIMING_KEYS = ("host_ms", "upload_ms", "kernels_ms", "readback_ms")
 
 
@@ -1017,13 +1018,15 @@ class _CandidatesOut(ctypes.Structure):      # include/kshost.h ksh_candidates_o
 
 def consolidation_candidates(snapshot: "ParsedProblem", pod_node: Optional[Sequence[int]], node_flags: Sequence[int], node_age_seconds: Sequence[float],
                              pod_flags: Sequence[int], pod_deletion_cost: Sequence[float], pod_priority: Sequence[int], prov_consolidation_enabled: Sequence[bool],
-                             prov_ttl_seconds: Sequence[Optional[int]], pdbs=(), deleting: Sequence[int] = (), device: int = 0, out: Optional[dict] = None) -> dict:
-    """candidateNodes + consolidation.ShouldDeprovision + sortAndFilterCandidates in ONE call (kshost.h `ksh_consolidation_candidates`): the per-pod eviction costs and
+                             prov_ttl_seconds: Sequence[Optional[int]], pdbs=(), deleting: Sequence[int] = (), device: int = 0, out: Optional[dict] = None,
+                             wide_selectors: bool = False) -> dict:
+    """candidateNodes + consolidation.ShouldDeprovision + sortAndFilterCandidates in ONE call (kshost.h `ksh_consolidation_candidates_ex`): the per-pod eviction costs and
     PDB matches, the per-node sums and reasons and the order are computed on the device.  The arrays run over the snapshot's node / pod slots and its provisioners;
     `pdbs`: `model.PodDisruptionBudget`s, or the block `model.pdbs_to_block` made of them; `prov_ttl_seconds`: None (or -1) for nil.  Returns {"order", "empty": lists of
     node slots; "why", "detail", "n_node_pods": int arrays per node slot; "cost": float64 per node slot; "ms": the library's split of the call}.  `order` is what
     `first_n_node_option` / `single_node_option` take as candidates.  `out`: preallocated arrays to fill instead
-    ({"order", "empty", "why", "n_node_pods": uint32, "detail": int32, "cost": float64}, one entry per node slot)."""
+    ({"order", "empty", "why", "n_node_pods": uint32, "detail": int32, "cost": float64}, one entry per node slot).  `wide_selectors`: KSH_CAND_WIDE_SELECTORS -- the
+    selectors go to the device as lists, so label keys, values per key and set sizes are unbounded (without it more than 16 keys or 62 values of a key are refused)."""
     import numpy as np
     from .model import pdbs_to_block
     kh = libs()[1]
@@ -1048,9 +1051,10 @@ def consolidation_candidates(snapshot: "ParsedProblem", pod_node: Optional[Seque
     pn, pn_ptr = _pod_node_arg(pod_node)
     dl = _u32s(deleting)
     ms = (ctypes.c_double * 4)()
-    kh.ksh_consolidation_candidates.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
-                                                ctypes.POINTER(ctypes.c_double)]
-    rc = kh.ksh_consolidation_candidates(snapshot._p, pn_ptr, dl.ctypes.data, len(deleting), ctypes.byref(inp), ctypes.byref(pb), device, ctypes.byref(out), ms)
+    kh.ksh_consolidation_candidates_ex.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32,
+                                                   ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]
+    rc = kh.ksh_consolidation_candidates_ex(snapshot._p, pn_ptr, dl.ctypes.data, len(deleting), ctypes.byref(inp), ctypes.byref(pb), device,
+                                            KSH_CAND_WIDE_SELECTORS if wide_selectors else 0, ctypes.byref(out), ms)
     if rc != KS_OK:
         raise KSolveError(rc, kh.ksh_last_error().decode())
     return {"order": [int(x) for x in order[:out.n_candidates]], "empty": [int(x) for x in empty[:out.n_empty]], "why": why[:n_nodes], "detail": detail[:n_nodes],
@@ -1077,9 +1081,9 @@ def deprovisioning_candidates(snapshot: "ParsedProblem", method: int, pod_node: 
                               node_creation_unix_nanos: Sequence[int], node_age_seconds: Sequence[float], pod_flags: Sequence[int], pod_deletion_cost: Sequence[float],
                               pod_priority: Sequence[int], prov_ttl_seconds: Sequence[Optional[int]], prov_ttl_seconds_after_empty: Sequence[Optional[int]] = None,
                               node_emptiness_unix_nanos: Sequence[int] = None, drift_enabled: bool = False, pdbs=(), deleting: Sequence[int] = (), device: int = 0,
-                              out: Optional[dict] = None) -> dict:
+                              out: Optional[dict] = None, wide_selectors: bool = False) -> dict:
     """candidateNodes under Expiration / Drift / Emptiness.ShouldDeprovision and the order their ComputeCommand walks, in ONE call (kshost.h
-    `ksh_deprovisioning_candidates`; `method`: KSH_METHOD_*).  Arrays as for `consolidation_candidates`; times are unix nanoseconds as Python ints (exact int64 arithmetic
+    `ksh_deprovisioning_candidates_ex`; `method`: KSH_METHOD_*; `wide_selectors`: as for `consolidation_candidates`).  Arrays as for `consolidation_candidates`; times are unix nanoseconds as Python ints (exact int64 arithmetic
     on the device); `node_flags` may carry KSH_CAND_NODE_HAS_EMPTINESS_TIMESTAMP / _EMPTINESS_UNPARSABLE / _DRIFTED; ttls: None (or -1) for nil.  Returns
     `consolidation_candidates`' dict plus "n_in_result": len(candidateNodes(...)) -- the controller moves to the next method when it is 0."""
     import numpy as np
@@ -1112,9 +1116,10 @@ def deprovisioning_candidates(snapshot: "ParsedProblem", method: int, pod_node: 
     pn, pn_ptr = _pod_node_arg(pod_node)
     dl = _u32s(deleting)
     ms = (ctypes.c_double * 4)()
-    kh.ksh_deprovisioning_candidates.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
-                                                 ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]
-    rc = kh.ksh_deprovisioning_candidates(snapshot._p, method, pn_ptr, dl.ctypes.data, len(deleting), ctypes.byref(inp), ctypes.byref(pb), device, ctypes.byref(res), ms)
+    kh.ksh_deprovisioning_candidates_ex.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                                    ctypes.c_uint32, ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]
+    rc = kh.ksh_deprovisioning_candidates_ex(snapshot._p, method, pn_ptr, dl.ctypes.data, len(deleting), ctypes.byref(inp), ctypes.byref(pb), device,
+                                             KSH_CAND_WIDE_SELECTORS if wide_selectors else 0, ctypes.byref(res), ms)
     if rc != KS_OK:
         raise KSolveError(rc, kh.ksh_last_error().decode())
     return {"order": [int(x) for x in order[:res.base.n_candidates]], "empty": [int(x) for x in empty[:res.base.n_empty]], "why": why[:n_nodes], "detail": detail[:n_nodes],
