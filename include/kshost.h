@@ -206,11 +206,27 @@ int ksh_types_subset(void** handles, uint32_t n, const uint32_t* node, const uin
  * ksh_check_whatif_derivation.  A parsed object keeps the flag-on flattenings (environment cache, snapshot) apart from the flag-off ones; after ksh_env_apply / _block an
  * event that makes a new name active falls back to the full flattening, as a new label value does.  Without the flag nothing changes. */
 #define KSH_ACTIVE_RESOURCES (1u << 17)
+/* KSH_DERIVE_GROUP_LISTS (opt-in; a library flag like KSH_DERIVE_VOLUMES: a bit no KS_FLAG_* uses, stripped before the flat problem is built): what a derived what-if's
+ * topology takes from its candidate set is held as LISTS PER NODE -- one entry (group, count, domain or stay count, owner bit) per (node, group) pair where a pod on
+ * the node is counted by the group or owns it (ksolve.h ks_whatif_topo_lists) -- instead of two dense [groups][nodes] tables, and ANY number of topology groups is
+ * accepted: the 1024 above are the dense kernel's shape (one thread per group in one block), not a property of the problem.  The host evaluates the node filter and
+ * the key-present test for such pairs only; an open copies the lists (entries, not groups x nodes) into its arena; ks_derive_topology_lists walks a candidate node's
+ * entries.  Every other refusal above stays, and the what-ifs are the dense route's cell by cell (the debug call below reads them).  The flag-on flattening of the
+ * snapshot is kept apart from the flag-off one, so ksh_snapshot_fingerprint with flags 0 does not move; after ksh_env_apply / _block the lists are rebuilt where the tables are.
+ * Accepted by ksh_open_whatifs_derived, ksh_consolidation_commands / ksh_first_n_node_option / ksh_single_node_option, ksh_replacement_commands / _option,
+ * ksh_validate_commands, ksh_single_node_resume, ksh_check_whatif_derivation (which then restates the derivation from the lists) and ksh_snapshot_fingerprint; combines
+ * with KSH_DERIVE_VOLUMES and KSH_ACTIVE_RESOURCES.  Where a command call falls back to flattening the what-ifs one by one the flag is dropped.  Without the flag nothing
+ * changes, the refusal above 1024 groups included. */
+#define KSH_DERIVE_GROUP_LISTS (1u << 18)
 int ksh_open_whatifs_derived(void* parsed_snapshot, uint32_t flags, uint32_t n, const uint32_t* cand_off, const uint32_t* cand, const int32_t* pod_node, int device, void** out_handles);
+/* Diagnostic: ks_debug_whatif_topology of ksolve.h for the handle of a derived what-if -- the group activity [G], domain counts [G][64] and positive-hostname
+ * extras [GH] its derivation left (ksh_dims names G and GH; any destination may be NULL).  Read-only, launches nothing; KS_ERR_INVALID for any other handle. */
+int ksh_debug_whatif_topology(void* handle, uint8_t* out_active, int32_t* out_count, int32_t* out_extra);
+uint64_t ksh_whatifs_upload_bytes(void* handle);     /* a derived what-if: the bytes its batch's open copied to the device (ks_whatifs_upload_bytes); 0 for any other handle */
 uint64_t ksh_whatifs_arena_bytes(void* handle);      /* a derived what-if: device bytes of the arena its batch shares (ks_whatifs_arena_bytes); 0 for any other handle */
 int ksh_open_whatifs_parsed(void* parsed_snapshot, uint32_t flags, uint32_t n, const uint32_t* cand_off, const uint32_t* cand, const int32_t* pod_node, uint32_t nthreads, void** out_handles);
 /* Diagnostic (no GPU needed, not on any solving path): what the device would derive for ONE candidate set -- group activity, domain counts, hostname rows --
- * restated in plain loops over the per-node tables and compared with that what-if flattened by itself.  KS_OK, or KS_ERR_INVALID with the first difference
+ * restated in plain loops over the per-node tables (under KSH_DERIVE_GROUP_LISTS: over the per-node lists) and compared with that what-if flattened by itself.  KS_OK, or KS_ERR_INVALID with the first difference
  * in ksh_last_error(); KS_ERR_UNSUPPORTED for a snapshot ksh_open_whatifs_derived refuses.  With KSH_DERIVE_VOLUMES it also restates, for every node that
  * stays, the volume counts and limits per driver and the multi claims it lists, and for every pod of the batch on every such node whether the volume test
  * admits it and what it adds per driver -- against the what-if's own (candidate-dependent) partition. */
@@ -220,7 +236,7 @@ int ksh_check_whatif_derivation(void* parsed_snapshot, uint32_t flags, const uin
  * firstNNodeConsolidationOption + filterOutSameType, singlenodeconsolidation.go:54-78 the scan of SingleNodeConsolidation.ComputeCommand): snapshot and candidate
  * sets in, one fixed-size row per candidate set out (layout: ksolve.h KS_CMD_*, KS_CMD_ROW_WORDS(words) uint64 each, words >= ceil(T/64)).
  * ksh_consolidation_commands opens the what-ifs derived on the device (flags: KS_FLAG_SIMULATION / _NO_RR / _ONE_WAVE / _NO_LEAN, KSH_DERIVE_VOLUMES,
- * KSH_ACTIVE_RESOURCES; any other bit is KS_ERR_INVALID) -- flattened one by one and uploaded where ksh_open_whatifs_derived answers KS_ERR_UNSUPPORTED --, solves
+ * KSH_ACTIVE_RESOURCES, KSH_DERIVE_GROUP_LISTS; any other bit is KS_ERR_INVALID) -- flattened one by one and uploaded where ksh_open_whatifs_derived answers KS_ERR_UNSUPPORTED --, solves
  * them resident in one launch, decides all of them in one more (ks_consolidation_commands_dev), reads the rows back and closes the handles.  Nothing but the rows
  * crosses back: no result is decoded on the host.  What the decision reads beside the simulation comes from the parsed nodes' labels:
  *   node.kubernetes.io/instance-type, topology.kubernetes.io/zone, karpenter.sh/capacity-type of every candidate: getNodePrices (the sum, in candidate order, of

@@ -405,8 +405,31 @@ typedef struct ks_whatifs_options {
 } ks_whatifs_options;
 int ks_whatifs_open_ex(const ks_dev_problem* base, uint32_t n_nodes, const int32_t* pod_node, const int32_t* node_row, uint32_t n, const uint32_t* cand_off,
                        const uint32_t* cand, const uint32_t* n_pods, const int64_t* remaining, const ks_whatifs_options* opt, ks_whatif_batch** out);
+/* The same per-node facts as LISTS (libkshost: KSH_DERIVE_GROUP_LISTS): a CSR by node with one entry per (node, group) pair that matters -- a pod on the node
+ * that the group counts, or that owns it -- instead of the two dense [G][n_nodes] tables and the [n_nodes][ceil(G/64)] owner words.  Any number of groups
+ * (the 1024 of ks_whatif_topo came from the dense kernel's shape: one thread per group in one block); what is copied per open grows with the entries, not with G * n_nodes.
+ * Entry k of node n, node_off[n] <= k < node_off[n + 1], ascending in g: */
+typedef struct ks_whatif_topo_lists {
+  const uint32_t* node_off;   /* [n_nodes + 1] ascending; node_off[n_nodes] = n_entries */
+  const uint32_t* ent_g;      /* [n_entries]  the group id; bit 31 (KS_TOPO_ENT_OWN): some pod bound to the node owns the group (ks_whatif_topo::node_own's bit) */
+  const int32_t* ent_cnt;     /* [n_entries]  ks_whatif_topo::node_cnt[g][n] */
+  const int32_t* ent_dom;     /* [n_entries]  ks_whatif_topo::node_dom[g][n]: the domain's value id in [0, 64) wherever ent_cnt != 0, or -1; hostname-keyed groups: the stay count */
+  uint64_t n_entries;
+  const int32_t* tot;         /* [G][64]      as ks_whatif_topo */
+  const int32_t* extra_tot;   /* [GH]         as ks_whatif_topo */
+  const int32_t* grph_base;   /* [GH][E]      as ks_whatif_topo */
+} ks_whatif_topo_lists;
+#define KS_TOPO_ENT_OWN 0x80000000u
+/* ks_whatifs_open_ex with the topology given as lists (`flags`: KS_WHATIFS_*).  The lists are checked before anything is launched (offsets, group ids, domains):
+ * KS_ERR_INVALID.  The what-ifs it opens are what ks_whatifs_open / _ex open from the dense tables of the same snapshot, cell by cell (ks_debug_whatif_topology). */
+int ks_whatifs_open_lists(const ks_dev_problem* base, uint32_t n_nodes, const int32_t* pod_node, const int32_t* node_row, uint32_t n, const uint32_t* cand_off,
+                          const uint32_t* cand, const uint32_t* n_pods, const int64_t* remaining, const ks_whatif_topo_lists* lists, uint32_t flags, ks_whatif_batch** out);
+/* Diagnostics: what the derivation left a derived what-if with -- grp_active [G], grp_count [G][64], grph_extra_pos [GH] (any of them NULL: not copied).  Read-only,
+ * launches nothing; KS_ERR_INVALID for a problem that is no derived what-if over a snapshot with topology groups. */
+int ks_debug_whatif_topology(ks_dev_problem* d, uint8_t* out_active, int32_t* out_count, int32_t* out_extra);
 ks_dev_problem* const* ks_whatifs_problems(ks_whatif_batch* b);
 uint64_t ks_whatifs_arena_bytes(const ks_whatif_batch* b);          /* device bytes of the batch's arena (diagnostics: tools/time_whatif_volumes.py) */
+uint64_t ks_whatifs_upload_bytes(const ks_whatif_batch* b);         /* of those, the bytes the open copied from the host (one host-to-device copy): masks, descriptors, the per-node topology tables or lists */
 uint32_t ks_whatifs_count(const ks_whatif_batch* b);
 int ks_whatifs_pod_ids(ks_whatif_batch* b, uint32_t i, uint32_t* out /* [n_pods of what-if i] snapshot pod ids, what-if pod order */);
 void ks_whatifs_free(ks_whatif_batch* b);

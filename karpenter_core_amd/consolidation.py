@@ -487,13 +487,20 @@ def _words(snapshot: Snapshot) -> int:
     return (len(snapshot.instance_types) + 63) // 64
 
 
-def compute_consolidations_dev(snapshot: Snapshot, candidate_sets: Sequence[Sequence[int]], timings: Optional[dict] = None) -> List[Command]:
+def _lists_flag(group_lists: bool) -> int:
+    """`group_lists` of the `*_dev` calls that simulate what-ifs: kshost.h KSH_DERIVE_GROUP_LISTS -- the what-ifs are derived on the device for any number of topology
+    groups (per-node lists) instead of falling back to the host above 1024.  The commands are the same either way."""
+    from . import scheduler as S
+    return S.KSH_DERIVE_GROUP_LISTS if group_lists else 0
+
+
+def compute_consolidations_dev(snapshot: Snapshot, candidate_sets: Sequence[Sequence[int]], timings: Optional[dict] = None, group_lists: bool = False) -> List[Command]:
     """`compute_consolidations` through `ksh_consolidation_commands`: one call, one command per candidate set.  `timings` (a dict) receives the call's open / solve /
     command kernel / read-back milliseconds."""
     from . import scheduler as S
     parsed, pod_node, leaving = _command_snapshot(snapshot)
     try:
-        rows, ms = S.consolidation_commands(parsed, pod_node, candidate_sets, _words(snapshot), deleting=leaving)
+        rows, ms = S.consolidation_commands(parsed, pod_node, candidate_sets, _words(snapshot), deleting=leaving, flags=_lists_flag(group_lists))
         if timings is not None:
             timings.update(ms)
         return [_command_of_row(snapshot, parsed, rows[i], _words(snapshot), cs) for i, cs in enumerate(candidate_sets)]
@@ -501,12 +508,12 @@ def compute_consolidations_dev(snapshot: Snapshot, candidate_sets: Sequence[Sequ
         parsed.close()
 
 
-def first_n_node_consolidation_option_dev(snapshot: Snapshot, candidates: Sequence[int], max_nodes: int = 100, timings: Optional[dict] = None) -> Command:
+def first_n_node_consolidation_option_dev(snapshot: Snapshot, candidates: Sequence[int], max_nodes: int = 100, timings: Optional[dict] = None, group_lists: bool = False) -> Command:
     """`first_n_node_consolidation_option` through `ksh_first_n_node_option`: every prefix AND its filterOutSameType in one batch, the search replayed in the library."""
     from . import scheduler as S
     parsed, pod_node, leaving = _command_snapshot(snapshot)
     try:
-        row, ms = S.first_n_node_option(parsed, pod_node, candidates, _words(snapshot), max_nodes=max_nodes, deleting=leaving)
+        row, ms = S.first_n_node_option(parsed, pod_node, candidates, _words(snapshot), max_nodes=max_nodes, deleting=leaving, flags=_lists_flag(group_lists))
         if timings is not None:
             timings.update(ms)
         cmd = _command_of_row(snapshot, parsed, row, _words(snapshot), list(candidates[: int(row[S.KS_CMD_ID])]), second_stage=True)
@@ -517,12 +524,12 @@ def first_n_node_consolidation_option_dev(snapshot: Snapshot, candidates: Sequen
         parsed.close()
 
 
-def single_node_consolidation_option_dev(snapshot: Snapshot, candidates: Sequence[int], timings: Optional[dict] = None) -> Command:
+def single_node_consolidation_option_dev(snapshot: Snapshot, candidates: Sequence[int], timings: Optional[dict] = None, group_lists: bool = False) -> Command:
     """`single_node_consolidation_option` through `ksh_single_node_option`."""
     from . import scheduler as S
     parsed, pod_node, leaving = _command_snapshot(snapshot)
     try:
-        row, ms = S.single_node_option(parsed, pod_node, candidates, _words(snapshot), deleting=leaving)
+        row, ms = S.single_node_option(parsed, pod_node, candidates, _words(snapshot), deleting=leaving, flags=_lists_flag(group_lists))
         if timings is not None:
             timings.update(ms)
         if (int(row[S.KS_CMD_DECISION]) & 0xFF) == S.KS_CMD_DO_NOTHING:
@@ -647,7 +654,7 @@ def emptiness_command_dev(snapshot: Snapshot, info: CandidateInfo, device: int =
         parsed.close()
 
 
-def _replacement_command_dev(snapshot: Snapshot, info: CandidateInfo, method: int, device: int, timings: Optional[dict]) -> Command:
+def _replacement_command_dev(snapshot: Snapshot, info: CandidateInfo, method: int, device: int, timings: Optional[dict], group_lists: bool = False) -> Command:
     from . import scheduler as S
     parsed, pod_node, leaving = _command_snapshot(snapshot)
     try:
@@ -655,7 +662,7 @@ def _replacement_command_dev(snapshot: Snapshot, info: CandidateInfo, method: in
         if got["n_in_result"] == 0:
             return Command()
         words = _words(snapshot)
-        head, nodes, _, pos, ms = S.replacement_option(parsed, pod_node, got["order"], got["why"], words, deleting=leaving, device=device)
+        head, nodes, _, pos, ms = S.replacement_option(parsed, pod_node, got["order"], got["why"], words, deleting=leaving, device=device, flags=_lists_flag(group_lists))
         if timings is not None:
             timings.update(ms)
         h = S.decode_replacement_head(head)
@@ -674,15 +681,15 @@ def _replacement_command_dev(snapshot: Snapshot, info: CandidateInfo, method: in
         parsed.close()
 
 
-def expiration_command_dev(snapshot: Snapshot, info: CandidateInfo, device: int = 0, timings: Optional[dict] = None) -> Command:
+def expiration_command_dev(snapshot: Snapshot, info: CandidateInfo, device: int = 0, timings: Optional[dict] = None, group_lists: bool = False) -> Command:
     """Expiration through the C ABI: `ksh_deprovisioning_candidates` (most expired first), then `ksh_replacement_option` -- ONE what-if simulated.  Command.replacements
     lists every replacement node.  Follows the reference where `replacement_command` does not: an uninitialised node that stays makes the command a plain delete."""
-    return _replacement_command_dev(snapshot, info, METHOD_EXPIRATION, device, timings)
+    return _replacement_command_dev(snapshot, info, METHOD_EXPIRATION, device, timings, group_lists)
 
 
-def drift_command_dev(snapshot: Snapshot, info: CandidateInfo, device: int = 0, timings: Optional[dict] = None) -> Command:
+def drift_command_dev(snapshot: Snapshot, info: CandidateInfo, device: int = 0, timings: Optional[dict] = None, group_lists: bool = False) -> Command:
     """Drift through the C ABI: one drifted node at a time, in slot order."""
-    return _replacement_command_dev(snapshot, info, METHOD_DRIFT, device, timings)
+    return _replacement_command_dev(snapshot, info, METHOD_DRIFT, device, timings, group_lists)
 
 
 # =====================================================================================================
@@ -700,7 +707,8 @@ def _command_inputs_now(snapshot_now: Snapshot, commands: Sequence[Command]):
     return node_sets, [bool(cmd.replacement_types) for cmd in commands], [[tindex[t] for t in cmd.replacement_types] for cmd in commands]
 
 
-def validate_commands_dev(snapshot_now: Snapshot, commands: Sequence[Command], info: CandidateInfo, device: int = 0, timings: Optional[dict] = None) -> List[Tuple[Optional[bool], int]]:
+def validate_commands_dev(snapshot_now: Snapshot, commands: Sequence[Command], info: CandidateInfo, device: int = 0, timings: Optional[dict] = None,
+                          group_lists: bool = False) -> List[Tuple[Optional[bool], int]]:
     """Validation.IsValid (after its wait) for every command in ONE call: candidates over `snapshot_now` (`ksh_consolidation_candidates`), then `ksh_validate_commands`.
     -> [(valid, why)] per command; valid is None where the reference returns an error (a node of the command that is still a candidate is being deleted); why: ksolve.h
     KS_VAL_WHY_*."""
@@ -709,7 +717,7 @@ def validate_commands_dev(snapshot_now: Snapshot, commands: Sequence[Command], i
     try:
         got, nf = _candidates_call(S, parsed, pod_node, snapshot_now, info, device)
         node_sets, expect, type_sets = _command_inputs_now(snapshot_now, commands)
-        rows, ms = S.validate_commands(parsed, pod_node, node_sets, expect, type_sets, got["why"], nf, _words(snapshot_now), deleting=leaving, device=device)
+        rows, ms = S.validate_commands(parsed, pod_node, node_sets, expect, type_sets, got["why"], nf, _words(snapshot_now), deleting=leaving, device=device, flags=_lists_flag(group_lists))
         if timings is not None:
             timings.update(ms)
         out = []
@@ -721,14 +729,15 @@ def validate_commands_dev(snapshot_now: Snapshot, commands: Sequence[Command], i
         parsed.close()
 
 
-def single_node_resume_dev(snapshot_now: Snapshot, candidates: Sequence[int], failed_before: bool, info: CandidateInfo, device: int = 0, timings: Optional[dict] = None) -> Tuple[str, Command]:
+def single_node_resume_dev(snapshot_now: Snapshot, candidates: Sequence[int], failed_before: bool, info: CandidateInfo, device: int = 0, timings: Optional[dict] = None,
+                           group_lists: bool = False) -> Tuple[str, Command]:
     """The rest of SingleNodeConsolidation.ComputeCommand's loop after a validation has failed, through `ksh_single_node_resume`: `candidates` are the node indices (of
     `snapshot_now`) that follow the failed one.  -> ("found", the valid command) | ("retry", Command()) | ("do-nothing", Command())."""
     from . import scheduler as S
     parsed, pod_node, leaving = _command_snapshot(snapshot_now)
     try:
         got, nf = _candidates_call(S, parsed, pod_node, snapshot_now, info, device)
-        state, row, _, ms = S.single_node_resume(parsed, pod_node, candidates, failed_before, got["why"], nf, _words(snapshot_now), deleting=leaving, device=device)
+        state, row, _, ms = S.single_node_resume(parsed, pod_node, candidates, failed_before, got["why"], nf, _words(snapshot_now), deleting=leaving, device=device, flags=_lists_flag(group_lists))
         if timings is not None:
             timings.update(ms)
         if state != 1:

@@ -1272,7 +1272,7 @@ __device__ __attribute__((noinline)) u32 rr_phase_a(const int lane, const u32 ci
       dst[lane] = src[lane]; if ((u32)lane + 64 < KS_PLAN_V) dst[lane + 64] = src[lane + 64];
       LSYNC(); if (lane == 0) L.staged_cls = cidx;
     }
-    stage_class(tb, sh, lane);      // (the per-pod, node-independent part of the topology items: domainMinCount; re-done every time: the counters move)
+    stage_class<false>(tb, sh, lane);      // (the per-pod, node-independent part of the topology items: domainMinCount; re-done every time: the counters move)
     const ClsPlan& c = sh.cls;
     cr.tol = UF64(c.tol); cr.reqmask = UF(c.reqmask); cr.ntouch = UF(c.ntouch); cr.nhost = 0; cr.hn_mode = 0; cr.port_cnt = 0; cr.vol_cnt = 0; cr.it_state = 0; cr.tkeys = UF64(c.tkeys); cr.eq = 0;
 #pragma unroll

@@ -391,8 +391,8 @@ struct PlanTouch {   // one narrow key the class touches: its own requirement (i
 };
 struct PlanTopo {    // static part of one matching topology group (getMatchingTopologies, topology.go:351-364)
   u64 PD;            // podDomains.Has(value) over the key's universe
-  i32 g; i32 maxskew; u8 type; u8 self; u8 pod_has; u8 hslot; u32 pad;
-};
+  i32 g; i32 maxskew; u8 type; u8 self; u8 pod_has; u8 hslot; u32 hrow;      // hrow: a hostname-keyed group's row of the hostname tables (grp_hslot) in full -- a snapshot that serves
+};                                                                               // derived what-ifs may hold more than 256 of them; hslot: its low 8 bits, for the variants that take GH <= 32
 struct PlanRec { i32 g; i32 key; u8 type; u8 owned_inverse; u16 hslot; u8 tidx; u8 filtered; u16 pad; };   // one group Topology.Record must visit (tidx: touch entry holding its key, 0xFF none)
 struct alignas(16) ClsPlan {
   u32 c, present, complement; i32 it_state;
@@ -456,11 +456,11 @@ __global__ __launch_bounds__(64) void ks_build_plans(const DevProb* probs) {
   const u32 ob = P.cls_own_off[c], oe = P.cls_own_off[c + 1], ib = P.cls_isel_off[c], ie = P.cls_isel_off[c + 1];
   for (u32 i = 0; i < (oe - ob) + (ie - ib); ++i) {
     const u32 ent = i < oe - ob ? P.own_list[ob + i] : P.isel_list[ib + (i - (oe - ob))];
-    PlanTopo it; it.g = (i32)(ent & 0x7FFFFFFFu); it.self = ent >> 31; it.type = P.grp_type[it.g]; it.maxskew = P.grp_max_skew[it.g]; it.pod_has = 0; it.PD = ~0ull; it.hslot = 0; it.pad = 0;
+    PlanTopo it; it.g = (i32)(ent & 0x7FFFFFFFu); it.self = ent >> 31; it.type = P.grp_type[it.g]; it.maxskew = P.grp_max_skew[it.g]; it.pod_has = 0; it.PD = ~0ull; it.hslot = 0; it.hrow = 0;
     const i32 k = P.grp_key[it.g];
     if (k == KS_KEY_HOSTNAME) {
       if (pl.nhost >= KS_MAX_HOST) { pl.overflow = 1; continue; }
-      it.hslot = (u8)P.grp_hslot[it.g]; pl.host[pl.nhost++] = it; continue;
+      it.hslot = (u8)P.grp_hslot[it.g]; it.hrow = (u32)P.grp_hslot[it.g]; pl.host[pl.nhost++] = it; continue;
     }
     KReq pd = kreq_exists();
     if ((pl.present >> k) & 1u) { pd = load_req(pl.present, pl.complement, P.cls.mask + (size_t)c * P.K, P.cls.gt + (size_t)c * P.K, P.cls.lt + (size_t)c * P.K, k); it.pod_has = 1; }
@@ -804,9 +804,9 @@ __device__ __forceinline__ void eval_node(const DevProb& P, const DevState& S, c
   KReq nxt = kreq_absent();
   if (ntouch) nxt = rec_req<BOUNDS>(r, present, complement, (int)((u32)cr.tkeys & 31u));
   i32 hc0 = -1, hc1 = -1, hc2 = -1;
-  if (cr.nhost > 0) hc0 = tb.hcnt[(size_t)slot * tb.GH + UF(c.host[0].hslot)];
-  if (cr.nhost > 1) hc1 = tb.hcnt[(size_t)slot * tb.GH + UF(c.host[1].hslot)];
-  if (cr.nhost > 2) hc2 = tb.hcnt[(size_t)slot * tb.GH + UF(c.host[2].hslot)];
+  if (cr.nhost > 0) hc0 = tb.hcnt[(size_t)slot * tb.GH + UF(c.host[0].hrow)];
+  if (cr.nhost > 1) hc1 = tb.hcnt[(size_t)slot * tb.GH + UF(c.host[1].hrow)];
+  if (cr.nhost > 2) hc2 = tb.hcnt[(size_t)slot * tb.GH + UF(c.host[2].hrow)];
 
   // ---- Taints.Tolerates, taints.go:28-40 ----
   if (taints & ~cr.tol) return;
@@ -1101,6 +1101,8 @@ __device__ __forceinline__ i64 wave_max_i64(i64 v) { for (int off = 32; off > 0;
 // The plan itself reaches LDS from registers: it was prefetched while the previous pod was being placed.
 constexpr u32 KS_PLAN_V = sizeof(ClsPlan) / 16;
 static_assert(KS_PLAN_V <= 128, "a class plan is prefetched as two 16-byte registers per lane");
+// WIDE_ROWS: a hostname item's row is read in full (PlanTopo::hrow); false: from its 8 bits, for a kernel that takes GH <= 256 only (ks_pack_rr: GH <= 32)
+template <bool WIDE_ROWS = true>
 __device__ __forceinline__ void stage_class(const Tabs& tb, WaveShared& sh, int lane) {
   LSYNC();
   const ClsPlan& L = sh.cls;
@@ -1110,7 +1112,7 @@ __device__ __forceinline__ void stage_class(const Tabs& tb, WaveShared& sh, int 
     for (u64 b = d.reg & t.PD; b; b &= b - 1) { const i32 cn = tb.gcnt[(size_t)t.g * 64 + __builtin_ctzll(b)]; if (cn < mn) mn = cn; }
     d.minc = mn; sh.dyn[lane] = d;
   }
-  if (lane >= 32 && (u32)(lane - 32) < L.nhost) { sh.host_anypos[lane - 32] = tb.g_hpos[L.host[lane - 32].hslot] > 0; sh.host_zero[lane - 32] = tb.g_hzero[L.host[lane - 32].hslot]; }
+  if (lane >= 32 && (u32)(lane - 32) < L.nhost) { const u32 row = WIDE_ROWS ? L.host[lane - 32].hrow : (u32)L.host[lane - 32].hslot; sh.host_anypos[lane - 32] = tb.g_hpos[row] > 0; sh.host_zero[lane - 32] = tb.g_hzero[row]; }
   LSYNC();
 }
 
@@ -1889,7 +1891,7 @@ __global__ __launch_bounds__(64 * NW) void ks_pack(const DevProb* probs, const D
         const bool want_zl = kw == 0 && (i32)UF(P.dyn_key) >= 0 && slot != 0xFFFFFFFFu; const u32 dk = want_zl ? UF((u32)P.dyn_key) : 0u;
         u64 zm_pre = 0; if (want_zl) zm_pre = slot_rec(S, tb, slot).mask()[dk];
         const u32 dyn2 = UF(c.dyn) & 2u; u32 h0f = 0, h0slot = 0; i32 h0max = 0, hc_pre = 0;
-        if (dyn2) { const PlanTopo& th = c.host[0]; h0f = UF(*(const u32*)&th.type); h0slot = UF(th.hslot); h0max = (i32)UF(th.maxskew); if (slot != 0xFFFFFFFFu) hc_pre = tb.hcnt[(size_t)slot * tb.GH + h0slot]; }
+        if (dyn2) { const PlanTopo& th = c.host[0]; h0f = UF(*(const u32*)&th.type); h0slot = UF(th.hslot);      /* (dyn tag 2 is set under GH <= 24 only: the 8 bits are the row) */ h0max = (i32)UF(th.maxskew); if (slot != 0xFFFFFFFFu) hc_pre = tb.hcnt[(size_t)slot * tb.GH + h0slot]; }
         if (slot != 0xFFFFFFFFu) eval_node<BOUNDS, LEAN, RM>(P, S, tb, sh, wb, slot, slot < tb.E, false, ev, lane, tprobe, cr, dync);
         if (want_zl && ((ev.present >> dk) & 1u) && !((ev.complement >> dk) & 1u) && __builtin_popcountll(zm_pre) == 1) zl = (u32)__builtin_ctzll(zm_pre);
         const u64 mo = ballot64((ev.rc & 3) == 2 && ev.rc > 0);
@@ -3185,6 +3187,62 @@ __global__ __launch_bounds__(1024) void ks_derive_topology(const TopoDesc* descs
   if (g >= n_topologies && !owners) d.count[(size_t)g * 64] = INT32_MIN;      // it does not exist in this what-if: the pack kernel's evaluation skips it (see its init)
 }
 
+// The same derivation from per-node LISTS (ks_whatif_topo_lists): one workgroup per what-if, any number of groups, work proportional to the entries of the
+// candidate nodes instead of G * ncand.  Three phases between workgroup barriers:
+//   (a) the what-if's count starts as the snapshot-wide totals, its extra as extra_tot, no group owned yet;
+//   (b) a lane per ENTRY of the candidate nodes (a workgroup scan over the candidates' list lengths maps lanes to entries, so one long list does not serialise a
+//       lane): value-keyed groups subtract the node's pods from their domain, hostname-keyed groups move extra -- ks_derive_topology's arithmetic --, an owner's entry
+//       marks the group.  Integer atomics on the what-if's own cells: adds commute, the result does not depend on the order.
+//   (c) a wave per group, lane = domain: NewTopologyGroup's registered domains join, -1 for what is not registered, the INT32_MIN mark of an inverse group that does not
+//       exist (ks_derive_topology's last lines, with the 64 domains across the lanes instead of a private array).
+// The what-if's cells are written and read by this workgroup alone, but the atomics execute in L2 while a plain load may be served by the CU's L1: phase (c) reads
+// what (a) and (b) wrote with agent-scope loads (L2-served).  Every index is checked on the host before the launch (whatifs_open): g < G, domain < 64 where cnt != 0.
+__global__ __launch_bounds__(256) void ks_derive_topology_lists(const TopoDesc* descs, u32 G, u32 GH, const u32* node_off, const u32* ent_g, const i32* ent_cnt, const i32* ent_dom,
+                                                              const i32* tot, const i32* reg, const i32* extra_tot, const i32* grp_hslot, const i32* node_row, u32 n_topologies) {
+  const TopoDesc d = descs[blockIdx.x]; const u32 t = threadIdx.x, lane = t & 63u, wv = t >> 6;
+  __shared__ u32 s_pre[256], s_beg[256], s_nd[256], s_wave[4];
+  // ---- (a) ----
+  for (size_t c = t; c < (size_t)G * 64; c += 256) d.count[c] = tot[c];
+  for (u32 g = t; g < G; g += 256) d.active[g] = 0;      // (until phase (c): "a pod of the batch owns it", for inverse groups too)
+  for (u32 h = t; h < GH; h += 256) d.extra[h] = extra_tot[h];
+  __syncthreads();
+  // ---- (b) ----
+  for (u32 i0 = 0; i0 < d.ncand; i0 += 256) {
+    u32 len = 0, beg = 0, nd = 0;
+    if (i0 + t < d.ncand) { nd = d.cand[i0 + t]; beg = node_off[nd]; len = node_off[nd + 1] - beg; }
+    u32 inc = len;      // inclusive scan of the list lengths: within the wave, then over the four wave totals
+    for (u32 o = 1; o < 64; o <<= 1) { const u32 y = __shfl(inc, (int)(lane >= o ? lane - o : lane)); if (lane >= o) inc += y; }
+    if (lane == 63) s_wave[wv] = inc;
+    __syncthreads();
+    u32 before = 0; for (u32 w = 0; w < wv; ++w) before += s_wave[w];
+    const u32 total = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+    s_pre[t] = before + inc - len; s_beg[t] = beg; s_nd[t] = nd;
+    __syncthreads();
+    for (u32 e = t; e < total; e += 256) {
+      u32 j = 0; for (u32 step = 128; step; step >>= 1) if (s_pre[j + step] <= e) j += step;      // the last candidate whose list begins at or before e (empty lists share a begin with their successor)
+      const u32 k = s_beg[j] + (e - s_pre[j]); const u32 gw = ent_g[k], g = gw & 0x7FFFFFFFu; const i32 cnt = ent_cnt[k], dom = ent_dom[k];
+      if (gw >> 31) d.active[g] = 1;
+      const i32 hs = grp_hslot[g];
+      if (hs >= 0) {      // (ent_dom of a hostname-keyed group: the pods that are never in a batch, as in ks_derive_topology)
+        const i32 stay = dom, all = stay + cnt; const i32 delta = node_row[s_nd[j]] < 0 ? (stay > 0) - (all > 0) : (i32)(stay > 0);
+        if (delta) atomicAdd(&d.extra[hs], delta);
+      } else if (dom >= 0 && cnt != 0) atomicAdd(&d.count[(size_t)g * 64 + (u32)dom], -cnt);
+    }
+    __syncthreads();
+  }
+  // ---- (c) ----
+  for (u32 g = wv; g < G; g += 4) {
+    const bool own = __hip_atomic_load(&d.active[g], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
+    const i32 r = reg[(size_t)g * 64 + lane]; i32 x = r;      // (hostname key: the rows are the snapshot's; the count cells are the snapshot's registered domains)
+    const bool value_keyed = grp_hslot[g] < 0;
+    if (value_keyed) { const i32 c = __hip_atomic_load(&d.count[(size_t)g * 64 + lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); x = (r >= 0 || c > 0) ? (r > 0 ? r : 0) + c : -1; }
+    const bool owners = own || __ballot(x > 0) != 0;      // an inverse group exists while an owner is in the batch, stays bound outside it, or is in no batch at all (topology.go:181-229)
+    if (value_keyed && g >= n_topologies && !owners && lane == 0) x = INT32_MIN;      // it does not exist in this what-if: the pack kernel's evaluation skips it
+    d.count[(size_t)g * 64 + lane] = x;
+    if (lane == 0 && g >= n_topologies && !own) d.active[g] = 1;      // (a hostname-keyed inverse group with zero counts constrains nothing: it may exist in every what-if)
+  }
+}
+
 struct ks_whatif_batch {
   int device = 0; u32 n = 0; hipStream_t stream = nullptr; bool own_stream = false;
   Arena a;      // the state of every what-if, and what their derivation reads
@@ -3201,6 +3259,7 @@ extern "C" void ks_whatifs_free(ks_whatif_batch* b) {
 extern "C" ks_dev_problem* const* ks_whatifs_problems(ks_whatif_batch* b) { return b ? b->views.data() : nullptr; }
 extern "C" uint32_t ks_whatifs_count(const ks_whatif_batch* b) { return b ? b->n : 0; }
 extern "C" uint64_t ks_whatifs_arena_bytes(const ks_whatif_batch* b) { return b ? (uint64_t)b->a.bytes() : 0; }
+extern "C" uint64_t ks_whatifs_upload_bytes(const ks_whatif_batch* b) { return b ? (uint64_t)b->a.sz[Arena::COPIED] : 0; }
 
 // base: the resident snapshot (tables built).  pod_node[base P]: snapshot node index of every snapshot pod (-1: none); node_row[n_nodes]: the node's
 // existing-node row in `base`, or -1 (a node no provisioner owns).  What-if w removes nodes cand[cand_off[w] .. cand_off[w+1]); n_pods[w] = pods
@@ -3208,14 +3267,24 @@ extern "C" uint64_t ks_whatifs_arena_bytes(const ks_whatif_batch* b) { return b 
 // volumes (ks_whatifs_open_ex, KS_WHATIFS_VOLUMES): a snapshot with volume drivers (ND > 0) is accepted; every what-if gets counts [E][ND] and multi-claim
 // sets [E][SW] of its own in the uninitialised region, which the pack kernel's prologue fills from the snapshot's en_vol_count / en_vol_set like any problem's.
 static int whatifs_open(const ks_dev_problem* base, uint32_t n_nodes, const int32_t* pod_node, const int32_t* node_row, uint32_t n, const uint32_t* cand_off,
-                        const uint32_t* cand, const uint32_t* n_pods, const int64_t* remaining, const ks_whatif_topo* topo, bool volumes, ks_whatif_batch** out) {
+                        const uint32_t* cand, const uint32_t* n_pods, const int64_t* remaining, const ks_whatif_topo* topo, const ks_whatif_topo_lists* lists, bool volumes, ks_whatif_batch** out) {
   if (out) *out = nullptr;
   if (!base || !out || (n && (!cand_off || !n_pods || !remaining)) || (n_nodes && (!node_row)) || (base->h.P && !pod_node)) return fail(KS_ERR_INVALID, "null argument");
   if (!base->tables_built) return fail(KS_ERR_INVALID, "the snapshot must be resident with its tables built (ks_problem_prepare)");
   if ((base->h.ND && !volumes) || base->h.pod_gid) return fail(KS_ERR_UNSUPPORTED, "what-ifs cannot be derived from a snapshot with volume limits");
   const bool with_topo = base->h.G != 0;
-  if (with_topo && (!topo || !topo->node_cnt || !topo->node_dom || !topo->node_own || !topo->tot || (base->h.GH && (!topo->extra_tot || (base->h.E && !topo->grph_base))))) return fail(KS_ERR_UNSUPPORTED, "the snapshot has topology groups: their per-node tables (ks_whatif_topo) are needed to derive what-ifs from it");
-  if (with_topo && base->h.G > 1024) return fail(KS_ERR_UNSUPPORTED, "derived what-ifs: at most 1024 topology groups");
+  if (with_topo && !lists && (!topo || !topo->node_cnt || !topo->node_dom || !topo->node_own || !topo->tot || (base->h.GH && (!topo->extra_tot || (base->h.E && !topo->grph_base))))) return fail(KS_ERR_UNSUPPORTED, "the snapshot has topology groups: their per-node tables (ks_whatif_topo) are needed to derive what-ifs from it");
+  if (with_topo && !lists && base->h.G > 1024) return fail(KS_ERR_UNSUPPORTED, "derived what-ifs: at most 1024 topology groups");
+  if (with_topo && lists) {      // the lists, checked: ks_derive_topology_lists indexes with what they hold
+    if (!lists->node_off || !lists->tot || (lists->n_entries && (!lists->ent_g || !lists->ent_cnt || !lists->ent_dom)) || (base->h.GH && (!lists->extra_tot || (base->h.E && !lists->grph_base))))
+      return fail(KS_ERR_UNSUPPORTED, "the snapshot has topology groups: their per-node lists (ks_whatif_topo_lists) are needed to derive what-ifs from it");
+    if (lists->n_entries >= (1ull << 32) || lists->node_off[0] != 0 || lists->node_off[n_nodes] != lists->n_entries) return fail(KS_ERR_INVALID, "ks_whatif_topo_lists: node_off does not span the entries");
+    for (uint32_t i = 0; i < n_nodes; ++i) if (lists->node_off[i + 1] < lists->node_off[i]) return fail(KS_ERR_INVALID, "ks_whatif_topo_lists: node_off not ascending");
+    for (uint64_t k = 0; k < lists->n_entries; ++k) {
+      const uint32_t g = lists->ent_g[k] & ~KS_TOPO_ENT_OWN; if (g >= base->h.G) return fail(KS_ERR_INVALID, "ks_whatif_topo_lists: group id out of range");
+      if (base->src.grp_hslot[g] < 0 && lists->ent_cnt[k] != 0 && (lists->ent_dom[k] < 0 || lists->ent_dom[k] >= 64)) return fail(KS_ERR_INVALID, "ks_whatif_topo_lists: a counted domain is out of range");
+    }
+  }
   const DevProb& bh = base->h; const u32 E = bh.E, M = bh.M, R = bh.R, K = bh.K, TW = bh.TW, C = bh.C, Pb = bh.P;
   const bool vols = volumes && bh.ND != 0;
   HIPCHK(hipSetDevice(base->device));
@@ -3234,14 +3303,20 @@ static int whatifs_open(const ks_dev_problem* base, uint32_t n_nodes, const int3
   }
   // what the two derivation kernels read, in the copied region: pod -> node and the descriptors; with groups, the snapshot's per-node tables
   const i32* d_pod_node = nullptr; const DeriveDesc* d_desc = nullptr; const TopoDesc* d_tdesc = nullptr; u32* d_mismatch = nullptr; const i32* t_cnt = nullptr; const i32* t_dom = nullptr; const u64* t_own = nullptr; const i32* t_tot = nullptr; const i32* t_ext = nullptr; const i32* t_row = nullptr;
+  const u32* l_off = nullptr; const u32* l_g = nullptr; const i32* l_cnt = nullptr; const i32* l_dom = nullptr;
   // ---- one layout, run twice (Arena::lay): the shared tables, then per what-if its copied pieces and its state, then the descriptors ----
   auto layout = [&]() -> int {
     Arena& a = b->a;
     DeriveDesc* hd = nullptr; TopoDesc* htd = nullptr; const i32* t_hbase = nullptr; const i32* t_hg = nullptr; const u32* t_cand = nullptr;
     TRY(dev_copy(a, pod_node, Pb, &d_pod_node));
     if (with_topo) {
-      TRY(dev_copy(a, topo->node_cnt, GN, &t_cnt)); TRY(dev_copy(a, topo->node_dom, GN, &t_dom)); TRY(dev_copy(a, topo->node_own, (size_t)n_nodes * GW, &t_own));
-      TRY(dev_copy(a, topo->tot, (size_t)G * 64, &t_tot)); TRY(dev_copy(a, topo->extra_tot, GH, &t_ext)); TRY(dev_copy(a, topo->grph_base, (size_t)GH * E, &t_hbase));
+      if (lists) {
+        TRY(dev_copy(a, lists->node_off, (size_t)n_nodes + 1, &l_off)); TRY(dev_copy(a, lists->ent_g, (size_t)lists->n_entries, &l_g)); TRY(dev_copy(a, lists->ent_cnt, (size_t)lists->n_entries, &l_cnt)); TRY(dev_copy(a, lists->ent_dom, (size_t)lists->n_entries, &l_dom));
+        TRY(dev_copy(a, lists->tot, (size_t)G * 64, &t_tot)); TRY(dev_copy(a, lists->extra_tot, GH, &t_ext)); TRY(dev_copy(a, lists->grph_base, (size_t)GH * E, &t_hbase));
+      } else {
+        TRY(dev_copy(a, topo->node_cnt, GN, &t_cnt)); TRY(dev_copy(a, topo->node_dom, GN, &t_dom)); TRY(dev_copy(a, topo->node_own, (size_t)n_nodes * GW, &t_own));
+        TRY(dev_copy(a, topo->tot, (size_t)G * 64, &t_tot)); TRY(dev_copy(a, topo->extra_tot, GH, &t_ext)); TRY(dev_copy(a, topo->grph_base, (size_t)GH * E, &t_hbase));
+      }
       TRY(dev_copy(a, node_row, n_nodes, &t_row)); TRY(dev_copy(a, cand, cand_off[n], &t_cand));
       i32* hg = nullptr; TRY(dev_stage(a, GH, &t_hg, &hg));
       if (hg) for (u32 g = 0; g < G; ++g) { const i32 hs = base->src.grp_hslot[g]; if (hs >= 0 && (u32)hs < GH) hg[hs] = (i32)g; }
@@ -3277,7 +3352,8 @@ static int whatifs_open(const ks_dev_problem* base, uint32_t n_nodes, const int3
   };
   TRY(b->a.lay(b->device, layout)); TRY(b->a.send(b->stream));
   if (n) hipLaunchKernelGGL(ks_derive_whatifs, dim3(n), dim3(256), 0, b->stream, bh.queue, d_pod_node, Pb, d_desc, d_mismatch);
-  if (n && with_topo) hipLaunchKernelGGL(ks_derive_topology, dim3(n), dim3(64 * GW), 0, b->stream, d_tdesc, G, GH, n_nodes, t_cnt, t_dom, t_own, t_tot, bh.grp_count, t_ext, bh.grp_hslot, t_row, bh.n_topologies);
+  if (n && with_topo && lists) hipLaunchKernelGGL(ks_derive_topology_lists, dim3(n), dim3(256), 0, b->stream, d_tdesc, G, GH, l_off, l_g, l_cnt, l_dom, t_tot, bh.grp_count, t_ext, bh.grp_hslot, t_row, bh.n_topologies);
+  else if (n && with_topo) hipLaunchKernelGGL(ks_derive_topology, dim3(n), dim3(64 * GW), 0, b->stream, d_tdesc, G, GH, n_nodes, t_cnt, t_dom, t_own, t_tot, bh.grp_count, t_ext, bh.grp_hslot, t_row, bh.n_topologies);
   u32 mismatch = 0;
   HIPCHK(hipMemcpyAsync(&mismatch, d_mismatch, 4, hipMemcpyDeviceToHost, b->stream));
   HIPCHK(hipStreamSynchronize(b->stream)); HIPCHK(hipGetLastError());
@@ -3286,14 +3362,32 @@ static int whatifs_open(const ks_dev_problem* base, uint32_t n_nodes, const int3
 }
 extern "C" int ks_whatifs_open(const ks_dev_problem* base, uint32_t n_nodes, const int32_t* pod_node, const int32_t* node_row, uint32_t n, const uint32_t* cand_off,
                                const uint32_t* cand, const uint32_t* n_pods, const int64_t* remaining, const ks_whatif_topo* topo, ks_whatif_batch** out) {
-  return whatifs_open(base, n_nodes, pod_node, node_row, n, cand_off, cand, n_pods, remaining, topo, false, out);
+  return whatifs_open(base, n_nodes, pod_node, node_row, n, cand_off, cand, n_pods, remaining, topo, nullptr, false, out);
 }
 extern "C" int ks_whatifs_open_ex(const ks_dev_problem* base, uint32_t n_nodes, const int32_t* pod_node, const int32_t* node_row, uint32_t n, const uint32_t* cand_off,
                                   const uint32_t* cand, const uint32_t* n_pods, const int64_t* remaining, const ks_whatifs_options* opt, ks_whatif_batch** out) {
   if (out) *out = nullptr;
   if (!opt) return fail(KS_ERR_INVALID, "null argument");
   if (opt->flags & ~KS_WHATIFS_VOLUMES) return fail(KS_ERR_INVALID, "unknown KS_WHATIFS_* flag");
-  return whatifs_open(base, n_nodes, pod_node, node_row, n, cand_off, cand, n_pods, remaining, opt->topo, (opt->flags & KS_WHATIFS_VOLUMES) != 0, out);
+  return whatifs_open(base, n_nodes, pod_node, node_row, n, cand_off, cand, n_pods, remaining, opt->topo, nullptr, (opt->flags & KS_WHATIFS_VOLUMES) != 0, out);
+}
+extern "C" int ks_whatifs_open_lists(const ks_dev_problem* base, uint32_t n_nodes, const int32_t* pod_node, const int32_t* node_row, uint32_t n, const uint32_t* cand_off,
+                                     const uint32_t* cand, const uint32_t* n_pods, const int64_t* remaining, const ks_whatif_topo_lists* lists, uint32_t flags, ks_whatif_batch** out) {
+  if (out) *out = nullptr;
+  if (flags & ~KS_WHATIFS_VOLUMES) return fail(KS_ERR_INVALID, "unknown KS_WHATIFS_* flag");
+  if (base && base->h.G && !lists) return fail(KS_ERR_UNSUPPORTED, "the snapshot has topology groups: their per-node lists (ks_whatif_topo_lists) are needed to derive what-ifs from it");
+  return whatifs_open(base, n_nodes, pod_node, node_row, n, cand_off, cand, n_pods, remaining, nullptr, lists, (flags & KS_WHATIFS_VOLUMES) != 0, out);
+}
+// Diagnostics: the topology state the derivation left a derived what-if with.  Copies only: nothing is launched (the open has synchronised its stream).
+extern "C" int ks_debug_whatif_topology(ks_dev_problem* d, uint8_t* out_active, int32_t* out_count, int32_t* out_extra) {
+  if (!d) return fail(KS_ERR_INVALID, "null argument");
+  if (!d->view || !d->h.derived_shared || !d->h.G) return fail(KS_ERR_INVALID, "not a derived what-if over a snapshot with topology groups");
+  HIPCHK(hipSetDevice(d->device));
+  HIPCHK(hipStreamSynchronize(d->stream));
+  if (out_active) HIPCHK(hipMemcpy(out_active, d->h.grp_active, (size_t)d->h.G, hipMemcpyDeviceToHost));
+  if (out_count) HIPCHK(hipMemcpy(out_count, d->h.grp_count, (size_t)d->h.G * 64 * sizeof(i32), hipMemcpyDeviceToHost));
+  if (out_extra && d->h.GH) HIPCHK(hipMemcpy(out_extra, d->h.grph_extra_pos, (size_t)d->h.GH * sizeof(i32), hipMemcpyDeviceToHost));
+  return KS_OK;
 }
 // the snapshot pods behind what-if i's batch, in ITS pod order (= the snapshot's queue order): out[n_pods]
 extern "C" int ks_whatifs_pod_ids(ks_whatif_batch* b, uint32_t i, uint32_t* out) {

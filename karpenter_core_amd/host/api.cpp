@@ -493,7 +493,9 @@ int ksh_open_whatifs_derived(void* parsed, uint32_t flags, uint32_t n, const uin
       }
     }
     lap("masks / remaining (host)");
-    if (in.volumes) {      // (KSH_DERIVE_VOLUMES: the snapshot was flattened with the candidate-independent claim partition; every what-if carries its own volume state)
+    if (in.lists || (flags & KSH_DERIVE_GROUP_LISTS)) {      // (KSH_DERIVE_GROUP_LISTS: the per-node topology facts as lists, any number of groups; a snapshot without groups has none)
+      rc = ks_whatifs_open_lists((const ks_dev_problem*)D->base_dev.get(), in.n_nodes, P->sb_pod_node.data(), in.node_row, n, cand_off, cand, npods.data(), rem.data(), in.lists, in.volumes ? KS_WHATIFS_VOLUMES : 0u, &D->b);
+    } else if (in.volumes) {      // (KSH_DERIVE_VOLUMES: the snapshot was flattened with the candidate-independent claim partition; every what-if carries its own volume state)
       ks_whatifs_options opt{}; opt.topo = in.topo; opt.flags = KS_WHATIFS_VOLUMES;
       rc = ks_whatifs_open_ex((const ks_dev_problem*)D->base_dev.get(), in.n_nodes, P->sb_pod_node.data(), in.node_row, n, cand_off, cand, npods.data(), rem.data(), &opt, &D->b);
     } else rc = ks_whatifs_open((const ks_dev_problem*)D->base_dev.get(), in.n_nodes, P->sb_pod_node.data(), in.node_row, n, cand_off, cand, npods.data(), rem.data(), in.topo, &D->b);
@@ -512,6 +514,12 @@ int ksh_open_whatifs_derived(void* parsed, uint32_t flags, uint32_t n, const uin
   });
 }
 
+int ksh_debug_whatif_topology(void* hv, uint8_t* out_active, int32_t* out_count, int32_t* out_extra) {
+  Handle* h = (Handle*)hv;
+  if (!h || !h->delta || !h->dev) return set_err(KS_ERR_INVALID, "not the handle of a derived what-if");
+  return dev_rc(ks_debug_whatif_topology(h->dev, out_active, out_count, out_extra));
+}
+uint64_t ksh_whatifs_upload_bytes(void* hv) { const Handle* h = (const Handle*)hv; return h && h->delta ? ks_whatifs_upload_bytes(h->delta->b) : 0; }
 uint64_t ksh_whatifs_arena_bytes(void* hv) { const Handle* h = (const Handle*)hv; return h && h->delta ? ks_whatifs_arena_bytes(h->delta->b) : 0; }
 
 // CPU self-check of what ksh_open_whatifs_derived would derive on the device for ONE candidate set (kshost.h).
@@ -819,7 +827,7 @@ struct SimBatch {
   // KS_ERR_INVALID for an unknown flag bit, a row too short, offsets that do not ascend, a node out of range; then the label table and the deleting nodes.  `call` / `row` word the messages
   int begin(Parsed* P_, const char* call, const char* row, uint32_t flags, uint32_t n, const uint32_t* off, const uint32_t* nodes, const uint32_t* deleting, uint32_t n_deleting, uint32_t words) {
     P = P_;
-    const uint32_t known = KS_FLAG_SIMULATION | KS_FLAG_NO_RR | KS_FLAG_ONE_WAVE | KS_FLAG_NO_LEAN | KSH_DERIVE_VOLUMES | KSH_ACTIVE_RESOURCES;
+    const uint32_t known = KS_FLAG_SIMULATION | KS_FLAG_NO_RR | KS_FLAG_ONE_WAVE | KS_FLAG_NO_LEAN | KSH_DERIVE_VOLUMES | KSH_ACTIVE_RESOURCES | KSH_DERIVE_GROUP_LISTS;
     if (flags & ~known) return set_err(KS_ERR_INVALID, std::string(call) + ": unknown flag bit");
     if (!n) return KS_OK;
     const ksp::Problem& pr = *P->pr; const size_t NN = pr.nodes.size(); const uint32_t TW = ((uint32_t)pr.instance_types.size() + 63) / 64;
@@ -861,7 +869,7 @@ struct SimBatch {
     auto t0 = clk::now();
     int rc = ksh_open_whatifs_derived(P, flags, m, off2.data(), cand2.data(), pod_node, device, hs.data());
     if (rc == KS_ERR_UNSUPPORTED) {      // what scheduler.open_whatifs(derive=None) does: flatten the what-ifs one by one, then make them resident
-      rc = ksh_open_whatifs_parsed(P, flags & ~(uint32_t)KSH_DERIVE_VOLUMES, m, off2.data(), cand2.data(), pod_node, 0, hs.data());
+      rc = ksh_open_whatifs_parsed(P, flags & ~(uint32_t)(KSH_DERIVE_VOLUMES | KSH_DERIVE_GROUP_LISTS), m, off2.data(), cand2.data(), pod_node, 0, hs.data());
       // KS_CMD_IT_STATE is spelled out through the snapshot's lattice (ksh_snapshot_it_state): a what-if flattened by itself that needed instance-type states of
       // its own cannot be read that way -- refused here, before anything is uploaded or launched
       for (uint32_t k = 0; rows_name_it_states && k < m && rc == KS_OK; ++k) { const ksh::Encoded& e = *((Handle*)hs[k])->enc; if (!(e.shared && e.shared_lattice)) rc = set_err(KS_ERR_UNSUPPORTED, "a what-if carries instance-type requirement states of its own: simulate it through ksh_open_whatifs_parsed and read it through ksh_result_text"); }

@@ -1695,6 +1695,8 @@ struct SnapshotBase {
   std::vector<int32_t> node_row, node_tmpl; std::vector<int64_t> node_cap; bool delta_ok = false; std::string delta_why;      // (delta_inputs)
   // snapshots with topology groups: what a what-if's NewTopology takes from its candidate set (ksolve.h ks_whatif_topo)
   std::vector<int32_t> t_node_cnt, t_node_dom, t_tot, t_extra_tot, t_grph_base; std::vector<uint64_t> t_node_own; ks_whatif_topo topo{}; bool has_topo = false;
+  // KSH_DERIVE_GROUP_LISTS: the same facts as lists per node (ksolve.h ks_whatif_topo_lists) -- t_tot, t_extra_tot and t_grph_base are shared, the dense tables stay empty
+  bool group_lists = false; std::vector<uint32_t> l_node_off, l_ent_g; std::vector<int32_t> l_ent_cnt, l_ent_dom; ks_whatif_topo_lists lists{}; bool has_lists = false;
 };
 // The per-node tables behind ks_whatif_topo.  A what-if's groups are the snapshot's (its pods' specs are a subset); what depends on the candidate set is
 // which groups a pod of the batch owns from the start, and which cluster pods countDomains still sees: a bound pod's cluster-pod record counts exactly
@@ -1778,10 +1780,100 @@ static std::string build_topo_tables(SnapshotBase& sb, const int32_t* pod_node) 
   sb.topo.extra_tot = sb.t_extra_tot.data(); sb.topo.grph_base = sb.t_grph_base.data(); sb.has_topo = true;
   return "";
 }
+// (KSH_DERIVE_GROUP_LISTS) What build_topo_tables holds in two dense [G][n_nodes] tables and the owner words, as a CSR by node: one entry per (node, group) pair
+// where a pod on the node is counted by the group or owns it -- any number of groups.  The key-present test and FilterMatches run for such pairs only (once per
+// pair, on first touch), not for all G x n_nodes.  Every other refusal of build_topo_tables holds here too.  Returns "" or what stands in the way.
+static std::string build_topo_lists(SnapshotBase& sb, const int32_t* pod_node) {
+  const Builder& b = *sb.builder; const Encoded& E = *sb.enc; const ksp::Problem& pr = *sb.snapshot;
+  const uint32_t G = E.prob.G, GH = E.prob.GH, NE = E.prob.E, NT = E.prob.n_topologies; const size_t NN = pr.nodes.size();
+  if (b.shared_filter_differs) return "two pods share a spread group while their node filters differ: the group's filter is that of the first pod of each batch";
+  for (uint32_t c = 0; c + 1 < E.cls_sel_off.size(); ++c)      // (the kernel's per-class record list: see build_topo_tables)
+    if ((E.cls_sel_off[c + 1] - E.cls_sel_off[c]) + (E.cls_iown_off[c + 1] - E.cls_iown_off[c]) > 24) return "a pod is selected by more than 24 of the snapshot's topology groups (the kernel's per-class record list)";
+  auto grp = [&](uint32_t gi) -> const Group& { return *b.groups[b.group_order[gi]]; };
+  if (NT < G) for (auto& n : pr.nodes) { auto hl = n.labels.find(ksp::kHostname); if (hl != n.labels.end() && hl->second.empty()) return "a node with an empty hostname label under hostname-keyed anti-affinity"; }
+  sb.t_tot.assign((size_t)G * 64, 0); sb.t_extra_tot.assign(GH, 0); sb.t_grph_base.assign((size_t)GH * NE, 0);
+  std::vector<int32_t> key_of(G, -1);
+  for (uint32_t g = 0; g < G; ++g) if (grp(g).key != ksp::kHostname) key_of[g] = b.key_id.at(grp(g).key);
+  // a pair, on first touch: does group g count pods on node n at all (key present, node filter), and under which domain
+  struct Ent { int32_t cnt = 0, dom = -1; bool own = false, known = false, counts = false; };
+  std::vector<std::map<uint32_t, Ent>> per(NN); std::vector<std::unique_ptr<Requirements>> node_req(NN);
+  auto at = [&](size_t n, uint32_t g) -> Ent& {
+    Ent& e = per[n][g]; if (e.known) return e;
+    e.known = true;
+    const Group& gr = grp(g); const bool host = key_of[g] < 0;
+    auto lt = pr.nodes[n].labels.find(gr.key);
+    if (g >= NT) { if (lt == pr.nodes[n].labels.end()) return e; }      // updateInverseAntiAffinity reads the node's label, nothing else
+    else {
+      if (!host && lt == pr.nodes[n].labels.end()) return e;
+      if (!node_req[n]) node_req[n] = std::make_unique<Requirements>(Requirements::FromLabels(pr.nodes[n].labels));
+      if (!FilterMatches(gr.filter, *node_req[n], b.wellKnown)) return e;
+    }
+    e.counts = true; e.dom = host ? 0 : b.value_id(key_of[g], lt->second);      // (hostname-keyed: the count of the pods that are never in a batch)
+    return e;
+  };
+  for (size_t i = 0; i < pr.pods.size(); ++i) {
+    const auto& sg = b.specs[b.pod_spec[i]].stages[0].sg;      // (required anti-affinity terms survive every relaxation: the first stage owns what all stages own)
+    if (pod_node[i] < 0) continue;      // (bound nowhere any more)
+    for (const auto* l : {&sg.own, &sg.iown}) for (int g : *l) at((size_t)pod_node[i], (uint32_t)b.group_remap[g]).own = true;
+  }
+  std::map<std::string, size_t> node_index; for (size_t n = 0; n < NN; ++n) node_index.emplace(pr.nodes[n].name, n);
+  std::unordered_map<std::string, std::vector<uint32_t>> selects;      // (namespace, labels) -> groups that list such a pod (TopologyListOptions: a nil selector lists everything)
+  auto count_one = [&](uint32_t g, size_t n, bool in_a_batch) -> const char* {
+    Ent& e = at(n, g); if (!e.counts) return nullptr;
+    const bool host = key_of[g] < 0;
+    if (in_a_batch) { e.cnt++; if (!host) { if (e.dom < 0 || e.dom >= 64) return "a counted topology domain is missing from the universe"; sb.t_tot[(size_t)g * 64 + e.dom]++; } }
+    else if (host) e.dom++;      // (value-keyed groups: the snapshot's own grp_count already holds the pods that are never in a batch)
+    return nullptr;
+  };
+  for (auto& cp : pr.cluster_pods) {
+    const int64_t pi = b.batch_uids.find(cp.uid);
+    auto ni = node_index.find(cp.node_name); if (ni == node_index.end()) continue;      // countDomains skips pods whose node it cannot find
+    const size_t n = ni->second;
+    if (pi >= 0 && (size_t)pod_node[pi] != n) return "a cluster pod record names another node than the one its pod is bound to";
+    std::string sig = cp.ns; sig += '\3'; sig_map(sig, cp.labels);
+    auto it = selects.find(sig);
+    if (it == selects.end()) {
+      std::vector<uint32_t> m;
+      for (uint32_t g = 0; g < NT; ++g) { const Group& gr = grp(g); if (gr.namespaces.count(cp.ns) && (gr.selector.nil || SelectorMatches(gr.selector, cp.labels))) m.push_back(g); }
+      it = selects.emplace(std::move(sig), std::move(m)).first;
+    }
+    for (uint32_t g : it->second) if (const char* why = count_one(g, n, pi >= 0)) return why;
+    for (auto& t : cp.anti_required) {      // the inverse group its required anti-affinity owns while the pod stays bound (topology.go:181-199)
+      auto gi = b.inverse_by_id.find(Builder::group_id(2, t.topology_key, Builder::ns_list(cp.ns, t.namespaces), t.selector, INT32_MAX, Filter{}));
+      if (gi == b.inverse_by_id.end()) return "a cluster pod's required anti-affinity names a group none of the bound pods owns";
+      if (const char* why = count_one((uint32_t)b.group_remap[gi->second], n, pi >= 0)) return why;
+    }
+  }
+  // hostname-keyed groups: a row without an entry counts nothing -- registered (0) or registered only under an owner of the batch (-2); the entries then say what counts
+  for (uint32_t g = 0; g < G; ++g) {
+    const int32_t hs = E.grp_hslot[g]; if (hs < 0) continue;
+    const Group& gr = grp(g);
+    for (size_t n = 0; n < NN; ++n) {
+      const int32_t e = sb.node_row[n]; if (e < 0) continue;
+      auto hl = pr.nodes[n].labels.find(ksp::kHostname); const std::string& hostname = (hl == pr.nodes[n].labels.end() || hl->second.empty()) ? pr.nodes[n].name : hl->second;
+      sb.t_grph_base[(size_t)hs * NE + e] = (g >= NT || gr.counts.count(hostname)) ? 0 : -2;      // -2: registered only if a pod of the batch owns the group (existingnode.go:73)
+    }
+  }
+  sb.l_node_off.assign(NN + 1, 0); sb.l_ent_g.clear(); sb.l_ent_cnt.clear(); sb.l_ent_dom.clear();
+  for (size_t n = 0; n < NN; ++n) {
+    for (auto& kv : per[n]) {
+      const uint32_t g = kv.first; const Ent& e = kv.second; const int32_t hs = E.grp_hslot[g];
+      if (hs >= 0 && e.cnt + e.dom > 0) { if (sb.node_row[n] < 0) sb.t_extra_tot[hs]++; else sb.t_grph_base[(size_t)hs * NE + sb.node_row[n]] = e.cnt + e.dom; }
+      if (e.cnt == 0 && !(key_of[g] < 0 && e.dom > 0) && !e.own) continue;
+      sb.l_ent_g.push_back(g | (e.own ? KS_TOPO_ENT_OWN : 0u)); sb.l_ent_cnt.push_back(e.cnt); sb.l_ent_dom.push_back(e.dom);
+    }
+    if (sb.l_ent_g.size() >= (1ull << 32)) return "more than 2^32 (node, group) entries";
+    sb.l_node_off[n + 1] = (uint32_t)sb.l_ent_g.size();
+  }
+  sb.lists.node_off = sb.l_node_off.data(); sb.lists.ent_g = sb.l_ent_g.data(); sb.lists.ent_cnt = sb.l_ent_cnt.data(); sb.lists.ent_dom = sb.l_ent_dom.data(); sb.lists.n_entries = sb.l_ent_g.size();
+  sb.lists.tot = sb.t_tot.data(); sb.lists.extra_tot = sb.t_extra_tot.data(); sb.lists.grph_base = sb.t_grph_base.data(); sb.has_lists = true;
+  return "";
+}
 std::shared_ptr<const SnapshotBase> make_snapshot_base(std::shared_ptr<const ksp::Problem> snapshot, const int32_t* pod_node, uint32_t flags, const SnapshotBase* before, const std::vector<ReplacedNode>* replaced,
                                                        const std::vector<ReplacedType>* replaced_types) {
   auto sb = std::make_shared<SnapshotBase>(); sb->snapshot = snapshot;
   sb->volumes = (flags & KSH_DERIVE_VOLUMES) != 0; flags &= ~KSH_DERIVE_VOLUMES;      // (a library flag: the flat problem never carries it)
+  sb->group_lists = (flags & KSH_DERIVE_GROUP_LISTS) != 0; flags &= ~KSH_DERIVE_GROUP_LISTS;      // (another: it decides how the per-node topology facts are held, nothing of the flat problem)
   sb->by_node.resize(snapshot->nodes.size());
   // pod_node[i] = -1: a pod that is bound nowhere any more (ksh_env_apply keeps it in place: nothing that points into the problem moves); it is in no what-if's batch
   for (size_t i = 0; i < snapshot->pods.size(); ++i) { if (pod_node[i] < 0) continue; if ((size_t)pod_node[i] >= snapshot->nodes.size()) throw ksp::Error("pod_node out of range"); sb->by_node[pod_node[i]].push_back((uint32_t)i); }
@@ -1803,7 +1895,7 @@ std::shared_ptr<const SnapshotBase> make_snapshot_base(std::shared_ptr<const ksp
     sb->delta_ok = true;
     if ((b.any_volume_limits || b.pods_have_volumes) && !sb->volumes) { sb->delta_ok = false; sb->delta_why = "volume limits / claims: the shared-claim partition depends on the candidate set"; }
     if (sb->volumes && (size_t)E.prob.E * (4ull * E.prob.ND + 8ull * E.prob.SW) > (64ull << 20)) { sb->delta_ok = false; sb->delta_why = "the per-what-if volume state (counts and multi-claim sets of every node) would exceed 64 MiB"; }
-    if (sb->delta_ok && !b.groups.empty()) { const std::string why = build_topo_tables(*sb, pod_node); if (!why.empty()) { sb->delta_ok = false; sb->delta_why = why; } }
+    if (sb->delta_ok && !b.groups.empty()) { const std::string why = sb->group_lists ? build_topo_lists(*sb, pod_node) : build_topo_tables(*sb, pod_node); if (!why.empty()) { sb->delta_ok = false; sb->delta_why = why; } }
   }
   return sb;
 }
@@ -1815,15 +1907,16 @@ uint64_t snapshot_fingerprint(const SnapshotBase& sb) {
   vec(sb.node_row); vec(sb.node_tmpl); vec(sb.node_cap); vec(sb.builder->pod_rank); vec(sb.builder->pod_spec); for (auto& l : sb.by_node) vec(l);
   const uint8_t ok = sb.delta_ok, topo = sb.has_topo; mix(&ok, 1); mix(&topo, 1); mix(sb.delta_why.data(), sb.delta_why.size());
   vec(sb.t_node_cnt); vec(sb.t_node_dom); vec(sb.t_tot); vec(sb.t_extra_tot); vec(sb.t_grph_base); vec(sb.t_node_own);
+  if (sb.group_lists) { const uint8_t lists = sb.has_lists; mix(&lists, 1); vec(sb.l_node_off); vec(sb.l_ent_g); vec(sb.l_ent_cnt); vec(sb.l_ent_dom); }      // (only under the flag: the flag-0 fingerprint does not move)
   return h;
 }
 DeltaInputs delta_inputs(const SnapshotBase& sb) {
   DeltaInputs d; d.base = sb.enc; d.n_nodes = (uint32_t)sb.snapshot->nodes.size(); d.node_row = sb.node_row.data(); d.by_node = &sb.by_node; d.pod_rank = sb.builder->pod_rank.data();
-  d.node_cap = sb.node_cap.data(); d.node_tmpl = sb.node_tmpl.data(); d.eligible = sb.delta_ok; d.why = sb.delta_why; d.topo = sb.has_topo ? &sb.topo : nullptr;
+  d.node_cap = sb.node_cap.data(); d.node_tmpl = sb.node_tmpl.data(); d.eligible = sb.delta_ok; d.why = sb.delta_why; d.topo = sb.has_topo ? &sb.topo : nullptr; d.lists = sb.has_lists ? &sb.lists : nullptr;
   d.volumes = sb.volumes && sb.enc->prob.ND != 0; return d;
 }
 std::unique_ptr<Encoded> encode_whatif(const SnapshotBase& sb, const uint32_t* cand, uint32_t ncand, uint32_t flags) {
-  flags &= ~KSH_DERIVE_VOLUMES;
+  flags &= ~(KSH_DERIVE_VOLUMES | KSH_DERIVE_GROUP_LISTS);
   auto e = std::make_unique<Encoded>(); e->src = sb.snapshot; e->shared = sb.enc;
   Builder b(*e, flags, *sb.builder, sb.by_node, cand, ncand);
   b.run();
@@ -1896,7 +1989,7 @@ static std::string check_derived_volumes(const SnapshotBase& sb, const Builder& 
 // first difference.  Not on any solving path.
 std::string check_derived_topology(const SnapshotBase& sb, const uint32_t* cand, uint32_t ncand, uint32_t flags) {
   if (!sb.delta_ok) return "not derivable: " + sb.delta_why;
-  flags &= ~KSH_DERIVE_VOLUMES;
+  flags &= ~(KSH_DERIVE_VOLUMES | KSH_DERIVE_GROUP_LISTS);
   const Builder& bb = *sb.builder; const Encoded& EB = *sb.enc; const uint32_t G = EB.prob.G, GH = EB.prob.GH, NE = EB.prob.E, NT = EB.prob.n_topologies, GW = (G + 63) / 64;
   const size_t NN = sb.snapshot->nodes.size();
   auto e = std::make_unique<Encoded>(); e->src = sb.snapshot; e->shared = sb.enc;
@@ -1907,8 +2000,26 @@ std::string check_derived_topology(const SnapshotBase& sb, const uint32_t* cand,
   if (!G) return EW.prob.G ? "the what-if has groups the snapshot lacks" : "";
   // ---- the derivation (ksolve.hip ks_derive_topology + ks_host_count0) ----
   std::vector<uint8_t> active(G, 0); std::vector<int32_t> count((size_t)G * 64, -1), extra(GH, 0); std::vector<uint8_t> exists(G, 1);
-  std::vector<uint64_t> own(GW, 0); for (uint32_t i = 0; i < ncand; ++i) for (uint32_t w = 0; w < GW; ++w) own[w] |= sb.t_node_own[(size_t)cand[i] * GW + w];
-  for (uint32_t g = 0; g < G; ++g) {
+  if (sb.group_lists) {      // ---- (KSH_DERIVE_GROUP_LISTS: ksolve.hip ks_derive_topology_lists, its three phases in plain loops) ----
+    std::vector<uint8_t> owned(G, 0);
+    for (size_t c = 0; c < (size_t)G * 64; ++c) count[c] = sb.t_tot[c];
+    for (uint32_t hs = 0; hs < GH; ++hs) extra[hs] = sb.t_extra_tot[hs];
+    for (uint32_t i = 0; i < ncand; ++i) for (uint32_t k = sb.l_node_off[cand[i]]; k < sb.l_node_off[cand[i] + 1]; ++k) {
+      const uint32_t g = sb.l_ent_g[k] & ~KS_TOPO_ENT_OWN; const int32_t cnt = sb.l_ent_cnt[k], dom = sb.l_ent_dom[k], hs = EB.grp_hslot[g];
+      if (sb.l_ent_g[k] & KS_TOPO_ENT_OWN) owned[g] = 1;
+      if (hs >= 0) { const int32_t stay = dom, all = stay + cnt; if (sb.node_row[cand[i]] < 0) extra[hs] -= (all > 0) - (stay > 0); else extra[hs] += stay > 0; }
+      else if (dom >= 0 && cnt != 0) count[(size_t)g * 64 + dom] -= cnt;
+    }
+    for (uint32_t g = 0; g < G; ++g) {
+      active[g] = g >= NT ? 1 : owned[g];
+      if (EB.grp_hslot[g] >= 0) continue;
+      bool owners = owned[g] != 0;
+      for (int v = 0; v < 64; ++v) { const int32_t r = EB.grp_count[(size_t)g * 64 + v], c = count[(size_t)g * 64 + v]; const int32_t x = (r >= 0 || c > 0) ? (r > 0 ? r : 0) + c : -1; count[(size_t)g * 64 + v] = x; if (x > 0) owners = true; }
+      if (g >= NT && !owners) exists[g] = 0;
+    }
+  }
+  std::vector<uint64_t> own(GW, 0); if (!sb.group_lists) for (uint32_t i = 0; i < ncand; ++i) for (uint32_t w = 0; w < GW; ++w) own[w] |= sb.t_node_own[(size_t)cand[i] * GW + w];
+  for (uint32_t g = 0; g < G && !sb.group_lists; ++g) {
     const bool ownbit = (own[g >> 6] >> (g & 63u)) & 1ull;
     active[g] = g >= NT ? 1 : (ownbit ? 1 : 0);
     const int32_t hs = EB.grp_hslot[g];

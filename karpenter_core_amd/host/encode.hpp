@@ -116,12 +116,13 @@ uint64_t snapshot_fingerprint(const SnapshotBase& sb);      // FNV-1a over the f
 std::unique_ptr<Encoded> encode_whatif(const SnapshotBase& sb, const uint32_t* cand, uint32_t ncand, uint32_t flags);
 // What deriving what-ifs on the device (include/ksolve.h ks_whatifs_open) needs of a snapshot's flattening.  `eligible`: its what-ifs differ in
 // nothing but the pod subset, the removed nodes, remainingResources and -- derived on the device from per-node tables -- which topology groups exist from
-// the start and what countDomains finds (at most 1024 groups; volume limits / claims only under KSH_DERIVE_VOLUMES); otherwise `why` says what stands in the way and the what-ifs are flattened one by one.
+// the start and what countDomains finds (at most 1024 groups unless KSH_DERIVE_GROUP_LISTS holds them as lists per node; volume limits / claims only under KSH_DERIVE_VOLUMES); otherwise `why` says what stands in the way and the what-ifs are flattened one by one.
 struct DeltaInputs {
   std::shared_ptr<const Encoded> base; uint32_t n_nodes = 0; const int32_t* node_row = nullptr; const std::vector<std::vector<uint32_t>>* by_node = nullptr;
   const uint32_t* pod_rank = nullptr; const int64_t* node_cap = nullptr /* [n_nodes][R] capacity of a node whose provisioner has limits, masked to the limited resources */;
   const int32_t* node_tmpl = nullptr /* template with limits the node counts against, or -1 */; bool eligible = false; std::string why;
   const ks_whatif_topo* topo = nullptr;      // snapshots with topology groups: the per-node tables a what-if's groups are derived from
+  const ks_whatif_topo_lists* lists = nullptr;      // ... or, under KSH_DERIVE_GROUP_LISTS, the per-node lists (any number of groups; `topo` is then null)
   bool volumes = false;                      // KSH_DERIVE_VOLUMES over a snapshot with volume drivers: every what-if carries its own volume state (ks_whatifs_open_ex)
 };
 DeltaInputs delta_inputs(const SnapshotBase& sb);

@@ -30,6 +30,7 @@ _LIBS = None
 KS_OK, KS_ERR_INVALID, KS_ERR_UNSUPPORTED, KS_ERR_DEVICE, KS_ERR_CAPACITY = 0, -1, -2, -3, -4
 KS_FLAG_SIMULATION, KS_FLAG_STATS, KS_FLAG_NO_RR, KS_FLAG_ONE_WAVE, KS_FLAG_NO_LEAN = 1, 2, 4, 8, 16
 KSH_DERIVE_VOLUMES = 1 << 16      # kshost.h: derive what-ifs over snapshots with CSI volume limits / claims too (opt-in)
+KSH_DERIVE_GROUP_LISTS = 1 << 18  # kshost.h: hold a derived what-if's per-node topology facts as lists per node -- any number of topology groups (opt-in)
 KSH_ACTIVE_RESOURCES = 1 << 17    # kshost.h: flatten over the resource names the problem requests or limits, not over all a catalogue lists (opt-in)
 KSH_APPLY_TRACK_CLUSTER_PODS = 1  # kshost.h: ksh_env_apply_block mirrors BIND / UNBIND into the cluster pods whatever the snapshot started with
 
@@ -68,6 +69,11 @@ def libs():
         kh.ksh_grid_install.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
         kh.ksh_debug_grid.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
         kh.ksh_debug_pod_classes.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        kh.ksh_debug_whatif_topology.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        kh.ksh_whatifs_arena_bytes.argtypes = [ctypes.c_void_p]
+        kh.ksh_whatifs_arena_bytes.restype = ctypes.c_uint64
+        kh.ksh_whatifs_upload_bytes.argtypes = [ctypes.c_void_p]
+        kh.ksh_whatifs_upload_bytes.restype = ctypes.c_uint64
         kh.ksh_debug_classes.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
         kh.ksh_price_filter.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint32),
                                         ctypes.POINTER(ctypes.c_uint64), ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]
@@ -130,7 +136,7 @@ class PlanTouch(ctypes.Structure):
 
 class PlanTopo(ctypes.Structure):
     _fields_ = [("PD", ctypes.c_uint64), ("g", ctypes.c_int32), ("maxskew", ctypes.c_int32), ("type", ctypes.c_uint8), ("self", ctypes.c_uint8), ("pod_has", ctypes.c_uint8),
-                ("hslot", ctypes.c_uint8), ("pad", ctypes.c_uint32)]
+                ("hslot", ctypes.c_uint8), ("hrow", ctypes.c_uint32)]
 
 
 class PlanRec(ctypes.Structure):
@@ -341,6 +347,26 @@ class FlatProblem:
             raise KSolveError(rc, kh.ksh_last_error().decode())
         return arr
 
+    def whatif_topology(self):
+        """ksh_debug_whatif_topology: what the derivation left this derived what-if with, as numpy arrays (active uint8 [G], count int32 [G, 64], extra int32 [GH]).
+        Read-only, nothing is launched; raises KS_ERR_INVALID for a handle that is no derived what-if over a snapshot with topology groups."""
+        import numpy as np
+        kh = libs()[1]
+        G, GH = self.dims["G"], self.dims["GH"]
+        active, count, extra = np.zeros(max(1, G), dtype=np.uint8), np.zeros((max(1, G), 64), dtype=np.int32), np.zeros(max(1, GH), dtype=np.int32)
+        rc = kh.ksh_debug_whatif_topology(self._h, active.ctypes.data, count.ctypes.data, extra.ctypes.data)
+        if rc != KS_OK:
+            raise KSolveError(rc, kh.ksh_last_error().decode())
+        return active[:G], count[:G], extra[:GH]
+
+    def arena_bytes(self) -> int:
+        """ksh_whatifs_arena_bytes: device bytes of the arena a derived what-if's batch shares; 0 for a handle flattened on the host."""
+        return int(libs()[1].ksh_whatifs_arena_bytes(self._h))
+
+    def upload_bytes(self) -> int:
+        """ksh_whatifs_upload_bytes: the bytes the open of a derived what-if's batch copied to the device; 0 for a handle flattened on the host."""
+        return int(libs()[1].ksh_whatifs_upload_bytes(self._h))
+
     def pod_classes(self):
         """ksh_debug_pod_classes: numpy uint32 [P], the pod class (grid row c) of every pod as submitted, in the caller's pod order."""
         import numpy as np
@@ -501,7 +527,8 @@ class ParsedProblem:
             raise KSolveError(rc, kh.ksh_last_error().decode())
         return out[:n_pods.value], int(n_nodes.value)
 
-    def snapshot_fingerprint(self, pod_node: Optional[Sequence[int]] = None, cold: bool = False, volumes: bool = False, active_resources: bool = False) -> int:
+    def snapshot_fingerprint(self, pod_node: Optional[Sequence[int]] = None, cold: bool = False, volumes: bool = False, active_resources: bool = False,
+                             group_lists: bool = False) -> int:
         """Hash of the snapshot's flattening (flat problem + the tables the device derivation reads); `cold`: of one made from scratch (tests: a flattening
         continued after `apply` must equal it); `volumes`: of the flattening derived what-ifs with volumes use (KSH_DERIVE_VOLUMES);
         `active_resources`: of the flattening over the active resource names (KSH_ACTIVE_RESOURCES)."""
@@ -510,7 +537,7 @@ class ParsedProblem:
         kh.ksh_snapshot_fingerprint.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64)]
         pn = None if pod_node is None else np.ascontiguousarray(np.asarray(pod_node, dtype=np.int32))
         out = ctypes.c_uint64()
-        rc = kh.ksh_snapshot_fingerprint(self._p, None if pn is None or pn.size == 0 else pn.ctypes.data, (KSH_DERIVE_VOLUMES if volumes else 0) | (KSH_ACTIVE_RESOURCES if active_resources else 0), 1 if cold else 0, ctypes.byref(out))
+        rc = kh.ksh_snapshot_fingerprint(self._p, None if pn is None or pn.size == 0 else pn.ctypes.data, (KSH_DERIVE_VOLUMES if volumes else 0) | (KSH_ACTIVE_RESOURCES if active_resources else 0) | (KSH_DERIVE_GROUP_LISTS if group_lists else 0), 1 if cold else 0, ctypes.byref(out))
         if rc != KS_OK:
             raise KSolveError(rc, kh.ksh_last_error().decode())
         return int(out.value)
@@ -619,7 +646,7 @@ def solve_from_batch(env: ParsedProblem, batch: PodBatch, device: int = 0, stats
 
 
 def open_whatifs(snapshot, pod_node: Sequence[int], candidate_sets: Sequence[Sequence[int]], threads: int = 0, stats: bool = False, derive=None, device: int = 0,
-                 volumes: bool = False, active_resources: bool = False) -> List[FlatProblem]:
+                 volumes: bool = False, active_resources: bool = False, group_lists: bool = False) -> List[FlatProblem]:
     """Flatten N consolidation what-ifs over one cluster snapshot natively (simulateScheduling, deprovisioning/helpers.go:42-115):
     `snapshot` (a `Problem`, or a `ParsedProblem` already held as objects) lists every state node and, as its pod batch, every bound pod
     (full spec); pod_node[i] = node index of pod i.  What-if w removes candidate_sets[w] from the state nodes and makes their pods
@@ -644,10 +671,11 @@ def open_whatifs(snapshot, pod_node: Sequence[int], candidate_sets: Sequence[Seq
     # derive: None = derive the what-ifs on the device when the snapshot allows it (a ParsedProblem without topology terms / volume limits), else flatten
     # them one by one on the host; True = derive or raise; False = always flatten on the host.  Derived what-ifs are resident on `device` at once.
     # volumes: opt in to deriving snapshots with CSI volume limits / claims too (kshost.h KSH_DERIVE_VOLUMES); the host route is the same either way.
+    # group_lists: opt in to the per-node lists behind a derived what-if's topology (kshost.h KSH_DERIVE_GROUP_LISTS): more than 1024 topology groups are derived too.
     if derive is not False and not stats and n:
         if not isinstance(snapshot, ParsedProblem):
             snapshot = ParsedProblem(snapshot)       # (the handles keep what they need of it alive)
-        rc = kh.ksh_open_whatifs_derived(snapshot._p, (KSH_DERIVE_VOLUMES if volumes else 0) | act, n, c_off, c_cand, c_pn, device, hs)
+        rc = kh.ksh_open_whatifs_derived(snapshot._p, (KSH_DERIVE_VOLUMES if volumes else 0) | (KSH_DERIVE_GROUP_LISTS if group_lists else 0) | act, n, c_off, c_cand, c_pn, device, hs)
         if rc == KS_OK:
             return [FlatProblem(None, _handle=ctypes.c_void_p(hs[i])) for i in range(n)]
         if derive is True or rc not in (KS_ERR_UNSUPPORTED, KS_ERR_DEVICE):
@@ -664,7 +692,8 @@ def open_whatifs(snapshot, pod_node: Sequence[int], candidate_sets: Sequence[Seq
     return [FlatProblem(None, _handle=ctypes.c_void_p(hs[i])) for i in range(n)]
 
 
-def check_whatif_derivation(snapshot: "ParsedProblem", pod_node: Sequence[int], candidates: Sequence[int], volumes: bool = False, active_resources: bool = False) -> None:
+def check_whatif_derivation(snapshot: "ParsedProblem", pod_node: Sequence[int], candidates: Sequence[int], volumes: bool = False, active_resources: bool = False,
+                            group_lists: bool = False) -> None:
     """Diagnostic, no GPU needed (kshost.h `ksh_check_whatif_derivation`): what the device would derive for this candidate set -- group activity, domain
     counts, hostname rows; with `volumes`, the volume state of every node that stays and the volume test of every pod of the batch on it -- restated on
     the host and compared with the what-if flattened by itself.  Raises KSolveError with the first difference."""
@@ -673,7 +702,7 @@ def check_whatif_derivation(snapshot: "ParsedProblem", pod_node: Sequence[int], 
     cand = np.ascontiguousarray(np.asarray(list(candidates) or [0], dtype=np.uint32))
     pn = None if pod_node is None else (np.ascontiguousarray(np.asarray(pod_node, dtype=np.int32)) if len(pod_node) else np.zeros(1, dtype=np.int32))
     kh.ksh_check_whatif_derivation.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint32, ctypes.POINTER(ctypes.c_int32)]
-    rc = kh.ksh_check_whatif_derivation(snapshot._p, (KSH_DERIVE_VOLUMES if volumes else 0) | (KSH_ACTIVE_RESOURCES if active_resources else 0), cand.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), len(candidates), None if pn is None else pn.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)))
+    rc = kh.ksh_check_whatif_derivation(snapshot._p, (KSH_DERIVE_VOLUMES if volumes else 0) | (KSH_ACTIVE_RESOURCES if active_resources else 0) | (KSH_DERIVE_GROUP_LISTS if group_lists else 0), cand.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), len(candidates), None if pn is None else pn.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)))
     if rc != KS_OK:
         raise KSolveError(rc, kh.ksh_last_error().decode())
 
