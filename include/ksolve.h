@@ -797,6 +797,12 @@ int ks_probe_has(const ks_req1* a, const int32_t* value_int, uint32_t nvalues, i
 const char* ks_last_error(void); /* thread-local message of the last non-OK return */
 const char* ks_version(void);
 uint32_t ks_rr_run_max(void);       /* queue entries one RUN round of ks_pack_rr takes at most (the library's RR_RUN_MAX: a build-time choice, a multiple of 64) */
+/* The cycle probes the library was compiled with (0: none -- the product).  ks_result.stats[12], [13], [21] and [25..31] hold another set of counters under each
+ * (ks_pack_rr.inc, the end of ks_pack_rr): a profiling tool asks before it gives them names. */
+#define KS_PROBE_BUILD_PROBES 1u    /* -DKS_PROBES: the phases of a normal round */
+#define KS_PROBE_BUILD_WIN 2u       /* -DKS_PROBES_WIN: the head window's loop */
+#define KS_PROBE_BUILD_RUN 4u       /* -DKS_PROBES_RUN: worker 1's phases of a RUN round's step */
+uint32_t ks_probe_build(void);
 
 #ifdef __cplusplus
 }

@@ -264,7 +264,7 @@ struct alignas(16) RRLds {
   DevProb P; DevState S; FastTabs ft; LeaderShared ls; WaveShared sh; RRNrc nt;
   RRCtl ctl[2];                             // the orders of a round (by round parity)
   u64 win[2][RR_B];                         // per pod of the round: min over the workers of key << 32 | ambiguous << 31 | nrc << 16 | node
-  u64 stepk[2][RR_NWK][8];                  // a run's step: per worker wave its smallest accepting keys (key << 32 | nrc << 16 | node), by step parity
+  u64 stepk[2][RR_NWK][8];                  // a run's step: per worker wave its accepting keys of one count bucket, at most eight (key << 32 | "the wave holds more" << 31 | nrc << 16 | node; all ones: none), by step parity
   u64 runitem[2][RR_RUN_MAX];               // ... and their hostname-keyed items (RR_ITEM_LIM), apart: every wave reads them at every step, lane = pod
   RRRunPod runtab[2][RR_RUN_MAX];           // a run's pods (by round parity: the workers still commit a round's last step while the leader forms the next round)
   u32 mrg_out[64], mrg_k[4];                // ... and what the leader's out-of-line copy hands back: the winners' payloads, kind | stop node | stop nrc
@@ -478,8 +478,13 @@ __device__ __forceinline__ u32 rr_run_group(const u64* items, const int lane, co
 // commits do), at most `rem`.  An existing node keeps its place when it takes a pod: a step that starts with one ends with it.  Lane j ends up holding
 // winner j (o_key / o_pay = nrc << 16 | node); o_rank: lane l's published key (wave l / 8, its l % 8-th) is the o_rank-th smallest -- a winner iff o_rank < the return value.
 // Returns the number of winners; kind = why the pod AFTER them stops the run (0: nothing does).
-// Round 5: by RANK -- every lane counts the published keys below its own (56 compares against LDS broadcasts), the keys go to their ranks through the wave's scratch, and the
-// stopping rules are ballots over the sorted lanes -- instead of one wave minimum per winner (~350 cycles each, 21 winners a step on config #3).  `scratch`: 64 words of this wave's own.
+// What a wave publishes (rr_worker): up to eight entries key << 32 | flag << 31 | nrc << 16 | node, the rest all ones, in NO particular order among themselves.  A wave
+// that holds at most eight accepting keys of its bucket publishes every one (each lane writes its own, at the place the ballots give it); one that holds more publishes
+// its eight smallest and sets the FLAG on the eighth, the largest of them: behind that key the wave may hold keys smaller than what the other waves have left, so the step
+// ends with it.  A wave whose smallest key is an existing node's publishes that one alone.  Every prefix of the merged order is exact; the flag only ends it early.
+// By RANK (round 5) -- every lane counts the published keys below its own (56 compares against LDS broadcasts), the keys go to their ranks through the wave's scratch, and
+// the stopping rules are ballots over the sorted lanes: about 2 450 cycles a step for a worker wave on config #3 (2 125 steps of 26.8 pods; profiles/r23_run_steps.txt), beside
+// about 2 150 to publish, 1 750 at the barrier and 2 000 to commit and evaluate again.  `scratch`: 64 words of this wave's own.
 __device__ __forceinline__ u32 rr_step_merge(const u64 (*stepk)[8], u64* const scratch, const int lane, const u32 rem, const u32 nE, const u64 vfy, u32& o_key, u32& o_pay, u32& kind, u32& stop_node, u32& stop_nrc, u32& o_rank) {
   const u64 v = (u32)lane < RR_NWK * 8u ? stepk[lane >> 3][lane & 7] : ~0ull;
   const u32 key = (u32)(v >> 32);
@@ -493,7 +498,7 @@ __device__ __forceinline__ u32 rr_step_merge(const u64 (*stepk)[8], u64* const s
   const u32 nvalid = (u32)__builtin_popcountll(ballot64(valid));
   if (rem == 0) return 0;
   if (nvalid == 0) { kind = 2; return 0; }
-  if (valid) scratch[rank] = (v & ~(1ull << 31)) | (((u32)lane & 7u) == 7u ? (1ull << 31) : 0ull);      // (bit 31: the last key its wave published -- the wave may hold more in this bucket, smaller than what the others have left)
+  if (valid) scratch[rank] = v;      // (bit 31, set by the wave that published it: its eighth and largest key, and the wave holds more in this bucket -- smaller, maybe, than what the others have left)
   LSYNC();
   const bool in = (u32)lane < nvalid;
   const u64 sv = in ? scratch[lane] : ~0ull;
@@ -1016,8 +1021,10 @@ __device__ __attribute__((noinline)) void rr_worker(const u32 wv, const int lane
       }
     }
     if (run) {
-      // ---- a RUN: pods of one evaluation class (no topology counters read).  They are evaluated once; per step every wave publishes its smallest accepting keys, and
-      // after ONE barrier everyone knows which nodes the next pods go to (rr_step_merge); the lanes that hold them commit side by side, and only they evaluate again. ----
+      // ---- a RUN: pods of one evaluation class (no topology counters read).  They are evaluated once; per step every wave publishes its accepting keys of ONE count
+      // bucket (all of them, lane by lane, if it holds at most eight: one wave minimum names the bucket, ballots do the rest; else its eight smallest), and after ONE
+      // barrier everyone knows which nodes the next pods go to (rr_step_merge); the lanes that hold them commit side by side, slot by slot, and only those slots are
+      // evaluated again. ----
       const RREntry& E = L.ring[pos0 & (RR_RING - 1u)];
       const u32 mw = E.m[lane & 31];
       do_eval(E, mw, 0u, true);              // (the shared half only: requests, requirements)
@@ -1052,28 +1059,63 @@ __device__ __attribute__((noinline)) void rr_worker(const u32 wv, const int lane
         u32 kk[RR_NPL];
 #pragma unroll
         for (int i = 0; i < RR_NPL; ++i) kk[i] = n_key[i] | (u32)(((i32)((okm >> i) & 1u)) - 1);
-        u32 myk = 0xFFFFFFFFu, mypay = 0, b0 = 0;
         RRT(7);
-        for (u32 r = 0; r < 8u && r < rem; ++r) {
-          u32 lb = kk[0];
+        u32 lb = kk[0];
 #pragma unroll
-          for (int i = 1; i < RR_NPL; ++i) lb = min(lb, kk[i]);
-          const u32 km = wave_min_u32(lb);
-          if (km == 0xFFFFFFFFu) break;
-          if (r == 0) b0 = km >> 22; else if ((km >> 22) != b0) break;
-          const int wl = __builtin_ctzll(ballot64(lb == km));
-          const u32 ws = km & 7u;
-          u32 bm = 0;
+        for (int i = 1; i < RR_NPL; ++i) lb = min(lb, kk[i]);
+        u32 km = wave_min_u32(lb);             // ONE wave minimum names the bucket
+        const u32 b0 = km >> 22;
+        u32 pubw = 0, pubm = 0;                // what THIS lane publishes: its slots (bits 0..7) and, three bits a slot from bit 8 on, their places among the wave's entries | pubm: the slots any lane of the wave publishes from
+        bool one_by_one = true;
+        if (km != 0xFFFFFFFFu && b0 != 0u) {
+          // new nodes lead (an existing node's key has count field 0, a new node's is >= 1): which lanes hold an accepting key of the bucket, slot by slot
+          u64 mb[RR_NPL]; u32 total = 0;
 #pragma unroll
-          for (int i = 0; i < RR_NPL; ++i) if ((u32)i == ws) bm = n_meta[i];
-          const u32 nd = RR_NODE_AT(ws, wk_i, wl);
-          const u32 bmu = RL(bm, wl);
-          if ((u32)lane == r) { myk = km; mypay = ((bmu & 0xFFu) << 16) | nd; }
+          for (int i = 0; i < RR_NPL; ++i) { mb[i] = ballot64(kk[i] != 0xFFFFFFFFu && (kk[i] >> 22) == b0); total += (u32)__builtin_popcountll(mb[i]); }
+          if (total <= 8u) {
+            // ... at most eight: every one is published by the lane that holds it, at the place the ballots give it (slot by slot, lane by lane -- NOT in key
+            // order: the merge ranks by counting and does not mind).  Nothing here waits for the key before.
+            one_by_one = false;
+            const u64 below = (1ull << lane) - 1ull;
+            u32 base = 0;
 #pragma unroll
-          for (int i = 0; i < RR_NPL; ++i) if ((u32)i == ws) kk[i] = lane == wl ? 0xFFFFFFFFu : kk[i];      // (the key names its slot: one register to touch)
-          if (nd < nE) break;
+            for (int i = 0; i < RR_NPL; ++i) {
+              if ((mb[i] >> lane) & 1ull) {
+                const u32 pl = base + (u32)__builtin_popcountll(mb[i] & below);
+                L.stepk[sp][wk_i][pl] = ((u64)kk[i] << 32) | (u64)(((n_meta[i] & 0xFFu) << 16) | RR_NODE_AT((u32)i, wk_i, lane));
+                pubw |= (1u << i) | (pl << (8 + 3 * i));
+              }
+              base += (u32)__builtin_popcountll(mb[i]); pubm |= mb[i] ? 1u << i : 0u;
+            }
+            if (lane < 8 && (u32)lane >= total) L.stepk[sp][wk_i][lane] = ~0ull;
+          }
         }
-        if (lane < 8) L.stepk[sp][wk_i][lane] = ((u64)myk << 32) | mypay;
+        if (one_by_one) {
+          // an existing node leads (it alone is published: a step that starts with an existing node ends with it), or the wave holds more than eight of the bucket:
+          // its eight smallest, one wave minimum each, the last of them flagged (bit 31 of the low word: the wave holds more in this bucket)
+          u32 myk = 0xFFFFFFFFu, mypay = 0;
+          if (km != 0xFFFFFFFFu) for (u32 r = 0;;) {
+            const int wl = __builtin_ctzll(ballot64(lb == km));
+            const u32 ws = km & 7u;
+            u32 bm = 0;
+#pragma unroll
+            for (int i = 0; i < RR_NPL; ++i) if ((u32)i == ws) bm = n_meta[i];
+            const u32 nd = RR_NODE_AT(ws, wk_i, wl);
+            const u32 bmu = RL(bm, wl);
+            if ((u32)lane == r) { myk = km; mypay = ((bmu & 0xFFu) << 16) | nd | (r == 7u ? 1u << 31 : 0u); }
+            if (lane == wl) pubw |= (1u << ws) | (r << (8u + 3u * ws));
+            pubm |= 1u << ws;
+            if (b0 == 0u || ++r >= 8u || r >= rem) break;
+#pragma unroll
+            for (int i = 0; i < RR_NPL; ++i) if ((u32)i == ws) kk[i] = lane == wl ? 0xFFFFFFFFu : kk[i];      // (the key names its slot: one register to touch)
+            lb = kk[0];
+#pragma unroll
+            for (int i = 1; i < RR_NPL; ++i) lb = min(lb, kk[i]);
+            km = wave_min_u32(lb);
+            if (km == 0xFFFFFFFFu || (km >> 22) != b0) break;
+          }
+          if (lane < 8) L.stepk[sp][wk_i][lane] = ((u64)myk << 32) | mypay;
+        }
         RRT(1);
         __syncthreads();
         RRT(2);
@@ -1081,31 +1123,31 @@ __device__ __attribute__((noinline)) void rr_worker(const u32 wv, const int lane
         u32 mrank;
         const u32 n_step = rr_step_merge(L.stepk[sp], L.mrg[wv], lane, rem, nE, rvfy, wkey, wpay, kind, snode, snrc, mrank);
         RRT(3);
-        // ---- COMMIT the step's pods, each by the lane that holds its node ----
+        // ---- COMMIT the step's pods, each by the lane that holds its node: slot by slot (one, as a rule: the nodes of a bucket were opened one after the other),
+        // all the winners a slot holds side by side.  A lane knows the place of what it published, the place names the entry, the merge has ranked the entry. ----
         u32 ts = 0;
-        for (u32 r = 0; r < 8u; ++r) {         // (this wave's own winners: its r-th published key is the step's j-th pod)
-          const u32 j = RL(mrank, (int)(wk_i * 8u + r));
-          if (j >= n_step) break;
-          const u32 pay = UF((u32)L.stepk[sp][wk_i][r]), node = pay & 0xFFFFu, nrc = (pay >> 16) & 0xFFu;
-          const u32 oslot = RR_NODE_SLOT(node), olane = RR_NODE_LANE(node);
-          const u32 nrc_new = ((rchg >> nrc) & 1ull) ? ((RL(mw, 8 + (int)(nrc >> 2)) >> (8u * (nrc & 3u))) & 0xFFu) : nrc;
-          const bool mine = (u32)lane == olane;
-          const u32 rpw = lane < 6 ? ((const u32*)&L.runtab[par][done + j])[lane] : 0u;      // the pod's record at once (lane i: word i -- pod, class, nh, hs[12])
-          const u32 pseq = seq0 + done + j, nh = RL(rpw, 2), pd = RL(rpw, 0);
-          if (mine) { tb.pod_node[pd] = (i32)node; tb.pod_seq[pd] = (i32)pseq; G_pod_reason[pd] = 0;
-          }
+        for (u32 sb = pubm; sb; sb &= sb - 1u) {
+          const u32 oslot = (u32)__builtin_ctz(sb);
+          const u32 j = __shfl(mrank, (int)(wk_i * 8u + ((pubw >> (8u + 3u * oslot)) & 7u)));      // (the step's j-th pod, if j < n_step)
+          const bool mine = ((pubw >> oslot) & 1u) != 0u && j < n_step;
+          if (!ballot64(mine)) continue;
           ts |= 1u << oslot;
+          const u32* const rpw = (const u32*)&L.runtab[par][done + (mine ? j : 0u)];      // the pod's record (pod, class, nh, hs[12]), read by the lane that commits it
+          const u32 pseq = seq0 + done + j, nh = mine ? rpw[2] : 0u;
+          if (mine) { const u32 pd = rpw[0]; tb.pod_node[pd] = (i32)RR_NODE_AT(oslot, wk_i, (u32)lane); tb.pod_seq[pd] = (i32)pseq; G_pod_reason[pd] = 0; }
 #define RR_RCOMMIT_SLOT(i) if (oslot == (i)) { \
-            i64 d0 = rq0, d1 = rq1, d2 = rq2, d3 = rq3; \
-            if (node >= nE && nrc_new != nrc) { d0 -= nt.cap[0][nrc_new] - nt.cap[0][nrc]; d1 -= nt.cap[1][nrc_new] - nt.cap[1][nrc]; d2 -= nt.cap[2][nrc_new] - nt.cap[2][nrc]; d3 -= nt.cap[3][nrc_new] - nt.cap[3][nrc]; } \
+            const u32 nrc = n_meta[i] & 0xFFu, chw = rchg ? __shfl(mw, (int)(8u + ((nrc >> 2) & 15u))) : 0u;      /* (the child byte of the run's answers, if any nrc has one) */ \
             if (mine) { \
-              n_room[i][0] -= d0; n_room[i][1] -= d1; n_room[i][2] -= d2; n_room[i][3] -= d3; \
-              if (node >= nE) n_key[i] = (((n_key[i] >> 22) + 1u) << 22) | ((RR_SEQMAX - pseq) << 3) | (n_key[i] & 7u); \
-              n_meta[i] = nrc_new | ((((n_meta[i] >> 8) | rprm) & 0xFFu) << 8); } \
-            for (u32 t = 0; t < nh; ++t) {       /* Topology.Record on the hostname-keyed groups that count the pod: this node's own counters */ \
-              const u32 hs = (RL(rpw, 3 + (int)(t >> 2)) >> (8u * (t & 3u))) & 0xFFu, sh8 = 8u * (hs & 3u); \
-              switch (hs >> 2) { RR_HREC_WORD(i, 0) RR_HREC_WORD(i, 1) RR_HREC_WORD(i, 2) RR_HREC_WORD(i, 3) RR_HREC_WORD(i, 4) RR_HREC_WORD(i, 5) RR_HREC_WORD(i, 6) RR_HREC_WORD(i, 7) default: break; } \
-            } }
+              const u32 nrc_new = ((rchg >> nrc) & 1ull) ? ((chw >> (8u * (nrc & 3u))) & 0xFFu) : nrc; \
+              n_room[i][0] -= rq0; n_room[i][1] -= rq1; n_room[i][2] -= rq2; n_room[i][3] -= rq3; \
+              if (b0 != 0u) { \
+                n_key[i] = (((n_key[i] >> 22) + 1u) << 22) | ((RR_SEQMAX - pseq) << 3) | (n_key[i] & 7u); \
+                if (nrc_new != nrc) { n_room[i][0] += nt.cap[0][nrc_new] - nt.cap[0][nrc]; n_room[i][1] += nt.cap[1][nrc_new] - nt.cap[1][nrc]; n_room[i][2] += nt.cap[2][nrc_new] - nt.cap[2][nrc]; n_room[i][3] += nt.cap[3][nrc_new] - nt.cap[3][nrc]; } } \
+              n_meta[i] = nrc_new | ((((n_meta[i] >> 8) | rprm) & 0xFFu) << 8); \
+              for (u32 t = 0; t < nh; ++t) {       /* Topology.Record on the hostname-keyed groups that count the pod: this node's own counters */ \
+                const u32 hs = ((const u8*)rpw)[12u + t], sh8 = 8u * (hs & 3u); \
+                switch (hs >> 2) { RR_HREC_WORD(i, 0) RR_HREC_WORD(i, 1) RR_HREC_WORD(i, 2) RR_HREC_WORD(i, 3) RR_HREC_WORD(i, 4) RR_HREC_WORD(i, 5) RR_HREC_WORD(i, 6) RR_HREC_WORD(i, 7) default: break; } \
+              } } }
           RR_RCOMMIT_SLOT(0) RR_RCOMMIT_SLOT(1) RR_RCOMMIT_SLOT(2) RR_RCOMMIT_SLOT(3) RR_RCOMMIT_SLOT(4) RR_RCOMMIT_SLOT(5) RR_RCOMMIT_SLOT(6) RR_RCOMMIT_SLOT(7)
         }
         RR_HZ_FLUSH()

@@ -4792,3 +4792,16 @@ extern "C" int ks_debug_classes(ks_dev_problem* d, void* briefs_out, void* plans
 extern "C" const char* ks_last_error(void) { return g_err.c_str(); }
 extern "C" const char* ks_version(void) { return "ksolve 0.1.0 (gfx950)"; }
 extern "C" uint32_t ks_rr_run_max(void) { return RR_RUN_MAX; }
+extern "C" uint32_t ks_probe_build(void) {      // which cycle probes ks_pack_rr was built with: what the statistics slots 12 / 13 / 21 / 25..31 hold depends on it
+  uint32_t f = 0;
+#ifdef KS_PROBES
+  f |= KS_PROBE_BUILD_PROBES;
+#endif
+#ifdef KS_PROBES_WIN
+  f |= KS_PROBE_BUILD_WIN;
+#endif
+#ifdef KS_PROBES_RUN
+  f |= KS_PROBE_BUILD_RUN;
+#endif
+  return f;
+}
