@@ -273,7 +273,8 @@ int ksh_single_node_option(void* parsed_snapshot, uint32_t flags, const uint32_t
  * shards them itself: ks_consolidation_commands_host (ksolve.h) over handles, the per-what-if inputs built by the caller. */
 int ksh_command_rows(void** handles, uint32_t n, const uint64_t* ids, const ks_command_inputs* in, uint32_t words, uint64_t* out_rows, double* ms /* [2] or NULL */);
 /* Turning a row into strings without a handle: what 0 = requirement key a (KS_CMD_MASK + a), 2 = resource a (KS_REP_NODE_REQ + a), 1 = value b of key a (bit b of that mask; a key encoded over value
- * classes names one member per class, as ksh_name does), 3 = state node a (a candidate index), 4 = instance type a (bit a of the option masks).  Keys and values
+ * classes names one member per class, as ksh_name does), 3 = state node a (a candidate index), 4 = instance type a (bit a of the option masks), 5 / 6 = value a of the
+ * zone / capacity-type universe (the ids ksh_provision's launch pick gives).  Keys and values
  * are the snapshot's flattening's: available once a what-if call flattened it.  NULL when out of range; the strings live as long as the snapshot is neither
  * changed (ksh_env_apply*) nor freed.  A requirement reads: present bit k of row[KS_CMD_PRESENT], complement bit k of its high half, values = the mask's bits,
  * greaterThan / lessThan = the low / high half of row[KS_CMD_BOUNDS + k] unless KS_NO_BOUND_GT / KS_NO_BOUND_LT.  row[KS_CMD_IT_STATE] != 0: the node also carries
@@ -481,6 +482,54 @@ uint64_t ksh_whatifs_simulated(void);
  * over handles, flags[i] = KS_REP_F_* built by the caller. */
 int ksh_replacement_rows(void** handles, uint32_t n, const uint64_t* ids, const uint32_t* flags, uint32_t words, uint64_t* out_heads, uint64_t* out_nodes, uint64_t cap_nodes,
                          uint64_t* out_total_nodes, double* ms /* [2] or NULL */);
+
+/* ---- provisioning over the snapshot kept by events (provisioning/provisioner.go:106-165 Provisioner.Reconcile): the OTHER reader of state.Cluster, through the same
+ * snapshot as the deprovisioner's methods.  Reconcile's Solve (:117-150) takes the state nodes that are not marked for deletion; its pods are GetPendingPods plus the
+ * pods of the nodes that are marked -- simulateScheduling (deprovisioning/helpers.go:48-93) with an empty candidate set.  ksh_provision builds that ONE what-if: the
+ * nodes of `deleting` leave with their pods as the batch, under ksh_consolidation_commands' convention -- the carrier of the pending pods (ONE node of the snapshot
+ * that no provisioner owns; pending pods are bound to it, BIND events keep it current) first, the nodes marked for deletion after it.  `flags`, `pod_node` and the
+ * route are those of every simulating call: derived on the device (KSH_DERIVE_VOLUMES, KSH_ACTIVE_RESOURCES, KSH_DERIVE_GROUP_LISTS honoured), flattened by itself
+ * where the derivation answers KS_ERR_UNSUPPORTED, solved resident either way; out->route says which.  The blocked rule (KS_CMD_F_BLOCKED) is NOT applied: Reconcile
+ * has no check like helpers.go:102-113, and an uninitialised node that stays is an ordinary in-flight ExistingNode.  ksh_whatifs_simulated grows by 1, or by 0 when no
+ * pod is pending and none sits on a deleting node: Reconcile returns before NewScheduler then (:145-147), and so does this -- route KSH_PROVISION_NOTHING, zero rows,
+ * nothing flattened or launched.
+ * What comes back (caller-owned tables, the KS_REP_* capacity convention: totals always, rows only when all fit, nothing at or beyond a capacity touched, KS_OK; a
+ * capacity of 0 with a NULL table is the sizing call -- though total_rows never exceeds the pods bound to `deleting`, and total_machines never exceeds total_rows):
+ *   head      ksolve.h KS_PLC_*: P, n_new, n_unscheduled, flags (KS_PLC_TRUNCATED: cap_rows was too small; KSH_PROVISION_MACHINES_TRUNCATED: cap_machines was)
+ *   rows      [cap_rows][KS_PLC_ROW_WORDS], one per pod of the batch in queue order, named by the snapshot's own stable ids on BOTH routes: the pod's index (the
+ *             order of `pod_node` / ksh_snapshot_bindings), and where it went -- -1, an existing node's SLOT (not its row in a flattening), or node slots + j for
+ *             new node j; head[KS_PLC_N_EXISTING] is the number of node slots.  The relaxation stage is what a shim applies back to pod.Spec, ascending commit
+ *             numbers within a node are Node.Pods (NominatePod, provisioner.go:352-357), the reason word feeds the failed-scheduling events (scheduler.go:135-172).
+ *   machines  [cap_machines][KS_REP_NODE_WORDS(words)], new node j in row j: ksh_replacement_commands' node rows (requirements, InstanceTypeOptions, requests --
+ *             what ToMachine needs), decoded the same way.
+ *   pick_*    [cap_machines] each, or all NULL: ksh_launch_pick per machine -- type index, zone and capacity-type value ids (ksh_snapshot_name what 5 / 6 names
+ *             them), price; written when the machine rows were.
+ * ms[5] as ksh_consolidation_commands ([2] = the kernels behind the three tables, [3] their read-backs).  Refusals as there: KS_ERR_INVALID for an unknown flag bit,
+ * words < ceil(T/64), a deleting node out of range, a NULL table with a capacity, pick arrays given in part.
+ * Limits.  The derived what-if runs ks_pack's single-wave variant: a burst that opens thousands of machines is faster through ksh_solve_from_batch (ks_pack_rr),
+ * which remains the door for such bursts (README has the measured crossover).  And the pending pods live in the snapshot's spare pod room: a full snapshot
+ * refuses the BIND ("spare room ... used up"); ingest it again. */
+#define KSH_PROVISION_NOTHING 0u
+#define KSH_PROVISION_DERIVED 1u
+#define KSH_PROVISION_FLATTENED 2u
+#define KSH_PROVISION_MACHINES_TRUNCATED 2u      /* head[KS_PLC_FLAGS]: the machine table was too small (KS_PLC_TRUNCATED is the row table's) */
+typedef struct ksh_provision_out {
+  uint32_t words;                            /* in: option words of a machine row, >= ceil(T/64) */
+  uint32_t route;                            /* out: KSH_PROVISION_* */
+  uint64_t cap_rows, cap_machines;           /* in */
+  uint64_t total_rows, total_machines;       /* out */
+  uint64_t head[KS_PLC_HEAD_WORDS];          /* out */
+  uint64_t* rows; uint64_t* machines;        /* in: the caller's tables, or NULL with a capacity of 0 */
+  int32_t* pick_type; int32_t* pick_zone; int32_t* pick_ct; double* pick_price;      /* in: [cap_machines] each, or all NULL */
+} ksh_provision_out;
+int ksh_provision(void* parsed_snapshot, uint32_t flags, const int32_t* pod_node /* or NULL after ksh_env_apply */, const uint32_t* deleting, uint32_t n_deleting, int device,
+                  ksh_provision_out* out, double* ms /* [5] or NULL */);
+/* The placement tables of handles whose results are on the device (ksh_solve_batch_resident / ksh_solve / ...; derived or not), ksh_replacement_rows' sibling:
+ * ks_placement_rows_host (ksolve.h KS_PLC_*) over handles -- with it the pods behind a replacement command are readable without text.  out_heads[n][KS_PLC_HEAD_WORDS],
+ * out_rows[cap_rows][KS_PLC_ROW_WORDS], capacity as above.  A what-if over a snapshot -- derived on the device or flattened by itself -- comes back in the snapshot's
+ * ids, as ksh_provision's rows do: snapshot pod index, node slot, node slots + j, head[KS_PLC_N_EXISTING] = node slots.  Any other handle keeps its own: the pod
+ * indices and existing-node indices ksh_result_arrays_get speaks of.  ms[2] (may be NULL): kernels | read-back and renaming. */
+int ksh_placement_rows(void** handles, uint32_t n, const uint64_t* ids, uint64_t* out_heads, uint64_t* out_rows, uint64_t cap_rows, uint64_t* out_total_rows, double* ms /* [2] or NULL */);
 
 /* ---- the snapshot kept current by EVENTS ("cached incremental SoA builder fed from state.Cluster") ----
  * Replaces, for the snapshot consolidation simulates over, what the reference does between two passes of the deprovisioner (deprovisioning/controller.go:64,

@@ -632,6 +632,40 @@ int ks_replacement_commands_dev(ks_dev_problem* const* ds, uint32_t n, const uin
 int ks_replacement_commands_host(ks_dev_problem* const* ds, uint32_t n, const uint64_t* ids, const uint32_t* flags, uint32_t words, uint64_t* out_heads, uint64_t* out_nodes,
                                  uint64_t cap_nodes, uint64_t* out_total_nodes, double* ms);
 
+/* ---- placement rows: the PER-POD half of a result, as fixed-size rows (provisioner.go:352-357 NominatePod over Node.Pods, preferences.go:36-56 the relaxation a shim
+ * applies back to pod.Spec, scheduler.go:135-172 the failed-scheduling events, ExistingNode.Pods).  For problem i, over the result the last ks_solve*_dev of ds[i] left
+ * on the device -- a what-if derived on the device or an ordinary problem alike --, ONE head of KS_PLC_HEAD_WORDS uint64 in d_heads[n][KS_PLC_HEAD_WORDS] and P rows of
+ * KS_PLC_ROW_WORDS uint64 in d_rows[cap_rows][KS_PLC_ROW_WORDS], one per pod of the batch in QUEUE order (queue.go:35 NewQueue's), found through the head's
+ * KS_PLC_ROW_OFF; both caller-owned DEVICE buffers of one width each.  Two launches on ds[0]'s stream (ks_placement_heads: one workgroup, an exclusive scan of P for
+ * row_off, no atomics -- ks_replacement_heads' way; ks_placement_rows: every problem's rows in one launch, lanes stride over a problem's pods); both buffers are
+ * complete when the call returns.  A row is 32 bytes, 32-byte aligned, written by one lane as two aligned 16-byte stores (five 32-bit fields do not fit the widest
+ * store there is); the pod it names is the pod's index in the problem it was flattened from -- for a derived what-if the SNAPSHOT's pod index (pod_gid), not the
+ * position in the batch.  Ascending commit numbers within a node are Node.Pods' order (KS_PLC_SEQ is ks_result.pod_seq).
+ * Capacity, the KS_REP_* convention: *out_total_rows = the sum of P.  Beyond cap_rows every head is still complete; rows are written for the problems whose rows fit
+ * entirely below cap_rows, the others carry KS_PLC_TRUNCATED; nothing at or beyond cap_rows is touched; the call returns KS_OK.  cap_rows = 0 with a NULL table is
+ * the sizing call.
+ * Refusals (KS_ERR_INVALID, nothing launched): a null array, a batch over two devices, a problem that was never solved (or whose last solve failed). */
+#define KS_PLC_HEAD_WORDS 8
+#define KS_PLC_ID 0                  /* ids[i] */
+#define KS_PLC_P 1                   /* pods of the batch = its rows */
+#define KS_PLC_N_NEW 2
+#define KS_PLC_N_UNSCHEDULED 3
+#define KS_PLC_ROW_OFF 4             /* index of its first row in the row table */
+#define KS_PLC_FLAGS 5               /* KS_PLC_TRUNCATED */
+#define KS_PLC_N_EXISTING 6          /* E: KS_PLC_WHERE values below it name existing nodes, E + j new node j */
+                                     /* word 7: reserved, zero */
+#define KS_PLC_TRUNCATED 1u
+/* the row: words of uint64, two 32-bit fields each */
+#define KS_PLC_ROW_WORDS 4
+#define KS_PLC_POD_WHERE 0           /* low: the pod's index | high: (int32) -1 unscheduled, existing node e, or E + new node j */
+#define KS_PLC_STAGE_SEQ 1           /* low: (int32) the relaxation stage the pod ended at | high: (int32) its commit number, -1 if unscheduled */
+#define KS_PLC_REASON_ID 2           /* low: ks_result.pod_reason (KS_WHY_* per machine template) | high: (uint32) ids[i] */
+#define KS_PLC_POSITION 3            /* the pod's position in its problem's queue */
+int ks_placement_rows_dev(ks_dev_problem* const* ds, uint32_t n, const uint64_t* ids, void* d_heads, void* d_rows, uint64_t cap_rows, uint64_t* out_total_rows);
+/* The same with both tables brought to HOST memory; of out_rows only the rows that were written are touched.  ms (may be NULL): [0] inputs up + launches + completion,
+ * [1] the read-back, milliseconds. */
+int ks_placement_rows_host(ks_dev_problem* const* ds, uint32_t n, const uint64_t* ids, uint64_t* out_heads, uint64_t* out_rows, uint64_t cap_rows, uint64_t* out_total_rows, double* ms);
+
 /* ---- consolidation CANDIDATES, selected and ordered on the device (deprovisioning/helpers.go:124-165,275-287 GetPodEvictionCost / disruptionCost /
  * calculateLifetimeRemaining, pdblimits.go:57-70 CanEvictPods, helpers.go:339-366 canBeTerminated / PodsPreventEviction, consolidation.go:83-104 the sort).
  * Flat arrays in, flat arrays out; three kernels (per pod, per node, rank), no host fallback.

@@ -758,3 +758,58 @@ def validate_empty_nodes(snapshot_now: Snapshot, node_names: Sequence[str], info
         return S.validate_empty_nodes([slot[n] for n in node_names if n in slot], got["why"], got["n_node_pods"], nf)
     finally:
         parsed.close()
+
+
+# =====================================================================================================
+# Provisioning over the same snapshot (include/kshost.h ksh_provision): Provisioner.Reconcile's Solve (provisioning/provisioner.go:117-150) is
+# simulateScheduling with no candidate -- `snapshot.pending` plus the pods of `snapshot.deleting` against the nodes that stay.
+# =====================================================================================================
+@dataclass
+class Provisioning:
+    """What `NewScheduler(...).Solve` returns (scheduler.go:96), plus what the launch needs: `nodes` are scheduler.Node with Pods in commit order, `existing`
+    scheduler.ExistingNode for the state nodes that took pods, `unscheduled` [(pod, packed reason word)] in queue order, `stages` {pod uid: relaxation stage > 0} to
+    apply back to pod.Spec, `picks` per new node (instance type name, zone, capacity type, price) or None -- the in-memory provider's launch pick --, `route` how the
+    what-if was made ("derived" / "flattened" / "nothing")."""
+    nodes: list = field(default_factory=list)
+    existing: list = field(default_factory=list)
+    unscheduled: list = field(default_factory=list)
+    stages: dict = field(default_factory=dict)
+    picks: list = field(default_factory=list)
+    route: str = "nothing"
+
+
+def provision_dev(snapshot: Snapshot, info: Optional["CandidateInfo"] = None, device: int = 0, timings: Optional[dict] = None, group_lists: bool = False, volumes: bool = False,
+                  active_resources: bool = False) -> Provisioning:
+    """Provisioner.Reconcile's scheduling pass through `ksh_provision`: one call, one what-if, the rows decoded into the shapes Solve returns.  `info` is accepted so
+    that the call reads like the other `*_dev` passes over a snapshot; provisioning reads nothing of it (no candidate is chosen)."""
+    import ctypes
+    from . import scheduler as S
+    parsed, pod_node, leaving = _command_snapshot(snapshot)
+    try:
+        words = _words(snapshot)
+        got = S.provision(parsed, pod_node, leaving, words, device=device, flags=_lists_flag(group_lists), volumes=volumes, active_resources=active_resources)
+        if timings is not None:
+            timings.update(got["ms"])
+        out = Provisioning(route=got["route"])
+        if got["route"] == "nothing":
+            return out
+        pods = [p for b in snapshot.bound for p in b] + list(snapshot.pending)      # the snapshot's pod order: _command_snapshot binds the pending pods to the carrier, the last node
+        head = got["head"]
+        lists = S.placement_lists([S.decode_placement_row(r, head["n_existing"]) for r in got["rows"]])
+        kh = S.libs()[1]
+        kh.ksh_snapshot_name.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32]
+        kh.ksh_snapshot_name.restype = ctypes.c_char_p
+        for j in range(head["n_new"]):
+            d = S.decode_replacement_node(parsed, got["machines"][j], words)
+            keep = set(d["options"])
+            reqs = {k: RequirementOut(k, v[0], tuple(v[1]), v[2], v[3]) for k, v in d["requirements"].items()}
+            out.nodes.append(S.Node(snapshot.provisioner.name, [pods[i] for i in lists["new"].get(j, [])], [snapshot.instance_types[t] for t in snapshot.provisioner.instance_types if t in keep],
+                                    reqs, d["requests"]))
+            pk = got["picks"][j]
+            out.picks.append(None if pk is None else (snapshot.instance_types[pk[0]].name, kh.ksh_snapshot_name(parsed._p, 5, pk[1], 0).decode(), kh.ksh_snapshot_name(parsed._p, 6, pk[2], 0).decode(), pk[3]))
+        out.existing = [S.ExistingNode(snapshot.nodes[slot], [pods[i] for i in idxs]) for slot, idxs in sorted(lists["existing"].items())]
+        out.unscheduled = [(pods[i], lists["reasons"][i]) for i in lists["unscheduled"]]
+        out.stages = {pods[i].uid: st for i, st in lists["stage"].items() if st > 0}
+        return out
+    finally:
+        parsed.close()

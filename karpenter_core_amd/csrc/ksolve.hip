@@ -2855,6 +2855,7 @@ struct ks_dev_problem {
   int pack_lean = 0;               // the last solve: 1 if that variant was a LEAN one
   int pack_row = -1;               // the last solve: index into pack_rows of the instantiation that ran, -1 if ks_pack_rr took it (or nothing ran)
   int rr_started = 0, rr_code = 0; // the last solve: ks_pack_rr was launched | why it declined (0: it took the Solve; the codes are in ks_pack_rr.inc)
+  bool solved = false;           // the device holds the result of a successful ks_solve*_dev (ks_placement_rows reads it there); false while none has run, and after one that failed
   bool no_multi = false;         // ... over a snapshot with topology groups: the class briefs (round eligibility, certain records) were built for the snapshot's group activity, not this what-if's -- single-wave kernel only
 };
 
@@ -3685,7 +3686,7 @@ extern "C" int ks_solve_batch_dev(ks_dev_problem* const* ds, uint32_t n, ks_resu
     bounds = bounds || ds[i]->any_bounds; lean = lean && ds[i]->lean_ok; any_flags |= q.flags;
     wide = wide || q.R > KS_RES_NARROW;      // (R > 8: never LEAN, so never ks_pack_rr)
     lean8 = lean8 || q.R > 4;                // a LEAN problem with 5..8 resources (ks_problem.lean_r8): the LEAN variants' RM = 8 instantiations; ks_pack_rr stays at 4
-    ds[i]->rr_started = 0; ds[i]->rr_code = 0; ds[i]->pack_rm = 0; ds[i]->pack_lean = 0; ds[i]->pack_row = -1;
+    ds[i]->rr_started = 0; ds[i]->rr_code = 0; ds[i]->pack_rm = 0; ds[i]->pack_lean = 0; ds[i]->pack_row = -1; ds[i]->solved = false;
   }
   // the flag bits of ksolve.h, and the variables that ask the same of the whole process (test hooks)
   if (getenv("KS_NO_LEAN") || (any_flags & KS_FLAG_NO_LEAN)) lean = false;                                // the general variant on a problem the LEAN one would take
@@ -3758,10 +3759,12 @@ extern "C" int ks_solve_batch_dev(ks_dev_problem* const* ds, uint32_t n, ks_resu
   if (!outs) {       // results stay on the device (ks_batch_records_dev / ks_price_filter_dev / ... read them there): only the error words come back
     if (n > 1) { std::vector<u64> meta((size_t)n * 34); HIPCHK(hipMemcpy(meta.data(), d_meta, meta.size() * sizeof(u64), hipMemcpyDeviceToHost)); for (u32 i = 0; i < n && rc == KS_OK; ++i) rc = ks_stats_error(&meta[(size_t)i * 34 + 2]); }
     else { u64 st[32]; HIPCHK(hipMemcpy(st, ds[0]->hs.stats, sizeof st, hipMemcpyDeviceToHost)); rc = ks_stats_error(st); }
+    for (u32 i = 0; i < n; ++i) ds[i]->solved = rc == KS_OK;
     return rc;
   }
   if (n > 1) rc = download_batch(ds, n, dsv, d_meta, outs);
   else rc = download(ds[0], outs[0]);
+  for (u32 i = 0; i < n; ++i) ds[i]->solved = rc == KS_OK;
   return rc;
 }
 
@@ -4264,6 +4267,125 @@ extern "C" int ks_replacement_commands_host(ks_dev_problem* const* ds, uint32_t 
   if (written > cap_nodes) return fail(KS_ERR_INTERNAL, "replacement commands: node rows beyond the table");
   if (written) HIPCHK(hipMemcpy(out_nodes, nbuf.p, (size_t)written * NW * sizeof(u64), hipMemcpyDeviceToHost));
   memcpy(out_heads, heads.data(), hbytes); *out_total_nodes = total;
+  if (ms) { ms[0] = std::chrono::duration<double, std::milli>(t1 - t0).count(); ms[1] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count(); }
+  return KS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Placement rows (ksolve.h KS_PLC_*): the per-pod half of results that are still on the device -- where every pod of the batch went, at which relaxation stage, in
+// which commit order, and why not -- as one fixed-size head per problem and one fixed-size row per pod in queue order.
+//   ks_placement_heads   ONE workgroup, ks_replacement_heads' shape: lane t of a tile takes problem base + t, row_off is an exclusive scan of P in problem order --
+//                        Hillis-Steele over an LDS tile, the tile's sum carried to the next.  No atomic.  Every lane walks every tile and every scan step.
+//   ks_placement_rows    grid (x, n): blockIdx.y is the problem, the lanes of its x-blocks stride over its pods.  Lane k reads the queue entry, the pod's four result
+//                        words, and writes its own row: 32 bytes, 32-byte aligned (row index * 32 on a 256-byte aligned table), as two 16-byte stores.  A problem
+//                        whose rows do not fit below the table's capacity is skipped by all of its lanes alike (the flag comes from its head).  No LDS, no barrier,
+//                        no wave operation: every lane's row is its own.
+// ------------------------------------------------------------------------------------------------
+struct PlcDesc { u64 id; };
+typedef u32 PlcHalf __attribute__((vector_size(16)));      // half a row: one 16-byte store
+__global__ __launch_bounds__(256) void ks_placement_heads(const DevProb* probs, const DevState* states, const PlcDesc* descs, u32 n, u64 cap_rows, u64* heads, u64* total) {
+  __shared__ u64 s_sum[KS_REP_TILE];
+  const u32 tid = threadIdx.x; u64 carry = 0;
+  for (u32 base = 0; base < n; base += KS_REP_TILE) {
+    const u32 i = base + tid; const bool live = i < n;
+    const u64 mine = live ? (u64)probs[i].P : 0ull;
+    s_sum[tid] = mine;
+    for (u32 off = 1; off < KS_REP_TILE; off <<= 1) {      // inclusive scan of the tile
+      __syncthreads();
+      const u64 x = tid >= off ? s_sum[tid - off] : 0ull;
+      __syncthreads();
+      s_sum[tid] += x;
+    }
+    __syncthreads();
+    const u64 row_off = carry + s_sum[tid] - mine;
+    carry += s_sum[KS_REP_TILE - 1];
+    __syncthreads();      // (the tile's sum has been read by every lane before the next tile overwrites it)
+    if (live) {
+      u64* h = heads + (size_t)i * KS_PLC_HEAD_WORDS;
+      h[KS_PLC_ID] = descs[i].id; h[KS_PLC_P] = mine; h[KS_PLC_N_NEW] = states[i].out_counts[0]; h[KS_PLC_N_UNSCHEDULED] = states[i].out_counts[1];
+      h[KS_PLC_ROW_OFF] = row_off; h[KS_PLC_FLAGS] = (mine && row_off + mine > cap_rows) ? (u64)KS_PLC_TRUNCATED : 0ull; h[KS_PLC_N_EXISTING] = probs[i].E; h[7] = 0;
+    }
+  }
+  if (tid == 0) *total = carry;
+}
+__global__ __launch_bounds__(256) void ks_placement_rows(const DevProb* probs, const DevState* states, const u64* heads, u64* rows) {
+  const DevProb& P = probs[blockIdx.y]; const DevState& S = states[blockIdx.y];
+  const u64* head = heads + (size_t)blockIdx.y * KS_PLC_HEAD_WORDS;
+  if (head[KS_PLC_FLAGS] & KS_PLC_TRUNCATED) return;      // (its rows would reach beyond the table: none is written)
+  const u64 off = head[KS_PLC_ROW_OFF]; const u32 id = (u32)head[KS_PLC_ID]; const u32 np = P.P;
+  for (u32 k = blockIdx.x * 256u + threadIdx.x; k < np; k += gridDim.x * 256u) {
+    const u32 pd = P.queue ? GC(u32, P.queue)[k] : k;       // (a derived what-if's batch is in queue order already)
+    const u32 pod = P.pod_gid ? GC(u32, P.pod_gid)[pd] : pd;      // ... and names the snapshot's pods
+    const PlcHalf a = {pod, (u32)GC(i32, S.pod_node)[pd], (u32)GC(i32, S.pod_stage)[pd], (u32)GC(i32, S.pod_seq)[pd]};
+    const PlcHalf b = {GC(u32, S.pod_reason)[pd], id, k, 0u};
+    GA PlcHalf* row = (GA PlcHalf*)(rows + (size_t)(off + k) * KS_PLC_ROW_WORDS);
+    row[0] = a; row[1] = b;
+  }
+}
+// every refusal of ks_placement_rows*: before any device work (`st` is opened by it)
+static int placement_check(BatchStage& st, ks_dev_problem* const* ds, u32 n, const uint64_t* ids) {
+  if (!ds || !ids) return fail(KS_ERR_INVALID, "null argument");
+  TRY(BatchStage::not_null(ds, n));
+  return st.open(ds, n, nullptr, false, [&](u32 i) { return ds[i]->solved ? (int)KS_OK : fail(KS_ERR_INVALID, "placement rows of a problem that holds no result: solve it first (or the last solve failed)"); });
+}
+// inputs up, the heads kernel, completion: the heads are complete in d_heads, *out_total = the sum of P, *pmax the largest P
+static int placement_heads(BatchStage& st, const uint64_t* ids, void* d_heads, uint64_t cap_rows, uint64_t* out_total, u32* pmax) {
+  const u32 n = st.n; *pmax = 0;
+  const size_t o_desc = st.add<PlcDesc>(n), o_total = st.add<u64>(1);
+  TRY(st.place());
+  for (u32 i = 0; i < n; ++i) { st.h<PlcDesc>(o_desc)[i] = PlcDesc{ids[i]}; *pmax = std::max(*pmax, st.ds[i]->h.P); }
+  TRY(st.upload(o_total));
+  hipLaunchKernelGGL(ks_placement_heads, dim3(1), dim3(KS_REP_TILE), 0, st.stream(), st.probs(), st.states(), st.d<const PlcDesc>(o_desc), n, (u64)cap_rows, (u64*)d_heads, st.d<u64>(o_total));
+  TRY(st.fetch(o_total));
+  *out_total = st.h<u64>(o_total)[0];
+  return KS_OK;
+}
+// the rows of every problem whose head says they fit, and completion.  grid.x: enough blocks for the largest problem at one pod per lane, at most 64 (a lane then
+// strides; the blocks of a smaller problem beyond its pods leave at once).  grid.y is the problem, and a grid holds at most 65 535 rows of blocks: a larger batch goes
+// in slices of that many, each with the views and heads of its own problems (row_off is batch-wide, so the row table is the same).
+static int placement_rows_launch(BatchStage& st, void* d_heads, void* d_rows, u32 pmax) {
+  const u32 KS_GRID_Y_MAX = 65535u;
+  for (u32 base = 0; base < st.n; base += KS_GRID_Y_MAX)
+    hipLaunchKernelGGL(ks_placement_rows, dim3(std::min(64u, (pmax + 255u) / 256u), std::min(KS_GRID_Y_MAX, st.n - base)), dim3(256), 0, st.stream(), st.probs() + base, st.states() + base,
+                       (const u64*)d_heads + (size_t)base * KS_PLC_HEAD_WORDS, (u64*)d_rows);
+  HIPCHK(hipStreamSynchronize(st.stream())); HIPCHK(hipGetLastError());
+  return KS_OK;
+}
+extern "C" int ks_placement_rows_dev(ks_dev_problem* const* ds, uint32_t n, const uint64_t* ids, void* d_heads, void* d_rows, uint64_t cap_rows, uint64_t* out_total_rows) {
+  if (!out_total_rows) return fail(KS_ERR_INVALID, "null argument");
+  *out_total_rows = 0;
+  if (!n) return KS_OK;
+  if (!d_heads || (cap_rows && !d_rows)) return fail(KS_ERR_INVALID, "null argument");
+  if (((uintptr_t)d_rows & 31u) || ((uintptr_t)d_heads & 7u)) return fail(KS_ERR_INVALID, "placement tables: the row table must be 32-byte aligned, the heads 8-byte aligned");
+  BatchStage st; TRY(placement_check(st, ds, n, ids));
+  u32 pmax = 0; TRY(placement_heads(st, ids, d_heads, cap_rows, out_total_rows, &pmax));
+  if (pmax && cap_rows) TRY(placement_rows_launch(st, d_heads, d_rows, pmax));      // (a batch without pods, or a sizing call, needs the heads only)
+  return KS_OK;
+}
+// The same with both tables brought to the host: the heads in full, and the rows that were written -- a prefix of the table, because row_off ascends: up to the first
+// truncated problem's row_off.  Nothing beyond that prefix is touched in out_rows.  The device block for the rows is sized once the heads kernel has said how many
+// there are -- min(cap_rows, total) rows: a generous capacity costs nothing.  ms[0] = inputs up + launches + completion, ms[1] = the read-back.
+extern "C" int ks_placement_rows_host(ks_dev_problem* const* ds, uint32_t n, const uint64_t* ids, uint64_t* out_heads, uint64_t* out_rows, uint64_t cap_rows, uint64_t* out_total_rows, double* ms) {
+  if (ms) ms[0] = ms[1] = 0.0;
+  if (!out_total_rows) return fail(KS_ERR_INVALID, "null argument");
+  *out_total_rows = 0;
+  if (!n) return KS_OK;
+  if (!out_heads || (cap_rows && !out_rows)) return fail(KS_ERR_INVALID, "null argument");
+  BatchStage st; TRY(placement_check(st, ds, n, ids));
+  const size_t hbytes = (size_t)n * KS_PLC_HEAD_WORDS * sizeof(u64), RB = KS_PLC_ROW_WORDS * sizeof(u64);
+  TmpDev hbuf(ds[0]->device), rbuf(ds[0]->device); TRY(hbuf.alloc(hbytes));
+  std::vector<u64> heads((size_t)n * KS_PLC_HEAD_WORDS);
+  const auto t0 = std::chrono::steady_clock::now();
+  uint64_t total = 0; u32 pmax = 0; TRY(placement_heads(st, ids, hbuf.p, cap_rows, &total, &pmax));
+  const uint64_t room = std::min<uint64_t>(cap_rows, total);      // (a problem is written only if it ends at or below cap_rows, and no row lies at or beyond the total)
+  if (pmax && room) { TRY(rbuf.alloc((size_t)room * RB)); TRY(placement_rows_launch(st, hbuf.p, rbuf.p, pmax)); }
+  const auto t1 = std::chrono::steady_clock::now();
+  HIPCHK(hipMemcpy(heads.data(), hbuf.p, hbytes, hipMemcpyDeviceToHost));
+  uint64_t written = total;
+  for (u32 i = 0; i < n; ++i) if (heads[(size_t)i * KS_PLC_HEAD_WORDS + KS_PLC_FLAGS] & KS_PLC_TRUNCATED) { written = heads[(size_t)i * KS_PLC_HEAD_WORDS + KS_PLC_ROW_OFF]; break; }
+  if (written > room) return fail(KS_ERR_INTERNAL, "placement rows: rows beyond the table");
+  if (written) HIPCHK(hipMemcpy(out_rows, rbuf.p, (size_t)written * RB, hipMemcpyDeviceToHost));
+  memcpy(out_heads, heads.data(), hbytes); *out_total_rows = total;
   if (ms) { ms[0] = std::chrono::duration<double, std::milli>(t1 - t0).count(); ms[1] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count(); }
   return KS_OK;
 }

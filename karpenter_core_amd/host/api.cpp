@@ -40,6 +40,8 @@ struct Handle {
   std::shared_ptr<void> base_dev;      // what-ifs over a snapshot: the snapshot's own flattening, resident on the device (shared catalogue + derived tables)
   bool solved = false;                 // rb holds the result of a successful solve (the result buffers are raw memory until then)
   bool dev_result = false;             // the device holds the result of a successful solve (price filter / launch pick / records read it there)
+  bool snapshot_whatif = false;        // a what-if over a cluster snapshot (ksh_open_whatifs* / ksh_open_whatifs_derived): ksh_placement_rows renames its rows to the snapshot's ids.  Said by the calls that open one, never inferred: a Solve flattened over the environment cache shares an Encoded and names a source problem too
+  std::vector<uint32_t> pod_ids;       // a what-if flattened by itself over a snapshot: batch pod i is the snapshot's pod pod_ids[i] (candidate order, then pod order; ksh_placement_rows names pods by it)
   std::vector<uint32_t> csr_off; std::vector<int32_t> csr_pods;      // ksh_result_arrays: the pods of every node in commit order (built on demand from pod_seq)
   ~Handle() { if (dev && !delta) ks_problem_free(dev); }
 };
@@ -287,10 +289,13 @@ static int open_whatifs_over(std::shared_ptr<const ksp::Problem> snapshot, uint3
     else { if (!pod_node && !snapshot->pods.empty()) return set_err(KS_ERR_INVALID, "no bindings (pod_node)"); sb = ksh::make_snapshot_base(snapshot, pod_node, flags); }
     if (timing()) { fprintf(stderr, "  what-ifs: snapshot base %8.2f ms\n", ms_since(t0)); t0 = clk::now(); }
     std::atomic<uint32_t> next{0}; std::atomic<int> rc{KS_OK}; std::vector<std::string> errs(n);
+    const std::vector<std::vector<uint32_t>>* by_node = ksh::delta_inputs(*sb).by_node;
     auto work = [&]() {
       for (;;) {
         const uint32_t w = next.fetch_add(1); if (w >= n) return;
-        try { out_handles[w] = new_handle(ksh::encode_whatif(*sb, cand + cand_off[w], cand_off[w + 1] - cand_off[w], flags));
+        try {
+          Handle* h = new_handle(ksh::encode_whatif(*sb, cand + cand_off[w], cand_off[w + 1] - cand_off[w], flags)); out_handles[w] = h; h->snapshot_whatif = true;
+          for (uint32_t i = cand_off[w]; i < cand_off[w + 1]; ++i) for (uint32_t p : (*by_node)[cand[i]]) h->pod_ids.push_back(p);      // (the batch's own order: encode.cpp Builder)
         } catch (const ksh::Unsupported& e) { errs[w] = e.what(); rc = KS_ERR_UNSUPPORTED;
         } catch (const std::exception& e) { errs[w] = e.what(); rc = KS_ERR_INVALID; }
       }
@@ -506,7 +511,7 @@ int ksh_open_whatifs_derived(void* parsed, uint32_t flags, uint32_t n, const uin
       auto h = std::make_unique<Handle>();
       h->enc = std::make_unique<ksh::Encoded>(); h->enc->src = snapshot; h->enc->shared = in.base; h->enc->shared_lattice = true; h->enc->view = true;
       h->enc->prob = bp; h->enc->prob.P = npods[w]; h->enc->prob.max_new_nodes = npods[w] ? npods[w] : 1;
-      h->dev = views[w]; h->delta = D; h->delta_index = w; h->base_dev = D->base_dev;
+      h->dev = views[w]; h->delta = D; h->delta_index = w; h->base_dev = D->base_dev; h->snapshot_whatif = true;
       out_handles[w] = h.release();
     }
     lap("handles");
@@ -795,6 +800,38 @@ int ksh_replacement_rows(void** hv, uint32_t n, const uint64_t* ids, const uint3
     return dev_rc(ks_replacement_commands_host(ds.data(), n, ids, flags, words, out_heads, out_nodes, cap_nodes, out_total_nodes, ms));
   });
 }
+// The placement tables of handles that hold a result on the device: ks_placement_rows_host for handles, then -- on the host, a pass over the rows that came back --
+// the rows of a what-if over a snapshot renamed to the snapshot's own stable ids: existing-node row e -> the node's slot (a derived what-if: the snapshot's
+// flattening's rows; a what-if flattened by itself: its own), new node j -> node slots + j, and for a what-if flattened by itself batch pod i -> the snapshot's pod
+// (a derived one's rows name snapshot pods already: pod_gid).  The head's KS_PLC_N_EXISTING becomes the number of node slots, so `where` reads the same way.
+int ksh_placement_rows(void** hv, uint32_t n, const uint64_t* ids, uint64_t* out_heads, uint64_t* out_rows, uint64_t cap_rows, uint64_t* out_total_rows, double* ms) {
+  if (ms) ms[0] = ms[1] = 0.0;
+  if (!out_total_rows || (n && (!hv || !ids || !out_heads)) || (cap_rows && !out_rows)) return set_err(KS_ERR_INVALID, "null argument");
+  return guarded([&] {
+    std::vector<ks_dev_problem*> ds;
+    int rc = device_problems(hv, n, true, "placement rows before solve", ds); if (rc != KS_OK) return rc;
+    rc = dev_rc(ks_placement_rows_host(ds.data(), n, ids, out_heads, out_rows, cap_rows, out_total_rows, ms)); if (rc != KS_OK) return rc;
+    const auto t0 = clk::now();
+    for (uint32_t i = 0; i < n; ++i) {
+      const Handle* h = (const Handle*)hv[i]; uint64_t* head = out_heads + (size_t)i * KS_PLC_HEAD_WORDS;
+      if (!h->snapshot_whatif) continue;      // any other problem -- a Solve over the environment cache included -- keeps its own pod and existing-node indices, as ksh_result_arrays_get gives them
+      const std::vector<int>& slot_of = h->enc->view ? h->enc->shared->existing : h->enc->existing;
+      const uint32_t E = (uint32_t)head[KS_PLC_N_EXISTING], slots = (uint32_t)h->enc->src->nodes.size();
+      if (!h->enc->shared || !h->enc->src || slot_of.size() != E || (!h->enc->view && h->pod_ids.size() != head[KS_PLC_P])) return set_err(KS_ERR_INTERNAL, "placement rows: the what-if's tables do not match its flattening");
+      head[KS_PLC_N_EXISTING] = slots;
+      if (head[KS_PLC_FLAGS] & KS_PLC_TRUNCATED) continue;
+      uint64_t* row = out_rows + (size_t)head[KS_PLC_ROW_OFF] * KS_PLC_ROW_WORDS;
+      for (uint64_t k = 0; k < head[KS_PLC_P]; ++k, row += KS_PLC_ROW_WORDS) {
+        uint32_t pod = (uint32_t)row[KS_PLC_POD_WHERE]; int32_t where = (int32_t)(uint32_t)(row[KS_PLC_POD_WHERE] >> 32);
+        if (!h->enc->view) { if (pod >= h->pod_ids.size()) return set_err(KS_ERR_INTERNAL, "placement rows: pod index out of range"); pod = h->pod_ids[pod]; }
+        if (where >= 0) where = (uint32_t)where < E ? (int32_t)slot_of[(uint32_t)where] : (int32_t)(slots + ((uint32_t)where - E));
+        row[KS_PLC_POD_WHERE] = (uint64_t)pod | ((uint64_t)(uint32_t)where << 32);
+      }
+    }
+    if (ms) ms[1] += ms_since(t0);
+    return KS_OK;
+  });
+}
 }  // extern "C"
 // What getNodePrices / filterOutSameType / simulateScheduling's readiness rule read of the snapshot's nodes, once per call
 namespace {
@@ -965,6 +1002,48 @@ int replacement_over(Parsed* P, uint32_t flags, uint32_t n, const uint32_t* cand
   if (ms) ms[4] = ms_since(t_call) - ms[0] - ms[1] - ms[2] - ms[3];
   return KS_OK;
 }
+// Provisioner.Reconcile's Solve (provisioning/provisioner.go:117-150) over the snapshot: ONE what-if with no candidate -- the carrier of the pending pods and the nodes
+// marked for deletion leave, their pods are the batch --, on SimBatch's route, then three tables off the result on the device: placement rows, machine rows
+// (ks_replacement_nodes' rows, every new node), the launch pick per machine.  ms[5] as commands_over: [2] the kernels of all three, [3] their read-backs.
+int provision_over(Parsed* P, uint32_t flags, const int32_t* pod_node, const uint32_t* deleting, uint32_t n_deleting, int device, ksh_provision_out* out, double* ms) {
+  zero(ms, 5);
+  if (!P || !out || (n_deleting && !deleting) || (out->cap_rows && !out->rows) || (out->cap_machines && !out->machines)) return set_err(KS_ERR_INVALID, "null argument");
+  const bool picks = out->pick_type || out->pick_zone || out->pick_ct || out->pick_price;
+  if (picks && !(out->pick_type && out->pick_zone && out->pick_ct && out->pick_price)) return set_err(KS_ERR_INVALID, "null argument");
+  out->route = KSH_PROVISION_NOTHING; out->total_rows = out->total_machines = 0; std::fill(out->head, out->head + KS_PLC_HEAD_WORDS, 0ull);
+  const uint32_t words = out->words, none[2] = {0, 0};
+  SimBatch B; int rc = B.begin(P, "provision", "machine", flags, 1, none, nullptr, deleting, n_deleting, words);
+  if (rc != KS_OK) return rc;
+  const auto t_call = clk::now();
+  // nothing pending, nothing on a node that is going: Reconcile returns before NewScheduler (provisioner.go:145-147) -- no flattening, no launch
+  const int32_t* bound = bindings_of(P, pod_node); const size_t np = P->pr->pods.size(), NN = P->pr->nodes.size(); size_t batch = 0;
+  if (!bound && np) return set_err(KS_ERR_INVALID, "no bindings (pod_node)");
+  for (size_t p = 0; p < np; ++p) { if (bound[p] < 0) continue; if ((size_t)bound[p] >= NN) return set_err(KS_ERR_INVALID, "pod_node out of range"); batch += B.is_del[bound[p]]; }
+  if (!batch) return KS_OK;
+  B.add(nullptr, 0, [](const CmdNode&) {});      // (its answer -- an uninitialised node stays -- is not read: Reconcile has no check like helpers.go:102-113, such a node is an in-flight ExistingNode)
+  rc = B.open_and_solve(flags, pod_node, device, true, ms);
+  if (rc != KS_OK) return rc;
+  out->route = ((Handle*)B.hs[0])->delta ? KSH_PROVISION_DERIVED : KSH_PROVISION_FLATTENED;
+  const uint64_t id = 0; const uint32_t no_flags = 0; double part[2] = {0.0, 0.0};
+  rc = ksh_placement_rows(B.hs.data(), 1, &id, out->head, out->rows, out->cap_rows, &out->total_rows, part);
+  if (rc != KS_OK) return rc;
+  if (ms) { ms[2] += part[0]; ms[3] += part[1]; }
+  uint64_t rep_head[KS_REP_HEAD_WORDS];
+  rc = ksh_replacement_rows(B.hs.data(), 1, &id, &no_flags, words, rep_head, out->machines, out->cap_machines, &out->total_machines, part);
+  if (rc != KS_OK) return rc;
+  if (ms) { ms[2] += part[0]; ms[3] += part[1]; }
+  if ((rep_head[KS_REP_DECISION] >> 16) & KS_REP_TRUNCATED) out->head[KS_PLC_FLAGS] |= KSH_PROVISION_MACHINES_TRUNCATED;
+  else if (picks && out->total_machines) {
+    const auto t0 = clk::now(); const uint32_t nm = (uint32_t)out->total_machines;
+    std::vector<void*> same(nm, B.hs[0]); std::vector<uint32_t> node(nm); for (uint32_t j = 0; j < nm; ++j) node[j] = j;
+    rc = ksh_launch_pick(same.data(), nm, node.data(), out->pick_type, out->pick_zone, out->pick_ct, out->pick_price);
+    if (rc != KS_OK) return rc;
+    if (ms) ms[2] += ms_since(t0);
+  }
+  B.close();
+  if (ms) ms[4] = ms_since(t_call) - ms[0] - ms[1] - ms[2] - ms[3];
+  return KS_OK;
+}
 // mapNodes (helpers.go:328-337) by reason code: a node of a command is still a candidate iff candidateNodes yields it under consolidation.ShouldDeprovision -- reasons
 // 0 and 10-12 (sortAndFilterCandidates is not applied in validation)
 inline bool still_candidate(uint32_t why) { return why == 0 || (why >= KS_CAND_WHY_DELETING_NODE && why <= KS_CAND_WHY_DO_NOT_EVICT); }
@@ -1099,6 +1178,10 @@ int ksh_replacement_option(void* parsed, uint32_t flags, const uint32_t* candida
     return KS_OK;
   }
   return KS_OK;
+}
+// ---- provisioning (kshost.h): Provisioner.Reconcile's Solve over the snapshot kept by events ----
+int ksh_provision(void* parsed, uint32_t flags, const int32_t* pod_node, const uint32_t* deleting, uint32_t n_deleting, int device, ksh_provision_out* out, double* ms) {
+  return guarded([&] { return provision_over((Parsed*)parsed, flags, pod_node, deleting, n_deleting, device, out, ms); });
 }
 // ---- validation (kshost.h): Validation.IsValid / ValidateCommand over the snapshot as it is NOW, and the two loops built on it ----
 int ksh_validate_commands(void* parsed, uint32_t flags, uint32_t n, const uint32_t* node_off, const uint32_t* nodes, const uint32_t* expect_replacement, const uint64_t* options,
@@ -1393,7 +1476,7 @@ int ksh_emptiness_command(const uint32_t* candidates, uint32_t n, const uint32_t
   return KS_OK;
 }
 // The names behind a row, without a handle: what 0 = requirement key a, 1 = value b of key a (the flattening's universes: available once a what-if call flattened the
-// snapshot), 3 = state node a, 4 = instance type a.  NULL when out of range.
+// snapshot), 3 = state node a, 4 = instance type a, 5 / 6 = value a of the zone / capacity-type universe (a launch pick's ids).  NULL when out of range.
 const char* ksh_snapshot_name(void* parsed, int what, uint32_t a, uint32_t b) {
   Parsed* P = (Parsed*)parsed; if (!P) return nullptr;
   std::lock_guard<std::mutex> g(P->mu);
@@ -1406,6 +1489,7 @@ const char* ksh_snapshot_name(void* parsed, int what, uint32_t a, uint32_t b) {
     if (what == 0 && a < E.key_names.size()) name = E.key_names[a].c_str();
     if (what == 1 && a < E.key_values.size() && b < E.key_values[a].size()) name = E.key_values[a][b].c_str();
     if (what == 2 && a < E.res_names.size()) name = E.res_names[a].c_str();
+    if (what == 5 || what == 6) { const int32_t k = what == 5 ? E.prob.key_zone : E.prob.key_ct; if (k >= 0 && a < E.key_values[k].size()) name = E.key_values[k][a].c_str(); }
     return KS_OK;
   });
   return name;

@@ -1302,6 +1302,127 @@ def decode_replacement_node(snapshot: "ParsedProblem", row, words: int) -> dict:
             "req_words": r[KS_REP_NODE_REQ:KS_REP_NODE_REQ + KS_MAX_RES]}
 
 
+# ---- placement rows and provisioning over the snapshot (include/ksolve.h KS_PLC_*, include/kshost.h ksh_provision / ksh_placement_rows) ----
+KS_PLC_HEAD_WORDS, KS_PLC_ROW_WORDS = 8, 4
+KS_PLC_ID, KS_PLC_P, KS_PLC_N_NEW, KS_PLC_N_UNSCHEDULED, KS_PLC_ROW_OFF, KS_PLC_FLAGS, KS_PLC_N_EXISTING = range(7)
+KS_PLC_POD_WHERE, KS_PLC_STAGE_SEQ, KS_PLC_REASON_ID, KS_PLC_POSITION = range(4)
+KS_PLC_TRUNCATED, KSH_PROVISION_MACHINES_TRUNCATED = 1, 2
+KSH_PROVISION_NOTHING, KSH_PROVISION_DERIVED, KSH_PROVISION_FLATTENED = 0, 1, 2
+PROVISION_ROUTES = {KSH_PROVISION_NOTHING: "nothing", KSH_PROVISION_DERIVED: "derived", KSH_PROVISION_FLATTENED: "flattened"}
+
+
+class _ProvisionOut(ctypes.Structure):      # include/kshost.h ksh_provision_out
+    _fields_ = [("words", ctypes.c_uint32), ("route", ctypes.c_uint32), ("cap_rows", ctypes.c_uint64), ("cap_machines", ctypes.c_uint64), ("total_rows", ctypes.c_uint64),
+                ("total_machines", ctypes.c_uint64), ("head", ctypes.c_uint64 * KS_PLC_HEAD_WORDS), ("rows", ctypes.c_void_p), ("machines", ctypes.c_void_p),
+                ("pick_type", ctypes.c_void_p), ("pick_zone", ctypes.c_void_p), ("pick_ct", ctypes.c_void_p), ("pick_price", ctypes.c_void_p)]
+
+
+def _s32(x: int) -> int:
+    return x - (1 << 32) if x >= (1 << 31) else x
+
+
+def decode_placement_head(head) -> dict:
+    """A KS_PLC_* head as Python values.  `n_existing`: `where` values below it name existing nodes (for a what-if over a snapshot: node slots), at or above it new nodes."""
+    r = [int(x) for x in head]
+    return {"id": r[KS_PLC_ID], "pods": r[KS_PLC_P], "n_new": r[KS_PLC_N_NEW], "n_unscheduled": r[KS_PLC_N_UNSCHEDULED], "row_off": r[KS_PLC_ROW_OFF],
+            "truncated": bool(r[KS_PLC_FLAGS] & KS_PLC_TRUNCATED), "machines_truncated": bool(r[KS_PLC_FLAGS] & KSH_PROVISION_MACHINES_TRUNCATED), "n_existing": r[KS_PLC_N_EXISTING],
+            "reserved": r[7]}
+
+
+def decode_placement_row(row, n_existing: int) -> dict:
+    """A KS_PLC_* row as Python values: `pod`; exactly one of `existing` (a node index / slot) and `new` (new node j) unless the pod is unscheduled (both None); the
+    relaxation `stage`; the commit number `seq` (-1 if unscheduled); the packed `reason` word (model.reason_codes unpacks it); the head's id; the queue position."""
+    r = [int(x) for x in row]
+    where = _s32(r[KS_PLC_POD_WHERE] >> 32)
+    return {"pod": r[KS_PLC_POD_WHERE] & 0xFFFFFFFF, "where": where, "existing": where if 0 <= where < n_existing else None, "new": where - n_existing if where >= n_existing else None,
+            "stage": _s32(r[KS_PLC_STAGE_SEQ] & 0xFFFFFFFF), "seq": _s32(r[KS_PLC_STAGE_SEQ] >> 32), "reason": r[KS_PLC_REASON_ID] & 0xFFFFFFFF, "id": r[KS_PLC_REASON_ID] >> 32,
+            "position": r[KS_PLC_POSITION]}
+
+
+def placement_lists(rows: Sequence[dict]) -> dict:
+    """Decoded rows of ONE problem regrouped as Solve returns them: `new` {j: pods in commit order (Node.Pods)}, `existing` {node: pods in commit order},
+    `unscheduled` [pods in queue order], `stage` {pod: stage}, `reasons` {unscheduled pod: packed reason}."""
+    new, existing = {}, {}
+    for d in sorted((d for d in rows if d["where"] >= 0), key=lambda d: d["seq"]):
+        (new.setdefault(d["new"], []) if d["new"] is not None else existing.setdefault(d["existing"], [])).append(d["pod"])
+    return {"new": new, "existing": existing, "unscheduled": [d["pod"] for d in rows if d["where"] < 0], "stage": {d["pod"]: d["stage"] for d in rows},
+            "reasons": {d["pod"]: d["reason"] for d in rows if d["where"] < 0}}
+
+
+def placement_rows(flats: Sequence[FlatProblem], ids: Sequence[int], cap_rows: Optional[int] = None, heads=None, rows=None):
+    """`ksh_placement_rows`: the placement tables of handles whose results are on the device.  cap_rows None: the sizing call first, then a table exactly large enough.
+    `heads` / `rows`: preallocated uint64 tables to fill (tests poison them).  Returns (heads [n, 8], rows [cap_rows, 4] or None, total rows)."""
+    import numpy as np
+    if len(ids) != len(flats):
+        raise ValueError("placement_rows: one id per handle")
+    kh = libs()[1]
+    n = len(flats)
+    hs = (ctypes.c_void_p * max(1, n))(*[f._h for f in flats])
+    c_ids = np.ascontiguousarray(np.asarray(list(ids) or [0], dtype=np.uint64))
+    kh.ksh_placement_rows.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p]
+
+    def call(cap, hd, rw):
+        total = ctypes.c_uint64(0)
+        rc = kh.ksh_placement_rows(hs, n, c_ids.ctypes.data, hd.ctypes.data, rw.ctypes.data if rw is not None else None, cap, ctypes.byref(total), None)
+        if rc != KS_OK:
+            raise KSolveError(rc, kh.ksh_last_error().decode())
+        return int(total.value)
+    if cap_rows is None:
+        cap_rows = call(0, np.zeros((max(1, n), KS_PLC_HEAD_WORDS), dtype=np.uint64), None)
+    if heads is None:
+        heads = np.zeros((max(1, n), KS_PLC_HEAD_WORDS), dtype=np.uint64)
+    if rows is None and cap_rows:
+        rows = np.zeros((cap_rows, KS_PLC_ROW_WORDS), dtype=np.uint64)
+    total = call(cap_rows, heads, rows)
+    return heads[:n], rows, total
+
+
+def provision(snapshot: "ParsedProblem", pod_node: Optional[Sequence[int]], deleting: Sequence[int], words: int, cap_rows: Optional[int] = None, cap_machines: Optional[int] = None,
+              device: int = 0, volumes: bool = False, active_resources: bool = False, flags: int = 0, picks: bool = True, rows=None, machines=None):
+    """Provisioner.Reconcile's Solve over the snapshot (kshost.h `ksh_provision`): ONE what-if without candidates -- the nodes of `deleting` (the carrier of the pending
+    pods first, then the nodes marked for deletion) leave, their pods are the batch.  cap_rows / cap_machines None: the pods bound to `deleting` bound both, read from the
+    bindings the library holds or from `pod_node`.  `rows` / `machines`: preallocated uint64 tables to fill (tests poison them).  Returns a dict: `head` (decoded), `rows`
+    [total_rows, 4] or None when truncated, `machines` [total_machines, replacement_node_words(words)] or None, `picks` [(type index, zone id, capacity-type id, price) or
+    None per machine] or None, `route`, `total_rows`, `total_machines`, `ms`."""
+    import numpy as np
+    if words < 1:
+        raise ValueError("provision: words must be at least 1")
+    kh = libs()[1]
+    pn, pn_ptr = _pod_node_arg(pod_node)
+    dl = _u32s(deleting)
+    if cap_rows is None or cap_machines is None:
+        bound = list(pod_node) if pod_node is not None else snapshot.bindings()[0]
+        gone = set(int(j) for j in deleting)
+        npods = sum(1 for b in bound if int(b) in gone)
+        cap_rows = npods if cap_rows is None else cap_rows
+        cap_machines = npods if cap_machines is None else cap_machines
+    if rows is None and cap_rows:
+        rows = np.zeros((cap_rows, KS_PLC_ROW_WORDS), dtype=np.uint64)
+    if machines is None and cap_machines:
+        machines = np.zeros((cap_machines, replacement_node_words(words)), dtype=np.uint64)
+    ty, zo, ct = (np.full(max(1, cap_machines), -1, dtype=np.int32) for _ in range(3))
+    pr = np.zeros(max(1, cap_machines), dtype=np.float64)
+    out = _ProvisionOut()
+    out.words, out.cap_rows, out.cap_machines = words, cap_rows, cap_machines
+    out.rows = rows.ctypes.data if rows is not None and cap_rows else None
+    out.machines = machines.ctypes.data if machines is not None and cap_machines else None
+    if picks:
+        out.pick_type, out.pick_zone, out.pick_ct, out.pick_price = ty.ctypes.data, zo.ctypes.data, ct.ctypes.data, pr.ctypes.data
+    fl = (KSH_DERIVE_VOLUMES if volumes else 0) | (KSH_ACTIVE_RESOURCES if active_resources else 0) | flags
+    ms = (ctypes.c_double * 5)()
+    kh.ksh_provision.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int, ctypes.POINTER(_ProvisionOut), ctypes.POINTER(ctypes.c_double)]
+    rc = kh.ksh_provision(snapshot._p, fl, pn_ptr, dl.ctypes.data, len(deleting), device, ctypes.byref(out), ms)
+    if rc != KS_OK:
+        raise KSolveError(rc, kh.ksh_last_error().decode())
+    head = decode_placement_head(out.head)
+    tr, tm = int(out.total_rows), int(out.total_machines)
+    got_machines = tm <= cap_machines and not head["machines_truncated"]
+    return {"head": head, "route": PROVISION_ROUTES[int(out.route)], "total_rows": tr, "total_machines": tm, "ms": dict(zip(COMMAND_TIMING_KEYS, [float(x) for x in ms])),
+            "rows": None if head["truncated"] else (rows[:tr] if rows is not None else np.zeros((0, KS_PLC_ROW_WORDS), dtype=np.uint64)),
+            "machines": (machines[:tm] if machines is not None else np.zeros((0, replacement_node_words(words)), dtype=np.uint64)) if got_machines else None,
+            "picks": [None if ty[j] < 0 else (int(ty[j]), int(zo[j]), int(ct[j]), float(pr[j])) for j in range(tm)] if picks and got_machines else None}
+
+
 def command_rows(flats: Sequence[FlatProblem], ids: Sequence[int], flags: Sequence[int], cand_prices: Sequence[float], type_lists: Sequence[Sequence[Tuple[int, float]]], words: int,
                  out=None, type_off=None):
     """`ksh_command_rows`: the command rows of handles whose results are on the device, the per-what-if inputs given by the caller (flags: KS_CMD_F_*; type_lists[i]:
