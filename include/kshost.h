@@ -531,6 +531,29 @@ int ksh_provision(void* parsed_snapshot, uint32_t flags, const int32_t* pod_node
  * indices and existing-node indices ksh_result_arrays_get speaks of.  ms[2] (may be NULL): kernels | read-back and renaming. */
 int ksh_placement_rows(void** handles, uint32_t n, const uint64_t* ids, uint64_t* out_heads, uint64_t* out_rows, uint64_t cap_rows, uint64_t* out_total_rows, double* ms /* [2] or NULL */);
 
+/* ---- the AUDIT of results (ksolve.h ks_audit_dev, KS_AUDIT_*): every placement, every new node's Requests and InstanceTypeOptions checked on the device against the
+ * problem the result answers -- the shim's gate before it acts on a result: a finding means "do not act on this, solve in Go, file the problem" (INTEGRATION.md).
+ * ksh_audit works over any handles whose results are on the device, derived or not, as one launch sequence.  The caller's tables are sized as for ksh_placement_rows:
+ * the totals are always written, the flag rows only when they fit (pod_flags: cap_pods >= n_pods; node_flags: cap_nodes >= n_nodes; else KSH_AUDIT_TRUNCATED_* and the
+ * caller calls again with larger tables; cap 0 with a NULL table asks for the totals alone).  Indices are the problem's own: pod i and node n as
+ * ksh_result_arrays_get numbers them (existing node n < n_existing, else new node n - n_existing); a what-if derived on the device numbers its pods in the snapshot's
+ * queue order (ksh_placement_rows' KS_PLC_POSITION) and its existing nodes by the snapshot flattening's rows.  ms[2] (may be NULL): kernels | read-back. */
+#define KSH_AUDIT_TRUNCATED_PODS 1u
+#define KSH_AUDIT_TRUNCATED_NODES 2u
+typedef struct ksh_audit_out {
+  uint32_t* pod_flags; uint64_t cap_pods;      /* [cap_pods] KS_AUDIT_POD_* */
+  uint32_t* node_flags; uint64_t cap_nodes;    /* [cap_nodes] KS_AUDIT_NODE_* */
+  uint32_t n_pods, n_nodes, n_new, n_unscheduled;
+  uint32_t n_pods_flagged, n_nodes_flagged, truncated /* KSH_AUDIT_TRUNCATED_* */, pad;
+  uint32_t pod_bit_count[32], node_bit_count[32];
+} ksh_audit_out;
+int ksh_audit(void** handles, uint32_t n, ksh_audit_out* outs /* [n] */, double* ms /* [2] kernels | read-back, or NULL */);
+/* The same for a result the caller CLAIMS for one flattened handle (uploaded if it is not; KS_ERR_UNSUPPORTED for a what-if derived on the device): the arrays of
+ * ksh_result_arrays as ksh_result_arrays_get lays them out -- unscheduled [n_unscheduled], the per-node arrays [n_new] -- from wherever the caller got them.
+ * node_pods_off / node_pods and pod_reason are not read; ksh_result_arrays carries no commit numbers, so the pod_seq clause of KS_AUDIT_POD_RANGE is ks_audit_dev's alone.
+ * KS_ERR_INVALID: a NULL table, dimensions that are not the handle's, n_new > max_new_nodes. */
+int ksh_audit_claimed(void* handle, const ksh_result_arrays* claimed, ksh_audit_out* out, double* ms /* [2] or NULL */);
+
 /* ---- the snapshot kept current by EVENTS ("cached incremental SoA builder fed from state.Cluster") ----
  * Replaces, for the snapshot consolidation simulates over, what the reference does between two passes of the deprovisioner (deprovisioning/controller.go:64,
  * every 10 s): state.Cluster hears UpdateNode / DeleteNode / UpdatePod / DeletePod (pkg/controllers/state/cluster.go:151-200) and patches its nodes in place

@@ -666,6 +666,51 @@ int ks_placement_rows_dev(ks_dev_problem* const* ds, uint32_t n, const uint64_t*
  * [1] the read-back, milliseconds. */
 int ks_placement_rows_host(ks_dev_problem* const* ds, uint32_t n, const uint64_t* ids, uint64_t* out_heads, uint64_t* out_rows, uint64_t cap_rows, uint64_t* out_total_rows, double* ms);
 
+/* ---- the AUDIT of a result against the problem it answers -- not against a second run of the algorithm.  Every placement, every new node's Requests and every new
+ * node's InstanceTypeOptions are checked on the device, over the result where it lies, in time that does not matter next to the Solve; it works at any size, and for
+ * what-ifs derived on the device.  A finding means: do not act on this result.  Each check is a bit; each bit is an invariant of the reference's algorithm that
+ * holds in the FINAL state, whatever order the pods were placed in.  Throughout, a pod's class is the one of the stage it ended at,
+ * stage_cls[pod_stage_off[p] + pod_stage[p]].
+ * Pod bits (ks_audit.pod_flags[p]): */
+#define KS_AUDIT_POD_RANGE 1u             /* pod_node outside [-1, E + n_new) (a derived what-if: or an existing node that left), pod_stage outside the pod's stages, pod_seq negative for a placed pod or != -1 for an unscheduled one */
+#define KS_AUDIT_POD_UNSCHEDULED_LIST 2u  /* a pod with pod_node == -1 is not exactly once in unscheduled[0, n_unscheduled), or a placed pod is in it */
+#define KS_AUDIT_POD_TAINTS 4u            /* (the node's taints & ~cls_tolerated) != 0 (taints.go:28-40) */
+#define KS_AUDIT_POD_REQUIREMENTS 8u      /* existing node: Compatible(en, cls) fails or its_fail[en.it_state * SC + cls.it_state]; new node: Intersects(the node's final requirements, cls) fails on a narrow key, or the same lattice test with node_it_state.  ks_algebra.h's functions, not a restatement */
+#define KS_AUDIT_POD_HOSTNAME 16u         /* cls_hn_mode against the node: In [list] on a node outside the list, NotIn [list] on a node inside it; a new node is in no list */
+#define KS_AUDIT_POD_PORTS 32u            /* an entry of the class matches a reservation of the existing node, or an entry of another pod on the same node (hostportusage.go:45-57); both pods are flagged */
+#define KS_AUDIT_POD_VOLUME_ERROR 64u     /* a class with the 0xFFFFFFFF volume entry sits on an existing node */
+/* Node bits (ks_audit.node_flags[n]: existing node n < E, else new node n - E).  A node nothing was placed on is not examined beyond KS_AUDIT_NODE_EMPTY: no test of
+ * the reference ever ran against it, so an existing node whose own daemon requests exceed what is available is as the caller gave it, not a finding. */
+#define KS_AUDIT_NODE_RESOURCES 1u        /* existing node: en_requests plus the sum of its new pods' cls_requests does not Fit en_avail under resources.Fits' presence rule (existingnode.go:98-102) */
+#define KS_AUDIT_NODE_VOLUMES 2u          /* existing node: for some driver a pod placed there mounts, the distinct claims after those pods (en_vol_set, en_vol_count, the classes' vol_list) exceed en_vol_limit */
+#define KS_AUDIT_NODE_EMPTY 4u            /* a new node has no pod (nothing else of it is examined) */
+#define KS_AUDIT_NODE_TEMPLATE 8u         /* node_tmpl outside [0, M) (nothing else of it is examined) */
+#define KS_AUDIT_NODE_REQUESTS 16u        /* node_requests / node_requests_present is not exactly tmpl_daemon[m] merged with the sum of its pods' requests; int64, no tolerance */
+#define KS_AUDIT_NODE_OPTIONS_EMPTY 32u   /* the node has no option */
+#define KS_AUDIT_NODE_OPTIONS_EXTRA 64u   /* a set bit names a type outside T, outside tmpl_types[m], outside its_types[node_it_state], or one that fails compatible && fits && hasOffering (node.go:137-159) against the node's final requirements and requests */
+#define KS_AUDIT_NODE_OPTIONS_MISSING 128u /* only for templates with tmpl_limit_present == 0xFFFFFFFF: a type that passes all of that is not set.  The filter is monotone -- requirements only narrow, requests only grow -- so the incremental filtering of node.go:94 equals one filtering by the final state; a limited template starts from an order-dependent subset (scheduler.go:199-208) and gets OPTIONS_EXTRA only */
+/* Deliberately NOT audited: topology skew and affinity (they hold at the moment of placement, not at the end), provisioner limits (subtractMax depends on the order),
+ * first-fit optimality (whether an earlier node would have taken the pod).
+ * The caller owns the tables: pod_flags [P] and node_flags [E + max_new_nodes] (of which E + n_new are written), either may be NULL (totals only).  Flags are written
+ * per index -- no list is appended through an atomic -- so the output is the same every run. */
+typedef struct ks_audit {
+  uint32_t* pod_flags;            /* [P] KS_AUDIT_POD_*, or NULL */
+  uint32_t* node_flags;           /* [E + max_new_nodes] KS_AUDIT_NODE_*; entries [0, n_nodes) are written; or NULL */
+  uint32_t n_pods, n_nodes;       /* out: P | E + n_new */
+  uint32_t n_new, n_unscheduled;  /* out: the counts of the result that was audited */
+  uint32_t n_pods_flagged, n_nodes_flagged;
+  uint32_t pod_bit_count[32], node_bit_count[32];   /* out: pods / nodes carrying bit i */
+  double kernel_ms, readback_ms;  /* out: inputs up + the launches + completion | the flags' way back and the totals (a batch: the batch's, in every member) */
+} ks_audit;
+/* claimed == NULL: the result the last ks_solve*_dev of `d` left on the device is audited where it lies -- the form for derived what-ifs.  claimed given: the caller's
+ * arrays (ks_result's sizes; pod_reason and stats are not read) are uploaded and audited instead; for flattened problems only (KS_ERR_UNSUPPORTED for a derived view) --
+ * how a shim audits a result it got from anywhere.  ks_audit_batch_dev: the resident form for a whole batch as one launch sequence (four launches on ds[0]'s stream).
+ * Refusals (nothing launched): KS_ERR_INVALID for a NULL argument or table, a problem with nothing solved (resident form), a claimed n_new > max_new_nodes or
+ * n_unscheduled > P, a batch over two devices. */
+int ks_audit_dev(ks_dev_problem* d, const ks_result* claimed /* or NULL */, ks_audit* out);
+int ks_audit_batch_dev(ks_dev_problem* const* ds, uint32_t n, ks_audit* const* outs);
+int ks_audit_sizes(const ks_dev_problem* d, uint32_t* n_pods /* P */, uint32_t* n_node_slots /* E + max_new_nodes */);   /* what the two tables of `d` must hold (a derived what-if has no ks_problem to read them from); either may be NULL */
+
 /* ---- consolidation CANDIDATES, selected and ordered on the device (deprovisioning/helpers.go:124-165,275-287 GetPodEvictionCost / disruptionCost /
  * calculateLifetimeRemaining, pdblimits.go:57-70 CanEvictPods, helpers.go:339-366 canBeTerminated / PodsPreventEviction, consolidation.go:83-104 the sort).
  * Flat arrays in, flat arrays out; three kernels (per pod, per node, rank), no host fallback.

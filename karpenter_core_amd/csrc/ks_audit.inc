@@ -1,0 +1,339 @@
+// ks_audit.inc -- the audit of a Solve's result against the problem it answers (ksolve.h ks_audit_dev / ks_audit_batch_dev, KS_AUDIT_*).  Included by ksolve.hip
+// after the placement rows, outside the emulator's guards: the tests/sim build compiles and runs these kernels too.
+//
+// Every check is an invariant of the reference's algorithm that holds in the FINAL state whatever order the pods were placed in, so the audit needs neither the
+// pack kernels nor a second run of them: it reads the problem's arrays and the result where it lies (a Solve's own DevState, or a claimed result uploaded for the
+// call) and writes one flag word per pod and per node.  Four launches on the problems' stream, blockIdx.y = the problem:
+//   ks_audit_count   one lane per pod: the unscheduled list marked in a P-sized scratch array, the pods of every node counted (a counting sort's first half; the
+//                    atomics go to scratch only -- no output is appended through one, so the flags are the same every run).
+//   ks_audit_scan    one workgroup per problem: the exclusive scan of the counts (Hillis-Steele over an LDS tile, ks_placement_heads' way) = the node -> pods CSR's offsets.
+//   ks_audit_pods    one lane per pod: the pod bits that need no neighbour, and the pod's slot in its node's list (the counting sort's second half: the order within a
+//                    node depends on the run, and nothing below depends on that order -- int64 sums, unions and all-pairs tests).
+//   ks_audit_nodes   one wave per node: lanes stride the node's pods for the int64 sums and reduce across the wave; then one instance type per lane -- it_mask[k*T+t]
+//                    coalesced over t, Fits over R, the offering test against the node's zone x capacity-type mask -- and a ballot gives the 64-bit word that is compared
+//                    with the node's InstanceTypeOptions.  Host ports and volumes are walked per node (rare and short).  The PORTS bit of a pod is added to its flag
+//                    word by the one lane that holds the pod: a plain read-modify-write, after ks_audit_pods has finished.
+struct AuditView {
+  const i32* pod_node; const i32* pod_stage; const i32* pod_seq; const i32* unscheduled; const u32* counts;      // counts: [0] n_new, [1] n_unscheduled
+  const i32* n_tmpl; const u64* n_types; const i64* o_req; const u32* o_reqmask; const u32* o_present; const u32* o_complement; const u64* o_mask; const i32* o_gt; const i32* o_lt; const i32* o_it;
+  u32* meta; u32* pod_flags; u32* node_flags;      // outputs: meta [0] n_new, [1] n_unscheduled as the kernels read them | [P] | [E + NMAX]
+  u32* mark; u32* cnt; u32* off; u32* fill; u32* pods;      // scratch, zeroed before the first launch: [P] | [E + NMAX] | [E + NMAX + 1] | [E + NMAX] | [P]
+};
+__device__ __forceinline__ u32 aud_n_new(const DevProb& P, const AuditView& V) { const u32 n = GC(u32, V.counts)[0]; return n < P.NMAX ? n : P.NMAX; }
+__device__ __forceinline__ u32 aud_n_unsched(const DevProb& P, const AuditView& V) { const u32 n = GC(u32, V.counts)[1]; return n < P.P ? n : P.P; }
+__device__ __forceinline__ u32 aud_n_stages(const DevProb& P, u32 p) { const u32 gp = P.pod_gid ? GC(u32, P.pod_gid)[p] : p; return GC(u32, P.pod_stage_off)[gp + 1] - GC(u32, P.pod_stage_off)[gp]; }
+// the class of the stage the pod ended at; a stage outside the pod's chain (flagged RANGE) reads as stage 0 where a node still has to count the pod
+__device__ __forceinline__ u32 aud_class(const DevProb& P, const AuditView& V, u32 p) {
+  const u32 gp = P.pod_gid ? GC(u32, P.pod_gid)[p] : p; const u32 o = GC(u32, P.pod_stage_off)[gp], n = GC(u32, P.pod_stage_off)[gp + 1] - o;
+  const i32 st = GC(i32, V.pod_stage)[p];
+  return GC(u32, P.stage_cls)[o + ((st >= 0 && (u32)st < n) ? (u32)st : 0u)];
+}
+// the node a pod is on, or -1: unscheduled, outside [0, E + n_new), or an existing node that left the cluster (a derived what-if's candidate)
+__device__ __forceinline__ i32 aud_where(const DevProb& P, const AuditView& V, u32 p, u32 NS) {
+  const i32 nd = GC(i32, V.pod_node)[p];
+  if (nd < 0 || (u32)nd >= NS) return -1;
+  if ((u32)nd < P.E && P.en_removed && ((GC(u64, P.en_removed)[(u32)nd >> 6] >> ((u32)nd & 63u)) & 1ull)) return -1;
+  return nd;
+}
+__device__ __forceinline__ u64 aud_xor64(u64 v, int x) { const u32 lo = __shfl_xor((u32)v, x), hi = __shfl_xor((u32)(v >> 32), x); return (u64)lo | ((u64)hi << 32); }
+__device__ __forceinline__ u64 aud_wave_or(u64 v) { for (int x = 32; x > 0; x >>= 1) v |= aud_xor64(v, x); return v; }
+__device__ __forceinline__ u64 aud_wave_add(u64 v) { for (int x = 32; x > 0; x >>= 1) v += aud_xor64(v, x); return v; }
+// entry.matches, hostportusage.go:45-57: protocol and port equal, and the addresses equal or either unspecified
+__device__ __forceinline__ bool aud_port_match(u64 a, u64 b) { if ((a >> 32) != (b >> 32)) return false; const u32 ia = (u32)a, ib = (u32)b; return ia == ib || ia == 0 || ib == 0; }
+
+__global__ __launch_bounds__(256) void ks_audit_count(const DevProb* probs, const AuditView* views) {
+  const DevProb& P = probs[blockIdx.y]; const AuditView& V = views[blockIdx.y];
+  const u32 np = P.P, NS = P.E + aud_n_new(P, V), nu = aud_n_unsched(P, V);
+  for (u32 i = blockIdx.x * 256u + threadIdx.x; i < np; i += gridDim.x * 256u) {
+    if (i < nu) { const i32 u = GC(i32, V.unscheduled)[i]; if (u >= 0 && (u32)u < np) atomicAdd(&V.mark[u], 1u); }
+    const i32 nd = aud_where(P, V, i, NS);
+    if (nd >= 0) atomicAdd(&V.cnt[nd], 1u);
+  }
+}
+__global__ __launch_bounds__(256) void ks_audit_scan(const DevProb* probs, const AuditView* views) {
+  __shared__ u32 s_sum[256];
+  const DevProb& P = probs[blockIdx.x]; const AuditView& V = views[blockIdx.x];
+  const u32 tid = threadIdx.x, NS = P.E + aud_n_new(P, V); u32 carry = 0;
+  for (u32 base = 0; base < NS; base += 256u) {      // (NS is read from one address by every lane: every lane walks every tile and every scan step)
+    const u32 i = base + tid; const u32 mine = i < NS ? V.cnt[i] : 0u;
+    s_sum[tid] = mine;
+    for (u32 o = 1; o < 256u; o <<= 1) {
+      __syncthreads();
+      const u32 x = tid >= o ? s_sum[tid - o] : 0u;
+      __syncthreads();
+      s_sum[tid] += x;
+    }
+    __syncthreads();
+    if (i < NS) V.off[i] = carry + s_sum[tid] - mine;
+    carry += s_sum[255];
+    __syncthreads();
+  }
+  if (tid == 0) { V.off[NS] = carry; V.meta[0] = aud_n_new(P, V); V.meta[1] = aud_n_unsched(P, V); }
+}
+__global__ __launch_bounds__(256) void ks_audit_pods(const DevProb* probs, const AuditView* views) {
+  const DevProb& P = probs[blockIdx.y]; const AuditView& V = views[blockIdx.y];
+  const u32 np = P.P, E = P.E, NS = E + aud_n_new(P, V), K = P.K;
+  for (u32 p = blockIdx.x * 256u + threadIdx.x; p < np; p += gridDim.x * 256u) {
+    u32 f = 0;
+    const i32 raw = GC(i32, V.pod_node)[p], st = GC(i32, V.pod_stage)[p], sq = GC(i32, V.pod_seq)[p];
+    const i32 nd = aud_where(P, V, p, NS);
+    const bool stage_ok = st >= 0 && (u32)st < aud_n_stages(P, p);
+    if (raw != -1 && nd < 0) f |= KS_AUDIT_POD_RANGE;
+    if (!stage_ok) f |= KS_AUDIT_POD_RANGE;
+    if (raw == -1 ? sq != -1 : sq < 0) f |= KS_AUDIT_POD_RANGE;
+    const u32 listed = V.mark[p];
+    if (raw == -1 ? listed != 1u : listed != 0u) f |= KS_AUDIT_POD_UNSCHEDULED_LIST;
+    if (nd >= 0) V.pods[V.off[nd] + atomicAdd(&V.fill[nd], 1u)] = p;      // (its node counts the pod whatever else is wrong with it)
+    if (nd >= 0 && stage_ok) {
+      const u32 c = aud_class(P, V, p); const bool existing = (u32)nd < E; const u32 j = (u32)nd - E;
+      const u32 cp = GC(u32, P.cls.present)[c], cc = GC(u32, P.cls.complement)[c]; const i32 sb = GC(i32, P.cls.it_state)[c];
+      const i32 m = existing ? 0 : GC(i32, V.n_tmpl)[j]; const bool tmpl_ok = existing || (m >= 0 && (u32)m < P.M);
+      // Taints.Tolerates, taints.go:28-40 (a new node whose template is out of range is the node's finding: KS_AUDIT_NODE_TEMPLATE)
+      if (tmpl_ok) { const u64 taints = existing ? GC(u64, P.en_taints)[nd] : GC(u64, P.tmpl_taints)[m]; if (taints & ~GC(u64, P.cls_tolerated)[c]) f |= KS_AUDIT_POD_TAINTS; }
+      // existing node: Compatible(node, pod) (existingnode.go:104); new node: Intersects(the node's final requirements, pod) -- the requirements only narrowed since the pod arrived
+      const u32 npres = existing ? GC(u32, P.en.present)[nd] : GC(u32, V.o_present)[j], ncomp = existing ? GC(u32, P.en.complement)[nd] : GC(u32, V.o_complement)[j];
+      const u64* nmask = existing ? P.en.mask + (size_t)nd * K : V.o_mask + (size_t)j * K;
+      const i32* ngt = existing ? P.en.gt + (size_t)nd * K : V.o_gt + (size_t)j * K; const i32* nlt = existing ? P.en.lt + (size_t)nd * K : V.o_lt + (size_t)j * K;
+      bool bad = false;
+      for (u32 k = 0; k < K; ++k) {
+        if (!((cp >> k) & 1u)) continue;
+        const KReq a = load_req(npres, ncomp, nmask, ngt, nlt, (int)k);
+        const KReq b = load_req(cp, cc, P.cls.mask + (size_t)c * K, P.cls.gt + (size_t)c * K, P.cls.lt + (size_t)c * K, (int)k);
+        const i32* vi = P.value_int + k * 64; const u32 nv = GC(u32, P.key_nvalues)[k];
+        if (existing ? kreq_compatible_fail(a, b, (P.wellknown_mask >> k) & 1u, vi, nv) : kreq_intersects_fail(a, b, vi, nv)) bad = true;
+      }
+      const i32 sa = existing ? GC(i32, P.en.it_state)[nd] : GC(i32, V.o_it)[j];
+      if (P.SC && (sa < 0 || (u32)sa >= P.S || sb < 0 || (u32)sb >= P.SC || GC(u8, P.its_fail)[(size_t)sa * P.SC + sb])) bad = true;
+      if (bad) f |= KS_AUDIT_POD_REQUIREMENTS;
+      // the hostname requirement: existing node e owns hostname e, a new node's placeholder is in no list (node.go:46)
+      const u32 hm = GC(u8, P.cls_hn_mode)[c];
+      if (hm) {
+        bool inlist = false;
+        if (existing) for (u32 i = GC(u32, P.cls_hn_off)[c]; i < GC(u32, P.cls_hn_off)[c + 1]; ++i) if (GC(u32, P.hn_list)[i] == (u32)nd) { inlist = true; break; }
+        if (hm == 1 ? !inlist : inlist) f |= KS_AUDIT_POD_HOSTNAME;
+      }
+      // VolumeUsage.validate failed for the pod: no existing node accepts it (existingnode.go:87-90)
+      if (existing) for (u32 i = GC(u32, P.cls_vol_off)[c]; i < GC(u32, P.cls_vol_off)[c + 1]; ++i) if (GC(u32, P.vol_list)[i] == 0xFFFFFFFFu) { f |= KS_AUDIT_POD_VOLUME_ERROR; break; }
+    }
+    V.pod_flags[p] = f;
+  }
+}
+__global__ __launch_bounds__(256) void ks_audit_nodes(const DevProb* probs, const AuditView* views) {
+  const DevProb& P = probs[blockIdx.y]; const AuditView& V = views[blockIdx.y];
+  const u32 lane = threadIdx.x & 63u, E = P.E, NS = E + aud_n_new(P, V), R = P.R, K = P.K, T = P.T, TW = P.TW;
+  for (u32 s = blockIdx.x * 4u + (threadIdx.x >> 6); s < NS; s += gridDim.x * 4u) {      // (s, and everything read through it, is the same in all 64 lanes)
+    const u32 b = V.off[s], e = V.off[s + 1]; const bool existing = s < E; const u32 j = s - E;
+    u32 f = 0;
+    if (e == b) {      // nothing placed here: an existing node is as the problem gave it (nothing of it was ever tested), a new node without a pod is not a node
+      if (!existing) f = KS_AUDIT_NODE_EMPTY;
+      if (lane == 0) V.node_flags[s] = f;
+      continue;
+    }
+    // ---- the pods' requests, summed (int64, wrapping like the kernels' own additions: the order does not matter) ----
+    i64 sum[KS_MAX_RES]; u32 pres = 0; u64 dmask = 0; bool ports = false;
+#pragma unroll
+    for (int r = 0; r < KS_MAX_RES; ++r) sum[r] = 0;
+    for (u32 i = b + lane; i < e; i += 64u) {
+      const u32 c = aud_class(P, V, V.pods[i]);
+      pres |= GC(u32, P.cls_requests_present)[c];
+#pragma unroll
+      for (int r = 0; r < KS_MAX_RES; ++r) if ((u32)r < R) sum[r] = (i64)((u64)sum[r] + (u64)GC(i64, P.cls_requests)[(size_t)c * R + r]);
+      if (GC(u32, P.cls_port_off)[c + 1] != GC(u32, P.cls_port_off)[c]) ports = true;
+      if (existing && P.ND) for (u32 v = GC(u32, P.cls_vol_off)[c]; v < GC(u32, P.cls_vol_off)[c + 1]; ++v) { const u32 ent = GC(u32, P.vol_list)[v]; if (ent != 0xFFFFFFFFu) dmask |= 1ull << ((ent >> 24) & 63u); }
+    }
+#pragma unroll
+    for (int r = 0; r < KS_MAX_RES; ++r) if ((u32)r < R) sum[r] = (i64)aud_wave_add((u64)sum[r]);
+    pres = (u32)aud_wave_or(pres); dmask = aud_wave_or(dmask);
+    const bool any_ports = __ballot(ports) != 0;
+    // ---- host ports (hostportusage.go:81-93): every entry of a pod against the node's reservations and against every other pod's entries ----
+    if (any_ports) for (u32 i = b + lane; i < e; i += 64u) {
+      const u32 p = V.pods[i], c = aud_class(P, V, p); bool hit = false;
+      for (u32 x = GC(u32, P.cls_port_off)[c]; x < GC(u32, P.cls_port_off)[c + 1] && !hit; ++x) {
+        const u64 a = GC(u64, P.ports)[x];
+        if (existing) for (u32 y = GC(u32, P.en_port_off)[s]; y < GC(u32, P.en_port_off)[s + 1]; ++y) if (aud_port_match(a, GC(u64, P.ports)[y])) { hit = true; break; }
+        for (u32 i2 = b; i2 < e && !hit; ++i2) {
+          if (i2 == i) continue;
+          const u32 c2 = aud_class(P, V, V.pods[i2]);
+          for (u32 y = GC(u32, P.cls_port_off)[c2]; y < GC(u32, P.cls_port_off)[c2 + 1]; ++y) if (aud_port_match(a, GC(u64, P.ports)[y])) { hit = true; break; }
+        }
+      }
+      if (hit) V.pod_flags[p] |= KS_AUDIT_POD_PORTS;
+    }
+    if (existing) {
+      // ---- resources.Fits(requests + the pods', Available()) under its presence rule: only a resource in the merged list is compared (existingnode.go:98-102) ----
+      const u32 rp = GC(u32, P.en_requests_present)[s] | pres; bool over = false;
+#pragma unroll
+      for (int r = 0; r < KS_MAX_RES; ++r) if ((u32)r < R && ((rp >> r) & 1u)) { if ((i64)((u64)GC(i64, P.en_requests)[(size_t)s * R + r] + (u64)sum[r]) > GC(i64, P.en_avail)[(size_t)s * R + r]) over = true; }
+      if (over) f |= KS_AUDIT_NODE_RESOURCES;
+      // ---- volume limits (volumeusage.go:102-143): per driver some pod here mounts, the node's claims + the distinct claims the pods add, against the limit ----
+      for (u64 dm = dmask; dm; dm &= dm - 1) {
+        const u32 d = (u32)__builtin_ctzll(dm); u64 run = 0;
+        for (u32 i = b + lane; i < e; i += 64u) {
+          const u32 c = aud_class(P, V, V.pods[i]);
+          for (u32 v = GC(u32, P.cls_vol_off)[c]; v < GC(u32, P.cls_vol_off)[c + 1]; ++v) { const u32 ent = GC(u32, P.vol_list)[v]; if (ent != 0xFFFFFFFFu && (ent >> 31) && ((ent >> 24) & 63u) == d) run += ent & 0xFFFFFFu; }
+        }
+        run = aud_wave_add(run);
+        for (u32 w = 0; w < P.SW; ++w) {
+          u64 bits = 0;
+          for (u32 i = b + lane; i < e; i += 64u) {
+            const u32 c = aud_class(P, V, V.pods[i]);
+            for (u32 v = GC(u32, P.cls_vol_off)[c]; v < GC(u32, P.cls_vol_off)[c + 1]; ++v) { const u32 ent = GC(u32, P.vol_list)[v]; if (!(ent >> 31) && ((ent >> 24) & 63u) == d && ((ent & 0xFFFFFFu) >> 6) == w) bits |= 1ull << (ent & 63u); }
+          }
+          bits = aud_wave_or(bits) & ~GC(u64, P.en_vol_set)[(size_t)s * P.SW + w];
+          run += (u64)__builtin_popcountll(bits);
+        }
+        if ((i64)GC(i32, P.en_vol_count)[(size_t)s * P.ND + d] + (i64)run > (i64)GC(i32, P.en_vol_limit)[(size_t)s * P.ND + d]) f |= KS_AUDIT_NODE_VOLUMES;
+      }
+      if (lane == 0) V.node_flags[s] = f;
+      continue;
+    }
+    // ---- a new node ----
+    const i32 m = GC(i32, V.n_tmpl)[j];
+    if (m < 0 || (u32)m >= P.M) { if (lane == 0) V.node_flags[s] = KS_AUDIT_NODE_TEMPLATE; continue; }
+    // Requests = the template's daemon overhead merged with the pods' (node.go:100-104), to the milli-unit
+    const u32 rmask = GC(u32, V.o_reqmask)[j]; bool req_bad = rmask != (GC(u32, P.tmpl_daemon_present)[m] | pres);
+#pragma unroll
+    for (int r = 0; r < KS_MAX_RES; ++r) if ((u32)r < R) { if (GC(i64, V.o_req)[(size_t)j * R + r] != (i64)((u64)GC(i64, P.tmpl_daemon)[(size_t)m * R + r] + (u64)sum[r])) req_bad = true; }
+    if (req_bad) f |= KS_AUDIT_NODE_REQUESTS;
+    // InstanceTypeOptions against filterInstanceTypesByRequirements (node.go:137-159) by the node's final requirements and requests: one type per lane
+    const u32 np_ = GC(u32, V.o_present)[j], nc_ = GC(u32, V.o_complement)[j]; const i32 its = GC(i32, V.o_it)[j]; const bool its_ok = its >= 0 && (u32)its < P.S;
+    u64 allowZ = ~0ull, allowC = ~0ull;
+    if (P.key_zone >= 0 && ((np_ >> P.key_zone) & 1u)) allowZ = kreq_has_mask(load_req(np_, nc_, V.o_mask + (size_t)j * K, V.o_gt + (size_t)j * K, V.o_lt + (size_t)j * K, P.key_zone), P.value_int + P.key_zone * 64, GC(u32, P.key_nvalues)[P.key_zone]);
+    if (P.key_ct >= 0 && ((np_ >> P.key_ct) & 1u)) allowC = kreq_has_mask(load_req(np_, nc_, V.o_mask + (size_t)j * K, V.o_gt + (size_t)j * K, V.o_lt + (size_t)j * K, P.key_ct), P.value_int + P.key_ct * 64, GC(u32, P.key_nvalues)[P.key_ct]);
+    u64 pairs = 0;
+    for (u64 zz = allowZ; zz; zz &= zz - 1) { const int z = __builtin_ctzll(zz); if ((u32)z * P.n_ct >= 64) break; pairs |= (allowC & ((1ull << P.n_ct) - 1)) << (z * P.n_ct); }
+    if (P.n_ct == 0) pairs = ~0ull;
+    u64 extra = 0, missing = 0, any = 0;
+    for (u32 w = 0; w < TW; ++w) {
+      const u32 t = w * 64u + lane; bool ok = t < T && its_ok;
+      if (ok) ok = ((GC(u64, P.tmpl_types)[(size_t)m * TW + w] >> lane) & 1ull) && ((GC(u64, P.its_types)[(size_t)its * TW + w] >> lane) & 1ull);
+      if (ok) {
+        const u32 tp = GC(u32, P.it_present)[t], tc = GC(u32, P.it_complement)[t];
+        for (u32 k = 0; k < K && ok; ++k) {
+          if (!((np_ >> k) & 1u) || !((tp >> k) & 1u)) continue;
+          KReq a; a.present = true; a.complement = (tc >> k) & 1u; a.mask = GC(u64, P.it_mask)[(size_t)k * T + t]; a.gt = KS_NOGT; a.lt = KS_NOLT;
+          if (kreq_intersects_fail(a, load_req(np_, nc_, V.o_mask + (size_t)j * K, V.o_gt + (size_t)j * K, V.o_lt + (size_t)j * K, (int)k), P.value_int + k * 64, GC(u32, P.key_nvalues)[k])) ok = false;
+        }
+        for (u32 r = 0; r < R && ok; ++r) if (((rmask >> r) & 1u) && GC(i64, V.o_req)[(size_t)j * R + r] > GC(i64, P.it_alloc)[(size_t)r * T + t]) ok = false;
+        if (ok) ok = (GC(u64, P.it_offer)[t] & pairs) != 0;
+      }
+      const u64 pass = __ballot(ok), have = GC(u64, V.n_types)[(size_t)j * TW + w];
+      extra |= have & ~pass; missing |= pass & ~have; any |= have;
+    }
+    if (!any) f |= KS_AUDIT_NODE_OPTIONS_EMPTY;
+    if (extra) f |= KS_AUDIT_NODE_OPTIONS_EXTRA;
+    if (missing && GC(u32, P.tmpl_limit_present)[m] == 0xFFFFFFFFu) f |= KS_AUDIT_NODE_OPTIONS_MISSING;      // (a limited template starts from an order-dependent subset, scheduler.go:199-208)
+    if (lane == 0) V.node_flags[s] = f;
+  }
+}
+
+// ---- host half ----
+// what the audit reads of a result: KS_RESULT_SEGS without the per-pod reasons
+#define KS_AUDIT_SEGS(X) \
+  X(pod_node, pod_node, i32, P) X(pod_stage, pod_stage, i32, P) X(pod_seq, pod_seq, i32, P) X(unscheduled, unscheduled, i32, P) \
+  X(n_tmpl, node_tmpl, i32, N) X(n_alive, node_types, u64, N * TW) X(o_req, node_requests, i64, N * R) X(o_reqmask, node_requests_present, u32, N) \
+  X(o_present, node_present, u32, N) X(o_complement, node_complement, u32, N) X(o_mask, node_mask, u64, N * K) X(o_gt, node_gt, i32, N * K) X(o_lt, node_lt, i32, N * K) \
+  X(o_it, node_it_state, i32, N)
+// every refusal about the out tables, then: scratch laid out and zeroed, four launches, one read-back of [meta | pod flags | node flags], the totals counted on the host
+static int audit_run(ks_dev_problem* const* ds, u32 n, const AuditView* results /* the result pointers of every problem */, ks_audit* const* outs) {
+  BatchStage st; TRY(st.open(ds, n, nullptr, false));
+  const size_t o_view = st.add<AuditView>(n);
+  TRY(st.place());
+  // one block of u32: [meta 2n | pod_flags of every problem | node_flags of every problem] (read back) then the scratch
+  std::vector<size_t> o_pf(n), o_nf(n); size_t at = 2 * (size_t)n; u32 pmax = 0, nsmax = 0;
+  for (u32 i = 0; i < n; ++i) { o_pf[i] = at; at += ds[i]->h.P; pmax = std::max(pmax, ds[i]->h.P); }
+  for (u32 i = 0; i < n; ++i) { o_nf[i] = at; at += (size_t)ds[i]->h.E + ds[i]->h.NMAX; nsmax = std::max(nsmax, ds[i]->h.E + ds[i]->h.NMAX); }
+  const size_t n_out = at;
+  std::vector<size_t> o_scr(n);
+  for (u32 i = 0; i < n; ++i) { o_scr[i] = at; at += 2 * (size_t)ds[i]->h.P + 3 * ((size_t)ds[i]->h.E + ds[i]->h.NMAX) + 1; }
+  TmpDev work(ds[0]->device); TRY(work.alloc(at * sizeof(u32)));
+  u32* w = work.as<u32>();
+  for (u32 i = 0; i < n; ++i) {
+    AuditView v = results[i]; const size_t Pn = ds[i]->h.P, NS = (size_t)ds[i]->h.E + ds[i]->h.NMAX;
+    v.meta = w + 2 * (size_t)i; v.pod_flags = w + o_pf[i]; v.node_flags = w + o_nf[i];
+    u32* s = w + o_scr[i]; v.mark = s; v.cnt = s + Pn; v.off = s + Pn + NS; v.fill = s + Pn + 2 * NS + 1; v.pods = s + Pn + 3 * NS + 1;
+    st.h<AuditView>(o_view)[i] = v;
+  }
+  const auto t0 = std::chrono::steady_clock::now();
+  TRY(st.upload(st.bytes));
+  HIPCHK(hipMemsetAsync(w, 0, at * sizeof(u32), st.stream()));
+  const u32 KS_GRID_Y_MAX = 65535u; const AuditView* dv = st.d<const AuditView>(o_view);
+  const u32 gx_p = std::max(1u, std::min(1024u, (pmax + 255u) / 256u)), gx_n = std::max(1u, std::min(4096u, (nsmax + 3u) / 4u));
+  for (u32 base = 0; base < n; base += KS_GRID_Y_MAX) {
+    const u32 ny = std::min(KS_GRID_Y_MAX, n - base);
+    hipLaunchKernelGGL(ks_audit_count, dim3(gx_p, ny), dim3(256), 0, st.stream(), st.probs() + base, dv + base);
+    hipLaunchKernelGGL(ks_audit_scan, dim3(ny), dim3(256), 0, st.stream(), st.probs() + base, dv + base);
+    hipLaunchKernelGGL(ks_audit_pods, dim3(gx_p, ny), dim3(256), 0, st.stream(), st.probs() + base, dv + base);
+    hipLaunchKernelGGL(ks_audit_nodes, dim3(gx_n, ny), dim3(256), 0, st.stream(), st.probs() + base, dv + base);
+  }
+  HIPCHK(hipStreamSynchronize(st.stream())); HIPCHK(hipGetLastError());
+  const auto t1 = std::chrono::steady_clock::now();
+  std::vector<u32> back(n_out);
+  HIPCHK(hipMemcpy(back.data(), w, n_out * sizeof(u32), hipMemcpyDeviceToHost));
+  for (u32 i = 0; i < n; ++i) {
+    ks_audit* o = outs[i]; const u32 Pn = ds[i]->h.P, NS = ds[i]->h.E + back[2 * (size_t)i];
+    o->n_pods = Pn; o->n_nodes = NS; o->n_new = back[2 * (size_t)i]; o->n_unscheduled = back[2 * (size_t)i + 1]; o->n_pods_flagged = 0; o->n_nodes_flagged = 0;
+    memset(o->pod_bit_count, 0, sizeof o->pod_bit_count); memset(o->node_bit_count, 0, sizeof o->node_bit_count);
+    const u32* pf = back.data() + o_pf[i]; const u32* nf = back.data() + o_nf[i];
+    for (u32 k = 0; k < Pn; ++k) if (pf[k]) { ++o->n_pods_flagged; for (u32 x = pf[k]; x; x &= x - 1) ++o->pod_bit_count[__builtin_ctz(x)]; }
+    for (u32 k = 0; k < NS; ++k) if (nf[k]) { ++o->n_nodes_flagged; for (u32 x = nf[k]; x; x &= x - 1) ++o->node_bit_count[__builtin_ctz(x)]; }
+    if (o->pod_flags && Pn) memcpy(o->pod_flags, pf, (size_t)Pn * sizeof(u32));
+    if (o->node_flags && NS) memcpy(o->node_flags, nf, (size_t)NS * sizeof(u32));
+    o->kernel_ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
+    o->readback_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
+  }
+  return KS_OK;
+}
+// the result a solve left on the device
+static AuditView audit_resident(const DevState& s) {
+  AuditView v{};
+  v.pod_node = s.pod_node; v.pod_stage = s.pod_stage; v.pod_seq = s.pod_seq; v.unscheduled = s.unscheduled; v.counts = s.out_counts;
+  v.n_tmpl = s.n_tmpl; v.n_types = s.n_alive; v.o_req = s.o_req; v.o_reqmask = s.o_reqmask; v.o_present = s.o_present; v.o_complement = s.o_complement;
+  v.o_mask = s.o_mask; v.o_gt = s.o_gt; v.o_lt = s.o_lt; v.o_it = s.o_it;
+  return v;
+}
+extern "C" int ks_audit_sizes(const ks_dev_problem* d, uint32_t* n_pods, uint32_t* n_node_slots) {
+  if (!d) return fail(KS_ERR_INVALID, "null argument");
+  if (n_pods) *n_pods = d->h.P;
+  if (n_node_slots) *n_node_slots = d->h.E + d->h.NMAX;
+  return KS_OK;
+}
+extern "C" int ks_audit_batch_dev(ks_dev_problem* const* ds, uint32_t n, ks_audit* const* outs) {
+  if (!n) return KS_OK;
+  if (!ds || !outs) return fail(KS_ERR_INVALID, "null argument");
+  TRY(BatchStage::not_null(ds, n));
+  std::vector<AuditView> res(n);
+  for (u32 i = 0; i < n; ++i) {
+    if (!outs[i]) return fail(KS_ERR_INVALID, "null audit table");
+    if (!ds[i]->solved) return fail(KS_ERR_INVALID, "audit of a problem that holds no result: solve it first (or the last solve failed)");
+    res[i] = audit_resident(ds[i]->hs);
+  }
+  return audit_run(ds, n, res.data(), outs);
+}
+extern "C" int ks_audit_dev(ks_dev_problem* d, const ks_result* claimed, ks_audit* out) {
+  if (!d || !out) return fail(KS_ERR_INVALID, "null argument");
+  if (!claimed) return ks_audit_batch_dev(&d, 1, &out);
+  if (d->view) return fail(KS_ERR_UNSUPPORTED, "a claimed result is audited against a flattened problem, not against a what-if derived on the device");
+  const DevProb& h = d->h; const u64 P = h.P, K = h.K, R = h.R, TW = h.TW, N = claimed->n_new;
+  if (N > h.NMAX) return fail(KS_ERR_INVALID, "claimed result: more new nodes than max_new_nodes");
+  if (claimed->n_unscheduled > P) return fail(KS_ERR_INVALID, "claimed result: more unscheduled pods than pods");
+#define X(sf, rf, T, cnt) if ((cnt) && !claimed->rf) return fail(KS_ERR_INVALID, "claimed result: null array " #rf);
+  KS_AUDIT_SEGS(X)
+#undef X
+  // the claimed arrays in one block, every piece 8-byte aligned, then the two counts: one transfer
+  size_t bytes = 0;
+#define X(sf, rf, T, cnt) bytes += ks_pad8((cnt) * sizeof(T));
+  KS_AUDIT_SEGS(X)
+#undef X
+  std::vector<u64> blob(bytes / 8 + 1, 0); u8* hb = (u8*)blob.data();
+  HIPCHK(hipSetDevice(d->device));
+  TmpDev up(d->device); TRY(up.alloc(bytes + 8)); u8* db = up.as<u8>();
+  DevState s{}; size_t at = 0;
+#define X(sf, rf, T, cnt) { const size_t b_ = (cnt) * sizeof(T); if (b_) memcpy(hb + at, claimed->rf, b_); s.sf = (T*)(db + at); at += ks_pad8(b_); }
+  KS_AUDIT_SEGS(X)
+#undef X
+  { u32 c2[2] = {claimed->n_new, claimed->n_unscheduled}; memcpy(hb + at, c2, 8); s.out_counts = (u32*)(db + at); }
+  HIPCHK(hipMemcpy(db, hb, bytes + 8, hipMemcpyHostToDevice));
+  const AuditView v = audit_resident(s);
+  return audit_run(&d, 1, &v, &out);
+}

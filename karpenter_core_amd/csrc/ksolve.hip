@@ -4390,6 +4390,8 @@ extern "C" int ks_placement_rows_host(ks_dev_problem* const* ds, uint32_t n, con
   return KS_OK;
 }
 
+#include "ks_audit.inc"      // the audit of a result against its problem (ks_audit_dev / ks_audit_batch_dev)
+
 // ------------------------------------------------------------------------------------------------
 // Consolidation candidates (ksolve.h ks_consolidation_candidates_host): which nodes sortAndFilterCandidates keeps, and in what order.
 //   ks_cand_pods   one lane per pod slot: GetPodEvictionCost (helpers.go:124-146), and the lowest-index PDB with disruptionsAllowed == 0 that matches the pod

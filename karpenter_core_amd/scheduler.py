@@ -33,6 +33,10 @@ KSH_DERIVE_VOLUMES = 1 << 16      # kshost.h: derive what-ifs over snapshots wit
 KSH_DERIVE_GROUP_LISTS = 1 << 18  # kshost.h: hold a derived what-if's per-node topology facts as lists per node -- any number of topology groups (opt-in)
 KSH_ACTIVE_RESOURCES = 1 << 17    # kshost.h: flatten over the resource names the problem requests or limits, not over all a catalogue lists (opt-in)
 KSH_APPLY_TRACK_CLUSTER_PODS = 1  # kshost.h: ksh_env_apply_block mirrors BIND / UNBIND into the cluster pods whatever the snapshot started with
+# ksolve.h KS_AUDIT_*: the bits of FlatProblem.audit() / audit_batch(), by name
+KS_AUDIT_POD_BITS = {"RANGE": 1, "UNSCHEDULED_LIST": 2, "TAINTS": 4, "REQUIREMENTS": 8, "HOSTNAME": 16, "PORTS": 32, "VOLUME_ERROR": 64}
+KS_AUDIT_NODE_BITS = {"RESOURCES": 1, "VOLUMES": 2, "EMPTY": 4, "TEMPLATE": 8, "REQUESTS": 16, "OPTIONS_EMPTY": 32, "OPTIONS_EXTRA": 64, "OPTIONS_MISSING": 128}
+KSH_AUDIT_TRUNCATED_PODS, KSH_AUDIT_TRUNCATED_NODES = 1, 2
 
 
 class KSolveError(RuntimeError):
@@ -309,9 +313,19 @@ class FlatProblem:
                 "unscheduled": arr(ra.unscheduled, ra.n_unscheduled, np.int32), "node_pods_off": off, "node_pods": arr(ra.node_pods, int(off[-1]) if len(off) else 0, np.int32),
                 "node_tmpl": arr(ra.node_tmpl, N, np.int32), "node_types": arr(ra.node_types, N * TW, np.uint64).reshape(N, TW), "node_requests": arr(ra.node_requests, N * R, np.int64).reshape(N, R),
                 "node_requests_present": arr(ra.node_requests_present, N, np.uint32), "node_present": arr(ra.node_present, N, np.uint32), "node_complement": arr(ra.node_complement, N, np.uint32),
-                "node_mask": arr(ra.node_mask, N * K, np.uint64).reshape(N, K),
+                "node_mask": arr(ra.node_mask, N * K, np.uint64).reshape(N, K), "node_gt": arr(ra.node_gt, N * K, np.int32).reshape(N, K), "node_lt": arr(ra.node_lt, N * K, np.int32).reshape(N, K),
+                "node_it_state": arr(ra.node_it_state, N, np.int32),
                 "key_names": [(kh.ksh_name(self._h, 0, k, 0) or b"").decode() for k in range(K)], "resource_names": [(kh.ksh_name(self._h, 2, r, 0) or b"").decode() for r in range(R)],
                 "key_value": lambda k, v: (kh.ksh_name(self._h, 1, k, v) or b"").decode()}
+
+    def audit(self, claimed: Optional[dict] = None) -> dict:
+        """Audit a result against this problem on the device (include/ksolve.h KS_AUDIT_*, kshost.h ksh_audit / ksh_audit_claimed).  Without `claimed`: the result the
+        last solve left on the device.  With `claimed`: a result in `result_arrays()`' form -- from anywhere -- is uploaded and audited instead (flattened problems
+        only).  Returns {"pod_flags": uint32 [P], "node_flags": uint32 [E + n_new], "n_pods_flagged", "n_nodes_flagged", "pod_bit_count", "node_bit_count" (by bit
+        name), "n_new", "n_unscheduled", "ms": (kernels, read-back)}; a clean result has no flag set."""
+        if claimed is None:
+            return audit_batch([self])[0]
+        return _audit_call([self], claimed)[0]
 
     def result(self) -> SolveResult:
         """Decode the result the handle holds (after `solve(decode=False)` or `solve_from_pods`)."""
@@ -724,6 +738,74 @@ def solve_batch(flats: Sequence[FlatProblem], decode: bool = True):
             res.append(parse_result(ctypes.string_at(outs[i]).decode()))
             kh.ksh_free(outs[i])
     return res, float(kms.value), float(wms.value)
+
+
+class _AuditOut(ctypes.Structure):      # include/kshost.h ksh_audit_out
+    _fields_ = [("pod_flags", ctypes.c_void_p), ("cap_pods", ctypes.c_uint64), ("node_flags", ctypes.c_void_p), ("cap_nodes", ctypes.c_uint64)] + \
+               [(n, ctypes.c_uint32) for n in ("n_pods", "n_nodes", "n_new", "n_unscheduled", "n_pods_flagged", "n_nodes_flagged", "truncated", "pad")] + \
+               [("pod_bit_count", ctypes.c_uint32 * 32), ("node_bit_count", ctypes.c_uint32 * 32)]
+
+
+class _ResultArrays(ctypes.Structure):      # include/kshost.h ksh_result_arrays
+    _fields_ = [(n, ctypes.c_uint32) for n in ("n_pods", "n_existing", "n_new", "n_unscheduled", "types_words", "n_resources", "n_keys", "pad")] + \
+               [(n, ctypes.c_void_p) for n in ("pod_node", "pod_stage", "pod_reason", "unscheduled", "node_pods_off", "node_pods", "node_tmpl", "node_types", "node_requests",
+                                               "node_requests_present", "node_present", "node_complement", "node_mask", "node_gt", "node_lt", "node_it_state")]
+
+
+def _audit_call(flats: Sequence["FlatProblem"], claimed: Optional[dict] = None) -> List[dict]:
+    import numpy as np
+    kh = libs()[1]
+    n = len(flats)
+    if not n:
+        return []
+    kh.ksh_audit.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32, ctypes.POINTER(_AuditOut), ctypes.POINTER(ctypes.c_double)]
+    kh.ksh_audit_claimed.argtypes = [ctypes.c_void_p, ctypes.POINTER(_ResultArrays), ctypes.POINTER(_AuditOut), ctypes.POINTER(ctypes.c_double)]
+    hs = (ctypes.c_void_p * n)(*[f._h for f in flats])
+    outs = (_AuditOut * n)()
+    ms = (ctypes.c_double * 2)()
+    keep = []
+    ra = None
+    if claimed is not None:
+        d = flats[0].dims
+        ra = _ResultArrays()
+        N = int(claimed["n_new"])
+        ra.n_pods, ra.n_existing, ra.n_new, ra.n_unscheduled = d["P"], d["E"], N, len(claimed["unscheduled"])
+        ra.types_words, ra.n_resources, ra.n_keys = (d["T"] + 63) // 64, d["R"], d["K"]
+        for name, dt in (("pod_node", np.int32), ("pod_stage", np.int32), ("unscheduled", np.int32), ("node_tmpl", np.int32), ("node_types", np.uint64), ("node_requests", np.int64),
+                         ("node_requests_present", np.uint32), ("node_present", np.uint32), ("node_complement", np.uint32), ("node_mask", np.uint64), ("node_gt", np.int32),
+                         ("node_lt", np.int32), ("node_it_state", np.int32)):
+            a = np.ascontiguousarray(np.asarray(claimed[name], dtype=dt).reshape(-1))
+            if not len(a):
+                a = np.zeros(1, dtype=dt)      # (a table of no elements is still a table: never NULL)
+            keep.append(a)
+            setattr(ra, name, a.ctypes.data)
+
+    def call(caps):
+        tabs = []
+        for i, (cp, cn) in enumerate(caps):
+            pf, nf = np.zeros(max(1, cp), dtype=np.uint32), np.zeros(max(1, cn), dtype=np.uint32)
+            tabs.append((pf, nf))
+            outs[i].pod_flags, outs[i].cap_pods, outs[i].node_flags, outs[i].cap_nodes = pf.ctypes.data, cp, nf.ctypes.data, cn
+        rc = kh.ksh_audit(hs, n, outs, ms) if ra is None else kh.ksh_audit_claimed(flats[0]._h, ctypes.byref(ra), outs, ms)
+        if rc != KS_OK:
+            raise KSolveError(rc, kh.ksh_last_error().decode())
+        return tabs
+    tabs = call([(f.dims["P"], f.dims["E"] + f.dims["P"]) for f in flats])
+    if any(o.truncated for o in outs):      # (a table was too short -- a what-if derived on the device states its own sizes only here: once more, with what the totals say)
+        tabs = call([(o.n_pods, o.n_nodes) for o in outs])
+    res = []
+    for i, o in enumerate(outs):
+        res.append({"pod_flags": tabs[i][0][:o.n_pods].copy(), "node_flags": tabs[i][1][:o.n_nodes].copy(), "n_pods_flagged": int(o.n_pods_flagged), "n_nodes_flagged": int(o.n_nodes_flagged),
+                    "pod_bit_count": {k: int(o.pod_bit_count[v.bit_length() - 1]) for k, v in KS_AUDIT_POD_BITS.items()},
+                    "node_bit_count": {k: int(o.node_bit_count[v.bit_length() - 1]) for k, v in KS_AUDIT_NODE_BITS.items()},
+                    "n_new": int(o.n_new), "n_unscheduled": int(o.n_unscheduled), "ms": (float(ms[0]), float(ms[1]))})
+    return res
+
+
+def audit_batch(flats: Sequence["FlatProblem"]) -> List[dict]:
+    """Audit the results the last solve left on the device, for a whole batch in one launch sequence (include/kshost.h ksh_audit): handles of any kind whose results
+    are there -- a Solve, what-ifs flattened one by one, what-ifs derived on the device.  One dict per problem, as `FlatProblem.audit` returns it."""
+    return _audit_call(flats)
 
 
 def deal_lpt(weights: Sequence[int], nshards: int) -> List[int]:
