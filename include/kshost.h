@@ -553,6 +553,21 @@ int ksh_audit(void** handles, uint32_t n, ksh_audit_out* outs /* [n] */, double*
  * node_pods_off / node_pods and pod_reason are not read; ksh_result_arrays carries no commit numbers, so the pod_seq clause of KS_AUDIT_POD_RANGE is ks_audit_dev's alone.
  * KS_ERR_INVALID: a NULL table, dimensions that are not the handle's, n_new > max_new_nodes. */
 int ksh_audit_claimed(void* handle, const ksh_result_arrays* claimed, ksh_audit_out* out, double* ms /* [2] or NULL */);
+/* The audit's SECOND pass, opt-in (ksolve.h ks_audit_topology_dev, KS_AUDIT_POD_SEQ .. KS_AUDIT_POD_HOSTNAME_SPREAD): pod (anti-)affinity and hostname spread, decided
+ * from the final state and the commit numbers.  The shim's gate is both passes: ksh_audit, then this, and on a finding of either, solve in Go.  The same conventions:
+ * the totals always, pod_flags when cap_pods >= n_pods (else KSH_AUDIT_TRUNCATED_PODS), indices as ksh_audit's.  checked[] says what each rule evaluated -- [0] placed
+ * pods whose commit number was examined, [1] anti-affinity, [2] affinity, [3] hostname spread (pod, group) pairs --, skipped_groups the groups no rule looked at. */
+typedef struct ksh_audit_topology_out {
+  uint32_t* pod_flags; uint64_t cap_pods;      /* [cap_pods] KS_AUDIT_POD_SEQ .. */
+  uint32_t n_pods, n_new, n_placed, skipped_groups;
+  uint32_t n_pods_flagged, truncated /* KSH_AUDIT_TRUNCATED_PODS */;
+  uint32_t checked[4];
+  uint32_t pod_bit_count[32];
+} ksh_audit_topology_out;
+int ksh_audit_topology(void** handles, uint32_t n, ksh_audit_topology_out* outs /* [n] */, double* ms /* [2] kernels | read-back, or NULL */);
+/* A claimed result for one flattened handle, as ksh_audit_claimed -- with the commit numbers as an array of their own, [n_pods] (KS_PLC_STAGE_SEQ's high half for a
+ * placed pod, -1 for an unscheduled one), because ksh_result_arrays carries none.  KS_ERR_INVALID: pod_seq NULL, and ksh_audit_claimed's refusals. */
+int ksh_audit_topology_claimed(void* handle, const ksh_result_arrays* claimed, const int32_t* pod_seq /* [n_pods] */, ksh_audit_topology_out* out, double* ms /* [2] or NULL */);
 
 /* ---- the snapshot kept current by EVENTS ("cached incremental SoA builder fed from state.Cluster") ----
  * Replaces, for the snapshot consolidation simulates over, what the reference does between two passes of the deprovisioner (deprovisioning/controller.go:64,

@@ -689,8 +689,10 @@ int ks_placement_rows_host(ks_dev_problem* const* ds, uint32_t n, const uint64_t
 #define KS_AUDIT_NODE_OPTIONS_EMPTY 32u   /* the node has no option */
 #define KS_AUDIT_NODE_OPTIONS_EXTRA 64u   /* a set bit names a type outside T, outside tmpl_types[m], outside its_types[node_it_state], or one that fails compatible && fits && hasOffering (node.go:137-159) against the node's final requirements and requests */
 #define KS_AUDIT_NODE_OPTIONS_MISSING 128u /* only for templates with tmpl_limit_present == 0xFFFFFFFF: a type that passes all of that is not set.  The filter is monotone -- requirements only narrow, requests only grow -- so the incremental filtering of node.go:94 equals one filtering by the final state; a limited template starts from an order-dependent subset (scheduler.go:199-208) and gets OPTIONS_EXTRA only */
-/* Deliberately NOT audited: topology skew and affinity (they hold at the moment of placement, not at the end), provisioner limits (subtractMax depends on the order),
- * first-fit optimality (whether an earlier node would have taken the pod).
+/* NOT audited by this pass: anything about topology -- skew and affinity hold at the moment of placement, not at the end.  The part of them that the final state
+ * decides together with the commit numbers is the second, opt-in pass below (ks_audit_topology_dev: pod (anti-)affinity, hostname spread).  Audited by neither:
+ * spread over narrow keys, hostname spread under a node filter, self-selecting affinity, groups created by a later Topology.Update, provisioner limits (subtractMax
+ * depends on the order), first-fit optimality (whether an earlier node would have taken the pod).
  * The caller owns the tables: pod_flags [P] and node_flags [E + max_new_nodes] (of which E + n_new are written), either may be NULL (totals only).  Flags are written
  * per index -- no list is appended through an atomic -- so the output is the same every run. */
 typedef struct ks_audit {
@@ -710,6 +712,42 @@ typedef struct ks_audit {
 int ks_audit_dev(ks_dev_problem* d, const ks_result* claimed /* or NULL */, ks_audit* out);
 int ks_audit_batch_dev(ks_dev_problem* const* ds, uint32_t n, ks_audit* const* outs);
 int ks_audit_sizes(const ks_dev_problem* d, uint32_t* n_pods /* P */, uint32_t* n_node_slots /* E + max_new_nodes */);   /* what the two tables of `d` must hold (a derived what-if has no ks_problem to read them from); either may be NULL */
+
+/* ---- the audit's SECOND pass, opt-in: pod (anti-)affinity and hostname spread in COMMIT ORDER.  Nothing calls it unless asked; ks_audit_dev is unchanged by it.
+ * The final state together with pod_seq decides these constraints one-sidedly, because a group's domain counts only grow (topologygroup.go:101-105) and a node's
+ * requirements only narrow (node.go:80,90,103): every bit below flags only what no run of the reference can have produced.  The bits are a word of their own
+ * (ks_audit_topology.pod_flags[p]), numbered on from the pod bits.
+ * Definitions.  A pod's class is the one of the stage it ended at.  Group g CONSTRAINS pod P when g is in own_list (bit 31: selfSelecting) or isel_list of P's class;
+ * g is RECORDED BY pod Q when g is in sel_list or iown_list of Q's class.  Groups with grp_active == 0 (created by a later Topology.Update: they never saw the earlier
+ * commits) are skipped and counted in skipped_groups.  init = grp_count / grph_count as the pack kernels start from them (a derived what-if: its own tables).
+ * Hostname-keyed groups are exact (a node is one domain): for P on node n, before = the pods Q != P on n that record g with seq(Q) < seq(P), c = init[g][n] (0 on a
+ * new node).  Narrow-key groups of type 1 / 2: dom(n, k) = node n's final requirement on k as an In-set (an existing node's label; a new node's node_mask when the key
+ * is present and no complement); a recorder is CERTAIN for k when its node was concrete on k at its own commit whatever happened later: an existing node with the
+ * label, a template or a class with an In-set on k, or a group on k that constrains the recorder (topology.go:160-164). */
+#define KS_AUDIT_POD_SEQ 128u               /* the pod_seq of the placed pods are not pairwise distinct and below their number: every pod of a collision, every pod out of range.  The other rules treat such a pod as unplaced */
+#define KS_AUDIT_POD_ANTI_AFFINITY 256u     /* type 2, inverse groups included.  Hostname: c + before > 0.  Narrow key: for some d in dom(node(P), k), init[g][d] > 0 or a CERTAIN recorder Q != P with seq(Q) < seq(P) has d in dom(node(Q), k) (Q on P's own node counts) */
+#define KS_AUDIT_POD_AFFINITY 512u          /* type 1, P not selfSelecting (the bootstrap branch, topologygroup.go:212-231, cannot be told from a violation).  Hostname: c + before == 0.  Narrow key: for some d in dom(node(P), k), init[g][d] <= 0 and no recorder Q != P, certain or not, with seq(Q) < seq(P) Has d in node(Q)'s final requirement on k (an absent key has every value) */
+#define KS_AUDIT_POD_HOSTNAME_SPREAD 1024u  /* type 0 on the hostname with an empty node filter -- no term in grp_filter_off, or a term that requires nothing (present == 0, it_state == 0: what MakeTopologyNodeFilter gives a pod without node selectors, topologynodefilter.go:30-70) --: c + before + (selfSelecting ? 1 : 0) > grp_max_skew[g] (domainMinCount is 0 for the hostname, topologygroup.go:186) */
+/* A pod constrained by a narrow-key group of type 1 / 2 whose own node is not concrete on the key carries the group's bit -- except on an existing node that lacks a
+ * well-known label: such a node is Compatible with any requirement on it (requirements.go:123-133) and keeps its labels here, so the pair is not examined.
+ * NOT attempted: spread over narrow keys (the chosen domain depends on a minimum at the time), hostname spread under a node filter (Counts depends on the node's
+ * requirements at the time), self-selecting affinity, late-created groups, provisioner limits, first-fit optimality. */
+typedef struct ks_audit_topology {
+  uint32_t* pod_flags;            /* [P] KS_AUDIT_POD_SEQ .. KS_AUDIT_POD_HOSTNAME_SPREAD, or NULL (totals only) */
+  uint32_t n_pods, n_new;         /* out: P | the new nodes of the result that was audited */
+  uint32_t n_placed;              /* out: pods on a node of the result */
+  uint32_t skipped_groups;        /* out: groups no rule examined (grp_active == 0, or absent from a derived what-if) */
+  uint32_t n_pods_flagged;
+  uint32_t pod_bit_count[32];     /* out: pods carrying bit i */
+  uint32_t checked[4];            /* out: what each rule actually evaluated -- [0] SEQ: placed pods; [1] ANTI_AFFINITY, [2] AFFINITY, [3] HOSTNAME_SPREAD: (pod, group) pairs.  A clean result with checked[i] == 0 was clean vacuously */
+  double kernel_ms, readback_ms;  /* out: as ks_audit's */
+} ks_audit_topology;
+/* claimed == NULL: the resident result, where it lies (the form for derived what-ifs).  claimed given (flattened problems only, KS_ERR_UNSUPPORTED for a derived
+ * view): pod_node, pod_stage, pod_seq, node_tmpl and the new nodes' requirement arrays are uploaded and read; every index is range-checked before it addresses
+ * memory.  The batch form walks its problems in slices of at most 64 MiB of its per-group scratch table (G x 64 words per problem), five launches per slice.
+ * Flags are written per index, no output through an atomic: the same flags every run.  Refusals as ks_audit_dev's. */
+int ks_audit_topology_dev(ks_dev_problem* d, const ks_result* claimed /* or NULL; pod_seq is read */, ks_audit_topology* out);
+int ks_audit_topology_batch_dev(ks_dev_problem* const* ds, uint32_t n, ks_audit_topology* const* outs);
 
 /* ---- consolidation CANDIDATES, selected and ordered on the device (deprovisioning/helpers.go:124-165,275-287 GetPodEvictionCost / disruptionCost /
  * calculateLifetimeRemaining, pdblimits.go:57-70 CanEvictPods, helpers.go:339-366 canBeTerminated / PodsPreventEviction, consolidation.go:83-104 the sort).

@@ -37,6 +37,9 @@ KSH_APPLY_TRACK_CLUSTER_PODS = 1  # kshost.h: ksh_env_apply_block mirrors BIND /
 KS_AUDIT_POD_BITS = {"RANGE": 1, "UNSCHEDULED_LIST": 2, "TAINTS": 4, "REQUIREMENTS": 8, "HOSTNAME": 16, "PORTS": 32, "VOLUME_ERROR": 64}
 KS_AUDIT_NODE_BITS = {"RESOURCES": 1, "VOLUMES": 2, "EMPTY": 4, "TEMPLATE": 8, "REQUESTS": 16, "OPTIONS_EMPTY": 32, "OPTIONS_EXTRA": 64, "OPTIONS_MISSING": 128}
 KSH_AUDIT_TRUNCATED_PODS, KSH_AUDIT_TRUNCATED_NODES = 1, 2
+# the second pass's bits (FlatProblem.audit_topology() / audit_topology_batch()), a word of their own, and what `checked` counts per rule
+KS_AUDIT_TOPOLOGY_BITS = {"SEQ": 128, "ANTI_AFFINITY": 256, "AFFINITY": 512, "HOSTNAME_SPREAD": 1024}
+KS_AUDIT_TOPOLOGY_RULES = ("SEQ", "ANTI_AFFINITY", "AFFINITY", "HOSTNAME_SPREAD")
 
 
 class KSolveError(RuntimeError):
@@ -326,6 +329,27 @@ class FlatProblem:
         if claimed is None:
             return audit_batch([self])[0]
         return _audit_call([self], claimed)[0]
+
+    def pod_seq(self):
+        """The commit numbers of the result on the device, int32 [P] by pod index (-1: unscheduled), read through `ksh_placement_rows` (KS_PLC_STAGE_SEQ).  For a
+        Solve's handle: the rows of a what-if over a snapshot name the snapshot's pods, not the what-if's own (`placement_rows`)."""
+        import numpy as np
+        heads, rows, _ = placement_rows([self], [0])
+        seq = np.full(int(heads[0][KS_PLC_P]), -1, dtype=np.int32)
+        if rows is not None and len(seq):
+            seq[(rows[:, KS_PLC_POD_WHERE] & np.uint64(0xFFFFFFFF)).astype(np.int64)] = (rows[:, KS_PLC_STAGE_SEQ] >> np.uint64(32)).astype(np.uint32).view(np.int32)
+        return seq
+
+    def audit_topology(self, claimed: Optional[dict] = None, pod_seq=None) -> dict:
+        """The audit's second, opt-in pass (include/ksolve.h KS_AUDIT_POD_SEQ .., kshost.h ksh_audit_topology / ksh_audit_topology_claimed): pod (anti-)affinity and hostname
+        spread, decided from the final state and the commit numbers.  Without `claimed`: the result on the device.  With `claimed` (a result in `result_arrays()`' form)
+        and `pod_seq` (int32 [P], as `pod_seq()` returns it): those are uploaded and audited instead (flattened problems only).  Returns {"pod_flags": uint32 [P],
+        "n_pods_flagged", "pod_bit_count" and "checked" (by rule name), "skipped_groups", "n_new", "n_placed", "ms"}."""
+        if claimed is None:
+            if pod_seq is not None:
+                raise ValueError("audit_topology: pod_seq goes with a claimed result")
+            return audit_topology_batch([self])[0]
+        return _audit_topology_call([self], claimed, pod_seq)[0]
 
     def result(self) -> SolveResult:
         """Decode the result the handle holds (after `solve(decode=False)` or `solve_from_pods`)."""
@@ -806,6 +830,69 @@ def audit_batch(flats: Sequence["FlatProblem"]) -> List[dict]:
     """Audit the results the last solve left on the device, for a whole batch in one launch sequence (include/kshost.h ksh_audit): handles of any kind whose results
     are there -- a Solve, what-ifs flattened one by one, what-ifs derived on the device.  One dict per problem, as `FlatProblem.audit` returns it."""
     return _audit_call(flats)
+
+
+class _AuditTopologyOut(ctypes.Structure):      # include/kshost.h ksh_audit_topology_out
+    _fields_ = [("pod_flags", ctypes.c_void_p), ("cap_pods", ctypes.c_uint64)] + \
+               [(n, ctypes.c_uint32) for n in ("n_pods", "n_new", "n_placed", "skipped_groups", "n_pods_flagged", "truncated")] + \
+               [("checked", ctypes.c_uint32 * 4), ("pod_bit_count", ctypes.c_uint32 * 32)]
+
+
+def _audit_topology_call(flats: Sequence["FlatProblem"], claimed: Optional[dict] = None, pod_seq=None) -> List[dict]:
+    import numpy as np
+    kh = libs()[1]
+    n = len(flats)
+    if not n:
+        return []
+    kh.ksh_audit_topology.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32, ctypes.POINTER(_AuditTopologyOut), ctypes.POINTER(ctypes.c_double)]
+    kh.ksh_audit_topology_claimed.argtypes = [ctypes.c_void_p, ctypes.POINTER(_ResultArrays), ctypes.c_void_p, ctypes.POINTER(_AuditTopologyOut), ctypes.POINTER(ctypes.c_double)]
+    hs = (ctypes.c_void_p * n)(*[f._h for f in flats])
+    outs = (_AuditTopologyOut * n)()
+    ms = (ctypes.c_double * 2)()
+    keep = []
+    ra = seq = None
+    if claimed is not None:
+        d = flats[0].dims
+        ra = _ResultArrays()
+        ra.n_pods, ra.n_existing, ra.n_new, ra.n_unscheduled = d["P"], d["E"], int(claimed["n_new"]), len(claimed["unscheduled"])
+        ra.types_words, ra.n_resources, ra.n_keys = (d["T"] + 63) // 64, d["R"], d["K"]
+        for name, dt in (("pod_node", np.int32), ("pod_stage", np.int32), ("node_tmpl", np.int32), ("node_present", np.uint32), ("node_complement", np.uint32),
+                         ("node_mask", np.uint64), ("node_gt", np.int32), ("node_lt", np.int32)):
+            a = np.ascontiguousarray(np.asarray(claimed[name], dtype=dt).reshape(-1))
+            if not len(a):
+                a = np.zeros(1, dtype=dt)      # (a table of no elements is still a table: never NULL)
+            keep.append(a)
+            setattr(ra, name, a.ctypes.data)
+        if pod_seq is not None:
+            seq = np.ascontiguousarray(np.asarray(pod_seq, dtype=np.int32).reshape(-1))
+            if len(seq) != d["P"]:
+                raise ValueError("audit_topology: pod_seq holds one commit number per pod")
+            if not len(seq):
+                seq = np.zeros(1, dtype=np.int32)
+
+    def call(caps):
+        tabs = []
+        for i, cp in enumerate(caps):
+            pf = np.zeros(max(1, cp), dtype=np.uint32)
+            tabs.append(pf)
+            outs[i].pod_flags, outs[i].cap_pods = pf.ctypes.data, cp
+        rc = kh.ksh_audit_topology(hs, n, outs, ms) if ra is None else kh.ksh_audit_topology_claimed(flats[0]._h, ctypes.byref(ra), seq.ctypes.data if seq is not None else None, outs, ms)
+        if rc != KS_OK:
+            raise KSolveError(rc, kh.ksh_last_error().decode())
+        return tabs
+    tabs = call([f.dims["P"] for f in flats])
+    if any(o.truncated for o in outs):      # (a what-if derived on the device states its own sizes only here: once more, with what the totals say)
+        tabs = call([o.n_pods for o in outs])
+    return [{"pod_flags": tabs[i][:o.n_pods].copy(), "n_pods_flagged": int(o.n_pods_flagged),
+             "pod_bit_count": {k: int(o.pod_bit_count[v.bit_length() - 1]) for k, v in KS_AUDIT_TOPOLOGY_BITS.items()},
+             "checked": {k: int(o.checked[j]) for j, k in enumerate(KS_AUDIT_TOPOLOGY_RULES)}, "skipped_groups": int(o.skipped_groups),
+             "n_new": int(o.n_new), "n_placed": int(o.n_placed), "ms": (float(ms[0]), float(ms[1]))} for i, o in enumerate(outs)]
+
+
+def audit_topology_batch(flats: Sequence["FlatProblem"]) -> List[dict]:
+    """The audit's second pass over the results the last solve left on the device, for a whole batch (include/kshost.h ksh_audit_topology): handles of any kind, derived
+    what-ifs included.  One dict per problem, as `FlatProblem.audit_topology` returns it."""
+    return _audit_topology_call(flats)
 
 
 def deal_lpt(weights: Sequence[int], nshards: int) -> List[int]:
