@@ -568,6 +568,20 @@ int ksh_audit_topology(void** handles, uint32_t n, ksh_audit_topology_out* outs 
 /* A claimed result for one flattened handle, as ksh_audit_claimed -- with the commit numbers as an array of their own, [n_pods] (KS_PLC_STAGE_SEQ's high half for a
  * placed pod, -1 for an unscheduled one), because ksh_result_arrays carries none.  KS_ERR_INVALID: pod_seq NULL, and ksh_audit_claimed's refusals. */
 int ksh_audit_topology_claimed(void* handle, const ksh_result_arrays* claimed, const int32_t* pod_seq /* [n_pods] */, ksh_audit_topology_out* out, double* ms /* [2] or NULL */);
+/* The audit's THIRD pass, opt-in (ksolve.h ks_audit_spread_dev, KS_AUDIT_POD_SPREAD): topology spread over narrow keys -- the zone -- decided from the final state and
+ * the commit numbers.  The shim's gate is the three passes in order: ksh_audit, ksh_audit_topology, then this, and on a finding of any, solve in Go.  The second
+ * pass's conventions: the totals always, pod_flags when cap_pods >= n_pods (else KSH_AUDIT_TRUNCATED_PODS), indices as ksh_audit's.  checked[0]: the placed pods;
+ * checked[1]: the (pod, group) pairs examined; exact_pairs: those for which the rule was the reference's own test; skipped_groups: the spread groups left unattempted. */
+typedef struct ksh_audit_spread_out {
+  uint32_t* pod_flags; uint64_t cap_pods;      /* [cap_pods] KS_AUDIT_POD_SEQ | KS_AUDIT_POD_SPREAD */
+  uint32_t n_pods, n_new, n_placed, skipped_groups;
+  uint32_t n_pods_flagged, truncated /* KSH_AUDIT_TRUNCATED_PODS */;
+  uint32_t checked[2];
+  uint32_t exact_pairs, pad;
+} ksh_audit_spread_out;
+int ksh_audit_spread(void** handles, uint32_t n, ksh_audit_spread_out* outs /* [n] */, double* ms /* [2] kernels | read-back, or NULL */);
+/* A claimed result for one flattened handle, exactly as ksh_audit_topology_claimed takes it. */
+int ksh_audit_spread_claimed(void* handle, const ksh_result_arrays* claimed, const int32_t* pod_seq /* [n_pods] */, ksh_audit_spread_out* out, double* ms /* [2] or NULL */);
 
 /* ---- the snapshot kept current by EVENTS ("cached incremental SoA builder fed from state.Cluster") ----
  * Replaces, for the snapshot consolidation simulates over, what the reference does between two passes of the deprovisioner (deprovisioning/controller.go:64,

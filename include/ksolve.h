@@ -692,7 +692,8 @@ int ks_placement_rows_host(ks_dev_problem* const* ds, uint32_t n, const uint64_t
 /* NOT audited by this pass: anything about topology -- skew and affinity hold at the moment of placement, not at the end.  The part of them that the final state
  * decides together with the commit numbers is the second, opt-in pass below (ks_audit_topology_dev: pod (anti-)affinity, hostname spread).  Audited by neither:
  * spread over narrow keys, hostname spread under a node filter, self-selecting affinity, groups created by a later Topology.Update, provisioner limits (subtractMax
- * depends on the order), first-fit optimality (whether an earlier node would have taken the pod).
+ * depends on the order), first-fit optimality (whether an earlier node would have taken the pod).  (Spread over narrow keys, unfiltered, is now the third pass's:
+ * ks_audit_spread_dev.)
  * The caller owns the tables: pod_flags [P] and node_flags [E + max_new_nodes] (of which E + n_new are written), either may be NULL (totals only).  Flags are written
  * per index -- no list is appended through an atomic -- so the output is the same every run. */
 typedef struct ks_audit {
@@ -731,7 +732,8 @@ int ks_audit_sizes(const ks_dev_problem* d, uint32_t* n_pods /* P */, uint32_t* 
 /* A pod constrained by a narrow-key group of type 1 / 2 whose own node is not concrete on the key carries the group's bit -- except on an existing node that lacks a
  * well-known label: such a node is Compatible with any requirement on it (requirements.go:123-133) and keeps its labels here, so the pair is not examined.
  * NOT attempted: spread over narrow keys (the chosen domain depends on a minimum at the time), hostname spread under a node filter (Counts depends on the node's
- * requirements at the time), self-selecting affinity, late-created groups, provisioner limits, first-fit optimality. */
+ * requirements at the time), self-selecting affinity, late-created groups, provisioner limits, first-fit optimality.  (Spread over narrow keys is now the third
+ * pass's, ks_audit_spread_dev below: the minimum at the time is a prefix count over the commit order.) */
 typedef struct ks_audit_topology {
   uint32_t* pod_flags;            /* [P] KS_AUDIT_POD_SEQ .. KS_AUDIT_POD_HOSTNAME_SPREAD, or NULL (totals only) */
   uint32_t n_pods, n_new;         /* out: P | the new nodes of the result that was audited */
@@ -748,6 +750,53 @@ typedef struct ks_audit_topology {
  * Flags are written per index, no output through an atomic: the same flags every run.  Refusals as ks_audit_dev's. */
 int ks_audit_topology_dev(ks_dev_problem* d, const ks_result* claimed /* or NULL; pod_seq is read */, ks_audit_topology* out);
 int ks_audit_topology_batch_dev(ks_dev_problem* const* ds, uint32_t n, ks_audit_topology* const* outs);
+
+/* ---- the audit's THIRD pass, opt-in: topology spread over NARROW keys (the zone) in COMMIT ORDER.  Nothing calls it unless asked; the first two passes are
+ * unchanged by it.  "The minimum at the time" of nextDomainTopologySpread (topologygroup.go:159-200) is a prefix count over the commit order, and both monotonicities
+ * above apply, so the skew inequality of topologygroup.go:171 can be tested one-sidedly: a LOWER bound of the chosen domain's count against an UPPER bound of the
+ * minimum.  It flags only what no run of the reference can have produced, and it is the reference's own test wherever every recorder sits on a node that was already
+ * pinned to one domain (a consolidation what-if: existing nodes with their zone label) -- exact_pairs counts those.  The bit shares its word with KS_AUDIT_POD_SEQ,
+ * defined as in the second pass; a pod that fails SEQ counts as unplaced here.
+ * ELIGIBLE group g: grp_type == 0, narrow key 0 <= k < K, not skipped (grp_active == 0, or absent from a derived what-if) and an empty node filter, both by the
+ * second pass's definitions.  Every other spread group is unattempted and counted in skipped_groups.  init[e] = grp_count[g*64+e] (a derived what-if: its own
+ * table); init[e] < 0: domain e is not registered.
+ * RECORDER Q of g: g is in sel_list of Q's class (Counts() reduces to selects for an unfiltered group, topologygroup.go:109-111; Record counts a spread only when
+ * Len() == 1, topology.go:129-132).  fd(Q): the final In-set of node(Q) on k (dom(n, k) above).
+ * PIN TIME: pin[n][k] = the least pod_seq over the pods on node n whose class has an In-requirement on k with exactly one value, or a type-0 group on key k in its
+ * own_list (any such group, filtered or skipped included: an owned group exists from the pod's own Topology.Update on, nextDomainTopologySpread returns one domain,
+ * topologygroup.go:181, and node.go:80 / existingnode.go:110 add the pod's own requirement before Record).  From that commit on the node's requirement on k is a
+ * single value, because requirements only narrow.
+ * Q is CERTAIN when node(Q) is an existing node with the label, or its template has a single-value In on k, or pin[node(Q)][k] <= seq(Q).  Q is WILD when node(Q)
+ * is an existing node whose requirement on k is absent: the reference may have pinned such a node through an earlier pod (existingnode.go:110-125), and the flat
+ * problem keeps only its labels.
+ * COUNTS at commit number s, per registered domain e:  L_s[e] = max(0, init[e]) + the certain Q with seq(Q) < s and fd(Q) == {e};  U_s[e] = max(0, init[e]) + the
+ * Q, certain or not, with seq(Q) < s and fd(Q) == {e};  W_s = the wild Q with seq(Q) < s.  The true count lies in [L_s[e], U_s[e] + W_s]: whatever was recorded was
+ * a single value, and that value is still the whole final set.
+ * THE TEST for pod P (seq s, class c) and each eligible g in own_list of c (bit 31: self):
+ *   1. mine = fd(P).  Absent on an existing node without a well-known label k: the pair is not examined (the second pass's exception).  Absent on any other node:
+ *      flag.  popcount(mine) != 1: flag.  Else mine = {d}.
+ *   2. init[d] < 0: flag.
+ *   3. L_s[d] + self - min_e (U_s[e] + W_s) > grp_max_skew[g]: flag.  The minimum runs over the registered e that podDomains.Has: class c's requirement on k
+ *      (kreq_has_mask), or every value when the class has none (topology.go:152-155, topologygroup.go:184-200); over no e it is INT32_MAX and nothing is flagged.
+ * Only the skew inequality: whether d was the arg-min among the node's domains is first-fit optimality, which stays unattempted. */
+#define KS_AUDIT_POD_SPREAD 2048u           /* a placed pod fails step 1, 2 or 3 above for some eligible group that constrains it */
+typedef struct ks_audit_spread {
+  uint32_t* pod_flags;            /* [P] KS_AUDIT_POD_SEQ | KS_AUDIT_POD_SPREAD, or NULL (totals only) */
+  uint32_t n_pods, n_new;         /* out: P | the new nodes of the result that was audited */
+  uint32_t n_placed;              /* out: pods on a node of the result */
+  uint32_t skipped_groups;        /* out: spread groups (grp_type == 0) that are not eligible: unattempted */
+  uint32_t n_pods_flagged;
+  uint32_t checked[2];            /* out: [0] the placed pods (SEQ); [1] the (pod, group) pairs examined.  A clean result with checked[1] == 0 was clean vacuously */
+  uint32_t exact_pairs;           /* out: the pairs that reached step 3 with W_s == 0 and L_s[e] == U_s[e] on d and on every e of the minimum: there the rule is the reference's own test */
+  double kernel_ms, readback_ms;  /* out: as ks_audit's */
+} ks_audit_spread;
+/* claimed == NULL: the resident result, where it lies (the form for derived what-ifs).  claimed given (flattened problems only, KS_ERR_UNSUPPORTED for a derived
+ * view): the second pass's arrays are uploaded and read; every index a result supplies is range-checked before it addresses memory.  Five launches; the commit
+ * order is cut into chunks of 256 commit numbers, the per-chunk table (chunks x G x 129 words per problem) is sized on the host, and the batch form walks its
+ * problems in slices of at most 64 MiB of it (or one problem).  Flags are written per index, no output through an atomic, no float: the same flags every run.
+ * Refusals as ks_audit_topology_dev's. */
+int ks_audit_spread_dev(ks_dev_problem* d, const ks_result* claimed /* or NULL; pod_seq is read */, ks_audit_spread* out);
+int ks_audit_spread_batch_dev(ks_dev_problem* const* ds, uint32_t n, ks_audit_spread* const* outs);
 
 /* ---- consolidation CANDIDATES, selected and ordered on the device (deprovisioning/helpers.go:124-165,275-287 GetPodEvictionCost / disruptionCost /
  * calculateLifetimeRemaining, pdblimits.go:57-70 CanEvictPods, helpers.go:339-366 canBeTerminated / PodsPreventEviction, consolidation.go:83-104 the sort).

@@ -40,6 +40,9 @@ KSH_AUDIT_TRUNCATED_PODS, KSH_AUDIT_TRUNCATED_NODES = 1, 2
 # the second pass's bits (FlatProblem.audit_topology() / audit_topology_batch()), a word of their own, and what `checked` counts per rule
 KS_AUDIT_TOPOLOGY_BITS = {"SEQ": 128, "ANTI_AFFINITY": 256, "AFFINITY": 512, "HOSTNAME_SPREAD": 1024}
 KS_AUDIT_TOPOLOGY_RULES = ("SEQ", "ANTI_AFFINITY", "AFFINITY", "HOSTNAME_SPREAD")
+# the third pass's (FlatProblem.audit_spread() / audit_spread_batch()): SEQ as above, and spread over narrow keys
+KS_AUDIT_SPREAD_BITS = {"SEQ": 128, "SPREAD": 2048}
+KS_AUDIT_SPREAD_RULES = ("SEQ", "SPREAD")
 
 
 class KSolveError(RuntimeError):
@@ -350,6 +353,16 @@ class FlatProblem:
                 raise ValueError("audit_topology: pod_seq goes with a claimed result")
             return audit_topology_batch([self])[0]
         return _audit_topology_call([self], claimed, pod_seq)[0]
+
+    def audit_spread(self, claimed: Optional[dict] = None, pod_seq=None) -> dict:
+        """The audit's third, opt-in pass (include/ksolve.h KS_AUDIT_POD_SPREAD, kshost.h ksh_audit_spread / ksh_audit_spread_claimed): topology spread over narrow keys --
+        the zone --, decided from the final state and the commit numbers.  Arguments as `audit_topology`'s.  Returns {"pod_flags": uint32 [P], "n_pods_flagged",
+        "pod_bit_count" and "checked" (by rule name: SEQ the placed pods, SPREAD the (pod, group) pairs examined), "exact_pairs", "skipped_groups", "n_new", "n_placed", "ms"}."""
+        if claimed is None:
+            if pod_seq is not None:
+                raise ValueError("audit_spread: pod_seq goes with a claimed result")
+            return audit_spread_batch([self])[0]
+        return _audit_spread_call([self], claimed, pod_seq)[0]
 
     def result(self) -> SolveResult:
         """Decode the result the handle holds (after `solve(decode=False)` or `solve_from_pods`)."""
@@ -838,16 +851,17 @@ class _AuditTopologyOut(ctypes.Structure):      # include/kshost.h ksh_audit_top
                [("checked", ctypes.c_uint32 * 4), ("pod_bit_count", ctypes.c_uint32 * 32)]
 
 
-def _audit_topology_call(flats: Sequence["FlatProblem"], claimed: Optional[dict] = None, pod_seq=None) -> List[dict]:
+def _audit_seq_pass(what: str, Out, flats: Sequence["FlatProblem"], claimed: Optional[dict], pod_seq):
+    """What the audit's passes over the commit order share (kshost.h ksh_audit_<what> / ksh_audit_<what>_claimed, out tables of type `Out`): the call over the resident
+    results of `flats`, or over `claimed` with `pod_seq` for flats[0]; once more with larger tables if one was too short.  Returns (outs, pod_flags per problem, ms)."""
     import numpy as np
     kh = libs()[1]
     n = len(flats)
-    if not n:
-        return []
-    kh.ksh_audit_topology.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32, ctypes.POINTER(_AuditTopologyOut), ctypes.POINTER(ctypes.c_double)]
-    kh.ksh_audit_topology_claimed.argtypes = [ctypes.c_void_p, ctypes.POINTER(_ResultArrays), ctypes.c_void_p, ctypes.POINTER(_AuditTopologyOut), ctypes.POINTER(ctypes.c_double)]
+    resident, claimed_fn = getattr(kh, "ksh_audit_" + what), getattr(kh, "ksh_audit_" + what + "_claimed")
+    resident.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32, ctypes.POINTER(Out), ctypes.POINTER(ctypes.c_double)]
+    claimed_fn.argtypes = [ctypes.c_void_p, ctypes.POINTER(_ResultArrays), ctypes.c_void_p, ctypes.POINTER(Out), ctypes.POINTER(ctypes.c_double)]
     hs = (ctypes.c_void_p * n)(*[f._h for f in flats])
-    outs = (_AuditTopologyOut * n)()
+    outs = (Out * n)()
     ms = (ctypes.c_double * 2)()
     keep = []
     ra = seq = None
@@ -866,7 +880,7 @@ def _audit_topology_call(flats: Sequence["FlatProblem"], claimed: Optional[dict]
         if pod_seq is not None:
             seq = np.ascontiguousarray(np.asarray(pod_seq, dtype=np.int32).reshape(-1))
             if len(seq) != d["P"]:
-                raise ValueError("audit_topology: pod_seq holds one commit number per pod")
+                raise ValueError("audit_%s: pod_seq holds one commit number per pod" % what)
             if not len(seq):
                 seq = np.zeros(1, dtype=np.int32)
 
@@ -876,23 +890,51 @@ def _audit_topology_call(flats: Sequence["FlatProblem"], claimed: Optional[dict]
             pf = np.zeros(max(1, cp), dtype=np.uint32)
             tabs.append(pf)
             outs[i].pod_flags, outs[i].cap_pods = pf.ctypes.data, cp
-        rc = kh.ksh_audit_topology(hs, n, outs, ms) if ra is None else kh.ksh_audit_topology_claimed(flats[0]._h, ctypes.byref(ra), seq.ctypes.data if seq is not None else None, outs, ms)
+        rc = resident(hs, n, outs, ms) if ra is None else claimed_fn(flats[0]._h, ctypes.byref(ra), seq.ctypes.data if seq is not None else None, outs, ms)
         if rc != KS_OK:
             raise KSolveError(rc, kh.ksh_last_error().decode())
         return tabs
     tabs = call([f.dims["P"] for f in flats])
     if any(o.truncated for o in outs):      # (a what-if derived on the device states its own sizes only here: once more, with what the totals say)
         tabs = call([o.n_pods for o in outs])
-    return [{"pod_flags": tabs[i][:o.n_pods].copy(), "n_pods_flagged": int(o.n_pods_flagged),
+    return outs, [tabs[i][:o.n_pods].copy() for i, o in enumerate(outs)], (float(ms[0]), float(ms[1]))
+
+
+def _audit_topology_call(flats: Sequence["FlatProblem"], claimed: Optional[dict] = None, pod_seq=None) -> List[dict]:
+    if not len(flats):
+        return []
+    outs, flags, ms = _audit_seq_pass("topology", _AuditTopologyOut, flats, claimed, pod_seq)
+    return [{"pod_flags": flags[i], "n_pods_flagged": int(o.n_pods_flagged),
              "pod_bit_count": {k: int(o.pod_bit_count[v.bit_length() - 1]) for k, v in KS_AUDIT_TOPOLOGY_BITS.items()},
              "checked": {k: int(o.checked[j]) for j, k in enumerate(KS_AUDIT_TOPOLOGY_RULES)}, "skipped_groups": int(o.skipped_groups),
-             "n_new": int(o.n_new), "n_placed": int(o.n_placed), "ms": (float(ms[0]), float(ms[1]))} for i, o in enumerate(outs)]
+             "n_new": int(o.n_new), "n_placed": int(o.n_placed), "ms": ms} for i, o in enumerate(outs)]
 
 
 def audit_topology_batch(flats: Sequence["FlatProblem"]) -> List[dict]:
     """The audit's second pass over the results the last solve left on the device, for a whole batch (include/kshost.h ksh_audit_topology): handles of any kind, derived
     what-ifs included.  One dict per problem, as `FlatProblem.audit_topology` returns it."""
     return _audit_topology_call(flats)
+
+
+class _AuditSpreadOut(ctypes.Structure):      # include/kshost.h ksh_audit_spread_out
+    _fields_ = [("pod_flags", ctypes.c_void_p), ("cap_pods", ctypes.c_uint64)] + \
+               [(n, ctypes.c_uint32) for n in ("n_pods", "n_new", "n_placed", "skipped_groups", "n_pods_flagged", "truncated")] + \
+               [("checked", ctypes.c_uint32 * 2), ("exact_pairs", ctypes.c_uint32), ("pad", ctypes.c_uint32)]
+
+
+def _audit_spread_call(flats: Sequence["FlatProblem"], claimed: Optional[dict] = None, pod_seq=None) -> List[dict]:
+    if not len(flats):
+        return []
+    outs, flags, ms = _audit_seq_pass("spread", _AuditSpreadOut, flats, claimed, pod_seq)
+    return [{"pod_flags": flags[i], "n_pods_flagged": int(o.n_pods_flagged), "pod_bit_count": {k: int(((flags[i] & v) != 0).sum()) for k, v in KS_AUDIT_SPREAD_BITS.items()},
+             "checked": {k: int(o.checked[j]) for j, k in enumerate(KS_AUDIT_SPREAD_RULES)}, "exact_pairs": int(o.exact_pairs), "skipped_groups": int(o.skipped_groups),
+             "n_new": int(o.n_new), "n_placed": int(o.n_placed), "ms": ms} for i, o in enumerate(outs)]
+
+
+def audit_spread_batch(flats: Sequence["FlatProblem"]) -> List[dict]:
+    """The audit's third pass over the results the last solve left on the device, for a whole batch (include/kshost.h ksh_audit_spread): handles of any kind, derived
+    what-ifs included.  One dict per problem, as `FlatProblem.audit_spread` returns it."""
+    return _audit_spread_call(flats)
 
 
 def deal_lpt(weights: Sequence[int], nshards: int) -> List[int]:
