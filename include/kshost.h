@@ -582,6 +582,22 @@ typedef struct ksh_audit_spread_out {
 int ksh_audit_spread(void** handles, uint32_t n, ksh_audit_spread_out* outs /* [n] */, double* ms /* [2] kernels | read-back, or NULL */);
 /* A claimed result for one flattened handle, exactly as ksh_audit_topology_claimed takes it. */
 int ksh_audit_spread_claimed(void* handle, const ksh_result_arrays* claimed, const int32_t* pod_seq /* [n_pods] */, ksh_audit_spread_out* out, double* ms /* [2] or NULL */);
+/* The audit's FOURTH pass, opt-in (ksolve.h ks_audit_firstfit_dev, KS_AUDIT_POD_FIT_*): first-fit order -- a pod may not have ended later than a node, new node or
+ * template whose final state would still take it -- decided from the final state and the commit numbers.  The shim's gate is the four passes in order: ksh_audit,
+ * ksh_audit_topology, ksh_audit_spread, then this, and on a finding of any, solve in Go.  The second pass's conventions: the totals always, pod_flags when
+ * cap_pods >= n_pods (else KSH_AUDIT_TRUNCATED_PODS), indices as ksh_audit's.  checked[0]: the placed pods; checked[1]: the pods examined (skipped_pods: the others);
+ * checked[2]: the (class, node-or-template) pairs evaluated; admitting_pairs: those that admitted -- a clean result with none of them proved little. */
+typedef struct ksh_audit_firstfit_out {
+  uint32_t* pod_flags; uint64_t cap_pods;      /* [cap_pods] KS_AUDIT_POD_SEQ | KS_AUDIT_POD_FIT_* */
+  uint32_t n_pods, n_new, n_placed, skipped_pods;
+  uint32_t n_pods_flagged, truncated /* KSH_AUDIT_TRUNCATED_PODS */;
+  uint32_t checked[3];
+  uint32_t admitting_pairs;
+} ksh_audit_firstfit_out;
+int ksh_audit_firstfit(void** handles, uint32_t n, ksh_audit_firstfit_out* outs /* [n] */, double* ms /* [2] kernels | read-back, or NULL */);
+/* A claimed result for one flattened handle, as ksh_audit_topology_claimed takes it; this pass also reads node_types, node_requests, node_requests_present and
+ * node_it_state of the claimed arrays. */
+int ksh_audit_firstfit_claimed(void* handle, const ksh_result_arrays* claimed, const int32_t* pod_seq /* [n_pods] */, ksh_audit_firstfit_out* out, double* ms /* [2] or NULL */);
 
 /* ---- the snapshot kept current by EVENTS ("cached incremental SoA builder fed from state.Cluster") ----
  * Replaces, for the snapshot consolidation simulates over, what the reference does between two passes of the deprovisioner (deprovisioning/controller.go:64,

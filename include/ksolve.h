@@ -693,7 +693,7 @@ int ks_placement_rows_host(ks_dev_problem* const* ds, uint32_t n, const uint64_t
  * decides together with the commit numbers is the second, opt-in pass below (ks_audit_topology_dev: pod (anti-)affinity, hostname spread).  Audited by neither:
  * spread over narrow keys, hostname spread under a node filter, self-selecting affinity, groups created by a later Topology.Update, provisioner limits (subtractMax
  * depends on the order), first-fit optimality (whether an earlier node would have taken the pod).  (Spread over narrow keys, unfiltered, is now the third pass's:
- * ks_audit_spread_dev.)
+ * ks_audit_spread_dev; first-fit order, for the pods no topology group constrains, the fourth pass's: ks_audit_firstfit_dev.)
  * The caller owns the tables: pod_flags [P] and node_flags [E + max_new_nodes] (of which E + n_new are written), either may be NULL (totals only).  Flags are written
  * per index -- no list is appended through an atomic -- so the output is the same every run. */
 typedef struct ks_audit {
@@ -797,6 +797,56 @@ typedef struct ks_audit_spread {
  * Refusals as ks_audit_topology_dev's. */
 int ks_audit_spread_dev(ks_dev_problem* d, const ks_result* claimed /* or NULL; pod_seq is read */, ks_audit_spread* out);
 int ks_audit_spread_batch_dev(ks_dev_problem* const* ds, uint32_t n, ks_audit_spread* const* outs);
+
+/* ---- the audit's FOURTH pass, opt-in: FIRST-FIT ORDER.  Nothing calls it unless asked; the first three passes are unchanged by it.  scheduler.add tries every
+ * existing node, then every new node, then every template before it opens a machine (scheduler.go:174-219).  Between the moment a pod was tried and the end of the
+ * Solve a node's requests only grow, its requirements only narrow, its InstanceTypeOptions only shrink, its port and volume sets only grow: a node whose FINAL state
+ * would still take pod P in addition to everything on it would have taken P at any earlier moment it existed, so P cannot legally have ended anywhere later.  One-sided
+ * like passes two and three: it flags only what no run of the reference can have produced.  The bits share their word with KS_AUDIT_POD_SEQ, defined as in the second
+ * pass.
+ * EXAMINED pod P: it does not fail SEQ (a placed pod), or it is unscheduled (pod_node == -1); its final-stage class c has an empty own_list and an empty isel_list
+ * (no topology group constrains it: Topology.AddRequirements adds nothing; being RECORDED by others -- sel_list, iown_list -- is fine, Record runs after admission)
+ * and no host ports.  Every other pod is counted in skipped_pods.  A class with any vol_list entry is examined against new nodes and templates only (new nodes track
+ * no volumes), not against existing nodes.
+ * admits_existing(c, e), existing node e of the view, not removed in a derived what-if.  The pair is examined only where every key the class names is labelled on e
+ * -- cls.present & ~en.present == 0, and en.it_state[e] != 0 if the class carries an instance-type requirement: the flat problem keeps only an existing node's
+ * labels, a label is a single-value In, so on those keys the node's requirement at any time IS the label and Compatible is exact; on an unlabelled key an earlier
+ * topology pod may have narrowed the node in a way the result does not carry.  Then all of: en_taints[e] & ~cls_tolerated[c] == 0; the hostname mode admits e;
+ * Compatible(en, cls) on every key (kreq_compatible_fail) and its_fail[en.it_state * SC + cls.it_state] == 0; Fits(en_requests[e] + the cls_requests of every pod the
+ * result puts on e + cls_requests[c], en_avail[e]) under resources.Fits' presence rule, int64.
+ * admits_new(c, j), new node j with template m in range.  All of: the template's taints are tolerated; cls_hn_mode[c] != 1 (a new node's placeholder hostname is in
+ * no list); every non-well-known key the class names with an operator other than NotIn / DoesNotExist is present in tmpl.present[m] ("custom labels, if not defined,
+ * are denied" looks at the node at the time, requirements.go:125-130; a later pod may have added the key to the final requirements, the template had it all along);
+ * on every narrow key present in both the node's final requirements and the class the INTERSECTION IS NON-EMPTY -- the NotIn / DoesNotExist exception of
+ * requirements.go:196-200 is not used: a final state that passes only through it can have failed earlier (a node at Exists refuses the DoesNotExist pod that the same
+ * node, later narrowed to DoesNotExist, lets through); its_fail[node_it_state * SC + cls.it_state] == 0; and some type t in node_types[j] & its_types[its_inter[..]]
+ * passes compatible && fits && hasOffering (node.go:137-159) against the node's final requirements intersected with the class and node_requests[j] + cls_requests[c].
+ * admits_template(c, m), only for tmpl_limit_present[m] == 0xFFFFFFFF: admits_new against a fresh node -- the template's requirements, tmpl_daemon[m], tmpl_types[m].
+ * open(j): the least pod_seq over the pods on new node j that do not fail SEQ.  first_e(c): the least e with admits_existing.  first_open(c): the least open(j) over
+ * the j with admits_new.  first_m(c): the least m with admits_template. */
+#define KS_AUDIT_POD_FIT_EXISTING 4096u     /* P is on existing node e and first_e(c) < e; or P is on a new node or unscheduled and first_e(c) exists */
+#define KS_AUDIT_POD_FIT_NEW 8192u          /* P opened its new node (seq(P) == open(node(P))) and first_open(c) < seq(P) -- strictly: its own node opened at seq(P); or P is unscheduled and first_open(c) exists */
+#define KS_AUDIT_POD_FIT_TEMPLATE 16384u    /* P opened a node of template m and first_m(c) < m; or P is unscheduled and first_m(c) exists */
+/* A pod on a new node it did not open is checked against existing nodes only: the order among new nodes at the time depends on pod counts at the time (sort.Slice,
+ * scheduler.go:183).  NOT attempted: topology-constrained pods (the next step would be hostname anti-affinity and unfiltered hostname spread, whose per-node counts
+ * also only grow), pods with host ports, limited templates, existing nodes on keys they do not label, the order among new nodes, provisioner limits. */
+typedef struct ks_audit_firstfit {
+  uint32_t* pod_flags;            /* [P] KS_AUDIT_POD_SEQ | KS_AUDIT_POD_FIT_*, or NULL (totals only) */
+  uint32_t n_pods, n_new;         /* out: P | the new nodes of the result that was audited */
+  uint32_t n_placed;              /* out: pods on a node of the result */
+  uint32_t skipped_pods;          /* out: the pods that are not examined */
+  uint32_t n_pods_flagged;
+  uint32_t checked[3];            /* out: [0] the placed pods (SEQ); [1] the pods examined; [2] the (class, node-or-template) pairs evaluated, over the distinct classes of the examined pods */
+  uint32_t admitting_pairs;       /* out: how many of those pairs admitted.  A clean result with admitting_pairs == 0 proved little */
+  double kernel_ms, readback_ms;  /* out: as ks_audit's */
+} ks_audit_firstfit;
+/* claimed == NULL: the resident result, where it lies (the form for derived what-ifs: removed nodes are skipped, the pods' classes are the snapshot's).  claimed given
+ * (flattened problems only, KS_ERR_UNSUPPORTED for a derived view): what the first pass uploads but the unscheduled list -- pod_seq among it -- is uploaded and read;
+ * every index a result supplies is range-checked before it addresses memory.  Six launches; the scratch of a problem is O(P + C + E x R + max_new_nodes) words, so a
+ * batch is one slice.  The tables behind the verdict are built by integer min, add and or; flags are written per index, no output through an atomic, no float: the
+ * same flags every run.  Refusals as ks_audit_spread_dev's. */
+int ks_audit_firstfit_dev(ks_dev_problem* d, const ks_result* claimed /* or NULL; pod_seq is read */, ks_audit_firstfit* out);
+int ks_audit_firstfit_batch_dev(ks_dev_problem* const* ds, uint32_t n, ks_audit_firstfit* const* outs);
 
 /* ---- consolidation CANDIDATES, selected and ordered on the device (deprovisioning/helpers.go:124-165,275-287 GetPodEvictionCost / disruptionCost /
  * calculateLifetimeRemaining, pdblimits.go:57-70 CanEvictPods, helpers.go:339-366 canBeTerminated / PodsPreventEviction, consolidation.go:83-104 the sort).

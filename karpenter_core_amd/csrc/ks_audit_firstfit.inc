@@ -1,0 +1,358 @@
+// ks_audit_firstfit.inc -- the audit's fourth, opt-in pass: FIRST-FIT ORDER (ksolve.h ks_audit_firstfit_dev / ks_audit_firstfit_batch_dev, KS_AUDIT_POD_FIT_*).
+// Included by ksolve.hip after ks_audit_spread.inc, outside the emulator's guards: the tests/sim build compiles and runs these kernels too.  The first three passes'
+// kernels, views and outputs are untouched; their helpers (aud_where, aud_class, aud_n_new, aud_wave_*) are called as they are, ks_algebra.h is as it was.
+//
+// scheduler.add tries every existing node, then every new node, then every template before it opens a machine (scheduler.go:174-219).  Between the moment a pod was
+// tried and the end of the Solve a node's requests only grow, its requirements only narrow, its InstanceTypeOptions only shrink: a node whose FINAL state would take
+// pod P on top of everything it holds would have taken P at any earlier moment it existed, so P cannot have ended anywhere later.  One-sided, as passes two and three:
+// it flags only what no run of the reference can have produced (DESIGN.md 7.24 has the argument per clause).  The work is per DISTINCT final-stage class used by an
+// examined pod -- a derived what-if shares its snapshot's thousands of classes and uses a few hundred.  Six launches on the problems' stream, blockIdx.y = the problem:
+//   ks_audit_ff_count     one lane per pod: the placed pods counted, and counted per commit number (the second pass's SEQ rule); the existing nodes' request sums and
+//                         presence masks by integer atomicAdd / atomicOr into scratch; open[] and the three first_* tables set to "never".
+//   ks_audit_ff_mark      one lane per pod: used[c] = 1 for the class of every examined pod; open[j] = the least commit number on new node j (atomicMin).  Integer
+//                         min, add and or: the same tables every run.
+//   ks_audit_ff_compact   one workgroup per problem: used[] compacted into the class list (ks_audit_scan's Hillis-Steele tile).
+//   ks_audit_ff_existing  one lane per (used class, existing node), a wave shares the class: the test is scalar per pair; a wave minimum, then atomicMin into first_e[u].
+//   ks_audit_ff_new       one wave per (used class, new node or unlimited template): the scalar clauses are wave-uniform; then one instance type per lane, word by
+//                         word -- it_mask[k*T+t] coalesced over t, Fits over R, the offering test against the zone x capacity-type mask, as ks_audit_nodes does --
+//                         and a ballot ends the walk at the first word a type passes in.  atomicMin into first_open[u] / first_m[u].
+//   ks_audit_ff_verdict   one lane per pod: its flag word and its checked word, one writer each, a plain store.
+// No float, no LDS beyond the count kernel's reduction and the scan tile, no dynamically indexed register array, no atomic on an output.
+#define KS_AF_NEVER 0xFFFFFFFFu
+struct AuditFitView {
+  u32* flags; u32* chk; u32* meta;      // outputs: [P] KS_AUDIT_POD_SEQ | KS_AUDIT_POD_FIT_* | [P] bit 0 examined, bit 29 skipped, bit 30 placed | [8]: n_new, placed pods, used classes, pairs evaluated, pairs that admitted
+  u64* esum; u32* epres;                // scratch: [E * R] the requests of the pods the result puts on existing node e | [E] their presence masks
+  u32* seqcnt; u32* used; u32* list;    // scratch: [P] placed pods per commit number | [C] the class is used by an examined pod, then its index in the list + 1 | [C] the used classes
+  u32* first_e; u32* first_open; u32* first_m; u32* open; u32* cntr;      // scratch: [C] by list index: the least admitting existing node | the least open() over the admitting new nodes | the least admitting unlimited template | [NMAX] the least commit number on new node j | [4] placed pods, used classes, pairs evaluated, pairs that admitted
+};
+__device__ __forceinline__ bool aud_fit_seq_ok(const AuditView& V, const AuditFitView& F, u32 p, u32 n_placed) {      // (aud_topo_seq_ok over this pass's counts)
+  const i32 sq = GC(i32, V.pod_seq)[p];
+  return sq >= 0 && (u32)sq < n_placed && F.seqcnt[sq] == 1u;
+}
+// no topology group constrains the class (Topology.AddRequirements adds nothing) and it reserves no host port
+__device__ __forceinline__ bool aud_fit_examinable(const DevProb& P, u32 c) {
+  return GC(u32, P.cls_own_off)[c + 1] == GC(u32, P.cls_own_off)[c] && GC(u32, P.cls_isel_off)[c + 1] == GC(u32, P.cls_isel_off)[c] && GC(u32, P.cls_port_off)[c + 1] == GC(u32, P.cls_port_off)[c];
+}
+__device__ __forceinline__ KReq aud_fit_cls_req(const DevProb& P, u32 c, u32 k) {
+  return load_req(GC(u32, P.cls.present)[c], GC(u32, P.cls.complement)[c], P.cls.mask + (size_t)c * P.K, P.cls.gt + (size_t)c * P.K, P.cls.lt + (size_t)c * P.K, (int)k);
+}
+// the intersection of two present requirements is EMPTY.  Requirements.Intersects lets an empty intersection pass when both operators are NotIn / DoesNotExist
+// (requirements.go:196-200); this pass does not: a final state that passes only through that exception can have failed earlier (a node at Exists refuses the
+// DoesNotExist pod that the same node, later narrowed to DoesNotExist, lets through)
+__device__ __forceinline__ bool aud_fit_meet_empty(const KReq& a, const KReq& b, const i32* vi, u32 nv) { return a.present && b.present && kreq_len0(kreq_intersect(a, b, vi, nv)); }
+// the zone x capacity-type pairs a requirement set allows (ks_audit_nodes' way)
+__device__ __forceinline__ u64 aud_fit_pairs(const DevProb& P, const KReq& z, const KReq& ct) {
+  u64 allowZ = ~0ull, allowC = ~0ull;
+  if (P.key_zone >= 0 && z.present) allowZ = kreq_has_mask(z, P.value_int + P.key_zone * 64, GC(u32, P.key_nvalues)[P.key_zone]);
+  if (P.key_ct >= 0 && ct.present) allowC = kreq_has_mask(ct, P.value_int + P.key_ct * 64, GC(u32, P.key_nvalues)[P.key_ct]);
+  if (P.n_ct == 0) return ~0ull;
+  u64 pairs = 0;
+  for (u64 zz = allowZ; zz; zz &= zz - 1) { const int zi = __builtin_ctzll(zz); if ((u32)zi * P.n_ct >= 64) break; pairs |= (allowC & ((1ull << P.n_ct) - 1)) << (zi * P.n_ct); }
+  return pairs;
+}
+// admits_existing(c, e) for a pair that is examined (every key of the class is labelled on e): static facts of the flat problem plus one sum
+__device__ __forceinline__ bool aud_fit_existing(const DevProb& P, const AuditFitView& F, u32 c, u32 e) {
+  const u32 K = P.K, R = P.R;
+  if (GC(u64, P.en_taints)[e] & ~GC(u64, P.cls_tolerated)[c]) return false;
+  const u32 hm = GC(u8, P.cls_hn_mode)[c];
+  if (hm) {
+    bool inlist = false;
+    for (u32 i = GC(u32, P.cls_hn_off)[c]; i < GC(u32, P.cls_hn_off)[c + 1]; ++i) if (GC(u32, P.hn_list)[i] == e) { inlist = true; break; }
+    if (hm == 1 ? !inlist : inlist) return false;
+  }
+  const u32 cp = GC(u32, P.cls.present)[c], ep = GC(u32, P.en.present)[e], ec = GC(u32, P.en.complement)[e];
+  for (u32 k = 0; k < K; ++k) {
+    if (!((cp >> k) & 1u)) continue;
+    const KReq a = load_req(ep, ec, P.en.mask + (size_t)e * K, P.en.gt + (size_t)e * K, P.en.lt + (size_t)e * K, (int)k);
+    if (kreq_compatible_fail(a, aud_fit_cls_req(P, c, k), (P.wellknown_mask >> k) & 1u, P.value_int + k * 64, GC(u32, P.key_nvalues)[k])) return false;
+  }
+  const i32 sa = GC(i32, P.en.it_state)[e], sb = GC(i32, P.cls.it_state)[c];
+  if (P.SC && (sa < 0 || (u32)sa >= P.S || sb < 0 || (u32)sb >= P.SC || GC(u8, P.its_fail)[(size_t)sa * P.SC + sb])) return false;
+  // resources.Fits under its presence rule: only a resource in the merged list is compared (existingnode.go:98-102)
+  const u32 rp = GC(u32, P.en_requests_present)[e] | F.epres[e] | GC(u32, P.cls_requests_present)[c];
+  for (u32 r = 0; r < R; ++r) {
+    if (!((rp >> r) & 1u)) continue;
+    const u64 need = (u64)GC(i64, P.en_requests)[(size_t)e * R + r] + F.esum[(size_t)e * R + r] + (u64)GC(i64, P.cls_requests)[(size_t)c * R + r];
+    if ((i64)need > GC(i64, P.en_avail)[(size_t)e * R + r]) return false;
+  }
+  return true;
+}
+
+__global__ __launch_bounds__(256) void ks_audit_ff_count(const DevProb* probs, const AuditView* views, const AuditFitView* fviews) {
+  __shared__ u32 s_sum[256];
+  const DevProb& P = probs[blockIdx.y]; const AuditView& V = views[blockIdx.y]; const AuditFitView& F = fviews[blockIdx.y];
+  const u32 np = P.P, E = P.E, NS = E + aud_n_new(P, V), R = P.R;
+  u32 mine = 0;
+  for (u32 i = blockIdx.x * 256u + threadIdx.x; i < np; i += gridDim.x * 256u) {
+    const i32 nd = aud_where(P, V, i, NS), sq = GC(i32, V.pod_seq)[i];
+    if (nd < 0) continue;
+    ++mine;
+    if (sq >= 0 && (u32)sq < np) atomicAdd(&F.seqcnt[sq], 1u);
+    if ((u32)nd < E) {      // (its node counts the pod whatever else is wrong with it, as the first pass does)
+      const u32 c = aud_class(P, V, i), pres = GC(u32, P.cls_requests_present)[c];
+      if (pres) atomicOr(&F.epres[nd], pres);
+      for (u32 r = 0; r < R; ++r) { const i64 v = GC(i64, P.cls_requests)[(size_t)c * R + r]; if (v) atomicAdd((unsigned long long*)&F.esum[(size_t)nd * R + r], (unsigned long long)v); }
+    }
+  }
+  s_sum[threadIdx.x] = mine;
+  for (u32 o = 128u; o > 0; o >>= 1) { __syncthreads(); if (threadIdx.x < o) s_sum[threadIdx.x] += s_sum[threadIdx.x + o]; }
+  if (threadIdx.x == 0 && s_sum[0]) atomicAdd(&F.cntr[0], s_sum[0]);
+  for (u32 i = blockIdx.x * 256u + threadIdx.x; i < P.C; i += gridDim.x * 256u) { F.first_e[i] = KS_AF_NEVER; F.first_open[i] = KS_AF_NEVER; F.first_m[i] = KS_AF_NEVER; }
+  for (u32 i = blockIdx.x * 256u + threadIdx.x; i < P.NMAX; i += gridDim.x * 256u) F.open[i] = KS_AF_NEVER;
+}
+__global__ __launch_bounds__(256) void ks_audit_ff_mark(const DevProb* probs, const AuditView* views, const AuditFitView* fviews) {
+  const DevProb& P = probs[blockIdx.y]; const AuditView& V = views[blockIdx.y]; const AuditFitView& F = fviews[blockIdx.y];
+  const u32 np = P.P, E = P.E, NS = E + aud_n_new(P, V), n_placed = F.cntr[0];
+  for (u32 p = blockIdx.x * 256u + threadIdx.x; p < np; p += gridDim.x * 256u) {
+    const i32 nd = aud_where(P, V, p, NS);
+    const bool ok = nd >= 0 && aud_fit_seq_ok(V, F, p, n_placed);
+    if (!ok && GC(i32, V.pod_node)[p] != -1) continue;      // fails SEQ, or names no node of the result
+    if (ok && (u32)nd >= E) atomicMin(&F.open[(u32)nd - E], (u32)GC(i32, V.pod_seq)[p]);
+    const u32 c = aud_class(P, V, p);
+    if (aud_fit_examinable(P, c)) F.used[c] = 1u;      // (every writer stores 1)
+  }
+}
+__global__ __launch_bounds__(256) void ks_audit_ff_compact(const DevProb* probs, const AuditFitView* fviews) {
+  __shared__ u32 s_sum[256];
+  const DevProb& P = probs[blockIdx.x]; const AuditFitView& F = fviews[blockIdx.x];
+  const u32 tid = threadIdx.x, C = P.C; u32 carry = 0;
+  for (u32 base = 0; base < C; base += 256u) {      // (C is read from one address by every lane: every lane walks every tile and every scan step)
+    const u32 i = base + tid; const u32 mine = i < C ? F.used[i] : 0u;
+    s_sum[tid] = mine;
+    for (u32 o = 1; o < 256u; o <<= 1) {
+      __syncthreads();
+      const u32 x = tid >= o ? s_sum[tid - o] : 0u;
+      __syncthreads();
+      s_sum[tid] += x;
+    }
+    __syncthreads();
+    if (mine) { const u32 u = carry + s_sum[tid] - 1u; F.list[u] = i; F.used[i] = u + 1u; }
+    carry += s_sum[255];
+    __syncthreads();
+  }
+  if (tid == 0) F.cntr[1] = carry;
+}
+__global__ __launch_bounds__(256) void ks_audit_ff_existing(const DevProb* probs, const AuditFitView* fviews) {
+  const DevProb& P = probs[blockIdx.y]; const AuditFitView& F = fviews[blockIdx.y];
+  const u32 lane = threadIdx.x & 63u, E = P.E, tiles = (E + 255u) / 256u, n_used = F.cntr[1];
+  const size_t total = (size_t)n_used * tiles;
+  for (size_t w = blockIdx.x; w < total; w += gridDim.x) {      // (w, u and c are the same in all 256 threads)
+    const u32 u = (u32)(w / tiles), e = (u32)(w % tiles) * 256u + threadIdx.x, c = F.list[u];
+    if (GC(u32, P.cls_vol_off)[c + 1] != GC(u32, P.cls_vol_off)[c]) continue;      // a class that mounts volumes is examined against new nodes only: they track none
+    bool exam = e < E && !(P.en_removed && ((GC(u64, P.en_removed)[e >> 6] >> (e & 63u)) & 1ull)), adm = false;
+    // every key the class names is labelled on e: there the node's requirement at any time IS the label, and Compatible is exact
+    if (exam) exam = (GC(u32, P.cls.present)[c] & ~GC(u32, P.en.present)[e]) == 0u && !(GC(i32, P.cls.it_state)[c] != 0 && GC(i32, P.en.it_state)[e] == 0);
+    if (exam) adm = aud_fit_existing(P, F, c, e);
+    u32 best = adm ? e : KS_AF_NEVER;
+    for (int x = 32; x > 0; x >>= 1) { const u32 o = __shfl_xor(best, x); best = o < best ? o : best; }
+    const u64 bx = ballot64(exam), ba = ballot64(adm);
+    if (lane == 0) {
+      if (best != KS_AF_NEVER) atomicMin(&F.first_e[u], best);
+      if (bx) atomicAdd(&F.cntr[2], (u32)__builtin_popcountll(bx));
+      if (ba) atomicAdd(&F.cntr[3], (u32)__builtin_popcountll(ba));
+    }
+  }
+}
+__global__ __launch_bounds__(256) void ks_audit_ff_new(const DevProb* probs, const AuditView* views, const AuditFitView* fviews) {
+  const DevProb& P = probs[blockIdx.y]; const AuditView& V = views[blockIdx.y]; const AuditFitView& F = fviews[blockIdx.y];
+  const u32 lane = threadIdx.x & 63u, NN = aud_n_new(P, V), M = P.M, K = P.K, R = P.R, T = P.T, TW = P.TW, X = NN + M, n_used = F.cntr[1];
+  const size_t total = (size_t)n_used * X;
+  for (size_t w = (size_t)blockIdx.x * 4u + (threadIdx.x >> 6); w < total; w += (size_t)gridDim.x * 4u) {      // (w, and everything read through it, is the same in all 64 lanes)
+    const u32 u = (u32)(w / X), x = (u32)(w % X), c = F.list[u];
+    const bool fresh = x >= NN; const u32 j = x;
+    i32 m;
+    if (fresh) { m = (i32)(x - NN); if (GC(u32, P.tmpl_limit_present)[m] != 0xFFFFFFFFu) continue; }      // a limited template starts from an order-dependent subset (scheduler.go:199-208)
+    else { m = GC(i32, V.n_tmpl)[j]; if (m < 0 || (u32)m >= M) continue; }
+    // the node's final requirements, requests and options -- or a fresh node's: the template's, its daemon overhead, its types
+    const u32 np_ = fresh ? GC(u32, P.tmpl.present)[m] : GC(u32, V.o_present)[j], nc_ = fresh ? GC(u32, P.tmpl.complement)[m] : GC(u32, V.o_complement)[j];
+    const u64* nmask = fresh ? P.tmpl.mask + (size_t)m * K : V.o_mask + (size_t)j * K;
+    const i32* ngt = fresh ? P.tmpl.gt + (size_t)m * K : V.o_gt + (size_t)j * K; const i32* nlt = fresh ? P.tmpl.lt + (size_t)m * K : V.o_lt + (size_t)j * K;
+    const i64* nreq = fresh ? P.tmpl_daemon + (size_t)m * R : V.o_req + (size_t)j * R;
+    const u32 rmask = (fresh ? GC(u32, P.tmpl_daemon_present)[m] : GC(u32, V.o_reqmask)[j]) | GC(u32, P.cls_requests_present)[c];
+    const u64* ntypes = fresh ? P.tmpl_types + (size_t)m * TW : V.n_types + (size_t)j * TW;
+    const i32 sa = fresh ? GC(i32, P.tmpl.it_state)[m] : GC(i32, V.o_it)[j], sb = GC(i32, P.cls.it_state)[c];
+    const u32 cp = GC(u32, P.cls.present)[c], tmp = GC(u32, P.tmpl.present)[m];
+    // ---- the scalar clauses ----
+    bool ok = (GC(u64, P.tmpl_taints)[m] & ~GC(u64, P.cls_tolerated)[c]) == 0ull && GC(u8, P.cls_hn_mode)[c] != 1;      // (a new node's placeholder hostname is in no list, node.go:46)
+    for (u32 k = 0; k < K && ok; ++k) {
+      if (!((cp >> k) & 1u)) continue;
+      const KReq b = aud_fit_cls_req(P, c, k);
+      // "custom labels, if not defined, are denied" looks at the node AT THE TIME (requirements.go:125-130): a later pod may have added the key, the template had it all along
+      if (!((P.wellknown_mask >> k) & 1u) && !kreq_nidne(b) && !((tmp >> k) & 1u)) ok = false;
+      else if (aud_fit_meet_empty(load_req(np_, nc_, nmask, ngt, nlt, (int)k), b, P.value_int + k * 64, GC(u32, P.key_nvalues)[k])) ok = false;
+    }
+    u32 si = 0;
+    if (ok) {
+      if (sa < 0 || (u32)sa >= P.S) ok = false;
+      else if (!P.SC) si = (u32)sa;
+      else if (sb < 0 || (u32)sb >= P.SC || GC(u8, P.its_fail)[(size_t)sa * P.SC + sb]) ok = false;
+      else { si = GC(u16, P.its_inter)[(size_t)sa * P.SC + sb]; if (si >= P.S) ok = false; }
+    }
+    // ---- filterInstanceTypesByRequirements (node.go:137-159) against the final requirements with the class added and the requests with the class's: one type per lane ----
+    bool adm = false;
+    if (ok) {
+      const u32 mp = np_ | cp;
+      KReq rz = kreq_absent(), rc = kreq_absent();
+      if (P.key_zone >= 0) rz = kreq_add(load_req(np_, nc_, nmask, ngt, nlt, P.key_zone), aud_fit_cls_req(P, c, (u32)P.key_zone), P.value_int + P.key_zone * 64, GC(u32, P.key_nvalues)[P.key_zone]);
+      if (P.key_ct >= 0) rc = kreq_add(load_req(np_, nc_, nmask, ngt, nlt, P.key_ct), aud_fit_cls_req(P, c, (u32)P.key_ct), P.value_int + P.key_ct * 64, GC(u32, P.key_nvalues)[P.key_ct]);
+      const u64 pairs = aud_fit_pairs(P, rz, rc);
+      for (u32 tw = 0; tw < TW; ++tw) {
+        const u32 t = tw * 64u + lane;
+        bool okl = t < T && ((GC(u64, ntypes)[tw] >> lane) & 1ull) && ((GC(u64, P.its_types)[(size_t)si * TW + tw] >> lane) & 1ull);
+        if (okl) {
+          const u32 tp = GC(u32, P.it_present)[t], tc = GC(u32, P.it_complement)[t];
+          for (u32 k = 0; k < K && okl; ++k) {
+            if (!((mp >> k) & 1u) || !((tp >> k) & 1u)) continue;
+            const KReq nr = kreq_add(load_req(np_, nc_, nmask, ngt, nlt, (int)k), aud_fit_cls_req(P, c, k), P.value_int + k * 64, GC(u32, P.key_nvalues)[k]);
+            KReq a; a.present = true; a.complement = (tc >> k) & 1u; a.mask = GC(u64, P.it_mask)[(size_t)k * T + t]; a.gt = KS_NOGT; a.lt = KS_NOLT;
+            if (kreq_intersects_fail(a, nr, P.value_int + k * 64, GC(u32, P.key_nvalues)[k])) okl = false;
+          }
+          for (u32 r = 0; r < R && okl; ++r) if (((rmask >> r) & 1u) && (i64)((u64)GC(i64, nreq)[r] + (u64)GC(i64, P.cls_requests)[(size_t)c * R + r]) > GC(i64, P.it_alloc)[(size_t)r * T + t]) okl = false;
+          if (okl) okl = (GC(u64, P.it_offer)[t] & pairs) != 0;
+        }
+        if (ballot64(okl)) { adm = true; break; }      // (the ballot is the same in all 64 lanes: they leave together)
+      }
+    }
+    if (lane == 0) {
+      atomicAdd(&F.cntr[2], 1u);
+      if (adm) {
+        atomicAdd(&F.cntr[3], 1u);
+        if (fresh) atomicMin(&F.first_m[u], (u32)m);
+        else { const u32 o = F.open[j]; if (o != KS_AF_NEVER) atomicMin(&F.first_open[u], o); }
+      }
+    }
+  }
+}
+__global__ __launch_bounds__(256) void ks_audit_ff_verdict(const DevProb* probs, const AuditView* views, const AuditFitView* fviews) {
+  const DevProb& P = probs[blockIdx.y]; const AuditView& V = views[blockIdx.y]; const AuditFitView& F = fviews[blockIdx.y];
+  const u32 np = P.P, E = P.E, NS = E + aud_n_new(P, V), n_placed = F.cntr[0];
+  if (blockIdx.x == 0 && threadIdx.x == 0) { F.meta[0] = aud_n_new(P, V); F.meta[1] = n_placed; F.meta[2] = F.cntr[1]; F.meta[3] = F.cntr[2]; F.meta[4] = F.cntr[3]; }
+  for (u32 p = blockIdx.x * 256u + threadIdx.x; p < np; p += gridDim.x * 256u) {
+    const i32 nd = aud_where(P, V, p, NS);
+    const bool ok = nd >= 0 && aud_fit_seq_ok(V, F, p, n_placed), unsched = GC(i32, V.pod_node)[p] == -1;
+    u32 f = (nd >= 0 && !ok) ? KS_AUDIT_POD_SEQ : 0u, chk = nd >= 0 ? 1u << 30 : 0u;
+    const u32 c = aud_class(P, V, p);
+    const u32 u1 = F.used[c];      // (ks_audit_ff_mark marked the class of every examined pod: never 0 for one)
+    if (!(ok || unsched) || !aud_fit_examinable(P, c) || !u1) { F.flags[p] = f; F.chk[p] = chk | (1u << 29); continue; }
+    const u32 u = u1 - 1u;
+    const u32 fe = F.first_e[u], fo = F.first_open[u], fm = F.first_m[u];
+    if (unsched) {
+      if (fe != KS_AF_NEVER) f |= KS_AUDIT_POD_FIT_EXISTING;
+      if (fo != KS_AF_NEVER) f |= KS_AUDIT_POD_FIT_NEW;
+      if (fm != KS_AF_NEVER) f |= KS_AUDIT_POD_FIT_TEMPLATE;
+    } else if ((u32)nd < E) {
+      if (fe < (u32)nd) f |= KS_AUDIT_POD_FIT_EXISTING;
+    } else {
+      const u32 j = (u32)nd - E, sq = (u32)GC(i32, V.pod_seq)[p];
+      if (fe != KS_AF_NEVER) f |= KS_AUDIT_POD_FIT_EXISTING;
+      if (sq == F.open[j]) {      // the opener of its node; a pod that joined a new node later is checked against existing nodes only (the order among new nodes depends on pod counts at the time)
+        if (fo < sq) f |= KS_AUDIT_POD_FIT_NEW;      // (strictly: its own node opened at sq)
+        const i32 m = GC(i32, V.n_tmpl)[j];
+        if (m >= 0 && (u32)m < P.M && fm < (u32)m) f |= KS_AUDIT_POD_FIT_TEMPLATE;
+      }
+    }
+    F.flags[p] = f; F.chk[p] = chk | 1u;
+  }
+}
+
+// ---- host half ----
+// One pooled block [meta | flags | checked words | scratch], one memset, the six launches, one read-back, the totals counted on the host.  The scratch of a problem is
+// 2P + 5C + 3E + 2ER + NMAX words: no slicing is needed.
+static int audit_firstfit_run(ks_dev_problem* const* ds, u32 n, const AuditView* results, ks_audit_firstfit* const* outs) {
+  BatchStage st; TRY(st.open(ds, n, nullptr, false));
+  const size_t o_view = st.add<AuditView>(n), o_fview = st.add<AuditFitView>(n);
+  TRY(st.place());
+  std::vector<size_t> o_fl(n), o_ck(n), o_scr(n); size_t at = 8 * (size_t)n; u32 pmax = 0; size_t emax = 1, nmax = 1;
+  for (u32 i = 0; i < n; ++i) { o_fl[i] = at; at += ds[i]->h.P; o_ck[i] = at; at += ds[i]->h.P; pmax = std::max(pmax, ds[i]->h.P); }
+  const size_t n_out = at;
+  for (u32 i = 0; i < n; ++i) {
+    const DevProb& h = ds[i]->h; at += at & 1; o_scr[i] = at;      // (the int64 sums come first: 8-byte aligned)
+    at += 2 * (size_t)h.E * h.R + h.E + h.P + 5 * (size_t)h.C + h.NMAX + 4;
+    const size_t used = std::min<size_t>(h.C, h.P);      // (no more classes are used than there are pods)
+    emax = std::max(emax, used * (((size_t)h.E + 255) / 256)); nmax = std::max(nmax, (used * ((size_t)h.NMAX + h.M) + 3) / 4);
+  }
+  TmpDev work(ds[0]->device); TRY(work.alloc(at * sizeof(u32)));
+  u32* w = work.as<u32>();
+  for (u32 i = 0; i < n; ++i) {
+    AuditView v = results[i]; AuditFitView t{}; const DevProb& h = ds[i]->h; const size_t Pn = h.P, Cn = h.C, En = h.E;
+    t.meta = w + 8 * (size_t)i; t.flags = w + o_fl[i]; t.chk = w + o_ck[i];
+    u32* s = w + o_scr[i]; t.esum = (u64*)s; s += 2 * En * h.R; t.epres = s; s += En; t.seqcnt = s; s += Pn; t.used = s; s += Cn; t.list = s; s += Cn;
+    t.first_e = s; s += Cn; t.first_open = s; s += Cn; t.first_m = s; s += Cn; t.open = s; s += h.NMAX; t.cntr = s;
+    v.meta = t.meta; v.mark = nullptr; v.pod_flags = nullptr; v.node_flags = nullptr; v.cnt = nullptr; v.off = nullptr; v.fill = nullptr; v.pods = nullptr;
+    st.h<AuditView>(o_view)[i] = v; st.h<AuditFitView>(o_fview)[i] = t;
+  }
+  const auto t0 = std::chrono::steady_clock::now();
+  TRY(st.upload(st.bytes));
+  HIPCHK(hipMemsetAsync(w, 0, at * sizeof(u32), st.stream()));
+  const u32 KS_GRID_Y_MAX = 65535u; const AuditView* dv = st.d<const AuditView>(o_view); const AuditFitView* df = st.d<const AuditFitView>(o_fview);
+  const u32 gx_p = std::max(1u, std::min(1024u, (pmax + 255u) / 256u)), gx_e = (u32)std::min<size_t>(4096, emax), gx_n = (u32)std::min<size_t>(4096, nmax);
+  for (u32 base = 0; base < n; base += KS_GRID_Y_MAX) {
+    const u32 ny = std::min(KS_GRID_Y_MAX, n - base);
+    hipLaunchKernelGGL(ks_audit_ff_count, dim3(gx_p, ny), dim3(256), 0, st.stream(), st.probs() + base, dv + base, df + base);
+    hipLaunchKernelGGL(ks_audit_ff_mark, dim3(gx_p, ny), dim3(256), 0, st.stream(), st.probs() + base, dv + base, df + base);
+    hipLaunchKernelGGL(ks_audit_ff_compact, dim3(ny), dim3(256), 0, st.stream(), st.probs() + base, df + base);
+    hipLaunchKernelGGL(ks_audit_ff_existing, dim3(gx_e, ny), dim3(256), 0, st.stream(), st.probs() + base, df + base);
+    hipLaunchKernelGGL(ks_audit_ff_new, dim3(gx_n, ny), dim3(256), 0, st.stream(), st.probs() + base, dv + base, df + base);
+    hipLaunchKernelGGL(ks_audit_ff_verdict, dim3(gx_p, ny), dim3(256), 0, st.stream(), st.probs() + base, dv + base, df + base);
+  }
+  HIPCHK(hipStreamSynchronize(st.stream())); HIPCHK(hipGetLastError());
+  const auto t1 = std::chrono::steady_clock::now();
+  std::vector<u32> back(n_out);
+  HIPCHK(hipMemcpy(back.data(), w, n_out * sizeof(u32), hipMemcpyDeviceToHost));
+  for (u32 i = 0; i < n; ++i) {
+    ks_audit_firstfit* o = outs[i]; const u32 Pn = ds[i]->h.P; const u32* meta = back.data() + 8 * (size_t)i;
+    o->n_pods = Pn; o->n_new = meta[0]; o->n_placed = meta[1]; o->skipped_pods = 0; o->n_pods_flagged = 0; o->checked[0] = o->checked[1] = 0; o->checked[2] = meta[3]; o->admitting_pairs = meta[4];
+    const u32* pf = back.data() + o_fl[i]; const u32* ck = back.data() + o_ck[i];
+    for (u32 k = 0; k < Pn; ++k) { if (pf[k]) ++o->n_pods_flagged; o->checked[0] += ck[k] >> 30; o->checked[1] += ck[k] & 1u; o->skipped_pods += (ck[k] >> 29) & 1u; }
+    if (o->pod_flags && Pn) memcpy(o->pod_flags, pf, (size_t)Pn * sizeof(u32));
+  }
+  const double kms = std::chrono::duration<double, std::milli>(t1 - t0).count(), rms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
+  for (u32 i = 0; i < n; ++i) { outs[i]->kernel_ms = kms; outs[i]->readback_ms = rms; }
+  return KS_OK;
+}
+extern "C" int ks_audit_firstfit_batch_dev(ks_dev_problem* const* ds, uint32_t n, ks_audit_firstfit* const* outs) {
+  if (!n) return KS_OK;
+  if (!ds || !outs) return fail(KS_ERR_INVALID, "null argument");
+  TRY(BatchStage::not_null(ds, n));
+  std::vector<AuditView> res(n);
+  for (u32 i = 0; i < n; ++i) {
+    if (!outs[i]) return fail(KS_ERR_INVALID, "null audit table");
+    if (ds[i]->device != ds[0]->device) return fail(KS_ERR_INVALID, "batch spans devices");
+    if (!ds[i]->solved) return fail(KS_ERR_INVALID, "audit of a problem that holds no result: solve it first (or the last solve failed)");
+    res[i] = audit_resident(ds[i]->hs);
+  }
+  return audit_firstfit_run(ds, n, res.data(), outs);
+}
+extern "C" int ks_audit_firstfit_dev(ks_dev_problem* d, const ks_result* claimed, ks_audit_firstfit* out) {
+  if (!d || !out) return fail(KS_ERR_INVALID, "null argument");
+  if (!claimed) return ks_audit_firstfit_batch_dev(&d, 1, &out);
+  if (d->view) return fail(KS_ERR_UNSUPPORTED, "a claimed result is audited against a flattened problem, not against a what-if derived on the device");
+  const DevProb& h = d->h; const u64 P = h.P, K = h.K, R = h.R, TW = h.TW, N = claimed->n_new;
+  if (N > h.NMAX) return fail(KS_ERR_INVALID, "claimed result: more new nodes than max_new_nodes");
+  if (claimed->n_unscheduled > P) return fail(KS_ERR_INVALID, "claimed result: more unscheduled pods than pods");
+  // what this pass reads of a result: the first pass's segments (pod_seq among them) without the unscheduled list
+#define KS_AUDIT_FIT_SEGS(X) \
+  X(pod_node, pod_node, i32, P) X(pod_stage, pod_stage, i32, P) X(pod_seq, pod_seq, i32, P) \
+  X(n_tmpl, node_tmpl, i32, N) X(n_alive, node_types, u64, N * TW) X(o_req, node_requests, i64, N * R) X(o_reqmask, node_requests_present, u32, N) \
+  X(o_present, node_present, u32, N) X(o_complement, node_complement, u32, N) X(o_mask, node_mask, u64, N * K) X(o_gt, node_gt, i32, N * K) X(o_lt, node_lt, i32, N * K) \
+  X(o_it, node_it_state, i32, N)
+#define X(sf, rf, T, cnt) if ((cnt) && !claimed->rf) return fail(KS_ERR_INVALID, "claimed result: null array " #rf);
+  KS_AUDIT_FIT_SEGS(X)
+#undef X
+  size_t bytes = 0;
+#define X(sf, rf, T, cnt) bytes += ks_pad8((cnt) * sizeof(T));
+  KS_AUDIT_FIT_SEGS(X)
+#undef X
+  std::vector<u64> blob(bytes / 8 + 1, 0); u8* hb = (u8*)blob.data();
+  HIPCHK(hipSetDevice(d->device));
+  TmpDev up(d->device); TRY(up.alloc(bytes + 8)); u8* db = up.as<u8>();
+  DevState s{}; size_t at = 0;
+#define X(sf, rf, T, cnt) { const size_t b_ = (cnt) * sizeof(T); if (b_) memcpy(hb + at, claimed->rf, b_); s.sf = (T*)(db + at); at += ks_pad8(b_); }
+  KS_AUDIT_FIT_SEGS(X)
+#undef X
+#undef KS_AUDIT_FIT_SEGS
+  { u32 c2[2] = {claimed->n_new, claimed->n_unscheduled}; memcpy(hb + at, c2, 8); s.out_counts = (u32*)(db + at); }
+  HIPCHK(hipMemcpy(db, hb, bytes + 8, hipMemcpyHostToDevice));
+  const AuditView v = audit_resident(s);
+  return audit_firstfit_run(&d, 1, &v, &out);
+}

@@ -4393,6 +4393,7 @@ extern "C" int ks_placement_rows_host(ks_dev_problem* const* ds, uint32_t n, con
 #include "ks_audit.inc"      // the audit of a result against its problem (ks_audit_dev / ks_audit_batch_dev)
 #include "ks_audit_topo.inc" // its second, opt-in pass: pod (anti-)affinity and hostname spread in commit order (ks_audit_topology_dev / ks_audit_topology_batch_dev)
 #include "ks_audit_spread.inc" // its third, opt-in pass: topology spread over narrow keys in commit order (ks_audit_spread_dev / ks_audit_spread_batch_dev)
+#include "ks_audit_firstfit.inc" // its fourth, opt-in pass: first-fit order from the final state and the commit numbers (ks_audit_firstfit_dev / ks_audit_firstfit_batch_dev)
 
 // ------------------------------------------------------------------------------------------------
 // Consolidation candidates (ksolve.h ks_consolidation_candidates_host): which nodes sortAndFilterCandidates keeps, and in what order.

@@ -43,6 +43,9 @@ KS_AUDIT_TOPOLOGY_RULES = ("SEQ", "ANTI_AFFINITY", "AFFINITY", "HOSTNAME_SPREAD"
 # the third pass's (FlatProblem.audit_spread() / audit_spread_batch()): SEQ as above, and spread over narrow keys
 KS_AUDIT_SPREAD_BITS = {"SEQ": 128, "SPREAD": 2048}
 KS_AUDIT_SPREAD_RULES = ("SEQ", "SPREAD")
+# the fourth pass's (FlatProblem.audit_firstfit() / audit_firstfit_batch()): SEQ as above, and first-fit order; `checked`: placed pods, examined pods, (class, node) pairs
+KS_AUDIT_FIRSTFIT_BITS = {"SEQ": 128, "FIT_EXISTING": 4096, "FIT_NEW": 8192, "FIT_TEMPLATE": 16384}
+KS_AUDIT_FIRSTFIT_CHECKED = ("SEQ", "PODS", "PAIRS")
 
 
 class KSolveError(RuntimeError):
@@ -363,6 +366,17 @@ class FlatProblem:
                 raise ValueError("audit_spread: pod_seq goes with a claimed result")
             return audit_spread_batch([self])[0]
         return _audit_spread_call([self], claimed, pod_seq)[0]
+
+    def audit_firstfit(self, claimed: Optional[dict] = None, pod_seq=None) -> dict:
+        """The audit's fourth, opt-in pass (include/ksolve.h KS_AUDIT_POD_FIT_*, kshost.h ksh_audit_firstfit / ksh_audit_firstfit_claimed): first-fit order -- no pod ended
+        later than an existing node, a new node or a template whose final state would still take it --, decided from the final state and the commit numbers.  Arguments
+        as `audit_topology`'s.  Returns {"pod_flags": uint32 [P], "n_pods_flagged", "pod_bit_count", "checked" (SEQ the placed pods, PODS the pods examined, PAIRS the
+        (class, node-or-template) pairs evaluated), "admitting_pairs", "skipped_pods", "n_new", "n_placed", "ms"}."""
+        if claimed is None:
+            if pod_seq is not None:
+                raise ValueError("audit_firstfit: pod_seq goes with a claimed result")
+            return audit_firstfit_batch([self])[0]
+        return _audit_firstfit_call([self], claimed, pod_seq)[0]
 
     def result(self) -> SolveResult:
         """Decode the result the handle holds (after `solve(decode=False)` or `solve_from_pods`)."""
@@ -851,7 +865,7 @@ class _AuditTopologyOut(ctypes.Structure):      # include/kshost.h ksh_audit_top
                [("checked", ctypes.c_uint32 * 4), ("pod_bit_count", ctypes.c_uint32 * 32)]
 
 
-def _audit_seq_pass(what: str, Out, flats: Sequence["FlatProblem"], claimed: Optional[dict], pod_seq):
+def _audit_seq_pass(what: str, Out, flats: Sequence["FlatProblem"], claimed: Optional[dict], pod_seq, more=()):
     """What the audit's passes over the commit order share (kshost.h ksh_audit_<what> / ksh_audit_<what>_claimed, out tables of type `Out`): the call over the resident
     results of `flats`, or over `claimed` with `pod_seq` for flats[0]; once more with larger tables if one was too short.  Returns (outs, pod_flags per problem, ms)."""
     import numpy as np
@@ -871,7 +885,7 @@ def _audit_seq_pass(what: str, Out, flats: Sequence["FlatProblem"], claimed: Opt
         ra.n_pods, ra.n_existing, ra.n_new, ra.n_unscheduled = d["P"], d["E"], int(claimed["n_new"]), len(claimed["unscheduled"])
         ra.types_words, ra.n_resources, ra.n_keys = (d["T"] + 63) // 64, d["R"], d["K"]
         for name, dt in (("pod_node", np.int32), ("pod_stage", np.int32), ("node_tmpl", np.int32), ("node_present", np.uint32), ("node_complement", np.uint32),
-                         ("node_mask", np.uint64), ("node_gt", np.int32), ("node_lt", np.int32)):
+                         ("node_mask", np.uint64), ("node_gt", np.int32), ("node_lt", np.int32)) + tuple(more):      # (more: the claimed arrays a pass reads beyond the second's)
             a = np.ascontiguousarray(np.asarray(claimed[name], dtype=dt).reshape(-1))
             if not len(a):
                 a = np.zeros(1, dtype=dt)      # (a table of no elements is still a table: never NULL)
@@ -935,6 +949,29 @@ def audit_spread_batch(flats: Sequence["FlatProblem"]) -> List[dict]:
     """The audit's third pass over the results the last solve left on the device, for a whole batch (include/kshost.h ksh_audit_spread): handles of any kind, derived
     what-ifs included.  One dict per problem, as `FlatProblem.audit_spread` returns it."""
     return _audit_spread_call(flats)
+
+
+class _AuditFirstFitOut(ctypes.Structure):      # include/kshost.h ksh_audit_firstfit_out
+    _fields_ = [("pod_flags", ctypes.c_void_p), ("cap_pods", ctypes.c_uint64)] + \
+               [(n, ctypes.c_uint32) for n in ("n_pods", "n_new", "n_placed", "skipped_pods", "n_pods_flagged", "truncated")] + \
+               [("checked", ctypes.c_uint32 * 3), ("admitting_pairs", ctypes.c_uint32)]
+
+
+def _audit_firstfit_call(flats: Sequence["FlatProblem"], claimed: Optional[dict] = None, pod_seq=None) -> List[dict]:
+    import numpy as np
+    if not len(flats):
+        return []
+    more = (("node_types", np.uint64), ("node_requests", np.int64), ("node_requests_present", np.uint32), ("node_it_state", np.int32))
+    outs, flags, ms = _audit_seq_pass("firstfit", _AuditFirstFitOut, flats, claimed, pod_seq, more)
+    return [{"pod_flags": flags[i], "n_pods_flagged": int(o.n_pods_flagged), "pod_bit_count": {k: int(((flags[i] & v) != 0).sum()) for k, v in KS_AUDIT_FIRSTFIT_BITS.items()},
+             "checked": {k: int(o.checked[j]) for j, k in enumerate(KS_AUDIT_FIRSTFIT_CHECKED)}, "admitting_pairs": int(o.admitting_pairs), "skipped_pods": int(o.skipped_pods),
+             "n_new": int(o.n_new), "n_placed": int(o.n_placed), "ms": ms} for i, o in enumerate(outs)]
+
+
+def audit_firstfit_batch(flats: Sequence["FlatProblem"]) -> List[dict]:
+    """The audit's fourth pass over the results the last solve left on the device, for a whole batch (include/kshost.h ksh_audit_firstfit): handles of any kind, derived
+    what-ifs included.  One dict per problem, as `FlatProblem.audit_firstfit` returns it."""
+    return _audit_firstfit_call(flats)
 
 
 def deal_lpt(weights: Sequence[int], nshards: int) -> List[int]:

@@ -1,0 +1,291 @@
+"""What tests/test_audit_firstfit.py (on the lane-fibre emulator) and tests/test_audit_firstfit_gpu.py (on the device) share: the comparison of the audit's fourth
+pass with its reference (tests/audit_firstfit_ref.py), the hand-made problems -- generic pods over existing nodes, new nodes and two templates, where the reference's
+first fit is known from how the problem was made --, the tamper matrix and the shapes at which the kernels take another path.  Every function takes the scheduler
+module `S` it is to go through (the HIP libraries' or the emulator's)."""
+import copy
+
+import numpy as np
+
+import audit_cases as C
+import audit_firstfit_ref as FR
+import audit_topo_cases as TC
+from karpenter_core_amd import fake
+from karpenter_core_amd.model import LABEL_INSTANCE_TYPE, Problem
+
+B = FR.BITS
+FIT = B["FIT_EXISTING"] | B["FIT_NEW"] | B["FIT_TEMPLATE"]
+
+
+def compare(S, flat, claimed=None, pod_seq=None):
+    """(device pass, reference flags) of the result `flat` holds -- or of `claimed` with `pod_seq` --, after asserting that device and reference agree bit for bit,
+    `checked`, `admitting_pairs` and `skipped_pods` included, and that the device's totals are the totals of its own flags."""
+    dev = flat.audit_firstfit(claimed, pod_seq)
+    res = flat.result_arrays() if claimed is None else claimed
+    prob = FR.problem_arrays(S, flat)
+    seq = TC.commit_numbers(S, flat, prob) if pod_seq is None else pod_seq
+    flags, checked, admitting, skipped = FR.audit(prob, res, seq)
+    bad = np.nonzero(dev["pod_flags"] != flags)[0]
+    assert not len(bad), (bad[:8], dev["pod_flags"][bad][:8], flags[bad][:8])
+    assert dev["checked"] == dict(zip(FR.CHECKED, checked)), (dev["checked"], checked)
+    assert dev["admitting_pairs"] == admitting, (dev["admitting_pairs"], admitting)
+    assert dev["skipped_pods"] == skipped, (dev["skipped_pods"], skipped)
+    assert dev["n_pods_flagged"] == int((flags != 0).sum())
+    assert dev["pod_bit_count"] == {k: int(((flags & v) != 0).sum()) for k, v in B.items()}
+    assert dev["checked"]["PODS"] + dev["skipped_pods"] == len(flags)
+    return dev, flags
+
+
+def assert_clean(S, flat):
+    dev, flags = compare(S, flat)
+    assert not flags.any() and dev["n_pods_flagged"] == 0, {k: int(((flags & v) != 0).sum()) for k, v in B.items()}
+    return dev
+
+
+def summary(dev):
+    return {"pods": {k: v for k, v in dev["pod_bit_count"].items() if v}, "checked": [dev["checked"][k] for k in FR.CHECKED], "admitting": dev["admitting_pairs"],
+            "skipped": dev["skipped_pods"], "n_new": dev["n_new"], "n_placed": dev["n_placed"]}
+
+
+def with_generic_pods(pr: Problem, n: int = 3) -> Problem:
+    """`pr` with a few pods under no constraint at all at the end of its list: whatever else the problem holds, some pod of it is examined."""
+    pr = copy.copy(pr)
+    pr.pods = list(pr.pods) + [TC._pod("zz-generic-%d" % i, cpu="10m", mem="8Mi") for i in range(n)]
+    return pr
+
+
+def _claimable(res):
+    return copy.deepcopy({k: v for k, v in res.items() if k != "key_value"})
+
+
+def flagged(flags):
+    return {int(i): int(flags[i]) for i in np.nonzero(flags)[0]}
+
+
+# ---------------------------------------------------------------------------------------------------------------- the tamper matrix
+TAMPER_NAMES = ["a generic pod moved to a later existing node with room", "the last pod of a new node claimed as the opener of an added node",
+                "a placed generic pod claimed unscheduled", "an opener's node re-templated to the heavier template", "two pods given one commit number"]
+N_PLAIN, N_BIG = 6, 3
+BIG_TYPE = "fake-it-5"
+
+
+def _small(name, zone):
+    return C._node(name, zone, "2")      # 2 cores available: the plain pods fit, a big pod does not
+
+
+def tamper_problem() -> Problem:
+    """Two existing nodes with two cores to spare each, two provisioners without limits (`open` before `second`), and pods under no topology constraint: six of 100m --
+    first fit puts them all on e0 -- and three of 2.5 cores that name the six-core type: no existing node holds one, the first opens a machine of `open`, the second
+    joins it, the third opens another."""
+    its = fake.instance_types(6)
+    provs = [fake.provisioner("open", len(its), weight=10), fake.provisioner("second", len(its), weight=1)]
+    pods = [TC._pod("big-%d" % i, cpu="2500m", mem="1Gi", node_selector={LABEL_INSTANCE_TYPE: BIG_TYPE}) for i in range(N_BIG)] + [TC._pod("plain-%d" % i) for i in range(N_PLAIN)]
+    return Problem(instance_types=its, provisioners=provs, pods=pods, nodes=[_small("e0", C.Z1), _small("e1", C.Z2)], extra_well_known=fake.EXTRA_WELL_KNOWN)
+
+
+def check_genuine(res, seq):
+    """The genuine result is the one `tamper_problem` describes; returns (the big pods in commit order, the plain pods)."""
+    big, plain = list(range(N_BIG)), list(range(N_BIG, N_BIG + N_PLAIN))
+    assert res["n_existing"] == 2 and res["n_new"] == 2 and not len(res["unscheduled"]), (res["n_existing"], res["n_new"], res["unscheduled"])
+    assert all(int(res["pod_node"][p]) == 0 for p in plain), res["pod_node"]
+    big.sort(key=lambda p: int(seq[p]))
+    assert [int(res["pod_node"][p]) for p in big] == [2, 2, 3] and list(res["node_tmpl"]) == [0, 0], (res["pod_node"], res["node_tmpl"])
+    assert sorted(int(s) for s in seq) == list(range(N_BIG + N_PLAIN))
+    return big, plain
+
+
+def tampers(res, seq, prob):
+    """[(name, edited copy of `res`, edited copy of `seq`, the tampered pod, the bits it must carry, True if nothing else may be flagged)]"""
+    big, plain = check_genuine(res, seq)
+    R, K, TW = prob["R"], prob["K"], (prob["T"] + 63) // 64
+    out = []
+
+    def case(name):
+        r, s = _claimable(res), np.array(seq, dtype=np.int32)
+        out.append([name, r, s, None, 0, False])
+        return r, s, out[-1]
+    r, s, o = case(TAMPER_NAMES[0])      # e0 still has room for it
+    r["pod_node"][plain[2]] = 1
+    o[3:] = [plain[2], B["FIT_EXISTING"], True]
+    r, s, o = case(TAMPER_NAMES[1])      # the second big pod leaves node 2 for an added node 4 of the same template and type: node 2, opened earlier, has room again
+    q = big[1]
+    c = int(prob["stage_cls"][int(prob["pod_stage_off"][q]) + int(r["pod_stage"][q])])
+    req = np.asarray(r["node_requests"], dtype=np.int64).reshape(-1, R).copy()
+    mine = prob["cls_requests"][c * R:(c + 1) * R].astype(np.int64)
+    tmpl = int(r["node_tmpl"][0])
+    added = prob["tmpl_daemon"][tmpl * R:(tmpl + 1) * R].astype(np.int64) + mine
+    req[0] -= mine
+    r["node_requests"] = np.concatenate([req, added[None, :]]).reshape(-1)
+    for name, width in (("node_tmpl", 1), ("node_types", TW), ("node_requests_present", 1), ("node_present", 1), ("node_complement", 1), ("node_mask", K), ("node_gt", K), ("node_lt", K),
+                        ("node_it_state", 1)):
+        a = np.asarray(r[name]).reshape(-1, width)
+        r[name] = np.concatenate([a, a[0:1]]).reshape(-1)      # (every big pod is of one class: the added node's requirements, presence masks and options are node 2's)
+    r["n_new"] = 3
+    r["pod_node"][q] = 4
+    o[3:] = [q, B["FIT_NEW"], False]      # (the third big pod opened its machine while node 2 -- as claimed -- had room: the reference says so too)
+    r, s, o = case(TAMPER_NAMES[2])      # e0 and e1, node 3 (one big pod on six cores) and a fresh machine would all take it
+    q = plain[4]
+    r["pod_node"][q] = -1
+    s[s > s[q]] -= 1
+    s[q] = -1
+    r["unscheduled"] = np.array([q], dtype=np.int32)
+    o[3:] = [q, FIT, True]
+    r, s, o = case(TAMPER_NAMES[3])      # template 0 takes the first big pod on a fresh machine: it cannot have opened one of template 1
+    r["node_tmpl"][0] = 1
+    o[3:] = [big[0], B["FIT_TEMPLATE"], False]
+    r, s, o = case(TAMPER_NAMES[4])
+    s[plain[1]] = s[plain[0]]
+    o[3:] = [plain[0], B["SEQ"], False]
+    assert [x[0] for x in out] == TAMPER_NAMES
+    return out
+
+
+def _verdict(S, flat, claimed, s, pod, bits, alone):
+    try:
+        dev, flags = compare(S, flat, claimed, s)
+    except AssertionError as e:
+        return "device and reference differ: %s" % (e,)
+    got = flagged(dev["pod_flags"])
+    if got.get(pod) != bits:
+        return "pod %d carries %s, expected %d: %s" % (pod, got.get(pod), bits, got)
+    if alone and set(got) != {pod}:
+        return "flags %s, expected pod %d alone" % (got, pod)
+    return True
+
+
+def run_tamper_matrix(S):
+    """Solve `tamper_problem`, audit the genuine result (clean) and every edit through the claimed form; returns [(name, True or what differs)]."""
+    flat = S.FlatProblem(tamper_problem())
+    flat.solve(decode=False)
+    dev = assert_clean(S, flat)
+    assert flat.dims["M"] == 2 and dev["skipped_pods"] == 0 and dev["checked"]["PODS"] == N_BIG + N_PLAIN and dev["admitting_pairs"] > 0, dev
+    res, seq, prob = flat.result_arrays(), flat.pod_seq(), FR.problem_arrays(S, flat)
+    report = []
+    for name, claimed, s, pod, bits, alone in tampers(res, seq, prob):
+        ok = _verdict(S, flat, claimed, s, pod, bits, alone)
+        if ok is True and name == TAMPER_NAMES[1]:      # the edit is consistent: the first pass finds nothing in it
+            first = flat.audit(claimed)
+            if first["n_pods_flagged"] or first["n_nodes_flagged"]:
+                ok = "the first pass flags the edit: %s %s" % (first["pod_bit_count"], first["node_bit_count"])
+        if ok is True and name == TAMPER_NAMES[4]:      # SEQ and nothing else, on both pods
+            got = flagged(flat.audit_firstfit(claimed, s)["pod_flags"])
+            if sorted(got.values()) != [B["SEQ"], B["SEQ"]]:
+                ok = "flags %s, expected SEQ on two pods" % (got,)
+        report.append((name, ok))
+    flat.close()
+    return report
+
+
+# ---------------------------------------------------------------------------------------------------------------- shapes where the kernels take another path
+TYPE_SHAPES = [(1, 0), (64, 63), (65, 64), (130, 129)]
+NODE_SHAPES = [(65, 0), (65, 63), (257, 0), (257, 255)]
+SHAPE_NAMES = ["T = %d: the only admitting type at bit %d" % ts for ts in TYPE_SHAPES] + ["E = 0", "n_new = 0", "P = 1 and exactly one used class", "257 used classes"] + \
+              ["E = %d: the only admitting node at index %d" % ns for ns in NODE_SHAPES] + ["a node with 1 100 pods", "12 resource names", "two templates"]
+
+
+def one_type_fits(T: int) -> Problem:
+    """The ladder of T types -- type i has i + 1 cores -- and one pod that only the largest holds."""
+    its = fake.instance_types(T)
+    return Problem(instance_types=its, provisioners=[fake.provisioner("open", len(its))], pods=[TC._pod("wide", cpu="%dm" % (T * 1000 - 500), mem="64Mi")], nodes=[], extra_well_known=fake.EXTRA_WELL_KNOWN)
+
+
+def one_node_fits(E: int, at: int) -> Problem:
+    """E existing nodes, all full but node `at`, and two pods."""
+    its = fake.instance_types(4)
+    nodes = [TC._roomy("e%03d" % i, C.Z1) if i == at else C._node("e%03d" % i, C.Z1, "50m") for i in range(E)]
+    return Problem(instance_types=its, provisioners=[fake.provisioner("open", len(its))], pods=[TC._pod("p0"), TC._pod("p1")], nodes=nodes, extra_well_known=fake.EXTRA_WELL_KNOWN)
+
+
+def many_classes(n: int) -> Problem:
+    """n pods of n different requests on two roomy existing nodes: n classes, all on e0."""
+    its = fake.instance_types(4)
+    return Problem(instance_types=its, provisioners=[fake.provisioner("open", len(its))], pods=[TC._pod("c%03d" % i, cpu="%dm" % (i + 1)) for i in range(n)],
+                   nodes=[TC._roomy("e0", C.Z1), TC._roomy("e1", C.Z2)], extra_well_known=fake.EXTRA_WELL_KNOWN)
+
+
+def crowded_node(n: int) -> Problem:
+    """n + 1 pods of one millicore; e0 has exactly n millicores to spare, e1 is roomy: n on e0, the last on e1 -- which is right only if e0's sum is n to the unit."""
+    its = fake.instance_types(4)
+    e0 = TC._roomy("e0", C.Z1)
+    e0.available = {"cpu": "%dm" % n, "memory": "64Gi", "pods": "2000"}
+    return Problem(instance_types=its, provisioners=[fake.provisioner("open", len(its))], pods=[TC._pod("m%04d" % i, cpu="1m", mem="1Mi") for i in range(n + 1)],
+                   nodes=[e0, TC._roomy("e1", C.Z2)], extra_well_known=fake.EXTRA_WELL_KNOWN)
+
+
+def wide_problem() -> Problem:
+    from karpenter_core_amd import workloads as W
+    return with_generic_pods(W.wide_catalogue(names=12, pods=60, types=10, existing=4, seed=3, dense=True))
+
+
+def run_shapes(S):
+    """[(name, True or what differs)] -- each shape solved (clean by device and reference) and, where it says so, one claimed edit."""
+    report = []
+
+    def shape(name, make, body):
+        flat = S.FlatProblem(make())
+        try:
+            flat.solve(decode=False)
+            dev = assert_clean(S, flat)
+            ok = body(flat, dev)
+        except AssertionError as e:
+            ok = "%s" % (e,)
+        flat.close()
+        report.append((name, ok))
+
+    def claim(flat, edit):
+        res, seq = _claimable(flat.result_arrays()), np.array(flat.pod_seq(), dtype=np.int32)
+        edit(res, seq)
+        dev, flags = compare(S, flat, res, seq)
+        return flagged(flags)
+
+    def last_type(T, bit):
+        def body(flat, dev):
+            res = flat.result_arrays()
+            words = np.asarray(res["node_types"], dtype=np.uint64).reshape(-1, (T + 63) // 64)
+            assert flat.dims["T"] == T and res["n_new"] == 1 and [int(w) for w in words[0]] == [(1 << (bit % 64)) if i == bit // 64 else 0 for i in range(words.shape[1])], (flat.dims, words)
+            assert dev["checked"] == {"SEQ": 1, "PODS": 1, "PAIRS": 2} and dev["admitting_pairs"] == 1, dev      # the fresh machine admits; the pod's own, with the pod on it, does not
+
+            def unschedule(r, s):
+                r["pod_node"][0], s[0], r["unscheduled"] = -1, -1, np.array([0], dtype=np.int32)
+            got = claim(flat, unschedule)      # the walk over the types must reach the one bit to say so
+            assert got == {0: B["FIT_TEMPLATE"]}, got
+            return True
+        return body
+    for (T, bit), name in zip(TYPE_SHAPES, SHAPE_NAMES):
+        shape(name, lambda T=T: one_type_fits(T), last_type(T, bit))
+    shape("E = 0", lambda: TC.plain(3), lambda flat, dev: True if flat.dims["E"] == 0 and dev["n_new"] == 1 and dev["checked"] == {"SEQ": 3, "PODS": 3, "PAIRS": 2} else str(dev))
+    shape("n_new = 0", lambda: TC.plain(3, True), lambda flat, dev: True if dev["n_new"] == 0 and dev["checked"] == {"SEQ": 3, "PODS": 3, "PAIRS": 2} and dev["admitting_pairs"] == 2 else str(dev))
+    shape("P = 1 and exactly one used class", lambda: TC.plain(1), lambda flat, dev: True if flat.dims["P"] == 1 and dev["checked"] == {"SEQ": 1, "PODS": 1, "PAIRS": 2} else str(dev))
+
+    def classes_257(flat, dev):
+        assert flat.dims["C"] >= 257 and dev["checked"] == {"SEQ": 257, "PODS": 257, "PAIRS": 257 * 3} and dev["admitting_pairs"] == 257 * 3 and dev["n_new"] == 0, dev
+
+        def move(r, s):
+            r["pod_node"][256] = 1
+        got = claim(flat, move)      # the class past the scan tile finds its own row of the first_* tables
+        assert got == {256: B["FIT_EXISTING"]}, got
+        return True
+    shape("257 used classes", lambda: many_classes(257), classes_257)
+
+    def only_node(E, at):
+        def body(flat, dev):
+            res = flat.result_arrays()
+            assert flat.dims["E"] == E and [int(x) for x in res["pod_node"]] == [at, at] and dev["checked"]["PAIRS"] == E + 1 and dev["admitting_pairs"] == 2, (res["pod_node"], dev)
+
+            def move(r, s):
+                r["pod_node"][1] = E - 1
+            got = claim(flat, move)      # the minimum over the existing nodes crosses lanes, waves and workgroups
+            assert got == {1: B["FIT_EXISTING"]}, got
+            return True
+        return body
+    for (E, at), name in zip(NODE_SHAPES, SHAPE_NAMES[8:12]):
+        shape(name, lambda E=E, at=at: one_node_fits(E, at), only_node(E, at))
+
+    def crowd(flat, dev):
+        where = np.asarray(flat.result_arrays()["pod_node"])
+        assert int((where == 0).sum()) == 1100 and int((where == 1).sum()) == 1 and dev["checked"] == {"SEQ": 1101, "PODS": 1101, "PAIRS": 3} and dev["admitting_pairs"] == 2, (dev, (where == 0).sum())
+        return True
+    shape("a node with 1 100 pods", lambda: crowded_node(1100), crowd)
+    shape("12 resource names", wide_problem, lambda flat, dev: True if flat.dims["R"] == 12 and dev["checked"]["PODS"] >= 3 and dev["admitting_pairs"] > 0 else str((flat.dims, dev)))
+    shape("two templates", tamper_problem, lambda flat, dev: True if flat.dims["M"] == 2 and dev["checked"]["PAIRS"] == 2 * (2 + 2 + 2) else str(dev))
+    assert [r[0] for r in report] == SHAPE_NAMES
+    return report
