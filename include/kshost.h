@@ -598,6 +598,26 @@ int ksh_audit_firstfit(void** handles, uint32_t n, ksh_audit_firstfit_out* outs 
 /* A claimed result for one flattened handle, as ksh_audit_topology_claimed takes it; this pass also reads node_types, node_requests, node_requests_present and
  * node_it_state of the claimed arrays. */
 int ksh_audit_firstfit_claimed(void* handle, const ksh_result_arrays* claimed, const int32_t* pod_seq /* [n_pods] */, ksh_audit_firstfit_out* out, double* ms /* [2] or NULL */);
+/* The audit's FIFTH pass, opt-in (ksolve.h ks_audit_limits_dev, KS_AUDIT_NODE_LIMIT_*, KS_AUDIT_POD_LIMIT_TEMPLATE): provisioner limits -- no machine of a limited
+ * provisioner keeps a type above what can have remained when it opened, none lacks a type that must have remained, and no pod passed over a limited provisioner that
+ * still had room for it -- decided from the final state and the commit numbers.  The shim's gate is the five passes in order: ksh_audit, ksh_audit_topology,
+ * ksh_audit_spread, ksh_audit_firstfit, then this, and on a finding of any, solve in Go.  The fourth pass's conventions for the pods (cap_pods,
+ * KSH_AUDIT_TRUNCATED_PODS) and ksh_audit's for the nodes (cap_nodes, KSH_AUDIT_TRUNCATED_NODES; node n as ksh_audit numbers it).  limited_templates == 0: the
+ * problem has no limits and nothing but the commit numbers was examined.  checked[0]: the placed pods; [1]: the new nodes of limited templates examined; [2]: the pods
+ * examined (skipped_pods: the others); [3]: the (class, template) pairs evaluated.  exact_nodes: the nodes for which the rule was the reference's own test;
+ * binding_nodes: the nodes whose limit excluded a type -- a clean result with none of them proved little; skipped_nodes: the new nodes without an opening order. */
+typedef struct ksh_audit_limits_out {
+  uint32_t* pod_flags; uint64_t cap_pods;      /* [cap_pods] KS_AUDIT_POD_SEQ | KS_AUDIT_POD_LIMIT_TEMPLATE */
+  uint32_t* node_flags; uint64_t cap_nodes;    /* [cap_nodes] KS_AUDIT_NODE_LIMIT_* */
+  uint32_t n_pods, n_nodes, n_new, n_placed;
+  uint32_t limited_templates, skipped_nodes, skipped_pods, truncated /* KSH_AUDIT_TRUNCATED_* */;
+  uint32_t n_pods_flagged, n_nodes_flagged, exact_nodes, binding_nodes;
+  uint32_t checked[4];
+  uint32_t pod_bit_count[32], node_bit_count[32];
+} ksh_audit_limits_out;
+int ksh_audit_limits(void** handles, uint32_t n, ksh_audit_limits_out* outs /* [n] */, double* ms /* [2] kernels | read-back, or NULL */);
+/* A claimed result for one flattened handle, exactly as ksh_audit_firstfit_claimed takes it. */
+int ksh_audit_limits_claimed(void* handle, const ksh_result_arrays* claimed, const int32_t* pod_seq /* [n_pods] */, ksh_audit_limits_out* out, double* ms /* [2] or NULL */);
 
 /* ---- the snapshot kept current by EVENTS ("cached incremental SoA builder fed from state.Cluster") ----
  * Replaces, for the snapshot consolidation simulates over, what the reference does between two passes of the deprovisioner (deprovisioning/controller.go:64,

@@ -693,7 +693,8 @@ int ks_placement_rows_host(ks_dev_problem* const* ds, uint32_t n, const uint64_t
  * decides together with the commit numbers is the second, opt-in pass below (ks_audit_topology_dev: pod (anti-)affinity, hostname spread).  Audited by neither:
  * spread over narrow keys, hostname spread under a node filter, self-selecting affinity, groups created by a later Topology.Update, provisioner limits (subtractMax
  * depends on the order), first-fit optimality (whether an earlier node would have taken the pod).  (Spread over narrow keys, unfiltered, is now the third pass's:
- * ks_audit_spread_dev; first-fit order, for the pods no topology group constrains, the fourth pass's: ks_audit_firstfit_dev.)
+ * ks_audit_spread_dev; first-fit order, for the pods no topology group constrains, the fourth pass's: ks_audit_firstfit_dev; provisioner limits, bounded from
+ * both sides in opening order, the fifth pass's: ks_audit_limits_dev -- KS_AUDIT_NODE_LIMIT_MISSING there is OPTIONS_MISSING for limited templates.)
  * The caller owns the tables: pod_flags [P] and node_flags [E + max_new_nodes] (of which E + n_new are written), either may be NULL (totals only).  Flags are written
  * per index -- no list is appended through an atomic -- so the output is the same every run. */
 typedef struct ks_audit {
@@ -733,7 +734,8 @@ int ks_audit_sizes(const ks_dev_problem* d, uint32_t* n_pods /* P */, uint32_t* 
  * well-known label: such a node is Compatible with any requirement on it (requirements.go:123-133) and keeps its labels here, so the pair is not examined.
  * NOT attempted: spread over narrow keys (the chosen domain depends on a minimum at the time), hostname spread under a node filter (Counts depends on the node's
  * requirements at the time), self-selecting affinity, late-created groups, provisioner limits, first-fit optimality.  (Spread over narrow keys is now the third
- * pass's, ks_audit_spread_dev below: the minimum at the time is a prefix count over the commit order.) */
+ * pass's, ks_audit_spread_dev below: the minimum at the time is a prefix count over the commit order.  Provisioner limits are the fifth pass's,
+ * ks_audit_limits_dev.) */
 typedef struct ks_audit_topology {
   uint32_t* pod_flags;            /* [P] KS_AUDIT_POD_SEQ .. KS_AUDIT_POD_HOSTNAME_SPREAD, or NULL (totals only) */
   uint32_t n_pods, n_new;         /* out: P | the new nodes of the result that was audited */
@@ -829,7 +831,8 @@ int ks_audit_spread_batch_dev(ks_dev_problem* const* ds, uint32_t n, ks_audit_sp
 #define KS_AUDIT_POD_FIT_TEMPLATE 16384u    /* P opened a node of template m and first_m(c) < m; or P is unscheduled and first_m(c) exists */
 /* A pod on a new node it did not open is checked against existing nodes only: the order among new nodes at the time depends on pod counts at the time (sort.Slice,
  * scheduler.go:183).  NOT attempted: topology-constrained pods (the next step would be hostname anti-affinity and unfiltered hostname spread, whose per-node counts
- * also only grow), pods with host ports, limited templates, existing nodes on keys they do not label, the order among new nodes, provisioner limits. */
+ * also only grow), pods with host ports, limited templates, existing nodes on keys they do not label, the order among new nodes, provisioner limits.  (Limited
+ * templates and provisioner limits are the fifth pass's, ks_audit_limits_dev below: KS_AUDIT_POD_LIMIT_TEMPLATE is FIT_TEMPLATE for them.) */
 typedef struct ks_audit_firstfit {
   uint32_t* pod_flags;            /* [P] KS_AUDIT_POD_SEQ | KS_AUDIT_POD_FIT_*, or NULL (totals only) */
   uint32_t n_pods, n_new;         /* out: P | the new nodes of the result that was audited */
@@ -847,6 +850,53 @@ typedef struct ks_audit_firstfit {
  * same flags every run.  Refusals as ks_audit_spread_dev's. */
 int ks_audit_firstfit_dev(ks_dev_problem* d, const ks_result* claimed /* or NULL; pod_seq is read */, ks_audit_firstfit* out);
 int ks_audit_firstfit_batch_dev(ks_dev_problem* const* ds, uint32_t n, ks_audit_firstfit* const* outs);
+
+/* ---- the audit's FIFTH pass, opt-in: PROVISIONER LIMITS in OPENING ORDER.  Nothing calls it unless asked; the first four passes are unchanged by it.  Before it
+ * opens a machine of a provisioner with limits scheduler.add keeps only the types whose Capacity is within the provisioner's remaining resources
+ * (filterByRemainingResources, scheduler.go:197-206,293-309), and after the opener's Add it takes the MaxResources of the node's options off them (subtractMax,
+ * scheduler.go:215,273-290).  remainingResources depends on the order of opening -- but a node's options only shrink, so the final state and pod_seq bound it from
+ * both sides, and every bit below flags only what no run of the reference can have produced.  The pod bit shares its word with KS_AUDIT_POD_SEQ, defined as in the
+ * second pass; the node bits continue KS_AUDIT_NODE_* in a word of this pass's own (ks_audit_limits.node_flags).
+ * Template m is LIMITED when lim = tmpl_limit_present[m] != 0xFFFFFFFF; lim == 0 (Spec.Limits non-nil and empty) is limited with no limited resource.  "On lim": over
+ * the resources r whose bit is set in lim.  cap[t][r] = it_cap[r*T+t].  R0[m] = tmpl_remaining[m*R..] (a derived what-if: its own table).
+ * open(j): the fourth pass's -- the least pod_seq over the pods on new node j that do not fail SEQ; that pod is j's OPENER.  A new node without such a pod, or with
+ * node_tmpl outside [0, M), is UNORDERED and counted in skipped_nodes (where the problem has a limited template at all).  The ordered nodes of a limited template
+ * are taken in the order of open(j), not of j (a result may come from a Go run, where sort.Slice has permuted newNodes); i < j: same template, opened earlier.  A
+ * limited template with an unordered node gets the EXTRA rule only, over its ordered nodes: without that node a lower bound of its remaining is not one.
+ *   mc(j)[r] = max(0, max over t in node_types[j], t < T, of cap[t][r]): the final options' MaxResources.
+ *   U_j = R0[m] - sum over i < j of mc(i), on lim: an UPPER bound of the remaining just before j opened (the options at opening include the final ones, so what
+ *         subtractMax took is at least mc(i)).  For an unordered node of a limited template U_j = R0[m].
+ *   W_j = the t in tmpl_types[m] with cap[t] <= U_j on lim that pass compatible && fits && hasOffering (node.go:137-159) for a fresh node of m holding only j's
+ *         opener: the fourth pass's per-type test of admits_template for the opener's final-stage class -- a superset of the options subtractMax saw (a
+ *         topology-constrained opener only narrows further).  mw(j) = max(0, MaxResources over W_j).
+ *   L_m[k] = R0[m] - the sum of mw over the first k openings of m, k = 0 .. n_m: a LOWER bound, non-increasing in k.  L_j = L_m[the openings before j].
+ *   Node j is EXACT when mw(i) == mc(i) on lim for every i < j: there L_j == U_j and the rule is the reference's own test.
+ * Sums are int64 and saturating; caps are taken as non-negative, a remaining that would pass below INT64_MIN stays there. */
+#define KS_AUDIT_NODE_LIMIT_EXTRA 256u      /* new node j of a limited template: some t in node_types[j] has cap[t][r] > U_j[r] for an r in lim (filterByRemainingResources, scheduler.go:293-309) */
+#define KS_AUDIT_NODE_LIMIT_MISSING 512u    /* new node j of an ordered limited template: some t in tmpl_types[m] is absent from node_types[j] although cap[t] <= L_j on lim and t passes the first pass's final-state filter for node j (the test behind KS_AUDIT_NODE_OPTIONS_MISSING; the filter is monotone): the equality the first pass grants unlimited templates, wherever the bound reaches */
+#define KS_AUDIT_POD_LIMIT_TEMPLATE 32768u  /* P examined as in the fourth pass (no constraining group, no host ports; it does not fail SEQ, or it is unscheduled).  P opened a node of template m': for an ordered limited m < m', k = the openings of m with open < seq(P); P is unscheduled: for every ordered limited m, k = n_m (remaining only falls, so the end state bounds every attempt).  Flagged when admits_template's scalar clauses hold for (c, m) and some t in tmpl_types[m] has cap[t] <= L_m[k] on lim and passes the fresh-node type test: the fourth pass's FIT_TEMPLATE, extended to limited templates */
+/* NOT attempted: pod_reason's KS_WHY_LIMITS nibble; tmpl_remaining itself (the caller's input); topology-constrained openers on the pod side. */
+typedef struct ks_audit_limits {
+  uint32_t* pod_flags;            /* [P] KS_AUDIT_POD_SEQ | KS_AUDIT_POD_LIMIT_TEMPLATE, or NULL (totals only) */
+  uint32_t* node_flags;           /* [E + max_new_nodes] KS_AUDIT_NODE_LIMIT_*; entries [0, n_nodes) are written (an existing node's is 0); or NULL */
+  uint32_t n_pods, n_nodes;       /* out: P | E + n_new */
+  uint32_t n_new, n_placed;       /* out: the new nodes of the result that was audited | pods on a node of the result */
+  uint32_t limited_templates;     /* out: the limited templates of the problem; 0: nothing but SEQ was examined, and every count below is 0 */
+  uint32_t skipped_nodes, skipped_pods;   /* out: the unordered new nodes | the pods that are not examined */
+  uint32_t n_pods_flagged, n_nodes_flagged;
+  uint32_t pod_bit_count[32], node_bit_count[32];   /* out: pods / nodes carrying bit i */
+  uint32_t checked[4];            /* out: [0] the placed pods (SEQ); [1] the new nodes of limited templates examined; [2] the pods examined; [3] the (class, ordered limited template) pairs evaluated, over the distinct classes of the examined pods */
+  uint32_t exact_nodes;           /* out: the exact nodes of the ordered limited templates */
+  uint32_t binding_nodes;         /* out: the nodes whose U_j excluded at least one type of tmpl_types[m].  A clean result with binding_nodes == 0 proved little */
+  double kernel_ms, readback_ms;  /* out: as ks_audit's */
+} ks_audit_limits;
+/* claimed == NULL: the resident result, where it lies (the form for derived what-ifs).  claimed given (flattened problems only, KS_ERR_UNSUPPORTED for a derived
+ * view): the fourth pass's arrays are uploaded and read; every index a result supplies is range-checked before it addresses memory.  A problem without a limited
+ * template returns KS_OK with limited_templates == 0 after the SEQ kernels alone (two launches); otherwise nine launches, the scratch of a problem is
+ * O(P + C x M + max_new_nodes x R) words, so a batch is one slice.  The tables behind the verdict are built by integer min, add and or; flags are written per index,
+ * no output through an atomic, no float: the same flags every run.  Refusals as ks_audit_firstfit_dev's. */
+int ks_audit_limits_dev(ks_dev_problem* d, const ks_result* claimed /* or NULL; pod_seq is read */, ks_audit_limits* out);
+int ks_audit_limits_batch_dev(ks_dev_problem* const* ds, uint32_t n, ks_audit_limits* const* outs);
 
 /* ---- consolidation CANDIDATES, selected and ordered on the device (deprovisioning/helpers.go:124-165,275-287 GetPodEvictionCost / disruptionCost /
  * calculateLifetimeRemaining, pdblimits.go:57-70 CanEvictPods, helpers.go:339-366 canBeTerminated / PodsPreventEviction, consolidation.go:83-104 the sort).

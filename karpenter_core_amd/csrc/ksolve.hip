@@ -2857,6 +2857,7 @@ struct ks_dev_problem {
   int rr_started = 0, rr_code = 0; // the last solve: ks_pack_rr was launched | why it declined (0: it took the Solve; the codes are in ks_pack_rr.inc)
   bool solved = false;           // the device holds the result of a successful ks_solve*_dev (ks_placement_rows reads it there); false while none has run, and after one that failed
   bool no_multi = false;         // ... over a snapshot with topology groups: the class briefs (round eligibility, certain records) were built for the snapshot's group activity, not this what-if's -- single-wave kernel only
+  u32 n_limited = 0;             // the templates with tmpl_limit_present != 0xFFFFFFFF (the audit's fifth pass leaves at once where there is none)
 };
 
 // What a call over a batch of resident problems sends to its kernel, and reads back: [DevProb n | DevState n | the caller's segments ...] in ONE host block and
@@ -3055,6 +3056,7 @@ static int upload_impl(const ks_problem* p, int device, const ks_dev_problem* ba
     for (u32 m = 0; m < M && lean; ++m) lean = p->tmpl_limit_present[m] == 0xFFFFFFFFu || p->tmpl_limit_present[m] == 0;
     for (u32 c = 0; c < C && lean; ++c) lean = p->cls_hn_mode[c] == 0 && p->cls_port_off[c + 1] == p->cls_port_off[c] && p->cls_vol_off[c + 1] == p->cls_vol_off[c];
     d->lean_ok = lean;
+    d->n_limited = 0; for (u32 m = 0; m < M; ++m) if (p->tmpl_limit_present[m] != 0xFFFFFFFFu) ++d->n_limited;
   }
   h.ct_spot = p->ct_spot; h.ct_ondemand = p->ct_ondemand; h.ND = p->ND; h.SW = p->SW;
   // the caller's arrays, row by row (KS_PROBLEM_ARRAYS): copied into the arena, or -- by the row's share rule -- the base's device copy
@@ -3300,7 +3302,7 @@ static int whatifs_open(const ks_dev_problem* base, uint32_t n_nodes, const int3
   b->views.resize(n, nullptr);
   for (u32 w = 0; w < n; ++w) {
     auto* v = new ks_dev_problem(); b->views[w] = v;
-    v->device = b->device; v->view = true; v->stream = b->stream; v->tables_built = true; v->any_bounds = base->any_bounds; v->lean_ok = base->lean_ok; v->src = base->src; v->no_multi = with_topo;
+    v->device = b->device; v->view = true; v->stream = b->stream; v->tables_built = true; v->any_bounds = base->any_bounds; v->lean_ok = base->lean_ok; v->src = base->src; v->no_multi = with_topo; v->n_limited = base->n_limited;
   }
   // what the two derivation kernels read, in the copied region: pod -> node and the descriptors; with groups, the snapshot's per-node tables
   const i32* d_pod_node = nullptr; const DeriveDesc* d_desc = nullptr; const TopoDesc* d_tdesc = nullptr; u32* d_mismatch = nullptr; const i32* t_cnt = nullptr; const i32* t_dom = nullptr; const u64* t_own = nullptr; const i32* t_tot = nullptr; const i32* t_ext = nullptr; const i32* t_row = nullptr;
@@ -4394,6 +4396,7 @@ extern "C" int ks_placement_rows_host(ks_dev_problem* const* ds, uint32_t n, con
 #include "ks_audit_topo.inc" // its second, opt-in pass: pod (anti-)affinity and hostname spread in commit order (ks_audit_topology_dev / ks_audit_topology_batch_dev)
 #include "ks_audit_spread.inc" // its third, opt-in pass: topology spread over narrow keys in commit order (ks_audit_spread_dev / ks_audit_spread_batch_dev)
 #include "ks_audit_firstfit.inc" // its fourth, opt-in pass: first-fit order from the final state and the commit numbers (ks_audit_firstfit_dev / ks_audit_firstfit_batch_dev)
+#include "ks_audit_limits.inc"   // its fifth, opt-in pass: provisioner limits in opening order (ks_audit_limits_dev / ks_audit_limits_batch_dev)
 
 // ------------------------------------------------------------------------------------------------
 // Consolidation candidates (ksolve.h ks_consolidation_candidates_host): which nodes sortAndFilterCandidates keeps, and in what order.

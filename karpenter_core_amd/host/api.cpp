@@ -1090,6 +1090,71 @@ int ksh_audit_firstfit_claimed(void* hv, const ksh_result_arrays* c, const int32
   });
 }
 }  // extern "C"
+// The fifth pass's tables (kshost.h ksh_audit_limits_out): the fourth pass's way for the pods, the first pass's for the nodes
+namespace {
+struct AuditLimitsTables {
+  std::vector<ks_audit_limits> a; std::vector<ks_audit_limits*> ptr; std::vector<std::vector<uint32_t>> pf, nf;
+  int size(const std::vector<ks_dev_problem*>& ds) {
+    const size_t n = ds.size(); a.assign(n, ks_audit_limits{}); ptr.resize(n); pf.resize(n); nf.resize(n);
+    for (size_t i = 0; i < n; ++i) {
+      uint32_t np = 0, ns = 0; int rc = dev_rc(ks_audit_sizes(ds[i], &np, &ns)); if (rc != KS_OK) return rc;
+      pf[i].assign(np, 0); nf[i].assign(ns, 0); a[i].pod_flags = pf[i].data(); a[i].node_flags = nf[i].data(); ptr[i] = &a[i];
+    }
+    return KS_OK;
+  }
+  void give(size_t i, ksh_audit_limits_out* o, double* ms) const {
+    const ks_audit_limits& r = a[i];
+    o->n_pods = r.n_pods; o->n_nodes = r.n_nodes; o->n_new = r.n_new; o->n_placed = r.n_placed; o->limited_templates = r.limited_templates; o->skipped_nodes = r.skipped_nodes;
+    o->skipped_pods = r.skipped_pods; o->truncated = 0; o->n_pods_flagged = r.n_pods_flagged; o->n_nodes_flagged = r.n_nodes_flagged; o->exact_nodes = r.exact_nodes; o->binding_nodes = r.binding_nodes;
+    memcpy(o->checked, r.checked, sizeof o->checked); memcpy(o->pod_bit_count, r.pod_bit_count, sizeof o->pod_bit_count); memcpy(o->node_bit_count, r.node_bit_count, sizeof o->node_bit_count);
+    if (o->cap_pods >= r.n_pods) { if (r.n_pods) memcpy(o->pod_flags, r.pod_flags, (size_t)r.n_pods * sizeof(uint32_t)); } else o->truncated |= KSH_AUDIT_TRUNCATED_PODS;
+    if (o->cap_nodes >= r.n_nodes) { if (r.n_nodes) memcpy(o->node_flags, r.node_flags, (size_t)r.n_nodes * sizeof(uint32_t)); } else o->truncated |= KSH_AUDIT_TRUNCATED_NODES;
+    if (ms) { ms[0] = r.kernel_ms; ms[1] = r.readback_ms; }
+  }
+};
+bool audit_limits_out_ok(const ksh_audit_limits_out* o) { return o && (!o->cap_pods || o->pod_flags) && (!o->cap_nodes || o->node_flags); }
+}  // namespace
+extern "C" {
+int ksh_audit_limits(void** hv, uint32_t n, ksh_audit_limits_out* outs, double* ms) {
+  zero(ms, 2);
+  if (n && (!hv || !outs)) return set_err(KS_ERR_INVALID, "null argument");
+  for (uint32_t i = 0; i < n; ++i) if (!audit_limits_out_ok(&outs[i])) return set_err(KS_ERR_INVALID, "null audit table");
+  if (!n) return KS_OK;
+  return guarded([&] {
+    std::vector<ks_dev_problem*> ds;
+    int rc = device_problems(hv, n, true, "audit before solve", ds); if (rc != KS_OK) return rc;
+    AuditLimitsTables t; rc = t.size(ds); if (rc != KS_OK) return rc;
+    rc = dev_rc(ks_audit_limits_batch_dev(ds.data(), n, t.ptr.data())); if (rc != KS_OK) return rc;
+    for (uint32_t i = 0; i < n; ++i) t.give(i, &outs[i], ms);
+    return KS_OK;
+  });
+}
+int ksh_audit_limits_claimed(void* hv, const ksh_result_arrays* c, const int32_t* pod_seq, ksh_audit_limits_out* out, double* ms) {
+  zero(ms, 2);
+  Handle* h = (Handle*)hv;
+  if (!h || !c || !pod_seq) return set_err(KS_ERR_INVALID, "null argument");
+  if (!audit_limits_out_ok(out)) return set_err(KS_ERR_INVALID, "null audit table");
+  if (h->delta || h->enc->view) return set_err(KS_ERR_UNSUPPORTED, "a claimed result is audited against a flattened problem, not against a what-if derived on the device");
+  return guarded([&] {
+    const ks_problem& p = h->enc->prob; const uint32_t TW = (p.T + 63) / 64;
+    if (c->n_pods != p.P || c->n_existing != p.E || c->types_words != TW || c->n_resources != p.R || c->n_keys != p.K) return set_err(KS_ERR_INVALID, "claimed result: its dimensions are not the handle's");
+    if (c->n_new > p.max_new_nodes) return set_err(KS_ERR_INVALID, "claimed result: more new nodes than max_new_nodes");
+    if (c->n_unscheduled > p.P) return set_err(KS_ERR_INVALID, "claimed result: more unscheduled pods than pods");
+    if (p.P && (!c->pod_node || !c->pod_stage)) return set_err(KS_ERR_INVALID, "claimed result: null array");
+    int rc = ensure_resident(h); if (rc != KS_OK) return rc;
+    ks_result r{}; r.pod_node = (int32_t*)c->pod_node; r.pod_stage = (int32_t*)c->pod_stage; r.pod_seq = (int32_t*)pod_seq;
+    r.n_new = c->n_new; r.n_unscheduled = c->n_unscheduled;
+    r.node_tmpl = (int32_t*)c->node_tmpl; r.node_types = (uint64_t*)c->node_types; r.node_requests = (int64_t*)c->node_requests; r.node_requests_present = (uint32_t*)c->node_requests_present;
+    r.node_present = (uint32_t*)c->node_present; r.node_complement = (uint32_t*)c->node_complement; r.node_mask = (uint64_t*)c->node_mask; r.node_gt = (int32_t*)c->node_gt; r.node_lt = (int32_t*)c->node_lt;
+    r.node_it_state = (int32_t*)c->node_it_state;
+    std::vector<ks_dev_problem*> ds{h->dev};
+    AuditLimitsTables t; rc = t.size(ds); if (rc != KS_OK) return rc;
+    rc = dev_rc(ks_audit_limits_dev(h->dev, &r, t.ptr[0])); if (rc != KS_OK) return rc;
+    t.give(0, out, ms);
+    return KS_OK;
+  });
+}
+}  // extern "C"
 // What getNodePrices / filterOutSameType / simulateScheduling's readiness rule read of the snapshot's nodes, once per call
 namespace {
 struct CmdNode { int32_t type = -1; bool spot = false, has_price = false, unready = false, owned = false; double price = 0.0; };

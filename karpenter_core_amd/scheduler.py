@@ -46,6 +46,11 @@ KS_AUDIT_SPREAD_RULES = ("SEQ", "SPREAD")
 # the fourth pass's (FlatProblem.audit_firstfit() / audit_firstfit_batch()): SEQ as above, and first-fit order; `checked`: placed pods, examined pods, (class, node) pairs
 KS_AUDIT_FIRSTFIT_BITS = {"SEQ": 128, "FIT_EXISTING": 4096, "FIT_NEW": 8192, "FIT_TEMPLATE": 16384}
 KS_AUDIT_FIRSTFIT_CHECKED = ("SEQ", "PODS", "PAIRS")
+# the fifth pass's (FlatProblem.audit_limits() / audit_limits_batch()): SEQ as above, and provisioner limits in opening order; its node bits continue KS_AUDIT_NODE_BITS
+# in a word of the pass's own; `checked`: placed pods, new nodes of limited templates, examined pods, (class, template) pairs
+KS_AUDIT_LIMITS_POD_BITS = {"SEQ": 128, "LIMIT_TEMPLATE": 32768}
+KS_AUDIT_LIMITS_NODE_BITS = {"LIMIT_EXTRA": 256, "LIMIT_MISSING": 512}
+KS_AUDIT_LIMITS_CHECKED = ("SEQ", "NODES", "PODS", "PAIRS")
 
 
 class KSolveError(RuntimeError):
@@ -377,6 +382,18 @@ class FlatProblem:
                 raise ValueError("audit_firstfit: pod_seq goes with a claimed result")
             return audit_firstfit_batch([self])[0]
         return _audit_firstfit_call([self], claimed, pod_seq)[0]
+
+    def audit_limits(self, claimed: Optional[dict] = None, pod_seq=None) -> dict:
+        """The audit's fifth, opt-in pass (include/ksolve.h KS_AUDIT_NODE_LIMIT_*, KS_AUDIT_POD_LIMIT_TEMPLATE, kshost.h ksh_audit_limits / ksh_audit_limits_claimed):
+        provisioner limits -- no machine of a limited provisioner holds a type above what can have remained when it opened or lacks one that must have remained, no pod
+        passed over a limited provisioner that still had room --, decided from the final state and the commit numbers.  Arguments as `audit_topology`'s.  Returns
+        `audit_firstfit`'s dict ("checked": SEQ the placed pods, NODES the new nodes of limited templates, PODS the pods examined, PAIRS the (class, template) pairs)
+        plus "node_flags" (uint32 [E + n_new]), "n_nodes_flagged", "node_bit_count", "limited_templates", "exact_nodes", "binding_nodes" and "skipped_nodes"."""
+        if claimed is None:
+            if pod_seq is not None:
+                raise ValueError("audit_limits: pod_seq goes with a claimed result")
+            return audit_limits_batch([self])[0]
+        return _audit_limits_call([self], claimed, pod_seq)[0]
 
     def result(self) -> SolveResult:
         """Decode the result the handle holds (after `solve(decode=False)` or `solve_from_pods`)."""
@@ -865,7 +882,7 @@ class _AuditTopologyOut(ctypes.Structure):      # include/kshost.h ksh_audit_top
                [("checked", ctypes.c_uint32 * 4), ("pod_bit_count", ctypes.c_uint32 * 32)]
 
 
-def _audit_seq_pass(what: str, Out, flats: Sequence["FlatProblem"], claimed: Optional[dict], pod_seq, more=()):
+def _audit_seq_pass(what: str, Out, flats: Sequence["FlatProblem"], claimed: Optional[dict], pod_seq, more=(), nodes=False):
     """What the audit's passes over the commit order share (kshost.h ksh_audit_<what> / ksh_audit_<what>_claimed, out tables of type `Out`): the call over the resident
     results of `flats`, or over `claimed` with `pod_seq` for flats[0]; once more with larger tables if one was too short.  Returns (outs, pod_flags per problem, ms)."""
     import numpy as np
@@ -898,12 +915,20 @@ def _audit_seq_pass(what: str, Out, flats: Sequence["FlatProblem"], claimed: Opt
             if not len(seq):
                 seq = np.zeros(1, dtype=np.int32)
 
+    ntabs = []
+
     def call(caps):
         tabs = []
+        del ntabs[:]
         for i, cp in enumerate(caps):
             pf = np.zeros(max(1, cp), dtype=np.uint32)
             tabs.append(pf)
             outs[i].pod_flags, outs[i].cap_pods = pf.ctypes.data, cp
+            if nodes:      # (the fifth pass: a table per node as well, ksh_audit's way)
+                cn = int(outs[i].n_nodes) if outs[i].truncated else flats[i].dims["E"] + flats[i].dims["P"]
+                nf = np.zeros(max(1, cn), dtype=np.uint32)
+                ntabs.append(nf)
+                outs[i].node_flags, outs[i].cap_nodes = nf.ctypes.data, cn
         rc = resident(hs, n, outs, ms) if ra is None else claimed_fn(flats[0]._h, ctypes.byref(ra), seq.ctypes.data if seq is not None else None, outs, ms)
         if rc != KS_OK:
             raise KSolveError(rc, kh.ksh_last_error().decode())
@@ -911,6 +936,8 @@ def _audit_seq_pass(what: str, Out, flats: Sequence["FlatProblem"], claimed: Opt
     tabs = call([f.dims["P"] for f in flats])
     if any(o.truncated for o in outs):      # (a what-if derived on the device states its own sizes only here: once more, with what the totals say)
         tabs = call([o.n_pods for o in outs])
+    if nodes:
+        return outs, [(tabs[i][:o.n_pods].copy(), ntabs[i][:o.n_nodes].copy()) for i, o in enumerate(outs)], (float(ms[0]), float(ms[1]))
     return outs, [tabs[i][:o.n_pods].copy() for i, o in enumerate(outs)], (float(ms[0]), float(ms[1]))
 
 
@@ -972,6 +999,33 @@ def audit_firstfit_batch(flats: Sequence["FlatProblem"]) -> List[dict]:
     """The audit's fourth pass over the results the last solve left on the device, for a whole batch (include/kshost.h ksh_audit_firstfit): handles of any kind, derived
     what-ifs included.  One dict per problem, as `FlatProblem.audit_firstfit` returns it."""
     return _audit_firstfit_call(flats)
+
+
+class _AuditLimitsOut(ctypes.Structure):      # include/kshost.h ksh_audit_limits_out
+    _fields_ = [("pod_flags", ctypes.c_void_p), ("cap_pods", ctypes.c_uint64), ("node_flags", ctypes.c_void_p), ("cap_nodes", ctypes.c_uint64)] + \
+               [(n, ctypes.c_uint32) for n in ("n_pods", "n_nodes", "n_new", "n_placed", "limited_templates", "skipped_nodes", "skipped_pods", "truncated", "n_pods_flagged",
+                                               "n_nodes_flagged", "exact_nodes", "binding_nodes")] + \
+               [("checked", ctypes.c_uint32 * 4), ("pod_bit_count", ctypes.c_uint32 * 32), ("node_bit_count", ctypes.c_uint32 * 32)]
+
+
+def _audit_limits_call(flats: Sequence["FlatProblem"], claimed: Optional[dict] = None, pod_seq=None) -> List[dict]:
+    import numpy as np
+    if not len(flats):
+        return []
+    more = (("node_types", np.uint64), ("node_requests", np.int64), ("node_requests_present", np.uint32), ("node_it_state", np.int32))
+    outs, flags, ms = _audit_seq_pass("limits", _AuditLimitsOut, flats, claimed, pod_seq, more, nodes=True)
+    return [{"pod_flags": flags[i][0], "node_flags": flags[i][1], "n_pods_flagged": int(o.n_pods_flagged), "n_nodes_flagged": int(o.n_nodes_flagged),
+             "pod_bit_count": {k: int(o.pod_bit_count[v.bit_length() - 1]) for k, v in KS_AUDIT_LIMITS_POD_BITS.items()},
+             "node_bit_count": {k: int(o.node_bit_count[v.bit_length() - 1]) for k, v in KS_AUDIT_LIMITS_NODE_BITS.items()},
+             "checked": {k: int(o.checked[j]) for j, k in enumerate(KS_AUDIT_LIMITS_CHECKED)}, "limited_templates": int(o.limited_templates),
+             "exact_nodes": int(o.exact_nodes), "binding_nodes": int(o.binding_nodes), "skipped_nodes": int(o.skipped_nodes), "skipped_pods": int(o.skipped_pods),
+             "n_new": int(o.n_new), "n_placed": int(o.n_placed), "ms": ms} for i, o in enumerate(outs)]
+
+
+def audit_limits_batch(flats: Sequence["FlatProblem"]) -> List[dict]:
+    """The audit's fifth pass over the results the last solve left on the device, for a whole batch (include/kshost.h ksh_audit_limits): handles of any kind, derived
+    what-ifs included.  One dict per problem, as `FlatProblem.audit_limits` returns it."""
+    return _audit_limits_call(flats)
 
 
 def deal_lpt(weights: Sequence[int], nshards: int) -> List[int]:
