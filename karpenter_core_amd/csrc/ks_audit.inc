@@ -40,6 +40,32 @@ __device__ __forceinline__ u64 aud_wave_or(u64 v) { for (int x = 32; x > 0; x >>
 __device__ __forceinline__ u64 aud_wave_add(u64 v) { for (int x = 32; x > 0; x >>= 1) v += aud_xor64(v, x); return v; }
 // entry.matches, hostportusage.go:45-57: protocol and port equal, and the addresses equal or either unspecified
 __device__ __forceinline__ bool aud_port_match(u64 a, u64 b) { if ((a >> 32) != (b >> 32)) return false; const u32 ia = (u32)a, ib = (u32)b; return ia == ib || ia == 0 || ib == 0; }
+// ---- what the passes over the commit order (ks_audit_topo.inc and the files after it) share with this one ----
+// is the placed pod's commit number one the rules may order by?  (below the number of placed pods, and no other placed pod's; seqcnt: the pass's own counts per commit number)
+__device__ __forceinline__ bool aud_seq_ok(const AuditView& V, const u32* seqcnt, u32 p, u32 n_placed) {
+  const i32 sq = GC(i32, V.pod_seq)[p];
+  return sq >= 0 && (u32)sq < n_placed && seqcnt[sq] == 1u;
+}
+// the zone x capacity-type pairs a requirement set allows: bit z * n_ct + c of it_offer's words (z, ct: the set's requirements on the two keys, absent where the problem has no such key)
+__device__ __forceinline__ u64 aud_pairs(const DevProb& P, const KReq& z, const KReq& ct) {
+  u64 allowZ = ~0ull, allowC = ~0ull;
+  if (P.key_zone >= 0 && z.present) allowZ = kreq_has_mask(z, P.value_int + P.key_zone * 64, GC(u32, P.key_nvalues)[P.key_zone]);
+  if (P.key_ct >= 0 && ct.present) allowC = kreq_has_mask(ct, P.value_int + P.key_ct * 64, GC(u32, P.key_nvalues)[P.key_ct]);
+  if (P.n_ct == 0) return ~0ull;
+  u64 pairs = 0;
+  for (u64 zz = allowZ; zz; zz &= zz - 1) { const int zi = __builtin_ctzll(zz); if ((u32)zi * P.n_ct >= 64) break; pairs |= (allowC & ((1ull << P.n_ct) - 1)) << (zi * P.n_ct); }
+  return pairs;
+}
+// is existing node e in class c's hostname list?  (existing node e owns hostname e; a new node's placeholder is in no list, node.go:46)
+__device__ __forceinline__ bool aud_hn_listed(const DevProb& P, u32 c, u32 e) {
+  for (u32 i = GC(u32, P.cls_hn_off)[c]; i < GC(u32, P.cls_hn_off)[c + 1]; ++i) if (GC(u32, P.hn_list)[i] == e) return true;
+  return false;
+}
+// the sum of `mine` over the 256 threads of the workgroup, in s[0] for thread 0 (s: an LDS tile of 256 the caller owns and may use again after a barrier)
+__device__ __forceinline__ void aud_block_sum(u32* s, u32 mine) {
+  s[threadIdx.x] = mine;
+  for (u32 o = 128u; o > 0; o >>= 1) { __syncthreads(); if (threadIdx.x < o) s[threadIdx.x] += s[threadIdx.x + o]; }
+}
 
 __global__ __launch_bounds__(256) void ks_audit_count(const DevProb* probs, const AuditView* views) {
   const DevProb& P = probs[blockIdx.y]; const AuditView& V = views[blockIdx.y];
@@ -108,8 +134,7 @@ __global__ __launch_bounds__(256) void ks_audit_pods(const DevProb* probs, const
       // the hostname requirement: existing node e owns hostname e, a new node's placeholder is in no list (node.go:46)
       const u32 hm = GC(u8, P.cls_hn_mode)[c];
       if (hm) {
-        bool inlist = false;
-        if (existing) for (u32 i = GC(u32, P.cls_hn_off)[c]; i < GC(u32, P.cls_hn_off)[c + 1]; ++i) if (GC(u32, P.hn_list)[i] == (u32)nd) { inlist = true; break; }
+        const bool inlist = existing && aud_hn_listed(P, c, (u32)nd);
         if (hm == 1 ? !inlist : inlist) f |= KS_AUDIT_POD_HOSTNAME;
       }
       // VolumeUsage.validate failed for the pod: no existing node accepts it (existingnode.go:87-90)
@@ -197,12 +222,10 @@ __global__ __launch_bounds__(256) void ks_audit_nodes(const DevProb* probs, cons
     if (req_bad) f |= KS_AUDIT_NODE_REQUESTS;
     // InstanceTypeOptions against filterInstanceTypesByRequirements (node.go:137-159) by the node's final requirements and requests: one type per lane
     const u32 np_ = GC(u32, V.o_present)[j], nc_ = GC(u32, V.o_complement)[j]; const i32 its = GC(i32, V.o_it)[j]; const bool its_ok = its >= 0 && (u32)its < P.S;
-    u64 allowZ = ~0ull, allowC = ~0ull;
-    if (P.key_zone >= 0 && ((np_ >> P.key_zone) & 1u)) allowZ = kreq_has_mask(load_req(np_, nc_, V.o_mask + (size_t)j * K, V.o_gt + (size_t)j * K, V.o_lt + (size_t)j * K, P.key_zone), P.value_int + P.key_zone * 64, GC(u32, P.key_nvalues)[P.key_zone]);
-    if (P.key_ct >= 0 && ((np_ >> P.key_ct) & 1u)) allowC = kreq_has_mask(load_req(np_, nc_, V.o_mask + (size_t)j * K, V.o_gt + (size_t)j * K, V.o_lt + (size_t)j * K, P.key_ct), P.value_int + P.key_ct * 64, GC(u32, P.key_nvalues)[P.key_ct]);
-    u64 pairs = 0;
-    for (u64 zz = allowZ; zz; zz &= zz - 1) { const int z = __builtin_ctzll(zz); if ((u32)z * P.n_ct >= 64) break; pairs |= (allowC & ((1ull << P.n_ct) - 1)) << (z * P.n_ct); }
-    if (P.n_ct == 0) pairs = ~0ull;
+    KReq rz = kreq_absent(), rc = kreq_absent();
+    if (P.key_zone >= 0) rz = load_req(np_, nc_, V.o_mask + (size_t)j * K, V.o_gt + (size_t)j * K, V.o_lt + (size_t)j * K, P.key_zone);
+    if (P.key_ct >= 0) rc = load_req(np_, nc_, V.o_mask + (size_t)j * K, V.o_gt + (size_t)j * K, V.o_lt + (size_t)j * K, P.key_ct);
+    const u64 pairs = aud_pairs(P, rz, rc);
     u64 extra = 0, missing = 0, any = 0;
     for (u32 w = 0; w < TW; ++w) {
       const u32 t = w * 64u + lane; bool ok = t < T && its_ok;
@@ -228,62 +251,26 @@ __global__ __launch_bounds__(256) void ks_audit_nodes(const DevProb* probs, cons
 }
 
 // ---- host half ----
-// what the audit reads of a result: KS_RESULT_SEGS without the per-pod reasons
+// The host path of all five passes.  A pass's own file keeps what is its own -- its view struct, the carve-up of its scratch, its launch list, the decoding of its
+// meta and checked words -- and calls the plain functions below for the rest: the claimed upload, the resident prelude, the pooled work block, the launch rows, the
+// wait and the two times, the flag tallies, the walk in slices.
+// what the audit reads of a result: KS_RESULT_SEGS without the per-pod reasons.  Each entry has a bit (its place here); a pass names the set it reads as a mask
 #define KS_AUDIT_SEGS(X) \
   X(pod_node, pod_node, i32, P) X(pod_stage, pod_stage, i32, P) X(pod_seq, pod_seq, i32, P) X(unscheduled, unscheduled, i32, P) \
   X(n_tmpl, node_tmpl, i32, N) X(n_alive, node_types, u64, N * TW) X(o_req, node_requests, i64, N * R) X(o_reqmask, node_requests_present, u32, N) \
   X(o_present, node_present, u32, N) X(o_complement, node_complement, u32, N) X(o_mask, node_mask, u64, N * K) X(o_gt, node_gt, i32, N * K) X(o_lt, node_lt, i32, N * K) \
   X(o_it, node_it_state, i32, N)
-// every refusal about the out tables, then: scratch laid out and zeroed, four launches, one read-back of [meta | pod flags | node flags], the totals counted on the host
-static int audit_run(ks_dev_problem* const* ds, u32 n, const AuditView* results /* the result pointers of every problem */, ks_audit* const* outs) {
-  BatchStage st; TRY(st.open(ds, n, nullptr, false));
-  const size_t o_view = st.add<AuditView>(n);
-  TRY(st.place());
-  // one block of u32: [meta 2n | pod_flags of every problem | node_flags of every problem] (read back) then the scratch
-  std::vector<size_t> o_pf(n), o_nf(n); size_t at = 2 * (size_t)n; u32 pmax = 0, nsmax = 0;
-  for (u32 i = 0; i < n; ++i) { o_pf[i] = at; at += ds[i]->h.P; pmax = std::max(pmax, ds[i]->h.P); }
-  for (u32 i = 0; i < n; ++i) { o_nf[i] = at; at += (size_t)ds[i]->h.E + ds[i]->h.NMAX; nsmax = std::max(nsmax, ds[i]->h.E + ds[i]->h.NMAX); }
-  const size_t n_out = at;
-  std::vector<size_t> o_scr(n);
-  for (u32 i = 0; i < n; ++i) { o_scr[i] = at; at += 2 * (size_t)ds[i]->h.P + 3 * ((size_t)ds[i]->h.E + ds[i]->h.NMAX) + 1; }
-  TmpDev work(ds[0]->device); TRY(work.alloc(at * sizeof(u32)));
-  u32* w = work.as<u32>();
-  for (u32 i = 0; i < n; ++i) {
-    AuditView v = results[i]; const size_t Pn = ds[i]->h.P, NS = (size_t)ds[i]->h.E + ds[i]->h.NMAX;
-    v.meta = w + 2 * (size_t)i; v.pod_flags = w + o_pf[i]; v.node_flags = w + o_nf[i];
-    u32* s = w + o_scr[i]; v.mark = s; v.cnt = s + Pn; v.off = s + Pn + NS; v.fill = s + Pn + 2 * NS + 1; v.pods = s + Pn + 3 * NS + 1;
-    st.h<AuditView>(o_view)[i] = v;
-  }
-  const auto t0 = std::chrono::steady_clock::now();
-  TRY(st.upload(st.bytes));
-  HIPCHK(hipMemsetAsync(w, 0, at * sizeof(u32), st.stream()));
-  const u32 KS_GRID_Y_MAX = 65535u; const AuditView* dv = st.d<const AuditView>(o_view);
-  const u32 gx_p = std::max(1u, std::min(1024u, (pmax + 255u) / 256u)), gx_n = std::max(1u, std::min(4096u, (nsmax + 3u) / 4u));
-  for (u32 base = 0; base < n; base += KS_GRID_Y_MAX) {
-    const u32 ny = std::min(KS_GRID_Y_MAX, n - base);
-    hipLaunchKernelGGL(ks_audit_count, dim3(gx_p, ny), dim3(256), 0, st.stream(), st.probs() + base, dv + base);
-    hipLaunchKernelGGL(ks_audit_scan, dim3(ny), dim3(256), 0, st.stream(), st.probs() + base, dv + base);
-    hipLaunchKernelGGL(ks_audit_pods, dim3(gx_p, ny), dim3(256), 0, st.stream(), st.probs() + base, dv + base);
-    hipLaunchKernelGGL(ks_audit_nodes, dim3(gx_n, ny), dim3(256), 0, st.stream(), st.probs() + base, dv + base);
-  }
-  HIPCHK(hipStreamSynchronize(st.stream())); HIPCHK(hipGetLastError());
-  const auto t1 = std::chrono::steady_clock::now();
-  std::vector<u32> back(n_out);
-  HIPCHK(hipMemcpy(back.data(), w, n_out * sizeof(u32), hipMemcpyDeviceToHost));
-  for (u32 i = 0; i < n; ++i) {
-    ks_audit* o = outs[i]; const u32 Pn = ds[i]->h.P, NS = ds[i]->h.E + back[2 * (size_t)i];
-    o->n_pods = Pn; o->n_nodes = NS; o->n_new = back[2 * (size_t)i]; o->n_unscheduled = back[2 * (size_t)i + 1]; o->n_pods_flagged = 0; o->n_nodes_flagged = 0;
-    memset(o->pod_bit_count, 0, sizeof o->pod_bit_count); memset(o->node_bit_count, 0, sizeof o->node_bit_count);
-    const u32* pf = back.data() + o_pf[i]; const u32* nf = back.data() + o_nf[i];
-    for (u32 k = 0; k < Pn; ++k) if (pf[k]) { ++o->n_pods_flagged; for (u32 x = pf[k]; x; x &= x - 1) ++o->pod_bit_count[__builtin_ctz(x)]; }
-    for (u32 k = 0; k < NS; ++k) if (nf[k]) { ++o->n_nodes_flagged; for (u32 x = nf[k]; x; x &= x - 1) ++o->node_bit_count[__builtin_ctz(x)]; }
-    if (o->pod_flags && Pn) memcpy(o->pod_flags, pf, (size_t)Pn * sizeof(u32));
-    if (o->node_flags && NS) memcpy(o->node_flags, nf, (size_t)NS * sizeof(u32));
-    o->kernel_ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
-    o->readback_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
-  }
-  return KS_OK;
-}
+enum {
+#define X(sf, rf, T, cnt) AUD_SEG_##rf,
+  KS_AUDIT_SEGS(X)
+#undef X
+  AUD_N_SEGS
+};
+#define AUD_READS(rf) (1u << AUD_SEG_##rf)
+static const u32 AUD_READS_ALL = (1u << AUD_N_SEGS) - 1u;                    // the first pass
+static const u32 AUD_READS_ORDER = AUD_READS(pod_node) | AUD_READS(pod_stage) | AUD_READS(pod_seq) | AUD_READS(node_tmpl) | AUD_READS(node_present) | AUD_READS(node_complement) |
+                                   AUD_READS(node_mask) | AUD_READS(node_gt) | AUD_READS(node_lt);      // topology and spread: where the pods are, at which stage, in which order; the new nodes' templates and final requirements
+static const u32 AUD_READS_FIT = AUD_READS_ALL & ~AUD_READS(unscheduled);   // first-fit and limits
 // the result a solve left on the device
 static AuditView audit_resident(const DevState& s) {
   AuditView v{};
@@ -292,48 +279,145 @@ static AuditView audit_resident(const DevState& s) {
   v.o_mask = s.o_mask; v.o_gt = s.o_gt; v.o_lt = s.o_lt; v.o_it = s.o_it;
   return v;
 }
-extern "C" int ks_audit_sizes(const ks_dev_problem* d, uint32_t* n_pods, uint32_t* n_node_slots) {
-  if (!d) return fail(KS_ERR_INVALID, "null argument");
-  if (n_pods) *n_pods = d->h.P;
-  if (n_node_slots) *n_node_slots = d->h.E + d->h.NMAX;
+// A claimed result for the one call: every refusal about it -- an array is refused only if the pass reads it --, then the arrays of `reads` in one block of `up`,
+// every piece 8-byte aligned, then the two counts: one transfer.  An array the pass does not read stays null in the view.
+static int audit_claimed(ks_dev_problem* d, const ks_result* claimed, u32 reads, TmpDev& up, AuditView* view) {
+  if (d->view) return fail(KS_ERR_UNSUPPORTED, "a claimed result is audited against a flattened problem, not against a what-if derived on the device");
+  const DevProb& h = d->h; const u64 P = h.P, K = h.K, R = h.R, TW = h.TW, N = claimed->n_new;
+  if (N > h.NMAX) return fail(KS_ERR_INVALID, "claimed result: more new nodes than max_new_nodes");
+  if (claimed->n_unscheduled > P) return fail(KS_ERR_INVALID, "claimed result: more unscheduled pods than pods");
+  size_t bytes = 0;
+#define X(sf, rf, T, cnt) if (reads & AUD_READS(rf)) { if ((cnt) && !claimed->rf) return fail(KS_ERR_INVALID, "claimed result: null array " #rf); bytes += ks_pad8((cnt) * sizeof(T)); }
+  KS_AUDIT_SEGS(X)
+#undef X
+  std::vector<u64> blob(bytes / 8 + 1, 0); u8* hb = (u8*)blob.data();
+  HIPCHK(hipSetDevice(d->device));
+  TRY(up.alloc(bytes + 8)); u8* db = up.as<u8>();
+  DevState s{}; size_t at = 0;
+#define X(sf, rf, T, cnt) if (reads & AUD_READS(rf)) { const size_t b_ = (cnt) * sizeof(T); if (b_) memcpy(hb + at, claimed->rf, b_); s.sf = (T*)(db + at); at += ks_pad8(b_); }
+  KS_AUDIT_SEGS(X)
+#undef X
+  { u32 c2[2] = {claimed->n_new, claimed->n_unscheduled}; memcpy(hb + at, c2, 8); s.out_counts = (u32*)(db + at); }
+  HIPCHK(hipMemcpy(db, hb, bytes + 8, hipMemcpyHostToDevice));
+  *view = audit_resident(s);
   return KS_OK;
 }
-extern "C" int ks_audit_batch_dev(ks_dev_problem* const* ds, uint32_t n, ks_audit* const* outs) {
+// The resident form of a pass over a batch: its refusals, then `run` over the results the solves left on the device.  own_device_check: the pass refuses a batch
+// that spans devices here, before a problem that holds no result (the first pass leaves that refusal to BatchStage::open, after them all)
+template <class Out> static int audit_batch(ks_dev_problem* const* ds, u32 n, Out* const* outs, bool own_device_check, int (*run)(ks_dev_problem* const*, u32, const AuditView*, Out* const*)) {
   if (!n) return KS_OK;
   if (!ds || !outs) return fail(KS_ERR_INVALID, "null argument");
   TRY(BatchStage::not_null(ds, n));
   std::vector<AuditView> res(n);
   for (u32 i = 0; i < n; ++i) {
     if (!outs[i]) return fail(KS_ERR_INVALID, "null audit table");
+    if (own_device_check && ds[i]->device != ds[0]->device) return fail(KS_ERR_INVALID, "batch spans devices");
     if (!ds[i]->solved) return fail(KS_ERR_INVALID, "audit of a problem that holds no result: solve it first (or the last solve failed)");
     res[i] = audit_resident(ds[i]->hs);
   }
-  return audit_run(ds, n, res.data(), outs);
+  return run(ds, n, res.data(), outs);
 }
-extern "C" int ks_audit_dev(ks_dev_problem* d, const ks_result* claimed, ks_audit* out) {
+// One problem: the result its solve left (claimed == NULL), or the caller's arrays, of which the pass reads `reads`
+template <class Out> static int audit_one(ks_dev_problem* d, const ks_result* claimed, Out* out, u32 reads, bool own_device_check, int (*run)(ks_dev_problem* const*, u32, const AuditView*, Out* const*)) {
   if (!d || !out) return fail(KS_ERR_INVALID, "null argument");
-  if (!claimed) return ks_audit_batch_dev(&d, 1, &out);
-  if (d->view) return fail(KS_ERR_UNSUPPORTED, "a claimed result is audited against a flattened problem, not against a what-if derived on the device");
-  const DevProb& h = d->h; const u64 P = h.P, K = h.K, R = h.R, TW = h.TW, N = claimed->n_new;
-  if (N > h.NMAX) return fail(KS_ERR_INVALID, "claimed result: more new nodes than max_new_nodes");
-  if (claimed->n_unscheduled > P) return fail(KS_ERR_INVALID, "claimed result: more unscheduled pods than pods");
-#define X(sf, rf, T, cnt) if ((cnt) && !claimed->rf) return fail(KS_ERR_INVALID, "claimed result: null array " #rf);
-  KS_AUDIT_SEGS(X)
-#undef X
-  // the claimed arrays in one block, every piece 8-byte aligned, then the two counts: one transfer
-  size_t bytes = 0;
-#define X(sf, rf, T, cnt) bytes += ks_pad8((cnt) * sizeof(T));
-  KS_AUDIT_SEGS(X)
-#undef X
-  std::vector<u64> blob(bytes / 8 + 1, 0); u8* hb = (u8*)blob.data();
-  HIPCHK(hipSetDevice(d->device));
-  TmpDev up(d->device); TRY(up.alloc(bytes + 8)); u8* db = up.as<u8>();
-  DevState s{}; size_t at = 0;
-#define X(sf, rf, T, cnt) { const size_t b_ = (cnt) * sizeof(T); if (b_) memcpy(hb + at, claimed->rf, b_); s.sf = (T*)(db + at); at += ks_pad8(b_); }
-  KS_AUDIT_SEGS(X)
-#undef X
-  { u32 c2[2] = {claimed->n_new, claimed->n_unscheduled}; memcpy(hb + at, c2, 8); s.out_counts = (u32*)(db + at); }
-  HIPCHK(hipMemcpy(db, hb, bytes + 8, hipMemcpyHostToDevice));
-  const AuditView v = audit_resident(s);
-  return audit_run(&d, 1, &v, &out);
+  if (!claimed) return audit_batch(&d, 1u, &out, own_device_check, run);
+  TmpDev up(d->device); AuditView v{};
+  TRY(audit_claimed(d, claimed, reads, up, &v));
+  return run(&d, 1, &v, &out);
 }
+// The pooled block of u32 a pass works in: [the words that are read back: meta, flag rows, checked rows | scratch], zeroed on the stream before the first launch.
+// The output words are reserved first; a pass carves each problem's scratch up itself, from the offset it gets here.
+struct AuditWork {
+  TmpDev dev; size_t words = 0, n_out = 0; std::vector<u32> back;
+  explicit AuditWork(int device) : dev(device) {}
+  size_t out(size_t n) { const size_t at = words; words += n; n_out = words; return at; }
+  size_t scratch(size_t n, bool align8 = false) { if (align8) words += words & 1; const size_t at = words; words += n; return at; }      // (align8: int64 tables come first in it)
+  int alloc() { return dev.alloc(words * sizeof(u32)); }
+  u32* w() const { return dev.as<u32>(); }
+  int zero(hipStream_t stream) { HIPCHK(hipMemsetAsync(w(), 0, words * sizeof(u32), stream)); return KS_OK; }
+  int read_back() { back.resize(n_out); HIPCHK(hipMemcpy(back.data(), w(), n_out * sizeof(u32), hipMemcpyDeviceToHost)); return KS_OK; }      // the output prefix, in one transfer
+};
+// a pass's launches, once per row of at most KS_GRID_Y_MAX problems: launches(base, ny)
+template <class F> static void audit_rows(u32 n, F&& launches) {
+  const u32 KS_GRID_Y_MAX = 65535u;
+  for (u32 base = 0; base < n; base += KS_GRID_Y_MAX) launches(base, std::min(KS_GRID_Y_MAX, n - base));
+}
+template <class Out> static void audit_times(Out* const* outs, u32 n, double kernel_ms, double readback_ms) { for (u32 i = 0; i < n; ++i) { outs[i]->kernel_ms = kernel_ms; outs[i]->readback_ms = readback_ms; } }
+// The two times of a pass: from before the upload of the views to the end of the last kernel | from there to the end of the host's tallies
+struct AuditClock {
+  std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now(), t1;
+  int wait(hipStream_t stream) { HIPCHK(hipStreamSynchronize(stream)); HIPCHK(hipGetLastError()); t1 = std::chrono::steady_clock::now(); return KS_OK; }
+  void add(double* kernel_ms, double* readback_ms) const {
+    *kernel_ms += std::chrono::duration<double, std::milli>(t1 - t0).count(); *readback_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
+  }
+  template <class Out> void store(Out* const* outs, u32 n) const { double kms = 0.0, rms = 0.0; add(&kms, &rms); audit_times(outs, n, kms, rms); }
+};
+// the rows of a flag table that are set, and (bit_count given) how often each bit is; the caller zeroes what it passes
+static void audit_tally(const u32* rows, u32 n, u32* n_flagged, u32* bit_count /* [32] or NULL */) {
+  for (u32 k = 0; k < n; ++k) if (rows[k]) { ++*n_flagged; if (bit_count) for (u32 x = rows[k]; x; x &= x - 1) ++bit_count[__builtin_ctz(x)]; }
+}
+// A batch walked in slices for a pass whose scratch per problem can be large: a slice holds problems of at most `budget` words_of(problem) together, or one problem
+template <class Out, class W, class S> static int audit_slices(ks_dev_problem* const* ds, u32 n, const AuditView* results, Out* const* outs, W&& words_of, size_t budget, S&& slice) {
+  double kms = 0.0, rms = 0.0;
+  for (u32 base = 0; base < n;) {
+    u32 m = 0; size_t words = 0;
+    while (base + m < n && (m == 0 || words + words_of(ds[base + m]) <= budget)) { words += words_of(ds[base + m]); ++m; }
+    TRY(slice(ds + base, m, results + base, outs + base, &kms, &rms));
+    base += m;
+  }
+  audit_times(outs, n, kms, rms);
+  return KS_OK;
+}
+
+// every refusal about the out tables, then: scratch laid out and zeroed, four launches, one read-back of [meta | pod flags | node flags], the totals counted on the host
+static int audit_run(ks_dev_problem* const* ds, u32 n, const AuditView* results /* the result pointers of every problem */, ks_audit* const* outs) {
+  BatchStage st; TRY(st.open(ds, n, nullptr, false));
+  const size_t o_view = st.add<AuditView>(n);
+  TRY(st.place());
+  // [meta 2n | pod_flags of every problem | node_flags of every problem] (read back) then the scratch
+  AuditWork W(ds[0]->device); std::vector<size_t> o_pf(n), o_nf(n), o_scr(n); u32 pmax = 0, nsmax = 0;
+  W.out(2 * (size_t)n);
+  for (u32 i = 0; i < n; ++i) { o_pf[i] = W.out(ds[i]->h.P); pmax = std::max(pmax, ds[i]->h.P); }
+  for (u32 i = 0; i < n; ++i) { o_nf[i] = W.out((size_t)ds[i]->h.E + ds[i]->h.NMAX); nsmax = std::max(nsmax, ds[i]->h.E + ds[i]->h.NMAX); }
+  for (u32 i = 0; i < n; ++i) o_scr[i] = W.scratch(2 * (size_t)ds[i]->h.P + 3 * ((size_t)ds[i]->h.E + ds[i]->h.NMAX) + 1);
+  TRY(W.alloc());
+  u32* w = W.w();
+  for (u32 i = 0; i < n; ++i) {
+    AuditView v = results[i]; const size_t Pn = ds[i]->h.P, NS = (size_t)ds[i]->h.E + ds[i]->h.NMAX;
+    v.meta = w + 2 * (size_t)i; v.pod_flags = w + o_pf[i]; v.node_flags = w + o_nf[i];
+    u32* s = w + o_scr[i]; v.mark = s; v.cnt = s + Pn; v.off = s + Pn + NS; v.fill = s + Pn + 2 * NS + 1; v.pods = s + Pn + 3 * NS + 1;
+    st.h<AuditView>(o_view)[i] = v;
+  }
+  AuditClock clock;
+  TRY(st.upload(st.bytes));
+  TRY(W.zero(st.stream()));
+  const AuditView* dv = st.d<const AuditView>(o_view);
+  const u32 gx_p = std::max(1u, std::min(1024u, (pmax + 255u) / 256u)), gx_n = std::max(1u, std::min(4096u, (nsmax + 3u) / 4u));
+  audit_rows(n, [&](u32 base, u32 ny) {
+    hipLaunchKernelGGL(ks_audit_count, dim3(gx_p, ny), dim3(256), 0, st.stream(), st.probs() + base, dv + base);
+    hipLaunchKernelGGL(ks_audit_scan, dim3(ny), dim3(256), 0, st.stream(), st.probs() + base, dv + base);
+    hipLaunchKernelGGL(ks_audit_pods, dim3(gx_p, ny), dim3(256), 0, st.stream(), st.probs() + base, dv + base);
+    hipLaunchKernelGGL(ks_audit_nodes, dim3(gx_n, ny), dim3(256), 0, st.stream(), st.probs() + base, dv + base);
+  });
+  TRY(clock.wait(st.stream()));
+  TRY(W.read_back());
+  for (u32 i = 0; i < n; ++i) {
+    ks_audit* o = outs[i]; const u32* meta = W.back.data() + 2 * (size_t)i; const u32 Pn = ds[i]->h.P, NS = ds[i]->h.E + meta[0];
+    o->n_pods = Pn; o->n_nodes = NS; o->n_new = meta[0]; o->n_unscheduled = meta[1]; o->n_pods_flagged = 0; o->n_nodes_flagged = 0;
+    memset(o->pod_bit_count, 0, sizeof o->pod_bit_count); memset(o->node_bit_count, 0, sizeof o->node_bit_count);
+    const u32* pf = W.back.data() + o_pf[i]; const u32* nf = W.back.data() + o_nf[i];
+    audit_tally(pf, Pn, &o->n_pods_flagged, o->pod_bit_count); audit_tally(nf, NS, &o->n_nodes_flagged, o->node_bit_count);
+    if (o->pod_flags && Pn) memcpy(o->pod_flags, pf, (size_t)Pn * sizeof(u32));
+    if (o->node_flags && NS) memcpy(o->node_flags, nf, (size_t)NS * sizeof(u32));
+  }
+  clock.store(outs, n);
+  return KS_OK;
+}
+extern "C" int ks_audit_sizes(const ks_dev_problem* d, uint32_t* n_pods, uint32_t* n_node_slots) {
+  if (!d) return fail(KS_ERR_INVALID, "null argument");
+  if (n_pods) *n_pods = d->h.P;
+  if (n_node_slots) *n_node_slots = d->h.E + d->h.NMAX;
+  return KS_OK;
+}
+extern "C" int ks_audit_batch_dev(ks_dev_problem* const* ds, uint32_t n, ks_audit* const* outs) { return audit_batch(ds, n, outs, false, audit_run); }
+extern "C" int ks_audit_dev(ks_dev_problem* d, const ks_result* claimed, ks_audit* out) { return audit_one(d, claimed, out, AUD_READS_ALL, false, audit_run); }

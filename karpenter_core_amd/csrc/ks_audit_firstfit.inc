@@ -25,10 +25,6 @@ struct AuditFitView {
   u32* seqcnt; u32* used; u32* list;    // scratch: [P] placed pods per commit number | [C] the class is used by an examined pod, then its index in the list + 1 | [C] the used classes
   u32* first_e; u32* first_open; u32* first_m; u32* open; u32* cntr;      // scratch: [C] by list index: the least admitting existing node | the least open() over the admitting new nodes | the least admitting unlimited template | [NMAX] the least commit number on new node j | [4] placed pods, used classes, pairs evaluated, pairs that admitted
 };
-__device__ __forceinline__ bool aud_fit_seq_ok(const AuditView& V, const AuditFitView& F, u32 p, u32 n_placed) {      // (aud_topo_seq_ok over this pass's counts)
-  const i32 sq = GC(i32, V.pod_seq)[p];
-  return sq >= 0 && (u32)sq < n_placed && F.seqcnt[sq] == 1u;
-}
 // no topology group constrains the class (Topology.AddRequirements adds nothing) and it reserves no host port
 __device__ __forceinline__ bool aud_fit_examinable(const DevProb& P, u32 c) {
   return GC(u32, P.cls_own_off)[c + 1] == GC(u32, P.cls_own_off)[c] && GC(u32, P.cls_isel_off)[c + 1] == GC(u32, P.cls_isel_off)[c] && GC(u32, P.cls_port_off)[c + 1] == GC(u32, P.cls_port_off)[c];
@@ -40,26 +36,12 @@ __device__ __forceinline__ KReq aud_fit_cls_req(const DevProb& P, u32 c, u32 k) 
 // (requirements.go:196-200); this pass does not: a final state that passes only through that exception can have failed earlier (a node at Exists refuses the
 // DoesNotExist pod that the same node, later narrowed to DoesNotExist, lets through)
 __device__ __forceinline__ bool aud_fit_meet_empty(const KReq& a, const KReq& b, const i32* vi, u32 nv) { return a.present && b.present && kreq_len0(kreq_intersect(a, b, vi, nv)); }
-// the zone x capacity-type pairs a requirement set allows (ks_audit_nodes' way)
-__device__ __forceinline__ u64 aud_fit_pairs(const DevProb& P, const KReq& z, const KReq& ct) {
-  u64 allowZ = ~0ull, allowC = ~0ull;
-  if (P.key_zone >= 0 && z.present) allowZ = kreq_has_mask(z, P.value_int + P.key_zone * 64, GC(u32, P.key_nvalues)[P.key_zone]);
-  if (P.key_ct >= 0 && ct.present) allowC = kreq_has_mask(ct, P.value_int + P.key_ct * 64, GC(u32, P.key_nvalues)[P.key_ct]);
-  if (P.n_ct == 0) return ~0ull;
-  u64 pairs = 0;
-  for (u64 zz = allowZ; zz; zz &= zz - 1) { const int zi = __builtin_ctzll(zz); if ((u32)zi * P.n_ct >= 64) break; pairs |= (allowC & ((1ull << P.n_ct) - 1)) << (zi * P.n_ct); }
-  return pairs;
-}
 // admits_existing(c, e) for a pair that is examined (every key of the class is labelled on e): static facts of the flat problem plus one sum
 __device__ __forceinline__ bool aud_fit_existing(const DevProb& P, const AuditFitView& F, u32 c, u32 e) {
   const u32 K = P.K, R = P.R;
   if (GC(u64, P.en_taints)[e] & ~GC(u64, P.cls_tolerated)[c]) return false;
   const u32 hm = GC(u8, P.cls_hn_mode)[c];
-  if (hm) {
-    bool inlist = false;
-    for (u32 i = GC(u32, P.cls_hn_off)[c]; i < GC(u32, P.cls_hn_off)[c + 1]; ++i) if (GC(u32, P.hn_list)[i] == e) { inlist = true; break; }
-    if (hm == 1 ? !inlist : inlist) return false;
-  }
+  if (hm && (hm == 1) != aud_hn_listed(P, c, e)) return false;
   const u32 cp = GC(u32, P.cls.present)[c], ep = GC(u32, P.en.present)[e], ec = GC(u32, P.en.complement)[e];
   for (u32 k = 0; k < K; ++k) {
     if (!((cp >> k) & 1u)) continue;
@@ -94,8 +76,7 @@ __global__ __launch_bounds__(256) void ks_audit_ff_count(const DevProb* probs, c
       for (u32 r = 0; r < R; ++r) { const i64 v = GC(i64, P.cls_requests)[(size_t)c * R + r]; if (v) atomicAdd((unsigned long long*)&F.esum[(size_t)nd * R + r], (unsigned long long)v); }
     }
   }
-  s_sum[threadIdx.x] = mine;
-  for (u32 o = 128u; o > 0; o >>= 1) { __syncthreads(); if (threadIdx.x < o) s_sum[threadIdx.x] += s_sum[threadIdx.x + o]; }
+  aud_block_sum(s_sum, mine);
   if (threadIdx.x == 0 && s_sum[0]) atomicAdd(&F.cntr[0], s_sum[0]);
   for (u32 i = blockIdx.x * 256u + threadIdx.x; i < P.C; i += gridDim.x * 256u) { F.first_e[i] = KS_AF_NEVER; F.first_open[i] = KS_AF_NEVER; F.first_m[i] = KS_AF_NEVER; }
   for (u32 i = blockIdx.x * 256u + threadIdx.x; i < P.NMAX; i += gridDim.x * 256u) F.open[i] = KS_AF_NEVER;
@@ -105,7 +86,7 @@ __global__ __launch_bounds__(256) void ks_audit_ff_mark(const DevProb* probs, co
   const u32 np = P.P, E = P.E, NS = E + aud_n_new(P, V), n_placed = F.cntr[0];
   for (u32 p = blockIdx.x * 256u + threadIdx.x; p < np; p += gridDim.x * 256u) {
     const i32 nd = aud_where(P, V, p, NS);
-    const bool ok = nd >= 0 && aud_fit_seq_ok(V, F, p, n_placed);
+    const bool ok = nd >= 0 && aud_seq_ok(V, F.seqcnt, p, n_placed);
     if (!ok && GC(i32, V.pod_node)[p] != -1) continue;      // fails SEQ, or names no node of the result
     if (ok && (u32)nd >= E) atomicMin(&F.open[(u32)nd - E], (u32)GC(i32, V.pod_seq)[p]);
     const u32 c = aud_class(P, V, p);
@@ -195,7 +176,7 @@ __global__ __launch_bounds__(256) void ks_audit_ff_new(const DevProb* probs, con
       KReq rz = kreq_absent(), rc = kreq_absent();
       if (P.key_zone >= 0) rz = kreq_add(load_req(np_, nc_, nmask, ngt, nlt, P.key_zone), aud_fit_cls_req(P, c, (u32)P.key_zone), P.value_int + P.key_zone * 64, GC(u32, P.key_nvalues)[P.key_zone]);
       if (P.key_ct >= 0) rc = kreq_add(load_req(np_, nc_, nmask, ngt, nlt, P.key_ct), aud_fit_cls_req(P, c, (u32)P.key_ct), P.value_int + P.key_ct * 64, GC(u32, P.key_nvalues)[P.key_ct]);
-      const u64 pairs = aud_fit_pairs(P, rz, rc);
+      const u64 pairs = aud_pairs(P, rz, rc);
       for (u32 tw = 0; tw < TW; ++tw) {
         const u32 t = tw * 64u + lane;
         bool okl = t < T && ((GC(u64, ntypes)[tw] >> lane) & 1ull) && ((GC(u64, P.its_types)[(size_t)si * TW + tw] >> lane) & 1ull);
@@ -229,7 +210,7 @@ __global__ __launch_bounds__(256) void ks_audit_ff_verdict(const DevProb* probs,
   if (blockIdx.x == 0 && threadIdx.x == 0) { F.meta[0] = aud_n_new(P, V); F.meta[1] = n_placed; F.meta[2] = F.cntr[1]; F.meta[3] = F.cntr[2]; F.meta[4] = F.cntr[3]; }
   for (u32 p = blockIdx.x * 256u + threadIdx.x; p < np; p += gridDim.x * 256u) {
     const i32 nd = aud_where(P, V, p, NS);
-    const bool ok = nd >= 0 && aud_fit_seq_ok(V, F, p, n_placed), unsched = GC(i32, V.pod_node)[p] == -1;
+    const bool ok = nd >= 0 && aud_seq_ok(V, F.seqcnt, p, n_placed), unsched = GC(i32, V.pod_node)[p] == -1;
     u32 f = (nd >= 0 && !ok) ? KS_AUDIT_POD_SEQ : 0u, chk = nd >= 0 ? 1u << 30 : 0u;
     const u32 c = aud_class(P, V, p);
     const u32 u1 = F.used[c];      // (ks_audit_ff_mark marked the class of every examined pod: never 0 for one)
@@ -262,17 +243,17 @@ static int audit_firstfit_run(ks_dev_problem* const* ds, u32 n, const AuditView*
   BatchStage st; TRY(st.open(ds, n, nullptr, false));
   const size_t o_view = st.add<AuditView>(n), o_fview = st.add<AuditFitView>(n);
   TRY(st.place());
-  std::vector<size_t> o_fl(n), o_ck(n), o_scr(n); size_t at = 8 * (size_t)n; u32 pmax = 0; size_t emax = 1, nmax = 1;
-  for (u32 i = 0; i < n; ++i) { o_fl[i] = at; at += ds[i]->h.P; o_ck[i] = at; at += ds[i]->h.P; pmax = std::max(pmax, ds[i]->h.P); }
-  const size_t n_out = at;
+  AuditWork W(ds[0]->device); std::vector<size_t> o_fl(n), o_ck(n), o_scr(n); u32 pmax = 0; size_t emax = 1, nmax = 1;
+  W.out(8 * (size_t)n);
+  for (u32 i = 0; i < n; ++i) { o_fl[i] = W.out(ds[i]->h.P); o_ck[i] = W.out(ds[i]->h.P); pmax = std::max(pmax, ds[i]->h.P); }
   for (u32 i = 0; i < n; ++i) {
-    const DevProb& h = ds[i]->h; at += at & 1; o_scr[i] = at;      // (the int64 sums come first: 8-byte aligned)
-    at += 2 * (size_t)h.E * h.R + h.E + h.P + 5 * (size_t)h.C + h.NMAX + 4;
+    const DevProb& h = ds[i]->h;
+    o_scr[i] = W.scratch(2 * (size_t)h.E * h.R + h.E + h.P + 5 * (size_t)h.C + h.NMAX + 4, true);      // (the int64 sums come first: 8-byte aligned)
     const size_t used = std::min<size_t>(h.C, h.P);      // (no more classes are used than there are pods)
     emax = std::max(emax, used * (((size_t)h.E + 255) / 256)); nmax = std::max(nmax, (used * ((size_t)h.NMAX + h.M) + 3) / 4);
   }
-  TmpDev work(ds[0]->device); TRY(work.alloc(at * sizeof(u32)));
-  u32* w = work.as<u32>();
+  TRY(W.alloc());
+  u32* w = W.w();
   for (u32 i = 0; i < n; ++i) {
     AuditView v = results[i]; AuditFitView t{}; const DevProb& h = ds[i]->h; const size_t Pn = h.P, Cn = h.C, En = h.E;
     t.meta = w + 8 * (size_t)i; t.flags = w + o_fl[i]; t.chk = w + o_ck[i];
@@ -281,78 +262,31 @@ static int audit_firstfit_run(ks_dev_problem* const* ds, u32 n, const AuditView*
     v.meta = t.meta; v.mark = nullptr; v.pod_flags = nullptr; v.node_flags = nullptr; v.cnt = nullptr; v.off = nullptr; v.fill = nullptr; v.pods = nullptr;
     st.h<AuditView>(o_view)[i] = v; st.h<AuditFitView>(o_fview)[i] = t;
   }
-  const auto t0 = std::chrono::steady_clock::now();
+  AuditClock clock;
   TRY(st.upload(st.bytes));
-  HIPCHK(hipMemsetAsync(w, 0, at * sizeof(u32), st.stream()));
-  const u32 KS_GRID_Y_MAX = 65535u; const AuditView* dv = st.d<const AuditView>(o_view); const AuditFitView* df = st.d<const AuditFitView>(o_fview);
+  TRY(W.zero(st.stream()));
+  const AuditView* dv = st.d<const AuditView>(o_view); const AuditFitView* df = st.d<const AuditFitView>(o_fview);
   const u32 gx_p = std::max(1u, std::min(1024u, (pmax + 255u) / 256u)), gx_e = (u32)std::min<size_t>(4096, emax), gx_n = (u32)std::min<size_t>(4096, nmax);
-  for (u32 base = 0; base < n; base += KS_GRID_Y_MAX) {
-    const u32 ny = std::min(KS_GRID_Y_MAX, n - base);
+  audit_rows(n, [&](u32 base, u32 ny) {
     hipLaunchKernelGGL(ks_audit_ff_count, dim3(gx_p, ny), dim3(256), 0, st.stream(), st.probs() + base, dv + base, df + base);
     hipLaunchKernelGGL(ks_audit_ff_mark, dim3(gx_p, ny), dim3(256), 0, st.stream(), st.probs() + base, dv + base, df + base);
     hipLaunchKernelGGL(ks_audit_ff_compact, dim3(ny), dim3(256), 0, st.stream(), st.probs() + base, df + base);
     hipLaunchKernelGGL(ks_audit_ff_existing, dim3(gx_e, ny), dim3(256), 0, st.stream(), st.probs() + base, df + base);
     hipLaunchKernelGGL(ks_audit_ff_new, dim3(gx_n, ny), dim3(256), 0, st.stream(), st.probs() + base, dv + base, df + base);
     hipLaunchKernelGGL(ks_audit_ff_verdict, dim3(gx_p, ny), dim3(256), 0, st.stream(), st.probs() + base, dv + base, df + base);
-  }
-  HIPCHK(hipStreamSynchronize(st.stream())); HIPCHK(hipGetLastError());
-  const auto t1 = std::chrono::steady_clock::now();
-  std::vector<u32> back(n_out);
-  HIPCHK(hipMemcpy(back.data(), w, n_out * sizeof(u32), hipMemcpyDeviceToHost));
+  });
+  TRY(clock.wait(st.stream()));
+  TRY(W.read_back());
   for (u32 i = 0; i < n; ++i) {
-    ks_audit_firstfit* o = outs[i]; const u32 Pn = ds[i]->h.P; const u32* meta = back.data() + 8 * (size_t)i;
+    ks_audit_firstfit* o = outs[i]; const u32 Pn = ds[i]->h.P; const u32* meta = W.back.data() + 8 * (size_t)i;
     o->n_pods = Pn; o->n_new = meta[0]; o->n_placed = meta[1]; o->skipped_pods = 0; o->n_pods_flagged = 0; o->checked[0] = o->checked[1] = 0; o->checked[2] = meta[3]; o->admitting_pairs = meta[4];
-    const u32* pf = back.data() + o_fl[i]; const u32* ck = back.data() + o_ck[i];
-    for (u32 k = 0; k < Pn; ++k) { if (pf[k]) ++o->n_pods_flagged; o->checked[0] += ck[k] >> 30; o->checked[1] += ck[k] & 1u; o->skipped_pods += (ck[k] >> 29) & 1u; }
+    const u32* pf = W.back.data() + o_fl[i]; const u32* ck = W.back.data() + o_ck[i];
+    audit_tally(pf, Pn, &o->n_pods_flagged, nullptr);
+    for (u32 k = 0; k < Pn; ++k) { o->checked[0] += ck[k] >> 30; o->checked[1] += ck[k] & 1u; o->skipped_pods += (ck[k] >> 29) & 1u; }
     if (o->pod_flags && Pn) memcpy(o->pod_flags, pf, (size_t)Pn * sizeof(u32));
   }
-  const double kms = std::chrono::duration<double, std::milli>(t1 - t0).count(), rms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
-  for (u32 i = 0; i < n; ++i) { outs[i]->kernel_ms = kms; outs[i]->readback_ms = rms; }
+  clock.store(outs, n);
   return KS_OK;
 }
-extern "C" int ks_audit_firstfit_batch_dev(ks_dev_problem* const* ds, uint32_t n, ks_audit_firstfit* const* outs) {
-  if (!n) return KS_OK;
-  if (!ds || !outs) return fail(KS_ERR_INVALID, "null argument");
-  TRY(BatchStage::not_null(ds, n));
-  std::vector<AuditView> res(n);
-  for (u32 i = 0; i < n; ++i) {
-    if (!outs[i]) return fail(KS_ERR_INVALID, "null audit table");
-    if (ds[i]->device != ds[0]->device) return fail(KS_ERR_INVALID, "batch spans devices");
-    if (!ds[i]->solved) return fail(KS_ERR_INVALID, "audit of a problem that holds no result: solve it first (or the last solve failed)");
-    res[i] = audit_resident(ds[i]->hs);
-  }
-  return audit_firstfit_run(ds, n, res.data(), outs);
-}
-extern "C" int ks_audit_firstfit_dev(ks_dev_problem* d, const ks_result* claimed, ks_audit_firstfit* out) {
-  if (!d || !out) return fail(KS_ERR_INVALID, "null argument");
-  if (!claimed) return ks_audit_firstfit_batch_dev(&d, 1, &out);
-  if (d->view) return fail(KS_ERR_UNSUPPORTED, "a claimed result is audited against a flattened problem, not against a what-if derived on the device");
-  const DevProb& h = d->h; const u64 P = h.P, K = h.K, R = h.R, TW = h.TW, N = claimed->n_new;
-  if (N > h.NMAX) return fail(KS_ERR_INVALID, "claimed result: more new nodes than max_new_nodes");
-  if (claimed->n_unscheduled > P) return fail(KS_ERR_INVALID, "claimed result: more unscheduled pods than pods");
-  // what this pass reads of a result: the first pass's segments (pod_seq among them) without the unscheduled list
-#define KS_AUDIT_FIT_SEGS(X) \
-  X(pod_node, pod_node, i32, P) X(pod_stage, pod_stage, i32, P) X(pod_seq, pod_seq, i32, P) \
-  X(n_tmpl, node_tmpl, i32, N) X(n_alive, node_types, u64, N * TW) X(o_req, node_requests, i64, N * R) X(o_reqmask, node_requests_present, u32, N) \
-  X(o_present, node_present, u32, N) X(o_complement, node_complement, u32, N) X(o_mask, node_mask, u64, N * K) X(o_gt, node_gt, i32, N * K) X(o_lt, node_lt, i32, N * K) \
-  X(o_it, node_it_state, i32, N)
-#define X(sf, rf, T, cnt) if ((cnt) && !claimed->rf) return fail(KS_ERR_INVALID, "claimed result: null array " #rf);
-  KS_AUDIT_FIT_SEGS(X)
-#undef X
-  size_t bytes = 0;
-#define X(sf, rf, T, cnt) bytes += ks_pad8((cnt) * sizeof(T));
-  KS_AUDIT_FIT_SEGS(X)
-#undef X
-  std::vector<u64> blob(bytes / 8 + 1, 0); u8* hb = (u8*)blob.data();
-  HIPCHK(hipSetDevice(d->device));
-  TmpDev up(d->device); TRY(up.alloc(bytes + 8)); u8* db = up.as<u8>();
-  DevState s{}; size_t at = 0;
-#define X(sf, rf, T, cnt) { const size_t b_ = (cnt) * sizeof(T); if (b_) memcpy(hb + at, claimed->rf, b_); s.sf = (T*)(db + at); at += ks_pad8(b_); }
-  KS_AUDIT_FIT_SEGS(X)
-#undef X
-#undef KS_AUDIT_FIT_SEGS
-  { u32 c2[2] = {claimed->n_new, claimed->n_unscheduled}; memcpy(hb + at, c2, 8); s.out_counts = (u32*)(db + at); }
-  HIPCHK(hipMemcpy(db, hb, bytes + 8, hipMemcpyHostToDevice));
-  const AuditView v = audit_resident(s);
-  return audit_firstfit_run(&d, 1, &v, &out);
-}
+extern "C" int ks_audit_firstfit_batch_dev(ks_dev_problem* const* ds, uint32_t n, ks_audit_firstfit* const* outs) { return audit_batch(ds, n, outs, true, audit_firstfit_run); }
+extern "C" int ks_audit_firstfit_dev(ks_dev_problem* d, const ks_result* claimed, ks_audit_firstfit* out) { return audit_one(d, claimed, out, AUD_READS_FIT, true, audit_firstfit_run); }

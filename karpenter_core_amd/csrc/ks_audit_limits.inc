@@ -37,10 +37,6 @@ struct AuditLimView {
 __device__ __forceinline__ i64 aud_lim_sat_add(i64 a, i64 b) { return a > INT64_MAX - b ? INT64_MAX : a + b; }      // (both non-negative)
 __device__ __forceinline__ i64 aud_lim_sat_sub(i64 a, i64 b) { return a < INT64_MIN + b ? INT64_MIN : a - b; }      // (b non-negative)
 __device__ __forceinline__ i64 aud_lim_wave_max(i64 v) { for (int x = 32; x > 0; x >>= 1) { const i64 o = (i64)aud_xor64((u64)v, x); v = o > v ? o : v; } return v; }
-__device__ __forceinline__ bool aud_lim_seq_ok(const AuditView& V, const AuditLimView& F, u32 p, u32 n_placed) {
-  const i32 sq = GC(i32, V.pod_seq)[p];
-  return sq >= 0 && (u32)sq < n_placed && F.seqcnt[sq] == 1u;
-}
 // the requirements, requests and type set a type is filtered against: a fresh node of template m with one pod of class c, or new node j as the result leaves it
 struct AudLimNode { u32 np_, nc_, rmask, c; const u64* nmask; const i32* ngt; const i32* nlt; const i64* nreq; u64 pairs; bool cls; };
 __device__ __forceinline__ KReq aud_lim_req(const DevProb& P, const AudLimNode& n, u32 k) {
@@ -51,7 +47,7 @@ __device__ __forceinline__ void aud_lim_pairs_of(const DevProb& P, AudLimNode& n
   KReq rz = kreq_absent(), rc = kreq_absent();
   if (P.key_zone >= 0) rz = aud_lim_req(P, n, (u32)P.key_zone);
   if (P.key_ct >= 0) rc = aud_lim_req(P, n, (u32)P.key_ct);
-  n.pairs = aud_fit_pairs(P, rz, rc);
+  n.pairs = aud_pairs(P, rz, rc);
 }
 __device__ __forceinline__ AudLimNode aud_lim_fresh(const DevProb& P, u32 m, u32 c) {
   AudLimNode n; const u32 K = P.K;
@@ -107,8 +103,7 @@ __global__ __launch_bounds__(256) void ks_audit_lim_count(const DevProb* probs, 
     ++mine;
     if (sq >= 0 && (u32)sq < np) atomicAdd(&F.seqcnt[sq], 1u);
   }
-  s_sum[threadIdx.x] = mine;
-  for (u32 o = 128u; o > 0; o >>= 1) { __syncthreads(); if (threadIdx.x < o) s_sum[threadIdx.x] += s_sum[threadIdx.x + o]; }
+  aud_block_sum(s_sum, mine);
   if (threadIdx.x == 0 && s_sum[0]) atomicAdd(&F.cntr[0], s_sum[0]);
   if (F.n_limited) for (u32 i = blockIdx.x * 256u + threadIdx.x; i < P.NMAX; i += gridDim.x * 256u) F.open[i] = KS_AL_NEVER64;
 }
@@ -118,7 +113,7 @@ __global__ __launch_bounds__(256) void ks_audit_lim_mark(const DevProb* probs, c
   const u32 np = P.P, E = P.E, NS = E + aud_n_new(P, V), n_placed = F.cntr[0];
   for (u32 p = blockIdx.x * 256u + threadIdx.x; p < np; p += gridDim.x * 256u) {
     const i32 nd = aud_where(P, V, p, NS);
-    const bool ok = nd >= 0 && aud_lim_seq_ok(V, F, p, n_placed);
+    const bool ok = nd >= 0 && aud_seq_ok(V, F.seqcnt, p, n_placed);
     if (!ok && GC(i32, V.pod_node)[p] != -1) continue;      // fails SEQ, or names no node of the result
     if (ok && (u32)nd >= E) atomicMin((unsigned long long*)&F.open[(u32)nd - E], (unsigned long long)(((u64)(u32)GC(i32, V.pod_seq)[p] << 32) | p));
     const u32 c = aud_class(P, V, p);
@@ -354,7 +349,7 @@ __global__ __launch_bounds__(256) void ks_audit_lim_verdict(const DevProb* probs
   if (blockIdx.x == 0 && threadIdx.x == 0) { F.meta[0] = aud_n_new(P, V); F.meta[1] = n_placed; F.meta[2] = F.cntr[2]; F.meta[3] = F.cntr[3]; F.meta[4] = F.cntr[4]; F.meta[5] = F.cntr[5]; F.meta[6] = F.cntr[6]; }
   for (u32 p = blockIdx.x * 256u + threadIdx.x; p < np; p += gridDim.x * 256u) {
     const i32 nd = aud_where(P, V, p, NS);
-    const bool ok = nd >= 0 && aud_lim_seq_ok(V, F, p, n_placed), unsched = GC(i32, V.pod_node)[p] == -1;
+    const bool ok = nd >= 0 && aud_seq_ok(V, F.seqcnt, p, n_placed), unsched = GC(i32, V.pod_node)[p] == -1;
     u32 f = (nd >= 0 && !ok) ? KS_AUDIT_POD_SEQ : 0u; const u32 chk = nd >= 0 ? 1u << 30 : 0u;
     if (!F.n_limited) { F.pflags[p] = f; F.pchk[p] = chk; continue; }
     const u32 c = aud_class(P, V, p);
@@ -384,19 +379,19 @@ static int audit_limits_run(ks_dev_problem* const* ds, u32 n, const AuditView* r
   BatchStage st; TRY(st.open(ds, n, nullptr, false));
   const size_t o_view = st.add<AuditView>(n), o_lview = st.add<AuditLimView>(n);
   TRY(st.place());
-  std::vector<size_t> o_fl(n), o_ck(n), o_nf(n), o_scr(n); size_t at = 8 * (size_t)n; u32 pmax = 0, nnmax = 1, mmax = 0; size_t prmax = 1; bool any_limited = false;
-  for (u32 i = 0; i < n; ++i) { const DevProb& h = ds[i]->h; o_fl[i] = at; at += h.P; o_ck[i] = at; at += h.P; o_nf[i] = at; at += (size_t)h.E + h.NMAX; pmax = std::max(pmax, h.P); }
-  const size_t n_out = at;
+  AuditWork W(ds[0]->device); std::vector<size_t> o_fl(n), o_ck(n), o_nf(n), o_scr(n); u32 pmax = 0, nnmax = 1, mmax = 0; size_t prmax = 1; bool any_limited = false;
+  W.out(8 * (size_t)n);
+  for (u32 i = 0; i < n; ++i) { const DevProb& h = ds[i]->h; o_fl[i] = W.out(h.P); o_ck[i] = W.out(h.P); o_nf[i] = W.out((size_t)h.E + h.NMAX); pmax = std::max(pmax, h.P); }
   for (u32 i = 0; i < n; ++i) {
-    const DevProb& h = ds[i]->h; at += at & 1; o_scr[i] = at;      // (the int64 tables come first: 8-byte aligned)
-    if (!ds[i]->n_limited) { at += (size_t)h.P + 8; continue; }      // (SEQ alone: the counts per commit number and the counters)
+    const DevProb& h = ds[i]->h;      // (the int64 tables come first in the scratch: 8-byte aligned)
+    if (!ds[i]->n_limited) { o_scr[i] = W.scratch((size_t)h.P + 8, true); continue; }      // (SEQ alone: the counts per commit number and the counters)
     any_limited = true;
     const size_t used = std::min<size_t>(h.C, h.P), NM = h.NMAX, R = h.R;
-    at += 2 * (3 * NM * R + (NM + h.M) * R + NM) + 2 * (size_t)h.P + 2 * (size_t)h.C + 3 * NM + 3 * (size_t)h.M + used * h.M + 8;
+    o_scr[i] = W.scratch(2 * (3 * NM * R + (NM + h.M) * R + NM) + 2 * (size_t)h.P + 2 * (size_t)h.C + 3 * NM + 3 * (size_t)h.M + used * h.M + 8, true);
     nnmax = std::max(nnmax, h.NMAX); mmax = std::max(mmax, h.M); prmax = std::max(prmax, (used * h.M + 3) / 4);
   }
-  TmpDev work(ds[0]->device); TRY(work.alloc(at * sizeof(u32)));
-  u32* w = work.as<u32>();
+  TRY(W.alloc());
+  u32* w = W.w();
   for (u32 i = 0; i < n; ++i) {
     AuditView v = results[i]; AuditLimView t{}; const DevProb& h = ds[i]->h; const size_t Pn = h.P, Cn = h.C, NM = h.NMAX, R = h.R, Mn = h.M;
     t.meta = w + 8 * (size_t)i; t.pflags = w + o_fl[i]; t.pchk = w + o_ck[i]; t.nflags = w + o_nf[i]; t.n_limited = ds[i]->n_limited;
@@ -410,13 +405,12 @@ static int audit_limits_run(ks_dev_problem* const* ds, u32 n, const AuditView* r
     v.meta = t.meta; v.mark = nullptr; v.pod_flags = nullptr; v.node_flags = nullptr; v.cnt = nullptr; v.off = nullptr; v.fill = nullptr; v.pods = nullptr;
     st.h<AuditView>(o_view)[i] = v; st.h<AuditLimView>(o_lview)[i] = t;
   }
-  const auto t0 = std::chrono::steady_clock::now();
+  AuditClock clock;
   TRY(st.upload(st.bytes));
-  HIPCHK(hipMemsetAsync(w, 0, at * sizeof(u32), st.stream()));
-  const u32 KS_GRID_Y_MAX = 65535u; const AuditView* dv = st.d<const AuditView>(o_view); const AuditLimView* df = st.d<const AuditLimView>(o_lview);
+  TRY(W.zero(st.stream()));
+  const AuditView* dv = st.d<const AuditView>(o_view); const AuditLimView* df = st.d<const AuditLimView>(o_lview);
   const u32 gx_p = std::max(1u, std::min(1024u, (pmax + 255u) / 256u)), gx_n = std::max(1u, std::min(4096u, (nnmax + 3u) / 4u)), gx_r = (u32)std::min<size_t>(4096, prmax);
-  for (u32 base = 0; base < n; base += KS_GRID_Y_MAX) {
-    const u32 ny = std::min(KS_GRID_Y_MAX, n - base);
+  audit_rows(n, [&](u32 base, u32 ny) {
     hipLaunchKernelGGL(ks_audit_lim_count, dim3(gx_p, ny), dim3(256), 0, st.stream(), st.probs() + base, dv + base, df + base);
     if (any_limited) {      // (no limited template anywhere in the batch: SEQ alone)
       hipLaunchKernelGGL(ks_audit_lim_mark, dim3(gx_p, ny), dim3(256), 0, st.stream(), st.probs() + base, dv + base, df + base);
@@ -428,72 +422,22 @@ static int audit_limits_run(ks_dev_problem* const* ds, u32 n, const AuditView* r
       hipLaunchKernelGGL(ks_audit_lim_pairs, dim3(gx_r, ny), dim3(256), 0, st.stream(), st.probs() + base, df + base);
     }
     hipLaunchKernelGGL(ks_audit_lim_verdict, dim3(gx_p, ny), dim3(256), 0, st.stream(), st.probs() + base, dv + base, df + base);
-  }
-  HIPCHK(hipStreamSynchronize(st.stream())); HIPCHK(hipGetLastError());
-  const auto t1 = std::chrono::steady_clock::now();
-  std::vector<u32> back(n_out);
-  HIPCHK(hipMemcpy(back.data(), w, n_out * sizeof(u32), hipMemcpyDeviceToHost));
+  });
+  TRY(clock.wait(st.stream()));
+  TRY(W.read_back());
   for (u32 i = 0; i < n; ++i) {
-    ks_audit_limits* o = outs[i]; const u32 Pn = ds[i]->h.P; const u32* meta = back.data() + 8 * (size_t)i; const u32 NS = ds[i]->h.E + meta[0];
+    ks_audit_limits* o = outs[i]; const u32 Pn = ds[i]->h.P; const u32* meta = W.back.data() + 8 * (size_t)i; const u32 NS = ds[i]->h.E + meta[0];
     o->n_pods = Pn; o->n_nodes = NS; o->n_new = meta[0]; o->n_placed = meta[1]; o->limited_templates = ds[i]->n_limited; o->skipped_nodes = meta[2]; o->skipped_pods = 0;
     o->n_pods_flagged = 0; o->n_nodes_flagged = 0; o->checked[0] = 0; o->checked[1] = meta[3]; o->checked[2] = 0; o->checked[3] = meta[4]; o->exact_nodes = meta[5]; o->binding_nodes = meta[6];
     memset(o->pod_bit_count, 0, sizeof o->pod_bit_count); memset(o->node_bit_count, 0, sizeof o->node_bit_count);
-    const u32* pf = back.data() + o_fl[i]; const u32* ck = back.data() + o_ck[i]; const u32* nf = back.data() + o_nf[i];
-    for (u32 k = 0; k < Pn; ++k) {
-      if (pf[k]) { ++o->n_pods_flagged; for (u32 x = pf[k]; x; x &= x - 1) ++o->pod_bit_count[__builtin_ctz(x)]; }
-      o->checked[0] += ck[k] >> 30; o->checked[2] += ck[k] & 1u; o->skipped_pods += (ck[k] >> 29) & 1u;
-    }
-    for (u32 k = 0; k < NS; ++k) if (nf[k]) { ++o->n_nodes_flagged; for (u32 x = nf[k]; x; x &= x - 1) ++o->node_bit_count[__builtin_ctz(x)]; }
+    const u32* pf = W.back.data() + o_fl[i]; const u32* ck = W.back.data() + o_ck[i]; const u32* nf = W.back.data() + o_nf[i];
+    audit_tally(pf, Pn, &o->n_pods_flagged, o->pod_bit_count); audit_tally(nf, NS, &o->n_nodes_flagged, o->node_bit_count);
+    for (u32 k = 0; k < Pn; ++k) { o->checked[0] += ck[k] >> 30; o->checked[2] += ck[k] & 1u; o->skipped_pods += (ck[k] >> 29) & 1u; }
     if (o->pod_flags && Pn) memcpy(o->pod_flags, pf, (size_t)Pn * sizeof(u32));
     if (o->node_flags && NS) memcpy(o->node_flags, nf, (size_t)NS * sizeof(u32));
   }
-  const double kms = std::chrono::duration<double, std::milli>(t1 - t0).count(), rms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
-  for (u32 i = 0; i < n; ++i) { outs[i]->kernel_ms = kms; outs[i]->readback_ms = rms; }
+  clock.store(outs, n);
   return KS_OK;
 }
-extern "C" int ks_audit_limits_batch_dev(ks_dev_problem* const* ds, uint32_t n, ks_audit_limits* const* outs) {
-  if (!n) return KS_OK;
-  if (!ds || !outs) return fail(KS_ERR_INVALID, "null argument");
-  TRY(BatchStage::not_null(ds, n));
-  std::vector<AuditView> res(n);
-  for (u32 i = 0; i < n; ++i) {
-    if (!outs[i]) return fail(KS_ERR_INVALID, "null audit table");
-    if (ds[i]->device != ds[0]->device) return fail(KS_ERR_INVALID, "batch spans devices");
-    if (!ds[i]->solved) return fail(KS_ERR_INVALID, "audit of a problem that holds no result: solve it first (or the last solve failed)");
-    res[i] = audit_resident(ds[i]->hs);
-  }
-  return audit_limits_run(ds, n, res.data(), outs);
-}
-extern "C" int ks_audit_limits_dev(ks_dev_problem* d, const ks_result* claimed, ks_audit_limits* out) {
-  if (!d || !out) return fail(KS_ERR_INVALID, "null argument");
-  if (!claimed) return ks_audit_limits_batch_dev(&d, 1, &out);
-  if (d->view) return fail(KS_ERR_UNSUPPORTED, "a claimed result is audited against a flattened problem, not against a what-if derived on the device");
-  const DevProb& h = d->h; const u64 P = h.P, K = h.K, R = h.R, TW = h.TW, N = claimed->n_new;
-  if (N > h.NMAX) return fail(KS_ERR_INVALID, "claimed result: more new nodes than max_new_nodes");
-  if (claimed->n_unscheduled > P) return fail(KS_ERR_INVALID, "claimed result: more unscheduled pods than pods");
-  // what this pass reads of a result: the fourth pass's segments
-#define KS_AUDIT_LIM_SEGS(X) \
-  X(pod_node, pod_node, i32, P) X(pod_stage, pod_stage, i32, P) X(pod_seq, pod_seq, i32, P) \
-  X(n_tmpl, node_tmpl, i32, N) X(n_alive, node_types, u64, N * TW) X(o_req, node_requests, i64, N * R) X(o_reqmask, node_requests_present, u32, N) \
-  X(o_present, node_present, u32, N) X(o_complement, node_complement, u32, N) X(o_mask, node_mask, u64, N * K) X(o_gt, node_gt, i32, N * K) X(o_lt, node_lt, i32, N * K) \
-  X(o_it, node_it_state, i32, N)
-#define X(sf, rf, T, cnt) if ((cnt) && !claimed->rf) return fail(KS_ERR_INVALID, "claimed result: null array " #rf);
-  KS_AUDIT_LIM_SEGS(X)
-#undef X
-  size_t bytes = 0;
-#define X(sf, rf, T, cnt) bytes += ks_pad8((cnt) * sizeof(T));
-  KS_AUDIT_LIM_SEGS(X)
-#undef X
-  std::vector<u64> blob(bytes / 8 + 1, 0); u8* hb = (u8*)blob.data();
-  HIPCHK(hipSetDevice(d->device));
-  TmpDev up(d->device); TRY(up.alloc(bytes + 8)); u8* db = up.as<u8>();
-  DevState s{}; size_t at = 0;
-#define X(sf, rf, T, cnt) { const size_t b_ = (cnt) * sizeof(T); if (b_) memcpy(hb + at, claimed->rf, b_); s.sf = (T*)(db + at); at += ks_pad8(b_); }
-  KS_AUDIT_LIM_SEGS(X)
-#undef X
-#undef KS_AUDIT_LIM_SEGS
-  { u32 c2[2] = {claimed->n_new, claimed->n_unscheduled}; memcpy(hb + at, c2, 8); s.out_counts = (u32*)(db + at); }
-  HIPCHK(hipMemcpy(db, hb, bytes + 8, hipMemcpyHostToDevice));
-  const AuditView v = audit_resident(s);
-  return audit_limits_run(&d, 1, &v, &out);
-}
+extern "C" int ks_audit_limits_batch_dev(ks_dev_problem* const* ds, uint32_t n, ks_audit_limits* const* outs) { return audit_batch(ds, n, outs, true, audit_limits_run); }
+extern "C" int ks_audit_limits_dev(ks_dev_problem* d, const ks_result* claimed, ks_audit_limits* out) { return audit_one(d, claimed, out, AUD_READS_FIT, true, audit_limits_run); }

@@ -27,10 +27,6 @@ struct AuditSpreadView {
   u32* elig; u32* cntr; u32* tab;        // scratch: [G] the group is examined | [1] placed pods | [chunks][G][KS_AS_ROW] the chunk's recorders, then (scanned) those of the chunks before it
 };
 __device__ __forceinline__ u32 aud_spr_chunks(u32 np) { const u32 n = (np + KS_AS_CHUNK - 1u) / KS_AS_CHUNK; return n ? n : 1u; }
-__device__ __forceinline__ bool aud_spr_seq_ok(const AuditView& V, const AuditSpreadView& S, u32 p, u32 n_placed) {      // (aud_topo_seq_ok over this pass's counts)
-  const i32 sq = GC(i32, V.pod_seq)[p];
-  return sq >= 0 && (u32)sq < n_placed && S.seqcnt[sq] == 1u;
-}
 // was the requirement of node nd on key k one value when the pod with commit number sq was recorded?
 __device__ __forceinline__ bool aud_spr_certain(const DevProb& P, const AuditView& V, const AuditSpreadView& S, u32 nd, u32 k, u32 sq) {
   if (nd < P.E) { if (((GC(u32, P.en.present)[nd] >> k) & 1u) && !((GC(u32, P.en.complement)[nd] >> k) & 1u)) return true; }
@@ -63,8 +59,7 @@ __global__ __launch_bounds__(256) void ks_audit_spread_count(const DevProb* prob
     const i32 nd = aud_where(P, V, i, NS), sq = GC(i32, V.pod_seq)[i];
     if (nd >= 0) { ++mine; if (sq >= 0 && (u32)sq < np) atomicAdd(&S.seqcnt[sq], 1u); }
   }
-  s_sum[threadIdx.x] = mine;
-  for (u32 o = 128u; o > 0; o >>= 1) { __syncthreads(); if (threadIdx.x < o) s_sum[threadIdx.x] += s_sum[threadIdx.x + o]; }
+  aud_block_sum(s_sum, mine);
   if (threadIdx.x == 0 && s_sum[0]) atomicAdd(&S.cntr[0], s_sum[0]);
   for (u32 i = blockIdx.x * 256u + threadIdx.x; i < npin; i += gridDim.x * 256u) S.pin[i] = KS_AT_NEVER;
   if (blockIdx.x == 0) {      // (the same in all 256 threads: every thread takes the barriers below)
@@ -76,8 +71,7 @@ __global__ __launch_bounds__(256) void ks_audit_spread_count(const DevProb* prob
       if (spread && !ok) ++un;
     }
     __syncthreads();
-    s_sum[threadIdx.x] = un;
-    for (u32 o = 128u; o > 0; o >>= 1) { __syncthreads(); if (threadIdx.x < o) s_sum[threadIdx.x] += s_sum[threadIdx.x + o]; }
+    aud_block_sum(s_sum, un);
     if (threadIdx.x == 0) S.meta[2] = s_sum[0];
   }
 }
@@ -87,7 +81,7 @@ __global__ __launch_bounds__(256) void ks_audit_spread_order(const DevProb* prob
   if (blockIdx.x == 0 && threadIdx.x == 0) { S.meta[0] = aud_n_new(P, V); S.meta[1] = n_placed; }
   for (u32 p = blockIdx.x * 256u + threadIdx.x; p < np; p += gridDim.x * 256u) {
     const i32 nd = aud_where(P, V, p, NS);
-    const bool ok = nd >= 0 && aud_spr_seq_ok(V, S, p, n_placed);
+    const bool ok = nd >= 0 && aud_seq_ok(V, S.seqcnt, p, n_placed);
     S.flags[p] = (nd >= 0 && !ok) ? KS_AUDIT_POD_SEQ : 0u; S.chk[p] = nd >= 0 ? 1u << 30 : 0u;
     if (!ok) continue;
     const u32 sq = (u32)GC(i32, V.pod_seq)[p], c = aud_class(P, V, p);
@@ -213,21 +207,21 @@ __global__ __launch_bounds__(64) void ks_audit_spread_pods(const DevProb* probs,
 }
 
 // ---- host half ----
-// A batch is walked in slices, as audit_topo_run walks it with `first`: the chunk table is chunks x G x KS_AS_ROW words per problem (sized here, from P and G), and a
-// slice holds at most KS_AUDIT_SPREAD_TAB_WORDS of them (64 MiB), or one problem.
+// A batch is walked in slices (audit_slices), as the second pass walks it with `first`: the chunk table is chunks x G x KS_AS_ROW words per problem (sized here, from
+// P and G), and a slice holds at most KS_AUDIT_SPREAD_TAB_WORDS of them (64 MiB), or one problem.
 #define KS_AUDIT_SPREAD_TAB_WORDS ((size_t)16 << 20)
 static size_t audit_spread_tab_words(const ks_dev_problem* d) { const size_t nch = std::max<size_t>(1, ((size_t)d->h.P + KS_AS_CHUNK - 1) / KS_AS_CHUNK); return nch * d->h.G * KS_AS_ROW; }
 static int audit_spread_slice(ks_dev_problem* const* ds, u32 n, const AuditView* results, ks_audit_spread* const* outs, double* kernel_ms, double* readback_ms) {
   BatchStage st; TRY(st.open(ds, n, nullptr, false));
   const size_t o_view = st.add<AuditView>(n), o_sview = st.add<AuditSpreadView>(n);
   TRY(st.place());
-  std::vector<size_t> o_fl(n), o_ck(n), o_scr(n); size_t at = 4 * (size_t)n; u32 pmax = 0, chmax = 1; size_t wmax = 1;
-  for (u32 i = 0; i < n; ++i) { o_fl[i] = at; at += ds[i]->h.P; o_ck[i] = at; at += ds[i]->h.P; pmax = std::max(pmax, ds[i]->h.P); wmax = std::max(wmax, (size_t)ds[i]->h.G * KS_AS_ROW); }
+  AuditWork W(ds[0]->device); std::vector<size_t> o_fl(n), o_ck(n), o_scr(n); u32 pmax = 0, chmax = 1; size_t wmax = 1;
+  W.out(4 * (size_t)n);
+  for (u32 i = 0; i < n; ++i) { o_fl[i] = W.out(ds[i]->h.P); o_ck[i] = W.out(ds[i]->h.P); pmax = std::max(pmax, ds[i]->h.P); wmax = std::max(wmax, (size_t)ds[i]->h.G * KS_AS_ROW); }
   chmax = std::max(1u, (pmax + KS_AS_CHUNK - 1u) / KS_AS_CHUNK);
-  const size_t n_out = at;
-  for (u32 i = 0; i < n; ++i) { const DevProb& h = ds[i]->h; o_scr[i] = at; at += 2 * (size_t)h.P + ((size_t)h.E + h.NMAX) * h.K + h.G + 1 + audit_spread_tab_words(ds[i]); }
-  TmpDev work(ds[0]->device); TRY(work.alloc(at * sizeof(u32)));
-  u32* w = work.as<u32>();
+  for (u32 i = 0; i < n; ++i) { const DevProb& h = ds[i]->h; o_scr[i] = W.scratch(2 * (size_t)h.P + ((size_t)h.E + h.NMAX) * h.K + h.G + 1 + audit_spread_tab_words(ds[i])); }
+  TRY(W.alloc());
+  u32* w = W.w();
   for (u32 i = 0; i < n; ++i) {
     AuditView v = results[i]; AuditSpreadView t{}; const DevProb& h = ds[i]->h; const size_t Pn = h.P, npin = ((size_t)h.E + h.NMAX) * h.K;
     t.meta = w + 4 * (size_t)i; t.flags = w + o_fl[i]; t.chk = w + o_ck[i];
@@ -235,88 +229,35 @@ static int audit_spread_slice(ks_dev_problem* const* ds, u32 n, const AuditView*
     v.meta = t.meta; v.mark = nullptr; v.pod_flags = nullptr; v.node_flags = nullptr; v.cnt = nullptr; v.off = nullptr; v.fill = nullptr; v.pods = nullptr;
     st.h<AuditView>(o_view)[i] = v; st.h<AuditSpreadView>(o_sview)[i] = t;
   }
-  const auto t0 = std::chrono::steady_clock::now();
+  AuditClock clock;
   TRY(st.upload(st.bytes));
-  HIPCHK(hipMemsetAsync(w, 0, at * sizeof(u32), st.stream()));
-  const u32 KS_GRID_Y_MAX = 65535u; const AuditView* dv = st.d<const AuditView>(o_view); const AuditSpreadView* dt = st.d<const AuditSpreadView>(o_sview);
+  TRY(W.zero(st.stream()));
+  const AuditView* dv = st.d<const AuditView>(o_view); const AuditSpreadView* dt = st.d<const AuditSpreadView>(o_sview);
   const u32 gx_p = std::max(1u, std::min(1024u, (pmax + 255u) / 256u)), gx_c = std::min(4096u, chmax), gx_s = (u32)std::max<size_t>(1, std::min<size_t>(1024, (wmax + 255) / 256));
-  for (u32 base = 0; base < n; base += KS_GRID_Y_MAX) {
-    const u32 ny = std::min(KS_GRID_Y_MAX, n - base);
+  audit_rows(n, [&](u32 base, u32 ny) {
     hipLaunchKernelGGL(ks_audit_spread_count, dim3(gx_p, ny), dim3(256), 0, st.stream(), st.probs() + base, dv + base, dt + base);
     hipLaunchKernelGGL(ks_audit_spread_order, dim3(gx_p, ny), dim3(256), 0, st.stream(), st.probs() + base, dv + base, dt + base);
     hipLaunchKernelGGL(ks_audit_spread_chunks, dim3(gx_p, ny), dim3(256), 0, st.stream(), st.probs() + base, dv + base, dt + base);
     hipLaunchKernelGGL(ks_audit_spread_scan, dim3(gx_s, ny), dim3(256), 0, st.stream(), st.probs() + base, dt + base);
     hipLaunchKernelGGL(ks_audit_spread_pods, dim3(gx_c, ny), dim3(64), 0, st.stream(), st.probs() + base, dv + base, dt + base);
-  }
-  HIPCHK(hipStreamSynchronize(st.stream())); HIPCHK(hipGetLastError());
-  const auto t1 = std::chrono::steady_clock::now();
-  std::vector<u32> back(n_out);
-  HIPCHK(hipMemcpy(back.data(), w, n_out * sizeof(u32), hipMemcpyDeviceToHost));
+  });
+  TRY(clock.wait(st.stream()));
+  TRY(W.read_back());
   for (u32 i = 0; i < n; ++i) {
-    ks_audit_spread* o = outs[i]; const u32 Pn = ds[i]->h.P; const u32* meta = back.data() + 4 * (size_t)i;
+    ks_audit_spread* o = outs[i]; const u32 Pn = ds[i]->h.P; const u32* meta = W.back.data() + 4 * (size_t)i;
     o->n_pods = Pn; o->n_new = meta[0]; o->n_placed = meta[1]; o->skipped_groups = meta[2]; o->n_pods_flagged = 0; o->checked[0] = o->checked[1] = 0; o->exact_pairs = 0;
-    const u32* pf = back.data() + o_fl[i]; const u32* ck = back.data() + o_ck[i];
-    for (u32 k = 0; k < Pn; ++k) { if (pf[k]) ++o->n_pods_flagged; o->checked[0] += ck[k] >> 30; o->checked[1] += ck[k] & 1023u; o->exact_pairs += (ck[k] >> 10) & 1023u; }
+    const u32* pf = W.back.data() + o_fl[i]; const u32* ck = W.back.data() + o_ck[i];
+    audit_tally(pf, Pn, &o->n_pods_flagged, nullptr);
+    for (u32 k = 0; k < Pn; ++k) { o->checked[0] += ck[k] >> 30; o->checked[1] += ck[k] & 1023u; o->exact_pairs += (ck[k] >> 10) & 1023u; }
     if (o->pod_flags && Pn) memcpy(o->pod_flags, pf, (size_t)Pn * sizeof(u32));
   }
-  *kernel_ms += std::chrono::duration<double, std::milli>(t1 - t0).count();
-  *readback_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
+  clock.add(kernel_ms, readback_ms);
   return KS_OK;
 }
 static int audit_spread_run(ks_dev_problem* const* ds, u32 n, const AuditView* results, ks_audit_spread* const* outs) {
-  double kms = 0.0, rms = 0.0;
   size_t budget = KS_AUDIT_SPREAD_TAB_WORDS;
   if (const char* e = getenv("KS_AUDIT_SPREAD_SLICE_WORDS")) budget = (size_t)strtoull(e, nullptr, 0);      // (diagnostic, as KS_POISON: lets a test walk a small batch in slices; the flags must not depend on it)
-  for (u32 base = 0; base < n;) {
-    u32 m = 0; size_t words = 0;
-    while (base + m < n && (m == 0 || words + audit_spread_tab_words(ds[base + m]) <= budget)) { words += audit_spread_tab_words(ds[base + m]); ++m; }
-    TRY(audit_spread_slice(ds + base, m, results + base, outs + base, &kms, &rms));
-    base += m;
-  }
-  for (u32 i = 0; i < n; ++i) { outs[i]->kernel_ms = kms; outs[i]->readback_ms = rms; }
-  return KS_OK;
+  return audit_slices(ds, n, results, outs, audit_spread_tab_words, budget, audit_spread_slice);
 }
-extern "C" int ks_audit_spread_batch_dev(ks_dev_problem* const* ds, uint32_t n, ks_audit_spread* const* outs) {
-  if (!n) return KS_OK;
-  if (!ds || !outs) return fail(KS_ERR_INVALID, "null argument");
-  TRY(BatchStage::not_null(ds, n));
-  std::vector<AuditView> res(n);
-  for (u32 i = 0; i < n; ++i) {
-    if (!outs[i]) return fail(KS_ERR_INVALID, "null audit table");
-    if (ds[i]->device != ds[0]->device) return fail(KS_ERR_INVALID, "batch spans devices");
-    if (!ds[i]->solved) return fail(KS_ERR_INVALID, "audit of a problem that holds no result: solve it first (or the last solve failed)");
-    res[i] = audit_resident(ds[i]->hs);
-  }
-  return audit_spread_run(ds, n, res.data(), outs);
-}
-extern "C" int ks_audit_spread_dev(ks_dev_problem* d, const ks_result* claimed, ks_audit_spread* out) {
-  if (!d || !out) return fail(KS_ERR_INVALID, "null argument");
-  if (!claimed) return ks_audit_spread_batch_dev(&d, 1, &out);
-  if (d->view) return fail(KS_ERR_UNSUPPORTED, "a claimed result is audited against a flattened problem, not against a what-if derived on the device");
-  const DevProb& h = d->h; const u64 P = h.P, K = h.K, N = claimed->n_new;
-  if (N > h.NMAX) return fail(KS_ERR_INVALID, "claimed result: more new nodes than max_new_nodes");
-  if (claimed->n_unscheduled > P) return fail(KS_ERR_INVALID, "claimed result: more unscheduled pods than pods");
-  // what this pass reads of a result: the second pass's segments
-#define KS_AUDIT_SPREAD_SEGS(X) \
-  X(pod_node, pod_node, i32, P) X(pod_stage, pod_stage, i32, P) X(pod_seq, pod_seq, i32, P) X(n_tmpl, node_tmpl, i32, N) \
-  X(o_present, node_present, u32, N) X(o_complement, node_complement, u32, N) X(o_mask, node_mask, u64, N * K) X(o_gt, node_gt, i32, N * K) X(o_lt, node_lt, i32, N * K)
-#define X(sf, rf, T, cnt) if ((cnt) && !claimed->rf) return fail(KS_ERR_INVALID, "claimed result: null array " #rf);
-  KS_AUDIT_SPREAD_SEGS(X)
-#undef X
-  size_t bytes = 0;
-#define X(sf, rf, T, cnt) bytes += ks_pad8((cnt) * sizeof(T));
-  KS_AUDIT_SPREAD_SEGS(X)
-#undef X
-  std::vector<u64> blob(bytes / 8 + 1, 0); u8* hb = (u8*)blob.data();
-  HIPCHK(hipSetDevice(d->device));
-  TmpDev up(d->device); TRY(up.alloc(bytes + 8)); u8* db = up.as<u8>();
-  DevState s{}; size_t at = 0;
-#define X(sf, rf, T, cnt) { const size_t b_ = (cnt) * sizeof(T); if (b_) memcpy(hb + at, claimed->rf, b_); s.sf = (T*)(db + at); at += ks_pad8(b_); }
-  KS_AUDIT_SPREAD_SEGS(X)
-#undef X
-#undef KS_AUDIT_SPREAD_SEGS
-  { u32 c2[2] = {claimed->n_new, claimed->n_unscheduled}; memcpy(hb + at, c2, 8); s.out_counts = (u32*)(db + at); }
-  HIPCHK(hipMemcpy(db, hb, bytes + 8, hipMemcpyHostToDevice));
-  const AuditView v = audit_resident(s);
-  return audit_spread_run(&d, 1, &v, &out);
-}
+extern "C" int ks_audit_spread_batch_dev(ks_dev_problem* const* ds, uint32_t n, ks_audit_spread* const* outs) { return audit_batch(ds, n, outs, true, audit_spread_run); }
+extern "C" int ks_audit_spread_dev(ks_dev_problem* d, const ks_result* claimed, ks_audit_spread* out) { return audit_one(d, claimed, out, AUD_READS_ORDER, true, audit_spread_run); }

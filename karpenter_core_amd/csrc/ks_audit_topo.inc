@@ -22,11 +22,6 @@ struct AuditTopoView {
   u32* seqcnt; u32* first;              // scratch: [P] placed pods per commit number | [G * 64] the least commit number that recorded domain d of group g (type 2: of the certain recorders)
 };
 #define KS_AT_NEVER 0xFFFFFFFFu
-// is the placed pod's commit number one the other rules may order by?  (below the number of placed pods, and no other placed pod's)
-__device__ __forceinline__ bool aud_topo_seq_ok(const AuditView& V, const AuditTopoView& T, u32 p, u32 n_placed) {
-  const i32 sq = GC(i32, V.pod_seq)[p];
-  return sq >= 0 && (u32)sq < n_placed && T.seqcnt[sq] == 1u;
-}
 __device__ __forceinline__ bool aud_topo_skipped(const DevProb& P, u32 g) {
   if (!GC(u8, P.grp_active)[g]) return true;
   return GC(i32, P.grp_key)[g] >= 0 && GC(i32, P.grp_count)[(size_t)g * 64] == INT32_MIN;      // (a derived what-if: the group does not exist in it)
@@ -85,8 +80,7 @@ __global__ __launch_bounds__(256) void ks_audit_topo_count(const DevProb* probs,
   if (blockIdx.x == 0) {
     u32 mine = 0;
     for (u32 g = threadIdx.x; g < P.G; g += 256u) if (aud_topo_skipped(P, g)) ++mine;
-    s_skip[threadIdx.x] = mine;
-    for (u32 o = 128u; o > 0; o >>= 1) { __syncthreads(); if (threadIdx.x < o) s_skip[threadIdx.x] += s_skip[threadIdx.x + o]; }
+    aud_block_sum(s_skip, mine);
     if (threadIdx.x == 0) T.meta[2] = s_skip[0];
   }
 }
@@ -97,7 +91,7 @@ __global__ __launch_bounds__(256) void ks_audit_topo_order(const DevProb* probs,
     const i32 nd = aud_where(P, V, p, NS);
     if (nd < 0) continue;
     V.pods[V.off[nd] + atomicAdd(&V.fill[nd], 1u)] = p;
-    if (!aud_topo_seq_ok(V, T, p, n_placed)) continue;
+    if (!aud_seq_ok(V, T.seqcnt, p, n_placed)) continue;
     const u32 c = aud_class(P, V, p), sq = (u32)GC(i32, V.pod_seq)[p];
     const u32 sb = GC(u32, P.cls_sel_off)[c], se = GC(u32, P.cls_sel_off)[c + 1], wb = GC(u32, P.cls_iown_off)[c], we = GC(u32, P.cls_iown_off)[c + 1];
     for (u32 i = 0; i < (se - sb) + (we - wb); ++i) {
@@ -120,7 +114,7 @@ __global__ __launch_bounds__(256) void ks_audit_topo_pods(const DevProb* probs, 
     const i32 nd = aud_where(P, V, p, NS);
     if (nd >= 0) {
       chk = 1u << 30;
-      if (!aud_topo_seq_ok(V, T, p, n_placed)) f = KS_AUDIT_POD_SEQ;
+      if (!aud_seq_ok(V, T.seqcnt, p, n_placed)) f = KS_AUDIT_POD_SEQ;
       else {
         const u32 c = aud_class(P, V, p), sq = (u32)GC(i32, V.pod_seq)[p];
         const u32 ob = GC(u32, P.cls_own_off)[c], oe = GC(u32, P.cls_own_off)[c + 1], ib = GC(u32, P.cls_isel_off)[c], ie = GC(u32, P.cls_isel_off)[c + 1];
@@ -160,14 +154,14 @@ __global__ __launch_bounds__(256) void ks_audit_topo_nodes(const DevProb* probs,
     const bool single = maxlen <= 256u;      // the usual case: the node's whole list is one tile, staged once
     if (single) {
       __syncthreads();
-      for (u32 t = lane; t < 256u; t += 64u) if (t < len) { const u32 q = V.pods[b + t]; s_seq[wv][t] = aud_topo_seq_ok(V, T, q, n_placed) ? (u32)GC(i32, V.pod_seq)[q] : KS_AT_NEVER; s_cls[wv][t] = aud_class(P, V, q); }
+      for (u32 t = lane; t < 256u; t += 64u) if (t < len) { const u32 q = V.pods[b + t]; s_seq[wv][t] = aud_seq_ok(V, T.seqcnt, q, n_placed) ? (u32)GC(i32, V.pod_seq)[q] : KS_AT_NEVER; s_cls[wv][t] = aud_class(P, V, q); }
       __syncthreads();
     }
     for (u32 i0 = 0; i0 < maxlen; i0 += 64u) {
       const bool mine = i0 + lane < len; u32 p = 0, c = 0, sq = 0, ob = 0, no = 0, ib = 0, ne = 0;
       if (mine) {
         p = V.pods[b + i0 + lane];
-        if (aud_topo_seq_ok(V, T, p, n_placed)) {
+        if (aud_seq_ok(V, T.seqcnt, p, n_placed)) {
           c = aud_class(P, V, p); sq = (u32)GC(i32, V.pod_seq)[p];
           ob = GC(u32, P.cls_own_off)[c]; no = GC(u32, P.cls_own_off)[c + 1] - ob; ib = GC(u32, P.cls_isel_off)[c]; ne = no + (GC(u32, P.cls_isel_off)[c + 1] - ib);
         }
@@ -195,7 +189,7 @@ __global__ __launch_bounds__(256) void ks_audit_topo_nodes(const DevProb* probs,
         for (u32 tb = 0; tb < maxlen; tb += 256u) {
           if (!single) {
             __syncthreads();
-            for (u32 t = lane; t < 256u; t += 64u) if (tb + t < len) { const u32 q = V.pods[b + tb + t]; s_seq[wv][t] = aud_topo_seq_ok(V, T, q, n_placed) ? (u32)GC(i32, V.pod_seq)[q] : KS_AT_NEVER; s_cls[wv][t] = aud_class(P, V, q); }
+            for (u32 t = lane; t < 256u; t += 64u) if (tb + t < len) { const u32 q = V.pods[b + tb + t]; s_seq[wv][t] = aud_seq_ok(V, T.seqcnt, q, n_placed) ? (u32)GC(i32, V.pod_seq)[q] : KS_AT_NEVER; s_cls[wv][t] = aud_class(P, V, q); }
             __syncthreads();
           }
           if (act && tb < len) {
@@ -216,20 +210,20 @@ __global__ __launch_bounds__(256) void ks_audit_topo_nodes(const DevProb* probs,
 }
 
 // ---- host half ----
-// A batch is walked in slices: `first` is G x 64 words per problem (G can exceed 1 024 for what-ifs with per-node group lists), and a slice holds at most
-// KS_AUDIT_TOPO_FIRST_WORDS of them (64 MiB), or one problem.
+// A batch is walked in slices (audit_slices): `first` is G x 64 words per problem (G can exceed 1 024 for what-ifs with per-node group lists), and a slice holds at
+// most KS_AUDIT_TOPO_FIRST_WORDS of them (64 MiB), or one problem.
 #define KS_AUDIT_TOPO_FIRST_WORDS ((size_t)16 << 20)
 // ks_audit.inc's audit_run pattern per slice: scratch laid out, one memset, the launches, one read-back of [meta | flags | chk], the totals counted on the host
 static int audit_topo_slice(ks_dev_problem* const* ds, u32 n, const AuditView* results, ks_audit_topology* const* outs, double* kernel_ms, double* readback_ms) {
   BatchStage st; TRY(st.open(ds, n, nullptr, false));
   const size_t o_view = st.add<AuditView>(n), o_tview = st.add<AuditTopoView>(n);
   TRY(st.place());
-  std::vector<size_t> o_fl(n), o_ck(n), o_scr(n); size_t at = 4 * (size_t)n; u32 pmax = 0, nsmax = 0;
-  for (u32 i = 0; i < n; ++i) { o_fl[i] = at; at += ds[i]->h.P; o_ck[i] = at; at += ds[i]->h.P; pmax = std::max(pmax, ds[i]->h.P); nsmax = std::max(nsmax, ds[i]->h.E + ds[i]->h.NMAX); }
-  const size_t n_out = at;
-  for (u32 i = 0; i < n; ++i) { o_scr[i] = at; at += 2 * (size_t)ds[i]->h.P + 3 * ((size_t)ds[i]->h.E + ds[i]->h.NMAX) + 1 + (size_t)ds[i]->h.G * 64; }
-  TmpDev work(ds[0]->device); TRY(work.alloc(at * sizeof(u32)));
-  u32* w = work.as<u32>();
+  AuditWork W(ds[0]->device); std::vector<size_t> o_fl(n), o_ck(n), o_scr(n); u32 pmax = 0, nsmax = 0;
+  W.out(4 * (size_t)n);
+  for (u32 i = 0; i < n; ++i) { o_fl[i] = W.out(ds[i]->h.P); o_ck[i] = W.out(ds[i]->h.P); pmax = std::max(pmax, ds[i]->h.P); nsmax = std::max(nsmax, ds[i]->h.E + ds[i]->h.NMAX); }
+  for (u32 i = 0; i < n; ++i) o_scr[i] = W.scratch(2 * (size_t)ds[i]->h.P + 3 * ((size_t)ds[i]->h.E + ds[i]->h.NMAX) + 1 + (size_t)ds[i]->h.G * 64);
+  TRY(W.alloc());
+  u32* w = W.w();
   for (u32 i = 0; i < n; ++i) {
     AuditView v = results[i]; AuditTopoView t{}; const size_t Pn = ds[i]->h.P, NS = (size_t)ds[i]->h.E + ds[i]->h.NMAX;
     t.meta = w + 4 * (size_t)i; t.flags = w + o_fl[i]; t.chk = w + o_ck[i];
@@ -237,90 +231,34 @@ static int audit_topo_slice(ks_dev_problem* const* ds, u32 n, const AuditView* r
     v.meta = t.meta; v.mark = nullptr; v.pod_flags = nullptr; v.node_flags = nullptr;
     st.h<AuditView>(o_view)[i] = v; st.h<AuditTopoView>(o_tview)[i] = t;
   }
-  const auto t0 = std::chrono::steady_clock::now();
+  AuditClock clock;
   TRY(st.upload(st.bytes));
-  HIPCHK(hipMemsetAsync(w, 0, at * sizeof(u32), st.stream()));
-  const u32 KS_GRID_Y_MAX = 65535u; const AuditView* dv = st.d<const AuditView>(o_view); const AuditTopoView* dt = st.d<const AuditTopoView>(o_tview);
+  TRY(W.zero(st.stream()));
+  const AuditView* dv = st.d<const AuditView>(o_view); const AuditTopoView* dt = st.d<const AuditTopoView>(o_tview);
   const u32 gx_p = std::max(1u, std::min(1024u, (pmax + 255u) / 256u)), gx_n = std::max(1u, std::min(4096u, (nsmax + 3u) / 4u));
-  for (u32 base = 0; base < n; base += KS_GRID_Y_MAX) {
-    const u32 ny = std::min(KS_GRID_Y_MAX, n - base);
+  audit_rows(n, [&](u32 base, u32 ny) {
     hipLaunchKernelGGL(ks_audit_topo_count, dim3(gx_p, ny), dim3(256), 0, st.stream(), st.probs() + base, dv + base, dt + base);
     hipLaunchKernelGGL(ks_audit_scan, dim3(ny), dim3(256), 0, st.stream(), st.probs() + base, dv + base);
     hipLaunchKernelGGL(ks_audit_topo_order, dim3(gx_p, ny), dim3(256), 0, st.stream(), st.probs() + base, dv + base, dt + base);
     hipLaunchKernelGGL(ks_audit_topo_pods, dim3(gx_p, ny), dim3(256), 0, st.stream(), st.probs() + base, dv + base, dt + base);
     hipLaunchKernelGGL(ks_audit_topo_nodes, dim3(gx_n, ny), dim3(256), 0, st.stream(), st.probs() + base, dv + base, dt + base);
-  }
-  HIPCHK(hipStreamSynchronize(st.stream())); HIPCHK(hipGetLastError());
-  const auto t1 = std::chrono::steady_clock::now();
-  std::vector<u32> back(n_out);
-  HIPCHK(hipMemcpy(back.data(), w, n_out * sizeof(u32), hipMemcpyDeviceToHost));
+  });
+  TRY(clock.wait(st.stream()));
+  TRY(W.read_back());
   for (u32 i = 0; i < n; ++i) {
-    ks_audit_topology* o = outs[i]; const u32 Pn = ds[i]->h.P; const u32* meta = back.data() + 4 * (size_t)i;
+    ks_audit_topology* o = outs[i]; const u32 Pn = ds[i]->h.P; const u32* meta = W.back.data() + 4 * (size_t)i;
     o->n_pods = Pn; o->n_new = meta[0]; o->n_placed = meta[3]; o->skipped_groups = meta[2]; o->n_pods_flagged = 0;
     memset(o->pod_bit_count, 0, sizeof o->pod_bit_count); memset(o->checked, 0, sizeof o->checked);
-    const u32* pf = back.data() + o_fl[i]; const u32* ck = back.data() + o_ck[i];
-    for (u32 k = 0; k < Pn; ++k) {
-      if (pf[k]) { ++o->n_pods_flagged; for (u32 x = pf[k]; x; x &= x - 1) ++o->pod_bit_count[__builtin_ctz(x)]; }
-      o->checked[0] += ck[k] >> 30; o->checked[1] += ck[k] & 1023u; o->checked[2] += (ck[k] >> 10) & 1023u; o->checked[3] += (ck[k] >> 20) & 1023u;
-    }
+    const u32* pf = W.back.data() + o_fl[i]; const u32* ck = W.back.data() + o_ck[i];
+    audit_tally(pf, Pn, &o->n_pods_flagged, o->pod_bit_count);
+    for (u32 k = 0; k < Pn; ++k) { o->checked[0] += ck[k] >> 30; o->checked[1] += ck[k] & 1023u; o->checked[2] += (ck[k] >> 10) & 1023u; o->checked[3] += (ck[k] >> 20) & 1023u; }
     if (o->pod_flags && Pn) memcpy(o->pod_flags, pf, (size_t)Pn * sizeof(u32));
   }
-  *kernel_ms += std::chrono::duration<double, std::milli>(t1 - t0).count();
-  *readback_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
+  clock.add(kernel_ms, readback_ms);
   return KS_OK;
 }
 static int audit_topo_run(ks_dev_problem* const* ds, u32 n, const AuditView* results, ks_audit_topology* const* outs) {
-  double kms = 0.0, rms = 0.0;
-  for (u32 base = 0; base < n;) {
-    u32 m = 0; size_t words = 0;
-    while (base + m < n && (m == 0 || words + (size_t)ds[base + m]->h.G * 64 <= KS_AUDIT_TOPO_FIRST_WORDS)) { words += (size_t)ds[base + m]->h.G * 64; ++m; }
-    TRY(audit_topo_slice(ds + base, m, results + base, outs + base, &kms, &rms));
-    base += m;
-  }
-  for (u32 i = 0; i < n; ++i) { outs[i]->kernel_ms = kms; outs[i]->readback_ms = rms; }
-  return KS_OK;
+  return audit_slices(ds, n, results, outs, [](const ks_dev_problem* d) { return (size_t)d->h.G * 64; }, KS_AUDIT_TOPO_FIRST_WORDS, audit_topo_slice);
 }
-extern "C" int ks_audit_topology_batch_dev(ks_dev_problem* const* ds, uint32_t n, ks_audit_topology* const* outs) {
-  if (!n) return KS_OK;
-  if (!ds || !outs) return fail(KS_ERR_INVALID, "null argument");
-  TRY(BatchStage::not_null(ds, n));
-  std::vector<AuditView> res(n);
-  for (u32 i = 0; i < n; ++i) {
-    if (!outs[i]) return fail(KS_ERR_INVALID, "null audit table");
-    if (ds[i]->device != ds[0]->device) return fail(KS_ERR_INVALID, "batch spans devices");
-    if (!ds[i]->solved) return fail(KS_ERR_INVALID, "audit of a problem that holds no result: solve it first (or the last solve failed)");
-    res[i] = audit_resident(ds[i]->hs);
-  }
-  return audit_topo_run(ds, n, res.data(), outs);
-}
-extern "C" int ks_audit_topology_dev(ks_dev_problem* d, const ks_result* claimed, ks_audit_topology* out) {
-  if (!d || !out) return fail(KS_ERR_INVALID, "null argument");
-  if (!claimed) return ks_audit_topology_batch_dev(&d, 1, &out);
-  if (d->view) return fail(KS_ERR_UNSUPPORTED, "a claimed result is audited against a flattened problem, not against a what-if derived on the device");
-  const DevProb& h = d->h; const u64 P = h.P, K = h.K, N = claimed->n_new;
-  if (N > h.NMAX) return fail(KS_ERR_INVALID, "claimed result: more new nodes than max_new_nodes");
-  if (claimed->n_unscheduled > P) return fail(KS_ERR_INVALID, "claimed result: more unscheduled pods than pods");
-  // what this pass reads of a result: where the pods are, at which stage, in which order; the new nodes' templates and final requirements
-#define KS_AUDIT_TOPO_SEGS(X) \
-  X(pod_node, pod_node, i32, P) X(pod_stage, pod_stage, i32, P) X(pod_seq, pod_seq, i32, P) X(n_tmpl, node_tmpl, i32, N) \
-  X(o_present, node_present, u32, N) X(o_complement, node_complement, u32, N) X(o_mask, node_mask, u64, N * K) X(o_gt, node_gt, i32, N * K) X(o_lt, node_lt, i32, N * K)
-#define X(sf, rf, T, cnt) if ((cnt) && !claimed->rf) return fail(KS_ERR_INVALID, "claimed result: null array " #rf);
-  KS_AUDIT_TOPO_SEGS(X)
-#undef X
-  size_t bytes = 0;
-#define X(sf, rf, T, cnt) bytes += ks_pad8((cnt) * sizeof(T));
-  KS_AUDIT_TOPO_SEGS(X)
-#undef X
-  std::vector<u64> blob(bytes / 8 + 1, 0); u8* hb = (u8*)blob.data();
-  HIPCHK(hipSetDevice(d->device));
-  TmpDev up(d->device); TRY(up.alloc(bytes + 8)); u8* db = up.as<u8>();
-  DevState s{}; size_t at = 0;
-#define X(sf, rf, T, cnt) { const size_t b_ = (cnt) * sizeof(T); if (b_) memcpy(hb + at, claimed->rf, b_); s.sf = (T*)(db + at); at += ks_pad8(b_); }
-  KS_AUDIT_TOPO_SEGS(X)
-#undef X
-#undef KS_AUDIT_TOPO_SEGS
-  { u32 c2[2] = {claimed->n_new, claimed->n_unscheduled}; memcpy(hb + at, c2, 8); s.out_counts = (u32*)(db + at); }
-  HIPCHK(hipMemcpy(db, hb, bytes + 8, hipMemcpyHostToDevice));
-  const AuditView v = audit_resident(s);
-  return audit_topo_run(&d, 1, &v, &out);
-}
+extern "C" int ks_audit_topology_batch_dev(ks_dev_problem* const* ds, uint32_t n, ks_audit_topology* const* outs) { return audit_batch(ds, n, outs, true, audit_topo_run); }
+extern "C" int ks_audit_topology_dev(ks_dev_problem* d, const ks_result* claimed, ks_audit_topology* out) { return audit_one(d, claimed, out, AUD_READS_ORDER, true, audit_topo_run); }

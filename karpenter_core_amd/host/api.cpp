@@ -833,327 +833,143 @@ int ksh_placement_rows(void** hv, uint32_t n, const uint64_t* ids, uint64_t* out
   });
 }
 }  // extern "C"
-// The audit's tables (kshost.h ksh_audit_out): libksolve fills tables of the library's own, sized from the device problems; the totals always reach the caller, the
-// flag rows only when they fit
+// The audit's five passes (kshost.h ksh_audit* / ksh_audit*_claimed).  What a pass is to this file: its table in libksolve and in kshost.h, whether it has a node
+// table beside the pod table, its two entry points in libksolve, whether its claimed form comes without commit numbers, and the totals it copies.
 namespace {
-struct AuditTables {
-  std::vector<ks_audit> a; std::vector<ks_audit*> ptr; std::vector<std::vector<uint32_t>> pf, nf;
-  int size(const std::vector<ks_dev_problem*>& ds) {
-    const size_t n = ds.size(); a.assign(n, ks_audit{}); ptr.resize(n); pf.resize(n); nf.resize(n);
-    for (size_t i = 0; i < n; ++i) {
-      uint32_t np = 0, ns = 0; int rc = dev_rc(ks_audit_sizes(ds[i], &np, &ns)); if (rc != KS_OK) return rc;
-      pf[i].assign(np, 0); nf[i].assign(ns, 0); a[i].pod_flags = pf[i].data(); a[i].node_flags = nf[i].data(); ptr[i] = &a[i];
-    }
-    return KS_OK;
-  }
-  void give(size_t i, ksh_audit_out* o, double* ms) const {
-    const ks_audit& r = a[i];
-    o->n_pods = r.n_pods; o->n_nodes = r.n_nodes; o->n_new = r.n_new; o->n_unscheduled = r.n_unscheduled; o->n_pods_flagged = r.n_pods_flagged; o->n_nodes_flagged = r.n_nodes_flagged;
-    o->truncated = 0; o->pad = 0;
+struct AuditFirst {
+  using Dev = ks_audit; using Out = ksh_audit_out; static constexpr bool nodes = true, no_pod_seq = true;
+  static constexpr auto batch_dev = ks_audit_batch_dev; static constexpr auto one_dev = ks_audit_dev;
+  static void totals(const Dev& r, Out* o) {
+    o->n_pods = r.n_pods; o->n_nodes = r.n_nodes; o->n_new = r.n_new; o->n_unscheduled = r.n_unscheduled; o->n_pods_flagged = r.n_pods_flagged; o->n_nodes_flagged = r.n_nodes_flagged; o->pad = 0;
     memcpy(o->pod_bit_count, r.pod_bit_count, sizeof o->pod_bit_count); memcpy(o->node_bit_count, r.node_bit_count, sizeof o->node_bit_count);
-    if (o->cap_pods >= r.n_pods) { if (r.n_pods) memcpy(o->pod_flags, r.pod_flags, (size_t)r.n_pods * sizeof(uint32_t)); } else o->truncated |= KSH_AUDIT_TRUNCATED_PODS;
-    if (o->cap_nodes >= r.n_nodes) { if (r.n_nodes) memcpy(o->node_flags, r.node_flags, (size_t)r.n_nodes * sizeof(uint32_t)); } else o->truncated |= KSH_AUDIT_TRUNCATED_NODES;
-    if (ms) { ms[0] = r.kernel_ms; ms[1] = r.readback_ms; }
   }
 };
-bool audit_out_ok(const ksh_audit_out* o) { return o && (!o->cap_pods || o->pod_flags) && (!o->cap_nodes || o->node_flags); }
-}  // namespace
-extern "C" {
-int ksh_audit(void** hv, uint32_t n, ksh_audit_out* outs, double* ms) {
-  zero(ms, 2);
-  if (n && (!hv || !outs)) return set_err(KS_ERR_INVALID, "null argument");
-  for (uint32_t i = 0; i < n; ++i) if (!audit_out_ok(&outs[i])) return set_err(KS_ERR_INVALID, "null audit table");
-  if (!n) return KS_OK;
-  return guarded([&] {
-    std::vector<ks_dev_problem*> ds;
-    int rc = device_problems(hv, n, true, "audit before solve", ds); if (rc != KS_OK) return rc;
-    AuditTables t; rc = t.size(ds); if (rc != KS_OK) return rc;
-    rc = dev_rc(ks_audit_batch_dev(ds.data(), n, t.ptr.data())); if (rc != KS_OK) return rc;
-    for (uint32_t i = 0; i < n; ++i) t.give(i, &outs[i], ms);
-    return KS_OK;
-  });
-}
-int ksh_audit_claimed(void* hv, const ksh_result_arrays* c, ksh_audit_out* out, double* ms) {
-  zero(ms, 2);
-  Handle* h = (Handle*)hv;
-  if (!h || !c) return set_err(KS_ERR_INVALID, "null argument");
-  if (!audit_out_ok(out)) return set_err(KS_ERR_INVALID, "null audit table");
-  if (h->delta || h->enc->view) return set_err(KS_ERR_UNSUPPORTED, "a claimed result is audited against a flattened problem, not against a what-if derived on the device");
-  return guarded([&] {
-    const ks_problem& p = h->enc->prob; const uint32_t TW = (p.T + 63) / 64;
-    if (c->n_pods != p.P || c->n_existing != p.E || c->types_words != TW || c->n_resources != p.R || c->n_keys != p.K) return set_err(KS_ERR_INVALID, "claimed result: its dimensions are not the handle's");
-    if (c->n_new > p.max_new_nodes) return set_err(KS_ERR_INVALID, "claimed result: more new nodes than max_new_nodes");
-    if (c->n_unscheduled > p.P) return set_err(KS_ERR_INVALID, "claimed result: more unscheduled pods than pods");
-    if ((p.P && (!c->pod_node || !c->pod_stage)) || (c->n_unscheduled && !c->unscheduled)) return set_err(KS_ERR_INVALID, "claimed result: null array");
-    int rc = ensure_resident(h); if (rc != KS_OK) return rc;
-    // ks_result's shape: the unscheduled list in an array of P, and commit numbers -- ksh_result_arrays has none, so placed pods are numbered in pod order
-    std::vector<int32_t> seq((size_t)p.P + 1, -1), un((size_t)p.P + 1, -1);
-    { int32_t k = 0; for (uint32_t i = 0; i < p.P; ++i) if (c->pod_node[i] != -1) seq[i] = k++; }
-    for (uint32_t i = 0; i < c->n_unscheduled; ++i) un[i] = c->unscheduled[i];
-    ks_result r{}; r.pod_node = (int32_t*)c->pod_node; r.pod_stage = (int32_t*)c->pod_stage; r.pod_seq = seq.data(); r.unscheduled = un.data();
-    r.n_new = c->n_new; r.n_unscheduled = c->n_unscheduled;
-    r.node_tmpl = (int32_t*)c->node_tmpl; r.node_types = (uint64_t*)c->node_types; r.node_requests = (int64_t*)c->node_requests; r.node_requests_present = (uint32_t*)c->node_requests_present;
-    r.node_present = (uint32_t*)c->node_present; r.node_complement = (uint32_t*)c->node_complement; r.node_mask = (uint64_t*)c->node_mask; r.node_gt = (int32_t*)c->node_gt; r.node_lt = (int32_t*)c->node_lt;
-    r.node_it_state = (int32_t*)c->node_it_state;
-    std::vector<ks_dev_problem*> ds{h->dev};
-    AuditTables t; rc = t.size(ds); if (rc != KS_OK) return rc;
-    rc = dev_rc(ks_audit_dev(h->dev, &r, t.ptr[0])); if (rc != KS_OK) return rc;
-    t.give(0, out, ms);
-    return KS_OK;
-  });
-}
-}  // extern "C"
-// The second pass's tables (kshost.h ksh_audit_topology_out), the same way
-namespace {
-struct AuditTopoTables {
-  std::vector<ks_audit_topology> a; std::vector<ks_audit_topology*> ptr; std::vector<std::vector<uint32_t>> pf;
-  int size(const std::vector<ks_dev_problem*>& ds) {
-    const size_t n = ds.size(); a.assign(n, ks_audit_topology{}); ptr.resize(n); pf.resize(n);
-    for (size_t i = 0; i < n; ++i) {
-      uint32_t np = 0; int rc = dev_rc(ks_audit_sizes(ds[i], &np, nullptr)); if (rc != KS_OK) return rc;
-      pf[i].assign(np, 0); a[i].pod_flags = pf[i].data(); ptr[i] = &a[i];
-    }
-    return KS_OK;
-  }
-  void give(size_t i, ksh_audit_topology_out* o, double* ms) const {
-    const ks_audit_topology& r = a[i];
-    o->n_pods = r.n_pods; o->n_new = r.n_new; o->n_placed = r.n_placed; o->skipped_groups = r.skipped_groups; o->n_pods_flagged = r.n_pods_flagged; o->truncated = 0;
+struct AuditTopology {
+  using Dev = ks_audit_topology; using Out = ksh_audit_topology_out; static constexpr bool nodes = false, no_pod_seq = false;
+  static constexpr auto batch_dev = ks_audit_topology_batch_dev; static constexpr auto one_dev = ks_audit_topology_dev;
+  static void totals(const Dev& r, Out* o) {
+    o->n_pods = r.n_pods; o->n_new = r.n_new; o->n_placed = r.n_placed; o->skipped_groups = r.skipped_groups; o->n_pods_flagged = r.n_pods_flagged;
     memcpy(o->checked, r.checked, sizeof o->checked); memcpy(o->pod_bit_count, r.pod_bit_count, sizeof o->pod_bit_count);
-    if (o->cap_pods >= r.n_pods) { if (r.n_pods) memcpy(o->pod_flags, r.pod_flags, (size_t)r.n_pods * sizeof(uint32_t)); } else o->truncated |= KSH_AUDIT_TRUNCATED_PODS;
-    if (ms) { ms[0] = r.kernel_ms; ms[1] = r.readback_ms; }
   }
 };
-bool audit_topo_out_ok(const ksh_audit_topology_out* o) { return o && (!o->cap_pods || o->pod_flags); }
-}  // namespace
-extern "C" {
-int ksh_audit_topology(void** hv, uint32_t n, ksh_audit_topology_out* outs, double* ms) {
-  zero(ms, 2);
-  if (n && (!hv || !outs)) return set_err(KS_ERR_INVALID, "null argument");
-  for (uint32_t i = 0; i < n; ++i) if (!audit_topo_out_ok(&outs[i])) return set_err(KS_ERR_INVALID, "null audit table");
-  if (!n) return KS_OK;
-  return guarded([&] {
-    std::vector<ks_dev_problem*> ds;
-    int rc = device_problems(hv, n, true, "audit before solve", ds); if (rc != KS_OK) return rc;
-    AuditTopoTables t; rc = t.size(ds); if (rc != KS_OK) return rc;
-    rc = dev_rc(ks_audit_topology_batch_dev(ds.data(), n, t.ptr.data())); if (rc != KS_OK) return rc;
-    for (uint32_t i = 0; i < n; ++i) t.give(i, &outs[i], ms);
-    return KS_OK;
-  });
-}
-int ksh_audit_topology_claimed(void* hv, const ksh_result_arrays* c, const int32_t* pod_seq, ksh_audit_topology_out* out, double* ms) {
-  zero(ms, 2);
-  Handle* h = (Handle*)hv;
-  if (!h || !c || !pod_seq) return set_err(KS_ERR_INVALID, "null argument");
-  if (!audit_topo_out_ok(out)) return set_err(KS_ERR_INVALID, "null audit table");
-  if (h->delta || h->enc->view) return set_err(KS_ERR_UNSUPPORTED, "a claimed result is audited against a flattened problem, not against a what-if derived on the device");
-  return guarded([&] {
-    const ks_problem& p = h->enc->prob; const uint32_t TW = (p.T + 63) / 64;
-    if (c->n_pods != p.P || c->n_existing != p.E || c->types_words != TW || c->n_resources != p.R || c->n_keys != p.K) return set_err(KS_ERR_INVALID, "claimed result: its dimensions are not the handle's");
-    if (c->n_new > p.max_new_nodes) return set_err(KS_ERR_INVALID, "claimed result: more new nodes than max_new_nodes");
-    if (c->n_unscheduled > p.P) return set_err(KS_ERR_INVALID, "claimed result: more unscheduled pods than pods");
-    if (p.P && (!c->pod_node || !c->pod_stage)) return set_err(KS_ERR_INVALID, "claimed result: null array");
-    int rc = ensure_resident(h); if (rc != KS_OK) return rc;
-    ks_result r{}; r.pod_node = (int32_t*)c->pod_node; r.pod_stage = (int32_t*)c->pod_stage; r.pod_seq = (int32_t*)pod_seq;
-    r.n_new = c->n_new; r.n_unscheduled = c->n_unscheduled;
-    r.node_tmpl = (int32_t*)c->node_tmpl; r.node_present = (uint32_t*)c->node_present; r.node_complement = (uint32_t*)c->node_complement; r.node_mask = (uint64_t*)c->node_mask;
-    r.node_gt = (int32_t*)c->node_gt; r.node_lt = (int32_t*)c->node_lt;
-    std::vector<ks_dev_problem*> ds{h->dev};
-    AuditTopoTables t; rc = t.size(ds); if (rc != KS_OK) return rc;
-    rc = dev_rc(ks_audit_topology_dev(h->dev, &r, t.ptr[0])); if (rc != KS_OK) return rc;
-    t.give(0, out, ms);
-    return KS_OK;
-  });
-}
-}  // extern "C"
-// The third pass's tables (kshost.h ksh_audit_spread_out), the same way
-namespace {
-struct AuditSpreadTables {
-  std::vector<ks_audit_spread> a; std::vector<ks_audit_spread*> ptr; std::vector<std::vector<uint32_t>> pf;
-  int size(const std::vector<ks_dev_problem*>& ds) {
-    const size_t n = ds.size(); a.assign(n, ks_audit_spread{}); ptr.resize(n); pf.resize(n);
-    for (size_t i = 0; i < n; ++i) {
-      uint32_t np = 0; int rc = dev_rc(ks_audit_sizes(ds[i], &np, nullptr)); if (rc != KS_OK) return rc;
-      pf[i].assign(np, 0); a[i].pod_flags = pf[i].data(); ptr[i] = &a[i];
-    }
-    return KS_OK;
-  }
-  void give(size_t i, ksh_audit_spread_out* o, double* ms) const {
-    const ks_audit_spread& r = a[i];
-    o->n_pods = r.n_pods; o->n_new = r.n_new; o->n_placed = r.n_placed; o->skipped_groups = r.skipped_groups; o->n_pods_flagged = r.n_pods_flagged; o->truncated = 0;
+struct AuditSpread {
+  using Dev = ks_audit_spread; using Out = ksh_audit_spread_out; static constexpr bool nodes = false, no_pod_seq = false;
+  static constexpr auto batch_dev = ks_audit_spread_batch_dev; static constexpr auto one_dev = ks_audit_spread_dev;
+  static void totals(const Dev& r, Out* o) {
+    o->n_pods = r.n_pods; o->n_new = r.n_new; o->n_placed = r.n_placed; o->skipped_groups = r.skipped_groups; o->n_pods_flagged = r.n_pods_flagged;
     memcpy(o->checked, r.checked, sizeof o->checked); o->exact_pairs = r.exact_pairs; o->pad = 0;
-    if (o->cap_pods >= r.n_pods) { if (r.n_pods) memcpy(o->pod_flags, r.pod_flags, (size_t)r.n_pods * sizeof(uint32_t)); } else o->truncated |= KSH_AUDIT_TRUNCATED_PODS;
-    if (ms) { ms[0] = r.kernel_ms; ms[1] = r.readback_ms; }
   }
 };
-bool audit_spread_out_ok(const ksh_audit_spread_out* o) { return o && (!o->cap_pods || o->pod_flags); }
-}  // namespace
-extern "C" {
-int ksh_audit_spread(void** hv, uint32_t n, ksh_audit_spread_out* outs, double* ms) {
-  zero(ms, 2);
-  if (n && (!hv || !outs)) return set_err(KS_ERR_INVALID, "null argument");
-  for (uint32_t i = 0; i < n; ++i) if (!audit_spread_out_ok(&outs[i])) return set_err(KS_ERR_INVALID, "null audit table");
-  if (!n) return KS_OK;
-  return guarded([&] {
-    std::vector<ks_dev_problem*> ds;
-    int rc = device_problems(hv, n, true, "audit before solve", ds); if (rc != KS_OK) return rc;
-    AuditSpreadTables t; rc = t.size(ds); if (rc != KS_OK) return rc;
-    rc = dev_rc(ks_audit_spread_batch_dev(ds.data(), n, t.ptr.data())); if (rc != KS_OK) return rc;
-    for (uint32_t i = 0; i < n; ++i) t.give(i, &outs[i], ms);
-    return KS_OK;
-  });
-}
-int ksh_audit_spread_claimed(void* hv, const ksh_result_arrays* c, const int32_t* pod_seq, ksh_audit_spread_out* out, double* ms) {
-  zero(ms, 2);
-  Handle* h = (Handle*)hv;
-  if (!h || !c || !pod_seq) return set_err(KS_ERR_INVALID, "null argument");
-  if (!audit_spread_out_ok(out)) return set_err(KS_ERR_INVALID, "null audit table");
-  if (h->delta || h->enc->view) return set_err(KS_ERR_UNSUPPORTED, "a claimed result is audited against a flattened problem, not against a what-if derived on the device");
-  return guarded([&] {
-    const ks_problem& p = h->enc->prob; const uint32_t TW = (p.T + 63) / 64;
-    if (c->n_pods != p.P || c->n_existing != p.E || c->types_words != TW || c->n_resources != p.R || c->n_keys != p.K) return set_err(KS_ERR_INVALID, "claimed result: its dimensions are not the handle's");
-    if (c->n_new > p.max_new_nodes) return set_err(KS_ERR_INVALID, "claimed result: more new nodes than max_new_nodes");
-    if (c->n_unscheduled > p.P) return set_err(KS_ERR_INVALID, "claimed result: more unscheduled pods than pods");
-    if (p.P && (!c->pod_node || !c->pod_stage)) return set_err(KS_ERR_INVALID, "claimed result: null array");
-    int rc = ensure_resident(h); if (rc != KS_OK) return rc;
-    ks_result r{}; r.pod_node = (int32_t*)c->pod_node; r.pod_stage = (int32_t*)c->pod_stage; r.pod_seq = (int32_t*)pod_seq;
-    r.n_new = c->n_new; r.n_unscheduled = c->n_unscheduled;
-    r.node_tmpl = (int32_t*)c->node_tmpl; r.node_present = (uint32_t*)c->node_present; r.node_complement = (uint32_t*)c->node_complement; r.node_mask = (uint64_t*)c->node_mask;
-    r.node_gt = (int32_t*)c->node_gt; r.node_lt = (int32_t*)c->node_lt;
-    std::vector<ks_dev_problem*> ds{h->dev};
-    AuditSpreadTables t; rc = t.size(ds); if (rc != KS_OK) return rc;
-    rc = dev_rc(ks_audit_spread_dev(h->dev, &r, t.ptr[0])); if (rc != KS_OK) return rc;
-    t.give(0, out, ms);
-    return KS_OK;
-  });
-}
-}  // extern "C"
-// The fourth pass's tables (kshost.h ksh_audit_firstfit_out), the same way
-namespace {
-struct AuditFirstFitTables {
-  std::vector<ks_audit_firstfit> a; std::vector<ks_audit_firstfit*> ptr; std::vector<std::vector<uint32_t>> pf;
-  int size(const std::vector<ks_dev_problem*>& ds) {
-    const size_t n = ds.size(); a.assign(n, ks_audit_firstfit{}); ptr.resize(n); pf.resize(n);
-    for (size_t i = 0; i < n; ++i) {
-      uint32_t np = 0; int rc = dev_rc(ks_audit_sizes(ds[i], &np, nullptr)); if (rc != KS_OK) return rc;
-      pf[i].assign(np, 0); a[i].pod_flags = pf[i].data(); ptr[i] = &a[i];
-    }
-    return KS_OK;
-  }
-  void give(size_t i, ksh_audit_firstfit_out* o, double* ms) const {
-    const ks_audit_firstfit& r = a[i];
-    o->n_pods = r.n_pods; o->n_new = r.n_new; o->n_placed = r.n_placed; o->skipped_pods = r.skipped_pods; o->n_pods_flagged = r.n_pods_flagged; o->truncated = 0;
+struct AuditFirstFit {
+  using Dev = ks_audit_firstfit; using Out = ksh_audit_firstfit_out; static constexpr bool nodes = false, no_pod_seq = false;
+  static constexpr auto batch_dev = ks_audit_firstfit_batch_dev; static constexpr auto one_dev = ks_audit_firstfit_dev;
+  static void totals(const Dev& r, Out* o) {
+    o->n_pods = r.n_pods; o->n_new = r.n_new; o->n_placed = r.n_placed; o->skipped_pods = r.skipped_pods; o->n_pods_flagged = r.n_pods_flagged;
     memcpy(o->checked, r.checked, sizeof o->checked); o->admitting_pairs = r.admitting_pairs;
-    if (o->cap_pods >= r.n_pods) { if (r.n_pods) memcpy(o->pod_flags, r.pod_flags, (size_t)r.n_pods * sizeof(uint32_t)); } else o->truncated |= KSH_AUDIT_TRUNCATED_PODS;
-    if (ms) { ms[0] = r.kernel_ms; ms[1] = r.readback_ms; }
   }
 };
-bool audit_firstfit_out_ok(const ksh_audit_firstfit_out* o) { return o && (!o->cap_pods || o->pod_flags); }
-}  // namespace
-extern "C" {
-int ksh_audit_firstfit(void** hv, uint32_t n, ksh_audit_firstfit_out* outs, double* ms) {
-  zero(ms, 2);
-  if (n && (!hv || !outs)) return set_err(KS_ERR_INVALID, "null argument");
-  for (uint32_t i = 0; i < n; ++i) if (!audit_firstfit_out_ok(&outs[i])) return set_err(KS_ERR_INVALID, "null audit table");
-  if (!n) return KS_OK;
-  return guarded([&] {
-    std::vector<ks_dev_problem*> ds;
-    int rc = device_problems(hv, n, true, "audit before solve", ds); if (rc != KS_OK) return rc;
-    AuditFirstFitTables t; rc = t.size(ds); if (rc != KS_OK) return rc;
-    rc = dev_rc(ks_audit_firstfit_batch_dev(ds.data(), n, t.ptr.data())); if (rc != KS_OK) return rc;
-    for (uint32_t i = 0; i < n; ++i) t.give(i, &outs[i], ms);
-    return KS_OK;
-  });
-}
-int ksh_audit_firstfit_claimed(void* hv, const ksh_result_arrays* c, const int32_t* pod_seq, ksh_audit_firstfit_out* out, double* ms) {
-  zero(ms, 2);
-  Handle* h = (Handle*)hv;
-  if (!h || !c || !pod_seq) return set_err(KS_ERR_INVALID, "null argument");
-  if (!audit_firstfit_out_ok(out)) return set_err(KS_ERR_INVALID, "null audit table");
-  if (h->delta || h->enc->view) return set_err(KS_ERR_UNSUPPORTED, "a claimed result is audited against a flattened problem, not against a what-if derived on the device");
-  return guarded([&] {
-    const ks_problem& p = h->enc->prob; const uint32_t TW = (p.T + 63) / 64;
-    if (c->n_pods != p.P || c->n_existing != p.E || c->types_words != TW || c->n_resources != p.R || c->n_keys != p.K) return set_err(KS_ERR_INVALID, "claimed result: its dimensions are not the handle's");
-    if (c->n_new > p.max_new_nodes) return set_err(KS_ERR_INVALID, "claimed result: more new nodes than max_new_nodes");
-    if (c->n_unscheduled > p.P) return set_err(KS_ERR_INVALID, "claimed result: more unscheduled pods than pods");
-    if (p.P && (!c->pod_node || !c->pod_stage)) return set_err(KS_ERR_INVALID, "claimed result: null array");
-    int rc = ensure_resident(h); if (rc != KS_OK) return rc;
-    ks_result r{}; r.pod_node = (int32_t*)c->pod_node; r.pod_stage = (int32_t*)c->pod_stage; r.pod_seq = (int32_t*)pod_seq;
-    r.n_new = c->n_new; r.n_unscheduled = c->n_unscheduled;
-    r.node_tmpl = (int32_t*)c->node_tmpl; r.node_types = (uint64_t*)c->node_types; r.node_requests = (int64_t*)c->node_requests; r.node_requests_present = (uint32_t*)c->node_requests_present;
-    r.node_present = (uint32_t*)c->node_present; r.node_complement = (uint32_t*)c->node_complement; r.node_mask = (uint64_t*)c->node_mask; r.node_gt = (int32_t*)c->node_gt; r.node_lt = (int32_t*)c->node_lt;
-    r.node_it_state = (int32_t*)c->node_it_state;
-    std::vector<ks_dev_problem*> ds{h->dev};
-    AuditFirstFitTables t; rc = t.size(ds); if (rc != KS_OK) return rc;
-    rc = dev_rc(ks_audit_firstfit_dev(h->dev, &r, t.ptr[0])); if (rc != KS_OK) return rc;
-    t.give(0, out, ms);
-    return KS_OK;
-  });
-}
-}  // extern "C"
-// The fifth pass's tables (kshost.h ksh_audit_limits_out): the fourth pass's way for the pods, the first pass's for the nodes
-namespace {
-struct AuditLimitsTables {
-  std::vector<ks_audit_limits> a; std::vector<ks_audit_limits*> ptr; std::vector<std::vector<uint32_t>> pf, nf;
+struct AuditLimits {
+  using Dev = ks_audit_limits; using Out = ksh_audit_limits_out; static constexpr bool nodes = true, no_pod_seq = false;
+  static constexpr auto batch_dev = ks_audit_limits_batch_dev; static constexpr auto one_dev = ks_audit_limits_dev;
+  static void totals(const Dev& r, Out* o) {
+    o->n_pods = r.n_pods; o->n_nodes = r.n_nodes; o->n_new = r.n_new; o->n_placed = r.n_placed; o->limited_templates = r.limited_templates; o->skipped_nodes = r.skipped_nodes;
+    o->skipped_pods = r.skipped_pods; o->n_pods_flagged = r.n_pods_flagged; o->n_nodes_flagged = r.n_nodes_flagged; o->exact_nodes = r.exact_nodes; o->binding_nodes = r.binding_nodes;
+    memcpy(o->checked, r.checked, sizeof o->checked); memcpy(o->pod_bit_count, r.pod_bit_count, sizeof o->pod_bit_count); memcpy(o->node_bit_count, r.node_bit_count, sizeof o->node_bit_count);
+  }
+};
+// A pass's tables: libksolve fills tables of the library's own, sized from the device problems; the totals always reach the caller, the flag rows only when they fit
+template <class P> struct AuditTables {
+  using Dev = typename P::Dev;
+  std::vector<Dev> a; std::vector<Dev*> ptr; std::vector<std::vector<uint32_t>> pf, nf;
   int size(const std::vector<ks_dev_problem*>& ds) {
-    const size_t n = ds.size(); a.assign(n, ks_audit_limits{}); ptr.resize(n); pf.resize(n); nf.resize(n);
+    const size_t n = ds.size(); a.assign(n, Dev{}); ptr.resize(n); pf.resize(n); nf.resize(n);
     for (size_t i = 0; i < n; ++i) {
-      uint32_t np = 0, ns = 0; int rc = dev_rc(ks_audit_sizes(ds[i], &np, &ns)); if (rc != KS_OK) return rc;
-      pf[i].assign(np, 0); nf[i].assign(ns, 0); a[i].pod_flags = pf[i].data(); a[i].node_flags = nf[i].data(); ptr[i] = &a[i];
+      uint32_t np = 0, ns = 0; int rc = dev_rc(ks_audit_sizes(ds[i], &np, P::nodes ? &ns : nullptr)); if (rc != KS_OK) return rc;
+      pf[i].assign(np, 0); a[i].pod_flags = pf[i].data(); ptr[i] = &a[i];
+      if constexpr (P::nodes) { nf[i].assign(ns, 0); a[i].node_flags = nf[i].data(); }
     }
     return KS_OK;
   }
-  void give(size_t i, ksh_audit_limits_out* o, double* ms) const {
-    const ks_audit_limits& r = a[i];
-    o->n_pods = r.n_pods; o->n_nodes = r.n_nodes; o->n_new = r.n_new; o->n_placed = r.n_placed; o->limited_templates = r.limited_templates; o->skipped_nodes = r.skipped_nodes;
-    o->skipped_pods = r.skipped_pods; o->truncated = 0; o->n_pods_flagged = r.n_pods_flagged; o->n_nodes_flagged = r.n_nodes_flagged; o->exact_nodes = r.exact_nodes; o->binding_nodes = r.binding_nodes;
-    memcpy(o->checked, r.checked, sizeof o->checked); memcpy(o->pod_bit_count, r.pod_bit_count, sizeof o->pod_bit_count); memcpy(o->node_bit_count, r.node_bit_count, sizeof o->node_bit_count);
+  void give(size_t i, typename P::Out* o, double* ms) const {
+    const Dev& r = a[i];
+    P::totals(r, o); o->truncated = 0;
     if (o->cap_pods >= r.n_pods) { if (r.n_pods) memcpy(o->pod_flags, r.pod_flags, (size_t)r.n_pods * sizeof(uint32_t)); } else o->truncated |= KSH_AUDIT_TRUNCATED_PODS;
-    if (o->cap_nodes >= r.n_nodes) { if (r.n_nodes) memcpy(o->node_flags, r.node_flags, (size_t)r.n_nodes * sizeof(uint32_t)); } else o->truncated |= KSH_AUDIT_TRUNCATED_NODES;
+    if constexpr (P::nodes) { if (o->cap_nodes >= r.n_nodes) { if (r.n_nodes) memcpy(o->node_flags, r.node_flags, (size_t)r.n_nodes * sizeof(uint32_t)); } else o->truncated |= KSH_AUDIT_TRUNCATED_NODES; }
     if (ms) { ms[0] = r.kernel_ms; ms[1] = r.readback_ms; }
   }
 };
-bool audit_limits_out_ok(const ksh_audit_limits_out* o) { return o && (!o->cap_pods || o->pod_flags) && (!o->cap_nodes || o->node_flags); }
-}  // namespace
-extern "C" {
-int ksh_audit_limits(void** hv, uint32_t n, ksh_audit_limits_out* outs, double* ms) {
+template <class P> bool audit_out_ok(const typename P::Out* o) {
+  if (!o || (o->cap_pods && !o->pod_flags)) return false;
+  if constexpr (P::nodes) return !o->cap_nodes || o->node_flags;
+  return true;
+}
+// the results the last solves left on the device, for handles of any kind
+template <class P> int audit_resident(void** hv, uint32_t n, typename P::Out* outs, double* ms) {
   zero(ms, 2);
   if (n && (!hv || !outs)) return set_err(KS_ERR_INVALID, "null argument");
-  for (uint32_t i = 0; i < n; ++i) if (!audit_limits_out_ok(&outs[i])) return set_err(KS_ERR_INVALID, "null audit table");
+  for (uint32_t i = 0; i < n; ++i) if (!audit_out_ok<P>(&outs[i])) return set_err(KS_ERR_INVALID, "null audit table");
   if (!n) return KS_OK;
   return guarded([&] {
     std::vector<ks_dev_problem*> ds;
     int rc = device_problems(hv, n, true, "audit before solve", ds); if (rc != KS_OK) return rc;
-    AuditLimitsTables t; rc = t.size(ds); if (rc != KS_OK) return rc;
-    rc = dev_rc(ks_audit_limits_batch_dev(ds.data(), n, t.ptr.data())); if (rc != KS_OK) return rc;
+    AuditTables<P> t; rc = t.size(ds); if (rc != KS_OK) return rc;
+    rc = dev_rc(P::batch_dev(ds.data(), n, t.ptr.data())); if (rc != KS_OK) return rc;
     for (uint32_t i = 0; i < n; ++i) t.give(i, &outs[i], ms);
     return KS_OK;
   });
 }
-int ksh_audit_limits_claimed(void* hv, const ksh_result_arrays* c, const int32_t* pod_seq, ksh_audit_limits_out* out, double* ms) {
+// The refusals about a claimed result's dimensions, then ks_result's shape over the caller's arrays.  lists_unscheduled: the pass reads the unscheduled list
+int claimed_result(const ks_problem& p, const ksh_result_arrays* c, bool lists_unscheduled, const int32_t* pod_seq, ks_result* r) {
+  const uint32_t TW = (p.T + 63) / 64;
+  if (c->n_pods != p.P || c->n_existing != p.E || c->types_words != TW || c->n_resources != p.R || c->n_keys != p.K) return set_err(KS_ERR_INVALID, "claimed result: its dimensions are not the handle's");
+  if (c->n_new > p.max_new_nodes) return set_err(KS_ERR_INVALID, "claimed result: more new nodes than max_new_nodes");
+  if (c->n_unscheduled > p.P) return set_err(KS_ERR_INVALID, "claimed result: more unscheduled pods than pods");
+  if ((p.P && (!c->pod_node || !c->pod_stage)) || (lists_unscheduled && c->n_unscheduled && !c->unscheduled)) return set_err(KS_ERR_INVALID, "claimed result: null array");
+  *r = ks_result{}; r->pod_node = (int32_t*)c->pod_node; r->pod_stage = (int32_t*)c->pod_stage; r->pod_seq = (int32_t*)pod_seq;
+  r->n_new = c->n_new; r->n_unscheduled = c->n_unscheduled;
+  r->node_tmpl = (int32_t*)c->node_tmpl; r->node_types = (uint64_t*)c->node_types; r->node_requests = (int64_t*)c->node_requests; r->node_requests_present = (uint32_t*)c->node_requests_present;
+  r->node_present = (uint32_t*)c->node_present; r->node_complement = (uint32_t*)c->node_complement; r->node_mask = (uint64_t*)c->node_mask; r->node_gt = (int32_t*)c->node_gt; r->node_lt = (int32_t*)c->node_lt;
+  r->node_it_state = (int32_t*)c->node_it_state;
+  return KS_OK;
+}
+// a claimed result for one flattened handle; pod_seq: the commit numbers, for every pass but the first
+template <class P> int audit_claimed(void* hv, const ksh_result_arrays* c, const int32_t* pod_seq, typename P::Out* out, double* ms) {
   zero(ms, 2);
   Handle* h = (Handle*)hv;
-  if (!h || !c || !pod_seq) return set_err(KS_ERR_INVALID, "null argument");
-  if (!audit_limits_out_ok(out)) return set_err(KS_ERR_INVALID, "null audit table");
+  if (!h || !c || (!P::no_pod_seq && !pod_seq)) return set_err(KS_ERR_INVALID, "null argument");
+  if (!audit_out_ok<P>(out)) return set_err(KS_ERR_INVALID, "null audit table");
   if (h->delta || h->enc->view) return set_err(KS_ERR_UNSUPPORTED, "a claimed result is audited against a flattened problem, not against a what-if derived on the device");
   return guarded([&] {
-    const ks_problem& p = h->enc->prob; const uint32_t TW = (p.T + 63) / 64;
-    if (c->n_pods != p.P || c->n_existing != p.E || c->types_words != TW || c->n_resources != p.R || c->n_keys != p.K) return set_err(KS_ERR_INVALID, "claimed result: its dimensions are not the handle's");
-    if (c->n_new > p.max_new_nodes) return set_err(KS_ERR_INVALID, "claimed result: more new nodes than max_new_nodes");
-    if (c->n_unscheduled > p.P) return set_err(KS_ERR_INVALID, "claimed result: more unscheduled pods than pods");
-    if (p.P && (!c->pod_node || !c->pod_stage)) return set_err(KS_ERR_INVALID, "claimed result: null array");
-    int rc = ensure_resident(h); if (rc != KS_OK) return rc;
-    ks_result r{}; r.pod_node = (int32_t*)c->pod_node; r.pod_stage = (int32_t*)c->pod_stage; r.pod_seq = (int32_t*)pod_seq;
-    r.n_new = c->n_new; r.n_unscheduled = c->n_unscheduled;
-    r.node_tmpl = (int32_t*)c->node_tmpl; r.node_types = (uint64_t*)c->node_types; r.node_requests = (int64_t*)c->node_requests; r.node_requests_present = (uint32_t*)c->node_requests_present;
-    r.node_present = (uint32_t*)c->node_present; r.node_complement = (uint32_t*)c->node_complement; r.node_mask = (uint64_t*)c->node_mask; r.node_gt = (int32_t*)c->node_gt; r.node_lt = (int32_t*)c->node_lt;
-    r.node_it_state = (int32_t*)c->node_it_state;
+    const ks_problem& p = h->enc->prob; ks_result r;
+    int rc = claimed_result(p, c, P::no_pod_seq, pod_seq, &r); if (rc != KS_OK) return rc;
+    rc = ensure_resident(h); if (rc != KS_OK) return rc;
+    std::vector<int32_t> seq, un;
+    if (P::no_pod_seq) {
+      // ks_result's shape: the unscheduled list in an array of P, and commit numbers -- ksh_result_arrays has none, so placed pods are numbered in pod order
+      seq.assign((size_t)p.P + 1, -1); un.assign((size_t)p.P + 1, -1);
+      { int32_t k = 0; for (uint32_t i = 0; i < p.P; ++i) if (c->pod_node[i] != -1) seq[i] = k++; }
+      for (uint32_t i = 0; i < c->n_unscheduled; ++i) un[i] = c->unscheduled[i];
+      r.pod_seq = seq.data(); r.unscheduled = un.data();
+    }
     std::vector<ks_dev_problem*> ds{h->dev};
-    AuditLimitsTables t; rc = t.size(ds); if (rc != KS_OK) return rc;
-    rc = dev_rc(ks_audit_limits_dev(h->dev, &r, t.ptr[0])); if (rc != KS_OK) return rc;
+    AuditTables<P> t; rc = t.size(ds); if (rc != KS_OK) return rc;
+    rc = dev_rc(P::one_dev(h->dev, &r, t.ptr[0])); if (rc != KS_OK) return rc;
     t.give(0, out, ms);
     return KS_OK;
   });
 }
+}  // namespace
+extern "C" {
+int ksh_audit(void** hv, uint32_t n, ksh_audit_out* outs, double* ms) { return audit_resident<AuditFirst>(hv, n, outs, ms); }
+int ksh_audit_claimed(void* hv, const ksh_result_arrays* c, ksh_audit_out* out, double* ms) { return audit_claimed<AuditFirst>(hv, c, nullptr, out, ms); }
+int ksh_audit_topology(void** hv, uint32_t n, ksh_audit_topology_out* outs, double* ms) { return audit_resident<AuditTopology>(hv, n, outs, ms); }
+int ksh_audit_topology_claimed(void* hv, const ksh_result_arrays* c, const int32_t* pod_seq, ksh_audit_topology_out* out, double* ms) { return audit_claimed<AuditTopology>(hv, c, pod_seq, out, ms); }
+int ksh_audit_spread(void** hv, uint32_t n, ksh_audit_spread_out* outs, double* ms) { return audit_resident<AuditSpread>(hv, n, outs, ms); }
+int ksh_audit_spread_claimed(void* hv, const ksh_result_arrays* c, const int32_t* pod_seq, ksh_audit_spread_out* out, double* ms) { return audit_claimed<AuditSpread>(hv, c, pod_seq, out, ms); }
+int ksh_audit_firstfit(void** hv, uint32_t n, ksh_audit_firstfit_out* outs, double* ms) { return audit_resident<AuditFirstFit>(hv, n, outs, ms); }
+int ksh_audit_firstfit_claimed(void* hv, const ksh_result_arrays* c, const int32_t* pod_seq, ksh_audit_firstfit_out* out, double* ms) { return audit_claimed<AuditFirstFit>(hv, c, pod_seq, out, ms); }
+int ksh_audit_limits(void** hv, uint32_t n, ksh_audit_limits_out* outs, double* ms) { return audit_resident<AuditLimits>(hv, n, outs, ms); }
+int ksh_audit_limits_claimed(void* hv, const ksh_result_arrays* c, const int32_t* pod_seq, ksh_audit_limits_out* out, double* ms) { return audit_claimed<AuditLimits>(hv, c, pod_seq, out, ms); }
 }  // extern "C"
 // What getNodePrices / filterOutSameType / simulateScheduling's readiness rule read of the snapshot's nodes, once per call
 namespace {

@@ -22,7 +22,7 @@ def _newer(target, sources):
 def build(force: bool = False, opt: str = "-O1") -> str:
     os.makedirs(OUT, exist_ok=True)
     ks_so = os.path.join(OUT, "libksolve.so")
-    src = [os.path.join(PKG, "csrc", f) for f in ("ksolve.hip", "ks_pack_rr.inc", "ks_algebra.h")] + \
+    src = [os.path.join(PKG, "csrc", f) for f in ["ksolve.hip"] + sorted(f for f in os.listdir(os.path.join(PKG, "csrc")) if f != "ksolve.hip")] + \
           [os.path.join(HERE, "hip_sim.h"), os.path.join(HERE, "hip_sim.cpp"), os.path.join(ROOT, "include", "ksolve.h")]
     if force or _newer(ks_so, src):
         subprocess.check_call(["g++", opt, "-g", "-std=c++17", "-fPIC", "-shared", "-w", "-DKS_SIM", "-I" + os.path.join(HERE, "fakeinc"),
