@@ -618,6 +618,22 @@ typedef struct ksh_audit_limits_out {
 int ksh_audit_limits(void** handles, uint32_t n, ksh_audit_limits_out* outs /* [n] */, double* ms /* [2] kernels | read-back, or NULL */);
 /* A claimed result for one flattened handle, exactly as ksh_audit_firstfit_claimed takes it. */
 int ksh_audit_limits_claimed(void* handle, const ksh_result_arrays* claimed, const int32_t* pod_seq /* [n_pods] */, ksh_audit_limits_out* out, double* ms /* [2] or NULL */);
+/* The audit's SIXTH pass, opt-in (ksolve.h ks_audit_hostfit_dev, KS_AUDIT_POD_HFIT_*): the fourth pass's first-fit order for the pods it leaves out because a
+ * topology group constrains them, where every such group is hostname anti-affinity or unfiltered hostname spread -- per-node counts that only grow.  The two passes
+ * partition the pods they examine.  The fourth pass's conventions (cap_pods, KSH_AUDIT_TRUNCATED_PODS, indices as ksh_audit's).  eligible_groups: the groups the rule
+ * covers, skipped_groups: the others.  checked[0]: the placed pods; [1]: the pods examined (skipped_pods: the others); [2]: the (class, node-or-template) pairs
+ * evaluated; [3]: the (pair, group) count tests evaluated; admitting_pairs: the pairs that admitted -- a clean result with none of them proved little. */
+typedef struct ksh_audit_hostfit_out {
+  uint32_t* pod_flags; uint64_t cap_pods;      /* [cap_pods] KS_AUDIT_POD_SEQ | KS_AUDIT_POD_HFIT_* */
+  uint32_t n_pods, n_new, n_placed, skipped_pods;
+  uint32_t n_pods_flagged, truncated /* KSH_AUDIT_TRUNCATED_PODS */;
+  uint32_t eligible_groups, skipped_groups;
+  uint32_t checked[4];
+  uint32_t admitting_pairs, pad;
+} ksh_audit_hostfit_out;
+int ksh_audit_hostfit(void** handles, uint32_t n, ksh_audit_hostfit_out* outs /* [n] */, double* ms /* [2] kernels | read-back, or NULL */);
+/* A claimed result for one flattened handle, exactly as ksh_audit_firstfit_claimed takes it. */
+int ksh_audit_hostfit_claimed(void* handle, const ksh_result_arrays* claimed, const int32_t* pod_seq /* [n_pods] */, ksh_audit_hostfit_out* out, double* ms /* [2] or NULL */);
 
 /* ---- the snapshot kept current by EVENTS ("cached incremental SoA builder fed from state.Cluster") ----
  * Replaces, for the snapshot consolidation simulates over, what the reference does between two passes of the deprovisioner (deprovisioning/controller.go:64,

@@ -694,7 +694,8 @@ int ks_placement_rows_host(ks_dev_problem* const* ds, uint32_t n, const uint64_t
  * spread over narrow keys, hostname spread under a node filter, self-selecting affinity, groups created by a later Topology.Update, provisioner limits (subtractMax
  * depends on the order), first-fit optimality (whether an earlier node would have taken the pod).  (Spread over narrow keys, unfiltered, is now the third pass's:
  * ks_audit_spread_dev; first-fit order, for the pods no topology group constrains, the fourth pass's: ks_audit_firstfit_dev; provisioner limits, bounded from
- * both sides in opening order, the fifth pass's: ks_audit_limits_dev -- KS_AUDIT_NODE_LIMIT_MISSING there is OPTIONS_MISSING for limited templates.)
+ * both sides in opening order, the fifth pass's: ks_audit_limits_dev -- KS_AUDIT_NODE_LIMIT_MISSING there is OPTIONS_MISSING for limited templates; first-fit
+ * order for pods under hostname anti-affinity and unfiltered hostname spread, the sixth pass's: ks_audit_hostfit_dev.)
  * The caller owns the tables: pod_flags [P] and node_flags [E + max_new_nodes] (of which E + n_new are written), either may be NULL (totals only).  Flags are written
  * per index -- no list is appended through an atomic -- so the output is the same every run. */
 typedef struct ks_audit {
@@ -832,7 +833,8 @@ int ks_audit_spread_batch_dev(ks_dev_problem* const* ds, uint32_t n, ks_audit_sp
 /* A pod on a new node it did not open is checked against existing nodes only: the order among new nodes at the time depends on pod counts at the time (sort.Slice,
  * scheduler.go:183).  NOT attempted: topology-constrained pods (the next step would be hostname anti-affinity and unfiltered hostname spread, whose per-node counts
  * also only grow), pods with host ports, limited templates, existing nodes on keys they do not label, the order among new nodes, provisioner limits.  (Limited
- * templates and provisioner limits are the fifth pass's, ks_audit_limits_dev below: KS_AUDIT_POD_LIMIT_TEMPLATE is FIT_TEMPLATE for them.) */
+ * templates and provisioner limits are the fifth pass's, ks_audit_limits_dev below: KS_AUDIT_POD_LIMIT_TEMPLATE is FIT_TEMPLATE for them.  Pods under hostname
+ * anti-affinity and unfiltered hostname spread are the sixth pass's, ks_audit_hostfit_dev below: KS_AUDIT_POD_HFIT_* are FIT_* for them.) */
 typedef struct ks_audit_firstfit {
   uint32_t* pod_flags;            /* [P] KS_AUDIT_POD_SEQ | KS_AUDIT_POD_FIT_*, or NULL (totals only) */
   uint32_t n_pods, n_new;         /* out: P | the new nodes of the result that was audited */
@@ -897,6 +899,49 @@ typedef struct ks_audit_limits {
  * no output through an atomic, no float: the same flags every run.  Refusals as ks_audit_firstfit_dev's. */
 int ks_audit_limits_dev(ks_dev_problem* d, const ks_result* claimed /* or NULL; pod_seq is read */, ks_audit_limits* out);
 int ks_audit_limits_batch_dev(ks_dev_problem* const* ds, uint32_t n, ks_audit_limits* const* outs);
+
+/* ---- the audit's SIXTH pass, opt-in: FIRST-FIT ORDER for pods under HOSTNAME anti-affinity and unfiltered HOSTNAME SPREAD.  Nothing calls it unless asked; the first
+ * five passes are unchanged by it.  For a pod whose constraining groups are all on the hostname Topology.AddRequirements (topology.go:149-167) adds a requirement on
+ * the hostname only, and a node's hostname is one value for its whole life.  nextDomainAntiAffinity (topologygroup.go:235-243) allows the node iff its domain is
+ * registered with count 0; nextDomainTopologySpread (topologygroup.go:155-182) has a hostname minimum of 0 (topologygroup.go:186) and allows it iff
+ * count + self <= maxSkew.  Counts only grow (Record, topologygroup.go:101-105): a node whose FINAL counts admit the pod admitted it at every earlier moment, and the
+ * fourth pass's argument carries over clause by clause.  Pod affinity (type 1) is NOT eligible: growing counts make affinity easier later, so a final state that
+ * admits proves nothing about earlier moments.  One-sided like the passes before it; the bits share their word with KS_AUDIT_POD_SEQ, defined as in the second pass.
+ * ELIGIBLE group g: grp_key[g] is the hostname (with a row of the hostname tables: 0 <= grp_hslot[g] < GH); g is not skipped by the second pass's definition
+ * (grp_active == 0, or absent from a derived what-if); grp_type[g] == 2 (inverse groups included), or grp_type[g] == 0 with an empty node filter by the second pass's
+ * definition.  eligible_groups counts them, skipped_groups every other group of the problem.
+ * EXAMINED pod P: it does not fail SEQ, or it is unscheduled; its final-stage class c reserves no host port; own_list(c) U isel_list(c) is non-empty and every entry
+ * of it is eligible.  A class with both lists empty is the fourth pass's: the two passes partition the pods they examine.  Every other pod is counted in skipped_pods.
+ * fin[g][n] = init[g][n] -- as the second pass defines it: grph_count for an existing node (a derived what-if: its own tables), 0 for a new node -- plus the number of
+ * pods the result puts on n whose final-stage class records g (sel_list or iown_list), the pods that fail SEQ included: a larger count only removes flags.
+ * init < 0 (the hostname is not registered with g): n never admits on g.
+ * ok(c, g, n), g constraining c: type 2: fin[g][n] == 0; type 0: fin[g][n] + self <= grp_max_skew[g], self = bit 31 of the own_list entry.
+ * admits_existing / admits_new / admits_template: the fourth pass's predicate of the same name AND ok(c, g, n) for every g constraining c -- with its examined-pair
+ * condition on labelled keys, its volume exception, its template-presence rule for custom labels, its non-empty-intersection rule and its exclusion of limited
+ * templates unchanged.  A fresh node of a template has every count 0.  open(j), first_e(c), first_open(c), first_m(c): as in the fourth pass, over these predicates. */
+#define KS_AUDIT_POD_HFIT_EXISTING 65536u   /* KS_AUDIT_POD_FIT_EXISTING's verdict: P is on existing node e and first_e(c) < e; or P is on a new node or unscheduled and first_e(c) exists */
+#define KS_AUDIT_POD_HFIT_NEW 131072u       /* KS_AUDIT_POD_FIT_NEW's: P opened its new node (seq(P) == open(node(P))) and first_open(c) < seq(P); or P is unscheduled and first_open(c) exists */
+#define KS_AUDIT_POD_HFIT_TEMPLATE 262144u  /* KS_AUDIT_POD_FIT_TEMPLATE's: P opened a node of template m and first_m(c) < m; or P is unscheduled and first_m(c) exists */
+/* A pod on a new node it did not open is checked against existing nodes only, as in the fourth pass.  NOT attempted: pod affinity, groups on narrow keys, hostname
+ * spread under a node filter, late-created groups, pods with host ports, limited templates, existing nodes on keys they do not label, the order among new nodes. */
+typedef struct ks_audit_hostfit {
+  uint32_t* pod_flags;            /* [P] KS_AUDIT_POD_SEQ | KS_AUDIT_POD_HFIT_*, or NULL (totals only) */
+  uint32_t n_pods, n_new;         /* out: P | the new nodes of the result that was audited */
+  uint32_t n_placed;              /* out: pods on a node of the result */
+  uint32_t eligible_groups, skipped_groups;   /* out: the eligible groups | the other groups of the problem */
+  uint32_t skipped_pods;          /* out: the pods that are not examined */
+  uint32_t n_pods_flagged;
+  uint32_t checked[4];            /* out: [0] the placed pods (SEQ); [1] the pods examined; [2] the (class, node-or-template) pairs evaluated, over the distinct classes of the examined pods; [3] the (pair, group) count tests evaluated: every pair evaluates the test of every group that constrains its class */
+  uint32_t admitting_pairs;       /* out: how many of those pairs admitted.  A clean result with admitting_pairs == 0 proved little */
+  double kernel_ms, readback_ms;  /* out: as ks_audit's */
+} ks_audit_hostfit;
+/* claimed == NULL: the resident result, where it lies (the form for derived what-ifs).  claimed given (flattened problems only, KS_ERR_UNSUPPORTED for a derived
+ * view): the fourth pass's arrays are uploaded and read; every index a result supplies is range-checked before it addresses memory.  Eight launches; fin is a dense
+ * int32 table of (E + max_new_nodes) x GH words per problem, sized on the host, and the batch form walks its problems in slices of at most 64 MiB of it (or one
+ * problem).  The tables behind the verdict are built by integer min, add and or; flags are written per index, no output through an atomic, no float: the same flags
+ * every run.  Refusals as ks_audit_firstfit_dev's. */
+int ks_audit_hostfit_dev(ks_dev_problem* d, const ks_result* claimed /* or NULL; pod_seq is read */, ks_audit_hostfit* out);
+int ks_audit_hostfit_batch_dev(ks_dev_problem* const* ds, uint32_t n, ks_audit_hostfit* const* outs);
 
 /* ---- consolidation CANDIDATES, selected and ordered on the device (deprovisioning/helpers.go:124-165,275-287 GetPodEvictionCost / disruptionCost /
  * calculateLifetimeRemaining, pdblimits.go:57-70 CanEvictPods, helpers.go:339-366 canBeTerminated / PodsPreventEviction, consolidation.go:83-104 the sort).

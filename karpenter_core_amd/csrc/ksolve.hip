@@ -4392,13 +4392,14 @@ extern "C" int ks_placement_rows_host(ks_dev_problem* const* ds, uint32_t n, con
   return KS_OK;
 }
 
-// The order matters: ks_audit.inc's host half is the host path of all five passes (the claimed upload, the resident prelude, the pooled work block, the launch rows,
+// The order matters: ks_audit.inc's host half is the host path of all six passes (the claimed upload, the resident prelude, the pooled work block, the launch rows,
 // the tallies, the slice walker -- DESIGN.md 7.26), and the device helpers the later files share stand beside its own; each later file adds a view, kernels and one run function.
 #include "ks_audit.inc"      // the audit of a result against its problem (ks_audit_dev / ks_audit_batch_dev), and what every pass's host half calls
 #include "ks_audit_topo.inc" // its second, opt-in pass: pod (anti-)affinity and hostname spread in commit order (ks_audit_topology_dev / ks_audit_topology_batch_dev)
 #include "ks_audit_spread.inc" // its third, opt-in pass: topology spread over narrow keys in commit order (ks_audit_spread_dev / ks_audit_spread_batch_dev)
 #include "ks_audit_firstfit.inc" // its fourth, opt-in pass: first-fit order from the final state and the commit numbers (ks_audit_firstfit_dev / ks_audit_firstfit_batch_dev)
 #include "ks_audit_limits.inc"   // its fifth, opt-in pass: provisioner limits in opening order (ks_audit_limits_dev / ks_audit_limits_batch_dev)
+#include "ks_audit_hostfit.inc"  // its sixth, opt-in pass: first-fit order for hostname anti-affinity and hostname spread pods (ks_audit_hostfit_dev / ks_audit_hostfit_batch_dev)
 
 // ------------------------------------------------------------------------------------------------
 // Consolidation candidates (ksolve.h ks_consolidation_candidates_host): which nodes sortAndFilterCandidates keeps, and in what order.

@@ -833,7 +833,7 @@ int ksh_placement_rows(void** hv, uint32_t n, const uint64_t* ids, uint64_t* out
   });
 }
 }  // extern "C"
-// The audit's five passes (kshost.h ksh_audit* / ksh_audit*_claimed).  What a pass is to this file: its table in libksolve and in kshost.h, whether it has a node
+// The audit's six passes (kshost.h ksh_audit* / ksh_audit*_claimed).  What a pass is to this file: its table in libksolve and in kshost.h, whether it has a node
 // table beside the pod table, its two entry points in libksolve, whether its claimed form comes without commit numbers, and the totals it copies.
 namespace {
 struct AuditFirst {
@@ -875,6 +875,14 @@ struct AuditLimits {
     o->n_pods = r.n_pods; o->n_nodes = r.n_nodes; o->n_new = r.n_new; o->n_placed = r.n_placed; o->limited_templates = r.limited_templates; o->skipped_nodes = r.skipped_nodes;
     o->skipped_pods = r.skipped_pods; o->n_pods_flagged = r.n_pods_flagged; o->n_nodes_flagged = r.n_nodes_flagged; o->exact_nodes = r.exact_nodes; o->binding_nodes = r.binding_nodes;
     memcpy(o->checked, r.checked, sizeof o->checked); memcpy(o->pod_bit_count, r.pod_bit_count, sizeof o->pod_bit_count); memcpy(o->node_bit_count, r.node_bit_count, sizeof o->node_bit_count);
+  }
+};
+struct AuditHostFit {
+  using Dev = ks_audit_hostfit; using Out = ksh_audit_hostfit_out; static constexpr bool nodes = false, no_pod_seq = false;
+  static constexpr auto batch_dev = ks_audit_hostfit_batch_dev; static constexpr auto one_dev = ks_audit_hostfit_dev;
+  static void totals(const Dev& r, Out* o) {
+    o->n_pods = r.n_pods; o->n_new = r.n_new; o->n_placed = r.n_placed; o->skipped_pods = r.skipped_pods; o->n_pods_flagged = r.n_pods_flagged;
+    o->eligible_groups = r.eligible_groups; o->skipped_groups = r.skipped_groups; memcpy(o->checked, r.checked, sizeof o->checked); o->admitting_pairs = r.admitting_pairs; o->pad = 0;
   }
 };
 // A pass's tables: libksolve fills tables of the library's own, sized from the device problems; the totals always reach the caller, the flag rows only when they fit
@@ -970,6 +978,8 @@ int ksh_audit_firstfit(void** hv, uint32_t n, ksh_audit_firstfit_out* outs, doub
 int ksh_audit_firstfit_claimed(void* hv, const ksh_result_arrays* c, const int32_t* pod_seq, ksh_audit_firstfit_out* out, double* ms) { return audit_claimed<AuditFirstFit>(hv, c, pod_seq, out, ms); }
 int ksh_audit_limits(void** hv, uint32_t n, ksh_audit_limits_out* outs, double* ms) { return audit_resident<AuditLimits>(hv, n, outs, ms); }
 int ksh_audit_limits_claimed(void* hv, const ksh_result_arrays* c, const int32_t* pod_seq, ksh_audit_limits_out* out, double* ms) { return audit_claimed<AuditLimits>(hv, c, pod_seq, out, ms); }
+int ksh_audit_hostfit(void** hv, uint32_t n, ksh_audit_hostfit_out* outs, double* ms) { return audit_resident<AuditHostFit>(hv, n, outs, ms); }
+int ksh_audit_hostfit_claimed(void* hv, const ksh_result_arrays* c, const int32_t* pod_seq, ksh_audit_hostfit_out* out, double* ms) { return audit_claimed<AuditHostFit>(hv, c, pod_seq, out, ms); }
 }  // extern "C"
 // What getNodePrices / filterOutSameType / simulateScheduling's readiness rule read of the snapshot's nodes, once per call
 namespace {

@@ -51,6 +51,10 @@ KS_AUDIT_FIRSTFIT_CHECKED = ("SEQ", "PODS", "PAIRS")
 KS_AUDIT_LIMITS_POD_BITS = {"SEQ": 128, "LIMIT_TEMPLATE": 32768}
 KS_AUDIT_LIMITS_NODE_BITS = {"LIMIT_EXTRA": 256, "LIMIT_MISSING": 512}
 KS_AUDIT_LIMITS_CHECKED = ("SEQ", "NODES", "PODS", "PAIRS")
+# the sixth pass's (FlatProblem.audit_hostfit() / audit_hostfit_batch()): SEQ as above, and first-fit order for pods under hostname anti-affinity / hostname spread;
+# `checked`: placed pods, examined pods, (class, node) pairs, (pair, group) count tests
+KS_AUDIT_HOSTFIT_BITS = {"SEQ": 128, "HFIT_EXISTING": 65536, "HFIT_NEW": 131072, "HFIT_TEMPLATE": 262144}
+KS_AUDIT_HOSTFIT_CHECKED = ("SEQ", "PODS", "PAIRS", "TESTS")
 
 
 class KSolveError(RuntimeError):
@@ -394,6 +398,16 @@ class FlatProblem:
                 raise ValueError("audit_limits: pod_seq goes with a claimed result")
             return audit_limits_batch([self])[0]
         return _audit_limits_call([self], claimed, pod_seq)[0]
+
+    def audit_hostfit(self, claimed: Optional[dict] = None, pod_seq=None) -> dict:
+        """The audit's sixth, opt-in pass (include/ksolve.h KS_AUDIT_POD_HFIT_*, kshost.h ksh_audit_hostfit / ksh_audit_hostfit_claimed): the fourth pass's first-fit order
+        for the pods whose constraining groups are all hostname anti-affinity or unfiltered hostname spread.  Arguments as `audit_topology`'s.  Returns
+        `audit_firstfit`'s dict ("checked": SEQ, PODS, PAIRS and TESTS, the (pair, group) count tests evaluated) plus "eligible_groups" and "skipped_groups"."""
+        if claimed is None:
+            if pod_seq is not None:
+                raise ValueError("audit_hostfit: pod_seq goes with a claimed result")
+            return audit_hostfit_batch([self])[0]
+        return _audit_hostfit_call([self], claimed, pod_seq)[0]
 
     def result(self) -> SolveResult:
         """Decode the result the handle holds (after `solve(decode=False)` or `solve_from_pods`)."""
@@ -1026,6 +1040,29 @@ def audit_limits_batch(flats: Sequence["FlatProblem"]) -> List[dict]:
     """The audit's fifth pass over the results the last solve left on the device, for a whole batch (include/kshost.h ksh_audit_limits): handles of any kind, derived
     what-ifs included.  One dict per problem, as `FlatProblem.audit_limits` returns it."""
     return _audit_limits_call(flats)
+
+
+class _AuditHostFitOut(ctypes.Structure):      # include/kshost.h ksh_audit_hostfit_out
+    _fields_ = [("pod_flags", ctypes.c_void_p), ("cap_pods", ctypes.c_uint64)] + \
+               [(n, ctypes.c_uint32) for n in ("n_pods", "n_new", "n_placed", "skipped_pods", "n_pods_flagged", "truncated", "eligible_groups", "skipped_groups")] + \
+               [("checked", ctypes.c_uint32 * 4), ("admitting_pairs", ctypes.c_uint32), ("pad", ctypes.c_uint32)]
+
+
+def _audit_hostfit_call(flats: Sequence["FlatProblem"], claimed: Optional[dict] = None, pod_seq=None) -> List[dict]:
+    import numpy as np
+    if not len(flats):
+        return []
+    more = (("node_types", np.uint64), ("node_requests", np.int64), ("node_requests_present", np.uint32), ("node_it_state", np.int32))
+    outs, flags, ms = _audit_seq_pass("hostfit", _AuditHostFitOut, flats, claimed, pod_seq, more)
+    return [{"pod_flags": flags[i], "n_pods_flagged": int(o.n_pods_flagged), "pod_bit_count": {k: int(((flags[i] & v) != 0).sum()) for k, v in KS_AUDIT_HOSTFIT_BITS.items()},
+             "checked": {k: int(o.checked[j]) for j, k in enumerate(KS_AUDIT_HOSTFIT_CHECKED)}, "admitting_pairs": int(o.admitting_pairs), "skipped_pods": int(o.skipped_pods),
+             "eligible_groups": int(o.eligible_groups), "skipped_groups": int(o.skipped_groups), "n_new": int(o.n_new), "n_placed": int(o.n_placed), "ms": ms} for i, o in enumerate(outs)]
+
+
+def audit_hostfit_batch(flats: Sequence["FlatProblem"]) -> List[dict]:
+    """The audit's sixth pass over the results the last solve left on the device, for a whole batch (include/kshost.h ksh_audit_hostfit): handles of any kind, derived
+    what-ifs included.  One dict per problem, as `FlatProblem.audit_hostfit` returns it."""
+    return _audit_hostfit_call(flats)
 
 
 def deal_lpt(weights: Sequence[int], nshards: int) -> List[int]:
