@@ -341,9 +341,7 @@ class FlatProblem:
         last solve left on the device.  With `claimed`: a result in `result_arrays()`' form -- from anywhere -- is uploaded and audited instead (flattened problems
         only).  Returns {"pod_flags": uint32 [P], "node_flags": uint32 [E + n_new], "n_pods_flagged", "n_nodes_flagged", "pod_bit_count", "node_bit_count" (by bit
         name), "n_new", "n_unscheduled", "ms": (kernels, read-back)}; a clean result has no flag set."""
-        if claimed is None:
-            return audit_batch([self])[0]
-        return _audit_call([self], claimed)[0]
+        return _audit("audit", [self], claimed)[0]
 
     def pod_seq(self):
         """The commit numbers of the result on the device, int32 [P] by pod index (-1: unscheduled), read through `ksh_placement_rows` (KS_PLC_STAGE_SEQ).  For a
@@ -360,32 +358,20 @@ class FlatProblem:
         spread, decided from the final state and the commit numbers.  Without `claimed`: the result on the device.  With `claimed` (a result in `result_arrays()`' form)
         and `pod_seq` (int32 [P], as `pod_seq()` returns it): those are uploaded and audited instead (flattened problems only).  Returns {"pod_flags": uint32 [P],
         "n_pods_flagged", "pod_bit_count" and "checked" (by rule name), "skipped_groups", "n_new", "n_placed", "ms"}."""
-        if claimed is None:
-            if pod_seq is not None:
-                raise ValueError("audit_topology: pod_seq goes with a claimed result")
-            return audit_topology_batch([self])[0]
-        return _audit_topology_call([self], claimed, pod_seq)[0]
+        return _audit("topology", [self], claimed, pod_seq)[0]
 
     def audit_spread(self, claimed: Optional[dict] = None, pod_seq=None) -> dict:
         """The audit's third, opt-in pass (include/ksolve.h KS_AUDIT_POD_SPREAD, kshost.h ksh_audit_spread / ksh_audit_spread_claimed): topology spread over narrow keys --
         the zone --, decided from the final state and the commit numbers.  Arguments as `audit_topology`'s.  Returns {"pod_flags": uint32 [P], "n_pods_flagged",
         "pod_bit_count" and "checked" (by rule name: SEQ the placed pods, SPREAD the (pod, group) pairs examined), "exact_pairs", "skipped_groups", "n_new", "n_placed", "ms"}."""
-        if claimed is None:
-            if pod_seq is not None:
-                raise ValueError("audit_spread: pod_seq goes with a claimed result")
-            return audit_spread_batch([self])[0]
-        return _audit_spread_call([self], claimed, pod_seq)[0]
+        return _audit("spread", [self], claimed, pod_seq)[0]
 
     def audit_firstfit(self, claimed: Optional[dict] = None, pod_seq=None) -> dict:
         """The audit's fourth, opt-in pass (include/ksolve.h KS_AUDIT_POD_FIT_*, kshost.h ksh_audit_firstfit / ksh_audit_firstfit_claimed): first-fit order -- no pod ended
         later than an existing node, a new node or a template whose final state would still take it --, decided from the final state and the commit numbers.  Arguments
         as `audit_topology`'s.  Returns {"pod_flags": uint32 [P], "n_pods_flagged", "pod_bit_count", "checked" (SEQ the placed pods, PODS the pods examined, PAIRS the
         (class, node-or-template) pairs evaluated), "admitting_pairs", "skipped_pods", "n_new", "n_placed", "ms"}."""
-        if claimed is None:
-            if pod_seq is not None:
-                raise ValueError("audit_firstfit: pod_seq goes with a claimed result")
-            return audit_firstfit_batch([self])[0]
-        return _audit_firstfit_call([self], claimed, pod_seq)[0]
+        return _audit("firstfit", [self], claimed, pod_seq)[0]
 
     def audit_limits(self, claimed: Optional[dict] = None, pod_seq=None) -> dict:
         """The audit's fifth, opt-in pass (include/ksolve.h KS_AUDIT_NODE_LIMIT_*, KS_AUDIT_POD_LIMIT_TEMPLATE, kshost.h ksh_audit_limits / ksh_audit_limits_claimed):
@@ -393,21 +379,13 @@ class FlatProblem:
         passed over a limited provisioner that still had room --, decided from the final state and the commit numbers.  Arguments as `audit_topology`'s.  Returns
         `audit_firstfit`'s dict ("checked": SEQ the placed pods, NODES the new nodes of limited templates, PODS the pods examined, PAIRS the (class, template) pairs)
         plus "node_flags" (uint32 [E + n_new]), "n_nodes_flagged", "node_bit_count", "limited_templates", "exact_nodes", "binding_nodes" and "skipped_nodes"."""
-        if claimed is None:
-            if pod_seq is not None:
-                raise ValueError("audit_limits: pod_seq goes with a claimed result")
-            return audit_limits_batch([self])[0]
-        return _audit_limits_call([self], claimed, pod_seq)[0]
+        return _audit("limits", [self], claimed, pod_seq)[0]
 
     def audit_hostfit(self, claimed: Optional[dict] = None, pod_seq=None) -> dict:
         """The audit's sixth, opt-in pass (include/ksolve.h KS_AUDIT_POD_HFIT_*, kshost.h ksh_audit_hostfit / ksh_audit_hostfit_claimed): the fourth pass's first-fit order
         for the pods whose constraining groups are all hostname anti-affinity or unfiltered hostname spread.  Arguments as `audit_topology`'s.  Returns
         `audit_firstfit`'s dict ("checked": SEQ, PODS, PAIRS and TESTS, the (pair, group) count tests evaluated) plus "eligible_groups" and "skipped_groups"."""
-        if claimed is None:
-            if pod_seq is not None:
-                raise ValueError("audit_hostfit: pod_seq goes with a claimed result")
-            return audit_hostfit_batch([self])[0]
-        return _audit_hostfit_call([self], claimed, pod_seq)[0]
+        return _audit("hostfit", [self], claimed, pod_seq)[0]
 
     def result(self) -> SolveResult:
         """Decode the result the handle holds (after `solve(decode=False)` or `solve_from_pods`)."""
@@ -822,89 +800,65 @@ def solve_batch(flats: Sequence[FlatProblem], decode: bool = True):
     return res, float(kms.value), float(wms.value)
 
 
-class _AuditOut(ctypes.Structure):      # include/kshost.h ksh_audit_out
-    _fields_ = [("pod_flags", ctypes.c_void_p), ("cap_pods", ctypes.c_uint64), ("node_flags", ctypes.c_void_p), ("cap_nodes", ctypes.c_uint64)] + \
-               [(n, ctypes.c_uint32) for n in ("n_pods", "n_nodes", "n_new", "n_unscheduled", "n_pods_flagged", "n_nodes_flagged", "truncated", "pad")] + \
-               [("pod_bit_count", ctypes.c_uint32 * 32), ("node_bit_count", ctypes.c_uint32 * 32)]
-
-
 class _ResultArrays(ctypes.Structure):      # include/kshost.h ksh_result_arrays
     _fields_ = [(n, ctypes.c_uint32) for n in ("n_pods", "n_existing", "n_new", "n_unscheduled", "types_words", "n_resources", "n_keys", "pad")] + \
                [(n, ctypes.c_void_p) for n in ("pod_node", "pod_stage", "pod_reason", "unscheduled", "node_pods_off", "node_pods", "node_tmpl", "node_types", "node_requests",
                                                "node_requests_present", "node_present", "node_complement", "node_mask", "node_gt", "node_lt", "node_it_state")]
 
 
-def _audit_call(flats: Sequence["FlatProblem"], claimed: Optional[dict] = None) -> List[dict]:
+# The claimed arrays every pass uploads, and the two sets some read beyond them (name, dtype: the fields of _ResultArrays).
+_CLAIMED_COMMON = (("pod_node", "int32"), ("pod_stage", "int32"), ("node_tmpl", "int32"), ("node_present", "uint32"), ("node_complement", "uint32"), ("node_mask", "uint64"),
+                   ("node_gt", "int32"), ("node_lt", "int32"))
+_CLAIMED_FIT = (("node_types", "uint64"), ("node_requests", "int64"), ("node_requests_present", "uint32"), ("node_it_state", "int32"))
+_CLAIMED_FIRST = (("unscheduled", "int32"),) + _CLAIMED_FIT
+
+# The audit's passes: what differs between them and nothing else.  stem: the C name (kshost.h <stem> / <stem>_claimed);  seq: the claimed form takes the commit numbers;
+# fields: the uint32 members of <stem>_out behind its tables ("name*N": an array of N) -- a bit count the struct holds is read from it, one it lacks is counted from the flags;
+# claimed: what a claimed result uploads beyond _CLAIMED_COMMON;  node_bits: the pass has a table per node as well;  checked: the names of `checked`' entries;
+# scalars: the members returned as they are, in the dict's order.
+_AUDIT_PASSES = {
+    "audit": dict(stem="ksh_audit", seq=False, out="_AuditOut", claimed=_CLAIMED_FIRST, pod_bits=KS_AUDIT_POD_BITS, node_bits=KS_AUDIT_NODE_BITS, checked=None,
+                  fields=("n_pods", "n_nodes", "n_new", "n_unscheduled", "n_pods_flagged", "n_nodes_flagged", "truncated", "pad", "pod_bit_count*32", "node_bit_count*32"),
+                  scalars=("n_new", "n_unscheduled")),
+    "topology": dict(stem="ksh_audit_topology", seq=True, out="_AuditTopologyOut", claimed=(), pod_bits=KS_AUDIT_TOPOLOGY_BITS, node_bits=None, checked=KS_AUDIT_TOPOLOGY_RULES,
+                     fields=("n_pods", "n_new", "n_placed", "skipped_groups", "n_pods_flagged", "truncated", "checked*4", "pod_bit_count*32"),
+                     scalars=("skipped_groups", "n_new", "n_placed")),
+    "spread": dict(stem="ksh_audit_spread", seq=True, out="_AuditSpreadOut", claimed=(), pod_bits=KS_AUDIT_SPREAD_BITS, node_bits=None, checked=KS_AUDIT_SPREAD_RULES,
+                   fields=("n_pods", "n_new", "n_placed", "skipped_groups", "n_pods_flagged", "truncated", "checked*2", "exact_pairs", "pad"),
+                   scalars=("exact_pairs", "skipped_groups", "n_new", "n_placed")),
+    "firstfit": dict(stem="ksh_audit_firstfit", seq=True, out="_AuditFirstFitOut", claimed=_CLAIMED_FIT, pod_bits=KS_AUDIT_FIRSTFIT_BITS, node_bits=None, checked=KS_AUDIT_FIRSTFIT_CHECKED,
+                     fields=("n_pods", "n_new", "n_placed", "skipped_pods", "n_pods_flagged", "truncated", "checked*3", "admitting_pairs"),
+                     scalars=("admitting_pairs", "skipped_pods", "n_new", "n_placed")),
+    "limits": dict(stem="ksh_audit_limits", seq=True, out="_AuditLimitsOut", claimed=_CLAIMED_FIT, pod_bits=KS_AUDIT_LIMITS_POD_BITS, node_bits=KS_AUDIT_LIMITS_NODE_BITS,
+                   checked=KS_AUDIT_LIMITS_CHECKED,
+                   fields=("n_pods", "n_nodes", "n_new", "n_placed", "limited_templates", "skipped_nodes", "skipped_pods", "truncated", "n_pods_flagged", "n_nodes_flagged",
+                           "exact_nodes", "binding_nodes", "checked*4", "pod_bit_count*32", "node_bit_count*32"),
+                   scalars=("limited_templates", "exact_nodes", "binding_nodes", "skipped_nodes", "skipped_pods", "n_new", "n_placed")),
+    "hostfit": dict(stem="ksh_audit_hostfit", seq=True, out="_AuditHostFitOut", claimed=_CLAIMED_FIT, pod_bits=KS_AUDIT_HOSTFIT_BITS, node_bits=None, checked=KS_AUDIT_HOSTFIT_CHECKED,
+                    fields=("n_pods", "n_new", "n_placed", "skipped_pods", "n_pods_flagged", "truncated", "eligible_groups", "skipped_groups", "checked*4", "admitting_pairs", "pad"),
+                    scalars=("admitting_pairs", "skipped_pods", "eligible_groups", "skipped_groups", "n_new", "n_placed")),
+}
+
+for _p in _AUDIT_PASSES.values():      # include/kshost.h <stem>_out: the tables and their capacities, then `fields`
+    _tables = [("pod_flags", ctypes.c_void_p), ("cap_pods", ctypes.c_uint64)] + ([("node_flags", ctypes.c_void_p), ("cap_nodes", ctypes.c_uint64)] if _p["node_bits"] else [])
+    _p["Out"] = type(_p["out"], (ctypes.Structure,), {"_fields_": _tables + [(n, ctypes.c_uint32 * int(k) if k else ctypes.c_uint32) for n, _, k in (f.partition("*") for f in _p["fields"])]})
+_AuditOut, _AuditTopologyOut, _AuditSpreadOut, _AuditFirstFitOut, _AuditLimitsOut, _AuditHostFitOut = (_AUDIT_PASSES[w]["Out"] for w in ("audit", "topology", "spread", "firstfit", "limits", "hostfit"))
+
+
+def _audit(what: str, flats: Sequence["FlatProblem"], claimed: Optional[dict] = None, pod_seq=None) -> List[dict]:
+    """One pass of the audit, as _AUDIT_PASSES[what] states it: the call over the resident results of `flats`, or over `claimed` (with `pod_seq`, where the pass takes
+    it) for flats[0]; once more with larger tables if one was too short.  One dict per problem."""
     import numpy as np
-    kh = libs()[1]
+    if claimed is None and pod_seq is not None:
+        raise ValueError("audit_%s: pod_seq goes with a claimed result" % what)
     n = len(flats)
     if not n:
         return []
-    kh.ksh_audit.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32, ctypes.POINTER(_AuditOut), ctypes.POINTER(ctypes.c_double)]
-    kh.ksh_audit_claimed.argtypes = [ctypes.c_void_p, ctypes.POINTER(_ResultArrays), ctypes.POINTER(_AuditOut), ctypes.POINTER(ctypes.c_double)]
-    hs = (ctypes.c_void_p * n)(*[f._h for f in flats])
-    outs = (_AuditOut * n)()
-    ms = (ctypes.c_double * 2)()
-    keep = []
-    ra = None
-    if claimed is not None:
-        d = flats[0].dims
-        ra = _ResultArrays()
-        N = int(claimed["n_new"])
-        ra.n_pods, ra.n_existing, ra.n_new, ra.n_unscheduled = d["P"], d["E"], N, len(claimed["unscheduled"])
-        ra.types_words, ra.n_resources, ra.n_keys = (d["T"] + 63) // 64, d["R"], d["K"]
-        for name, dt in (("pod_node", np.int32), ("pod_stage", np.int32), ("unscheduled", np.int32), ("node_tmpl", np.int32), ("node_types", np.uint64), ("node_requests", np.int64),
-                         ("node_requests_present", np.uint32), ("node_present", np.uint32), ("node_complement", np.uint32), ("node_mask", np.uint64), ("node_gt", np.int32),
-                         ("node_lt", np.int32), ("node_it_state", np.int32)):
-            a = np.ascontiguousarray(np.asarray(claimed[name], dtype=dt).reshape(-1))
-            if not len(a):
-                a = np.zeros(1, dtype=dt)      # (a table of no elements is still a table: never NULL)
-            keep.append(a)
-            setattr(ra, name, a.ctypes.data)
-
-    def call(caps):
-        tabs = []
-        for i, (cp, cn) in enumerate(caps):
-            pf, nf = np.zeros(max(1, cp), dtype=np.uint32), np.zeros(max(1, cn), dtype=np.uint32)
-            tabs.append((pf, nf))
-            outs[i].pod_flags, outs[i].cap_pods, outs[i].node_flags, outs[i].cap_nodes = pf.ctypes.data, cp, nf.ctypes.data, cn
-        rc = kh.ksh_audit(hs, n, outs, ms) if ra is None else kh.ksh_audit_claimed(flats[0]._h, ctypes.byref(ra), outs, ms)
-        if rc != KS_OK:
-            raise KSolveError(rc, kh.ksh_last_error().decode())
-        return tabs
-    tabs = call([(f.dims["P"], f.dims["E"] + f.dims["P"]) for f in flats])
-    if any(o.truncated for o in outs):      # (a table was too short -- a what-if derived on the device states its own sizes only here: once more, with what the totals say)
-        tabs = call([(o.n_pods, o.n_nodes) for o in outs])
-    res = []
-    for i, o in enumerate(outs):
-        res.append({"pod_flags": tabs[i][0][:o.n_pods].copy(), "node_flags": tabs[i][1][:o.n_nodes].copy(), "n_pods_flagged": int(o.n_pods_flagged), "n_nodes_flagged": int(o.n_nodes_flagged),
-                    "pod_bit_count": {k: int(o.pod_bit_count[v.bit_length() - 1]) for k, v in KS_AUDIT_POD_BITS.items()},
-                    "node_bit_count": {k: int(o.node_bit_count[v.bit_length() - 1]) for k, v in KS_AUDIT_NODE_BITS.items()},
-                    "n_new": int(o.n_new), "n_unscheduled": int(o.n_unscheduled), "ms": (float(ms[0]), float(ms[1]))})
-    return res
-
-
-def audit_batch(flats: Sequence["FlatProblem"]) -> List[dict]:
-    """Audit the results the last solve left on the device, for a whole batch in one launch sequence (include/kshost.h ksh_audit): handles of any kind whose results
-    are there -- a Solve, what-ifs flattened one by one, what-ifs derived on the device.  One dict per problem, as `FlatProblem.audit` returns it."""
-    return _audit_call(flats)
-
-
-class _AuditTopologyOut(ctypes.Structure):      # include/kshost.h ksh_audit_topology_out
-    _fields_ = [("pod_flags", ctypes.c_void_p), ("cap_pods", ctypes.c_uint64)] + \
-               [(n, ctypes.c_uint32) for n in ("n_pods", "n_new", "n_placed", "skipped_groups", "n_pods_flagged", "truncated")] + \
-               [("checked", ctypes.c_uint32 * 4), ("pod_bit_count", ctypes.c_uint32 * 32)]
-
-
-def _audit_seq_pass(what: str, Out, flats: Sequence["FlatProblem"], claimed: Optional[dict], pod_seq, more=(), nodes=False):
-    """What the audit's passes over the commit order share (kshost.h ksh_audit_<what> / ksh_audit_<what>_claimed, out tables of type `Out`): the call over the resident
-    results of `flats`, or over `claimed` with `pod_seq` for flats[0]; once more with larger tables if one was too short.  Returns (outs, pod_flags per problem, ms)."""
-    import numpy as np
-    kh = libs()[1]
-    n = len(flats)
-    resident, claimed_fn = getattr(kh, "ksh_audit_" + what), getattr(kh, "ksh_audit_" + what + "_claimed")
+    p, kh = _AUDIT_PASSES[what], libs()[1]
+    Out, nodes = p["Out"], p["node_bits"] is not None
+    resident, claimed_fn = getattr(kh, p["stem"]), getattr(kh, p["stem"] + "_claimed")
     resident.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32, ctypes.POINTER(Out), ctypes.POINTER(ctypes.c_double)]
-    claimed_fn.argtypes = [ctypes.c_void_p, ctypes.POINTER(_ResultArrays), ctypes.c_void_p, ctypes.POINTER(Out), ctypes.POINTER(ctypes.c_double)]
+    claimed_fn.argtypes = [ctypes.c_void_p, ctypes.POINTER(_ResultArrays)] + [ctypes.c_void_p] * p["seq"] + [ctypes.POINTER(Out), ctypes.POINTER(ctypes.c_double)]
     hs = (ctypes.c_void_p * n)(*[f._h for f in flats])
     outs = (Out * n)()
     ms = (ctypes.c_double * 2)()
@@ -915,8 +869,7 @@ def _audit_seq_pass(what: str, Out, flats: Sequence["FlatProblem"], claimed: Opt
         ra = _ResultArrays()
         ra.n_pods, ra.n_existing, ra.n_new, ra.n_unscheduled = d["P"], d["E"], int(claimed["n_new"]), len(claimed["unscheduled"])
         ra.types_words, ra.n_resources, ra.n_keys = (d["T"] + 63) // 64, d["R"], d["K"]
-        for name, dt in (("pod_node", np.int32), ("pod_stage", np.int32), ("node_tmpl", np.int32), ("node_present", np.uint32), ("node_complement", np.uint32),
-                         ("node_mask", np.uint64), ("node_gt", np.int32), ("node_lt", np.int32)) + tuple(more):      # (more: the claimed arrays a pass reads beyond the second's)
+        for name, dt in _CLAIMED_COMMON + p["claimed"]:
             a = np.ascontiguousarray(np.asarray(claimed[name], dtype=dt).reshape(-1))
             if not len(a):
                 a = np.zeros(1, dtype=dt)      # (a table of no elements is still a table: never NULL)
@@ -929,140 +882,83 @@ def _audit_seq_pass(what: str, Out, flats: Sequence["FlatProblem"], claimed: Opt
             if not len(seq):
                 seq = np.zeros(1, dtype=np.int32)
 
-    ntabs = []
-
     def call(caps):
         tabs = []
-        del ntabs[:]
-        for i, cp in enumerate(caps):
-            pf = np.zeros(max(1, cp), dtype=np.uint32)
-            tabs.append(pf)
-            outs[i].pod_flags, outs[i].cap_pods = pf.ctypes.data, cp
-            if nodes:      # (the fifth pass: a table per node as well, ksh_audit's way)
-                cn = int(outs[i].n_nodes) if outs[i].truncated else flats[i].dims["E"] + flats[i].dims["P"]
-                nf = np.zeros(max(1, cn), dtype=np.uint32)
-                ntabs.append(nf)
-                outs[i].node_flags, outs[i].cap_nodes = nf.ctypes.data, cn
-        rc = resident(hs, n, outs, ms) if ra is None else claimed_fn(flats[0]._h, ctypes.byref(ra), seq.ctypes.data if seq is not None else None, outs, ms)
+        for o, (cp, cn) in zip(outs, caps):
+            pf, nf = np.zeros(max(1, cp), dtype=np.uint32), np.zeros(max(1, cn), dtype=np.uint32) if nodes else None
+            tabs.append((pf, nf))
+            o.pod_flags, o.cap_pods = pf.ctypes.data, cp
+            if nodes:
+                o.node_flags, o.cap_nodes = nf.ctypes.data, cn
+        if ra is None:
+            rc = resident(hs, n, outs, ms)
+        else:
+            rc = claimed_fn(flats[0]._h, ctypes.byref(ra), *([seq.ctypes.data if seq is not None else None] * p["seq"]), outs, ms)
         if rc != KS_OK:
             raise KSolveError(rc, kh.ksh_last_error().decode())
         return tabs
-    tabs = call([f.dims["P"] for f in flats])
-    if any(o.truncated for o in outs):      # (a what-if derived on the device states its own sizes only here: once more, with what the totals say)
-        tabs = call([o.n_pods for o in outs])
-    if nodes:
-        return outs, [(tabs[i][:o.n_pods].copy(), ntabs[i][:o.n_nodes].copy()) for i, o in enumerate(outs)], (float(ms[0]), float(ms[1]))
-    return outs, [tabs[i][:o.n_pods].copy() for i, o in enumerate(outs)], (float(ms[0]), float(ms[1]))
+    tabs = call([(f.dims["P"], f.dims["E"] + f.dims["P"]) for f in flats])
+    if any(o.truncated for o in outs):      # (a table was too short -- a what-if derived on the device states its own sizes only here: once more, with what the totals say)
+        tabs = call([(o.n_pods, o.n_nodes if nodes else 0) for o in outs])
+
+    def bit_count(o, flags, field, bits):
+        if hasattr(o, field):
+            return {k: int(getattr(o, field)[v.bit_length() - 1]) for k, v in bits.items()}
+        return {k: int(((flags & v) != 0).sum()) for k, v in bits.items()}
+    res = []
+    for o, (pf, nf) in zip(outs, tabs):
+        pf = pf[:o.n_pods].copy()
+        r = {"pod_flags": pf}
+        if nodes:
+            r["node_flags"] = nf[:o.n_nodes].copy()
+        r["n_pods_flagged"] = int(o.n_pods_flagged)
+        if nodes:
+            r["n_nodes_flagged"] = int(o.n_nodes_flagged)
+        r["pod_bit_count"] = bit_count(o, pf, "pod_bit_count", p["pod_bits"])
+        if nodes:
+            r["node_bit_count"] = bit_count(o, r["node_flags"], "node_bit_count", p["node_bits"])
+        if p["checked"]:
+            r["checked"] = {k: int(o.checked[j]) for j, k in enumerate(p["checked"])}
+        r.update((k, int(getattr(o, k))) for k in p["scalars"])
+        r["ms"] = (float(ms[0]), float(ms[1]))
+        res.append(r)
+    return res
 
 
-def _audit_topology_call(flats: Sequence["FlatProblem"], claimed: Optional[dict] = None, pod_seq=None) -> List[dict]:
-    if not len(flats):
-        return []
-    outs, flags, ms = _audit_seq_pass("topology", _AuditTopologyOut, flats, claimed, pod_seq)
-    return [{"pod_flags": flags[i], "n_pods_flagged": int(o.n_pods_flagged),
-             "pod_bit_count": {k: int(o.pod_bit_count[v.bit_length() - 1]) for k, v in KS_AUDIT_TOPOLOGY_BITS.items()},
-             "checked": {k: int(o.checked[j]) for j, k in enumerate(KS_AUDIT_TOPOLOGY_RULES)}, "skipped_groups": int(o.skipped_groups),
-             "n_new": int(o.n_new), "n_placed": int(o.n_placed), "ms": ms} for i, o in enumerate(outs)]
+def audit_batch(flats: Sequence["FlatProblem"]) -> List[dict]:
+    """Audit the results the last solve left on the device, for a whole batch in one launch sequence (include/kshost.h ksh_audit): handles of any kind whose results
+    are there -- a Solve, what-ifs flattened one by one, what-ifs derived on the device.  One dict per problem, as `FlatProblem.audit` returns it."""
+    return _audit("audit", flats)
 
 
 def audit_topology_batch(flats: Sequence["FlatProblem"]) -> List[dict]:
     """The audit's second pass over the results the last solve left on the device, for a whole batch (include/kshost.h ksh_audit_topology): handles of any kind, derived
     what-ifs included.  One dict per problem, as `FlatProblem.audit_topology` returns it."""
-    return _audit_topology_call(flats)
-
-
-class _AuditSpreadOut(ctypes.Structure):      # include/kshost.h ksh_audit_spread_out
-    _fields_ = [("pod_flags", ctypes.c_void_p), ("cap_pods", ctypes.c_uint64)] + \
-               [(n, ctypes.c_uint32) for n in ("n_pods", "n_new", "n_placed", "skipped_groups", "n_pods_flagged", "truncated")] + \
-               [("checked", ctypes.c_uint32 * 2), ("exact_pairs", ctypes.c_uint32), ("pad", ctypes.c_uint32)]
-
-
-def _audit_spread_call(flats: Sequence["FlatProblem"], claimed: Optional[dict] = None, pod_seq=None) -> List[dict]:
-    if not len(flats):
-        return []
-    outs, flags, ms = _audit_seq_pass("spread", _AuditSpreadOut, flats, claimed, pod_seq)
-    return [{"pod_flags": flags[i], "n_pods_flagged": int(o.n_pods_flagged), "pod_bit_count": {k: int(((flags[i] & v) != 0).sum()) for k, v in KS_AUDIT_SPREAD_BITS.items()},
-             "checked": {k: int(o.checked[j]) for j, k in enumerate(KS_AUDIT_SPREAD_RULES)}, "exact_pairs": int(o.exact_pairs), "skipped_groups": int(o.skipped_groups),
-             "n_new": int(o.n_new), "n_placed": int(o.n_placed), "ms": ms} for i, o in enumerate(outs)]
+    return _audit("topology", flats)
 
 
 def audit_spread_batch(flats: Sequence["FlatProblem"]) -> List[dict]:
     """The audit's third pass over the results the last solve left on the device, for a whole batch (include/kshost.h ksh_audit_spread): handles of any kind, derived
     what-ifs included.  One dict per problem, as `FlatProblem.audit_spread` returns it."""
-    return _audit_spread_call(flats)
-
-
-class _AuditFirstFitOut(ctypes.Structure):      # include/kshost.h ksh_audit_firstfit_out
-    _fields_ = [("pod_flags", ctypes.c_void_p), ("cap_pods", ctypes.c_uint64)] + \
-               [(n, ctypes.c_uint32) for n in ("n_pods", "n_new", "n_placed", "skipped_pods", "n_pods_flagged", "truncated")] + \
-               [("checked", ctypes.c_uint32 * 3), ("admitting_pairs", ctypes.c_uint32)]
-
-
-def _audit_firstfit_call(flats: Sequence["FlatProblem"], claimed: Optional[dict] = None, pod_seq=None) -> List[dict]:
-    import numpy as np
-    if not len(flats):
-        return []
-    more = (("node_types", np.uint64), ("node_requests", np.int64), ("node_requests_present", np.uint32), ("node_it_state", np.int32))
-    outs, flags, ms = _audit_seq_pass("firstfit", _AuditFirstFitOut, flats, claimed, pod_seq, more)
-    return [{"pod_flags": flags[i], "n_pods_flagged": int(o.n_pods_flagged), "pod_bit_count": {k: int(((flags[i] & v) != 0).sum()) for k, v in KS_AUDIT_FIRSTFIT_BITS.items()},
-             "checked": {k: int(o.checked[j]) for j, k in enumerate(KS_AUDIT_FIRSTFIT_CHECKED)}, "admitting_pairs": int(o.admitting_pairs), "skipped_pods": int(o.skipped_pods),
-             "n_new": int(o.n_new), "n_placed": int(o.n_placed), "ms": ms} for i, o in enumerate(outs)]
+    return _audit("spread", flats)
 
 
 def audit_firstfit_batch(flats: Sequence["FlatProblem"]) -> List[dict]:
     """The audit's fourth pass over the results the last solve left on the device, for a whole batch (include/kshost.h ksh_audit_firstfit): handles of any kind, derived
     what-ifs included.  One dict per problem, as `FlatProblem.audit_firstfit` returns it."""
-    return _audit_firstfit_call(flats)
-
-
-class _AuditLimitsOut(ctypes.Structure):      # include/kshost.h ksh_audit_limits_out
-    _fields_ = [("pod_flags", ctypes.c_void_p), ("cap_pods", ctypes.c_uint64), ("node_flags", ctypes.c_void_p), ("cap_nodes", ctypes.c_uint64)] + \
-               [(n, ctypes.c_uint32) for n in ("n_pods", "n_nodes", "n_new", "n_placed", "limited_templates", "skipped_nodes", "skipped_pods", "truncated", "n_pods_flagged",
-                                               "n_nodes_flagged", "exact_nodes", "binding_nodes")] + \
-               [("checked", ctypes.c_uint32 * 4), ("pod_bit_count", ctypes.c_uint32 * 32), ("node_bit_count", ctypes.c_uint32 * 32)]
-
-
-def _audit_limits_call(flats: Sequence["FlatProblem"], claimed: Optional[dict] = None, pod_seq=None) -> List[dict]:
-    import numpy as np
-    if not len(flats):
-        return []
-    more = (("node_types", np.uint64), ("node_requests", np.int64), ("node_requests_present", np.uint32), ("node_it_state", np.int32))
-    outs, flags, ms = _audit_seq_pass("limits", _AuditLimitsOut, flats, claimed, pod_seq, more, nodes=True)
-    return [{"pod_flags": flags[i][0], "node_flags": flags[i][1], "n_pods_flagged": int(o.n_pods_flagged), "n_nodes_flagged": int(o.n_nodes_flagged),
-             "pod_bit_count": {k: int(o.pod_bit_count[v.bit_length() - 1]) for k, v in KS_AUDIT_LIMITS_POD_BITS.items()},
-             "node_bit_count": {k: int(o.node_bit_count[v.bit_length() - 1]) for k, v in KS_AUDIT_LIMITS_NODE_BITS.items()},
-             "checked": {k: int(o.checked[j]) for j, k in enumerate(KS_AUDIT_LIMITS_CHECKED)}, "limited_templates": int(o.limited_templates),
-             "exact_nodes": int(o.exact_nodes), "binding_nodes": int(o.binding_nodes), "skipped_nodes": int(o.skipped_nodes), "skipped_pods": int(o.skipped_pods),
-             "n_new": int(o.n_new), "n_placed": int(o.n_placed), "ms": ms} for i, o in enumerate(outs)]
+    return _audit("firstfit", flats)
 
 
 def audit_limits_batch(flats: Sequence["FlatProblem"]) -> List[dict]:
     """The audit's fifth pass over the results the last solve left on the device, for a whole batch (include/kshost.h ksh_audit_limits): handles of any kind, derived
     what-ifs included.  One dict per problem, as `FlatProblem.audit_limits` returns it."""
-    return _audit_limits_call(flats)
-
-
-class _AuditHostFitOut(ctypes.Structure):      # include/kshost.h ksh_audit_hostfit_out
-    _fields_ = [("pod_flags", ctypes.c_void_p), ("cap_pods", ctypes.c_uint64)] + \
-               [(n, ctypes.c_uint32) for n in ("n_pods", "n_new", "n_placed", "skipped_pods", "n_pods_flagged", "truncated", "eligible_groups", "skipped_groups")] + \
-               [("checked", ctypes.c_uint32 * 4), ("admitting_pairs", ctypes.c_uint32), ("pad", ctypes.c_uint32)]
-
-
-def _audit_hostfit_call(flats: Sequence["FlatProblem"], claimed: Optional[dict] = None, pod_seq=None) -> List[dict]:
-    import numpy as np
-    if not len(flats):
-        return []
-    more = (("node_types", np.uint64), ("node_requests", np.int64), ("node_requests_present", np.uint32), ("node_it_state", np.int32))
-    outs, flags, ms = _audit_seq_pass("hostfit", _AuditHostFitOut, flats, claimed, pod_seq, more)
-    return [{"pod_flags": flags[i], "n_pods_flagged": int(o.n_pods_flagged), "pod_bit_count": {k: int(((flags[i] & v) != 0).sum()) for k, v in KS_AUDIT_HOSTFIT_BITS.items()},
-             "checked": {k: int(o.checked[j]) for j, k in enumerate(KS_AUDIT_HOSTFIT_CHECKED)}, "admitting_pairs": int(o.admitting_pairs), "skipped_pods": int(o.skipped_pods),
-             "eligible_groups": int(o.eligible_groups), "skipped_groups": int(o.skipped_groups), "n_new": int(o.n_new), "n_placed": int(o.n_placed), "ms": ms} for i, o in enumerate(outs)]
+    return _audit("limits", flats)
 
 
 def audit_hostfit_batch(flats: Sequence["FlatProblem"]) -> List[dict]:
     """The audit's sixth pass over the results the last solve left on the device, for a whole batch (include/kshost.h ksh_audit_hostfit): handles of any kind, derived
     what-ifs included.  One dict per problem, as `FlatProblem.audit_hostfit` returns it."""
-    return _audit_hostfit_call(flats)
+    return _audit("hostfit", flats)
 
 
 def deal_lpt(weights: Sequence[int], nshards: int) -> List[int]:

@@ -1,10 +1,11 @@
 """What tests/test_audit.py (on the lane-fibre emulator) and tests/test_audit_gpu.py (on the device) share: the hand-made problem of the tamper matrix, the matrix
 itself -- one minimal edit of a genuine result per audit bit, with the flags the edit must raise known by construction --, and the comparison of the device audit
-with the reference audit (tests/audit_ref.py).  Every function takes the scheduler module `S` it is to go through (the HIP libraries' or the emulator's)."""
+with the reference audit (tests/audit_ref.py, through tests/audit_harness.py).  Every function takes the scheduler module `S` it is to go through (the HIP libraries' or the emulator's)."""
 import copy
 
 import numpy as np
 
+import audit_harness as H
 import audit_ref as A
 from karpenter_core_amd import fake
 from karpenter_core_amd.model import (LABEL_ARCH, LABEL_CAPACITY_TYPE, LABEL_HOSTNAME, LABEL_INSTANCE_TYPE, LABEL_OS, LABEL_PROVISIONER, LABEL_ZONE, NO_SCHEDULE, Container,
@@ -12,27 +13,8 @@ from karpenter_core_amd.model import (LABEL_ARCH, LABEL_CAPACITY_TYPE, LABEL_HOS
 from karpenter_core_amd.workloads import EBS_DRIVER
 
 Z1, Z2, Z3 = "test-zone-1", "test-zone-2", "test-zone-3"
-
-
-def compare(S, flat, claimed=None):
-    """(device audit, reference pod flags, reference node flags) of the result `flat` holds -- or of `claimed` --, after asserting that the two audits agree bit for bit
-    and that the device's totals are the totals of its own flags."""
-    dev = flat.audit(claimed)
-    res = flat.result_arrays() if claimed is None else claimed
-    pf, nf = A.audit(A.problem_arrays(S, flat), res)
-    assert np.array_equal(dev["pod_flags"], pf), (np.nonzero(dev["pod_flags"] != pf)[0][:8], dev["pod_flags"][dev["pod_flags"] != pf][:8], pf[dev["pod_flags"] != pf][:8])
-    assert np.array_equal(dev["node_flags"], nf), (np.nonzero(dev["node_flags"] != nf)[0][:8], dev["node_flags"][dev["node_flags"] != nf][:8], nf[dev["node_flags"] != nf][:8])
-    assert dev["n_pods_flagged"] == int((pf != 0).sum()) and dev["n_nodes_flagged"] == int((nf != 0).sum())
-    assert dev["pod_bit_count"] == {k: int(((pf & v) != 0).sum()) for k, v in A.POD.items()}
-    assert dev["node_bit_count"] == {k: int(((nf & v) != 0).sum()) for k, v in A.NODE.items()}
-    return dev, pf, nf
-
-
-def assert_clean(S, flat):
-    dev, pf, nf = compare(S, flat)
-    assert not pf.any() and not nf.any(), ({k: int(((pf & v) != 0).sum()) for k, v in A.POD.items()}, {k: int(((nf & v) != 0).sum()) for k, v in A.NODE.items()})
-    assert dev["n_pods_flagged"] == 0 and dev["n_nodes_flagged"] == 0
-    return dev
+D = H.PASSES["audit"]      # the pass, and its comparison with the reference (tests/audit_harness.py)
+compare, assert_clean, summary = D.compare, D.assert_clean, D.summary
 
 
 # ---------------------------------------------------------------------------------------------------------------- the tamper matrix's problem

@@ -1,5 +1,5 @@
 """What tests/test_audit_firstfit.py (on the lane-fibre emulator) and tests/test_audit_firstfit_gpu.py (on the device) share: the comparison of the audit's fourth
-pass with its reference (tests/audit_firstfit_ref.py), the hand-made problems -- generic pods over existing nodes, new nodes and two templates, where the reference's
+pass with its reference (tests/audit_firstfit_ref.py, through tests/audit_harness.py), the hand-made problems -- generic pods over existing nodes, new nodes and two templates, where the reference's
 first fit is known from how the problem was made --, the tamper matrix and the shapes at which the kernels take another path.  Every function takes the scheduler
 module `S` it is to go through (the HIP libraries' or the emulator's)."""
 import copy
@@ -7,43 +7,18 @@ import copy
 import numpy as np
 
 import audit_cases as C
+import audit_ref as A
 import audit_firstfit_ref as FR
+import audit_harness as H
+from audit_harness import _claimable, flagged
 import audit_topo_cases as TC
 from karpenter_core_amd import fake
 from karpenter_core_amd.model import LABEL_INSTANCE_TYPE, Problem
 
 B = FR.BITS
+D = H.PASSES["firstfit"]      # the pass, and its comparison with the reference (tests/audit_harness.py)
+compare, assert_clean, summary = D.compare, D.assert_clean, D.summary
 FIT = B["FIT_EXISTING"] | B["FIT_NEW"] | B["FIT_TEMPLATE"]
-
-
-def compare(S, flat, claimed=None, pod_seq=None):
-    """(device pass, reference flags) of the result `flat` holds -- or of `claimed` with `pod_seq` --, after asserting that device and reference agree bit for bit,
-    `checked`, `admitting_pairs` and `skipped_pods` included, and that the device's totals are the totals of its own flags."""
-    dev = flat.audit_firstfit(claimed, pod_seq)
-    res = flat.result_arrays() if claimed is None else claimed
-    prob = FR.problem_arrays(S, flat)
-    seq = TC.commit_numbers(S, flat, prob) if pod_seq is None else pod_seq
-    flags, checked, admitting, skipped = FR.audit(prob, res, seq)
-    bad = np.nonzero(dev["pod_flags"] != flags)[0]
-    assert not len(bad), (bad[:8], dev["pod_flags"][bad][:8], flags[bad][:8])
-    assert dev["checked"] == dict(zip(FR.CHECKED, checked)), (dev["checked"], checked)
-    assert dev["admitting_pairs"] == admitting, (dev["admitting_pairs"], admitting)
-    assert dev["skipped_pods"] == skipped, (dev["skipped_pods"], skipped)
-    assert dev["n_pods_flagged"] == int((flags != 0).sum())
-    assert dev["pod_bit_count"] == {k: int(((flags & v) != 0).sum()) for k, v in B.items()}
-    assert dev["checked"]["PODS"] + dev["skipped_pods"] == len(flags)
-    return dev, flags
-
-
-def assert_clean(S, flat):
-    dev, flags = compare(S, flat)
-    assert not flags.any() and dev["n_pods_flagged"] == 0, {k: int(((flags & v) != 0).sum()) for k, v in B.items()}
-    return dev
-
-
-def summary(dev):
-    return {"pods": {k: v for k, v in dev["pod_bit_count"].items() if v}, "checked": [dev["checked"][k] for k in FR.CHECKED], "admitting": dev["admitting_pairs"],
-            "skipped": dev["skipped_pods"], "n_new": dev["n_new"], "n_placed": dev["n_placed"]}
 
 
 def with_generic_pods(pr: Problem, n: int = 3) -> Problem:
@@ -51,14 +26,6 @@ def with_generic_pods(pr: Problem, n: int = 3) -> Problem:
     pr = copy.copy(pr)
     pr.pods = list(pr.pods) + [TC._pod("zz-generic-%d" % i, cpu="10m", mem="8Mi") for i in range(n)]
     return pr
-
-
-def _claimable(res):
-    return copy.deepcopy({k: v for k, v in res.items() if k != "key_value"})
-
-
-def flagged(flags):
-    return {int(i): int(flags[i]) for i in np.nonzero(flags)[0]}
 
 
 # ---------------------------------------------------------------------------------------------------------------- the tamper matrix
@@ -289,3 +256,43 @@ def run_shapes(S):
     shape("two templates", tamper_problem, lambda flat, dev: True if flat.dims["M"] == 2 and dev["checked"]["PAIRS"] == 2 * (2 + 2 + 2) else str(dev))
     assert [r[0] for r in report] == SHAPE_NAMES
     return report
+
+
+# ---------------------------------------------------------------------------------------------------------------- the hand-made problem of the reference's unit cases
+CLASSES = PLAIN, ZONE2, TEAM, NO_TEAM, PORTS, VOLUMES, NAMED, OWNER, HUGE = range(9)
+NODES = E0, E1, E2, N0, N1, N2, N3 = range(7)
+
+
+def _tiny():
+    """Two keys -- 0 the zone (well known, values 0 1 2), 1 `team` (a custom label, values 0 1) --, one resource, two types (4 000 and 8 000 units), three templates
+    (0 limited | 1 without limits | 2 without limits, labelled team In {0}), three existing nodes with 1 000 units to spare (e0 in zone 0, e1 in zone 1, e2 without a
+    label) and four new nodes (n0: template 1, no requirement | n1: template 1, ended with team In {0} | n2: template 2, team In {0} | n3: template 1, ended with team
+    DoesNotExist).  Classes: 0 plain, 100 units | 1 zone In {2} | 2 team In {0} | 3 team DoesNotExist | 4 a host port | 5 a volume | 6 hostname In [e1] | 7 owns a
+    topology group | 8 huge: 2 000 units, which no existing node holds.  Six pods, all plain until a case says otherwise, on e0 in commit order 0 .. 5."""
+    u32, i32 = (lambda *x: np.array(x, dtype=np.uint32)), (lambda *x: np.array(x, dtype=np.int32))
+    C, Pn, K = 9, 6, 2
+    off = lambda ns: np.cumsum([0] + list(ns)).astype(np.uint32)
+    p = {"P": Pn, "C": C, "M": 3, "E": 3, "K": K, "R": 1, "T": 2, "S": 1, "SC": 1, "wellknown_mask": 1, "key_zone": 0, "key_ct": -1, "n_ct": 0,
+         "key_nvalues": u32(3, 2), "value_int": np.full(K * 64, A.NOT_INT, dtype=np.int32),
+         "pod_stage_off": np.arange(Pn + 1, dtype=np.uint32), "stage_cls": np.zeros(Pn, dtype=np.uint32),
+         "cls_own_off": off([1 if c == OWNER else 0 for c in range(C)]), "cls_isel_off": off([0] * C), "cls_port_off": off([1 if c == PORTS else 0 for c in range(C)]),
+         "cls_vol_off": off([1 if c == VOLUMES else 0 for c in range(C)]), "cls_hn_off": off([1 if c == NAMED else 0 for c in range(C)]), "hn_list": u32(E1),
+         "cls_hn_mode": np.array([1 if c == NAMED else 0 for c in range(C)], dtype=np.uint8),
+         "cls_requests": np.array([2000 if c == HUGE else 100 for c in range(C)], dtype=np.int64), "cls_requests_present": np.ones(C, dtype=np.uint32),
+         "cls_tolerated": np.zeros(C, dtype=np.uint64), "en_taints": np.zeros(3, dtype=np.uint64), "tmpl_taints": np.zeros(3, dtype=np.uint64),
+         "en_requests": np.zeros(3, dtype=np.int64), "en_requests_present": np.ones(3, dtype=np.uint32), "en_avail": np.full(3, 1000, dtype=np.int64),
+         "its_fail": np.zeros(1, dtype=np.uint8), "its_inter": np.zeros(1, dtype=np.uint16), "its_types": np.array([3], dtype=np.uint64),
+         "it_present": u32(0, 0), "it_complement": u32(0, 0), "it_mask": np.zeros(K * 2, dtype=np.uint64), "it_alloc": np.array([4000, 8000], dtype=np.int64),
+         "it_offer": np.array([1, 1], dtype=np.uint64), "tmpl_limit_present": u32(1, FR.UNLIMITED, FR.UNLIMITED), "tmpl_daemon": np.zeros(3, dtype=np.int64),
+         "tmpl_daemon_present": np.zeros(3, dtype=np.uint32), "tmpl_types": np.array([3, 3, 3], dtype=np.uint64)}
+    fams = {"tmpl": ([0, 0, 2], [[0, 0], [0, 0], [0, 1]]), "en": ([1, 1, 0], [[1, 0], [2, 0], [0, 0]]),
+            "cls": ([2 if c in (TEAM, NO_TEAM) else 1 if c == ZONE2 else 0 for c in range(C)], [[4 if c == ZONE2 else 0, 1 if c == TEAM else 0] for c in range(C)])}
+    for fam, (present, mask) in fams.items():
+        n = len(present)
+        p.update({fam + ".present": np.array(present, dtype=np.uint32), fam + ".complement": np.zeros(n, dtype=np.uint32), fam + ".mask": np.array(mask, dtype=np.uint64).reshape(-1),
+                  fam + ".gt": np.full(n * K, A.NOGT, dtype=np.int32), fam + ".lt": np.full(n * K, A.NOLT, dtype=np.int32), fam + ".it_state": np.zeros(n, dtype=np.int32)})
+    r = {"n_existing": 3, "n_new": 4, "pod_node": np.zeros(Pn, dtype=np.int32), "pod_stage": np.zeros(Pn, dtype=np.int32), "unscheduled": i32(), "node_tmpl": i32(1, 1, 2, 1),
+         "node_present": u32(0, 2, 2, 2), "node_complement": u32(0, 0, 0, 0), "node_mask": np.array([[0, 0], [0, 1], [0, 1], [0, 0]], dtype=np.uint64),
+         "node_gt": np.full((4, K), A.NOGT, dtype=np.int32), "node_lt": np.full((4, K), A.NOLT, dtype=np.int32), "node_types": np.array([3, 3, 3, 3], dtype=np.uint64),
+         "node_requests_present": np.ones(4, dtype=np.uint32), "node_it_state": np.zeros(4, dtype=np.int32)}
+    return p, r, np.arange(Pn, dtype=np.int32)

@@ -1,5 +1,5 @@
 """What tests/test_audit_hostfit.py (on the lane-fibre emulator) and tests/test_audit_hostfit_gpu.py (on the device) share: the comparison of the audit's sixth pass
-with its reference (tests/audit_hostfit_ref.py), the hand-made problems -- pods under hostname anti-affinity and hostname spread over existing nodes, new nodes and two
+with its reference (tests/audit_hostfit_ref.py, through tests/audit_harness.py), the hand-made problems -- pods under hostname anti-affinity and hostname spread over existing nodes, new nodes and two
 templates, where the reference's first fit is known from how the problem was made --, the tamper matrix, the claimed results with indices out of range and the shapes
 at which the kernels take another path.  Every function takes the scheduler module `S` it is to go through (the HIP libraries' or the emulator's)."""
 import copy
@@ -7,45 +7,18 @@ import copy
 import numpy as np
 
 import audit_cases as C
+import audit_harness as H
+from audit_harness import _claimable, flagged
 import audit_hostfit_ref as HR
 import audit_topo_cases as TC
 from karpenter_core_amd import fake
 from karpenter_core_amd.model import DO_NOT_SCHEDULE, LABEL_HOSTNAME, ClusterPod, Container, LabelSelector, Pod, PodAffinityTerm, Problem, TopologySpreadConstraint
 
 B = HR.BITS
+D = H.PASSES["hostfit"]      # the pass, and its comparison with the reference (tests/audit_harness.py)
+compare, assert_clean, summary = D.compare, D.assert_clean, D.summary
 HFIT = B["HFIT_EXISTING"] | B["HFIT_NEW"] | B["HFIT_TEMPLATE"]
 HISTORICAL_POD = 810      # rr_problem(9013): the pod a stale window flag once gave a machine of its own while a node held by a worker had room
-
-
-def compare(S, flat, claimed=None, pod_seq=None):
-    """(device pass, reference flags) of the result `flat` holds -- or of `claimed` with `pod_seq` --, after asserting that device and reference agree bit for bit,
-    every counter included, and that the device's totals are the totals of its own flags."""
-    dev = flat.audit_hostfit(claimed, pod_seq)
-    res = flat.result_arrays() if claimed is None else claimed
-    prob = HR.problem_arrays(S, flat)
-    seq = TC.commit_numbers(S, flat, prob) if pod_seq is None else pod_seq
-    flags, checked, admitting, skipped, eligible, skipped_groups = HR.audit(prob, res, seq)
-    bad = np.nonzero(dev["pod_flags"] != flags)[0]
-    assert not len(bad), (bad[:8], dev["pod_flags"][bad][:8], flags[bad][:8])
-    assert dev["checked"] == dict(zip(HR.CHECKED, checked)), (dev["checked"], checked)
-    assert dev["admitting_pairs"] == admitting, (dev["admitting_pairs"], admitting)
-    assert dev["skipped_pods"] == skipped, (dev["skipped_pods"], skipped)
-    assert (dev["eligible_groups"], dev["skipped_groups"]) == (eligible, skipped_groups), (dev["eligible_groups"], dev["skipped_groups"], eligible, skipped_groups)
-    assert dev["n_pods_flagged"] == int((flags != 0).sum())
-    assert dev["pod_bit_count"] == {k: int(((flags & v) != 0).sum()) for k, v in B.items()}
-    assert dev["checked"]["PODS"] + dev["skipped_pods"] == len(flags)
-    return dev, flags
-
-
-def assert_clean(S, flat):
-    dev, flags = compare(S, flat)
-    assert not flags.any() and dev["n_pods_flagged"] == 0, {k: int(((flags & v) != 0).sum()) for k, v in B.items()}
-    return dev
-
-
-def summary(dev):
-    return {"pods": {k: v for k, v in dev["pod_bit_count"].items() if v}, "checked": [dev["checked"][k] for k in HR.CHECKED], "admitting": dev["admitting_pairs"],
-            "skipped": dev["skipped_pods"], "groups": [dev["eligible_groups"], dev["skipped_groups"]], "n_new": dev["n_new"], "n_placed": dev["n_placed"]}
 
 
 def is_examined(prob, res, seq, p):
@@ -56,14 +29,6 @@ def is_examined(prob, res, seq, p):
     before = HR.audit(prob, res, s)[3]
     s[p] = 1 << 30
     return HR.audit(prob, res, s)[3] == before + 1
-
-
-def _claimable(res):
-    return copy.deepcopy({k: v for k, v in res.items() if k != "key_value"})
-
-
-def flagged(flags):
-    return {int(i): int(flags[i]) for i in np.nonzero(flags)[0]}
 
 
 def class_of(prob, res, p):
@@ -97,7 +62,7 @@ def historical_case(S, flat):
     that did not -- is claimed as the opener of an added node while the node it joined, opened earlier, has room again.  Returns a dict: the pod, whether it is 810,
     whether the reference examines 810, the flags it got and True or what is wrong."""
     prob, res = HR.problem_arrays(S, flat), flat.result_arrays()
-    seq = TC.commit_numbers(S, flat, prob)
+    seq = H.commit_numbers(S, flat, prob)
     E, NS = prob["E"], prob["E"] + int(res["n_new"])
     opened = {}
     for p in range(prob["P"]):

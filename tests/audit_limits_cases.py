@@ -1,13 +1,14 @@
 """What tests/test_audit_limits.py (on the lane-fibre emulator) and tests/test_audit_limits_gpu.py (on the device) share: the comparison of the audit's fifth pass
-with its reference (tests/audit_limits_ref.py), the hand-made problems -- a provisioner `capped` with a cpu limit over the ladder of instance types, where the
+with its reference (tests/audit_limits_ref.py, through tests/audit_harness.py), the hand-made problems -- a provisioner `capped` with a cpu limit over the ladder of instance types, where the
 reference's openings are known from how the problem was made --, the tamper matrix, the pinned one-sidedness and the shapes at which the kernels take another path.
 Every function takes the scheduler module `S` it is to go through (the HIP libraries' or the emulator's)."""
-import copy
 import random
 
 import numpy as np
 
 import audit_cases as C
+import audit_harness as H
+from audit_harness import _claimable, flagged
 import audit_limits_ref as LR
 import audit_topo_cases as TC
 from karpenter_core_amd import fake
@@ -15,50 +16,9 @@ from karpenter_core_amd.model import LABEL_PROVISIONER, Problem
 
 PB, NB = LR.POD_BITS, LR.NODE_BITS
 EXTRA, MISSING, LIMIT, SEQ = NB["LIMIT_EXTRA"], NB["LIMIT_MISSING"], PB["LIMIT_TEMPLATE"], PB["SEQ"]
-COUNTERS = ("limited_templates", "skipped_nodes", "skipped_pods", "exact_nodes", "binding_nodes", "n_new", "n_placed")
+D = H.PASSES["limits"]      # the pass, and its comparison with the reference (tests/audit_harness.py)
+compare, assert_clean, summary = D.compare, D.assert_clean, D.summary
 KS_WHY_LIMITS = 1
-
-
-def compare(S, flat, claimed=None, pod_seq=None):
-    """(device pass, reference pass) of the result `flat` holds -- or of `claimed` with `pod_seq` --, after asserting that device and reference agree bit for bit,
-    every counter included, and that the device's totals are the totals of its own flags."""
-    dev = flat.audit_limits(claimed, pod_seq)
-    res = flat.result_arrays() if claimed is None else claimed
-    prob = LR.problem_arrays(S, flat)
-    seq = TC.commit_numbers(S, flat, prob) if pod_seq is None else pod_seq
-    ref = LR.audit(prob, res, seq)
-    bad = np.nonzero(dev["pod_flags"] != ref["pod_flags"])[0]
-    assert not len(bad), ("pods", bad[:8], dev["pod_flags"][bad][:8], ref["pod_flags"][bad][:8])
-    bad = np.nonzero(dev["node_flags"] != ref["node_flags"])[0]
-    assert not len(bad), ("nodes", bad[:8], dev["node_flags"][bad][:8], ref["node_flags"][bad][:8])
-    assert dev["checked"] == dict(zip(LR.CHECKED, ref["checked"])), (dev["checked"], ref["checked"])
-    for k in COUNTERS:
-        assert dev[k] == ref[k], (k, dev[k], ref[k])
-    assert dev["n_pods_flagged"] == int((ref["pod_flags"] != 0).sum()) and dev["n_nodes_flagged"] == int((ref["node_flags"] != 0).sum())
-    assert dev["pod_bit_count"] == {k: int(((ref["pod_flags"] & v) != 0).sum()) for k, v in PB.items()}
-    assert dev["node_bit_count"] == {k: int(((ref["node_flags"] & v) != 0).sum()) for k, v in NB.items()}
-    if dev["limited_templates"]:
-        assert dev["checked"]["PODS"] + dev["skipped_pods"] == len(ref["pod_flags"])
-    return dev, ref
-
-
-def assert_clean(S, flat):
-    dev, ref = compare(S, flat)
-    assert not dev["n_pods_flagged"] and not dev["n_nodes_flagged"], (dev["pod_bit_count"], dev["node_bit_count"])
-    return dev
-
-
-def summary(dev):
-    return {"pods": {k: v for k, v in dev["pod_bit_count"].items() if v}, "nodes": {k: v for k, v in dev["node_bit_count"].items() if v},
-            "checked": [dev["checked"][k] for k in LR.CHECKED], **{k: dev[k] for k in COUNTERS}}
-
-
-def _claimable(res):
-    return copy.deepcopy({k: v for k, v in res.items() if k != "key_value"})
-
-
-def flagged(flags):
-    return {int(i): int(flags[i]) for i in np.nonzero(flags)[0]}
 
 
 def _type_words(res, j):

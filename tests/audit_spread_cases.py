@@ -1,43 +1,26 @@
 """What tests/test_audit_spread.py (on the lane-fibre emulator) and tests/test_audit_spread_gpu.py (on the device) share: the comparison of the audit's third pass
-with its reference (tests/audit_spread_ref.py), the hand-made problems -- zonal spreads on labelled existing nodes, where the rule is exact and the placement is
+with its reference (tests/audit_spread_ref.py, through tests/audit_harness.py), the hand-made problems -- zonal spreads on labelled existing nodes, where the rule is exact and the placement is
 known from how the problem was made --, the tamper matrix and the shapes at which the kernels take another path.  Every function takes the scheduler module `S` it
 is to go through (the HIP libraries' or the emulator's)."""
 import copy
 
 import numpy as np
 
+import audit_harness as H
 import audit_spread_ref as SR
 import audit_topo_cases as TC
+import test_fuzz as F
+import test_fuzz_mid as T
+import test_problem_arrays as PA
 from karpenter_core_amd import fake
+from karpenter_core_amd import workloads as W
 from karpenter_core_amd.model import DO_NOT_SCHEDULE, LABEL_ZONE, Expr, Problem, TopologySpreadConstraint
 
 B = SR.BITS
+D = H.PASSES["spread"]      # the pass, and its comparison with the reference (tests/audit_harness.py)
+compare, assert_clean, summary = D.compare, D.assert_clean, D.summary
 ZONES = (TC.Z1, TC.Z2, TC.Z3)
 CHUNK = 256      # csrc/ks_audit_spread.inc KS_AS_CHUNK: commit numbers per chunk; a tile is 64
-
-
-def compare(S, flat, claimed=None, pod_seq=None):
-    """(device pass, reference flags) of the result `flat` holds -- or of `claimed` with `pod_seq` --, after asserting that device and reference agree bit for bit,
-    `checked`, `exact_pairs` and `skipped_groups` included, and that the device's totals are the totals of its own flags."""
-    dev = flat.audit_spread(claimed, pod_seq)
-    res = flat.result_arrays() if claimed is None else claimed
-    prob = SR.problem_arrays(S, flat)
-    seq = TC.commit_numbers(S, flat, prob) if pod_seq is None else pod_seq
-    flags, checked, exact, skipped = SR.audit(prob, res, seq)
-    bad = np.nonzero(dev["pod_flags"] != flags)[0]
-    assert not len(bad), (bad[:8], dev["pod_flags"][bad][:8], flags[bad][:8])
-    assert dev["checked"] == dict(zip(SR.RULES, checked)), (dev["checked"], checked)
-    assert dev["exact_pairs"] == exact, (dev["exact_pairs"], exact)
-    assert dev["skipped_groups"] == skipped, (dev["skipped_groups"], skipped)
-    assert dev["n_pods_flagged"] == int((flags != 0).sum())
-    assert dev["pod_bit_count"] == {k: int(((flags & v) != 0).sum()) for k, v in B.items()}
-    return dev, flags
-
-
-def assert_clean(S, flat):
-    dev, flags = compare(S, flat)
-    assert not flags.any() and dev["n_pods_flagged"] == 0, {k: int(((flags & v) != 0).sum()) for k, v in B.items()}
-    return dev
 
 
 def sliced_batch_says_the_same(S, flats, whole):
@@ -53,11 +36,6 @@ def sliced_batch_says_the_same(S, flats, whole):
     for a, b in zip(sliced, whole):
         assert np.array_equal(a["pod_flags"], b["pod_flags"]) and summary(a) == summary(b), (summary(a), summary(b))
     return True
-
-
-def summary(dev):
-    return {"pods": {k: v for k, v in dev["pod_bit_count"].items() if v}, "checked": [dev["checked"][k] for k in SR.RULES], "exact": dev["exact_pairs"], "skipped": dev["skipped_groups"],
-            "n_new": dev["n_new"], "n_placed": dev["n_placed"]}
 
 
 # ---------------------------------------------------------------------------------------------------------------- hand-made problems
@@ -99,6 +77,19 @@ def two_keys() -> Problem:
     pods = [TC._pod("tk-%d" % i, app="tk", spread=[_spread(LABEL_ZONE, "tk"), _spread(TC.RACK, "tk")]) for i in range(4)]
     prov = fake.provisioner("open", len(its), requirements=[Expr(TC.RACK, "In", ["rack-a", "rack-b"])])
     return Problem(instance_types=its, provisioners=[prov], pods=pods, nodes=nodes, extra_well_known=fake.EXTRA_WELL_KNOWN)
+
+
+# the problems whose genuine results the GPU tests of this pass audit -- and, with pods of their own added, those of the fourth and the sixth
+GENUINE = {
+    "mid (topology, limits)": lambda: T.mid_problem(0),
+    "node filter": lambda: PA.build_case("filter"),
+    "existing nodes": lambda: PA.build_case("r3"),
+    "fuzz 0": lambda: F.fuzz_problem(0), "fuzz 3": lambda: F.fuzz_problem(3), "fuzz 5": lambda: F.fuzz_problem(5), "fuzz 11": lambda: F.fuzz_problem(11), "fuzz 16": lambda: F.fuzz_problem(16),
+    "config3": lambda: W.config3(pods=140, sizes=3, seed=1),
+    "config3, 700 pods": lambda: W.config3(pods=700, sizes=10, seed=7),
+    "a zonal spread on labelled nodes": lambda: zonal(40, plain=3),
+    "two keys": two_keys,
+}
 
 
 # ---------------------------------------------------------------------------------------------------------------- the tamper matrix

@@ -1,5 +1,5 @@
 """What tests/test_audit_topology.py (on the lane-fibre emulator) and tests/test_audit_topology_gpu.py (on the device) share: the comparison of the audit's second
-pass with its reference (tests/audit_topo_ref.py), the hand-made problems -- leaders and followers, the tamper matrix's cluster, the shapes at which the kernels take
+pass with its reference (tests/audit_topo_ref.py, through tests/audit_harness.py), the hand-made problems -- leaders and followers, the tamper matrix's cluster, the shapes at which the kernels take
 another path --, and the tamper matrix: one minimal edit of a genuine result or of its commit numbers per rule and direction, with the pods the edit must flag known
 from how the problem was made.  Every function takes the scheduler module `S` it is to go through (the HIP libraries' or the emulator's)."""
 import copy
@@ -7,45 +7,15 @@ import copy
 import numpy as np
 
 import audit_cases as C
+import audit_harness as H
 import audit_topo_ref as TR
 from karpenter_core_amd import fake
 from karpenter_core_amd.model import (DO_NOT_SCHEDULE, LABEL_HOSTNAME, LABEL_ZONE, Container, Expr, LabelSelector, Pod, PodAffinityTerm, Problem, TopologySpreadConstraint)
 
 Z1, Z2, Z3 = C.Z1, C.Z2, C.Z3
 B = TR.BITS
-
-
-def compare(S, flat, claimed=None, pod_seq=None):
-    """(device pass, reference flags, reference checked) of the result `flat` holds -- or of `claimed` with `pod_seq` --, after asserting that device and reference agree
-    bit for bit, `checked` and `skipped_groups` included, and that the device's totals are the totals of its own flags."""
-    dev = flat.audit_topology(claimed, pod_seq)
-    res = flat.result_arrays() if claimed is None else claimed
-    prob = TR.problem_arrays(S, flat)
-    seq = commit_numbers(S, flat, prob) if pod_seq is None else pod_seq
-    flags, checked, skipped = TR.audit(prob, res, seq)
-    bad = np.nonzero(dev["pod_flags"] != flags)[0]
-    assert not len(bad), (bad[:8], dev["pod_flags"][bad][:8], flags[bad][:8])
-    assert dev["checked"] == dict(zip(TR.RULES, checked)), (dev["checked"], checked)
-    assert dev["skipped_groups"] == skipped
-    assert dev["n_pods_flagged"] == int((flags != 0).sum())
-    assert dev["pod_bit_count"] == {k: int(((flags & v) != 0).sum()) for k, v in B.items()}
-    return dev, flags, checked
-
-
-def commit_numbers(S, flat, prob):
-    """The commit numbers of the result on the device by the problem's OWN pod indices, through `ksh_placement_rows`: row k is the pod at position k of the problem's
-    queue.  (`FlatProblem.pod_seq` goes by the pod the row names, which for a what-if over a snapshot is the snapshot's.)"""
-    heads, rows, _ = S.placement_rows([flat], [0])
-    seq = np.full(prob["P"], -1, dtype=np.int32)
-    if rows is not None and prob["P"]:
-        seq[prob["queue"][rows[:, S.KS_PLC_POSITION].astype(np.int64)]] = (rows[:, S.KS_PLC_STAGE_SEQ] >> np.uint64(32)).astype(np.uint32).view(np.int32)
-    return seq
-
-
-def assert_clean(S, flat):
-    dev, flags, _ = compare(S, flat)
-    assert not flags.any() and dev["n_pods_flagged"] == 0, {k: int(((flags & v) != 0).sum()) for k, v in B.items()}
-    return dev
+D = H.PASSES["topology"]      # the pass, and its comparison with the reference (tests/audit_harness.py)
+compare, assert_clean, summary = D.compare, D.assert_clean, D.summary
 
 
 # ---------------------------------------------------------------------------------------------------------------- hand-made problems

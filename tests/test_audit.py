@@ -4,19 +4,12 @@ must find NOTHING, on every case; a check that flags one of them would be a wron
 (karpenter_core_amd/csrc/ks_audit.inc) is compiled into the emulator build too and runs beside the reference: the two agree bit for bit, on the genuine results and on
 the tamper matrix (tests/audit_cases.py).  And unit cases of the reference audit alone on hand-made results, one per bit.  Runs the emulator in a subprocess: its build
 replaces the two libraries for the whole process (tests/simlib.py)."""
-import json
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
+import audit_harness as H
 import audit_ref as A
 import test_rr_emulated as E
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 
 CHILD = r"""
 import json, sys
@@ -71,13 +64,7 @@ NAMES = ["rr/" + c[0] for c in E.CASES] + ["pack/" + c[0] for c in E.PACK_CASES]
 
 @pytest.fixture(scope="module")
 def emulated():
-    env = dict(os.environ)
-    env.pop("KS_TEST_SIM", None); env.pop("KS_NO_RR", None)
-    env["KS_SIM_ALARM"] = "600"
-    pr = subprocess.run([sys.executable, "-c", CHILD % {"root": ROOT, "tests": HERE}, json.dumps([E.CASES, E.PACK_CASES])], capture_output=True, text=True, env=env, timeout=1500)
-    line = [l for l in pr.stdout.splitlines() if l.startswith("RESULT ")]
-    assert line, pr.stdout[-2000:] + pr.stderr[-2000:]
-    return json.loads(line[-1][7:])
+    return H.run_emulated(CHILD, [E.CASES, E.PACK_CASES])
 
 
 @pytest.mark.parametrize("name", NAMES)

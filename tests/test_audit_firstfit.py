@@ -8,21 +8,13 @@ validated where a correct result is known, before any GPU run:
   b) the tamper matrix and the kernels' other paths (tests/audit_firstfit_cases.py) on the emulator;
   c) unit cases of the reference alone on a hand-made problem: one per clause of the rule and per direction.
 Runs the emulator in a subprocess: its build replaces the two libraries for the whole process (tests/simlib.py)."""
-import json
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
-import audit_ref as A
 import audit_firstfit_cases as FC
 import audit_firstfit_ref as FR
+import audit_harness as H
 import test_rr_emulated as E
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 
 CHILD = r"""
 import json, sys
@@ -75,22 +67,14 @@ out["shapes"] = [[n, ok if ok is True else str(ok)] for n, ok in FC.run_shapes(S
 print("RESULT " + json.dumps(out))
 """
 
-TOPOLOGY_SETS = [[0, 3], [5], [1, 2, 9], [7, 11], [4, 6, 8, 10, 12], [15]]
-WHATIFS = ["whatifs/%d" % i for i in range(4)] + ["wide_whatifs/%d" % i for i in range(len(E.WIDE_SETS))] + ["topology_whatifs/%d" % i for i in range(len(TOPOLOGY_SETS))]
-FLAT = ["rr/" + c[0] for c in E.CASES] + ["no_rr/" + c[0] for c in E.CASES] + ["pack/" + c[0] for c in E.PACK_CASES] + WHATIFS
-DERIVED = ["wide_whatifs_derived/%d" % i for i in range(len(E.WIDE_SETS))] + ["topology_whatifs_derived/%d" % i for i in range(len(TOPOLOGY_SETS))]
+TOPOLOGY_SETS = H.WHATIF_SETS
+WHATIFS, FLAT, DERIVED = H.gate_names()
 NAMES = FLAT + DERIVED
 
 
 @pytest.fixture(scope="module")
 def emulated():
-    env = dict(os.environ)
-    env.pop("KS_TEST_SIM", None); env.pop("KS_NO_RR", None)
-    env["KS_SIM_ALARM"] = "600"
-    pr = subprocess.run([sys.executable, "-c", CHILD % {"root": ROOT, "tests": HERE}, json.dumps([E.CASES, E.PACK_CASES]), json.dumps(TOPOLOGY_SETS)], capture_output=True, text=True, env=env, timeout=1500)
-    line = [l for l in pr.stdout.splitlines() if l.startswith("RESULT ")]
-    assert line, pr.stdout[-2000:] + pr.stderr[-2000:]
-    return json.loads(line[-1][7:])
+    return H.run_emulated(CHILD, [E.CASES, E.PACK_CASES], TOPOLOGY_SETS)
 
 
 @pytest.mark.parametrize("name", NAMES)
@@ -134,49 +118,14 @@ def test_the_kernels_other_paths_on_the_emulator(emulated, i):
 
 
 # ---------------------------------------------------------------------------------------------------------------- the reference pass alone, on a hand-made problem
-PLAIN, ZONE2, TEAM, NO_TEAM, PORTS, VOLUMES, NAMED, OWNER, HUGE = range(9)
-E0, E1, E2, N0, N1, N2, N3 = range(7)
+PLAIN, ZONE2, TEAM, NO_TEAM, PORTS, VOLUMES, NAMED, OWNER, HUGE = FC.CLASSES
+E0, E1, E2, N0, N1, N2, N3 = FC.NODES
 EX, NW, TM, SQ = FR.BITS["FIT_EXISTING"], FR.BITS["FIT_NEW"], FR.BITS["FIT_TEMPLATE"], FR.BITS["SEQ"]
-
-
-def _tiny():
-    """Two keys -- 0 the zone (well known, values 0 1 2), 1 `team` (a custom label, values 0 1) --, one resource, two types (4 000 and 8 000 units), three templates
-    (0 limited | 1 without limits | 2 without limits, labelled team In {0}), three existing nodes with 1 000 units to spare (e0 in zone 0, e1 in zone 1, e2 without a
-    label) and four new nodes (n0: template 1, no requirement | n1: template 1, ended with team In {0} | n2: template 2, team In {0} | n3: template 1, ended with team
-    DoesNotExist).  Classes: 0 plain, 100 units | 1 zone In {2} | 2 team In {0} | 3 team DoesNotExist | 4 a host port | 5 a volume | 6 hostname In [e1] | 7 owns a
-    topology group | 8 huge: 2 000 units, which no existing node holds.  Six pods, all plain until a case says otherwise, on e0 in commit order 0 .. 5."""
-    u32, i32 = (lambda *x: np.array(x, dtype=np.uint32)), (lambda *x: np.array(x, dtype=np.int32))
-    C, Pn, K = 9, 6, 2
-    off = lambda ns: np.cumsum([0] + list(ns)).astype(np.uint32)
-    p = {"P": Pn, "C": C, "M": 3, "E": 3, "K": K, "R": 1, "T": 2, "S": 1, "SC": 1, "wellknown_mask": 1, "key_zone": 0, "key_ct": -1, "n_ct": 0,
-         "key_nvalues": u32(3, 2), "value_int": np.full(K * 64, A.NOT_INT, dtype=np.int32),
-         "pod_stage_off": np.arange(Pn + 1, dtype=np.uint32), "stage_cls": np.zeros(Pn, dtype=np.uint32),
-         "cls_own_off": off([1 if c == OWNER else 0 for c in range(C)]), "cls_isel_off": off([0] * C), "cls_port_off": off([1 if c == PORTS else 0 for c in range(C)]),
-         "cls_vol_off": off([1 if c == VOLUMES else 0 for c in range(C)]), "cls_hn_off": off([1 if c == NAMED else 0 for c in range(C)]), "hn_list": u32(E1),
-         "cls_hn_mode": np.array([1 if c == NAMED else 0 for c in range(C)], dtype=np.uint8),
-         "cls_requests": np.array([2000 if c == HUGE else 100 for c in range(C)], dtype=np.int64), "cls_requests_present": np.ones(C, dtype=np.uint32),
-         "cls_tolerated": np.zeros(C, dtype=np.uint64), "en_taints": np.zeros(3, dtype=np.uint64), "tmpl_taints": np.zeros(3, dtype=np.uint64),
-         "en_requests": np.zeros(3, dtype=np.int64), "en_requests_present": np.ones(3, dtype=np.uint32), "en_avail": np.full(3, 1000, dtype=np.int64),
-         "its_fail": np.zeros(1, dtype=np.uint8), "its_inter": np.zeros(1, dtype=np.uint16), "its_types": np.array([3], dtype=np.uint64),
-         "it_present": u32(0, 0), "it_complement": u32(0, 0), "it_mask": np.zeros(K * 2, dtype=np.uint64), "it_alloc": np.array([4000, 8000], dtype=np.int64),
-         "it_offer": np.array([1, 1], dtype=np.uint64), "tmpl_limit_present": u32(1, FR.UNLIMITED, FR.UNLIMITED), "tmpl_daemon": np.zeros(3, dtype=np.int64),
-         "tmpl_daemon_present": np.zeros(3, dtype=np.uint32), "tmpl_types": np.array([3, 3, 3], dtype=np.uint64)}
-    fams = {"tmpl": ([0, 0, 2], [[0, 0], [0, 0], [0, 1]]), "en": ([1, 1, 0], [[1, 0], [2, 0], [0, 0]]),
-            "cls": ([2 if c in (TEAM, NO_TEAM) else 1 if c == ZONE2 else 0 for c in range(C)], [[4 if c == ZONE2 else 0, 1 if c == TEAM else 0] for c in range(C)])}
-    for fam, (present, mask) in fams.items():
-        n = len(present)
-        p.update({fam + ".present": np.array(present, dtype=np.uint32), fam + ".complement": np.zeros(n, dtype=np.uint32), fam + ".mask": np.array(mask, dtype=np.uint64).reshape(-1),
-                  fam + ".gt": np.full(n * K, A.NOGT, dtype=np.int32), fam + ".lt": np.full(n * K, A.NOLT, dtype=np.int32), fam + ".it_state": np.zeros(n, dtype=np.int32)})
-    r = {"n_existing": 3, "n_new": 4, "pod_node": np.zeros(Pn, dtype=np.int32), "pod_stage": np.zeros(Pn, dtype=np.int32), "unscheduled": i32(), "node_tmpl": i32(1, 1, 2, 1),
-         "node_present": u32(0, 2, 2, 2), "node_complement": u32(0, 0, 0, 0), "node_mask": np.array([[0, 0], [0, 1], [0, 1], [0, 0]], dtype=np.uint64),
-         "node_gt": np.full((4, K), A.NOGT, dtype=np.int32), "node_lt": np.full((4, K), A.NOLT, dtype=np.int32), "node_types": np.array([3, 3, 3, 3], dtype=np.uint64),
-         "node_requests_present": np.ones(4, dtype=np.uint32), "node_it_state": np.zeros(4, dtype=np.int32)}
-    return p, r, np.arange(Pn, dtype=np.int32)
 
 
 def _unit(name):
     """(problem, result, commit numbers, {pod: bits}, pods examined, (class, node) pairs evaluated)"""
-    p, r, s = _tiny()
+    p, r, s = FC._tiny()
     cls, node = p["stage_cls"], r["pod_node"]
     EXISTING, NEW, TEMPLATES = 3, 4, 2      # what one class is evaluated against: every existing node it is labelled for, the new nodes, the unlimited templates
     want, pods, pairs = {}, 6, EXISTING + NEW + TEMPLATES      # (the plain class names no key: e2 is examined for it too)

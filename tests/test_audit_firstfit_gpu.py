@@ -1,25 +1,23 @@
 """(GPU) The audit's fourth pass on the device (include/ksolve.h ks_audit_firstfit_dev, KS_AUDIT_POD_FIT_*; kernels in karpenter_core_amd/csrc/ks_audit_firstfit.inc)
 against its literal reference (tests/audit_firstfit_ref.py):
   a) genuine results are clean and not vacuously so -- every flag zero, bit for bit what the reference says, `checked`, `admitting_pairs` and `skipped_pods` included --
-     over the problem list of tests/test_audit_spread_gpu.py with a few generic pods added, through ks_pack_rr and through ks_pack;
+     over the third pass's problem list (tests/audit_spread_cases.py GENUINE) with a few generic pods added, through ks_pack_rr and through ks_pack;
   b) a batch of what-ifs derived on the device against the same what-ifs flattened one by one;
   c) the tamper matrix through the claimed form, the commit numbers read from ksh_placement_rows and edited;
   d) the shapes where the kernels take another path; the same flags every run; the refusals.
 tests/test_audit_firstfit.py runs the same kernels' source on the emulator."""
-import ctypes
-
-import numpy as np
 import pytest
 
 import audit_firstfit_cases as FC
 import audit_firstfit_ref as FR
-import test_audit_spread_gpu as SG
+import audit_harness as H
+import audit_spread_cases as SC
 from karpenter_core_amd import scheduler as S
 from karpenter_core_amd import workloads as W
 
 pytestmark = pytest.mark.gpu
 
-GENUINE = {name: (lambda make=make: FC.with_generic_pods(make())) for name, make in SG.GENUINE.items()}
+GENUINE = {name: (lambda make=make: FC.with_generic_pods(make())) for name, make in SC.GENUINE.items()}
 CHECKED = {}      # (name, kernel) -> (pods examined, pairs, admitting pairs), filled by the test below and summed by the one after it
 
 
@@ -49,32 +47,9 @@ def test_the_clean_results_were_not_clean_vacuously(no_rr):
 
 
 def test_a_batch_of_derived_whatifs_is_clean():
-    """tests/test_audit_spread_gpu.py's decorated snapshot: the what-ifs flattened one by one are clean by the reference and by the device; the device pass over the
-    batch derived on the device -- the snapshot's classes, the removed nodes skipped -- finds the same, nothing, over as many pods and pairs, as many of them admitting."""
-    import test_whatif_derived as WD
-    its, prov, nodes, bound, snap, pod_node = WD._topology_snapshot(24, 5, 11, spare=2, extras=False, anti=True)
-    sets = [[0, 3], [5], [1, 2, 9], [7, 11], [4, 6, 8, 10, 12], [15]]
-    parsed = S.ParsedProblem(snap)
-    flats = S.open_whatifs(parsed, pod_node, sets, derive=False)
-    S.solve_batch(flats, decode=False)
-    plain = [FC.assert_clean(S, f) for f in flats]
-    batch = S.audit_firstfit_batch(flats)      # the batch form over flattened problems says what one call each said
-    for b, p in zip(batch, plain):
-        assert np.array_equal(b["pod_flags"], p["pod_flags"]) and FC.summary(b) == FC.summary(p)
-    derived = S.open_whatifs(parsed, pod_node, sets, derive=True)
-    S.solve_batch_resident(derived)
-    got = S.audit_firstfit_batch(derived)
-    assert len(got) == len(sets)
-    for d, p in zip(got, plain):
-        print(FC.summary(d), FC.summary(p))
-        assert not d["pod_flags"].any() and d["n_pods_flagged"] == 0
-        assert len(d["pod_flags"]) == len(p["pod_flags"]) and FC.summary(d) == FC.summary(p)
-    assert sum(d["checked"]["PODS"] for d in got) > 0
-    with pytest.raises(S.KSolveError) as e:      # a claimed result on a derived view
-        derived[0].audit_firstfit(claimed=flats[0].result_arrays(), pod_seq=np.zeros(len(plain[0]["pod_flags"]), dtype=np.int32))
-    assert e.value.code == S.KS_ERR_UNSUPPORTED
-    for f in flats + derived:
-        f.close()
+    """tests/audit_harness.py's decorated snapshot: the device pass over the batch derived on the device -- the snapshot's classes, the removed nodes skipped -- finds what
+    the what-ifs flattened one by one say, nothing, over as many pods and pairs, as many of them admitting."""
+    H.derived_whatifs_are_clean(FC.D, S, same=FC.summary, examined=lambda d: d["checked"]["PODS"])
 
 
 @pytest.fixture(scope="module")
@@ -101,50 +76,11 @@ def test_the_kernels_other_paths(shapes, name):
 
 
 def test_flags_are_the_same_every_run():
-    f = S.FlatProblem(FC.tamper_problem())
-    f.solve(decode=False)
-    name, claimed, seq, pod, bits, alone = FC.tampers(f.result_arrays(), f.pod_seq(), FR.problem_arrays(S, f))[1]
-    runs = [f.audit_firstfit(claimed, seq) for _ in range(3)]
-    assert all(np.array_equal(r["pod_flags"], runs[0]["pod_flags"]) and FC.summary(r) == FC.summary(runs[0]) for r in runs) and runs[0]["n_pods_flagged"] >= 1
-    g = S.FlatProblem(W.config3(pods=700, sizes=10, seed=7))      # new nodes and many classes: open[] and first_*[] by atomicMin, the sums by atomicAdd
-    g.solve(decode=False)
-    runs = [g.audit_firstfit() for _ in range(3)]
-    assert all(np.array_equal(r["pod_flags"], runs[0]["pod_flags"]) and FC.summary(r) == FC.summary(runs[0]) for r in runs) and runs[0]["checked"]["PODS"] > 0
-    f.close(); g.close()
+    first = H.same_flags_every_run(FC.D, S, FC.tamper_problem(), lambda f: FC.tampers(f.result_arrays(), f.pod_seq(), FR.problem_arrays(S, f))[1][1:3])
+    assert first["n_pods_flagged"] >= 1
+    first = H.same_flags_every_run(FC.D, S, W.config3(pods=700, sizes=10, seed=7))      # new nodes and many classes: open[] and first_*[] by atomicMin, the sums by atomicAdd
+    assert first["checked"]["PODS"] > 0
 
 
 def test_refusals():
-    ks, kh = S.libs()
-    f = S.FlatProblem(FC.tamper_problem())
-    f.upload(0)
-    with pytest.raises(S.KSolveError) as e:      # nothing solved
-        f.audit_firstfit()
-    assert e.value.code == S.KS_ERR_INVALID
-    f.solve(decode=False)
-    kh.ksh_audit_firstfit.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32, ctypes.POINTER(S._AuditFirstFitOut), ctypes.POINTER(ctypes.c_double)]
-    hs = (ctypes.c_void_p * 1)(f._h)
-    out = (S._AuditFirstFitOut * 1)()
-    out[0].cap_pods, out[0].pod_flags = 64, None      # a table promised and not given
-    assert kh.ksh_audit_firstfit(hs, 1, out, None) == S.KS_ERR_INVALID
-    assert kh.ksh_audit_firstfit(hs, 1, None, None) == S.KS_ERR_INVALID
-    assert kh.ksh_audit_firstfit(None, 1, out, None) == S.KS_ERR_INVALID
-    out[0].cap_pods = 0      # the totals alone: no table needed
-    assert kh.ksh_audit_firstfit(hs, 1, out, None) == S.KS_OK and out[0].n_pods == f.dims["P"] and out[0].truncated == S.KSH_AUDIT_TRUNCATED_PODS and out[0].checked[0] == f.dims["P"]
-    ks.ks_audit_firstfit_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-    assert ks.ks_audit_firstfit_dev(None, None, None) == S.KS_ERR_INVALID
-    ks.ks_audit_firstfit_batch_dev.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]
-    assert ks.ks_audit_firstfit_batch_dev(None, 1, None) == S.KS_ERR_INVALID
-    res, seq = f.result_arrays(), f.pod_seq()
-    many = dict(res, n_new=f.dims["P"] + 1)      # more new nodes than max_new_nodes
-    with pytest.raises(S.KSolveError) as e:
-        f.audit_firstfit(claimed=many, pod_seq=seq)
-    assert e.value.code == S.KS_ERR_INVALID
-    with pytest.raises(S.KSolveError) as e:      # no commit numbers
-        f.audit_firstfit(claimed=res)
-    assert e.value.code == S.KS_ERR_INVALID
-    kh.ksh_audit_firstfit_claimed.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(S._AuditFirstFitOut), ctypes.POINTER(ctypes.c_double)]
-    assert kh.ksh_audit_firstfit_claimed(f._h, None, seq.ctypes.data, out, None) == S.KS_ERR_INVALID
-    ra = S._ResultArrays()      # the right dimensions and no arrays
-    ra.n_pods, ra.n_existing, ra.types_words, ra.n_resources, ra.n_keys = f.dims["P"], f.dims["E"], (f.dims["T"] + 63) // 64, f.dims["R"], f.dims["K"]
-    assert kh.ksh_audit_firstfit_claimed(f._h, ctypes.byref(ra), seq.ctypes.data, out, None) == S.KS_ERR_INVALID
-    f.close()
+    H.refusals(FC.D, S, FC.tamper_problem())

@@ -6,12 +6,11 @@
   b) the tamper matrix (tests/audit_cases.py) through the claimed form: one minimal edit per bit raises exactly that bit on exactly those indices;
   c) the refusals.
 tests/test_audit.py runs the same kernels' source on the emulator."""
-import ctypes
-
 import numpy as np
 import pytest
 
 import audit_cases as C
+import audit_harness as H
 import audit_ref as A
 import test_fuzz as F
 import test_fuzz_mid as T
@@ -127,42 +126,9 @@ def test_the_matrix_is_the_list(matrix):
 
 
 def test_flags_are_the_same_every_run():
-    f = S.FlatProblem(C.tamper_problem())
-    f.solve(decode=False)
-    res, prob = f.result_arrays(), A.problem_arrays(S, f)
-    name, claimed, _, _ = C.tampers(res, prob)[4]
-    runs = [f.audit(claimed) for _ in range(3)]
-    assert all(np.array_equal(r["pod_flags"], runs[0]["pod_flags"]) and np.array_equal(r["node_flags"], runs[0]["node_flags"]) for r in runs) and runs[0]["n_pods_flagged"] == 2
-    f.close()
+    first = H.same_flags_every_run(C.D, S, C.tamper_problem(), lambda f: (C.tampers(f.result_arrays(), A.problem_arrays(S, f))[4][1],))
+    assert first["n_pods_flagged"] == 2
 
 
 def test_refusals():
-    ks, kh = S.libs()
-    f = S.FlatProblem(C.tamper_problem())
-    f.upload(0)
-    with pytest.raises(S.KSolveError) as e:      # nothing solved
-        f.audit()
-    assert e.value.code == S.KS_ERR_INVALID
-    f.solve(decode=False)
-    kh.ksh_audit.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32, ctypes.POINTER(S._AuditOut), ctypes.POINTER(ctypes.c_double)]
-    hs = (ctypes.c_void_p * 1)(f._h)
-    out = (S._AuditOut * 1)()
-    out[0].cap_pods, out[0].pod_flags = 64, None      # a table promised and not given
-    assert kh.ksh_audit(hs, 1, out, None) == S.KS_ERR_INVALID
-    assert kh.ksh_audit(hs, 1, None, None) == S.KS_ERR_INVALID
-    assert kh.ksh_audit(None, 1, out, None) == S.KS_ERR_INVALID
-    out[0].cap_pods = 0      # the totals alone: no table needed
-    assert kh.ksh_audit(hs, 1, out, None) == S.KS_OK and out[0].n_pods == f.dims["P"] and out[0].truncated == S.KSH_AUDIT_TRUNCATED_PODS | S.KSH_AUDIT_TRUNCATED_NODES
-    ks.ks_audit_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-    assert ks.ks_audit_dev(None, None, None) == S.KS_ERR_INVALID
-    res = f.result_arrays()
-    many = dict(res, n_new=f.dims["P"] + 1)      # more new nodes than max_new_nodes
-    with pytest.raises(S.KSolveError) as e:
-        f.audit(claimed=many)
-    assert e.value.code == S.KS_ERR_INVALID
-    kh.ksh_audit_claimed.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(S._AuditOut), ctypes.POINTER(ctypes.c_double)]
-    assert kh.ksh_audit_claimed(f._h, None, out, None) == S.KS_ERR_INVALID
-    ra = S._ResultArrays()      # the right dimensions and no arrays
-    ra.n_pods, ra.n_existing, ra.types_words, ra.n_resources, ra.n_keys = f.dims["P"], f.dims["E"], (f.dims["T"] + 63) // 64, f.dims["R"], f.dims["K"]
-    assert kh.ksh_audit_claimed(f._h, ctypes.byref(ra), out, None) == S.KS_ERR_INVALID
-    f.close()
+    H.refusals(C.D, S, C.tamper_problem())

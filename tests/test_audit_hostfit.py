@@ -9,21 +9,14 @@ KS_AUDIT_POD_HFIT_*) -- validated where a correct result is known, before any GP
      (tests/audit_hostfit_cases.py) on the emulator;
   c) unit cases of the reference alone on a hand-made problem: one per clause of the rule, silent, and its counterpart that flags.
 Runs the emulator in a subprocess: its build replaces the two libraries for the whole process (tests/simlib.py)."""
-import json
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
+import audit_firstfit_cases as FC
+import audit_harness as H
 import audit_hostfit_cases as HC
 import audit_hostfit_ref as HR
-import test_audit_firstfit as TF
 import test_rr_emulated as E
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 
 CHILD = r"""
 import json, sys
@@ -81,18 +74,14 @@ out["shapes"] = [[n, ok if ok is True else str(ok)[:600]] for n, ok in HC.run_sh
 print("RESULT " + json.dumps(out))
 """
 
-TOPOLOGY_SETS, WHATIFS, FLAT, DERIVED, NAMES = TF.TOPOLOGY_SETS, TF.WHATIFS, TF.FLAT, TF.DERIVED, TF.NAMES
+TOPOLOGY_SETS = H.WHATIF_SETS
+WHATIFS, FLAT, DERIVED = H.gate_names()
+NAMES = FLAT + DERIVED
 
 
 @pytest.fixture(scope="module")
 def emulated():
-    env = dict(os.environ)
-    env.pop("KS_TEST_SIM", None); env.pop("KS_NO_RR", None)
-    env["KS_SIM_ALARM"] = "600"
-    pr = subprocess.run([sys.executable, "-c", CHILD % {"root": ROOT, "tests": HERE}, json.dumps([E.CASES, E.PACK_CASES]), json.dumps(TOPOLOGY_SETS)], capture_output=True, text=True, env=env, timeout=1500)
-    line = [l for l in pr.stdout.splitlines() if l.startswith("RESULT ")]
-    assert line, pr.stdout[-2000:] + pr.stderr[-2000:]
-    return json.loads(line[-1][7:])
+    return H.run_emulated(CHILD, [E.CASES, E.PACK_CASES], TOPOLOGY_SETS)
 
 
 @pytest.mark.parametrize("name", NAMES)
@@ -153,18 +142,18 @@ def test_the_kernels_other_paths_on_the_emulator(emulated, i):
 
 
 # ---------------------------------------------------------------------------------------------------------------- the reference pass alone, on a hand-made problem
-PLAIN, PORTS, OWNER = TF.PLAIN, TF.PORTS, TF.OWNER
-E0, E1, N0, N2 = TF.E0, TF.E1, TF.N0, TF.N2
+PLAIN, PORTS, OWNER = FC.PLAIN, FC.PORTS, FC.OWNER
+E0, E1, N0, N2 = FC.E0, FC.E1, FC.N0, FC.N2
 EX, NW, TM = HR.BITS["HFIT_EXISTING"], HR.BITS["HFIT_NEW"], HR.BITS["HFIT_TEMPLATE"]
 ANTI, SPREAD, ZONAL, AFFINITY, FILTERED, INACTIVE = range(6)      # the groups: 0 hostname anti-affinity | 1 hostname spread, maxSkew 1 | 2 spread over the zone | 3 hostname affinity | 4 hostname spread under a node filter | 5 a hostname anti-affinity group created later
 SELF = 1 << 31
 
 
 def _hand(name):
-    """tests/test_audit_firstfit.py's hand-made problem -- three existing nodes with 1 000 units to spare, four new nodes, template 0 limited, six pods of 100 units on
+    """tests/audit_firstfit_cases.py's hand-made problem -- three existing nodes with 1 000 units to spare, four new nodes, template 0 limited, six pods of 100 units on
     e0 -- with six topology groups.  Pod 3 is the subject: of class OWNER, constrained by the groups the case names, placed on e1 although e0 has room for its
     requests -- flagged HFIT_EXISTING unless a clause of the rule keeps e0 from admitting it.  Returns (problem, result, commit numbers, {pod: bits}, pods examined)."""
-    p, r, s = TF._tiny()
+    p, r, s = FC._tiny()
     C, En = p["C"], p["E"]
     u32 = lambda x: np.array(x, dtype=np.uint32)
     p.update({"G": 6, "GH": 5, "grp_key": np.array([-2, -2, 0, -2, -2, -2], dtype=np.int32), "grp_type": np.array([2, 0, 0, 1, 0, 2], dtype=np.uint8),

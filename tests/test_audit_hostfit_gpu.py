@@ -1,21 +1,20 @@
 """(GPU) The audit's sixth pass on the device (include/ksolve.h ks_audit_hostfit_dev, KS_AUDIT_POD_HFIT_*; kernels in karpenter_core_amd/csrc/ks_audit_hostfit.inc)
 against its literal reference (tests/audit_hostfit_ref.py):
   a) genuine results are clean -- every flag zero, bit for bit what the reference says, every counter included -- over the problem list of
-     tests/test_audit_spread_gpu.py with a few hostname-spread pods added, through ks_pack_rr and through ks_pack, and not vacuously so;
+     tests/audit_spread_cases.py (GENUINE) with a few hostname-spread pods added, through ks_pack_rr and through ks_pack, and not vacuously so;
   b) rr_problem(9013): the fourth pass examines no pod of it, this pass examines pod 810, and the historical edit raises HFIT_NEW;
   c) a batch of what-ifs derived on the device -- removed nodes among them -- against the same what-ifs flattened one by one;
   d) the tamper matrix and the claimed results with indices out of range (proved on the emulator first: tests/test_audit_hostfit.py) through the claimed form;
   e) the shapes where the kernels take another path; the same flags every run; the refusals.
 tests/test_audit_hostfit.py runs the same kernels' source on the emulator."""
 import copy
-import ctypes
 
-import numpy as np
 import pytest
 
+import audit_harness as H
 import audit_hostfit_cases as HC
+import audit_spread_cases as SC
 import audit_topo_cases as TC
-import test_audit_spread_gpu as SG
 from karpenter_core_amd import scheduler as S
 from karpenter_core_amd import workloads as W
 
@@ -29,7 +28,7 @@ def _with_spread_pods(pr, n=3):
     return pr
 
 
-GENUINE = {name: (lambda make=make: _with_spread_pods(make())) for name, make in SG.GENUINE.items()}
+GENUINE = {name: (lambda make=make: _with_spread_pods(make())) for name, make in SC.GENUINE.items()}
 CHECKED = {}      # (name, kernel) -> (pods examined, pairs, count tests, admitting pairs), filled by the test below and summed by the one after it
 
 
@@ -76,34 +75,10 @@ def test_rr_9013_is_examined_and_the_historical_edit_is_flagged():
 
 
 def test_a_batch_of_derived_whatifs_with_removed_nodes_is_clean():
-    """tests/test_audit_spread_gpu.py's decorated snapshot: the what-ifs flattened one by one are clean by the reference and by the device; the device pass over the
-    batch derived on the device -- the snapshot's classes and groups, the removed nodes skipped and their hostnames unregistered (init == -1) -- finds the same,
-    nothing, over as many pods, pairs and count tests, as many of them admitting."""
-    import test_whatif_derived as WD
-    its, prov, nodes, bound, snap, pod_node = WD._topology_snapshot(24, 5, 11, spare=2, extras=False, anti=True)
-    sets = [[0, 3], [5], [1, 2, 9], [7, 11], [4, 6, 8, 10, 12], [15]]
-    parsed = S.ParsedProblem(snap)
-    flats = S.open_whatifs(parsed, pod_node, sets, derive=False)
-    S.solve_batch(flats, decode=False)
-    plain = [HC.assert_clean(S, f) for f in flats]
-    batch = S.audit_hostfit_batch(flats)      # the batch form over flattened problems says what one call each said
-    for b, p in zip(batch, plain):
-        assert np.array_equal(b["pod_flags"], p["pod_flags"]) and HC.summary(b) == HC.summary(p)
-    derived = S.open_whatifs(parsed, pod_node, sets, derive=True)
-    S.solve_batch_resident(derived)
-    got = S.audit_hostfit_batch(derived)
-    assert len(got) == len(sets)
-    same = lambda d: {k: v for k, v in HC.summary(d).items() if k != "groups"}      # (a derived what-if numbers the snapshot's groups: more of them are skipped, as many are eligible)
-    for d, p in zip(got, plain):
-        print(HC.summary(d), HC.summary(p))
-        assert not d["pod_flags"].any() and d["n_pods_flagged"] == 0
-        assert len(d["pod_flags"]) == len(p["pod_flags"]) and same(d) == same(p) and d["eligible_groups"] == p["eligible_groups"]
-    assert sum(d["checked"]["PODS"] for d in got) > 0
-    with pytest.raises(S.KSolveError) as e:      # a claimed result on a derived view
-        derived[0].audit_hostfit(claimed=flats[0].result_arrays(), pod_seq=np.zeros(len(plain[0]["pod_flags"]), dtype=np.int32))
-    assert e.value.code == S.KS_ERR_UNSUPPORTED
-    for f in flats + derived:
-        f.close()
+    """tests/audit_harness.py's decorated snapshot: the device pass over the batch derived on the device -- the snapshot's classes and groups, the removed nodes skipped
+    and their hostnames unregistered (init == -1) -- finds what the what-ifs flattened one by one say, nothing, over as many pods, pairs and count tests, as many of them
+    admitting.  (A derived what-if numbers the snapshot's groups: more of them are skipped, as many are eligible.)"""
+    H.derived_whatifs_are_clean(HC.D, S, same=lambda d: dict(HC.summary(d), groups=d["eligible_groups"]), examined=lambda d: d["checked"]["PODS"])
 
 
 @pytest.fixture(scope="module")
@@ -143,50 +118,11 @@ def test_the_kernels_other_paths(shapes, name):
 
 
 def test_flags_are_the_same_every_run():
-    f = S.FlatProblem(HC.tamper_problem())
-    f.solve(decode=False)
-    name, claimed, seq, want = HC.tampers(f.result_arrays(), f.pod_seq())[1]
-    runs = [f.audit_hostfit(claimed, seq) for _ in range(3)]
-    assert all(np.array_equal(r["pod_flags"], runs[0]["pod_flags"]) and HC.summary(r) == HC.summary(runs[0]) for r in runs) and runs[0]["n_pods_flagged"] >= 1
-    g = S.FlatProblem(W.hostname_herd(pods=600, labels=3, seed=3))      # new nodes, many pods per group: fin by atomicAdd, open[] and first_*[] by atomicMin
-    g.solve(decode=False)
-    runs = [g.audit_hostfit() for _ in range(3)]
-    assert all(np.array_equal(r["pod_flags"], runs[0]["pod_flags"]) and HC.summary(r) == HC.summary(runs[0]) for r in runs) and runs[0]["checked"]["PODS"] > 0
-    f.close(); g.close()
+    first = H.same_flags_every_run(HC.D, S, HC.tamper_problem(), lambda f: HC.tampers(f.result_arrays(), f.pod_seq())[1][1:3])
+    assert first["n_pods_flagged"] >= 1
+    first = H.same_flags_every_run(HC.D, S, W.hostname_herd(pods=600, labels=3, seed=3))      # new nodes, many pods per group: fin by atomicAdd, open[] and first_*[] by atomicMin
+    assert first["checked"]["PODS"] > 0
 
 
 def test_refusals():
-    ks, kh = S.libs()
-    f = S.FlatProblem(HC.tamper_problem())
-    f.upload(0)
-    with pytest.raises(S.KSolveError) as e:      # nothing solved
-        f.audit_hostfit()
-    assert e.value.code == S.KS_ERR_INVALID
-    f.solve(decode=False)
-    kh.ksh_audit_hostfit.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32, ctypes.POINTER(S._AuditHostFitOut), ctypes.POINTER(ctypes.c_double)]
-    hs = (ctypes.c_void_p * 1)(f._h)
-    out = (S._AuditHostFitOut * 1)()
-    out[0].cap_pods, out[0].pod_flags = 64, None      # a table promised and not given
-    assert kh.ksh_audit_hostfit(hs, 1, out, None) == S.KS_ERR_INVALID
-    assert kh.ksh_audit_hostfit(hs, 1, None, None) == S.KS_ERR_INVALID
-    assert kh.ksh_audit_hostfit(None, 1, out, None) == S.KS_ERR_INVALID
-    out[0].cap_pods = 0      # the totals alone: no table needed
-    assert kh.ksh_audit_hostfit(hs, 1, out, None) == S.KS_OK and out[0].n_pods == f.dims["P"] and out[0].truncated == S.KSH_AUDIT_TRUNCATED_PODS and out[0].checked[0] == f.dims["P"]
-    ks.ks_audit_hostfit_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-    assert ks.ks_audit_hostfit_dev(None, None, None) == S.KS_ERR_INVALID
-    ks.ks_audit_hostfit_batch_dev.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]
-    assert ks.ks_audit_hostfit_batch_dev(None, 1, None) == S.KS_ERR_INVALID
-    res, seq = f.result_arrays(), f.pod_seq()
-    many = dict(res, n_new=f.dims["P"] + 1)      # more new nodes than max_new_nodes
-    with pytest.raises(S.KSolveError) as e:
-        f.audit_hostfit(claimed=many, pod_seq=seq)
-    assert e.value.code == S.KS_ERR_INVALID
-    with pytest.raises(S.KSolveError) as e:      # no commit numbers
-        f.audit_hostfit(claimed=res)
-    assert e.value.code == S.KS_ERR_INVALID
-    kh.ksh_audit_hostfit_claimed.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(S._AuditHostFitOut), ctypes.POINTER(ctypes.c_double)]
-    assert kh.ksh_audit_hostfit_claimed(f._h, None, seq.ctypes.data, out, None) == S.KS_ERR_INVALID
-    ra = S._ResultArrays()      # the right dimensions and no arrays
-    ra.n_pods, ra.n_existing, ra.types_words, ra.n_resources, ra.n_keys = f.dims["P"], f.dims["E"], (f.dims["T"] + 63) // 64, f.dims["R"], f.dims["K"]
-    assert kh.ksh_audit_hostfit_claimed(f._h, ctypes.byref(ra), seq.ctypes.data, out, None) == S.KS_ERR_INVALID
-    f.close()
+    H.refusals(HC.D, S, HC.tamper_problem())

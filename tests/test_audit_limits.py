@@ -9,20 +9,13 @@ KS_AUDIT_POD_LIMIT_TEMPLATE) -- validated where a correct result is known, befor
   b) the tamper matrix, the pinned one-sidedness, a batch of what-ifs derived on the device and the kernels' other paths (tests/audit_limits_cases.py) on the emulator;
   c) unit cases of the reference alone on a hand-made problem: one per clause of the rule and per direction.
 Runs the emulator in a subprocess: its build replaces the two libraries for the whole process (tests/simlib.py)."""
-import json
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
+import audit_harness as H
 import audit_limits_cases as LC
 import audit_limits_ref as LR
 import test_rr_emulated as E
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 
 CHILD = r"""
 import json, sys
@@ -79,13 +72,7 @@ PROVEN = ["config5"] + FAMILY
 
 @pytest.fixture(scope="module")
 def emulated():
-    env = dict(os.environ)
-    env.pop("KS_TEST_SIM", None); env.pop("KS_NO_RR", None)
-    env["KS_SIM_ALARM"] = "600"
-    pr = subprocess.run([sys.executable, "-c", CHILD % {"root": ROOT, "tests": HERE}, json.dumps(PACK)], capture_output=True, text=True, env=env, timeout=1500)
-    line = [l for l in pr.stdout.splitlines() if l.startswith("RESULT ")]
-    assert line, pr.stdout[-2000:] + pr.stderr[-2000:]
-    return json.loads(line[-1][7:])
+    return H.run_emulated(CHILD, PACK)
 
 
 @pytest.mark.parametrize("name", ["pack/" + c[0] for c in PACK] + PROVEN)

@@ -6,11 +6,10 @@ karpenter_core_amd/csrc/ks_audit_limits.inc) against its literal reference (test
   c) a batch of six what-ifs of a 24-node snapshot whose provisioner carries a limit, derived on the device against flattened one by one;
   d) the shapes where the kernels take another path; the same flags every run; the refusals.
 tests/test_audit_limits.py runs the same kernels' source on the emulator."""
-import ctypes
-
 import numpy as np
 import pytest
 
+import audit_harness as H
 import audit_limits_cases as LC
 from karpenter_core_amd import scheduler as S
 
@@ -75,57 +74,16 @@ def test_the_kernels_other_paths(shapes, name):
 
 
 def test_flags_are_the_same_every_run():
-    f = S.FlatProblem(LC.capped_problem())
-    f.solve(decode=False)
-    r, s = LC._claimable(f.result_arrays()), np.array(f.pod_seq(), dtype=np.int32)
-    r["node_tmpl"][1] = 1
-    LC._set_types(r, 0, 0x30)
-    runs = [f.audit_limits(r, s) for _ in range(3)]
-    assert all(np.array_equal(x["pod_flags"], runs[0]["pod_flags"]) and np.array_equal(x["node_flags"], runs[0]["node_flags"]) and LC.summary(x) == LC.summary(runs[0]) for x in runs)
-    assert runs[0]["n_pods_flagged"] >= 1
-    g = S.FlatProblem(LC.chain_problem(257))      # open[] by atomicMin, the counters by atomicAdd, 257 nodes through the scans
-    g.solve(decode=False)
-    runs = [g.audit_limits() for _ in range(3)]
-    assert all(np.array_equal(x["pod_flags"], runs[0]["pod_flags"]) and np.array_equal(x["node_flags"], runs[0]["node_flags"]) and LC.summary(x) == LC.summary(runs[0]) for x in runs)
-    assert runs[0]["exact_nodes"] == 257
-    f.close(); g.close()
+    def edit(f):
+        r, s = LC._claimable(f.result_arrays()), np.array(f.pod_seq(), dtype=np.int32)
+        r["node_tmpl"][1] = 1
+        LC._set_types(r, 0, 0x30)
+        return r, s
+    first = H.same_flags_every_run(LC.D, S, LC.capped_problem(), edit)
+    assert first["n_pods_flagged"] >= 1
+    first = H.same_flags_every_run(LC.D, S, LC.chain_problem(257))      # open[] by atomicMin, the counters by atomicAdd, 257 nodes through the scans
+    assert first["exact_nodes"] == 257
 
 
 def test_refusals():
-    ks, kh = S.libs()
-    f = S.FlatProblem(LC.capped_problem())
-    f.upload(0)
-    with pytest.raises(S.KSolveError) as e:      # nothing solved
-        f.audit_limits()
-    assert e.value.code == S.KS_ERR_INVALID
-    f.solve(decode=False)
-    kh.ksh_audit_limits.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32, ctypes.POINTER(S._AuditLimitsOut), ctypes.POINTER(ctypes.c_double)]
-    hs = (ctypes.c_void_p * 1)(f._h)
-    out = (S._AuditLimitsOut * 1)()
-    out[0].cap_pods, out[0].pod_flags = 64, None      # a table promised and not given
-    assert kh.ksh_audit_limits(hs, 1, out, None) == S.KS_ERR_INVALID
-    out[0].cap_pods, out[0].cap_nodes, out[0].node_flags = 0, 64, None
-    assert kh.ksh_audit_limits(hs, 1, out, None) == S.KS_ERR_INVALID
-    assert kh.ksh_audit_limits(hs, 1, None, None) == S.KS_ERR_INVALID
-    assert kh.ksh_audit_limits(None, 1, out, None) == S.KS_ERR_INVALID
-    out[0].cap_nodes = 0      # the totals alone: no table needed
-    assert kh.ksh_audit_limits(hs, 1, out, None) == S.KS_OK and out[0].n_pods == f.dims["P"] and out[0].n_nodes == 3 and out[0].checked[0] == f.dims["P"]
-    assert out[0].truncated == S.KSH_AUDIT_TRUNCATED_PODS | S.KSH_AUDIT_TRUNCATED_NODES and out[0].limited_templates == 1 and out[0].exact_nodes == 2
-    ks.ks_audit_limits_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-    assert ks.ks_audit_limits_dev(None, None, None) == S.KS_ERR_INVALID
-    ks.ks_audit_limits_batch_dev.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]
-    assert ks.ks_audit_limits_batch_dev(None, 1, None) == S.KS_ERR_INVALID
-    res, seq = f.result_arrays(), f.pod_seq()
-    many = dict(res, n_new=f.dims["P"] + 1)      # more new nodes than max_new_nodes
-    with pytest.raises(S.KSolveError) as e:
-        f.audit_limits(claimed=many, pod_seq=seq)
-    assert e.value.code == S.KS_ERR_INVALID
-    with pytest.raises(S.KSolveError) as e:      # no commit numbers
-        f.audit_limits(claimed=res)
-    assert e.value.code == S.KS_ERR_INVALID
-    kh.ksh_audit_limits_claimed.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(S._AuditLimitsOut), ctypes.POINTER(ctypes.c_double)]
-    assert kh.ksh_audit_limits_claimed(f._h, None, seq.ctypes.data, out, None) == S.KS_ERR_INVALID
-    ra = S._ResultArrays()      # the right dimensions and no arrays
-    ra.n_pods, ra.n_existing, ra.types_words, ra.n_resources, ra.n_keys = f.dims["P"], f.dims["E"], (f.dims["T"] + 63) // 64, f.dims["R"], f.dims["K"]
-    assert kh.ksh_audit_limits_claimed(f._h, ctypes.byref(ra), seq.ctypes.data, out, None) == S.KS_ERR_INVALID
-    f.close()
+    H.refusals(LC.D, S, LC.capped_problem(), totals=lambda out, f: (out.n_nodes, out.limited_templates, out.exact_nodes) == (3, 1, 2))

@@ -1,21 +1,16 @@
-"""(CPU) Every refusal of the five audit passes, resident and claimed, through the C ABI (include/kshost.h ksh_audit* / ksh_audit*_claimed; include/ksolve.h
+"""(CPU) Every refusal of the six audit passes, resident and claimed, through the C ABI (include/kshost.h ksh_audit* / ksh_audit*_claimed; include/ksolve.h
 ks_audit*_dev / ks_audit*_batch_dev for the refusals that need no device problem): the (code, message) of each, and which refusal wins where two apply at once.
 EXPECTED was recorded from the commit before the five passes' host halves were folded into one path (csrc/ks_audit.inc's host half, host/api.cpp's audit entry
-template) and holds unchanged after it: a caller sees the same refusals in the same order.  No kernel result is asserted here -- the calls that are accepted only
+template) and holds unchanged after it: a caller sees the same refusals in the same order.  The sixth pass, added on that one path, has its entries from the commit
+before the Python binding's six copies were folded into one table (karpenter_core_amd/scheduler.py _AUDIT_PASSES).  No kernel result is asserted here -- the calls that are accepted only
 say so.  The problem is the smallest with a new node and an unscheduled pod: tests/audit_limits_cases.py's `capped` provisioner alone with five pods (two machines,
 pods 3 and 4 unscheduled for the limit).
 Runs the emulator in a subprocess: its build replaces the two libraries for the whole process (tests/simlib.py)."""
-import json
-import os
-import subprocess
-import sys
-
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
+import audit_harness as H
 
-PASSES = ["audit", "topology", "spread", "firstfit", "limits"]
+PASSES = ["audit", "topology", "spread", "firstfit", "limits", "hostfit"]
 ARRAYS = ["pod_node", "pod_stage", "pod_reason", "unscheduled", "node_pods_off", "node_pods", "node_tmpl", "node_types", "node_requests", "node_requests_present",
           "node_present", "node_complement", "node_mask", "node_gt", "node_lt", "node_it_state"]
 
@@ -29,7 +24,7 @@ import audit_limits_cases as LC
 ks, kh = S.libs()
 kh.ksh_last_error.restype = ctypes.c_char_p; ks.ks_last_error.restype = ctypes.c_char_p
 PASSES, ARRAYS = json.loads(sys.argv[1])
-OUT = {"audit": S._AuditOut, "topology": S._AuditTopologyOut, "spread": S._AuditSpreadOut, "firstfit": S._AuditFirstFitOut, "limits": S._AuditLimitsOut}
+OUT = {"audit": S._AuditOut, "topology": S._AuditTopologyOut, "spread": S._AuditSpreadOut, "firstfit": S._AuditFirstFitOut, "limits": S._AuditLimitsOut, "hostfit": S._AuditHostFitOut}
 out = {}
 def rec(key, rc, lib=kh):
     out[key] = [int(rc), "" if rc == S.KS_OK else (lib.ksh_last_error() if lib is kh else lib.ks_last_error()).decode()]
@@ -148,13 +143,7 @@ print("RESULT " + json.dumps(out))
 
 @pytest.fixture(scope="module")
 def recorded():
-    env = dict(os.environ)
-    env.pop("KS_TEST_SIM", None); env.pop("KS_NO_RR", None)
-    env["KS_SIM_ALARM"] = "600"
-    pr = subprocess.run([sys.executable, "-c", CHILD % {"root": ROOT, "tests": HERE}, json.dumps([PASSES, ARRAYS])], capture_output=True, text=True, env=env, timeout=1500)
-    line = [l for l in pr.stdout.splitlines() if l.startswith("RESULT ")]
-    assert line, pr.stdout[-2000:] + pr.stderr[-2000:]
-    return json.loads(line[-1][7:])
+    return H.run_emulated(CHILD, [PASSES, ARRAYS])
 
 
 ACCEPTED = (0, "")
@@ -174,24 +163,24 @@ EXPECTED = {
     'claimed/n_unscheduled above P': (-1, 'claimed result: more unscheduled pods than pods'),
     'claimed/null array node_complement': (-1, 'claimed result: null array node_complement'),
     'claimed/null array node_gt': (-1, 'claimed result: null array node_gt'),
-    'claimed/null array node_it_state': {'audit': (-1, 'claimed result: null array node_it_state'), 'topology': ACCEPTED, 'spread': ACCEPTED, 'firstfit': (-1, 'claimed result: null array node_it_state'), 'limits': (-1, 'claimed result: null array node_it_state')},
+    'claimed/null array node_it_state': {'audit': (-1, 'claimed result: null array node_it_state'), 'topology': ACCEPTED, 'spread': ACCEPTED, 'firstfit': (-1, 'claimed result: null array node_it_state'), 'limits': (-1, 'claimed result: null array node_it_state'), 'hostfit': (-1, 'claimed result: null array node_it_state')},
     'claimed/null array node_lt': (-1, 'claimed result: null array node_lt'),
     'claimed/null array node_mask': (-1, 'claimed result: null array node_mask'),
     'claimed/null array node_pods': ACCEPTED,
     'claimed/null array node_pods_off': ACCEPTED,
     'claimed/null array node_present': (-1, 'claimed result: null array node_present'),
-    'claimed/null array node_requests': {'audit': (-1, 'claimed result: null array node_requests'), 'topology': ACCEPTED, 'spread': ACCEPTED, 'firstfit': (-1, 'claimed result: null array node_requests'), 'limits': (-1, 'claimed result: null array node_requests')},
-    'claimed/null array node_requests_present': {'audit': (-1, 'claimed result: null array node_requests_present'), 'topology': ACCEPTED, 'spread': ACCEPTED, 'firstfit': (-1, 'claimed result: null array node_requests_present'), 'limits': (-1, 'claimed result: null array node_requests_present')},
+    'claimed/null array node_requests': {'audit': (-1, 'claimed result: null array node_requests'), 'topology': ACCEPTED, 'spread': ACCEPTED, 'firstfit': (-1, 'claimed result: null array node_requests'), 'limits': (-1, 'claimed result: null array node_requests'), 'hostfit': (-1, 'claimed result: null array node_requests')},
+    'claimed/null array node_requests_present': {'audit': (-1, 'claimed result: null array node_requests_present'), 'topology': ACCEPTED, 'spread': ACCEPTED, 'firstfit': (-1, 'claimed result: null array node_requests_present'), 'limits': (-1, 'claimed result: null array node_requests_present'), 'hostfit': (-1, 'claimed result: null array node_requests_present')},
     'claimed/null array node_tmpl': (-1, 'claimed result: null array node_tmpl'),
-    'claimed/null array node_types': {'audit': (-1, 'claimed result: null array node_types'), 'topology': ACCEPTED, 'spread': ACCEPTED, 'firstfit': (-1, 'claimed result: null array node_types'), 'limits': (-1, 'claimed result: null array node_types')},
+    'claimed/null array node_types': {'audit': (-1, 'claimed result: null array node_types'), 'topology': ACCEPTED, 'spread': ACCEPTED, 'firstfit': (-1, 'claimed result: null array node_types'), 'limits': (-1, 'claimed result: null array node_types'), 'hostfit': (-1, 'claimed result: null array node_types')},
     'claimed/null array pod_node': (-1, 'claimed result: null array'),
     'claimed/null array pod_reason': ACCEPTED,
     'claimed/null array pod_stage': (-1, 'claimed result: null array'),
-    'claimed/null array unscheduled': {'audit': (-1, 'claimed result: null array'), 'topology': ACCEPTED, 'spread': ACCEPTED, 'firstfit': ACCEPTED, 'limits': ACCEPTED},
+    'claimed/null array unscheduled': {'audit': (-1, 'claimed result: null array'), 'topology': ACCEPTED, 'spread': ACCEPTED, 'firstfit': ACCEPTED, 'limits': ACCEPTED, 'hostfit': ACCEPTED},
     'claimed/null claimed': (-1, 'null argument'),
     'claimed/null handle': (-1, 'null argument'),
     'claimed/null node arrays, n_new == 0': ACCEPTED,
-    'claimed/null node table, capacity 1': {'audit': (-1, 'null audit table'), 'topology': None, 'spread': None, 'firstfit': None, 'limits': (-1, 'null audit table')},
+    'claimed/null node table, capacity 1': {'audit': (-1, 'null audit table'), 'topology': None, 'spread': None, 'firstfit': None, 'limits': (-1, 'null audit table'), 'hostfit': None},
     'claimed/null out': (-1, 'null audit table'),
     'claimed/null pod table, capacity 1': (-1, 'null audit table'),
     'claimed/null tables, capacity 0': ACCEPTED,
@@ -219,13 +208,13 @@ EXPECTED = {
     'resident/n == 0': ACCEPTED,
     'resident/n == 0, everything null': ACCEPTED,
     'resident/null handles': (-1, 'null argument'),
-    'resident/null node table, capacity 1': {'audit': (-1, 'null audit table'), 'topology': None, 'spread': None, 'firstfit': None, 'limits': (-1, 'null audit table')},
+    'resident/null node table, capacity 1': {'audit': (-1, 'null audit table'), 'topology': None, 'spread': None, 'firstfit': None, 'limits': (-1, 'null audit table'), 'hostfit': None},
     'resident/null outs': (-1, 'null argument'),
     'resident/null pod table, capacity 1': (-1, 'null audit table'),
     'resident/null tables, capacity 0': ACCEPTED,
     'resident/two at once: null handles and null pod table': (-1, 'null argument'),
     'resident/two at once: null pod table and audit before solve': (-1, 'null audit table'),
-    'claimed/null pod_seq': {'audit': None, 'topology': (-1, 'null argument'), 'spread': (-1, 'null argument'), 'firstfit': (-1, 'null argument'), 'limits': (-1, 'null argument')},
+    'claimed/null pod_seq': {'audit': None, 'topology': (-1, 'null argument'), 'spread': (-1, 'null argument'), 'firstfit': (-1, 'null argument'), 'limits': (-1, 'null argument'), 'hostfit': (-1, 'null argument')},
 }
 
 
@@ -244,12 +233,12 @@ def test_every_refusal_is_the_recorded_one(recorded, what):
 
 
 def test_a_pass_refuses_only_the_arrays_it_reads(recorded):
-    """The first pass reads all fourteen of KS_AUDIT_SEGS (pod_seq is made by the entry point), topology and spread nine, first-fit and limits all but the
+    """The first pass reads all fourteen of KS_AUDIT_SEGS (pod_seq is made by the entry point), topology and spread nine, first-fit, limits and host-fit all but the
     unscheduled list; pod_reason and the node -> pods CSR are read by none.  A null array outside a pass's set is accepted."""
     OK = 0
     node9, node13 = ["node_tmpl", "node_present", "node_complement", "node_mask", "node_gt", "node_lt"], [a for a in ARRAYS if a.startswith("node_") and not a.startswith("node_pods")]
     reads = {"audit": ["pod_node", "pod_stage", "unscheduled"] + node13, "topology": ["pod_node", "pod_stage"] + node9, "spread": ["pod_node", "pod_stage"] + node9,
-             "firstfit": ["pod_node", "pod_stage"] + node13, "limits": ["pod_node", "pod_stage"] + node13}
+             "firstfit": ["pod_node", "pod_stage"] + node13, "limits": ["pod_node", "pod_stage"] + node13, "hostfit": ["pod_node", "pod_stage"] + node13}
     for what in PASSES:
         for a in ARRAYS:
             code = recorded["%s/claimed/null array %s" % (what, a)][0]

@@ -8,21 +8,14 @@ correct result is known, before any GPU run:
   b) the tamper matrix and the kernels' other paths (tests/audit_spread_cases.py) on the emulator;
   c) unit cases of the reference alone on a hand-made problem: one per clause of the rule and per direction.
 Runs the emulator in a subprocess: its build replaces the two libraries for the whole process (tests/simlib.py)."""
-import json
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
+import audit_harness as H
 import audit_ref as A
 import audit_spread_cases as SC
 import audit_spread_ref as SR
 import test_rr_emulated as E
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 
 CHILD = r"""
 import json, sys
@@ -80,22 +73,14 @@ out["shapes"] = [[n, ok if ok is True else str(ok)] for n, ok in SC.run_shapes(S
 print("RESULT " + json.dumps(out))
 """
 
-TOPOLOGY_SETS = [[0, 3], [5], [1, 2, 9], [7, 11], [4, 6, 8, 10, 12], [15]]
-FLAT = ["rr/" + c[0] for c in E.CASES] + ["no_rr/" + c[0] for c in E.CASES] + ["pack/" + c[0] for c in E.PACK_CASES] + ["whatifs/%d" % i for i in range(4)] + \
-       ["wide_whatifs/%d" % i for i in range(len(E.WIDE_SETS))] + ["topology_whatifs/%d" % i for i in range(len(TOPOLOGY_SETS))]
-DERIVED = ["wide_whatifs_derived/%d" % i for i in range(len(E.WIDE_SETS))] + ["topology_whatifs_derived/%d" % i for i in range(len(TOPOLOGY_SETS))]
+TOPOLOGY_SETS = H.WHATIF_SETS
+WHATIFS, FLAT, DERIVED = H.gate_names()
 NAMES = FLAT + DERIVED
 
 
 @pytest.fixture(scope="module")
 def emulated():
-    env = dict(os.environ)
-    env.pop("KS_TEST_SIM", None); env.pop("KS_NO_RR", None)
-    env["KS_SIM_ALARM"] = "600"
-    pr = subprocess.run([sys.executable, "-c", CHILD % {"root": ROOT, "tests": HERE}, json.dumps([E.CASES, E.PACK_CASES]), json.dumps(TOPOLOGY_SETS)], capture_output=True, text=True, env=env, timeout=1500)
-    line = [l for l in pr.stdout.splitlines() if l.startswith("RESULT ")]
-    assert line, pr.stdout[-2000:] + pr.stderr[-2000:]
-    return json.loads(line[-1][7:])
+    return H.run_emulated(CHILD, [E.CASES, E.PACK_CASES], TOPOLOGY_SETS)
 
 
 @pytest.mark.parametrize("name", NAMES)

@@ -6,32 +6,16 @@ against its literal reference (tests/audit_spread_ref.py):
   c) the tamper matrix through the claimed form, the commit numbers read from ksh_placement_rows and edited;
   d) the shapes where the kernels take another path; the same flags every run; the refusals.
 tests/test_audit_spread.py runs the same kernels' source on the emulator."""
-import ctypes
-
-import numpy as np
 import pytest
 
+import audit_harness as H
 import audit_spread_cases as SC
-import audit_spread_ref as SR
-import audit_topo_cases as TC
-import test_fuzz as F
-import test_fuzz_mid as T
-import test_problem_arrays as PA
 from karpenter_core_amd import scheduler as S
 from karpenter_core_amd import workloads as W
 
 pytestmark = pytest.mark.gpu
 
-GENUINE = {
-    "mid (topology, limits)": lambda: T.mid_problem(0),
-    "node filter": lambda: PA.build_case("filter"),
-    "existing nodes": lambda: PA.build_case("r3"),
-    "fuzz 0": lambda: F.fuzz_problem(0), "fuzz 3": lambda: F.fuzz_problem(3), "fuzz 5": lambda: F.fuzz_problem(5), "fuzz 11": lambda: F.fuzz_problem(11), "fuzz 16": lambda: F.fuzz_problem(16),
-    "config3": lambda: W.config3(pods=140, sizes=3, seed=1),
-    "config3, 700 pods": lambda: W.config3(pods=700, sizes=10, seed=7),
-    "a zonal spread on labelled nodes": lambda: SC.zonal(40, plain=3),
-    "two keys": SC.two_keys,
-}
+GENUINE = SC.GENUINE
 CHECKED = {}      # (name, kernel) -> (pairs, exact pairs), filled by the test below and summed by the one after it
 
 
@@ -62,33 +46,11 @@ def test_the_clean_results_were_not_clean_vacuously(no_rr):
 
 
 def test_a_batch_of_derived_whatifs_is_clean():
-    """tests/test_audit_topology_gpu.py's decorated snapshot: the what-ifs flattened one by one are clean by the reference and by the device; the device pass over the
-    batch derived on the device finds the same -- nothing -- over as many placed pods and pairs, as many of them exact."""
-    import test_whatif_derived as WD
-    its, prov, nodes, bound, snap, pod_node = WD._topology_snapshot(24, 5, 11, spare=2, extras=False, anti=True)
-    sets = [[0, 3], [5], [1, 2, 9], [7, 11], [4, 6, 8, 10, 12], [15]]
-    parsed = S.ParsedProblem(snap)
-    flats = S.open_whatifs(parsed, pod_node, sets, derive=False)
-    S.solve_batch(flats, decode=False)
-    plain = [SC.assert_clean(S, f) for f in flats]
-    batch = S.audit_spread_batch(flats)      # the batch form over flattened problems says what one call each said
-    for b, p in zip(batch, plain):
-        assert np.array_equal(b["pod_flags"], p["pod_flags"]) and SC.summary(b) == SC.summary(p)
-    derived = S.open_whatifs(parsed, pod_node, sets, derive=True)
-    S.solve_batch_resident(derived)
-    got = S.audit_spread_batch(derived)
-    assert len(got) == len(sets)
-    for d, p in zip(got, plain):
-        print(SC.summary(d), SC.summary(p))
-        assert not d["pod_flags"].any() and d["n_pods_flagged"] == 0
-        assert len(d["pod_flags"]) == len(p["pod_flags"]) and (d["n_new"], d["n_placed"], d["checked"], d["exact_pairs"]) == (p["n_new"], p["n_placed"], p["checked"], p["exact_pairs"])
-    assert sum(d["checked"]["SPREAD"] for d in got) > 0
-    assert SC.sliced_batch_says_the_same(S, derived, got)
-    with pytest.raises(S.KSolveError) as e:      # a claimed result on a derived view
-        derived[0].audit_spread(claimed=flats[0].result_arrays(), pod_seq=np.zeros(len(plain[0]["pod_flags"]), dtype=np.int32))
-    assert e.value.code == S.KS_ERR_UNSUPPORTED
-    for f in flats + derived:
-        f.close()
+    """tests/audit_harness.py's decorated snapshot: the device pass over the batch derived on the device finds what the what-ifs flattened one by one say -- nothing --
+    over as many placed pods and pairs, as many of them exact."""
+    def sliced(derived, got):
+        assert SC.sliced_batch_says_the_same(S, derived, got)
+    H.derived_whatifs_are_clean(SC.D, S, same=lambda d: (d["n_new"], d["n_placed"], d["checked"], d["exact_pairs"]), examined=lambda d: d["checked"]["SPREAD"], after=sliced)
 
 
 @pytest.fixture(scope="module")
@@ -114,50 +76,11 @@ def test_the_kernels_other_paths(shapes, name):
 
 
 def test_flags_are_the_same_every_run():
-    f = S.FlatProblem(SC.tamper_problem())
-    f.solve(decode=False)
-    name, claimed, seq, want = SC.tampers(f.result_arrays(), f.pod_seq())[1]
-    runs = [f.audit_spread(claimed, seq) for _ in range(3)]
-    assert all(np.array_equal(r["pod_flags"], runs[0]["pod_flags"]) and SC.summary(r) == SC.summary(runs[0]) for r in runs) and runs[0]["n_pods_flagged"] == 2
-    g = S.FlatProblem(W.config3(pods=700, sizes=10, seed=7))      # new nodes: the pin table is built with atomicMin, the chunk table with atomicAdd
-    g.solve(decode=False)
-    runs = [g.audit_spread() for _ in range(3)]
-    assert all(np.array_equal(r["pod_flags"], runs[0]["pod_flags"]) and SC.summary(r) == SC.summary(runs[0]) for r in runs) and runs[0]["checked"]["SPREAD"] > 0
-    f.close(); g.close()
+    first = H.same_flags_every_run(SC.D, S, SC.tamper_problem(), lambda f: SC.tampers(f.result_arrays(), f.pod_seq())[1][1:3])
+    assert first["n_pods_flagged"] == 2
+    first = H.same_flags_every_run(SC.D, S, W.config3(pods=700, sizes=10, seed=7))      # new nodes: the pin table is built with atomicMin, the chunk table with atomicAdd
+    assert first["checked"]["SPREAD"] > 0
 
 
 def test_refusals():
-    ks, kh = S.libs()
-    f = S.FlatProblem(SC.tamper_problem())
-    f.upload(0)
-    with pytest.raises(S.KSolveError) as e:      # nothing solved
-        f.audit_spread()
-    assert e.value.code == S.KS_ERR_INVALID
-    f.solve(decode=False)
-    kh.ksh_audit_spread.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32, ctypes.POINTER(S._AuditSpreadOut), ctypes.POINTER(ctypes.c_double)]
-    hs = (ctypes.c_void_p * 1)(f._h)
-    out = (S._AuditSpreadOut * 1)()
-    out[0].cap_pods, out[0].pod_flags = 64, None      # a table promised and not given
-    assert kh.ksh_audit_spread(hs, 1, out, None) == S.KS_ERR_INVALID
-    assert kh.ksh_audit_spread(hs, 1, None, None) == S.KS_ERR_INVALID
-    assert kh.ksh_audit_spread(None, 1, out, None) == S.KS_ERR_INVALID
-    out[0].cap_pods = 0      # the totals alone: no table needed
-    assert kh.ksh_audit_spread(hs, 1, out, None) == S.KS_OK and out[0].n_pods == f.dims["P"] and out[0].truncated == S.KSH_AUDIT_TRUNCATED_PODS and out[0].checked[0] == f.dims["P"]
-    ks.ks_audit_spread_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-    assert ks.ks_audit_spread_dev(None, None, None) == S.KS_ERR_INVALID
-    ks.ks_audit_spread_batch_dev.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]
-    assert ks.ks_audit_spread_batch_dev(None, 1, None) == S.KS_ERR_INVALID
-    res, seq = f.result_arrays(), f.pod_seq()
-    many = dict(res, n_new=f.dims["P"] + 1)      # more new nodes than max_new_nodes
-    with pytest.raises(S.KSolveError) as e:
-        f.audit_spread(claimed=many, pod_seq=seq)
-    assert e.value.code == S.KS_ERR_INVALID
-    with pytest.raises(S.KSolveError) as e:      # no commit numbers
-        f.audit_spread(claimed=res)
-    assert e.value.code == S.KS_ERR_INVALID
-    kh.ksh_audit_spread_claimed.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(S._AuditSpreadOut), ctypes.POINTER(ctypes.c_double)]
-    assert kh.ksh_audit_spread_claimed(f._h, None, seq.ctypes.data, out, None) == S.KS_ERR_INVALID
-    ra = S._ResultArrays()      # the right dimensions and no arrays
-    ra.n_pods, ra.n_existing, ra.types_words, ra.n_resources, ra.n_keys = f.dims["P"], f.dims["E"], (f.dims["T"] + 63) // 64, f.dims["R"], f.dims["K"]
-    assert kh.ksh_audit_spread_claimed(f._h, ctypes.byref(ra), seq.ctypes.data, out, None) == S.KS_ERR_INVALID
-    f.close()
+    H.refusals(SC.D, S, SC.tamper_problem())

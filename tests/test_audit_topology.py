@@ -19,6 +19,7 @@ import tempfile
 import numpy as np
 import pytest
 
+import audit_harness as H
 import audit_ref as A
 import audit_topo_cases as TC
 import audit_topo_ref as TR
@@ -34,7 +35,7 @@ import simlib
 S = simlib.use_sim()
 import numpy as np
 from karpenter_core_amd import workloads as W
-import audit_topo_ref as TR, audit_topo_cases as TC
+import audit_harness as H, audit_topo_ref as TR, audit_topo_cases as TC
 import test_fuzz_mid as T, test_fuzz_rr as R, test_rr_emulated as E, test_wide_resources as WR
 out = {}
 def bits(flags):
@@ -44,7 +45,7 @@ def audited(name, f):
     try:
         dev = f.audit_topology()
         prob = TR.problem_arrays(S, f)
-        seq = TC.commit_numbers(S, f, prob)
+        seq = H.commit_numbers(S, f, prob)
         flags, checked, skipped = TR.audit(prob, f.result_arrays(), seq)
         out[name] = {"pods": bits(flags), "checked": checked, "skipped": skipped, "E": f.dims["E"], "seq": [int(x) for x in seq],
                      "device_agrees": bool(np.array_equal(flags, dev["pod_flags"]) and dev["checked"] == dict(zip(TR.RULES, checked)) and dev["skipped_groups"] == skipped)}
@@ -95,13 +96,7 @@ SHAPES = ["leaders and followers", "a key of 64 values", "24 groups", "P = 1", "
 
 @pytest.fixture(scope="module")
 def emulated():
-    env = dict(os.environ)
-    env.pop("KS_TEST_SIM", None); env.pop("KS_NO_RR", None)
-    env["KS_SIM_ALARM"] = "600"
-    pr = subprocess.run([sys.executable, "-c", CHILD % {"root": ROOT, "tests": HERE}, json.dumps([E.CASES, E.PACK_CASES, ORDER_CASES])], capture_output=True, text=True, env=env, timeout=1500)
-    line = [l for l in pr.stdout.splitlines() if l.startswith("RESULT ")]
-    assert line, pr.stdout[-2000:] + pr.stderr[-2000:]
-    return json.loads(line[-1][7:])
+    return H.run_emulated(CHILD, [E.CASES, E.PACK_CASES, ORDER_CASES])
 
 
 @pytest.mark.parametrize("name", NAMES)

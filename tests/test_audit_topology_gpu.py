@@ -6,11 +6,10 @@ karpenter_core_amd/csrc/ks_audit_topo.inc) against its literal reference (tests/
   c) the tamper matrix (tests/audit_topo_cases.py) through the claimed form, the commit numbers read from ksh_placement_rows and edited;
   d) the shapes where the kernels take another path; the same flags every run; the refusals.
 tests/test_audit_topology.py runs the same kernels' source on the emulator."""
-import ctypes
-
 import numpy as np
 import pytest
 
+import audit_harness as H
 import audit_topo_cases as TC
 import audit_topo_ref as TR
 import test_fuzz as F
@@ -62,39 +61,10 @@ def test_the_clean_results_were_not_clean_vacuously(no_rr):
     assert generators["ANTI_AFFINITY"] > 0 and generators["HOSTNAME_SPREAD"] > 0, generators
 
 
-def derived_batch_is_clean(S):
-    """tests/test_audit_gpu.py's snapshot shape, its bound pods carrying terms (tests/test_whatif_derived.py's decoration: spread, affinity, required anti-affinity
-    over the hostname and the zone): the what-ifs flattened one by one are clean by the reference and by the device; the device pass over the batch derived on the
-    device -- one launch sequence over the results where they lie, the what-ifs' own group tables -- finds the same: nothing, over as many placed pods."""
-    import test_whatif_derived as WD
-    its, prov, nodes, bound, snap, pod_node = WD._topology_snapshot(24, 5, 11, spare=2, extras=False, anti=True)
-    sets = [[0, 3], [5], [1, 2, 9], [7, 11], [4, 6, 8, 10, 12], [15]]
-    parsed = S.ParsedProblem(snap)
-    flats = S.open_whatifs(parsed, pod_node, sets, derive=False)
-    S.solve_batch(flats, decode=False)
-    plain = [TC.assert_clean(S, f) for f in flats]
-    batch = S.audit_topology_batch(flats)      # the batch form over flattened problems says what one call each said
-    for b, p in zip(batch, plain):
-        assert np.array_equal(b["pod_flags"], p["pod_flags"]) and b["checked"] == p["checked"] and b["skipped_groups"] == p["skipped_groups"]
-    derived = S.open_whatifs(parsed, pod_node, sets, derive=True)
-    S.solve_batch_resident(derived)
-    got = S.audit_topology_batch(derived)
-    assert len(got) == len(sets)
-    for d, p in zip(got, plain):
-        print(d["checked"], p["checked"], d["skipped_groups"], p["skipped_groups"])
-        assert not d["pod_flags"].any() and d["n_pods_flagged"] == 0
-        # comparable: the pods, where they went, what each rule evaluated (the groups are the snapshot's in a derived what-if: the skipped ones are not)
-        assert len(d["pod_flags"]) == len(p["pod_flags"]) and d["n_new"] == p["n_new"] and d["n_placed"] == p["n_placed"] and d["checked"] == p["checked"]
-    assert sum(sum(d["checked"][k] for k in TR.RULES[1:]) for d in got) > 0 and sum(sum(p["checked"][k] for k in TR.RULES[1:]) for p in plain) > 0
-    with pytest.raises(S.KSolveError) as e:      # a claimed result on a derived view
-        derived[0].audit_topology(claimed=flats[0].result_arrays(), pod_seq=np.zeros(len(plain[0]["pod_flags"]), dtype=np.int32))
-    assert e.value.code == S.KS_ERR_UNSUPPORTED
-    for f in flats + derived:
-        f.close()
-
-
 def test_a_batch_of_derived_whatifs_is_clean():
-    derived_batch_is_clean(S)
+    """tests/audit_harness.py's decorated snapshot: the device pass over the batch derived on the device -- the what-ifs' own group tables -- finds what the what-ifs
+    flattened one by one say, nothing, over as many placed pods and what each rule evaluated (the groups are the snapshot's in a derived what-if: the skipped ones are not)."""
+    H.derived_whatifs_are_clean(TC.D, S, same=lambda d: (d["n_new"], d["n_placed"], d["checked"]), examined=lambda d: sum(d["checked"][k] for k in TR.RULES[1:]))
 
 
 @pytest.fixture(scope="module")
@@ -147,50 +117,11 @@ def test_nothing_to_check(name, make, checked, n_new):
 
 
 def test_flags_are_the_same_every_run():
-    f = S.FlatProblem(TC.tamper_problem())
-    f.solve(decode=False)
-    name, claimed, seq, want = TC.tampers(f.result_arrays(), f.pod_seq())[4]      # the narrow-key rule: the table of least commit numbers is built with atomicMin
-    runs = [f.audit_topology(claimed, seq) for _ in range(3)]
-    assert all(np.array_equal(r["pod_flags"], runs[0]["pod_flags"]) and r["checked"] == runs[0]["checked"] for r in runs) and runs[0]["n_pods_flagged"] == 1
-    g = S.FlatProblem(T.mid_problem(0))
-    g.solve(decode=False)
-    runs = [g.audit_topology() for _ in range(3)]
-    assert all(np.array_equal(r["pod_flags"], runs[0]["pod_flags"]) and r["checked"] == runs[0]["checked"] for r in runs)
-    f.close(); g.close()
+    # the narrow-key rule: the table of least commit numbers is built with atomicMin
+    first = H.same_flags_every_run(TC.D, S, TC.tamper_problem(), lambda f: TC.tampers(f.result_arrays(), f.pod_seq())[4][1:3])
+    assert first["n_pods_flagged"] == 1
+    H.same_flags_every_run(TC.D, S, T.mid_problem(0))
 
 
 def test_refusals():
-    ks, kh = S.libs()
-    f = S.FlatProblem(TC.tamper_problem())
-    f.upload(0)
-    with pytest.raises(S.KSolveError) as e:      # nothing solved
-        f.audit_topology()
-    assert e.value.code == S.KS_ERR_INVALID
-    f.solve(decode=False)
-    kh.ksh_audit_topology.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32, ctypes.POINTER(S._AuditTopologyOut), ctypes.POINTER(ctypes.c_double)]
-    hs = (ctypes.c_void_p * 1)(f._h)
-    out = (S._AuditTopologyOut * 1)()
-    out[0].cap_pods, out[0].pod_flags = 64, None      # a table promised and not given
-    assert kh.ksh_audit_topology(hs, 1, out, None) == S.KS_ERR_INVALID
-    assert kh.ksh_audit_topology(hs, 1, None, None) == S.KS_ERR_INVALID
-    assert kh.ksh_audit_topology(None, 1, out, None) == S.KS_ERR_INVALID
-    out[0].cap_pods = 0      # the totals alone: no table needed
-    assert kh.ksh_audit_topology(hs, 1, out, None) == S.KS_OK and out[0].n_pods == f.dims["P"] and out[0].truncated == S.KSH_AUDIT_TRUNCATED_PODS and out[0].checked[0] == f.dims["P"]
-    ks.ks_audit_topology_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-    assert ks.ks_audit_topology_dev(None, None, None) == S.KS_ERR_INVALID
-    ks.ks_audit_topology_batch_dev.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]
-    assert ks.ks_audit_topology_batch_dev(None, 1, None) == S.KS_ERR_INVALID
-    res, seq = f.result_arrays(), f.pod_seq()
-    many = dict(res, n_new=f.dims["P"] + 1)      # more new nodes than max_new_nodes
-    with pytest.raises(S.KSolveError) as e:
-        f.audit_topology(claimed=many, pod_seq=seq)
-    assert e.value.code == S.KS_ERR_INVALID
-    with pytest.raises(S.KSolveError) as e:      # no commit numbers
-        f.audit_topology(claimed=res)
-    assert e.value.code == S.KS_ERR_INVALID
-    kh.ksh_audit_topology_claimed.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(S._AuditTopologyOut), ctypes.POINTER(ctypes.c_double)]
-    assert kh.ksh_audit_topology_claimed(f._h, None, seq.ctypes.data, out, None) == S.KS_ERR_INVALID
-    ra = S._ResultArrays()      # the right dimensions and no arrays
-    ra.n_pods, ra.n_existing, ra.types_words, ra.n_resources, ra.n_keys = f.dims["P"], f.dims["E"], (f.dims["T"] + 63) // 64, f.dims["R"], f.dims["K"]
-    assert kh.ksh_audit_topology_claimed(f._h, ctypes.byref(ra), seq.ctypes.data, out, None) == S.KS_ERR_INVALID
-    f.close()
+    H.refusals(TC.D, S, TC.tamper_problem())

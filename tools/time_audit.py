@@ -1,37 +1,63 @@
 #!/usr/bin/env python3
-"""The audit (ksolve.h ks_audit_dev / ks_audit_batch_dev) beside the Solve it audits: its kernel and read-back time next to the pack kernel time of the same Solve on
-the same box, and whether it found anything.  Needs a GPU.
-   usage: tools/time_audit.py [legs, comma separated] [reps]      (defaults: config3,whatifs,config5 9)
-   legs   config3       BASELINE configs[2]: 100 000 pods / 2 000 types (workloads.config3 seed 44) -- bench.py's contract workload
-          whatifs       BASELINE configs[3]: 512 what-ifs derived on the device over the 2 048-node snapshot, audited as ONE batch where their results lie
-          config5       BASELINE configs[4]'s generator at 250 000 pods / 5 000 types
-          config5_full  the same at the stated 1 000 000 pods (minutes of generation; not part of the default)
-Per leg: the Solve once (its pack kernel time as the library reports it), then the audit `reps` times over the same resident result: median with min and max of the
-kernels' lap (inputs up, four launches, completion) and of the read-back lap (the flag words to the host and the totals), milliseconds."""
+"""Passes of the audit (ksolve.h ks_audit*_dev / ks_audit*_batch_dev) beside the Solve they audit: kernel and read-back time of each on the same resident result in the
+same run on the same box next to the pack kernel time of that Solve, what each pass examined -- `checked` by name and every counter it returns --, and whether it found
+anything.  Needs a GPU.
+   usage: tools/time_audit.py <pass>[,<pass>] [legs, comma separated] [reps]      (defaults: config3,whatifs,config5 9)
+   pass   audit | topology | spread | firstfit | limits | hostfit (scheduler._AUDIT_PASSES); the first one named is the subject, the others are timed beside it
+          (hostfit,firstfit: the sixth pass beside the fourth, with the cost per evaluated pair of each)
+   legs   config3       BASELINE configs[2]: 100 000 pods / 2 000 types (workloads.config3 seed 44) -- bench.py's contract workload; no limited template
+          whatifs       512 what-ifs derived on the device over a 2 048-node snapshot, audited as ONE batch where their results lie.  For `audit` BASELINE configs[3]'s
+                        snapshot; for the later passes config #4b's shape with topology, the bound pods carrying spread / affinity / anti-affinity terms
+                        (tests/test_whatif_derived.py's generator); for `limits` that snapshot's provisioner limited to the cpu its nodes hold
+          config5       BASELINE configs[4]'s generator at 250 000 pods / 5 000 types: its `high` provisioner carries a cpu limit
+          config5low    the same with that limit divided by eight (for the case that the limit as generated never excludes a type)
+          config5_full  config5 at the stated 1 000 000 pods (minutes of generation; not part of the default)
+Per leg: the Solve (its pack kernel time as the library reports it), one untimed call of each pass, then each pass `reps` times: median with min and max of the
+kernels' lap (inputs up, the launches, completion) and of the read-back lap (the flag words to the host and the totals), milliseconds."""
 import os, statistics, sys, time
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from karpenter_core_amd import scheduler as S, workloads as W
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
+from karpenter_core_amd import fake, scheduler as S, workloads as W
 
-legs = (sys.argv[1] if len(sys.argv) > 1 else "config3,whatifs,config5").split(",")
-reps = int(sys.argv[2]) if len(sys.argv) > 2 else 9
+if len(sys.argv) < 2 or not all(p in S._AUDIT_PASSES for p in sys.argv[1].split(",")):
+    sys.exit(__doc__)
+passes = sys.argv[1].split(",")
+legs = (sys.argv[2] if len(sys.argv) > 2 else "config3,whatifs,config5").split(",")
+reps = int(sys.argv[3]) if len(sys.argv) > 3 else 9
 if S.device_count() < 1:
     sys.exit("time_audit.py needs a gfx950 device: there is no CPU path to time")
+SIZES = ("n_new", "n_placed", "n_unscheduled")      # (of the result, not of what a pass examined: in the leg's first line)
 
 
 def stat(xs):
     return f"{statistics.median(xs):9.3f} ms (min {min(xs):.3f}, max {max(xs):.3f})"
 
 
-def findings(audits):
-    pods, nodes = sum(a["n_pods_flagged"] for a in audits), sum(a["n_nodes_flagged"] for a in audits)
-    if not pods and not nodes:
-        return "clean"
-    bits = {}
-    for a in audits:
-        for k, v in list(a["pod_bit_count"].items()) + list(a["node_bit_count"].items()):
-            if v:
-                bits[k] = bits.get(k, 0) + v
-    return f"FLAGGED: {pods} pods, {nodes} nodes {bits}"
+def timed(call):
+    """[reps] results of `call` -- each a list of per-problem dicts of one batch, the timings the batch's in every member -- after one untimed"""
+    return [call() for _ in range(reps + 1)][1:]
+
+
+def report(pack_ms, runs):
+    """runs: {pass: timed()}"""
+    per_pair = {}
+    for what, laps in runs.items():
+        p, last = S._AUDIT_PASSES[what], laps[-1]
+        kernels, both = statistics.median(l[0]["ms"][0] for l in laps), statistics.median(sum(l[0]["ms"]) for l in laps)
+        print(f"   {what} kernels   {stat([l[0]['ms'][0] for l in laps])}")
+        print(f"   {what} read-back {stat([l[0]['ms'][1] for l in laps])}")
+        print(f"   {what} / pack kernel: kernels {kernels / pack_ms * 100:.2f} %, kernels + read-back {both / pack_ms * 100:.2f} %")
+        checked = {k: sum(a["checked"][k] for a in last) for k in p["checked"] or ()}
+        counters = {k: sum(a[k] for a in last) for k in p["scalars"] if k not in SIZES}
+        if checked or counters:
+            print(f"   {what}: checked {checked}; " + "; ".join(f"{k} {v}" for k, v in counters.items()))
+        if checked.get("PAIRS"):
+            per_pair[what] = kernels * 1e6 / checked["PAIRS"]
+        flagged = {k: sum(a[t][k] for a in last) for t, bits in (("pod_bit_count", p["pod_bits"]), ("node_bit_count", p["node_bits"] or {})) for k in bits}
+        print(f"   result: {what} {'clean (nothing flagged)' if not any(flagged.values()) else 'FLAGGED %s' % {k: v for k, v in flagged.items() if v}}", flush=True)
+    if len(per_pair) > 1:      # (passes that count (class, node) pairs, side by side)
+        first = next(iter(per_pair.values()))
+        print("   per evaluated pair: " + ", ".join(f"{w} {ns:.3f} ns" for w, ns in per_pair.items()) + "".join(f"; {passes[0]} / {w} {first / ns:.2f}" for w, ns in list(per_pair.items())[1:]), flush=True)
 
 
 def single(name, problem):
@@ -43,39 +69,56 @@ def single(name, problem):
     pack_ms, wall_ms = f.kernel_ms, f.wall_ms
     f.solve(decode=False)      # (the second Solve of a resident problem: tables built, kernels loaded)
     pack_ms = min(pack_ms, f.kernel_ms)
-    laps = [f.audit() for _ in range(reps + 1)][1:]
-    d = f.dims
-    print(f"{name}: {d['P']} pods, {d['T']} types, {d['E']} existing nodes; {laps[0]['n_new']} new nodes, {laps[0]['n_unscheduled']} unscheduled; ks_pack_rr {f.rr_status()}", flush=True)
+    runs = {what: timed(lambda: S._audit(what, [f])) for what in passes}
+    d, first = f.dims, runs[passes[0]][0][0]
+    print(f"{name}: {d['P']} pods, {d['T']} types, {d['E']} existing nodes, {d['C']} classes, {d['M']} templates, {d['G']} topology groups ({d['GH']} on the hostname); "
+          + ", ".join(f"{k} {first[k]}" for k in SIZES if k in first) + f"; ks_pack_rr {f.rr_status()}", flush=True)
     print(f"   flatten + upload {(t1 - t0) * 1e3:.0f} ms; pack kernel {pack_ms:.2f} ms (Solve wall {wall_ms:.2f} ms)")
-    print(f"   audit kernels  {stat([a['ms'][0] for a in laps])}")
-    print(f"   audit read-back {stat([a['ms'][1] for a in laps])}")
-    print(f"   audit / pack kernel: {statistics.median(a['ms'][0] for a in laps) / pack_ms * 100:.2f} %;  result: {findings(laps[-1:])}", flush=True)
+    report(pack_ms, runs)
     f.close()
+
+
+def whatifs():
+    if passes[0] == "audit":
+        its, prov, nodes, bound = W.cluster_snapshot(2048, 50, 45)
+        snap, pod_node = W.snapshot_problem(its, prov, nodes, bound, False)
+        name = "BASELINE configs[3]"
+    else:
+        from test_whatif_derived import _topology_snapshot      # (the generator of the differential tests)
+        its, prov, nodes, bound, snap, pod_node = _topology_snapshot(2048, 50, 45, spare=-1, extras=True, anti=True)
+        name = "config #4b with topology"
+        if passes[0] == "limits":
+            limit = {"cpu": str(int(sum(fake._qty_value(n.capacity.get("cpu", "0")) for n in nodes)))}
+            for p in snap.provisioners:
+                p.limits = dict(limit)
+            name += f", provisioner limited to {limit}"
+    flats = S.open_whatifs(S.ParsedProblem(snap), pod_node, W.config4_sets(512, 2048, 45), derive=True)
+    S.solve_batch_resident(flats)
+    pack_ms, _ = S.solve_batch_resident(flats)
+    runs = {what: timed(lambda: S._audit(what, flats)) for what in passes}
+    first = runs[passes[0]][0]
+    print(f"{name}: {len(flats)} what-ifs derived on the device over {len(nodes)} nodes / {len(its)} types; {sum(len(a['pod_flags']) for a in first)} pods, "
+          f"{sum(a['n_new'] for a in first)} new nodes in all", flush=True)
+    print(f"   pack kernel (one batched launch) {pack_ms:.2f} ms")
+    report(pack_ms, runs)
+    for f in flats:
+        f.close()
 
 
 for leg in legs:
     print(f"--- {leg} (generating) ---", flush=True)
     if leg == "config3":
         single("BASELINE configs[2]", W.config3(pods=100_000, sizes=50, seed=44))
-    elif leg == "config5":
-        single("BASELINE configs[4] at 250 000 pods", W.config5(pods=250_000, sizes=50, seed=46))
+    elif leg in ("config5", "config5low"):
+        pr = W.config5(pods=250_000, sizes=50, seed=46)
+        for p in pr.provisioners:
+            if p.limits and leg == "config5low":
+                p.limits = {k: str(int(fake._qty_value(v)) // 8) for k, v in p.limits.items()}
+        print("   limits: " + ", ".join(f"{p.name} {p.limits}" for p in pr.provisioners))
+        single("BASELINE configs[4] at 250 000 pods" + (", the limit divided by eight" if leg == "config5low" else ""), pr)
     elif leg == "config5_full":
         single("BASELINE configs[4] at the stated 1 000 000 pods", W.config5(pods=1_000_000, sizes=50, seed=46))
     elif leg == "whatifs":
-        its, prov, nodes, bound = W.cluster_snapshot(2048, 50, 45)
-        snap, pod_node = W.snapshot_problem(its, prov, nodes, bound, False)
-        parsed, sets = S.ParsedProblem(snap), W.config4_sets(512, 2048, 45)
-        flats = S.open_whatifs(parsed, pod_node, sets, derive=True)
-        S.solve_batch_resident(flats)
-        pack_ms, _ = S.solve_batch_resident(flats)
-        laps = [S.audit_batch(flats) for _ in range(reps + 1)][1:]
-        pods = sum(len(a["pod_flags"]) for a in laps[0])
-        print(f"BASELINE configs[3]: {len(flats)} what-ifs derived on the device over {len(nodes)} nodes / {len(its)} types; {pods} pods, {sum(a['n_new'] for a in laps[0])} new nodes in all", flush=True)
-        print(f"   pack kernel (one batched launch) {pack_ms:.2f} ms")
-        print(f"   audit kernels  {stat([l[0]['ms'][0] for l in laps])}")
-        print(f"   audit read-back {stat([l[0]['ms'][1] for l in laps])}")
-        print(f"   audit / pack kernel: {statistics.median(l[0]['ms'][0] for l in laps) / pack_ms * 100:.2f} %;  result: {findings(laps[-1])}", flush=True)
-        for f in flats:
-            f.close()
+        whatifs()
     else:
         sys.exit(f"unknown leg {leg}")
