@@ -634,6 +634,25 @@ typedef struct ksh_audit_hostfit_out {
 int ksh_audit_hostfit(void** handles, uint32_t n, ksh_audit_hostfit_out* outs /* [n] */, double* ms /* [2] kernels | read-back, or NULL */);
 /* A claimed result for one flattened handle, exactly as ksh_audit_firstfit_claimed takes it. */
 int ksh_audit_hostfit_claimed(void* handle, const ksh_result_arrays* claimed, const int32_t* pod_seq /* [n_pods] */, ksh_audit_hostfit_out* out, double* ms /* [2] or NULL */);
+/* The GATE (ksolve.h ks_audit_gate_dev, KS_AUDIT_PASS_*): the passes of a mask in ONE call, their totals and a list of findings reduced on the device.  This is the
+ * shim's gate: one call behind every result, and on a finding, solve in Go; the per-pass calls above remain the way to the flag rows.  No flag row is read back: for
+ * every requested pass the caller gives an array of n of that pass's out structs and receives in each exactly the totals the pass's own call writes -- the tables and
+ * their capacities are neither read nor written, truncated is 0 -- and the passes that are not requested are not looked at.  findings: ks_audit_finding records
+ * (problem = the handle's position in the batch | pass << 8 | table | index | flag word), ordered by pass, problem, pods before nodes, index -- the same list every
+ * run.  n_findings is always the full count; with more than cap_findings of them the first cap_findings are written, KS_AUDIT_GATE_TRUNCATED is set and the table
+ * beyond them is untouched.  cap_findings == 0 with findings == NULL is the plain yes/no gate: the results are clean iff n_findings == 0.
+ * Refusals (nothing launched, nothing written): KS_ERR_INVALID for a mask that is empty or names an unknown pass, for findings == NULL with cap_findings != 0, for a
+ * requested pass without its array; then the requested passes' own refusals, the earliest pass of the mask first. */
+typedef struct ksh_audit_gate_out {
+  ks_audit_finding* findings; uint64_t cap_findings;
+  ksh_audit_out* audit; ksh_audit_topology_out* topology; ksh_audit_spread_out* spread; ksh_audit_firstfit_out* firstfit; ksh_audit_limits_out* limits; ksh_audit_hostfit_out* hostfit;   /* [n] each, for the requested passes */
+  uint32_t n_findings, truncated /* KS_AUDIT_GATE_TRUNCATED */;
+} ksh_audit_gate_out;
+int ksh_audit_gate(void** handles, uint32_t n, uint32_t passes /* KS_AUDIT_PASS_* */, ksh_audit_gate_out* out, double* ms /* [2] kernels | read-back, or NULL */);
+/* A claimed result for one flattened handle through the gate: taken once and uploaded once, with the union of the arrays the requested passes read.  pod_seq as
+ * ksh_audit_topology_claimed takes it -- it may be NULL only when KS_AUDIT_PASS_FIRST is the whole mask; the first pass reads the placed pods numbered in pod order,
+ * as ksh_audit_claimed gives them to it, whatever pod_seq says.  out's arrays hold one struct each. */
+int ksh_audit_gate_claimed(void* handle, const ksh_result_arrays* claimed, const int32_t* pod_seq /* [n_pods] */, uint32_t passes, ksh_audit_gate_out* out, double* ms /* [2] or NULL */);
 
 /* ---- the snapshot kept current by EVENTS ("cached incremental SoA builder fed from state.Cluster") ----
  * Replaces, for the snapshot consolidation simulates over, what the reference does between two passes of the deprovisioner (deprovisioning/controller.go:64,

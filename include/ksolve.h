@@ -943,6 +943,54 @@ typedef struct ks_audit_hostfit {
 int ks_audit_hostfit_dev(ks_dev_problem* d, const ks_result* claimed /* or NULL; pod_seq is read */, ks_audit_hostfit* out);
 int ks_audit_hostfit_batch_dev(ks_dev_problem* const* ds, uint32_t n, ks_audit_hostfit* const* outs);
 
+/* ---- the audit's GATE: chosen passes in ONE call, their totals and a list of FINDINGS reduced on the device.  The question a caller puts behind every result is
+ * "is it clean?", and the answer is usually yes: the gate runs the chosen passes' own kernels, leaves their flag tables on the device, tallies them there and reads
+ * back the totals alone -- no row of a flag table reaches the host.  The six passes and their entry points above are unchanged by it; they remain the way to the rows.
+ * Every requested pass's out struct receives exactly what that pass's own entry point writes into it -- every count, bit count, `checked` entry and counter -- but
+ * for its tables, which are neither read nor written (the pointers may be anything), and its two times, which are that pass's share of the gate's.
+ * FINDINGS: one record per non-zero flag word, ordered by pass (the order of the mask bits), then by problem, then pods before nodes, then by index.  The order comes
+ * from a scan on the device, not from an atomic append: the list is the same every run.  n_findings is always the full count; when it exceeds cap_findings the first
+ * cap_findings records are written, KS_AUDIT_GATE_TRUNCATED is set and the table beyond them is untouched.  cap_findings == 0 with findings == NULL is the plain
+ * yes/no gate: clean iff n_findings == 0. */
+#define KS_AUDIT_PASS_FIRST 1u       /* ks_audit_dev */
+#define KS_AUDIT_PASS_TOPOLOGY 2u    /* ks_audit_topology_dev */
+#define KS_AUDIT_PASS_SPREAD 4u      /* ks_audit_spread_dev */
+#define KS_AUDIT_PASS_FIRSTFIT 8u    /* ks_audit_firstfit_dev */
+#define KS_AUDIT_PASS_LIMITS 16u     /* ks_audit_limits_dev */
+#define KS_AUDIT_PASS_HOSTFIT 32u    /* ks_audit_hostfit_dev */
+#define KS_AUDIT_PASS_ALL 63u
+#define KS_AUDIT_GATE_TRUNCATED 1u
+typedef struct ks_audit_finding {
+  uint32_t problem;               /* the problem's position in the batch (0 for the single form) */
+  uint32_t where;                 /* pass << 8 | table: pass = the index of its mask bit (0 first .. 5 hostfit), table 0 = pod_flags, 1 = node_flags */
+  uint32_t index;                 /* the pod, or the node slot */
+  uint32_t flags;                 /* the flag word, as the pass's own table holds it */
+} ks_audit_finding;
+typedef struct ks_audit_gate {
+  uint32_t passes;                /* in: KS_AUDIT_PASS_*, at least one */
+  uint32_t cap_findings;          /* in: records `findings` holds */
+  ks_audit_finding* findings;     /* in: the caller's table, or NULL with cap_findings == 0 */
+  ks_audit* first; ks_audit_topology* topology; ks_audit_spread* spread; ks_audit_firstfit* firstfit; ks_audit_limits* limits; ks_audit_hostfit* hostfit;
+                                  /* in: for every requested pass an array of one out struct per problem (the others are not looked at) */
+  const int32_t* first_pod_seq;   /* in, claimed form only: the commit numbers the FIRST pass is to read instead of claimed->pod_seq, or NULL (kshost's claimed form
+                                   * numbers the placed pods in pod order for it, as ksh_audit_claimed does, while the later passes read the caller's) */
+  uint32_t n_findings, truncated; /* out: the non-zero flag words of all requested passes | KS_AUDIT_GATE_TRUNCATED */
+  double kernel_ms, readback_ms;  /* out: the sums of the passes' times: uploads, launches (the reduction's among them) and completion | the totals' and the findings' way back */
+} ks_audit_gate;
+/* ks_audit_gate_dev: one problem -- the resident result (claimed == NULL) or the caller's arrays, taken once and uploaded once with the union of the arrays the
+ * requested passes read.  ks_audit_gate_batch_dev: the resident results of a batch.  Refusals (nothing launched, no out struct written): nothing runs unless every
+ * requested pass accepts the call; the refusals are the passes' own, code and text, and where two apply the earliest pass in the mask wins.  The gate's own, before
+ * them: KS_ERR_INVALID for an empty mask, for a bit outside KS_AUDIT_PASS_ALL, and for findings == NULL with cap_findings != 0.  A sliced pass (topology, spread,
+ * hostfit) reduces per slice; slices are consecutive runs of problems, so the findings keep their order. */
+int ks_audit_gate_dev(ks_dev_problem* d, const ks_result* claimed /* or NULL */, ks_audit_gate* gate);
+int ks_audit_gate_batch_dev(ks_dev_problem* const* ds, uint32_t n, ks_audit_gate* gate);
+/* The gate's reduction over any table of words, so that its kernels can be tested apart from the passes: `rows` [n] (host memory) is uploaded to `device` and tallied
+ * there both ways -- as a flag table (rows set, bit counts) and as a table of checked words with up to four bit fields (field_sum[i] = the sum of
+ * (row >> shift[i]) & mask[i]).  All sums are modulo 2^32, as the totals' are. */
+typedef struct ks_audit_fields { uint32_t n_fields; uint32_t shift[4], mask[4]; } ks_audit_fields;   /* n_fields <= 4, shift < 32 */
+typedef struct ks_audit_row_totals { uint32_t n_set; uint32_t bit_count[32]; uint32_t field_sum[4]; } ks_audit_row_totals;
+int ks_audit_reduce_rows(int device, const uint32_t* rows, uint32_t n, const ks_audit_fields* fields /* or NULL: none */, ks_audit_row_totals* out);
+
 /* ---- consolidation CANDIDATES, selected and ordered on the device (deprovisioning/helpers.go:124-165,275-287 GetPodEvictionCost / disruptionCost /
  * calculateLifetimeRemaining, pdblimits.go:57-70 CanEvictPods, helpers.go:339-366 canBeTerminated / PodsPreventEviction, consolidation.go:83-104 the sort).
  * Flat arrays in, flat arrays out; three kernels (per pod, per node, rank), no host fallback.

@@ -250,10 +250,13 @@ __global__ __launch_bounds__(256) void ks_audit_nodes(const DevProb* probs, cons
   }
 }
 
+#include "ks_audit_reduce.inc"      // the gate's kernels over the passes' flag tables: after aud_block_sum and ks_audit_scan, which they build on, and before the host half, whose tail launches them
+
 // ---- host half ----
 // The host path of all five passes.  A pass's own file keeps what is its own -- its view struct, the carve-up of its scratch, its launch list, the decoding of its
 // meta and checked words -- and calls the plain functions below for the rest: the claimed upload, the resident prelude, the pooled work block, the launch rows, the
-// wait and the two times, the flag tallies, the walk in slices.
+// wait and the two times, the flag tallies, the walk in slices, and the tail behind the launches -- the read-back and the host's counts for a pass's own entry points, the
+// reduction on the device for the gate (ksolve.h ks_audit_gate_dev), whose entry points close this file.
 // what the audit reads of a result: KS_RESULT_SEGS without the per-pod reasons.  Each entry has a bit (its place here); a pass names the set it reads as a mask
 #define KS_AUDIT_SEGS(X) \
   X(pod_node, pod_node, i32, P) X(pod_stage, pod_stage, i32, P) X(pod_seq, pod_seq, i32, P) X(unscheduled, unscheduled, i32, P) \
@@ -281,49 +284,70 @@ static AuditView audit_resident(const DevState& s) {
 }
 // A claimed result for the one call: every refusal about it -- an array is refused only if the pass reads it --, then the arrays of `reads` in one block of `up`,
 // every piece 8-byte aligned, then the two counts: one transfer.  An array the pass does not read stays null in the view.
-static int audit_claimed(ks_dev_problem* d, const ks_result* claimed, u32 reads, TmpDev& up, AuditView* view) {
+static int audit_claimed_check(const ks_dev_problem* d, const ks_result* claimed, u32 reads) {
   if (d->view) return fail(KS_ERR_UNSUPPORTED, "a claimed result is audited against a flattened problem, not against a what-if derived on the device");
   const DevProb& h = d->h; const u64 P = h.P, K = h.K, R = h.R, TW = h.TW, N = claimed->n_new;
   if (N > h.NMAX) return fail(KS_ERR_INVALID, "claimed result: more new nodes than max_new_nodes");
   if (claimed->n_unscheduled > P) return fail(KS_ERR_INVALID, "claimed result: more unscheduled pods than pods");
-  size_t bytes = 0;
-#define X(sf, rf, T, cnt) if (reads & AUD_READS(rf)) { if ((cnt) && !claimed->rf) return fail(KS_ERR_INVALID, "claimed result: null array " #rf); bytes += ks_pad8((cnt) * sizeof(T)); }
+#define X(sf, rf, T, cnt) if ((reads & AUD_READS(rf)) && (cnt) && !claimed->rf) return fail(KS_ERR_INVALID, "claimed result: null array " #rf);
   KS_AUDIT_SEGS(X)
 #undef X
-  std::vector<u64> blob(bytes / 8 + 1, 0); u8* hb = (u8*)blob.data();
+  return KS_OK;
+}
+// seq_too (the gate's, or NULL): a second array of commit numbers behind the counts, and the view that reads it in pod_seq's place
+static int audit_claimed_upload(ks_dev_problem* d, const ks_result* claimed, u32 reads, TmpDev& up, AuditView* view, const i32* seq_too = nullptr, AuditView* view_too = nullptr) {
+  const DevProb& h = d->h; const u64 P = h.P, K = h.K, R = h.R, TW = h.TW, N = claimed->n_new;
+  size_t bytes = 0;
+#define X(sf, rf, T, cnt) if (reads & AUD_READS(rf)) bytes += ks_pad8((cnt) * sizeof(T));
+  KS_AUDIT_SEGS(X)
+#undef X
+  const size_t all = bytes + 8 + (seq_too ? ks_pad8(P * sizeof(i32)) : 0);
+  std::vector<u64> blob(all / 8 + 1, 0); u8* hb = (u8*)blob.data();
   HIPCHK(hipSetDevice(d->device));
-  TRY(up.alloc(bytes + 8)); u8* db = up.as<u8>();
+  TRY(up.alloc(all)); u8* db = up.as<u8>();
   DevState s{}; size_t at = 0;
 #define X(sf, rf, T, cnt) if (reads & AUD_READS(rf)) { const size_t b_ = (cnt) * sizeof(T); if (b_) memcpy(hb + at, claimed->rf, b_); s.sf = (T*)(db + at); at += ks_pad8(b_); }
   KS_AUDIT_SEGS(X)
 #undef X
-  { u32 c2[2] = {claimed->n_new, claimed->n_unscheduled}; memcpy(hb + at, c2, 8); s.out_counts = (u32*)(db + at); }
-  HIPCHK(hipMemcpy(db, hb, bytes + 8, hipMemcpyHostToDevice));
+  { u32 c2[2] = {claimed->n_new, claimed->n_unscheduled}; memcpy(hb + at, c2, 8); s.out_counts = (u32*)(db + at); at += 8; }
+  if (seq_too && P) memcpy(hb + at, seq_too, P * sizeof(i32));
+  HIPCHK(hipMemcpy(db, hb, all, hipMemcpyHostToDevice));
   *view = audit_resident(s);
+  if (seq_too) { *view_too = *view; view_too->pod_seq = (const i32*)(db + at); }
   return KS_OK;
+}
+static int audit_claimed(ks_dev_problem* d, const ks_result* claimed, u32 reads, TmpDev& up, AuditView* view) {
+  TRY(audit_claimed_check(d, claimed, reads));
+  return audit_claimed_upload(d, claimed, reads, up, view);
 }
 // The resident form of a pass over a batch: its refusals, then `run` over the results the solves left on the device.  own_device_check: the pass refuses a batch
 // that spans devices here, before a problem that holds no result (the first pass leaves that refusal to BatchStage::open, after them all)
-template <class Out> static int audit_batch(ks_dev_problem* const* ds, u32 n, Out* const* outs, bool own_device_check, int (*run)(ks_dev_problem* const*, u32, const AuditView*, Out* const*)) {
-  if (!n) return KS_OK;
-  if (!ds || !outs) return fail(KS_ERR_INVALID, "null argument");
+struct AuditGate;      // the gate's side of a pass's run (below): null for the pass's own entry points
+// the refusals of the resident form, in the pass's order, and the views of the results (outs: null from the gate, whose tables are arrays it has looked at itself)
+template <class Out> static int audit_resident_check(ks_dev_problem* const* ds, u32 n, Out* const* outs, bool own_device_check, AuditView* res) {
   TRY(BatchStage::not_null(ds, n));
-  std::vector<AuditView> res(n);
   for (u32 i = 0; i < n; ++i) {
-    if (!outs[i]) return fail(KS_ERR_INVALID, "null audit table");
+    if (outs && !outs[i]) return fail(KS_ERR_INVALID, "null audit table");
     if (own_device_check && ds[i]->device != ds[0]->device) return fail(KS_ERR_INVALID, "batch spans devices");
     if (!ds[i]->solved) return fail(KS_ERR_INVALID, "audit of a problem that holds no result: solve it first (or the last solve failed)");
     res[i] = audit_resident(ds[i]->hs);
   }
-  return run(ds, n, res.data(), outs);
+  return KS_OK;
+}
+template <class Out> static int audit_batch(ks_dev_problem* const* ds, u32 n, Out* const* outs, bool own_device_check, int (*run)(ks_dev_problem* const*, u32, const AuditView*, Out* const*, AuditGate*)) {
+  if (!n) return KS_OK;
+  if (!ds || !outs) return fail(KS_ERR_INVALID, "null argument");
+  std::vector<AuditView> res(n);
+  TRY(audit_resident_check(ds, n, outs, own_device_check, res.data()));
+  return run(ds, n, res.data(), outs, nullptr);
 }
 // One problem: the result its solve left (claimed == NULL), or the caller's arrays, of which the pass reads `reads`
-template <class Out> static int audit_one(ks_dev_problem* d, const ks_result* claimed, Out* out, u32 reads, bool own_device_check, int (*run)(ks_dev_problem* const*, u32, const AuditView*, Out* const*)) {
+template <class Out> static int audit_one(ks_dev_problem* d, const ks_result* claimed, Out* out, u32 reads, bool own_device_check, int (*run)(ks_dev_problem* const*, u32, const AuditView*, Out* const*, AuditGate*)) {
   if (!d || !out) return fail(KS_ERR_INVALID, "null argument");
   if (!claimed) return audit_batch(&d, 1u, &out, own_device_check, run);
   TmpDev up(d->device); AuditView v{};
   TRY(audit_claimed(d, claimed, reads, up, &v));
-  return run(&d, 1, &v, &out);
+  return run(&d, 1, &v, &out, nullptr);
 }
 // The pooled block of u32 a pass works in: [the words that are read back: meta, flag rows, checked rows | scratch], zeroed on the stream before the first launch.
 // The output words are reserved first; a pass carves each problem's scratch up itself, from the offset it gets here.
@@ -356,21 +380,101 @@ struct AuditClock {
 static void audit_tally(const u32* rows, u32 n, u32* n_flagged, u32* bit_count /* [32] or NULL */) {
   for (u32 k = 0; k < n; ++k) if (rows[k]) { ++*n_flagged; if (bit_count) for (u32 x = rows[k]; x; x &= x - 1) ++bit_count[__builtin_ctz(x)]; }
 }
+// ---- what follows a pass's launches: the TAIL.  A pass says where its tables lie in its work block and which bit fields of a checked word its totals sum
+// (AuditTail), and gives a function that writes a problem's out struct from the sums (AuditTotals).  Two tails produce the sums:
+//   the pass's own entry points: wait, the output prefix read back, the rows counted on the host, the tables copied to the caller's;
+//   the gate's (g given): the reduce kernels of ks_audit_reduce.inc over the same work block on the same stream, then wait and ONE read-back of the totals' block
+//   [meta | sums] of every problem; the findings go to the gate's table on the device; no row of a flag table is copied to the host.
+struct AuditTail {
+  u32 n_meta;                                      // meta words per problem, at the head of the work block: problem i's at n_meta * i
+  const size_t* o_pf; const size_t* o_ck; const size_t* o_nf;      // per problem: its pod flags | its checked words, or null | its node flags, or null (offsets in the work block)
+  u32 n_fields, shift[4], mask[4];
+};
+struct AuditTotals {
+  const u32* meta; u32 n_pods_flagged, n_nodes_flagged;
+  const u32* pod_bits; const u32* node_bits;      // [32] each
+  const u32* field;                                // [4]: the sums of the tail's fields over the checked words
+};
+struct AuditGate {
+  ks_audit_finding* d_find; u32 cap;               // the findings' table on the device
+  u32 found;                                       // findings so far: the passes before, and this pass's earlier slices
+  u32 pass;                                        // a finding's pass
+  const void* outs0;                               // the pass's array of out pointers: a slice's position in the batch is its distance from here
+};
+// The reduce kernels over `probs` (device pointers inside), queued on `stream`: the totals' blocks come back in `tot` ([KS_AR_TOT] per problem) after the wait, which
+// is `clock`'s where there is one.  R: the call's block for the descriptors, the partial sums, the findings' places and the totals.
+static int audit_reduce(hipStream_t stream, const std::vector<AuditRedProb>& probs, u32 maxlen, ks_audit_finding* d_find, u32 cap, u32 before, TmpDev& R, AuditClock* clock, std::vector<u32>& tot) {
+  const u32 n = (u32)probs.size(), runs = std::min(KS_AR_MAX_RUNS, std::max(1u, (maxlen + 255u) / 256u));
+  const size_t nt = (size_t)n * KS_AR_TABS * runs;
+  if (nt > 0x7FFFFFFFu / KS_AR_W) return fail(KS_ERR_UNSUPPORTED, "audit gate: the flag tables of the batch are too many runs for one reduction");
+  const size_t b_probs = ks_pad8(n * sizeof(AuditRedProb)), w_part = nt * KS_AR_W, w_fbase = nt, w_tot = (size_t)n * KS_AR_TOT;
+  TRY(R.alloc(b_probs + (w_part + w_fbase + w_tot) * sizeof(u32)));
+  AuditRedView V{}; V.probs = R.as<const AuditRedProb>(); V.part = (u32*)(R.as<u8>() + b_probs); V.fbase = V.part + w_part; V.tot = V.fbase + w_fbase;
+  V.find = d_find; V.n = n; V.runs = runs; V.cap = cap; V.before = before;
+  HIPCHK(hipMemcpyAsync(R.p, probs.data(), n * sizeof(AuditRedProb), hipMemcpyHostToDevice, stream));
+  const bool scatter = cap != 0u && before < cap;      // (a full table takes no more records: the count comes from the totals)
+  const u32 KS_GRID_Y_PROBS = 65535u / KS_AR_TABS;
+  for (u32 base = 0; base < n; base += KS_GRID_Y_PROBS) hipLaunchKernelGGL(ks_audit_tally, dim3(runs, std::min(KS_GRID_Y_PROBS, n - base) * KS_AR_TABS), dim3(256), 0, stream, V, base);
+  hipLaunchKernelGGL(ks_audit_tally_finish, dim3(n), dim3(64), 0, stream, V);
+  if (scatter) {
+    hipLaunchKernelGGL(ks_audit_find_scan, dim3(1), dim3(256), 0, stream, V);
+    for (u32 base = 0; base < n; base += KS_GRID_Y_PROBS) hipLaunchKernelGGL(ks_audit_find_scatter, dim3(runs, std::min(KS_GRID_Y_PROBS, n - base) * KS_AR_TABS), dim3(256), 0, stream, V, base);
+  }
+  if (clock) TRY(clock->wait(stream)); else { HIPCHK(hipStreamSynchronize(stream)); HIPCHK(hipGetLastError()); }
+  tot.resize(w_tot);
+  HIPCHK(hipMemcpy(tot.data(), V.tot, w_tot * sizeof(u32), hipMemcpyDeviceToHost));
+  return KS_OK;
+}
+static AuditTotals audit_totals_of(const u32* tot) {      // a totals' block as the finish kernel lays it out
+  AuditTotals T{}; T.meta = tot; T.pod_bits = tot + KS_AR_META; T.n_pods_flagged = tot[KS_AR_META + 32u]; T.node_bits = tot + KS_AR_META + 33u; T.n_nodes_flagged = tot[KS_AR_META + 65u]; T.field = tot + KS_AR_META + 66u;
+  return T;
+}
+static int audit_tail_gate(hipStream_t stream, u32* w, AuditClock& clock, ks_dev_problem* const* ds, u32 n, const AuditTail& L, AuditGate& g, u32 position, const std::function<void(u32, const AuditTotals&)>& fill) {
+  std::vector<AuditRedProb> probs(n); u32 maxlen = 0;
+  for (u32 i = 0; i < n; ++i) {
+    AuditRedProb& D = probs[i]; const DevProb& h = ds[i]->h;
+    D.meta = w + (size_t)L.n_meta * i; D.n_meta = L.n_meta; D.pod_flags = w + L.o_pf[i]; D.node_flags = L.o_nf ? w + L.o_nf[i] : nullptr; D.chk = L.o_ck ? w + L.o_ck[i] : nullptr;
+    D.P = h.P; D.E = h.E; D.NMAX = h.NMAX; D.n_fields = L.n_fields; memcpy(D.shift, L.shift, sizeof D.shift); memcpy(D.mask, L.mask, sizeof D.mask);
+    D.problem = position + i; D.where = g.pass << 8;
+    maxlen = std::max(maxlen, std::max(h.P, L.o_nf ? h.E + h.NMAX : 0u));
+  }
+  TmpDev R(ds[0]->device); std::vector<u32> tot;
+  TRY(audit_reduce(stream, probs, maxlen, g.d_find, g.cap, g.found, R, &clock, tot));
+  for (u32 i = 0; i < n; ++i) { const AuditTotals T = audit_totals_of(tot.data() + (size_t)i * KS_AR_TOT); fill(i, T); g.found += T.n_pods_flagged + T.n_nodes_flagged; }
+  return KS_OK;
+}
+// fill(i, totals, pod flags, node flags): problem i's out struct from its sums; the two rows are the read-back's, for the caller's tables -- null from the gate
+template <class Out, class F> static int audit_tail(BatchStage& st, AuditWork& W, AuditClock& clock, ks_dev_problem* const* ds, u32 n, Out* const* outs, const AuditTail& L, AuditGate* g, F&& fill) {
+  if (g) return audit_tail_gate(st.stream(), W.w(), clock, ds, n, L, *g, (u32)(outs - (Out* const*)g->outs0), [&](u32 i, const AuditTotals& T) { fill(i, T, (const u32*)nullptr, (const u32*)nullptr); });
+  TRY(clock.wait(st.stream()));
+  TRY(W.read_back());
+  for (u32 i = 0; i < n; ++i) {
+    u32 pod_bits[32] = {0}, node_bits[32] = {0}, field[4] = {0, 0, 0, 0};
+    AuditTotals T{}; T.meta = W.back.data() + (size_t)L.n_meta * i; T.pod_bits = pod_bits; T.node_bits = node_bits; T.field = field;
+    const u32 Pn = ds[i]->h.P, NS = ds[i]->h.E + T.meta[0];
+    const u32* pf = W.back.data() + L.o_pf[i]; const u32* nf = L.o_nf ? W.back.data() + L.o_nf[i] : nullptr;
+    audit_tally(pf, Pn, &T.n_pods_flagged, pod_bits);
+    if (nf) audit_tally(nf, NS, &T.n_nodes_flagged, node_bits);
+    if (L.o_ck) { const u32* ck = W.back.data() + L.o_ck[i]; for (u32 k = 0; k < Pn; ++k) for (u32 f = 0; f < L.n_fields; ++f) field[f] += (ck[k] >> L.shift[f]) & L.mask[f]; }
+    fill(i, T, pf, nf);
+  }
+  return KS_OK;
+}
 // A batch walked in slices for a pass whose scratch per problem can be large: a slice holds problems of at most `budget` words_of(problem) together, or one problem
-template <class Out, class W, class S> static int audit_slices(ks_dev_problem* const* ds, u32 n, const AuditView* results, Out* const* outs, W&& words_of, size_t budget, S&& slice) {
+template <class Out, class W, class S> static int audit_slices(ks_dev_problem* const* ds, u32 n, const AuditView* results, Out* const* outs, AuditGate* g, W&& words_of, size_t budget, S&& slice) {
   double kms = 0.0, rms = 0.0;
   for (u32 base = 0; base < n;) {
     u32 m = 0; size_t words = 0;
     while (base + m < n && (m == 0 || words + words_of(ds[base + m]) <= budget)) { words += words_of(ds[base + m]); ++m; }
-    TRY(slice(ds + base, m, results + base, outs + base, &kms, &rms));
+    TRY(slice(ds + base, m, results + base, outs + base, g, &kms, &rms));
     base += m;
   }
   audit_times(outs, n, kms, rms);
   return KS_OK;
 }
 
-// every refusal about the out tables, then: scratch laid out and zeroed, four launches, one read-back of [meta | pod flags | node flags], the totals counted on the host
-static int audit_run(ks_dev_problem* const* ds, u32 n, const AuditView* results /* the result pointers of every problem */, ks_audit* const* outs) {
+// every refusal about the out tables, then: scratch laid out and zeroed, four launches, then the tail: one read-back of [meta | pod flags | node flags] and the totals counted on the host, or (g given) the gate's reduction on the device
+static int audit_run(ks_dev_problem* const* ds, u32 n, const AuditView* results /* the result pointers of every problem */, ks_audit* const* outs, AuditGate* g /* or null: the rows are read back */) {
   BatchStage st; TRY(st.open(ds, n, nullptr, false));
   const size_t o_view = st.add<AuditView>(n);
   TRY(st.place());
@@ -399,17 +503,14 @@ static int audit_run(ks_dev_problem* const* ds, u32 n, const AuditView* results 
     hipLaunchKernelGGL(ks_audit_pods, dim3(gx_p, ny), dim3(256), 0, st.stream(), st.probs() + base, dv + base);
     hipLaunchKernelGGL(ks_audit_nodes, dim3(gx_n, ny), dim3(256), 0, st.stream(), st.probs() + base, dv + base);
   });
-  TRY(clock.wait(st.stream()));
-  TRY(W.read_back());
-  for (u32 i = 0; i < n; ++i) {
-    ks_audit* o = outs[i]; const u32* meta = W.back.data() + 2 * (size_t)i; const u32 Pn = ds[i]->h.P, NS = ds[i]->h.E + meta[0];
-    o->n_pods = Pn; o->n_nodes = NS; o->n_new = meta[0]; o->n_unscheduled = meta[1]; o->n_pods_flagged = 0; o->n_nodes_flagged = 0;
-    memset(o->pod_bit_count, 0, sizeof o->pod_bit_count); memset(o->node_bit_count, 0, sizeof o->node_bit_count);
-    const u32* pf = W.back.data() + o_pf[i]; const u32* nf = W.back.data() + o_nf[i];
-    audit_tally(pf, Pn, &o->n_pods_flagged, o->pod_bit_count); audit_tally(nf, NS, &o->n_nodes_flagged, o->node_bit_count);
-    if (o->pod_flags && Pn) memcpy(o->pod_flags, pf, (size_t)Pn * sizeof(u32));
-    if (o->node_flags && NS) memcpy(o->node_flags, nf, (size_t)NS * sizeof(u32));
-  }
+  AuditTail tail{}; tail.n_meta = 2; tail.o_pf = o_pf.data(); tail.o_nf = o_nf.data();
+  TRY(audit_tail(st, W, clock, ds, n, outs, tail, g, [&](u32 i, const AuditTotals& t, const u32* pf, const u32* nf) {
+    ks_audit* o = outs[i]; const u32* meta = t.meta; const u32 Pn = ds[i]->h.P, NS = ds[i]->h.E + meta[0];
+    o->n_pods = Pn; o->n_nodes = NS; o->n_new = meta[0]; o->n_unscheduled = meta[1]; o->n_pods_flagged = t.n_pods_flagged; o->n_nodes_flagged = t.n_nodes_flagged;
+    memcpy(o->pod_bit_count, t.pod_bits, sizeof o->pod_bit_count); memcpy(o->node_bit_count, t.node_bits, sizeof o->node_bit_count);
+    if (pf && o->pod_flags && Pn) memcpy(o->pod_flags, pf, (size_t)Pn * sizeof(u32));
+    if (nf && o->node_flags && NS) memcpy(o->node_flags, nf, (size_t)NS * sizeof(u32));
+  }));
   clock.store(outs, n);
   return KS_OK;
 }
@@ -421,3 +522,81 @@ extern "C" int ks_audit_sizes(const ks_dev_problem* d, uint32_t* n_pods, uint32_
 }
 extern "C" int ks_audit_batch_dev(ks_dev_problem* const* ds, uint32_t n, ks_audit* const* outs) { return audit_batch(ds, n, outs, false, audit_run); }
 extern "C" int ks_audit_dev(ks_dev_problem* d, const ks_result* claimed, ks_audit* out) { return audit_one(d, claimed, out, AUD_READS_ALL, false, audit_run); }
+
+// ---- the gate (ksolve.h ks_audit_gate_dev / ks_audit_gate_batch_dev): the passes a mask names, each through its own run with the gate's tail ----
+// What the gate knows of a pass: X(the index of its mask bit, its member of ks_audit_gate, what it reads of a claimed result, whether it refuses a batch over two
+// devices itself, its run).  The later passes' runs are defined in the files after this one.
+static int audit_topo_run(ks_dev_problem* const*, u32, const AuditView*, ks_audit_topology* const*, AuditGate*);
+static int audit_spread_run(ks_dev_problem* const*, u32, const AuditView*, ks_audit_spread* const*, AuditGate*);
+static int audit_firstfit_run(ks_dev_problem* const*, u32, const AuditView*, ks_audit_firstfit* const*, AuditGate*);
+static int audit_limits_run(ks_dev_problem* const*, u32, const AuditView*, ks_audit_limits* const*, AuditGate*);
+static int audit_hostfit_run(ks_dev_problem* const*, u32, const AuditView*, ks_audit_hostfit* const*, AuditGate*);
+#define KS_AUDIT_GATE_PASSES(X) \
+  X(0, first, AUD_READS_ALL, false, audit_run) X(1, topology, AUD_READS_ORDER, true, audit_topo_run) X(2, spread, AUD_READS_ORDER, true, audit_spread_run) \
+  X(3, firstfit, AUD_READS_FIT, true, audit_firstfit_run) X(4, limits, AUD_READS_FIT, true, audit_limits_run) X(5, hostfit, AUD_READS_FIT, true, audit_hostfit_run)
+template <class Out> static int audit_gate_pass(AuditGate& g, u32 pass, ks_dev_problem* const* ds, u32 n, const AuditView* views, Out* outs, int (*run)(ks_dev_problem* const*, u32, const AuditView*, Out* const*, AuditGate*), ks_audit_gate* gate) {
+  std::vector<Out*> ptr(n); for (u32 i = 0; i < n; ++i) ptr[i] = outs + i;
+  g.pass = pass; g.outs0 = ptr.data();
+  TRY(run(ds, n, views, ptr.data(), &g));
+  gate->kernel_ms += outs[0].kernel_ms; gate->readback_ms += outs[0].readback_ms;      // (a batch's times are in every member)
+  return KS_OK;
+}
+// one problem with a claimed result (n == 1), or the resident results of n problems
+static int audit_gate(ks_dev_problem* const* ds, u32 n, const ks_result* claimed, ks_audit_gate* gate) {
+  if (!gate) return fail(KS_ERR_INVALID, "null argument");
+  if (!gate->passes) return fail(KS_ERR_INVALID, "audit gate: no pass requested");
+  if (gate->passes & ~KS_AUDIT_PASS_ALL) return fail(KS_ERR_INVALID, "audit gate: unknown pass");
+  if (gate->cap_findings && !gate->findings) return fail(KS_ERR_INVALID, "audit gate: null findings table");
+  if (!n) { gate->n_findings = 0; gate->truncated = 0; gate->kernel_ms = gate->readback_ms = 0.0; return KS_OK; }
+  // every refusal of every requested pass, in the order of the mask: nothing is launched and no out struct written unless they all accept
+  std::vector<AuditView> views(n); AuditView first_view{}; u32 reads = 0;
+#define X(k, member, rd, own_check, run) if (gate->passes & (1u << k)) { \
+    if (!ds || !gate->member) return fail(KS_ERR_INVALID, "null argument"); \
+    if (claimed) { if (!ds[0]) return fail(KS_ERR_INVALID, "null argument"); TRY(audit_claimed_check(ds[0], claimed, rd)); reads |= rd; } \
+    else { \
+      TRY(audit_resident_check<void>(ds, n, nullptr, own_check, views.data())); \
+      if (!own_check) for (u32 i = 0; i < n; ++i) if (ds[i]->device != ds[0]->device) return fail(KS_ERR_INVALID, "batch spans devices"); \
+    } }
+  KS_AUDIT_GATE_PASSES(X)
+#undef X
+  const int device = ds[0]->device;
+  HIPCHK(hipSetDevice(device));
+  TmpDev up(device), F(device);
+  const bool own_seq = claimed && gate->first_pod_seq && (gate->passes & KS_AUDIT_PASS_FIRST);
+  if (claimed) TRY(audit_claimed_upload(ds[0], claimed, reads, up, &views[0], own_seq ? gate->first_pod_seq : nullptr, &first_view));      // taken once, uploaded once: the union of what the passes read
+  if (gate->cap_findings) TRY(F.alloc((size_t)gate->cap_findings * sizeof(ks_audit_finding)));
+  AuditGate g{}; g.d_find = gate->cap_findings ? F.as<ks_audit_finding>() : nullptr; g.cap = gate->cap_findings;
+  gate->n_findings = 0; gate->truncated = 0; gate->kernel_ms = gate->readback_ms = 0.0;
+#define X(k, member, rd, own_check, run) if (gate->passes & (1u << k)) TRY(audit_gate_pass(g, k, ds, n, (k == 0 && own_seq) ? &first_view : views.data(), gate->member, run, gate));
+  KS_AUDIT_GATE_PASSES(X)
+#undef X
+  const auto t0 = std::chrono::steady_clock::now();
+  gate->n_findings = g.found;
+  if (g.found > g.cap) gate->truncated |= KS_AUDIT_GATE_TRUNCATED;
+  if (const u32 m = std::min(g.found, g.cap)) HIPCHK(hipMemcpy(gate->findings, g.d_find, (size_t)m * sizeof(ks_audit_finding), hipMemcpyDeviceToHost));      // (the table beyond them is not touched)
+  gate->readback_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return KS_OK;
+}
+extern "C" int ks_audit_gate_batch_dev(ks_dev_problem* const* ds, uint32_t n, ks_audit_gate* gate) { return audit_gate(ds, n, nullptr, gate); }
+extern "C" int ks_audit_gate_dev(ks_dev_problem* d, const ks_result* claimed, ks_audit_gate* gate) { if (!d) return fail(KS_ERR_INVALID, "null argument"); return audit_gate(&d, 1u, claimed, gate); }
+extern "C" int ks_audit_reduce_rows(int device, const uint32_t* rows, uint32_t n, const ks_audit_fields* fields, ks_audit_row_totals* out) {
+  if (!out || (n && !rows)) return fail(KS_ERR_INVALID, "null argument");
+  if (fields && fields->n_fields > 4u) return fail(KS_ERR_INVALID, "audit reduce: more than four fields");
+  if (fields) for (u32 f = 0; f < fields->n_fields; ++f) if (fields->shift[f] > 31u) return fail(KS_ERR_INVALID, "audit reduce: a field's shift is a bit of the word");
+  int n_dev = 0; HIPCHK(hipGetDeviceCount(&n_dev));
+  if (device < 0 || device >= n_dev) return fail(KS_ERR_INVALID, "no such device");
+  HIPCHK(hipSetDevice(device));
+  TmpDev T(device), R(device);
+  TRY(T.alloc(((size_t)n + 2) * sizeof(u32)));
+  u32* meta = T.as<u32>();      // [meta 2 | rows]: the one table is the pod flags and the checked words at once
+  HIPCHK(hipMemsetAsync(meta, 0, 2 * sizeof(u32), nullptr));
+  if (n) HIPCHK(hipMemcpyAsync(meta + 2, rows, (size_t)n * sizeof(u32), hipMemcpyHostToDevice, nullptr));
+  std::vector<AuditRedProb> probs(1); AuditRedProb& D = probs[0];
+  D = AuditRedProb{}; D.meta = meta; D.n_meta = 2; D.pod_flags = meta + 2; D.chk = meta + 2; D.P = n;
+  if (fields) { D.n_fields = fields->n_fields; for (u32 f = 0; f < fields->n_fields; ++f) { D.shift[f] = fields->shift[f]; D.mask[f] = fields->mask[f]; } }
+  std::vector<u32> tot;
+  TRY(audit_reduce(nullptr, probs, n, nullptr, 0u, 0u, R, nullptr, tot));
+  const AuditTotals t = audit_totals_of(tot.data());
+  out->n_set = t.n_pods_flagged; memcpy(out->bit_count, t.pod_bits, sizeof out->bit_count); memcpy(out->field_sum, t.field, sizeof out->field_sum);
+  return KS_OK;
+}

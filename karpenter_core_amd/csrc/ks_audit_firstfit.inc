@@ -239,7 +239,7 @@ __global__ __launch_bounds__(256) void ks_audit_ff_verdict(const DevProb* probs,
 // ---- host half ----
 // One pooled block [meta | flags | checked words | scratch], one memset, the six launches, one read-back, the totals counted on the host.  The scratch of a problem is
 // 2P + 5C + 3E + 2ER + NMAX words: no slicing is needed.
-static int audit_firstfit_run(ks_dev_problem* const* ds, u32 n, const AuditView* results, ks_audit_firstfit* const* outs) {
+static int audit_firstfit_run(ks_dev_problem* const* ds, u32 n, const AuditView* results, ks_audit_firstfit* const* outs, AuditGate* g) {
   BatchStage st; TRY(st.open(ds, n, nullptr, false));
   const size_t o_view = st.add<AuditView>(n), o_fview = st.add<AuditFitView>(n);
   TRY(st.place());
@@ -275,16 +275,12 @@ static int audit_firstfit_run(ks_dev_problem* const* ds, u32 n, const AuditView*
     hipLaunchKernelGGL(ks_audit_ff_new, dim3(gx_n, ny), dim3(256), 0, st.stream(), st.probs() + base, dv + base, df + base);
     hipLaunchKernelGGL(ks_audit_ff_verdict, dim3(gx_p, ny), dim3(256), 0, st.stream(), st.probs() + base, dv + base, df + base);
   });
-  TRY(clock.wait(st.stream()));
-  TRY(W.read_back());
-  for (u32 i = 0; i < n; ++i) {
-    ks_audit_firstfit* o = outs[i]; const u32 Pn = ds[i]->h.P; const u32* meta = W.back.data() + 8 * (size_t)i;
-    o->n_pods = Pn; o->n_new = meta[0]; o->n_placed = meta[1]; o->skipped_pods = 0; o->n_pods_flagged = 0; o->checked[0] = o->checked[1] = 0; o->checked[2] = meta[3]; o->admitting_pairs = meta[4];
-    const u32* pf = W.back.data() + o_fl[i]; const u32* ck = W.back.data() + o_ck[i];
-    audit_tally(pf, Pn, &o->n_pods_flagged, nullptr);
-    for (u32 k = 0; k < Pn; ++k) { o->checked[0] += ck[k] >> 30; o->checked[1] += ck[k] & 1u; o->skipped_pods += (ck[k] >> 29) & 1u; }
-    if (o->pod_flags && Pn) memcpy(o->pod_flags, pf, (size_t)Pn * sizeof(u32));
-  }
+  const AuditTail tail{8, o_fl.data(), o_ck.data(), nullptr, 3, {30, 0, 29, 0}, {3u, 1u, 1u, 0u}};      // checked[0], checked[1], skipped_pods of a checked word
+  TRY(audit_tail(st, W, clock, ds, n, outs, tail, g, [&](u32 i, const AuditTotals& t, const u32* pf, const u32*) {
+    ks_audit_firstfit* o = outs[i]; const u32 Pn = ds[i]->h.P; const u32* meta = t.meta;
+    o->n_pods = Pn; o->n_new = meta[0]; o->n_placed = meta[1]; o->skipped_pods = t.field[2]; o->n_pods_flagged = t.n_pods_flagged; o->checked[0] = t.field[0]; o->checked[1] = t.field[1]; o->checked[2] = meta[3]; o->admitting_pairs = meta[4];
+    if (pf && o->pod_flags && Pn) memcpy(o->pod_flags, pf, (size_t)Pn * sizeof(u32));
+  }));
   clock.store(outs, n);
   return KS_OK;
 }

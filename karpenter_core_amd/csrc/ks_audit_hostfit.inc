@@ -248,7 +248,7 @@ __global__ __launch_bounds__(256) void ks_audit_hf_verdict(const DevProb* probs,
 // KS_AUDIT_HOSTFIT_FIN_WORDS of fin (64 MiB), or one problem.
 #define KS_AUDIT_HOSTFIT_FIN_WORDS ((size_t)16 << 20)
 static size_t audit_hostfit_fin_words(const ks_dev_problem* d) { return ((size_t)d->h.E + d->h.NMAX) * d->h.GH; }
-static int audit_hostfit_slice(ks_dev_problem* const* ds, u32 n, const AuditView* results, ks_audit_hostfit* const* outs, double* kernel_ms, double* readback_ms) {
+static int audit_hostfit_slice(ks_dev_problem* const* ds, u32 n, const AuditView* results, ks_audit_hostfit* const* outs, AuditGate* g, double* kernel_ms, double* readback_ms) {
   BatchStage st; TRY(st.open(ds, n, nullptr, false));
   const size_t o_view = st.add<AuditView>(n), o_fview = st.add<AuditFitView>(n), o_hview = st.add<AuditHostView>(n);
   TRY(st.place());
@@ -287,22 +287,18 @@ static int audit_hostfit_slice(ks_dev_problem* const* ds, u32 n, const AuditView
     hipLaunchKernelGGL(ks_audit_hf_new, dim3(gx_n, ny), dim3(256), 0, st.stream(), st.probs() + base, dv + base, df + base, dh + base);
     hipLaunchKernelGGL(ks_audit_hf_verdict, dim3(gx_p, ny), dim3(256), 0, st.stream(), st.probs() + base, dv + base, df + base, dh + base);
   });
-  TRY(clock.wait(st.stream()));
-  TRY(W.read_back());
-  for (u32 i = 0; i < n; ++i) {
-    ks_audit_hostfit* o = outs[i]; const u32 Pn = ds[i]->h.P; const u32* meta = W.back.data() + 8 * (size_t)i;
-    o->n_pods = Pn; o->n_new = meta[0]; o->n_placed = meta[1]; o->eligible_groups = meta[5]; o->skipped_groups = ds[i]->h.G - meta[5]; o->skipped_pods = 0; o->n_pods_flagged = 0;
-    o->checked[0] = o->checked[1] = 0; o->checked[2] = meta[3]; o->checked[3] = meta[6]; o->admitting_pairs = meta[4];
-    const u32* pf = W.back.data() + o_fl[i]; const u32* ck = W.back.data() + o_ck[i];
-    audit_tally(pf, Pn, &o->n_pods_flagged, nullptr);
-    for (u32 k = 0; k < Pn; ++k) { o->checked[0] += ck[k] >> 30; o->checked[1] += ck[k] & 1u; o->skipped_pods += (ck[k] >> 29) & 1u; }
-    if (o->pod_flags && Pn) memcpy(o->pod_flags, pf, (size_t)Pn * sizeof(u32));
-  }
+  const AuditTail tail{8, o_fl.data(), o_ck.data(), nullptr, 3, {30, 0, 29, 0}, {3u, 1u, 1u, 0u}};      // checked[0], checked[1], skipped_pods of a checked word
+  TRY(audit_tail(st, W, clock, ds, n, outs, tail, g, [&](u32 i, const AuditTotals& t, const u32* pf, const u32*) {
+    ks_audit_hostfit* o = outs[i]; const u32 Pn = ds[i]->h.P; const u32* meta = t.meta;
+    o->n_pods = Pn; o->n_new = meta[0]; o->n_placed = meta[1]; o->eligible_groups = meta[5]; o->skipped_groups = ds[i]->h.G - meta[5]; o->skipped_pods = t.field[2]; o->n_pods_flagged = t.n_pods_flagged;
+    o->checked[0] = t.field[0]; o->checked[1] = t.field[1]; o->checked[2] = meta[3]; o->checked[3] = meta[6]; o->admitting_pairs = meta[4];
+    if (pf && o->pod_flags && Pn) memcpy(o->pod_flags, pf, (size_t)Pn * sizeof(u32));
+  }));
   clock.add(kernel_ms, readback_ms);
   return KS_OK;
 }
-static int audit_hostfit_run(ks_dev_problem* const* ds, u32 n, const AuditView* results, ks_audit_hostfit* const* outs) {
-  return audit_slices(ds, n, results, outs, audit_hostfit_fin_words, KS_AUDIT_HOSTFIT_FIN_WORDS, audit_hostfit_slice);
+static int audit_hostfit_run(ks_dev_problem* const* ds, u32 n, const AuditView* results, ks_audit_hostfit* const* outs, AuditGate* g) {
+  return audit_slices(ds, n, results, outs, g, audit_hostfit_fin_words, KS_AUDIT_HOSTFIT_FIN_WORDS, audit_hostfit_slice);
 }
 extern "C" int ks_audit_hostfit_batch_dev(ks_dev_problem* const* ds, uint32_t n, ks_audit_hostfit* const* outs) { return audit_batch(ds, n, outs, true, audit_hostfit_run); }
 extern "C" int ks_audit_hostfit_dev(ks_dev_problem* d, const ks_result* claimed, ks_audit_hostfit* out) { return audit_one(d, claimed, out, AUD_READS_FIT, true, audit_hostfit_run); }

@@ -375,7 +375,7 @@ __global__ __launch_bounds__(256) void ks_audit_lim_verdict(const DevProb* probs
 
 // ---- host half ----
 // One pooled block [meta | pod flags | checked words | node flags | scratch], one memset, the launches, one read-back, the totals counted on the host.
-static int audit_limits_run(ks_dev_problem* const* ds, u32 n, const AuditView* results, ks_audit_limits* const* outs) {
+static int audit_limits_run(ks_dev_problem* const* ds, u32 n, const AuditView* results, ks_audit_limits* const* outs, AuditGate* g) {
   BatchStage st; TRY(st.open(ds, n, nullptr, false));
   const size_t o_view = st.add<AuditView>(n), o_lview = st.add<AuditLimView>(n);
   TRY(st.place());
@@ -423,19 +423,15 @@ static int audit_limits_run(ks_dev_problem* const* ds, u32 n, const AuditView* r
     }
     hipLaunchKernelGGL(ks_audit_lim_verdict, dim3(gx_p, ny), dim3(256), 0, st.stream(), st.probs() + base, dv + base, df + base);
   });
-  TRY(clock.wait(st.stream()));
-  TRY(W.read_back());
-  for (u32 i = 0; i < n; ++i) {
-    ks_audit_limits* o = outs[i]; const u32 Pn = ds[i]->h.P; const u32* meta = W.back.data() + 8 * (size_t)i; const u32 NS = ds[i]->h.E + meta[0];
-    o->n_pods = Pn; o->n_nodes = NS; o->n_new = meta[0]; o->n_placed = meta[1]; o->limited_templates = ds[i]->n_limited; o->skipped_nodes = meta[2]; o->skipped_pods = 0;
-    o->n_pods_flagged = 0; o->n_nodes_flagged = 0; o->checked[0] = 0; o->checked[1] = meta[3]; o->checked[2] = 0; o->checked[3] = meta[4]; o->exact_nodes = meta[5]; o->binding_nodes = meta[6];
-    memset(o->pod_bit_count, 0, sizeof o->pod_bit_count); memset(o->node_bit_count, 0, sizeof o->node_bit_count);
-    const u32* pf = W.back.data() + o_fl[i]; const u32* ck = W.back.data() + o_ck[i]; const u32* nf = W.back.data() + o_nf[i];
-    audit_tally(pf, Pn, &o->n_pods_flagged, o->pod_bit_count); audit_tally(nf, NS, &o->n_nodes_flagged, o->node_bit_count);
-    for (u32 k = 0; k < Pn; ++k) { o->checked[0] += ck[k] >> 30; o->checked[2] += ck[k] & 1u; o->skipped_pods += (ck[k] >> 29) & 1u; }
-    if (o->pod_flags && Pn) memcpy(o->pod_flags, pf, (size_t)Pn * sizeof(u32));
-    if (o->node_flags && NS) memcpy(o->node_flags, nf, (size_t)NS * sizeof(u32));
-  }
+  const AuditTail tail{8, o_fl.data(), o_ck.data(), o_nf.data(), 3, {30, 0, 29, 0}, {3u, 1u, 1u, 0u}};      // checked[0], checked[2], skipped_pods of a checked word
+  TRY(audit_tail(st, W, clock, ds, n, outs, tail, g, [&](u32 i, const AuditTotals& t, const u32* pf, const u32* nf) {
+    ks_audit_limits* o = outs[i]; const u32 Pn = ds[i]->h.P; const u32* meta = t.meta; const u32 NS = ds[i]->h.E + meta[0];
+    o->n_pods = Pn; o->n_nodes = NS; o->n_new = meta[0]; o->n_placed = meta[1]; o->limited_templates = ds[i]->n_limited; o->skipped_nodes = meta[2]; o->skipped_pods = t.field[2];
+    o->n_pods_flagged = t.n_pods_flagged; o->n_nodes_flagged = t.n_nodes_flagged; o->checked[0] = t.field[0]; o->checked[1] = meta[3]; o->checked[2] = t.field[1]; o->checked[3] = meta[4]; o->exact_nodes = meta[5]; o->binding_nodes = meta[6];
+    memcpy(o->pod_bit_count, t.pod_bits, sizeof o->pod_bit_count); memcpy(o->node_bit_count, t.node_bits, sizeof o->node_bit_count);
+    if (pf && o->pod_flags && Pn) memcpy(o->pod_flags, pf, (size_t)Pn * sizeof(u32));
+    if (nf && o->node_flags && NS) memcpy(o->node_flags, nf, (size_t)NS * sizeof(u32));
+  }));
   clock.store(outs, n);
   return KS_OK;
 }

@@ -211,7 +211,7 @@ __global__ __launch_bounds__(64) void ks_audit_spread_pods(const DevProb* probs,
 // P and G), and a slice holds at most KS_AUDIT_SPREAD_TAB_WORDS of them (64 MiB), or one problem.
 #define KS_AUDIT_SPREAD_TAB_WORDS ((size_t)16 << 20)
 static size_t audit_spread_tab_words(const ks_dev_problem* d) { const size_t nch = std::max<size_t>(1, ((size_t)d->h.P + KS_AS_CHUNK - 1) / KS_AS_CHUNK); return nch * d->h.G * KS_AS_ROW; }
-static int audit_spread_slice(ks_dev_problem* const* ds, u32 n, const AuditView* results, ks_audit_spread* const* outs, double* kernel_ms, double* readback_ms) {
+static int audit_spread_slice(ks_dev_problem* const* ds, u32 n, const AuditView* results, ks_audit_spread* const* outs, AuditGate* g, double* kernel_ms, double* readback_ms) {
   BatchStage st; TRY(st.open(ds, n, nullptr, false));
   const size_t o_view = st.add<AuditView>(n), o_sview = st.add<AuditSpreadView>(n);
   TRY(st.place());
@@ -241,23 +241,19 @@ static int audit_spread_slice(ks_dev_problem* const* ds, u32 n, const AuditView*
     hipLaunchKernelGGL(ks_audit_spread_scan, dim3(gx_s, ny), dim3(256), 0, st.stream(), st.probs() + base, dt + base);
     hipLaunchKernelGGL(ks_audit_spread_pods, dim3(gx_c, ny), dim3(64), 0, st.stream(), st.probs() + base, dv + base, dt + base);
   });
-  TRY(clock.wait(st.stream()));
-  TRY(W.read_back());
-  for (u32 i = 0; i < n; ++i) {
-    ks_audit_spread* o = outs[i]; const u32 Pn = ds[i]->h.P; const u32* meta = W.back.data() + 4 * (size_t)i;
-    o->n_pods = Pn; o->n_new = meta[0]; o->n_placed = meta[1]; o->skipped_groups = meta[2]; o->n_pods_flagged = 0; o->checked[0] = o->checked[1] = 0; o->exact_pairs = 0;
-    const u32* pf = W.back.data() + o_fl[i]; const u32* ck = W.back.data() + o_ck[i];
-    audit_tally(pf, Pn, &o->n_pods_flagged, nullptr);
-    for (u32 k = 0; k < Pn; ++k) { o->checked[0] += ck[k] >> 30; o->checked[1] += ck[k] & 1023u; o->exact_pairs += (ck[k] >> 10) & 1023u; }
-    if (o->pod_flags && Pn) memcpy(o->pod_flags, pf, (size_t)Pn * sizeof(u32));
-  }
+  const AuditTail tail{4, o_fl.data(), o_ck.data(), nullptr, 3, {30, 0, 10, 0}, {3u, 1023u, 1023u, 0u}};      // checked[0], checked[1], exact_pairs of a checked word
+  TRY(audit_tail(st, W, clock, ds, n, outs, tail, g, [&](u32 i, const AuditTotals& t, const u32* pf, const u32*) {
+    ks_audit_spread* o = outs[i]; const u32 Pn = ds[i]->h.P; const u32* meta = t.meta;
+    o->n_pods = Pn; o->n_new = meta[0]; o->n_placed = meta[1]; o->skipped_groups = meta[2]; o->n_pods_flagged = t.n_pods_flagged; o->checked[0] = t.field[0]; o->checked[1] = t.field[1]; o->exact_pairs = t.field[2];
+    if (pf && o->pod_flags && Pn) memcpy(o->pod_flags, pf, (size_t)Pn * sizeof(u32));
+  }));
   clock.add(kernel_ms, readback_ms);
   return KS_OK;
 }
-static int audit_spread_run(ks_dev_problem* const* ds, u32 n, const AuditView* results, ks_audit_spread* const* outs) {
+static int audit_spread_run(ks_dev_problem* const* ds, u32 n, const AuditView* results, ks_audit_spread* const* outs, AuditGate* g) {
   size_t budget = KS_AUDIT_SPREAD_TAB_WORDS;
   if (const char* e = getenv("KS_AUDIT_SPREAD_SLICE_WORDS")) budget = (size_t)strtoull(e, nullptr, 0);      // (diagnostic, as KS_POISON: lets a test walk a small batch in slices; the flags must not depend on it)
-  return audit_slices(ds, n, results, outs, audit_spread_tab_words, budget, audit_spread_slice);
+  return audit_slices(ds, n, results, outs, g, audit_spread_tab_words, budget, audit_spread_slice);
 }
 extern "C" int ks_audit_spread_batch_dev(ks_dev_problem* const* ds, uint32_t n, ks_audit_spread* const* outs) { return audit_batch(ds, n, outs, true, audit_spread_run); }
 extern "C" int ks_audit_spread_dev(ks_dev_problem* d, const ks_result* claimed, ks_audit_spread* out) { return audit_one(d, claimed, out, AUD_READS_ORDER, true, audit_spread_run); }

@@ -214,7 +214,7 @@ __global__ __launch_bounds__(256) void ks_audit_topo_nodes(const DevProb* probs,
 // most KS_AUDIT_TOPO_FIRST_WORDS of them (64 MiB), or one problem.
 #define KS_AUDIT_TOPO_FIRST_WORDS ((size_t)16 << 20)
 // ks_audit.inc's audit_run pattern per slice: scratch laid out, one memset, the launches, one read-back of [meta | flags | chk], the totals counted on the host
-static int audit_topo_slice(ks_dev_problem* const* ds, u32 n, const AuditView* results, ks_audit_topology* const* outs, double* kernel_ms, double* readback_ms) {
+static int audit_topo_slice(ks_dev_problem* const* ds, u32 n, const AuditView* results, ks_audit_topology* const* outs, AuditGate* g, double* kernel_ms, double* readback_ms) {
   BatchStage st; TRY(st.open(ds, n, nullptr, false));
   const size_t o_view = st.add<AuditView>(n), o_tview = st.add<AuditTopoView>(n);
   TRY(st.place());
@@ -243,22 +243,18 @@ static int audit_topo_slice(ks_dev_problem* const* ds, u32 n, const AuditView* r
     hipLaunchKernelGGL(ks_audit_topo_pods, dim3(gx_p, ny), dim3(256), 0, st.stream(), st.probs() + base, dv + base, dt + base);
     hipLaunchKernelGGL(ks_audit_topo_nodes, dim3(gx_n, ny), dim3(256), 0, st.stream(), st.probs() + base, dv + base, dt + base);
   });
-  TRY(clock.wait(st.stream()));
-  TRY(W.read_back());
-  for (u32 i = 0; i < n; ++i) {
-    ks_audit_topology* o = outs[i]; const u32 Pn = ds[i]->h.P; const u32* meta = W.back.data() + 4 * (size_t)i;
-    o->n_pods = Pn; o->n_new = meta[0]; o->n_placed = meta[3]; o->skipped_groups = meta[2]; o->n_pods_flagged = 0;
-    memset(o->pod_bit_count, 0, sizeof o->pod_bit_count); memset(o->checked, 0, sizeof o->checked);
-    const u32* pf = W.back.data() + o_fl[i]; const u32* ck = W.back.data() + o_ck[i];
-    audit_tally(pf, Pn, &o->n_pods_flagged, o->pod_bit_count);
-    for (u32 k = 0; k < Pn; ++k) { o->checked[0] += ck[k] >> 30; o->checked[1] += ck[k] & 1023u; o->checked[2] += (ck[k] >> 10) & 1023u; o->checked[3] += (ck[k] >> 20) & 1023u; }
-    if (o->pod_flags && Pn) memcpy(o->pod_flags, pf, (size_t)Pn * sizeof(u32));
-  }
+  const AuditTail tail{4, o_fl.data(), o_ck.data(), nullptr, 4, {30, 0, 10, 20}, {3u, 1023u, 1023u, 1023u}};      // checked[0..3] of a checked word
+  TRY(audit_tail(st, W, clock, ds, n, outs, tail, g, [&](u32 i, const AuditTotals& t, const u32* pf, const u32*) {
+    ks_audit_topology* o = outs[i]; const u32 Pn = ds[i]->h.P; const u32* meta = t.meta;
+    o->n_pods = Pn; o->n_new = meta[0]; o->n_placed = meta[3]; o->skipped_groups = meta[2]; o->n_pods_flagged = t.n_pods_flagged;
+    memcpy(o->pod_bit_count, t.pod_bits, sizeof o->pod_bit_count); memcpy(o->checked, t.field, sizeof o->checked);
+    if (pf && o->pod_flags && Pn) memcpy(o->pod_flags, pf, (size_t)Pn * sizeof(u32));
+  }));
   clock.add(kernel_ms, readback_ms);
   return KS_OK;
 }
-static int audit_topo_run(ks_dev_problem* const* ds, u32 n, const AuditView* results, ks_audit_topology* const* outs) {
-  return audit_slices(ds, n, results, outs, [](const ks_dev_problem* d) { return (size_t)d->h.G * 64; }, KS_AUDIT_TOPO_FIRST_WORDS, audit_topo_slice);
+static int audit_topo_run(ks_dev_problem* const* ds, u32 n, const AuditView* results, ks_audit_topology* const* outs, AuditGate* g) {
+  return audit_slices(ds, n, results, outs, g, [](const ks_dev_problem* d) { return (size_t)d->h.G * 64; }, KS_AUDIT_TOPO_FIRST_WORDS, audit_topo_slice);
 }
 extern "C" int ks_audit_topology_batch_dev(ks_dev_problem* const* ds, uint32_t n, ks_audit_topology* const* outs) { return audit_batch(ds, n, outs, true, audit_topo_run); }
 extern "C" int ks_audit_topology_dev(ks_dev_problem* d, const ks_result* claimed, ks_audit_topology* out) { return audit_one(d, claimed, out, AUD_READS_ORDER, true, audit_topo_run); }

@@ -2745,6 +2745,7 @@ __global__ void ks_probe_has_kernel(ks_req1 a, const i32* vint, u32 nv, ks_req_f
 // hipHostMalloc per Solve would cost more than the upload itself, so freed blocks are kept (per device, by power-of-two size
 // class, a few of each) and handed out again.  Thread-safe; blocks never migrate between devices.
 #include <chrono>
+#include <functional>
 #include <mutex>
 #include <thread>
 #include <map>
@@ -4394,7 +4395,9 @@ extern "C" int ks_placement_rows_host(ks_dev_problem* const* ds, uint32_t n, con
 
 // The order matters: ks_audit.inc's host half is the host path of all six passes (the claimed upload, the resident prelude, the pooled work block, the launch rows,
 // the tallies, the slice walker -- DESIGN.md 7.26), and the device helpers the later files share stand beside its own; each later file adds a view, kernels and one run function.
-#include "ks_audit.inc"      // the audit of a result against its problem (ks_audit_dev / ks_audit_batch_dev), and what every pass's host half calls
+#include "ks_audit.inc"      // the audit of a result against its problem (ks_audit_dev / ks_audit_batch_dev), and what every pass's host half calls; between its two
+                             // halves it includes ks_audit_reduce.inc, the gate's kernels (ks_audit_gate_dev / ks_audit_gate_batch_dev / ks_audit_reduce_rows): they
+                             // build on its device helpers and its host half's tail launches them
 #include "ks_audit_topo.inc" // its second, opt-in pass: pod (anti-)affinity and hostname spread in commit order (ks_audit_topology_dev / ks_audit_topology_batch_dev)
 #include "ks_audit_spread.inc" // its third, opt-in pass: topology spread over narrow keys in commit order (ks_audit_spread_dev / ks_audit_spread_batch_dev)
 #include "ks_audit_firstfit.inc" // its fourth, opt-in pass: first-fit order from the final state and the commit numbers (ks_audit_firstfit_dev / ks_audit_firstfit_batch_dev)

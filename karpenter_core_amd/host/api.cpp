@@ -966,8 +966,69 @@ template <class P> int audit_claimed(void* hv, const ksh_result_arrays* c, const
     return KS_OK;
   });
 }
+// The gate (kshost.h ksh_audit_gate / ksh_audit_gate_claimed): X(the pass's mask bit, its traits, its member of ks_audit_gate, its member of ksh_audit_gate_out).
+// libksolve fills out structs of the library's own -- no tables in them -- and every requested pass's totals reach the caller through the pass's own `totals`.
+#define KSH_AUDIT_GATE_PASSES(X) \
+  X(KS_AUDIT_PASS_FIRST, AuditFirst, first, audit) X(KS_AUDIT_PASS_TOPOLOGY, AuditTopology, topology, topology) X(KS_AUDIT_PASS_SPREAD, AuditSpread, spread, spread) \
+  X(KS_AUDIT_PASS_FIRSTFIT, AuditFirstFit, firstfit, firstfit) X(KS_AUDIT_PASS_LIMITS, AuditLimits, limits, limits) X(KS_AUDIT_PASS_HOSTFIT, AuditHostFit, hostfit, hostfit)
+// the gate's own refusals, before any pass's
+int audit_gate_ok(uint32_t passes, const ksh_audit_gate_out* out) {
+  if (!out) return set_err(KS_ERR_INVALID, "null argument");
+  if (!passes) return set_err(KS_ERR_INVALID, "audit gate: no pass requested");
+  if (passes & ~KS_AUDIT_PASS_ALL) return set_err(KS_ERR_INVALID, "audit gate: unknown pass");
+  if (out->cap_findings && !out->findings) return set_err(KS_ERR_INVALID, "audit gate: null findings table");
+#define X(bit, P, km, hm) if ((passes & bit) && !out->hm) return set_err(KS_ERR_INVALID, "null argument");
+  KSH_AUDIT_GATE_PASSES(X)
+#undef X
+  return KS_OK;
+}
+// dev_call(gate): the call into libksolve, over tables of n structs per requested pass
+template <class F> int audit_gate_call(uint32_t n, uint32_t passes, ksh_audit_gate_out* out, double* ms, F&& dev_call) {
+  ks_audit_gate g{}; g.passes = passes; g.findings = out->findings; g.cap_findings = (uint32_t)std::min<uint64_t>(out->cap_findings, 0xFFFFFFFFu);
+#define X(bit, P, km, hm) std::vector<P::Dev> v_##km; if (passes & bit) { v_##km.assign(n, P::Dev{}); g.km = v_##km.data(); }
+  KSH_AUDIT_GATE_PASSES(X)
+#undef X
+  int rc = dev_rc(dev_call(&g)); if (rc != KS_OK) return rc;
+#define X(bit, P, km, hm) if (passes & bit) for (uint32_t i = 0; i < n; ++i) { P::totals(v_##km[i], &out->hm[i]); out->hm[i].truncated = 0; }
+  KSH_AUDIT_GATE_PASSES(X)
+#undef X
+  out->n_findings = g.n_findings; out->truncated = g.truncated;
+  if (ms) { ms[0] = g.kernel_ms; ms[1] = g.readback_ms; }
+  return KS_OK;
+}
 }  // namespace
 extern "C" {
+int ksh_audit_gate(void** hv, uint32_t n, uint32_t passes, ksh_audit_gate_out* out, double* ms) {
+  zero(ms, 2);
+  int rc = audit_gate_ok(passes, out); if (rc != KS_OK) return rc;
+  if (n && !hv) return set_err(KS_ERR_INVALID, "null argument");
+  if (!n) { out->n_findings = 0; out->truncated = 0; return KS_OK; }
+  return guarded([&] {
+    std::vector<ks_dev_problem*> ds;
+    int rc = device_problems(hv, n, true, "audit before solve", ds); if (rc != KS_OK) return rc;
+    return audit_gate_call(n, passes, out, ms, [&](ks_audit_gate* g) { return ks_audit_gate_batch_dev(ds.data(), n, g); });
+  });
+}
+int ksh_audit_gate_claimed(void* hv, const ksh_result_arrays* c, const int32_t* pod_seq, uint32_t passes, ksh_audit_gate_out* out, double* ms) {
+  zero(ms, 2);
+  int rc = audit_gate_ok(passes, out); if (rc != KS_OK) return rc;
+  Handle* h = (Handle*)hv; const bool first = passes & KS_AUDIT_PASS_FIRST;
+  if (!h || !c || ((passes & ~KS_AUDIT_PASS_FIRST) && !pod_seq)) return set_err(KS_ERR_INVALID, "null argument");
+  if (h->delta || h->enc->view) return set_err(KS_ERR_UNSUPPORTED, "a claimed result is audited against a flattened problem, not against a what-if derived on the device");
+  return guarded([&] {
+    const ks_problem& p = h->enc->prob; ks_result r;
+    int rc = claimed_result(p, c, first, pod_seq, &r); if (rc != KS_OK) return rc;
+    rc = ensure_resident(h); if (rc != KS_OK) return rc;
+    std::vector<int32_t> seq, un;
+    if (first) {      // (what ksh_audit_claimed gives the first pass: the unscheduled list in an array of P, the placed pods numbered in pod order)
+      seq.assign((size_t)p.P + 1, -1); un.assign((size_t)p.P + 1, -1);
+      { int32_t k = 0; for (uint32_t i = 0; i < p.P; ++i) if (c->pod_node[i] != -1) seq[i] = k++; }
+      for (uint32_t i = 0; i < c->n_unscheduled; ++i) un[i] = c->unscheduled[i];
+      r.unscheduled = un.data(); if (!pod_seq) r.pod_seq = seq.data();
+    }
+    return audit_gate_call(1, passes, out, ms, [&](ks_audit_gate* g) { g->first_pod_seq = first && pod_seq ? seq.data() : nullptr; return ks_audit_gate_dev(h->dev, &r, g); });
+  });
+}
 int ksh_audit(void** hv, uint32_t n, ksh_audit_out* outs, double* ms) { return audit_resident<AuditFirst>(hv, n, outs, ms); }
 int ksh_audit_claimed(void* hv, const ksh_result_arrays* c, ksh_audit_out* out, double* ms) { return audit_claimed<AuditFirst>(hv, c, nullptr, out, ms); }
 int ksh_audit_topology(void** hv, uint32_t n, ksh_audit_topology_out* outs, double* ms) { return audit_resident<AuditTopology>(hv, n, outs, ms); }

@@ -387,6 +387,14 @@ class FlatProblem:
         `audit_firstfit`'s dict ("checked": SEQ, PODS, PAIRS and TESTS, the (pair, group) count tests evaluated) plus "eligible_groups" and "skipped_groups"."""
         return _audit("hostfit", [self], claimed, pod_seq)[0]
 
+    def audit_gate(self, claimed: Optional[dict] = None, pod_seq=None, passes=None, cap_findings: int = 1024, findings_table=None) -> dict:
+        """The audit's gate (include/ksolve.h KS_AUDIT_PASS_*, kshost.h ksh_audit_gate / ksh_audit_gate_claimed): the passes named in `passes` (default: all six) in one
+        call, tallied on the device -- no flag row is read back.  Arguments as `audit_topology`'s.  Returns `scheduler.audit_gate`'s dict, "passes" holding one dict per
+        pass: what the pass's own method returns, without its flag arrays."""
+        g = audit_gate([self], passes, cap_findings, claimed, pod_seq, findings_table)
+        g["passes"] = {w: v[0] for w, v in g["passes"].items()}
+        return g
+
     def result(self) -> SolveResult:
         """Decode the result the handle holds (after `solve(decode=False)` or `solve_from_pods`)."""
         kh = libs()[1]
@@ -845,6 +853,29 @@ for _p in _AUDIT_PASSES.values():      # include/kshost.h <stem>_out: the tables
 _AuditOut, _AuditTopologyOut, _AuditSpreadOut, _AuditFirstFitOut, _AuditLimitsOut, _AuditHostFitOut = (_AUDIT_PASSES[w]["Out"] for w in ("audit", "topology", "spread", "firstfit", "limits", "hostfit"))
 
 
+def _claimed_arrays(flat: "FlatProblem", claimed: dict, pod_seq, beyond, what: str):
+    """ksh_result_arrays over the arrays of `claimed` that a pass uploads (_CLAIMED_COMMON and `beyond`), the commit numbers as an array of their own (or None), and what
+    must stay alive for the call."""
+    import numpy as np
+    d, keep, seq = flat.dims, [], None
+    ra = _ResultArrays()
+    ra.n_pods, ra.n_existing, ra.n_new, ra.n_unscheduled = d["P"], d["E"], int(claimed["n_new"]), len(claimed["unscheduled"])
+    ra.types_words, ra.n_resources, ra.n_keys = (d["T"] + 63) // 64, d["R"], d["K"]
+    for name, dt in dict(_CLAIMED_COMMON + tuple(beyond)).items():
+        a = np.ascontiguousarray(np.asarray(claimed[name], dtype=dt).reshape(-1))
+        if not len(a):
+            a = np.zeros(1, dtype=dt)      # (a table of no elements is still a table: never NULL)
+        keep.append(a)
+        setattr(ra, name, a.ctypes.data)
+    if pod_seq is not None:
+        seq = np.ascontiguousarray(np.asarray(pod_seq, dtype=np.int32).reshape(-1))
+        if len(seq) != d["P"]:
+            raise ValueError("audit_%s: pod_seq holds one commit number per pod" % what)
+        if not len(seq):
+            seq = np.zeros(1, dtype=np.int32)
+    return ra, seq, keep
+
+
 def _audit(what: str, flats: Sequence["FlatProblem"], claimed: Optional[dict] = None, pod_seq=None) -> List[dict]:
     """One pass of the audit, as _AUDIT_PASSES[what] states it: the call over the resident results of `flats`, or over `claimed` (with `pod_seq`, where the pass takes
     it) for flats[0]; once more with larger tables if one was too short.  One dict per problem."""
@@ -862,25 +893,9 @@ def _audit(what: str, flats: Sequence["FlatProblem"], claimed: Optional[dict] = 
     hs = (ctypes.c_void_p * n)(*[f._h for f in flats])
     outs = (Out * n)()
     ms = (ctypes.c_double * 2)()
-    keep = []
     ra = seq = None
     if claimed is not None:
-        d = flats[0].dims
-        ra = _ResultArrays()
-        ra.n_pods, ra.n_existing, ra.n_new, ra.n_unscheduled = d["P"], d["E"], int(claimed["n_new"]), len(claimed["unscheduled"])
-        ra.types_words, ra.n_resources, ra.n_keys = (d["T"] + 63) // 64, d["R"], d["K"]
-        for name, dt in _CLAIMED_COMMON + p["claimed"]:
-            a = np.ascontiguousarray(np.asarray(claimed[name], dtype=dt).reshape(-1))
-            if not len(a):
-                a = np.zeros(1, dtype=dt)      # (a table of no elements is still a table: never NULL)
-            keep.append(a)
-            setattr(ra, name, a.ctypes.data)
-        if pod_seq is not None:
-            seq = np.ascontiguousarray(np.asarray(pod_seq, dtype=np.int32).reshape(-1))
-            if len(seq) != d["P"]:
-                raise ValueError("audit_%s: pod_seq holds one commit number per pod" % what)
-            if not len(seq):
-                seq = np.zeros(1, dtype=np.int32)
+        ra, seq, _keep = _claimed_arrays(flats[0], claimed, pod_seq, p["claimed"], what)
 
     def call(caps):
         tabs = []
@@ -901,28 +916,102 @@ def _audit(what: str, flats: Sequence["FlatProblem"], claimed: Optional[dict] = 
     if any(o.truncated for o in outs):      # (a table was too short -- a what-if derived on the device states its own sizes only here: once more, with what the totals say)
         tabs = call([(o.n_pods, o.n_nodes if nodes else 0) for o in outs])
 
-    def bit_count(o, flags, field, bits):
-        if hasattr(o, field):
-            return {k: int(getattr(o, field)[v.bit_length() - 1]) for k, v in bits.items()}
-        return {k: int(((flags & v) != 0).sum()) for k, v in bits.items()}
     res = []
     for o, (pf, nf) in zip(outs, tabs):
-        pf = pf[:o.n_pods].copy()
-        r = {"pod_flags": pf}
-        if nodes:
-            r["node_flags"] = nf[:o.n_nodes].copy()
-        r["n_pods_flagged"] = int(o.n_pods_flagged)
-        if nodes:
-            r["n_nodes_flagged"] = int(o.n_nodes_flagged)
-        r["pod_bit_count"] = bit_count(o, pf, "pod_bit_count", p["pod_bits"])
-        if nodes:
-            r["node_bit_count"] = bit_count(o, r["node_flags"], "node_bit_count", p["node_bits"])
-        if p["checked"]:
-            r["checked"] = {k: int(o.checked[j]) for j, k in enumerate(p["checked"])}
-        r.update((k, int(getattr(o, k))) for k in p["scalars"])
+        r = _audit_totals(p, o, pf[:o.n_pods].copy(), nf[:o.n_nodes].copy() if nodes else None)
         r["ms"] = (float(ms[0]), float(ms[1]))
         res.append(r)
     return res
+
+
+def _audit_totals(p: dict, o, pf=None, nf=None) -> dict:
+    """One problem's dict of the pass `p` of _AUDIT_PASSES from its out struct `o`.  pf / nf: its flag rows -- None from the gate, which reads none back: the dict
+    then holds no flag array, and a bit count only where the struct carries it (the others are counted from the rows)."""
+    nodes = p["node_bits"] is not None
+
+    def bit_count(flags, field, bits):
+        if hasattr(o, field):
+            return {k: int(getattr(o, field)[v.bit_length() - 1]) for k, v in bits.items()}
+        return None if flags is None else {k: int(((flags & v) != 0).sum()) for k, v in bits.items()}
+    r = {}
+    if pf is not None:
+        r["pod_flags"] = pf
+        if nodes:
+            r["node_flags"] = nf
+    r["n_pods_flagged"] = int(o.n_pods_flagged)
+    if nodes:
+        r["n_nodes_flagged"] = int(o.n_nodes_flagged)
+    r["pod_bit_count"] = bit_count(pf, "pod_bit_count", p["pod_bits"])
+    if nodes:
+        r["node_bit_count"] = bit_count(nf, "node_bit_count", p["node_bits"])
+    if r["pod_bit_count"] is None:
+        del r["pod_bit_count"]
+    if p["checked"]:
+        r["checked"] = {k: int(o.checked[j]) for j, k in enumerate(p["checked"])}
+    r.update((k, int(getattr(o, k))) for k in p["scalars"])
+    return r
+
+
+# The gate (include/kshost.h ksh_audit_gate / ksh_audit_gate_claimed, include/ksolve.h KS_AUDIT_PASS_*): a pass's mask bit is its place in _AUDIT_PASSES
+KS_AUDIT_PASS = {name: 1 << i for i, name in enumerate(_AUDIT_PASSES)}
+KS_AUDIT_GATE_TRUNCATED = 1
+AUDIT_FINDING = [("problem", "<u4"), ("where", "<u4"), ("index", "<u4"), ("flags", "<u4")]      # ks_audit_finding; where = pass << 8 | table (0 pods, 1 nodes)
+
+
+def audit_reduce_rows(rows, fields: Sequence[tuple] = (), device: int = 0) -> dict:
+    """The gate's reduction over any table of words (include/ksolve.h ks_audit_reduce_rows): `rows` tallied on the device as a flag table -- {"n_set", "bit_count":
+    [32]} -- and as a table of checked words with up to four `fields` (shift, mask): "field_sum": [sum of (row >> shift) & mask].  All sums modulo 2**32."""
+    import numpy as np
+    ks = libs()[0]
+    rows = np.ascontiguousarray(np.asarray(rows, dtype=np.uint32).reshape(-1))
+    f, out = (ctypes.c_uint32 * 9)(len(fields), *[int(s) for s, _ in fields], *([0] * (4 - len(fields))), *[int(m) for _, m in fields]), (ctypes.c_uint32 * 37)()
+    ks.ks_audit_reduce_rows.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]
+    rc = ks.ks_audit_reduce_rows(device, rows.ctypes.data if len(rows) else None, len(rows), f, out)
+    if rc != KS_OK:
+        ks.ks_last_error.restype = ctypes.c_char_p
+        raise KSolveError(rc, ks.ks_last_error().decode())
+    return {"n_set": int(out[0]), "bit_count": [int(x) for x in out[1:33]], "field_sum": [int(x) for x in out[33:33 + len(fields)]]}
+
+
+class _AuditGateOut(ctypes.Structure):      # include/kshost.h ksh_audit_gate_out
+    _fields_ = [("findings", ctypes.c_void_p), ("cap_findings", ctypes.c_uint64)] + [(name, ctypes.POINTER(p["Out"])) for name, p in _AUDIT_PASSES.items()] + \
+               [("n_findings", ctypes.c_uint32), ("truncated", ctypes.c_uint32)]
+
+
+def audit_gate(flats: Sequence["FlatProblem"], passes: Optional[Sequence[str]] = None, cap_findings: int = 1024, claimed: Optional[dict] = None, pod_seq=None,
+               findings_table=None) -> dict:
+    """The audit's gate (include/kshost.h ksh_audit_gate): the passes named in `passes` (default: all six of _AUDIT_PASSES) over the resident results of `flats` in one
+    call -- or over `claimed` with `pod_seq` for flats[0] --, tallied on the device: no flag row is read back.  Returns {"clean": no pass found anything, "passes":
+    {name: one dict per problem, as the pass's own call returns it without its flag arrays}, "findings": a structured array (AUDIT_FINDING) of the first
+    min(n_findings, cap_findings) non-zero flag words, ordered by pass, problem, pods before nodes, index, "n_findings": all of them, "truncated", "ms"}.
+    findings_table: an array of `cap_findings` AUDIT_FINDING records to write into (a caller who wants to see what is left untouched)."""
+    import numpy as np
+    names = list(_AUDIT_PASSES) if passes is None else list(passes)
+    mask = 0
+    for w in names:
+        mask |= KS_AUDIT_PASS[w]
+    n, kh = len(flats), libs()[1]
+    out = _AuditGateOut()
+    table = np.zeros(max(1, cap_findings), dtype=AUDIT_FINDING) if findings_table is None else findings_table
+    out.findings, out.cap_findings = (table.ctypes.data if cap_findings else None), cap_findings
+    outs = {w: (_AUDIT_PASSES[w]["Out"] * max(1, n))() for w in names}
+    for w, a in outs.items():
+        setattr(out, w, a)
+    ms = (ctypes.c_double * 2)()
+    if claimed is None:
+        if pod_seq is not None:
+            raise ValueError("audit_gate: pod_seq goes with a claimed result")
+        kh.ksh_audit_gate.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(_AuditGateOut), ctypes.POINTER(ctypes.c_double)]
+        rc = kh.ksh_audit_gate((ctypes.c_void_p * max(1, n))(*[f._h for f in flats]), n, mask, ctypes.byref(out), ms)
+    else:
+        ra, seq, _keep = _claimed_arrays(flats[0], claimed, pod_seq, sum((_AUDIT_PASSES[w]["claimed"] for w in names), ()), "gate")
+        kh.ksh_audit_gate_claimed.argtypes = [ctypes.c_void_p, ctypes.POINTER(_ResultArrays), ctypes.c_void_p, ctypes.c_uint32, ctypes.POINTER(_AuditGateOut), ctypes.POINTER(ctypes.c_double)]
+        rc = kh.ksh_audit_gate_claimed(flats[0]._h, ctypes.byref(ra), seq.ctypes.data if seq is not None else None, mask, ctypes.byref(out), ms)
+    if rc != KS_OK:
+        raise KSolveError(rc, kh.ksh_last_error().decode())
+    return {"clean": out.n_findings == 0, "passes": {w: [_audit_totals(_AUDIT_PASSES[w], outs[w][i]) for i in range(n)] for w in names},
+            "findings": table[:min(int(out.n_findings), cap_findings)].copy(), "n_findings": int(out.n_findings), "truncated": bool(out.truncated & KS_AUDIT_GATE_TRUNCATED),
+            "ms": (float(ms[0]), float(ms[1]))}
 
 
 def audit_batch(flats: Sequence["FlatProblem"]) -> List[dict]:

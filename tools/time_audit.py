@@ -5,6 +5,8 @@ anything.  Needs a GPU.
    usage: tools/time_audit.py <pass>[,<pass>] [legs, comma separated] [reps]      (defaults: config3,whatifs,config5 9)
    pass   audit | topology | spread | firstfit | limits | hostfit (scheduler._AUDIT_PASSES); the first one named is the subject, the others are timed beside it
           (hostfit,firstfit: the sixth pass beside the fourth, with the cost per evaluated pair of each)
+          gate   the audit's gate (ksh_audit_gate) over the passes named beside it -- all six if it is named alone --, with no findings table: one call, totals
+                 reduced on the device.  Timed in the same run as those passes' own calls, and set against their sum.  The what-ifs are `limits`' snapshot
    legs   config3       BASELINE configs[2]: 100 000 pods / 2 000 types (workloads.config3 seed 44) -- bench.py's contract workload; no limited template
           whatifs       512 what-ifs derived on the device over a 2 048-node snapshot, audited as ONE batch where their results lie.  For `audit` BASELINE configs[3]'s
                         snapshot; for the later passes config #4b's shape with topology, the bound pods carrying spread / affinity / anti-affinity terms
@@ -19,9 +21,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 from karpenter_core_amd import fake, scheduler as S, workloads as W
 
-if len(sys.argv) < 2 or not all(p in S._AUDIT_PASSES for p in sys.argv[1].split(",")):
+if len(sys.argv) < 2 or not all(p in S._AUDIT_PASSES or p == "gate" for p in sys.argv[1].split(",")):
     sys.exit(__doc__)
 passes = sys.argv[1].split(",")
+gated = [p for p in passes if p != "gate"] or list(S._AUDIT_PASSES)      # what the gate runs
+if passes == ["gate"]:
+    passes += gated
 legs = (sys.argv[2] if len(sys.argv) > 2 else "config3,whatifs,config5").split(",")
 reps = int(sys.argv[3]) if len(sys.argv) > 3 else 9
 if S.device_count() < 1:
@@ -38,10 +43,34 @@ def timed(call):
     return [call() for _ in range(reps + 1)][1:]
 
 
+def audit(what, flats):
+    """one timed call: a pass's own, or the gate's -- [its dict], the times in it as in a pass's"""
+    return S._audit(what, flats) if what != "gate" else [S.audit_gate(flats, gated, cap_findings=0)]
+
+
+def report_gate(pack_ms, runs):
+    laps = runs["gate"]
+    wall = [sum(l[0]["ms"]) for l in laps]
+    print(f"   gate ({', '.join(gated)}) kernels   {stat([l[0]['ms'][0] for l in laps])}")
+    print(f"   gate read-back {stat([l[0]['ms'][1] for l in laps])}")
+    print(f"   gate kernels + read-back {stat(wall)}; / pack kernel {statistics.median(wall) / pack_ms * 100:.2f} %")
+    own = [w for w in gated if w in runs]
+    if own == gated:
+        k, r = (sum(statistics.median(l[0]["ms"][i] for l in runs[w]) for w in own) for i in (0, 1))
+        print(f"   the {len(own)} calls' own, summed medians: kernels {k:.3f} ms, read-back {r:.3f} ms, kernels + read-back {k + r:.3f} ms")
+        print(f"   gate / the calls: kernels + read-back {statistics.median(wall) / (k + r):.3f}, read-back {statistics.median(l[0]['ms'][1] for l in laps) / r:.3f}")
+    last = laps[-1][0]
+    print(f"   result: gate {'clean' if last['clean'] else 'FOUND %d' % last['n_findings']}", flush=True)
+
+
 def report(pack_ms, runs):
     """runs: {pass: timed()}"""
     per_pair = {}
+    if "gate" in runs:
+        report_gate(pack_ms, runs)
     for what, laps in runs.items():
+        if what == "gate":
+            continue
         p, last = S._AUDIT_PASSES[what], laps[-1]
         kernels, both = statistics.median(l[0]["ms"][0] for l in laps), statistics.median(sum(l[0]["ms"]) for l in laps)
         print(f"   {what} kernels   {stat([l[0]['ms'][0] for l in laps])}")
@@ -57,7 +86,7 @@ def report(pack_ms, runs):
         print(f"   result: {what} {'clean (nothing flagged)' if not any(flagged.values()) else 'FLAGGED %s' % {k: v for k, v in flagged.items() if v}}", flush=True)
     if len(per_pair) > 1:      # (passes that count (class, node) pairs, side by side)
         first = next(iter(per_pair.values()))
-        print("   per evaluated pair: " + ", ".join(f"{w} {ns:.3f} ns" for w, ns in per_pair.items()) + "".join(f"; {passes[0]} / {w} {first / ns:.2f}" for w, ns in list(per_pair.items())[1:]), flush=True)
+        print("   per evaluated pair: " + ", ".join(f"{w} {ns:.3f} ns" for w, ns in per_pair.items()) + "".join(f"; {next(iter(per_pair))} / {w} {first / ns:.2f}" for w, ns in list(per_pair.items())[1:]), flush=True)
 
 
 def single(name, problem):
@@ -69,8 +98,8 @@ def single(name, problem):
     pack_ms, wall_ms = f.kernel_ms, f.wall_ms
     f.solve(decode=False)      # (the second Solve of a resident problem: tables built, kernels loaded)
     pack_ms = min(pack_ms, f.kernel_ms)
-    runs = {what: timed(lambda: S._audit(what, [f])) for what in passes}
-    d, first = f.dims, runs[passes[0]][0][0]
+    runs = {what: timed(lambda: audit(what, [f])) for what in passes}
+    d, first = f.dims, runs[[p for p in passes if p != "gate"][0]][0][0]
     print(f"{name}: {d['P']} pods, {d['T']} types, {d['E']} existing nodes, {d['C']} classes, {d['M']} templates, {d['G']} topology groups ({d['GH']} on the hostname); "
           + ", ".join(f"{k} {first[k]}" for k in SIZES if k in first) + f"; ks_pack_rr {f.rr_status()}", flush=True)
     print(f"   flatten + upload {(t1 - t0) * 1e3:.0f} ms; pack kernel {pack_ms:.2f} ms (Solve wall {wall_ms:.2f} ms)")
@@ -87,7 +116,7 @@ def whatifs():
         from test_whatif_derived import _topology_snapshot      # (the generator of the differential tests)
         its, prov, nodes, bound, snap, pod_node = _topology_snapshot(2048, 50, 45, spare=-1, extras=True, anti=True)
         name = "config #4b with topology"
-        if passes[0] == "limits":
+        if passes[0] in ("limits", "gate"):
             limit = {"cpu": str(int(sum(fake._qty_value(n.capacity.get("cpu", "0")) for n in nodes)))}
             for p in snap.provisioners:
                 p.limits = dict(limit)
@@ -95,8 +124,8 @@ def whatifs():
     flats = S.open_whatifs(S.ParsedProblem(snap), pod_node, W.config4_sets(512, 2048, 45), derive=True)
     S.solve_batch_resident(flats)
     pack_ms, _ = S.solve_batch_resident(flats)
-    runs = {what: timed(lambda: S._audit(what, flats)) for what in passes}
-    first = runs[passes[0]][0]
+    runs = {what: timed(lambda: audit(what, flats)) for what in passes}
+    first = runs[[p for p in passes if p != "gate"][0]][0]
     print(f"{name}: {len(flats)} what-ifs derived on the device over {len(nodes)} nodes / {len(its)} types; {sum(len(a['pod_flags']) for a in first)} pods, "
           f"{sum(a['n_new'] for a in first)} new nodes in all", flush=True)
     print(f"   pack kernel (one batched launch) {pack_ms:.2f} ms")
