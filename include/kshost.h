@@ -634,6 +634,21 @@ typedef struct ksh_audit_hostfit_out {
 int ksh_audit_hostfit(void** handles, uint32_t n, ksh_audit_hostfit_out* outs /* [n] */, double* ms /* [2] kernels | read-back, or NULL */);
 /* A claimed result for one flattened handle, exactly as ksh_audit_firstfit_claimed takes it. */
 int ksh_audit_hostfit_claimed(void* handle, const ksh_result_arrays* claimed, const int32_t* pod_seq /* [n_pods] */, ksh_audit_hostfit_out* out, double* ms /* [2] or NULL */);
+/* The audit's SEVENTH pass, opt-in (ksolve.h ks_audit_stages_dev, KS_AUDIT_POD_STAGE_*): relaxation order -- no pod ended at a later stage of its chain than one at
+ * which an existing node's final state, or a fresh machine of a provisioner without limits, would have taken it, and no unscheduled pod stopped short of its chain's
+ * end.  It is not one of the gate's passes yet: the shim calls it beside ksh_audit_gate.  The fourth pass's conventions (cap_pods, KSH_AUDIT_TRUNCATED_PODS, indices
+ * as ksh_audit's).  checked[0]: the placed pods; [1]: the pods with an examined earlier stage (skipped_pods: the others -- most pods never relax); [2]: the examined
+ * stages; [3]: the (class, existing-node-or-template) pairs evaluated; admitting_pairs: the pairs that admitted -- none in a clean result. */
+typedef struct ksh_audit_stages_out {
+  uint32_t* pod_flags; uint64_t cap_pods;      /* [cap_pods] KS_AUDIT_POD_SEQ | KS_AUDIT_POD_STAGE_* */
+  uint32_t n_pods, n_new, n_placed, skipped_pods;
+  uint32_t n_pods_flagged, truncated /* KSH_AUDIT_TRUNCATED_PODS */;
+  uint32_t checked[4];
+  uint32_t admitting_pairs, pad;
+} ksh_audit_stages_out;
+int ksh_audit_stages(void** handles, uint32_t n, ksh_audit_stages_out* outs /* [n] */, double* ms /* [2] kernels | read-back, or NULL */);
+/* A claimed result for one flattened handle, exactly as ksh_audit_firstfit_claimed takes it. */
+int ksh_audit_stages_claimed(void* handle, const ksh_result_arrays* claimed, const int32_t* pod_seq /* [n_pods] */, ksh_audit_stages_out* out, double* ms /* [2] or NULL */);
 /* The GATE (ksolve.h ks_audit_gate_dev, KS_AUDIT_PASS_*): the passes of a mask in ONE call, their totals and a list of findings reduced on the device.  This is the
  * shim's gate: one call behind every result, and on a finding, solve in Go; the per-pass calls above remain the way to the flag rows.  No flag row is read back: for
  * every requested pass the caller gives an array of n of that pass's out structs and receives in each exactly the totals the pass's own call writes -- the tables and

@@ -943,6 +943,42 @@ typedef struct ks_audit_hostfit {
 int ks_audit_hostfit_dev(ks_dev_problem* d, const ks_result* claimed /* or NULL; pod_seq is read */, ks_audit_hostfit* out);
 int ks_audit_hostfit_batch_dev(ks_dev_problem* const* ds, uint32_t n, ks_audit_hostfit* const* outs);
 
+/* ---- the audit's SEVENTH pass, opt-in: RELAXATION ORDER -- the one column of a result the six passes above take on trust, pod_stage.  Nothing calls it unless
+ * asked, the gate below included; the first six passes are unchanged by it.  Solve relaxes a pod one step per failed add (scheduler.go:118-127, preferences.go:36-145):
+ * a pod P that ended at stage k = pod_stage[P], placed or unscheduled, was tried and refused at every stage j < k, each try at some moment before the end.  Let
+ * c_j = stage_cls[pod_stage_off[gp] + j].  By the fourth pass's monotonicity two kinds of target need no knowledge of WHEN stage j was tried: an existing node was
+ * there from the start and only filled up, and a fresh node of a template without limits is static data.  One-sided like passes two to six: it flags only what no run
+ * of the reference can have produced.  The bits share their word with KS_AUDIT_POD_SEQ, defined as in the second pass.
+ * EXAMINED stage j of pod P: j < k; P does not fail SEQ, or is unscheduled (pod_node == -1); pod_stage[P] lies inside P's chain; c_j is examinable in the fourth
+ * pass's sense (empty own_list and isel_list, no host port).  A pod with k == 0 or without an examined stage is counted in skipped_pods.
+ * admits_existing(c, e), admits_template(c, m): the fourth pass's predicates of those names, with its examined-pair condition on labelled keys, its volume exception
+ * (a class with any vol_list entry is not examined against existing nodes), its skipping of the nodes that left a derived what-if and its exclusion of limited
+ * templates.  When P itself sits on e its own requests are in e's sum and the class's are added again: that only removes flags. */
+#define KS_AUDIT_POD_STAGE_EXISTING 524288u   /* for some examined stage j of P, some existing node e has admits_existing(c_j, e): the node took no less at the moment stage j was tried, so that add cannot have failed */
+#define KS_AUDIT_POD_STAGE_TEMPLATE 1048576u  /* for some examined stage j of P, some template m without limits has admits_template(c_j, m): add would have opened a machine at stage j */
+#define KS_AUDIT_POD_STAGE_UNRELAXED 2097152u /* P is unscheduled and pod_stage[P], in range, is not the last stage of its chain: the queue ends only on pods pushed back unrelaxed (queue.go:44-68), and Relax returns false only at the end of the chain */
+/* NOT attempted: new nodes as targets (whether node j existed when stage j was tried is not in the result); earlier stages constrained by any topology group (the
+ * hostname kinds are the next step, by the sixth pass's count tests: a fresh node's counts are 0); limited templates; classes with host ports; existing nodes on
+ * keys they do not label. */
+typedef struct ks_audit_stages {
+  uint32_t* pod_flags;            /* [P] KS_AUDIT_POD_SEQ | KS_AUDIT_POD_STAGE_*, or NULL (totals only) */
+  uint32_t n_pods, n_new;         /* out: P | the new nodes of the result that was audited */
+  uint32_t n_placed;              /* out: pods on a node of the result */
+  uint32_t skipped_pods;          /* out: the pods without an examined stage */
+  uint32_t n_pods_flagged;
+  uint32_t checked[4];            /* out: [0] the placed pods (SEQ); [1] the pods with an examined stage; [2] the examined stages, summed over those pods; [3] the (class, existing-node-or-template) pairs evaluated, over the distinct classes of the examined stages */
+  uint32_t admitting_pairs;       /* out: how many of those pairs admitted: 0 in a clean result */
+  double kernel_ms, readback_ms;  /* out: as ks_audit's -- but kernel_ms holds one host wait more than the other passes': the read-back of the meta words between the second and the third launch, which decides whether the last four run */
+} ks_audit_stages;
+/* claimed == NULL: the resident result, where it lies (the form for derived what-ifs).  claimed given (flattened problems only, KS_ERR_UNSUPPORTED for a derived
+ * view): the fourth pass's arrays are uploaded and read; every index a result supplies -- pod_stage above all -- is range-checked before it addresses memory.  Two
+ * launches, then the meta words are read back: where no pod of the CALL has an examined stage (nothing relaxed) the flags are final; else -- for every problem of
+ * the batch, the ones that relaxed nothing included: they evaluate no pair -- four more launches, three
+ * of them the fourth pass's kernels over the distinct classes of the examined stages.  The scratch of a problem is the fourth pass's: a batch is one slice.  Integer
+ * min, add and or; flags are written per index, no output through an atomic, no float: the same flags every run.  Refusals as ks_audit_firstfit_dev's. */
+int ks_audit_stages_dev(ks_dev_problem* d, const ks_result* claimed /* or NULL; pod_seq is read */, ks_audit_stages* out);
+int ks_audit_stages_batch_dev(ks_dev_problem* const* ds, uint32_t n, ks_audit_stages* const* outs);
+
 /* ---- the audit's GATE: chosen passes in ONE call, their totals and a list of FINDINGS reduced on the device.  The question a caller puts behind every result is
  * "is it clean?", and the answer is usually yes: the gate runs the chosen passes' own kernels, leaves their flag tables on the device, tallies them there and reads
  * back the totals alone -- no row of a flag table reaches the host.  The six passes and their entry points above are unchanged by it; they remain the way to the rows.

@@ -833,7 +833,7 @@ int ksh_placement_rows(void** hv, uint32_t n, const uint64_t* ids, uint64_t* out
   });
 }
 }  // extern "C"
-// The audit's six passes (kshost.h ksh_audit* / ksh_audit*_claimed).  What a pass is to this file: its table in libksolve and in kshost.h, whether it has a node
+// The audit's seven passes (kshost.h ksh_audit* / ksh_audit*_claimed).  What a pass is to this file: its table in libksolve and in kshost.h, whether it has a node
 // table beside the pod table, its two entry points in libksolve, whether its claimed form comes without commit numbers, and the totals it copies.
 namespace {
 struct AuditFirst {
@@ -883,6 +883,14 @@ struct AuditHostFit {
   static void totals(const Dev& r, Out* o) {
     o->n_pods = r.n_pods; o->n_new = r.n_new; o->n_placed = r.n_placed; o->skipped_pods = r.skipped_pods; o->n_pods_flagged = r.n_pods_flagged;
     o->eligible_groups = r.eligible_groups; o->skipped_groups = r.skipped_groups; memcpy(o->checked, r.checked, sizeof o->checked); o->admitting_pairs = r.admitting_pairs; o->pad = 0;
+  }
+};
+struct AuditStages {
+  using Dev = ks_audit_stages; using Out = ksh_audit_stages_out; static constexpr bool nodes = false, no_pod_seq = false;
+  static constexpr auto batch_dev = ks_audit_stages_batch_dev; static constexpr auto one_dev = ks_audit_stages_dev;
+  static void totals(const Dev& r, Out* o) {
+    o->n_pods = r.n_pods; o->n_new = r.n_new; o->n_placed = r.n_placed; o->skipped_pods = r.skipped_pods; o->n_pods_flagged = r.n_pods_flagged;
+    memcpy(o->checked, r.checked, sizeof o->checked); o->admitting_pairs = r.admitting_pairs; o->pad = 0;
   }
 };
 // A pass's tables: libksolve fills tables of the library's own, sized from the device problems; the totals always reach the caller, the flag rows only when they fit
@@ -1041,6 +1049,8 @@ int ksh_audit_limits(void** hv, uint32_t n, ksh_audit_limits_out* outs, double* 
 int ksh_audit_limits_claimed(void* hv, const ksh_result_arrays* c, const int32_t* pod_seq, ksh_audit_limits_out* out, double* ms) { return audit_claimed<AuditLimits>(hv, c, pod_seq, out, ms); }
 int ksh_audit_hostfit(void** hv, uint32_t n, ksh_audit_hostfit_out* outs, double* ms) { return audit_resident<AuditHostFit>(hv, n, outs, ms); }
 int ksh_audit_hostfit_claimed(void* hv, const ksh_result_arrays* c, const int32_t* pod_seq, ksh_audit_hostfit_out* out, double* ms) { return audit_claimed<AuditHostFit>(hv, c, pod_seq, out, ms); }
+int ksh_audit_stages(void** hv, uint32_t n, ksh_audit_stages_out* outs, double* ms) { return audit_resident<AuditStages>(hv, n, outs, ms); }
+int ksh_audit_stages_claimed(void* hv, const ksh_result_arrays* c, const int32_t* pod_seq, ksh_audit_stages_out* out, double* ms) { return audit_claimed<AuditStages>(hv, c, pod_seq, out, ms); }
 }  // extern "C"
 // What getNodePrices / filterOutSameType / simulateScheduling's readiness rule read of the snapshot's nodes, once per call
 namespace {

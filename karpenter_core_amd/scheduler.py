@@ -55,6 +55,10 @@ KS_AUDIT_LIMITS_CHECKED = ("SEQ", "NODES", "PODS", "PAIRS")
 # `checked`: placed pods, examined pods, (class, node) pairs, (pair, group) count tests
 KS_AUDIT_HOSTFIT_BITS = {"SEQ": 128, "HFIT_EXISTING": 65536, "HFIT_NEW": 131072, "HFIT_TEMPLATE": 262144}
 KS_AUDIT_HOSTFIT_CHECKED = ("SEQ", "PODS", "PAIRS", "TESTS")
+# the seventh pass's (FlatProblem.audit_stages() / audit_stages_batch()): SEQ as above, and relaxation order -- a pod's earlier stages against the existing nodes' final
+# state and fresh machines of unlimited templates; `checked`: placed pods, pods with an examined stage, examined stages, (class, node-or-template) pairs
+KS_AUDIT_STAGES_BITS = {"SEQ": 128, "STAGE_EXISTING": 524288, "STAGE_TEMPLATE": 1048576, "STAGE_UNRELAXED": 2097152}
+KS_AUDIT_STAGES_CHECKED = ("SEQ", "PODS", "STAGES", "PAIRS")
 
 
 class KSolveError(RuntimeError):
@@ -386,6 +390,13 @@ class FlatProblem:
         for the pods whose constraining groups are all hostname anti-affinity or unfiltered hostname spread.  Arguments as `audit_topology`'s.  Returns
         `audit_firstfit`'s dict ("checked": SEQ, PODS, PAIRS and TESTS, the (pair, group) count tests evaluated) plus "eligible_groups" and "skipped_groups"."""
         return _audit("hostfit", [self], claimed, pod_seq)[0]
+
+    def audit_stages(self, claimed: Optional[dict] = None, pod_seq=None) -> dict:
+        """The audit's seventh, opt-in pass (include/ksolve.h KS_AUDIT_POD_STAGE_*, kshost.h ksh_audit_stages / ksh_audit_stages_claimed): relaxation order -- no pod ended
+        at a later stage of its chain than one at which an existing node's final state or a fresh machine of an unlimited template admits it, and no unscheduled pod
+        stopped short of its chain's end.  Not one of the gate's passes.  Arguments as `audit_topology`'s.  Returns `audit_firstfit`'s dict ("checked": SEQ, PODS the
+        pods with an examined earlier stage, STAGES those stages, PAIRS the (class, node-or-template) pairs)."""
+        return _audit("stages", [self], claimed, pod_seq)[0]
 
     def audit_gate(self, claimed: Optional[dict] = None, pod_seq=None, passes=None, cap_findings: int = 1024, findings_table=None) -> dict:
         """The audit's gate (include/ksolve.h KS_AUDIT_PASS_*, kshost.h ksh_audit_gate / ksh_audit_gate_claimed): the passes named in `passes` (default: all six) in one
@@ -847,10 +858,19 @@ _AUDIT_PASSES = {
                     scalars=("admitting_pairs", "skipped_pods", "eligible_groups", "skipped_groups", "n_new", "n_placed")),
 }
 
-for _p in _AUDIT_PASSES.values():      # include/kshost.h <stem>_out: the tables and their capacities, then `fields`
+# The passes the gate does not run (yet): described as the ones above and called through the same _audit(), but outside _AUDIT_PASSES, whose places are the gate's mask
+# bits and the members of its struct.
+_AUDIT_PASSES_BESIDE = {
+    "stages": dict(stem="ksh_audit_stages", seq=True, out="_AuditStagesOut", claimed=_CLAIMED_FIT, pod_bits=KS_AUDIT_STAGES_BITS, node_bits=None, checked=KS_AUDIT_STAGES_CHECKED,
+                   fields=("n_pods", "n_new", "n_placed", "skipped_pods", "n_pods_flagged", "truncated", "checked*4", "admitting_pairs", "pad"),
+                   scalars=("admitting_pairs", "skipped_pods", "n_new", "n_placed")),
+}
+
+for _p in list(_AUDIT_PASSES.values()) + list(_AUDIT_PASSES_BESIDE.values()):      # include/kshost.h <stem>_out: the tables and their capacities, then `fields`
     _tables = [("pod_flags", ctypes.c_void_p), ("cap_pods", ctypes.c_uint64)] + ([("node_flags", ctypes.c_void_p), ("cap_nodes", ctypes.c_uint64)] if _p["node_bits"] else [])
     _p["Out"] = type(_p["out"], (ctypes.Structure,), {"_fields_": _tables + [(n, ctypes.c_uint32 * int(k) if k else ctypes.c_uint32) for n, _, k in (f.partition("*") for f in _p["fields"])]})
 _AuditOut, _AuditTopologyOut, _AuditSpreadOut, _AuditFirstFitOut, _AuditLimitsOut, _AuditHostFitOut = (_AUDIT_PASSES[w]["Out"] for w in ("audit", "topology", "spread", "firstfit", "limits", "hostfit"))
+_AuditStagesOut = _AUDIT_PASSES_BESIDE["stages"]["Out"]
 
 
 def _claimed_arrays(flat: "FlatProblem", claimed: dict, pod_seq, beyond, what: str):
@@ -877,7 +897,7 @@ def _claimed_arrays(flat: "FlatProblem", claimed: dict, pod_seq, beyond, what: s
 
 
 def _audit(what: str, flats: Sequence["FlatProblem"], claimed: Optional[dict] = None, pod_seq=None) -> List[dict]:
-    """One pass of the audit, as _AUDIT_PASSES[what] states it: the call over the resident results of `flats`, or over `claimed` (with `pod_seq`, where the pass takes
+    """One pass of the audit, as _AUDIT_PASSES[what] (or _AUDIT_PASSES_BESIDE[what]) states it: the call over the resident results of `flats`, or over `claimed` (with `pod_seq`, where the pass takes
     it) for flats[0]; once more with larger tables if one was too short.  One dict per problem."""
     import numpy as np
     if claimed is None and pod_seq is not None:
@@ -885,7 +905,7 @@ def _audit(what: str, flats: Sequence["FlatProblem"], claimed: Optional[dict] = 
     n = len(flats)
     if not n:
         return []
-    p, kh = _AUDIT_PASSES[what], libs()[1]
+    p, kh = _AUDIT_PASSES.get(what) or _AUDIT_PASSES_BESIDE[what], libs()[1]
     Out, nodes = p["Out"], p["node_bits"] is not None
     resident, claimed_fn = getattr(kh, p["stem"]), getattr(kh, p["stem"] + "_claimed")
     resident.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32, ctypes.POINTER(Out), ctypes.POINTER(ctypes.c_double)]
@@ -1048,6 +1068,12 @@ def audit_hostfit_batch(flats: Sequence["FlatProblem"]) -> List[dict]:
     """The audit's sixth pass over the results the last solve left on the device, for a whole batch (include/kshost.h ksh_audit_hostfit): handles of any kind, derived
     what-ifs included.  One dict per problem, as `FlatProblem.audit_hostfit` returns it."""
     return _audit("hostfit", flats)
+
+
+def audit_stages_batch(flats: Sequence["FlatProblem"]) -> List[dict]:
+    """The audit's seventh pass over the results the last solve left on the device, for a whole batch (include/kshost.h ksh_audit_stages): handles of any kind, derived
+    what-ifs included.  One dict per problem, as `FlatProblem.audit_stages` returns it."""
+    return _audit("stages", flats)
 
 
 def deal_lpt(weights: Sequence[int], nshards: int) -> List[int]:

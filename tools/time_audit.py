@@ -3,8 +3,9 @@
 same run on the same box next to the pack kernel time of that Solve, what each pass examined -- `checked` by name and every counter it returns --, and whether it found
 anything.  Needs a GPU.
    usage: tools/time_audit.py <pass>[,<pass>] [legs, comma separated] [reps]      (defaults: config3,whatifs,config5 9)
-   pass   audit | topology | spread | firstfit | limits | hostfit (scheduler._AUDIT_PASSES); the first one named is the subject, the others are timed beside it
-          (hostfit,firstfit: the sixth pass beside the fourth, with the cost per evaluated pair of each)
+   pass   audit | topology | spread | firstfit | limits | hostfit (scheduler._AUDIT_PASSES) | stages (scheduler._AUDIT_PASSES_BESIDE); the first one named is the
+          subject, the others are timed beside it (hostfit,firstfit: the sixth pass beside the fourth, with the cost per evaluated pair of each; stages,firstfit:
+          the seventh beside the fourth, whose pair kernels it runs over fewer classes)
           gate   the audit's gate (ksh_audit_gate) over the passes named beside it -- all six if it is named alone --, with no findings table: one call, totals
                  reduced on the device.  Timed in the same run as those passes' own calls, and set against their sum.  The what-ifs are `limits`' snapshot
    legs   config3       BASELINE configs[2]: 100 000 pods / 2 000 types (workloads.config3 seed 44) -- bench.py's contract workload; no limited template
@@ -14,6 +15,9 @@ anything.  Needs a GPU.
           config5       BASELINE configs[4]'s generator at 250 000 pods / 5 000 types: its `high` provisioner carries a cpu limit
           config5low    the same with that limit divided by eight (for the case that the limit as generated never excludes a type)
           config5_full  config5 at the stated 1 000 000 pods (minutes of generation; not part of the default)
+          relax         tests/audit_stages_cases.py's family -- pods whose preferences cannot hold, over three existing nodes -- scaled until some thousand pods relax
+          relaxwide     2 000 pods of 2 000 different requests that all relax once, over 1 024 existing nodes: as many distinct earlier-stage classes as pods, so that
+                        the pair kernels, not the launches, are what is timed
 Per leg: the Solve (its pack kernel time as the library reports it), one untimed call of each pass, then each pass `reps` times: median with min and max of the
 kernels' lap (inputs up, the launches, completion) and of the read-back lap (the flag words to the host and the totals), milliseconds."""
 import os, statistics, sys, time
@@ -21,10 +25,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 from karpenter_core_amd import fake, scheduler as S, workloads as W
 
-if len(sys.argv) < 2 or not all(p in S._AUDIT_PASSES or p == "gate" for p in sys.argv[1].split(",")):
+PASSES = dict(S._AUDIT_PASSES, **S._AUDIT_PASSES_BESIDE)      # every pass with a call of its own; the gate runs the first table's
+if len(sys.argv) < 2 or not all(p in PASSES or p == "gate" for p in sys.argv[1].split(",")):
     sys.exit(__doc__)
 passes = sys.argv[1].split(",")
-gated = [p for p in passes if p != "gate"] or list(S._AUDIT_PASSES)      # what the gate runs
+gated = [p for p in passes if p in S._AUDIT_PASSES] or list(S._AUDIT_PASSES)      # what the gate runs
 if passes == ["gate"]:
     passes += gated
 legs = (sys.argv[2] if len(sys.argv) > 2 else "config3,whatifs,config5").split(",")
@@ -71,7 +76,7 @@ def report(pack_ms, runs):
     for what, laps in runs.items():
         if what == "gate":
             continue
-        p, last = S._AUDIT_PASSES[what], laps[-1]
+        p, last = PASSES[what], laps[-1]
         kernels, both = statistics.median(l[0]["ms"][0] for l in laps), statistics.median(sum(l[0]["ms"]) for l in laps)
         print(f"   {what} kernels   {stat([l[0]['ms'][0] for l in laps])}")
         print(f"   {what} read-back {stat([l[0]['ms'][1] for l in laps])}")
@@ -149,5 +154,11 @@ for leg in legs:
         single("BASELINE configs[4] at the stated 1 000 000 pods", W.config5(pods=1_000_000, sizes=50, seed=46))
     elif leg == "whatifs":
         whatifs()
+    elif leg == "relax":
+        import audit_stages_cases
+        single("the relaxing family, seed 3 with existing nodes, scale 400", audit_stages_cases.relax_problem(3, True, scale=400))
+    elif leg == "relaxwide":
+        import audit_stages_cases
+        single("2 000 relaxing pods of 2 000 classes over 1 024 existing nodes", audit_stages_cases.many_relaxed(2000, nodes=1024))
     else:
         sys.exit(f"unknown leg {leg}")
