@@ -649,6 +649,23 @@ typedef struct ksh_audit_stages_out {
 int ksh_audit_stages(void** handles, uint32_t n, ksh_audit_stages_out* outs /* [n] */, double* ms /* [2] kernels | read-back, or NULL */);
 /* A claimed result for one flattened handle, exactly as ksh_audit_firstfit_claimed takes it. */
 int ksh_audit_stages_claimed(void* handle, const ksh_result_arrays* claimed, const int32_t* pod_seq /* [n_pods] */, ksh_audit_stages_out* out, double* ms /* [2] or NULL */);
+/* The audit's EIGHTH pass, opt-in (ksolve.h ks_audit_reasons_dev, KS_AUDIT_POD_REASON_*): the failure reasons -- pod_reason, the column recordSchedulingResults turns
+ * into PodFailedToSchedule events, against what a fresh node of every machine template answers the pod's class: a placed pod carries no word, an unscheduled pod a
+ * reason for each of the first eight templates, and wherever the flat problem alone decides the reason (taints, requirements, no instance type) the nibble equals it.
+ * Not one of the gate's passes: the shim calls it beside ksh_audit_gate, before it synthesises events.  The other passes' conventions (cap_pods,
+ * KSH_AUDIT_TRUNCATED_PODS, indices as ksh_audit's).  checked[0]: the unscheduled pods examined; [1]: their nibbles decided exactly; [2]: bounded to a set (a
+ * topology-constrained class: one of 5, 6, 7); [3]: not examined (KS_WHY_LIMITS on a limited template, a template without types). */
+typedef struct ksh_audit_reasons_out {
+  uint32_t* pod_flags; uint64_t cap_pods;      /* [cap_pods] KS_AUDIT_POD_REASON_* */
+  uint32_t n_pods, n_new, n_placed, n_unscheduled;
+  uint32_t skipped_pods, n_pods_flagged, truncated /* KSH_AUDIT_TRUNCATED_PODS */, used_classes;
+  uint32_t checked[4];
+  uint32_t pairs, pad;
+} ksh_audit_reasons_out;
+int ksh_audit_reasons(void** handles, uint32_t n, ksh_audit_reasons_out* outs /* [n] */, double* ms /* [2] kernels | read-back, or NULL */);
+/* A claimed result for one flattened handle: pod_node, pod_stage and pod_reason are read -- here pod_reason IS read --, nothing else and no commit numbers; a null
+ * pod_reason is KS_ERR_INVALID, the remaining refusals are ksh_audit_claimed's. */
+int ksh_audit_reasons_claimed(void* handle, const ksh_result_arrays* claimed, ksh_audit_reasons_out* out, double* ms /* [2] or NULL */);
 /* The GATE (ksolve.h ks_audit_gate_dev, KS_AUDIT_PASS_*): the passes of a mask in ONE call, their totals and a list of findings reduced on the device.  This is the
  * shim's gate: one call behind every result, and on a finding, solve in Go; the per-pass calls above remain the way to the flag rows.  No flag row is read back: for
  * every requested pass the caller gives an array of n of that pass's out structs and receives in each exactly the totals the pass's own call writes -- the tables and

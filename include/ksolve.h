@@ -979,6 +979,49 @@ typedef struct ks_audit_stages {
 int ks_audit_stages_dev(ks_dev_problem* d, const ks_result* claimed /* or NULL; pod_seq is read */, ks_audit_stages* out);
 int ks_audit_stages_batch_dev(ks_dev_problem* const* ds, uint32_t n, ks_audit_stages* const* outs);
 
+/* ---- the audit's EIGHTH pass, opt-in: FAILURE REASONS -- the one column of a result the seven passes above do not read, pod_reason (ks_result above: KS_WHY_* per
+ * machine template, four bits each, what the shim turns into PodFailedToSchedule events and "incompatible with provisioner ..., <reason>" lines).  Nothing calls it
+ * unless asked, the gate below included; the first seven passes are unchanged by it.  A fresh node of a template is static data and Node.Add (node.go:62-107) runs
+ * its steps in a fixed order -- taints, host ports, Compatible, topology, topology requirements, instance types --, so for many (pod, template) pairs the nibble has
+ * exactly one right value: those get an EQUALITY check.  w = pod_reason[P]; M templates; MT = min(M, 8); c = the class of the stage the result claims (aud_class).
+ * On the whole word: */
+#define KS_AUDIT_POD_REASON_PLACED 4194304u    /* P names a node of the result and w != 0: both pack kernels and the oracle clear the word on every successful add */
+#define KS_AUDIT_POD_REASON_MISSING 8388608u   /* P is unscheduled (pod_node == -1), pod_stage in range, and some template m < MT has nibble KS_WHY_NONE: add returns an error only after every template produced one (scheduler.go:193-218) */
+#define KS_AUDIT_POD_REASON_SHAPE 16777216u    /* such a P, and: a nibble at m >= M is non-zero; or a nibble is above 7; or is KS_WHY_HOST_PORTS (a fresh node has no port in use); or is KS_WHY_LIMITS on a template without limits (tmpl_limit_present[m] == 0xFFFFFFFF) */
+#define KS_AUDIT_POD_REASON_STATIC 33554432u   /* such a P, and a nibble at m < MT that neither MISSING nor SHAPE flags contradicts the static verdict s(c, m) below */
+/* s(c, m), from the flat problem through ks_algebra.h alone (no mc_* table, no feasibility grid: those are the pack kernels' own), in Node.Add's order:
+ *   1. tmpl_taints[m] & ~cls_tolerated[c] != 0                                                                 -> 2 (TAINTS)
+ *   2. cls_hn_mode[c] == 1 (a fresh node's hostname is a placeholder no pod names, node.go:46); or kreq_compatible_fail(template, class) on any key -- the EXACT
+ *      Compatible, with its custom-label rule and its NotIn / DoesNotExist exception; or the its_fail entry of the two it_states   -> 4 (REQUIREMENTS)
+ *   3. c is not examinable in the fourth pass's sense (an own group, an inverse group or a host port)           -> U (undecided: topology speaks next)
+ *   4. filterInstanceTypesByRequirements over the template's FULL type set, its daemon overhead plus the class's requests and the merged requirements:
+ *      a type passes -> 0, none does -> 7 (NO_INSTANCE_TYPE)
+ * The verdict on the nibble at m < MT of an unscheduled pod:
+ *   template without limits:  s in {2, 4, 7, 0}: the nibble is exactly s (0: KS_WHY_NONE, which MISSING flags -- the fourth pass's FIT_TEMPLATE with the exact Compatible);
+ *                             s == U: the nibble is one of {5, 6, 7}
+ *   template with limits:     KS_WHY_LIMITS is always allowed and not examined (counted); otherwise s in {2, 4}: exactly s; s in {7, 0}: 7 (the limit only shrinks
+ *                             the type set); s == U: one of {5, 6, 7}
+ * NOT attempted: whether a LIMITS nibble on a limited template is true; which of {5, 6, 7} a topology-constrained class carries; templates from the ninth on (they
+ * have no nibble); pods whose pod_stage is out of range (the first pass's RANGE); a template that lists no instance type at all (counted with the unexamined). */
+typedef struct ks_audit_reasons {
+  uint32_t* pod_flags;            /* [P] KS_AUDIT_POD_REASON_*, or NULL (totals only) */
+  uint32_t n_pods, n_new;         /* out: P | the new nodes of the result that was audited */
+  uint32_t n_placed;              /* out: pods on a node of the result: each examined for PLACED */
+  uint32_t n_unscheduled;         /* out: pods with pod_node == -1 */
+  uint32_t skipped_pods;          /* out: the pods neither placed nor examined: a stage out of range, a node the result does not have */
+  uint32_t n_pods_flagged;
+  uint32_t checked[4];            /* out: [0] the unscheduled pods examined; [1] their nibbles decided exactly; [2] their nibbles bounded to a set; [3] their nibbles not examined (LIMITS on a limited template, a template without types): [1] + [2] + [3] == min(M, 8) * [0] */
+  uint32_t used_classes, pairs;   /* out: the distinct classes of the examined pods | the (class, template) verdicts computed: used_classes * min(M, 8) */
+  double kernel_ms, readback_ms;  /* out: as ks_audit's */
+} ks_audit_reasons;
+/* claimed == NULL: the resident result, where it lies (the form for derived what-ifs).  claimed given (flattened problems only, KS_ERR_UNSUPPORTED for a derived
+ * view): pod_node, pod_stage and pod_reason are uploaded and read, nothing else and no commit numbers; a null pod_reason is KS_ERR_INVALID "claimed result: null
+ * array pod_reason"; the remaining refusals are ks_audit_dev's.  Four launches with no host wait between them: mark, the fourth pass's compaction, one wave per
+ * (used class, template) pair, verdict; with no unscheduled pod the third finds an empty list and the fourth repeats the first one's words.  Integer only; flags are
+ * written per index, no output through an atomic: the same flags every run. */
+int ks_audit_reasons_dev(ks_dev_problem* d, const ks_result* claimed /* or NULL; pod_node, pod_stage, pod_reason are read */, ks_audit_reasons* out);
+int ks_audit_reasons_batch_dev(ks_dev_problem* const* ds, uint32_t n, ks_audit_reasons* const* outs);
+
 /* ---- the audit's GATE: chosen passes in ONE call, their totals and a list of FINDINGS reduced on the device.  The question a caller puts behind every result is
  * "is it clean?", and the answer is usually yes: the gate runs the chosen passes' own kernels, leaves their flag tables on the device, tallies them there and reads
  * back the totals alone -- no row of a flag table reaches the host.  The six passes and their entry points above are unchanged by it; they remain the way to the rows.

@@ -4393,7 +4393,7 @@ extern "C" int ks_placement_rows_host(ks_dev_problem* const* ds, uint32_t n, con
   return KS_OK;
 }
 
-// The order matters: ks_audit.inc's host half is the host path of all seven passes (the claimed upload, the resident prelude, the pooled work block, the launch rows,
+// The order matters: ks_audit.inc's host half is the host path of all eight passes (the claimed upload, the resident prelude, the pooled work block, the launch rows,
 // the tallies, the slice walker -- DESIGN.md 7.26), and the device helpers the later files share stand beside its own; each later file adds a view, kernels and one run function.
 #include "ks_audit.inc"      // the audit of a result against its problem (ks_audit_dev / ks_audit_batch_dev), and what every pass's host half calls; between its two
                              // halves it includes ks_audit_reduce.inc, the gate's kernels (ks_audit_gate_dev / ks_audit_gate_batch_dev / ks_audit_reduce_rows): they
@@ -4404,6 +4404,7 @@ extern "C" int ks_placement_rows_host(ks_dev_problem* const* ds, uint32_t n, con
 #include "ks_audit_limits.inc"   // its fifth, opt-in pass: provisioner limits in opening order (ks_audit_limits_dev / ks_audit_limits_batch_dev)
 #include "ks_audit_hostfit.inc"  // its sixth, opt-in pass: first-fit order for hostname anti-affinity and hostname spread pods (ks_audit_hostfit_dev / ks_audit_hostfit_batch_dev)
 #include "ks_audit_stages.inc"   // its seventh, opt-in pass: relaxation order -- no pod ended at a later stage than one an existing node or a fresh machine would have taken it at (ks_audit_stages_dev / ks_audit_stages_batch_dev)
+#include "ks_audit_reasons.inc"  // its eighth, opt-in pass: failure reasons -- pod_reason's nibbles against what a fresh node of every template answers the pod's class (ks_audit_reasons_dev / ks_audit_reasons_batch_dev)
 
 // ------------------------------------------------------------------------------------------------
 // Consolidation candidates (ksolve.h ks_consolidation_candidates_host): which nodes sortAndFilterCandidates keeps, and in what order.

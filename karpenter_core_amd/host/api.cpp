@@ -10,6 +10,7 @@
 #include <cstring>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <unordered_map>
 
 #include "encode.hpp"
@@ -833,7 +834,7 @@ int ksh_placement_rows(void** hv, uint32_t n, const uint64_t* ids, uint64_t* out
   });
 }
 }  // extern "C"
-// The audit's seven passes (kshost.h ksh_audit* / ksh_audit*_claimed).  What a pass is to this file: its table in libksolve and in kshost.h, whether it has a node
+// The audit's eight passes (kshost.h ksh_audit* / ksh_audit*_claimed).  What a pass is to this file: its table in libksolve and in kshost.h, whether it has a node
 // table beside the pod table, its two entry points in libksolve, whether its claimed form comes without commit numbers, and the totals it copies.
 namespace {
 struct AuditFirst {
@@ -893,6 +894,17 @@ struct AuditStages {
     memcpy(o->checked, r.checked, sizeof o->checked); o->admitting_pairs = r.admitting_pairs; o->pad = 0;
   }
 };
+struct AuditReasons {
+  using Dev = ks_audit_reasons; using Out = ksh_audit_reasons_out; static constexpr bool nodes = false, no_pod_seq = true, reads_reason = true;
+  static constexpr auto batch_dev = ks_audit_reasons_batch_dev; static constexpr auto one_dev = ks_audit_reasons_dev;
+  static void totals(const Dev& r, Out* o) {
+    o->n_pods = r.n_pods; o->n_new = r.n_new; o->n_placed = r.n_placed; o->n_unscheduled = r.n_unscheduled; o->skipped_pods = r.skipped_pods; o->n_pods_flagged = r.n_pods_flagged;
+    o->used_classes = r.used_classes; memcpy(o->checked, r.checked, sizeof o->checked); o->pairs = r.pairs; o->pad = 0;
+  }
+};
+// does the pass's claimed form read pod_reason (and neither the unscheduled list nor commit numbers)?  Only a pass that says so
+template <class P, class = void> struct audit_reads_reason : std::false_type {};
+template <class P> struct audit_reads_reason<P, std::void_t<decltype(P::reads_reason)>> : std::true_type {};
 // A pass's tables: libksolve fills tables of the library's own, sized from the device problems; the totals always reach the caller, the flag rows only when they fit
 template <class P> struct AuditTables {
   using Dev = typename P::Dev;
@@ -957,10 +969,12 @@ template <class P> int audit_claimed(void* hv, const ksh_result_arrays* c, const
   if (h->delta || h->enc->view) return set_err(KS_ERR_UNSUPPORTED, "a claimed result is audited against a flattened problem, not against a what-if derived on the device");
   return guarded([&] {
     const ks_problem& p = h->enc->prob; ks_result r;
-    int rc = claimed_result(p, c, P::no_pod_seq, pod_seq, &r); if (rc != KS_OK) return rc;
+    constexpr bool reasons = audit_reads_reason<P>::value;
+    int rc = claimed_result(p, c, P::no_pod_seq && !reasons, pod_seq, &r); if (rc != KS_OK) return rc;
+    if (reasons) r.pod_reason = (uint32_t*)c->pod_reason;
     rc = ensure_resident(h); if (rc != KS_OK) return rc;
     std::vector<int32_t> seq, un;
-    if (P::no_pod_seq) {
+    if (P::no_pod_seq && !reasons) {
       // ks_result's shape: the unscheduled list in an array of P, and commit numbers -- ksh_result_arrays has none, so placed pods are numbered in pod order
       seq.assign((size_t)p.P + 1, -1); un.assign((size_t)p.P + 1, -1);
       { int32_t k = 0; for (uint32_t i = 0; i < p.P; ++i) if (c->pod_node[i] != -1) seq[i] = k++; }
@@ -1051,6 +1065,8 @@ int ksh_audit_hostfit(void** hv, uint32_t n, ksh_audit_hostfit_out* outs, double
 int ksh_audit_hostfit_claimed(void* hv, const ksh_result_arrays* c, const int32_t* pod_seq, ksh_audit_hostfit_out* out, double* ms) { return audit_claimed<AuditHostFit>(hv, c, pod_seq, out, ms); }
 int ksh_audit_stages(void** hv, uint32_t n, ksh_audit_stages_out* outs, double* ms) { return audit_resident<AuditStages>(hv, n, outs, ms); }
 int ksh_audit_stages_claimed(void* hv, const ksh_result_arrays* c, const int32_t* pod_seq, ksh_audit_stages_out* out, double* ms) { return audit_claimed<AuditStages>(hv, c, pod_seq, out, ms); }
+int ksh_audit_reasons(void** hv, uint32_t n, ksh_audit_reasons_out* outs, double* ms) { return audit_resident<AuditReasons>(hv, n, outs, ms); }
+int ksh_audit_reasons_claimed(void* hv, const ksh_result_arrays* c, ksh_audit_reasons_out* out, double* ms) { return audit_claimed<AuditReasons>(hv, c, nullptr, out, ms); }
 }  // extern "C"
 // What getNodePrices / filterOutSameType / simulateScheduling's readiness rule read of the snapshot's nodes, once per call
 namespace {

@@ -59,6 +59,11 @@ KS_AUDIT_HOSTFIT_CHECKED = ("SEQ", "PODS", "PAIRS", "TESTS")
 # state and fresh machines of unlimited templates; `checked`: placed pods, pods with an examined stage, examined stages, (class, node-or-template) pairs
 KS_AUDIT_STAGES_BITS = {"SEQ": 128, "STAGE_EXISTING": 524288, "STAGE_TEMPLATE": 1048576, "STAGE_UNRELAXED": 2097152}
 KS_AUDIT_STAGES_CHECKED = ("SEQ", "PODS", "STAGES", "PAIRS")
+# the eighth pass's (FlatProblem.audit_reasons() / audit_reasons_batch()): pod_reason's nibbles (KS_WHY_* per machine template) against what a fresh node of every template
+# answers the pod's class; `checked`: unscheduled pods examined, nibbles decided exactly, nibbles bounded to a set, nibbles not examined
+KS_AUDIT_REASONS_BITS = {"REASON_PLACED": 4194304, "REASON_MISSING": 8388608, "REASON_SHAPE": 16777216, "REASON_STATIC": 33554432}
+KS_AUDIT_REASONS_CHECKED = ("PODS", "EXACT", "BOUNDED", "UNEXAMINED")
+KS_WHY = {"NONE": 0, "LIMITS": 1, "TAINTS": 2, "HOST_PORTS": 3, "REQUIREMENTS": 4, "TOPOLOGY": 5, "TOPOLOGY_REQS": 6, "NO_INSTANCE_TYPE": 7}      # ksolve.h KS_WHY_*
 
 
 class KSolveError(RuntimeError):
@@ -397,6 +402,14 @@ class FlatProblem:
         stopped short of its chain's end.  Not one of the gate's passes.  Arguments as `audit_topology`'s.  Returns `audit_firstfit`'s dict ("checked": SEQ, PODS the
         pods with an examined earlier stage, STAGES those stages, PAIRS the (class, node-or-template) pairs)."""
         return _audit("stages", [self], claimed, pod_seq)[0]
+
+    def audit_reasons(self, claimed: Optional[dict] = None) -> dict:
+        """The audit's eighth, opt-in pass (include/ksolve.h KS_AUDIT_POD_REASON_*, kshost.h ksh_audit_reasons / ksh_audit_reasons_claimed): the failure reasons -- a
+        placed pod carries no word, an unscheduled pod a KS_WHY_* nibble for each of the first eight templates, and where the flat problem alone decides the nibble
+        (taints, requirements, no instance type) it is that value.  Not one of the gate's passes.  `claimed`: a result in `result_arrays()`' form, of which
+        pod_node, pod_stage and pod_reason are read; no commit numbers.  Returns {"pod_flags", "n_pods_flagged", "pod_bit_count", "checked": PODS the unscheduled
+        pods examined, EXACT / BOUNDED / UNEXAMINED their nibbles, "skipped_pods", "n_unscheduled", "used_classes", "pairs", "n_new", "n_placed", "ms"}."""
+        return _audit("reasons", [self], claimed)[0]
 
     def audit_gate(self, claimed: Optional[dict] = None, pod_seq=None, passes=None, cap_findings: int = 1024, findings_table=None) -> dict:
         """The audit's gate (include/ksolve.h KS_AUDIT_PASS_*, kshost.h ksh_audit_gate / ksh_audit_gate_claimed): the passes named in `passes` (default: all six) in one
@@ -866,11 +879,21 @@ _AUDIT_PASSES_BESIDE = {
                    scalars=("admitting_pairs", "skipped_pods", "n_new", "n_placed")),
 }
 
-for _p in list(_AUDIT_PASSES.values()) + list(_AUDIT_PASSES_BESIDE.values()):      # include/kshost.h <stem>_out: the tables and their capacities, then `fields`
+# The pass over pod_reason: in the same form, in a table of its own -- the two above stay what they were.  Its claimed form reads pod_reason, which no other pass
+# uploads, and takes no commit numbers.
+_AUDIT_PASSES_REASONS = {
+    "reasons": dict(stem="ksh_audit_reasons", seq=False, out="_AuditReasonsOut", claimed=(("pod_reason", "uint32"),), pod_bits=KS_AUDIT_REASONS_BITS, node_bits=None,
+                    checked=KS_AUDIT_REASONS_CHECKED,
+                    fields=("n_pods", "n_new", "n_placed", "n_unscheduled", "skipped_pods", "n_pods_flagged", "truncated", "used_classes", "checked*4", "pairs", "pad"),
+                    scalars=("skipped_pods", "n_unscheduled", "used_classes", "pairs", "n_new", "n_placed")),
+}
+
+for _p in list(_AUDIT_PASSES.values()) + list(_AUDIT_PASSES_BESIDE.values()) + list(_AUDIT_PASSES_REASONS.values()):      # include/kshost.h <stem>_out: the tables and their capacities, then `fields`
     _tables = [("pod_flags", ctypes.c_void_p), ("cap_pods", ctypes.c_uint64)] + ([("node_flags", ctypes.c_void_p), ("cap_nodes", ctypes.c_uint64)] if _p["node_bits"] else [])
     _p["Out"] = type(_p["out"], (ctypes.Structure,), {"_fields_": _tables + [(n, ctypes.c_uint32 * int(k) if k else ctypes.c_uint32) for n, _, k in (f.partition("*") for f in _p["fields"])]})
 _AuditOut, _AuditTopologyOut, _AuditSpreadOut, _AuditFirstFitOut, _AuditLimitsOut, _AuditHostFitOut = (_AUDIT_PASSES[w]["Out"] for w in ("audit", "topology", "spread", "firstfit", "limits", "hostfit"))
 _AuditStagesOut = _AUDIT_PASSES_BESIDE["stages"]["Out"]
+_AuditReasonsOut = _AUDIT_PASSES_REASONS["reasons"]["Out"]
 
 
 def _claimed_arrays(flat: "FlatProblem", claimed: dict, pod_seq, beyond, what: str):
@@ -897,7 +920,7 @@ def _claimed_arrays(flat: "FlatProblem", claimed: dict, pod_seq, beyond, what: s
 
 
 def _audit(what: str, flats: Sequence["FlatProblem"], claimed: Optional[dict] = None, pod_seq=None) -> List[dict]:
-    """One pass of the audit, as _AUDIT_PASSES[what] (or _AUDIT_PASSES_BESIDE[what]) states it: the call over the resident results of `flats`, or over `claimed` (with `pod_seq`, where the pass takes
+    """One pass of the audit, as _AUDIT_PASSES[what] (or _AUDIT_PASSES_BESIDE[what], or _AUDIT_PASSES_REASONS[what]) states it: the call over the resident results of `flats`, or over `claimed` (with `pod_seq`, where the pass takes
     it) for flats[0]; once more with larger tables if one was too short.  One dict per problem."""
     import numpy as np
     if claimed is None and pod_seq is not None:
@@ -905,7 +928,7 @@ def _audit(what: str, flats: Sequence["FlatProblem"], claimed: Optional[dict] = 
     n = len(flats)
     if not n:
         return []
-    p, kh = _AUDIT_PASSES.get(what) or _AUDIT_PASSES_BESIDE[what], libs()[1]
+    p, kh = _AUDIT_PASSES.get(what) or _AUDIT_PASSES_BESIDE.get(what) or _AUDIT_PASSES_REASONS[what], libs()[1]
     Out, nodes = p["Out"], p["node_bits"] is not None
     resident, claimed_fn = getattr(kh, p["stem"]), getattr(kh, p["stem"] + "_claimed")
     resident.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32, ctypes.POINTER(Out), ctypes.POINTER(ctypes.c_double)]
@@ -1074,6 +1097,12 @@ def audit_stages_batch(flats: Sequence["FlatProblem"]) -> List[dict]:
     """The audit's seventh pass over the results the last solve left on the device, for a whole batch (include/kshost.h ksh_audit_stages): handles of any kind, derived
     what-ifs included.  One dict per problem, as `FlatProblem.audit_stages` returns it."""
     return _audit("stages", flats)
+
+
+def audit_reasons_batch(flats: Sequence["FlatProblem"]) -> List[dict]:
+    """The audit's eighth pass over the results the last solve left on the device, for a whole batch (include/kshost.h ksh_audit_reasons): handles of any kind, derived
+    what-ifs included.  One dict per problem, as `FlatProblem.audit_reasons` returns it."""
+    return _audit("reasons", flats)
 
 
 def deal_lpt(weights: Sequence[int], nshards: int) -> List[int]:

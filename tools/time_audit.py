@@ -3,9 +3,10 @@
 same run on the same box next to the pack kernel time of that Solve, what each pass examined -- `checked` by name and every counter it returns --, and whether it found
 anything.  Needs a GPU.
    usage: tools/time_audit.py <pass>[,<pass>] [legs, comma separated] [reps]      (defaults: config3,whatifs,config5 9)
-   pass   audit | topology | spread | firstfit | limits | hostfit (scheduler._AUDIT_PASSES) | stages (scheduler._AUDIT_PASSES_BESIDE); the first one named is the
-          subject, the others are timed beside it (hostfit,firstfit: the sixth pass beside the fourth, with the cost per evaluated pair of each; stages,firstfit:
-          the seventh beside the fourth, whose pair kernels it runs over fewer classes)
+   pass   audit | topology | spread | firstfit | limits | hostfit (scheduler._AUDIT_PASSES) | stages (scheduler._AUDIT_PASSES_BESIDE) | reasons
+          (scheduler._AUDIT_PASSES_REASONS); the first one named is the subject, the others are timed beside it (hostfit,firstfit: the sixth pass beside the fourth,
+          with the cost per evaluated pair of each; stages,firstfit: the seventh beside the fourth, whose pair kernels it runs over fewer classes; reasons,audit: the
+          eighth beside the first, the other pass that reads no commit numbers)
           gate   the audit's gate (ksh_audit_gate) over the passes named beside it -- all six if it is named alone --, with no findings table: one call, totals
                  reduced on the device.  Timed in the same run as those passes' own calls, and set against their sum.  The what-ifs are `limits`' snapshot
    legs   config3       BASELINE configs[2]: 100 000 pods / 2 000 types (workloads.config3 seed 44) -- bench.py's contract workload; no limited template
@@ -18,6 +19,8 @@ anything.  Needs a GPU.
           relax         tests/audit_stages_cases.py's family -- pods whose preferences cannot hold, over three existing nodes -- scaled until some thousand pods relax
           relaxwide     2 000 pods of 2 000 different requests that all relax once, over 1 024 existing nodes: as many distinct earlier-stage classes as pods, so that
                         the pair kernels, not the launches, are what is timed
+          stay          tests/audit_reasons_cases.py's family -- pods that stay unscheduled, each kind on purpose, nine provisioners of mixed kinds over two existing
+                        nodes -- scaled until some thousand pods of many hundred classes stay unscheduled
 Per leg: the Solve (its pack kernel time as the library reports it), one untimed call of each pass, then each pass `reps` times: median with min and max of the
 kernels' lap (inputs up, the launches, completion) and of the read-back lap (the flag words to the host and the totals), milliseconds."""
 import os, statistics, sys, time
@@ -25,7 +28,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 from karpenter_core_amd import fake, scheduler as S, workloads as W
 
-PASSES = dict(S._AUDIT_PASSES, **S._AUDIT_PASSES_BESIDE)      # every pass with a call of its own; the gate runs the first table's
+PASSES = dict(S._AUDIT_PASSES, **S._AUDIT_PASSES_BESIDE, **S._AUDIT_PASSES_REASONS)      # every pass with a call of its own; the gate runs the first table's
 if len(sys.argv) < 2 or not all(p in PASSES or p == "gate" for p in sys.argv[1].split(",")):
     sys.exit(__doc__)
 passes = sys.argv[1].split(",")
@@ -160,5 +163,8 @@ for leg in legs:
     elif leg == "relaxwide":
         import audit_stages_cases
         single("2 000 relaxing pods of 2 000 classes over 1 024 existing nodes", audit_stages_cases.many_relaxed(2000, nodes=1024))
+    elif leg == "stay":
+        import audit_reasons_cases
+        single("the unscheduled family, seed 7 with nine provisioners and existing nodes, scale 300", audit_reasons_cases.stay_problem(**dict(audit_reasons_cases.FAMILY[6][1], scale=300)))
     else:
         sys.exit(f"unknown leg {leg}")
