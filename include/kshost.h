@@ -636,7 +636,7 @@ int ksh_audit_hostfit(void** handles, uint32_t n, ksh_audit_hostfit_out* outs /*
 int ksh_audit_hostfit_claimed(void* handle, const ksh_result_arrays* claimed, const int32_t* pod_seq /* [n_pods] */, ksh_audit_hostfit_out* out, double* ms /* [2] or NULL */);
 /* The audit's SEVENTH pass, opt-in (ksolve.h ks_audit_stages_dev, KS_AUDIT_POD_STAGE_*): relaxation order -- no pod ended at a later stage of its chain than one at
  * which an existing node's final state, or a fresh machine of a provisioner without limits, would have taken it, and no unscheduled pod stopped short of its chain's
- * end.  It is not one of the gate's passes yet: the shim calls it beside ksh_audit_gate.  The fourth pass's conventions (cap_pods, KSH_AUDIT_TRUNCATED_PODS, indices
+ * end.  It is the gate's seventh pass (KS_AUDIT_PASS_STAGES through ksh_audit_gate_ex); this call remains the way to its flag rows.  The fourth pass's conventions (cap_pods, KSH_AUDIT_TRUNCATED_PODS, indices
  * as ksh_audit's).  checked[0]: the placed pods; [1]: the pods with an examined earlier stage (skipped_pods: the others -- most pods never relax); [2]: the examined
  * stages; [3]: the (class, existing-node-or-template) pairs evaluated; admitting_pairs: the pairs that admitted -- none in a clean result. */
 typedef struct ksh_audit_stages_out {
@@ -652,7 +652,8 @@ int ksh_audit_stages_claimed(void* handle, const ksh_result_arrays* claimed, con
 /* The audit's EIGHTH pass, opt-in (ksolve.h ks_audit_reasons_dev, KS_AUDIT_POD_REASON_*): the failure reasons -- pod_reason, the column recordSchedulingResults turns
  * into PodFailedToSchedule events, against what a fresh node of every machine template answers the pod's class: a placed pod carries no word, an unscheduled pod a
  * reason for each of the first eight templates, and wherever the flat problem alone decides the reason (taints, requirements, no instance type) the nibble equals it.
- * Not one of the gate's passes: the shim calls it beside ksh_audit_gate, before it synthesises events.  The other passes' conventions (cap_pods,
+ * It is the gate's eighth pass (KS_AUDIT_PASS_REASONS through ksh_audit_gate_ex), which the shim calls before it synthesises events; this call remains the way to its
+ * flag rows.  The other passes' conventions (cap_pods,
  * KSH_AUDIT_TRUNCATED_PODS, indices as ksh_audit's).  checked[0]: the unscheduled pods examined; [1]: their nibbles decided exactly; [2]: bounded to a set (a
  * topology-constrained class: one of 5, 6, 7); [3]: not examined (KS_WHY_LIMITS on a limited template, a template without types). */
 typedef struct ksh_audit_reasons_out {
@@ -685,6 +686,26 @@ int ksh_audit_gate(void** handles, uint32_t n, uint32_t passes /* KS_AUDIT_PASS_
  * ksh_audit_topology_claimed takes it -- it may be NULL only when KS_AUDIT_PASS_FIRST is the whole mask; the first pass reads the placed pods numbered in pod order,
  * as ksh_audit_claimed gives them to it, whatever pod_seq says.  out's arrays hold one struct each. */
 int ksh_audit_gate_claimed(void* handle, const ksh_result_arrays* claimed, const int32_t* pod_seq /* [n_pods] */, uint32_t passes, ksh_audit_gate_out* out, double* ms /* [2] or NULL */);
+/* The gate over ALL EIGHT passes (ksolve.h ks_audit_gate_ex_dev, KS_AUDIT_PASS_STAGES, KS_AUDIT_PASS_REASONS, KS_AUDIT_PASS_ALL_EX): ONE call behind every result.
+ * ksh_audit_gate_out above is pinned -- its layout and bit 64's refusal through the two calls above stay --, so the wide form is a struct that can grow:
+ * struct_size leads, the caller's sizeof, and the passes after the sixth have their pointers at the END, in the order of their bits.  A mask bit is known iff it
+ * lies within KS_AUDIT_PASS_ALL_EX and its pointer lies wholly within struct_size; any other bit is KS_ERR_INVALID "audit gate: unknown pass", as is a struct_size
+ * below the offset of `stages`.  Everything else -- totals, findings (pass 6 and 7 in `where` for the two new passes, pod tables only), their order, n_findings,
+ * the truncation bit, the untouched tail, capacity 0 -- is ksh_audit_gate's. */
+typedef struct ksh_audit_gate_ex_out {
+  uint32_t struct_size, pad;      /* in: sizeof(ksh_audit_gate_ex_out) as the caller was compiled */
+  ks_audit_finding* findings; uint64_t cap_findings;
+  ksh_audit_out* audit; ksh_audit_topology_out* topology; ksh_audit_spread_out* spread; ksh_audit_firstfit_out* firstfit; ksh_audit_limits_out* limits; ksh_audit_hostfit_out* hostfit;   /* [n] each, for the requested passes */
+  uint32_t n_findings, truncated /* KS_AUDIT_GATE_TRUNCATED */;
+  ksh_audit_stages_out* stages;   /* [n], for KS_AUDIT_PASS_STAGES */
+  ksh_audit_reasons_out* reasons; /* [n], for KS_AUDIT_PASS_REASONS */
+} ksh_audit_gate_ex_out;
+int ksh_audit_gate_ex(void** handles, uint32_t n, uint32_t passes /* KS_AUDIT_PASS_* */, ksh_audit_gate_ex_out* out, double* ms /* [2] kernels | read-back, or NULL */);
+/* A claimed result for one flattened handle through the wide gate: taken once and uploaded once, with the union of the arrays the requested passes read -- pod_reason
+ * (ksh_result_arrays) among them only when KS_AUDIT_PASS_REASONS is requested; a null pod_reason is then that pass's refusal, after every earlier pass's.  pod_seq
+ * may be NULL only when the mask lies within KS_AUDIT_PASS_FIRST | KS_AUDIT_PASS_REASONS, the two passes that take no commit numbers; the first pass reads the
+ * placed pods numbered in pod order, as ksh_audit_claimed gives them to it, whatever pod_seq says. */
+int ksh_audit_gate_ex_claimed(void* handle, const ksh_result_arrays* claimed, const int32_t* pod_seq /* [n_pods] */, uint32_t passes, ksh_audit_gate_ex_out* out, double* ms /* [2] or NULL */);
 
 /* ---- the snapshot kept current by EVENTS ("cached incremental SoA builder fed from state.Cluster") ----
  * Replaces, for the snapshot consolidation simulates over, what the reference does between two passes of the deprovisioner (deprovisioning/controller.go:64,

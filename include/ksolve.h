@@ -944,7 +944,7 @@ int ks_audit_hostfit_dev(ks_dev_problem* d, const ks_result* claimed /* or NULL;
 int ks_audit_hostfit_batch_dev(ks_dev_problem* const* ds, uint32_t n, ks_audit_hostfit* const* outs);
 
 /* ---- the audit's SEVENTH pass, opt-in: RELAXATION ORDER -- the one column of a result the six passes above take on trust, pod_stage.  Nothing calls it unless
- * asked, the gate below included; the first six passes are unchanged by it.  Solve relaxes a pod one step per failed add (scheduler.go:118-127, preferences.go:36-145):
+ * asked: the gate below runs it for KS_AUDIT_PASS_STAGES (ks_audit_gate_ex); the first six passes are unchanged by it.  Solve relaxes a pod one step per failed add (scheduler.go:118-127, preferences.go:36-145):
  * a pod P that ended at stage k = pod_stage[P], placed or unscheduled, was tried and refused at every stage j < k, each try at some moment before the end.  Let
  * c_j = stage_cls[pod_stage_off[gp] + j].  By the fourth pass's monotonicity two kinds of target need no knowledge of WHEN stage j was tried: an existing node was
  * there from the start and only filled up, and a fresh node of a template without limits is static data.  One-sided like passes two to six: it flags only what no run
@@ -981,7 +981,7 @@ int ks_audit_stages_batch_dev(ks_dev_problem* const* ds, uint32_t n, ks_audit_st
 
 /* ---- the audit's EIGHTH pass, opt-in: FAILURE REASONS -- the one column of a result the seven passes above do not read, pod_reason (ks_result above: KS_WHY_* per
  * machine template, four bits each, what the shim turns into PodFailedToSchedule events and "incompatible with provisioner ..., <reason>" lines).  Nothing calls it
- * unless asked, the gate below included; the first seven passes are unchanged by it.  A fresh node of a template is static data and Node.Add (node.go:62-107) runs
+ * unless asked: the gate below runs it for KS_AUDIT_PASS_REASONS (ks_audit_gate_ex); the first seven passes are unchanged by it.  A fresh node of a template is static data and Node.Add (node.go:62-107) runs
  * its steps in a fixed order -- taints, host ports, Compatible, topology, topology requirements, instance types --, so for many (pod, template) pairs the nibble has
  * exactly one right value: those get an EQUALITY check.  w = pod_reason[P]; M templates; MT = min(M, 8); c = the class of the stage the result claims (aud_class).
  * On the whole word: */
@@ -1041,7 +1041,7 @@ int ks_audit_reasons_batch_dev(ks_dev_problem* const* ds, uint32_t n, ks_audit_r
 #define KS_AUDIT_GATE_TRUNCATED 1u
 typedef struct ks_audit_finding {
   uint32_t problem;               /* the problem's position in the batch (0 for the single form) */
-  uint32_t where;                 /* pass << 8 | table: pass = the index of its mask bit (0 first .. 5 hostfit), table 0 = pod_flags, 1 = node_flags */
+  uint32_t where;                 /* pass << 8 | table: pass = the index of its mask bit (0 first .. 5 hostfit; 6 stages, 7 reasons through ks_audit_gate_ex), table 0 = pod_flags, 1 = node_flags */
   uint32_t index;                 /* the pod, or the node slot */
   uint32_t flags;                 /* the flag word, as the pass's own table holds it */
 } ks_audit_finding;
@@ -1063,6 +1063,36 @@ typedef struct ks_audit_gate {
  * hostfit) reduces per slice; slices are consecutive runs of problems, so the findings keep their order. */
 int ks_audit_gate_dev(ks_dev_problem* d, const ks_result* claimed /* or NULL */, ks_audit_gate* gate);
 int ks_audit_gate_batch_dev(ks_dev_problem* const* ds, uint32_t n, ks_audit_gate* gate);
+/* The gate over ALL EIGHT passes, in a struct that can grow.  ks_audit_gate above is pinned: its size, its six pointers and KS_AUDIT_PASS_ALL stay what they are, and
+ * bit 64 through the two calls above stays "audit gate: unknown pass".  ks_audit_gate_ex carries everything ks_audit_gate carries -- same meaning, same rules, same
+ * findings, where = 6 << 8 and 7 << 8 for the two new passes, which have a pod table only -- behind a leading struct_size, the caller's sizeof, and the later passes'
+ * pointers AFTER everything else: a ninth pass appends a pointer and a bit, not a third family of entry points.  A mask bit is KNOWN iff it lies within
+ * KS_AUDIT_PASS_ALL_EX and its pointer lies wholly within struct_size; anything else is KS_ERR_INVALID "audit gate: unknown pass" (so a caller compiled against a
+ * shorter struct is refused a pass it has no pointer for, and never has memory behind its struct read).  struct_size below the offset of `stages` is KS_ERR_INVALID.
+ * The two calls above are this gate restricted to the six bits and the old struct: one function.
+ * Under the gate the seventh pass queues all six of its launches and meets the host once, like every other pass: the decision its own call takes on the host between
+ * the second and the third launch is taken on the device, per problem -- a problem in which no pod relaxed compacts an empty class list, the two pair kernels make no
+ * trip for it and the verdict repeats the mark kernel's words, whatever its neighbours in the batch do.
+ * Claimed form: the upload carries the union of what the requested passes read; pod_reason travels (beside the block, as first_pod_seq does) only when
+ * KS_AUDIT_PASS_REASONS is requested, and a null pod_reason is then that pass's own refusal, "claimed result: null array pod_reason", at its place in the mask order
+ * -- the last.  Without that bit a null pod_reason is accepted as before. */
+#define KS_AUDIT_PASS_STAGES 64u     /* ks_audit_stages_dev */
+#define KS_AUDIT_PASS_REASONS 128u   /* ks_audit_reasons_dev */
+#define KS_AUDIT_PASS_ALL_EX 255u
+typedef struct ks_audit_gate_ex {
+  uint32_t struct_size;           /* in: sizeof(ks_audit_gate_ex) as the caller was compiled */
+  uint32_t passes;                /* in: KS_AUDIT_PASS_*, at least one, each of them known (above) */
+  uint32_t cap_findings, pad;     /* in: records `findings` holds */
+  ks_audit_finding* findings;     /* in: the caller's table, or NULL with cap_findings == 0 */
+  ks_audit* first; ks_audit_topology* topology; ks_audit_spread* spread; ks_audit_firstfit* firstfit; ks_audit_limits* limits; ks_audit_hostfit* hostfit;
+  const int32_t* first_pod_seq;   /* in, claimed form only: as ks_audit_gate's */
+  uint32_t n_findings, truncated; /* out: as ks_audit_gate's */
+  double kernel_ms, readback_ms;  /* out: as ks_audit_gate's */
+  ks_audit_stages* stages;        /* in: bit 64's array of one out struct per problem.  The passes after the sixth follow here, in the order of their bits */
+  ks_audit_reasons* reasons;      /* in: bit 128's */
+} ks_audit_gate_ex;
+int ks_audit_gate_ex_dev(ks_dev_problem* d, const ks_result* claimed /* or NULL */, ks_audit_gate_ex* gate);
+int ks_audit_gate_ex_batch_dev(ks_dev_problem* const* ds, uint32_t n, ks_audit_gate_ex* gate);
 /* The gate's reduction over any table of words, so that its kernels can be tested apart from the passes: `rows` [n] (host memory) is uploaded to `device` and tallied
  * there both ways -- as a flag table (rows set, bit counts) and as a table of checked words with up to four bit fields (field_sum[i] = the sum of
  * (row >> shift[i]) & mask[i]).  All sums are modulo 2^32, as the totals' are. */

@@ -273,7 +273,8 @@ enum {
 static const u32 AUD_READS_ALL = (1u << AUD_N_SEGS) - 1u;                    // the first pass
 static const u32 AUD_READS_ORDER = AUD_READS(pod_node) | AUD_READS(pod_stage) | AUD_READS(pod_seq) | AUD_READS(node_tmpl) | AUD_READS(node_present) | AUD_READS(node_complement) |
                                    AUD_READS(node_mask) | AUD_READS(node_gt) | AUD_READS(node_lt);      // topology and spread: where the pods are, at which stage, in which order; the new nodes' templates and final requirements
-static const u32 AUD_READS_FIT = AUD_READS_ALL & ~AUD_READS(unscheduled);   // first-fit and limits
+static const u32 AUD_READS_FIT = AUD_READS_ALL & ~AUD_READS(unscheduled);   // first-fit, limits, hostfit and stages
+static const u32 AUD_READS_REASONS = AUD_READS(pod_node) | AUD_READS(pod_stage);      // the eighth pass: where the pods are and at which stage -- and pod_reason, a side array (below), no member of KS_AUDIT_SEGS
 // the result a solve left on the device
 static AuditView audit_resident(const DevState& s) {
   AuditView v{};
@@ -294,14 +295,18 @@ static int audit_claimed_check(const ks_dev_problem* d, const ks_result* claimed
 #undef X
   return KS_OK;
 }
-// seq_too (the gate's, or NULL): a second array of commit numbers behind the counts, and the view that reads it in pod_seq's place
-static int audit_claimed_upload(ks_dev_problem* d, const ks_result* claimed, u32 reads, TmpDev& up, AuditView* view, const i32* seq_too = nullptr, AuditView* view_too = nullptr) {
+// A SIDE array: [P] words of four bytes that travel behind the counts in the same transfer and are no member of KS_AUDIT_SEGS -- the commit numbers the gate's first
+// pass reads in pod_seq's place, the pod_reason column the eighth pass audits.  src: the caller's array, or null: not carried; dev: its place on the device after
+// the upload (null where it is not carried).  Each user makes a view of its own from `dev`; the block's views are untouched by a side array.
+struct AuditSide { const void* src; const void* dev; };
+static int audit_claimed_upload(ks_dev_problem* d, const ks_result* claimed, u32 reads, TmpDev& up, AuditView* view, AuditSide* sides = nullptr, u32 n_sides = 0) {
   const DevProb& h = d->h; const u64 P = h.P, K = h.K, R = h.R, TW = h.TW, N = claimed->n_new;
   size_t bytes = 0;
 #define X(sf, rf, T, cnt) if (reads & AUD_READS(rf)) bytes += ks_pad8((cnt) * sizeof(T));
   KS_AUDIT_SEGS(X)
 #undef X
-  const size_t all = bytes + 8 + (seq_too ? ks_pad8(P * sizeof(i32)) : 0);
+  size_t all = bytes + 8;
+  for (u32 k = 0; k < n_sides; ++k) if (sides[k].src) all += ks_pad8(P * sizeof(u32));
   std::vector<u64> blob(all / 8 + 1, 0); u8* hb = (u8*)blob.data();
   HIPCHK(hipSetDevice(d->device));
   TRY(up.alloc(all)); u8* db = up.as<u8>();
@@ -310,10 +315,14 @@ static int audit_claimed_upload(ks_dev_problem* d, const ks_result* claimed, u32
   KS_AUDIT_SEGS(X)
 #undef X
   { u32 c2[2] = {claimed->n_new, claimed->n_unscheduled}; memcpy(hb + at, c2, 8); s.out_counts = (u32*)(db + at); at += 8; }
-  if (seq_too && P) memcpy(hb + at, seq_too, P * sizeof(i32));
+  for (u32 k = 0; k < n_sides; ++k) {
+    sides[k].dev = nullptr;
+    if (!sides[k].src) continue;
+    if (P) memcpy(hb + at, sides[k].src, P * sizeof(u32));
+    sides[k].dev = db + at; at += ks_pad8(P * sizeof(u32));
+  }
   HIPCHK(hipMemcpy(db, hb, all, hipMemcpyHostToDevice));
   *view = audit_resident(s);
-  if (seq_too) { *view_too = *view; view_too->pod_seq = (const i32*)(db + at); }
   return KS_OK;
 }
 static int audit_claimed(ks_dev_problem* d, const ks_result* claimed, u32 reads, TmpDev& up, AuditView* view) {
@@ -400,6 +409,7 @@ struct AuditGate {
   u32 found;                                       // findings so far: the passes before, and this pass's earlier slices
   u32 pass;                                        // a finding's pass
   const void* outs0;                               // the pass's array of out pointers: a slice's position in the batch is its distance from here
+  const u32* const* reasons;                       // the eighth pass's column per problem on the device (a claimed result's side array), or null: the resident DevState's
 };
 // The reduce kernels over `probs` (device pointers inside), queued on `stream`: the totals' blocks come back in `tot` ([KS_AR_TOT] per problem) after the wait, which
 // is `clock`'s where there is one.  R: the call's block for the descriptors, the partial sums, the findings' places and the totals.
@@ -523,18 +533,33 @@ extern "C" int ks_audit_sizes(const ks_dev_problem* d, uint32_t* n_pods, uint32_
 extern "C" int ks_audit_batch_dev(ks_dev_problem* const* ds, uint32_t n, ks_audit* const* outs) { return audit_batch(ds, n, outs, false, audit_run); }
 extern "C" int ks_audit_dev(ks_dev_problem* d, const ks_result* claimed, ks_audit* out) { return audit_one(d, claimed, out, AUD_READS_ALL, false, audit_run); }
 
-// ---- the gate (ksolve.h ks_audit_gate_dev / ks_audit_gate_batch_dev): the passes a mask names, each through its own run with the gate's tail ----
-// What the gate knows of a pass: X(the index of its mask bit, its member of ks_audit_gate, what it reads of a claimed result, whether it refuses a batch over two
-// devices itself, its run).  The later passes' runs are defined in the files after this one.
+// ---- the gate (ksolve.h ks_audit_gate_ex_dev / ks_audit_gate_ex_batch_dev, and ks_audit_gate_dev / ks_audit_gate_batch_dev: the same function restricted to the
+// six bits and the old struct): the passes a mask names, each through its own run with the gate's tail ----
+// What the gate knows of a pass: X(the index of its mask bit, its member of ks_audit_gate_ex, what it reads of a claimed result's block, whether it refuses a batch
+// over two devices itself, its run, the side array it reads of a claimed result).  The later passes' runs are defined in the files after this one.
 static int audit_topo_run(ks_dev_problem* const*, u32, const AuditView*, ks_audit_topology* const*, AuditGate*);
 static int audit_spread_run(ks_dev_problem* const*, u32, const AuditView*, ks_audit_spread* const*, AuditGate*);
 static int audit_firstfit_run(ks_dev_problem* const*, u32, const AuditView*, ks_audit_firstfit* const*, AuditGate*);
 static int audit_limits_run(ks_dev_problem* const*, u32, const AuditView*, ks_audit_limits* const*, AuditGate*);
 static int audit_hostfit_run(ks_dev_problem* const*, u32, const AuditView*, ks_audit_hostfit* const*, AuditGate*);
+static int audit_stages_run(ks_dev_problem* const*, u32, const AuditView*, ks_audit_stages* const*, AuditGate*);
+static int audit_reasons_run(ks_dev_problem* const*, u32, const AuditView*, ks_audit_reasons* const*, AuditGate*);
+enum { AUD_SIDE_NONE = -1, AUD_SIDE_SEQ = 0, AUD_SIDE_REASON = 1, AUD_N_SIDES = 2 };      // SEQ: first_pod_seq, where the caller gives one | REASON: claimed->pod_reason, required
 #define KS_AUDIT_GATE_PASSES(X) \
-  X(0, first, AUD_READS_ALL, false, audit_run) X(1, topology, AUD_READS_ORDER, true, audit_topo_run) X(2, spread, AUD_READS_ORDER, true, audit_spread_run) \
-  X(3, firstfit, AUD_READS_FIT, true, audit_firstfit_run) X(4, limits, AUD_READS_FIT, true, audit_limits_run) X(5, hostfit, AUD_READS_FIT, true, audit_hostfit_run)
-template <class Out> static int audit_gate_pass(AuditGate& g, u32 pass, ks_dev_problem* const* ds, u32 n, const AuditView* views, Out* outs, int (*run)(ks_dev_problem* const*, u32, const AuditView*, Out* const*, AuditGate*), ks_audit_gate* gate) {
+  X(0, first, AUD_READS_ALL, false, audit_run, AUD_SIDE_SEQ) X(1, topology, AUD_READS_ORDER, true, audit_topo_run, AUD_SIDE_NONE) X(2, spread, AUD_READS_ORDER, true, audit_spread_run, AUD_SIDE_NONE) \
+  X(3, firstfit, AUD_READS_FIT, true, audit_firstfit_run, AUD_SIDE_NONE) X(4, limits, AUD_READS_FIT, true, audit_limits_run, AUD_SIDE_NONE) X(5, hostfit, AUD_READS_FIT, true, audit_hostfit_run, AUD_SIDE_NONE) \
+  X(6, stages, AUD_READS_FIT, true, audit_stages_run, AUD_SIDE_NONE) X(7, reasons, AUD_READS_REASONS, true, audit_reasons_run, AUD_SIDE_REASON)
+// the least struct_size: everything ks_audit_gate carries; the passes after the sixth have their pointers behind it
+static const u32 KS_AUDIT_GATE_EX_BASE = (u32)offsetof(ks_audit_gate_ex, stages);
+// the bits a caller of this struct_size can ask for: within KS_AUDIT_PASS_ALL_EX, the pointer wholly within the struct
+static u32 audit_gate_known(u32 struct_size) {
+  u32 known = 0;
+#define X(k, member, rd, own_check, run, side) if (offsetof(ks_audit_gate_ex, member) + sizeof(void*) <= struct_size) known |= 1u << k;
+  KS_AUDIT_GATE_PASSES(X)
+#undef X
+  return known & KS_AUDIT_PASS_ALL_EX;
+}
+template <class Out> static int audit_gate_pass(AuditGate& g, u32 pass, ks_dev_problem* const* ds, u32 n, const AuditView* views, Out* outs, int (*run)(ks_dev_problem* const*, u32, const AuditView*, Out* const*, AuditGate*), ks_audit_gate_ex* gate) {
   std::vector<Out*> ptr(n); for (u32 i = 0; i < n; ++i) ptr[i] = outs + i;
   g.pass = pass; g.outs0 = ptr.data();
   TRY(run(ds, n, views, ptr.data(), &g));
@@ -542,18 +567,24 @@ template <class Out> static int audit_gate_pass(AuditGate& g, u32 pass, ks_dev_p
   return KS_OK;
 }
 // one problem with a claimed result (n == 1), or the resident results of n problems
-static int audit_gate(ks_dev_problem* const* ds, u32 n, const ks_result* claimed, ks_audit_gate* gate) {
+static int audit_gate(ks_dev_problem* const* ds, u32 n, const ks_result* claimed, ks_audit_gate_ex* gate) {
   if (!gate) return fail(KS_ERR_INVALID, "null argument");
+  if (gate->struct_size < KS_AUDIT_GATE_EX_BASE) return fail(KS_ERR_INVALID, "audit gate: struct_size is less than the struct's first version");
   if (!gate->passes) return fail(KS_ERR_INVALID, "audit gate: no pass requested");
-  if (gate->passes & ~KS_AUDIT_PASS_ALL) return fail(KS_ERR_INVALID, "audit gate: unknown pass");
+  if (gate->passes & ~audit_gate_known(gate->struct_size)) return fail(KS_ERR_INVALID, "audit gate: unknown pass");
   if (gate->cap_findings && !gate->findings) return fail(KS_ERR_INVALID, "audit gate: null findings table");
   if (!n) { gate->n_findings = 0; gate->truncated = 0; gate->kernel_ms = gate->readback_ms = 0.0; return KS_OK; }
   // every refusal of every requested pass, in the order of the mask: nothing is launched and no out struct written unless they all accept
   std::vector<AuditView> views(n); AuditView first_view{}; u32 reads = 0;
-#define X(k, member, rd, own_check, run) if (gate->passes & (1u << k)) { \
+  AuditSide sides[AUD_N_SIDES] = {{nullptr, nullptr}, {nullptr, nullptr}};
+#define X(k, member, rd, own_check, run, side) if (gate->passes & (1u << k)) { \
     if (!ds || !gate->member) return fail(KS_ERR_INVALID, "null argument"); \
-    if (claimed) { if (!ds[0]) return fail(KS_ERR_INVALID, "null argument"); TRY(audit_claimed_check(ds[0], claimed, rd)); reads |= rd; } \
-    else { \
+    if (claimed) { \
+      if (!ds[0]) return fail(KS_ERR_INVALID, "null argument"); \
+      TRY(audit_claimed_check(ds[0], claimed, rd)); reads |= rd; \
+      if (side == AUD_SIDE_REASON) { if (ds[0]->h.P && !claimed->pod_reason) return fail(KS_ERR_INVALID, "claimed result: null array pod_reason"); sides[AUD_SIDE_REASON].src = claimed->pod_reason; } \
+      if (side == AUD_SIDE_SEQ) sides[AUD_SIDE_SEQ].src = gate->first_pod_seq; \
+    } else { \
       TRY(audit_resident_check<void>(ds, n, nullptr, own_check, views.data())); \
       if (!own_check) for (u32 i = 0; i < n; ++i) if (ds[i]->device != ds[0]->device) return fail(KS_ERR_INVALID, "batch spans devices"); \
     } }
@@ -562,12 +593,14 @@ static int audit_gate(ks_dev_problem* const* ds, u32 n, const ks_result* claimed
   const int device = ds[0]->device;
   HIPCHK(hipSetDevice(device));
   TmpDev up(device), F(device);
-  const bool own_seq = claimed && gate->first_pod_seq && (gate->passes & KS_AUDIT_PASS_FIRST);
-  if (claimed) TRY(audit_claimed_upload(ds[0], claimed, reads, up, &views[0], own_seq ? gate->first_pod_seq : nullptr, &first_view));      // taken once, uploaded once: the union of what the passes read
+  if (claimed) TRY(audit_claimed_upload(ds[0], claimed, reads, up, &views[0], sides, AUD_N_SIDES));      // taken once, uploaded once: the union of what the passes read, the side arrays of the passes that have one
+  const bool own_seq = sides[AUD_SIDE_SEQ].dev != nullptr;
+  if (own_seq) { first_view = views[0]; first_view.pod_seq = (const i32*)sides[AUD_SIDE_SEQ].dev; }      // the first pass's view of its own
+  const u32* reason_col = (const u32*)sides[AUD_SIDE_REASON].dev;                                        // the eighth pass's
   if (gate->cap_findings) TRY(F.alloc((size_t)gate->cap_findings * sizeof(ks_audit_finding)));
-  AuditGate g{}; g.d_find = gate->cap_findings ? F.as<ks_audit_finding>() : nullptr; g.cap = gate->cap_findings;
+  AuditGate g{}; g.d_find = gate->cap_findings ? F.as<ks_audit_finding>() : nullptr; g.cap = gate->cap_findings; g.reasons = reason_col ? &reason_col : nullptr;
   gate->n_findings = 0; gate->truncated = 0; gate->kernel_ms = gate->readback_ms = 0.0;
-#define X(k, member, rd, own_check, run) if (gate->passes & (1u << k)) TRY(audit_gate_pass(g, k, ds, n, (k == 0 && own_seq) ? &first_view : views.data(), gate->member, run, gate));
+#define X(k, member, rd, own_check, run, side) if (gate->passes & (1u << k)) TRY(audit_gate_pass(g, k, ds, n, (side == AUD_SIDE_SEQ && own_seq) ? &first_view : views.data(), gate->member, run, gate));
   KS_AUDIT_GATE_PASSES(X)
 #undef X
   const auto t0 = std::chrono::steady_clock::now();
@@ -577,8 +610,19 @@ static int audit_gate(ks_dev_problem* const* ds, u32 n, const ks_result* claimed
   gate->readback_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   return KS_OK;
 }
-extern "C" int ks_audit_gate_batch_dev(ks_dev_problem* const* ds, uint32_t n, ks_audit_gate* gate) { return audit_gate(ds, n, nullptr, gate); }
-extern "C" int ks_audit_gate_dev(ks_dev_problem* d, const ks_result* claimed, ks_audit_gate* gate) { if (!d) return fail(KS_ERR_INVALID, "null argument"); return audit_gate(&d, 1u, claimed, gate); }
+// the old struct as the wide one's first version: struct_size ends before `stages`, so the six bits are all it knows; what the gate wrote comes back on success alone
+static int audit_gate_six(ks_dev_problem* const* ds, u32 n, const ks_result* claimed, ks_audit_gate* gate) {
+  if (!gate) return fail(KS_ERR_INVALID, "null argument");
+  ks_audit_gate_ex x{}; x.struct_size = KS_AUDIT_GATE_EX_BASE; x.passes = gate->passes; x.cap_findings = gate->cap_findings; x.findings = gate->findings;
+  x.first = gate->first; x.topology = gate->topology; x.spread = gate->spread; x.firstfit = gate->firstfit; x.limits = gate->limits; x.hostfit = gate->hostfit; x.first_pod_seq = gate->first_pod_seq;
+  TRY(audit_gate(ds, n, claimed, &x));
+  gate->n_findings = x.n_findings; gate->truncated = x.truncated; gate->kernel_ms = x.kernel_ms; gate->readback_ms = x.readback_ms;
+  return KS_OK;
+}
+extern "C" int ks_audit_gate_batch_dev(ks_dev_problem* const* ds, uint32_t n, ks_audit_gate* gate) { return audit_gate_six(ds, n, nullptr, gate); }
+extern "C" int ks_audit_gate_dev(ks_dev_problem* d, const ks_result* claimed, ks_audit_gate* gate) { if (!d) return fail(KS_ERR_INVALID, "null argument"); return audit_gate_six(&d, 1u, claimed, gate); }
+extern "C" int ks_audit_gate_ex_batch_dev(ks_dev_problem* const* ds, uint32_t n, ks_audit_gate_ex* gate) { return audit_gate(ds, n, nullptr, gate); }
+extern "C" int ks_audit_gate_ex_dev(ks_dev_problem* d, const ks_result* claimed, ks_audit_gate_ex* gate) { if (!d) return fail(KS_ERR_INVALID, "null argument"); return audit_gate(&d, 1u, claimed, gate); }
 extern "C" int ks_audit_reduce_rows(int device, const uint32_t* rows, uint32_t n, const ks_audit_fields* fields, ks_audit_row_totals* out) {
   if (!out || (n && !rows)) return fail(KS_ERR_INVALID, "null argument");
   if (fields && fields->n_fields > 4u) return fail(KS_ERR_INVALID, "audit reduce: more than four fields");

@@ -198,19 +198,18 @@ static int audit_reasons_run_on(ks_dev_problem* const* ds, u32 n, const AuditVie
   clock.store(outs, n);
   return KS_OK;
 }
-// the run function in the form every pass has (a later gate can call it): the resident column of every problem
-static int audit_reasons_run(ks_dev_problem* const* ds, u32 n, const AuditView* results, ks_audit_reasons* const* outs, AuditGate* g) { return audit_reasons_run_on(ds, n, results, nullptr, outs, g); }
-// What the claimed form reads: where the pods are and at which stage -- and pod_reason, which is no member of KS_AUDIT_SEGS (AUD_READS_ALL stays the seven passes'
-// set): it is uploaded beside the block, as the gate's second array of commit numbers is.
-static const u32 AUD_READS_REASONS = AUD_READS(pod_node) | AUD_READS(pod_stage);
+// the run function in the form every pass has: the resident column of every problem, or (from the gate's claimed form) the column the gate uploaded beside the block
+static int audit_reasons_run(ks_dev_problem* const* ds, u32 n, const AuditView* results, ks_audit_reasons* const* outs, AuditGate* g) { return audit_reasons_run_on(ds, n, results, g ? g->reasons : nullptr, outs, g); }
+// What the claimed form reads: AUD_READS_REASONS (ks_audit.inc) -- and pod_reason, which is no member of KS_AUDIT_SEGS (AUD_READS_ALL stays the seven passes' set): it
+// is uploaded beside the block as a side array, as the gate's second array of commit numbers is.
 extern "C" int ks_audit_reasons_batch_dev(ks_dev_problem* const* ds, uint32_t n, ks_audit_reasons* const* outs) { return audit_batch(ds, n, outs, true, audit_reasons_run); }
 extern "C" int ks_audit_reasons_dev(ks_dev_problem* d, const ks_result* claimed, ks_audit_reasons* out) {
   if (!d || !out) return fail(KS_ERR_INVALID, "null argument");
   if (!claimed) return audit_batch(&d, 1u, &out, true, audit_reasons_run);
   TRY(audit_claimed_check(d, claimed, AUD_READS_REASONS));
   if (d->h.P && !claimed->pod_reason) return fail(KS_ERR_INVALID, "claimed result: null array pod_reason");
-  TmpDev up(d->device); AuditView v{}, beside{};
-  TRY(audit_claimed_upload(d, claimed, AUD_READS_REASONS, up, &v, (const i32*)claimed->pod_reason, &beside));
-  const u32* reasons = (const u32*)beside.pod_seq;      // (the second array's place in the upload)
+  TmpDev up(d->device); AuditView v{}; AuditSide side{claimed->pod_reason, nullptr};      // (null only where P == 0: nothing is carried, nothing is read)
+  TRY(audit_claimed_upload(d, claimed, AUD_READS_REASONS, up, &v, &side, 1));
+  const u32* reasons = (const u32*)side.dev;
   return audit_reasons_run_on(&d, 1, &v, &reasons, &out, nullptr);
 }

@@ -11,7 +11,8 @@
 //   ks_audit_ff_count     the fourth pass's: placed pods, pods per commit number, the existing nodes' request sums and presence masks; the tables set to "never".
 //   ks_audit_st_mark      one lane per pod walking its stages j < k: used[c_j] = 1 for the examinable ones; the pod's flag word (SEQ, UNRELAXED) and its checked word
 //                         with the number of stages examined -- what the verdict would say if no pair admitted.  meta[5] = 1 where a class was marked.
-//   -- the host reads the meta words back: where no problem of the call marked a class (no pod relaxed), the tables above are the answer and nothing more is launched --
+//   -- the pass's own entry points read the meta words back here: where no problem of the call marked a class (no pod relaxed), the tables above are the answer and
+//      nothing more is launched.  Under the gate (ks_audit_gate_ex) there is no wait: the four below are queued at once and decide per problem (host half) --
 //   ks_audit_ff_compact   the fourth pass's: used[] compacted into the class list.
 //   ks_audit_ff_existing  the fourth pass's: first_e[u] per used class.
 //   ks_audit_ff_new       the fourth pass's, templates only: first_m[u] per used class.
@@ -72,7 +73,8 @@ __global__ __launch_bounds__(256) void ks_audit_st_verdict(const DevProb* probs,
 
 // ---- host half ----
 // The fourth pass's block [meta | flags | checked words | scratch] and its scratch, plus two zero words per problem for the view ks_audit_ff_new reads its node count
-// from.  After the first two launches the meta words -- the head of the block -- are read back: one small transfer that decides whether the pair kernels run at all.
+// from.  After the first two launches the meta words -- the head of the block -- are read back: one small transfer that decides whether the pair kernels run at all
+// (the pass's own entry points; the gate's form queues all six).
 static int audit_stages_run(ks_dev_problem* const* ds, u32 n, const AuditView* results, ks_audit_stages* const* outs, AuditGate* g) {
   BatchStage st; TRY(st.open(ds, n, nullptr, false));
   const size_t o_view = st.add<AuditView>(n), o_tview = st.add<AuditView>(n), o_fview = st.add<AuditFitView>(n);
@@ -102,21 +104,36 @@ static int audit_stages_run(ks_dev_problem* const* ds, u32 n, const AuditView* r
   TRY(W.zero(st.stream()));
   const AuditView* dv = st.d<const AuditView>(o_view); const AuditView* dt = st.d<const AuditView>(o_tview); const AuditFitView* df = st.d<const AuditFitView>(o_fview);
   const u32 gx_p = std::max(1u, std::min(1024u, (pmax + 255u) / 256u)), gx_e = (u32)std::min<size_t>(4096, emax), gx_n = (u32)std::min<size_t>(4096, nmax);
-  audit_rows(n, [&](u32 base, u32 ny) {
+  const auto first_two = [&](u32 base, u32 ny) {
     hipLaunchKernelGGL(ks_audit_ff_count, dim3(gx_p, ny), dim3(256), 0, st.stream(), st.probs() + base, dv + base, df + base);
     hipLaunchKernelGGL(ks_audit_st_mark, dim3(gx_p, ny), dim3(256), 0, st.stream(), st.probs() + base, dv + base, df + base);
-  });
-  std::vector<u32> meta(8 * (size_t)n);
-  HIPCHK(hipMemcpyAsync(meta.data(), w, meta.size() * sizeof(u32), hipMemcpyDeviceToHost, st.stream()));
-  HIPCHK(hipStreamSynchronize(st.stream()));
-  bool relaxed = false;
-  for (u32 i = 0; i < n && !relaxed; ++i) relaxed = meta[8 * (size_t)i + 5] != 0u;
-  if (relaxed) audit_rows(n, [&](u32 base, u32 ny) {
+  };
+  const auto last_four = [&](u32 base, u32 ny) {
     hipLaunchKernelGGL(ks_audit_ff_compact, dim3(ny), dim3(256), 0, st.stream(), st.probs() + base, df + base);
     hipLaunchKernelGGL(ks_audit_ff_existing, dim3(gx_e, ny), dim3(256), 0, st.stream(), st.probs() + base, df + base);
     hipLaunchKernelGGL(ks_audit_ff_new, dim3(gx_n, ny), dim3(256), 0, st.stream(), st.probs() + base, dt + base, df + base);
     hipLaunchKernelGGL(ks_audit_st_verdict, dim3(gx_p, ny), dim3(256), 0, st.stream(), st.probs() + base, dv + base, df + base);
-  });
+  };
+  if (g) {
+    // Under the gate: all six queued, no host wait between them (the gate's rule: one wait per pass and slice, in the tail).  The decision the read-back below takes
+    // per CALL is taken on the device per PROBLEM, by the kernels as they are.  A problem whose meta[5] is 0 marked no class: its used[] is all zero, so
+    //   ks_audit_ff_compact   finds `mine` 0 in every tile: it stores nothing to list[] or used[], and cntr[1] = 0 -- what the memset left;
+    //   ks_audit_ff_existing  reads n_used = cntr[1] = 0: total = 0, its loop makes no trip, no atomic, no store;
+    //   ks_audit_ff_new       the same: total = n_used * X = 0;
+    //   ks_audit_st_verdict   walks the stages ks_audit_st_mark walked, through the same aud_stage_pod: no stage is examined (else the mark kernel had set meta[5]),
+    //                         n_exam is 0, f is s.f, and the two stores repeat the mark kernel's words; meta[2 .. 4] = cntr[1 .. 3] = 0, what the memset left.
+    // So its eight meta words, flag words and checked words are those of the pass's own call -- early-out or not, whatever its neighbours in the batch do -- and it
+    // costs four workgroup dispatches that leave at once.  A problem that did mark classes takes exactly the launches its own call gives it.
+    audit_rows(n, [&](u32 base, u32 ny) { first_two(base, ny); last_four(base, ny); });
+  } else {
+    audit_rows(n, first_two);
+    std::vector<u32> meta(8 * (size_t)n);
+    HIPCHK(hipMemcpyAsync(meta.data(), w, meta.size() * sizeof(u32), hipMemcpyDeviceToHost, st.stream()));
+    HIPCHK(hipStreamSynchronize(st.stream()));
+    bool relaxed = false;
+    for (u32 i = 0; i < n && !relaxed; ++i) relaxed = meta[8 * (size_t)i + 5] != 0u;
+    if (relaxed) audit_rows(n, last_four);
+  }
   const AuditTail tail{8, o_fl.data(), o_ck.data(), nullptr, 4, {30, 0, 29, KS_AS_STAGES_SHIFT}, {1u, 1u, 1u, KS_AS_STAGES_MASK}};      // checked[0], checked[1], skipped_pods, checked[2] of a checked word
   TRY(audit_tail(st, W, clock, ds, n, outs, tail, g, [&](u32 i, const AuditTotals& t, const u32* pf, const u32*) {
     ks_audit_stages* o = outs[i]; const u32 Pn = ds[i]->h.P; const u32* m = t.meta;

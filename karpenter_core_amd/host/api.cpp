@@ -988,16 +988,28 @@ template <class P> int audit_claimed(void* hv, const ksh_result_arrays* c, const
     return KS_OK;
   });
 }
-// The gate (kshost.h ksh_audit_gate / ksh_audit_gate_claimed): X(the pass's mask bit, its traits, its member of ks_audit_gate, its member of ksh_audit_gate_out).
+// The gate (kshost.h ksh_audit_gate_ex / ksh_audit_gate_ex_claimed, and ksh_audit_gate / ksh_audit_gate_claimed: the same bodies over the old struct as the wide one's
+// first version): X(the pass's mask bit, its traits, its member of ks_audit_gate_ex, its member of ksh_audit_gate_ex_out).
 // libksolve fills out structs of the library's own -- no tables in them -- and every requested pass's totals reach the caller through the pass's own `totals`.
 #define KSH_AUDIT_GATE_PASSES(X) \
   X(KS_AUDIT_PASS_FIRST, AuditFirst, first, audit) X(KS_AUDIT_PASS_TOPOLOGY, AuditTopology, topology, topology) X(KS_AUDIT_PASS_SPREAD, AuditSpread, spread, spread) \
-  X(KS_AUDIT_PASS_FIRSTFIT, AuditFirstFit, firstfit, firstfit) X(KS_AUDIT_PASS_LIMITS, AuditLimits, limits, limits) X(KS_AUDIT_PASS_HOSTFIT, AuditHostFit, hostfit, hostfit)
+  X(KS_AUDIT_PASS_FIRSTFIT, AuditFirstFit, firstfit, firstfit) X(KS_AUDIT_PASS_LIMITS, AuditLimits, limits, limits) X(KS_AUDIT_PASS_HOSTFIT, AuditHostFit, hostfit, hostfit) \
+  X(KS_AUDIT_PASS_STAGES, AuditStages, stages, stages) X(KS_AUDIT_PASS_REASONS, AuditReasons, reasons, reasons)
+const uint32_t KSH_AUDIT_GATE_EX_BASE = (uint32_t)offsetof(ksh_audit_gate_ex_out, stages);      // the least struct_size: everything ksh_audit_gate_out carries
+// the bits a caller of this struct_size can ask for: within KS_AUDIT_PASS_ALL_EX, the pointer wholly within the struct
+uint32_t audit_gate_known(uint32_t struct_size) {
+  uint32_t known = 0;
+#define X(bit, P, km, hm) if (offsetof(ksh_audit_gate_ex_out, hm) + sizeof(void*) <= struct_size) known |= bit;
+  KSH_AUDIT_GATE_PASSES(X)
+#undef X
+  return known & KS_AUDIT_PASS_ALL_EX;
+}
 // the gate's own refusals, before any pass's
-int audit_gate_ok(uint32_t passes, const ksh_audit_gate_out* out) {
+int audit_gate_ok(uint32_t passes, const ksh_audit_gate_ex_out* out) {
   if (!out) return set_err(KS_ERR_INVALID, "null argument");
+  if (out->struct_size < KSH_AUDIT_GATE_EX_BASE) return set_err(KS_ERR_INVALID, "audit gate: struct_size is less than the struct's first version");
   if (!passes) return set_err(KS_ERR_INVALID, "audit gate: no pass requested");
-  if (passes & ~KS_AUDIT_PASS_ALL) return set_err(KS_ERR_INVALID, "audit gate: unknown pass");
+  if (passes & ~audit_gate_known(out->struct_size)) return set_err(KS_ERR_INVALID, "audit gate: unknown pass");
   if (out->cap_findings && !out->findings) return set_err(KS_ERR_INVALID, "audit gate: null findings table");
 #define X(bit, P, km, hm) if ((passes & bit) && !out->hm) return set_err(KS_ERR_INVALID, "null argument");
   KSH_AUDIT_GATE_PASSES(X)
@@ -1005,8 +1017,8 @@ int audit_gate_ok(uint32_t passes, const ksh_audit_gate_out* out) {
   return KS_OK;
 }
 // dev_call(gate): the call into libksolve, over tables of n structs per requested pass
-template <class F> int audit_gate_call(uint32_t n, uint32_t passes, ksh_audit_gate_out* out, double* ms, F&& dev_call) {
-  ks_audit_gate g{}; g.passes = passes; g.findings = out->findings; g.cap_findings = (uint32_t)std::min<uint64_t>(out->cap_findings, 0xFFFFFFFFu);
+template <class F> int audit_gate_call(uint32_t n, uint32_t passes, ksh_audit_gate_ex_out* out, double* ms, F&& dev_call) {
+  ks_audit_gate_ex g{}; g.struct_size = (uint32_t)sizeof g; g.passes = passes; g.findings = out->findings; g.cap_findings = (uint32_t)std::min<uint64_t>(out->cap_findings, 0xFFFFFFFFu);
 #define X(bit, P, km, hm) std::vector<P::Dev> v_##km; if (passes & bit) { v_##km.assign(n, P::Dev{}); g.km = v_##km.data(); }
   KSH_AUDIT_GATE_PASSES(X)
 #undef X
@@ -1018,9 +1030,8 @@ template <class F> int audit_gate_call(uint32_t n, uint32_t passes, ksh_audit_ga
   if (ms) { ms[0] = g.kernel_ms; ms[1] = g.readback_ms; }
   return KS_OK;
 }
-}  // namespace
-extern "C" {
-int ksh_audit_gate(void** hv, uint32_t n, uint32_t passes, ksh_audit_gate_out* out, double* ms) {
+// the two entry bodies, over the wide struct
+int audit_gate_resident(void** hv, uint32_t n, uint32_t passes, ksh_audit_gate_ex_out* out, double* ms) {
   zero(ms, 2);
   int rc = audit_gate_ok(passes, out); if (rc != KS_OK) return rc;
   if (n && !hv) return set_err(KS_ERR_INVALID, "null argument");
@@ -1028,18 +1039,19 @@ int ksh_audit_gate(void** hv, uint32_t n, uint32_t passes, ksh_audit_gate_out* o
   return guarded([&] {
     std::vector<ks_dev_problem*> ds;
     int rc = device_problems(hv, n, true, "audit before solve", ds); if (rc != KS_OK) return rc;
-    return audit_gate_call(n, passes, out, ms, [&](ks_audit_gate* g) { return ks_audit_gate_batch_dev(ds.data(), n, g); });
+    return audit_gate_call(n, passes, out, ms, [&](ks_audit_gate_ex* g) { return ks_audit_gate_ex_batch_dev(ds.data(), n, g); });
   });
 }
-int ksh_audit_gate_claimed(void* hv, const ksh_result_arrays* c, const int32_t* pod_seq, uint32_t passes, ksh_audit_gate_out* out, double* ms) {
+int audit_gate_claimed(void* hv, const ksh_result_arrays* c, const int32_t* pod_seq, uint32_t passes, ksh_audit_gate_ex_out* out, double* ms) {
   zero(ms, 2);
   int rc = audit_gate_ok(passes, out); if (rc != KS_OK) return rc;
   Handle* h = (Handle*)hv; const bool first = passes & KS_AUDIT_PASS_FIRST;
-  if (!h || !c || ((passes & ~KS_AUDIT_PASS_FIRST) && !pod_seq)) return set_err(KS_ERR_INVALID, "null argument");
+  if (!h || !c || ((passes & ~(KS_AUDIT_PASS_FIRST | KS_AUDIT_PASS_REASONS)) && !pod_seq)) return set_err(KS_ERR_INVALID, "null argument");      // (the two passes that take no commit numbers)
   if (h->delta || h->enc->view) return set_err(KS_ERR_UNSUPPORTED, "a claimed result is audited against a flattened problem, not against a what-if derived on the device");
   return guarded([&] {
     const ks_problem& p = h->enc->prob; ks_result r;
     int rc = claimed_result(p, c, first, pod_seq, &r); if (rc != KS_OK) return rc;
+    if (passes & KS_AUDIT_PASS_REASONS) r.pod_reason = (uint32_t*)c->pod_reason;      // (read by that pass alone; its null is that pass's refusal, in libksolve's order)
     rc = ensure_resident(h); if (rc != KS_OK) return rc;
     std::vector<int32_t> seq, un;
     if (first) {      // (what ksh_audit_claimed gives the first pass: the unscheduled list in an array of P, the placed pods numbered in pod order)
@@ -1048,9 +1060,28 @@ int ksh_audit_gate_claimed(void* hv, const ksh_result_arrays* c, const int32_t* 
       for (uint32_t i = 0; i < c->n_unscheduled; ++i) un[i] = c->unscheduled[i];
       r.unscheduled = un.data(); if (!pod_seq) r.pod_seq = seq.data();
     }
-    return audit_gate_call(1, passes, out, ms, [&](ks_audit_gate* g) { g->first_pod_seq = first && pod_seq ? seq.data() : nullptr; return ks_audit_gate_dev(h->dev, &r, g); });
+    return audit_gate_call(1, passes, out, ms, [&](ks_audit_gate_ex* g) { g->first_pod_seq = first && pod_seq ? seq.data() : nullptr; return ks_audit_gate_ex_dev(h->dev, &r, g); });
   });
 }
+// the old struct as the wide one's first version: struct_size ends before `stages`, so the six bits are all it knows; the counts come back on success alone
+template <class F> int audit_gate_six(ksh_audit_gate_out* out, double* ms, F&& body) {
+  if (!out) { zero(ms, 2); return set_err(KS_ERR_INVALID, "null argument"); }
+  ksh_audit_gate_ex_out x{}; x.struct_size = KSH_AUDIT_GATE_EX_BASE; x.findings = out->findings; x.cap_findings = out->cap_findings;
+  x.audit = out->audit; x.topology = out->topology; x.spread = out->spread; x.firstfit = out->firstfit; x.limits = out->limits; x.hostfit = out->hostfit;
+  int rc = body(&x); if (rc != KS_OK) return rc;
+  out->n_findings = x.n_findings; out->truncated = x.truncated;
+  return KS_OK;
+}
+}  // namespace
+extern "C" {
+int ksh_audit_gate(void** hv, uint32_t n, uint32_t passes, ksh_audit_gate_out* out, double* ms) {
+  return audit_gate_six(out, ms, [&](ksh_audit_gate_ex_out* x) { return audit_gate_resident(hv, n, passes, x, ms); });
+}
+int ksh_audit_gate_claimed(void* hv, const ksh_result_arrays* c, const int32_t* pod_seq, uint32_t passes, ksh_audit_gate_out* out, double* ms) {
+  return audit_gate_six(out, ms, [&](ksh_audit_gate_ex_out* x) { return audit_gate_claimed(hv, c, pod_seq, passes, x, ms); });
+}
+int ksh_audit_gate_ex(void** hv, uint32_t n, uint32_t passes, ksh_audit_gate_ex_out* out, double* ms) { return audit_gate_resident(hv, n, passes, out, ms); }
+int ksh_audit_gate_ex_claimed(void* hv, const ksh_result_arrays* c, const int32_t* pod_seq, uint32_t passes, ksh_audit_gate_ex_out* out, double* ms) { return audit_gate_claimed(hv, c, pod_seq, passes, out, ms); }
 int ksh_audit(void** hv, uint32_t n, ksh_audit_out* outs, double* ms) { return audit_resident<AuditFirst>(hv, n, outs, ms); }
 int ksh_audit_claimed(void* hv, const ksh_result_arrays* c, ksh_audit_out* out, double* ms) { return audit_claimed<AuditFirst>(hv, c, nullptr, out, ms); }
 int ksh_audit_topology(void** hv, uint32_t n, ksh_audit_topology_out* outs, double* ms) { return audit_resident<AuditTopology>(hv, n, outs, ms); }

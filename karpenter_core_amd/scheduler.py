@@ -399,20 +399,20 @@ class FlatProblem:
     def audit_stages(self, claimed: Optional[dict] = None, pod_seq=None) -> dict:
         """The audit's seventh, opt-in pass (include/ksolve.h KS_AUDIT_POD_STAGE_*, kshost.h ksh_audit_stages / ksh_audit_stages_claimed): relaxation order -- no pod ended
         at a later stage of its chain than one at which an existing node's final state or a fresh machine of an unlimited template admits it, and no unscheduled pod
-        stopped short of its chain's end.  Not one of the gate's passes.  Arguments as `audit_topology`'s.  Returns `audit_firstfit`'s dict ("checked": SEQ, PODS the
+        stopped short of its chain's end.  The gate runs it when `passes` names "stages".  Arguments as `audit_topology`'s.  Returns `audit_firstfit`'s dict ("checked": SEQ, PODS the
         pods with an examined earlier stage, STAGES those stages, PAIRS the (class, node-or-template) pairs)."""
         return _audit("stages", [self], claimed, pod_seq)[0]
 
     def audit_reasons(self, claimed: Optional[dict] = None) -> dict:
         """The audit's eighth, opt-in pass (include/ksolve.h KS_AUDIT_POD_REASON_*, kshost.h ksh_audit_reasons / ksh_audit_reasons_claimed): the failure reasons -- a
         placed pod carries no word, an unscheduled pod a KS_WHY_* nibble for each of the first eight templates, and where the flat problem alone decides the nibble
-        (taints, requirements, no instance type) it is that value.  Not one of the gate's passes.  `claimed`: a result in `result_arrays()`' form, of which
+        (taints, requirements, no instance type) it is that value.  The gate runs it when `passes` names "reasons".  `claimed`: a result in `result_arrays()`' form, of which
         pod_node, pod_stage and pod_reason are read; no commit numbers.  Returns {"pod_flags", "n_pods_flagged", "pod_bit_count", "checked": PODS the unscheduled
         pods examined, EXACT / BOUNDED / UNEXAMINED their nibbles, "skipped_pods", "n_unscheduled", "used_classes", "pairs", "n_new", "n_placed", "ms"}."""
         return _audit("reasons", [self], claimed)[0]
 
     def audit_gate(self, claimed: Optional[dict] = None, pod_seq=None, passes=None, cap_findings: int = 1024, findings_table=None) -> dict:
-        """The audit's gate (include/ksolve.h KS_AUDIT_PASS_*, kshost.h ksh_audit_gate / ksh_audit_gate_claimed): the passes named in `passes` (default: all six) in one
+        """The audit's gate (include/ksolve.h KS_AUDIT_PASS_*, kshost.h ksh_audit_gate / ksh_audit_gate_claimed): the passes named in `passes` (default: all six; "stages" and "reasons" may be named too, scheduler.AUDIT_GATE_ALL) in one
         call, tallied on the device -- no flag row is read back.  Arguments as `audit_topology`'s.  Returns `scheduler.audit_gate`'s dict, "passes" holding one dict per
         pass: what the pass's own method returns, without its flag arrays."""
         g = audit_gate([self], passes, cap_findings, claimed, pod_seq, findings_table)
@@ -871,7 +871,7 @@ _AUDIT_PASSES = {
                     scalars=("admitting_pairs", "skipped_pods", "eligible_groups", "skipped_groups", "n_new", "n_placed")),
 }
 
-# The passes the gate does not run (yet): described as the ones above and called through the same _audit(), but outside _AUDIT_PASSES, whose places are the gate's mask
+# The pass beside the six (the gate runs it through its wide form, _AUDIT_PASSES_EX below): described as the ones above and called through the same _audit(), but outside _AUDIT_PASSES, whose places are the gate's mask
 # bits and the members of its struct.
 _AUDIT_PASSES_BESIDE = {
     "stages": dict(stem="ksh_audit_stages", seq=True, out="_AuditStagesOut", claimed=_CLAIMED_FIT, pod_bits=KS_AUDIT_STAGES_BITS, node_bits=None, checked=KS_AUDIT_STAGES_CHECKED,
@@ -1021,38 +1021,64 @@ class _AuditGateOut(ctypes.Structure):      # include/kshost.h ksh_audit_gate_ou
                [("n_findings", ctypes.c_uint32), ("truncated", ctypes.c_uint32)]
 
 
+# The gate over all eight passes (include/kshost.h ksh_audit_gate_ex / ksh_audit_gate_ex_claimed, include/ksolve.h KS_AUDIT_PASS_ALL_EX): the six tables above stay what
+# they are; the wide form names the passes beside them too.  A pass's mask bit is its place in AUDIT_GATE_ALL.
+_AUDIT_PASSES_EX = dict(_AUDIT_PASSES, **_AUDIT_PASSES_BESIDE, **_AUDIT_PASSES_REASONS)
+AUDIT_GATE_ALL = tuple(_AUDIT_PASSES_EX)      # the eight names in mask order
+KS_AUDIT_PASS_EX = {name: 1 << i for i, name in enumerate(AUDIT_GATE_ALL)}
+
+
+class _AuditGateExOut(ctypes.Structure):      # include/kshost.h ksh_audit_gate_ex_out: struct_size leads, the passes after the sixth have their pointers at the end
+    _fields_ = [("struct_size", ctypes.c_uint32), ("pad", ctypes.c_uint32), ("findings", ctypes.c_void_p), ("cap_findings", ctypes.c_uint64)] + \
+               [(name, ctypes.POINTER(p["Out"])) for name, p in _AUDIT_PASSES.items()] + [("n_findings", ctypes.c_uint32), ("truncated", ctypes.c_uint32)] + \
+               [(name, ctypes.POINTER(_AUDIT_PASSES_EX[name]["Out"])) for name in AUDIT_GATE_ALL[len(_AUDIT_PASSES):]]
+
+
 def audit_gate(flats: Sequence["FlatProblem"], passes: Optional[Sequence[str]] = None, cap_findings: int = 1024, claimed: Optional[dict] = None, pod_seq=None,
-               findings_table=None) -> dict:
+               findings_table=None, wide: Optional[bool] = None) -> dict:
     """The audit's gate (include/kshost.h ksh_audit_gate): the passes named in `passes` (default: all six of _AUDIT_PASSES) over the resident results of `flats` in one
     call -- or over `claimed` with `pod_seq` for flats[0] --, tallied on the device: no flag row is read back.  Returns {"clean": no pass found anything, "passes":
     {name: one dict per problem, as the pass's own call returns it without its flag arrays}, "findings": a structured array (AUDIT_FINDING) of the first
     min(n_findings, cap_findings) non-zero flag words, ordered by pass, problem, pods before nodes, index, "n_findings": all of them, "truncated", "ms"}.
-    findings_table: an array of `cap_findings` AUDIT_FINDING records to write into (a caller who wants to see what is left untouched)."""
+    findings_table: an array of `cap_findings` AUDIT_FINDING records to write into (a caller who wants to see what is left untouched).
+    `passes` may name "stages" and "reasons" too (AUDIT_GATE_ALL: all eight): the call then goes through the wide gate (ksh_audit_gate_ex), "passes" comes back in
+    mask order, a claimed result carries `pod_reason` when "reasons" is named, and `pod_seq` may be left out when only "audit" and "reasons" are.  wide=True sends
+    a mask of the six through the wide gate as well (it answers what the old one answers); wide=None decides by the names."""
     import numpy as np
     names = list(_AUDIT_PASSES) if passes is None else list(passes)
+    if wide is None:
+        wide = any(w not in _AUDIT_PASSES and w in KS_AUDIT_PASS_EX for w in names)
+    if wide:
+        names = [w for w in AUDIT_GATE_ALL if w in names] + [w for w in names if w not in KS_AUDIT_PASS_EX]      # (an unknown name: the KeyError below)
+    table_of, bit_of = (_AUDIT_PASSES_EX, KS_AUDIT_PASS_EX) if wide else (_AUDIT_PASSES, KS_AUDIT_PASS)
     mask = 0
     for w in names:
-        mask |= KS_AUDIT_PASS[w]
+        mask |= bit_of[w]
     n, kh = len(flats), libs()[1]
-    out = _AuditGateOut()
+    Gate, stem = (_AuditGateExOut, "ksh_audit_gate_ex") if wide else (_AuditGateOut, "ksh_audit_gate")
+    out = Gate()
+    if wide:
+        out.struct_size = ctypes.sizeof(Gate)
     table = np.zeros(max(1, cap_findings), dtype=AUDIT_FINDING) if findings_table is None else findings_table
     out.findings, out.cap_findings = (table.ctypes.data if cap_findings else None), cap_findings
-    outs = {w: (_AUDIT_PASSES[w]["Out"] * max(1, n))() for w in names}
+    outs = {w: (table_of[w]["Out"] * max(1, n))() for w in names}
     for w, a in outs.items():
         setattr(out, w, a)
     ms = (ctypes.c_double * 2)()
     if claimed is None:
         if pod_seq is not None:
             raise ValueError("audit_gate: pod_seq goes with a claimed result")
-        kh.ksh_audit_gate.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(_AuditGateOut), ctypes.POINTER(ctypes.c_double)]
-        rc = kh.ksh_audit_gate((ctypes.c_void_p * max(1, n))(*[f._h for f in flats]), n, mask, ctypes.byref(out), ms)
+        resident = getattr(kh, stem)
+        resident.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(Gate), ctypes.POINTER(ctypes.c_double)]
+        rc = resident((ctypes.c_void_p * max(1, n))(*[f._h for f in flats]), n, mask, ctypes.byref(out), ms)
     else:
-        ra, seq, _keep = _claimed_arrays(flats[0], claimed, pod_seq, sum((_AUDIT_PASSES[w]["claimed"] for w in names), ()), "gate")
-        kh.ksh_audit_gate_claimed.argtypes = [ctypes.c_void_p, ctypes.POINTER(_ResultArrays), ctypes.c_void_p, ctypes.c_uint32, ctypes.POINTER(_AuditGateOut), ctypes.POINTER(ctypes.c_double)]
-        rc = kh.ksh_audit_gate_claimed(flats[0]._h, ctypes.byref(ra), seq.ctypes.data if seq is not None else None, mask, ctypes.byref(out), ms)
+        ra, seq, _keep = _claimed_arrays(flats[0], claimed, pod_seq, sum((table_of[w]["claimed"] for w in names), ()), "gate")
+        claimed_fn = getattr(kh, stem + "_claimed")
+        claimed_fn.argtypes = [ctypes.c_void_p, ctypes.POINTER(_ResultArrays), ctypes.c_void_p, ctypes.c_uint32, ctypes.POINTER(Gate), ctypes.POINTER(ctypes.c_double)]
+        rc = claimed_fn(flats[0]._h, ctypes.byref(ra), seq.ctypes.data if seq is not None else None, mask, ctypes.byref(out), ms)
     if rc != KS_OK:
         raise KSolveError(rc, kh.ksh_last_error().decode())
-    return {"clean": out.n_findings == 0, "passes": {w: [_audit_totals(_AUDIT_PASSES[w], outs[w][i]) for i in range(n)] for w in names},
+    return {"clean": out.n_findings == 0, "passes": {w: [_audit_totals(table_of[w], outs[w][i]) for i in range(n)] for w in names},
             "findings": table[:min(int(out.n_findings), cap_findings)].copy(), "n_findings": int(out.n_findings), "truncated": bool(out.truncated & KS_AUDIT_GATE_TRUNCATED),
             "ms": (float(ms[0]), float(ms[1]))}
 

@@ -3,12 +3,15 @@
 same run on the same box next to the pack kernel time of that Solve, what each pass examined -- `checked` by name and every counter it returns --, and whether it found
 anything.  Needs a GPU.
    usage: tools/time_audit.py <pass>[,<pass>] [legs, comma separated] [reps]      (defaults: config3,whatifs,config5 9)
-   pass   audit | topology | spread | firstfit | limits | hostfit (scheduler._AUDIT_PASSES) | stages (scheduler._AUDIT_PASSES_BESIDE) | reasons
+   pass   gate | gate_ex (below) | audit | topology | spread | firstfit | limits | hostfit (scheduler._AUDIT_PASSES) | stages (scheduler._AUDIT_PASSES_BESIDE) | reasons
           (scheduler._AUDIT_PASSES_REASONS); the first one named is the subject, the others are timed beside it (hostfit,firstfit: the sixth pass beside the fourth,
           with the cost per evaluated pair of each; stages,firstfit: the seventh beside the fourth, whose pair kernels it runs over fewer classes; reasons,audit: the
           eighth beside the first, the other pass that reads no commit numbers)
           gate   the audit's gate (ksh_audit_gate) over the passes named beside it -- all six if it is named alone --, with no findings table: one call, totals
                  reduced on the device.  Timed in the same run as those passes' own calls, and set against their sum.  The what-ifs are `limits`' snapshot
+          gate_ex  the wide gate (ksh_audit_gate_ex) over all eight passes, with no findings table, against the cheapest sequence there was before it: the old gate
+                 over the six, then the seventh pass's own call, then the eighth's.  The four calls are timed INTERLEAVED -- one round of all four per repetition --
+                 and the sequence's time is summed per round.  The what-ifs are `limits`' snapshot
    legs   config3       BASELINE configs[2]: 100 000 pods / 2 000 types (workloads.config3 seed 44) -- bench.py's contract workload; no limited template
           whatifs       512 what-ifs derived on the device over a 2 048-node snapshot, audited as ONE batch where their results lie.  For `audit` BASELINE configs[3]'s
                         snapshot; for the later passes config #4b's shape with topology, the bound pods carrying spread / affinity / anti-affinity terms
@@ -29,12 +32,15 @@ sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 from karpenter_core_amd import fake, scheduler as S, workloads as W
 
 PASSES = dict(S._AUDIT_PASSES, **S._AUDIT_PASSES_BESIDE, **S._AUDIT_PASSES_REASONS)      # every pass with a call of its own; the gate runs the first table's
-if len(sys.argv) < 2 or not all(p in PASSES or p == "gate" for p in sys.argv[1].split(",")):
+if len(sys.argv) < 2 or not all(p in PASSES or p in ("gate", "gate_ex") for p in sys.argv[1].split(",")):
     sys.exit(__doc__)
 passes = sys.argv[1].split(",")
 gated = [p for p in passes if p in S._AUDIT_PASSES] or list(S._AUDIT_PASSES)      # what the gate runs
 if passes == ["gate"]:
     passes += gated
+BESIDE = [w for w in S.AUDIT_GATE_ALL if w not in S._AUDIT_PASSES]      # the passes the old gate leaves to calls of their own
+if "gate_ex" in passes:
+    passes = ["gate_ex", "gate"] + BESIDE
 legs = (sys.argv[2] if len(sys.argv) > 2 else "config3,whatifs,config5").split(",")
 reps = int(sys.argv[3]) if len(sys.argv) > 3 else 9
 if S.device_count() < 1:
@@ -51,9 +57,43 @@ def timed(call):
     return [call() for _ in range(reps + 1)][1:]
 
 
+def timed_runs(flats):
+    """{pass: timed()} over `flats`: pass after pass -- or, with gate_ex, interleaved: after one untimed call of each, `reps` rounds of one call of each"""
+    if "gate_ex" not in passes:
+        return {what: timed(lambda: audit(what, flats)) for what in passes}
+    for what in passes:
+        audit(what, flats)
+    runs = {what: [] for what in passes}
+    for _ in range(reps):
+        for what in passes:
+            runs[what].append(audit(what, flats))
+    return runs
+
+
 def audit(what, flats):
     """one timed call: a pass's own, or the gate's -- [its dict], the times in it as in a pass's"""
+    if what == "gate_ex":
+        return [S.audit_gate(flats, list(S.AUDIT_GATE_ALL), cap_findings=0)]
     return S._audit(what, flats) if what != "gate" else [S.audit_gate(flats, gated, cap_findings=0)]
+
+
+def report_gate_ex(pack_ms, runs):
+    """the wide gate against the three calls, round by round"""
+    laps, three = runs["gate_ex"], ["gate"] + BESIDE
+    wall = [sum(l[0]["ms"]) for l in laps]
+    seq_k = [sum(runs[w][i][0]["ms"][0] for w in three) for i in range(len(laps))]
+    seq_r = [sum(runs[w][i][0]["ms"][1] for w in three) for i in range(len(laps))]
+    seq = [k + r for k, r in zip(seq_k, seq_r)]
+    print(f"   gate_ex ({', '.join(S.AUDIT_GATE_ALL)}) kernels   {stat([l[0]['ms'][0] for l in laps])}")
+    print(f"   gate_ex read-back {stat([l[0]['ms'][1] for l in laps])}")
+    print(f"   gate_ex kernels + read-back {stat(wall)}; / pack kernel {statistics.median(wall) / pack_ms * 100:.2f} %")
+    print(f"   the three calls (gate over the six, {', '.join(BESIDE)}), summed per round: kernels {stat(seq_k)}")
+    print(f"   the three calls read-back {stat(seq_r)}")
+    print(f"   the three calls kernels + read-back {stat(seq)}")
+    print(f"   gate_ex / the three calls: kernels + read-back {statistics.median(wall) / statistics.median(seq):.3f}, kernels {statistics.median(l[0]['ms'][0] for l in laps) / statistics.median(seq_k):.3f}, "
+          f"read-back {statistics.median(l[0]['ms'][1] for l in laps) / statistics.median(seq_r):.3f}; gate_ex max {max(wall):.3f} ms against the three calls' min {min(seq):.3f} ms")
+    last = laps[-1][0]
+    print(f"   result: gate_ex {'clean' if last['clean'] else 'FOUND %d' % last['n_findings']}", flush=True)
 
 
 def report_gate(pack_ms, runs):
@@ -74,10 +114,12 @@ def report_gate(pack_ms, runs):
 def report(pack_ms, runs):
     """runs: {pass: timed()}"""
     per_pair = {}
+    if "gate_ex" in runs:
+        report_gate_ex(pack_ms, runs)
     if "gate" in runs:
         report_gate(pack_ms, runs)
     for what, laps in runs.items():
-        if what == "gate":
+        if what in ("gate", "gate_ex"):
             continue
         p, last = PASSES[what], laps[-1]
         kernels, both = statistics.median(l[0]["ms"][0] for l in laps), statistics.median(sum(l[0]["ms"]) for l in laps)
@@ -106,8 +148,8 @@ def single(name, problem):
     pack_ms, wall_ms = f.kernel_ms, f.wall_ms
     f.solve(decode=False)      # (the second Solve of a resident problem: tables built, kernels loaded)
     pack_ms = min(pack_ms, f.kernel_ms)
-    runs = {what: timed(lambda: audit(what, [f])) for what in passes}
-    d, first = f.dims, runs[[p for p in passes if p != "gate"][0]][0][0]
+    runs = timed_runs([f])
+    d, first = f.dims, runs[[p for p in passes if p not in ("gate", "gate_ex")][0]][0][0]
     print(f"{name}: {d['P']} pods, {d['T']} types, {d['E']} existing nodes, {d['C']} classes, {d['M']} templates, {d['G']} topology groups ({d['GH']} on the hostname); "
           + ", ".join(f"{k} {first[k]}" for k in SIZES if k in first) + f"; ks_pack_rr {f.rr_status()}", flush=True)
     print(f"   flatten + upload {(t1 - t0) * 1e3:.0f} ms; pack kernel {pack_ms:.2f} ms (Solve wall {wall_ms:.2f} ms)")
@@ -124,7 +166,7 @@ def whatifs():
         from test_whatif_derived import _topology_snapshot      # (the generator of the differential tests)
         its, prov, nodes, bound, snap, pod_node = _topology_snapshot(2048, 50, 45, spare=-1, extras=True, anti=True)
         name = "config #4b with topology"
-        if passes[0] in ("limits", "gate"):
+        if passes[0] in ("limits", "gate", "gate_ex"):
             limit = {"cpu": str(int(sum(fake._qty_value(n.capacity.get("cpu", "0")) for n in nodes)))}
             for p in snap.provisioners:
                 p.limits = dict(limit)
@@ -132,8 +174,8 @@ def whatifs():
     flats = S.open_whatifs(S.ParsedProblem(snap), pod_node, W.config4_sets(512, 2048, 45), derive=True)
     S.solve_batch_resident(flats)
     pack_ms, _ = S.solve_batch_resident(flats)
-    runs = {what: timed(lambda: audit(what, flats)) for what in passes}
-    first = runs[[p for p in passes if p != "gate"][0]][0]
+    runs = timed_runs(flats)
+    first = runs[[p for p in passes if p not in ("gate", "gate_ex")][0]][0]
     print(f"{name}: {len(flats)} what-ifs derived on the device over {len(nodes)} nodes / {len(its)} types; {sum(len(a['pod_flags']) for a in first)} pods, "
           f"{sum(a['n_new'] for a in first)} new nodes in all", flush=True)
     print(f"   pack kernel (one batched launch) {pack_ms:.2f} ms")
