@@ -634,6 +634,25 @@ typedef struct ksh_audit_hostfit_out {
 int ksh_audit_hostfit(void** handles, uint32_t n, ksh_audit_hostfit_out* outs /* [n] */, double* ms /* [2] kernels | read-back, or NULL */);
 /* A claimed result for one flattened handle, exactly as ksh_audit_firstfit_claimed takes it. */
 int ksh_audit_hostfit_claimed(void* handle, const ksh_result_arrays* claimed, const int32_t* pod_seq /* [n_pods] */, ksh_audit_hostfit_out* out, double* ms /* [2] or NULL */);
+/* The audit's NINTH pass, opt-in and beside the gate (ksolve.h ks_audit_zonefit_dev, KS_AUDIT_POD_ZFIT_*): first-fit order for the pods whose constraining groups are
+ * all eligible zonal spread groups -- the pods neither the fourth nor the sixth pass examines.  The final state together with the commit numbers gives, per pod, the
+ * zones that certainly admitted it at its moment; an earlier existing node, or an earlier-opened machine, in such a zone that the fourth pass's predicate admits
+ * cannot have been passed over.  The fourth pass's conventions (cap_pods, KSH_AUDIT_TRUNCATED_PODS, indices as ksh_audit's).  eligible_groups / skipped_groups as the
+ * sixth pass's; mixed_pods: the skipped pods whose class mixes zonal and hostname groups; checked[0]: the placed pods; [1]: the pods examined (skipped_pods: the
+ * others); [2]: the (pod, node) pairs whose zone test ran; [3]: those that passed it; admitting_pairs: the pairs that admitted; exact_pods: the examined pods whose
+ * zone masks are the reference's own numbers. */
+typedef struct ksh_audit_zonefit_out {
+  uint32_t* pod_flags; uint64_t cap_pods;      /* [cap_pods] KS_AUDIT_POD_SEQ | KS_AUDIT_POD_ZFIT_* */
+  uint32_t n_pods, n_new, n_placed, skipped_pods;
+  uint32_t n_pods_flagged, truncated /* KSH_AUDIT_TRUNCATED_PODS */;
+  uint32_t eligible_groups, skipped_groups;
+  uint32_t mixed_pods, exact_pods;
+  uint32_t checked[4];
+  uint32_t admitting_pairs, pad;
+} ksh_audit_zonefit_out;
+int ksh_audit_zonefit(void** handles, uint32_t n, ksh_audit_zonefit_out* outs /* [n] */, double* ms /* [2] kernels | read-back, or NULL */);
+/* A claimed result for one flattened handle, exactly as ksh_audit_firstfit_claimed takes it. */
+int ksh_audit_zonefit_claimed(void* handle, const ksh_result_arrays* claimed, const int32_t* pod_seq /* [n_pods] */, ksh_audit_zonefit_out* out, double* ms /* [2] or NULL */);
 /* The audit's SEVENTH pass, opt-in (ksolve.h ks_audit_stages_dev, KS_AUDIT_POD_STAGE_*): relaxation order -- no pod ended at a later stage of its chain than one at
  * which an existing node's final state, or a fresh machine of a provisioner without limits, would have taken it, and no unscheduled pod stopped short of its chain's
  * end.  It is the gate's seventh pass (KS_AUDIT_PASS_STAGES through ksh_audit_gate_ex); this call remains the way to its flag rows.  The fourth pass's conventions (cap_pods, KSH_AUDIT_TRUNCATED_PODS, indices

@@ -1022,6 +1022,58 @@ typedef struct ks_audit_reasons {
 int ks_audit_reasons_dev(ks_dev_problem* d, const ks_result* claimed /* or NULL; pod_node, pod_stage, pod_reason are read */, ks_audit_reasons* out);
 int ks_audit_reasons_batch_dev(ks_dev_problem* const* ds, uint32_t n, ks_audit_reasons* const* outs);
 
+/* ---- the audit's NINTH pass, opt-in and beside the gate: FIRST-FIT ORDER for pods under ZONAL SPREAD -- the pods the fourth pass leaves out because a topology group
+ * constrains them and the sixth leaves out because the group is on a narrow key.  Nothing calls it unless asked; the eight passes above and the gate are unchanged by
+ * it.  A zonal group's minimum moves over time, so the final state alone decides nothing; the final state TOGETHER WITH the commit numbers does.  One-sided like the
+ * passes before it; the bits share their word with KS_AUDIT_POD_SEQ, defined as in the second pass.
+ * ELIGIBLE group g: the third pass's definition, unchanged: grp_type[g] == 0, a narrow key 0 <= grp_key[g] < K, not skipped, an empty node filter.  eligible_groups
+ * counts them, skipped_groups every other group of the problem.
+ * EXAMINED pod P: it does not fail SEQ, or it is unscheduled; its final-stage class c reserves no host port; isel_list(c) is empty; own_list(c) holds between one and
+ * KS_AZ_GROUPS entries and every one of them is eligible.  Every other pod is counted in skipped_pods; of those, the pods whose class owns an eligible zonal group and
+ * is also constrained by a hostname-keyed group (own_list or isel_list) are counted in mixed_pods as well: the named next step.  The fourth, the sixth and this pass
+ * partition the pods they examine.
+ * THE MOMENT s: a placed P was tried for the last time when exactly the pods with commit number < s = pod_seq[P] had committed (scheduler.add walks the existing nodes,
+ * the new nodes and the templates, and nothing commits in between); an unscheduled P was tried last against the final state: s = n_placed (queue.go:52-66).
+ * ADMISSIBLE DOMAINS at s, per g in own_list(c) on key k: the third pass's bounds at prefix s -- L_s[e] over the certain recorders with commit number < s, U_s[e]
+ * over all of them, the wild count W_s --, its `among` (the registered domains e, grp_count[g][e] >= 0, for which the class's requirement on k Has e; an absent key
+ * has every value) and self (bit 31 of the entry):
+ *   OK_s[g] = { e registered : U_s[e] + W_s + self - min over e' in among of L_s[e'] <= grp_max_skew[g] }
+ * The true count is at most U + W and the true minimum at least min L: e in OK_s[g] implies that the inequality of topologygroup.go:171 held at s -- the opposite
+ * pairing of the bounds to the third pass's test, on purpose.  With `among` empty OK_s[g] is empty: Go's MaxInt32 minimum admits everything there and the pass proves
+ * nothing from it.
+ * TARGETS.  Existing node e (a class that mounts volumes has none): the fourth pass's admits_existing(c, e), with its condition on labelled keys and Fits over the
+ * final sums, AND for every g of c: e carries the label of key(g) with the single value z, and z is in OK_s[g] (the node's nodeDomains is {z} for its whole life, so
+ * the topology step admits iff z is admissible, existingnode.go:104-120).  New node j, only
+ * for a pod that opened its node (s == open(node(P))) or is unscheduled: open(j) < s; for every g the requirement of j on key(g) was one value before s (the third
+ * pass's `certain` at commit number s - 1) and its final single value z is in OK_s[g]; the fourth pass's admits_new(c, j) with its template-presence and
+ * non-empty-intersection rules.  Requirements only narrow, so the value at s was z.  Templates are no targets: with several zones open the arg-min domain and Go's
+ * map order decide. */
+#define KS_AZ_GROUPS 4u                        /* the most eligible groups a class may own and still be examined */
+#define KS_AUDIT_POD_ZFIT_EXISTING 67108864u   /* P is on existing node e_P and some target e < e_P admits at s; or P is on a new node or unscheduled and some existing node admits at s */
+#define KS_AUDIT_POD_ZFIT_NEW 134217728u       /* P opened its new node or is unscheduled, and some new node j with open(j) < s admits at s */
+/* A pod that joined a new node it did not open is checked against existing nodes only, as in the fourth pass.  NOT attempted: templates, limited templates, the order
+ * among new nodes, classes mixing zonal and hostname groups, groups under a node filter, late-created groups, host ports, existing nodes on keys they do not label. */
+typedef struct ks_audit_zonefit {
+  uint32_t* pod_flags;            /* [P] KS_AUDIT_POD_SEQ | KS_AUDIT_POD_ZFIT_*, or NULL (totals only) */
+  uint32_t n_pods, n_new;         /* out: P | the new nodes of the result that was audited */
+  uint32_t n_placed;              /* out: pods on a node of the result */
+  uint32_t eligible_groups, skipped_groups;   /* out: the eligible groups | the other groups of the problem */
+  uint32_t skipped_pods, mixed_pods;          /* out: the pods that are not examined | those of them whose class mixes eligible zonal groups with hostname groups */
+  uint32_t n_pods_flagged;
+  uint32_t checked[4];            /* out: [0] the placed pods (SEQ); [1] the pods examined; [2] the (pod, node) pairs whose zone test ran; [3] the pairs that passed the zone test and had the static predicate evaluated */
+  uint32_t admitting_pairs;       /* out: the pairs that admitted -- in a clean result: existing nodes at or behind the pod's own.  A clean result with admitting_pairs == 0 proved little */
+  uint32_t exact_pods;            /* out: the examined pods with W == 0 and L == U on every registered domain of every group they own, and a non-empty `among`: there the masks are the reference's own numbers */
+  double kernel_ms, readback_ms;  /* out: as ks_audit's */
+} ks_audit_zonefit;
+/* claimed == NULL: the resident result, where it lies (the form for derived what-ifs).  claimed given (flattened problems only, KS_ERR_UNSUPPORTED for a derived
+ * view): the fourth pass's arrays are uploaded and read; every index a result supplies is range-checked before it addresses memory.  Twelve launches with no host
+ * wait between them, six of them the third and fourth passes' kernels as they are; a problem with no eligible group or no examined pod ends, as far as this pass's
+ * own work goes, after the count and mark launches (four): the kernels behind them that are this pass's return after one load, and the last writes the SEQ bits.
+ * The chunk table is the third pass's, so the batch form walks its problems in the third pass's slices.  Integer min, add and or; flags are written per index, no
+ * output through an atomic, no float: the same flags every run.  Refusals as ks_audit_firstfit_dev's. */
+int ks_audit_zonefit_dev(ks_dev_problem* d, const ks_result* claimed /* or NULL; pod_seq is read */, ks_audit_zonefit* out);
+int ks_audit_zonefit_batch_dev(ks_dev_problem* const* ds, uint32_t n, ks_audit_zonefit* const* outs);
+
 /* ---- the audit's GATE: chosen passes in ONE call, their totals and a list of FINDINGS reduced on the device.  The question a caller puts behind every result is
  * "is it clean?", and the answer is usually yes: the gate runs the chosen passes' own kernels, leaves their flag tables on the device, tallies them there and reads
  * back the totals alone -- no row of a flag table reaches the host.  The six passes and their entry points above are unchanged by it; they remain the way to the rows.

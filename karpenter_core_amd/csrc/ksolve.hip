@@ -4405,6 +4405,7 @@ extern "C" int ks_placement_rows_host(ks_dev_problem* const* ds, uint32_t n, con
 #include "ks_audit_hostfit.inc"  // its sixth, opt-in pass: first-fit order for hostname anti-affinity and hostname spread pods (ks_audit_hostfit_dev / ks_audit_hostfit_batch_dev)
 #include "ks_audit_stages.inc"   // its seventh, opt-in pass: relaxation order -- no pod ended at a later stage than one an existing node or a fresh machine would have taken it at (ks_audit_stages_dev / ks_audit_stages_batch_dev)
 #include "ks_audit_reasons.inc"  // its eighth, opt-in pass: failure reasons -- pod_reason's nibbles against what a fresh node of every template answers the pod's class (ks_audit_reasons_dev / ks_audit_reasons_batch_dev)
+#include "ks_audit_zonefit.inc"  // its ninth, opt-in pass, beside the gate: first-fit order for pods under zonal spread, from the prefix counts at each pod's commit number (ks_audit_zonefit_dev / ks_audit_zonefit_batch_dev)
 
 // ------------------------------------------------------------------------------------------------
 // Consolidation candidates (ksolve.h ks_consolidation_candidates_host): which nodes sortAndFilterCandidates keeps, and in what order.

@@ -886,6 +886,15 @@ struct AuditHostFit {
     o->eligible_groups = r.eligible_groups; o->skipped_groups = r.skipped_groups; memcpy(o->checked, r.checked, sizeof o->checked); o->admitting_pairs = r.admitting_pairs; o->pad = 0;
   }
 };
+struct AuditZoneFit {
+  using Dev = ks_audit_zonefit; using Out = ksh_audit_zonefit_out; static constexpr bool nodes = false, no_pod_seq = false;
+  static constexpr auto batch_dev = ks_audit_zonefit_batch_dev; static constexpr auto one_dev = ks_audit_zonefit_dev;
+  static void totals(const Dev& r, Out* o) {
+    o->n_pods = r.n_pods; o->n_new = r.n_new; o->n_placed = r.n_placed; o->skipped_pods = r.skipped_pods; o->n_pods_flagged = r.n_pods_flagged;
+    o->eligible_groups = r.eligible_groups; o->skipped_groups = r.skipped_groups; o->mixed_pods = r.mixed_pods; o->exact_pods = r.exact_pods;
+    memcpy(o->checked, r.checked, sizeof o->checked); o->admitting_pairs = r.admitting_pairs; o->pad = 0;
+  }
+};
 struct AuditStages {
   using Dev = ks_audit_stages; using Out = ksh_audit_stages_out; static constexpr bool nodes = false, no_pod_seq = false;
   static constexpr auto batch_dev = ks_audit_stages_batch_dev; static constexpr auto one_dev = ks_audit_stages_dev;
@@ -1094,6 +1103,8 @@ int ksh_audit_limits(void** hv, uint32_t n, ksh_audit_limits_out* outs, double* 
 int ksh_audit_limits_claimed(void* hv, const ksh_result_arrays* c, const int32_t* pod_seq, ksh_audit_limits_out* out, double* ms) { return audit_claimed<AuditLimits>(hv, c, pod_seq, out, ms); }
 int ksh_audit_hostfit(void** hv, uint32_t n, ksh_audit_hostfit_out* outs, double* ms) { return audit_resident<AuditHostFit>(hv, n, outs, ms); }
 int ksh_audit_hostfit_claimed(void* hv, const ksh_result_arrays* c, const int32_t* pod_seq, ksh_audit_hostfit_out* out, double* ms) { return audit_claimed<AuditHostFit>(hv, c, pod_seq, out, ms); }
+int ksh_audit_zonefit(void** hv, uint32_t n, ksh_audit_zonefit_out* outs, double* ms) { return audit_resident<AuditZoneFit>(hv, n, outs, ms); }
+int ksh_audit_zonefit_claimed(void* hv, const ksh_result_arrays* c, const int32_t* pod_seq, ksh_audit_zonefit_out* out, double* ms) { return audit_claimed<AuditZoneFit>(hv, c, pod_seq, out, ms); }
 int ksh_audit_stages(void** hv, uint32_t n, ksh_audit_stages_out* outs, double* ms) { return audit_resident<AuditStages>(hv, n, outs, ms); }
 int ksh_audit_stages_claimed(void* hv, const ksh_result_arrays* c, const int32_t* pod_seq, ksh_audit_stages_out* out, double* ms) { return audit_claimed<AuditStages>(hv, c, pod_seq, out, ms); }
 int ksh_audit_reasons(void** hv, uint32_t n, ksh_audit_reasons_out* outs, double* ms) { return audit_resident<AuditReasons>(hv, n, outs, ms); }

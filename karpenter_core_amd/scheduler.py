@@ -63,6 +63,10 @@ KS_AUDIT_STAGES_CHECKED = ("SEQ", "PODS", "STAGES", "PAIRS")
 # answers the pod's class; `checked`: unscheduled pods examined, nibbles decided exactly, nibbles bounded to a set, nibbles not examined
 KS_AUDIT_REASONS_BITS = {"REASON_PLACED": 4194304, "REASON_MISSING": 8388608, "REASON_SHAPE": 16777216, "REASON_STATIC": 33554432}
 KS_AUDIT_REASONS_CHECKED = ("PODS", "EXACT", "BOUNDED", "UNEXAMINED")
+# the ninth pass's (FlatProblem.audit_zonefit() / audit_zonefit_batch()), beside the gate: SEQ as above, and first-fit order for pods under zonal spread; `checked`: placed
+# pods, examined pods, (pod, node) pairs whose zone test ran, pairs that passed it
+KS_AUDIT_ZONEFIT_BITS = {"SEQ": 128, "ZFIT_EXISTING": 67108864, "ZFIT_NEW": 134217728}
+KS_AUDIT_ZONEFIT_CHECKED = ("SEQ", "PODS", "ZONE", "STATIC")
 KS_WHY = {"NONE": 0, "LIMITS": 1, "TAINTS": 2, "HOST_PORTS": 3, "REQUIREMENTS": 4, "TOPOLOGY": 5, "TOPOLOGY_REQS": 6, "NO_INSTANCE_TYPE": 7}      # ksolve.h KS_WHY_*
 
 
@@ -395,6 +399,13 @@ class FlatProblem:
         for the pods whose constraining groups are all hostname anti-affinity or unfiltered hostname spread.  Arguments as `audit_topology`'s.  Returns
         `audit_firstfit`'s dict ("checked": SEQ, PODS, PAIRS and TESTS, the (pair, group) count tests evaluated) plus "eligible_groups" and "skipped_groups"."""
         return _audit("hostfit", [self], claimed, pod_seq)[0]
+
+    def audit_zonefit(self, claimed: Optional[dict] = None, pod_seq=None) -> dict:
+        """The audit's ninth, opt-in pass, beside the gate (include/ksolve.h KS_AUDIT_POD_ZFIT_*, kshost.h ksh_audit_zonefit / ksh_audit_zonefit_claimed): first-fit order for
+        the pods whose constraining groups are all eligible zonal spread groups, from the final state and the prefix counts at each pod's commit number.  Arguments as
+        `audit_topology`'s.  Returns `audit_hostfit`'s dict ("checked": SEQ, PODS, ZONE the (pod, node) pairs whose zone test ran, STATIC those that passed it) plus
+        "mixed_pods" and "exact_pods"."""
+        return _audit("zonefit", [self], claimed, pod_seq)[0]
 
     def audit_stages(self, claimed: Optional[dict] = None, pod_seq=None) -> dict:
         """The audit's seventh, opt-in pass (include/ksolve.h KS_AUDIT_POD_STAGE_*, kshost.h ksh_audit_stages / ksh_audit_stages_claimed): relaxation order -- no pod ended
@@ -888,12 +899,21 @@ _AUDIT_PASSES_REASONS = {
                     scalars=("skipped_pods", "n_unscheduled", "used_classes", "pairs", "n_new", "n_placed")),
 }
 
-for _p in list(_AUDIT_PASSES.values()) + list(_AUDIT_PASSES_BESIDE.values()) + list(_AUDIT_PASSES_REASONS.values()):      # include/kshost.h <stem>_out: the tables and their capacities, then `fields`
+# The pass over zonal spread pods: in the same form, in a table of its own, beside the gate -- the three above, and everything derived from them, stay what they were.
+_AUDIT_PASSES_ZONEFIT = {
+    "zonefit": dict(stem="ksh_audit_zonefit", seq=True, out="_AuditZoneFitOut", claimed=_CLAIMED_FIT, pod_bits=KS_AUDIT_ZONEFIT_BITS, node_bits=None, checked=KS_AUDIT_ZONEFIT_CHECKED,
+                    fields=("n_pods", "n_new", "n_placed", "skipped_pods", "n_pods_flagged", "truncated", "eligible_groups", "skipped_groups", "mixed_pods", "exact_pods", "checked*4",
+                            "admitting_pairs", "pad"),
+                    scalars=("admitting_pairs", "exact_pods", "skipped_pods", "mixed_pods", "eligible_groups", "skipped_groups", "n_new", "n_placed")),
+}
+
+for _p in list(_AUDIT_PASSES.values()) + list(_AUDIT_PASSES_BESIDE.values()) + list(_AUDIT_PASSES_REASONS.values()) + list(_AUDIT_PASSES_ZONEFIT.values()):      # include/kshost.h <stem>_out: the tables and their capacities, then `fields`
     _tables = [("pod_flags", ctypes.c_void_p), ("cap_pods", ctypes.c_uint64)] + ([("node_flags", ctypes.c_void_p), ("cap_nodes", ctypes.c_uint64)] if _p["node_bits"] else [])
     _p["Out"] = type(_p["out"], (ctypes.Structure,), {"_fields_": _tables + [(n, ctypes.c_uint32 * int(k) if k else ctypes.c_uint32) for n, _, k in (f.partition("*") for f in _p["fields"])]})
 _AuditOut, _AuditTopologyOut, _AuditSpreadOut, _AuditFirstFitOut, _AuditLimitsOut, _AuditHostFitOut = (_AUDIT_PASSES[w]["Out"] for w in ("audit", "topology", "spread", "firstfit", "limits", "hostfit"))
 _AuditStagesOut = _AUDIT_PASSES_BESIDE["stages"]["Out"]
 _AuditReasonsOut = _AUDIT_PASSES_REASONS["reasons"]["Out"]
+_AuditZoneFitOut = _AUDIT_PASSES_ZONEFIT["zonefit"]["Out"]
 
 
 def _claimed_arrays(flat: "FlatProblem", claimed: dict, pod_seq, beyond, what: str):
@@ -920,7 +940,7 @@ def _claimed_arrays(flat: "FlatProblem", claimed: dict, pod_seq, beyond, what: s
 
 
 def _audit(what: str, flats: Sequence["FlatProblem"], claimed: Optional[dict] = None, pod_seq=None) -> List[dict]:
-    """One pass of the audit, as _AUDIT_PASSES[what] (or _AUDIT_PASSES_BESIDE[what], or _AUDIT_PASSES_REASONS[what]) states it: the call over the resident results of `flats`, or over `claimed` (with `pod_seq`, where the pass takes
+    """One pass of the audit, as _AUDIT_PASSES[what] (or _AUDIT_PASSES_BESIDE[what], _AUDIT_PASSES_REASONS[what] or, last, _AUDIT_PASSES_ZONEFIT[what]) states it: the call over the resident results of `flats`, or over `claimed` (with `pod_seq`, where the pass takes
     it) for flats[0]; once more with larger tables if one was too short.  One dict per problem."""
     import numpy as np
     if claimed is None and pod_seq is not None:
@@ -928,7 +948,7 @@ def _audit(what: str, flats: Sequence["FlatProblem"], claimed: Optional[dict] = 
     n = len(flats)
     if not n:
         return []
-    p, kh = _AUDIT_PASSES.get(what) or _AUDIT_PASSES_BESIDE.get(what) or _AUDIT_PASSES_REASONS[what], libs()[1]
+    p, kh = _AUDIT_PASSES.get(what) or _AUDIT_PASSES_BESIDE.get(what) or _AUDIT_PASSES_REASONS.get(what) or _AUDIT_PASSES_ZONEFIT[what], libs()[1]
     Out, nodes = p["Out"], p["node_bits"] is not None
     resident, claimed_fn = getattr(kh, p["stem"]), getattr(kh, p["stem"] + "_claimed")
     resident.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32, ctypes.POINTER(Out), ctypes.POINTER(ctypes.c_double)]
@@ -1117,6 +1137,12 @@ def audit_hostfit_batch(flats: Sequence["FlatProblem"]) -> List[dict]:
     """The audit's sixth pass over the results the last solve left on the device, for a whole batch (include/kshost.h ksh_audit_hostfit): handles of any kind, derived
     what-ifs included.  One dict per problem, as `FlatProblem.audit_hostfit` returns it."""
     return _audit("hostfit", flats)
+
+
+def audit_zonefit_batch(flats: Sequence["FlatProblem"]) -> List[dict]:
+    """The audit's ninth pass over the results the last solve left on the device, for a whole batch (include/kshost.h ksh_audit_zonefit): handles of any kind, derived
+    what-ifs included.  One dict per problem, as `FlatProblem.audit_zonefit` returns it."""
+    return _audit("zonefit", flats)
 
 
 def audit_stages_batch(flats: Sequence["FlatProblem"]) -> List[dict]:

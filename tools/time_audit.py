@@ -4,7 +4,8 @@ same run on the same box next to the pack kernel time of that Solve, what each p
 anything.  Needs a GPU.
    usage: tools/time_audit.py <pass>[,<pass>] [legs, comma separated] [reps]      (defaults: config3,whatifs,config5 9)
    pass   gate | gate_ex (below) | audit | topology | spread | firstfit | limits | hostfit (scheduler._AUDIT_PASSES) | stages (scheduler._AUDIT_PASSES_BESIDE) | reasons
-          (scheduler._AUDIT_PASSES_REASONS); the first one named is the subject, the others are timed beside it (hostfit,firstfit: the sixth pass beside the fourth,
+          (scheduler._AUDIT_PASSES_REASONS) | zonefit (scheduler._AUDIT_PASSES_ZONEFIT; zonefit,hostfit,spread: the ninth pass beside the sixth, its yardstick, and the
+          third, whose chunk table it builds again); the first one named is the subject, the others are timed beside it (hostfit,firstfit: the sixth pass beside the fourth,
           with the cost per evaluated pair of each; stages,firstfit: the seventh beside the fourth, whose pair kernels it runs over fewer classes; reasons,audit: the
           eighth beside the first, the other pass that reads no commit numbers)
           gate   the audit's gate (ksh_audit_gate) over the passes named beside it -- all six if it is named alone --, with no findings table: one call, totals
@@ -22,6 +23,8 @@ anything.  Needs a GPU.
           relax         tests/audit_stages_cases.py's family -- pods whose preferences cannot hold, over three existing nodes -- scaled until some thousand pods relax
           relaxwide     2 000 pods of 2 000 different requests that all relax once, over 1 024 existing nodes: as many distinct earlier-stage classes as pods, so that
                         the pair kernels, not the launches, are what is timed
+          zonal         tests/audit_zonefit_cases.py's family -- existing nodes over three zones, pods under zonal spread, some of which open machines -- seed 1 at
+                        scale 200: some 2 800 existing nodes and 9 000 pods
           stay          tests/audit_reasons_cases.py's family -- pods that stay unscheduled, each kind on purpose, nine provisioners of mixed kinds over two existing
                         nodes -- scaled until some thousand pods of many hundred classes stay unscheduled
 Per leg: the Solve (its pack kernel time as the library reports it), one untimed call of each pass, then each pass `reps` times: median with min and max of the
@@ -31,7 +34,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 from karpenter_core_amd import fake, scheduler as S, workloads as W
 
-PASSES = dict(S._AUDIT_PASSES, **S._AUDIT_PASSES_BESIDE, **S._AUDIT_PASSES_REASONS)      # every pass with a call of its own; the gate runs the first table's
+PASSES = dict(S._AUDIT_PASSES, **S._AUDIT_PASSES_BESIDE, **S._AUDIT_PASSES_REASONS, **S._AUDIT_PASSES_ZONEFIT)      # every pass with a call of its own; the gate runs the first table's
 if len(sys.argv) < 2 or not all(p in PASSES or p in ("gate", "gate_ex") for p in sys.argv[1].split(",")):
     sys.exit(__doc__)
 passes = sys.argv[1].split(",")
@@ -130,8 +133,8 @@ def report(pack_ms, runs):
         counters = {k: sum(a[k] for a in last) for k in p["scalars"] if k not in SIZES}
         if checked or counters:
             print(f"   {what}: checked {checked}; " + "; ".join(f"{k} {v}" for k, v in counters.items()))
-        if checked.get("PAIRS"):
-            per_pair[what] = kernels * 1e6 / checked["PAIRS"]
+        if checked.get("PAIRS") or checked.get("ZONE"):      # (the ninth pass counts its (pod, node) pairs under ZONE: the zone test runs on every one)
+            per_pair[what] = kernels * 1e6 / (checked.get("PAIRS") or checked["ZONE"])
         flagged = {k: sum(a[t][k] for a in last) for t, bits in (("pod_bit_count", p["pod_bits"]), ("node_bit_count", p["node_bits"] or {})) for k in bits}
         print(f"   result: {what} {'clean (nothing flagged)' if not any(flagged.values()) else 'FLAGGED %s' % {k: v for k, v in flagged.items() if v}}", flush=True)
     if len(per_pair) > 1:      # (passes that count (class, node) pairs, side by side)
@@ -205,6 +208,9 @@ for leg in legs:
     elif leg == "relaxwide":
         import audit_stages_cases
         single("2 000 relaxing pods of 2 000 classes over 1 024 existing nodes", audit_stages_cases.many_relaxed(2000, nodes=1024))
+    elif leg == "zonal":
+        import audit_zonefit_cases
+        single("the zonal family, seed 1 at scale 200", audit_zonefit_cases.zonal_cluster(1, scale=200))
     elif leg == "stay":
         import audit_reasons_cases
         single("the unscheduled family, seed 7 with nine provisioners and existing nodes, scale 300", audit_reasons_cases.stay_problem(**dict(audit_reasons_cases.FAMILY[6][1], scale=300)))
