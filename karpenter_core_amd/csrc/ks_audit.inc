@@ -9,9 +9,9 @@
 //   ks_audit_scan    one workgroup per problem: the exclusive scan of the counts (Hillis-Steele over an LDS tile, ks_placement_heads' way) = the node -> pods CSR's offsets.
 //   ks_audit_pods    one lane per pod: the pod bits that need no neighbour, and the pod's slot in its node's list (the counting sort's second half: the order within a
 //                    node depends on the run, and nothing below depends on that order -- int64 sums, unions and all-pairs tests).
-//   ks_audit_nodes   one wave per node: lanes stride the node's pods for the int64 sums and reduce across the wave; then one instance type per lane -- it_mask[k*T+t]
-//                    coalesced over t, Fits over R, the offering test against the node's zone x capacity-type mask -- and a ballot gives the 64-bit word that is compared
-//                    with the node's InstanceTypeOptions.  Host ports and volumes are walked per node (rare and short).  The PORTS bit of a pod is added to its flag
+//   ks_audit_nodes   one wave per node: lanes stride the node's pods for the int64 sums and reduce across the wave; then one instance type per lane -- the per-type
+//                    predicate every pass shares (AudNode, aud_node_type_ok below), over the node as the result leaves it -- and a ballot gives the 64-bit word that is
+//                    compared with the node's InstanceTypeOptions.  Host ports and volumes are walked per node (rare and short).  The PORTS bit of a pod is added to its flag
 //                    word by the one lane that holds the pod: a plain read-modify-write, after ks_audit_pods has finished.
 struct AuditView {
   const i32* pod_node; const i32* pod_stage; const i32* pod_seq; const i32* unscheduled; const u32* counts;      // counts: [0] n_new, [1] n_unscheduled
@@ -60,6 +60,85 @@ __device__ __forceinline__ u64 aud_pairs(const DevProb& P, const KReq& z, const 
 __device__ __forceinline__ bool aud_hn_listed(const DevProb& P, u32 c, u32 e) {
   for (u32 i = GC(u32, P.cls_hn_off)[c]; i < GC(u32, P.cls_hn_off)[c + 1]; ++i) if (GC(u32, P.hn_list)[i] == e) return true;
   return false;
+}
+// ---- filterInstanceTypesByRequirements (node.go:137-159) as every pass evaluates it: one view of the node, one state meet, one predicate per type, one walk ----
+__device__ __forceinline__ KReq aud_fit_cls_req(const DevProb& P, u32 c, u32 k) {
+  return load_req(GC(u32, P.cls.present)[c], GC(u32, P.cls.complement)[c], P.cls.mask + (size_t)c * P.K, P.cls.gt + (size_t)c * P.K, P.cls.lt + (size_t)c * P.K, (int)k);
+}
+// what an instance type is filtered against: the node's requirements (presence and complement words; mask, gt and lt rows), its requests and their presence mask, its
+// type set, its instance-type state and its template -- as the makers below leave it, or with one pod of class c on top (aud_node_add); pairs: aud_node_pairs
+struct AudNode { u32 np_, nc_, rmask, c; const u64* nmask; const i32* ngt; const i32* nlt; const i64* nreq; const u64* ntypes; i32 it, m; u64 pairs; bool cls; };
+// new node j as the result leaves it (m: as claimed -- the caller tests its range before it reads anything through it)
+__device__ __forceinline__ AudNode aud_node_final(const DevProb& P, const AuditView& V, u32 j) {
+  AudNode n; const u32 K = P.K;
+  n.np_ = GC(u32, V.o_present)[j]; n.nc_ = GC(u32, V.o_complement)[j]; n.nmask = V.o_mask + (size_t)j * K; n.ngt = V.o_gt + (size_t)j * K; n.nlt = V.o_lt + (size_t)j * K;
+  n.nreq = V.o_req + (size_t)j * P.R; n.rmask = GC(u32, V.o_reqmask)[j]; n.ntypes = V.n_types + (size_t)j * P.TW; n.it = GC(i32, V.o_it)[j]; n.m = GC(i32, V.n_tmpl)[j];
+  n.c = 0; n.cls = false; n.pairs = 0;
+  return n;
+}
+// a fresh node of template m: the template's requirements, its daemon overhead, its types
+__device__ __forceinline__ AudNode aud_node_fresh(const DevProb& P, u32 m) {
+  AudNode n; const u32 K = P.K;
+  n.np_ = GC(u32, P.tmpl.present)[m]; n.nc_ = GC(u32, P.tmpl.complement)[m]; n.nmask = P.tmpl.mask + (size_t)m * K; n.ngt = P.tmpl.gt + (size_t)m * K; n.nlt = P.tmpl.lt + (size_t)m * K;
+  n.nreq = P.tmpl_daemon + (size_t)m * P.R; n.rmask = GC(u32, P.tmpl_daemon_present)[m]; n.ntypes = P.tmpl_types + (size_t)m * P.TW; n.it = GC(i32, P.tmpl.it_state)[m]; n.m = (i32)m;
+  n.c = 0; n.cls = false; n.pairs = 0;
+  return n;
+}
+// the view's requirement on key k
+__device__ __forceinline__ KReq aud_node_req(const DevProb& P, const AudNode& n, u32 k) {
+  const KReq a = load_req(n.np_, n.nc_, n.nmask, n.ngt, n.nlt, (int)k);
+  return n.cls ? kreq_add(a, aud_fit_cls_req(P, n.c, k), P.value_int + k * 64, GC(u32, P.key_nvalues)[k]) : a;
+}
+// the zone x capacity-type pairs the view allows: taken once per view, after the last change to it
+__device__ __forceinline__ void aud_node_pairs(const DevProb& P, AudNode& n) {
+  KReq rz = kreq_absent(), rc = kreq_absent();
+  if (P.key_zone >= 0) rz = aud_node_req(P, n, (u32)P.key_zone);
+  if (P.key_ct >= 0) rc = aud_node_req(P, n, (u32)P.key_ct);
+  n.pairs = aud_pairs(P, rz, rc);
+}
+// one pod of class c on top: its requirements met with the node's, its requests added
+__device__ __forceinline__ void aud_node_add(const DevProb& P, AudNode& n, u32 c) {
+  n.c = c; n.cls = true; n.rmask |= GC(u32, P.cls_requests_present)[c];
+  aud_node_pairs(P, n);
+}
+// the view's instance-type state met with class c's, or S where the lattice has no meet; aud_node_state_refuses: the two are not Compatible at all
+__device__ __forceinline__ bool aud_node_state_refuses(const DevProb& P, const AudNode& n, u32 c) {
+  const i32 sa = n.it, sb = GC(i32, P.cls.it_state)[c];
+  return sa < 0 || (u32)sa >= P.S || (P.SC && (sb < 0 || (u32)sb >= P.SC || GC(u8, P.its_fail)[(size_t)sa * P.SC + sb]));
+}
+__device__ __forceinline__ u32 aud_node_state_meet(const DevProb& P, const AudNode& n, u32 c) {
+  if (aud_node_state_refuses(P, n, c)) return P.S;
+  if (!P.SC) return (u32)n.it;
+  const u32 si = GC(u16, P.its_inter)[(size_t)n.it * P.SC + (u32)GC(i32, P.cls.it_state)[c]];
+  return si < P.S ? si : P.S;
+}
+// compatible && fits && hasOffering (node.go:137-159) for type t
+__device__ __forceinline__ bool aud_node_type_ok(const DevProb& P, const AudNode& n, u32 t) {
+  const u32 K = P.K, R = P.R, T = P.T, tp = GC(u32, P.it_present)[t], tc = GC(u32, P.it_complement)[t], mp = n.cls ? (n.np_ | GC(u32, P.cls.present)[n.c]) : n.np_;
+  bool ok = true;
+  for (u32 k = 0; k < K && ok; ++k) {
+    if (!((mp >> k) & 1u) || !((tp >> k) & 1u)) continue;
+    KReq a; a.present = true; a.complement = (tc >> k) & 1u; a.mask = GC(u64, P.it_mask)[(size_t)k * T + t]; a.gt = KS_NOGT; a.lt = KS_NOLT;
+    if (kreq_intersects_fail(a, aud_node_req(P, n, k), P.value_int + k * 64, GC(u32, P.key_nvalues)[k])) ok = false;
+  }
+  for (u32 r = 0; r < R && ok; ++r) {
+    if (!((n.rmask >> r) & 1u)) continue;
+    const i64 need = n.cls ? (i64)((u64)GC(i64, n.nreq)[r] + (u64)GC(i64, P.cls_requests)[(size_t)n.c * R + r]) : GC(i64, n.nreq)[r];
+    if (need > GC(i64, P.it_alloc)[(size_t)r * T + t]) ok = false;
+  }
+  return ok && (GC(u64, P.it_offer)[t] & n.pairs) != 0;
+}
+// does any type of the view's set and of state si pass?  One type per lane, word by word -- it_mask[k*T+t] coalesced over t --; a ballot ends the walk at the first
+// word a type passes in (the ballot is the same in all 64 lanes: they leave together)
+__device__ __forceinline__ bool aud_node_any_type(const DevProb& P, const AudNode& n, u32 si, u32 lane) {
+  bool any = false;
+  for (u32 tw = 0; tw < P.TW && !any; ++tw) {
+    const u32 t = tw * 64u + lane;
+    bool ok = t < P.T && ((GC(u64, n.ntypes)[tw] >> lane) & 1ull) && ((GC(u64, P.its_types)[(size_t)si * P.TW + tw] >> lane) & 1ull);
+    if (ok) ok = aud_node_type_ok(P, n, t);
+    any = ballot64(ok) != 0;
+  }
+  return any;
 }
 // the sum of `mine` over the 256 threads of the workgroup, in s[0] for thread 0 (s: an LDS tile of 256 the caller owns and may use again after a barrier)
 __device__ __forceinline__ void aud_block_sum(u32* s, u32 mine) {
@@ -145,7 +224,7 @@ __global__ __launch_bounds__(256) void ks_audit_pods(const DevProb* probs, const
 }
 __global__ __launch_bounds__(256) void ks_audit_nodes(const DevProb* probs, const AuditView* views) {
   const DevProb& P = probs[blockIdx.y]; const AuditView& V = views[blockIdx.y];
-  const u32 lane = threadIdx.x & 63u, E = P.E, NS = E + aud_n_new(P, V), R = P.R, K = P.K, T = P.T, TW = P.TW;
+  const u32 lane = threadIdx.x & 63u, E = P.E, NS = E + aud_n_new(P, V), R = P.R, T = P.T, TW = P.TW;
   for (u32 s = blockIdx.x * 4u + (threadIdx.x >> 6); s < NS; s += gridDim.x * 4u) {      // (s, and everything read through it, is the same in all 64 lanes)
     const u32 b = V.off[s], e = V.off[s + 1]; const bool existing = s < E; const u32 j = s - E;
     u32 f = 0;
@@ -221,25 +300,12 @@ __global__ __launch_bounds__(256) void ks_audit_nodes(const DevProb* probs, cons
     for (int r = 0; r < KS_MAX_RES; ++r) if ((u32)r < R) { if (GC(i64, V.o_req)[(size_t)j * R + r] != (i64)((u64)GC(i64, P.tmpl_daemon)[(size_t)m * R + r] + (u64)sum[r])) req_bad = true; }
     if (req_bad) f |= KS_AUDIT_NODE_REQUESTS;
     // InstanceTypeOptions against filterInstanceTypesByRequirements (node.go:137-159) by the node's final requirements and requests: one type per lane
-    const u32 np_ = GC(u32, V.o_present)[j], nc_ = GC(u32, V.o_complement)[j]; const i32 its = GC(i32, V.o_it)[j]; const bool its_ok = its >= 0 && (u32)its < P.S;
-    KReq rz = kreq_absent(), rc = kreq_absent();
-    if (P.key_zone >= 0) rz = load_req(np_, nc_, V.o_mask + (size_t)j * K, V.o_gt + (size_t)j * K, V.o_lt + (size_t)j * K, P.key_zone);
-    if (P.key_ct >= 0) rc = load_req(np_, nc_, V.o_mask + (size_t)j * K, V.o_gt + (size_t)j * K, V.o_lt + (size_t)j * K, P.key_ct);
-    const u64 pairs = aud_pairs(P, rz, rc);
+    AudNode fn = aud_node_final(P, V, j); const i32 its = fn.it; const bool its_ok = its >= 0 && (u32)its < P.S;
+    aud_node_pairs(P, fn);
     u64 extra = 0, missing = 0, any = 0;
     for (u32 w = 0; w < TW; ++w) {
       const u32 t = w * 64u + lane; bool ok = t < T && its_ok;
-      if (ok) ok = ((GC(u64, P.tmpl_types)[(size_t)m * TW + w] >> lane) & 1ull) && ((GC(u64, P.its_types)[(size_t)its * TW + w] >> lane) & 1ull);
-      if (ok) {
-        const u32 tp = GC(u32, P.it_present)[t], tc = GC(u32, P.it_complement)[t];
-        for (u32 k = 0; k < K && ok; ++k) {
-          if (!((np_ >> k) & 1u) || !((tp >> k) & 1u)) continue;
-          KReq a; a.present = true; a.complement = (tc >> k) & 1u; a.mask = GC(u64, P.it_mask)[(size_t)k * T + t]; a.gt = KS_NOGT; a.lt = KS_NOLT;
-          if (kreq_intersects_fail(a, load_req(np_, nc_, V.o_mask + (size_t)j * K, V.o_gt + (size_t)j * K, V.o_lt + (size_t)j * K, (int)k), P.value_int + k * 64, GC(u32, P.key_nvalues)[k])) ok = false;
-        }
-        for (u32 r = 0; r < R && ok; ++r) if (((rmask >> r) & 1u) && GC(i64, V.o_req)[(size_t)j * R + r] > GC(i64, P.it_alloc)[(size_t)r * T + t]) ok = false;
-        if (ok) ok = (GC(u64, P.it_offer)[t] & pairs) != 0;
-      }
+      if (ok) ok = ((GC(u64, P.tmpl_types)[(size_t)m * TW + w] >> lane) & 1ull) && ((GC(u64, P.its_types)[(size_t)its * TW + w] >> lane) & 1ull) && aud_node_type_ok(P, fn, t);
       const u64 pass = __ballot(ok), have = GC(u64, V.n_types)[(size_t)j * TW + w];
       extra |= have & ~pass; missing |= pass & ~have; any |= have;
     }
@@ -275,6 +341,12 @@ static const u32 AUD_READS_ORDER = AUD_READS(pod_node) | AUD_READS(pod_stage) | 
                                    AUD_READS(node_mask) | AUD_READS(node_gt) | AUD_READS(node_lt);      // topology and spread: where the pods are, at which stage, in which order; the new nodes' templates and final requirements
 static const u32 AUD_READS_FIT = AUD_READS_ALL & ~AUD_READS(unscheduled);   // first-fit, limits, hostfit and stages
 static const u32 AUD_READS_REASONS = AUD_READS(pod_node) | AUD_READS(pod_stage);      // the eighth pass: where the pods are and at which stage -- and pod_reason, a side array (below), no member of KS_AUDIT_SEGS
+// a later pass's view of the result: the first pass's own outputs and scratch blanked, meta pointed at the pass's block
+static AuditView audit_pass_view(const AuditView& result, u32* meta) {
+  AuditView v = result;
+  v.meta = meta; v.mark = nullptr; v.pod_flags = nullptr; v.node_flags = nullptr; v.cnt = nullptr; v.off = nullptr; v.fill = nullptr; v.pods = nullptr;
+  return v;
+}
 // the result a solve left on the device
 static AuditView audit_resident(const DevState& s) {
   AuditView v{};

@@ -13,10 +13,12 @@
 //                         min, add and or: the same tables every run.
 //   ks_audit_ff_compact   one workgroup per problem: used[] compacted into the class list (ks_audit_scan's Hillis-Steele tile).
 //   ks_audit_ff_existing  one lane per (used class, existing node), a wave shares the class: the test is scalar per pair; a wave minimum, then atomicMin into first_e[u].
-//   ks_audit_ff_new       one wave per (used class, new node or unlimited template): the scalar clauses are wave-uniform; then one instance type per lane, word by
-//                         word -- it_mask[k*T+t] coalesced over t, Fits over R, the offering test against the zone x capacity-type mask, as ks_audit_nodes does --
-//                         and a ballot ends the walk at the first word a type passes in.  atomicMin into first_open[u] / first_m[u].
+//   ks_audit_ff_new       one wave per (used class, new node or unlimited template): aud_fit_admits_new below -- the one-sided clauses, wave-uniform, then ks_audit.inc's
+//                         walk over the types (AudNode, aud_node_any_type), one instance type per lane.  atomicMin into first_open[u] / first_m[u].
 //   ks_audit_ff_verdict   one lane per pod: its flag word and its checked word, one writer each, a plain store.
+// aud_fit_admits_new is THE new-node predicate of the audit: the sixth and the ninth pass call it for their own pairs, the fifth takes its clauses
+// (aud_fit_new_clauses), the eighth the state meet and the walk.  The existing-node kernels of the fourth and sixth pass are one body (aud_fit_existing_pairs), their
+// verdict kernels another (aud_fit_verdict); the ninth uses the body's predicates (aud_fit_mounts / _live / _labelled).
 // No float, no LDS beyond the count kernel's reduction and the scan tile, no dynamically indexed register array, no atomic on an output.
 #define KS_AF_NEVER 0xFFFFFFFFu
 struct AuditFitView {
@@ -28,9 +30,6 @@ struct AuditFitView {
 // no topology group constrains the class (Topology.AddRequirements adds nothing) and it reserves no host port
 __device__ __forceinline__ bool aud_fit_examinable(const DevProb& P, u32 c) {
   return GC(u32, P.cls_own_off)[c + 1] == GC(u32, P.cls_own_off)[c] && GC(u32, P.cls_isel_off)[c + 1] == GC(u32, P.cls_isel_off)[c] && GC(u32, P.cls_port_off)[c + 1] == GC(u32, P.cls_port_off)[c];
-}
-__device__ __forceinline__ KReq aud_fit_cls_req(const DevProb& P, u32 c, u32 k) {
-  return load_req(GC(u32, P.cls.present)[c], GC(u32, P.cls.complement)[c], P.cls.mask + (size_t)c * P.K, P.cls.gt + (size_t)c * P.K, P.cls.lt + (size_t)c * P.K, (int)k);
 }
 // the intersection of two present requirements is EMPTY.  Requirements.Intersects lets an empty intersection pass when both operators are NotIn / DoesNotExist
 // (requirements.go:196-200); this pass does not: a final state that passes only through that exception can have failed earlier (a node at Exists refuses the
@@ -58,6 +57,86 @@ __device__ __forceinline__ bool aud_fit_existing(const DevProb& P, const AuditFi
     if ((i64)need > GC(i64, P.en_avail)[(size_t)e * R + r]) return false;
   }
   return true;
+}
+// ---- admits_new(c, n): would new node n -- as the result leaves it, or a fresh one of a template (ks_audit.inc's views) -- have taken one more pod of class c? ----
+// The clauses that make the test one-sided, the same in all 64 lanes.  n: the node WITHOUT the pod on top
+__device__ __forceinline__ bool aud_fit_new_clauses(const DevProb& P, const AudNode& n, u32 c) {
+  bool ok = (GC(u64, P.tmpl_taints)[n.m] & ~GC(u64, P.cls_tolerated)[c]) == 0ull && GC(u8, P.cls_hn_mode)[c] != 1;      // (a new node's placeholder hostname is in no list, node.go:46)
+  const u32 cp = GC(u32, P.cls.present)[c], tmp = GC(u32, P.tmpl.present)[n.m];
+  for (u32 k = 0; k < P.K && ok; ++k) {
+    if (!((cp >> k) & 1u)) continue;
+    const KReq b = aud_fit_cls_req(P, c, k);
+    // "custom labels, if not defined, are denied" looks at the node AT THE TIME (requirements.go:125-130): a later pod may have added the key, the template had it all along
+    if (!((P.wellknown_mask >> k) & 1u) && !kreq_nidne(b) && !((tmp >> k) & 1u)) ok = false;
+    else if (aud_fit_meet_empty(aud_node_req(P, n, k), b, P.value_int + k * 64, GC(u32, P.key_nvalues)[k])) ok = false;
+  }
+  return ok;
+}
+// the clauses, the instance-type state's meet, then filterInstanceTypesByRequirements (node.go:137-159) against the requirements with the class added and the requests
+// with the class's: one type per lane.  Wave-uniform up to the walk; every lane returns the same
+__device__ __forceinline__ bool aud_fit_admits_new(const DevProb& P, AudNode n, u32 c, u32 lane) {
+  const u32 si = aud_fit_new_clauses(P, n, c) ? aud_node_state_meet(P, n, c) : P.S;
+  bool adm = false;
+  if (si < P.S) { aud_node_add(P, n, c); adm = aud_node_any_type(P, n, si, lane); }
+  return adm;
+}
+// ---- what the existing-node kernels share: the classes and nodes left out, the condition under which a pair is examined, and the tile's body ----
+// a class that mounts volumes is examined against new nodes only: they track none
+__device__ __forceinline__ bool aud_fit_mounts(const DevProb& P, u32 c) { return GC(u32, P.cls_vol_off)[c + 1] != GC(u32, P.cls_vol_off)[c]; }
+__device__ __forceinline__ bool aud_fit_live(const DevProb& P, u32 e) { return e < P.E && !(P.en_removed && ((GC(u64, P.en_removed)[e >> 6] >> (e & 63u)) & 1ull)); }
+// every key the class names is labelled on e: there the node's requirement at any time IS the label, and Compatible is exact
+__device__ __forceinline__ bool aud_fit_labelled(const DevProb& P, u32 c, u32 e) {
+  return (GC(u32, P.cls.present)[c] & ~GC(u32, P.en.present)[e]) == 0u && !(GC(i32, P.cls.it_state)[c] != 0 && GC(i32, P.en.it_state)[e] == 0);
+}
+// one lane per (used class, existing node), a workgroup shares the class.  more(c, e): what the pass tests before aud_fit_existing; counted(c, n): lane 0 of a wave,
+// after n pairs of it were examined
+template <class More, class Counted> __device__ __forceinline__ void aud_fit_existing_pairs(const DevProb& P, const AuditFitView& F, More&& more, Counted&& counted) {
+  const u32 lane = threadIdx.x & 63u, E = P.E, tiles = (E + 255u) / 256u, n_used = F.cntr[1];
+  const size_t total = (size_t)n_used * tiles;
+  for (size_t w = blockIdx.x; w < total; w += gridDim.x) {      // (w, u and c are the same in all 256 threads)
+    const u32 u = (u32)(w / tiles), e = (u32)(w % tiles) * 256u + threadIdx.x, c = F.list[u];
+    if (aud_fit_mounts(P, c)) continue;
+    const bool exam = aud_fit_live(P, e) && aud_fit_labelled(P, c, e), adm = exam && more(c, e) && aud_fit_existing(P, F, c, e);
+    u32 best = adm ? e : KS_AF_NEVER;
+    for (int x = 32; x > 0; x >>= 1) { const u32 o = __shfl_xor(best, x); best = o < best ? o : best; }
+    const u64 bx = ballot64(exam), ba = ballot64(adm);
+    if (lane == 0) {
+      if (best != KS_AF_NEVER) atomicMin(&F.first_e[u], best);
+      if (bx) { const u32 nx = (u32)__builtin_popcountll(bx); atomicAdd(&F.cntr[2], nx); counted(c, nx); }
+      if (ba) atomicAdd(&F.cntr[3], (u32)__builtin_popcountll(ba));
+    }
+  }
+}
+// ---- the verdict of the fourth and the sixth pass: one lane per pod, its flag word and its checked word.  BE, BN, BT: the pass's three bits; examinable(c): its test ----
+template <u32 BE, u32 BN, u32 BT, class Examinable> __device__ __forceinline__ void aud_fit_verdict(const DevProb& P, const AuditView& V, const AuditFitView& F, Examinable&& examinable) {
+  const u32 np = P.P, E = P.E, NS = E + aud_n_new(P, V), n_placed = F.cntr[0];
+  if (blockIdx.x == 0 && threadIdx.x == 0) { F.meta[0] = aud_n_new(P, V); F.meta[1] = n_placed; F.meta[2] = F.cntr[1]; F.meta[3] = F.cntr[2]; F.meta[4] = F.cntr[3]; }
+  for (u32 p = blockIdx.x * 256u + threadIdx.x; p < np; p += gridDim.x * 256u) {
+    const i32 nd = aud_where(P, V, p, NS);
+    const bool ok = nd >= 0 && aud_seq_ok(V, F.seqcnt, p, n_placed), unsched = GC(i32, V.pod_node)[p] == -1;
+    u32 f = (nd >= 0 && !ok) ? KS_AUDIT_POD_SEQ : 0u, chk = nd >= 0 ? 1u << 30 : 0u;
+    const u32 c = aud_class(P, V, p);
+    const u32 u1 = F.used[c];      // (the pass's mark kernel marked the class of every examined pod: never 0 for one)
+    if (!(ok || unsched) || !u1 || !examinable(c)) { F.flags[p] = f; F.chk[p] = chk | (1u << 29); continue; }
+    const u32 u = u1 - 1u;
+    const u32 fe = F.first_e[u], fo = F.first_open[u], fm = F.first_m[u];
+    if (unsched) {
+      if (fe != KS_AF_NEVER) f |= BE;
+      if (fo != KS_AF_NEVER) f |= BN;
+      if (fm != KS_AF_NEVER) f |= BT;
+    } else if ((u32)nd < E) {
+      if (fe < (u32)nd) f |= BE;
+    } else {
+      const u32 j = (u32)nd - E, sq = (u32)GC(i32, V.pod_seq)[p];
+      if (fe != KS_AF_NEVER) f |= BE;
+      if (sq == F.open[j]) {      // the opener of its node; a pod that joined a new node later is checked against existing nodes only (the order among new nodes depends on pod counts at the time)
+        if (fo < sq) f |= BN;      // (strictly: its own node opened at sq)
+        const i32 m = GC(i32, V.n_tmpl)[j];
+        if (m >= 0 && (u32)m < P.M && fm < (u32)m) f |= BT;
+      }
+    }
+    F.flags[p] = f; F.chk[p] = chk | 1u;
+  }
 }
 
 __global__ __launch_bounds__(256) void ks_audit_ff_count(const DevProb* probs, const AuditView* views, const AuditFitView* fviews) {
@@ -114,131 +193,52 @@ __global__ __launch_bounds__(256) void ks_audit_ff_compact(const DevProb* probs,
   if (tid == 0) F.cntr[1] = carry;
 }
 __global__ __launch_bounds__(256) void ks_audit_ff_existing(const DevProb* probs, const AuditFitView* fviews) {
-  const DevProb& P = probs[blockIdx.y]; const AuditFitView& F = fviews[blockIdx.y];
-  const u32 lane = threadIdx.x & 63u, E = P.E, tiles = (E + 255u) / 256u, n_used = F.cntr[1];
-  const size_t total = (size_t)n_used * tiles;
-  for (size_t w = blockIdx.x; w < total; w += gridDim.x) {      // (w, u and c are the same in all 256 threads)
-    const u32 u = (u32)(w / tiles), e = (u32)(w % tiles) * 256u + threadIdx.x, c = F.list[u];
-    if (GC(u32, P.cls_vol_off)[c + 1] != GC(u32, P.cls_vol_off)[c]) continue;      // a class that mounts volumes is examined against new nodes only: they track none
-    bool exam = e < E && !(P.en_removed && ((GC(u64, P.en_removed)[e >> 6] >> (e & 63u)) & 1ull)), adm = false;
-    // every key the class names is labelled on e: there the node's requirement at any time IS the label, and Compatible is exact
-    if (exam) exam = (GC(u32, P.cls.present)[c] & ~GC(u32, P.en.present)[e]) == 0u && !(GC(i32, P.cls.it_state)[c] != 0 && GC(i32, P.en.it_state)[e] == 0);
-    if (exam) adm = aud_fit_existing(P, F, c, e);
-    u32 best = adm ? e : KS_AF_NEVER;
-    for (int x = 32; x > 0; x >>= 1) { const u32 o = __shfl_xor(best, x); best = o < best ? o : best; }
-    const u64 bx = ballot64(exam), ba = ballot64(adm);
-    if (lane == 0) {
-      if (best != KS_AF_NEVER) atomicMin(&F.first_e[u], best);
-      if (bx) atomicAdd(&F.cntr[2], (u32)__builtin_popcountll(bx));
-      if (ba) atomicAdd(&F.cntr[3], (u32)__builtin_popcountll(ba));
-    }
-  }
+  aud_fit_existing_pairs(probs[blockIdx.y], fviews[blockIdx.y], [](u32, u32) { return true; }, [](u32, u32) {});
 }
-__global__ __launch_bounds__(256) void ks_audit_ff_new(const DevProb* probs, const AuditView* views, const AuditFitView* fviews) {
+// (probs is __restrict__: no store of this kernel reaches the problem descriptors, and said so their words stay in scalar registers across the atomics of the loop
+//  -- without it the walk holds some twenty more vector registers and the kernel drops from seven waves a SIMD to five)
+__global__ __launch_bounds__(256) void ks_audit_ff_new(const DevProb* __restrict__ probs, const AuditView* views, const AuditFitView* fviews) {
   const DevProb& P = probs[blockIdx.y]; const AuditView& V = views[blockIdx.y]; const AuditFitView& F = fviews[blockIdx.y];
-  const u32 lane = threadIdx.x & 63u, NN = aud_n_new(P, V), M = P.M, K = P.K, R = P.R, T = P.T, TW = P.TW, X = NN + M, n_used = F.cntr[1];
+  const u32 lane = threadIdx.x & 63u, NN = aud_n_new(P, V), M = P.M, X = NN + M, n_used = F.cntr[1];
   const size_t total = (size_t)n_used * X;
   for (size_t w = (size_t)blockIdx.x * 4u + (threadIdx.x >> 6); w < total; w += (size_t)gridDim.x * 4u) {      // (w, and everything read through it, is the same in all 64 lanes)
     const u32 u = (u32)(w / X), x = (u32)(w % X), c = F.list[u];
-    const bool fresh = x >= NN; const u32 j = x;
-    i32 m;
-    if (fresh) { m = (i32)(x - NN); if (GC(u32, P.tmpl_limit_present)[m] != 0xFFFFFFFFu) continue; }      // a limited template starts from an order-dependent subset (scheduler.go:199-208)
-    else { m = GC(i32, V.n_tmpl)[j]; if (m < 0 || (u32)m >= M) continue; }
-    // the node's final requirements, requests and options -- or a fresh node's: the template's, its daemon overhead, its types
-    const u32 np_ = fresh ? GC(u32, P.tmpl.present)[m] : GC(u32, V.o_present)[j], nc_ = fresh ? GC(u32, P.tmpl.complement)[m] : GC(u32, V.o_complement)[j];
-    const u64* nmask = fresh ? P.tmpl.mask + (size_t)m * K : V.o_mask + (size_t)j * K;
-    const i32* ngt = fresh ? P.tmpl.gt + (size_t)m * K : V.o_gt + (size_t)j * K; const i32* nlt = fresh ? P.tmpl.lt + (size_t)m * K : V.o_lt + (size_t)j * K;
-    const i64* nreq = fresh ? P.tmpl_daemon + (size_t)m * R : V.o_req + (size_t)j * R;
-    const u32 rmask = (fresh ? GC(u32, P.tmpl_daemon_present)[m] : GC(u32, V.o_reqmask)[j]) | GC(u32, P.cls_requests_present)[c];
-    const u64* ntypes = fresh ? P.tmpl_types + (size_t)m * TW : V.n_types + (size_t)j * TW;
-    const i32 sa = fresh ? GC(i32, P.tmpl.it_state)[m] : GC(i32, V.o_it)[j], sb = GC(i32, P.cls.it_state)[c];
-    const u32 cp = GC(u32, P.cls.present)[c], tmp = GC(u32, P.tmpl.present)[m];
-    // ---- the scalar clauses ----
-    bool ok = (GC(u64, P.tmpl_taints)[m] & ~GC(u64, P.cls_tolerated)[c]) == 0ull && GC(u8, P.cls_hn_mode)[c] != 1;      // (a new node's placeholder hostname is in no list, node.go:46)
-    for (u32 k = 0; k < K && ok; ++k) {
-      if (!((cp >> k) & 1u)) continue;
-      const KReq b = aud_fit_cls_req(P, c, k);
-      // "custom labels, if not defined, are denied" looks at the node AT THE TIME (requirements.go:125-130): a later pod may have added the key, the template had it all along
-      if (!((P.wellknown_mask >> k) & 1u) && !kreq_nidne(b) && !((tmp >> k) & 1u)) ok = false;
-      else if (aud_fit_meet_empty(load_req(np_, nc_, nmask, ngt, nlt, (int)k), b, P.value_int + k * 64, GC(u32, P.key_nvalues)[k])) ok = false;
-    }
-    u32 si = 0;
-    if (ok) {
-      if (sa < 0 || (u32)sa >= P.S) ok = false;
-      else if (!P.SC) si = (u32)sa;
-      else if (sb < 0 || (u32)sb >= P.SC || GC(u8, P.its_fail)[(size_t)sa * P.SC + sb]) ok = false;
-      else { si = GC(u16, P.its_inter)[(size_t)sa * P.SC + sb]; if (si >= P.S) ok = false; }
-    }
-    // ---- filterInstanceTypesByRequirements (node.go:137-159) against the final requirements with the class added and the requests with the class's: one type per lane ----
-    bool adm = false;
-    if (ok) {
-      const u32 mp = np_ | cp;
-      KReq rz = kreq_absent(), rc = kreq_absent();
-      if (P.key_zone >= 0) rz = kreq_add(load_req(np_, nc_, nmask, ngt, nlt, P.key_zone), aud_fit_cls_req(P, c, (u32)P.key_zone), P.value_int + P.key_zone * 64, GC(u32, P.key_nvalues)[P.key_zone]);
-      if (P.key_ct >= 0) rc = kreq_add(load_req(np_, nc_, nmask, ngt, nlt, P.key_ct), aud_fit_cls_req(P, c, (u32)P.key_ct), P.value_int + P.key_ct * 64, GC(u32, P.key_nvalues)[P.key_ct]);
-      const u64 pairs = aud_pairs(P, rz, rc);
-      for (u32 tw = 0; tw < TW; ++tw) {
-        const u32 t = tw * 64u + lane;
-        bool okl = t < T && ((GC(u64, ntypes)[tw] >> lane) & 1ull) && ((GC(u64, P.its_types)[(size_t)si * TW + tw] >> lane) & 1ull);
-        if (okl) {
-          const u32 tp = GC(u32, P.it_present)[t], tc = GC(u32, P.it_complement)[t];
-          for (u32 k = 0; k < K && okl; ++k) {
-            if (!((mp >> k) & 1u) || !((tp >> k) & 1u)) continue;
-            const KReq nr = kreq_add(load_req(np_, nc_, nmask, ngt, nlt, (int)k), aud_fit_cls_req(P, c, k), P.value_int + k * 64, GC(u32, P.key_nvalues)[k]);
-            KReq a; a.present = true; a.complement = (tc >> k) & 1u; a.mask = GC(u64, P.it_mask)[(size_t)k * T + t]; a.gt = KS_NOGT; a.lt = KS_NOLT;
-            if (kreq_intersects_fail(a, nr, P.value_int + k * 64, GC(u32, P.key_nvalues)[k])) okl = false;
-          }
-          for (u32 r = 0; r < R && okl; ++r) if (((rmask >> r) & 1u) && (i64)((u64)GC(i64, nreq)[r] + (u64)GC(i64, P.cls_requests)[(size_t)c * R + r]) > GC(i64, P.it_alloc)[(size_t)r * T + t]) okl = false;
-          if (okl) okl = (GC(u64, P.it_offer)[t] & pairs) != 0;
-        }
-        if (ballot64(okl)) { adm = true; break; }      // (the ballot is the same in all 64 lanes: they leave together)
-      }
+    const bool fresh = x >= NN;
+    bool adm;
+    if (fresh) {
+      if (GC(u32, P.tmpl_limit_present)[x - NN] != 0xFFFFFFFFu) continue;      // a limited template starts from an order-dependent subset (scheduler.go:199-208)
+      adm = aud_fit_admits_new(P, aud_node_fresh(P, x - NN), c, lane);
+    } else {
+      const AudNode n = aud_node_final(P, V, x);
+      if (n.m < 0 || (u32)n.m >= M) continue;      // a node of no template is the first pass's finding
+      adm = aud_fit_admits_new(P, n, c, lane);
     }
     if (lane == 0) {
       atomicAdd(&F.cntr[2], 1u);
       if (adm) {
         atomicAdd(&F.cntr[3], 1u);
-        if (fresh) atomicMin(&F.first_m[u], (u32)m);
-        else { const u32 o = F.open[j]; if (o != KS_AF_NEVER) atomicMin(&F.first_open[u], o); }
+        if (fresh) atomicMin(&F.first_m[u], x - NN);
+        else { const u32 o = F.open[x]; if (o != KS_AF_NEVER) atomicMin(&F.first_open[u], o); }
       }
     }
   }
 }
 __global__ __launch_bounds__(256) void ks_audit_ff_verdict(const DevProb* probs, const AuditView* views, const AuditFitView* fviews) {
-  const DevProb& P = probs[blockIdx.y]; const AuditView& V = views[blockIdx.y]; const AuditFitView& F = fviews[blockIdx.y];
-  const u32 np = P.P, E = P.E, NS = E + aud_n_new(P, V), n_placed = F.cntr[0];
-  if (blockIdx.x == 0 && threadIdx.x == 0) { F.meta[0] = aud_n_new(P, V); F.meta[1] = n_placed; F.meta[2] = F.cntr[1]; F.meta[3] = F.cntr[2]; F.meta[4] = F.cntr[3]; }
-  for (u32 p = blockIdx.x * 256u + threadIdx.x; p < np; p += gridDim.x * 256u) {
-    const i32 nd = aud_where(P, V, p, NS);
-    const bool ok = nd >= 0 && aud_seq_ok(V, F.seqcnt, p, n_placed), unsched = GC(i32, V.pod_node)[p] == -1;
-    u32 f = (nd >= 0 && !ok) ? KS_AUDIT_POD_SEQ : 0u, chk = nd >= 0 ? 1u << 30 : 0u;
-    const u32 c = aud_class(P, V, p);
-    const u32 u1 = F.used[c];      // (ks_audit_ff_mark marked the class of every examined pod: never 0 for one)
-    if (!(ok || unsched) || !aud_fit_examinable(P, c) || !u1) { F.flags[p] = f; F.chk[p] = chk | (1u << 29); continue; }
-    const u32 u = u1 - 1u;
-    const u32 fe = F.first_e[u], fo = F.first_open[u], fm = F.first_m[u];
-    if (unsched) {
-      if (fe != KS_AF_NEVER) f |= KS_AUDIT_POD_FIT_EXISTING;
-      if (fo != KS_AF_NEVER) f |= KS_AUDIT_POD_FIT_NEW;
-      if (fm != KS_AF_NEVER) f |= KS_AUDIT_POD_FIT_TEMPLATE;
-    } else if ((u32)nd < E) {
-      if (fe < (u32)nd) f |= KS_AUDIT_POD_FIT_EXISTING;
-    } else {
-      const u32 j = (u32)nd - E, sq = (u32)GC(i32, V.pod_seq)[p];
-      if (fe != KS_AF_NEVER) f |= KS_AUDIT_POD_FIT_EXISTING;
-      if (sq == F.open[j]) {      // the opener of its node; a pod that joined a new node later is checked against existing nodes only (the order among new nodes depends on pod counts at the time)
-        if (fo < sq) f |= KS_AUDIT_POD_FIT_NEW;      // (strictly: its own node opened at sq)
-        const i32 m = GC(i32, V.n_tmpl)[j];
-        if (m >= 0 && (u32)m < P.M && fm < (u32)m) f |= KS_AUDIT_POD_FIT_TEMPLATE;
-      }
-    }
-    F.flags[p] = f; F.chk[p] = chk | 1u;
-  }
+  const DevProb& P = probs[blockIdx.y];
+  aud_fit_verdict<KS_AUDIT_POD_FIT_EXISTING, KS_AUDIT_POD_FIT_NEW, KS_AUDIT_POD_FIT_TEMPLATE>(P, views[blockIdx.y], fviews[blockIdx.y], [&](u32 c) { return aud_fit_examinable(P, c); });
 }
 
 // ---- host half ----
 // One pooled block [meta | flags | checked words | scratch], one memset, the six launches, one read-back, the totals counted on the host.  The scratch of a problem is
-// 2P + 5C + 3E + 2ER + NMAX words: no slicing is needed.
+// audit_fit_words: no slicing is needed.  The sixth, seventh and ninth pass carve the same tables out of their own blocks.
+static size_t audit_fit_words(const DevProb& h) { return 2 * (size_t)h.E * h.R + h.E + h.P + 5 * (size_t)h.C + h.NMAX + 4; }
+// the scratch tables of `t` from s on (8-byte aligned: the int64 sums come first); returns the first word behind them
+static u32* audit_fit_carve(AuditFitView& t, const DevProb& h, u32* s) {
+  const size_t Cn = h.C;
+  t.esum = (u64*)s; s += 2 * (size_t)h.E * h.R; t.epres = s; s += h.E; t.seqcnt = s; s += h.P; t.used = s; s += Cn; t.list = s; s += Cn;
+  t.first_e = s; s += Cn; t.first_open = s; s += Cn; t.first_m = s; s += Cn; t.open = s; s += h.NMAX; t.cntr = s; s += 4;
+  return s;
+}
 static int audit_firstfit_run(ks_dev_problem* const* ds, u32 n, const AuditView* results, ks_audit_firstfit* const* outs, AuditGate* g) {
   BatchStage st; TRY(st.open(ds, n, nullptr, false));
   const size_t o_view = st.add<AuditView>(n), o_fview = st.add<AuditFitView>(n);
@@ -248,18 +248,17 @@ static int audit_firstfit_run(ks_dev_problem* const* ds, u32 n, const AuditView*
   for (u32 i = 0; i < n; ++i) { o_fl[i] = W.out(ds[i]->h.P); o_ck[i] = W.out(ds[i]->h.P); pmax = std::max(pmax, ds[i]->h.P); }
   for (u32 i = 0; i < n; ++i) {
     const DevProb& h = ds[i]->h;
-    o_scr[i] = W.scratch(2 * (size_t)h.E * h.R + h.E + h.P + 5 * (size_t)h.C + h.NMAX + 4, true);      // (the int64 sums come first: 8-byte aligned)
+    o_scr[i] = W.scratch(audit_fit_words(h), true);
     const size_t used = std::min<size_t>(h.C, h.P);      // (no more classes are used than there are pods)
     emax = std::max(emax, used * (((size_t)h.E + 255) / 256)); nmax = std::max(nmax, (used * ((size_t)h.NMAX + h.M) + 3) / 4);
   }
   TRY(W.alloc());
   u32* w = W.w();
   for (u32 i = 0; i < n; ++i) {
-    AuditView v = results[i]; AuditFitView t{}; const DevProb& h = ds[i]->h; const size_t Pn = h.P, Cn = h.C, En = h.E;
+    AuditFitView t{}; const DevProb& h = ds[i]->h;
     t.meta = w + 8 * (size_t)i; t.flags = w + o_fl[i]; t.chk = w + o_ck[i];
-    u32* s = w + o_scr[i]; t.esum = (u64*)s; s += 2 * En * h.R; t.epres = s; s += En; t.seqcnt = s; s += Pn; t.used = s; s += Cn; t.list = s; s += Cn;
-    t.first_e = s; s += Cn; t.first_open = s; s += Cn; t.first_m = s; s += Cn; t.open = s; s += h.NMAX; t.cntr = s;
-    v.meta = t.meta; v.mark = nullptr; v.pod_flags = nullptr; v.node_flags = nullptr; v.cnt = nullptr; v.off = nullptr; v.fill = nullptr; v.pods = nullptr;
+    audit_fit_carve(t, h, w + o_scr[i]);
+    const AuditView v = audit_pass_view(results[i], t.meta);
     st.h<AuditView>(o_view)[i] = v; st.h<AuditFitView>(o_fview)[i] = t;
   }
   AuditClock clock;

@@ -1,7 +1,7 @@
 // ks_audit_hostfit.inc -- the audit's sixth, opt-in pass: FIRST-FIT ORDER for the pods whose constraining groups are all HOSTNAME-keyed anti-affinity or unfiltered
 // hostname spread (ksolve.h ks_audit_hostfit_dev / ks_audit_hostfit_batch_dev, KS_AUDIT_POD_HFIT_*).  Included by ksolve.hip after ks_audit_limits.inc, outside the
 // emulator's guards: the tests/sim build compiles and runs these kernels too.  The five earlier passes' kernels, views and outputs are untouched; their helpers
-// (aud_where, aud_class, aud_n_new, aud_seq_ok, aud_fit_existing, aud_fit_cls_req, aud_fit_meet_empty, aud_topo_skipped, aud_topo_unfiltered) are called as they are,
+// (aud_where, aud_class, aud_n_new, aud_seq_ok, aud_fit_existing_pairs, aud_fit_admits_new, aud_fit_verdict, aud_topo_skipped, aud_topo_unfiltered) are called as they are,
 // and two of the fourth pass's kernels -- ks_audit_ff_count and ks_audit_ff_compact, which know nothing of which pods are examined -- are launched as they are, over
 // this pass's own AuditFitView.
 //
@@ -15,10 +15,10 @@
 //   ks_audit_ff_compact   the fourth pass's: used[] compacted into the class list.
 //   ks_audit_hf_fin       one lane per pod walking its class's sel_list / iown_list: integer atomicAdd into fin; one lane per (existing node, slot): init added in
 //                         (an unregistered hostname adds INT32_MIN: the entry stays negative whatever is counted on top, and a negative entry never admits).
-//   ks_audit_hf_existing  one lane per (used class, existing node): the group clauses -- a load per group -- then the fourth pass's aud_fit_existing.
+//   ks_audit_hf_existing  one lane per (used class, existing node): the fourth pass's body (aud_fit_existing_pairs) with the group clauses -- a load per group -- first.
 //   ks_audit_hf_new       one wave per (used class, 64 new nodes or templates): the group clauses a lane per pair -- most pairs end there --, then a wave per pair the
-//                         counts admit: the scalar clauses and the type walk, as ks_audit_ff_new has them.
-//   ks_audit_hf_verdict   one lane per pod: its flag word and its checked word, one writer each, a plain store.
+//                         counts admit: the fourth pass's aud_fit_admits_new.
+//   ks_audit_hf_verdict   one lane per pod: the fourth pass's aud_fit_verdict with this pass's bits and its own "examinable".
 // No float, no LDS beyond the scan tile, no dynamically indexed register array, no atomic on an output.
 #define KS_AH_UNREGISTERED 0x80000000u
 struct AuditHostView {
@@ -114,31 +114,18 @@ __global__ __launch_bounds__(256) void ks_audit_hf_fin(const DevProb* probs, con
   }
 }
 __global__ __launch_bounds__(256) void ks_audit_hf_existing(const DevProb* probs, const AuditFitView* fviews, const AuditHostView* hviews) {
-  const DevProb& P = probs[blockIdx.y]; const AuditFitView& F = fviews[blockIdx.y]; const AuditHostView& H = hviews[blockIdx.y];
-  const u32 lane = threadIdx.x & 63u, E = P.E, tiles = (E + 255u) / 256u, n_used = F.cntr[1], GE = H.hcntr[0];
-  const size_t total = (size_t)n_used * tiles;
-  for (size_t w = blockIdx.x; w < total; w += gridDim.x) {      // (w, u and c are the same in all 256 threads)
-    const u32 u = (u32)(w / tiles), e = (u32)(w % tiles) * 256u + threadIdx.x, c = F.list[u];
-    if (GC(u32, P.cls_vol_off)[c + 1] != GC(u32, P.cls_vol_off)[c]) continue;      // a class that mounts volumes is examined against new nodes only: they track none
-    bool exam = e < E && !(P.en_removed && ((GC(u64, P.en_removed)[e >> 6] >> (e & 63u)) & 1ull)), adm = false;
-    if (exam) exam = (GC(u32, P.cls.present)[c] & ~GC(u32, P.en.present)[e]) == 0u && !(GC(i32, P.cls.it_state)[c] != 0 && GC(i32, P.en.it_state)[e] == 0);
-    if (exam) adm = aud_hf_groups_ok(P, H, c, H.fin + (size_t)e * GE) && aud_fit_existing(P, F, c, e);      // the counts first: a load per group
-    u32 best = adm ? e : KS_AF_NEVER;
-    for (int x = 32; x > 0; x >>= 1) { const u32 o = __shfl_xor(best, x); best = o < best ? o : best; }
-    const u64 bx = ballot64(exam), ba = ballot64(adm);
-    if (lane == 0) {
-      if (best != KS_AF_NEVER) atomicMin(&F.first_e[u], best);
-      if (bx) { const u32 nx = (u32)__builtin_popcountll(bx); atomicAdd(&F.cntr[2], nx); atomicAdd(&H.hcntr[1], nx * aud_hf_n_groups(P, c)); }
-      if (ba) atomicAdd(&F.cntr[3], (u32)__builtin_popcountll(ba));
-    }
-  }
+  const DevProb& P = probs[blockIdx.y]; const AuditHostView& H = hviews[blockIdx.y];
+  const u32 GE = H.hcntr[0];
+  aud_fit_existing_pairs(P, fviews[blockIdx.y], [&](u32 c, u32 e) { return aud_hf_groups_ok(P, H, c, H.fin + (size_t)e * GE); },      // the counts first: a load per group
+                         [&](u32 c, u32 nx) { atomicAdd(&H.hcntr[1], nx * aud_hf_n_groups(P, c)); });
 }
-__global__ __launch_bounds__(256) void ks_audit_hf_new(const DevProb* probs, const AuditView* views, const AuditFitView* fviews, const AuditHostView* hviews) {
+// (probs is __restrict__ for the reason ks_audit_ff_new gives)
+__global__ __launch_bounds__(256) void ks_audit_hf_new(const DevProb* __restrict__ probs, const AuditView* views, const AuditFitView* fviews, const AuditHostView* hviews) {
   const DevProb& P = probs[blockIdx.y]; const AuditView& V = views[blockIdx.y]; const AuditFitView& F = fviews[blockIdx.y]; const AuditHostView& H = hviews[blockIdx.y];
-  const u32 lane = threadIdx.x & 63u, NN = aud_n_new(P, V), M = P.M, K = P.K, R = P.R, T = P.T, TW = P.TW, X = NN + M, tiles = (X + 63u) / 64u, n_used = F.cntr[1], GE = H.hcntr[0];
+  const u32 lane = threadIdx.x & 63u, NN = aud_n_new(P, V), M = P.M, X = NN + M, tiles = (X + 63u) / 64u, n_used = F.cntr[1], GE = H.hcntr[0];
   const size_t total = (size_t)n_used * tiles;
   for (size_t w = (size_t)blockIdx.x * 4u + (threadIdx.x >> 6); w < total; w += (size_t)gridDim.x * 4u) {      // (w, u, c and x0 are the same in all 64 lanes)
-    const u32 u = (u32)(w / tiles), x0 = (u32)(w % tiles) * 64u, c = F.list[u];
+    const u32 u = (u32)(w / tiles), x0 = (u32)(w % tiles) * 64u, c = UF(F.list[u]);      // (c is the same in all 64 lanes, and said so to the compiler: the class's rows are read through scalar registers)
     // ---- the group clauses, a lane per pair: most pairs end here (a node that holds a pod of the group), and a pair that ends here costs a few loads, not a wave ----
     const u32 xl = x0 + lane;
     bool valid = xl < X;
@@ -149,97 +136,24 @@ __global__ __launch_bounds__(256) void ks_audit_hf_new(const DevProb* probs, con
     const bool gok = valid && aud_hf_groups_ok(P, H, c, xl >= NN ? nullptr : H.fin + (size_t)(P.E + xl) * GE);      // (a fresh node of a template has every count 0)
     const u64 bv = ballot64(valid);
     if (lane == 0 && bv) { const u32 nx = (u32)__builtin_popcountll(bv); atomicAdd(&F.cntr[2], nx); atomicAdd(&H.hcntr[1], nx * aud_hf_n_groups(P, c)); }
-    // ---- the pairs the counts admit, a wave per pair as ks_audit_ff_new takes them ----
+    // ---- the pairs the counts admit, a wave per pair: the fourth pass's admits_new ----
     for (u64 todo = ballot64(gok); todo; todo &= todo - 1) {      // (the ballot is the same in all 64 lanes: x, and everything read through it, is too)
       const u32 x = x0 + (u32)__builtin_ctzll(todo);
-      const bool fresh = x >= NN; const u32 j = x;
-      const i32 m = fresh ? (i32)(x - NN) : GC(i32, V.n_tmpl)[j];
-      // the node's final requirements, requests and options -- or a fresh node's: the template's, its daemon overhead, its types
-      const u32 np_ = fresh ? GC(u32, P.tmpl.present)[m] : GC(u32, V.o_present)[j], nc_ = fresh ? GC(u32, P.tmpl.complement)[m] : GC(u32, V.o_complement)[j];
-      const u64* nmask = fresh ? P.tmpl.mask + (size_t)m * K : V.o_mask + (size_t)j * K;
-      const i32* ngt = fresh ? P.tmpl.gt + (size_t)m * K : V.o_gt + (size_t)j * K; const i32* nlt = fresh ? P.tmpl.lt + (size_t)m * K : V.o_lt + (size_t)j * K;
-      const i64* nreq = fresh ? P.tmpl_daemon + (size_t)m * R : V.o_req + (size_t)j * R;
-      const u32 rmask = (fresh ? GC(u32, P.tmpl_daemon_present)[m] : GC(u32, V.o_reqmask)[j]) | GC(u32, P.cls_requests_present)[c];
-      const u64* ntypes = fresh ? P.tmpl_types + (size_t)m * TW : V.n_types + (size_t)j * TW;
-      const i32 sa = fresh ? GC(i32, P.tmpl.it_state)[m] : GC(i32, V.o_it)[j], sb = GC(i32, P.cls.it_state)[c];
-      const u32 cp = GC(u32, P.cls.present)[c], tmp = GC(u32, P.tmpl.present)[m];
-      // ---- the scalar clauses ----
-      bool ok = (GC(u64, P.tmpl_taints)[m] & ~GC(u64, P.cls_tolerated)[c]) == 0ull && GC(u8, P.cls_hn_mode)[c] != 1;      // (a new node's placeholder hostname is in no list, node.go:46)
-      for (u32 k = 0; k < K && ok; ++k) {
-        if (!((cp >> k) & 1u)) continue;
-        const KReq b = aud_fit_cls_req(P, c, k);
-        if (!((P.wellknown_mask >> k) & 1u) && !kreq_nidne(b) && !((tmp >> k) & 1u)) ok = false;      // "custom labels, if not defined, are denied" at the time: the template's presence
-        else if (aud_fit_meet_empty(load_req(np_, nc_, nmask, ngt, nlt, (int)k), b, P.value_int + k * 64, GC(u32, P.key_nvalues)[k])) ok = false;
-      }
-      u32 si = 0;
-      if (ok) {
-        if (sa < 0 || (u32)sa >= P.S) ok = false;
-        else if (!P.SC) si = (u32)sa;
-        else if (sb < 0 || (u32)sb >= P.SC || GC(u8, P.its_fail)[(size_t)sa * P.SC + sb]) ok = false;
-        else { si = GC(u16, P.its_inter)[(size_t)sa * P.SC + sb]; if (si >= P.S) ok = false; }
-      }
-      if (!ok) continue;
-      // ---- filterInstanceTypesByRequirements (node.go:137-159), one type per lane, as ks_audit_ff_new walks it ----
-      bool adm = false;
-      const u32 mp = np_ | cp;
-      KReq rz = kreq_absent(), rc = kreq_absent();
-      if (P.key_zone >= 0) rz = kreq_add(load_req(np_, nc_, nmask, ngt, nlt, P.key_zone), aud_fit_cls_req(P, c, (u32)P.key_zone), P.value_int + P.key_zone * 64, GC(u32, P.key_nvalues)[P.key_zone]);
-      if (P.key_ct >= 0) rc = kreq_add(load_req(np_, nc_, nmask, ngt, nlt, P.key_ct), aud_fit_cls_req(P, c, (u32)P.key_ct), P.value_int + P.key_ct * 64, GC(u32, P.key_nvalues)[P.key_ct]);
-      const u64 pairs = aud_pairs(P, rz, rc);
-      for (u32 tw = 0; tw < TW; ++tw) {
-        const u32 t = tw * 64u + lane;
-        bool okl = t < T && ((GC(u64, ntypes)[tw] >> lane) & 1ull) && ((GC(u64, P.its_types)[(size_t)si * TW + tw] >> lane) & 1ull);
-        if (okl) {
-          const u32 tp = GC(u32, P.it_present)[t], tc = GC(u32, P.it_complement)[t];
-          for (u32 k = 0; k < K && okl; ++k) {
-            if (!((mp >> k) & 1u) || !((tp >> k) & 1u)) continue;
-            const KReq nr = kreq_add(load_req(np_, nc_, nmask, ngt, nlt, (int)k), aud_fit_cls_req(P, c, k), P.value_int + k * 64, GC(u32, P.key_nvalues)[k]);
-            KReq a; a.present = true; a.complement = (tc >> k) & 1u; a.mask = GC(u64, P.it_mask)[(size_t)k * T + t]; a.gt = KS_NOGT; a.lt = KS_NOLT;
-            if (kreq_intersects_fail(a, nr, P.value_int + k * 64, GC(u32, P.key_nvalues)[k])) okl = false;
-          }
-          for (u32 r = 0; r < R && okl; ++r) if (((rmask >> r) & 1u) && (i64)((u64)GC(i64, nreq)[r] + (u64)GC(i64, P.cls_requests)[(size_t)c * R + r]) > GC(i64, P.it_alloc)[(size_t)r * T + t]) okl = false;
-          if (okl) okl = (GC(u64, P.it_offer)[t] & pairs) != 0;
-        }
-        if (ballot64(okl)) { adm = true; break; }      // (the ballot is the same in all 64 lanes: they leave together)
-      }
+      const bool fresh = x >= NN;
+      const AudNode n = fresh ? aud_node_fresh(P, x - NN) : aud_node_final(P, V, x);
+      const bool adm = aud_fit_admits_new(P, n, c, lane);      // (every lane takes the walk's ballots)
       if (lane == 0 && adm) {
         atomicAdd(&F.cntr[3], 1u);
-        if (fresh) atomicMin(&F.first_m[u], (u32)m);
-        else { const u32 o = F.open[j]; if (o != KS_AF_NEVER) atomicMin(&F.first_open[u], o); }
+        if (fresh) atomicMin(&F.first_m[u], (u32)n.m);
+        else { const u32 o = F.open[x]; if (o != KS_AF_NEVER) atomicMin(&F.first_open[u], o); }
       }
     }
   }
 }
 __global__ __launch_bounds__(256) void ks_audit_hf_verdict(const DevProb* probs, const AuditView* views, const AuditFitView* fviews, const AuditHostView* hviews) {
-  const DevProb& P = probs[blockIdx.y]; const AuditView& V = views[blockIdx.y]; const AuditFitView& F = fviews[blockIdx.y]; const AuditHostView& H = hviews[blockIdx.y];
-  const u32 np = P.P, E = P.E, NS = E + aud_n_new(P, V), n_placed = F.cntr[0];
-  if (blockIdx.x == 0 && threadIdx.x == 0) { F.meta[0] = aud_n_new(P, V); F.meta[1] = n_placed; F.meta[2] = F.cntr[1]; F.meta[3] = F.cntr[2]; F.meta[4] = F.cntr[3]; F.meta[5] = H.hcntr[0]; F.meta[6] = H.hcntr[1]; }
-  for (u32 p = blockIdx.x * 256u + threadIdx.x; p < np; p += gridDim.x * 256u) {
-    const i32 nd = aud_where(P, V, p, NS);
-    const bool ok = nd >= 0 && aud_seq_ok(V, F.seqcnt, p, n_placed), unsched = GC(i32, V.pod_node)[p] == -1;
-    u32 f = (nd >= 0 && !ok) ? KS_AUDIT_POD_SEQ : 0u, chk = nd >= 0 ? 1u << 30 : 0u;
-    const u32 c = aud_class(P, V, p);
-    const u32 u1 = F.used[c];      // (ks_audit_hf_mark marked the class of every examined pod: never 0 for one)
-    if (!(ok || unsched) || !u1 || !aud_hf_examinable(P, H, c)) { F.flags[p] = f; F.chk[p] = chk | (1u << 29); continue; }
-    const u32 u = u1 - 1u;
-    const u32 fe = F.first_e[u], fo = F.first_open[u], fm = F.first_m[u];
-    if (unsched) {
-      if (fe != KS_AF_NEVER) f |= KS_AUDIT_POD_HFIT_EXISTING;
-      if (fo != KS_AF_NEVER) f |= KS_AUDIT_POD_HFIT_NEW;
-      if (fm != KS_AF_NEVER) f |= KS_AUDIT_POD_HFIT_TEMPLATE;
-    } else if ((u32)nd < E) {
-      if (fe < (u32)nd) f |= KS_AUDIT_POD_HFIT_EXISTING;
-    } else {
-      const u32 j = (u32)nd - E, sq = (u32)GC(i32, V.pod_seq)[p];
-      if (fe != KS_AF_NEVER) f |= KS_AUDIT_POD_HFIT_EXISTING;
-      if (sq == F.open[j]) {      // the opener of its node; a pod that joined a new node later is checked against existing nodes only
-        if (fo < sq) f |= KS_AUDIT_POD_HFIT_NEW;      // (strictly: its own node opened at sq)
-        const i32 m = GC(i32, V.n_tmpl)[j];
-        if (m >= 0 && (u32)m < P.M && fm < (u32)m) f |= KS_AUDIT_POD_HFIT_TEMPLATE;
-      }
-    }
-    F.flags[p] = f; F.chk[p] = chk | 1u;
-  }
+  const DevProb& P = probs[blockIdx.y]; const AuditFitView& F = fviews[blockIdx.y]; const AuditHostView& H = hviews[blockIdx.y];
+  if (blockIdx.x == 0 && threadIdx.x == 0) { F.meta[5] = H.hcntr[0]; F.meta[6] = H.hcntr[1]; }
+  aud_fit_verdict<KS_AUDIT_POD_HFIT_EXISTING, KS_AUDIT_POD_HFIT_NEW, KS_AUDIT_POD_HFIT_TEMPLATE>(P, views[blockIdx.y], F, [&](u32 c) { return aud_hf_examinable(P, H, c); });
 }
 
 // ---- host half ----
@@ -257,19 +171,18 @@ static int audit_hostfit_slice(ks_dev_problem* const* ds, u32 n, const AuditView
   for (u32 i = 0; i < n; ++i) { o_fl[i] = W.out(ds[i]->h.P); o_ck[i] = W.out(ds[i]->h.P); pmax = std::max(pmax, ds[i]->h.P); }
   for (u32 i = 0; i < n; ++i) {
     const DevProb& h = ds[i]->h;
-    o_scr[i] = W.scratch(2 * (size_t)h.E * h.R + h.E + h.P + 5 * (size_t)h.C + h.NMAX + 4 + 2 * (size_t)h.G + 2 + audit_hostfit_fin_words(ds[i]), true);      // (the int64 sums come first: 8-byte aligned)
+    o_scr[i] = W.scratch(audit_fit_words(h) + 2 * (size_t)h.G + 2 + audit_hostfit_fin_words(ds[i]), true);
     const size_t used = std::min<size_t>(h.C, h.P);      // (no more classes are used than there are pods)
     emax = std::max(emax, used * (((size_t)h.E + 255) / 256)); nmax = std::max(nmax, (used * (((size_t)h.NMAX + h.M + 63) / 64) + 3) / 4);
   }
   TRY(W.alloc());
   u32* w = W.w();
   for (u32 i = 0; i < n; ++i) {
-    AuditView v = results[i]; AuditFitView t{}; AuditHostView x{}; const DevProb& h = ds[i]->h; const size_t Pn = h.P, Cn = h.C, En = h.E;
+    AuditFitView t{}; AuditHostView x{}; const DevProb& h = ds[i]->h;
     t.meta = w + 8 * (size_t)i; t.flags = w + o_fl[i]; t.chk = w + o_ck[i];
-    u32* s = w + o_scr[i]; t.esum = (u64*)s; s += 2 * En * h.R; t.epres = s; s += En; t.seqcnt = s; s += Pn; t.used = s; s += Cn; t.list = s; s += Cn;
-    t.first_e = s; s += Cn; t.first_open = s; s += Cn; t.first_m = s; s += Cn; t.open = s; s += h.NMAX; t.cntr = s; s += 4;
+    u32* s = audit_fit_carve(t, h, w + o_scr[i]);
     x.slot = s; s += h.G; x.glist = s; s += h.G; x.hcntr = s; s += 2; x.fin = (i32*)s;
-    v.meta = t.meta; v.mark = nullptr; v.pod_flags = nullptr; v.node_flags = nullptr; v.cnt = nullptr; v.off = nullptr; v.fill = nullptr; v.pods = nullptr;
+    const AuditView v = audit_pass_view(results[i], t.meta);
     st.h<AuditView>(o_view)[i] = v; st.h<AuditFitView>(o_fview)[i] = t; st.h<AuditHostView>(o_hview)[i] = x;
   }
   AuditClock clock;

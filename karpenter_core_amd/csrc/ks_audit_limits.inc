@@ -1,7 +1,7 @@
 // ks_audit_limits.inc -- the audit's fifth, opt-in pass: PROVISIONER LIMITS in opening order (ksolve.h ks_audit_limits_dev / ks_audit_limits_batch_dev,
 // KS_AUDIT_NODE_LIMIT_*, KS_AUDIT_POD_LIMIT_TEMPLATE).  Included by ksolve.hip after ks_audit_firstfit.inc, outside the emulator's guards: the tests/sim build compiles
-// and runs these kernels too.  The four passes' kernels, views and outputs are untouched; their helpers (aud_where, aud_class, aud_n_new, aud_wave_*, aud_fit_*) are
-// called as they are, ks_algebra.h is as it was.
+// and runs these kernels too.  The four passes' kernels, views and outputs are untouched; their helpers (aud_where, aud_class, aud_n_new, aud_wave_*, aud_fit_*) and
+// ks_audit.inc's view of a node and its per-type predicate (AudNode, aud_node_state_meet, aud_node_type_ok) are called as they are, ks_algebra.h is as it was.
 //
 // Before it opens a machine of a limited provisioner scheduler.add keeps the types whose Capacity is within the remaining resources (scheduler.go:197-206,293-309);
 // after the opener's Add it takes the MaxResources of the node's options off them (scheduler.go:215,273-290).  A node's options only shrink, so per limited template,
@@ -21,7 +21,7 @@
 //   ks_audit_lim_lower    one workgroup per (problem, ordered limited template): the prefix sum of mw: L_m[0 .. n_m]; the first node whose mw differs from mc.
 //   ks_audit_lim_missing  one wave per new node of a limited template: MISSING (a type within L_j that passes the first pass's final-state filter and is not an
 //                         option); the node's flag word, one writer, a plain store.
-//   ks_audit_lim_pairs    one wave per (used class, ordered limited template): the scalar clauses of admits_template, then one type per lane: a binary search in
+//   ks_audit_lim_pairs    one wave per (used class, ordered limited template): the fourth pass's clauses (aud_fit_new_clauses), then one type per lane: a binary search in
 //                         L_m[] per limited resource for the last opening count the type is still within, and a wave maximum.
 //   ks_audit_lim_verdict  one lane per pod: its flag word and its checked word, one writer each, a plain store.
 // No float, no LDS beyond the reductions' and the scans' tiles, no dynamically indexed register array, no atomic on an output.
@@ -37,49 +37,8 @@ struct AuditLimView {
 __device__ __forceinline__ i64 aud_lim_sat_add(i64 a, i64 b) { return a > INT64_MAX - b ? INT64_MAX : a + b; }      // (both non-negative)
 __device__ __forceinline__ i64 aud_lim_sat_sub(i64 a, i64 b) { return a < INT64_MIN + b ? INT64_MIN : a - b; }      // (b non-negative)
 __device__ __forceinline__ i64 aud_lim_wave_max(i64 v) { for (int x = 32; x > 0; x >>= 1) { const i64 o = (i64)aud_xor64((u64)v, x); v = o > v ? o : v; } return v; }
-// the requirements, requests and type set a type is filtered against: a fresh node of template m with one pod of class c, or new node j as the result leaves it
-struct AudLimNode { u32 np_, nc_, rmask, c; const u64* nmask; const i32* ngt; const i32* nlt; const i64* nreq; u64 pairs; bool cls; };
-__device__ __forceinline__ KReq aud_lim_req(const DevProb& P, const AudLimNode& n, u32 k) {
-  const KReq a = load_req(n.np_, n.nc_, n.nmask, n.ngt, n.nlt, (int)k);
-  return n.cls ? kreq_add(a, aud_fit_cls_req(P, n.c, k), P.value_int + k * 64, GC(u32, P.key_nvalues)[k]) : a;
-}
-__device__ __forceinline__ void aud_lim_pairs_of(const DevProb& P, AudLimNode& n) {
-  KReq rz = kreq_absent(), rc = kreq_absent();
-  if (P.key_zone >= 0) rz = aud_lim_req(P, n, (u32)P.key_zone);
-  if (P.key_ct >= 0) rc = aud_lim_req(P, n, (u32)P.key_ct);
-  n.pairs = aud_pairs(P, rz, rc);
-}
-__device__ __forceinline__ AudLimNode aud_lim_fresh(const DevProb& P, u32 m, u32 c) {
-  AudLimNode n; const u32 K = P.K;
-  n.np_ = GC(u32, P.tmpl.present)[m]; n.nc_ = GC(u32, P.tmpl.complement)[m]; n.nmask = P.tmpl.mask + (size_t)m * K; n.ngt = P.tmpl.gt + (size_t)m * K; n.nlt = P.tmpl.lt + (size_t)m * K;
-  n.nreq = P.tmpl_daemon + (size_t)m * P.R; n.rmask = GC(u32, P.tmpl_daemon_present)[m] | GC(u32, P.cls_requests_present)[c]; n.c = c; n.cls = true;
-  aud_lim_pairs_of(P, n);
-  return n;
-}
-// the instance-type state of template m met with class c's, or S where the lattice has no meet
-__device__ __forceinline__ u32 aud_lim_fresh_state(const DevProb& P, u32 m, u32 c) {
-  const i32 sa = GC(i32, P.tmpl.it_state)[m], sb = GC(i32, P.cls.it_state)[c];
-  if (sa < 0 || (u32)sa >= P.S) return P.S;
-  if (!P.SC) return (u32)sa;
-  if (sb < 0 || (u32)sb >= P.SC || GC(u8, P.its_fail)[(size_t)sa * P.SC + sb]) return P.S;
-  const u32 si = GC(u16, P.its_inter)[(size_t)sa * P.SC + sb];
-  return si < P.S ? si : P.S;
-}
-// compatible && fits && hasOffering (node.go:137-159) for type t
-__device__ __forceinline__ bool aud_lim_type_ok(const DevProb& P, const AudLimNode& n, u32 t) {
-  const u32 K = P.K, R = P.R, T = P.T, tp = GC(u32, P.it_present)[t], tc = GC(u32, P.it_complement)[t], mp = n.cls ? (n.np_ | GC(u32, P.cls.present)[n.c]) : n.np_;
-  for (u32 k = 0; k < K; ++k) {
-    if (!((mp >> k) & 1u) || !((tp >> k) & 1u)) continue;
-    KReq a; a.present = true; a.complement = (tc >> k) & 1u; a.mask = GC(u64, P.it_mask)[(size_t)k * T + t]; a.gt = KS_NOGT; a.lt = KS_NOLT;
-    if (kreq_intersects_fail(a, aud_lim_req(P, n, k), P.value_int + k * 64, GC(u32, P.key_nvalues)[k])) return false;
-  }
-  for (u32 r = 0; r < R; ++r) {
-    if (!((n.rmask >> r) & 1u)) continue;
-    const i64 need = n.cls ? (i64)((u64)GC(i64, n.nreq)[r] + (u64)GC(i64, P.cls_requests)[(size_t)n.c * R + r]) : GC(i64, n.nreq)[r];
-    if (need > GC(i64, P.it_alloc)[(size_t)r * T + t]) return false;
-  }
-  return (GC(u64, P.it_offer)[t] & n.pairs) != 0;
-}
+// a fresh node of template m with one pod of class c on it (ks_audit.inc's view)
+__device__ __forceinline__ AudNode aud_lim_fresh(const DevProb& P, u32 m, u32 c) { AudNode n = aud_node_fresh(P, m); aud_node_add(P, n, c); return n; }
 // Capacity of type t within bound[r] on every limited resource; the bound's rows are global memory
 __device__ __forceinline__ bool aud_lim_within(const DevProb& P, u32 lim, u32 t, const i64* bound) {
   for (u32 bits = lim; bits; bits &= bits - 1) { const u32 r = (u32)__builtin_ctz(bits); if (r < P.R && GC(i64, P.it_cap)[(size_t)r * P.T + t] > bound[r]) return false; }
@@ -228,8 +187,8 @@ __global__ __launch_bounds__(256) void ks_audit_lim_upper(const DevProb* probs, 
     const u32 lim = GC(u32, P.tmpl_limit_present)[m]; const u64 o = F.open[j]; const bool ordered = o != KS_AL_NEVER64;
     const i64* U = ordered ? F.uv + (size_t)j * R : P.tmpl_remaining + (size_t)m * R;      // (an unordered node: nothing is known to have opened before it)
     const bool whole = ordered && F.tunord[m] == 0u;      // W_j feeds the lower bound, which an unordered node of the template voids
-    AudLimNode fn{}; u32 si = P.S;
-    if (whole) { const u32 c = aud_class(P, V, (u32)o); fn = aud_lim_fresh(P, (u32)m, c); si = aud_lim_fresh_state(P, (u32)m, c); }
+    AudNode fn{}; u32 si = P.S;
+    if (whole) { const u32 c = aud_class(P, V, (u32)o); fn = aud_lim_fresh(P, (u32)m, c); si = aud_node_state_meet(P, fn, c); }
     bool extra = false, binding = false;
     i64 mx[KS_MAX_RES];
 #pragma unroll
@@ -240,7 +199,7 @@ __global__ __launch_bounds__(256) void ks_audit_lim_upper(const DevProb* probs, 
       const bool over = in && !aud_lim_within(P, lim, t, U);
       if (have && over) extra = true;
       if (tm && over) binding = true;
-      if (whole && tm && !over && si < P.S && ((GC(u64, P.its_types)[(size_t)si * TW + tw] >> lane) & 1ull) && aud_lim_type_ok(P, fn, t)) {      // t is in W_j
+      if (whole && tm && !over && si < P.S && ((GC(u64, P.its_types)[(size_t)si * TW + tw] >> lane) & 1ull) && aud_node_type_ok(P, fn, t)) {      // t is in W_j
 #pragma unroll
         for (int r = 0; r < KS_MAX_RES; ++r) if ((u32)r < R) { const i64 cp = GC(i64, P.it_cap)[(size_t)r * T + t]; mx[r] = cp > mx[r] ? cp : mx[r]; }
       }
@@ -280,7 +239,7 @@ __global__ __launch_bounds__(256) void ks_audit_lim_lower(const DevProb* probs, 
 __global__ __launch_bounds__(256) void ks_audit_lim_missing(const DevProb* probs, const AuditView* views, const AuditLimView* lviews) {
   const DevProb& P = probs[blockIdx.y]; const AuditView& V = views[blockIdx.y]; const AuditLimView& F = lviews[blockIdx.y];
   if (!F.n_limited) return;
-  const u32 lane = threadIdx.x & 63u, E = P.E, NN = aud_n_new(P, V), R = P.R, K = P.K, T = P.T, TW = P.TW;
+  const u32 lane = threadIdx.x & 63u, E = P.E, NN = aud_n_new(P, V), R = P.R, T = P.T, TW = P.TW;
   for (u32 j = blockIdx.x * 4u + (threadIdx.x >> 6); j < NN; j += gridDim.x * 4u) {      // (wave-uniform)
     const i32 m = aud_lim_tmpl(P, V, j);
     if (m < 0) continue;
@@ -288,14 +247,13 @@ __global__ __launch_bounds__(256) void ks_audit_lim_missing(const DevProb* probs
     const i32 its = GC(i32, V.o_it)[j];
     if (F.open[j] != KS_AL_NEVER64 && F.tunord[m] == 0u && its >= 0 && (u32)its < P.S) {
       const i64* L = F.lv + ((size_t)F.tbase[m] + m + F.rank[j]) * R;
-      AudLimNode fn{}; fn.np_ = GC(u32, V.o_present)[j]; fn.nc_ = GC(u32, V.o_complement)[j]; fn.nmask = V.o_mask + (size_t)j * K; fn.ngt = V.o_gt + (size_t)j * K; fn.nlt = V.o_lt + (size_t)j * K;
-      fn.nreq = V.o_req + (size_t)j * R; fn.rmask = GC(u32, V.o_reqmask)[j]; fn.c = 0; fn.cls = false;
-      aud_lim_pairs_of(P, fn);
+      AudNode fn = aud_node_final(P, V, j);
+      aud_node_pairs(P, fn);
       bool missing = false;
       for (u32 tw = 0; tw < TW; ++tw) {
         const u32 t = tw * 64u + lane;
         if (t < T && ((GC(u64, P.tmpl_types)[(size_t)m * TW + tw] >> lane) & 1ull) && !((GC(u64, V.n_types)[(size_t)j * TW + tw] >> lane) & 1ull) &&
-            ((GC(u64, P.its_types)[(size_t)its * TW + tw] >> lane) & 1ull) && aud_lim_within(P, lim, t, L) && aud_lim_type_ok(P, fn, t)) missing = true;
+            ((GC(u64, P.its_types)[(size_t)its * TW + tw] >> lane) & 1ull) && aud_lim_within(P, lim, t, L) && aud_node_type_ok(P, fn, t)) missing = true;
       }
       if (ballot64(missing)) f |= KS_AUDIT_NODE_LIMIT_MISSING;
     }
@@ -305,28 +263,21 @@ __global__ __launch_bounds__(256) void ks_audit_lim_missing(const DevProb* probs
 __global__ __launch_bounds__(256) void ks_audit_lim_pairs(const DevProb* probs, const AuditLimView* lviews) {
   const DevProb& P = probs[blockIdx.y]; const AuditLimView& F = lviews[blockIdx.y];
   if (!F.n_limited) return;
-  const u32 lane = threadIdx.x & 63u, M = P.M, K = P.K, R = P.R, T = P.T, TW = P.TW, n_used = F.cntr[1];
+  const u32 lane = threadIdx.x & 63u, M = P.M, R = P.R, T = P.T, TW = P.TW, n_used = F.cntr[1];
   const size_t total = (size_t)n_used * M;
   for (size_t w = (size_t)blockIdx.x * 4u + (threadIdx.x >> 6); w < total; w += (size_t)gridDim.x * 4u) {      // (w, and everything read through it, is the same in all 64 lanes)
     const u32 u = (u32)(w / M), m = (u32)(w % M), c = F.list[u], lim = GC(u32, P.tmpl_limit_present)[m];
     if (lim == 0xFFFFFFFFu || F.tunord[m]) continue;
     const u32 n_m = F.tcnt[m]; const i64* L = F.lv + ((size_t)F.tbase[m] + m) * R;
-    // ---- admits_template's scalar clauses (the fourth pass's) ----
-    const u32 cp = GC(u32, P.cls.present)[c], tmp = GC(u32, P.tmpl.present)[m];
-    bool ok = (GC(u64, P.tmpl_taints)[m] & ~GC(u64, P.cls_tolerated)[c]) == 0ull && GC(u8, P.cls_hn_mode)[c] != 1;
-    for (u32 k = 0; k < K && ok; ++k) {
-      if (!((cp >> k) & 1u)) continue;
-      const KReq b = aud_fit_cls_req(P, c, k);
-      if (!((P.wellknown_mask >> k) & 1u) && !kreq_nidne(b) && !((tmp >> k) & 1u)) ok = false;
-      else if (aud_fit_meet_empty(load_req(tmp, GC(u32, P.tmpl.complement)[m], P.tmpl.mask + (size_t)m * K, P.tmpl.gt + (size_t)m * K, P.tmpl.lt + (size_t)m * K, (int)k), b, P.value_int + k * 64, GC(u32, P.key_nvalues)[k])) ok = false;
-    }
-    const u32 si = ok ? aud_lim_fresh_state(P, m, c) : P.S;
+    // ---- admits_template: the fourth pass's clauses and state meet, then a walk of this kernel's own ----
+    AudNode fn = aud_node_fresh(P, m);
+    const u32 si = aud_fit_new_clauses(P, fn, c) ? aud_node_state_meet(P, fn, c) : P.S;
     i32 best = -1;
     if (si < P.S) {
-      const AudLimNode fn = aud_lim_fresh(P, m, c);
+      aud_node_add(P, fn, c);
       for (u32 tw = 0; tw < TW; ++tw) {
         const u32 t = tw * 64u + lane;
-        if (!(t < T && ((GC(u64, P.tmpl_types)[(size_t)m * TW + tw] >> lane) & 1ull) && ((GC(u64, P.its_types)[(size_t)si * TW + tw] >> lane) & 1ull) && aud_lim_type_ok(P, fn, t))) continue;
+        if (!(t < T && ((GC(u64, P.tmpl_types)[(size_t)m * TW + tw] >> lane) & 1ull) && ((GC(u64, P.its_types)[(size_t)si * TW + tw] >> lane) & 1ull) && aud_node_type_ok(P, fn, t))) continue;
         i32 kt = (i32)n_m;      // the last opening count at which t is within L_m[k] on every limited resource (L_m falls with k)
         for (u32 bits = lim; bits && kt >= 0; bits &= bits - 1) {
           const u32 r = (u32)__builtin_ctz(bits); if (r >= R) break;
@@ -393,7 +344,7 @@ static int audit_limits_run(ks_dev_problem* const* ds, u32 n, const AuditView* r
   TRY(W.alloc());
   u32* w = W.w();
   for (u32 i = 0; i < n; ++i) {
-    AuditView v = results[i]; AuditLimView t{}; const DevProb& h = ds[i]->h; const size_t Pn = h.P, Cn = h.C, NM = h.NMAX, R = h.R, Mn = h.M;
+    AuditLimView t{}; const DevProb& h = ds[i]->h; const size_t Pn = h.P, Cn = h.C, NM = h.NMAX, R = h.R, Mn = h.M;
     t.meta = w + 8 * (size_t)i; t.pflags = w + o_fl[i]; t.pchk = w + o_ck[i]; t.nflags = w + o_nf[i]; t.n_limited = ds[i]->n_limited;
     u32* s = w + o_scr[i];
     if (!t.n_limited) { t.seqcnt = s; s += Pn; t.cntr = s; }
@@ -402,8 +353,7 @@ static int audit_limits_run(ks_dev_problem* const* ds, u32 n, const AuditView* r
       t.seqcnt = s; s += Pn; t.seqnode = s; s += Pn; t.used = s; s += Cn; t.list = s; s += Cn; t.rank = s; s += NM; t.ord = s; s += NM; t.nx = s; s += NM;
       t.tcnt = s; s += Mn; t.tunord = s; s += Mn; t.tbase = s; s += Mn; t.kadm = s; s += std::min<size_t>(Cn, Pn) * Mn; t.cntr = s;
     }
-    v.meta = t.meta; v.mark = nullptr; v.pod_flags = nullptr; v.node_flags = nullptr; v.cnt = nullptr; v.off = nullptr; v.fill = nullptr; v.pods = nullptr;
-    st.h<AuditView>(o_view)[i] = v; st.h<AuditLimView>(o_lview)[i] = t;
+    st.h<AuditView>(o_view)[i] = audit_pass_view(results[i], t.meta); st.h<AuditLimView>(o_lview)[i] = t;
   }
   AuditClock clock;
   TRY(st.upload(st.bytes));

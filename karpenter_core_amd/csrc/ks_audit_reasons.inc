@@ -1,7 +1,8 @@
 // ks_audit_reasons.inc -- the audit's eighth, opt-in pass: FAILURE REASONS (ksolve.h ks_audit_reasons_dev / ks_audit_reasons_batch_dev, KS_AUDIT_POD_REASON_*).
 // Included by ksolve.hip after ks_audit_stages.inc, outside the emulator's guards: the tests/sim build compiles and runs these kernels too.  The seven earlier passes'
-// kernels, views and outputs are untouched; their helpers (aud_where, aud_n_new, aud_n_stages, aud_fit_examinable, aud_fit_cls_req, aud_pairs, aud_block_sum) are
-// called as they are, and the fourth pass's ks_audit_ff_compact is launched as it is over this pass's own AuditFitView (its `used`, `list` and `cntr`).
+// kernels, views and outputs are untouched; their helpers (aud_where, aud_n_new, aud_n_stages, aud_fit_examinable, aud_fit_cls_req, aud_block_sum; AudNode with its
+// state meet and its walk) are called as they are, and the fourth pass's ks_audit_ff_compact is launched as it is over this pass's own AuditFitView (its `used`,
+// `list` and `cntr`).
 //
 // pod_reason carries, per unscheduled pod, the KS_WHY_* step at which the last scheduler.add refused the pod on a FRESH node of every template (four bits each, the
 // first eight templates).  A fresh node of a template is static data and Node.Add runs its steps in a fixed order (node.go:62-107), so the step is decided by the
@@ -12,9 +13,9 @@
 //                         (every class, not only the examinable ones: steps 1 and 2 are decided for all); the unscheduled pods counted (a block sum, one atomicAdd
 //                         into a scratch counter).
 //   ks_audit_ff_compact   the fourth pass's: used[] compacted into the class list; cntr[1] = the used classes.
-//   ks_audit_rs_static    one wave per (used class, template m < min(M, 8)): the scalar clauses are wave-uniform; then one instance type per lane, word by word --
-//                         it_mask[k*T+t] coalesced over t, Fits over R, the offering test against the zone x capacity-type mask -- and a ballot ends the walk at the
-//                         first word a type passes in.  Lane 0 stores s into nib[u * 8 + m], a plain store.  With no unscheduled pod the list is empty: no trip.
+//   ks_audit_rs_static    one wave per (used class, template m < min(M, 8)): this pass's own scalar part -- the EXACT Compatible, answers that are reasons -- is
+//                         wave-uniform; then ks_audit.inc's state meet and walk over the types (aud_node_state_meet, aud_node_any_type), one instance type per lane.
+//                         Lane 0 stores s into nib[u * 8 + m], a plain store.  With no unscheduled pod the list is empty: no trip.
 //   ks_audit_rs_verdict   one lane per pod: the eight nibbles against nib[] by list index; one plain store each for the flag word and the checked word.
 // Integer only: no float, no scratch, no dynamically indexed register array, no atomic on an output.
 #define KS_AR_S_UNDECIDED 8u      // s(c, m): the class is not examinable -- topology speaks next (one of KS_WHY_TOPOLOGY, _TOPOLOGY_REQS, _NO_INSTANCE_TYPE)
@@ -56,55 +57,27 @@ __global__ __launch_bounds__(256) void ks_audit_rs_mark(const DevProb* probs, co
 }
 // s(c, m): what a fresh node of template m answers class c, in Node.Add's order.  Everything read here is the same in all 64 lanes up to the walk over the types.
 __device__ __forceinline__ u32 aud_reason_static(const DevProb& P, u32 c, u32 m, u32 lane) {
-  const u32 K = P.K, R = P.R, T = P.T, TW = P.TW;
+  const u32 K = P.K, TW = P.TW;
   const u64* ntypes = P.tmpl_types + (size_t)m * TW;
   bool listed = false;
   for (u32 tw = 0; tw < TW; ++tw) if (GC(u64, ntypes)[tw]) listed = true;
   if (!listed) return KS_AR_S_NO_TYPES;
   if (GC(u64, P.tmpl_taints)[m] & ~GC(u64, P.cls_tolerated)[c]) return (u32)KS_WHY_TAINTS;      // Taints.Tolerates, node.go:64
   // (HostPortUsage.Validate, node.go:69: a fresh node has no port in use)
-  const u32 np_ = GC(u32, P.tmpl.present)[m], nc_ = GC(u32, P.tmpl.complement)[m], cp = GC(u32, P.cls.present)[c];
-  const u64* nmask = P.tmpl.mask + (size_t)m * K; const i32* ngt = P.tmpl.gt + (size_t)m * K; const i32* nlt = P.tmpl.lt + (size_t)m * K;
+  AudNode n = aud_node_fresh(P, m);
+  const u32 cp = GC(u32, P.cls.present)[c];
   bool ok = GC(u8, P.cls_hn_mode)[c] != 1;      // (a new node's placeholder hostname is in no list, node.go:46)
   for (u32 k = 0; k < K && ok; ++k) {      // nodeRequirements.Compatible(podRequirements), node.go:77: exact -- nothing here depends on a moment
     if (!((cp >> k) & 1u)) continue;
-    if (kreq_compatible_fail(load_req(np_, nc_, nmask, ngt, nlt, (int)k), aud_fit_cls_req(P, c, k), (P.wellknown_mask >> k) & 1u, P.value_int + k * 64, GC(u32, P.key_nvalues)[k])) ok = false;
+    if (kreq_compatible_fail(aud_node_req(P, n, k), aud_fit_cls_req(P, c, k), (P.wellknown_mask >> k) & 1u, P.value_int + k * 64, GC(u32, P.key_nvalues)[k])) ok = false;
   }
-  const i32 sa = GC(i32, P.tmpl.it_state)[m], sb = GC(i32, P.cls.it_state)[c];
-  u32 si = 0;
-  if (ok) {
-    if (sa < 0 || (u32)sa >= P.S) ok = false;
-    else if (!P.SC) si = (u32)sa;
-    else if (sb < 0 || (u32)sb >= P.SC || GC(u8, P.its_fail)[(size_t)sa * P.SC + sb]) ok = false;
-    else si = GC(u16, P.its_inter)[(size_t)sa * P.SC + sb];
-  }
-  if (!ok) return (u32)KS_WHY_REQUIREMENTS;
+  if (!ok || aud_node_state_refuses(P, n, c)) return (u32)KS_WHY_REQUIREMENTS;
   if (!aud_fit_examinable(P, c)) return KS_AR_S_UNDECIDED;      // Topology.AddRequirements speaks next (node.go:83-87)
+  const u32 si = aud_node_state_meet(P, n, c);
   if (si >= P.S) return (u32)KS_WHY_NO_INSTANCE_TYPE;            // (the lattice's meet names no state: no type)
   // ---- filterInstanceTypesByRequirements (node.go:137-159) over the template's FULL type set, the merged requirements, daemon overhead + the class's requests ----
-  const i64* nreq = P.tmpl_daemon + (size_t)m * R;
-  const u32 rmask = GC(u32, P.tmpl_daemon_present)[m] | GC(u32, P.cls_requests_present)[c], mp = np_ | cp;
-  KReq rz = kreq_absent(), rc = kreq_absent();
-  if (P.key_zone >= 0) rz = kreq_add(load_req(np_, nc_, nmask, ngt, nlt, P.key_zone), aud_fit_cls_req(P, c, (u32)P.key_zone), P.value_int + P.key_zone * 64, GC(u32, P.key_nvalues)[P.key_zone]);
-  if (P.key_ct >= 0) rc = kreq_add(load_req(np_, nc_, nmask, ngt, nlt, P.key_ct), aud_fit_cls_req(P, c, (u32)P.key_ct), P.value_int + P.key_ct * 64, GC(u32, P.key_nvalues)[P.key_ct]);
-  const u64 pairs = aud_pairs(P, rz, rc);
-  for (u32 tw = 0; tw < TW; ++tw) {
-    const u32 t = tw * 64u + lane;
-    bool okl = t < T && ((GC(u64, ntypes)[tw] >> lane) & 1ull) && ((GC(u64, P.its_types)[(size_t)si * TW + tw] >> lane) & 1ull);
-    if (okl) {
-      const u32 tp = GC(u32, P.it_present)[t], tc = GC(u32, P.it_complement)[t];
-      for (u32 k = 0; k < K && okl; ++k) {
-        if (!((mp >> k) & 1u) || !((tp >> k) & 1u)) continue;
-        const KReq nr = kreq_add(load_req(np_, nc_, nmask, ngt, nlt, (int)k), aud_fit_cls_req(P, c, k), P.value_int + k * 64, GC(u32, P.key_nvalues)[k]);
-        KReq a; a.present = true; a.complement = (tc >> k) & 1u; a.mask = GC(u64, P.it_mask)[(size_t)k * T + t]; a.gt = KS_NOGT; a.lt = KS_NOLT;
-        if (kreq_intersects_fail(a, nr, P.value_int + k * 64, GC(u32, P.key_nvalues)[k])) okl = false;
-      }
-      for (u32 r = 0; r < R && okl; ++r) if (((rmask >> r) & 1u) && (i64)((u64)GC(i64, nreq)[r] + (u64)GC(i64, P.cls_requests)[(size_t)c * R + r]) > GC(i64, P.it_alloc)[(size_t)r * T + t]) okl = false;
-      if (okl) okl = (GC(u64, P.it_offer)[t] & pairs) != 0;
-    }
-    if (ballot64(okl)) return (u32)KS_WHY_NONE;      // (the ballot is the same in all 64 lanes: they leave together)
-  }
-  return (u32)KS_WHY_NO_INSTANCE_TYPE;
+  aud_node_add(P, n, c);
+  return aud_node_any_type(P, n, si, lane) ? (u32)KS_WHY_NONE : (u32)KS_WHY_NO_INSTANCE_TYPE;
 }
 __global__ __launch_bounds__(256) void ks_audit_rs_static(const DevProb* probs, const AuditFitView* fviews, const AuditReasonView* rviews) {
   const DevProb& P = probs[blockIdx.y]; const AuditFitView& F = fviews[blockIdx.y]; const AuditReasonView& Q = rviews[blockIdx.y];
@@ -169,12 +142,11 @@ static int audit_reasons_run_on(ks_dev_problem* const* ds, u32 n, const AuditVie
   TRY(W.alloc());
   u32* w = W.w();
   for (u32 i = 0; i < n; ++i) {
-    AuditView v = results[i]; AuditFitView t{}; AuditReasonView q{}; const DevProb& h = ds[i]->h; const size_t Cn = h.C;
+    AuditFitView t{}; AuditReasonView q{}; const DevProb& h = ds[i]->h; const size_t Cn = h.C;
     t.meta = w + 8 * (size_t)i; t.flags = w + o_fl[i]; t.chk = w + o_ck[i];
     u32* s = w + o_scr[i]; t.used = s; s += Cn; t.list = s; s += Cn; q.nib = s; s += 8 * Cn; t.cntr = s;
     q.pod_reason = reasons ? reasons[i] : ds[i]->hs.pod_reason;
-    v.meta = t.meta; v.mark = nullptr; v.pod_flags = nullptr; v.node_flags = nullptr; v.cnt = nullptr; v.off = nullptr; v.fill = nullptr; v.pods = nullptr;
-    st.h<AuditView>(o_view)[i] = v; st.h<AuditFitView>(o_fview)[i] = t; st.h<AuditReasonView>(o_rview)[i] = q;
+    st.h<AuditView>(o_view)[i] = audit_pass_view(results[i], t.meta); st.h<AuditFitView>(o_fview)[i] = t; st.h<AuditReasonView>(o_rview)[i] = q;
   }
   AuditClock clock;
   TRY(st.upload(st.bytes));

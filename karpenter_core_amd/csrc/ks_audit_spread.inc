@@ -223,11 +223,10 @@ static int audit_spread_slice(ks_dev_problem* const* ds, u32 n, const AuditView*
   TRY(W.alloc());
   u32* w = W.w();
   for (u32 i = 0; i < n; ++i) {
-    AuditView v = results[i]; AuditSpreadView t{}; const DevProb& h = ds[i]->h; const size_t Pn = h.P, npin = ((size_t)h.E + h.NMAX) * h.K;
+    AuditSpreadView t{}; const DevProb& h = ds[i]->h; const size_t Pn = h.P, npin = ((size_t)h.E + h.NMAX) * h.K;
     t.meta = w + 4 * (size_t)i; t.flags = w + o_fl[i]; t.chk = w + o_ck[i];
     u32* s = w + o_scr[i]; t.seqcnt = s; t.ord = s + Pn; t.pin = s + 2 * Pn; t.elig = s + 2 * Pn + npin; t.cntr = s + 2 * Pn + npin + h.G; t.tab = s + 2 * Pn + npin + h.G + 1;
-    v.meta = t.meta; v.mark = nullptr; v.pod_flags = nullptr; v.node_flags = nullptr; v.cnt = nullptr; v.off = nullptr; v.fill = nullptr; v.pods = nullptr;
-    st.h<AuditView>(o_view)[i] = v; st.h<AuditSpreadView>(o_sview)[i] = t;
+    st.h<AuditView>(o_view)[i] = audit_pass_view(results[i], t.meta); st.h<AuditSpreadView>(o_sview)[i] = t;
   }
   AuditClock clock;
   TRY(st.upload(st.bytes));

@@ -84,18 +84,17 @@ static int audit_stages_run(ks_dev_problem* const* ds, u32 n, const AuditView* r
   for (u32 i = 0; i < n; ++i) { o_fl[i] = W.out(ds[i]->h.P); o_ck[i] = W.out(ds[i]->h.P); pmax = std::max(pmax, ds[i]->h.P); }
   for (u32 i = 0; i < n; ++i) {
     const DevProb& h = ds[i]->h;
-    o_scr[i] = W.scratch(2 * (size_t)h.E * h.R + h.E + h.P + 5 * (size_t)h.C + h.NMAX + 4 + 2, true);      // (the int64 sums come first: 8-byte aligned)
+    o_scr[i] = W.scratch(audit_fit_words(h) + 2, true);
     const size_t used = h.C;      // (a pod marks up to 63 classes: the classes bound the list)
     emax = std::max(emax, used * (((size_t)h.E + 255) / 256)); nmax = std::max(nmax, (used * (size_t)h.M + 3) / 4);
   }
   TRY(W.alloc());
   u32* w = W.w();
   for (u32 i = 0; i < n; ++i) {
-    AuditView v = results[i]; AuditFitView t{}; const DevProb& h = ds[i]->h; const size_t Pn = h.P, Cn = h.C, En = h.E;
+    AuditFitView t{}; const DevProb& h = ds[i]->h;
     t.meta = w + 8 * (size_t)i; t.flags = w + o_fl[i]; t.chk = w + o_ck[i];
-    u32* s = w + o_scr[i]; t.esum = (u64*)s; s += 2 * En * h.R; t.epres = s; s += En; t.seqcnt = s; s += Pn; t.used = s; s += Cn; t.list = s; s += Cn;
-    t.first_e = s; s += Cn; t.first_open = s; s += Cn; t.first_m = s; s += Cn; t.open = s; s += h.NMAX; t.cntr = s; s += 4;
-    v.meta = t.meta; v.mark = nullptr; v.pod_flags = nullptr; v.node_flags = nullptr; v.cnt = nullptr; v.off = nullptr; v.fill = nullptr; v.pods = nullptr;
+    const u32* s = audit_fit_carve(t, h, w + o_scr[i]);
+    const AuditView v = audit_pass_view(results[i], t.meta);
     AuditView tv = v; tv.counts = s;      // (two words the memset zeroed: no new node, no unscheduled list)
     st.h<AuditView>(o_view)[i] = v; st.h<AuditView>(o_tview)[i] = tv; st.h<AuditFitView>(o_fview)[i] = t;
   }

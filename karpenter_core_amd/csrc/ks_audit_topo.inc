@@ -225,10 +225,10 @@ static int audit_topo_slice(ks_dev_problem* const* ds, u32 n, const AuditView* r
   TRY(W.alloc());
   u32* w = W.w();
   for (u32 i = 0; i < n; ++i) {
-    AuditView v = results[i]; AuditTopoView t{}; const size_t Pn = ds[i]->h.P, NS = (size_t)ds[i]->h.E + ds[i]->h.NMAX;
+    AuditTopoView t{}; const size_t Pn = ds[i]->h.P, NS = (size_t)ds[i]->h.E + ds[i]->h.NMAX;
     t.meta = w + 4 * (size_t)i; t.flags = w + o_fl[i]; t.chk = w + o_ck[i];
+    AuditView v = audit_pass_view(results[i], t.meta);      // (its node -> pods CSR is this pass's own: set below)
     u32* s = w + o_scr[i]; t.seqcnt = s; v.pods = s + Pn; v.cnt = s + 2 * Pn; v.off = s + 2 * Pn + NS; v.fill = s + 2 * Pn + 2 * NS + 1; t.first = s + 2 * Pn + 3 * NS + 1;
-    v.meta = t.meta; v.mark = nullptr; v.pod_flags = nullptr; v.node_flags = nullptr;
     st.h<AuditView>(o_view)[i] = v; st.h<AuditTopoView>(o_tview)[i] = t;
   }
   AuditClock clock;

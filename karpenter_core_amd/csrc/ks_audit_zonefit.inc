@@ -3,7 +3,7 @@
 // ks_audit_reasons.inc, outside the emulator's guards: the tests/sim build compiles and runs these kernels too.  The earlier passes' kernels, views and outputs are
 // untouched.  Four of the third pass's kernels (ks_audit_spread_count / _order / _chunks / _scan: elig, ord, pin and the scanned chunk table) and two of the fourth's
 // (ks_audit_ff_count / ks_audit_ff_mark: the existing nodes' request sums and presence masks, open[]) are launched as they are, over this pass's own views of them, and
-// their helpers (aud_where, aud_class, aud_n_new, aud_seq_ok, aud_spr_record, aud_spr_certain, aud_topo_dom, aud_fit_existing, aud_fit_cls_req, aud_fit_meet_empty) are
+// their helpers (aud_where, aud_class, aud_n_new, aud_seq_ok, aud_spr_record, aud_spr_certain, aud_topo_dom, aud_fit_existing, aud_fit_mounts / _live / _labelled, aud_fit_admits_new) are
 // called as they are.
 //
 // A zonal group's minimum moves over time, so the final counts alone decide nothing; the final state TOGETHER WITH the commit numbers does.  Pod P was tried for the
@@ -25,7 +25,7 @@
 //   ks_audit_zf_existing    one lane per (examined pod, existing node): the bit test of the node's label value against the pod's masks first -- a lane ends the pairs the
 //                           zone refuses, not a wave --, then the fourth pass's aud_fit_existing; a wave minimum, then atomicMin into the pod's scratch word.
 //   ks_audit_zf_new         one lane per (opener or unscheduled pod, new node): open(j) < s, the key already one value at s - 1, the value in the mask; then a wave per
-//                           surviving pair: the scalar clauses and the type walk, as ks_audit_ff_new has them.
+//                           surviving pair: the fourth pass's aud_fit_admits_new.
 //   ks_audit_zf_verdict     one lane per pod: its flag word and its checked word, one writer each, a plain store.
 // No float, no LDS beyond the reused kernels' and the count of the eligible groups, no dynamically indexed register array, no atomic on an output; the lists are
 // appended by integer atomicAdd into scratch and only minima and sums are taken over them: the same flags and counters every run.
@@ -207,8 +207,8 @@ __global__ __launch_bounds__(256) void ks_audit_zf_existing(const DevProb* probs
   const size_t total = (size_t)n_exam * tiles;
   for (size_t w = (size_t)blockIdx.x * 4u + (threadIdx.x >> 6); w < total; w += (size_t)gridDim.x * 4u) {      // (w, p and c are the same in all 64 lanes)
     const u32 p = Z.xlist[w / tiles], e = (u32)(w % tiles) * 64u + lane, c = aud_class(P, V, p);
-    if (GC(u32, P.cls_vol_off)[c + 1] != GC(u32, P.cls_vol_off)[c]) continue;      // a class that mounts volumes is examined against new nodes only: they track none
-    const bool live = e < E && !(P.en_removed && ((GC(u64, P.en_removed)[e >> 6] >> (e & 63u)) & 1ull));
+    if (aud_fit_mounts(P, c)) continue;
+    const bool live = aud_fit_live(P, e);
     // ---- the zone test, a lane per pair: the node carries the label of key(g) with the single value z, and z is in the pod's mask
     bool zok = live;
     if (zok) {
@@ -219,8 +219,7 @@ __global__ __launch_bounds__(256) void ks_audit_zf_existing(const DevProb* probs
       }
     }
     // ---- the fourth pass's predicate, under its condition on labelled keys
-    bool adm = zok && (GC(u32, P.cls.present)[c] & ~GC(u32, P.en.present)[e]) == 0u && !(GC(i32, P.cls.it_state)[c] != 0 && GC(i32, P.en.it_state)[e] == 0);
-    if (adm) adm = aud_fit_existing(P, F, c, e);
+    const bool adm = zok && aud_fit_labelled(P, c, e) && aud_fit_existing(P, F, c, e);
     u32 best = adm ? e : KS_AF_NEVER;
     for (int x = 32; x > 0; x >>= 1) { const u32 o = __shfl_xor(best, x); best = o < best ? o : best; }
     const u64 bl = ballot64(live), bz = ballot64(zok), ba = ballot64(adm);
@@ -232,12 +231,13 @@ __global__ __launch_bounds__(256) void ks_audit_zf_existing(const DevProb* probs
     }
   }
 }
-__global__ __launch_bounds__(256) void ks_audit_zf_new(const DevProb* probs, const AuditView* views, const AuditFitView* fviews, const AuditSpreadView* sviews, const AuditZoneView* zviews) {
+// (probs is __restrict__ for the reason ks_audit_ff_new gives)
+__global__ __launch_bounds__(256) void ks_audit_zf_new(const DevProb* __restrict__ probs, const AuditView* views, const AuditFitView* fviews, const AuditSpreadView* sviews, const AuditZoneView* zviews) {
   const DevProb& P = probs[blockIdx.y]; const AuditView& V = views[blockIdx.y]; const AuditFitView& F = fviews[blockIdx.y]; const AuditSpreadView& S = sviews[blockIdx.y]; const AuditZoneView& Z = zviews[blockIdx.y];
-  const u32 lane = threadIdx.x & 63u, E = P.E, NN = aud_n_new(P, V), M = P.M, K = P.K, R = P.R, T = P.T, TW = P.TW, tiles = (NN + 63u) / 64u, nn = Z.zcntr[1], n_placed = F.cntr[0];
+  const u32 lane = threadIdx.x & 63u, E = P.E, NN = aud_n_new(P, V), M = P.M, tiles = (NN + 63u) / 64u, nn = Z.zcntr[1], n_placed = F.cntr[0];
   const size_t total = (size_t)nn * tiles;
   for (size_t w = (size_t)blockIdx.x * 4u + (threadIdx.x >> 6); w < total; w += (size_t)gridDim.x * 4u) {      // (w, p, c and s are the same in all 64 lanes)
-    const u32 p = Z.nlist[w / tiles], j0 = (u32)(w % tiles) * 64u, c = aud_class(P, V, p);
+    const u32 p = Z.nlist[w / tiles], j0 = (u32)(w % tiles) * 64u, c = UF(aud_class(P, V, p));      // (c is the same in all 64 lanes, and said so to the compiler: the class's rows are read through scalar registers)
     const u32 s = GC(i32, V.pod_node)[p] == -1 ? n_placed : (u32)GC(i32, V.pod_seq)[p];      // (an opener does not fail SEQ: its commit number is below n_placed)
     if (s == 0u) continue;      // nothing had committed: no new node existed
     // ---- the lane-level filter: the node existed at s, its requirement on every key(g) was one value before s, and its final value is in the pod's mask
@@ -255,55 +255,10 @@ __global__ __launch_bounds__(256) void ks_audit_zf_new(const DevProb* probs, con
     }
     const u64 bl = ballot64(live), bz = ballot64(zok);
     if (lane == 0) { if (bl) atomicAdd(&Z.zcntr[2], (u32)__builtin_popcountll(bl)); if (bz) atomicAdd(&Z.zcntr[3], (u32)__builtin_popcountll(bz)); }
-    // ---- the pairs the zone admits, a wave per pair: admits_new(c, j) as ks_audit_ff_new evaluates it for a node of the result
+    // ---- the pairs the zone admits, a wave per pair: the fourth pass's admits_new for a node of the result
     for (u64 todo = bz; todo; todo &= todo - 1) {      // (the ballot is the same in all 64 lanes: j, and everything read through it, is too)
       const u32 j = j0 + (u32)__builtin_ctzll(todo);
-      const i32 m = GC(i32, V.n_tmpl)[j];
-      const u32 np_ = GC(u32, V.o_present)[j], nc_ = GC(u32, V.o_complement)[j];
-      const u64* nmask = V.o_mask + (size_t)j * K; const i32* ngt = V.o_gt + (size_t)j * K; const i32* nlt = V.o_lt + (size_t)j * K; const i64* nreq = V.o_req + (size_t)j * R;
-      const u32 rmask = GC(u32, V.o_reqmask)[j] | GC(u32, P.cls_requests_present)[c];
-      const u64* ntypes = V.n_types + (size_t)j * TW;
-      const i32 sa = GC(i32, V.o_it)[j], sb = GC(i32, P.cls.it_state)[c];
-      const u32 cp = GC(u32, P.cls.present)[c], tmp = GC(u32, P.tmpl.present)[m];
-      // ---- the scalar clauses ----
-      bool ok = (GC(u64, P.tmpl_taints)[m] & ~GC(u64, P.cls_tolerated)[c]) == 0ull && GC(u8, P.cls_hn_mode)[c] != 1;      // (a new node's placeholder hostname is in no list, node.go:46)
-      for (u32 k = 0; k < K && ok; ++k) {
-        if (!((cp >> k) & 1u)) continue;
-        const KReq b = aud_fit_cls_req(P, c, k);
-        if (!((P.wellknown_mask >> k) & 1u) && !kreq_nidne(b) && !((tmp >> k) & 1u)) ok = false;      // "custom labels, if not defined, are denied" at the time: the template's presence
-        else if (aud_fit_meet_empty(load_req(np_, nc_, nmask, ngt, nlt, (int)k), b, P.value_int + k * 64, GC(u32, P.key_nvalues)[k])) ok = false;
-      }
-      u32 si = 0;
-      if (ok) {
-        if (sa < 0 || (u32)sa >= P.S) ok = false;
-        else if (!P.SC) si = (u32)sa;
-        else if (sb < 0 || (u32)sb >= P.SC || GC(u8, P.its_fail)[(size_t)sa * P.SC + sb]) ok = false;
-        else { si = GC(u16, P.its_inter)[(size_t)sa * P.SC + sb]; if (si >= P.S) ok = false; }
-      }
-      if (!ok) continue;
-      // ---- filterInstanceTypesByRequirements (node.go:137-159), one type per lane, as ks_audit_ff_new walks it ----
-      bool adm = false;
-      const u32 mp = np_ | cp;
-      KReq rz = kreq_absent(), rc = kreq_absent();
-      if (P.key_zone >= 0) rz = kreq_add(load_req(np_, nc_, nmask, ngt, nlt, P.key_zone), aud_fit_cls_req(P, c, (u32)P.key_zone), P.value_int + P.key_zone * 64, GC(u32, P.key_nvalues)[P.key_zone]);
-      if (P.key_ct >= 0) rc = kreq_add(load_req(np_, nc_, nmask, ngt, nlt, P.key_ct), aud_fit_cls_req(P, c, (u32)P.key_ct), P.value_int + P.key_ct * 64, GC(u32, P.key_nvalues)[P.key_ct]);
-      const u64 pairs = aud_pairs(P, rz, rc);
-      for (u32 tw = 0; tw < TW; ++tw) {
-        const u32 t = tw * 64u + lane;
-        bool okl = t < T && ((GC(u64, ntypes)[tw] >> lane) & 1ull) && ((GC(u64, P.its_types)[(size_t)si * TW + tw] >> lane) & 1ull);
-        if (okl) {
-          const u32 tp = GC(u32, P.it_present)[t], tc = GC(u32, P.it_complement)[t];
-          for (u32 k = 0; k < K && okl; ++k) {
-            if (!((mp >> k) & 1u) || !((tp >> k) & 1u)) continue;
-            const KReq nr = kreq_add(load_req(np_, nc_, nmask, ngt, nlt, (int)k), aud_fit_cls_req(P, c, k), P.value_int + k * 64, GC(u32, P.key_nvalues)[k]);
-            KReq a; a.present = true; a.complement = (tc >> k) & 1u; a.mask = GC(u64, P.it_mask)[(size_t)k * T + t]; a.gt = KS_NOGT; a.lt = KS_NOLT;
-            if (kreq_intersects_fail(a, nr, P.value_int + k * 64, GC(u32, P.key_nvalues)[k])) okl = false;
-          }
-          for (u32 r = 0; r < R && okl; ++r) if (((rmask >> r) & 1u) && (i64)((u64)GC(i64, nreq)[r] + (u64)GC(i64, P.cls_requests)[(size_t)c * R + r]) > GC(i64, P.it_alloc)[(size_t)r * T + t]) okl = false;
-          if (okl) okl = (GC(u64, P.it_offer)[t] & pairs) != 0;
-        }
-        if (ballot64(okl)) { adm = true; break; }      // (the ballot is the same in all 64 lanes: they leave together)
-      }
+      const bool adm = aud_fit_admits_new(P, aud_node_final(P, V, j), c, lane);      // (every lane takes the walk's ballots)
       if (lane == 0 && adm) { atomicAdd(&Z.zcntr[4], 1u); atomicMin(&Z.first_open[p], F.open[j]); }
     }
   }
@@ -338,9 +293,8 @@ static int audit_zonefit_slice(ks_dev_problem* const* ds, u32 n, const AuditView
   for (u32 i = 0; i < n; ++i) { o_fl[i] = W.out(ds[i]->h.P); o_ck[i] = W.out(ds[i]->h.P); pmax = std::max(pmax, ds[i]->h.P); }
   for (u32 i = 0; i < n; ++i) {
     const DevProb& h = ds[i]->h; const size_t Pn = h.P;
-    // the int64 tables first (8-byte aligned): the request sums, the masks | the fourth pass's words | the third pass's | this pass's
-    o_scr[i] = W.scratch(2 * (size_t)h.E * h.R + 2 * KS_AZ_GROUPS * Pn + (h.E + Pn + 2 * (size_t)h.C + h.NMAX + 4) + (4 * Pn + ((size_t)h.E + h.NMAX) * h.K + h.G + 1 + 4 + audit_spread_tab_words(ds[i])) +
-                             (5 * Pn + 8 + (size_t)h.G * KS_AS_ROW), true);
+    // the int64 tables first (8-byte aligned): the masks, then the fourth pass's tables with the request sums at their head | the third pass's | this pass's
+    o_scr[i] = W.scratch(2 * KS_AZ_GROUPS * Pn + audit_fit_words(h) + (4 * Pn + ((size_t)h.E + h.NMAX) * h.K + h.G + 1 + 4 + audit_spread_tab_words(ds[i])) + (5 * Pn + 8 + (size_t)h.G * KS_AS_ROW), true);
     wmax = std::max(wmax, (size_t)h.G * KS_AS_ROW); gmax = std::max(gmax, h.G);
     emax = std::max(emax, (Pn * (((size_t)h.E + 63) / 64) + 3) / 4); nmax = std::max(nmax, (Pn * (((size_t)h.NMAX + 63) / 64) + 3) / 4);
   }
@@ -348,17 +302,14 @@ static int audit_zonefit_slice(ks_dev_problem* const* ds, u32 n, const AuditView
   TRY(W.alloc());
   u32* w = W.w();
   for (u32 i = 0; i < n; ++i) {
-    AuditView v = results[i]; AuditFitView t{}; AuditSpreadView x{}; AuditZoneView z{}; const DevProb& h = ds[i]->h; const size_t Pn = h.P, Cn = h.C, En = h.E, npin = ((size_t)h.E + h.NMAX) * h.K;
+    AuditFitView t{}; AuditSpreadView x{}; AuditZoneView z{}; const DevProb& h = ds[i]->h; const size_t Pn = h.P, npin = ((size_t)h.E + h.NMAX) * h.K;
     t.meta = w + 8 * (size_t)i; t.flags = w + o_fl[i]; t.chk = w + o_ck[i];
-    u32* s = w + o_scr[i]; t.esum = (u64*)s; s += 2 * En * h.R; z.okmask = (u64*)s; s += 2 * KS_AZ_GROUPS * Pn;
-    t.epres = s; s += En; t.seqcnt = s; s += Pn; t.used = s; s += Cn; t.list = nullptr;
-    t.first_e = t.first_open = t.first_m = s; s += Cn;      // (ks_audit_ff_count sets the three per-class tables to "never" and nothing here reads them: one table serves)
-    t.open = s; s += h.NMAX; t.cntr = s; s += 4;
+    u32* s = w + o_scr[i]; z.okmask = (u64*)s; s += 2 * KS_AZ_GROUPS * Pn;      // (an even number of words: the request sums behind it stay 8-byte aligned)
+    s = audit_fit_carve(t, h, s);      // (of the fourth pass's tables ks_audit_ff_count sets the three per-class ones to "never" and ks_audit_ff_mark marks used[]; nothing here reads those four, and list[] is neither written nor read: this pass keeps its minima per pod)
     x.seqcnt = s; s += Pn; x.ord = s; s += Pn; x.flags = s; s += Pn; x.chk = s; s += Pn;      // (the third pass's flag and checked words: scratch here)
     x.pin = s; s += npin; x.elig = s; s += h.G; x.cntr = s; s += 1; x.meta = s; s += 4; x.tab = s; s += audit_spread_tab_words(ds[i]);
     z.zst = s; s += Pn; z.first_e = s; s += Pn; z.first_open = s; s += Pn; z.xlist = s; s += Pn; z.nlist = s; s += Pn; z.zcntr = s; s += 8; z.ztot = s;
-    v.meta = t.meta; v.mark = nullptr; v.pod_flags = nullptr; v.node_flags = nullptr; v.cnt = nullptr; v.off = nullptr; v.fill = nullptr; v.pods = nullptr;
-    st.h<AuditView>(o_view)[i] = v; st.h<AuditFitView>(o_fview)[i] = t; st.h<AuditSpreadView>(o_sview)[i] = x; st.h<AuditZoneView>(o_zview)[i] = z;
+    st.h<AuditView>(o_view)[i] = audit_pass_view(results[i], t.meta); st.h<AuditFitView>(o_fview)[i] = t; st.h<AuditSpreadView>(o_sview)[i] = x; st.h<AuditZoneView>(o_zview)[i] = z;
   }
   AuditClock clock;
   TRY(st.upload(st.bytes));

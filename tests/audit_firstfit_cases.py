@@ -296,3 +296,204 @@ def _tiny():
          "node_gt": np.full((4, K), A.NOGT, dtype=np.int32), "node_lt": np.full((4, K), A.NOLT, dtype=np.int32), "node_types": np.array([3, 3, 3, 3], dtype=np.uint64),
          "node_requests_present": np.ones(4, dtype=np.uint32), "node_it_state": np.zeros(4, dtype=np.int32)}
     return p, r, np.arange(Pn, dtype=np.int32)
+
+
+# ---------------------------------------------------------------------------------------------------------------- the clauses of admits_new / admits_template, through the kernels
+# Pairs of claimed results of one small solved problem each: the two of a pair differ in the one clause under test; in the first the reference raises no FIT_NEW /
+# FIT_TEMPLATE bit on the target pod, in the second exactly that bit.  tests/audit_hostfit_cases.py and tests/audit_zonefit_cases.py run pairs of their own through
+# `run_clause_pairs` with their pass's compare.
+from karpenter_core_amd.model import Expr, Taint, Toleration      # noqa: E402
+
+SIX_CORES = {LABEL_INSTANCE_TYPE: BIG_TYPE}      # the one type the clause problems' nodes end with: a walk over the types that admits, admits through it
+
+
+def clause_problem(pods, provs=None, nodes=()) -> Problem:
+    its = fake.instance_types(6)
+    return Problem(instance_types=its, provisioners=provs or [fake.provisioner("open", len(its))], pods=list(pods), nodes=list(nodes), extra_well_known=fake.EXTRA_WELL_KNOWN)
+
+
+def six_core_pod(uid, cpu, selector=None, **kw):
+    return TC._pod(uid, cpu=cpu, mem="1Gi", node_selector=dict(selector or {}, **SIX_CORES), **kw)
+
+
+def class_of(prob, r, p):
+    return int(prob["stage_cls"][int(prob["pod_stage_off"][p]) + int(r["pod_stage"][p])])
+
+
+def new_node_of(prob, r, p):
+    j = int(r["pod_node"][p]) - prob["E"]
+    assert 0 <= j < int(r["n_new"]), (p, r["pod_node"])
+    return j
+
+
+def custom_key(prob, c):
+    """the one key class c names that is no well-known label"""
+    bits = int(prob["cls.present"][c]) & ~int(prob["wellknown_mask"])
+    assert bits and not bits & (bits - 1), bits
+    return bits.bit_length() - 1
+
+
+def copy_key(r, prob, k, src, dst):
+    """new node dst's final requirement on key k becomes new node src's"""
+    K = prob["K"]
+    for name in ("node_present", "node_complement"):
+        a = np.asarray(r[name]).copy()
+        a[dst] = (int(a[dst]) & ~(1 << k)) | (int(a[src]) & (1 << k))
+        r[name] = a
+    for name in ("node_mask", "node_gt", "node_lt"):
+        a = np.asarray(r[name]).reshape(-1, K).copy()
+        a[dst, k] = a[src, k]
+        r[name] = a.reshape(-1)
+
+
+def opened_in_order(r, s, prob, first, target):
+    """`first` and `target` opened a new node each, `first` its own the earlier: the nodes"""
+    j0, j1 = new_node_of(prob, r, first), new_node_of(prob, r, target)
+    on = lambda j: [int(s[p]) for p in range(prob["P"]) if int(r["pod_node"][p]) == prob["E"] + j]
+    assert j0 != j1 and min(on(j0)) == int(s[first]) < int(s[target]) == min(on(j1)), (r["pod_node"], s)
+    return j0, j1
+
+
+def boundary_requests(r, prob, j, c, past):
+    """new node j ends with ONE type; its requests on the one resource that kept a pod of class c out are set so that need == that type's allocatable (+ `past`)"""
+    R, T = prob["R"], prob["T"]
+    words = np.asarray(r["node_types"], dtype=np.uint64).reshape(int(r["n_new"]), -1)[j]
+    bits = [w * 64 + b for w in range(len(words)) for b in range(64) if (int(words[w]) >> b) & 1]
+    assert len(bits) == 1, bits
+    req = np.asarray(r["node_requests"], dtype=np.int64).reshape(-1, R).copy()
+    mine = prob["cls_requests"][c * R:(c + 1) * R].astype(np.int64)
+    alloc = np.array([int(prob["it_alloc"][x * T + bits[0]]) for x in range(R)], dtype=np.int64)
+    over = [x for x in range(R) if req[j][x] + mine[x] > alloc[x]]
+    assert len(over) == 1 and (int(r["node_requests_present"][j]) >> over[0]) & 1, (over, req[j], mine, alloc)
+    req[j][over[0]] = alloc[over[0]] - mine[over[0]] + past
+    r["node_requests"] = req.reshape(-1)
+
+
+def _custom_key_pair():
+    """`first` opens a machine of `open`; `teamed` names the custom label team=a, which only the second provisioner defines, and opens a machine of that one.  Claimed:
+    the first machine ended with `teamed`'s requirement on the key (a later pod added it) -- and, in the second of the pair, is of the template that has the key."""
+    its = fake.instance_types(6)
+    provs = [fake.provisioner("open", len(its), weight=10), fake.provisioner("teamed", len(its), weight=1, labels={"team": "a"})]
+    make = lambda: clause_problem([six_core_pod("first", "2500m"), six_core_pod("teamed", "2400m", {"team": "a"})], provs)
+
+    def edit(r, s, prob, admit):
+        j0, j1 = opened_in_order(r, s, prob, 0, 1)
+        assert int(r["node_tmpl"][j0]) == 0 and int(r["node_tmpl"][j1]) == 1, r["node_tmpl"]
+        k = custom_key(prob, class_of(prob, r, 1))
+        assert not (int(prob["tmpl.present"][0]) >> k) & 1 and (int(prob["tmpl.present"][1]) >> k) & 1
+        copy_key(r, prob, k, j1, j0)
+        assert (int(r["node_present"][j0]) >> k) & 1
+        if admit:
+            r["node_tmpl"][j0] = 1
+        return 1
+    return make, edit, "FIT_NEW"
+
+
+def _does_not_exist_pair():
+    """Two pods fill a machine; `without`, which asks for team DoesNotExist, opens the next.  Claimed: the first machine has room for it and ended with team DoesNotExist
+    itself -- and, in the second of the pair, without the key."""
+    make = lambda: clause_problem([six_core_pod("first", "2500m"), six_core_pod("second", "2500m"),
+                                   six_core_pod("without", "2400m", required_affinity=[[Expr("team", "DoesNotExist")]])])
+
+    def edit(r, s, prob, admit):
+        j0, j1 = opened_in_order(r, s, prob, 0, 2)
+        assert new_node_of(prob, r, 1) == j0
+        R, c = prob["R"], class_of(prob, r, 2)
+        req = np.asarray(r["node_requests"], dtype=np.int64).reshape(-1, R).copy()
+        req[j0] -= prob["cls_requests"][class_of(prob, r, 1) * R:(class_of(prob, r, 1) + 1) * R].astype(np.int64)
+        r["node_requests"] = req.reshape(-1)
+        k = custom_key(prob, c)
+        copy_key(r, prob, k, j1, j0)
+        K = prob["K"]
+        assert (int(r["node_present"][j0]) >> k) & 1 and not (int(r["node_complement"][j0]) >> k) & 1 and int(np.asarray(r["node_mask"]).reshape(-1, K)[j0, k]) == 0      # DoesNotExist
+        if admit:
+            a = np.asarray(r["node_present"]).copy()
+            a[j0] = int(a[j0]) & ~(1 << k)
+            r["node_present"] = a
+        return 2
+    return make, edit, "FIT_NEW"
+
+
+def fits_pair(bit="FIT_NEW", filler=None, **late):
+    """Two pods fill a machine of the six-core type; `late` opens the next.  Claimed: the first machine's requests are such that with `late` on top the need is one
+    milli-unit past the type's allocatable -- and, in the second of the pair, equal to it.  filler, late: what the other passes' pods carry."""
+    filler = filler or {}
+    make = lambda: clause_problem([six_core_pod("first", "2500m", filler), six_core_pod("second", "2500m", filler), TC._pod("late", cpu="2400m", mem="1Gi", **late)])
+
+    def edit(r, s, prob, admit):
+        j0, j1 = opened_in_order(r, s, prob, 0, 2)
+        assert new_node_of(prob, r, 1) == j0
+        boundary_requests(r, prob, j0, class_of(prob, r, 2), 0 if admit else 1)
+        return 2
+    return make, edit, bit
+
+
+def taint_pair(bit="FIT_TEMPLATE", tolerant=None, intolerant=None):
+    """The first provisioner taints its machines.  `tolerant` opens a machine of it, `intolerant` one of the second.  Claimed: the target's machine is of the second
+    template -- `intolerant` is the target of the first of the pair (a fresh machine of the first template refuses it), `tolerant` of the second.  The pair differs in the
+    target pod's toleration, the one thing the clause reads besides the problem's own taints, which no claimed array carries: `intolerant`'s machine is of the second
+    template already, so the refusing claimed result is the genuine one and only the admitting one is an edit -- weaker than the other pairs, where both are edits, and
+    still enough to catch a dropped or inverted taint clause (the kernels would flag `intolerant` where the reference does not, or miss `tolerant`)."""
+    its = fake.instance_types(6)
+    provs = [fake.provisioner("tainted", len(its), weight=10, taints=[Taint("dedicated", "x")]), fake.provisioner("open", len(its), weight=1)]
+    make = lambda: clause_problem([six_core_pod("tolerant", "3500m", tolerations=[Toleration(key="dedicated", operator="Exists")], **(tolerant or {})),
+                                   six_core_pod("intolerant", "3400m", **(intolerant or {}))], provs)
+
+    def edit(r, s, prob, admit):
+        j0, j1 = new_node_of(prob, r, 0), new_node_of(prob, r, 1)
+        assert j0 != j1 and int(r["node_tmpl"][j0]) == 0 and int(r["node_tmpl"][j1]) == 1 and int(prob["tmpl_taints"][0]) and not int(prob["tmpl_taints"][1]), (r["node_tmpl"], prob["tmpl_taints"])
+        target = 0 if admit else 1
+        r["node_tmpl"][new_node_of(prob, r, target)] = 1
+        return target
+    return make, edit, bit
+
+
+FITS_NAMES = ("Fits: one milli-unit past the allocatable of the only remaining type", "Fits: need == allocatable of the only remaining type")
+TAINT_NAMES = ("a template taint the class does not tolerate", "a template taint the class tolerates")
+CLAUSE_PAIRS = [("a later pod added a custom key the template lacks", "the same node on a template that has the key", _custom_key_pair),
+                ("node final DoesNotExist against class DoesNotExist", "the same node without the key", _does_not_exist_pair),
+                FITS_NAMES + (lambda: fits_pair(node_selector=SIX_CORES),), TAINT_NAMES + (taint_pair,)]
+
+
+def clause_names(pairs):
+    return [n + (": admitted" if i else ": not admitted") for refused, admitted, _ in pairs for i, n in enumerate((refused, admitted))]
+
+
+CLAUSE_NAMES = clause_names(CLAUSE_PAIRS)
+
+
+def run_clause_pairs(S, pairs, compare, assert_clean, problem_arrays, bits, fit_new_or_template):
+    """[(name, True or what differs)], two per pair: the problem solved (at most 8 pods, 3 templates, 6 types, 2 existing nodes) and its genuine result clean; then
+    each of the pair's two claimed results audited by the device pass and the reference through `compare` -- bit for bit, counters included -- and the target pod's
+    word: none of `fit_new_or_template` where the clause refuses, the pair's bit and nothing else where it admits."""
+    report = []
+    for (refused, admitted, pair), names in zip(pairs, zip(*[iter(clause_names(pairs))] * 2)):
+        make, edit, bit = pair()
+        flat = S.FlatProblem(make())
+        try:
+            flat.solve(decode=False)
+            assert flat.dims["P"] <= 8 and flat.dims["M"] <= 3 and flat.dims["T"] <= 6 and flat.dims["E"] <= 2, flat.dims
+            assert_clean(S, flat)
+            prob = problem_arrays(S, flat)
+            for admit, name in zip((False, True), names):
+                try:
+                    r, s = _claimable(flat.result_arrays()), np.array(flat.pod_seq(), dtype=np.int32)
+                    target = edit(r, s, prob, admit)
+                    got = compare(S, flat, r, s)[1]
+                    word = int(got[target])
+                    if admit:
+                        ok = True if word == bits[bit] else "pod %d carries %d, expected %s alone: %s" % (target, word, bit, flagged(got))
+                    else:
+                        ok = True if not word & fit_new_or_template else "pod %d carries %d, expected neither new-node bit: %s" % (target, word, flagged(got))
+                except AssertionError as e:
+                    ok = "%s" % (e,)
+                report.append((name, ok))
+        except AssertionError as e:
+            report.extend((name, "%s" % (e,)) for name in names)
+        flat.close()
+    assert [x[0] for x in report] == clause_names(pairs)
+    return report
+
+
+def run_clauses(S):
+    return run_clause_pairs(S, CLAUSE_PAIRS, compare, assert_clean, FR.problem_arrays, B, B["FIT_NEW"] | B["FIT_TEMPLATE"])

@@ -9,6 +9,7 @@ import numpy as np
 import audit_cases as C
 import audit_harness as H
 from audit_harness import _claimable, flagged
+import audit_firstfit_cases as FC
 import audit_hostfit_ref as HR
 import audit_topo_cases as TC
 from karpenter_core_amd import fake
@@ -467,3 +468,19 @@ def run_shapes(S):
     shape("two templates", tamper_problem, lambda flat, dev: True if flat.dims["M"] == 2 and dev["checked"]["PAIRS"] == 3 * (4 + 2 + 2) else str(dev))
     assert [r[0] for r in report] == SHAPE_NAMES, [r[0] for r in report]
     return report
+
+
+# ---------------------------------------------------------------------------------------------------------------- two clauses of the new-node predicate, through this pass's kernels
+def _alone(app):
+    """hostname anti-affinity against a label the pod alone carries: every count is 0, the new-node predicate decides"""
+    return {"app": app, "anti_required": TC._anti(LABEL_HOSTNAME, app)}
+
+
+CLAUSE_PAIRS = [FC.FITS_NAMES + (lambda: FC.fits_pair("HFIT_NEW", node_selector=FC.SIX_CORES, **_alone("late")),),
+                FC.TAINT_NAMES + (lambda: FC.taint_pair("HFIT_TEMPLATE", _alone("tolerant"), _alone("intolerant")),)]
+CLAUSE_NAMES = FC.clause_names(CLAUSE_PAIRS)
+
+
+def run_clauses(S):
+    """tests/audit_firstfit_cases.py's Fits pair and taint pair on classes under hostname anti-affinity: [(name, True or what differs)]"""
+    return FC.run_clause_pairs(S, CLAUSE_PAIRS, compare, assert_clean, HR.problem_arrays, B, B["HFIT_NEW"] | B["HFIT_TEMPLATE"])

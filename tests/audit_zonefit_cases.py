@@ -8,13 +8,14 @@ import random
 import numpy as np
 
 import audit_cases as C
+import audit_firstfit_cases as FC
 import audit_harness as H
 from audit_harness import _claimable, flagged
 import audit_hostfit_cases as HC
 import audit_topo_cases as TC
 import audit_zonefit_ref as ZR
 from karpenter_core_amd import fake
-from karpenter_core_amd.model import DO_NOT_SCHEDULE, LABEL_HOSTNAME, LABEL_ZONE, Expr, PreferredTerm, Problem, TopologySpreadConstraint
+from karpenter_core_amd.model import DO_NOT_SCHEDULE, LABEL_HOSTNAME, LABEL_ZONE, Expr, PreferredTerm, Problem, Taint, Toleration, TopologySpreadConstraint
 
 B = ZR.BITS
 ZFIT = B["ZFIT_EXISTING"] | B["ZFIT_NEW"]
@@ -429,3 +430,38 @@ def run_shapes(S):
     report.append((SHAPE_NAMES[14], ok))
     assert [r[0] for r in report] == SHAPE_NAMES, [r[0] for r in report]
     return report
+
+
+# ---------------------------------------------------------------------------------------------------------------- two clauses of the new-node predicate, through this pass's kernels
+# The class is under one zonal spread group, so it names no node selector of its own (the group keeps its empty node filter): the fillers pin their machine to zone 1
+# and to the six-core type, and only the new-node path exists.
+PINNED = {LABEL_ZONE: Z1}
+
+
+def _zonal_taint_pair():
+    """Two pods fill a machine of `open`, pinned to zone 1; `tolerant` and `intolerant`, each under a zonal spread of its own and too large in memory to share a machine, open the next two.  Claimed: the first
+    machine has room to the milli-unit for the target and is of the second template, which taints its machines -- the target is `intolerant`, then `tolerant`."""
+    its = fake.instance_types(6)
+    provs = [fake.provisioner("open", len(its), weight=10), fake.provisioner("tainted", len(its), weight=1, taints=[Taint("dedicated", "x")])]
+    pods = [FC.six_core_pod("first", "2500m", PINNED), FC.six_core_pod("second", "2500m", PINNED),
+            TC._pod("tolerant", app="t", cpu="2400m", mem="7Gi", spread=[_zspread(1, "t")], tolerations=[Toleration(key="dedicated", operator="Exists")]),
+            TC._pod("intolerant", app="i", cpu="2300m", mem="7Gi", spread=[_zspread(1, "i")])]
+    make = lambda: FC.clause_problem(pods, provs)
+
+    def edit(r, s, prob, admit):
+        target = 2 if admit else 3
+        j0, j1 = FC.opened_in_order(r, s, prob, 0, target)
+        assert FC.new_node_of(prob, r, 1) == j0 and int(r["node_tmpl"][j0]) == 0 and int(prob["tmpl_taints"][1]) and not int(prob["tmpl_taints"][0]), (r["node_tmpl"], prob["tmpl_taints"])
+        FC.boundary_requests(r, prob, j0, FC.class_of(prob, r, target), 0)
+        r["node_tmpl"][j0] = 1
+        return target
+    return make, edit, "ZFIT_NEW"
+
+
+CLAUSE_PAIRS = [FC.FITS_NAMES + (lambda: FC.fits_pair("ZFIT_NEW", PINNED, app="z", spread=[_zspread(1, "z")]),), FC.TAINT_NAMES + (_zonal_taint_pair,)]
+CLAUSE_NAMES = FC.clause_names(CLAUSE_PAIRS)
+
+
+def run_clauses(S):
+    """tests/audit_firstfit_cases.py's Fits pair, and a taint pair, on classes under one zonal spread group: [(name, True or what differs)]"""
+    return FC.run_clause_pairs(S, CLAUSE_PAIRS, compare, assert_clean, ZR.problem_arrays, B, B["ZFIT_NEW"])

@@ -5,7 +5,7 @@ validated where a correct result is known, before any GPU run:
      decorated snapshot raises NO flag; a rule that flagged one of them would be a wrong rule, not a finding.  The kernels' own source
      (karpenter_core_amd/csrc/ks_audit_firstfit.inc) is compiled into the emulator build and runs beside the reference: the two agree bit for bit, `checked`,
      `admitting_pairs` and `skipped_pods` included.  Over the set the rule examined pods, and some (class, node) pairs admitted;
-  b) the tamper matrix and the kernels' other paths (tests/audit_firstfit_cases.py) on the emulator;
+  b) the tamper matrix, the kernels' other paths and the clauses of the new-node predicate in pairs (tests/audit_firstfit_cases.py) on the emulator;
   c) unit cases of the reference alone on a hand-made problem: one per clause of the rule and per direction.
 Runs the emulator in a subprocess: its build replaces the two libraries for the whole process (tests/simlib.py)."""
 import numpy as np
@@ -64,6 +64,7 @@ its, prov, nodes, bound, snap, pod_node = WD._topology_snapshot(24, 5, 11, spare
 both_forms("topology_whatifs", S.ParsedProblem(snap), pod_node, json.loads(sys.argv[2]))
 out["tamper"] = [[n, ok if ok is True else str(ok)] for n, ok in FC.run_tamper_matrix(S)]
 out["shapes"] = [[n, ok if ok is True else str(ok)] for n, ok in FC.run_shapes(S)]
+out["clauses"] = [[n, ok if ok is True else str(ok)] for n, ok in FC.run_clauses(S)]
 print("RESULT " + json.dumps(out))
 """
 
@@ -114,6 +115,15 @@ def test_tamper_matrix_on_the_emulator(emulated, i):
 def test_the_kernels_other_paths_on_the_emulator(emulated, i):
     name, ok = emulated["shapes"][i]
     assert name == FC.SHAPE_NAMES[i]
+    assert ok is True, (name, ok)
+
+
+@pytest.mark.parametrize("i", range(len(FC.CLAUSE_NAMES)))
+def test_the_clauses_of_the_new_node_predicate_on_the_emulator(emulated, i):
+    """tests/audit_firstfit_cases.py run_clauses: per clause a pair of claimed results that differ in that clause alone -- the reference refuses the one and admits the
+    other, and the kernels say what it says, counters included."""
+    name, ok = emulated["clauses"][i]
+    assert name == FC.CLAUSE_NAMES[i]
     assert ok is True, (name, ok)
 
 

@@ -4,7 +4,7 @@ against its literal reference (tests/audit_firstfit_ref.py):
      over the third pass's problem list (tests/audit_spread_cases.py GENUINE) with a few generic pods added, through ks_pack_rr and through ks_pack;
   b) a batch of what-ifs derived on the device against the same what-ifs flattened one by one;
   c) the tamper matrix through the claimed form, the commit numbers read from ksh_placement_rows and edited;
-  d) the shapes where the kernels take another path; the same flags every run; the refusals.
+  d) the shapes where the kernels take another path; the clauses of the new-node predicate in pairs; the same flags every run; the refusals.
 tests/test_audit_firstfit.py runs the same kernels' source on the emulator."""
 import pytest
 
@@ -73,6 +73,17 @@ def test_the_kernels_other_paths(shapes, name):
     tile); E = 65 and 257 with the only admitting node at index 0 and at E - 2 (the minimum crosses lanes, waves and workgroups); 1 100 pods on one node (the request
     sum); 12 resource names; two templates."""
     assert shapes[name] is True, shapes[name]
+
+
+@pytest.fixture(scope="module")
+def clauses():
+    return dict(FC.run_clauses(S))
+
+
+@pytest.mark.parametrize("name", FC.CLAUSE_NAMES)
+def test_the_clauses_of_the_new_node_predicate(clauses, name):
+    """Per clause a pair of claimed results that differ in that clause alone: the reference refuses the one and admits the other, and the kernels say what it says."""
+    assert clauses[name] is True, clauses[name]
 
 
 def test_flags_are_the_same_every_run():

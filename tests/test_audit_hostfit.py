@@ -71,6 +71,7 @@ both_forms("topology_whatifs", S.ParsedProblem(snap), pod_node, json.loads(sys.a
 out["tamper"] = [[n, ok if ok is True else str(ok)] for n, ok in HC.run_tamper_matrix(S)]
 out["range"] = [[n, ok if ok is True else str(ok)] for n, ok in HC.run_range_cases(S)]
 out["shapes"] = [[n, ok if ok is True else str(ok)[:600]] for n, ok in HC.run_shapes(S)]
+out["clauses"] = [[n, ok if ok is True else str(ok)[:600]] for n, ok in HC.run_clauses(S)]
 print("RESULT " + json.dumps(out))
 """
 
@@ -131,6 +132,14 @@ def test_claimed_indices_out_of_range_on_the_emulator(emulated, i):
     """Flags or skips, as the reference -- which never reads past a table -- says; the same cases go to the GPU only in tests/test_audit_hostfit_gpu.py, after these."""
     name, ok = emulated["range"][i]
     assert name == HC.RANGE_NAMES[i]
+    assert ok is True, (name, ok)
+
+
+@pytest.mark.parametrize("i", range(len(HC.CLAUSE_NAMES)))
+def test_the_clauses_of_the_new_node_predicate_on_the_emulator(emulated, i):
+    """tests/audit_hostfit_cases.py run_clauses: the Fits pair and the taint pair of tests/audit_firstfit_cases.py through this pass's kernels."""
+    name, ok = emulated["clauses"][i]
+    assert name == HC.CLAUSE_NAMES[i]
     assert ok is True, (name, ok)
 
 

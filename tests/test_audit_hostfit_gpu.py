@@ -104,6 +104,18 @@ def test_claimed_indices_out_of_range(ranges, name):
 
 
 @pytest.fixture(scope="module")
+def clauses():
+    return dict(HC.run_clauses(S))
+
+
+@pytest.mark.parametrize("name", HC.CLAUSE_NAMES)
+def test_the_clauses_of_the_new_node_predicate(clauses, name):
+    """The Fits pair and the taint pair of tests/audit_firstfit_cases.py through this pass's kernels: the reference refuses the one and admits the other, and the kernels
+    say what it says."""
+    assert clauses[name] is True, clauses[name]
+
+
+@pytest.fixture(scope="module")
 def shapes():
     return dict(HC.run_shapes(S))
 
